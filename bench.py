@@ -8,12 +8,15 @@ before the timed region (trajectories are pre-staged).  N > 1: one
 merges the integer accumulators.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c3d|c4|c5] [--frames F] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 Default (no flags): N = 1, workload c3 = BASELINE.json configs[2], the configuration the metric and north_star are quoted on
-(1M-atom box, 1k frames, all-heavy-atom RDF r_cut 12 A; 12 GB resident).  At N = 1 the same JSON line carries a `secondary`
-block with short runs of the other single-GPU configurations (c2 = configs[1], c4 = configs[3], c5 = configs[4], c3d = SURVEY 8d's dense
-variant of configs[2], c4_1250 = one rank's share of configs[3] at 8 GPUs): value,
-ms_per_step, dominant-kernel time, kernel-level and step-level HBM fraction each.
+(1M-atom box, 1k frames, all-heavy-atom RDF r_cut 12 A; 12 GB resident).  A plain run measures that workload and nothing else:
+set-up, W warm-up steps, K timed steps, the outputs of the last step (--dump-outputs), one JSON line.
+--full adds what takes runs of its own: the CPU baseline (`cpu_baseline`, any workload, N = 1) and, for the default workload, a
+`secondary` block with short runs of the other configurations (N = 1: c2 = configs[1], c4 = configs[3], c5 = configs[4], c3d = SURVEY
+8d's dense variant of configs[2], one rank's share of configs[2] / [3] / [4] at 8 GPUs, the C1 size class - value, ms_per_step,
+dominant-kernel time, kernel-level and step-level HBM fraction each; N > 1: configs[3] / [4] at strong scaling).
 --scaling strong: the workload's frames are block-sharded over the ranks (configs[3]: 10 000 frames / N) instead of every
 rank owning its own frames; either way ONE vmd_eval_reduce (RCCL, C++ behind the ABI) merges per step.
 """
@@ -61,6 +64,37 @@ WORKLOADS = {
                        "d3 = distance_min(residue(3), residue(150)); d4 = distance_max(residue(10), residue(20));"),
                desc="BASELINE configs[4]: 1M-atom box + blob, 3x RDF + 1x SDF + 4x distance co-evaluated per frame"),
 }
+
+
+DUMP_MAX_ELEMS = 1 << 21                 # per array (16 MB as float64): a larger one is written as a fixed, seeded sample of its elements
+DUMP_MAX_BYTES = 64 << 20                # all arrays of one --dump-outputs together
+
+
+def dump_outputs(ev, info, out_dir):
+    """--dump-outputs: what a caller of the timed path receives from its last step, for every property of the script - the arrays of
+    md_script_property_data_t (values, weights, the aggregate of a temporal property) as float32, the integer accumulators (counts) as
+    float64, and min / max value and range - written as <out_dir>/<property>_<array>.npy.  The inputs are seeded, so two builds of the
+    project run with the same arguments can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name in info:
+        pd = ev.property_data(name)
+        arrays = {"values": pd.values, "weights": pd.weights, "counts": pd.counts}
+        agg = pd.aggregate
+        if agg is not None:
+            arrays.update(mean=agg["mean"], var=agg["var"], ext=agg["ext"])
+        arrays["range"] = np.array([pd.min_value, pd.max_value, *pd.min_range, *pd.max_range], np.float64)
+        for kind, a in arrays.items():
+            if a is None:
+                continue
+            a = np.array(a, np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+            if a.size > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+                a = a.reshape(-1)[idx]
+            total += a.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise SystemExit(f"--dump-outputs: the outputs exceed {DUMP_MAX_BYTES >> 20} MB")
+            np.save(os.path.join(out_dir, f"{name}_{kind}.npy"), a)
 
 
 def host_cpus():
@@ -310,9 +344,10 @@ def run_c1(ctx, dry):
                     "threshold md_script_eval_create leaves the whole script with the evaluator behind the shim"}
 
 
-def run_workload(name, args, ctx, steps, warmup, frames=None, with_cpu=False, opts=(), defer_views=False):
+def run_workload(name, args, ctx, steps, warmup, frames=None, with_cpu=False, opts=(), defer_views=False, dump_dir=None):
     """One workload end to end: synthesise the (rank's) trajectory in HBM, compile the script, W untimed + K timed steps
-    bracketed by barrier + device sync, max over ranks.  Returns the result dict (rank 0: complete)."""
+    bracketed by barrier + device sync, max over ranks; dump_dir: rank 0 writes the outputs of the last step there.
+    Returns the result dict (rank 0: complete)."""
     import torch
     V, lib, script, synth, reduce_eval, dist = ctx["V"], ctx["lib"], ctx["script"], ctx["synth"], ctx["reduce_eval"], ctx["dist"]
     world, rank = ctx["world"], ctx["rank"]
@@ -458,6 +493,8 @@ def run_workload(name, args, ctx, steps, warmup, frames=None, with_cpu=False, op
     # after the merge every rank holds the counts of all ranks' frames
     hits_per_step = sum(int(ev.property_data(n).counts.sum()) for n, d in info.items() if d["kind"] == "rdf")
     voxel_hits = sum(int(ev.property_data(n).counts.sum()) for n, d in info.items() if d["kind"] == "sdf")
+    if dump_dir and rank == 0:
+        dump_outputs(ev, info, dump_dir)
     frames_per_step = F if strong else F * world          # whole job
     value = steps * frames_per_step / elapsed
     local_frames = end - beg
@@ -680,16 +717,20 @@ def dryrun_setup():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: per workload)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline and, for the default workload, the `secondary` configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (every property's arrays) as DIR/<property>_<array>.npy")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (weak) / in total (strong); default: per workload")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank owns `frames` frames of its own; strong: the workload's frames are block-sharded over the ranks")
     ap.add_argument("--variant", type=int, default=0, help="pair-kernel hit compaction: 0 = per column (default), 1 = bin in place, 2 = pair entries, 3 = 0 behind a bounding-box test of the j windows (A/B)")
     ap.add_argument("--batch", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short c2 / c4 / c5 runs of the default N = 1 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the short runs of the other configurations")
     ap.add_argument("--opt", action="append", default=[], help="library tuning knob key=value (vmd_set_option)")
     ap.add_argument("--pool-threads", type=int, default=0, help="evaluate a step the way VIAMD calls the boundary: this many threads pull ranges of --grain frames and call frame_range on ONE eval (0 = one call per step, the metric's configuration)")
     ap.add_argument("--grain", type=int, default=1, help="frames per frame_range call with --pool-threads (VIAMD's create_pool_task default: 1)")
@@ -701,6 +742,10 @@ def main():
                          "dcd / xtc / trr: frames decoded from a trajectory file on disk by the native readers "
                          "(file -> decode on host threads -> pinned staging -> PCIe); xtc is lossy (0.01 A grid)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the bare command `python bench.py --gpus N ...`: this process becomes the launcher of N ranks (one per GPU) and relays
@@ -744,10 +789,10 @@ def main():
     w = WORKLOADS[args.workload]
     steps = args.steps if args.steps is not None else w["steps"]
     warmup = args.warmup if args.warmup is not None else 2
-    out = run_workload(args.workload, args, ctx, steps, warmup, frames=args.frames, with_cpu=(world == 1 and not args.no_cpu_baseline),
-                       opts=args.opt)
-    # the other single-GPU configurations of BASELINE.json, short runs in the same line (N = 1, default invocation only)
-    if world == 1 and not args.no_secondary and args.workload == "c3" and args.traj == "device" and not args.frames:
+    out = run_workload(args.workload, args, ctx, steps, warmup, frames=args.frames, opts=args.opt, dump_dir=args.dump_outputs,
+                       with_cpu=(args.full and world == 1 and not args.no_cpu_baseline))
+    # --full: the other single-GPU configurations of BASELINE.json, short runs in the same line (N = 1, default workload only)
+    if args.full and world == 1 and not args.no_secondary and args.workload == "c3" and args.traj == "device" and not args.frames:
         sec = {}
         for nm in ("c2", "c4", "c5", "c3d"):       # c3d: SURVEY 8d's C3-dense variant (every atom counted as heavy), 200 frames
             r = run_workload(nm, args, ctx, WORKLOADS[nm].get("sec_steps", 2), 1, opts=args.opt)
@@ -796,7 +841,7 @@ def main():
         # same host cores through the oracle: what include/vmd_md_script_shim.h's work threshold (vmd_shim_set_min_work) is set from
         sec["c1"] = run_c1(ctx, dry)
         out["secondary"] = sec
-    if world > 1 and not args.no_secondary and args.workload == "c3" and args.traj == "device" and not args.frames and args.scaling == "weak":
+    if args.full and world > 1 and not args.no_secondary and args.workload == "c3" and args.traj == "device" and not args.frames and args.scaling == "weak":
         # the two configurations BASELINE.json quotes on 8 GPUs, STRONG scaling (the named trajectory block-sharded over the ranks,
         # one merge per step), short runs next to the weak-scaling c3 curve.  Every rank takes the same decisions here (a failure is
         # caught on all ranks alike or the job dies as one), so the primary line is printed in any case.

@@ -2,7 +2,7 @@
 # parity tests + all four workloads (no CPU baseline unless $2 = cpu).  usage: bash scripts/gpu_bench_all.sh <tag> [cpu]
 TAG=${1:-b}; R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R; export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -3
-EXTRA="--no-cpu-baseline"; [ "$2" = "cpu" ] && EXTRA=""
+EXTRA="--no-cpu-baseline"; [ "$2" = "cpu" ] && EXTRA="--full"
 for w in c2 c3 c4 c5; do
   timeout 900 python bench.py --workload $w $EXTRA > $OUT/bench_$w.json 2> $OUT/bench_$w.err
   python - <<PY

@@ -4,7 +4,7 @@ bash $R/scripts/gpu_pmc.sh ${T}_pmc_c3d --workload c3d > $O/pmc_c3d.log 2>&1
 python $R/scripts/pmc_traffic.py $R/gpurun_out/${T}_pmc_c3d c3d 200 $O/pmc_traffic.json 2 200 > /dev/null
 cp $R/gpurun_out/${T}_pmc_c3d/summary.txt $O/pmc_summary_c3d.txt; rm -rf $R/gpurun_out/${T}_pmc_c3d
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json")); s = d["secondary"]

@@ -41,7 +41,7 @@ with open("$O/timeline_c4_1250.txt", "w") as out:
 print(open("$O/timeline_c4_1250.txt").read()[-4500:])
 PY
 find $O/trace_c4_1250 -name "*.csv" -size +2M -delete
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))

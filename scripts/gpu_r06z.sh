@@ -19,7 +19,7 @@ for w in c3 c2 c4 c5 c3d; do
   rm -rf $R/gpurun_out/${T}_pmc_$w
 done
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 cd /tmp
 for w in c3 c2 c4 c5 c3d; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- python $R/bench.py --workload $w --no-cpu-baseline --no-secondary --steps 5 --warmup 2 > $O/prof_$w.log 2>&1
@@ -39,7 +39,7 @@ for k, v in d.get("secondary", {}).items():
 PY
 for w in c3 c4; do echo "== kernel stats $w"; head -5 $O/rocprofv3_kernel_stats_$w.csv | cut -c1-170; done
 g++ -std=c++17 -O2 tests/native/exp_threads.cpp -Iinclude viamd_amd/libviamd_amd.so -Wl,-rpath,$R/viamd_amd -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -Wl,-rpath-link,/opt/rocm/lib -lpthread -o /tmp/exp_threads && { /tmp/exp_threads 100002 1000; VMD_SDF=1 /tmp/exp_threads 100002 10000; } > $O/readahead_call_pattern.txt 2>&1; cat $O/readahead_call_pattern.txt | cut -c1-400
-VIAMD_BENCH_SHARE_GPU=1 timeout 900 python3 bench.py --gpus 2 --steps 3 --warmup 1 2> $O/bench_share2.err | grep "^{" > $O/bench_share2.json; echo "share2 rc=$?"
+VIAMD_BENCH_SHARE_GPU=1 timeout 900 python3 bench.py --gpus 2 --steps 3 --warmup 1 --full 2> $O/bench_share2.err | grep "^{" > $O/bench_share2.json; echo "share2 rc=$?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_share2.json")); print("share2: n_gpus", d["n_gpus"], "ranks", d.get("ranks"), round(d["value"]), "frames/s", d["config"]["parallelism"][:60])

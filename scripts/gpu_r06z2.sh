@@ -12,7 +12,7 @@ bash $R/scripts/gpu_pmc.sh ${T}_pmc_c5 --workload c5 --no-secondary > $O/pmc_c5.
 python $R/scripts/pmc_traffic.py $R/gpurun_out/${T}_pmc_c5 c5 1000 $O/pmc_traffic.json 2 1000 > /dev/null
 cp $R/gpurun_out/${T}_pmc_c5/summary.txt $O/pmc_summary_c5.txt 2>/dev/null; rm -rf $R/gpurun_out/${T}_pmc_c5
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5 -o c5 -- python $R/bench.py --workload c5 --no-cpu-baseline --no-secondary --steps 5 --warmup 2 > $O/prof_c5.log 2>&1
 f=$(find $O/prof_c5 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/rocprofv3_kernel_stats_c5.csv; rm -rf $O/prof_c5

@@ -16,10 +16,10 @@ grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -3
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
 echo "== bench (default = c2, with cpu baseline)"
-timeout 900 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench rc=$?"; cat $OUT/bench_c2.json
+timeout 900 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench rc=$?"; cat $OUT/bench_c2.json
 for w in c3 c4 c5; do
   echo "== bench $w"
-  timeout 900 python bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; cat $OUT/bench_$w.json
+  timeout 900 python bench.py --workload $w --full > $OUT/bench_$w.json 2> $OUT/bench_$w.err; cat $OUT/bench_$w.json
 done
 echo "== bench c2, trajectory in pinned host memory (PCIe-inclusive)"
 timeout 300 python bench.py --traj pinned --no-cpu-baseline > $OUT/bench_c2_pinned.json 2>> $OUT/bench_c2.err; cat $OUT/bench_c2_pinned.json
@@ -39,7 +39,7 @@ for ch in 128 256 1024; do
 done
 echo "== rocprofv3 --kernel-trace --stats of the default bench command"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o c2 -- python $R/bench.py --no-cpu-baseline > $OUT/prof_c2.log 2>&1; echo "rocprof rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o c2 -- python $R/bench.py --full --no-cpu-baseline > $OUT/prof_c2.log 2>&1; echo "rocprof rc=$?"
 for f in $(find $OUT/prof_c2 -name "*kernel_stats.csv"); do cat $f; done
 tail -1 $OUT/prof_c2.log
 find $OUT/prof_c2 -name "*kernel_trace.csv" -size +20M -delete

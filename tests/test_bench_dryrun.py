@@ -1,5 +1,5 @@
 """bench.py's own logic (workload table, weak / strong sharding, one vmd_eval_reduce per step, max-over-ranks timing, the JSON
-line with `roofline`, `cpu_baseline` and `secondary`) dry-run on the CPU: the SIMT-emulator build of the library, tiny workloads,
+line with `roofline`, and with --full `cpu_baseline` and `secondary`; --dump-outputs) dry-run on the CPU: the SIMT-emulator build of the library, tiny workloads,
 world_size 1 and 2 (gloo).  No GPU, no timing claims - it keeps the N > 1 path of the file the driver launches from rotting."""
 import json
 import os
@@ -35,12 +35,12 @@ def _run(tmp_path, emu, nproc, extra, launcher=False):
 
 def test_bare_command_launches_its_own_ranks(tmp_path, emu_lib):
     """VERDICT r03 #1: `python3 bench.py --gpus 2 --steps 2 --warmup 1` with WORLD_SIZE unset must produce the N = 2 line."""
-    d = _run(tmp_path, emu_lib.path, 2, ["--steps", "2", "--warmup", "1"])
+    d = _run(tmp_path, emu_lib.path, 2, ["--steps", "2", "--warmup", "1", "--full"])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["config"]["name"] == "c3"
     assert d["merge"]["rccl_ranks"] == 2 and d["merge"]["collective"] and len(d["per_rank_ms_per_step"]) == 2
     assert abs(max(d["per_rank_ms_per_step"]) - d["ms_per_step"]) < 1e-6 * max(1.0, d["ms_per_step"])
     assert d["config"]["frames_per_step"] == 12 and "DRY RUN" in d["data"]
-    # the 8-GPU configurations of BASELINE.json ride along as strong-scaling lines
+    # --full: the 8-GPU configurations of BASELINE.json ride along as strong-scaling lines
     s4, s5 = d["secondary"]["c4_strong"], d["secondary"]["c5_strong"]
     assert s4["scaling"] == "strong" and s4["frames_per_step"] == 6 and s4["frames_per_step_per_gpu"] == 3 and s4["voxel_hits_per_s"] > 0
     assert s5["pairs_per_s"] > 0 and s5["voxel_hits_per_s"] > 0 and s5["merge"]["rccl_ranks"] == 2
@@ -53,8 +53,8 @@ def test_under_the_launcher(tmp_path, emu_lib):
 
 @pytest.fixture(scope="module")
 def default_line(tmp_path_factory, emu_lib):
-    """ONE dry run of the default command, shared by the tests that read its line"""
-    return _run(tmp_path_factory.mktemp("default_line"), emu_lib.path, 1, ["--steps", "1", "--warmup", "1"])
+    """ONE dry run of the default command with --full, shared by the tests that read its line"""
+    return _run(tmp_path_factory.mktemp("default_line"), emu_lib.path, 1, ["--steps", "1", "--warmup", "1", "--full"])
 
 
 def test_default_line_has_the_contract_fields(default_line):
@@ -79,6 +79,28 @@ def test_default_line_has_the_contract_fields(default_line):
     # (the CPU column - median of three samples, spread printed, VERDICT r05 next #4c - is stubbed in a dry run; the measured line carries it)
     assert d["secondary"]["c4"]["voxel_hits_per_s"] > 0 and d["pairs_per_s"] > 0
     assert 0.0 <= d["cell_build"]["frac_of_step"] < 1.0             # the sorted copies behind the pair kernel: share of the step (event times are 0 on the emulator)
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path, emu_lib):
+    """A plain run measures its workload only (no CPU baseline, no other configurations); --steps sets the timed steps; --dump-outputs
+    writes every property's arrays of the last step as float32 / float64 .npy files, the same from run to run."""
+    import numpy as np
+    d = _run(tmp_path, emu_lib.path, 1, ["--steps", "3", "--warmup", "1"])
+    assert d["steps"] == 3 and d["config"]["name"] == "c3" and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "secondary" not in d
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"dump{i}"
+        _run(tmp_path, emu_lib.path, 1, ["--steps", "2", "--warmup", "0", "--workload", "c5", "--dump-outputs", str(out)])
+        dumps.append({p.name: np.load(p) for p in sorted(out.iterdir())})
+    a, b = dumps
+    assert {"g_values.npy", "g_weights.npy", "g_counts.npy", "v_values.npy", "v_counts.npy", "d_values.npy"} <= set(a) and set(a) == set(b)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name, x in a.items():
+        assert x.dtype in (np.float32, np.float64) and x.size > 0, name
+        assert x.tobytes() == b[name].tobytes(), name
+    assert a["g_counts.npy"].sum() > 0 and a["v_counts.npy"].sum() > 0
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
