@@ -204,6 +204,25 @@ bool vmd_ir_add_distance(vmd_script_ir_t* ir, const char* name, vmd_distance_kin
  * back to back; context c owns a[a_offsets[c] .. a_offsets[c+1]) and b[b_offsets[c] .. b_offsets[c+1]). */
 bool vmd_ir_add_distance_population(vmd_script_ir_t* ir, const char* name, vmd_distance_kind_t kind, size_t P,
                                     const int32_t* a, const int32_t* a_offsets, const int32_t* b, const int32_t* b_offsets);
+/* `name = angle(a, b, c) [in <contexts>];` and `name = dihedral(a, b, c, d) [in <contexts>];` (DESIGN S6b): temporal, one value per
+ * context and frame (dim[1] = P), degrees by default (vmd_set_option("spec_angle_radians", 1): radians).  Every argument is the S6 centre
+ * of its set, the same point distance(a, b) uses; the angle is at the middle argument, the dihedral follows the IUPAC sign convention.
+ * The populations hold every context's sets back to back as vmd_ir_add_distance_population does: context c owns
+ * a[a_offsets[c] .. a_offsets[c+1]), and likewise for b, c, d.  Empty sets, negative indices and offsets that do not start at 0 and
+ * increase are errors (vmd_last_error). */
+bool vmd_ir_add_angle(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
+                      const int32_t* c, size_t nc);
+bool vmd_ir_add_dihedral(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
+                         const int32_t* c, size_t nc, const int32_t* d, size_t nd);
+bool vmd_ir_add_angle_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
+                                 const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets);
+bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
+                                    const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets,
+                                    const int32_t* d, const int32_t* d_offsets);
+/* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order: returns how many
+ * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
+ * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
+size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
 /* md_script_ir_compile_from_source stand-in (src/main.cpp:878) for the script subset of the hot path: statements
  * `s = <selection>;`, `r = rdf(sel, sel, rmax | rmin:rmax | {rmin, rmax});`, `v = sdf(structures, sel, cutoff);`,
  * `d = distance[_min|_max|_pair](sel, sel) [in <structures>];` with selections element('X'), type/name/label('X'),
@@ -241,6 +260,13 @@ bool     vmd_ir_compile_from_source_partial(vmd_script_ir_t* ir, const char* sou
 size_t   vmd_script_report_skipped_count(const vmd_script_report_t* report);
 const vmd_script_skipped_t* vmd_script_report_skipped(const vmd_script_report_t* report);
 const char* vmd_script_report_fallback_source(const vmd_script_report_t* report);
+/* Both compilers with opt-in features: report == NULL is vmd_ir_compile_from_source (strict), otherwise
+ * vmd_ir_compile_from_source_partial.  features = 0 is exactly those two.  VMD_SCRIPT_FEATURE_ANGLES also compiles
+ * `angle(sel, sel, sel)` and `dihedral(sel, sel, sel, sel)`, plain or `in <contexts>`, with the selection and context rules of distance()
+ * (DESIGN S6b); VIAMD's default script then leaves only `{lin,plan,iso} = shape_weights(all);` to the fallback. */
+#define VMD_SCRIPT_FEATURE_ANGLES 1u
+bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
+                                       vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
 bool     vmd_ir_valid(const vmd_script_ir_t* ir);                       /* md_script_ir_valid, src/main.cpp:936 */
 uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir);                 /* md_script_ir_fingerprint, src/main.cpp:937 */

@@ -14,6 +14,7 @@
  *   vmd_hip_rdf_*     <- rdf() pair loop + md_spatial_hash query (a4, a5)
  *   vmd_hip_sdf_*     <- sdf() alignment + density-volume accumulation (a6, a7, a9)
  *   vmd_hip_distance  <- distance / distance_min / distance_max / distance_pair (a8)
+ *   vmd_hip_geometry  <- angle / dihedral (DESIGN S6b)
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -156,6 +157,13 @@ int vmd_hip_distance(void* stream, const float* xyz, size_t frame_stride, size_t
                      const float* boxes, uint32_t pbc_flags, int B, int kind, int P, int per,
                      const int32_t* a, const float* mass_a, const int32_t* aoff,
                      const int32_t* b, const float* mass_b, const int32_t* boff, float* out);
+
+/* K5b: angle(a,b,c) (nargs 3) / dihedral(a,b,c,d) (nargs 4), DESIGN S6b: out f32[B][P], one value per frame and context.  Argument k
+ * of context c is the S6 centre of sets[k][offsets[k][c] .. offsets[k][c+1]) with masses[k] parallel to sets[k] (device arrays; the
+ * three pointer arrays themselves are host arrays of nargs entries).  radians = 0: degrees (D-ANGLE-UNIT). */
+int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                     const float* boxes, uint32_t pbc_flags, int B, int nargs, int P,
+                     const int32_t* const* sets, const float* const* masses, const int32_t* const* offsets, int radians, float* out);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -17,8 +17,9 @@
  * put them elsewhere.
  *
  * Hooks (define before including; the defaults name mdlib's own functions): VMD_SHIM_BONDS(sys, vsys) hands md_system_t::bond over;
- * VMD_SHIM_UNIT(dst, str) turns the backend's printed unit ("\xC3\x85" or "") into an md_unit_t (default: md_unit_angstrom() /
- * md_unit_none()); VMD_SHIM_BITFIELD_INIT / _SET / _TEST / _CLEAR / _FREE are how the shim touches ANY md_bitfield_t - the reference
+ * VMD_SHIM_UNIT(dst, str) turns the backend's printed unit ("\xC3\x85" or "", and "\xC2\xB0" / "rad" for an opted-in angle or dihedral)
+ * into an md_unit_t (default: md_unit_angstrom() for "\xC3\x85", md_unit_none() otherwise - a host that opts in to angles maps the degree
+ * sign to its own degree unit here); VMD_SHIM_BITFIELD_INIT / _SET / _TEST / _CLEAR / _FREE are how the shim touches ANY md_bitfield_t - the reference
  * structures of a vis payload and the frame mask it hands out (defaults: md_bitfield_init / _set_bit / _test_bit / _clear / _free); md_array_resize
  * / md_array_size are mdlib's stretchy-buffer macros.  The block "what this header requires of mdlib" below lists, and checks at compile time,
  * every name and field used directly, each with the line of the reference where it is observable.
@@ -74,7 +75,7 @@
 struct md_script_vis_payload_o { const md_script_ir_t* ir; std::string name; };
 
 #ifndef VMD_SHIM_UNIT
-#define VMD_SHIM_UNIT(dst, str) do { (dst) = ((str) && (str)[0]) ? md_unit_angstrom() : md_unit_none(); } while (0)
+#define VMD_SHIM_UNIT(dst, str) do { (dst) = ((str) && !strcmp((str), "\xC3\x85")) ? md_unit_angstrom() : md_unit_none(); } while (0)
 #endif
 #ifndef VMD_SHIM_BITFIELD_INIT
 #define VMD_SHIM_BITFIELD_INIT(bf, alloc) md_bitfield_init((bf), (alloc))
@@ -663,8 +664,10 @@ inline const md_script_vis_payload_o* VMD_SHIM_PREFIX(md_script_ir_property_vis_
 /* md_script_vis_eval_payload(&vis, payload, subidx, &ctx, flags).  Served for sdf() properties - the one payload on the evaluation
  * path: MD_SCRIPT_VISUALIZE_SDF fills vis->sdf.{extent, matrices, structures} for trajectory frame 0 of ctx->traj (the reference pose
  * VIAMD draws the volume in: density_volume.cpp:190-204, 263-269; export_cube, src/main.cpp:5751-5803), MD_SCRIPT_VISUALIZE_ATOMS adds
- * the atoms of the reference structures to vis->atom_mask (src/viamd.cpp:3205-3207).  subidx >= 0 selects one structure.  Payloads of
- * other property kinds return false (their highlighting is mdlib's own). */
+ * the atoms of the reference structures to vis->atom_mask (src/viamd.cpp:3205-3207).  subidx >= 0 selects one structure.  An angle() /
+ * dihedral() property the host compiled with VMD_SCRIPT_FEATURE_ANGLES gets MD_SCRIPT_VISUALIZE_ATOMS too: the atoms of its argument
+ * sets (subidx >= 0: of one context).  Payloads of other property kinds return false (their highlighting is mdlib's own, INTEGRATION.md
+ * section 3). */
 inline bool VMD_SHIM_PREFIX(md_script_vis_eval_payload)(md_script_vis_t* vis, const md_script_vis_payload_o* payload, int subidx,
                                                         const md_script_vis_ctx_t* ctx, md_script_vis_flags_t flags) {
     if (!vis || !payload || !ctx) return false;
@@ -684,8 +687,19 @@ inline bool VMD_SHIM_PREFIX(md_script_vis_eval_payload)(md_script_vis_t* vis, co
 #endif
         }
     }
-    if (!ctx->mol || !ctx->traj) return false;
     const vmd_script_ir_t* vir = vmd_shim::find_ir(payload->ir);
+    if (vir && (flags & MD_SCRIPT_VISUALIZE_ATOMS)) {
+        /* angle / dihedral bound to the GPU (the host opted in, VMD_SCRIPT_FEATURE_ANGLES): the atoms of its argument sets, of context
+         * `subidx` when >= 0.  The arcs mdlib draws for them are not reproduced */
+        const size_t n = vmd_ir_geometry_atoms(vir, payload->name.c_str(), subidx, nullptr, 0);
+        if (n) {
+            std::vector<int32_t> atoms(n);
+            vmd_ir_geometry_atoms(vir, payload->name.c_str(), subidx, atoms.data(), n);
+            for (int32_t a : atoms) VMD_SHIM_BITFIELD_SET(&vis->atom_mask, (uint64_t)a);
+            return true;
+        }
+    }
+    if (!ctx->mol || !ctx->traj) return false;
     if (!vir || !(vmd_ir_property_flags(vir, payload->name.c_str()) & VMD_PROPERTY_FLAG_VOLUME)) return false;
     vmd_shim::Registry& r = vmd_shim::registry();
     vmd_script_eval_t* ev = nullptr;

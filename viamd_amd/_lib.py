@@ -145,7 +145,16 @@ SIGNATURES = [
     ("vmd_ir_add_sdf", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.c_size_t, c_int32_p, C.c_size_t, C.c_float]),
     ("vmd_ir_add_distance", C.c_bool, [_vp, C.c_char_p, C.c_int, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t]),
     ("vmd_ir_add_distance_population", C.c_bool, [_vp, C.c_char_p, C.c_int, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    ("vmd_ir_add_angle", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t]),
+    ("vmd_ir_add_dihedral", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t,
+                                       c_int32_p, C.c_size_t]),
+    ("vmd_ir_add_angle_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                               c_int32_p]),
+    ("vmd_ir_add_dihedral_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                                  c_int32_p, c_int32_p, c_int32_p]),
+    ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
+    ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
     ("vmd_ir_compile_from_source_partial", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.POINTER(_vp)]),
     ("vmd_script_report_skipped_count", C.c_size_t, [_vp]),
     ("vmd_script_report_skipped", C.POINTER(ScriptSkippedC), [_vp]),
@@ -309,6 +318,8 @@ SIGNATURES = [
     ("vmd_hip_set_sdf_rows", C.c_int, [C.c_int]),
     ("vmd_hip_distance", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("vmd_hip_geometry", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.c_int, _vp]),
     ("vmd_hip_add_u64", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("vmd_hip_counts_to_float", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_float]),
     ("vmd_hip_bump_u64", C.c_int, [_vp, _vp, C.c_uint64]),

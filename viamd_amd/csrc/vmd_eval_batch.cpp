@@ -699,10 +699,20 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 p->dirty = p->dirty || !spec;
             } else {
                 if (!p->d_out.ensure(c.nb * p->dim1)) return false;
-                e->prof.begin("distance", e->stream);
-                KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
-                        d.dist_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
-                        p->d_out.p));
+                if (d.nargs() > 2) {
+                    // angle / dihedral (DESIGN S6b): the same [nb][P] block, the same copy below
+                    const int32_t* sets[4] = {p->d_a.p, p->d_b.p, p->d_c.p, p->d_d.p};
+                    const float* ms[4] = {p->d_ma.p, p->d_mb.p, p->d_mc.p, p->d_md.p};
+                    const int32_t* offs[4] = {p->d_aoff.p, p->d_boff.p, p->d_coff.p, p->d_doff.p};
+                    e->prof.begin("geometry", e->stream);
+                    KRN_OK(vmd_hip_geometry(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+                            d.nargs(), (int)p->dist_P, sets, ms, offs, e->spec.angle_radians ? 1 : 0, p->d_out.p));
+                } else {
+                    e->prof.begin("distance", e->stream);
+                    KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+                            d.dist_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
+                            p->d_out.p));
+                }
                 e->prof.end(e->stream);
                 HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + toff, p->d_out.p, c.nb * p->dim1 * sizeof(float),
                         hipMemcpyDeviceToHost, e->stream));

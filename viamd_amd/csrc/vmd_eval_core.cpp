@@ -167,6 +167,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     e->spec.rdf_raw = g_opt.spec_rdf_raw.load() != 0;
     e->spec.rdf_norm = g_opt.spec_rdf_norm.load();
     e->spec.dist_geometric_com = g_opt.spec_dist_geometric_com.load() != 0;
+    e->spec.angle_radians = g_opt.spec_angle_radians.load() != 0;
     e->frame_mask.assign(num_frames, 0);
     for (auto& p : ir->props) {
         auto st = std::make_unique<PropState>();
@@ -202,6 +203,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             st->values.assign(num_frames * st->dim1, 0.0f);
             st->data.dim[0] = (int32_t)num_frames; st->data.dim[1] = (int32_t)st->dim1;
             st->data.unit_str[0] = ""; st->data.unit_str[1] = "\xC3\x85";
+            if (p.nargs() > 2) st->data.unit_str[1] = e->spec.angle_radians ? "rad" : "\xC2\xB0";     // DESIGN S6b, D-ANGLE-UNIT
             if (st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;
@@ -724,6 +726,19 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
             if (!p->d_ma.upload(tmp.data(), tmp.size(), e->stream)) return false;
             masses(d.b, tmp);
             if (!p->d_mb.upload(tmp.data(), tmp.size(), e->stream)) return false;
+            // angle / dihedral: the third and fourth argument sets (DESIGN S6b)
+            if (d.nargs() > 2) {
+                HIP_OK(hipStreamSynchronize(e->stream));       // tmp is refilled below
+                if (!p->d_c.upload(d.c.data(), d.c.size(), e->stream) || !p->d_coff.upload(d.coff.data(), d.coff.size(), e->stream)) return false;
+                masses(d.c, tmp);
+                if (!p->d_mc.upload(tmp.data(), tmp.size(), e->stream)) return false;
+            }
+            if (d.nargs() > 3) {
+                HIP_OK(hipStreamSynchronize(e->stream));
+                if (!p->d_d.upload(d.d.data(), d.d.size(), e->stream) || !p->d_doff.upload(d.doff.data(), d.doff.size(), e->stream)) return false;
+                masses(d.d, tmp);
+                if (!p->d_md.upload(tmp.data(), tmp.size(), e->stream)) return false;
+            }
         }
         HIP_OK(hipStreamSynchronize(e->stream));   // tmp goes out of scope
         p->uploaded = true;

@@ -119,6 +119,7 @@ struct Options {
     std::atomic<int> spec_sdf_include_self{0};    // D-SDF-EXCL: targets that are atoms of structure k are scattered like any other
     std::atomic<int> spec_sdf_density{0};         // D-SDF-NORM: values = counts / (frames evaluated x voxel volume) instead of raw counts
     std::atomic<int> spec_dist_geometric_com{0};  // D-DIST-COM: distance(a, b) between geometric centres, not centres of mass
+    std::atomic<int> spec_angle_radians{0};       // D-ANGLE-UNIT: angle() / dihedral() in radians, not degrees (DESIGN S6b)
     // D-WRAP: positions enter rdf() as they are, minimum image by rounding - evaluated by k_rdf_brute (all pairs: a
     std::atomic<int> spec_rdf_raw{0};
                                                   // setting for matching an mdlib that does it this way, not a fast path)
@@ -347,6 +348,9 @@ struct HostBuf {
 // ------------------------------------------------------------------------------------------------ IR
 enum PropKind { PROP_RDF = 0, PROP_SDF = 1, PROP_DIST = 2 };
 
+// temporal properties of DESIGN S6b: PROP_DIST descriptors with three or four argument sets (dist_kind past vmd_distance_kind_t)
+enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
+
 struct Property {
     std::string name;
     PropKind kind;
@@ -354,8 +358,10 @@ struct Property {
     std::vector<int32_t> a, b;      // RDF: ref/target; SDF: structures (K*m)/target; DIST: a/b
     float rmin = 0.0f, rmax = 0.0f; // RDF range; SDF: rmax = cutoff (half extent)
     size_t K = 0, m = 0;
-    int dist_kind = 0;
+    int dist_kind = 0;              // DIST: vmd_distance_kind_t, or GEOM_ANGLE / GEOM_DIHEDRAL
     std::vector<int32_t> aoff, boff;   // DIST: context offsets into a / b (population), size P + 1
+    std::vector<int32_t> c, d, coff, doff;   // angle / dihedral: the third and fourth argument sets, offsets as aoff
+    int nargs() const { return dist_kind == GEOM_DIHEDRAL ? 4 : (dist_kind == GEOM_ANGLE ? 3 : 2); }
 };
 
 struct vmd_script_ir_t {
@@ -460,6 +466,8 @@ struct PropState {
     // DIST
     DevBuf<int32_t> d_a, d_b, d_aoff, d_boff;
     DevBuf<float> d_ma, d_mb, d_out;
+    DevBuf<int32_t> d_c, d_d, d_coff, d_doff;     // angle / dihedral
+    DevBuf<float> d_mc, d_md;
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh
@@ -735,7 +743,7 @@ struct vmd_script_eval_t {
     vmd_reduce_stats_t reduce_stats = {};
     // fixed at creation
     struct Spec { bool rdf_closed = false, sdf_include_self = false, sdf_density = false, dist_geometric_com = false, rdf_raw = false;
-            int rdf_norm = 0; } spec;
+            int rdf_norm = 0; bool angle_radians = false; } spec;
     size_t atoms_checked = (size_t)-1;       // trajectory atom count the properties' indices were validated against (under mtx)
 };
 

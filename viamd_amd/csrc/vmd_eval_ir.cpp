@@ -1,5 +1,5 @@
 // viamd_amd/csrc/vmd_eval_ir.cpp - the property descriptors behind vmd_ir_*: what md_script_ir_t carries for the hot-path properties
-// (rdf / sdf / distance family; /root/reference/src/main.cpp:528, 2817-2858), their fingerprint and the work estimate a host compares
+// (rdf / sdf / distance family, angle / dihedral; /root/reference/src/main.cpp:528, 2817-2858), their fingerprint and the work estimate a host compares
 // with its threshold (include/vmd_md_script_shim.h).
 #include "vmd_eval_internal.h"
 
@@ -12,7 +12,7 @@ uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
 extern "C" vmd_script_ir_t* vmd_ir_create(void) { return new vmd_script_ir_t(); }
 
 // atom pairs one frame of this script asks for (rdf: |ref| x |target|; sdf: K x |target| + K m for the alignment; distance: |a| x |b| of
-// every context): what a host compares with its threshold before it sends a SMALL script to the GPU at all (include/vmd_md_script_shim.h,
+// every context; angle / dihedral: the atoms of every context's sets): what a host compares with its threshold before it sends a SMALL script to the GPU at all (include/vmd_md_script_shim.h,
 // vmd_shim_set_min_work; VIAMD's default dataset is ~1e2 atoms, src/main.cpp:522-528)
 extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     if (!ir) return 0;
@@ -20,6 +20,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     for (const Property& p : ir->props) {
         if (p.kind == PROP_RDF) w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
         else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
+        else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
         else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
                 * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
         else w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
@@ -107,6 +108,87 @@ extern "C" bool vmd_ir_add_distance_population(vmd_script_ir_t* ir, const char* 
     return true;
 }
 
+// angle / dihedral (DESIGN S6b): n argument sets per context, validated like the distance population
+static bool ir_add_geometry(vmd_script_ir_t* ir, const char* name, int kind, size_t P, const int32_t* const* sets, const int32_t* const* offs) {
+    static const char* const arg[4] = {"a", "b", "c", "d"};
+    const char* what = kind == GEOM_ANGLE ? "angle" : "dihedral";
+    const int n = kind == GEOM_ANGLE ? 3 : 4;
+    if (!ir_name_ok(ir, name)) return false;
+    if (P == 0) return vmd_fail("%s population is empty", what);
+    char label[48];
+    for (int k = 0; k < n; ++k) {
+        if (!offs[k]) return vmd_fail("%s set %s has no context offsets", what, arg[k]);
+        if (offs[k][0] != 0) return vmd_fail("context offsets must start at 0");
+        for (size_t c = 0; c < P; ++c)
+            if (offs[k][c + 1] <= offs[k][c]) return vmd_fail("%s context %zu has an empty set %s (offsets must increase)", what, c, arg[k]);
+        snprintf(label, sizeof(label), "%s set %s", what, arg[k]);
+        if (!idx_ok(sets[k], (size_t)offs[k][P], label)) return false;
+    }
+    Property p;
+    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    p.dist_kind = kind;
+    std::vector<int32_t>* dst[4] = {&p.a, &p.b, &p.c, &p.d};
+    std::vector<int32_t>* dof[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
+    for (int k = 0; k < n; ++k) { dst[k]->assign(sets[k], sets[k] + offs[k][P]); dof[k]->assign(offs[k], offs[k] + P + 1); }
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
+extern "C" bool vmd_ir_add_angle(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
+                                 const int32_t* c, size_t nc) {
+    if (na > 0x7fffffff || nb > 0x7fffffff || nc > 0x7fffffff) return vmd_fail("angle set too large");
+    const int32_t ao[2] = {0, (int32_t)na}, bo[2] = {0, (int32_t)nb}, co[2] = {0, (int32_t)nc};
+    const int32_t* sets[3] = {a, b, c};
+    const int32_t* offs[3] = {ao, bo, co};
+    return ir_add_geometry(ir, name, GEOM_ANGLE, 1, sets, offs);
+}
+
+extern "C" bool vmd_ir_add_dihedral(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
+                                    const int32_t* c, size_t nc, const int32_t* d, size_t nd) {
+    if (na > 0x7fffffff || nb > 0x7fffffff || nc > 0x7fffffff || nd > 0x7fffffff) return vmd_fail("dihedral set too large");
+    const int32_t ao[2] = {0, (int32_t)na}, bo[2] = {0, (int32_t)nb}, co[2] = {0, (int32_t)nc}, dof[2] = {0, (int32_t)nd};
+    const int32_t* sets[4] = {a, b, c, d};
+    const int32_t* offs[4] = {ao, bo, co, dof};
+    return ir_add_geometry(ir, name, GEOM_DIHEDRAL, 1, sets, offs);
+}
+
+extern "C" bool vmd_ir_add_angle_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
+                                            const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets) {
+    const int32_t* sets[3] = {a, b, c};
+    const int32_t* offs[3] = {a_offsets, b_offsets, c_offsets};
+    return ir_add_geometry(ir, name, GEOM_ANGLE, P, sets, offs);
+}
+
+extern "C" bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
+                                               const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets,
+                                               const int32_t* d, const int32_t* d_offsets) {
+    const int32_t* sets[4] = {a, b, c, d};
+    const int32_t* offs[4] = {a_offsets, b_offsets, c_offsets, d_offsets};
+    return ir_add_geometry(ir, name, GEOM_DIHEDRAL, P, sets, offs);
+}
+
+// the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
+// count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
+extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
+    if (!ir || !name) return 0;
+    for (const Property& p : ir->props) {
+        if (p.name != name) continue;
+        if (p.kind != PROP_DIST || p.nargs() < 3) return 0;
+        const size_t P = p.aoff.size() - 1;
+        if (context >= (int64_t)P) return 0;
+        const size_t c0 = context < 0 ? 0 : (size_t)context, c1 = context < 0 ? P : (size_t)context + 1;
+        const std::vector<int32_t>* sets[4] = {&p.a, &p.b, &p.c, &p.d};
+        const std::vector<int32_t>* offs[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
+        size_t n = 0;
+        for (size_t c = c0; c < c1; ++c)
+            for (int k = 0; k < p.nargs(); ++k)
+                for (int32_t i = (*offs[k])[c]; i < (*offs[k])[c + 1]; ++i) { if (out && n < cap) out[n] = (*sets[k])[(size_t)i]; n += 1; }
+        return n;
+    }
+    return 0;
+}
+
 extern "C" bool vmd_ir_valid(const vmd_script_ir_t* ir) { return ir != nullptr; }
 
 extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
@@ -122,6 +204,9 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         h = fnv1a(h, &p.rmin, sizeof(float)); h = fnv1a(h, &p.rmax, sizeof(float));
         h = fnv1a(h, &p.K, sizeof(p.K)); h = fnv1a(h, &p.m, sizeof(p.m)); h = fnv1a(h, &p.dist_kind, sizeof(int));
         h = fnv1a(h, p.aoff.data(), p.aoff.size() * sizeof(int32_t)); h = fnv1a(h, p.boff.data(), p.boff.size() * sizeof(int32_t));
+        // angle / dihedral only (empty otherwise: hashing no bytes leaves every earlier fingerprint as it was)
+        h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
+        h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
     }
     h = h ? h : 1;
     ir->fingerprint = h;

@@ -94,6 +94,7 @@ extern "C" int vmd_set_option(const char* key, int value) {
     else if (!strcmp(key, "spec_sdf_include_self")) o = &g_opt.spec_sdf_include_self;
     else if (!strcmp(key, "spec_sdf_density")) o = &g_opt.spec_sdf_density;
     else if (!strcmp(key, "spec_dist_geometric_com")) o = &g_opt.spec_dist_geometric_com;
+    else if (!strcmp(key, "spec_angle_radians")) o = &g_opt.spec_angle_radians;
     else if (!strcmp(key, "spec_rdf_raw")) o = &g_opt.spec_rdf_raw;
     else if (!strcmp(key, "spec_rdf_norm")) o = &g_opt.spec_rdf_norm;
     else if (!strcmp(key, "rdf_blocks_decode")) o = &g_opt.rdf_blocks_decode;

@@ -12,6 +12,7 @@
 //   rdf()                        -> k_rdf_pencil (periodic, grid) / k_rdf_brute (general)
 //   sdf() + density volume       -> k_sdf_align (fp64 Horn/Jacobi) + k_sdf_scatter
 //   distance*()                  -> k_distance_com / k_distance_minmax / k_distance_pair
+//   angle() / dihedral()         -> k_geom<3> / k_geom<4>
 //
 // Design notes (DESIGN.md has the long form):
 //  * wave64 everywhere; a wave is the unit of work in the pair kernel (private LDS histogram + private LDS
@@ -2649,6 +2650,75 @@ __global__ __launch_bounds__(256) void k_distance_pair(vmd_dist_params_t p) {
     p.out[((size_t)b * p.P + c) * p.per + k] = sqrtf(vmd_pair_d2(p, b, p.a[a0 + ia], p.b[b0 + ib]));
 }
 
+// ------------------------------------------------------------------------------------------------ K5b: angle / dihedral (DESIGN S6b)
+
+struct vmd_geom_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    // argument k of context c: set[k][off[k][c] .. off[k][c+1]), masses parallel to set[k]
+    const int32_t* set[4]; const float* mass[4]; const int32_t* off[4]; int P;
+    int radians;  // D-ANGLE-UNIT: 0 = degrees
+    float* out;   // [B][P]
+};
+
+// a x b, components in the order DESIGN S6b writes them
+__device__ __forceinline__ void vmd_cross_d(double ax, double ay, double az, double bx, double by, double bz, double& cx, double& cy,
+                                            double& cz) {
+    cx = ay * bz - az * by;
+    cy = az * bx - ax * bz;
+    cz = ax * by - ay * bx;
+}
+__device__ __forceinline__ double vmd_dot_d(double ax, double ay, double az, double bx, double by, double bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// one thread per (frame, context): the NARG argument points are the S6 centres of distance(a, b) (vmd_set_com), joined by fp32
+// minimum-image differences; the value is formed in fp64 (no contraction) and rounded once.  `+ 0.0` turns a -0 operand of atan2
+// into +0: degenerate input gives atan2(+0, +0) = 0 (D-ANGLE-DEGENERATE) and a dihedral never comes out as -180.
+template <int NARG>
+__global__ __launch_bounds__(64) void k_geom(vmd_geom_params_t p) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.B * p.P) return;
+    const int b = t / p.P, c = t - b * p.P;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    float q[NARG][3];
+#pragma unroll
+    for (int k = 0; k < NARG; ++k) {
+        const int k0 = p.off[k][c], n = p.off[k][c + 1] - k0;
+        vmd_set_com(fx, fy, fz, p.set[k] + k0, p.mass[k] + k0, n, bx, q[k]);
+    }
+    double rad;
+    if constexpr (NARG == 3) {
+        // angle(a, b, c) at the middle point: u = mi(pa - pb), v = mi(pc - pb)
+        float ux = q[0][0] - q[1][0], uy = q[0][1] - q[1][1], uz = q[0][2] - q[1][2];
+        float vx = q[2][0] - q[1][0], vy = q[2][1] - q[1][1], vz = q[2][2] - q[1][2];
+        vmd_mi3_rintf(bx, ux, uy, uz);
+        vmd_mi3_rintf(bx, vx, vy, vz);
+        double cx, cy, cz;
+        vmd_cross_d(ux, uy, uz, vx, vy, vz, cx, cy, cz);
+        const double s = sqrt(vmd_dot_d(cx, cy, cz, cx, cy, cz));
+        rad = atan2(s + 0.0, vmd_dot_d(ux, uy, uz, vx, vy, vz) + 0.0);
+    } else {
+        // dihedral(a, b, c, d): b1 = mi(pb - pa), b2 = mi(pc - pb), b3 = mi(pd - pc); IUPAC sign
+        float d[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k][0] = q[k + 1][0] - q[k][0]; d[k][1] = q[k + 1][1] - q[k][1]; d[k][2] = q[k + 1][2] - q[k][2];
+            vmd_mi3_rintf(bx, d[k][0], d[k][1], d[k][2]);
+        }
+        double n1x, n1y, n1z, n2x, n2y, n2z;
+        vmd_cross_d(d[0][0], d[0][1], d[0][2], d[1][0], d[1][1], d[1][2], n1x, n1y, n1z);
+        vmd_cross_d(d[1][0], d[1][1], d[1][2], d[2][0], d[2][1], d[2][2], n2x, n2y, n2z);
+        const double l2 = sqrt(vmd_dot_d(d[1][0], d[1][1], d[1][2], d[1][0], d[1][1], d[1][2]));
+        const double y = l2 * vmd_dot_d(d[0][0], d[0][1], d[0][2], n2x, n2y, n2z);
+        rad = atan2(y + 0.0, vmd_dot_d(n1x, n1y, n1z, n2x, n2y, n2z) + 0.0);
+    }
+    p.out[t] = p.radians ? (float)rad : (float)(rad * (180.0 / M_PI));
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -3050,6 +3120,26 @@ extern "C" int vmd_hip_distance(void* stream, const float* xyz, size_t frame_str
         break;
     default: return (int)hipErrorInvalidValue;
     }
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                const float* boxes, uint32_t pbc_flags, int B, int nargs, int P,
+                                const int32_t* const* sets, const float* const* masses, const int32_t* const* offsets, int radians,
+                                float* out) {
+    if (B <= 0 || P <= 0) return 0;
+    if ((nargs != 3 && nargs != 4) || !sets || !masses || !offsets || (long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    vmd_geom_params_t p{};
+    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
+    for (int k = 0; k < nargs; ++k) {
+        if (!sets[k] || !masses[k] || !offsets[k]) return (int)hipErrorInvalidValue;
+        p.set[k] = sets[k]; p.mass[k] = masses[k]; p.off[k] = offsets[k];
+    }
+    p.radians = radians; p.out = out;
+    const dim3 g((unsigned)(((long long)B * P + 63) / 64));
+    if (nargs == 3) hipLaunchKernelGGL((k_geom<3>), g, dim3(64), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((k_geom<4>), g, dim3(64), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

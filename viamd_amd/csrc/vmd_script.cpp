@@ -336,7 +336,8 @@ struct Report {
 // hands to the evaluator it falls back on (include/vmd_md_script_shim.h), e.g. `a1 = angle(2,1,3) in resname("ALA");` and
 // `{lin,plan,iso} = shape_weights(all);` of VIAMD's default script (src/main.cpp:528).  A later statement that uses an identifier of a
 // skipped one is skipped with it ("unknown identifier").
-void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report) {
+// features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral() (opt-in; 0 = the subset above, byte for byte)
+void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
     std::map<std::string, Sel> env;
@@ -383,7 +384,8 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
             p.take("=");
             const Token k = p.peek();
             const bool is_func = k.kind == T_ID && (k.text == "rdf" || k.text == "sdf" || k.text == "distance" || k.text == "distance_min" ||
-                                                    k.text == "distance_max" || k.text == "distance_pair");
+                                                    k.text == "distance_max" || k.text == "distance_pair" ||
+                                                    ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")));
             if (is_func) {
                 is_property = true;
                 const std::string v = k.text;
@@ -429,34 +431,57 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                         if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
                         ++j;
                     }
+                    // distance*: two argument sets; angle: three; dihedral: four (DESIGN S6b)
+                    const int nargs = v == "angle" ? 3 : (v == "dihedral" ? 4 : 2);
                     if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
                         Parser q(toks, topo, env);
                         q.i = j + 1;
                         const Sel ctx = q.sel_or();
                         if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", name.c_str());
-                        std::vector<int32_t> a_all, b_all, a_off{0}, b_off{0};
+                        std::vector<std::vector<int32_t>> all(nargs), off(nargs, std::vector<int32_t>{0});
                         for (auto& st : ctx.structs) {
                             Parser r(toks, topo, env, &st);
                             r.i = start;
-                            const Sel a = r.sel_or(); r.take(","); const Sel b = r.sel_or(); r.take(")");
-                            const auto ai = a.indices(), bi = b.indices();
-                            if (ai.empty() || bi.empty()) fail("%s: empty selection inside a context", name.c_str());
-                            a_all.insert(a_all.end(), ai.begin(), ai.end()); a_off.push_back((int32_t)a_all.size());
-                            b_all.insert(b_all.end(), bi.begin(), bi.end()); b_off.push_back((int32_t)b_all.size());
+                            std::vector<std::vector<int32_t>> idx;
+                            for (int k = 0; k < nargs; ++k) { if (k) r.take(","); idx.push_back(r.sel_or().indices()); }
+                            r.take(")");
+                            for (auto& ix : idx) if (ix.empty()) fail("%s: empty selection inside a context", name.c_str());
+                            for (int k = 0; k < nargs; ++k) { all[k].insert(all[k].end(), idx[k].begin(), idx[k].end()); off[k].push_back((int32_t)all[k].size()); }
                         }
                         p.i = q.i;
                         const size_t P = ctx.structs.size();
-                        const vmd_distance_kind_t kind = dist_kind(v);
-                        commit = [=]() {
-                            if (!vmd_ir_add_distance_population(ir, name.c_str(), kind, P, a_all.data(), a_off.data(), b_all.data(), b_off.data())) throw ScriptError(vmd_last_error());
-                        };
+                        if (nargs == 2) {
+                            const vmd_distance_kind_t kind = dist_kind(v);
+                            const std::vector<int32_t> a_all = all[0], b_all = all[1], a_off = off[0], b_off = off[1];
+                            commit = [=]() {
+                                if (!vmd_ir_add_distance_population(ir, name.c_str(), kind, P, a_all.data(), a_off.data(), b_all.data(), b_off.data())) throw ScriptError(vmd_last_error());
+                            };
+                        } else {
+                            commit = [=]() {
+                                const bool ok = nargs == 3
+                                    ? vmd_ir_add_angle_population(ir, name.c_str(), P, all[0].data(), off[0].data(), all[1].data(), off[1].data(), all[2].data(), off[2].data())
+                                    : vmd_ir_add_dihedral_population(ir, name.c_str(), P, all[0].data(), off[0].data(), all[1].data(), off[1].data(), all[2].data(),
+                                                                     off[2].data(), all[3].data(), off[3].data());
+                                if (!ok) throw ScriptError(vmd_last_error());
+                            };
+                        }
                     } else {
-                        const Sel a = p.sel_or(); p.take(",");
-                        const Sel b = p.sel_or();
+                        std::vector<std::vector<int32_t>> idx;
+                        for (int k = 0; k < nargs; ++k) { if (k) p.take(","); idx.push_back(p.sel_or().indices()); }
                         p.take(")");
-                        const auto ai = a.indices(), bi = b.indices();
-                        const vmd_distance_kind_t kind = dist_kind(v);
-                        commit = [=]() { if (!vmd_ir_add_distance(ir, name.c_str(), kind, ai.data(), ai.size(), bi.data(), bi.size())) throw ScriptError(vmd_last_error()); };
+                        if (nargs == 2) {
+                            const auto ai = idx[0], bi = idx[1];
+                            const vmd_distance_kind_t kind = dist_kind(v);
+                            commit = [=]() { if (!vmd_ir_add_distance(ir, name.c_str(), kind, ai.data(), ai.size(), bi.data(), bi.size())) throw ScriptError(vmd_last_error()); };
+                        } else {
+                            commit = [=]() {
+                                const bool ok = nargs == 3
+                                    ? vmd_ir_add_angle(ir, name.c_str(), idx[0].data(), idx[0].size(), idx[1].data(), idx[1].size(), idx[2].data(), idx[2].size())
+                                    : vmd_ir_add_dihedral(ir, name.c_str(), idx[0].data(), idx[0].size(), idx[1].data(), idx[1].size(), idx[2].data(),
+                                                          idx[2].size(), idx[3].data(), idx[3].size());
+                                if (!ok) throw ScriptError(vmd_last_error());
+                            };
+                        }
                     }
                 }
             } else {
@@ -506,10 +531,10 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
 
 }  // namespace
 
-extern "C" bool vmd_ir_compile_from_source(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology) {
+static bool compile_strict(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features) {
     if (!ir || !source || !topology) { vmd_set_last_error("vmd_ir_compile_from_source: NULL argument"); return false; }
     try {
-        compile(ir, source, topology, nullptr);
+        compile(ir, source, topology, nullptr, features);
     } catch (const std::exception& e) {
         vmd_set_last_error(e.what());
         return false;
@@ -517,14 +542,19 @@ extern "C" bool vmd_ir_compile_from_source(vmd_script_ir_t* ir, const char* sour
     return true;
 }
 
+extern "C" bool vmd_ir_compile_from_source(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology) {
+    return compile_strict(ir, source, topology, 0);
+}
+
 struct vmd_script_report_t { Report r; };
 
-extern "C" bool vmd_ir_compile_from_source_partial(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, vmd_script_report_t** report) {
+static bool compile_partial(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, vmd_script_report_t** report,
+                            uint32_t features) {
     if (report) *report = nullptr;
     if (!ir || !source || !topology || !report) { vmd_set_last_error("vmd_ir_compile_from_source_partial: NULL argument"); return false; }
     std::unique_ptr<vmd_script_report_t> rep(new vmd_script_report_t());
     try {
-        compile(ir, source, topology, &rep->r);
+        compile(ir, source, topology, &rep->r, features);
     } catch (const std::exception& e) {          // the topology itself is malformed: nothing a fallback could take over
         vmd_set_last_error(e.what());
         return false;
@@ -532,6 +562,15 @@ extern "C" bool vmd_ir_compile_from_source_partial(vmd_script_ir_t* ir, const ch
     for (const Skipped& k : rep->r.skipped) rep->r.view.push_back(vmd_script_skipped_t{k.names.c_str(), k.beg, k.end, k.reason.c_str()});
     *report = rep.release();
     return true;
+}
+
+extern "C" bool vmd_ir_compile_from_source_partial(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, vmd_script_report_t** report) {
+    return compile_partial(ir, source, topology, report, 0);
+}
+
+extern "C" bool vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
+                                              vmd_script_report_t** report) {
+    return report ? compile_partial(ir, source, topology, report, features) : compile_strict(ir, source, topology, features);
 }
 extern "C" size_t vmd_script_report_skipped_count(const vmd_script_report_t* r) { return r ? r->r.view.size() : 0; }
 extern "C" const vmd_script_skipped_t* vmd_script_report_skipped(const vmd_script_report_t* r) { return r && !r->r.view.empty() ? r->r.view.data() : nullptr; }

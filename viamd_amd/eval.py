@@ -108,6 +108,43 @@ class ScriptIR:
                                                             a.ctypes.data_as(L.c_int32_p), ao.ctypes.data_as(L.c_int32_p),
                                                             b.ctypes.data_as(L.c_int32_p), bo.ctypes.data_as(L.c_int32_p)))
 
+    def add_angle(self, name, a, b, c):
+        """`name = angle(a, b, c);` (DESIGN S6b): the angle at the centre of b, degrees unless spec_angle_radians is set."""
+        sets = [_idx(x) for x in (a, b, c)]
+        self._check(self.lib.vmd_ir_add_angle(self.h, name.encode(), *[v for x, xp in sets for v in (xp, x.size)]))
+
+    def add_dihedral(self, name, a, b, c, d):
+        """`name = dihedral(a, b, c, d);` (DESIGN S6b): IUPAC sign, (-180, 180]."""
+        sets = [_idx(x) for x in (a, b, c, d)]
+        self._check(self.lib.vmd_ir_add_dihedral(self.h, name.encode(), *[v for x, xp in sets for v in (xp, x.size)]))
+
+    def _add_geometry_population(self, fn, name, arg_sets):
+        P = len(arg_sets[0])
+        assert P > 0 and all(len(s) == P for s in arg_sets)
+        args, keep = [], []
+        for sets in arg_sets:
+            flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in sets]).astype(np.int32)
+            off = np.concatenate([[0], np.cumsum([len(x) for x in sets])]).astype(np.int32)
+            keep += [flat, off]
+            args += [flat.ctypes.data_as(L.c_int32_p), off.ctypes.data_as(L.c_int32_p)]
+        self._check(fn(self.h, name.encode(), P, *args))
+
+    def add_angle_population(self, name, a_sets, b_sets, c_sets):
+        """`name = angle(a, b, c) in <contexts>`: one (a, b, c) triple of index sets per context -> dim[1] = number of contexts."""
+        self._add_geometry_population(self.lib.vmd_ir_add_angle_population, name, (a_sets, b_sets, c_sets))
+
+    def add_dihedral_population(self, name, a_sets, b_sets, c_sets, d_sets):
+        """`name = dihedral(a, b, c, d) in <contexts>`: one quadruple of index sets per context."""
+        self._add_geometry_population(self.lib.vmd_ir_add_dihedral_population, name, (a_sets, b_sets, c_sets, d_sets))
+
+    def geometry_atoms(self, name, context=-1):
+        """the atoms of an angle / dihedral property (one context, or all when context < 0), in argument order"""
+        n = int(self.lib.vmd_ir_geometry_atoms(self.h, name.encode(), int(context), None, 0))
+        out = np.zeros(n, np.int32)
+        if n:
+            self.lib.vmd_ir_geometry_atoms(self.h, name.encode(), int(context), out.ctypes.data_as(L.c_int32_p), n)
+        return out
+
     def valid(self):
         return bool(self.lib.vmd_ir_valid(self.h))
 

@@ -264,14 +264,19 @@ class _Parser:
 
 _FUNCS = {"rdf", "sdf", "distance", "distance_min", "distance_max", "distance_pair"}
 _DIST_KIND = {"distance": L.DIST_COM, "distance_min": L.DIST_MIN, "distance_max": L.DIST_MAX, "distance_pair": L.DIST_PAIR}
+_GEOM_NARGS = {"angle": 3, "dihedral": 4}       # opt-in (angles=True)
+FEATURE_ANGLES = 1                              # VMD_SCRIPT_FEATURE_ANGLES
 
 
-def compile_script(text, topo, lib=None, partial=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
     returns (ScriptIR, info, report) with report = dict(skipped=[dict(names, beg, end, reason)], fallback_source=text with the compiled
-    property statements blanked out).  VIAMD's default script (src/main.cpp:528) then yields d1, r, v and reports a1 and lin,plan,iso."""
+    property statements blanked out).  VIAMD's default script (src/main.cpp:528) then yields d1, r, v and reports a1 and lin,plan,iso.
+
+    angles=True (VMD_SCRIPT_FEATURE_ANGLES, opt-in): angle(sel, sel, sel) and dihedral(sel, sel, sel, sel), plain or `in <contexts>`,
+    are compiled too (DESIGN S6b); the default script then yields d1, a1, r, v and reports lin,plan,iso only."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -308,7 +313,7 @@ def compile_script(text, topo, lib=None, partial=False):
             name = p.take(kind="id")
             names = name
             p.take("=")
-            commit, is_property = _statement(p, name, topo, env, ir, info)
+            commit, is_property = _statement(p, name, topo, env, ir, info, angles)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -354,11 +359,11 @@ def compile_script(text, topo, lib=None, partial=False):
     return ir, info
 
 
-def _statement(p, name, topo, env, ir, info):
+def _statement(p, name, topo, env, ir, info, angles=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
-    if not (k == "id" and v in _FUNCS):
+    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS))):
         sel = p.sel_or()
         return (lambda: env.__setitem__(name, sel)), False
     p.i += 1
@@ -403,25 +408,50 @@ def _statement(p, name, topo, env, ir, info):
             raise ScriptError(f"{name}: missing ')'")
         depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
         j += 1
+    nargs = _GEOM_NARGS.get(v, 2)       # distance*: two argument sets; angle: three; dihedral: four (DESIGN S6b)
     if j < len(p.t) and p.t[j] == ("id", "in"):
         q = _Parser(p.t, topo, env)
         q.i = j + 1
         ctx = q.sel_or()
         if ctx.structures is None or not ctx.structures:
             raise ScriptError(f"{name}: `in` needs an array of structures (residue(...), resname(...))")
-        a_sets, b_sets = [], []
+        sets = [[] for _ in range(nargs)]
         for st in ctx.structures:
             r = _Parser(p.t, topo, env, ctx=np.asarray(st))
             r.i = start
-            a = r.sel_or(); r.take(","); b = r.sel_or(); r.take(")")
-            if a.indices().size == 0 or b.indices().size == 0:
+            idx = []
+            for n in range(nargs):
+                if n:
+                    r.take(",")
+                idx.append(r.sel_or().indices())
+            r.take(")")
+            if any(x.size == 0 for x in idx):
                 raise ScriptError(f"{name}: empty selection inside a context")
-            a_sets.append(a.indices()); b_sets.append(b.indices())
+            for n in range(nargs):
+                sets[n].append(idx[n])
         p.i = q.i
+        if nargs > 2:
+            def commit():
+                (ir.add_angle_population if nargs == 3 else ir.add_dihedral_population)(name, *sets)
+                info[name] = dict(kind=v, sets=sets)
+            return commit, True
+        a_sets, b_sets = sets
 
         def commit():
             ir.add_distance_population(name, a_sets, b_sets, _DIST_KIND[v])
             info[name] = dict(kind=v, a_sets=a_sets, b_sets=b_sets)
+        return commit, True
+    if nargs > 2:
+        idx = []
+        for n in range(nargs):
+            if n:
+                p.take(",")
+            idx.append(p.sel_or().indices())
+        p.take(")")
+
+        def commit():
+            (ir.add_angle if nargs == 3 else ir.add_dihedral)(name, *idx)
+            info[name] = dict(kind=v, sets=idx)
         return commit, True
     a = p.sel_or(); p.take(",")
     b = p.sel_or()
@@ -433,9 +463,10 @@ def _statement(p, name, topo, env, ir, info):
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
-    Returns a ScriptIR; raises ScriptError with the library's message."""
+    Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
+    VMD_SCRIPT_FEATURE_ANGLES."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
@@ -448,11 +479,15 @@ def compile_script_native(text, topo, lib=None, partial=False):
     sq = None if topo.residue_seq_id is None else np.ascontiguousarray(topo.residue_seq_id, np.int32)
     tc = L.TopologyC(n, el, nm, rn, ri.ctypes.data_as(L.c_int32_p), sq.ctypes.data_as(L.c_int32_p) if sq is not None else None)
     if not partial:
-        if not ir.lib.vmd_ir_compile_from_source(ir.h, text.encode(), C.byref(tc)):
+        ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), FEATURE_ANGLES, None) if angles
+              else ir.lib.vmd_ir_compile_from_source(ir.h, text.encode(), C.byref(tc)))
+        if not ok:
             raise ScriptError(ir.lib.last_error())
         return ir
     rep = C.c_void_p()
-    if not ir.lib.vmd_ir_compile_from_source_partial(ir.h, text.encode(), C.byref(tc), C.byref(rep)):
+    ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), FEATURE_ANGLES, C.byref(rep)) if angles
+          else ir.lib.vmd_ir_compile_from_source_partial(ir.h, text.encode(), C.byref(tc), C.byref(rep)))
+    if not ok:
         raise ScriptError(ir.lib.last_error())
     try:
         n = ir.lib.vmd_script_report_skipped_count(rep)
