@@ -219,7 +219,17 @@ bool vmd_ir_add_angle_population(vmd_script_ir_t* ir, const char* name, size_t P
 bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
                                     const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets,
                                     const int32_t* d, const int32_t* d_offsets);
-/* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order: returns how many
+/* `{n0, n1, n2} = shape_weights(sel) [in <contexts>];`: Westin's linear, planar and isotropic measures of the set's
+ * covariance matrix (weights: masses, 1 under spec_dist_geometric_com), each >= 0, summing to 1 (0, 0, 0 for a degenerate set).  One
+ * statement defines three temporal properties, names[0..2], one value per context and frame each (dim[1] = P, no unit); the device
+ * computes them together, once per batch.  The population form holds every context's set back to back: context c owns
+ * idx[offsets[c] .. offsets[c+1]).  Empty sets, negative indices, offsets that do not start at 0 and increase, and names that are
+ * already defined or equal to each other are errors (vmd_last_error). */
+bool vmd_ir_add_shape_weights(vmd_script_ir_t* ir, const char* const names[3], const int32_t* idx, size_t n);
+bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx,
+                                         const int32_t* offsets);
+/* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
+ * shape_weights property: returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
@@ -245,7 +255,8 @@ typedef struct vmd_topology_t {
 bool     vmd_ir_compile_from_source(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
- * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements.  The report lists, per skipped statement, its
+ * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of
+ * vmd_ir_compile_from_source_ex below).  The report lists, per skipped statement, its
  * left-hand names ("a1", "lin,plan,iso"), its byte range in `source` (without the ';') and the reason; a statement that uses an identifier
  * of a skipped one is skipped with it.  vmd_script_report_fallback_source is `source` with the COMPILED property statements blanked out
  * (offsets unchanged, selections kept): the text the evaluator behind include/vmd_md_script_shim.h's fallback hooks compiles, so that no
@@ -263,8 +274,12 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
 /* Both compilers with opt-in features: report == NULL is vmd_ir_compile_from_source (strict), otherwise
  * vmd_ir_compile_from_source_partial.  features = 0 is exactly those two.  VMD_SCRIPT_FEATURE_ANGLES also compiles
  * `angle(sel, sel, sel)` and `dihedral(sel, sel, sel, sel)`, plain or `in <contexts>`, with the selection and context rules of distance()
- * (DESIGN S6b); VIAMD's default script then leaves only `{lin,plan,iso} = shape_weights(all);` to the fallback. */
+ * (DESIGN S6b); VIAMD's default script then leaves only `{lin,plan,iso} = shape_weights(all);` to the fallback.
+ * VMD_SCRIPT_FEATURE_SHAPE also compiles `{n0, n1, n2} = shape_weights(sel) [in <contexts>];` (any other tuple assignment
+ * stays outside the subset).  With both, the default script compiles whole - d1, a1, r, v, lin, plan, iso - and the fallback source
+ * keeps no property statement. */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
+#define VMD_SCRIPT_FEATURE_SHAPE 2u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -273,7 +288,8 @@ uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir);                 /* md_sc
 size_t   vmd_ir_property_count(const vmd_script_ir_t* ir);              /* md_script_ir_property_count, src/main.cpp:992,1277 */
 const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir);    /* md_script_ir_property_names, src/main.cpp:1278 */
 vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name); /* src/main.cpp:1285 */
-/* atom pairs ONE frame of the script asks for (rdf |ref| x |target|, sdf K x (|target| + m), distance |a| x |b| per context): the size a host
+/* atom pairs ONE frame of the script asks for (rdf |ref| x |target|, sdf K x (|target| + m), distance |a| x |b| per context, angle /
+ * dihedral / shape_weights: the atoms of every context's sets): the size a host
  * compares with a threshold before it sends a small script to the GPU (vmd_shim_set_min_work; VIAMD's default dataset, src/main.cpp:522-528) */
 uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir);
 

@@ -15,6 +15,7 @@
  *   vmd_hip_sdf_*     <- sdf() alignment + density-volume accumulation (a6, a7, a9)
  *   vmd_hip_distance  <- distance / distance_min / distance_max / distance_pair (a8)
  *   vmd_hip_geometry  <- angle / dihedral (DESIGN S6b)
+ *   vmd_hip_shape     <- shape_weights
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -164,6 +165,16 @@ int vmd_hip_distance(void* stream, const float* xyz, size_t frame_stride, size_t
 int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                      const float* boxes, uint32_t pbc_flags, int B, int nargs, int P,
                      const int32_t* const* sets, const float* const* masses, const int32_t* const* offsets, int radians, float* out);
+
+/* K5c: {lin, plan, iso} = shape_weights(sel), DESIGN 1.4: three f32[B][P] blocks, one value per frame and context.  Context c is
+ * set[offsets[c] .. offsets[c+1]) with mass parallel to set (device arrays); max_set is the size of the largest context's set.  Sets of
+ * more than 64 atoms are summed in chunks through `partial`, a device workspace of vmd_hip_shape_partial_doubles(B, P, max_set)
+ * doubles (0 and partial == NULL when max_set <= 64: one wave per set, no workspace). */
+size_t vmd_hip_shape_partial_doubles(int B, int P, int max_set);
+int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                  const float* boxes, uint32_t pbc_flags, int B, int P,
+                  const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                  double* partial, float* lin, float* plan, float* iso);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

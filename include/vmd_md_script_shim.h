@@ -37,7 +37,9 @@
  * -Dmd_script_eval_create=mdlib_md_script_eval_create ... (INTEGRATION.md section 2 lists the ten defines), or define
  * VMD_SHIM_FALLBACK(name) yourself (dlsym(RTLD_NEXT, #name) wrappers, a test double).  Per call: create / free / clear_data / interrupt
  * go to both evaluators; frame_range runs the GPU part, then the fallback on the same range; property_data answers bound names from the
- * GPU eval and every other name from the fallback; frame_mask is the AND of the two masks (a frame counts once both have it);
+ * GPU eval and every other name from the fallback; frame_mask is the AND of the two masks (a frame counts once both have it; a
+ * reduced fallback IR without any property - VMD_SHIM_IR_PROPERTY_COUNT, default md_script_ir_property_count - is not driven over
+ * frames at all, and the mask is then the GPU evaluator's alone);
  * ir_fingerprint is the fallback's - what src/main.cpp:987 compares with md_script_ir_fingerprint(ir) - perturbed while the GPU
  * binding of the ir is not the one the eval was created with (VIAMD then re-creates the evals).  The fallback evaluates the IR it is
  * given: the whole script (the bound properties are then computed twice, their CPU copies ignored), or - vmd_shim_bind_fallback_ir - an
@@ -335,6 +337,11 @@ inline void vmd_shim_bind_trajectory(const md_trajectory_i* md_traj, vmd_traject
     if (native) r.native_traj[md_traj] = native; else r.native_traj.erase(md_traj);
 }
 
+/* how many properties an IR of mdlib's holds (src/main.cpp:992, 1277): asked once per eval, of the reduced fallback IR only */
+#ifndef VMD_SHIM_IR_PROPERTY_COUNT
+#define VMD_SHIM_IR_PROPERTY_COUNT(ir) md_script_ir_property_count(ir)
+#endif
+
 /* ---- md_script_eval_t ------------------------------------------------------------------------------------------------------ */
 struct md_script_eval_t {
     vmd_script_eval_t* eval = nullptr;           /* the GPU evaluator of the bound properties; NULL for a script without any */
@@ -343,6 +350,7 @@ struct md_script_eval_t {
     const md_script_ir_t* md_ir = nullptr;
     vmd_shim_fallback_eval_t* fb = nullptr;      /* mdlib's evaluator of everything else; NULL without fallback hooks */
     const md_script_ir_t* fb_ir = nullptr;       /* the IR `fb` was created from (md_ir, or the reduced one of vmd_shim_bind_fallback_ir) */
+    bool fb_idle = false;                        /* the reduced IR holds no property (the GPU took every statement): `fb` is never driven over frames */
     size_t num_frames = 0;
     /* md_script_property_data_t records handed to VIAMD: fetched once and cached by the GUI (src/main.cpp:1286,1303), so their
      * addresses are stable for the eval's lifetime; the arrays they point at are the owning evaluator's (equally stable), the scalar
@@ -425,6 +433,9 @@ inline md_script_eval_t* VMD_SHIM_PREFIX(md_script_eval_create)(size_t num_frame
     /* mdlib's evaluator of the same script (or of the reduced one): every property the GPU does not evaluate lives there */
     e->fb_ir = too_small ? ir : vmd_shim::fallback_ir_of(ir);
     e->fb = VMD_SHIM_FALLBACK(md_script_eval_create)(num_frames, e->fb_ir, alloc);
+    /* every property statement compiled for the GPU (VIAMD's default script with VMD_SCRIPT_FEATURE_ANGLES | VMD_SCRIPT_FEATURE_SHAPE): the
+     * reduced IR has selections only, so mdlib's evaluator stays for the calls that are not per frame and loads no frame */
+    e->fb_idle = e->fb && vir && e->fb_ir != ir && VMD_SHIM_IR_PROPERTY_COUNT(e->fb_ir) == 0;
 #else
     e->vir = vir;                                /* nobody to leave a small script with: the threshold does not apply */
 #endif
@@ -570,7 +581,7 @@ inline bool VMD_SHIM_PREFIX(md_script_eval_frame_range)(md_script_eval_t* e, con
         e->advance();
     }
 #if VMD_SHIM_HAVE_FALLBACK
-    if (e->fb && ok) {
+    if (e->fb && ok && !(e->fb_idle && e->eval)) {
         ok = VMD_SHIM_FALLBACK(md_script_eval_frame_range)(e->fb, e->fb_ir, sys, traj, frame_beg, frame_end);
         /* the AND of the masks has grown by this range only now: the records' fingerprints move once more, or a GUI that built a
          * histogram between the two parts would keep it (found by the reference's own update_display_properties, tests/native/ref_callsites.cpp) */
@@ -616,7 +627,7 @@ inline const md_bitfield_t* VMD_SHIM_PREFIX(md_script_eval_frame_mask)(const md_
     std::lock_guard<std::mutex> l(e->mtx);
     vmd_eval_frame_mask_bits(e->eval, e->mask_words.data(), e->mask_words.size());
 #if VMD_SHIM_HAVE_FALLBACK
-    if (e->fb) {
+    if (e->fb && !e->fb_idle) {                  /* (an idle fallback has evaluated no frame: the mask is the GPU evaluator's alone) */
         const md_bitfield_t* fm = VMD_SHIM_FALLBACK(md_script_eval_frame_mask)(e->fb);
         for (size_t w = 0; w < e->mask_words.size(); ++w) {
             uint64_t word = e->mask_words[w];
@@ -666,7 +677,7 @@ inline const md_script_vis_payload_o* VMD_SHIM_PREFIX(md_script_ir_property_vis_
  * VIAMD draws the volume in: density_volume.cpp:190-204, 263-269; export_cube, src/main.cpp:5751-5803), MD_SCRIPT_VISUALIZE_ATOMS adds
  * the atoms of the reference structures to vis->atom_mask (src/viamd.cpp:3205-3207).  subidx >= 0 selects one structure.  An angle() /
  * dihedral() property the host compiled with VMD_SCRIPT_FEATURE_ANGLES gets MD_SCRIPT_VISUALIZE_ATOMS too: the atoms of its argument
- * sets (subidx >= 0: of one context).  Payloads of other property kinds return false (their highlighting is mdlib's own, INTEGRATION.md
+ * sets (subidx >= 0: of one context); so does each name of a shape_weights() statement (VMD_SCRIPT_FEATURE_SHAPE): its selection.  Payloads of other property kinds return false (their highlighting is mdlib's own, INTEGRATION.md
  * section 3). */
 inline bool VMD_SHIM_PREFIX(md_script_vis_eval_payload)(md_script_vis_t* vis, const md_script_vis_payload_o* payload, int subidx,
                                                         const md_script_vis_ctx_t* ctx, md_script_vis_flags_t flags) {
@@ -689,7 +700,7 @@ inline bool VMD_SHIM_PREFIX(md_script_vis_eval_payload)(md_script_vis_t* vis, co
     }
     const vmd_script_ir_t* vir = vmd_shim::find_ir(payload->ir);
     if (vir && (flags & MD_SCRIPT_VISUALIZE_ATOMS)) {
-        /* angle / dihedral bound to the GPU (the host opted in, VMD_SCRIPT_FEATURE_ANGLES): the atoms of its argument sets, of context
+        /* angle / dihedral / shape_weights bound to the GPU (the host opted in, VMD_SCRIPT_FEATURE_*): the atoms of its argument sets, of context
          * `subidx` when >= 0.  The arcs mdlib draws for them are not reproduced */
         const size_t n = vmd_ir_geometry_atoms(vir, payload->name.c_str(), subidx, nullptr, 0);
         if (n) {

@@ -1,0 +1,517 @@
+"""shape_weights() on the emulator build and in the host-only entry points: known answers, bit parity with the pinned
+restatement and the absolute tolerance against the plain one (tests/shape_ref.py), the reduction-order rule (call patterns), one
+computation per statement, ABI validation, the opt-in script front-end (C++ and Python twin), VIAMD's call pattern (interrupt /
+clear_data, multi-rank merges), export, and VIAMD's default script through the shim with both opt-ins."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import viamd_amd as V
+from viamd_amd import _lib as L
+from viamd_amd import script, synth
+
+import shape_ref as S
+import test_geometry as TG
+from test_geometry import bits_equal, blob_system, evaluate, rows
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHIM_SHAPE_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_shape.cpp")
+SHIM_SHAPE_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_shape")
+NAMES = ("lin", "plan", "iso")
+VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
+
+
+def weights(ev, names=NAMES):
+    """float32 [3, F, P]"""
+    return np.stack([rows(ev, n) for n in names])
+
+
+def check_tolerance(got, ref, what):
+    """|got - ref| <= 2^-23, absolute, every value (both sides carry fp64 errors far below fp32 resolution, then each rounds
+    once to fp32 - at most half an ulp of a value in [0, 1], 2^-24, on either side).  Never a ulp count: the small weights of a rod or a
+    plane differ by millions of ulps while agreeing to 1e-16."""
+    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    off = int((got.view(np.int32) != ref.view(np.int32)).sum())
+    worst = float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max())
+    print(f"{what}: {got.size} values, {off} not bit-identical, worst absolute difference {worst:.3g}")
+    assert np.isfinite(got).all(), what
+    assert worst <= S.TOL, f"{what}: {worst:.3g} from the reference"
+
+
+# ---- known answers -----------------------------------------------------------------------------------------------------------------
+
+def one_frame(lib, pts, box=50.0, mass=None):
+    xyz = np.asarray(pts, np.float32).T.copy()[None]
+    ir = V.ScriptIR(lib)
+    ir.add_shape_weights(NAMES, list(range(xyz.shape[2])))
+    return tuple(float(v) for v in weights(evaluate(lib, ir, xyz, box, mass=mass))[:, 0, 0])
+
+
+def known_answers(lib):
+    assert one_frame(lib, [(0, 0, 0), (1, 0, 0), (2, 0, 0), (5, 0, 0)]) == (1.0, 0.0, 0.0)                       # atoms on a line
+    assert one_frame(lib, [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0)]) == (0.0, 1.0, 0.0)                       # corners of a square
+    assert one_frame(lib, [(x, y, z) for x in (0, 1) for y in (0, 1) for z in (0, 1)]) == (0.0, 0.0, 1.0)       # ... of a cube
+    assert one_frame(lib, [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]) == (0.0, 0.0, 1.0)   # octahedron
+    assert one_frame(lib, [(3, 4, 5)]) == (0.0, 0.0, 0.0)                                                       # one atom: 0, 0, 0, never NaN
+    assert one_frame(lib, [(3, 4, 5)] * 5) == (0.0, 0.0, 0.0)                                                   # coincident atoms
+    # a set straddling the periodic faces of a cube of 20 equals its unwrapped copy and the copy shifted into the middle of the cell
+    straddling = [(19, 1, 10), (1, 2, 10), (0.5, 19, 9), (2, 3, 11)]
+    unwrapped = [(-1, 1, 10), (1, 2, 10), (0.5, -1, 9), (2, 3, 11)]
+    middle = [(x + 10, y + 10, z) for x, y, z in unwrapped]
+    a, b, c = (one_frame(lib, p, box=20.0) for p in (straddling, unwrapped, middle))
+    assert a == b == c and abs(sum(a) - 1.0) < 3e-7 and min(a) > 0.0
+    assert one_frame(lib, straddling, box=None) != a                                                             # no cell: the raw coordinates
+    # unequal masses pull the measures; spec_dist_geometric_com ignores them
+    ell = [(0, 0, 0), (4, 0, 0), (0, 1, 0), (0, 0, 0.5)]
+    heavy = np.array([1, 1, 1, 12], np.float32)
+    plain, weighted = one_frame(lib, ell), one_frame(lib, ell, mass=heavy)
+    assert plain != weighted
+    old = lib.vmd_set_option(b"spec_dist_geometric_com", 1)
+    try:
+        assert one_frame(lib, ell, mass=heavy) == plain
+    finally:
+        lib.vmd_set_option(b"spec_dist_geometric_com", old)
+    xyz = np.asarray(ell, np.float32).T.copy()[None]
+    assert bits_equal(np.array(weighted, np.float32), S.values(xyz, 50.0, [0, 1, 2, 3], heavy)[:, 0, 0])
+    ir = V.ScriptIR(lib)
+    ir.add_shape_weights(("a", "b", "c"), [0, 1, 2])
+    assert [ir.property_flags(n) for n in "abc"] == [L.FLAG_TEMPORAL] * 3
+    ev = evaluate(lib, ir, xyz, 50.0)
+    pd = ev.property_data("b")
+    assert pd.unit_str == ("", "") and tuple(pd.dim[:2]) == (1, 1)
+
+
+def test_known_answers_on_the_emulator(emu_lib):
+    known_answers(emu_lib)
+
+
+# ---- parity with the references --------------------------------------------------------------------------------------------------------
+
+CELLS = [((30.0, 30.0, 30.0), (0.0, 0.0, 0.0)), ((24.0, 22.0, 20.0), (5.0, -3.0, 4.0))]
+SIZES = [1, 3, 64, 65, S.CHUNK - 1, S.CHUNK, S.CHUNK + 1, 2 * S.CHUNK + 808]
+
+
+def random_system(seed, n_atoms, F=2):
+    rng = np.random.default_rng(seed)
+    # an anisotropic cloud that spills over the periodic faces
+    coords = (rng.uniform(-6, 36, (F, 3, n_atoms)) * np.array([1.0, 0.5, 0.2])[None, :, None]).astype(np.float32)
+    return rng, coords, rng.uniform(1, 16, n_atoms).astype(np.float32)
+
+
+@pytest.mark.parametrize("box,tilt", CELLS)
+def test_emulator_matches_the_pinned_reference_bit_for_bit(emu_lib, box, tilt):
+    rng, coords, mass = random_system(1, 9100)
+    for n in SIZES:
+        idx = rng.choice(9100, n, replace=False).astype(np.int32)
+        ir = V.ScriptIR(emu_lib)
+        ir.add_shape_weights(NAMES, idx)
+        got = weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))
+        assert bits_equal(got, S.values(coords, box + tilt, idx, mass)), n
+        check_tolerance(got, S.values(coords, box + tilt, idx, mass, pinned=False), f"emulator, {n} atoms, tilt {tilt}")
+    # populations: unequal sets, the largest beyond one chunk (blocks per chunk) / of at most 64 atoms (one wave per set)
+    for sizes in ([1, 3, 64, 65, 200, S.CHUNK + 5, 700], [1, 2, 3, 10, 64, 33]):
+        sets = [rng.choice(9100, n, replace=False).astype(np.int32) for n in sizes]
+        ir = V.ScriptIR(emu_lib)
+        ir.add_shape_weights_population(NAMES, sets)
+        got = weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))
+        assert got.shape == (3, 2, len(sizes))
+        assert bits_equal(got, S.values(coords, box + tilt, sets, mass)), sizes
+        check_tolerance(got, S.values(coords, box + tilt, sets, mass, pinned=False), f"emulator, population {sizes}, tilt {tilt}")
+    # a set gives the same bits alone, in a population of small sets and in a population with a large one
+    small = rng.choice(9100, 40, replace=False).astype(np.int32)
+    big = rng.choice(9100, 5000, replace=False).astype(np.int32)
+    res = []
+    for sets, pos in (([small], 0), ([small, small[:7]], 0), ([big, small], 1)):
+        ir = V.ScriptIR(emu_lib)
+        ir.add_shape_weights_population(NAMES, sets)
+        res.append(weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))[:, :, pos])
+    assert bits_equal(res[0], res[1]) and bits_equal(res[0], res[2])
+
+
+@pytest.mark.parametrize("geometric", [0, 1])
+def test_script_populations_on_the_emulator(emu_lib, oracle, geometric):
+    coords, topo = blob_system(oracle)
+    old = emu_lib.vmd_set_option(b"spec_dist_geometric_com", geometric)
+    try:
+        src = ('{l,p,i} = shape_weights(all);\n{la,pa,ia} = shape_weights(resname("ALA"));\n'
+               '{lr,pr,ir} = shape_weights(all) in resname("ALA");\n{lw,pw,iw} = shape_weights(element(\'O\')) in residue(15:60);')
+        ir, info = script.compile_script(src, topo, lib=emu_lib, shape=True)
+        ev = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
+        for names in (("l", "p", "i"), ("la", "pa", "ia"), ("lr", "pr", "ir"), ("lw", "pw", "iw")):
+            sets = info[names[0]]["sets"]
+            assert [info[n]["component"] for n in names] == [0, 1, 2] and info[names[2]]["sets"] is sets
+            got = weights(ev, names)
+            assert got.shape[2] == len(sets)
+            assert bits_equal(got, S.values(coords, 30.0, sets, topo.mass, geometric=geometric)), names
+            check_tolerance(got, S.values(coords, 30.0, sets, topo.mass, geometric=geometric, pinned=False), f"{names} geometric={geometric}")
+        assert len(info["l"]["sets"]) == 1 and info["l"]["sets"][0].size == 1200
+        assert len(info["la"]["sets"]) == 1 and info["la"]["sets"][0].size == 200
+        assert [s.size for s in info["lr"]["sets"]] == [10] * 20                # inside a context `all` is the context's atoms
+        assert len(info["lw"]["sets"]) == 46 and all(s.size == 1 for s in info["lw"]["sets"])      # one oxygen per residue: 0, 0, 0
+        assert not weights(ev, ("lw", "pw", "iw")).any()
+    finally:
+        emu_lib.vmd_set_option(b"spec_dist_geometric_com", old)
+
+
+# ---- the reduction-order rule: call patterns ----------------------------------------------------------------------------------------
+
+CALL_SCRIPT = '{l,p,i} = shape_weights(all); {lr,pr,ir} = shape_weights(all) in resname("ALA"); {lb,pb,ib} = shape_weights(resname("ALA"));'
+CALL_NAMES = ("l", "p", "i", "lr", "pr", "ir", "lb", "pb", "ib")
+RAGGED = [(0, 7), (7, 8), (8, 31), (31, 60)]
+
+
+def call_patterns(lib, run):
+    """run(ranges=None, pooled=None) -> eval; every pattern must give the bits of the single call"""
+    one = run()
+    variants = {"16 pool threads, grain 1": dict(pooled=(16, 1)), "ragged ranges": dict(ranges=RAGGED)}
+    got = {k: run(**kw) for k, kw in variants.items()}
+    for bf in (3, 16):
+        old = lib.vmd_set_option(b"batch_frames", bf)
+        try:
+            got[f"batch_frames {bf}"] = run()
+        finally:
+            lib.vmd_set_option(b"batch_frames", old)
+    for what, ev in got.items():
+        for name in CALL_NAMES:
+            assert bits_equal(rows(ev, name), rows(one, name)), (what, name)
+    return one
+
+
+def test_call_patterns_are_bit_identical(emu_lib, oracle):
+    coords, topo = blob_system(oracle, n_atoms=5200, n_blob=200, F=60)       # `all`: two chunks
+    ir = script.compile_script(CALL_SCRIPT, topo, lib=emu_lib, shape=True)[0]
+    one = call_patterns(emu_lib, lambda **kw: evaluate(emu_lib, ir, coords, 30.0, topo.mass, **kw))
+    agg = one.property_data("pr").aggregate
+    r = rows(one, "pr")
+    np.testing.assert_allclose(agg["mean"], r.mean(axis=1), rtol=1e-5, atol=1e-6)       # population aggregates: arithmetic, as for distances
+    np.testing.assert_array_equal(agg["ext"][:, 0], r.min(axis=1))
+
+
+# ---- one computation per statement ----------------------------------------------------------------------------------------------------
+
+def launch_counts(lib, make_eval, read):
+    """launches booked under "shape" and "distance" while the eval runs and `read` names are fetched"""
+    lib.vmd_profile_reset()
+    lib.vmd_profile_enable(True)
+    try:
+        ev = make_eval()
+        for n in read:
+            ev.property_data(n)
+    finally:
+        lib.vmd_profile_enable(False)
+    out = []
+    for key in (b"shape", b"distance"):
+        n = C.c_uint64(0)
+        lib.vmd_profile_ms(key, C.byref(n))
+        out.append(int(n.value))
+    return out
+
+
+def one_computation_per_statement(lib, coords, topo, box):
+    ir = script.compile_script('d = distance(1, 2); {l,p,i} = shape_weights(all);', topo, lib=lib, shape=True)[0]
+    F = coords.shape[0]
+    old = lib.vmd_set_option(b"batch_frames", 5)
+    try:
+        one = launch_counts(lib, lambda: evaluate(lib, ir, coords, box, topo.mass), ["i"])
+        all3 = launch_counts(lib, lambda: evaluate(lib, ir, coords, box, topo.mass), ["l", "p", "i"])
+    finally:
+        lib.vmd_set_option(b"batch_frames", old)
+    batches = (F + 4) // 5
+    assert one == all3 == [batches, batches], (one, all3)        # per statement and batch - as often as the one distance statement
+
+
+def test_one_computation_per_statement(emu_lib, oracle):
+    coords, topo = blob_system(oracle, F=18)
+    one_computation_per_statement(emu_lib, coords, topo, 30.0)
+
+
+# ---- ABI -----------------------------------------------------------------------------------------------------------------------------
+
+def test_ir_validation_errors(host_lib):
+    lib = host_lib
+    ir = V.ScriptIR(lib)
+    with pytest.raises(V.VmdError, match="empty"):
+        ir.add_shape_weights(NAMES, [])
+    with pytest.raises(V.VmdError, match="negative"):
+        ir.add_shape_weights(NAMES, [0, -1])
+    with pytest.raises(V.VmdError, match="empty"):
+        ir.add_shape_weights_population(NAMES, [[0], []])                          # offsets that do not increase
+    with pytest.raises(V.VmdError, match="already defined"):
+        ir.add_shape_weights(("a", "b", "a"), [0, 1])                              # a name twice in one statement
+    with pytest.raises(V.VmdError, match="name is empty"):
+        ir.add_shape_weights(("a", "", "c"), [0, 1])
+    a = np.array([0, 1], np.int32)
+    p = lambda x: x.ctypes.data_as(L.c_int32_p)
+    names = (C.c_char_p * 3)(b"x", b"y", b"z")
+    assert not lib.vmd_ir_add_shape_weights_population(ir.h, names, 2, p(a), p(np.array([1, 2, 3], np.int32)))
+    assert "start at 0" in lib.last_error()
+    assert not lib.vmd_ir_add_shape_weights_population(ir.h, names, 0, p(a), p(np.array([0, 1, 2], np.int32)))
+    assert "empty" in lib.last_error()
+    assert not lib.vmd_ir_add_shape_weights(ir.h, None, p(a), 2)
+    assert "three property names" in lib.last_error()
+    assert ir.property_count() == 0                                                # a refused statement leaves none of its names behind
+    ir.add_distance("lin", [0], [1])
+    with pytest.raises(V.VmdError, match="already defined"):
+        ir.add_shape_weights(NAMES, [0, 1])                                        # clashes with an earlier property
+    assert ir.property_names() == ["lin"]
+    ir.add_shape_weights(("l2", "p2", "i2"), [0, 1])
+    assert ir.property_names() == ["lin", "l2", "p2", "i2"]
+    with pytest.raises(V.VmdError, match="already defined"):
+        ir.add_distance("p2", [0], [1])
+    ir2 = V.ScriptIR(lib)
+    ir2.add_shape_weights(NAMES, [0, 99])
+    if lib.vmd_device_count() > 0:
+        with pytest.raises(V.VmdError, match="references atom 99"):
+            evaluate(lib, ir2, np.zeros((1, 3, 10), np.float32), 10.0)
+
+
+# fingerprint of the IR built by _old_ir on the parent commit (before shape_weights existed): an IR without shape properties keeps it
+PARENT_FINGERPRINT = 0x4E212B8F7C856C8C
+
+
+def _old_ir(lib):
+    ir = V.ScriptIR(lib)
+    ir.add_rdf("r", [0, 1, 2], [3, 4], (0.5, 9.0))
+    ir.add_distance("d", [0, 1], [2])
+    ir.add_distance_population("dp", [[0], [1, 2]], [[3], [4]], L.DIST_MIN)
+    ir.add_angle_population("a", [[0], [1, 2]], [[3], [4]], [[5, 6, 7], [8]])
+    ir.add_dihedral("t", [0], [1], [2], [3, 4])
+    return ir
+
+
+def test_fingerprint_work_and_atoms(host_lib):
+    assert _old_ir(host_lib).fingerprint() == PARENT_FINGERPRINT
+
+    def fp(build):
+        ir = V.ScriptIR(host_lib)
+        build(ir)
+        return ir.fingerprint(), int(host_lib.vmd_ir_work_per_frame(ir.h))
+    f0, w0 = fp(lambda ir: ir.add_shape_weights(NAMES, [0, 1, 2, 3]))
+    f_names, _ = fp(lambda ir: ir.add_shape_weights(("lin", "plan", "isx"), [0, 1, 2, 3]))
+    f_order, _ = fp(lambda ir: ir.add_shape_weights(("plan", "lin", "iso"), [0, 1, 2, 3]))
+    f_set, _ = fp(lambda ir: ir.add_shape_weights(NAMES, [0, 1, 2, 4]))
+    f_pop, w_pop = fp(lambda ir: ir.add_shape_weights_population(NAMES, [[0, 1], [2, 3]]))
+    f_pop2, w_pop2 = fp(lambda ir: ir.add_shape_weights_population(NAMES, [[0, 1, 2], [3], [4, 5, 6, 7]]))
+    f_dist, _ = fp(lambda ir: [ir.add_distance(n, [0, 1, 2, 3], [0]) for n in NAMES])
+    assert len({f0, f_names, f_order, f_set, f_pop, f_pop2, f_dist}) == 7
+    assert (w0, w_pop, w_pop2) == (4, 4, 8)                  # the atoms of every context's set, once per statement
+    ir = _old_ir(host_lib)
+    w_old = int(host_lib.vmd_ir_work_per_frame(ir.h))
+    ir.add_shape_weights_population(NAMES, [[0, 1, 2], [3], [4, 5, 6, 7]])
+    assert ir.fingerprint() != PARENT_FINGERPRINT and int(host_lib.vmd_ir_work_per_frame(ir.h)) == w_old + 8
+    for n in NAMES:
+        assert list(ir.geometry_atoms(n)) == [0, 1, 2, 3, 4, 5, 6, 7]
+        assert list(ir.geometry_atoms(n, 2)) == [4, 5, 6, 7] and list(ir.geometry_atoms(n, 1)) == [3]
+        assert ir.geometry_atoms(n, 3).size == 0
+    assert ir.geometry_atoms("d").size == 0
+
+
+# ---- front-end -----------------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def topo():
+    return synth.water_box_topology(200 + 933 * 3, n_blob=200)
+
+
+def test_default_script_without_the_shape_opt_in_is_unchanged(host_lib, topo):
+    """what tests/test_geometry.py::test_default_script_with_the_opt_in expects today, from every entry point that can say `shape off`"""
+    text = VIAMD_DEFAULT_SCRIPT
+    ir_a, rep_a = script.compile_script_native(text, topo, lib=host_lib, partial=True, angles=True)
+    ir_b, rep_b = script.compile_script_native(text, topo, lib=host_lib, partial=True, angles=True, shape=False)
+    ir_py, _, rep_py = script.compile_script(text, topo, lib=host_lib, partial=True, angles=True, shape=False)
+    assert ir_a.property_names() == ir_b.property_names() == ir_py.property_names() == ["d1", "a1", "r", "v"]
+    assert ir_a.fingerprint() == ir_b.fingerprint() == ir_py.fingerprint()
+    assert rep_a == rep_b == rep_py
+    assert [k["names"] for k in rep_a["skipped"]] == ["lin,plan,iso"]
+    assert rep_a["skipped"][0]["reason"] == "unsupported function 'shape_weights' (outside the rdf / sdf / distance path)"
+    fb = rep_a["fallback_source"]
+    assert len(fb) == len(text) and "angle" not in fb and "{lin,plan,iso} = shape_weights(all);" in fb
+    # neither opt-in: d1, r, v and both statements reported, as ever
+    ir_0, rep_0 = script.compile_script_native(text, topo, lib=host_lib, partial=True)
+    assert ir_0.property_names() == ["d1", "r", "v"] and [k["names"] for k in rep_0["skipped"]] == ["a1", "lin,plan,iso"]
+    with pytest.raises(script.ScriptError, match="unsupported function 'shape_weights'"):
+        script.compile_script_native("{a,b,c} = shape_weights(all);", topo, lib=host_lib, angles=True)
+    with pytest.raises(script.ScriptError, match="unsupported function 'shape_weights'"):
+        script.compile_script("{a,b,c} = shape_weights(all);", topo, lib=host_lib, angles=True)
+
+
+def test_default_script_with_both_opt_ins(host_lib, topo):
+    text = VIAMD_DEFAULT_SCRIPT
+    ir_c, rep_c = script.compile_script_native(text, topo, lib=host_lib, partial=True, angles=True, shape=True)
+    ir_py, info, rep_py = script.compile_script(text, topo, lib=host_lib, partial=True, angles=True, shape=True)
+    assert ir_c.property_names() == ir_py.property_names() == ["d1", "a1", "r", "v", "lin", "plan", "iso"]
+    assert ir_c.fingerprint() == ir_py.fingerprint()
+    assert [ir_c.property_flags(n) for n in NAMES] == [L.FLAG_TEMPORAL] * 3
+    assert rep_c == rep_py and rep_c["skipped"] == []
+    fb = rep_c["fallback_source"]
+    assert len(fb) == len(text) and fb.strip() == 's1 = resname("ALA")[2:8];'            # every property statement blanked
+    assert fb.count("\n") == text.count("\n")
+    assert info["lin"]["sets"][0].size == topo.num_atoms and list(ir_c.geometry_atoms("iso")) == list(range(topo.num_atoms))
+    # the strict form takes the whole script now
+    strict_c = script.compile_script_native(text, topo, lib=host_lib, angles=True, shape=True)
+    strict_py = script.compile_script(text, topo, lib=host_lib, angles=True, shape=True)[0]
+    assert strict_c.fingerprint() == strict_py.fingerprint() == ir_c.fingerprint()
+    # shape alone: the angle statement is the one left
+    ir_s, rep_s = script.compile_script_native(text, topo, lib=host_lib, partial=True, shape=True)
+    ir_sp, _, rep_sp = script.compile_script(text, topo, lib=host_lib, partial=True, shape=True)
+    assert ir_s.property_names() == ir_sp.property_names() == ["d1", "r", "v", "lin", "plan", "iso"]
+    assert rep_s == rep_sp and [k["names"] for k in rep_s["skipped"]] == ["a1"] and ir_s.fingerprint() == ir_sp.fingerprint()
+    # a skipped statement that uses one of the three names keeps the shape statement in the fallback's text
+    ir_k, rep_k = script.compile_script_native(text + "\nx = plan * 2;", topo, lib=host_lib, partial=True, angles=True, shape=True)
+    ir_kp, _, rep_kp = script.compile_script(text + "\nx = plan * 2;", topo, lib=host_lib, partial=True, angles=True, shape=True)
+    assert rep_k == rep_kp and [k["names"] for k in rep_k["skipped"]] == ["x"]
+    assert "{lin,plan,iso} = shape_weights(all);" in rep_k["fallback_source"] and "angle" not in rep_k["fallback_source"]
+    assert ir_k.property_names() == ir_kp.property_names() == ["d1", "a1", "r", "v", "lin", "plan", "iso"]
+
+
+BAD_STATEMENTS = [
+    ("{a,b} = shape_weights(all);", "a,b", "a,b: shape_weights defines three properties"),
+    ("{a,b,c,d} = shape_weights(all);", "a,b,c,d", "a,b,c,d: shape_weights defines three properties"),
+    ("a = shape_weights(all);", "a", "a: shape_weights defines three properties"),
+    ("{a,b,c} = shape_weights(all, water);", "a,b,c", "a,b,c: shape_weights takes one selection"),
+    ('{a,b,c} = shape_weights(resname("XYZ"));', "a,b,c", "a,b,c: empty selection"),
+    ('{a,b,c} = shape_weights(element(\'N\')) in resname("HOH");', "a,b,c", "a,b,c: empty selection inside a context"),
+    ("{a,b,c} = shape_weights(all) in element('O');", "a,b,c", "a,b,c: `in` needs an array of structures"),
+    ("{a,b,a} = shape_weights(all);", "a,b,a", "already defined"),
+    ("{a,b,c} = distance(1, 2);", "a,b,c", "unsupported function 'distance'"),            # any other tuple assignment: as today
+]
+
+
+@pytest.mark.parametrize("stmt,names,reason", BAD_STATEMENTS)
+def test_arity_and_argument_errors(host_lib, topo, stmt, names, reason):
+    text = "d = distance(1, 2);\n" + stmt + "\ne = distance(3, 4);"
+    for compiler in (script.compile_script_native, script.compile_script):
+        with pytest.raises((script.ScriptError, V.VmdError)) as err:        # (the twin passes a descriptor the library refuses on as VmdError)
+            compiler(text, topo, lib=host_lib, shape=True)
+        assert reason in str(err.value)
+    ir_c, rep_c = script.compile_script_native(text, topo, lib=host_lib, partial=True, shape=True)
+    ir_py, _, rep_py = script.compile_script(text, topo, lib=host_lib, partial=True, shape=True)
+    assert ir_c.property_names() == ir_py.property_names() == ["d", "e"] and ir_c.fingerprint() == ir_py.fingerprint()
+    assert rep_c == rep_py and len(rep_c["skipped"]) == 1
+    k = rep_c["skipped"][0]
+    assert k["names"] == names and reason in k["reason"] and text[k["beg"]:k["end"]] == stmt[:-1]
+    assert stmt in rep_c["fallback_source"] and "distance(3, 4)" not in rep_c["fallback_source"]
+
+
+def test_forms_the_twins_agree_on(host_lib, topo):
+    t = script.Topology(topo.elements, topo.resnames, topo.residue_index, mass=topo.mass, residue_seq_id=topo.residue_index + 101)
+    for form, P in (('{a,b,c} = shape_weights(protein);', 1), ('{a,b,c} = shape_weights(all) in residue(4);', 1),
+                    ('{a,b,c} = shape_weights(all) in resid(104:110);', 7), ('{a,b,c} = shape_weights(element(\'H\')) in resname("HOH");', 933),
+                    ('s = resname("ALA")[2:8]; {a,b,c} = shape_weights(s); {e,f,g} = shape_weights(all) in s;', None)):
+        ir_c = script.compile_script_native(form, t, lib=host_lib, shape=True)
+        ir_py, info = script.compile_script(form, t, lib=host_lib, shape=True)
+        assert ir_c.property_names() == ir_py.property_names() and ir_c.fingerprint() == ir_py.fingerprint(), form
+        if P is not None:
+            assert len(info["a"]["sets"]) == P
+        else:
+            assert len(info["a"]["sets"]) == 1 and info["a"]["sets"][0].size == 70 and [s.size for s in info["e"]["sets"]] == [10] * 7
+
+
+# ---- VIAMD's call pattern ----------------------------------------------------------------------------------------------------------------
+
+def test_interrupt_and_clear(emu_lib, oracle):
+    coords, topo = blob_system(oracle, F=9)
+    ir = script.compile_script(CALL_SCRIPT, topo, lib=emu_lib, shape=True)[0]
+    one = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
+    cell = V.make_unitcell(30.0)
+    ev = V.ScriptEval(coords.shape[0], ir)
+    sysm, traj = V.MolSystem(coords.shape[2], mass=topo.mass, unitcell=cell), V.HostTrajectory(coords, cell)
+    ev.interrupt()
+    ev.frame_range(sysm, traj, 0, coords.shape[0])
+    ev.clear_data()
+    assert not ev.frame_mask().any() and not rows(ev, "l").any()
+    assert ev.frame_range(sysm, traj, 0, coords.shape[0])
+    for name in CALL_NAMES:
+        assert bits_equal(rows(ev, name), rows(one, name))
+
+
+MERGE_SCRIPT = '{l,p,i} = shape_weights(all); {lr,pr,ir} = shape_weights(all) in resname("ALA"); d = distance(10, 30);'
+
+
+def _merge_worker(rank, world, port, tmpdir):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch.distributed as dist
+    import conftest
+    from viamd_amd.dist import reduce_eval, shard_frames
+    from oracle import oracle as O
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    lib = V.VmdLib(conftest.EMU_LIB)
+    coords, topo = blob_system(O, F=7)
+    ir = script.compile_script(MERGE_SCRIPT, topo, lib=lib, shape=True)[0]
+    F = coords.shape[0]
+    ev = V.ScriptEval(F, ir)
+    beg, end = shard_frames(F, rank, world)
+    cell = V.make_unitcell(30.0)
+    assert ev.frame_range(V.MolSystem(coords.shape[2], mass=topo.mass, unitcell=cell), V.HostTrajectory(coords, cell), beg, end)
+    reduce_eval(ev)
+    assert ev.frame_mask().all()
+    out = {n: ev.property_data(n).values for n in ("l", "p", "i", "lr", "pr", "ir", "d")}
+    np.savez(os.path.join(tmpdir, f"rank{rank}.npz"), mean=ev.property_data("pr").aggregate["mean"], **out)
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_multi_rank_merge(emu_lib, oracle, tmp_path, world):
+    import torch.multiprocessing as mp
+    port = 35500 + (os.getpid() % 2000) + 7 * world
+    mp.spawn(_merge_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
+    coords, topo = blob_system(oracle, F=7)
+    ir = script.compile_script(MERGE_SCRIPT, topo, lib=emu_lib, shape=True)[0]
+    one = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
+    for r in range(world):
+        z = np.load(tmp_path / f"rank{r}.npz")
+        for n in ("l", "p", "i", "lr", "pr", "ir", "d"):
+            assert bits_equal(z[n].reshape(7, -1), rows(one, n)), n
+        assert bits_equal(z["mean"], one.property_data("pr").aggregate["mean"])
+
+
+def test_export_table(emu_lib, oracle, tmp_path):
+    coords, topo = blob_system(oracle, F=5)
+    ir = script.compile_script('{lin,plan,iso} = shape_weights(resname("ALA"));', topo, lib=emu_lib, shape=True)[0]
+    ev = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
+    for name in NAMES:
+        y = rows(ev, name)[:, 0]
+        for ext in ("xvg", "csv"):
+            path = tmp_path / f"{name}.{ext}"
+            ev.export_table(path, name, ext)
+            text = open(path, encoding="utf-8").read()
+            assert name in text, text[:400]
+            nums = [ln.replace(",", " ").split() for ln in text.splitlines() if ln.strip() and ln.strip()[0] in "0123456789"]
+            assert len(nums) == 5
+            np.testing.assert_allclose(np.array([float(ln[1]) for ln in nums], np.float32), y, rtol=1e-5, atol=2e-6)   # six decimals in the file
+
+
+# ---- VIAMD's default script through the shim, both opt-ins ---------------------------------------------------------------------------
+
+def build_shim_shape():
+    """tests/native/shim_default_script_shape.cpp linked against the product library"""
+    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
+    from viamd_amd import build
+    lib = build.build()
+    deps = [SHIM_SHAPE_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
+            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
+    if os.path.exists(SHIM_SHAPE_EXE) and os.path.getmtime(SHIM_SHAPE_EXE) >= max(os.path.getmtime(d) for d in deps):
+        return SHIM_SHAPE_EXE
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_SHAPE_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
+                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
+                           "-lpthread", "-o", SHIM_SHAPE_EXE])
+    return SHIM_SHAPE_EXE
+
+
+def test_shim_default_script_with_both_opt_ins_on_the_emulator(emu_lib, tmp_path):
+    import conftest
+    emu = conftest.build_emu()
+    exe = str(tmp_path / "shim_shape_emu")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_SHAPE_SRC, "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
+    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.startswith("OK frames=8 properties=7 a1=gpu lin=gpu"), out.stdout

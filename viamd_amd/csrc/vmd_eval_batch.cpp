@@ -699,7 +699,24 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 p->dirty = p->dirty || !spec;
             } else {
                 if (!p->d_out.ensure(c.nb * p->dim1)) return false;
-                if (d.nargs() > 2) {
+                if (d.is_shape()) {
+                    // shape_weights: the statement's three descriptors stand in a row; the first one computes all three
+                    // [nb][P] blocks, each of them copies its own below
+                    if (d.shape_comp == 0) {
+                        const size_t pi = (size_t)(&p - e->props.data());
+                        if (pi + 2 >= e->props.size() || !e->props[pi + 1]->prop.is_shape() || !e->props[pi + 2]->prop.is_shape())
+                            return vmd_fail("shape_weights property '%s' has lost its companions", d.name.c_str());
+                        PropState* p1 = e->props[pi + 1].get();
+                        PropState* p2 = e->props[pi + 2].get();
+                        if (!p1->d_out.ensure(c.nb * p->dim1) || !p2->d_out.ensure(c.nb * p->dim1)) return false;
+                        if (!p->d_shape_partial.ensure(vmd_hip_shape_partial_doubles((int)c.nb, (int)p->dist_P, p->shape_max_set))) return false;
+                        e->prof.begin("shape", e->stream);
+                        KRN_OK(vmd_hip_shape(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+                                (int)p->dist_P, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->shape_max_set, p->d_shape_partial.p, p->d_out.p,
+                                p1->d_out.p, p2->d_out.p));
+                        e->prof.end(e->stream);
+                    }
+                } else if (d.nargs() > 2) {
                     // angle / dihedral (DESIGN S6b): the same [nb][P] block, the same copy below
                     const int32_t* sets[4] = {p->d_a.p, p->d_b.p, p->d_c.p, p->d_d.p};
                     const float* ms[4] = {p->d_ma.p, p->d_mb.p, p->d_mc.p, p->d_md.p};
@@ -713,7 +730,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                             d.dist_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
                             p->d_out.p));
                 }
-                e->prof.end(e->stream);
+                if (!d.is_shape()) e->prof.end(e->stream);
                 HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + toff, p->d_out.p, c.nb * p->dim1 * sizeof(float),
                         hipMemcpyDeviceToHost, e->stream));
                 toff += c.nb * p->dim1;

@@ -204,6 +204,10 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             st->data.dim[0] = (int32_t)num_frames; st->data.dim[1] = (int32_t)st->dim1;
             st->data.unit_str[0] = ""; st->data.unit_str[1] = "\xC3\x85";
             if (p.nargs() > 2) st->data.unit_str[1] = e->spec.angle_radians ? "rad" : "\xC2\xB0";     // DESIGN S6b, D-ANGLE-UNIT
+            if (p.is_shape()) {                                                                     // a pure number
+                st->data.unit_str[1] = "";
+                for (size_t c = 0; c < st->dist_P; ++c) st->shape_max_set = std::max(st->shape_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
+            }
             if (st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;

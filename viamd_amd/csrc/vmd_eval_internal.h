@@ -350,6 +350,9 @@ enum PropKind { PROP_RDF = 0, PROP_SDF = 1, PROP_DIST = 2 };
 
 // temporal properties of DESIGN S6b: PROP_DIST descriptors with three or four argument sets (dist_kind past vmd_distance_kind_t)
 enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
+// `{lin, plan, iso} = shape_weights(sel)`: three PROP_DIST descriptors in a row, one per name, that carry the same set (a / aoff)
+// and a component index; the device work is done once, where the batch meets component 0
+enum { GEOM_SHAPE = 6 };
 
 struct Property {
     std::string name;
@@ -362,6 +365,8 @@ struct Property {
     std::vector<int32_t> aoff, boff;   // DIST: context offsets into a / b (population), size P + 1
     std::vector<int32_t> c, d, coff, doff;   // angle / dihedral: the third and fourth argument sets, offsets as aoff
     int nargs() const { return dist_kind == GEOM_DIHEDRAL ? 4 : (dist_kind == GEOM_ANGLE ? 3 : 2); }
+    int shape_comp = 0;             // shape_weights: 0 = linear, 1 = planar, 2 = isotropic
+    bool is_shape() const { return kind == PROP_DIST && dist_kind == GEOM_SHAPE; }
 };
 
 struct vmd_script_ir_t {
@@ -468,6 +473,8 @@ struct PropState {
     DevBuf<float> d_ma, d_mb, d_out;
     DevBuf<int32_t> d_c, d_d, d_coff, d_doff;     // angle / dihedral
     DevBuf<float> d_mc, d_md;
+    DevBuf<double> d_shape_partial;               // shape_weights, component 0: chunk sums of the batch (vmd_hip_shape)
+    int shape_max_set = 0;                        // ... and the size of the largest context's set
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh

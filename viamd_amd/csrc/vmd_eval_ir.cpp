@@ -1,5 +1,5 @@
 // viamd_amd/csrc/vmd_eval_ir.cpp - the property descriptors behind vmd_ir_*: what md_script_ir_t carries for the hot-path properties
-// (rdf / sdf / distance family, angle / dihedral; /root/reference/src/main.cpp:528, 2817-2858), their fingerprint and the work estimate a host compares
+// (rdf / sdf / distance family, angle / dihedral, shape_weights; /root/reference/src/main.cpp:528, 2817-2858), their fingerprint and the work estimate a host compares
 // with its threshold (include/vmd_md_script_shim.h).
 #include "vmd_eval_internal.h"
 
@@ -12,7 +12,7 @@ uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
 extern "C" vmd_script_ir_t* vmd_ir_create(void) { return new vmd_script_ir_t(); }
 
 // atom pairs one frame of this script asks for (rdf: |ref| x |target|; sdf: K x |target| + K m for the alignment; distance: |a| x |b| of
-// every context; angle / dihedral: the atoms of every context's sets): what a host compares with its threshold before it sends a SMALL script to the GPU at all (include/vmd_md_script_shim.h,
+// every context; angle / dihedral / shape_weights: the atoms of every context's sets): what a host compares with its threshold before it sends a SMALL script to the GPU at all (include/vmd_md_script_shim.h,
 // vmd_shim_set_min_work; VIAMD's default dataset is ~1e2 atoms, src/main.cpp:522-528)
 extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     if (!ir) return 0;
@@ -20,6 +20,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     for (const Property& p : ir->props) {
         if (p.kind == PROP_RDF) w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
         else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
+        else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
         else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
                 * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
@@ -168,16 +169,58 @@ extern "C" bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* 
     return ir_add_geometry(ir, name, GEOM_DIHEDRAL, P, sets, offs);
 }
 
+// `{n0, n1, n2} = shape_weights(sel) [in <contexts>];`: three temporal properties over one population of sets
+static bool ir_add_shape(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx, const int32_t* offs) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names) return vmd_fail("shape_weights needs three property names");
+    for (int k = 0; k < 3; ++k) {
+        if (!ir_name_ok(ir, names[k])) return false;
+        for (int j = 0; j < k; ++j)
+            if (!strcmp(names[j], names[k])) return vmd_fail("property '%s' already defined", names[k]);
+    }
+    if (P == 0) return vmd_fail("shape_weights population is empty");
+    if (!offs) return vmd_fail("shape_weights set has no context offsets");
+    if (offs[0] != 0) return vmd_fail("context offsets must start at 0");
+    for (size_t c = 0; c < P; ++c)
+        if (offs[c + 1] <= offs[c]) return vmd_fail("shape_weights context %zu has an empty set (offsets must increase)", c);
+    if (!idx_ok(idx, (size_t)offs[P], "shape_weights set")) return false;
+    for (int k = 0; k < 3; ++k) {
+        Property p;
+        p.name = names[k]; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+        p.dist_kind = GEOM_SHAPE; p.shape_comp = k;
+        p.a.assign(idx, idx + offs[P]); p.aoff.assign(offs, offs + P + 1);
+        ir->props.push_back(std::move(p));
+    }
+    ir->rebuild_names();
+    return true;
+}
+
+extern "C" bool vmd_ir_add_shape_weights(vmd_script_ir_t* ir, const char* const names[3], const int32_t* idx, size_t n) {
+    if (n > 0x7fffffff) return vmd_fail("shape_weights set too large");
+    const int32_t off[2] = {0, (int32_t)n};
+    return ir_add_shape(ir, names, 1, idx, off);
+}
+
+extern "C" bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx,
+                                                    const int32_t* offsets) {
+    return ir_add_shape(ir, names, P, idx, offsets);
+}
+
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
 extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
     if (!ir || !name) return 0;
     for (const Property& p : ir->props) {
         if (p.name != name) continue;
-        if (p.kind != PROP_DIST || p.nargs() < 3) return 0;
+        if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape())) return 0;
         const size_t P = p.aoff.size() - 1;
         if (context >= (int64_t)P) return 0;
         const size_t c0 = context < 0 ? 0 : (size_t)context, c1 = context < 0 ? P : (size_t)context + 1;
+        if (p.is_shape()) {     // shape_weights: the set of the context(s)
+            size_t n = 0;
+            for (int32_t i = p.aoff[c0]; i < p.aoff[c1]; ++i) { if (out && n < cap) out[n] = p.a[(size_t)i]; n += 1; }
+            return n;
+        }
         const std::vector<int32_t>* sets[4] = {&p.a, &p.b, &p.c, &p.d};
         const std::vector<int32_t>* offs[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
         size_t n = 0;
@@ -207,6 +250,7 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         // angle / dihedral only (empty otherwise: hashing no bytes leaves every earlier fingerprint as it was)
         h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
         h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
+        if (p.is_shape()) h = fnv1a(h, &p.shape_comp, sizeof(int));     // shape_weights only, as above
     }
     h = h ? h : 1;
     ir->fingerprint = h;

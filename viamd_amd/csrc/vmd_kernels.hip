@@ -13,6 +13,7 @@
 //   sdf() + density volume       -> k_sdf_align (fp64 Horn/Jacobi) + k_sdf_scatter
 //   distance*()                  -> k_distance_com / k_distance_minmax / k_distance_pair
 //   angle() / dihedral()         -> k_geom<3> / k_geom<4>
+//   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
 //
 // Design notes (DESIGN.md has the long form):
 //  * wave64 everywhere; a wave is the unit of work in the pair kernel (private LDS histogram + private LDS
@@ -2719,6 +2720,213 @@ __global__ __launch_bounds__(64) void k_geom(vmd_geom_params_t p) {
     p.out[t] = p.radians ? (float)rad : (float)(rad * (180.0 / M_PI));
 }
 
+// ------------------------------------------------------------------------------------------------ K5c: shape_weights
+
+// The reduction order is a function of the set size alone: a set is cut into chunks of VMD_SHAPE_CHUNK atoms; atom j of a chunk belongs to
+// thread j % 256, which adds its atoms in increasing j; the 64 lanes of a wave are summed by the xor butterfly 32, 16, 8, 4, 2, 1; the four
+// waves of the block and then the chunks are added in increasing order.
+#define VMD_SHAPE_CHUNK 4096
+#define VMD_SHAPE_BLOCK 256
+#define VMD_SHAPE_WAVE_SET 64      // a population whose largest set has at most this many atoms: one wave per set (k_shape_small)
+
+struct vmd_shape_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* set; const float* mass; const int32_t* off; int P;   // context c: set[off[c] .. off[c+1]), masses parallel to set
+    int nchunk;        // chunks of the largest set
+    double* partial;   // [B][P][nchunk][10]: W, S1 x y z, S2 xx xy xz yy yz zz
+    float* lin; float* plan; float* iso;   // [B][P] each
+};
+
+// both 32-bit halves of a double through the float shuffle (bit moves)
+__device__ __forceinline__ double vmd_shfl_xor_f64(double v, int o) {
+    int h[2];
+    __builtin_memcpy(h, &v, 8);
+    h[0] = __float_as_int(__shfl_xor(__int_as_float(h[0]), o));
+    h[1] = __float_as_int(__shfl_xor(__int_as_float(h[1]), o));
+    __builtin_memcpy(&v, h, 8);
+    return v;
+}
+
+// The shape kernels' offset e = mi(x - x_first), vmd_mi3_rint bit for bit.  Orthorhombic axes avoid the division in the common case:
+// d - L rint(d / L) needs only the INTEGER nearest to d / L, and q = d * (1 / L) is within 2^-51 |q| of the quotient, so rint(q) is that
+// integer unless q lies that close to a half-integer; then (and for huge |q|) the quotients themselves are formed - one rare branch per
+// atom, behind the loads.  iL = 1 / L in fp64, once per thread.
+struct vmd_shape_box_t { vmd_box_t bx; double Lx, Ly, Lz, iLx, iLy, iLz; };
+__device__ __forceinline__ vmd_shape_box_t vmd_shape_box(const float* boxes, int b, uint32_t pbc) {
+    vmd_shape_box_t s;
+    s.bx = vmd_load_box(boxes, b, pbc);
+    s.Lx = (double)s.bx.Lx; s.Ly = (double)s.bx.Ly; s.Lz = (double)s.bx.Lz;
+    s.iLx = 1.0 / s.Lx; s.iLy = 1.0 / s.Ly; s.iLz = 1.0 / s.Lz;
+    return s;
+}
+__device__ __forceinline__ bool vmd_shape_round_sure(double q, double r) { return fabs(q - r) < 0.499999 && fabs(q) < 1.0e9; }
+__device__ __forceinline__ void vmd_shape_mi(const vmd_shape_box_t& s, double& dx, double& dy, double& dz) {
+    if (s.bx.tri) { vmd_mi3_rint(s.bx, dx, dy, dz); return; }
+    const double qx = dx * s.iLx, qy = dy * s.iLy, qz = dz * s.iLz;
+    double rx = rint(qx), ry = rint(qy), rz = rint(qz);
+    const bool sure = (!s.bx.px || vmd_shape_round_sure(qx, rx)) && (!s.bx.py || vmd_shape_round_sure(qy, ry)) &&
+                      (!s.bx.pz || vmd_shape_round_sure(qz, rz));
+    if (__builtin_expect(!sure, 0)) { rx = rint(dx / s.Lx); ry = rint(dy / s.Ly); rz = rint(dz / s.Lz); }
+    if (s.bx.px) dx = dx - s.Lx * rx;
+    if (s.bx.py) dy = dy - s.Ly * ry;
+    if (s.bx.pz) dz = dz - s.Lz * rz;
+}
+
+// Atom a of the set in two steps, so that a thread has the loads of several atoms in flight before it looks at the first (a branch
+// between two loads makes the compiler wait for each of them).  An atom past the end is read as atom 0 with weight 0: every term is
+// +-0 and leaves the sums as they are.
+struct vmd_shape_atom_t { float x, y, z, w; };
+__device__ __forceinline__ vmd_shape_atom_t vmd_shape_load(const float* fx, const float* fy, const float* fz, const int32_t* set,
+                                                           const float* mass, int a, int n) {
+    const bool live = a < n;
+    const int aa = live ? a : 0;
+    const int i = set[aa];
+    vmd_shape_atom_t q;
+    q.x = fx[i]; q.y = fy[i]; q.z = fz[i];
+    const float m = mass[aa];
+    q.w = live ? m : 0.0f;
+    return q;
+}
+// the ten moments of one atom added to s
+__device__ __forceinline__ void vmd_shape_add(const vmd_shape_atom_t& q, const vmd_shape_box_t& bx, double p0x, double p0y, double p0z,
+                                              double s[10]) {
+    const double w = (double)q.w;
+    double ex = (double)q.x - p0x, ey = (double)q.y - p0y, ez = (double)q.z - p0z;
+    vmd_shape_mi(bx, ex, ey, ez);
+    const double wx = w * ex, wy = w * ey, wz = w * ez;
+    s[0] = s[0] + w;
+    s[1] = s[1] + wx; s[2] = s[2] + wy; s[3] = s[3] + wz;
+    s[4] = s[4] + wx * ex; s[5] = s[5] + wx * ey; s[6] = s[6] + wx * ez;
+    s[7] = s[7] + wy * ey; s[8] = s[8] + wy * ez; s[9] = s[9] + wz * ez;
+}
+
+__device__ __forceinline__ void vmd_shape_wave_sum(double s[10]) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] = s[k] + vmd_shfl_xor_f64(s[k], o);
+}
+
+// Westin's measures of M = S2 - S1 S1^T / W: eigenvalues by cyclic Jacobi (pairs (0,1), (0,2), (1,2), at most 16 sweeps, ends when the
+// off-diagonal is exactly 0), sorted, clamped at 0.  t == 0 or W == 0: 0, 0, 0 (D-SHAPE-DEGENERATE).
+__device__ void vmd_shape_values(const double s[10], float& lin, float& plan, float& iso) {
+    lin = 0.0f; plan = 0.0f; iso = 0.0f;
+    const double W = s[0];
+    if (W == 0.0) return;
+    double a00 = s[4] - (s[1] * s[1]) / W, a01 = s[5] - (s[1] * s[2]) / W, a02 = s[6] - (s[1] * s[3]) / W;
+    double a11 = s[7] - (s[2] * s[2]) / W, a12 = s[8] - (s[2] * s[3]) / W, a22 = s[9] - (s[3] * s[3]) / W;
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        if ((fabs(a01) + fabs(a02)) + fabs(a12) == 0.0) break;
+#pragma unroll
+        for (int pair = 0; pair < 3; ++pair) {
+            // (p, q, r): the rotated pair and the third index
+            double& app = pair == 2 ? a11 : a00;
+            double& aqq = pair == 0 ? a11 : a22;
+            double& apq = pair == 0 ? a01 : (pair == 1 ? a02 : a12);
+            double& arp = pair == 0 ? a02 : (pair == 1 ? a01 : a01);     // A[r][p]
+            double& arq = pair == 0 ? a12 : (pair == 1 ? a12 : a02);     // A[r][q]
+            if (apq == 0.0) continue;
+            const double theta = (aqq - app) / (2.0 * apq);
+            double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+            if (theta < 0.0) t = -t;
+            const double c = 1.0 / sqrt(t * t + 1.0);
+            const double sn = t * c;
+            const double rp = arp, rq = arq;
+            arp = c * rp - sn * rq;
+            arq = sn * rp + c * rq;
+            app = app - t * apq;
+            aqq = aqq + t * apq;
+            apq = 0.0;
+        }
+    }
+    double l1 = a00, l2 = a11, l3 = a22, h;
+    if (l1 < l2) { h = l1; l1 = l2; l2 = h; }
+    if (l2 < l3) { h = l2; l2 = l3; l3 = h; }
+    if (l1 < l2) { h = l1; l1 = l2; l2 = h; }
+    l1 = l1 < 0.0 ? 0.0 : l1; l2 = l2 < 0.0 ? 0.0 : l2; l3 = l3 < 0.0 ? 0.0 : l3;
+    const double t = (l1 + l2) + l3;
+    if (t == 0.0) return;
+    lin = (float)((l1 - l2) / t);
+    plan = (float)((2.0 * (l2 - l3)) / t);
+    iso = (float)((3.0 * l3) / t);
+}
+
+// one block per (frame, context, chunk): ten fp64 sums per thread in registers, wave butterfly, the four wave sums through LDS
+__global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_moments(vmd_shape_params_t p) {
+    __shared__ double s_wave[VMD_SHAPE_BLOCK / 64][10];
+    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
+    const int b = bc / p.P, c = bc - b * p.P;
+    const int k0 = p.off[c], n = p.off[c + 1] - k0;
+    const int a0 = chunk * VMD_SHAPE_CHUNK;
+    if (a0 >= n) return;          // the whole block: a context with fewer chunks than the largest set
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_shape_box_t bx = vmd_shape_box(p.boxes, b, p.pbc);
+    const int32_t* set = p.set + k0;
+    const float* mass = p.mass + k0;
+    const int i0 = set[0];
+    const double p0x = (double)fx[i0], p0y = (double)fy[i0], p0z = (double)fz[i0];
+    double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int tid = threadIdx.x;
+    // four atoms per step: their sixteen loads first, then the sums in atom order
+#pragma unroll 1
+    for (int k = 0; k < VMD_SHAPE_CHUNK / VMD_SHAPE_BLOCK; k += 4) {
+        vmd_shape_atom_t q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = vmd_shape_load(fx, fy, fz, set, mass, a0 + (k + u) * VMD_SHAPE_BLOCK + tid, n);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vmd_shape_add(q[u], bx, p0x, p0y, p0z, s);
+    }
+    vmd_shape_wave_sum(s);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < 10; ++k) s_wave[tid >> 6][k] = s[k];
+    __syncthreads();
+    if (tid < 10) p.partial[(size_t)blockIdx.x * 10 + tid] = ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid];
+}
+
+// one thread per (frame, context): the chunk sums in chunk order, then the three values
+__global__ __launch_bounds__(64) void k_shape_finish(vmd_shape_params_t p) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.B * p.P) return;
+    const int c = t % p.P;
+    const int n = p.off[c + 1] - p.off[c];
+    const int nch = (n + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK;
+    const double* q = p.partial + (size_t)t * p.nchunk * 10;
+    double s[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) s[k] = q[k];
+    for (int ch = 1; ch < nch; ++ch)
+#pragma unroll
+        for (int k = 0; k < 10; ++k) s[k] = s[k] + q[ch * 10 + k];
+    vmd_shape_values(s, p.lin[t], p.plan[t], p.iso[t]);
+}
+
+// populations of small sets (`... in residue(:)`): one wave per (frame, context), lane j holds atom j; the same sums in the same order as
+// k_shape_moments + k_shape_finish give for such a set (one chunk, one atom per thread, three empty waves), without the partials
+__global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_small(vmd_shape_params_t p) {
+    const int t = blockIdx.x * (VMD_SHAPE_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= p.B * p.P) return;   // the whole wave
+    const int b = t / p.P, c = t - b * p.P;
+    const int k0 = p.off[c], n = p.off[c + 1] - k0;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_shape_box_t bx = vmd_shape_box(p.boxes, b, p.pbc);
+    const int32_t* set = p.set + k0;
+    const int i0 = set[0];
+    const double p0x = (double)fx[i0], p0y = (double)fy[i0], p0z = (double)fz[i0];
+    double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    vmd_shape_add(vmd_shape_load(fx, fy, fz, set, p.mass + k0, lane, n), bx, p0x, p0y, p0z, s);
+    vmd_shape_wave_sum(s);
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) s[k] = ((s[k] + 0.0) + 0.0) + 0.0;
+    vmd_shape_values(s, p.lin[t], p.plan[t], p.iso[t]);
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -3140,6 +3348,36 @@ extern "C" int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_str
     const dim3 g((unsigned)(((long long)B * P + 63) / 64));
     if (nargs == 3) hipLaunchKernelGGL((k_geom<3>), g, dim3(64), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((k_geom<4>), g, dim3(64), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t vmd_hip_shape_partial_doubles(int B, int P, int max_set) {
+    if (B <= 0 || P <= 0 || max_set <= VMD_SHAPE_WAVE_SET) return 0;
+    return (size_t)B * (size_t)P * (size_t)((max_set + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK) * 10;
+}
+
+extern "C" int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                             const float* boxes, uint32_t pbc_flags, int B, int P,
+                             const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                             double* partial, float* lin, float* plan, float* iso) {
+    if (B <= 0 || P <= 0) return 0;
+    if (!set || !mass || !offsets || !lin || !plan || !iso || max_set <= 0 || (long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    vmd_shape_params_t p{};
+    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
+    p.set = set; p.mass = mass; p.off = offsets; p.lin = lin; p.plan = plan; p.iso = iso;
+    if (max_set <= VMD_SHAPE_WAVE_SET) {
+        const int per = VMD_SHAPE_BLOCK / 64;
+        hipLaunchKernelGGL(k_shape_small, dim3((unsigned)(((long long)B * P + per - 1) / per)), dim3(VMD_SHAPE_BLOCK), 0, (hipStream_t)stream, p);
+        VMD_LAUNCH_CHECK();
+        return 0;
+    }
+    p.nchunk = (max_set + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK;
+    p.partial = partial;
+    if (!partial || (long long)B * P * p.nchunk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shape_moments, dim3((unsigned)((long long)B * P * p.nchunk)), dim3(VMD_SHAPE_BLOCK), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_shape_finish, dim3((unsigned)(((long long)B * P + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

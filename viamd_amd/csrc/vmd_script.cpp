@@ -336,7 +336,8 @@ struct Report {
 // hands to the evaluator it falls back on (include/vmd_md_script_shim.h), e.g. `a1 = angle(2,1,3) in resname("ALA");` and
 // `{lin,plan,iso} = shape_weights(all);` of VIAMD's default script (src/main.cpp:528).  A later statement that uses an identifier of a
 // skipped one is skipped with it ("unknown identifier").
-// features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral() (opt-in; 0 = the subset above, byte for byte)
+// features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
+// `{lin, plan, iso} = shape_weights(sel)` (opt-in; 0 = the subset above, byte for byte)
 void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
@@ -368,6 +369,18 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
         std::string names;
         std::function<void()> commit;
         bool is_property = false;
+        // the end of every statement: its ';', the descriptor, and in partial mode the statement's text taken out of the fallback's
+        auto finish_statement = [&]() {
+            if (p.peek().kind != T_END && !p.is_word(";")) fail("expected ;, found '%s'", p.peek().text.c_str());
+            commit();
+            if (p.peek().kind != T_END) p.take(";");
+            if (is_property && report) {
+                // the fallback evaluates the text WITHOUT this statement: blanked in place, so that every other offset stays what the editor shows
+                const size_t e = last < toks.size() ? toks[last].end : toks[last - 1].end;
+                for (size_t c = toks[first].beg; c < e && c < fallback.size(); ++c) if (fallback[c] != '\n') fallback[c] = ' ';
+                blanked.push_back(Blanked{names, first, last, toks[first].beg, std::min(e, fallback.size()), false});
+            }
+        };
         try {
             if (p.is_word("{")) {
                 // tuple assignment `{a, b, c} = f(...)`: no hot-path function returns a tuple
@@ -377,12 +390,58 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                 p.take("}");
                 p.take("=");
                 const Token& f = p.peek();
-                fail("unsupported %s '%s' (outside the rdf / sdf / distance path)", f.kind == T_ID ? "function" : "expression", f.text.c_str());
+                if (!((features & VMD_SCRIPT_FEATURE_SHAPE) && f.kind == T_ID && f.text == "shape_weights"))
+                    fail("unsupported %s '%s' (outside the rdf / sdf / distance path)", f.kind == T_ID ? "function" : "expression", f.text.c_str());
+                // `{lin, plan, iso} = shape_weights(sel) [in <contexts>];`: the one function of the subset that defines a tuple
+                std::vector<std::string> nm(1);
+                for (char ch : names) { if (ch == ',') nm.emplace_back(); else nm.back() += ch; }
+                if (nm.size() != 3) fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not %zu", names.c_str(), nm.size());
+                ++p.i;
+                p.take("(");
+                const size_t start = p.i;
+                size_t j = p.i;
+                int depth = 1;
+                while (depth) {
+                    if (j >= toks.size()) fail("%s: missing ')'", names.c_str());
+                    if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
+                    if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
+                    ++j;
+                }
+                std::vector<int32_t> all, off{0};
+                auto one_set = [&](Parser& r, const char* where) {
+                    const std::vector<int32_t> ix = r.sel_or().indices();
+                    if (r.is_word(",")) fail("%s: shape_weights takes one selection", names.c_str());
+                    r.take(")");
+                    if (ix.empty()) fail("%s: empty selection%s", names.c_str(), where);
+                    all.insert(all.end(), ix.begin(), ix.end());
+                    off.push_back((int32_t)all.size());
+                };
+                if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
+                    Parser q(toks, topo, env);
+                    q.i = j + 1;
+                    const Sel ctx = q.sel_or();
+                    if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", names.c_str());
+                    for (auto& st : ctx.structs) {
+                        Parser r(toks, topo, env, &st);
+                        r.i = start;
+                        one_set(r, " inside a context");
+                    }
+                    p.i = q.i;
+                } else one_set(p, "");
+                is_property = true;
+                commit = [=]() {
+                    const char* const cn[3] = {nm[0].c_str(), nm[1].c_str(), nm[2].c_str()};
+                    if (!vmd_ir_add_shape_weights_population(ir, cn, off.size() - 1, all.data(), off.data())) throw ScriptError(vmd_last_error());
+                };
+                finish_statement();
+                continue;
             }
             const std::string name = p.take(nullptr, T_ID);
             names = name;
             p.take("=");
             const Token k = p.peek();
+            if ((features & VMD_SCRIPT_FEATURE_SHAPE) && k.kind == T_ID && k.text == "shape_weights")
+                fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not 1", name.c_str());
             const bool is_func = k.kind == T_ID && (k.text == "rdf" || k.text == "sdf" || k.text == "distance" || k.text == "distance_min" ||
                                                     k.text == "distance_max" || k.text == "distance_pair" ||
                                                     ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")));
@@ -488,15 +547,7 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                 const Sel sel = p.sel_or();
                 commit = [&env, name, sel]() { env[name] = sel; };
             }
-            if (p.peek().kind != T_END && !p.is_word(";")) fail("expected ;, found '%s'", p.peek().text.c_str());
-            commit();
-            if (p.peek().kind != T_END) p.take(";");
-            if (is_property && report) {
-                // the fallback evaluates the text WITHOUT this statement: blanked in place, so that every other offset stays what the editor shows
-                const size_t e = last < toks.size() ? toks[last].end : toks[last - 1].end;
-                for (size_t c = toks[first].beg; c < e && c < fallback.size(); ++c) if (fallback[c] != '\n') fallback[c] = ' ';
-                blanked.push_back(Blanked{names, first, last, toks[first].beg, std::min(e, fallback.size()), false});
-            }
+            finish_statement();
         } catch (const ScriptError& e) {
             if (!report) throw;
             (void)check;
@@ -519,7 +570,14 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
         for (bool changed = true; changed;) {
             changed = false;
             for (Blanked& b : blanked) {
-                if (b.kept || !used.count(b.name)) continue;
+                // (a shape_weights statement carries its three names joined by ',')
+                bool mentioned = false;
+                for (size_t n0 = 0; n0 <= b.name.size() && !mentioned;) {
+                    const size_t n1 = std::min(b.name.find(',', n0), b.name.size());
+                    mentioned = used.count(b.name.substr(n0, n1 - n0)) != 0;
+                    n0 = n1 + 1;
+                }
+                if (b.kept || !mentioned) continue;
                 b.kept = changed = true;
                 for (size_t c = b.beg; c < b.end; ++c) fallback[c] = source[c];        // the GPU still evaluates it; mdlib evaluates it too, for its users
                 collect(b.tok_first, b.tok_end);

@@ -137,8 +137,29 @@ class ScriptIR:
         """`name = dihedral(a, b, c, d) in <contexts>`: one quadruple of index sets per context."""
         self._add_geometry_population(self.lib.vmd_ir_add_dihedral_population, name, (a_sets, b_sets, c_sets, d_sets))
 
+    def add_shape_weights(self, names, idx):
+        """`{n0, n1, n2} = shape_weights(idx);`: three temporal properties - linear, planar, isotropic - of one set."""
+        x, xp = _idx(idx)
+        self._check(self.lib.vmd_ir_add_shape_weights(self.h, self._names3(names), xp, x.size))
+
+    def add_shape_weights_population(self, names, sets):
+        """`{n0, n1, n2} = shape_weights(sel) in <contexts>`: one index set per context -> dim[1] = number of contexts."""
+        assert len(sets) > 0
+        flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in sets]).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum([len(x) for x in sets])]).astype(np.int32)
+        self._check(self.lib.vmd_ir_add_shape_weights_population(self.h, self._names3(names), len(sets), flat.ctypes.data_as(L.c_int32_p),
+                                                                 off.ctypes.data_as(L.c_int32_p)))
+
+    @staticmethod
+    def _names3(names):
+        import ctypes as C
+        names = list(names)
+        assert len(names) == 3, "shape_weights defines three properties"
+        return (C.c_char_p * 3)(*[n.encode() for n in names])
+
     def geometry_atoms(self, name, context=-1):
-        """the atoms of an angle / dihedral property (one context, or all when context < 0), in argument order"""
+        """the atoms of an angle / dihedral property (one context, or all when context < 0) in argument order, or the set of a
+        shape_weights property"""
         n = int(self.lib.vmd_ir_geometry_atoms(self.h, name.encode(), int(context), None, 0))
         out = np.zeros(n, np.int32)
         if n:

@@ -266,9 +266,10 @@ _FUNCS = {"rdf", "sdf", "distance", "distance_min", "distance_max", "distance_pa
 _DIST_KIND = {"distance": L.DIST_COM, "distance_min": L.DIST_MIN, "distance_max": L.DIST_MAX, "distance_pair": L.DIST_PAIR}
 _GEOM_NARGS = {"angle": 3, "dihedral": 4}       # opt-in (angles=True)
 FEATURE_ANGLES = 1                              # VMD_SCRIPT_FEATURE_ANGLES
+FEATURE_SHAPE = 2                               # VMD_SCRIPT_FEATURE_SHAPE
 
 
-def compile_script(text, topo, lib=None, partial=False, angles=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -276,7 +277,11 @@ def compile_script(text, topo, lib=None, partial=False, angles=False):
     property statements blanked out).  VIAMD's default script (src/main.cpp:528) then yields d1, r, v and reports a1 and lin,plan,iso.
 
     angles=True (VMD_SCRIPT_FEATURE_ANGLES, opt-in): angle(sel, sel, sel) and dihedral(sel, sel, sel, sel), plain or `in <contexts>`,
-    are compiled too (DESIGN S6b); the default script then yields d1, a1, r, v and reports lin,plan,iso only."""
+    are compiled too (DESIGN S6b); the default script then yields d1, a1, r, v and reports lin,plan,iso only.
+
+    shape=True (VMD_SCRIPT_FEATURE_SHAPE, opt-in): `{n0, n1, n2} = shape_weights(sel)`, plain or `in <contexts>`, defines three temporal
+    properties, info[n] = dict(kind="shape_weights", component=0 | 1 | 2, sets=[one index array per context]); with both
+    opt-ins the default script compiles whole: d1, a1, r, v, lin, plan, iso, nothing skipped."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -309,11 +314,16 @@ def compile_script(text, topo, lib=None, partial=False, angles=False):
                 p.take("}")
                 p.take("=")
                 k, v = p.peek()
-                raise ScriptError(f"unsupported {'function' if k == 'id' else 'expression'} {v!r} (outside the rdf / sdf / distance path)")
-            name = p.take(kind="id")
-            names = name
-            p.take("=")
-            commit, is_property = _statement(p, name, topo, env, ir, info, angles)
+                if not (shape and k == "id" and v == "shape_weights"):
+                    raise ScriptError(f"unsupported {'function' if k == 'id' else 'expression'} {v!r} (outside the rdf / sdf / distance path)")
+                commit, is_property = _shape_statement(p, names, topo, env, ir, info), True
+            else:
+                name = p.take(kind="id")
+                names = name
+                p.take("=")
+                if shape and p.peek() == ("id", "shape_weights"):
+                    raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -350,13 +360,59 @@ def compile_script(text, topo, lib=None, partial=False, angles=False):
         while changed:
             changed = False
             for item in blanked:
-                if item[5] or item[0] not in used:
+                if item[5] or not any(n in used for n in item[0].split(",")):      # (shape_weights: three names joined by ',')
                     continue
                 item[5] = changed = True
                 fallback[item[3]:item[4]] = text[item[3]:item[4]]
                 collect(item[1], item[2])
         return ir, info, dict(skipped=skipped, fallback_source="".join(fallback))
     return ir, info
+
+
+def _shape_statement(p, names, topo, env, ir, info):
+    """`{n0, n1, n2} = shape_weights(sel) [in <contexts>]` from the function name on (the twin of the tuple branch of vmd_script.cpp)."""
+    nm = names.split(",")
+    if len(nm) != 3:
+        raise ScriptError(f"{names}: shape_weights defines three properties, {{linear, planar, isotropic}}, not {len(nm)}")
+    p.i += 1
+    p.take("(")
+    start = p.i
+    j, depth = p.i, 1
+    while depth:
+        if j >= len(p.t):
+            raise ScriptError(f"{names}: missing ')'")
+        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
+        j += 1
+    sets = []
+
+    def one_set(r, where):
+        ix = r.sel_or().indices()
+        if r.peek() == ("op", ","):
+            raise ScriptError(f"{names}: shape_weights takes one selection")
+        r.take(")")
+        if ix.size == 0:
+            raise ScriptError(f"{names}: empty selection{where}")
+        sets.append(ix)
+
+    if j < len(p.t) and p.t[j] == ("id", "in"):
+        q = _Parser(p.t, topo, env)
+        q.i = j + 1
+        ctx = q.sel_or()
+        if ctx.structures is None or not ctx.structures:
+            raise ScriptError(f"{names}: `in` needs an array of structures (residue(...), resname(...))")
+        for st in ctx.structures:
+            r = _Parser(p.t, topo, env, ctx=np.asarray(st))
+            r.i = start
+            one_set(r, " inside a context")
+        p.i = q.i
+    else:
+        one_set(p, "")
+
+    def commit():
+        ir.add_shape_weights_population(nm, sets)
+        for k, n in enumerate(nm):
+            info[n] = dict(kind="shape_weights", component=k, sets=sets)
+    return commit
 
 
 def _statement(p, name, topo, env, ir, info, angles=False):
@@ -463,13 +519,14 @@ def _statement(p, name, topo, env, ir, info, angles=False):
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False, angles=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
-    VMD_SCRIPT_FEATURE_ANGLES."""
+    VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
+    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
@@ -479,13 +536,13 @@ def compile_script_native(text, topo, lib=None, partial=False, angles=False):
     sq = None if topo.residue_seq_id is None else np.ascontiguousarray(topo.residue_seq_id, np.int32)
     tc = L.TopologyC(n, el, nm, rn, ri.ctypes.data_as(L.c_int32_p), sq.ctypes.data_as(L.c_int32_p) if sq is not None else None)
     if not partial:
-        ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), FEATURE_ANGLES, None) if angles
+        ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), features, None) if features
               else ir.lib.vmd_ir_compile_from_source(ir.h, text.encode(), C.byref(tc)))
         if not ok:
             raise ScriptError(ir.lib.last_error())
         return ir
     rep = C.c_void_p()
-    ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), FEATURE_ANGLES, C.byref(rep)) if angles
+    ok = (ir.lib.vmd_ir_compile_from_source_ex(ir.h, text.encode(), C.byref(tc), features, C.byref(rep)) if features
           else ir.lib.vmd_ir_compile_from_source_partial(ir.h, text.encode(), C.byref(tc), C.byref(rep)))
     if not ok:
         raise ScriptError(ir.lib.last_error())
