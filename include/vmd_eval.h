@@ -228,8 +228,16 @@ bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* name, size_
 bool vmd_ir_add_shape_weights(vmd_script_ir_t* ir, const char* const names[3], const int32_t* idx, size_t n);
 bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx,
                                          const int32_t* offsets);
+/* `name = rmsd(sel) [in <contexts>];`: the mass-weighted root-mean-square deviation of the set from its own pose at
+ * trajectory frame 0 after the best rigid fit (translation and proper rotation), in Angstrom; weights are the masses, 1 under
+ * spec_dist_geometric_com.  One temporal property laid out like distance(a, b) in <contexts>: values[frame * dim[1] + c], dim[1] = P.
+ * The row of trajectory frame 0 is +0, and so is every row of a set of one atom.  The population form holds every context's set back to
+ * back: context c owns idx[offsets[c] .. offsets[c+1]).  Empty sets, negative indices, offsets that do not start at 0 and increase,
+ * and a name that is already defined are errors (vmd_last_error). */
+bool vmd_ir_add_rmsd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n);
+bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
- * shape_weights property: returns how many
+ * shape_weights or rmsd property: returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
@@ -277,9 +285,12 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
  * (DESIGN S6b); VIAMD's default script then leaves only `{lin,plan,iso} = shape_weights(all);` to the fallback.
  * VMD_SCRIPT_FEATURE_SHAPE also compiles `{n0, n1, n2} = shape_weights(sel) [in <contexts>];` (any other tuple assignment
  * stays outside the subset).  With both, the default script compiles whole - d1, a1, r, v, lin, plan, iso - and the fallback source
- * keeps no property statement. */
+ * keeps no property statement.
+ * VMD_SCRIPT_FEATURE_RMSD also compiles `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context
+ * rules of distance(). */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
 #define VMD_SCRIPT_FEATURE_SHAPE 2u
+#define VMD_SCRIPT_FEATURE_RMSD 4u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -289,7 +300,7 @@ size_t   vmd_ir_property_count(const vmd_script_ir_t* ir);              /* md_sc
 const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir);    /* md_script_ir_property_names, src/main.cpp:1278 */
 vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name); /* src/main.cpp:1285 */
 /* atom pairs ONE frame of the script asks for (rdf |ref| x |target|, sdf K x (|target| + m), distance |a| x |b| per context, angle /
- * dihedral / shape_weights: the atoms of every context's sets): the size a host
+ * dihedral / shape_weights / rmsd: the atoms of every context's sets): the size a host
  * compares with a threshold before it sends a small script to the GPU (vmd_shim_set_min_work; VIAMD's default dataset, src/main.cpp:522-528) */
 uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir);
 

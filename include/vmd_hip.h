@@ -16,6 +16,7 @@
  *   vmd_hip_distance  <- distance / distance_min / distance_max / distance_pair (a8)
  *   vmd_hip_geometry  <- angle / dihedral (DESIGN S6b)
  *   vmd_hip_shape     <- shape_weights
+ *   vmd_hip_rmsd      <- rmsd
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -175,6 +176,22 @@ int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride, size_t ro
                   const float* boxes, uint32_t pbc_flags, int B, int P,
                   const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
                   double* partial, float* lin, float* plan, float* iso);
+
+/* K5d: name = rmsd(sel), DESIGN 1.5: one f32[B][P] block, the mass-weighted RMSD of every context's set after the best rigid fit onto
+ * its pose at trajectory frame 0.  Context c is set[offsets[c] .. offsets[c+1]) with mass parallel to set (device arrays); max_set is the
+ * size of the largest context's set.  vmd_hip_rmsd_pose runs once per trajectory over frame 0 (xyz, box: that one frame) and fills
+ * pose (3 doubles per entry of set) and consts (8 doubles per context); vmd_hip_rmsd reads them for every batch.  zero_row is the row
+ * of the batch that IS trajectory frame 0 - its values are +0 by definition - or -1.  `workspace` is device memory of
+ * vmd_hip_rmsd_workspace_bytes(B, P, max_set) bytes, 8-byte aligned (B = 1 for the pose): the sums of every (frame, context, chunk of
+ * 4096 atoms) and the chunks' link shifts; the sums alone when max_set <= 64 (one wave per set). */
+size_t vmd_hip_rmsd_workspace_bytes(int B, int P, int max_set);
+int vmd_hip_rmsd_pose(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, int P,
+                      const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                      void* workspace, double* pose, double* consts);
+int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                 const float* boxes, uint32_t pbc_flags, int B, int P,
+                 const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                 const double* pose, const double* consts, int zero_row, void* workspace, float* out);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -154,6 +154,8 @@ SIGNATURES = [
                                                   c_int32_p, c_int32_p, c_int32_p]),
     ("vmd_ir_add_shape_weights", C.c_bool, [_vp, C.POINTER(C.c_char_p), c_int32_p, C.c_size_t]),
     ("vmd_ir_add_shape_weights_population", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.c_size_t, c_int32_p, c_int32_p]),
+    ("vmd_ir_add_rmsd", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
+    ("vmd_ir_add_rmsd_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -325,6 +327,10 @@ SIGNATURES = [
     ("vmd_hip_shape_partial_doubles", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("vmd_hip_shape", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                 _vp, _vp, _vp, _vp]),
+    ("vmd_hip_rmsd_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("vmd_hip_rmsd_pose", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_rmsd", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
+                               _vp, _vp, C.c_int, _vp, _vp]),
     ("vmd_hip_add_u64", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("vmd_hip_counts_to_float", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_float]),
     ("vmd_hip_bump_u64", C.c_int, [_vp, _vp, C.c_uint64]),

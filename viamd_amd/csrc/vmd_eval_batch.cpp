@@ -260,6 +260,26 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         p->ref_pose_ready = true;
     }
 
+    // rmsd reference pose: every context's set at trajectory frame 0.  It belongs to (evaluator, trajectory): rebuilt when
+    // this call's trajectory is not the one it was built for
+    for (auto& p : e->props) {
+        if (!p->prop.is_rmsd()) continue;
+        const TrajId now = traj_id(traj);
+        if (p->rmsd_pose_ready && p->rmsd_pose_inst == now.inst && p->rmsd_pose_fn == now.fn) continue;
+        BatchSrc src;
+        if (!fetch_batch(e, traj, view_holds(have_view, view, 0) ? &view : nullptr, num_atoms, 0, 1, &src)) return false;
+        const size_t ws = vmd_hip_rmsd_workspace_bytes(1, (int)p->dist_P, p->rmsd_max_set);
+        if (!p->d_rmsd_pose.ensure(p->prop.a.size() * 3) || !p->d_rmsd_const.ensure(p->dist_P * 8) || !p->d_rmsd_ws.ensure((ws + 7) / 8))
+            return false;
+        e->prof.begin("rmsd", e->stream);
+        KRN_OK(vmd_hip_rmsd_pose(e->stream, src.base, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), (int)p->dist_P,
+                p->d_a.p, p->d_ma.p, p->d_aoff.p, p->rmsd_max_set, p->d_rmsd_ws.p, p->d_rmsd_pose.p, p->d_rmsd_const.p));
+        e->prof.end(e->stream);
+        HIP_OK(hipStreamSynchronize(e->stream));
+        p->rmsd_pose_inst = now.inst; p->rmsd_pose_fn = now.fn;
+        p->rmsd_pose_ready = true;
+    }
+
     // frames served from the block partials of the source eval (filtered evaluation), the rest is computed
     std::vector<std::pair<size_t, size_t>> segments;
     // a region's blocks are adopted from the source by the region leader, or evaluated here
@@ -716,6 +736,14 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                                 p1->d_out.p, p2->d_out.p));
                         e->prof.end(e->stream);
                     }
+                } else if (d.is_rmsd()) {
+                    // rmsd: the same [nb][P] block, the same copy below; the batch knows which of its rows is frame 0
+                    const size_t ws = vmd_hip_rmsd_workspace_bytes((int)c.nb, (int)p->dist_P, p->rmsd_max_set);
+                    if (!p->d_rmsd_ws.ensure((ws + 7) / 8)) return false;
+                    e->prof.begin("rmsd", e->stream);
+                    KRN_OK(vmd_hip_rmsd(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+                            (int)p->dist_P, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->rmsd_max_set, p->d_rmsd_pose.p, p->d_rmsd_const.p,
+                            c.f0 == 0 ? 0 : -1, p->d_rmsd_ws.p, p->d_out.p));
                 } else if (d.nargs() > 2) {
                     // angle / dihedral (DESIGN S6b): the same [nb][P] block, the same copy below
                     const int32_t* sets[4] = {p->d_a.p, p->d_b.p, p->d_c.p, p->d_d.p};

@@ -208,6 +208,8 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
                 st->data.unit_str[1] = "";
                 for (size_t c = 0; c < st->dist_P; ++c) st->shape_max_set = std::max(st->shape_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
             }
+            if (p.is_rmsd())                                                                      // Angstrom, as distance
+                for (size_t c = 0; c < st->dist_P; ++c) st->rmsd_max_set = std::max(st->rmsd_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
             if (st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;

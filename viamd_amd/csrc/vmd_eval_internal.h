@@ -353,6 +353,8 @@ enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
 // `{lin, plan, iso} = shape_weights(sel)`: three PROP_DIST descriptors in a row, one per name, that carry the same set (a / aoff)
 // and a component index; the device work is done once, where the batch meets component 0
 enum { GEOM_SHAPE = 6 };
+// `name = rmsd(sel)`: one PROP_DIST descriptor that carries the set (a / aoff); the evaluator keeps the frame-0 pose of the set
+enum { GEOM_RMSD = 7 };
 
 struct Property {
     std::string name;
@@ -367,6 +369,7 @@ struct Property {
     int nargs() const { return dist_kind == GEOM_DIHEDRAL ? 4 : (dist_kind == GEOM_ANGLE ? 3 : 2); }
     int shape_comp = 0;             // shape_weights: 0 = linear, 1 = planar, 2 = isotropic
     bool is_shape() const { return kind == PROP_DIST && dist_kind == GEOM_SHAPE; }
+    bool is_rmsd() const { return kind == PROP_DIST && dist_kind == GEOM_RMSD; }
 };
 
 struct vmd_script_ir_t {
@@ -475,6 +478,13 @@ struct PropState {
     DevBuf<float> d_mc, d_md;
     DevBuf<double> d_shape_partial;               // shape_weights, component 0: chunk sums of the batch (vmd_hip_shape)
     int shape_max_set = 0;                        // ... and the size of the largest context's set
+    // rmsd: the set's pose at trajectory frame 0 (3 doubles per entry of a), its constants (8 doubles per context), the
+    // kernels' workspace, the size of the largest context's set, and the trajectory (traj_id) the pose was built for
+    DevBuf<double> d_rmsd_pose, d_rmsd_const, d_rmsd_ws;
+    int rmsd_max_set = 0;
+    const void* rmsd_pose_inst = nullptr;
+    const void* rmsd_pose_fn = nullptr;
+    bool rmsd_pose_ready = false;
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh

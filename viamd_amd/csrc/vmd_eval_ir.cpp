@@ -21,6 +21,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         if (p.kind == PROP_RDF) w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
         else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
+        else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
         else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
         else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
                 * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
@@ -206,17 +207,45 @@ extern "C" bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const c
     return ir_add_shape(ir, names, P, idx, offsets);
 }
 
+// `name = rmsd(sel) [in <contexts>];`: one temporal property over a population of sets, validated like ir_add_geometry
+static bool ir_add_rmsd(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offs) {
+    if (!ir_name_ok(ir, name)) return false;
+    if (P == 0) return vmd_fail("rmsd population is empty");
+    if (!offs) return vmd_fail("rmsd set has no context offsets");
+    if (offs[0] != 0) return vmd_fail("context offsets must start at 0");
+    for (size_t c = 0; c < P; ++c)
+        if (offs[c + 1] <= offs[c]) return vmd_fail("rmsd context %zu has an empty set (offsets must increase)", c);
+    if (!idx_ok(idx, (size_t)offs[P], "rmsd set")) return false;
+    Property p;
+    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    p.dist_kind = GEOM_RMSD;
+    p.a.assign(idx, idx + offs[P]); p.aoff.assign(offs, offs + P + 1);
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
+extern "C" bool vmd_ir_add_rmsd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n) {
+    if (n > 0x7fffffff) return vmd_fail("rmsd set too large");
+    const int32_t off[2] = {0, (int32_t)n};
+    return ir_add_rmsd(ir, name, 1, idx, off);
+}
+
+extern "C" bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets) {
+    return ir_add_rmsd(ir, name, P, idx, offsets);
+}
+
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
 extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
     if (!ir || !name) return 0;
     for (const Property& p : ir->props) {
         if (p.name != name) continue;
-        if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape())) return 0;
+        if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape() && !p.is_rmsd())) return 0;
         const size_t P = p.aoff.size() - 1;
         if (context >= (int64_t)P) return 0;
         const size_t c0 = context < 0 ? 0 : (size_t)context, c1 = context < 0 ? P : (size_t)context + 1;
-        if (p.is_shape()) {     // shape_weights: the set of the context(s)
+        if (p.is_shape() || p.is_rmsd()) {     // shape_weights, rmsd: the set of the context(s)
             size_t n = 0;
             for (int32_t i = p.aoff[c0]; i < p.aoff[c1]; ++i) { if (out && n < cap) out[n] = p.a[(size_t)i]; n += 1; }
             return n;

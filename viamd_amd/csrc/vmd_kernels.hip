@@ -14,6 +14,7 @@
 //   distance*()                  -> k_distance_com / k_distance_minmax / k_distance_pair
 //   angle() / dihedral()         -> k_geom<3> / k_geom<4>
 //   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
+//   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
 //
 // Design notes (DESIGN.md has the long form):
 //  * wave64 everywhere; a wave is the unit of work in the pair kernel (private LDS histogram + private LDS
@@ -1956,8 +1957,10 @@ __global__ __launch_bounds__(256) void k_rdf_brute(vmd_brute_params_t p) {
 // ------------------------------------------------------------------------------------------------ K3: SDF alignment (fp64)
 
 // cyclic Jacobi on a symmetric 4x4 — identical operation order to oracle vo_jacobi4
-__device__ void vmd_jacobi4(double A[4][4], double V[4][4]) {
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+// (VEC = false: the eigenvalues alone - the same rotations of A, V untouched)
+template <bool VEC>
+__device__ void vmd_jacobi4_t(double A[4][4], double V[4][4]) {
+    if (VEC) for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 24; ++sweep) {
         double off = 0.0;
         for (int p = 0; p < 3; ++p) for (int q = p + 1; q < 4; ++q) off = off + fabs(A[p][q]);
@@ -1983,7 +1986,7 @@ __device__ void vmd_jacobi4(double A[4][4], double V[4][4]) {
                     A[q][k] = s * apk + c * aqk;
                 }
                 A[p][q] = 0.0; A[q][p] = 0.0;
-                for (int k = 0; k < 4; ++k) {
+                if (VEC) for (int k = 0; k < 4; ++k) {
                     const double vkp = V[k][p], vkq = V[k][q];
                     V[k][p] = c * vkp - s * vkq;
                     V[k][q] = s * vkp + c * vkq;
@@ -1993,8 +1996,10 @@ __device__ void vmd_jacobi4(double A[4][4], double V[4][4]) {
     }
 }
 
-__device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
-    double N[4][4], V[4][4];
+__device__ void vmd_jacobi4(double A[4][4], double V[4][4]) { vmd_jacobi4_t<true>(A, V); }
+
+// Horn's symmetric 4x4 matrix of a 3x3 correlation matrix S; its largest eigenvalue belongs to the quaternion of the best rotation
+__device__ __forceinline__ void vmd_horn_matrix(const double S[3][3], double N[4][4]) {
     N[0][0] = S[0][0] + S[1][1] + S[2][2];
     N[0][1] = S[1][2] - S[2][1];
     N[0][2] = S[2][0] - S[0][2];
@@ -2006,6 +2011,11 @@ __device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
     N[2][3] = S[1][2] + S[2][1];
     N[3][3] = S[2][2] - S[0][0] - S[1][1];
     for (int i = 0; i < 4; ++i) for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
+}
+
+__device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
+    double N[4][4], V[4][4];
+    vmd_horn_matrix(S, N);
     vmd_jacobi4(N, V);
     int best = 0;
     for (int i = 1; i < 4; ++i) if (N[i][i] > N[best][best]) best = i;
@@ -2927,6 +2937,317 @@ __global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_small(vmd_shape_param
     vmd_shape_values(s, p.lin[t], p.plan[t], p.iso[t]);
 }
 
+// ------------------------------------------------------------------------------------------------ K5d: rmsd
+
+// `name = rmsd(sel)`: the mass-weighted RMSD of a set after the best rigid fit onto its own pose at trajectory frame 0.  The set is made
+// whole along its index chain with INTEGER link shifts (n_a = -rint(frac(x_a - x_{a-1})), k_a = n_1 + ... + n_a: a prefix sum any order
+// of which gives the same result), the offsets e_a = (x_a - x_0) + cart(k_a) enter thirteen fp64 sums, and Horn's largest eigenvalue
+// gives the value without the rotation.  The reduction order is shape_weights' (DESIGN 1.4): a function of the set size alone.
+#define VMD_RMSD_CHUNK 4096
+#define VMD_RMSD_BLOCK 256
+#define VMD_RMSD_STEPS (VMD_RMSD_CHUNK / VMD_RMSD_BLOCK)
+#define VMD_RMSD_WAVE_SET 64       // a population whose largest set has at most this many atoms: one wave per set (k_rmsd_small)
+#define VMD_RMSD_GROUP 2           // atoms a thread takes per step of k_rmsd_moments (loads first, one barrier per step)
+#define VMD_RMSD_NSUM 14           // S1 x y z, G, C xx xy xz yx yy yz zx zy zz (C_ij = sum (w e_i) u_j), W (the pose pass only)
+#define VMD_RMSD_NCONST 8          // the pose's constants per context: W, U1 x y z, Gu (three unused)
+
+struct vmd_rmsd_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* set; const float* mass; const int32_t* off; int P;   // context c: set[off[c] .. off[c+1]), masses parallel to set
+    int nchunk;         // chunks of the largest set
+    int32_t* shift;     // [B][P][nchunk][4]: the chunk's total link shift x y z (one unused)
+    double* partial;    // [B][P][nchunk][VMD_RMSD_NSUM]
+    double* pose;       // [off[P]][3]: u_a, parallel to set (written by the pose pass, read by the frame pass)
+    double* cst;        // [P][VMD_RMSD_NCONST]
+    int zero_row;       // the row of this batch that is trajectory frame 0 (its value is +0 by definition), or -1
+    float* out;         // [B][P]
+};
+
+struct vmd_rmsd_box_t { bool px, py, pz, tri; double Lx, Ly, Lz, iLx, iLy, iLz, xy, xz, yz; };
+__device__ __forceinline__ vmd_rmsd_box_t vmd_rmsd_box(const float* boxes, int b, uint32_t pbc) {
+    const vmd_box_t bx = vmd_load_box(boxes, b, pbc);
+    vmd_rmsd_box_t s;
+    s.Lx = (double)bx.Lx; s.Ly = (double)bx.Ly; s.Lz = (double)bx.Lz;
+    s.xy = (double)bx.xy; s.xz = (double)bx.xz; s.yz = (double)bx.yz;
+    s.tri = bx.tri;
+    s.px = bx.px && s.Lx > 0.0; s.py = bx.py && s.Ly > 0.0; s.pz = bx.pz && s.Lz > 0.0;
+    s.iLx = 1.0 / s.Lx; s.iLy = 1.0 / s.Ly; s.iLz = 1.0 / s.Lz;
+    return s;
+}
+// -rint(d / L) as an integer.  Only the integer is needed, so the quotient is formed through 1 / L unless that could round to the other
+// side of a half-integer (vmd_shape_round_sure); then the division itself decides.
+__device__ __forceinline__ int vmd_rmsd_axis_shift(double d, double L, double iL) {
+    const double q = d * iL;
+    double r = rint(q);
+    if (__builtin_expect(!vmd_shape_round_sure(q, r), 0)) r = rint(d / L);
+    return -(int)r;
+}
+// the lattice vector k in Cartesian components, in this written-out order
+__device__ __forceinline__ void vmd_rmsd_cart(const vmd_rmsd_box_t& b, int kx, int ky, int kz, double& cx, double& cy, double& cz) {
+    const double fx = (double)kx, fy = (double)ky, fz = (double)kz;
+    if (b.tri) {
+        cx = (fx * b.Lx + b.xy * fy) + b.xz * fz;
+        cy = fy * b.Ly + b.yz * fz;
+        cz = fz * b.Lz;
+    } else { cx = fx * b.Lx; cy = fy * b.Ly; cz = fz * b.Lz; }
+}
+
+// Atom a of the set and its predecessor in the chain, loaded together (all loads of a step stand before its first branch, as in
+// k_shape_moments).  An atom past the end is read as atom 0 with weight 0; atom 0 is its own predecessor: both have link shift 0.
+struct vmd_rmsd_atom_t { float x, y, z, qx, qy, qz, w; };
+__device__ __forceinline__ vmd_rmsd_atom_t vmd_rmsd_load(const float* fx, const float* fy, const float* fz, const int32_t* set,
+                                                         const float* mass, int a, int n) {
+    const bool live = a < n;
+    const int aa = live ? a : 0;
+    const int pa = aa > 0 ? aa - 1 : 0;
+    const int i = set[aa], j = set[pa];
+    vmd_rmsd_atom_t q;
+    q.x = fx[i]; q.y = fy[i]; q.z = fz[i];
+    q.qx = fx[j]; q.qy = fy[j]; q.qz = fz[j];
+    const float m = mass[aa];
+    q.w = live ? m : 0.0f;
+    return q;
+}
+__device__ __forceinline__ void vmd_rmsd_link(const vmd_rmsd_atom_t& q, const vmd_rmsd_box_t& b, int& nx, int& ny, int& nz) {
+    const double dx = (double)q.x - (double)q.qx, dy = (double)q.y - (double)q.qy, dz = (double)q.z - (double)q.qz;
+    if (b.tri) {
+        const double sz = dz / b.Lz;
+        const double sy = (dy - b.yz * sz) / b.Ly;
+        const double sx = ((dx - b.xy * sy) - b.xz * sz) / b.Lx;
+        nx = -(int)rint(sx); ny = -(int)rint(sy); nz = -(int)rint(sz);
+        return;
+    }
+    nx = b.px ? vmd_rmsd_axis_shift(dx, b.Lx, b.iLx) : 0;
+    ny = b.py ? vmd_rmsd_axis_shift(dy, b.Ly, b.iLy) : 0;
+    nz = b.pz ? vmd_rmsd_axis_shift(dz, b.Lz, b.iLz) : 0;
+}
+
+__device__ __forceinline__ int vmd_shfl_xor_i32(int v, int o) { return __float_as_int(__shfl_xor(__int_as_float(v), o)); }
+// inclusive prefix sum over the 64 lanes of a wave and the wave's total, by the xor butterfly (integers: the order does not matter)
+__device__ __forceinline__ void vmd_wave_scan_i32(int v, int lane, int& incl, int& total) {
+    incl = v; total = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = vmd_shfl_xor_i32(total, o);
+        if (lane & o) incl += t;
+        total += t;
+    }
+}
+
+// the sums of one atom: k = its accumulated shift, u = its pose offset (frame pass) / where its pose offset goes (pose pass, live atoms)
+template <bool POSE>
+__device__ __forceinline__ void vmd_rmsd_add(const vmd_rmsd_atom_t& q, const vmd_rmsd_box_t& b, double x0, double y0, double z0,
+                                             int kx, int ky, int kz, const double u[3], double* pose_out, double s[VMD_RMSD_NSUM]) {
+    const double w = (double)q.w;
+    double cx, cy, cz;
+    vmd_rmsd_cart(b, kx, ky, kz, cx, cy, cz);
+    const double ex = ((double)q.x - x0) + cx, ey = ((double)q.y - y0) + cy, ez = ((double)q.z - z0) + cz;
+    const double wx = w * ex, wy = w * ey, wz = w * ez;
+    s[0] = s[0] + wx; s[1] = s[1] + wy; s[2] = s[2] + wz;
+    s[3] = s[3] + ((wx * ex + wy * ey) + wz * ez);
+    if (POSE) {
+        s[13] = s[13] + w;
+        if (pose_out) { pose_out[0] = ex; pose_out[1] = ey; pose_out[2] = ez; }
+    } else {
+        s[4] = s[4] + wx * u[0]; s[5] = s[5] + wx * u[1]; s[6] = s[6] + wx * u[2];
+        s[7] = s[7] + wy * u[0]; s[8] = s[8] + wy * u[1]; s[9] = s[9] + wy * u[2];
+        s[10] = s[10] + wz * u[0]; s[11] = s[11] + wz * u[1]; s[12] = s[12] + wz * u[2];
+    }
+}
+
+__device__ __forceinline__ void vmd_rmsd_wave_sum(double s[VMD_RMSD_NSUM]) {
+#pragma unroll
+    for (int k = 0; k < VMD_RMSD_NSUM; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] = s[k] + vmd_shfl_xor_f64(s[k], o);
+}
+
+// the value from the thirteen sums and the pose's constants: Horn's largest eigenvalue, no rotation matrix
+__device__ float vmd_rmsd_value(const double s[VMD_RMSD_NSUM], const double* cst, int n) {
+    const double W = cst[0];
+    if (n <= 1 || W == 0.0) return 0.0f;                    // D-RMSD-DEGENERATE
+    const double U1[3] = {cst[1], cst[2], cst[3]}, Gu = cst[4];
+    const double Gp = s[3] - ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]) / W;
+    const double Gq = Gu - ((U1[0] * U1[0] + U1[1] * U1[1]) + U1[2] * U1[2]) / W;
+    double S[3][3], N[4][4];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = s[4 + 3 * i + j] - (s[i] * U1[j]) / W;
+    vmd_horn_matrix(S, N);
+    vmd_jacobi4_t<false>(N, nullptr);                        // vmd_jacobi4's rotations; the eigenvectors are not needed
+    double lam = N[0][0];
+    for (int i = 1; i < 4; ++i) if (N[i][i] > lam) lam = N[i][i];
+    double msd = ((Gp + Gq) - 2.0 * lam) / W;
+    msd = msd < 0.0 ? 0.0 : msd;                            // a rigid copy rounds to -1e-13
+    return (float)sqrt(msd);
+}
+
+// one block per (frame, context, chunk): the chunk's total link shift, the link to the previous chunk's last atom included
+__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_shift(vmd_rmsd_params_t p) {
+    __shared__ int s_w[VMD_RMSD_BLOCK / 64][3];
+    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
+    const int b = bc / p.P, c = bc - b * p.P;
+    const int k0 = p.off[c], n = p.off[c + 1] - k0;
+    const int a0 = chunk * VMD_RMSD_CHUNK;
+    if (a0 >= n) return;          // the whole block
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
+    const int32_t* set = p.set + k0;
+    const float* mass = p.mass + k0;
+    const int tid = threadIdx.x;
+    int sx = 0, sy = 0, sz = 0;
+#pragma unroll 1
+    for (int g = 0; g < VMD_RMSD_STEPS; g += 4) {
+        vmd_rmsd_atom_t q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = vmd_rmsd_load(fx, fy, fz, set, mass, a0 + (g + u) * VMD_RMSD_BLOCK + tid, n);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            int nx, ny, nz;
+            vmd_rmsd_link(q[u], bx, nx, ny, nz);
+            sx += nx; sy += ny; sz += nz;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sx += vmd_shfl_xor_i32(sx, o); sy += vmd_shfl_xor_i32(sy, o); sz += vmd_shfl_xor_i32(sz, o); }
+    if ((tid & 63) == 0) { s_w[tid >> 6][0] = sx; s_w[tid >> 6][1] = sy; s_w[tid >> 6][2] = sz; }
+    __syncthreads();
+    if (tid < 3) p.shift[(size_t)blockIdx.x * 4 + tid] = ((s_w[0][tid] + s_w[1][tid]) + s_w[2][tid]) + s_w[3][tid];
+}
+
+// one block per (frame, context, chunk): carry-in from the earlier chunks' totals, the in-chunk prefix sum of the link shifts (a wave
+// scan per step, the waves and steps joined through LDS), the sums per thread in registers, wave butterfly, the four waves through LDS.
+// POSE: the same over trajectory frame 0 - stores u_a and sums W instead of C.
+template <bool POSE>
+__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_moments(vmd_rmsd_params_t p) {
+    __shared__ int s_tot[VMD_RMSD_STEPS][VMD_RMSD_BLOCK / 64][3];
+    __shared__ double s_wave[VMD_RMSD_BLOCK / 64][VMD_RMSD_NSUM];
+    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
+    const int b = bc / p.P, c = bc - b * p.P;
+    const int k0 = p.off[c], n = p.off[c + 1] - k0;
+    const int a0 = chunk * VMD_RMSD_CHUNK;
+    if (a0 >= n) return;          // the whole block: a context with fewer chunks than the largest set
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
+    const int32_t* set = p.set + k0;
+    const float* mass = p.mass + k0;
+    double* pose = p.pose + (size_t)k0 * 3;
+    const int i0 = set[0];
+    const double x0 = (double)fx[i0], y0 = (double)fy[i0], z0 = (double)fz[i0];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the shift of every atom in front of the current step
+    int rx = 0, ry = 0, rz = 0;
+    const int32_t* sh = p.shift + (size_t)bc * p.nchunk * 4;
+    for (int ch = 0; ch < chunk; ++ch) { rx += sh[4 * ch + 0]; ry += sh[4 * ch + 1]; rz += sh[4 * ch + 2]; }
+    double s[VMD_RMSD_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // VMD_RMSD_GROUP atoms per step: their loads first, the link shifts and their wave scans, one barrier, then the sums in atom order
+#pragma unroll 1
+    for (int g = 0; g < VMD_RMSD_STEPS; g += VMD_RMSD_GROUP) {
+        vmd_rmsd_atom_t q[VMD_RMSD_GROUP];
+        double u[VMD_RMSD_GROUP][3];
+        int ix[VMD_RMSD_GROUP], iy[VMD_RMSD_GROUP], iz[VMD_RMSD_GROUP];
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+            const int a = a0 + (g + k) * VMD_RMSD_BLOCK + tid;
+            q[k] = vmd_rmsd_load(fx, fy, fz, set, mass, a, n);
+            const int aa = a < n ? a : 0;
+            if (!POSE) { u[k][0] = pose[3 * aa + 0]; u[k][1] = pose[3 * aa + 1]; u[k][2] = pose[3 * aa + 2]; }
+            else { u[k][0] = 0.0; u[k][1] = 0.0; u[k][2] = 0.0; }
+        }
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+            int nx, ny, nz, tx, ty, tz;
+            vmd_rmsd_link(q[k], bx, nx, ny, nz);
+            // a molecule that is whole in the cell has no shift along most of its chain: a wave without any skips its three scans
+            if (__ballot((nx | ny | nz) != 0) == 0ull) { ix[k] = iy[k] = iz[k] = tx = ty = tz = 0; }
+            else {
+                vmd_wave_scan_i32(nx, lane, ix[k], tx);
+                vmd_wave_scan_i32(ny, lane, iy[k], ty);
+                vmd_wave_scan_i32(nz, lane, iz[k], tz);
+            }
+            if (lane == 0) { s_tot[g + k][wave][0] = tx; s_tot[g + k][wave][1] = ty; s_tot[g + k][wave][2] = tz; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+            int kx = rx + ix[k], ky = ry + iy[k], kz = rz + iz[k];
+#pragma unroll
+            for (int w = 0; w < VMD_RMSD_BLOCK / 64; ++w) {
+                const int tx = s_tot[g + k][w][0], ty = s_tot[g + k][w][1], tz = s_tot[g + k][w][2];
+                if (w < wave) { kx += tx; ky += ty; kz += tz; }
+                rx += tx; ry += ty; rz += tz;
+            }
+            const int a = a0 + (g + k) * VMD_RMSD_BLOCK + tid;
+            vmd_rmsd_add<POSE>(q[k], bx, x0, y0, z0, kx, ky, kz, u[k], (POSE && a < n) ? pose + 3 * (size_t)a : nullptr, s);
+        }
+    }
+    vmd_rmsd_wave_sum(s);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_NSUM; ++k) s_wave[wave][k] = s[k];
+    __syncthreads();
+    if (tid < VMD_RMSD_NSUM)
+        p.partial[(size_t)blockIdx.x * VMD_RMSD_NSUM + tid] = ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid];
+}
+
+// one thread per (frame, context): the chunk sums in chunk order, then the value (POSE: the constants of the context)
+template <bool POSE>
+__global__ __launch_bounds__(64) void k_rmsd_finish(vmd_rmsd_params_t p) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.B * p.P) return;
+    const int b = t / p.P, c = t - b * p.P;
+    const int n = p.off[c + 1] - p.off[c];
+    const int nch = (n + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK;
+    const double* q = p.partial + (size_t)t * p.nchunk * VMD_RMSD_NSUM;
+    double s[VMD_RMSD_NSUM];
+#pragma unroll
+    for (int k = 0; k < VMD_RMSD_NSUM; ++k) s[k] = q[k];
+    for (int ch = 1; ch < nch; ++ch)
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_NSUM; ++k) s[k] = s[k] + q[ch * VMD_RMSD_NSUM + k];
+    double* cst = p.cst + (size_t)c * VMD_RMSD_NCONST;
+    if (POSE) { cst[0] = s[13]; cst[1] = s[0]; cst[2] = s[1]; cst[3] = s[2]; cst[4] = s[3]; }
+    else p.out[t] = b == p.zero_row ? 0.0f : vmd_rmsd_value(s, cst, n);
+}
+
+// populations of small sets (`rmsd(all) in residue(:)`): one wave per (frame, context), lane j holds atom j; the same sums in the same
+// order as the block form gives for such a set (one chunk, one atom per thread, three empty waves), without shifts in memory.  The sums go
+// to the partials (one "chunk" per set) and k_rmsd_finish forms the values, 64 sets per wave: a Jacobi iteration in lane 0 of every
+// wave kept the other 63 lanes waiting (1.97 ms per 200 000 sets against 0.3 ms this way)
+template <bool POSE>
+__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_small(vmd_rmsd_params_t p) {
+    const int t = blockIdx.x * (VMD_RMSD_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= p.B * p.P) return;   // the whole wave
+    const int b = t / p.P, c = t - b * p.P;
+    const int k0 = p.off[c], n = p.off[c + 1] - k0;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
+    const int32_t* set = p.set + k0;
+    double* pose = p.pose + (size_t)k0 * 3;
+    const int i0 = set[0];
+    const double x0 = (double)fx[i0], y0 = (double)fy[i0], z0 = (double)fz[i0];
+    const vmd_rmsd_atom_t q = vmd_rmsd_load(fx, fy, fz, set, p.mass + k0, lane, n);
+    const int aa = lane < n ? lane : 0;
+    double u[3] = {0.0, 0.0, 0.0};
+    if (!POSE) { u[0] = pose[3 * aa + 0]; u[1] = pose[3 * aa + 1]; u[2] = pose[3 * aa + 2]; }
+    int nx, ny, nz, kx, ky, kz, tx, ty, tz;
+    vmd_rmsd_link(q, bx, nx, ny, nz);
+    vmd_wave_scan_i32(nx, lane, kx, tx);
+    vmd_wave_scan_i32(ny, lane, ky, ty);
+    vmd_wave_scan_i32(nz, lane, kz, tz);
+    double s[VMD_RMSD_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    vmd_rmsd_add<POSE>(q, bx, x0, y0, z0, kx, ky, kz, u, (POSE && lane < n) ? pose + 3 * (size_t)lane : nullptr, s);
+    vmd_rmsd_wave_sum(s);
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < VMD_RMSD_NSUM; ++k) p.partial[(size_t)t * VMD_RMSD_NSUM + k] = ((s[k] + 0.0) + 0.0) + 0.0;
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -3380,6 +3701,69 @@ extern "C" int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride
     hipLaunchKernelGGL(k_shape_finish, dim3((unsigned)(((long long)B * P + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" size_t vmd_hip_rmsd_workspace_bytes(int B, int P, int max_set) {
+    if (B <= 0 || P <= 0 || max_set <= 0) return 0;
+    if (max_set <= VMD_RMSD_WAVE_SET) return (size_t)B * (size_t)P * VMD_RMSD_NSUM * sizeof(double);      // one wave per set: the sums only
+    const size_t blocks = (size_t)B * (size_t)P * (size_t)((max_set + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK);
+    return blocks * (VMD_RMSD_NSUM * sizeof(double) + 4 * sizeof(int32_t));
+}
+
+// both passes: pose = true runs the kernels' POSE forms over one frame
+static int vmd_rmsd_launch(bool pose_pass, hipStream_t stream, vmd_rmsd_params_t p, int max_set, void* workspace) {
+    const long long BP = (long long)p.B * p.P;
+    p.nchunk = (max_set + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK;
+    if (!workspace || BP * p.nchunk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    p.partial = (double*)workspace;
+    const dim3 rows((unsigned)((BP + 63) / 64));
+    if (max_set <= VMD_RMSD_WAVE_SET) {
+        const int per = VMD_RMSD_BLOCK / 64;
+        const dim3 grid((unsigned)((BP + per - 1) / per));
+        if (pose_pass) hipLaunchKernelGGL(k_rmsd_small<true>, grid, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+        else hipLaunchKernelGGL(k_rmsd_small<false>, grid, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+        VMD_LAUNCH_CHECK();
+        if (pose_pass) hipLaunchKernelGGL(k_rmsd_finish<true>, rows, dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(k_rmsd_finish<false>, rows, dim3(64), 0, stream, p);
+        VMD_LAUNCH_CHECK();
+        return 0;
+    }
+    p.shift = (int32_t*)((char*)workspace + (size_t)(BP * p.nchunk) * VMD_RMSD_NSUM * sizeof(double));
+    const dim3 blocks((unsigned)(BP * p.nchunk));
+    hipLaunchKernelGGL(k_rmsd_shift, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+    VMD_LAUNCH_CHECK();
+    if (pose_pass) hipLaunchKernelGGL(k_rmsd_moments<true>, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+    else hipLaunchKernelGGL(k_rmsd_moments<false>, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+    VMD_LAUNCH_CHECK();
+    if (pose_pass) hipLaunchKernelGGL(k_rmsd_finish<true>, rows, dim3(64), 0, stream, p);
+    else hipLaunchKernelGGL(k_rmsd_finish<false>, rows, dim3(64), 0, stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_rmsd_pose(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, int P,
+                                 const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                                 void* workspace, double* pose, double* consts) {
+    if (P <= 0) return 0;
+    if (!xyz || !set || !mass || !offsets || !pose || !consts || max_set <= 0) return (int)hipErrorInvalidValue;
+    vmd_rmsd_params_t p{};
+    p.xyz = xyz; p.frame_stride = 0; p.row_stride = row_stride; p.boxes = box; p.pbc = pbc_flags; p.B = 1; p.P = P;
+    p.set = set; p.mass = mass; p.off = offsets; p.pose = pose; p.cst = consts; p.zero_row = -1;
+    return vmd_rmsd_launch(true, (hipStream_t)stream, p, max_set, workspace);
+}
+
+extern "C" int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                            const float* boxes, uint32_t pbc_flags, int B, int P,
+                            const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                            const double* pose, const double* consts, int zero_row, void* workspace, float* out) {
+    if (B <= 0 || P <= 0) return 0;
+    if (!xyz || !set || !mass || !offsets || !pose || !consts || !out || max_set <= 0 || (long long)B * P > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    vmd_rmsd_params_t p{};
+    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
+    p.set = set; p.mass = mass; p.off = offsets; p.pose = const_cast<double*>(pose); p.cst = const_cast<double*>(consts);
+    p.zero_row = zero_row; p.out = out;
+    return vmd_rmsd_launch(false, (hipStream_t)stream, p, max_set, workspace);
 }
 
 extern "C" int vmd_hip_bbox(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, int B, int natoms, float* out) {

@@ -337,7 +337,7 @@ struct Report {
 // `{lin,plan,iso} = shape_weights(all);` of VIAMD's default script (src/main.cpp:528).  A later statement that uses an identifier of a
 // skipped one is skipped with it ("unknown identifier").
 // features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
-// `{lin, plan, iso} = shape_weights(sel)` (opt-in; 0 = the subset above, byte for byte)
+// `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)` (opt-in; 0 = the subset above, byte for byte)
 void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
@@ -390,6 +390,8 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                 p.take("}");
                 p.take("=");
                 const Token& f = p.peek();
+                if ((features & VMD_SCRIPT_FEATURE_RMSD) && f.kind == T_ID && f.text == "rmsd")
+                    fail("%s: rmsd defines one property, not a tuple", names.c_str());
                 if (!((features & VMD_SCRIPT_FEATURE_SHAPE) && f.kind == T_ID && f.text == "shape_weights"))
                     fail("unsupported %s '%s' (outside the rdf / sdf / distance path)", f.kind == T_ID ? "function" : "expression", f.text.c_str());
                 // `{lin, plan, iso} = shape_weights(sel) [in <contexts>];`: the one function of the subset that defines a tuple
@@ -444,7 +446,8 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                 fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not 1", name.c_str());
             const bool is_func = k.kind == T_ID && (k.text == "rdf" || k.text == "sdf" || k.text == "distance" || k.text == "distance_min" ||
                                                     k.text == "distance_max" || k.text == "distance_pair" ||
-                                                    ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")));
+                                                    ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")) ||
+                                                    ((features & VMD_SCRIPT_FEATURE_RMSD) && k.text == "rmsd"));
             if (is_func) {
                 is_property = true;
                 const std::string v = k.text;
@@ -479,6 +482,41 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                     const auto tg = tgt.indices();
                     const size_t K = structs.size();
                     commit = [=]() { if (!vmd_ir_add_sdf(ir, name.c_str(), flat.data(), K, m, tg.data(), tg.size(), (float)cutoff)) throw ScriptError(vmd_last_error()); };
+                } else if (v == "rmsd") {
+                    // `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context rules of distance()
+                    const size_t start = p.i;
+                    size_t j = p.i;
+                    int depth = 1;
+                    while (depth) {
+                        if (j >= toks.size()) fail("%s: missing ')'", name.c_str());
+                        if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
+                        if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
+                        ++j;
+                    }
+                    std::vector<int32_t> all, off{0};
+                    auto one_set = [&](Parser& r, const char* where) {
+                        const std::vector<int32_t> ix = r.sel_or().indices();
+                        if (r.is_word(",")) fail("%s: rmsd takes one selection", name.c_str());
+                        r.take(")");
+                        if (ix.empty()) fail("%s: empty selection%s", name.c_str(), where);
+                        all.insert(all.end(), ix.begin(), ix.end());
+                        off.push_back((int32_t)all.size());
+                    };
+                    if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
+                        Parser q(toks, topo, env);
+                        q.i = j + 1;
+                        const Sel ctx = q.sel_or();
+                        if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", name.c_str());
+                        for (auto& st : ctx.structs) {
+                            Parser r(toks, topo, env, &st);
+                            r.i = start;
+                            one_set(r, " inside a context");
+                        }
+                        p.i = q.i;
+                    } else one_set(p, "");
+                    commit = [=]() {
+                        if (!vmd_ir_add_rmsd_population(ir, name.c_str(), off.size() - 1, all.data(), off.data())) throw ScriptError(vmd_last_error());
+                    };
                 } else {
                     // the arguments may be followed by `in <contexts>`: find the closing parenthesis first
                     const size_t start = p.i;

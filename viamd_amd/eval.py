@@ -150,6 +150,19 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_shape_weights_population(self.h, self._names3(names), len(sets), flat.ctypes.data_as(L.c_int32_p),
                                                                  off.ctypes.data_as(L.c_int32_p)))
 
+    def add_rmsd(self, name, idx):
+        """`name = rmsd(idx);`: the RMSD of one set from its pose at trajectory frame 0 after the best rigid fit."""
+        x, xp = _idx(idx)
+        self._check(self.lib.vmd_ir_add_rmsd(self.h, name.encode(), xp, x.size))
+
+    def add_rmsd_population(self, name, sets):
+        """`name = rmsd(sel) in <contexts>`: one index set per context -> dim[1] = number of contexts."""
+        assert len(sets) > 0
+        flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in sets]).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum([len(x) for x in sets])]).astype(np.int32)
+        self._check(self.lib.vmd_ir_add_rmsd_population(self.h, name.encode(), len(sets), flat.ctypes.data_as(L.c_int32_p),
+                                                        off.ctypes.data_as(L.c_int32_p)))
+
     @staticmethod
     def _names3(names):
         import ctypes as C
@@ -159,7 +172,7 @@ class ScriptIR:
 
     def geometry_atoms(self, name, context=-1):
         """the atoms of an angle / dihedral property (one context, or all when context < 0) in argument order, or the set of a
-        shape_weights property"""
+        shape_weights or rmsd property"""
         n = int(self.lib.vmd_ir_geometry_atoms(self.h, name.encode(), int(context), None, 0))
         out = np.zeros(n, np.int32)
         if n:

@@ -267,9 +267,10 @@ _DIST_KIND = {"distance": L.DIST_COM, "distance_min": L.DIST_MIN, "distance_max"
 _GEOM_NARGS = {"angle": 3, "dihedral": 4}       # opt-in (angles=True)
 FEATURE_ANGLES = 1                              # VMD_SCRIPT_FEATURE_ANGLES
 FEATURE_SHAPE = 2                               # VMD_SCRIPT_FEATURE_SHAPE
+FEATURE_RMSD = 4                                # VMD_SCRIPT_FEATURE_RMSD
 
 
-def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -281,7 +282,10 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
 
     shape=True (VMD_SCRIPT_FEATURE_SHAPE, opt-in): `{n0, n1, n2} = shape_weights(sel)`, plain or `in <contexts>`, defines three temporal
     properties, info[n] = dict(kind="shape_weights", component=0 | 1 | 2, sets=[one index array per context]); with both
-    opt-ins the default script compiles whole: d1, a1, r, v, lin, plan, iso, nothing skipped."""
+    opt-ins the default script compiles whole: d1, a1, r, v, lin, plan, iso, nothing skipped.
+
+    rmsd=True (VMD_SCRIPT_FEATURE_RMSD, opt-in): `name = rmsd(sel)`, plain or `in <contexts>`,
+    info[name] = dict(kind="rmsd", sets=[one index array per context])."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -314,6 +318,8 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("}")
                 p.take("=")
                 k, v = p.peek()
+                if rmsd and k == "id" and v == "rmsd":
+                    raise ScriptError(f"{names}: rmsd defines one property, not a tuple")
                 if not (shape and k == "id" and v == "shape_weights"):
                     raise ScriptError(f"unsupported {'function' if k == 'id' else 'expression'} {v!r} (outside the rdf / sdf / distance path)")
                 commit, is_property = _shape_statement(p, names, topo, env, ir, info), True
@@ -323,7 +329,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("=")
                 if shape and p.peek() == ("id", "shape_weights"):
                     raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles)
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -415,15 +421,57 @@ def _shape_statement(p, names, topo, env, ir, info):
     return commit
 
 
-def _statement(p, name, topo, env, ir, info, angles=False):
+def _rmsd_statement(p, name, topo, env, ir, info):
+    """`name = rmsd(sel) [in <contexts>]` behind the opening parenthesis (the twin of the rmsd branch of vmd_script.cpp)."""
+    start = p.i
+    j, depth = p.i, 1
+    while depth:
+        if j >= len(p.t):
+            raise ScriptError(f"{name}: missing ')'")
+        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
+        j += 1
+    sets = []
+
+    def one_set(r, where):
+        ix = r.sel_or().indices()
+        if r.peek() == ("op", ","):
+            raise ScriptError(f"{name}: rmsd takes one selection")
+        r.take(")")
+        if ix.size == 0:
+            raise ScriptError(f"{name}: empty selection{where}")
+        sets.append(ix)
+
+    if j < len(p.t) and p.t[j] == ("id", "in"):
+        q = _Parser(p.t, topo, env)
+        q.i = j + 1
+        ctx = q.sel_or()
+        if ctx.structures is None or not ctx.structures:
+            raise ScriptError(f"{name}: `in` needs an array of structures (residue(...), resname(...))")
+        for st in ctx.structures:
+            r = _Parser(p.t, topo, env, ctx=np.asarray(st))
+            r.i = start
+            one_set(r, " inside a context")
+        p.i = q.i
+    else:
+        one_set(p, "")
+
+    def commit():
+        ir.add_rmsd_population(name, sets)
+        info[name] = dict(kind="rmsd", sets=sets)
+    return commit
+
+
+def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
-    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS))):
+    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS) or (rmsd and v == "rmsd"))):
         sel = p.sel_or()
         return (lambda: env.__setitem__(name, sel)), False
     p.i += 1
     p.take("(")
+    if v == "rmsd":
+        return _rmsd_statement(p, name, topo, env, ir, info), True
     if v == "rdf":
         ref = p.sel_or(); p.take(",")
         tgt = p.sel_or(); p.take(",")
@@ -519,14 +567,14 @@ def _statement(p, name, topo, env, ir, info, angles=False):
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
-    VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE."""
+    VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
-    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0)
+    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
