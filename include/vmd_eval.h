@@ -236,8 +236,15 @@ bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const 
  * and a name that is already defined are errors (vmd_last_error). */
 bool vmd_ir_add_rmsd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n);
 bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets);
+/* `name = count(<T> and within(rmin:rmax, <R>));`: the population of a shell per frame - how many atoms of the target set have
+ * SOME atom of the reference set (itself included) at rmin <= d < rmax, d the pair distance rdf() bins (positions wrapped, SPEC S3 image).
+ * The scalar form within(r, R) is rmin = 0.  One temporal property, values[frame], dim = {num_frames, 1}, no unit.
+ * vmd_set_option("spec_within_closed", 1): d <= rmax; ("spec_within_exclude_ref", 1): atoms of R are dropped from T (read at eval creation).
+ * Empty sets, negative indices, a range that is not finite or not 0 <= rmin < rmax and a name already defined are errors. */
+bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
+                             const int32_t* ref, size_t nref, float rmin, float rmax);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
- * shape_weights or rmsd property: returns how many
+ * shape_weights or rmsd property, or the reference set followed by the target set of a within count: returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
@@ -287,10 +294,13 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
  * stays outside the subset).  With both, the default script compiles whole - d1, a1, r, v, lin, plan, iso - and the fallback source
  * keeps no property statement.
  * VMD_SCRIPT_FEATURE_RMSD also compiles `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context
- * rules of distance(). */
+ * rules of distance().
+ * VMD_SCRIPT_FEATURE_WITHIN also compiles `name = count(<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]);`: exactly
+ * one within() factor at the top level of the AND, every other factor and its argument a static selection. */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
 #define VMD_SCRIPT_FEATURE_SHAPE 2u
 #define VMD_SCRIPT_FEATURE_RMSD 4u
+#define VMD_SCRIPT_FEATURE_WITHIN 8u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -300,7 +310,7 @@ size_t   vmd_ir_property_count(const vmd_script_ir_t* ir);              /* md_sc
 const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir);    /* md_script_ir_property_names, src/main.cpp:1278 */
 vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name); /* src/main.cpp:1285 */
 /* atom pairs ONE frame of the script asks for (rdf |ref| x |target|, sdf K x (|target| + m), distance |a| x |b| per context, angle /
- * dihedral / shape_weights / rmsd: the atoms of every context's sets): the size a host
+ * dihedral / shape_weights / rmsd: the atoms of every context's sets, within count: |target| + |ref|): the size a host
  * compares with a threshold before it sends a small script to the GPU (vmd_shim_set_min_work; VIAMD's default dataset, src/main.cpp:522-528) */
 uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir);
 

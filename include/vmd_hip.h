@@ -17,6 +17,7 @@
  *   vmd_hip_geometry  <- angle / dihedral (DESIGN S6b)
  *   vmd_hip_shape     <- shape_weights
  *   vmd_hip_rmsd      <- rmsd
+ *   vmd_hip_within_*  <- count(sel and within(r, sel))
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -192,6 +193,24 @@ int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride, size_t row
                  const float* boxes, uint32_t pbc_flags, int B, int P,
                  const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
                  const double* pose, const double* consts, int zero_row, void* workspace, float* out);
+
+/* K6: count(T and within(rmin:rmax, R)), DESIGN 1.6: count_out u32[B] (zeroed by the call) = the atoms t of the target set for which SOME
+ * atom a of the reference set (a == t included) lies at rmin <= d(t, a) < rmax (closed != 0: <= rmax); positions wrapped (SPEC S2 / S3t),
+ * d the correctly rounded root of the SPEC S3 / S3t squared distance - the d the RDF kernels bin.  B <= 65535.
+ *   vmd_hip_within_brute   all pairs from the raw frame: any pbc_flags, any cutoff; tgt / ref: device index lists (NULL = 0..n-1)
+ *   vmd_hip_within_pencil  the cell walk over the cell-sorted copies of both sets (K1, same grid, same boxes and flags, the pencil reach set
+ *                          by vmd_hip_set_pencil_reach); the grid edge must be >= rmax as for vmd_hip_rdf_pencil.  Does nothing but the
+ *                          zeroing when *skip_flag != 0 (see vmd_hip_cells_build_pencil).
+ *   vmd_hip_within_to_float  out[b] = (float)counts[b] (does nothing when *skip_flag != 0) */
+int vmd_hip_within_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                         const float* boxes, uint32_t pbc_flags, int B,
+                         const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                         float rmin, float rmax, int closed, uint32_t* count_out);
+int vmd_hip_within_pencil(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+                          const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
+                          const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
+                          uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag);
+int vmd_hip_within_to_float(void* stream, const uint32_t* counts, int B, float* out, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

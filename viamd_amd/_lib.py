@@ -156,6 +156,7 @@ SIGNATURES = [
     ("vmd_ir_add_shape_weights_population", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.c_size_t, c_int32_p, c_int32_p]),
     ("vmd_ir_add_rmsd", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
     ("vmd_ir_add_rmsd_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
+    ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -331,6 +332,11 @@ SIGNATURES = [
     ("vmd_hip_rmsd_pose", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("vmd_hip_rmsd", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                _vp, _vp, C.c_int, _vp, _vp]),
+    ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                       C.c_float, C.c_float, C.c_int, _vp]),
+    ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,
+                                        C.c_float, C.c_float, C.c_int, C.c_uint32, _vp, _vp]),
+    ("vmd_hip_within_to_float", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     ("vmd_hip_add_u64", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("vmd_hip_counts_to_float", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_float]),
     ("vmd_hip_bump_u64", C.c_int, [_vp, _vp, C.c_uint64]),

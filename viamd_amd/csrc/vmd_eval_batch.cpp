@@ -125,6 +125,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     size_t per_frame = staged ? 12 * num_atoms : 0;
     std::vector<char> used(e->sels.size(), 0);
     for (auto& g : e->rdf_groups) for (auto& ps : g.passes) { used[ps.sel_a] = 1; used[ps.sel_b] = 1; }
+    for (int pi : e->within_props) { if (e->props[pi]->sel_a >= 0) used[e->props[pi]->sel_a] = 1; used[e->props[pi]->sel_b] = 1; }
     for (size_t i = 0; i < e->sels.size(); ++i) if (used[i]) per_frame += 40 * e->sels[i]->idx.size();
     for (auto& p : e->props) per_frame += p->prop.kind == PROP_SDF ? 64 * p->prop.K : (p->prop.kind == PROP_DIST ? 4 * p->dim1 : 0);
     // 288 GB of HBM: a 16 GB scratch budget holds the 1 000 frames of the 1M-atom RDF (333k selected atoms) in ONE batch
@@ -133,7 +134,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     // pair passes are long (a 1 024-frame batch of the 1M-atom RDF runs ~90 ms: interrupts are polled between batches); scripts
     // without them stream whole frames at HBM speed and take much larger batches, so that launches, the alignment kernel's
     // latency and the per-batch synchronisation stay small against the stream (grid.y = frames of the batch <= 65535)
-    const size_t cap = e->rdf_groups.empty() ? 16384 : 1024;
+    const size_t cap = (e->rdf_groups.empty() && e->within_props.empty()) ? 16384 : 1024;
     B = std::max<size_t>(1, std::min<size_t>(B, cap));
     return B;
 }
@@ -423,6 +424,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         bool active = false;        // queued, not completed
         bool poisoned = false;      // queued behind a batch that overflowed: its RDF part saw the flag and did nothing
         bool snapshot = false;      // h_snap[slot] holds the RDF counts behind this batch's commits (+ w_snap: the weights)
+        std::vector<size_t> within_toff;    // within counts: where each one's rows start in h_temporal_slot[slot]
     };
     BatchCtx ctx[2];
     const bool defer = g_opt.defer_sync.load() != 0 && e->block_frames == 0 && batches.size() > 1;
@@ -453,7 +455,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         for (auto& g : e->rdf_groups) scratch_rows += std::max(g.passes.size(), g.props.size());
         scratch_rows *= c.subs.size();
         if (!e->d_pass.ensure(std::max<size_t>(scratch_rows, 1) * VMD_RDF_NUM_BINS)) return false;
-        HIP_OK(hipMemsetAsync(e->d_pass.p, 0, scratch_rows * VMD_RDF_NUM_BINS * sizeof(uint64_t), e->stream));
+        if (scratch_rows) HIP_OK(hipMemsetAsync(e->d_pass.p, 0, scratch_rows * VMD_RDF_NUM_BINS * sizeof(uint64_t), e->stream));
         struct Commit { uint64_t* dst; const uint64_t* src; uint64_t mult; };
         std::vector<Commit> commits;
         size_t row = 0;
@@ -541,6 +543,52 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         if (forked) {
             HIP_OK(hipEventRecord(e->pair_join, e->pair_stream));
             HIP_OK(hipStreamWaitEvent(e->stream, e->pair_join, 0));
+        }
+        // ---- within counts: the same grids and cell-sorted copies (a selection an RDF pass of this batch sorted on the same
+        // grid is not sorted again), an any-reduction per target atom instead of a histogram.  Part of launch_rdf because a bucket overflow
+        // of ITS cell builds repeats the batch like any other; the rows travel to the host from here for the same reason.  Always wrapped
+        // positions (spec_rdf_raw does not apply); no grid -> all pairs from the raw frame.
+        for (size_t wi = 0; wi < e->within_props.size(); ++wi) {
+            PropState* p = e->props[e->within_props[wi]].get();
+            const Property& d = p->prop;
+            if (!p->d_out.ensure(c.nb) || !p->d_within_count.ensure(c.nb)) return false;
+            if (p->within_empty) {
+                HIP_OK(hipMemsetAsync(p->d_out.p, 0, c.nb * sizeof(float), e->stream));       // T minus R is empty: +0 in every frame
+            } else {
+                Selection* st = e->sels[p->sel_a].get();
+                Selection* sr = e->sels[p->sel_b].get();
+                vmd_grid_t grid;
+                const bool open_axes = (c.pbc & 8u) == 0 && (c.pbc & VMD_UNITCELL_PBC_ALL) != VMD_UNITCELL_PBC_ALL;
+                if (open_axes && !g_opt.force_brute && !prepare_open_boxes(e, *c.src, c.nb, c.pbc, num_atoms)) return false;
+                const std::vector<float>& gb = (open_axes && c.src->gboxes_ready) ? c.src->h_gboxes : c.src->h_boxes;
+                const float* d_gb = (open_axes && c.src->gboxes_ready) ? c.src->d_gboxes.p : c.src->d_boxes.p;
+                // the pencil split rule of the RDF groups, so that equal cutoffs over equal selections meet on equal grids
+                bool dense_lanes = !open_axes;
+                if (dense_lanes) {
+                    const float* q = gb.data();
+                    const double vol = (double)q[0] * q[1] * q[2];
+                    dense_lanes = vol > 0.0 && (double)std::max(st->idx.size(), sr->idx.size()) / vol >= 0.08;
+                }
+                if (choose_grid(gb, c.pbc, c.nb, d.rmax, &grid, dense_lanes)) {
+                    if (!build_selection(e, st, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+                    if (sr != st && !build_selection(e, sr, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+                    e->prof.begin("within_pencil", e->stream);
+                    KRN_OK(vmd_hip_within_pencil(e->stream, sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, st->sorted.p,
+                            st->cell_start.p, (int)st->idx.size(), st->nsel_pad, d_gb, (int)c.nb, grid, d.rmin, d.rmax,
+                            e->spec.within_closed ? 1 : 0, c.pbc, p->d_within_count.p, e->d_overflow.p));
+                    e->prof.end(e->stream);
+                    KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, e->d_overflow.p));
+                } else {
+                    e->prof.begin("within_brute", e->stream);
+                    KRN_OK(vmd_hip_within_brute(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                            (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), d.rmin, d.rmax,
+                            e->spec.within_closed ? 1 : 0, p->d_within_count.p));
+                    e->prof.end(e->stream);
+                    KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, nullptr));
+                }
+            }
+            HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.within_toff[wi], p->d_out.p, c.nb * sizeof(float),
+                    hipMemcpyDeviceToHost, e->stream));
         }
         for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
         HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -670,7 +718,15 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         c.two_streams = c.subs.size() > 1 && g_opt.block_two_streams.load() != 0;
 
         e->h_overflow[c.slot] = 0;
-        if (!e->rdf_groups.empty() && !launch_rdf(c)) return false;
+        if (!e->within_props.empty()) {
+            size_t off = 0;
+            for (auto& p : e->props) {
+                if (p->prop.kind != PROP_DIST) continue;
+                if (p->prop.is_within()) c.within_toff.push_back(off);
+                off += c.nb * p->dim1;
+            }
+        }
+        if ((!e->rdf_groups.empty() || !e->within_props.empty()) && !launch_rdf(c)) return false;
 
         for (auto& p : e->props) {
             const Property& d = p->prop;
@@ -718,6 +774,12 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 e->prof.end(e->stream);
                 p->dirty = p->dirty || !spec;
             } else {
+                if (d.is_within()) {
+                    // within count: computed and sent on its way by launch_rdf above, behind the batch's cell builds
+                    toff += c.nb * p->dim1;
+                    p->dirty = p->dirty || !spec;
+                    continue;
+                }
                 if (!p->d_out.ensure(c.nb * p->dim1)) return false;
                 if (d.is_shape()) {
                     // shape_weights: the statement's three descriptors stand in a row; the first one computes all three

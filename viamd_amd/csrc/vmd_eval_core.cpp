@@ -145,6 +145,26 @@ void build_rdf_plan(vmd_script_eval_t* e) {
     }
 }
 
+// within counts: the target and reference sets become interned selections - shared with the RDF properties of the script -
+// so that a cell-sorted copy one of them built on the same grid in a batch is not built again.  D-WITHIN-SELF flipped: T minus R, formed here
+void build_within_plan(vmd_script_eval_t* e) {
+    e->within_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        if (!p->prop.is_within()) continue;
+        std::vector<int32_t> tgt = p->prop.a;
+        if (e->spec.within_exclude_ref) {
+            std::vector<int32_t> ref = p->prop.b;
+            std::sort(ref.begin(), ref.end());
+            tgt.erase(std::remove_if(tgt.begin(), tgt.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), tgt.end());
+        }
+        p->within_empty = tgt.empty();
+        p->sel_a = p->within_empty ? -1 : intern_selection(e, tgt);
+        p->sel_b = intern_selection(e, p->prop.b);
+        e->within_props.push_back((int)i);
+    }
+}
+
 extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_script_ir_t* ir) {
     if (!ir) { vmd_fail("vmd_eval_create: ir is NULL"); return nullptr; }
     if (vmd_device_count() <= 0) { vmd_fail("vmd_eval_create: no usable HIP device (the evaluator has no CPU path)"); return nullptr; }
@@ -168,6 +188,8 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     e->spec.rdf_norm = g_opt.spec_rdf_norm.load();
     e->spec.dist_geometric_com = g_opt.spec_dist_geometric_com.load() != 0;
     e->spec.angle_radians = g_opt.spec_angle_radians.load() != 0;
+    e->spec.within_closed = g_opt.spec_within_closed.load() != 0;
+    e->spec.within_exclude_ref = g_opt.spec_within_exclude_ref.load() != 0;
     e->frame_mask.assign(num_frames, 0);
     for (auto& p : ir->props) {
         auto st = std::make_unique<PropState>();
@@ -210,6 +232,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             }
             if (p.is_rmsd())                                                                      // Angstrom, as distance
                 for (size_t c = 0; c < st->dist_P; ++c) st->rmsd_max_set = std::max(st->rmsd_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
+            if (p.is_within()) st->data.unit_str[1] = "";                                         // a count
             if (st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;
@@ -232,6 +255,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         e->props.push_back(std::move(st));
     }
     build_rdf_plan(e.get());
+    build_within_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
                 return nullptr; }

@@ -122,6 +122,8 @@ struct Options {
     std::atomic<int> spec_angle_radians{0};       // D-ANGLE-UNIT: angle() / dihedral() in radians, not degrees (DESIGN S6b)
     // D-WRAP: positions enter rdf() as they are, minimum image by rounding - evaluated by k_rdf_brute (all pairs: a
     std::atomic<int> spec_rdf_raw{0};
+    std::atomic<int> spec_within_closed{0};        // DECISION(D-WITHIN-INTERVAL) flipped: hit iff r_min <= d <= r_max
+    std::atomic<int> spec_within_exclude_ref{0};   // DECISION(D-WITHIN-SELF) flipped: the evaluator counts over T minus R
                                                   // setting for matching an mdlib that does it this way, not a fast path)
     // D-RDF-NORM: 0 = cell volume when fully periodic, else the cutoff sphere; 1 = always the cutoff sphere;
     std::atomic<int> spec_rdf_norm{0};
@@ -355,6 +357,9 @@ enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
 enum { GEOM_SHAPE = 6 };
 // `name = rmsd(sel)`: one PROP_DIST descriptor that carries the set (a / aoff); the evaluator keeps the frame-0 pose of the set
 enum { GEOM_RMSD = 7 };
+// `name = count(T and within(rmin:rmax, R))`: one PROP_DIST descriptor, a = T, b = R, the range in rmin / rmax; one value per
+// frame, the number of atoms of T with an atom of R in range
+enum { GEOM_WITHIN = 8 };
 
 struct Property {
     std::string name;
@@ -370,6 +375,7 @@ struct Property {
     int shape_comp = 0;             // shape_weights: 0 = linear, 1 = planar, 2 = isotropic
     bool is_shape() const { return kind == PROP_DIST && dist_kind == GEOM_SHAPE; }
     bool is_rmsd() const { return kind == PROP_DIST && dist_kind == GEOM_RMSD; }
+    bool is_within() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN; }
 };
 
 struct vmd_script_ir_t {
@@ -485,6 +491,10 @@ struct PropState {
     const void* rmsd_pose_inst = nullptr;
     const void* rmsd_pose_fn = nullptr;
     bool rmsd_pose_ready = false;
+    // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
+    // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
+    DevBuf<uint32_t> d_within_count;
+    bool within_empty = false;
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh
@@ -683,6 +693,7 @@ struct vmd_script_eval_t {
     hipStream_t pair_stream = nullptr;       // every other block of a batch of frame blocks runs its pair kernel here
     hipEvent_t pair_fork = nullptr, pair_join = nullptr;
     std::vector<RdfGroup> rdf_groups;
+    std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;
     DevBuf<uint32_t> d_overflow;             // device flag raised by the two-level cell build when a pencil bucket is full
@@ -760,7 +771,7 @@ struct vmd_script_eval_t {
     vmd_reduce_stats_t reduce_stats = {};
     // fixed at creation
     struct Spec { bool rdf_closed = false, sdf_include_self = false, sdf_density = false, dist_geometric_com = false, rdf_raw = false;
-            int rdf_norm = 0; bool angle_radians = false; } spec;
+            int rdf_norm = 0; bool angle_radians = false; bool within_closed = false, within_exclude_ref = false; } spec;
     size_t atoms_checked = (size_t)-1;       // trajectory atom count the properties' indices were validated against (under mtx)
 };
 
@@ -773,6 +784,7 @@ PropState* find_prop(const vmd_script_eval_t* e, const char* name);
 int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx);
 
 void build_rdf_plan(vmd_script_eval_t* e);
+void build_within_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
 

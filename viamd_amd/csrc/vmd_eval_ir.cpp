@@ -22,6 +22,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
+        else if (p.is_within()) w += (uint64_t)p.a.size() + (uint64_t)p.b.size();        // |T| + |R|: a neighbour query, not all pairs
         else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
         else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
                 * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
@@ -235,12 +236,36 @@ extern "C" bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name
     return ir_add_rmsd(ir, name, P, idx, offsets);
 }
 
+// `name = count(T and within(rmin:rmax, R));`: one temporal property, one value per frame; validated like ir_add_geometry
+extern "C" bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
+                                        const int32_t* ref, size_t nref, float rmin, float rmax) {
+    if (!ir_name_ok(ir, name) || !idx_ok(target, ntarget, "within target set") || !idx_ok(ref, nref, "within reference set")) return false;
+    if (ntarget > 0x7fffffff || nref > 0x7fffffff) return vmd_fail("within set too large");
+    if (!std::isfinite(rmin) || !std::isfinite(rmax) || !(rmin >= 0.0f) || !(rmax > rmin))
+        return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
+    Property p;
+    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    p.dist_kind = GEOM_WITHIN;
+    p.a.assign(target, target + ntarget); p.b.assign(ref, ref + nref);
+    p.aoff = {0, (int32_t)ntarget}; p.boff = {0, (int32_t)nref};
+    p.rmin = rmin; p.rmax = rmax;
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
 extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
     if (!ir || !name) return 0;
     for (const Property& p : ir->props) {
         if (p.name != name) continue;
+        if (p.is_within()) {     // the static candidates: the reference set, then the target set (one context)
+            if (context > 0) return 0;
+            size_t n = 0;
+            for (const auto* v : {&p.b, &p.a}) for (int32_t i : *v) { if (out && n < cap) out[n] = i; n += 1; }
+            return n;
+        }
         if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape() && !p.is_rmsd())) return 0;
         const size_t P = p.aoff.size() - 1;
         if (context >= (int64_t)P) return 0;

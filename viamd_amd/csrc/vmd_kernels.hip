@@ -1954,6 +1954,159 @@ __global__ __launch_bounds__(256) void k_rdf_brute(vmd_brute_params_t p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ K6: within
+
+// count(T and within(r_min:r_max, R)): target t is in iff SOME reference atom lies at r_min <= d < r_max (closed: d <= r_max), d the
+// correctly rounded sqrtf of the S3 / S3t squared distance - the d vmd_bin_of bins.  r2_up is a coarse bound in front of the root: every
+// d2 whose root can be <= r_max lies below it (+inf where r_max^2 leaves the normal range: the root decides alone).
+struct vmd_within_test_t { float rmin, rmax, r2_up; int closed; };
+static inline vmd_within_test_t vmd_make_within_test(float rmin, float rmax, int closed) {
+    vmd_within_test_t w;
+    w.rmin = rmin; w.rmax = rmax; w.closed = closed ? 1 : 0;
+    const float r2 = rmax * rmax;
+    w.r2_up = (r2 > 1.0e-30f && r2 < 1.0e30f) ? nextafterf(r2, 3.0e38f) * 1.0001f : INFINITY;
+    return w;
+}
+__device__ __forceinline__ bool vmd_within_hit(const vmd_within_test_t& w, float d2) {
+    if (!(d2 < w.r2_up)) return false;
+    const float d = sqrtf(d2);
+    return w.rmin <= d && (w.closed ? d <= w.rmax : d < w.rmax);
+}
+
+struct vmd_within_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* tgt; int ntgt; const int32_t* ref; int nref;
+    vmd_within_test_t w;
+    unsigned* count;
+};
+
+// all pairs from the raw frame (any cell, any cutoff): one lane per target atom, the reference set staged through LDS in tiles of 256, a
+// lane stops testing at its first hit.  One integer atomic per wave.  The device-side definition the cell walk below is tested against.
+__global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t p) {
+    __shared__ float s_r[3][256];
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    const bool valid = t < p.ntgt;
+    if (valid) {
+        const int a = p.tgt ? p.tgt[t] : t;
+        vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi);
+    }
+    bool hit = false;
+    for (int j0 = 0; j0 < p.nref; j0 += 256) {
+        __syncthreads();
+        const int j = j0 + threadIdx.x;
+        if (j < p.nref) {
+            const int a = p.ref ? p.ref[j] : j;
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][threadIdx.x], s_r[1][threadIdx.x], s_r[2][threadIdx.x]);
+        }
+        __syncthreads();
+        const int nj = p.nref - j0 < 256 ? p.nref - j0 : 256;
+        if (valid && !hit)
+            for (int jj = 0; jj < nj && !hit; ++jj)
+                hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
+    }
+    const unsigned long long m = __ballot(hit ? 1 : 0);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
+}
+
+struct vmd_within_pencil_params_t {
+    const float* sref; const uint32_t* cs_ref; int nref_pad;
+    const float* stgt; const uint32_t* cs_tgt; int ntgt_pad;
+    const float* boxes; int B; vmd_grid_t grid;
+    vmd_within_test_t w; float rpad;
+    uint32_t pbc; int ry, rz;
+    unsigned* count; const uint32_t* skip;
+};
+
+// the cell walk: one block (one wave) per (frame, pencil), one lane per target atom of the pencil.  Both sets come cell-sorted (K1), so
+// the x window [x - r, x + r] of a neighbour pencil is one run of the sorted reference copy per periodic image; pencils, images, window
+// arithmetic and the pair arithmetic are those of k_rdf_pencil (the neighbour cell's image is the comparison's for every d < r_max), with
+// the window of ONE atom instead of a chunk's.  A lane leaves the walk at its first hit.
+__global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t p) {
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch
+    const int lane = threadIdx.x;
+    const int b = blockIdx.y, pen = blockIdx.x;
+    const int nxf = p.grid.nxf, ny = p.grid.ny, nz = p.grid.nz;
+    const int pz = pen / ny, py = pen - pz * ny;
+    const bool tri = (p.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.pbc & 7u) != 7u;
+    const float* q = p.boxes + (size_t)VMD_BOX_STRIDE * b;
+    const float Lx = q[0], Ly = q[1], Lz = q[2];
+    const float inv_cx = (float)nxf * q[3];
+    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
+    const bool open_x = open && !(p.pbc & 1u), open_y = open && !(p.pbc & 2u), open_z = open && !(p.pbc & 4u);
+    const float orgx = open_x ? q[6] : 0.0f;
+    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
+    const uint32_t* csr = p.cs_ref + (size_t)b * (p.grid.ncell + 1);
+    const uint32_t* cst = p.cs_tgt + (size_t)b * (p.grid.ncell + 1);
+    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
+    const float* ry_ = rx + p.nref_pad;
+    const float* rz_ = ry_ + p.nref_pad;
+    const float* tx = p.stgt + (size_t)b * 3 * p.ntgt_pad;
+    const unsigned pbeg = cst[pen * nxf], pend = cst[(pen + 1) * nxf];
+    unsigned total = 0;
+    for (unsigned i0 = pbeg; i0 < pend; i0 += VMD_WAVE) {
+        const unsigned i = i0 + lane;
+        bool hit = false;
+        if (i < pend) {
+            const float xi = tx[i], yi = tx[p.ntgt_pad + i], zi = tx[2 * (size_t)p.ntgt_pad + i];
+            for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
+                int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
+                if (open_z && (qz < 0 || qz >= nz)) continue;
+                if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
+                for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
+                    int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+                    if (open_y && (qy < 0 || qy >= ny)) continue;
+                    if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
+                    const int qp = qz * ny + qy;
+                    float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
+                    if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
+                        const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
+                        const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                        const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                        if (rr <= 0.0f) continue;
+                        rpad = sqrtf(rr) * 1.0001f;
+                    }
+                    if (tri) {
+                        const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
+                        const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
+                        offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                        offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+                    }
+                    for (int kx = -1; kx <= 1 && !hit; ++kx) {
+                        if (open_x && kx != 0) continue;
+                        float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
+                        if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
+                        const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
+                        const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
+                        if (hi < 0.0f || lo >= Lx) continue;
+                        const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
+                        const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
+                        const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
+                        for (unsigned j = ja; j < jb && !hit; ++j) {
+                            const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
+                            hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
+                        }
+                    }
+                }
+            }
+        }
+        total += (unsigned)__popcll(__ballot(hit ? 1 : 0));
+    }
+    if (lane == 0 && total) atomicAdd(&p.count[b], total);
+}
+
+__global__ __launch_bounds__(256) void k_within_to_float(const unsigned* count, int B, float* out, const uint32_t* skip) {
+    if (skip && *skip) return;
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) out[b] = (float)count[b];
+}
+
 // ------------------------------------------------------------------------------------------------ K3: SDF alignment (fp64)
 
 // cyclic Jacobi on a symmetric 4x4 — identical operation order to oracle vo_jacobi4
@@ -3518,6 +3671,53 @@ extern "C" int vmd_hip_rdf_brute(void* stream, const float* xyz, size_t frame_st
     vmd_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, ref, nref, tgt, ntgt, {}, counts, g_rdf_raw};
     p.bin = vmd_make_binning(rmin, rmax, nbins, g_rdf_closed);
     hipLaunchKernelGGL(k_rdf_brute, dim3((nref + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_within_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                    const float* boxes, uint32_t pbc_flags, int B,
+                                    const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                                    float rmin, float rmax, int closed, uint32_t* count_out) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !count_out) return (int)hipErrorInvalidValue;
+    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    if (ntgt <= 0 || nref <= 0) return 0;
+    vmd_within_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref,
+                                vmd_make_within_test(rmin, rmax, closed), count_out};
+    hipLaunchKernelGGL(k_within_brute, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_within_pencil(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+                                     const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
+                                     const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
+                                     uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !count_out || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0) return (int)hipErrorInvalidValue;
+    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    if (ntgt <= 0 || nref <= 0) return 0;
+    vmd_within_pencil_params_t p;
+    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
+    p.stgt = sorted_tgt; p.cs_tgt = cell_start_tgt; p.ntgt_pad = ntgt_pad;
+    p.boxes = boxes; p.B = B; p.grid = grid;
+    p.w = vmd_make_within_test(rmin, rmax, closed);
+    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_rdf_pencil
+    p.pbc = pbc_flags; p.ry = g_pen_ry; p.rz = g_pen_rz;
+    p.count = count_out; p.skip = skip_flag;
+    hipLaunchKernelGGL(k_within_pencil, dim3(grid.ny * grid.nz, B), dim3(VMD_WAVE), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_within_to_float(void* stream, const uint32_t* counts, int B, float* out, const uint32_t* skip_flag) {
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(k_within_to_float, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, counts, B, out, skip_flag);
     VMD_LAUNCH_CHECK();
     return 0;
 }

@@ -337,7 +337,8 @@ struct Report {
 // `{lin,plan,iso} = shape_weights(all);` of VIAMD's default script (src/main.cpp:528).  A later statement that uses an identifier of a
 // skipped one is skipped with it ("unknown identifier").
 // features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
-// `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)` (opt-in; 0 = the subset above, byte for byte)
+// `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)`, VMD_SCRIPT_FEATURE_WITHIN
+// `name = count(sel and within(r, sel))` (opt-in; 0 = the subset above, byte for byte)
 void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
@@ -447,7 +448,8 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
             const bool is_func = k.kind == T_ID && (k.text == "rdf" || k.text == "sdf" || k.text == "distance" || k.text == "distance_min" ||
                                                     k.text == "distance_max" || k.text == "distance_pair" ||
                                                     ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")) ||
-                                                    ((features & VMD_SCRIPT_FEATURE_RMSD) && k.text == "rmsd"));
+                                                    ((features & VMD_SCRIPT_FEATURE_RMSD) && k.text == "rmsd") ||
+                                                    ((features & VMD_SCRIPT_FEATURE_WITHIN) && k.text == "count"));
             if (is_func) {
                 is_property = true;
                 const std::string v = k.text;
@@ -482,6 +484,64 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                     const auto tg = tgt.indices();
                     const size_t K = structs.size();
                     commit = [=]() { if (!vmd_ir_add_sdf(ir, name.c_str(), flat.data(), K, m, tg.data(), tg.size(), (float)cutoff)) throw ScriptError(vmd_last_error()); };
+                } else if (v == "count") {
+                    // `name = count(<factor> and <factor> ...);`: exactly one factor is within(<r> | <a>:<b>, <static selection>),
+                    // the others are static selections whose AND is the target set (all atoms when there is none)
+                    const size_t start = p.i;
+                    size_t j = p.i;
+                    int depth = 1;
+                    while (depth) {
+                        if (j >= toks.size()) fail("%s: missing ')'", name.c_str());
+                        if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
+                        if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
+                        ++j;
+                    }
+                    size_t n_within = 0, n_top = 0;
+                    bool top_or = false;
+                    depth = 0;
+                    for (size_t q = start; q + 1 < j; ++q) {
+                        const Token& tk = toks[q];
+                        if (tk.kind == T_OP && tk.text == "(") depth += 1;
+                        if (tk.kind == T_OP && tk.text == ")") depth -= 1;
+                        if (tk.kind == T_ID && tk.text == "within" && toks[q + 1].kind == T_OP && toks[q + 1].text == "(") {
+                            n_within += 1;
+                            if (depth == 0 && (q == start || (toks[q - 1].kind == T_ID && toks[q - 1].text == "and"))) n_top += 1;
+                        }
+                        if (tk.kind == T_ID && tk.text == "or" && depth == 0) top_or = true;
+                    }
+                    if (n_within == 0) fail("%s: count of a static selection is a constant (left to the fallback)", name.c_str());
+                    if (n_within > 1) fail("%s: count takes exactly one within() factor, found %zu", name.c_str(), n_within);
+                    if (n_top != 1 || top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", name.c_str());
+                    std::vector<uint8_t> tmask(topo.n, 1);
+                    std::vector<int32_t> ref;
+                    double rmin = 0.0, rmax = 0.0;
+                    do {
+                        if (p.peek().kind == T_ID && p.peek().text == "within") {
+                            ++p.i;
+                            p.take("(");
+                            rmax = p.number();
+                            if (p.accept(":")) {
+                                rmin = rmax; rmax = p.number();
+                                if (!(rmin < rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
+                            } else if (!(rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
+                            p.take(",");
+                            ref = p.sel_or().indices();
+                            p.take(")");
+                            if (ref.empty()) fail("%s: empty selection", name.c_str());
+                        } else {
+                            const Sel f = p.sel_not();
+                            for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a];
+                        }
+                    } while (p.accept("and"));
+                    p.take(")");
+                    if (p.is_word("in")) fail("%s: count(...) in <contexts> is outside the subset", name.c_str());
+                    std::vector<int32_t> tgt;
+                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) tgt.push_back((int32_t)a);
+                    if (tgt.empty()) fail("%s: empty selection", name.c_str());
+                    commit = [=]() {
+                        if (!vmd_ir_add_within_count(ir, name.c_str(), tgt.data(), tgt.size(), ref.data(), ref.size(), (float)rmin, (float)rmax))
+                            throw ScriptError(vmd_last_error());
+                    };
                 } else if (v == "rmsd") {
                     // `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context rules of distance()
                     const size_t start = p.i;

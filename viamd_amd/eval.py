@@ -163,6 +163,13 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_rmsd_population(self.h, name.encode(), len(sets), flat.ctypes.data_as(L.c_int32_p),
                                                         off.ctypes.data_as(L.c_int32_p)))
 
+    def add_within_count(self, name, target, ref, rmin, rmax):
+        """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
+        (itself included) at rmin <= d < rmax."""
+        t, tp = _idx(target)
+        r, rp = _idx(ref)
+        self._check(self.lib.vmd_ir_add_within_count(self.h, name.encode(), tp, t.size, rp, r.size, float(rmin), float(rmax)))
+
     @staticmethod
     def _names3(names):
         import ctypes as C
@@ -172,7 +179,7 @@ class ScriptIR:
 
     def geometry_atoms(self, name, context=-1):
         """the atoms of an angle / dihedral property (one context, or all when context < 0) in argument order, or the set of a
-        shape_weights or rmsd property"""
+        shape_weights or rmsd property, or the reference set followed by the target set of a within count"""
         n = int(self.lib.vmd_ir_geometry_atoms(self.h, name.encode(), int(context), None, 0))
         out = np.zeros(n, np.int32)
         if n:

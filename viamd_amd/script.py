@@ -268,9 +268,10 @@ _GEOM_NARGS = {"angle": 3, "dihedral": 4}       # opt-in (angles=True)
 FEATURE_ANGLES = 1                              # VMD_SCRIPT_FEATURE_ANGLES
 FEATURE_SHAPE = 2                               # VMD_SCRIPT_FEATURE_SHAPE
 FEATURE_RMSD = 4                                # VMD_SCRIPT_FEATURE_RMSD
+FEATURE_WITHIN = 8                              # VMD_SCRIPT_FEATURE_WITHIN
 
 
-def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -285,7 +286,11 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
     opt-ins the default script compiles whole: d1, a1, r, v, lin, plan, iso, nothing skipped.
 
     rmsd=True (VMD_SCRIPT_FEATURE_RMSD, opt-in): `name = rmsd(sel)`, plain or `in <contexts>`,
-    info[name] = dict(kind="rmsd", sets=[one index array per context])."""
+    info[name] = dict(kind="rmsd", sets=[one index array per context]).
+
+    within=True (VMD_SCRIPT_FEATURE_WITHIN, opt-in): `name = count(<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...])`:
+    exactly one within() factor at the top level of the AND, everything else static;
+    info[name] = dict(kind="within_count", target=idx, ref=idx, rmin=, rmax=)."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -329,7 +334,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("=")
                 if shape and p.peek() == ("id", "shape_weights"):
                     raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd)
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -461,17 +466,82 @@ def _rmsd_statement(p, name, topo, env, ir, info):
     return commit
 
 
-def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False):
+def _count_statement(p, name, topo, env, ir, info):
+    """`name = count(<factor> and ...)` behind the opening parenthesis (the twin of the count branch of vmd_script.cpp)."""
+    start = p.i
+    j, depth = p.i, 1
+    while depth:
+        if j >= len(p.t):
+            raise ScriptError(f"{name}: missing ')'")
+        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
+        j += 1
+    n_within = n_top = depth = 0
+    top_or = False
+    for q in range(start, j - 1):
+        k, v = p.t[q]
+        if k == "op":
+            depth += {"(": 1, ")": -1}.get(v, 0)
+        if (k, v) == ("id", "within") and p.t[q + 1] == ("op", "("):
+            n_within += 1
+            if depth == 0 and (q == start or p.t[q - 1] == ("id", "and")):
+                n_top += 1
+        if (k, v) == ("id", "or") and depth == 0:
+            top_or = True
+    if n_within == 0:
+        raise ScriptError(f"{name}: count of a static selection is a constant (left to the fallback)")
+    if n_within > 1:
+        raise ScriptError(f"{name}: count takes exactly one within() factor, found {n_within}")
+    if n_top != 1 or top_or:
+        raise ScriptError(f"{name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
+    tmask = np.ones(topo.num_atoms, bool)
+    ref, rmin, rmax = None, 0.0, 0.0
+    while True:
+        if p.peek() == ("id", "within"):
+            p.i += 1
+            p.take("(")
+            rmax = p.number()
+            if p.accept(":"):
+                rmin, rmax = rmax, p.number()
+                if not rmin < rmax:
+                    raise ScriptError(f"{name}: within range needs 0 <= a < b")
+            elif not rmax > 0.0:
+                raise ScriptError(f"{name}: within needs a radius > 0")
+            p.take(",")
+            ref = p.sel_or().indices()
+            p.take(")")
+            if ref.size == 0:
+                raise ScriptError(f"{name}: empty selection")
+        else:
+            tmask = tmask & p.sel_not().mask
+        if not p.accept("and"):
+            break
+    p.take(")")
+    if p.peek() == ("id", "in"):
+        raise ScriptError(f"{name}: count(...) in <contexts> is outside the subset")
+    tgt = np.nonzero(tmask)[0].astype(np.int32)
+    if tgt.size == 0:
+        raise ScriptError(f"{name}: empty selection")
+    lo, hi = float(np.float32(rmin)), float(np.float32(rmax))
+
+    def commit():
+        ir.add_within_count(name, tgt, ref, lo, hi)
+        info[name] = dict(kind="within_count", target=tgt, ref=ref, rmin=lo, rmax=hi)
+    return commit
+
+
+def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
-    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS) or (rmsd and v == "rmsd"))):
+    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS) or (rmsd and v == "rmsd") or (within and v == "count"))):
         sel = p.sel_or()
         return (lambda: env.__setitem__(name, sel)), False
     p.i += 1
     p.take("(")
     if v == "rmsd":
         return _rmsd_statement(p, name, topo, env, ir, info), True
+    if v == "count":
+        return _count_statement(p, name, topo, env, ir, info), True
     if v == "rdf":
         ref = p.sel_or(); p.take(",")
         tgt = p.sel_or(); p.take(",")
@@ -567,14 +637,16 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False):
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
-    VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD."""
+    VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD; within=True: with
+    VMD_SCRIPT_FEATURE_WITHIN."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
-    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0)
+    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0) | \
+        (FEATURE_WITHIN if within else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
