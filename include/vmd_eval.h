@@ -243,6 +243,15 @@ bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P,
  * Empty sets, negative indices, a range that is not finite or not 0 <= rmin < rmax and a name already defined are errors. */
 bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
                              const int32_t* ref, size_t nref, float rmin, float rmax);
+/* `name = rdf(<T> and within(a:b, <R>), <target>, {rmin,rmax});`: an rdf argument that is a SHELL - per frame, the atoms of
+ * its list that have some atom of shell.ref (itself included) at shell.rmin <= d < shell.rmax, exactly the atoms vmd_ir_add_within_count
+ * counts.  `ref` / `target` are the parent lists T; ref_shell / target_shell make that side dynamic, NULL leaves it the static list (both
+ * NULL: vmd_ir_add_rdf).  The record is an rdf's; the S4 weights use the shell's population of every frame (DECISION D-SHELL-NORM;
+ * vmd_set_option("spec_shell_norm", 1): the parent lists' sizes).  spec_within_closed / spec_within_exclude_ref act on the shells,
+ * spec_rdf_* on the histogram.  Validation as vmd_ir_add_rdf plus, per shell, that of vmd_ir_add_within_count. */
+typedef struct vmd_shell_t { const int32_t* ref; size_t nref; float rmin, rmax; } vmd_shell_t;
+bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const vmd_shell_t* ref_shell,
+                          const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float rmin, float rmax);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count: returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
@@ -296,11 +305,14 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
  * VMD_SCRIPT_FEATURE_RMSD also compiles `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context
  * rules of distance().
  * VMD_SCRIPT_FEATURE_WITHIN also compiles `name = count(<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]);`: exactly
- * one within() factor at the top level of the AND, every other factor and its argument a static selection. */
+ * one within() factor at the top level of the AND, every other factor and its argument a static selection.
+ * VMD_SCRIPT_FEATURE_SHELL_RDF lets either selection argument of rdf() be such an AND, `<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]`
+ * (DESIGN 1.7), under the same rules; sdf() and the distance family keep answering "unsupported function 'within'". */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
 #define VMD_SCRIPT_FEATURE_SHAPE 2u
 #define VMD_SCRIPT_FEATURE_RMSD 4u
 #define VMD_SCRIPT_FEATURE_WITHIN 8u
+#define VMD_SCRIPT_FEATURE_SHELL_RDF 16u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -309,7 +321,7 @@ uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir);                 /* md_sc
 size_t   vmd_ir_property_count(const vmd_script_ir_t* ir);              /* md_script_ir_property_count, src/main.cpp:992,1277 */
 const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir);    /* md_script_ir_property_names, src/main.cpp:1278 */
 vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name); /* src/main.cpp:1285 */
-/* atom pairs ONE frame of the script asks for (rdf |ref| x |target|, sdf K x (|target| + m), distance |a| x |b| per context, angle /
+/* atom pairs ONE frame of the script asks for (rdf |ref| x |target| of the parent lists, plus |T| + |R| per shell; sdf K x (|target| + m), distance |a| x |b| per context, angle /
  * dihedral / shape_weights / rmsd: the atoms of every context's sets, within count: |target| + |ref|): the size a host
  * compares with a threshold before it sends a small script to the GPU (vmd_shim_set_min_work; VIAMD's default dataset, src/main.cpp:522-528) */
 uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir);

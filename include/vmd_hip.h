@@ -18,6 +18,7 @@
  *   vmd_hip_shape     <- shape_weights
  *   vmd_hip_rmsd      <- rmsd
  *   vmd_hip_within_*  <- count(sel and within(r, sel))
+ *   vmd_hip_within_*_flags, vmd_hip_shell_compact, vmd_hip_rdf_brute_masked  <- rdf() over within() shells
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -211,6 +212,35 @@ int vmd_hip_within_pencil(void* stream, const float* sorted_ref, const uint32_t*
                           const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
                           uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag);
 int vmd_hip_within_to_float(void* stream, const uint32_t* counts, int B, float* out, const uint32_t* skip_flag);
+
+/* K7: a within() shell as an rdf() argument, DESIGN 1.7.  The walks of K6 with one more product - WHICH entries are in:
+ *   vmd_hip_within_brute_flags   flags_out u8[B][ntgt] in list order (1 = in the shell); count_out as vmd_hip_within_brute
+ *   vmd_hip_within_pencil_flags  flags_out u8[B][ntgt_pad], one byte per SORTED position of the target copy (positions < ntgt are written);
+ *                                pen_hits_out u32[B][ny*nz + 1], the hits of every pencil (the last entry is scratch); count_out as
+ *                                vmd_hip_within_pencil.  Nothing but the zeroing of count_out happens when *skip_flag != 0
+ *   vmd_hip_shell_compact        the flagged entries of (sorted, cell_start), in place order, become (sorted_hit f32[B][3][nsel_pad],
+ *                                cell_start_hit u32[B][ncell+1]) on the same grid: a selection vmd_hip_rdf_pencil takes as it is.
+ *                                pen_base u32[B][ny*nz + 1] is scratch (must not alias pen_hits).  Entries of sorted_hit beyond a frame's
+ *                                population are left as they are: give the buffer the slack and the finite contents of a parent's rows.
+ *                                Does nothing but the prefix when *skip_flag != 0
+ *   vmd_hip_rdf_brute_masked     vmd_hip_rdf_brute with optional per-frame masks u8[B][nref] / u8[B][ntgt] (NULL = every entry): an entry
+ *                                whose byte is 0 takes no part in that frame.  B <= 65535 */
+int vmd_hip_within_brute_flags(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                               const float* boxes, uint32_t pbc_flags, int B,
+                               const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                               float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* flags_out);
+int vmd_hip_within_pencil_flags(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+                                const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
+                                const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
+                                uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag,
+                                uint8_t* flags_out, uint32_t* pen_hits_out);
+int vmd_hip_shell_compact(void* stream, const uint8_t* flags, const uint32_t* pen_hits, uint32_t* pen_base,
+                          const float* sorted, const uint32_t* cell_start, int nsel_pad, int B, vmd_grid_t grid,
+                          float* sorted_hit, uint32_t* cell_start_hit, const uint32_t* skip_flag);
+int vmd_hip_rdf_brute_masked(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                             const float* boxes, uint32_t pbc_flags, int B,
+                             const int32_t* ref, int nref, const uint8_t* ref_mask, const int32_t* tgt, int ntgt,
+                             const uint8_t* tgt_mask, float rmin, float rmax, int nbins, uint64_t* counts);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -67,6 +67,10 @@ class TopologyC(C.Structure):
                 ("resnames", C.POINTER(C.c_char_p)), ("residue_index", c_int32_p), ("residue_seq_id", c_int32_p)]
 
 
+class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
+    _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
+
+
 class XtcFrame(C.Structure):             # vmd_xtc_frame_t (include/vmd_hip.h)
     _fields_ = [("precision", C.c_float), ("minint", C.c_int32 * 3), ("maxint", C.c_int32 * 3), ("smallidx", C.c_int32),
                 ("offset", C.c_uint64), ("nbytes", C.c_uint64)]
@@ -157,6 +161,8 @@ SIGNATURES = [
     ("vmd_ir_add_rmsd", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
     ("vmd_ir_add_rmsd_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
+    ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
+                                        C.POINTER(ShellC), C.c_float, C.c_float]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -337,6 +343,13 @@ SIGNATURES = [
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,
                                         C.c_float, C.c_float, C.c_int, C.c_uint32, _vp, _vp]),
     ("vmd_hip_within_to_float", C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    ("vmd_hip_within_brute_flags", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                             C.c_float, C.c_float, C.c_int, _vp, _vp]),
+    ("vmd_hip_within_pencil_flags", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,
+                                              C.c_float, C.c_float, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("vmd_hip_shell_compact", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, Grid, _vp, _vp, _vp]),
+    ("vmd_hip_rdf_brute_masked", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
+                                           _vp, C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_add_u64", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("vmd_hip_counts_to_float", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_float]),
     ("vmd_hip_bump_u64", C.c_int, [_vp, _vp, C.c_uint64]),

@@ -126,6 +126,9 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     std::vector<char> used(e->sels.size(), 0);
     for (auto& g : e->rdf_groups) for (auto& ps : g.passes) { used[ps.sel_a] = 1; used[ps.sel_b] = 1; }
     for (int pi : e->within_props) { if (e->props[pi]->sel_a >= 0) used[e->props[pi]->sel_a] = 1; used[e->props[pi]->sel_b] = 1; }
+    for (auto& g : e->rdf_groups) for (int pi : g.shell_props) for (int sl : {e->props[pi]->sel_a, e->props[pi]->sel_b}) if (sl >= 0) used[sl] = 1;
+    // a shell keeps a hit copy the size of its parent's sorted rows, one byte per entry and its tables
+    for (auto& h : e->shells) { used[h->sel_r] = 1; if (h->sel_t >= 0) per_frame += 24 * e->sels[h->sel_t]->idx.size(); }
     for (size_t i = 0; i < e->sels.size(); ++i) if (used[i]) per_frame += 40 * e->sels[i]->idx.size();
     for (auto& p : e->props) per_frame += p->prop.kind == PROP_SDF ? 64 * p->prop.K : (p->prop.kind == PROP_DIST ? 4 * p->dim1 : 0);
     // 288 GB of HBM: a 16 GB scratch budget holds the 1 000 frames of the 1M-atom RDF (333k selected atoms) in ONE batch
@@ -425,6 +428,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         bool poisoned = false;      // queued behind a batch that overflowed: its RDF part saw the flag and did nothing
         bool snapshot = false;      // h_snap[slot] holds the RDF counts behind this batch's commits (+ w_snap: the weights)
         std::vector<size_t> within_toff;    // within counts: where each one's rows start in h_temporal_slot[slot]
+        std::vector<std::vector<uint32_t>> shell_pop;    // rdf over shells: [shell][frame of the batch] populations
     };
     BatchCtx ctx[2];
     const bool defer = g_opt.defer_sync.load() != 0 && e->block_frames == 0 && batches.size() > 1;
@@ -452,7 +456,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         vmd_hip_set_rdf_closed(e->spec.rdf_closed ? 1 : 0);
         vmd_hip_set_rdf_raw(e->spec.rdf_raw ? 1 : 0);
         size_t scratch_rows = 0;
-        for (auto& g : e->rdf_groups) scratch_rows += std::max(g.passes.size(), g.props.size());
+        for (auto& g : e->rdf_groups) scratch_rows += std::max(g.passes.size(), g.props.size()) + g.shell_props.size();
         scratch_rows *= c.subs.size();
         if (!e->d_pass.ensure(std::max<size_t>(scratch_rows, 1) * VMD_RDF_NUM_BINS)) return false;
         if (scratch_rows) HIP_OK(hipMemsetAsync(e->d_pass.p, 0, scratch_rows * VMD_RDF_NUM_BINS * sizeof(uint64_t), e->stream));
@@ -460,6 +464,81 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         std::vector<Commit> commits;
         size_t row = 0;
         bool forked = false;
+        // ---- shells as rdf arguments.  One walk + one compaction per shell, batch and grid, whichever properties use it; the
+        // per-frame populations travel to the host from here, behind the overflow flag like everything else of launch_rdf.
+        for (auto& h : e->shells) h->built = 0;
+        c.shell_pop.resize(e->shells.size());
+        auto shell_pops = [&](size_t hi) -> bool {
+            Shell* h = e->shells[hi].get();
+            c.shell_pop[hi].assign(c.nb, 0);
+            if (h->sel_t >= 0) HIP_OK(hipMemcpyAsync(c.shell_pop[hi].data(), h->count.p, c.nb * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+            return true;
+        };
+        // the hit copy of shell hi on `grid`: (sorted, cell_start) of the members, a selection the pair kernel takes as it is
+        auto shell_pencil = [&](size_t hi, const float* d_gb, const vmd_grid_t& grid) -> bool {
+            Shell* h = e->shells[hi].get();
+            if (h->sel_t < 0) { h->built = 1; return shell_pops(hi); }
+            if (h->built == 1 && h->built_grid.nxf == grid.nxf && h->built_grid.ny == grid.ny && h->built_grid.nz == grid.nz) return true;
+            Selection* st = e->sels[h->sel_t].get();
+            Selection* sr = e->sels[h->sel_r].get();
+            if (!build_selection(e, st, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+            if (sr != st && !build_selection(e, sr, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+            const size_t npen = (size_t)grid.ny * grid.nz;
+            const size_t rows = c.nb * 3 * (size_t)st->nsel_pad + 64;           // the parent's rows, slack included
+            if (rows > h->sorted.cap) {
+                if (!h->sorted.ensure(rows)) return false;
+                HIP_OK(hipMemsetAsync(h->sorted.p, 0, rows * sizeof(float), e->stream));     // what lies beyond a population stays finite
+            }
+            if (!h->flags.ensure(c.nb * (size_t)st->nsel_pad) || !h->count.ensure(c.nb) || !h->pen_hits.ensure(c.nb * (npen + 1)) ||
+                !h->pen_base.ensure(c.nb * (npen + 1)) || !h->cell_start.ensure(c.nb * (size_t)(grid.ncell + 1))) return false;
+            e->prof.begin("shell_flags", e->stream);
+            KRN_OK(vmd_hip_within_pencil_flags(e->stream, sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, st->sorted.p,
+                    st->cell_start.p, (int)st->idx.size(), st->nsel_pad, d_gb, (int)c.nb, grid, h->rmin, h->rmax,
+                    e->spec.within_closed ? 1 : 0, c.pbc, h->count.p, e->d_overflow.p, h->flags.p, h->pen_hits.p));
+            e->prof.end(e->stream);
+            e->prof.begin("shell_compact", e->stream);
+            KRN_OK(vmd_hip_shell_compact(e->stream, h->flags.p, h->pen_hits.p, h->pen_base.p, st->sorted.p, st->cell_start.p, st->nsel_pad,
+                    (int)c.nb, grid, h->sorted.p, h->cell_start.p, e->d_overflow.p));
+            e->prof.end(e->stream);
+            h->built = 1; h->built_grid = grid;
+            return shell_pops(hi);
+        };
+        // no grid: the members as one byte per list entry, from all pairs of the raw frame (always wrapped positions)
+        auto shell_brute = [&](size_t hi) -> bool {
+            Shell* h = e->shells[hi].get();
+            if (h->built == 2) return true;
+            if (h->sel_t >= 0) {
+                Selection* st = e->sels[h->sel_t].get();
+                Selection* sr = e->sels[h->sel_r].get();
+                if (!h->flags.ensure(c.nb * st->idx.size()) || !h->count.ensure(c.nb)) return false;
+                e->prof.begin("shell_brute", e->stream);
+                KRN_OK(vmd_hip_within_brute_flags(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                        (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), h->rmin, h->rmax,
+                        e->spec.within_closed ? 1 : 0, h->count.p, h->flags.p));
+                e->prof.end(e->stream);
+            }
+            h->built = 2;
+            return shell_pops(hi);
+        };
+        // a shell property by all pairs: list-order masks on the shell sides.  choose_grid failed for the group, or this is spec_rdf_raw
+        auto shell_rdf_brute = [&](RdfGroup& g, PropState* p) -> bool {
+            for (int k = 0; k < 2; ++k) if (p->shell_of[k] >= 0 && !shell_brute((size_t)p->shell_of[k])) return false;
+            for (auto& su : c.subs) {
+                uint64_t* dst = e->d_pass.p + (row++) * VMD_RDF_NUM_BINS;
+                if (p->sel_a < 0 || p->sel_b < 0) continue;                      // T minus R is empty: no member in any frame
+                Selection* sa = e->sels[p->sel_a].get();
+                Selection* sb = e->sels[p->sel_b].get();
+                const uint8_t* ma = p->shell_of[0] >= 0 ? e->shells[p->shell_of[0]]->flags.p + su.off * sa->idx.size() : nullptr;
+                const uint8_t* mb = p->shell_of[1] >= 0 ? e->shells[p->shell_of[1]]->flags.p + su.off * sb->idx.size() : nullptr;
+                e->prof.begin("rdf_brute", e->stream);
+                KRN_OK(vmd_hip_rdf_brute_masked(e->stream, c.src->base + su.off * c.src->frame_stride, c.src->frame_stride,
+                        c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, sa->d_idx.p, (int)sa->idx.size(), ma,
+                        sb->d_idx.p, (int)sb->idx.size(), mb, g.rmin, g.rmax, VMD_RDF_NUM_BINS, dst));
+                e->prof.end(e->stream);
+                commits.push_back({acc_of(p, su), dst, 1});
+            }
+            return true;
+        };
         for (auto& g : e->rdf_groups) {
             vmd_grid_t grid;
             // fully periodic cells use the frame boxes; open axes (non-periodic systems, slabs) span the batch's bounding box
@@ -469,7 +548,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
             const float* d_gb = (open_axes && c.src->gboxes_ready) ? c.src->d_gboxes.p : c.src->d_boxes.p;
             // density of the sparsest selection any pass of this group puts in the lanes (the denser of its two), against the first frame's
             // cell
-            bool dense_lanes = !open_axes && !g.passes.empty();
+            bool dense_lanes = !open_axes && !(g.passes.empty() && g.shell_props.empty());
             if (dense_lanes) {
                 const float* q = gb.data();
                 const double vol = (double)q[0] * q[1] * q[2];
@@ -477,8 +556,14 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                     const size_t lanes = std::max(e->sels[ps.sel_a]->idx.size(), e->sels[ps.sel_b]->idx.size());
                     dense_lanes = dense_lanes && vol > 0.0 && (double)lanes / vol >= 0.08;
                 }
+                for (int pi : g.shell_props) {      // by the parent lists: what the cell builds sort
+                    const PropState* p = e->props[pi].get();
+                    const size_t lanes = std::max(p->sel_a >= 0 ? e->sels[p->sel_a]->idx.size() : 0, p->sel_b >= 0 ? e->sels[p->sel_b]->idx.size() : 0);
+                    dense_lanes = dense_lanes && vol > 0.0 && (double)lanes / vol >= 0.08;
+                }
             }
-            if (e->spec.rdf_raw || !choose_grid(gb, c.pbc, c.nb, g.rmax, &grid, dense_lanes)) {
+            // (grid_r: the larger of the pair cutoff and the shell radii of the group's members - walk and pair kernel accept a wider edge)
+            if (e->spec.rdf_raw || !choose_grid(gb, c.pbc, c.nb, g.grid_r, &grid, dense_lanes)) {
                 // no grid for this batch (cutoff >= half the cell width, ...): all pairs, per property
                 for (int pi : g.props) {
                     PropState* p = e->props[pi].get();
@@ -494,6 +579,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                         commits.push_back({acc_of(p, su), dst, 1});
                     }
                 }
+                for (int pi : g.shell_props) if (!shell_rdf_brute(g, e->props[pi].get())) return false;
                 continue;
             }
             if (!e->d_partial.ensure(vmd_hip_rdf_partial_words())) return false;
@@ -537,6 +623,44 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                         KRN_OK(vmd_hip_bump_u64(ks, dst + bin0, (uint64_t)su.nb * (uint64_t)sa->idx.size()));
                     }
                     for (auto& tg : ps.targets) commits.push_back({acc_of(e->props[tg.first].get(), su), dst, tg.second});
+                }
+            }
+            // ---- the group's rdfs over shells: the same pair kernel over the hit copies.  Never the half-shell pass: a shell pass counts
+            // ordered pairs, (i, i) included at d = 0 where the sides overlap (dropped by the open interval, a hit under spec_rdf_closed)
+            for (int pi : g.shell_props) {
+                PropState* p = e->props[pi].get();
+                if (forked) {     // the second stream may still read a hit copy or sorted rows the builds below overwrite
+                    HIP_OK(hipEventRecord(e->pair_join, e->pair_stream));
+                    HIP_OK(hipStreamWaitEvent(e->stream, e->pair_join, 0));
+                    forked = false;
+                }
+                for (int k = 0; k < 2; ++k) if (p->shell_of[k] >= 0 && !shell_pencil((size_t)p->shell_of[k], d_gb, grid)) return false;
+                if (p->sel_a < 0 || p->sel_b < 0) { row += c.subs.size(); continue; }     // T minus R is empty
+                const float* srt[2]; const uint32_t* cst[2]; int n[2], npad[2];
+                for (int k = 0; k < 2; ++k) {
+                    Selection* sl = e->sels[k ? p->sel_b : p->sel_a].get();
+                    if (p->shell_of[k] < 0 && !build_selection(e, sl, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+                    const Shell* h = p->shell_of[k] >= 0 ? e->shells[p->shell_of[k]].get() : nullptr;
+                    srt[k] = h ? h->sorted.p : sl->sorted.p; cst[k] = h ? h->cell_start.p : sl->cell_start.p;
+                    n[k] = (int)sl->idx.size(); npad[k] = sl->nsel_pad;       // sizes feed launch heuristics only: the parents'
+                }
+                if (c.two_streams) {
+                    HIP_OK(hipEventRecord(e->pair_fork, e->stream));
+                    HIP_OK(hipStreamWaitEvent(e->pair_stream, e->pair_fork, 0));
+                    forked = true;
+                }
+                size_t si = 0;
+                for (auto& su : c.subs) {
+                    uint64_t* dst = e->d_pass.p + (row++) * VMD_RDF_NUM_BINS;
+                    const bool second = c.two_streams && (si++ & 1);
+                    hipStream_t ks = second ? e->pair_stream : e->stream;
+                    if (!second) e->prof.begin("rdf_pencil", ks);
+                    KRN_OK(vmd_hip_rdf_pencil(ks, srt[0] + su.off * 3 * (size_t)npad[0], cst[0] + su.off * (size_t)(grid.ncell + 1), n[0], npad[0],
+                            srt[1] + su.off * 3 * (size_t)npad[1], cst[1] + su.off * (size_t)(grid.ncell + 1), n[1], npad[1], d_gb + 9 * su.off,
+                            (int)su.nb, grid, g.rmin, g.rmax, VMD_RDF_NUM_BINS, 0, g_opt.rdf_variant, c.pbc,
+                            second ? e->d_partial2.p : e->d_partial.p, dst, e->d_overflow.p));
+                    if (!second) e->prof.end(ks);
+                    commits.push_back({acc_of(p, su), dst, 1});
                 }
             }
         }
@@ -595,6 +719,46 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         return true;
     };
 
+    // SPEC S4 normalisation of one RDF property over the frames of a batch, fp64 on the host
+    auto rdf_weights = [&](BatchCtx& c, PropState* p) {
+        const Property& d = p->prop;
+        const bool shells = d.is_shell_rdf();
+        for (auto& su : c.subs) {
+            double* bw = su.blk >= 0 ? &p->block_weights64[(size_t)su.blk * p->ncounts] : nullptr;
+            if (bw) std::fill(bw, bw + p->ncounts, 0.0);
+            for (size_t b = su.off; b < su.off + su.nb; ++b) {
+                const float* L = &c.src->h_boxes[9 * b];
+                double V;
+                // also the triclinic volume
+                if ((c.pbc & VMD_UNITCELL_PBC_ALL) == VMD_UNITCELL_PBC_ALL && e->spec.rdf_norm != 1) V = (double)L[0]
+                        * (double)L[1] * (double)L[2];
+                else V = (4.0 / 3.0) * M_PI * (double)d.rmax * (double)d.rmax * (double)d.rmax;
+                double Na = (double)d.a.size(), Nb = (double)d.b.size();
+                if (shells) {
+                    // DECISION(D-SHELL-NORM): the populations of this frame; a frame with an empty shell adds no weight (whatever
+                    // spec_rdf_norm and spec_shell_norm say: nothing was counted in it)
+                    bool empty = false;
+                    for (int k = 0; k < 2; ++k) {
+                        if (p->shell_of[k] < 0) continue;
+                        const uint32_t pop = c.shell_pop[p->shell_of[k]][b];
+                        empty = empty || pop == 0;
+                        if (!e->spec.shell_norm) (k ? Nb : Na) = (double)pop;
+                    }
+                    if (empty) continue;
+                }
+                const double rho = (e->spec.rdf_norm == 2 ? 1.0 : Na) * Nb / V;
+                const double w = ((double)d.rmax - (double)d.rmin) / (double)p->ncounts;
+                for (size_t k = 0; k < p->ncounts; ++k) {
+                    const double r0 = (double)d.rmin + w * (double)k;
+                    const double r1 = (double)d.rmin + w * (double)(k + 1);
+                    const double wk = rho * (4.0 / 3.0) * M_PI * (r1 * r1 * r1 - r0 * r0 * r0);
+                    if (!spec) p->weights64[k] += wk;
+                    if (bw) bw[k] += wk;
+                }
+            }
+        }
+    };
+
     // waits for a queued batch (`later`: the batch already queued behind it, if any), repeats its RDF part when a bucket overflowed, books
     // its frames
     auto complete_batch = [&](BatchCtx& c, BatchCtx* later) -> bool {
@@ -651,6 +815,8 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
             HIP_OK(hipStreamSynchronize(e->stream));
             repeated = true;
         }
+        // rdfs over shells: the populations of this batch are final now (a repeated batch sent them again)
+        for (auto& g : e->rdf_groups) for (int pi : g.shell_props) rdf_weights(c, e->props[pi].get());
         if (c.bt.blk >= 0 && !spec)
             for (auto& su : c.subs)
                 for (auto& p : e->props) if (p->ncounts) KRN_OK(vmd_hip_add_u64(e->stream, p->d_counts.p, acc_of(p.get(), su), p->ncounts));
@@ -676,8 +842,9 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         size_t soff = (size_t)c.slot * rdf_counts;
         for (auto& p : e->props) {
             if (p->prop.kind != PROP_RDF) continue;
+            // (an rdf over shells has its weights up to THIS batch in weights64: the batch behind adds its own at its completion)
             if (behind && c.snapshot && !repeated && !(later && later->poisoned)) refresh_distribution_from(p.get(), e->h_snap + soff,
-                    e->w_snap.data() + soff);
+                    p->prop.is_shell_rdf() ? p->weights64.data() : e->w_snap.data() + soff);
             else if (!behind && views) { if (!refresh_distribution(e, p.get())) return false; }
             soff += p->ncounts;
         }
@@ -731,28 +898,9 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         for (auto& p : e->props) {
             const Property& d = p->prop;
             if (d.kind == PROP_RDF) {
-                // SPEC S4 normalisation, fp64 on the host (needs only the box)
-                for (auto& su : c.subs) {
-                    double* bw = su.blk >= 0 ? &p->block_weights64[(size_t)su.blk * p->ncounts] : nullptr;
-                    if (bw) std::fill(bw, bw + p->ncounts, 0.0);
-                    for (size_t b = su.off; b < su.off + su.nb; ++b) {
-                        const float* L = &c.src->h_boxes[9 * b];
-                        double V;
-                        // also the triclinic volume
-                        if ((c.pbc & VMD_UNITCELL_PBC_ALL) == VMD_UNITCELL_PBC_ALL && e->spec.rdf_norm != 1) V = (double)L[0]
-                                * (double)L[1] * (double)L[2];
-                        else V = (4.0 / 3.0) * M_PI * (double)d.rmax * (double)d.rmax * (double)d.rmax;
-                        const double rho = (e->spec.rdf_norm == 2 ? 1.0 : (double)d.a.size()) * (double)d.b.size() / V;
-                        const double w = ((double)d.rmax - (double)d.rmin) / (double)p->ncounts;
-                        for (size_t k = 0; k < p->ncounts; ++k) {
-                            const double r0 = (double)d.rmin + w * (double)k;
-                            const double r1 = (double)d.rmin + w * (double)(k + 1);
-                            const double wk = rho * (4.0 / 3.0) * M_PI * (r1 * r1 * r1 - r0 * r0 * r0);
-                            if (!spec) p->weights64[k] += wk;
-                            if (bw) bw[k] += wk;
-                        }
-                    }
-                }
+                // SPEC S4 normalisation, fp64 on the host (needs only the box).  An rdf over shells needs the populations too: its weights
+                // are formed in complete_batch, when they have arrived
+                if (!d.is_shell_rdf()) rdf_weights(c, p.get());
                 p->dirty = p->dirty || !spec;
             } else if (d.kind == PROP_SDF) {
                 if (!p->d_R32.ensure(c.nb * d.K * 9) || !p->d_c32.ensure(c.nb * d.K * 3) || !p->d_group.ensure(c.nb * 4)) return false;

@@ -59,19 +59,55 @@ int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx) {
 // (sum over passes of n_a * n_b, halved for same-set passes) drops by at least 10 %.
 void build_rdf_plan(vmd_script_eval_t* e) {
     e->rdf_groups.clear();
+    e->shells.clear();
     for (size_t i = 0; i < e->props.size(); ++i) {
         const Property& d = e->props[i]->prop;
         if (d.kind != PROP_RDF) continue;
         RdfGroup* g = nullptr;
         for (auto& q : e->rdf_groups) if (memcmp(&q.rmin, &d.rmin, sizeof(float)) == 0 && memcmp(&q.rmax, &d.rmax, sizeof(float)) == 0) g =
                 &q;
-        if (!g) { e->rdf_groups.emplace_back(); g = &e->rdf_groups.back(); g->rmin = d.rmin; g->rmax = d.rmax; }
-        g->props.push_back((int)i);
+        if (!g) { e->rdf_groups.emplace_back(); g = &e->rdf_groups.back(); g->rmin = d.rmin; g->rmax = d.rmax; g->grid_r = d.rmax; }
+        // an rdf over shells joins the group of its pair range - one grid, shared sorted copies - but not its passes or classes
+        if (d.is_shell_rdf()) {
+            g->shell_props.push_back((int)i);
+            for (int k = 0; k < 2; ++k) if (d.shell[k].on) g->grid_r = std::max(g->grid_r, d.shell[k].rmax);
+        } else g->props.push_back((int)i);
     }
     // every property keeps its own sets as selections (index lists only; sorted copies exist for the selections passes use):
     // the all-pairs kernel, which takes over when a batch cannot use the grid, works per property
     for (auto& p : e->props) {
         if (p->prop.kind != PROP_RDF) continue;
+        if (p->prop.is_shell_rdf()) {
+            // a shell side: its list T (T minus R under D-WITHIN-SELF flipped, as build_within_plan) and R are selections like any other;
+            // the shell itself is interned, so that properties which use the same one share its walk and compaction
+            for (int k = 0; k < 2; ++k) {
+                const Property::ShellArg& h = p->prop.shell[k];
+                std::vector<int32_t> t = k ? p->prop.b : p->prop.a;
+                if (h.on && e->spec.within_exclude_ref) {
+                    std::vector<int32_t> ref = h.ref;
+                    std::sort(ref.begin(), ref.end());
+                    t.erase(std::remove_if(t.begin(), t.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), t.end());
+                }
+                const int st = t.empty() ? -1 : intern_selection(e, t);
+                (k ? p->sel_b : p->sel_a) = st;
+                if (!h.on) continue;
+                const int sr = intern_selection(e, h.ref);
+                int found = -1;
+                for (size_t q = 0; q < e->shells.size() && found < 0; ++q) {
+                    const Shell& x = *e->shells[q];
+                    if (x.sel_t == st && x.sel_r == sr && memcmp(&x.rmin, &h.rmin, sizeof(float)) == 0 && memcmp(&x.rmax, &h.rmax, sizeof(float)) == 0)
+                        found = (int)q;
+                }
+                if (found < 0) {
+                    auto x = std::make_unique<Shell>();
+                    x->sel_t = st; x->sel_r = sr; x->rmin = h.rmin; x->rmax = h.rmax;
+                    e->shells.push_back(std::move(x));
+                    found = (int)e->shells.size() - 1;
+                }
+                p->shell_of[k] = found;
+            }
+            continue;
+        }
         p->sel_a = intern_selection(e, p->prop.a);
         p->sel_b = p->same_set ? p->sel_a : intern_selection(e, p->prop.b);
     }
@@ -190,6 +226,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     e->spec.angle_radians = g_opt.spec_angle_radians.load() != 0;
     e->spec.within_closed = g_opt.spec_within_closed.load() != 0;
     e->spec.within_exclude_ref = g_opt.spec_within_exclude_ref.load() != 0;
+    e->spec.shell_norm = g_opt.spec_shell_norm.load() != 0;
     e->frame_mask.assign(num_frames, 0);
     for (auto& p : ir->props) {
         auto st = std::make_unique<PropState>();

@@ -123,6 +123,7 @@ struct Options {
     // D-WRAP: positions enter rdf() as they are, minimum image by rounding - evaluated by k_rdf_brute (all pairs: a
     std::atomic<int> spec_rdf_raw{0};
     std::atomic<int> spec_within_closed{0};        // DECISION(D-WITHIN-INTERVAL) flipped: hit iff r_min <= d <= r_max
+    std::atomic<int> spec_shell_norm{0};           // DECISION(D-SHELL-NORM) flipped: S4 weights with the parent lists' sizes
     std::atomic<int> spec_within_exclude_ref{0};   // DECISION(D-WITHIN-SELF) flipped: the evaluator counts over T minus R
                                                   // setting for matching an mdlib that does it this way, not a fast path)
     // D-RDF-NORM: 0 = cell volume when fully periodic, else the cutoff sphere; 1 = always the cutoff sphere;
@@ -376,6 +377,9 @@ struct Property {
     bool is_shape() const { return kind == PROP_DIST && dist_kind == GEOM_SHAPE; }
     bool is_rmsd() const { return kind == PROP_DIST && dist_kind == GEOM_RMSD; }
     bool is_within() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN; }
+    // rdf over within() shells: side 0 = a (reference), 1 = b (target); on: that argument is the shell (list, ref, rmin, rmax)
+    struct ShellArg { bool on = false; std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; } shell[2];
+    bool is_shell_rdf() const { return kind == PROP_RDF && (shell[0].on || shell[1].on); }
 };
 
 struct vmd_script_ir_t {
@@ -435,8 +439,25 @@ struct PairPass {
 struct RdfGroup {
     float rmin = 0.0f, rmax = 0.0f;
     std::vector<int> props;                             // indices into eval->props
+    // rdfs over shells: members of the group - same pair range, same grid - with passes of their own, outside the classes
+    std::vector<int> shell_props;
+    float grid_r = 0.0f;                                // what the grid is chosen for: the larger of rmax and the members' shell radii
     std::vector<PairPass> passes;
     bool classes = false;                               // passes come from the class decomposition
+};
+
+// A within() shell an rdf argument uses, interned per (T, R, r_min, r_max): one walk and one compaction per batch and grid,
+// whichever properties share it.  sel_t is T (T minus R under spec_within_exclude_ref; -1: nothing left, the shell is empty in every frame).
+struct Shell {
+    int sel_t = -1, sel_r = -1;
+    float rmin = 0.0f, rmax = 0.0f;
+    DevBuf<uint8_t> flags;                  // pencil: [B][nsel_pad] by sorted position; brute: [B][n] in list order
+    DevBuf<uint32_t> count;                 // [B] the population of every frame of the batch
+    DevBuf<uint32_t> pen_hits, pen_base;    // [B][npen + 1]
+    DevBuf<uint32_t> cell_start;            // the hit copy: [B][ncell + 1] ...
+    DevBuf<float> sorted;                   // ... and [B][3][nsel_pad] (+ the parent's slack), zeroed when allocated
+    int built = 0;                          // for the current batch: 0 no, 1 the hit copy on built_grid, 2 the list-order flags
+    vmd_grid_t built_grid;
 };
 
 float* zero_volume_view(size_t nfloats);
@@ -495,6 +516,8 @@ struct PropState {
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
     bool within_empty = false;
+    // rdf over shells: the interned shell of either side (-1: that side is its static list, sel_a / sel_b)
+    int shell_of[2] = {-1, -1};
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh
@@ -693,6 +716,7 @@ struct vmd_script_eval_t {
     hipStream_t pair_stream = nullptr;       // every other block of a batch of frame blocks runs its pair kernel here
     hipEvent_t pair_fork = nullptr, pair_join = nullptr;
     std::vector<RdfGroup> rdf_groups;
+    std::vector<std::unique_ptr<Shell>> shells;         // within() shells that rdf arguments use
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;
@@ -771,7 +795,8 @@ struct vmd_script_eval_t {
     vmd_reduce_stats_t reduce_stats = {};
     // fixed at creation
     struct Spec { bool rdf_closed = false, sdf_include_self = false, sdf_density = false, dist_geometric_com = false, rdf_raw = false;
-            int rdf_norm = 0; bool angle_radians = false; bool within_closed = false, within_exclude_ref = false; } spec;
+            int rdf_norm = 0; bool angle_radians = false; bool within_closed = false, within_exclude_ref = false;
+            bool shell_norm = false; } spec;
     size_t atoms_checked = (size_t)-1;       // trajectory atom count the properties' indices were validated against (under mtx)
 };
 

@@ -18,7 +18,11 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     if (!ir) return 0;
     uint64_t w = 0;
     for (const Property& p : ir->props) {
-        if (p.kind == PROP_RDF) w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
+        if (p.kind == PROP_RDF) {
+            w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
+            // the parent sizes (a bound that needs no frame) plus one neighbour query per shell, |T| + |R|
+            for (int k = 0; k < 2; ++k) if (p.shell[k].on) w += (uint64_t)(k ? p.b : p.a).size() + (uint64_t)p.shell[k].ref.size();
+        }
         else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
@@ -236,6 +240,37 @@ extern "C" bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name
     return ir_add_rmsd(ir, name, P, idx, offsets);
 }
 
+// `name = rdf(T and within(a:b, R), target, {rmin, rmax});`: vmd_ir_add_rdf with either side a shell; the shells validated like
+// vmd_ir_add_within_count
+extern "C" bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const vmd_shell_t* ref_shell,
+                                     const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float rmin, float rmax) {
+    if (!ref_shell && !target_shell) return vmd_ir_add_rdf(ir, name, ref, nref, target, ntarget, rmin, rmax);
+    if (!ir_name_ok(ir, name) || !idx_ok(ref, nref, "rdf reference set") || !idx_ok(target, ntarget, "rdf target set")) return false;
+    if (!(rmin >= 0.0f) || !(rmax > rmin)) return vmd_fail("rdf range must satisfy 0 <= rmin < rmax");
+    if (nref > 0x7fffffff || ntarget > 0x7fffffff) return vmd_fail("within set too large");
+    const vmd_shell_t* sh[2] = {ref_shell, target_shell};
+    for (const vmd_shell_t* h : sh) {
+        if (!h) continue;
+        if (!idx_ok(h->ref, h->nref, "within reference set")) return false;
+        if (h->nref > 0x7fffffff) return vmd_fail("within set too large");
+        if (!std::isfinite(h->rmin) || !std::isfinite(h->rmax) || !(h->rmin >= 0.0f) || !(h->rmax > h->rmin))
+            return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
+    }
+    Property p;
+    p.name = name; p.kind = PROP_RDF; p.flags = VMD_PROPERTY_FLAG_DISTRIBUTION;
+    p.a.assign(ref, ref + nref); p.b.assign(target, target + ntarget);
+    p.rmin = rmin; p.rmax = rmax;
+    for (int k = 0; k < 2; ++k) {
+        if (!sh[k]) continue;
+        p.shell[k].on = true;
+        p.shell[k].ref.assign(sh[k]->ref, sh[k]->ref + sh[k]->nref);
+        p.shell[k].rmin = sh[k]->rmin; p.shell[k].rmax = sh[k]->rmax;
+    }
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
 // `name = count(T and within(rmin:rmax, R));`: one temporal property, one value per frame; validated like ir_add_geometry
 extern "C" bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
                                         const int32_t* ref, size_t nref, float rmin, float rmax) {
@@ -305,6 +340,13 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
         h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
         if (p.is_shape()) h = fnv1a(h, &p.shape_comp, sizeof(int));     // shape_weights only, as above
+        for (int k = 0; k < 2; ++k) {                                   // rdf over shells only, as above
+            if (!p.shell[k].on) continue;
+            const int32_t side = 0x5348454c + k;                        // "SHEL": which side carries the shell
+            h = fnv1a(h, &side, sizeof(side));
+            h = fnv1a(h, p.shell[k].ref.data(), p.shell[k].ref.size() * sizeof(int32_t));
+            h = fnv1a(h, &p.shell[k].rmin, sizeof(float)); h = fnv1a(h, &p.shell[k].rmax, sizeof(float));
+        }
     }
     h = h ? h : 1;
     ir->fingerprint = h;

@@ -13,7 +13,7 @@ bool check_atoms(vmd_script_eval_t* e, size_t num_atoms) {
         for (int32_t i : p->prop.b)
             if ((size_t)i >= num_atoms)
                 return vmd_fail("property '%s' references atom %d but the trajectory has %zu atoms", p->prop.name.c_str(), i, num_atoms);
-        for (const std::vector<int32_t>* v : {&p->prop.c, &p->prop.d})
+        for (const std::vector<int32_t>* v : {&p->prop.c, &p->prop.d, &p->prop.shell[0].ref, &p->prop.shell[1].ref})
             for (int32_t i : *v)
                 if ((size_t)i >= num_atoms)
                     return vmd_fail("property '%s' references atom %d but the trajectory has %zu atoms", p->prop.name.c_str(), i, num_atoms);

@@ -1905,11 +1905,15 @@ struct vmd_brute_params_t {
     vmd_binning_t bin;
     uint64_t* counts;
     int raw;            // DECISION(D-WRAP) flipped: positions as they are, minimum image by rounding (oracle: vo_set_spec("rdf_raw", 1))
+    const unsigned char* mref; const unsigned char* mtgt;     // MASKED: u8[B][nref] / u8[B][ntgt] per-frame masks, NULL = all
 };
 
+// MASKED: list entries whose byte is 0 take no part in that frame - a shell where no grid exists
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_rdf_brute(vmd_brute_params_t p) {
     __shared__ unsigned s_hist[VMD_MAX_BINS];
     __shared__ float s_t[3][256];
+    __shared__ unsigned char s_m[MASKED ? 256 : 1];
     const int b = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;
     const float* fx = p.xyz + (size_t)b * p.frame_stride;
@@ -1918,7 +1922,8 @@ __global__ __launch_bounds__(256) void k_rdf_brute(vmd_brute_params_t p) {
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
     for (int k = threadIdx.x; k < p.bin.nbins; k += 256) s_hist[k] = 0u;
     float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
-    const bool valid = t < p.nref;
+    bool valid = t < p.nref;
+    if (MASKED) { if (valid && p.mref) valid = p.mref[(size_t)b * p.nref + t] != 0; }
     if (valid) {
         const int a = p.ref ? p.ref[t] : t;
         if (p.raw) { xi = fx[a]; yi = fy[a]; zi = fz[a]; }
@@ -1931,11 +1936,13 @@ __global__ __launch_bounds__(256) void k_rdf_brute(vmd_brute_params_t p) {
             const int a = p.tgt ? p.tgt[j] : j;
             if (p.raw) { s_t[0][threadIdx.x] = fx[a]; s_t[1][threadIdx.x] = fy[a]; s_t[2][threadIdx.x] = fz[a]; }
             else vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_t[0][threadIdx.x], s_t[1][threadIdx.x], s_t[2][threadIdx.x]);
+            if (MASKED) s_m[threadIdx.x] = p.mtgt ? p.mtgt[(size_t)b * p.ntgt + j] : 1;
         }
         __syncthreads();
         const int nj = p.ntgt - j0 < 256 ? p.ntgt - j0 : 256;
         if (valid) {
             for (int jj = 0; jj < nj; ++jj) {
+                if (MASKED) { if (!s_m[jj]) continue; }
                 float d2;
                 if (p.raw && !bx.tri) {
                     float dx = xi - s_t[0][jj], dy = yi - s_t[1][jj], dz = zi - s_t[2][jj];
@@ -1979,10 +1986,13 @@ struct vmd_within_brute_params_t {
     const int32_t* tgt; int ntgt; const int32_t* ref; int nref;
     vmd_within_test_t w;
     unsigned* count;
+    unsigned char* flags;       // FLAGS instantiation: u8[B][ntgt], 1 = the list entry is in the shell
 };
 
 // all pairs from the raw frame (any cell, any cutoff): one lane per target atom, the reference set staged through LDS in tiles of 256, a
 // lane stops testing at its first hit.  One integer atomic per wave.  The device-side definition the cell walk below is tested against.
+// FLAGS: also one byte per list entry, in list order - the mask vmd_hip_rdf_brute_masked takes.
+template <bool FLAGS>
 __global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t p) {
     __shared__ float s_r[3][256];
     const int b = blockIdx.y;
@@ -2011,6 +2021,7 @@ __global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t 
             for (int jj = 0; jj < nj && !hit; ++jj)
                 hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
     }
+    if (FLAGS) { if (valid) p.flags[(size_t)b * p.ntgt + t] = hit ? 1 : 0; }
     const unsigned long long m = __ballot(hit ? 1 : 0);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
 }
@@ -2022,12 +2033,17 @@ struct vmd_within_pencil_params_t {
     vmd_within_test_t w; float rpad;
     uint32_t pbc; int ry, rz;
     unsigned* count; const uint32_t* skip;
+    // FLAGS instantiation: u8[B][ntgt_pad], one byte per SORTED position of the target copy; u32[B][npen + 1], the hits of
+    // every pencil (entry npen is not written: the scan's total goes there)
+    unsigned char* flags; uint32_t* pen_hits;
 };
 
 // the cell walk: one block (one wave) per (frame, pencil), one lane per target atom of the pencil.  Both sets come cell-sorted (K1), so
 // the x window [x - r, x + r] of a neighbour pencil is one run of the sorted reference copy per periodic image; pencils, images, window
 // arithmetic and the pair arithmetic are those of k_rdf_pencil (the neighbour cell's image is the comparison's for every d < r_max), with
 // the window of ONE atom instead of a chunk's.  A lane leaves the walk at its first hit.
+// FLAGS: the same walk also says WHICH sorted entries are in - what k_shell_compact turns into a selection of its own.
+template <bool FLAGS>
 __global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t p) {
     if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch
     const int lane = threadIdx.x;
@@ -2096,9 +2112,59 @@ __global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t
                 }
             }
         }
+        if (FLAGS) { if (i < pend) p.flags[(size_t)b * p.ntgt_pad + i] = hit ? 1 : 0; }
         total += (unsigned)__popcll(__ballot(hit ? 1 : 0));
     }
+    if (FLAGS) { if (lane == 0) p.pen_hits[(size_t)b * (ny * nz + 1) + pen] = total; }
     if (lane == 0 && total) atomicAdd(&p.count[b], total);
+}
+
+// ------------------------------------------------------------------------------------------------ K7: shells as selections
+
+// Stream compaction of a cell-sorted copy: the entries k_within_pencil<true> flagged, in place order, become a second sorted copy with its
+// own cell_start on the SAME grid - a selection k_rdf_pencil takes unchanged.  One wave per (frame, pencil); pen_base is the exclusive
+// prefix of the pencils' hit counts (k_cells_scan), so a pencil's output is one contiguous run starting there: a chunk of 64 flags is one
+// ballot, an entry's place is the run so far plus the hits below its lane, and a cell's start is the same count taken at the cell's first
+// position.  Stable within every cell.  Entries beyond a frame's population keep whatever an earlier batch left there (finite coordinates
+// or the zeros of the allocation): k_rdf_pencil reads past a segment only into columns it moves out of every cutoff (x = -VMD_FAR), the same
+// terms on which it reads the slack behind a parent's rows.
+struct vmd_shell_compact_params_t {
+    const unsigned char* flags; const uint32_t* pen_base;
+    const float* sorted; const uint32_t* cs; int nsel_pad;
+    float* sorted_hit; uint32_t* cs_hit;
+    int B; vmd_grid_t grid; const uint32_t* skip;
+};
+
+__global__ __launch_bounds__(64) void k_shell_compact(vmd_shell_compact_params_t p) {
+    if (p.skip && *p.skip) return;       // the flags were not written either
+    const int lane = threadIdx.x;
+    const int b = blockIdx.y, pen = blockIdx.x;
+    const int nxf = p.grid.nxf, npen = p.grid.ny * p.grid.nz;
+    const uint32_t* cs = p.cs + (size_t)b * (p.grid.ncell + 1) + (size_t)pen * nxf;
+    uint32_t* csh = p.cs_hit + (size_t)b * (p.grid.ncell + 1) + (size_t)pen * nxf;
+    const unsigned char* fl = p.flags + (size_t)b * p.nsel_pad;
+    const float* sx = p.sorted + (size_t)b * 3 * p.nsel_pad;
+    float* hx = p.sorted_hit + (size_t)b * 3 * p.nsel_pad;
+    const unsigned pbeg = cs[0], pend = cs[nxf];
+    unsigned run = p.pen_base[(size_t)b * (npen + 1) + pen];
+    for (unsigned i0 = pbeg; i0 < pend; i0 += VMD_WAVE) {
+        const unsigned i = i0 + lane;
+        const bool h = i < pend && fl[i] != 0;
+        const unsigned long long m = __ballot(h ? 1 : 0);
+        if (h) {
+            const unsigned dst = run + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+            hx[dst] = sx[i];
+            hx[p.nsel_pad + dst] = sx[p.nsel_pad + i];
+            hx[2 * (size_t)p.nsel_pad + dst] = sx[2 * (size_t)p.nsel_pad + i];
+        }
+        for (int c = lane; c < nxf; c += VMD_WAVE) {          // the cells that begin inside this chunk
+            const unsigned s = cs[c];
+            if (s >= i0 && s < i0 + VMD_WAVE && s < pend) csh[c] = run + (unsigned)__popcll(m & ((1ull << (s - i0)) - 1ull));
+        }
+        run += (unsigned)__popcll(m);
+    }
+    for (int c = lane; c < nxf; c += VMD_WAVE) if (cs[c] >= pend) csh[c] = run;       // empty cells at the pencil's end, an empty pencil
+    if (pen == npen - 1 && lane == 0) csh[nxf] = run;                                   // cell_start[ncell]: the frame's population
 }
 
 __global__ __launch_bounds__(256) void k_within_to_float(const unsigned* count, int B, float* out, const uint32_t* skip) {
@@ -3668,9 +3734,42 @@ extern "C" int vmd_hip_rdf_brute(void* stream, const float* xyz, size_t frame_st
     hipStream_t s = (hipStream_t)stream;
     if (nbins <= 0 || nbins > VMD_MAX_BINS) return (int)hipErrorInvalidValue;
     if (B <= 0 || nref <= 0 || ntgt <= 0) return 0;
-    vmd_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, ref, nref, tgt, ntgt, {}, counts, g_rdf_raw};
+    vmd_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, ref, nref, tgt, ntgt, {}, counts, g_rdf_raw, nullptr, nullptr};
     p.bin = vmd_make_binning(rmin, rmax, nbins, g_rdf_closed);
-    hipLaunchKernelGGL(k_rdf_brute, dim3((nref + 255) / 256, B), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_rdf_brute<false>, dim3((nref + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_rdf_brute_masked(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                        const float* boxes, uint32_t pbc_flags, int B,
+                                        const int32_t* ref, int nref, const uint8_t* ref_mask, const int32_t* tgt, int ntgt,
+                                        const uint8_t* tgt_mask, float rmin, float rmax, int nbins, uint64_t* counts) {
+    hipStream_t s = (hipStream_t)stream;
+    if (nbins <= 0 || nbins > VMD_MAX_BINS) return (int)hipErrorInvalidValue;
+    if (B <= 0 || nref <= 0 || ntgt <= 0) return 0;
+    if (B > 65535) return (int)hipErrorInvalidValue;
+    vmd_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, ref, nref, tgt, ntgt, {}, counts, g_rdf_raw, ref_mask, tgt_mask};
+    p.bin = vmd_make_binning(rmin, rmax, nbins, g_rdf_closed);
+    hipLaunchKernelGGL(k_rdf_brute<true>, dim3((nref + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+static int vmd_within_brute_launch(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                    const float* boxes, uint32_t pbc_flags, int B,
+                                    const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                                    float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* flags_out) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !count_out) return (int)hipErrorInvalidValue;
+    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    if (ntgt <= 0 || nref <= 0) return 0;
+    vmd_within_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref,
+                                vmd_make_within_test(rmin, rmax, closed), count_out, flags_out};
+    if (flags_out) hipLaunchKernelGGL(k_within_brute<true>, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_within_brute<false>, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }
@@ -3679,29 +3778,30 @@ extern "C" int vmd_hip_within_brute(void* stream, const float* xyz, size_t frame
                                     const float* boxes, uint32_t pbc_flags, int B,
                                     const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
                                     float rmin, float rmax, int closed, uint32_t* count_out) {
-    hipStream_t s = (hipStream_t)stream;
-    if (B <= 0) return 0;
-    if (B > 65535 || !count_out) return (int)hipErrorInvalidValue;
-    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
-    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
-    if (ntgt <= 0 || nref <= 0) return 0;
-    vmd_within_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref,
-                                vmd_make_within_test(rmin, rmax, closed), count_out};
-    hipLaunchKernelGGL(k_within_brute, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
-    VMD_LAUNCH_CHECK();
-    return 0;
+    return vmd_within_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref, rmin, rmax, closed,
+                                   count_out, nullptr);
 }
 
-extern "C" int vmd_hip_within_pencil(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+extern "C" int vmd_hip_within_brute_flags(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                          const float* boxes, uint32_t pbc_flags, int B,
+                                          const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                                          float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* flags_out) {
+    if (!flags_out) return (int)hipErrorInvalidValue;
+    return vmd_within_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref, rmin, rmax, closed,
+                                   count_out, flags_out);
+}
+
+static int vmd_within_pencil_launch(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
                                      const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
                                      const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
-                                     uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag) {
+                                     uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag,
+                                     uint8_t* flags_out, uint32_t* pen_hits_out) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     if (B > 65535 || !count_out || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0) return (int)hipErrorInvalidValue;
     if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
-    if (ntgt <= 0 || nref <= 0) return 0;
+    if ((ntgt <= 0 || nref <= 0) && !flags_out) return 0;
     vmd_within_pencil_params_t p;
     p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
     p.stgt = sorted_tgt; p.cs_tgt = cell_start_tgt; p.ntgt_pad = ntgt_pad;
@@ -3710,7 +3810,44 @@ extern "C" int vmd_hip_within_pencil(void* stream, const float* sorted_ref, cons
     p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_rdf_pencil
     p.pbc = pbc_flags; p.ry = g_pen_ry; p.rz = g_pen_rz;
     p.count = count_out; p.skip = skip_flag;
-    hipLaunchKernelGGL(k_within_pencil, dim3(grid.ny * grid.nz, B), dim3(VMD_WAVE), 0, s, p);
+    p.flags = flags_out; p.pen_hits = pen_hits_out;
+    if (flags_out) hipLaunchKernelGGL(k_within_pencil<true>, dim3(grid.ny * grid.nz, B), dim3(VMD_WAVE), 0, s, p);
+    else hipLaunchKernelGGL(k_within_pencil<false>, dim3(grid.ny * grid.nz, B), dim3(VMD_WAVE), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_within_pencil(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+                                     const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
+                                     const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
+                                     uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag) {
+    return vmd_within_pencil_launch(stream, sorted_ref, cell_start_ref, nref, nref_pad, sorted_tgt, cell_start_tgt, ntgt, ntgt_pad, boxes, B,
+                                    grid, rmin, rmax, closed, pbc_flags, count_out, skip_flag, nullptr, nullptr);
+}
+
+extern "C" int vmd_hip_within_pencil_flags(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
+                                           const float* sorted_tgt, const uint32_t* cell_start_tgt, int ntgt, int ntgt_pad,
+                                           const float* boxes, int B, vmd_grid_t grid, float rmin, float rmax, int closed,
+                                           uint32_t pbc_flags, uint32_t* count_out, const uint32_t* skip_flag,
+                                           uint8_t* flags_out, uint32_t* pen_hits_out) {
+    if (!flags_out || !pen_hits_out || ntgt <= 0 || nref <= 0) return (int)hipErrorInvalidValue;
+    return vmd_within_pencil_launch(stream, sorted_ref, cell_start_ref, nref, nref_pad, sorted_tgt, cell_start_tgt, ntgt, ntgt_pad, boxes, B,
+                                    grid, rmin, rmax, closed, pbc_flags, count_out, skip_flag, flags_out, pen_hits_out);
+}
+
+extern "C" int vmd_hip_shell_compact(void* stream, const uint8_t* flags, const uint32_t* pen_hits, uint32_t* pen_base,
+                                     const float* sorted, const uint32_t* cell_start, int nsel_pad, int B, vmd_grid_t grid,
+                                     float* sorted_hit, uint32_t* cell_start_hit, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !flags || !pen_hits || !pen_base || !sorted || !cell_start || !sorted_hit || !cell_start_hit || nsel_pad <= 0 ||
+        grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 || grid.ncell != grid.nxf * grid.ny * grid.nz) return (int)hipErrorInvalidValue;
+    const int npen = grid.ny * grid.nz;
+    // exclusive prefix of the pencils' hit counts, one block per frame: the cell build's own scan over a table of npen entries
+    hipLaunchKernelGGL(k_cells_scan, dim3(B), dim3(1024), 0, s, pen_hits, pen_base, npen);
+    VMD_LAUNCH_CHECK();
+    vmd_shell_compact_params_t p{flags, pen_base, sorted, cell_start, nsel_pad, sorted_hit, cell_start_hit, B, grid, skip_flag};
+    hipLaunchKernelGGL(k_shell_compact, dim3(npen, B), dim3(VMD_WAVE), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

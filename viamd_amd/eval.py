@@ -82,6 +82,25 @@ class ScriptIR:
         t, tp = _idx(target)
         self._check(self.lib.vmd_ir_add_rdf(self.h, name.encode(), rp, r.size, tp, t.size, float(rmin), float(cutoff)))
 
+    def add_rdf_shell(self, name, ref, target, cutoff, rmin=0.0, ref_shell=None, target_shell=None):
+        """`name = rdf(ref and within(a:b, R), target, cutoff)`: either side may be a shell, given as (R, r_min, r_max) - per
+        frame, the atoms of that side's list with some atom of R at r_min <= d < r_max.  Both None: add_rdf."""
+        if not np.isscalar(cutoff):
+            rmin, cutoff = cutoff
+        import ctypes as C
+        r, rp = _idx(ref)
+        t, tp = _idx(target)
+        keep, ptrs = [], []
+        for sh in (ref_shell, target_shell):
+            if sh is None:
+                ptrs.append(None)
+                continue
+            x, xp = _idx(sh[0])
+            c = L.ShellC(xp, x.size, float(sh[1]), float(sh[2]))
+            keep.append((x, c))
+            ptrs.append(C.byref(c))
+        self._check(self.lib.vmd_ir_add_rdf_shell(self.h, name.encode(), rp, r.size, ptrs[0], tp, t.size, ptrs[1], float(rmin), float(cutoff)))
+
     def add_sdf(self, name, structures, target, cutoff):
         """`name = sdf(structures, target, cutoff)`; structures: [K, m] atom indices."""
         s = np.ascontiguousarray(structures, dtype=np.int32)

@@ -269,9 +269,10 @@ FEATURE_ANGLES = 1                              # VMD_SCRIPT_FEATURE_ANGLES
 FEATURE_SHAPE = 2                               # VMD_SCRIPT_FEATURE_SHAPE
 FEATURE_RMSD = 4                                # VMD_SCRIPT_FEATURE_RMSD
 FEATURE_WITHIN = 8                              # VMD_SCRIPT_FEATURE_WITHIN
+FEATURE_SHELL_RDF = 16                          # VMD_SCRIPT_FEATURE_SHELL_RDF
 
 
-def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -290,7 +291,11 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
 
     within=True (VMD_SCRIPT_FEATURE_WITHIN, opt-in): `name = count(<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...])`:
     exactly one within() factor at the top level of the AND, everything else static;
-    info[name] = dict(kind="within_count", target=idx, ref=idx, rmin=, rmax=)."""
+    info[name] = dict(kind="within_count", target=idx, ref=idx, rmin=, rmax=).
+
+    shell_rdf=True (VMD_SCRIPT_FEATURE_SHELL_RDF, opt-in): either selection argument of rdf() may be such an AND (DESIGN 1.7);
+    info[name] = dict(kind="rdf", ref=idx, target=idx, rmin=, rmax=, ref_shell=, target_shell=), a shell being None (that side is its
+    static list) or dict(ref=idx, rmin=, rmax=)."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -334,7 +339,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("=")
                 if shape and p.peek() == ("id", "shape_weights"):
                     raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within)
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -529,7 +534,59 @@ def _count_statement(p, name, topo, env, ir, info):
     return commit
 
 
-def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False):
+def _dyn_arg(p, name, topo):
+    """one selection argument of rdf() under shell_rdf=True (the twin of dyn_arg in vmd_script.cpp) -> (index list, shell or None)"""
+    start = p.i
+    n_within = n_top = depth = 0
+    top_or = False
+    for q in range(start, len(p.t)):
+        k, v = p.t[q]
+        if k == "op" and v in (",", ";") and depth == 0:
+            break
+        if k == "op" and v == "(":
+            depth += 1
+        if k == "op" and v == ")":
+            if depth == 0:
+                break
+            depth -= 1
+        if (k, v) == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "("):
+            n_within += 1
+            if depth == 0 and (q == start or p.t[q - 1] == ("id", "and")):
+                n_top += 1
+        if (k, v) == ("id", "or") and depth == 0:
+            top_or = True
+    if n_within == 0:
+        return p.sel_or().indices(), None
+    if n_within > 1:
+        raise ScriptError(f"{name}: an rdf argument takes exactly one within() factor, found {n_within}")
+    if n_top != 1 or top_or:
+        raise ScriptError(f"{name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
+    tmask = np.ones(topo.num_atoms, bool)
+    ref, rmin, rmax = None, 0.0, 0.0
+    while True:
+        if p.peek() == ("id", "within"):
+            p.i += 1
+            p.take("(")
+            rmax = p.number()
+            if p.accept(":"):
+                rmin, rmax = rmax, p.number()
+                if not rmin < rmax:
+                    raise ScriptError(f"{name}: within range needs 0 <= a < b")
+            elif not rmax > 0.0:
+                raise ScriptError(f"{name}: within needs a radius > 0")
+            p.take(",")
+            ref = p.sel_or().indices()
+            p.take(")")
+            if ref.size == 0:
+                raise ScriptError(f"{name}: empty selection")
+        else:
+            tmask = tmask & p.sel_not().mask
+        if not p.accept("and"):
+            break
+    return np.nonzero(tmask)[0].astype(np.int32), dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
+
+
+def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
@@ -542,6 +599,28 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
         return _rmsd_statement(p, name, topo, env, ir, info), True
     if v == "count":
         return _count_statement(p, name, topo, env, ir, info), True
+    if v == "rdf" and shell_rdf:
+        a, sha = _dyn_arg(p, name, topo); p.take(",")
+        b, shb = _dyn_arg(p, name, topo); p.take(",")
+        if p.accept("{"):
+            rmin = p.number(); p.take(","); rmax = p.number(); p.take("}")
+        else:
+            rmin, rmax = 0.0, p.number()
+            if p.accept(":"):
+                rmin, rmax = rmax, p.number()
+        p.take(")")
+        if a.size == 0 or b.size == 0:
+            raise ScriptError(f"{name}: empty selection")
+
+        def commit():
+            if sha is None and shb is None:
+                ir.add_rdf(name, a, b, (rmin, rmax))
+                info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax)
+                return
+            ir.add_rdf_shell(name, a, b, (rmin, rmax), ref_shell=sha and (sha["ref"], sha["rmin"], sha["rmax"]),
+                             target_shell=shb and (shb["ref"], shb["rmin"], shb["rmax"]))
+            info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax, ref_shell=sha, target_shell=shb)
+        return commit, True
     if v == "rdf":
         ref = p.sel_or(); p.take(",")
         tgt = p.sel_or(); p.take(",")
@@ -637,16 +716,16 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
     VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD; within=True: with
-    VMD_SCRIPT_FEATURE_WITHIN."""
+    VMD_SCRIPT_FEATURE_WITHIN; shell_rdf=True: with VMD_SCRIPT_FEATURE_SHELL_RDF."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
     features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0) | \
-        (FEATURE_WITHIN if within else 0)
+        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
