@@ -252,6 +252,12 @@ bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_
 typedef struct vmd_shell_t { const int32_t* ref; size_t nref; float rmin, rmax; } vmd_shell_t;
 bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const vmd_shell_t* ref_shell,
                           const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float rmin, float rmax);
+/* `name = sdf(<structures>, <T> and within(a:b, <R>), cutoff);`: an sdf whose TARGET is a shell - per frame, only the atoms of
+ * `target` that are members (the membership of vmd_ir_add_within_count) are scattered; the structures are always static (the alignment
+ * needs fixed atoms).  The record is an sdf's; a frame whose shell is empty adds no voxels but is an evaluated frame.  target_shell NULL:
+ * vmd_ir_add_sdf, with its fingerprint.  Validation as vmd_ir_add_sdf plus, for the shell, that of vmd_ir_add_within_count. */
+bool vmd_ir_add_sdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
+                          const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float cutoff);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count: returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
@@ -307,12 +313,15 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
  * VMD_SCRIPT_FEATURE_WITHIN also compiles `name = count(<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]);`: exactly
  * one within() factor at the top level of the AND, every other factor and its argument a static selection.
  * VMD_SCRIPT_FEATURE_SHELL_RDF lets either selection argument of rdf() be such an AND, `<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]`
- * (DESIGN 1.7), under the same rules; sdf() and the distance family keep answering "unsupported function 'within'". */
+ * (DESIGN 1.7), under the same rules.
+ * VMD_SCRIPT_FEATURE_SHELL_SDF lets the TARGET argument of sdf() be such an AND, under the same rules; within() in the structures
+ * argument is refused with a reason of its own, and the distance family keeps answering "unsupported function 'within'". */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
 #define VMD_SCRIPT_FEATURE_SHAPE 2u
 #define VMD_SCRIPT_FEATURE_RMSD 4u
 #define VMD_SCRIPT_FEATURE_WITHIN 8u
 #define VMD_SCRIPT_FEATURE_SHELL_RDF 16u
+#define VMD_SCRIPT_FEATURE_SHELL_SDF 32u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -406,6 +415,19 @@ typedef struct vmd_sdf_payload_t {
 } vmd_sdf_payload_t;
 bool vmd_eval_sdf_payload(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
                           vmd_sdf_payload_t* out);
+
+/* The members of a within() shell at ONE frame, in atom order: what a host highlights as the dynamic selection of the displayed
+ * frame.  `name` is a count(... within ...) property, an rdf over shells or an sdf over a shell; `which` selects the side: 0 = the reference
+ * argument (rdf only), 1 = the target argument (rdf, sdf; the counted set of a count).  Bit a of `words` (word a / 64, bit a % 64) is atom a;
+ * (num_atoms + 63) / 64 words are needed, and all of them are written.  Returns the number of members - 0 is a legitimate answer - or
+ * VMD_SHELL_MASK_FAILED ((size_t)-1) with vmd_last_error set: unknown property, a property or side that is not a shell, a frame outside the
+ * trajectory, a device error, or `cap` too small (nothing is written then).  The frame is evaluated on demand, the way vmd_eval_sdf_payload
+ * evaluates its frame: accumulated results, fingerprints and the frame mask are untouched, and the call may come while pool threads are
+ * inside vmd_eval_frame_range (it takes its turn between their batches).  Membership is vmd_ir_add_within_count's (spec_within_closed,
+ * spec_within_exclude_ref as they stood when the eval was created). */
+#define VMD_SHELL_MASK_FAILED ((size_t)-1)
+size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name, int which, const vmd_system_t* sys, vmd_trajectory_i* traj,
+                           uint32_t frame, uint64_t* words, size_t cap);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

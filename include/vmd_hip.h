@@ -19,6 +19,7 @@
  *   vmd_hip_rmsd      <- rmsd
  *   vmd_hip_within_*  <- count(sel and within(r, sel))
  *   vmd_hip_within_*_flags, vmd_hip_shell_compact, vmd_hip_rdf_brute_masked  <- rdf() over within() shells
+ *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -241,6 +242,34 @@ int vmd_hip_rdf_brute_masked(void* stream, const float* xyz, size_t frame_stride
                              const float* boxes, uint32_t pbc_flags, int B,
                              const int32_t* ref, int nref, const uint8_t* ref_mask, const int32_t* tgt, int ntgt,
                              const uint8_t* tgt_mask, float rmin, float rmax, int nbins, uint64_t* counts);
+
+/* K8: a within() shell's members BY ATOM, DESIGN 1.8.  mask_out is u8[B][mask_stride] indexed by atom index: mask_out[b][tgt[t]] = 1 when
+ * entry t of the target list is in the shell of frame b, else 0 - the membership of vmd_hip_within_brute_flags, bit for bit.  The calls write
+ * the bytes of the atoms of `tgt` and nothing else: whoever allocates the mask zeroes it once if bytes of other atoms are ever read (the
+ * evaluator does, for a target list that lost its reference atoms to spec_within_exclude_ref); mask_stride must exceed every index of tgt.
+ * count_out u32[B] (zeroed by the call) = the per-frame populations.  B <= 65535.
+ *   vmd_hip_within_atoms        the cell walk with only the REFERENCE set cell-sorted (K1; `boxes`, pbc_flags and grid those of its build, the
+ *                               pencil reach set by vmd_hip_set_pencil_reach): one lane per list entry reads the raw frame, wraps the atom and
+ *                               finds its pencil as a cell build would.  Nothing but the zeroing of count_out happens when *skip_flag != 0
+ *   vmd_hip_within_brute_atoms  all pairs from the raw frame (any cell, any cutoff), vmd_hip_within_brute_flags with the bytes in atom order
+ *   vmd_hip_sdf_scatter_masked  vmd_hip_sdf_scatter for a shell target: a target atom whose mask byte of frame b is 0 takes no part in frame b;
+ *                               exclusion rule, arithmetic and atomics are vmd_hip_sdf_scatter's.  Always the index-list / progression kernel
+ *                               (no atom_tag, none of the tuning variants).  Does nothing when *skip_flag != 0 */
+int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                         const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
+                         const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad, vmd_grid_t grid,
+                         float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* mask_out, size_t mask_stride,
+                         const uint32_t* skip_flag);
+int vmd_hip_within_brute_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                               const float* boxes, uint32_t pbc_flags, int B,
+                               const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                               float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* mask_out, size_t mask_stride);
+int vmd_hip_sdf_scatter_masked(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                               const float* boxes, uint32_t pbc_flags, int B,
+                               const int32_t* structs, int K, int m, const float* R32, const float* c32,
+                               const int32_t* tgt, const int8_t* owner, int ntgt, float extent, int dim, uint64_t* volume,
+                               const float* group, int tgt_first, int tgt_stride, int unowned,
+                               const uint8_t* mask, size_t mask_stride, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -677,7 +677,7 @@ inline const md_script_vis_payload_o* VMD_SHIM_PREFIX(md_script_ir_property_vis_
  * VIAMD draws the volume in: density_volume.cpp:190-204, 263-269; export_cube, src/main.cpp:5751-5803), MD_SCRIPT_VISUALIZE_ATOMS adds
  * the atoms of the reference structures to vis->atom_mask (src/viamd.cpp:3205-3207).  subidx >= 0 selects one structure.  An angle() /
  * dihedral() property the host compiled with VMD_SCRIPT_FEATURE_ANGLES gets MD_SCRIPT_VISUALIZE_ATOMS too: the atoms of its argument
- * sets (subidx >= 0: of one context); so does each name of a shape_weights() statement (VMD_SCRIPT_FEATURE_SHAPE) and an rmsd() property (VMD_SCRIPT_FEATURE_RMSD): its selection; a count(... within ...) property (VMD_SCRIPT_FEATURE_WITHIN): its reference and target sets (an rdf over shells, VMD_SCRIPT_FEATURE_SHELL_RDF, is an rdf: no atoms).  Payloads of other property kinds return false (their highlighting is mdlib's own, INTEGRATION.md
+ * sets (subidx >= 0: of one context); so does each name of a shape_weights() statement (VMD_SCRIPT_FEATURE_SHAPE) and an rmsd() property (VMD_SCRIPT_FEATURE_RMSD): its selection; a count(... within ...) property (VMD_SCRIPT_FEATURE_WITHIN): its reference and target sets (an rdf over shells, VMD_SCRIPT_FEATURE_SHELL_RDF, is an rdf: no atoms; an sdf over a shell, VMD_SCRIPT_FEATURE_SHELL_SDF, is an sdf: its structures; the members of a shell at one frame are vmd_eval_shell_mask's).  Payloads of other property kinds return false (their highlighting is mdlib's own, INTEGRATION.md
  * section 3). */
 inline bool VMD_SHIM_PREFIX(md_script_vis_eval_payload)(md_script_vis_t* vis, const md_script_vis_payload_o* payload, int subidx,
                                                         const md_script_vis_ctx_t* ctx, md_script_vis_flags_t flags) {

@@ -71,6 +71,9 @@ class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
     _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
 
 
+SHELL_MASK_FAILED = C.c_size_t(-1).value      # VMD_SHELL_MASK_FAILED (include/vmd_eval.h)
+
+
 class XtcFrame(C.Structure):             # vmd_xtc_frame_t (include/vmd_hip.h)
     _fields_ = [("precision", C.c_float), ("minint", C.c_int32 * 3), ("maxint", C.c_int32 * 3), ("smallidx", C.c_int32),
                 ("offset", C.c_uint64), ("nbytes", C.c_uint64)]
@@ -163,6 +166,8 @@ SIGNATURES = [
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
+    ("vmd_ir_add_sdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.c_size_t, c_int32_p, C.c_size_t, C.POINTER(ShellC),
+                                        C.c_float]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -200,6 +205,8 @@ SIGNATURES = [
     ("vmd_eval_set_settled_callback", C.c_bool, [_vp, SETTLED_FN, C.c_void_p]),
     ("vmd_eval_set_frame_mask", None, [_vp, c_uint8_p, C.c_size_t]),
     ("vmd_eval_sdf_structures", c_int32_p, [_vp, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("vmd_eval_shell_mask", C.c_size_t, [_vp, C.c_char_p, C.c_int, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32,
+                                         C.POINTER(C.c_uint64), C.c_size_t]),
     ("vmd_eval_sdf_payload", C.c_bool, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, C.POINTER(SdfPayload)]),
     ("vmd_export_xvg", C.c_bool, [C.c_char_p, C.POINTER(c_float_p), C.POINTER(C.c_char_p), C.c_size_t, C.c_size_t]),
     ("vmd_export_csv", C.c_bool, [C.c_char_p, C.POINTER(c_float_p), C.POINTER(C.c_char_p), C.c_size_t, C.c_size_t]),
@@ -350,6 +357,13 @@ SIGNATURES = [
     ("vmd_hip_shell_compact", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, Grid, _vp, _vp, _vp]),
     ("vmd_hip_rdf_brute_masked", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
                                            _vp, C.c_float, C.c_float, C.c_int, _vp]),
+    ("vmd_hip_within_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int,
+                                       Grid, C.c_float, C.c_float, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    ("vmd_hip_within_brute_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                             C.c_float, C.c_float, C.c_int, _vp, _vp, C.c_size_t]),
+    ("vmd_hip_sdf_scatter_masked", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp,
+                                             _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
+                                             _vp]),
     ("vmd_hip_add_u64", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("vmd_hip_counts_to_float", C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_float]),
     ("vmd_hip_bump_u64", C.c_int, [_vp, _vp, C.c_uint64]),

@@ -128,7 +128,13 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     for (int pi : e->within_props) { if (e->props[pi]->sel_a >= 0) used[e->props[pi]->sel_a] = 1; used[e->props[pi]->sel_b] = 1; }
     for (auto& g : e->rdf_groups) for (int pi : g.shell_props) for (int sl : {e->props[pi]->sel_a, e->props[pi]->sel_b}) if (sl >= 0) used[sl] = 1;
     // a shell keeps a hit copy the size of its parent's sorted rows, one byte per entry and its tables
-    for (auto& h : e->shells) { used[h->sel_r] = 1; if (h->sel_t >= 0) per_frame += 24 * e->sels[h->sel_t]->idx.size(); }
+    // ... and an sdf over it one byte per atom of the frame, the mask in atom order; R is sorted for either
+    for (auto& h : e->shells) {
+        used[h->sel_r] = 1;
+        if (h->sel_t < 0) continue;
+        if (h->rdf_use) per_frame += 24 * e->sels[h->sel_t]->idx.size();
+        if (h->sdf_use) per_frame += num_atoms + 64;
+    }
     for (size_t i = 0; i < e->sels.size(); ++i) if (used[i]) per_frame += 40 * e->sels[i]->idx.size();
     for (auto& p : e->props) per_frame += p->prop.kind == PROP_SDF ? 64 * p->prop.K : (p->prop.kind == PROP_DIST ? 4 * p->dim1 : 0);
     // 288 GB of HBM: a 16 GB scratch budget holds the 1 000 frames of the 1M-atom RDF (333k selected atoms) in ONE batch
@@ -137,7 +143,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     // pair passes are long (a 1 024-frame batch of the 1M-atom RDF runs ~90 ms: interrupts are polled between batches); scripts
     // without them stream whole frames at HBM speed and take much larger batches, so that launches, the alignment kernel's
     // latency and the per-batch synchronisation stay small against the stream (grid.y = frames of the batch <= 65535)
-    const size_t cap = (e->rdf_groups.empty() && e->within_props.empty()) ? 16384 : 1024;
+    const size_t cap = (e->rdf_groups.empty() && e->within_props.empty() && e->shell_sdf_props.empty()) ? 16384 : 1024;
     B = std::max<size_t>(1, std::min<size_t>(B, cap));
     return B;
 }
@@ -464,6 +470,24 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         std::vector<Commit> commits;
         size_t row = 0;
         bool forked = false;
+        // The grid of this batch for radius r, and the boxes it is cut from: fully periodic cells use the frame boxes; open axes (non-periodic
+        // systems, slabs) span the batch's bounding box.  `lanes` is the size of the sparsest list a walk over this grid puts in its lanes
+        // (the denser of the two sides of every pass); its density against the first frame's cell decides the pencil split, so that equal
+        // radii over equal selections meet on equal grids whoever asks.  -> 1 a grid, 0 none (all pairs), -1 an error
+        auto grid_for = [&](size_t lanes, float r, vmd_grid_t* grid, const float** d_gb) -> int {
+            const bool open_axes = (c.pbc & 8u) == 0 && (c.pbc & VMD_UNITCELL_PBC_ALL) != VMD_UNITCELL_PBC_ALL;
+            if (open_axes && !g_opt.force_brute && !prepare_open_boxes(e, *c.src, c.nb, c.pbc, num_atoms)) return -1;
+            const bool gboxes = open_axes && c.src->gboxes_ready;
+            const std::vector<float>& gb = gboxes ? c.src->h_gboxes : c.src->h_boxes;
+            *d_gb = gboxes ? c.src->d_gboxes.p : c.src->d_boxes.p;
+            bool dense_lanes = !open_axes;
+            if (dense_lanes) {
+                const float* q = gb.data();
+                const double vol = (double)q[0] * q[1] * q[2];
+                dense_lanes = vol > 0.0 && (double)lanes / vol >= 0.08;
+            }
+            return choose_grid(gb, c.pbc, c.nb, r, grid, dense_lanes) ? 1 : 0;
+        };
         // ---- shells as rdf arguments.  One walk + one compaction per shell, batch and grid, whichever properties use it; the
         // per-frame populations travel to the host from here, behind the overflow flag like everything else of launch_rdf.
         for (auto& h : e->shells) h->built = 0;
@@ -541,29 +565,19 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
         };
         for (auto& g : e->rdf_groups) {
             vmd_grid_t grid;
-            // fully periodic cells use the frame boxes; open axes (non-periodic systems, slabs) span the batch's bounding box
-            const bool open_axes = (c.pbc & 8u) == 0 && (c.pbc & VMD_UNITCELL_PBC_ALL) != VMD_UNITCELL_PBC_ALL;
-            if (open_axes && !g_opt.force_brute && !prepare_open_boxes(e, *c.src, c.nb, c.pbc, num_atoms)) return false;
-            const std::vector<float>& gb = (open_axes && c.src->gboxes_ready) ? c.src->h_gboxes : c.src->h_boxes;
-            const float* d_gb = (open_axes && c.src->gboxes_ready) ? c.src->d_gboxes.p : c.src->d_boxes.p;
-            // density of the sparsest selection any pass of this group puts in the lanes (the denser of its two), against the first frame's
-            // cell
-            bool dense_lanes = !open_axes && !(g.passes.empty() && g.shell_props.empty());
-            if (dense_lanes) {
-                const float* q = gb.data();
-                const double vol = (double)q[0] * q[1] * q[2];
-                for (auto& ps : g.passes) {
-                    const size_t lanes = std::max(e->sels[ps.sel_a]->idx.size(), e->sels[ps.sel_b]->idx.size());
-                    dense_lanes = dense_lanes && vol > 0.0 && (double)lanes / vol >= 0.08;
-                }
-                for (int pi : g.shell_props) {      // by the parent lists: what the cell builds sort
-                    const PropState* p = e->props[pi].get();
-                    const size_t lanes = std::max(p->sel_a >= 0 ? e->sels[p->sel_a]->idx.size() : 0, p->sel_b >= 0 ? e->sels[p->sel_b]->idx.size() : 0);
-                    dense_lanes = dense_lanes && vol > 0.0 && (double)lanes / vol >= 0.08;
-                }
+            const float* d_gb = nullptr;
+            // the sparsest selection any pass of this group puts in the lanes (the denser of its two); shell properties by the parent
+            // lists: what the cell builds sort
+            size_t lanes = (g.passes.empty() && g.shell_props.empty()) ? 0 : SIZE_MAX;
+            for (auto& ps : g.passes) lanes = std::min(lanes, std::max(e->sels[ps.sel_a]->idx.size(), e->sels[ps.sel_b]->idx.size()));
+            for (int pi : g.shell_props) {
+                const PropState* p = e->props[pi].get();
+                lanes = std::min(lanes, std::max(p->sel_a >= 0 ? e->sels[p->sel_a]->idx.size() : 0, p->sel_b >= 0 ? e->sels[p->sel_b]->idx.size() : 0));
             }
             // (grid_r: the larger of the pair cutoff and the shell radii of the group's members - walk and pair kernel accept a wider edge)
-            if (e->spec.rdf_raw || !choose_grid(gb, c.pbc, c.nb, g.grid_r, &grid, dense_lanes)) {
+            const int have_grid = grid_for(lanes, g.grid_r, &grid, &d_gb);
+            if (have_grid < 0) return false;
+            if (e->spec.rdf_raw || !have_grid) {
                 // no grid for this batch (cutoff >= half the cell width, ...): all pairs, per property
                 for (int pi : g.props) {
                     PropState* p = e->props[pi].get();
@@ -682,18 +696,10 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 Selection* st = e->sels[p->sel_a].get();
                 Selection* sr = e->sels[p->sel_b].get();
                 vmd_grid_t grid;
-                const bool open_axes = (c.pbc & 8u) == 0 && (c.pbc & VMD_UNITCELL_PBC_ALL) != VMD_UNITCELL_PBC_ALL;
-                if (open_axes && !g_opt.force_brute && !prepare_open_boxes(e, *c.src, c.nb, c.pbc, num_atoms)) return false;
-                const std::vector<float>& gb = (open_axes && c.src->gboxes_ready) ? c.src->h_gboxes : c.src->h_boxes;
-                const float* d_gb = (open_axes && c.src->gboxes_ready) ? c.src->d_gboxes.p : c.src->d_boxes.p;
-                // the pencil split rule of the RDF groups, so that equal cutoffs over equal selections meet on equal grids
-                bool dense_lanes = !open_axes;
-                if (dense_lanes) {
-                    const float* q = gb.data();
-                    const double vol = (double)q[0] * q[1] * q[2];
-                    dense_lanes = vol > 0.0 && (double)std::max(st->idx.size(), sr->idx.size()) / vol >= 0.08;
-                }
-                if (choose_grid(gb, c.pbc, c.nb, d.rmax, &grid, dense_lanes)) {
+                const float* d_gb = nullptr;
+                const int have_grid = grid_for(std::max(st->idx.size(), sr->idx.size()), d.rmax, &grid, &d_gb);
+                if (have_grid < 0) return false;
+                if (have_grid) {
                     if (!build_selection(e, st, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
                     if (sr != st && !build_selection(e, sr, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
                     e->prof.begin("within_pencil", e->stream);
@@ -713,6 +719,71 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
             }
             HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.within_toff[wi], p->d_out.p, c.nb * sizeof(float),
                     hipMemcpyDeviceToHost, e->stream));
+        }
+        // ---- sdfs over a shell target.  First every shell's mask in atom order, then, behind the LAST cell build of the batch,
+        // alignment and masked scatter.  RULE for the mask: all pairs from the raw frame when R has fewer than shell_brute_below atoms (480:
+        // the walk and the build of R cost the same whatever |R| is, all pairs is linear in it, and DESIGN 1.8 measures where they cross) or
+        // when no grid exists for the shell radius; otherwise the walk over the cell-sorted copy of R on the grid a within count of the same
+        // radius and lists would get.  The scatter adds to the volume with atomics, so unlike a static sdf it has to be all or nothing: it
+        // sits here, where the overflow flag is final, and tests it like the commits below; a repeated batch runs launch_rdf again and its
+        // voxels are added exactly once.
+        for (auto& h : e->shells) h->abuilt = 0;
+        for (int pi : e->shell_sdf_props) {
+            PropState* p = e->props[pi].get();
+            Shell* h = e->shells[p->shell_of[1]].get();
+            if (h->abuilt || h->sel_t < 0) continue;
+            Selection* st = e->sels[h->sel_t].get();
+            Selection* sr = e->sels[h->sel_r].get();
+            const size_t stride = c.src->row_stride;
+            if (h->amask_stride != stride || c.nb * stride > h->amask.cap) {
+                if (!h->amask.ensure(c.nb * stride)) return false;
+                HIP_OK(hipMemsetAsync(h->amask.p, 0, h->amask.cap, e->stream));        // atoms outside T' read 0 for ever
+                h->amask_stride = stride;
+            }
+            if (!h->acount.ensure(c.nb)) return false;
+            vmd_grid_t grid;
+            const float* d_gb = nullptr;
+            const int below = g_opt.shell_brute_below.load();
+            const int have_grid = (int)sr->idx.size() < below ? 0 : grid_for(std::max(st->idx.size(), sr->idx.size()), h->rmax, &grid, &d_gb);
+            if (have_grid < 0) return false;
+            if (have_grid) {
+                if (!build_selection(e, sr, *c.src, d_gb, c.pbc, c.nb, grid)) return false;
+                e->prof.begin("shell_mask", e->stream);
+                KRN_OK(vmd_hip_within_atoms(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, d_gb, c.pbc, (int)c.nb, st->d_idx.p,
+                        (int)st->idx.size(), sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, grid, h->rmin, h->rmax,
+                        e->spec.within_closed ? 1 : 0, h->acount.p, h->amask.p, stride, e->d_overflow.p));
+                e->prof.end(e->stream);
+                h->abuilt = 1;
+            } else {
+                e->prof.begin("shell_mask_brute", e->stream);
+                KRN_OK(vmd_hip_within_brute_atoms(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                        (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), h->rmin, h->rmax,
+                        e->spec.within_closed ? 1 : 0, h->acount.p, h->amask.p, stride));
+                e->prof.end(e->stream);
+                h->abuilt = 2;
+            }
+        }
+        for (int pi : e->shell_sdf_props) {
+            PropState* p = e->props[pi].get();
+            const Property& d = p->prop;
+            Shell* h = e->shells[p->shell_of[1]].get();
+            if (h->sel_t < 0) continue;                   // T minus R is empty: no member in any frame, no voxel
+            if (!p->d_R32.ensure(c.nb * d.K * 9) || !p->d_c32.ensure(c.nb * d.K * 3) || !p->d_group.ensure(c.nb * 4)) return false;
+            e->prof.begin("sdf_align", e->stream);
+            if (p->have_tree && !p->d_tree_pos.ensure(c.nb * d.K * d.m * 3)) return false;
+            KRN_OK(vmd_hip_sdf_align(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                    (int)c.nb, p->d_structs.p, p->d_mass.p, (int)d.K, (int)d.m, p->d_ref_pose.p, p->d_R32.p, p->d_c32.p, nullptr,
+                    p->d_group.p, p->have_tree ? p->d_tree_order.p : nullptr, p->have_tree ? p->d_tree_parent.p : nullptr, p->have_tree
+                    ? p->d_tree_pos.p : nullptr));
+            e->prof.end(e->stream);
+            e->prof.begin("sdf_scatter", e->stream);
+            for (auto& su : c.subs) KRN_OK(vmd_hip_sdf_scatter_masked(e->stream, c.src->base + su.off * c.src->frame_stride,
+                    c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, p->d_structs.p, (int)d.K,
+                    (int)d.m, p->d_R32.p + su.off * d.K * 9, p->d_c32.p + su.off * d.K * 3, p->d_tgt.p, (p->have_owner
+                    && !e->spec.sdf_include_self) ? p->d_owner.p : nullptr, (int)d.b.size(), d.rmax, VMD_VOLUME_DIM, acc_of(p, su),
+                    p->d_group.p + 4 * su.off, p->tgt_first, p->tgt_stride, (p->unowned || e->spec.sdf_include_self) ? 1 : 0,
+                    h->amask.p + su.off * h->amask_stride, h->amask_stride, e->d_overflow.p));
+            e->prof.end(e->stream);
         }
         for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
         HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -893,7 +964,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 off += c.nb * p->dim1;
             }
         }
-        if ((!e->rdf_groups.empty() || !e->within_props.empty()) && !launch_rdf(c)) return false;
+        if ((!e->rdf_groups.empty() || !e->within_props.empty() || !e->shell_sdf_props.empty()) && !launch_rdf(c)) return false;
 
         for (auto& p : e->props) {
             const Property& d = p->prop;
@@ -901,6 +972,9 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
                 // SPEC S4 normalisation, fp64 on the host (needs only the box).  An rdf over shells needs the populations too: its weights
                 // are formed in complete_batch, when they have arrived
                 if (!d.is_shell_rdf()) rdf_weights(c, p.get());
+                p->dirty = p->dirty || !spec;
+            } else if (d.is_shell_sdf()) {
+                // sdf over a shell: aligned and scattered by launch_rdf above, behind the batch's cell builds
                 p->dirty = p->dirty || !spec;
             } else if (d.kind == PROP_SDF) {
                 if (!p->d_R32.ensure(c.nb * d.K * 9) || !p->d_c32.ensure(c.nb * d.K * 3) || !p->d_group.ensure(c.nb * 4)) return false;

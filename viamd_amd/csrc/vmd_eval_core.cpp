@@ -54,6 +54,29 @@ int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx) {
     return (int)e->sels.size() - 1;
 }
 
+// A shell argument (T, R, r_min, r_max) of an rdf or an sdf (1.8) as selections plus an interned Shell: its list T (T minus R
+// under D-WITHIN-SELF flipped, as build_within_plan) and R are selections like any other, and properties that name the same shell share
+// one object - its walk, its compaction, its mask.  -> the index in e->shells; *sel_t is T' (-1: nothing left, empty in every frame)
+static int intern_shell(vmd_script_eval_t* e, std::vector<int32_t> t, const Property::ShellArg& h, int* sel_t) {
+    if (e->spec.within_exclude_ref) {
+        std::vector<int32_t> ref = h.ref;
+        std::sort(ref.begin(), ref.end());
+        t.erase(std::remove_if(t.begin(), t.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), t.end());
+    }
+    const int st = t.empty() ? -1 : intern_selection(e, t);
+    const int sr = intern_selection(e, h.ref);
+    *sel_t = st;
+    for (size_t q = 0; q < e->shells.size(); ++q) {
+        const Shell& x = *e->shells[q];
+        if (x.sel_t == st && x.sel_r == sr && memcmp(&x.rmin, &h.rmin, sizeof(float)) == 0 && memcmp(&x.rmax, &h.rmax, sizeof(float)) == 0)
+            return (int)q;
+    }
+    auto x = std::make_unique<Shell>();
+    x->sel_t = st; x->sel_r = sr; x->rmin = h.rmin; x->rmax = h.rmax;
+    e->shells.push_back(std::move(x));
+    return (int)e->shells.size() - 1;
+}
+
 // Groups the RDF properties by range and decides, per group, between one pair pass per property and the class decomposition
 // (see PairPass).  Classes are used when every set is duplicate-free, there are at most 8 of them, and the pair work
 // (sum over passes of n_a * n_b, halved for same-set passes) drops by at least 10 %.
@@ -78,38 +101,29 @@ void build_rdf_plan(vmd_script_eval_t* e) {
     for (auto& p : e->props) {
         if (p->prop.kind != PROP_RDF) continue;
         if (p->prop.is_shell_rdf()) {
-            // a shell side: its list T (T minus R under D-WITHIN-SELF flipped, as build_within_plan) and R are selections like any other;
-            // the shell itself is interned, so that properties which use the same one share its walk and compaction
             for (int k = 0; k < 2; ++k) {
                 const Property::ShellArg& h = p->prop.shell[k];
-                std::vector<int32_t> t = k ? p->prop.b : p->prop.a;
-                if (h.on && e->spec.within_exclude_ref) {
-                    std::vector<int32_t> ref = h.ref;
-                    std::sort(ref.begin(), ref.end());
-                    t.erase(std::remove_if(t.begin(), t.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), t.end());
-                }
-                const int st = t.empty() ? -1 : intern_selection(e, t);
-                (k ? p->sel_b : p->sel_a) = st;
-                if (!h.on) continue;
-                const int sr = intern_selection(e, h.ref);
-                int found = -1;
-                for (size_t q = 0; q < e->shells.size() && found < 0; ++q) {
-                    const Shell& x = *e->shells[q];
-                    if (x.sel_t == st && x.sel_r == sr && memcmp(&x.rmin, &h.rmin, sizeof(float)) == 0 && memcmp(&x.rmax, &h.rmax, sizeof(float)) == 0)
-                        found = (int)q;
-                }
-                if (found < 0) {
-                    auto x = std::make_unique<Shell>();
-                    x->sel_t = st; x->sel_r = sr; x->rmin = h.rmin; x->rmax = h.rmax;
-                    e->shells.push_back(std::move(x));
-                    found = (int)e->shells.size() - 1;
-                }
-                p->shell_of[k] = found;
+                const std::vector<int32_t>& t = k ? p->prop.b : p->prop.a;
+                int& sel = k ? p->sel_b : p->sel_a;
+                if (!h.on) { sel = t.empty() ? -1 : intern_selection(e, t); continue; }
+                p->shell_of[k] = intern_shell(e, t, h, &sel);
+                e->shells[p->shell_of[k]]->rdf_use = true;
             }
             continue;
         }
         p->sel_a = intern_selection(e, p->prop.a);
         p->sel_b = p->same_set ? p->sel_a : intern_selection(e, p->prop.b);
+    }
+    // sdfs over a shell target: (T or T minus R, R, r_min, r_max) interned with the rdfs' shells - a shell an rdf and an sdf
+    // both name is one Shell, and R one selection whose cell-sorted copy every user on the same grid shares.  sel_b of the property is the
+    // shell's T'; the scatter itself keeps the property's own target list (owner, progression), the mask says who takes part
+    e->shell_sdf_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        if (!p->prop.is_shell_sdf()) continue;
+        p->shell_of[1] = intern_shell(e, p->prop.b, p->prop.shell[1], &p->sel_b);
+        e->shells[p->shell_of[1]]->sdf_use = true;
+        e->shell_sdf_props.push_back((int)i);
     }
     for (auto& g : e->rdf_groups) {
         auto direct = [&]() {
@@ -866,4 +880,68 @@ extern "C" bool vmd_eval_sdf_matrices(vmd_script_eval_t* eval, const char* name,
     if (K_out) *K_out = K;
     if (extent_out) *extent_out = p->prop.rmax;
     return true;
+}
+
+// The members of one shell at one frame, by atom.  One frame on demand, as vmd_eval_sdf_matrices: all pairs from the raw frame
+// with the bytes in atom order (for ONE frame the cell build a walk needs costs more than it saves), packed to bits on the host.  Nothing
+// the evaluation keeps is touched: the mask and count live in two buffers of the eval that only this call uses (kept between calls: a
+// host asks for every displayed frame, and giving device memory back may wait for the device).
+extern "C" size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name, int which, const vmd_system_t* sys, vmd_trajectory_i* traj,
+                                      uint32_t frame, uint64_t* words, size_t cap) {
+    const size_t failed = VMD_SHELL_MASK_FAILED;
+    if (!eval || !traj || !name) { vmd_fail("vmd_eval_shell_mask: NULL argument"); return failed; }
+    PropState* p = find_prop(eval, name);
+    if (!p) { vmd_fail("unknown property '%s'", name); return failed; }
+    if (which != 0 && which != 1) { vmd_fail("vmd_eval_shell_mask: which must be 0 (reference) or 1 (target)"); return failed; }
+    vmd_script_eval_t* e = eval;
+    // (properties, selections and shells are read in front of the mutex: build_rdf_plan / build_within_plan run once, when the eval is
+    // created, and nothing changes them afterwards - pool threads inside frame_range only read them too)
+    int sel_t = -1, sel_r = -1;
+    float rmin = 0.0f, rmax = 0.0f;
+    if (p->prop.is_within() && which == 1) {
+        sel_t = p->sel_a; sel_r = p->sel_b; rmin = p->prop.rmin; rmax = p->prop.rmax;
+    } else if ((p->prop.is_shell_rdf() || p->prop.is_shell_sdf()) && p->prop.shell[which].on) {
+        const Shell& h = *e->shells[p->shell_of[which]];
+        sel_t = h.sel_t; sel_r = h.sel_r; rmin = h.rmin; rmax = h.rmax;
+    } else {
+        vmd_fail("the %s side of '%s' is not a within() shell", which ? "target" : "reference", name);
+        return failed;
+    }
+    if (frame >= e->num_frames) { vmd_fail("vmd_eval_shell_mask: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
+    std::lock_guard<std::mutex> lock(eval->mtx);
+    if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
+    const size_t num_atoms = traj->num_atoms(traj->inst);
+    const size_t nwords = (num_atoms + 63) / 64;
+    if (cap < nwords || (!words && nwords)) { vmd_fail("vmd_eval_shell_mask: %zu words needed, room for %zu", nwords, words ? cap : (size_t)0); return failed; }
+    if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
+    std::fill(words, words + nwords, (uint64_t)0);
+    if (sel_t < 0) return 0;                   // T minus R is empty (spec_within_exclude_ref)
+    auto run = [&](size_t* members) -> bool {
+        vmd_device_view_t view;
+        memset(&view, 0, sizeof(view));
+        const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
+        BatchSrc src;
+        if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+        const Selection* st = e->sels[sel_t].get();
+        const Selection* sr = e->sels[sel_r].get();
+        const size_t stride = std::max(src.row_stride, num_atoms);
+        DevBuf<uint8_t>& d_mask = e->d_one_mask;
+        DevBuf<uint32_t>& d_count = e->d_one_count;
+        if (!d_mask.ensure(stride) || !d_count.ensure(1)) return false;
+        HIP_OK(hipMemsetAsync(d_mask.p, 0, stride, e->stream));
+        KRN_OK(vmd_hip_within_brute_atoms(e->stream, src.base, src.frame_stride, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]),
+                1, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), rmin, rmax, e->spec.within_closed ? 1 : 0, d_count.p,
+                d_mask.p, stride));
+        std::vector<uint8_t> bytes(num_atoms);
+        HIP_OK(hipMemcpyAsync(bytes.data(), d_mask.p, num_atoms, hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        // counted from the bytes, not taken from d_count: a list that names an atom twice marks it once, and the answer is in ATOMS
+        size_t set = 0;
+        for (size_t a = 0; a < num_atoms; ++a) if (bytes[a]) { words[a >> 6] |= (uint64_t)1 << (a & 63); set += 1; }
+        *members = set;
+        return true;
+    };
+    size_t members = 0;
+    if (!run(&members)) { std::fill(words, words + nwords, (uint64_t)0); return failed; }
+    return members;
 }

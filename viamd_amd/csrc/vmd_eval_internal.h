@@ -171,6 +171,9 @@ struct Options {
     std::atomic<int> cells_cap_sample{3};
     // ... and never below the selection's mean population per pencil x 1.15 (0: measured populations only)
     std::atomic<int> cells_cap_floor{1};
+    // an sdf over a shell: a reference list of fewer atoms than this gets its mask from all pairs even where a grid exists -
+    // the walk costs the same whatever |R| is, all pairs is linear in it, and the two cross here (0: the walk whenever a grid exists)
+    std::atomic<int> shell_brute_below{480};
 };
 
 extern Options g_opt;
@@ -380,6 +383,7 @@ struct Property {
     // rdf over within() shells: side 0 = a (reference), 1 = b (target); on: that argument is the shell (list, ref, rmin, rmax)
     struct ShellArg { bool on = false; std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; } shell[2];
     bool is_shell_rdf() const { return kind == PROP_RDF && (shell[0].on || shell[1].on); }
+    bool is_shell_sdf() const { return kind == PROP_SDF && shell[1].on; }     // sdf over a shell target: side 1 only
 };
 
 struct vmd_script_ir_t {
@@ -457,6 +461,13 @@ struct Shell {
     DevBuf<uint32_t> cell_start;            // the hit copy: [B][ncell + 1] ...
     DevBuf<float> sorted;                   // ... and [B][3][nsel_pad] (+ the parent's slack), zeroed when allocated
     int built = 0;                          // for the current batch: 0 no, 1 the hit copy on built_grid, 2 the list-order flags
+    // sdf over this shell: u8[B][amask_stride] by ATOM index (zeroed when allocated: only the atoms of sel_t are ever
+    // written), its populations, and whether it stands for the current batch (0 no, 1 from the walk, 2 from all pairs)
+    DevBuf<uint8_t> amask;
+    DevBuf<uint32_t> acount;
+    size_t amask_stride = 0;
+    int abuilt = 0;
+    bool rdf_use = false, sdf_use = false;  // who named it (build_rdf_plan): scratch is charged and populations are fetched by use
     vmd_grid_t built_grid;
 };
 
@@ -716,7 +727,10 @@ struct vmd_script_eval_t {
     hipStream_t pair_stream = nullptr;       // every other block of a batch of frame blocks runs its pair kernel here
     hipEvent_t pair_fork = nullptr, pair_join = nullptr;
     std::vector<RdfGroup> rdf_groups;
-    std::vector<std::unique_ptr<Shell>> shells;         // within() shells that rdf arguments use
+    std::vector<std::unique_ptr<Shell>> shells;         // within() shells that rdf and sdf (1.8) arguments use
+    std::vector<int> shell_sdf_props;                   // indices into props of the sdfs over a shell: masked scatter in launch_rdf
+    DevBuf<uint8_t> d_one_mask;                         // vmd_eval_shell_mask: one frame's mask by atom and its population, kept between calls
+    DevBuf<uint32_t> d_one_count;
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;

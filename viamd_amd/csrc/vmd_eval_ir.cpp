@@ -23,7 +23,10 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
             // the parent sizes (a bound that needs no frame) plus one neighbour query per shell, |T| + |R|
             for (int k = 0; k < 2; ++k) if (p.shell[k].on) w += (uint64_t)(k ? p.b : p.a).size() + (uint64_t)p.shell[k].ref.size();
         }
-        else if (p.kind == PROP_SDF) w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
+        else if (p.kind == PROP_SDF) {
+            w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
+            if (p.shell[1].on) w += (uint64_t)p.b.size() + (uint64_t)p.shell[1].ref.size();     // the parent list plus the shell's query
+        }
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
         else if (p.is_within()) w += (uint64_t)p.a.size() + (uint64_t)p.b.size();        // |T| + |R|: a neighbour query, not all pairs
@@ -271,6 +274,31 @@ extern "C" bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, cons
     return true;
 }
 
+// `name = sdf(structures, T and within(a:b, R), cutoff);`: vmd_ir_add_sdf with the target a shell, validated like
+// vmd_ir_add_within_count
+extern "C" bool vmd_ir_add_sdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
+                                     const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float cutoff) {
+    if (!target_shell) return vmd_ir_add_sdf(ir, name, structures, K, m, target, ntarget, cutoff);
+    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget,
+            "sdf target set")) return false;
+    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
+    const vmd_shell_t* h = target_shell;
+    if (!idx_ok(h->ref, h->nref, "within reference set")) return false;
+    if (ntarget > 0x7fffffff || h->nref > 0x7fffffff) return vmd_fail("within set too large");
+    if (!std::isfinite(h->rmin) || !std::isfinite(h->rmax) || !(h->rmin >= 0.0f) || !(h->rmax > h->rmin))
+        return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
+    Property p;
+    p.name = name; p.kind = PROP_SDF; p.flags = VMD_PROPERTY_FLAG_VOLUME;
+    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
+    p.K = K; p.m = m; p.rmax = cutoff;
+    p.shell[1].on = true;
+    p.shell[1].ref.assign(h->ref, h->ref + h->nref);
+    p.shell[1].rmin = h->rmin; p.shell[1].rmax = h->rmax;
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
 // `name = count(T and within(rmin:rmax, R));`: one temporal property, one value per frame; validated like ir_add_geometry
 extern "C" bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
                                         const int32_t* ref, size_t nref, float rmin, float rmax) {
@@ -340,7 +368,7 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
         h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
         if (p.is_shape()) h = fnv1a(h, &p.shape_comp, sizeof(int));     // shape_weights only, as above
-        for (int k = 0; k < 2; ++k) {                                   // rdf over shells only, as above
+        for (int k = 0; k < 2; ++k) {                                   // rdf / sdf over shells only, as above
             if (!p.shell[k].on) continue;
             const int32_t side = 0x5348454c + k;                        // "SHEL": which side carries the shell
             h = fnv1a(h, &side, sizeof(side));

@@ -1987,12 +1987,14 @@ struct vmd_within_brute_params_t {
     vmd_within_test_t w;
     unsigned* count;
     unsigned char* flags;       // FLAGS instantiation: u8[B][ntgt], 1 = the list entry is in the shell
+    size_t flag_stride;         // ATOMS instantiation: flags is u8[B][flag_stride] indexed by ATOM, flags[b][tgt[t]]
 };
 
 // all pairs from the raw frame (any cell, any cutoff): one lane per target atom, the reference set staged through LDS in tiles of 256, a
 // lane stops testing at its first hit.  One integer atomic per wave.  The device-side definition the cell walk below is tested against.
 // FLAGS: also one byte per list entry, in list order - the mask vmd_hip_rdf_brute_masked takes.
-template <bool FLAGS>
+// ATOMS (with FLAGS): the byte goes to the atom's place instead, the mask vmd_hip_sdf_scatter_masked takes where no grid exists.
+template <bool FLAGS, bool ATOMS = false>
 __global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t p) {
     __shared__ float s_r[3][256];
     const int b = blockIdx.y;
@@ -2021,7 +2023,8 @@ __global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t 
             for (int jj = 0; jj < nj && !hit; ++jj)
                 hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
     }
-    if (FLAGS) { if (valid) p.flags[(size_t)b * p.ntgt + t] = hit ? 1 : 0; }
+    if (FLAGS && ATOMS) { if (valid) p.flags[(size_t)b * p.flag_stride + (size_t)(p.tgt ? p.tgt[t] : t)] = hit ? 1 : 0; }
+    else if (FLAGS) { if (valid) p.flags[(size_t)b * p.ntgt + t] = hit ? 1 : 0; }
     const unsigned long long m = __ballot(hit ? 1 : 0);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
 }
@@ -2117,6 +2120,91 @@ __global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t
     }
     if (FLAGS) { if (lane == 0) p.pen_hits[(size_t)b * (ny * nz + 1) + pen] = total; }
     if (lane == 0 && total) atomicAdd(&p.count[b], total);
+}
+
+// ------------------------------------------------------------------------------------------------ K8: a shell's mask in atom order
+
+struct vmd_within_atoms_params_t {
+    vmd_cells_params_t c;       // T as a cell build would read it: raw frame, the GRID's boxes, pbc, index list, grid (pat.m = 0; no outputs)
+    const float* sref; const uint32_t* cs_ref; int nref_pad;
+    vmd_within_test_t w; float rpad; int ry, rz;
+    unsigned char* mask; size_t mask_stride;     // u8[B][mask_stride], indexed by ATOM: mask[b][T[t]] = hit
+    unsigned* count; const uint32_t* skip;
+};
+
+// The walk of k_within_pencil with T NOT sorted: one lane per list entry t, in list order.  The lane wraps its atom and derives its cell with
+// vmd_cell_of - the function every cell build bins with, on the same fp32 values - so an atom on a cell boundary stands in the pencil a build
+// would have put it in and sees the neighbour pencils k_within_pencil would have walked for it; pencils, images, split-pencil windows,
+// triclinic offsets, open axes and the pair arithmetic are that kernel's, statement for statement (kept as a copy: the instantiations of
+// k_within_pencil keep the code the compiler gave them).  Only R is cell-sorted, so nothing needs a rank: the answer goes to mask[b][atom].
+// Lanes of a wave are spatially unrelated: every lane walks its own windows and the loads do not coalesce; with a small R under a large T
+// nearly every lane finds its windows empty and leaves after the cell_start reads.
+__global__ __launch_bounds__(256) void k_within_atoms(vmd_within_atoms_params_t p) {
+    if (p.skip && *p.skip) return;       // the cell build of R (or another one of this batch) overflowed a bucket: the host repeats the batch
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int nxf = p.c.grid.nxf, ny = p.c.grid.ny, nz = p.c.grid.nz;
+    const bool tri = (p.c.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.c.pbc & 7u) != 7u;
+    const float* q = p.c.boxes + (size_t)VMD_BOX_STRIDE * b;
+    const float Lx = q[0], Ly = q[1], Lz = q[2];
+    const float inv_cx = (float)nxf * q[3];
+    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
+    const bool open_x = open && !(p.c.pbc & 1u), open_y = open && !(p.c.pbc & 2u), open_z = open && !(p.c.pbc & 4u);
+    const float orgx = open_x ? q[6] : 0.0f;
+    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
+    const uint32_t* csr = p.cs_ref + (size_t)b * (p.c.grid.ncell + 1);
+    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
+    const float* ry_ = rx + p.nref_pad;
+    const float* rz_ = ry_ + p.nref_pad;
+    bool hit = false;
+    if (t < p.c.nsel) {
+        float xi, yi, zi;
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)nxf);
+        const int pz = pen / ny, py = pen - pz * ny;
+        for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
+            int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
+            if (open_z && (qz < 0 || qz >= nz)) continue;
+            if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
+            for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
+                int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+                if (open_y && (qy < 0 || qy >= ny)) continue;
+                if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
+                const int qp = qz * ny + qy;
+                float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
+                if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
+                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
+                    const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                    const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                    if (rr <= 0.0f) continue;
+                    rpad = sqrtf(rr) * 1.0001f;
+                }
+                if (tri) {
+                    const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
+                    const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
+                    offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                    offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+                }
+                for (int kx = -1; kx <= 1 && !hit; ++kx) {
+                    if (open_x && kx != 0) continue;
+                    float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
+                    if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
+                    const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
+                    const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
+                    if (hi < 0.0f || lo >= Lx) continue;
+                    const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
+                    const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
+                    const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
+                    for (unsigned j = ja; j < jb && !hit; ++j) {
+                        const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
+                        hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
+                    }
+                }
+            }
+        }
+        p.mask[(size_t)b * p.mask_stride + (size_t)vmd_sel_atom(p.c, t)] = hit ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(hit ? 1 : 0);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
 }
 
 // ------------------------------------------------------------------------------------------------ K7: shells as selections
@@ -2478,8 +2566,16 @@ __device__ __forceinline__ bool vmd_sdf_near(const vmd_scatter_params_t& p, cons
 // instead of two (the kernel is bound by the latency of its loads under load: a wave used to live ~12 us).
 // ILP atoms per thread: all their gathers are in flight at once.
 #define VMD_SDF_CAP 512      // survivors of the group test a block holds in LDS at a time (~1 % of its atoms pass; more take another round)
-template <int ILP, bool ARITH>
-__global__ __launch_bounds__(256) void k_sdf_scatter(vmd_scatter_params_t p) {
+// MASKED: the target is a within() shell.  mask is u8[B][mask_stride] indexed by ATOM (k_within_atoms, or k_within_brute<true, true>);
+// a target whose byte of frame b is 0 drops out where the group pre-filter drops atoms - everything behind that (D-SDF-EXCL by atom identity,
+// the S5 arithmetic, the u64 voxel atomics) is the static path.  The mask hangs on a cell build, so this instantiation alone tests the batch's
+// overflow flag, all or nothing: the host launches it where the flag is final and repeats the batch otherwise.
+struct vmd_scatter_masked_params_t : vmd_scatter_params_t { const unsigned char* mask; size_t mask_stride; const uint32_t* skip; };
+template <bool MASKED> struct vmd_scatter_arg { typedef vmd_scatter_params_t type; };
+template <> struct vmd_scatter_arg<true> { typedef vmd_scatter_masked_params_t type; };
+template <int ILP, bool ARITH, bool MASKED = false>
+__global__ __launch_bounds__(256) void k_sdf_scatter(typename vmd_scatter_arg<MASKED>::type p) {
+    if constexpr (MASKED) { if (p.skip && *p.skip) return; }
     __shared__ float s_x[VMD_SDF_CAP], s_y[VMD_SDF_CAP], s_z[VMD_SDF_CAP];
     __shared__ int s_own[VMD_SDF_CAP], s_idx[VMD_SDF_CAP];
     __shared__ unsigned s_n;
@@ -2510,6 +2606,11 @@ __global__ __launch_bounds__(256) void k_sdf_scatter(vmd_scatter_params_t p) {
         }
     }
     unsigned pending = 0u;
+    if constexpr (MASKED) {
+        const unsigned char* mk = p.mask + (size_t)b * p.mask_stride;
+#pragma unroll
+        for (int u = 0; u < ILP; ++u) if (idx[u] >= 0 && mk[idx[u]] == 0) idx[u] = -1;
+    }
 #pragma unroll
     for (int u = 0; u < ILP; ++u) if (idx[u] >= 0 && vmd_sdf_near(p, bx, b, x[u], y[u], z[u])) pending |= 1u << u;
     for (;;) {
@@ -3759,7 +3860,7 @@ extern "C" int vmd_hip_rdf_brute_masked(void* stream, const float* xyz, size_t f
 static int vmd_within_brute_launch(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                     const float* boxes, uint32_t pbc_flags, int B,
                                     const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
-                                    float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* flags_out) {
+                                    float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* flags_out, size_t atom_stride = 0) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     if (B > 65535 || !count_out) return (int)hipErrorInvalidValue;
@@ -3767,8 +3868,9 @@ static int vmd_within_brute_launch(void* stream, const float* xyz, size_t frame_
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
     if (ntgt <= 0 || nref <= 0) return 0;
     vmd_within_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref,
-                                vmd_make_within_test(rmin, rmax, closed), count_out, flags_out};
-    if (flags_out) hipLaunchKernelGGL(k_within_brute<true>, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+                                vmd_make_within_test(rmin, rmax, closed), count_out, flags_out, atom_stride};
+    if (flags_out && atom_stride) hipLaunchKernelGGL((k_within_brute<true, true>), dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+    else if (flags_out) hipLaunchKernelGGL(k_within_brute<true>, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_within_brute<false>, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
@@ -3789,6 +3891,41 @@ extern "C" int vmd_hip_within_brute_flags(void* stream, const float* xyz, size_t
     if (!flags_out) return (int)hipErrorInvalidValue;
     return vmd_within_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref, rmin, rmax, closed,
                                    count_out, flags_out);
+}
+
+extern "C" int vmd_hip_within_brute_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                          const float* boxes, uint32_t pbc_flags, int B,
+                                          const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                                          float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* mask_out, size_t mask_stride) {
+    if (!mask_out || !mask_stride) return (int)hipErrorInvalidValue;
+    return vmd_within_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref, rmin, rmax, closed,
+                                   count_out, mask_out, mask_stride);
+}
+
+extern "C" int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                    const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
+                                    const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad, vmd_grid_t grid,
+                                    float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* mask_out, size_t mask_stride,
+                                    const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !count_out || !mask_out || !mask_stride || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 ||
+        grid.ncell != grid.nxf * grid.ny * grid.nz) return (int)hipErrorInvalidValue;
+    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    if (ntgt <= 0) return 0;
+    if (nref <= 0 || !sorted_ref || !cell_start_ref) return (int)hipErrorInvalidValue;
+    vmd_within_atoms_params_t p{};
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
+    p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
+    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
+    p.w = vmd_make_within_test(rmin, rmax, closed);
+    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_within_pencil
+    p.ry = g_pen_ry; p.rz = g_pen_rz;
+    p.mask = mask_out; p.mask_stride = mask_stride; p.count = count_out; p.skip = skip_flag;
+    hipLaunchKernelGGL(k_within_atoms, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
 }
 
 static int vmd_within_pencil_launch(void* stream, const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad,
@@ -3964,6 +4101,39 @@ extern "C" int vmd_hip_sdf_scatter(void* stream, const float* xyz, size_t frame_
         const dim3 g((ntgt + 256 * 4 - 1) / (256 * 4), B);
         if (arith) hipLaunchKernelGGL((k_sdf_scatter<4, true>), g, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((k_sdf_scatter<4, false>), g, dim3(256), 0, s, p);
+    }
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// the masked scatter of a shell target: always k_sdf_scatter<ILP, ARITH, true> - the _wave, _stream, _rows and _dense variants have
+// no masked form and are never chosen for a shell, whatever their switches say
+extern "C" int vmd_hip_sdf_scatter_masked(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                          const float* boxes, uint32_t pbc_flags, int B,
+                                          const int32_t* structs, int K, int m, const float* R32, const float* c32,
+                                          const int32_t* tgt, const int8_t* owner, int ntgt, float extent, int dim, uint64_t* volume,
+                                          const float* group, int tgt_first, int tgt_stride, int unowned,
+                                          const uint8_t* mask, size_t mask_stride, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0 || K <= 0 || ntgt <= 0) return 0;
+    if (B > 65535 || !mask || !mask_stride) return (int)hipErrorInvalidValue;
+    vmd_scatter_masked_params_t p;
+    (vmd_scatter_params_t&)p = vmd_scatter_params_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt,
+                                                    extent, dim, (unsigned long long*)volume, group, tgt_first, tgt_stride, unowned, g_sdf_nt};
+    p.mask = mask; p.mask_stride = mask_stride; p.skip = skip_flag;
+    const bool arith = tgt_stride > 0;
+    if (g_sdf_ilp == 16) {
+        const dim3 g((ntgt + 256 * 16 - 1) / (256 * 16), B);
+        if (arith) hipLaunchKernelGGL((k_sdf_scatter<16, true, true>), g, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_sdf_scatter<16, false, true>), g, dim3(256), 0, s, p);
+    } else if (g_sdf_ilp == 8) {
+        const dim3 g((ntgt + 256 * 8 - 1) / (256 * 8), B);
+        if (arith) hipLaunchKernelGGL((k_sdf_scatter<8, true, true>), g, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_sdf_scatter<8, false, true>), g, dim3(256), 0, s, p);
+    } else {
+        const dim3 g((ntgt + 256 * 4 - 1) / (256 * 4), B);
+        if (arith) hipLaunchKernelGGL((k_sdf_scatter<4, true, true>), g, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_sdf_scatter<4, false, true>), g, dim3(256), 0, s, p);
     }
     VMD_LAUNCH_CHECK();
     return 0;

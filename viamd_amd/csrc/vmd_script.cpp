@@ -338,8 +338,8 @@ struct Report {
 // skipped one is skipped with it ("unknown identifier").
 // features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
 // `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)`, VMD_SCRIPT_FEATURE_WITHIN
-// `name = count(sel and within(r, sel))`, VMD_SCRIPT_FEATURE_SHELL_RDF the same AND as an argument of rdf() (opt-in; 0 = the subset above,
-// byte for byte)
+// `name = count(sel and within(r, sel))`, VMD_SCRIPT_FEATURE_SHELL_RDF the same AND as an argument of rdf(), VMD_SCRIPT_FEATURE_SHELL_SDF as the
+// target argument of sdf() (opt-in; 0 = the subset above, byte for byte)
 void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
@@ -456,55 +456,56 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                 const std::string v = k.text;
                 ++p.i;
                 p.take("(");
-                if (v == "rdf" && (features & VMD_SCRIPT_FEATURE_SHELL_RDF)) {
-                    // either selection argument may be `<factor> and ... and within(<r> | <a>:<b>, <static selection>)` - the rules of
-                    // the count form below: exactly one within() per argument, at the top level of the AND, its argument static
-                    struct DynArg { std::vector<int32_t> list, ref; bool shell = false; double rmin = 0.0, rmax = 0.0; };
-                    auto dyn_arg = [&]() -> DynArg {
-                        DynArg out;
-                        const size_t start = p.i;
-                        size_t n_within = 0, n_top = 0;
-                        bool top_or = false;
-                        int depth = 0;
-                        for (size_t q = start; q < toks.size(); ++q) {      // up to the ',' that ends the argument
-                            const Token& tk = toks[q];
-                            if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
-                            if (tk.kind == T_OP && tk.text == "(") depth += 1;
-                            if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
-                            if (tk.kind == T_ID && tk.text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(") {
-                                n_within += 1;
-                                if (depth == 0 && (q == start || (toks[q - 1].kind == T_ID && toks[q - 1].text == "and"))) n_top += 1;
-                            }
-                            if (tk.kind == T_ID && tk.text == "or" && depth == 0) top_or = true;
+                // a selection argument of rdf() (either one) or sdf() (the target) may be
+                // `<factor> and ... and within(<r> | <a>:<b>, <static selection>)` - the rules of the count form below: exactly one within() per
+                // argument, at the top level of the AND, its argument static
+                struct DynArg { std::vector<int32_t> list, ref; bool shell = false; double rmin = 0.0, rmax = 0.0; };
+                auto dyn_arg = [&](const char* fn) -> DynArg {
+                    DynArg out;
+                    const size_t start = p.i;
+                    size_t n_within = 0, n_top = 0;
+                    bool top_or = false;
+                    int depth = 0;
+                    for (size_t q = start; q < toks.size(); ++q) {      // up to the ',' that ends the argument
+                        const Token& tk = toks[q];
+                        if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
+                        if (tk.kind == T_OP && tk.text == "(") depth += 1;
+                        if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
+                        if (tk.kind == T_ID && tk.text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(") {
+                            n_within += 1;
+                            if (depth == 0 && (q == start || (toks[q - 1].kind == T_ID && toks[q - 1].text == "and"))) n_top += 1;
                         }
-                        if (n_within == 0) { out.list = p.sel_or().indices(); return out; }
-                        if (n_within > 1) fail("%s: an rdf argument takes exactly one within() factor, found %zu", name.c_str(), n_within);
-                        if (n_top != 1 || top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", name.c_str());
-                        std::vector<uint8_t> tmask(topo.n, 1);
-                        out.shell = true;
-                        do {
-                            if (p.peek().kind == T_ID && p.peek().text == "within") {
-                                ++p.i;
-                                p.take("(");
-                                out.rmax = p.number();
-                                if (p.accept(":")) {
-                                    out.rmin = out.rmax; out.rmax = p.number();
-                                    if (!(out.rmin < out.rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
-                                } else if (!(out.rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
-                                p.take(",");
-                                out.ref = p.sel_or().indices();
-                                p.take(")");
-                                if (out.ref.empty()) fail("%s: empty selection", name.c_str());
-                            } else {
-                                const Sel f = p.sel_not();
-                                for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a];
-                            }
-                        } while (p.accept("and"));
-                        for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
-                        return out;
-                    };
-                    const DynArg A = dyn_arg(); p.take(",");
-                    const DynArg B = dyn_arg(); p.take(",");
+                        if (tk.kind == T_ID && tk.text == "or" && depth == 0) top_or = true;
+                    }
+                    if (n_within == 0) { out.list = p.sel_or().indices(); return out; }
+                    if (n_within > 1) fail("%s: an %s argument takes exactly one within() factor, found %zu", name.c_str(), fn, n_within);
+                    if (n_top != 1 || top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", name.c_str());
+                    std::vector<uint8_t> tmask(topo.n, 1);
+                    out.shell = true;
+                    do {
+                        if (p.peek().kind == T_ID && p.peek().text == "within") {
+                            ++p.i;
+                            p.take("(");
+                            out.rmax = p.number();
+                            if (p.accept(":")) {
+                                out.rmin = out.rmax; out.rmax = p.number();
+                                if (!(out.rmin < out.rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
+                            } else if (!(out.rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
+                            p.take(",");
+                            out.ref = p.sel_or().indices();
+                            p.take(")");
+                            if (out.ref.empty()) fail("%s: empty selection", name.c_str());
+                        } else {
+                            const Sel f = p.sel_not();
+                            for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a];
+                        }
+                    } while (p.accept("and"));
+                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
+                    return out;
+                };
+                if (v == "rdf" && (features & VMD_SCRIPT_FEATURE_SHELL_RDF)) {
+                    const DynArg A = dyn_arg("rdf"); p.take(",");
+                    const DynArg B = dyn_arg("rdf"); p.take(",");
                     double rmin = 0.0, rmax;
                     if (p.accept("{")) { rmin = p.number(); p.take(","); rmax = p.number(); p.take("}"); }
                     else {
@@ -533,8 +534,22 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                     if (a.empty() || b.empty()) fail("%s: empty selection", name.c_str());
                     commit = [=]() { if (!vmd_ir_add_rdf(ir, name.c_str(), a.data(), a.size(), b.data(), b.size(), (float)rmin, (float)rmax)) throw ScriptError(vmd_last_error()); };
                 } else if (v == "sdf") {
+                    const bool shells = (features & VMD_SCRIPT_FEATURE_SHELL_SDF) != 0;
+                    if (shells) {       // the structures stay static - the alignment needs fixed atoms
+                        int depth = 0;
+                        for (size_t q = p.i; q < toks.size(); ++q) {
+                            const Token& tk = toks[q];
+                            if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
+                            if (tk.kind == T_OP && tk.text == "(") depth += 1;
+                            if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
+                            if (tk.kind == T_ID && tk.text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(")
+                                fail("%s: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)", name.c_str());
+                        }
+                    }
                     const Sel ref = p.sel_or(); p.take(",");
-                    const Sel tgt = p.sel_or(); p.take(",");
+                    DynArg T;
+                    if (shells) T = dyn_arg("sdf"); else T.list = p.sel_or().indices();
+                    p.take(",");
                     const double cutoff = p.number();
                     p.take(")");
                     std::vector<std::vector<int32_t>> structs = ref.has_structs ? ref.structs : std::vector<std::vector<int32_t>>{ref.indices()};
@@ -545,9 +560,13 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                         if (st.size() != m || m == 0) fail("%s: sdf reference structures must be non-empty and of equal size", name.c_str());
                         flat.insert(flat.end(), st.begin(), st.end());
                     }
-                    const auto tg = tgt.indices();
                     const size_t K = structs.size();
-                    commit = [=]() { if (!vmd_ir_add_sdf(ir, name.c_str(), flat.data(), K, m, tg.data(), tg.size(), (float)cutoff)) throw ScriptError(vmd_last_error()); };
+                    if (T.shell && T.list.empty()) fail("%s: empty selection", name.c_str());
+                    commit = [=]() {
+                        const vmd_shell_t sh{T.ref.data(), T.ref.size(), (float)T.rmin, (float)T.rmax};
+                        if (!vmd_ir_add_sdf_shell(ir, name.c_str(), flat.data(), K, m, T.list.data(), T.list.size(), T.shell ? &sh : nullptr, (float)cutoff))
+                            throw ScriptError(vmd_last_error());
+                    };
                 } else if (v == "count") {
                     // `name = count(<factor> and <factor> ...);`: exactly one factor is within(<r> | <a>:<b>, <static selection>),
                     // the others are static selections whose AND is the target set (all atoms when there is none)

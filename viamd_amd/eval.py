@@ -110,6 +110,22 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_sdf(self.h, name.encode(), s.ctypes.data_as(L.c_int32_p), s.shape[0], s.shape[1],
                                             tp, t.size, float(cutoff)))
 
+    def add_sdf_shell(self, name, structures, target, cutoff, target_shell=None):
+        """`name = sdf(structures, target and within(a:b, R), cutoff)`: the target may be a shell, given as (R, r_min, r_max) -
+        per frame, only the atoms of `target` with some atom of R at r_min <= d < r_max are scattered.  None: add_sdf."""
+        import ctypes as C
+        s = np.ascontiguousarray(structures, dtype=np.int32)
+        if s.ndim != 2:
+            raise ValueError("structures must be a [K, m] index array")
+        t, tp = _idx(target)
+        ptr = None
+        if target_shell is not None:
+            x, xp = _idx(target_shell[0])
+            c = L.ShellC(xp, x.size, float(target_shell[1]), float(target_shell[2]))
+            ptr = C.byref(c)
+        self._check(self.lib.vmd_ir_add_sdf_shell(self.h, name.encode(), s.ctypes.data_as(L.c_int32_p), s.shape[0], s.shape[1],
+                                                  tp, t.size, ptr, float(cutoff)))
+
     def add_distance(self, name, a, b, kind=L.DIST_COM):
         """`name = distance|distance_min|distance_max|distance_pair(a, b)` (src/main.cpp:2817-2858)."""
         a_, ap = _idx(a)
@@ -492,6 +508,21 @@ def _sdf_payload(self, name, sys, traj, frame):
     return mats, structures, float(pl.extent)
 
 
+def _shell_mask(self, name, sys, traj, frame, which=1):
+    """the members of a within() shell at one frame (vmd_eval_shell_mask) as bool [num_atoms]; `name` a count(... within ...)
+    property, an rdf over shells or an sdf over a shell; which: 0 = the reference argument, 1 = the target argument"""
+    n = int(traj.num_atoms())
+    words = np.zeros((n + 63) // 64, np.uint64)
+    sysp = C.byref(sys.c) if sys is not None else None
+    got = self.lib.vmd_eval_shell_mask(self.h, name.encode(), int(which), sysp, traj.interface(), int(frame),
+                                       words.ctypes.data_as(C.POINTER(C.c_uint64)), words.size)
+    if got == L.SHELL_MASK_FAILED:
+        raise VmdError(self.lib.last_error())
+    mask = np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+    assert int(mask.sum()) == got
+    return mask
+
+
 def _export_cube(self, path, name, sys, traj, frame=0, atomic_numbers=None):
     """export_cube (src/main.cpp:5718-5830) in C++ behind the ABI: the volume + the atoms of reference structure 0."""
     an = None if atomic_numbers is None else np.ascontiguousarray(atomic_numbers, np.uint8)
@@ -511,6 +542,7 @@ def _export_table(self, path, name, fmt="xvg", frame_times=None, num_bins=0, tim
 
 
 ScriptEval.sdf_payload = _sdf_payload
+ScriptEval.shell_mask = _shell_mask
 ScriptEval.export_cube = _export_cube
 ScriptEval.export_table = _export_table
 

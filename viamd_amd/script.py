@@ -270,9 +270,11 @@ FEATURE_SHAPE = 2                               # VMD_SCRIPT_FEATURE_SHAPE
 FEATURE_RMSD = 4                                # VMD_SCRIPT_FEATURE_RMSD
 FEATURE_WITHIN = 8                              # VMD_SCRIPT_FEATURE_WITHIN
 FEATURE_SHELL_RDF = 16                          # VMD_SCRIPT_FEATURE_SHELL_RDF
+FEATURE_SHELL_SDF = 32                          # VMD_SCRIPT_FEATURE_SHELL_SDF
 
 
-def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False):
+def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
+                   shell_sdf=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -295,7 +297,10 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
 
     shell_rdf=True (VMD_SCRIPT_FEATURE_SHELL_RDF, opt-in): either selection argument of rdf() may be such an AND (DESIGN 1.7);
     info[name] = dict(kind="rdf", ref=idx, target=idx, rmin=, rmax=, ref_shell=, target_shell=), a shell being None (that side is its
-    static list) or dict(ref=idx, rmin=, rmax=)."""
+    static list) or dict(ref=idx, rmin=, rmax=).
+
+    shell_sdf=True (VMD_SCRIPT_FEATURE_SHELL_SDF, opt-in): the target argument of sdf() may be such an AND; within() in the
+    structures argument is refused; info[name] = dict(kind="sdf", structures=, target=idx, cutoff=, target_shell=) with the shell as above."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -339,7 +344,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("=")
                 if shape and p.peek() == ("id", "shape_weights"):
                     raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf)
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf, shell_sdf)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -534,8 +539,9 @@ def _count_statement(p, name, topo, env, ir, info):
     return commit
 
 
-def _dyn_arg(p, name, topo):
-    """one selection argument of rdf() under shell_rdf=True (the twin of dyn_arg in vmd_script.cpp) -> (index list, shell or None)"""
+def _dyn_arg(p, name, topo, fn="rdf"):
+    """one selection argument of rdf() under shell_rdf=True / the target of sdf() under shell_sdf=True (the twin of dyn_arg in
+    vmd_script.cpp) -> (index list, shell or None)"""
     start = p.i
     n_within = n_top = depth = 0
     top_or = False
@@ -558,7 +564,7 @@ def _dyn_arg(p, name, topo):
     if n_within == 0:
         return p.sel_or().indices(), None
     if n_within > 1:
-        raise ScriptError(f"{name}: an rdf argument takes exactly one within() factor, found {n_within}")
+        raise ScriptError(f"{name}: an {fn} argument takes exactly one within() factor, found {n_within}")
     if n_top != 1 or top_or:
         raise ScriptError(f"{name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
     tmask = np.ones(topo.num_atoms, bool)
@@ -586,7 +592,7 @@ def _dyn_arg(p, name, topo):
     return np.nonzero(tmask)[0].astype(np.int32), dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
 
 
-def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False):
+def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False, shell_sdf=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
@@ -638,6 +644,40 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
         def commit():
             ir.add_rdf(name, a, b, (rmin, rmax))
             info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax)
+        return commit, True
+    if v == "sdf" and shell_sdf:
+        depth = 0
+        for q in range(p.i, len(p.t)):          # the structures stay static - the alignment needs fixed atoms
+            k_, v_ = p.t[q]
+            if k_ == "op" and v_ in (",", ";") and depth == 0:
+                break
+            if k_ == "op" and v_ == "(":
+                depth += 1
+            if k_ == "op" and v_ == ")":
+                if depth == 0:
+                    break
+                depth -= 1
+            if (k_, v_) == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "("):
+                raise ScriptError(f"{name}: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)")
+        ref = p.sel_or(); p.take(",")
+        tg, sh = _dyn_arg(p, name, topo, "sdf"); p.take(",")
+        cutoff = p.number()
+        p.take(")")
+        structs = ref.structures if ref.structures is not None else [ref.indices()]
+        sizes = {len(s) for s in structs}
+        if len(sizes) != 1 or 0 in sizes:
+            raise ScriptError(f"{name}: sdf reference structures must be non-empty and of equal size, got sizes {sorted(sizes)}")
+        st = np.stack([np.asarray(s, np.int32) for s in structs])
+        if sh is not None and tg.size == 0:
+            raise ScriptError(f"{name}: empty selection")
+
+        def commit():
+            if sh is None:
+                ir.add_sdf(name, st, tg, cutoff)
+                info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff)
+                return
+            ir.add_sdf_shell(name, st, tg, cutoff, target_shell=(sh["ref"], sh["rmin"], sh["rmax"]))
+            info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff, target_shell=sh)
         return commit, True
     if v == "sdf":
         ref = p.sel_or(); p.take(",")
@@ -716,16 +756,17 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
     return commit, True
 
 
-def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False):
+def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
+                          shell_sdf=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
     VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD; within=True: with
-    VMD_SCRIPT_FEATURE_WITHIN; shell_rdf=True: with VMD_SCRIPT_FEATURE_SHELL_RDF."""
+    VMD_SCRIPT_FEATURE_WITHIN; shell_rdf=True: with VMD_SCRIPT_FEATURE_SHELL_RDF; shell_sdf=True: with VMD_SCRIPT_FEATURE_SHELL_SDF."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
     features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0) | \
-        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0)
+        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0) | (FEATURE_SHELL_SDF if shell_sdf else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
