@@ -22,12 +22,14 @@ VIAMD_DEFAULT_SCRIPT = ("s1 = resname(\"ALA\")[2:8];\nd1 = distance(10,30);\na1 
                         "r = rdf(element('C'), element('H'), 10.0);\nv = sdf(s1, element('H'), 10.0);\n{lin,plan,iso} = shape_weights(all);")
 
 
-def evaluate(lib, ir, coords, box, mass=None, tilt=(0.0, 0.0, 0.0), ranges=None, pooled=None):
+def evaluate(lib, ir, coords, box, mass=None, tilt=(0.0, 0.0, 0.0), ranges=None, pooled=None, flags=L.PBC_ALL, device=False):
+    """device=True: the frames are a resident DeviceTrajectory (cases.make_traj); flags: the cell's periodic-axis bits"""
+    import cases
     F, _, N = coords.shape
-    cell = V.make_unitcell(box, tilt=tilt)
+    cell = V.make_unitcell(box, flags, tilt)
     ev = V.ScriptEval(F, ir)
     sysm = V.MolSystem(N, mass=mass, unitcell=cell)
-    traj = V.HostTrajectory(coords, cell)
+    traj = cases.make_traj(lib, coords, cell, device)
     for beg, end in (ranges or [(0, F)]):
         assert (ev.frame_range_pooled(sysm, traj, beg, end, *pooled) if pooled else ev.frame_range(sysm, traj, beg, end))
     return ev
@@ -41,6 +43,30 @@ def rows(ev, name):
 def bits_equal(a, b):
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
     return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def ulps(a, b):
+    """distance in fp32 units in the last place; the bit patterns are mapped to one ordered line, so values on either side of 0 count
+    too (+0 and -0 are 0 apart: the sign bit is checked where it matters)"""
+    def line(v):
+        i = np.asarray(v, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return np.abs(line(a) - line(b))
+
+
+def check_values(got, ref, what, exact=True):
+    """exact (the emulator): bit-identical to the restatement.  Otherwise (the device, whose atan2 is ocml's) the rule of
+    test_geometry_gpu._check: every value within 1 fp32 ulp, at most max(1, size // 1000) values not bit-identical."""
+    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    if exact:
+        assert bits_equal(got, ref), what
+        return
+    u = ulps(got, ref)
+    off = int((got.view(np.int32) != ref.view(np.int32)).sum())
+    print(f"{what}: {got.size} values, {off} not bit-identical, max {int(u.max())} ulp")
+    assert u.max() <= 1, f"{what}: {int(u.max())} ulp from the reference"
+    assert off <= max(1, got.size // 1000), f"{what}: {off} values not bit-identical"
 
 
 def blob_system(oracle, n_atoms=1200, n_blob=200, box=30.0, F=4, seed=5):
@@ -61,8 +87,7 @@ def _one_frame(lib, pts, box=50.0, tilt=(0.0, 0.0, 0.0), kind="angle"):
     return float(rows(evaluate(lib, ir, xyz, box, tilt=tilt), "g")[0, 0])
 
 
-def test_known_answers_on_the_emulator(emu_lib):
-    lib = emu_lib
+def known_answers(lib):
     assert _one_frame(lib, [(1, 0, 0), (0, 0, 0), (0, 1, 0)]) == 90.0                # the angle sits at the middle argument
     assert _one_frame(lib, [(0, 0, 0), (1, 0, 0), (0, 1, 0)]) == np.float32(45.0)
     assert _one_frame(lib, [(-1, 0, 0), (0, 0, 0), (2, 0, 0)]) == 180.0               # straight
@@ -83,72 +108,217 @@ def test_known_answers_on_the_emulator(emu_lib):
     assert ir.property_flags("a") == L.FLAG_TEMPORAL
 
 
-def test_triclinic_cell_matches_the_reference(emu_lib):
+def test_known_answers_on_the_emulator(emu_lib):
+    known_answers(emu_lib)
+
+
+TRICLINIC = ((24.0, 22.0, 20.0), (5.0, -3.0, 4.0))
+DIH_POP = [[[6 + c] for c in range(4)], [[10 + c, 20 + c] for c in range(4)], [[30 + c] for c in range(4)],
+           [[40 + c, 50 + c] for c in range(4)]]
+
+
+def multi_atom_cell_case(lib, box, tilt=(0.0, 0.0, 0.0), flags=L.PBC_ALL, exact=True, device=False, what="cell"):
+    """multi-atom, mass-weighted arguments of one angle and of a dihedral population in the given cell -> (angle, dihedral) of the
+    restatement"""
     rng = np.random.default_rng(3)
-    box, tilt = (24.0, 22.0, 20.0), (5.0, -3.0, 4.0)
     coords = rng.uniform(-6, 30, (3, 3, 60)).astype(np.float32)
     mass = rng.uniform(1, 16, 60).astype(np.float32)
-    ir = V.ScriptIR(emu_lib)
+    ir = V.ScriptIR(lib)
     ir.add_angle("a", [0, 1], [2], [3, 4, 5])
-    ir.add_dihedral_population("d", [[6 + c] for c in range(4)], [[10 + c, 20 + c] for c in range(4)], [[30 + c] for c in range(4)],
-                               [[40 + c, 50 + c] for c in range(4)])
-    ev = evaluate(emu_lib, ir, coords, box, mass, tilt=tilt)
-    assert bits_equal(rows(ev, "a"), G.values(coords, box + tilt, [[0, 1], [2], [3, 4, 5]], mass))
-    ref = G.values(coords, box + tilt, [[[6 + c] for c in range(4)], [[10 + c, 20 + c] for c in range(4)], [[30 + c] for c in range(4)],
-                                        [[40 + c, 50 + c] for c in range(4)]], mass)
-    assert bits_equal(rows(ev, "d"), ref)
+    ir.add_dihedral_population("d", *DIH_POP)
+    ev = evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags, device=device)
+    bx = tuple(box) + tuple(tilt) if tuple(tilt) != (0.0, 0.0, 0.0) else box
+    ref_a = G.values(coords, bx, [[0, 1], [2], [3, 4, 5]], mass, flags=flags)
+    ref_d = G.values(coords, bx, DIH_POP, mass, flags=flags)
+    check_values(rows(ev, "a"), ref_a, f"{what}: angle of multi-atom arguments", exact)
+    check_values(rows(ev, "d"), ref_d, f"{what}: dihedral population", exact)
+    return ref_a, ref_d
+
+
+def triclinic_cell(lib, exact=True, device=False):
+    multi_atom_cell_case(lib, *TRICLINIC, exact=exact, device=device, what="triclinic cell")
+
+
+def test_triclinic_cell_matches_the_reference(emu_lib):
+    triclinic_cell(emu_lib)
+
+
+def partly_periodic_cell(lib, exact=True, device=False):
+    """a slab: y open (flags 5).  The restatement's own numbers must differ from the fully periodic cell's, or the open axis is idle."""
+    box = (24.0, 22.0, 20.0)
+    slab = multi_atom_cell_case(lib, box, flags=5, exact=exact, device=device, what="slab, y open")
+    full = multi_atom_cell_case(lib, box, exact=exact, device=device, what="the same cell, periodic")
+    for s, f in zip(slab, full):
+        assert (s != f).mean() > 0.5, "the open axis changes too few values"
+
+
+def test_partly_periodic_cell_matches_the_reference(emu_lib):
+    partly_periodic_cell(emu_lib)
 
 
 # ---- parity with the reference ------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("geometric", [0, 1])
-def test_emulator_matches_reference_bit_for_bit(emu_lib, oracle, geometric):
+PARITY_SCRIPT = ('pa = angle(2,1,3) in resname("ALA");\npd = dihedral(1,2,3,4) in residue(2:15);\n'
+                 'pr = angle(element(\'C\'), 1, 4) in resid(103:112);\npw = dihedral(1,2,3,1) in resname("HOH")[1:40];')
+
+
+def parity(lib, oracle, geometric, exact=True, device=False):
+    """single atoms, multi-atom mass-weighted arguments and script populations against the restatement, under spec_dist_geometric_com"""
     coords, topo = blob_system(oracle)
     F, _, N = coords.shape
-    old = emu_lib.vmd_set_option(b"spec_dist_geometric_com", geometric)
+    old = lib.vmd_set_option(b"spec_dist_geometric_com", geometric)
     try:
         rng = np.random.default_rng(11)
-        ir = V.ScriptIR(emu_lib)
+        ir = V.ScriptIR(lib)
         ir.add_angle("a1", [7], [3], [250])                                  # single atoms: the atoms' own coordinates
         multi = [rng.choice(N, 5, replace=False) for _ in range(4)]
         ir.add_angle("am", *multi[:3])
         ir.add_dihedral("dm", *multi)
-        src = ('pa = angle(2,1,3) in resname("ALA");\npd = dihedral(1,2,3,4) in residue(2:15);\n'
-               'pr = angle(element(\'C\'), 1, 4) in resid(103:112);\npw = dihedral(1,2,3,1) in resname("HOH")[1:40];')
-        ir_src, info = script.compile_script(src, topo, lib=emu_lib, angles=True)
-        ev = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
-        ev2 = evaluate(emu_lib, ir_src, coords, 30.0, topo.mass)
+        ir_src, info = script.compile_script(PARITY_SCRIPT, topo, lib=lib, angles=True)
+        ev = evaluate(lib, ir, coords, 30.0, topo.mass, device=device)
+        ev2 = evaluate(lib, ir_src, coords, 30.0, topo.mass, device=device)
         for name, sets in (("a1", [[7], [3], [250]]), ("am", multi[:3]), ("dm", multi)):
-            assert bits_equal(rows(ev, name), G.values(coords, 30.0, sets, topo.mass, geometric=geometric)), name
+            check_values(rows(ev, name), G.values(coords, 30.0, sets, topo.mass, geometric=geometric), f"{name} geometric={geometric}", exact)
         for name in ("pa", "pd", "pr", "pw"):
             ref = G.values(coords, 30.0, info[name]["sets"], topo.mass, geometric=geometric)
             got = rows(ev2, name)
-            assert got.shape[1] == len(info[name]["sets"][0]) > 1 and bits_equal(got, ref), name
+            assert got.shape[1] == len(info[name]["sets"][0]) > 1, name
+            check_values(got, ref, f"{name} geometric={geometric}", exact)
         assert len(info["pa"]["sets"][0]) == 20 and len(info["pw"]["sets"][0]) == 40
     finally:
-        emu_lib.vmd_set_option(b"spec_dist_geometric_com", 0)
+        lib.vmd_set_option(b"spec_dist_geometric_com", 0)
     # a one-atom set IS the atom: the same values from the raw coordinates, whatever the weights
     one = G.values(coords, 30.0, [[7], [3], [250]], None)
-    assert bits_equal(rows(ev, "a1"), one)
+    check_values(rows(ev, "a1"), one, "a1 from the raw coordinates", exact)
 
 
-def test_radians_switch(emu_lib, oracle):
+@pytest.mark.parametrize("geometric", [0, 1])
+def test_emulator_matches_reference_bit_for_bit(emu_lib, oracle, geometric):
+    parity(emu_lib, oracle, geometric)
+
+
+def radians_switch(lib, oracle, exact=True, device=False):
     coords, topo = blob_system(oracle, F=2)
-    ir = script.compile_script('pa = angle(2,1,3) in resname("ALA"); pd = dihedral(1,2,3,4) in resname("ALA");', topo, lib=emu_lib,
+    ir = script.compile_script('pa = angle(2,1,3) in resname("ALA"); pd = dihedral(1,2,3,4) in resname("ALA");', topo, lib=lib,
                                angles=True)[0]
-    deg = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
-    old = emu_lib.vmd_set_option(b"spec_angle_radians", 1)
+    deg = evaluate(lib, ir, coords, 30.0, topo.mass, device=device)
+    old = lib.vmd_set_option(b"spec_angle_radians", 1)
     try:
-        rad = evaluate(emu_lib, ir, coords, 30.0, topo.mass)
+        rad = evaluate(lib, ir, coords, 30.0, topo.mass, device=device)
     finally:
-        emu_lib.vmd_set_option(b"spec_angle_radians", old)
+        lib.vmd_set_option(b"spec_angle_radians", old)
     assert deg.property_data("pa").unit_str == ("", "°") and rad.property_data("pa").unit_str == ("", "rad")
     for name in ("pa", "pd"):
         info_sets = script.compile_script(f'x = {"angle(2,1,3)" if name == "pa" else "dihedral(1,2,3,4)"} in resname("ALA");', topo,
-                                          lib=emu_lib, angles=True)[1]["x"]["sets"]
-        assert bits_equal(rows(rad, name), G.values(coords, 30.0, info_sets, topo.mass, radians=True))
-        assert bits_equal(rows(deg, name), G.values(coords, 30.0, info_sets, topo.mass))
+                                          lib=lib, angles=True)[1]["x"]["sets"]
+        check_values(rows(rad, name), G.values(coords, 30.0, info_sets, topo.mass, radians=True), f"{name} in radians", exact)
+        check_values(rows(deg, name), G.values(coords, 30.0, info_sets, topo.mass), f"{name} in degrees", exact)
         assert not np.array_equal(rows(rad, name), rows(deg, name))
+
+
+def test_radians_switch(emu_lib, oracle):
+    radians_switch(emu_lib, oracle)
+
+
+# ---- values at the ends of the range -----------------------------------------------------------------------------------------------
+
+def range_ends_system():
+    """-> (coords float32 [1, 3, N], angle argument sets, dihedral argument sets, masks of the contexts meant to sit at 0 / at 180).
+    Every coordinate lies in [2, 8) on the 2^-21 grid, so the fp32 copy is exact.  Angles: the arms a - b and c - b run along one
+    direction, straight or folded back, and c is moved sideways by 0 - 64 ulps (2^-21 of an arm of 2 - 2.5: under 1e-3 degrees).
+    Dihedrals: a and d stand on the same side of b - c (cis) or on opposite sides (trans), and d is turned about b - c by as much to
+    either side.  The last contexts are degenerate on purpose: an operand of atan2 is -0 before `+ 0.0` there."""
+    rng = np.random.default_rng(21)
+    ulp = 2.0 ** -21
+    dirs = np.array([d for d in np.ndindex(5, 5, 5)], np.float64) - 2.0                  # components -2 .. 2
+    dirs = dirs[np.abs(dirs).max(axis=1) == 2]                                           # longest component 2: |d| in [2, 3.5]
+    pts, ang, dih = [], [], []
+    near0_a, near180_a, near0_d, near180_d = [], [], [], []
+
+    def add(*p):
+        pts.extend(p)
+        return list(range(len(pts) - len(p), len(pts)))
+
+    n_each = 96
+    for c in range(n_each):
+        b = 5.25 + rng.integers(0, 2 ** 19, 3) * ulp                                    # [5.25, 5.5)
+        d = dirs[rng.integers(len(dirs))]                                                # |d| in [2, 3.5]
+        k = 0 if c < 8 else int(rng.integers(1, 65))
+        bump = np.zeros(3)
+        bump[int(np.argmin(np.abs(d)))] = k * ulp * (1 if c % 4 < 2 else -1)             # sideways: along the arm's shortest component
+        folded = c % 2 == 0
+        a = b - d * (1.25 if c % 3 == 0 else 1.0)
+        cc = b + (-d if folded else d) + bump
+        ang.append(add(a, b, cc))
+        (near0_a if folded else near180_a).append(len(ang) - 1)
+    for c in range(n_each):
+        b = 5.25 + rng.integers(0, 2 ** 19, 3) * ulp
+        axis = c % 3
+        b2 = np.zeros(3); b2[axis] = 1.0 if c % 2 else -1.25
+        up = np.zeros(3); up[(axis + 1) % 3] = 2.0 if c % 4 < 2 else -2.25
+        turn = np.zeros(3)
+        k = 0 if c < 8 else int(rng.integers(1, 65))
+        turn[(axis + 2) % 3] = k * ulp * (1 if c % 8 < 4 else -1)
+        trans = c % 2 == 1
+        a, cc = b + up, b + b2
+        d = cc + (-up if trans else up) + turn
+        dih.append(add(a, b, cc, d))
+        (near180_d if trans else near0_d).append(len(dih) - 1)
+    # degenerate on purpose.  An angle with a zero-length arm whose other arm has three negative components: u . v = -0.
+    b = np.array([5.25, 5.375, 5.5])
+    ang.append(add(b, b, b - np.array([2.0, 1.0, 0.5])))
+    near0_a.append(len(ang) - 1)
+    # A dihedral with b1 = -b2 / 2 (n1 = +0 exactly) and n2 = b2 x b3 all negative: n1 . n2 = -0 and y = +0 -> 0, not 180
+    b2, b3 = np.array([2.0, -1.0, 0.5]), np.array([-2.5, 1.0, 0.5])
+    assert (np.cross(b2, b3) < 0).all()
+    a = b + b2 / 2
+    dih.append(add(a, b, b + b2, b + b2 + b3))
+    near0_d.append(len(dih) - 1)
+    # Planar trans dihedrals on small integers: b1 . n2 sums three products that are each -0, so y = -0 before `+ 0.0` -> +180, not -180
+    for b1, b2, b3 in (((-2, -2, 0), (1, -1, 0), (1, -2, 0)), ((-2, -2, 0), (1, 0, 0), (0, -2, 0)), ((-2, -2, 0), (-1, -2, 0), (-2, -1, 0))):
+        b1, b2, b3 = (np.array(v, np.float64) for v in (b1, b2, b3))
+        n2 = np.cross(b2, b3)
+        assert all(v == 0.0 and np.signbit(v) for v in b1 * n2) and np.dot(np.cross(b1, b2), n2) < 0.0
+        dih.append(add(b - b1, b, b + b2, b + b2 + b3))
+        near180_d.append(len(dih) - 1)
+    coords = np.asarray(pts, np.float64).T[None]
+    assert coords.min() >= 2.0 and coords.max() < 8.0 and np.array_equal(coords, np.round(coords / ulp) * ulp)
+    as_sets = lambda ctx: [[[c[k]] for c in ctx] for k in range(len(ctx[0]))]
+    return coords.astype(np.float32), as_sets(ang), as_sets(dih), (near0_a, near180_a, near0_d, near180_d)
+
+
+def range_ends(lib, exact=True, device=False):
+    """0 <= angle <= 180 and -180 < dihedral <= 180; where the restatement gives exactly 0 or +180 so does the kernel, sign bit
+    included; every value within 1 ulp of the restatement (the emulator: bit-identical).  Both sides form the operands of atan2 by the
+    same uncontracted fp64 operations: only atan2 itself and the final rounding can differ."""
+    coords, ang, dih, (near0_a, near180_a, near0_d, near180_d) = range_ends_system()
+    ir = V.ScriptIR(lib)
+    ir.add_angle_population("a", *ang)
+    ir.add_dihedral_population("d", *dih)
+    ev = evaluate(lib, ir, coords, 64.0, device=device)
+    got_a, got_d = rows(ev, "a")[0], rows(ev, "d")[0]
+    ref_a, ref_d = G.values(coords, 64.0, ang)[0], G.values(coords, 64.0, dih)[0]
+    # the inputs are what they are meant to be (the restatement's own numbers)
+    assert (ref_a[near0_a] < 1e-3).all() and (ref_a[near180_a] > 180.0 - 1e-3).all()
+    assert (np.abs(ref_d[near0_d]) < 1e-3).all() and (np.abs(ref_d[near180_d]) > 180.0 - 1e-3).all()
+    assert (ref_a == 0.0).sum() >= 4 and (ref_a == 180.0).sum() >= 4 and (ref_d == 0.0).sum() >= 4 and (ref_d == 180.0).sum() >= 4
+    assert (ref_d[near180_d] < 0.0).sum() >= 20 and (ref_d[near180_d] > 0.0).sum() >= 20             # both sides of trans
+    assert (ref_d[near0_d] < 0.0).sum() >= 20 and ((ref_a > 0.0) & (ref_a < 1e-3)).sum() >= 20
+    for what, got, ref in (("angles at the ends of the range", got_a, ref_a), ("dihedrals at the ends of the range", got_d, ref_d)):
+        assert np.isfinite(got).all(), what
+        for end in (0.0, 180.0):
+            at = ref == np.float32(end)
+            assert np.array_equal(got[at].view(np.int32), ref[at].view(np.int32)), f"{what}: {got[at]} where the reference has +{end}"
+        u = ulps(got, ref)
+        print(f"{what}: {got.size} values, {int((got.view(np.int32) != ref.view(np.int32)).sum())} not bit-identical, max {int(u.max())} ulp")
+        assert u.max() <= 1, f"{what}: {int(u.max())} ulp from the reference"
+        assert not exact or bits_equal(got, ref), what
+    assert got_a.min() >= 0.0 and got_a.max() <= 180.0 and not np.signbit(got_a[got_a == 0.0]).any()
+    assert got_d.min() > -180.0 and got_d.max() <= 180.0
+
+
+def test_values_at_the_ends_of_the_range_on_the_emulator(emu_lib):
+    range_ends(emu_lib)
 
 
 def _ala(topo):

@@ -1,5 +1,6 @@
-"""angle() / dihedral() (DESIGN S6b) on the MI355X: parity with tests/geometry_ref.py at BASELINE sizes, determinism of the call
-patterns, and VIAMD's default script through the shim with the angle opt-in, linked against the product."""
+"""angle() / dihedral() (DESIGN S6b) on the MI355X: known answers, values at the ends of the range, multi-atom arguments in triclinic
+and partly periodic cells, parity with tests/geometry_ref.py at BASELINE sizes, determinism of the call patterns, and VIAMD's default
+script through the shim with the angle opt-in, linked against the product."""
 import os
 import subprocess
 
@@ -28,6 +29,32 @@ def _check(got, ref, what):
     print(f"{what}: {got.size} values, {off} not bit-identical, max {int(u.max())} ulp")
     assert u.max() <= 1, f"{what}: {int(u.max())} ulp from the reference"
     assert off <= max(1, got.size // 1000), f"{what}: {off} values not bit-identical"
+
+
+def test_known_answers_on_the_device(gpu_lib):
+    """exact equalities: `+ 0.0` in k_geom keeps trans at +180 and degenerate input at 0 - a property of the device compile"""
+    TG.known_answers(gpu_lib)
+
+
+def test_values_at_the_ends_of_the_range_on_the_device(gpu_lib):
+    TG.range_ends(gpu_lib, exact=False, device=True)
+
+
+def test_triclinic_cell_on_the_device(gpu_lib):
+    TG.triclinic_cell(gpu_lib, exact=False, device=True)
+
+
+def test_partly_periodic_cell_on_the_device(gpu_lib):
+    TG.partly_periodic_cell(gpu_lib, exact=False, device=True)
+
+
+@pytest.mark.parametrize("geometric", [0, 1])
+def test_multi_atom_arguments_and_populations_on_the_device(gpu_lib, oracle, geometric):
+    TG.parity(gpu_lib, oracle, geometric, exact=False, device=True)
+
+
+def test_radians_switch_on_the_device(gpu_lib, oracle):
+    TG.radians_switch(gpu_lib, oracle, exact=False, device=True)
 
 
 def test_water_angle_population_config2(gpu_lib):

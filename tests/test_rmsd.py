@@ -17,6 +17,7 @@ from viamd_amd import script, synth
 
 import rmsd_ref as R
 import test_geometry as TG
+import test_shape as TS
 from test_geometry import bits_equal, blob_system, evaluate, rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,12 +27,12 @@ VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
 RM_LINE = '\nrm = rmsd(resname("ALA"));'
 
 
-def check_tolerance(got, coords, box, sets, mass, what, geometric=False, frames=None):
+def check_tolerance(got, coords, box, sets, mass, what, geometric=False, frames=None, flags=7):
     """|got - ref| <= 2^-23 ref + min(delta / ref, sqrt(delta)), delta = max(n, 64) 2^-52 (Gp + Gq) / W (rmsd_ref.bound), against
     the SVD restatement, every value; bit-identity with the pinned restatement is counted and printed.  Returns that count."""
     got = np.asarray(got, np.float32)
-    ref, bnd = R.values(coords, box, sets, mass, geometric=geometric, frames=frames, pinned=False, with_bound=True)
-    pin = R.values(coords, box, sets, mass, geometric=geometric, frames=frames)
+    ref, bnd = R.values(coords, box, sets, mass, geometric=geometric, flags=flags, frames=frames, pinned=False, with_bound=True)
+    pin = R.values(coords, box, sets, mass, geometric=geometric, flags=flags, frames=frames)
     assert got.shape == ref.shape, (got.shape, ref.shape)
     assert np.isfinite(got).all(), what
     off = int((got.view(np.int32) != pin.view(np.int32)).sum())
@@ -184,7 +185,13 @@ def test_a_wide_chain_that_tumbles_on_the_emulator(emu_lib):
 # ---- parity with the references --------------------------------------------------------------------------------------------------------
 
 CELLS = [((30.0, 30.0, 30.0), (0.0, 0.0, 0.0)), ((24.0, 22.0, 20.0), (5.0, -3.0, 4.0))]
-SIZES = [1, 2, 3, 64, 65, R.CHUNK - 1, R.CHUNK, R.CHUNK + 1, 2 * R.CHUNK + 808]
+OPEN_CELLS = TS.OPEN_CELLS          # a slab with y open, a wire along y: links longer than half a cell that take no shift
+# 63: one idle lane in the butterfly and the wave scan; 64 / 65: wave-per-set kernel / block kernels; 255 / 256 / 257: thread 0 takes a
+# second atom (the second s_tot slot); CHUNK +- 1, 2 CHUNK - 1: the chunk seams - the link across and the carried-in shift, a last chunk
+# of one atom included; the last: three chunks
+SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, R.CHUNK - 1, R.CHUNK, R.CHUNK + 1, 2 * R.CHUNK - 1, 2 * R.CHUNK + 808]
+POPULATIONS = [[1, 3, 64, 65, 200, R.CHUNK + 5, 700], [1, 2, 3, 10, 64, 33], [10, 64, 700, R.CHUNK + 5]]
+COPIES = TS.COPIES
 
 
 def random_system(seed, n_atoms, F=3):
@@ -194,32 +201,97 @@ def random_system(seed, n_atoms, F=3):
     return rng, coords, rng.uniform(1, 16, n_atoms).astype(np.float32)
 
 
-@pytest.mark.parametrize("box,tilt", CELLS)
-def test_emulator_matches_the_pinned_reference_bit_for_bit(emu_lib, box, tilt):
+def size_sweep(lib, box, tilt=(0.0, 0.0, 0.0), flags=7, exact=True, device=False, sizes=SIZES, populations=POPULATIONS):
+    """Single sets of the edge sizes, unequal populations, the alone / small-population / next-to-large identity and the equal columns,
+    in one cell.  exact (the emulator): bit-identical to the pinned restatement.  Every value within rmsd_ref.bound of the SVD
+    restatement; the values not bit-identical to the pinned one are counted and printed.  Row 0 is +0 bit for bit.  device: a resident
+    trajectory, which must give the bits of the host-staged one.  A partly periodic cell (flags != 7) must change the restatement's
+    own numbers."""
     rng, coords, mass = random_system(1, 9100)
-    for n in SIZES:
-        idx = rng.choice(9100, n, replace=False).astype(np.int32)
-        ir = V.ScriptIR(emu_lib)
-        ir.add_rmsd("g", idx)
-        got = rows(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt), "g")
-        assert check_tolerance(got, coords, box + tilt, idx, mass, f"emulator, {n} atoms, tilt {tilt}") == 0, n
-    # populations: unequal sets, the largest beyond one chunk (blocks per chunk) / of at most 64 atoms (one wave per set)
-    for sizes in ([1, 3, 64, 65, 200, R.CHUNK + 5, 700], [1, 2, 3, 10, 64, 33]):
-        sets = [rng.choice(9100, n, replace=False).astype(np.int32) for n in sizes]
-        ir = V.ScriptIR(emu_lib)
+    bx = tuple(box) + tuple(tilt)
+    tag = f"tilt {tilt}, flags {flags}"
+
+    def run(sets):
+        ir = V.ScriptIR(lib)
         ir.add_rmsd_population("g", sets)
-        got = rows(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt), "g")
-        assert got.shape == (3, len(sizes))
-        assert check_tolerance(got, coords, box + tilt, sets, mass, f"emulator, population {sizes}, tilt {tilt}") == 0, sizes
+        got = rows(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags, device=device), "g")
+        assert got.shape == (3, len(sets)) and not got.view(np.int32)[0].any()                      # trajectory frame 0: +0
+        if device:
+            assert bits_equal(got, rows(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags), "g")), "resident / host-staged"
+        return got
+
+    for n in sizes:
+        idx = rng.choice(9100, n, replace=False).astype(np.int32)
+        ir = V.ScriptIR(lib)
+        ir.add_rmsd("g", idx)
+        got = rows(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags, device=device), "g")
+        assert got.shape == (3, 1) and not got.view(np.int32)[0].any()
+        if device:
+            assert bits_equal(got, rows(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags), "g")), "resident / host-staged"
+        off = check_tolerance(got, coords, bx, idx, mass, f"{n} atoms, {tag}", flags=flags)
+        assert not exact or off == 0, n
+        if flags != 7 and n >= 63:
+            assert not bits_equal(R.values(coords, bx, idx, mass, flags=flags), R.values(coords, bx, idx, mass)), \
+                f"{n} atoms: the open axes change nothing"
+    for sizes_p in populations:
+        sets = [rng.choice(9100, n, replace=False).astype(np.int32) for n in sizes_p]
+        off = check_tolerance(run(sets), coords, bx, sets, mass, f"population {sizes_p}, {tag}", flags=flags)
+        assert not exact or off == 0, sizes_p
     # a set gives the same bits alone, in a population of small sets and in a population with a large one
     small = rng.choice(9100, 40, replace=False).astype(np.int32)
     big = rng.choice(9100, 5000, replace=False).astype(np.int32)
-    res = []
-    for sets, pos in (([small], 0), ([small, small[:7]], 0), ([big, small], 1)):
-        ir = V.ScriptIR(emu_lib)
-        ir.add_rmsd_population("g", sets)
-        res.append(rows(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt), "g")[:, pos])
+    res = [run(sets)[:, pos] for sets, pos in (([small], 0), ([small, small[:7]], 0), ([big, small], 1))]
     assert bits_equal(res[0], res[1]) and bits_equal(res[0], res[2]) and res[0][1] > 0.0
+    # P columns of that set: bit-equal, whichever wave of whichever block forms them
+    for P in COPIES:
+        got = run([small] * P)
+        for c in range(P):
+            assert bits_equal(got[:, c], res[0]), (P, c)
+
+
+@pytest.mark.parametrize("box,tilt", CELLS)
+def test_emulator_matches_the_pinned_reference_bit_for_bit(emu_lib, box, tilt):
+    size_sweep(emu_lib, box, tilt)
+
+
+@pytest.mark.parametrize("box,flags", OPEN_CELLS)
+def test_emulator_matches_the_pinned_reference_in_partly_periodic_cells(emu_lib, box, flags):
+    size_sweep(emu_lib, box, flags=flags)
+
+
+# ---- half-cell ties ------------------------------------------------------------------------------------------------------------------
+
+def half_cell_ties(lib, box, flags=7, exact=True, device=False):
+    """TS.tie_system along the chain: every third link is exactly L / 2, -L / 2, 3 L / 2 or -3 L / 2 long on one axis.  Frame 0 is the
+    pose; frame 1 holds the same points in reverse order (every link negated: the ties round the other way) and frame 2 a rigidly moved
+    copy (the same links from other coordinates)."""
+    pose, sets = TS.tie_system(box, chain=True)
+    rev = pose.copy()
+    for s in sets:
+        rev[0][:, s] = pose[0][:, s[::-1]]
+    moved = pose + np.array([7.25, -11.5, 2.125], np.float32)[None, :, None]
+    coords = np.concatenate([pose, rev, moved]).astype(np.float32)
+    x = coords.astype(np.float64)
+    Lf = np.asarray(box, np.float32).astype(np.float64)
+    if float(np.float32(box[0])) == box[0]:                     # the ties are exact: d / L is a half-integer, bit for bit, in every frame
+        for f in range(3):
+            q = np.concatenate([np.diff(x[f][:, s], axis=1) / Lf[:, None] for s in sets], axis=1)
+            assert ((np.abs(q) == 0.5).sum(axis=1) >= 6).all() and ((np.abs(q) == 1.5).sum(axis=1) >= 6).all(), f
+    mass = np.random.default_rng(32).uniform(1, 16, coords.shape[2]).astype(np.float32)
+    for group, what in ((sets[:3], "ties, one wave per set"), (sets[3:] + sets[:1], "ties, block kernels")):
+        ir = V.ScriptIR(lib)
+        ir.add_rmsd_population("g", group)
+        got = rows(evaluate(lib, ir, coords, box, mass, flags=flags, device=device), "g")
+        assert not got.view(np.int32)[0].any()
+        off = check_tolerance(got, coords, box, group, mass, f"{what}, cell {box}, flags {flags}", flags=flags)
+        assert not exact or off == 0, (what, box, flags)
+        if flags != 7:          # the open axis takes no shift however long the link is: the periodic cell's numbers differ
+            assert not bits_equal(R.values(coords, box, group, mass, flags=flags), R.values(coords, box, group, mass))
+
+
+@pytest.mark.parametrize("box,flags", TS.TIE_CELLS)
+def test_half_cell_ties_on_the_emulator(emu_lib, box, flags):
+    half_cell_ties(emu_lib, box, flags)
 
 
 POP_SCRIPT = ('g = rmsd(all);\nga = rmsd(resname("ALA"));\ngr = rmsd(all) in resname("ALA");\n'

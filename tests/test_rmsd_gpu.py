@@ -1,6 +1,7 @@
-"""rmsd() on the MI355X: known answers and the chain that tumbles, the derived tolerance against both restatements of
-tests/rmsd_ref.py at BASELINE sizes, the reduction-order rule under VIAMD's call patterns, the pose's lifetime, and VIAMD's default script
-plus an rmsd line through the shim with the three opt-ins, linked against the product."""
+"""rmsd() on the MI355X: known answers and the chain that tumbles, the set sizes at the kernels' edges, partly periodic
+cells, half-cell ties, the derived tolerance against both restatements of tests/rmsd_ref.py at BASELINE sizes, the reduction-order rule
+under VIAMD's call patterns, the pose's lifetime, and VIAMD's default script plus an rmsd line through the shim with the three opt-ins,
+linked against the product."""
 import subprocess
 
 import numpy as np
@@ -21,6 +22,24 @@ def test_known_answers_on_the_device(gpu_lib):
 
 def test_a_wide_chain_that_tumbles_on_the_device(gpu_lib):
     TR.wide_chain(gpu_lib)
+
+
+@pytest.mark.parametrize("box,tilt", TR.CELLS)
+def test_size_sweep_on_the_device(gpu_lib, box, tilt):
+    """the set sizes at which the kernels change path (the chunk seams with their carried-in shifts among them), the unequal populations
+    and the bit identities (alone / in a population / next to a large set, resident / host-staged, equal columns) on the hardware's
+    own schedule"""
+    TR.size_sweep(gpu_lib, box, tilt, exact=False, device=True)
+
+
+@pytest.mark.parametrize("box,flags", TR.OPEN_CELLS)
+def test_size_sweep_in_partly_periodic_cells_on_the_device(gpu_lib, box, flags):
+    TR.size_sweep(gpu_lib, box, flags=flags, exact=False, device=True)
+
+
+@pytest.mark.parametrize("box,flags", TR.TS.TIE_CELLS)
+def test_half_cell_ties_on_the_device(gpu_lib, box, flags):
+    TR.half_cell_ties(gpu_lib, box, flags, exact=False, device=True)
 
 
 def test_water_box_config2(gpu_lib):

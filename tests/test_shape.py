@@ -93,7 +93,17 @@ def test_known_answers_on_the_emulator(emu_lib):
 # ---- parity with the references --------------------------------------------------------------------------------------------------------
 
 CELLS = [((30.0, 30.0, 30.0), (0.0, 0.0, 0.0)), ((24.0, 22.0, 20.0), (5.0, -3.0, 4.0))]
-SIZES = [1, 3, 64, 65, S.CHUNK - 1, S.CHUNK, S.CHUNK + 1, 2 * S.CHUNK + 808]
+# partly periodic orthorhombic cells (box, periodic-axis bits): a slab with y open, a wire along y (x and z open).  random_system's
+# cloud is 42 wide in x and 21 in y, so with these cells every set of 63 atoms or more has offsets beyond half of Lx or Ly that the open
+# axis must leave alone.  (z open alone changes nothing - the cloud's z extent never exceeds half a cell - so it is not used.)
+OPEN_CELLS = [((30.0, 12.0, 30.0), 5), ((30.0, 14.0, 26.0), 2)]
+# 63: one idle lane in the butterfly; 64 / 65: wave-per-set kernel / block kernels; 255 / 256 / 257: thread 0 takes a second atom;
+# CHUNK +- 1, 2 CHUNK - 1: the chunk seams (a last chunk of one atom included); the last: three chunks
+SIZES = [1, 2, 3, 63, 64, 65, 255, 256, 257, S.CHUNK - 1, S.CHUNK, S.CHUNK + 1, 2 * S.CHUNK - 1, 2 * S.CHUNK + 808]
+# unequal sets: the largest beyond one chunk (blocks per chunk, contexts with fewer chunks than the largest) / of at most 64 atoms (one wave
+# per set) / the large set last
+POPULATIONS = [[1, 3, 64, 65, 200, S.CHUNK + 5, 700], [1, 2, 3, 10, 64, 33], [10, 64, 700, S.CHUNK + 5]]
+COPIES = (1, 4, 5, 64, 65)        # columns of one set: the partial last block of k_*_small, the partial last wave of k_*_finish
 
 
 def random_system(seed, n_atoms, F=2):
@@ -103,34 +113,129 @@ def random_system(seed, n_atoms, F=2):
     return rng, coords, rng.uniform(1, 16, n_atoms).astype(np.float32)
 
 
-@pytest.mark.parametrize("box,tilt", CELLS)
-def test_emulator_matches_the_pinned_reference_bit_for_bit(emu_lib, box, tilt):
+def size_sweep(lib, box, tilt=(0.0, 0.0, 0.0), flags=7, exact=True, device=False, sizes=SIZES, populations=POPULATIONS):
+    """Single sets of the edge sizes, unequal populations, the alone / small-population / next-to-large identity and the equal columns,
+    in one cell.  exact (the emulator): bit-identical to the pinned restatement.  Every value within S.TOL of both restatements; the
+    values not bit-identical to the pinned one are counted and printed.  device: a resident trajectory, which must give the bits of
+    the host-staged one.  A partly periodic cell (flags != 7) must change the restatement's own numbers."""
     rng, coords, mass = random_system(1, 9100)
-    for n in SIZES:
+    bx = tuple(box) + tuple(tilt)
+    tag = f"tilt {tilt}, flags {flags}"
+
+    def run(build):
+        ir = V.ScriptIR(lib)
+        build(ir)
+        got = weights(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags, device=device))
+        if device:
+            assert bits_equal(got, weights(evaluate(lib, ir, coords, box, mass, tilt=tilt, flags=flags))), "resident / host-staged"
+        return got
+
+    def check(got, sets, what):
+        pin = S.values(coords, bx, sets, mass, flags=flags)
+        if exact:
+            assert bits_equal(got, pin), what
+        check_tolerance(got, pin, f"{what}, {tag} / pinned")
+        check_tolerance(got, S.values(coords, bx, sets, mass, flags=flags, pinned=False), f"{what}, {tag} / plain")
+        return pin
+
+    for n in sizes:
         idx = rng.choice(9100, n, replace=False).astype(np.int32)
-        ir = V.ScriptIR(emu_lib)
-        ir.add_shape_weights(NAMES, idx)
-        got = weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))
-        assert bits_equal(got, S.values(coords, box + tilt, idx, mass)), n
-        check_tolerance(got, S.values(coords, box + tilt, idx, mass, pinned=False), f"emulator, {n} atoms, tilt {tilt}")
-    # populations: unequal sets, the largest beyond one chunk (blocks per chunk) / of at most 64 atoms (one wave per set)
-    for sizes in ([1, 3, 64, 65, 200, S.CHUNK + 5, 700], [1, 2, 3, 10, 64, 33]):
-        sets = [rng.choice(9100, n, replace=False).astype(np.int32) for n in sizes]
-        ir = V.ScriptIR(emu_lib)
-        ir.add_shape_weights_population(NAMES, sets)
-        got = weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))
-        assert got.shape == (3, 2, len(sizes))
-        assert bits_equal(got, S.values(coords, box + tilt, sets, mass)), sizes
-        check_tolerance(got, S.values(coords, box + tilt, sets, mass, pinned=False), f"emulator, population {sizes}, tilt {tilt}")
+        pin = check(run(lambda ir: ir.add_shape_weights(NAMES, idx)), idx, f"{n} atoms")
+        if flags != 7 and n >= 63:
+            assert not bits_equal(pin, S.values(coords, bx, idx, mass)), f"{n} atoms: the open axes change nothing"
+    for sizes_p in populations:
+        sets = [rng.choice(9100, n, replace=False).astype(np.int32) for n in sizes_p]
+        got = run(lambda ir: ir.add_shape_weights_population(NAMES, sets))
+        assert got.shape == (3, 2, len(sizes_p))
+        check(got, sets, f"population {sizes_p}")
     # a set gives the same bits alone, in a population of small sets and in a population with a large one
     small = rng.choice(9100, 40, replace=False).astype(np.int32)
     big = rng.choice(9100, 5000, replace=False).astype(np.int32)
     res = []
     for sets, pos in (([small], 0), ([small, small[:7]], 0), ([big, small], 1)):
-        ir = V.ScriptIR(emu_lib)
-        ir.add_shape_weights_population(NAMES, sets)
-        res.append(weights(evaluate(emu_lib, ir, coords, box, mass, tilt=tilt))[:, :, pos])
+        res.append(run(lambda ir: ir.add_shape_weights_population(NAMES, sets))[:, :, pos])
     assert bits_equal(res[0], res[1]) and bits_equal(res[0], res[2])
+    # P columns of that set: bit-equal, whichever wave of whichever block forms them
+    for P in COPIES:
+        got = run(lambda ir: ir.add_shape_weights_population(NAMES, [small] * P))
+        assert got.shape == (3, 2, P)
+        for c in range(P):
+            assert bits_equal(got[:, :, c], res[0]), (P, c)
+
+
+@pytest.mark.parametrize("box,tilt", CELLS)
+def test_emulator_matches_the_pinned_reference_bit_for_bit(emu_lib, box, tilt):
+    size_sweep(emu_lib, box, tilt)
+
+
+@pytest.mark.parametrize("box,flags", OPEN_CELLS)
+def test_emulator_matches_the_pinned_reference_in_partly_periodic_cells(emu_lib, box, flags):
+    size_sweep(emu_lib, box, flags=flags)
+
+
+# ---- half-cell ties ------------------------------------------------------------------------------------------------------------------
+
+TIE_STEPS = (0.5, -0.5, 1.5, -1.5)
+# (cell, periodic-axis bits): 1 / 20 ... are inexact in fp64 for 30 and 100 (d * (1 / L) falls beside the half-integer: the division
+# decides); 24.7f is no fp32-exact half (the near-tie, not the tie); one cell with a different L per axis; a slab with y open and a
+# wire along y, where the open axes must take no shift from atoms 3 L / 2 away.  49: with those cells fl(d * fl(1 / L)) happens to land
+# on the half-integer itself, so rint of it already agrees with the quotient's; 73.5 * fl(1 / 49) is 1.5 - 2^-52, which rounds to 1
+# where the tie goes to 2 - the cell at which the result depends on the division branch
+TIE_CELLS = [((20.0, 20.0, 20.0), 7), ((30.0, 30.0, 30.0), 7), ((100.0, 100.0, 100.0), 7), ((24.7, 24.7, 24.7), 7),
+             ((20.0, 30.0, 100.0), 7), ((30.0, 30.0, 30.0), 5), ((30.0, 30.0, 30.0), 2), ((49.0, 49.0, 49.0), 7)]
+assert np.rint(73.5 * (1.0 / 49.0)) == 1.0 and np.rint(73.5 / 49.0) == 2.0
+TIE_SIZES = (5, 23, 64, 70)          # three sets for the wave-per-set kernels, one for the block kernels
+
+
+def tie_system(box, sizes=TIE_SIZES, chain=False, seed=31):
+    """-> (float32 [1, 3, N], the index sets).  Every set starts at (3, 4, 5).  Every third atom lies exactly L / 2, -L / 2, 3 L / 2 or
+    -3 L / 2 (fp32 arithmetic on the fp32 cell) along one axis from the set's first atom - chain=True: from its predecessor in the
+    set - and off by an ordinary amount along the others; the rest are ordinary.  Ordinary offsets are on a 2^-8 grid, so with
+    L / 2 on that grid every sum is exact in fp32.  Not collinear, not planar."""
+    rng = np.random.default_rng(seed)
+    L = np.asarray(box, np.float32)
+    pts, sets = [], []
+    for n in sizes:
+        first = len(pts)
+        p = [np.array([3.0, 4.0, 5.0], np.float32)]
+        for j in range(1, n):
+            ordinary = (rng.integers(-640, 641, 3) / np.float32(256.0)).astype(np.float32)       # |offset| <= 2.5
+            if chain:
+                ordinary = ordinary * np.float32(0.5)
+            if j % 3 == 1:
+                axis, step = (j // 3) % 3, np.float32(TIE_STEPS[(j // 9) % 4])
+                ordinary[axis] = step * L[axis]
+            p.append(((p[-1] if chain else p[0]) + ordinary).astype(np.float32))
+        pts.extend(p)
+        sets.append(np.arange(first, first + n, dtype=np.int32))
+    return np.asarray(pts, np.float32).T.copy()[None], sets
+
+
+def half_cell_ties(lib, box, flags=7, exact=True, device=False):
+    coords, sets = tie_system(box)
+    x = coords[0].astype(np.float64)
+    Lf = np.asarray(box, np.float32).astype(np.float64)
+    if float(np.float32(box[0])) == box[0]:                     # the ties are exact: d / L is a half-integer, bit for bit
+        q = np.concatenate([(x[:, s] - x[:, s[:1]]) / Lf[:, None] for s in sets], axis=1)
+        assert ((np.abs(q) == 0.5).sum(axis=1) >= 6).all() and ((np.abs(q) == 1.5).sum(axis=1) >= 6).all()
+    mass = np.random.default_rng(32).uniform(1, 16, coords.shape[2]).astype(np.float32)
+    for group, what in ((sets[:3], "ties, one wave per set"), (sets[3:] + sets[:1], "ties, block kernels")):
+        ir = V.ScriptIR(lib)
+        ir.add_shape_weights_population(NAMES, group)
+        got = weights(evaluate(lib, ir, coords, box, mass, flags=flags, device=device))
+        pin = S.values(coords, box, group, mass, flags=flags)
+        if exact:
+            assert bits_equal(got, pin), (what, box, flags)
+        check_tolerance(got, pin, f"{what}, cell {box}, flags {flags} / pinned")
+        check_tolerance(got, S.values(coords, box, group, mass, flags=flags, pinned=False), f"{what}, cell {box}, flags {flags} / plain")
+        assert min(v.min() for v in pin[:, 0, [k for k, g in enumerate(group) if g.size > 5]]) > 1e-3          # no rod, no plane
+        if flags != 7:          # the open axis takes no shift however far the atom is: the periodic cell's numbers differ
+            assert not bits_equal(pin, S.values(coords, box, group, mass))
+
+
+@pytest.mark.parametrize("box,flags", TIE_CELLS)
+def test_half_cell_ties_on_the_emulator(emu_lib, box, flags):
+    half_cell_ties(emu_lib, box, flags)
 
 
 @pytest.mark.parametrize("geometric", [0, 1])

@@ -1,6 +1,6 @@
-"""shape_weights() on the MI355X: known answers, the absolute tolerance against both restatements of tests/shape_ref.py at
-BASELINE sizes, the reduction-order rule under VIAMD's call patterns, one computation per statement, and VIAMD's default script through
-the shim with both opt-ins, linked against the product."""
+"""shape_weights() on the MI355X: known answers, the set sizes at the kernels' edges, partly periodic cells, half-cell ties,
+the absolute tolerance against both restatements of tests/shape_ref.py at BASELINE sizes, the reduction-order rule under VIAMD's call
+patterns, one computation per statement, and VIAMD's default script through the shim with both opt-ins, linked against the product."""
 import subprocess
 
 import numpy as np
@@ -25,6 +25,23 @@ def _check_both(got, coords, box, sets, mass, what):
 
 def test_known_answers_on_the_device(gpu_lib):
     TS.known_answers(gpu_lib)
+
+
+@pytest.mark.parametrize("box,tilt", TS.CELLS)
+def test_size_sweep_on_the_device(gpu_lib, box, tilt):
+    """the set sizes at which the kernels change path, the unequal populations and the bit identities (alone / in a population / next to
+    a large set, resident / host-staged, equal columns) on the hardware's own schedule"""
+    TS.size_sweep(gpu_lib, box, tilt, exact=False, device=True)
+
+
+@pytest.mark.parametrize("box,flags", TS.OPEN_CELLS)
+def test_size_sweep_in_partly_periodic_cells_on_the_device(gpu_lib, box, flags):
+    TS.size_sweep(gpu_lib, box, flags=flags, exact=False, device=True)
+
+
+@pytest.mark.parametrize("box,flags", TS.TIE_CELLS)
+def test_half_cell_ties_on_the_device(gpu_lib, box, flags):
+    TS.half_cell_ties(gpu_lib, box, flags, exact=False, device=True)
 
 
 def test_water_box_config2(gpu_lib):
