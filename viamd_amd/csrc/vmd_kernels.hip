@@ -1683,11 +1683,31 @@ __device__ __forceinline__ int vmd_next_item(unsigned* counters, int& q, int& tr
 // is told to: c3 71.7 -> 70.4 ms per 1 000 frames, c2 7.35 -> 7.23 (profiles/r06u_eight_waves_ab.txt).  Round 2 had measured the shared
 // histogram at seven waves (no gain) and an SGPR cap of 80 on the kernel of that time (no gain); the two together are the default now.
 // Wave-private histograms keep the budget of seven waves (96 SGPRs, as capped since round 1: LDS admits no more).
+// Neighbour walk: a chunk of 64 i atoms meets the j atoms of its neighbour pencils as segments [ja, jb) of the sorted target copy, one per
+// (neighbour pencil, x image) whose x window reaches the chunk.  The segments of a chunk are found by the LANES, not by nested wave-uniform
+// loops (gfx9 has no scalar float ALU: every uniform float op ran on the 64-lane VALU for one number, and each segment waited for a
+// dependent pair of scalar offset loads; what the table saved is in profiles/segment_table_ab.txt): lane c takes neighbour
+// combo c of the (dz, dy) enumeration (dz outer, dy inner; rounds of TABW combos - split pencils 4 x 4 have 81), applies the skip rules
+// (half shell, open axis beyond the bounding box, the item's part of an nsplit launch, a shrunk window that vanishes), wraps the pencil and
+// derives sy, sz, the shrunk rpad and the triclinic offset range, then for each x image kx = -1, 0, 1 the window [lo, hi], its fine cells and -
+// with all loads of the chunk in flight together - ja and jb from the cell offsets.  Everything is the expression, in the order, of the scalar
+// walk it replaces.  The entries go to a per-wave LDS table; one ballot per x image says which of them end in a segment (window on the cell,
+// ja < jb), and a scalar loop takes those off the masks, reads ja, jb and the shifts back into wave-uniform registers and runs vmd_segment.
+// The own pencil is combo (0, 0) = index ry of the half shell.  Segments are walked image by image instead of pencil by pencil: the
+// histograms are integer sums.  The table costs 8 KB of LDS per block (5.5 triclinic); with one histogram per block eight blocks still fit a
+// CU, with wave-private histograms five do instead of seven.
 #ifndef VMD_NO_INLINE_ASM
 #define VMD_PENCIL_OCC(SH) __attribute__((amdgpu_waves_per_eu((SH) ? 8 : 7, (SH) ? 8 : 7)))      /* (amdgpu_num_sgpr takes no template-dependent value; seven waves = the cap of 96 SGPRs of rounds 1 - 5) */
 #else
 #define VMD_PENCIL_OCC(SH)
 #endif
+// dword offsets into a wave's neighbour segment table of W combo lanes: ja / jb per x image and combo lane, sy / sz per combo lane,
+// (triclinic) sx per x image and combo lane
+#define VMD_TAB_JA(W) 0
+#define VMD_TAB_JB(W) (3 * (W))
+#define VMD_TAB_SY(W) (6 * (W))
+#define VMD_TAB_SZ(W) (7 * (W))
+#define VMD_TAB_SX(W) (8 * (W))
 template <int VARIANT_, bool SAME, int CELL, bool SHIST, int POP = 0>
 __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pair_params_t p) {
     constexpr bool TRI = CELL == 1, OPEN = CELL == 2;
@@ -1697,6 +1717,10 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
     // (looking at the stack once per EIGHT columns - a 640-float stack, which the one-histogram kernels have the LDS for - measured 1 % slower
     // than once per four: profiles/r06v_salu_ab.txt)
     __shared__ float s_queue[4][VMD_QUEUE_CAP];
+    // the wave's neighbour segment table (one round of combos).  A triclinic cell also keeps sx per entry and takes its rounds on 32 lanes, so
+    // that histogram, stack and table of eight blocks still fit a CU (5.5 KB and 8 KB of table per block)
+    constexpr int TABW = TRI ? 32 : VMD_WAVE;
+    __shared__ unsigned s_tab[4][(TRI ? 11 : 8) * TABW];
     constexpr unsigned INC = SAME ? 2u : 1u;
     if (p.skip && *p.skip) return;       // set before this launch by the cell build; the host repeats the batch with larger buckets
 
@@ -1736,6 +1760,11 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
     const int nsub = p.nsub;
     const int nsplit = p.nsplit;
     const int nitem_frame = npen * nsub * nsplit;
+    // neighbour combos (dz, dy) in the order dz outer, dy inner; the same-set half shell starts at dz = 0 and drops dy < 0 there
+    const int ncy = 2 * p.ry + 1, dz0 = SAME ? 0 : -p.rz;
+    const int ncombo = (p.rz - dz0 + 1) * ncy;
+    const int cdiv = 65536 / ncy + 1;                       // (c * cdiv) >> 16 == c / ncy for c * ncy < 65536 (the reach is at most 4: 81 combos)
+    unsigned* tab = s_tab[wave];
     if (lane == 0) item = vmd_next_item(p.work_counter, q, tries, p.B, nitem_frame);
     item = __builtin_amdgcn_readfirstlane(item);
     for (; item >= 0; item = next_item) {
@@ -1786,48 +1815,79 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                 bb.rp2 = rp * rp;
             }
 
-            for (int dz = SAME ? 0 : -p.rz; dz <= p.rz; ++dz) {
+            // the neighbour table: lane c of a round takes combo c0 + c, all three x images of it
+            for (int c0 = 0; c0 < ncombo; c0 += TABW) {
+                const int c = c0 + lane;
+                const int dzi = (c * cdiv) >> 16;                   // c / ncy
+                const int dz = dz0 + dzi, dy = c - dzi * ncy - p.ry;
+                bool ok = c < ncombo && lane < TABW;
                 int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
-                if (open_z && (qz < 0 || qz >= nz)) continue;       // nothing beyond the bounding box
+                if (open_z && (qz < 0 || qz >= nz)) ok = false;     // nothing beyond the bounding box
                 if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
-                for (int dy = -p.ry; dy <= p.ry; ++dy) {
-                    if (SAME && dz == 0 && dy < 0) continue;
-                    if (nsplit > 1 && ((dz + p.rz) * (2 * p.ry + 1) + (dy + p.ry)) % nsplit != part) continue;
-                    int qy = py + dy; float sy = 0.0f, nb = 0.0f;
-                    if (open_y && (qy < 0 || qy >= ny)) continue;
-                    if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
-                    const bool own = SAME && dz == 0 && dy == 0;
-                    const int q = qz * ny + qy;
-                    float offmin = 0.0f, offmax = 0.0f;
-                    // split pencils: a neighbour two pencils away is at least one pencil width off in that axis, so its x window shrinks
-                    // (orthorhombic periodic cells only; the widths of the other cell kinds are not the box edge over the count)
-                    float rpad = p.rpad;
-                    if (CELL == 0 && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {
-                        const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
-                        const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
-                        const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
-                        if (rr <= 0.0f) continue;
-                        rpad = sqrtf(rr) * 1.0001f;
-                    }
-                    if (TRI) {
-                        // range of xy*s_y + xz*s_z over the cross-section of pencil q (+ head room for the roundings)
-                        const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
-                        const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
-                        offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
-                        offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
-                    }
-                    for (int kx = -1; kx <= 1; ++kx) {
-                        if (open_x && kx != 0) continue;
-                        float sx = (float)kx * Lx;
-                        if (TRI) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy, sz);
-                        const float lo = (xlo - rpad) - sx - offmax - orgx - pad_open;
-                        const float hi = (xhi + rpad) - sx - offmin - orgx + pad_open;
-                        if (hi < 0.0f || lo >= Lx) continue;
-                        const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
-                        const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
-                        unsigned ja = cst[q * nxf + ca];
-                        const unsigned jb = cst[q * nxf + cb + 1];
-                        if (own) {
+                if (SAME && dz == 0 && dy < 0) ok = false;
+                if (nsplit > 1 && ((dz + p.rz) * ncy + (dy + p.ry)) % nsplit != part) ok = false;
+                int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+                if (open_y && (qy < 0 || qy >= ny)) ok = false;
+                if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
+                const int q = qz * ny + qy;
+                float offmin = 0.0f, offmax = 0.0f;
+                // split pencils: a neighbour two pencils away is at least one pencil width off in that axis, so its x window shrinks
+                // (orthorhombic periodic cells only; the widths of the other cell kinds are not the box edge over the count)
+                float rpad = p.rpad;
+                if (CELL == 0 && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {
+                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
+                    const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                    const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                    if (rr <= 0.0f) ok = false;
+                    rpad = sqrtf(rr) * 1.0001f;
+                }
+                if (TRI) {
+                    // range of xy*s_y + xz*s_z over the cross-section of pencil q (+ head room for the roundings)
+                    const float fny = vmd_uniform((float)ny), fnz = vmd_uniform((float)nz);      // (wave-uniform: not held in a VGPR across the segments)
+                    const float y0 = txy * ((float)qy / fny), y1 = txy * ((float)(qy + 1) / fny);
+                    const float z0 = txz * ((float)qz / fnz), z1 = txz * ((float)(qz + 1) / fnz);
+                    offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                    offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+                }
+                int ia[3], ib[3];
+                bool in[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int kx = k - 1;
+                    float sx = (float)kx * Lx;
+                    if (TRI) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy, sz);      // sy, sz: the same for every kx
+                    const float lo = (xlo - rpad) - sx - offmax - orgx - pad_open;
+                    const float hi = (xhi + rpad) - sx - offmin - orgx + pad_open;
+                    in[k] = ok && !(open_x && kx != 0) && !(hi < 0.0f || lo >= Lx);
+                    const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
+                    const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
+                    ia[k] = in[k] ? q * nxf + ca : 0;               // (a lane without a window reads cst[0]: always there)
+                    ib[k] = in[k] ? q * nxf + cb + 1 : 0;
+                    if (TRI && lane < TABW) tab[VMD_TAB_SX(TABW) + k * TABW + lane] = (unsigned)__float_as_int(sx);
+                }
+                // all of the chunk's offsets travel together
+                const unsigned ja0 = cst[ia[0]], jb0 = cst[ib[0]], ja1 = cst[ia[1]], jb1 = cst[ib[1]], ja2 = cst[ia[2]], jb2 = cst[ib[2]];
+                if (lane < TABW) {
+                    tab[VMD_TAB_JA(TABW) + lane] = ja0; tab[VMD_TAB_JA(TABW) + TABW + lane] = ja1; tab[VMD_TAB_JA(TABW) + 2 * TABW + lane] = ja2;
+                    tab[VMD_TAB_JB(TABW) + lane] = jb0; tab[VMD_TAB_JB(TABW) + TABW + lane] = jb1; tab[VMD_TAB_JB(TABW) + 2 * TABW + lane] = jb2;
+                    tab[VMD_TAB_SY(TABW) + lane] = (unsigned)__float_as_int(sy); tab[VMD_TAB_SZ(TABW) + lane] = (unsigned)__float_as_int(sz);
+                }
+                // the entries that end in a segment (an own pencil's two parts are both empty when ja >= jb)
+                const unsigned long long m0 = VMD_BALLOT(in[0] && ja0 < jb0), m1 = VMD_BALLOT(in[1] && ja1 < jb1), m2 = VMD_BALLOT(in[2] && ja2 < jb2);
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+                for (int k = 0; k < 3; ++k) {
+                    unsigned long long m = k == 0 ? m0 : (k == 1 ? m1 : m2);
+                    const float sxk = vmd_uniform((float)(k - 1) * Lx);
+                    while (m) {
+                        const int e = __builtin_ctzll(m);
+                        m &= m - 1ull;
+                        unsigned ja = (unsigned)__builtin_amdgcn_readfirstlane(tab[VMD_TAB_JA(TABW) + k * TABW + e]);
+                        const unsigned jb = (unsigned)__builtin_amdgcn_readfirstlane(tab[VMD_TAB_JB(TABW) + k * TABW + e]);
+                        const float sx = TRI ? __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SX(TABW) + k * TABW + e])) : sxk;
+                        const float sy = __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SY(TABW) + e]));
+                        const float sz = __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SZ(TABW) + e]));
+                        if (SAME && c0 + e == p.ry) {               // the own pencil: combo (dz, dy) = (0, 0)
                             // unordered pairs once: j > i.  Inside the chunk the test is per lane, above it all lanes pass.
                             const unsigned cend = cbeg + VMD_WAVE;
                             const unsigned ma = ja > cbeg ? ja : cbeg;
@@ -1850,6 +1910,7 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                         }
                     }
                 }
+                __builtin_amdgcn_wave_barrier();                    // the table is read out before the next round overwrites it
             }
             // u32 LDS counters: every candidate column adds at most 64*INC; flush long before 2^32 (rare: straight to the
             // device accumulators with atomics)
