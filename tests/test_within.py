@@ -1,7 +1,8 @@
 """count(T and within(r, R)) on the emulator build and in the host-only entry points: known answers, exactness at the
 interval ends, both kernels against the numpy restatement (tests/within_ref.py), script-level parity, the cross-check against rdf(),
-call patterns, a pencil-bucket overflow, multi-rank merges, export, the opt-in front-end (C++ and Python twin), ABI validation and
-VIAMD's default script plus a hydration-number line through the shim.  Counts are integers: every comparison is `==`."""
+call patterns, a pencil-bucket overflow, the row offsets of a script with its temporal properties in an unusual order, multi-rank
+merges, export, the opt-in front-end (C++ and Python twin), ABI validation and VIAMD's default script plus a hydration-number line
+through the shim.  Counts are integers: every comparison is `==`."""
 import ctypes as C
 import os
 import subprocess
@@ -428,6 +429,68 @@ def overflow_case(lib, oracle, device=False):
 
 def test_a_bucket_overflow_repeats_the_batch(emu_lib, oracle):
     overflow_case(emu_lib, oracle)
+
+
+ORDER_SCRIPT = ["n1 = count(element('O') and within(3.5, residue(1:10)));", "d = distance(1, 50);",
+                "{lin,plan,iso} = shape_weights(all) in residue(1:100);", "n2 = count(element('O') and within(5.0, residue(1:10)));",
+                "rm = rmsd(all) in residue(1:8);", "a = angle(2,1,3) in residue(1:100);", "dm = distance_min(1:2, element('O')) in residue(2:5);"]
+ORDER_NAMES = ["n1", "d", "lin", "plan", "iso", "n2", "rm", "a", "dm"]
+ORDER_WIDTHS = [1, 1, 100, 100, 100, 1, 8, 100, 4]
+
+
+def row_order_case(lib, oracle, device=False):
+    """temporal properties of every kind in an order no other script has them in, the within counts (whose rows leave from launch_rdf)
+    first and in the middle, rows of 1, 4, 8 and 100 floats: every property's rows, bit for bit, are the rows it has as the only
+    statement of an evaluator of its own - whether the batch's host slot is filled and read in batches of 3, 3, 2 (completed behind
+    the next batch or at once), in one batch, or by pooled calls whose rows wait in ahead_values"""
+    import cases
+    n, box, F = 300, 20.0, 8
+    coords = cases.water_box(oracle, 11, n, box, F)
+    topo = synth.water_box_topology(n)
+    opt_ins = dict(within=True, angles=True, shape=True, rmsd=True)
+    want = {}
+    with options(lib, batch_frames=0):
+        for stmt in ORDER_SCRIPT:
+            ir, info = script.compile_script(stmt, topo, lib=lib, **opt_ins)
+            alone = evaluate(lib, ir, coords, box, device=device)
+            for name in ir.property_names():
+                want[name] = rows(alone, name)
+                if info[name]["kind"] == "within_count":
+                    i = info[name]
+                    assert np.array_equal(want[name][:, 0], W.counts(coords, box, i["target"], i["ref"], i["rmin"], i["rmax"], slab=True)), name
+    assert list(want) == ORDER_NAMES and [want[nm].shape for nm in ORDER_NAMES] == [(F, w) for w in ORDER_WIDTHS]
+    assert not np.array_equal(want["n1"], want["n2"]) and len({want[nm].tobytes() for nm in ("lin", "plan", "iso", "a")}) == 4
+    ir = script.compile_script("\n".join(ORDER_SCRIPT), topo, lib=lib, **opt_ins)[0]
+    assert ir.property_names() == ORDER_NAMES
+    settings = {"batches of 3, deferred": (dict(batch_frames=3, defer_sync=1), {}), "batches of 3": (dict(batch_frames=3, defer_sync=0), {}),
+                "one batch": (dict(batch_frames=0), {}), "pooled, read ahead": (dict(readahead=1), dict(pooled=(8, 1)))}
+    for what, (opts, kw) in settings.items():
+        lib.vmd_profile_reset(); lib.vmd_profile_enable(True)
+        try:
+            with options(lib, **opts):
+                ev = evaluate(lib, ir, coords, box, device=device, **kw)
+        finally:
+            lib.vmd_profile_enable(False)
+        if "batch_frames" in opts:
+            assert launches(lib, "batches") == (3 if opts["batch_frames"] else 1), what
+        for name in ORDER_NAMES:
+            assert bits_equal(rows(ev, name), want[name]), (what, name)
+    # whether a pool's calls meet in a read-ahead region is up to its threads; one caller walking frame by frame with the deferred settle
+    # always does: blocks of 3, 3 and 2 frames evaluated ahead in one batch, their rows in ahead_values until the blocks are committed
+    cell = V.make_unitcell(box)
+    sysm, traj = V.MolSystem(n, unitcell=cell), cases.make_traj(lib, coords, cell, device)
+    ev = V.ScriptEval(F, ir); ev.set_block_frames(3); ev.set_deferred_settle(1)
+    for f in range(F):
+        assert ev.frame_range(sysm, traj, f, f + 1)
+    ev.wait_settled()
+    st = ev.readahead_stats()
+    assert ev.frame_mask().all() and st["regions"] >= 1 and st["region_frames"] == F and st["committed_blocks"] == 3, st
+    for name in ORDER_NAMES:
+        assert bits_equal(rows(ev, name), want[name]), ("evaluated ahead", name)
+
+
+def test_rows_of_temporal_properties_in_an_unusual_order(emu_lib, oracle):
+    row_order_case(emu_lib, oracle)
 
 
 # ---- 7. multi-rank, export -----------------------------------------------------------------------------------------------------------------

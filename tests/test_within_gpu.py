@@ -47,6 +47,10 @@ def test_a_bucket_overflow_repeats_the_batch(gpu_lib, oracle):
     TW.overflow_case(gpu_lib, oracle, device=True)
 
 
+def test_rows_of_temporal_properties_in_an_unusual_order(gpu_lib, oracle):
+    TW.row_order_case(gpu_lib, oracle, device=True)
+
+
 FULL_SCRIPT = ("a = count(element('O') and within(3.5, atom(1:300)));\n"
                "b = count(element('O') and within(0.5:2.0, element('O')));\n"
                "c = count(element('O') and within(1.2:1.8, element('H')));")

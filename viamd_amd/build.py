@@ -10,7 +10,9 @@ EVAL_SOURCES = ["vmd_eval_runtime.cpp",      # errors, options, logging, profili
                 "vmd_eval_ir.cpp",           # property descriptors (vmd_ir_*)
                 "vmd_eval_core.cpp",         # create / free / clear_data / interrupt, host views, accessors, sdf payload
                 "vmd_eval_stage.cpp",        # static uploads, trajectory staging (device views, pinned batches, raw XTC frames + device decode)
-                "vmd_eval_batch.cpp",        # grids, cell builds, batch planning, block reuse, process_range
+                "vmd_eval_batch.cpp",        # cell builds, batch planning, block reuse, view refresh, the combining round
+                "vmd_eval_range.cpp",        # process_range: reference poses, the plan, the batch loop, completion of a batch
+                "vmd_eval_launch.cpp",       # what a batch launches: launch_rdf and one launch function per property kind
                 "vmd_eval_calls.cpp",        # how calls arrive: combining queue, read-ahead, deferred settle, vmd_eval_frame_range
                 "vmd_eval_traj.cpp",         # trajectory kinds in HBM / pinned memory, decoder checkpoints, mapped-file windows
                 "vmd_eval_post.cpp"]         # VIAMD's consumer-side histogram post-processing

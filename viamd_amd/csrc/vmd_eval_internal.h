@@ -4,10 +4,11 @@
 // Mirrors the md_script_eval_* lifecycle VIAMD drives (/root/reference/src/main.cpp:951-1039): create -> clear_data -> frame_range from
 // pool threads -> property_data / frame_mask polled by the GUI thread.  All arithmetic happens in the HIP kernels of vmd_kernels.hip;
 // the host code only batches frames, owns the device buffers and keeps the md_script_property_data_t views up to date.  There is no
-// CPU compute path.  Round 6: the one translation unit this used to be (4 300 lines) is eight files by concern -
+// CPU compute path.  Round 6: the one translation unit this used to be (4 300 lines) is ten files by concern -
 //     vmd_eval_runtime.cpp  errors, options, profiling, resource pool        vmd_eval_ir.cpp     property descriptors
 //     vmd_eval_core.cpp     the eval object, host views, accessors           vmd_eval_stage.cpp  static uploads, trajectory staging
-//     vmd_eval_batch.cpp    grids, cell builds, batches, process_range       vmd_eval_calls.cpp  queue, read-ahead, deferred settle
+//     vmd_eval_batch.cpp    cell builds, batch planning, block reuse         vmd_eval_calls.cpp  queue, read-ahead, deferred settle
+//     vmd_eval_range.cpp    process_range: plan, batch loop, completion      vmd_eval_launch.cpp launch_rdf, one launch per property kind
 //     vmd_eval_traj.cpp     trajectory kinds, checkpoint / mapping caches    vmd_eval_post.cpp   histogram post-processing
 // - and this header holds every struct they share, in the order the single file declared them, with each function's prototype where
 // its definition used to stand.  Nothing here is part of the ABI.
@@ -915,6 +916,89 @@ bool reuse_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t beg, siz
 bool view_sharded(const vmd_device_view_t& view);
 
 bool view_holds(bool have_view, const vmd_device_view_t& view, size_t frame);
+
+// ---- one call of process_range_locked: vmd_eval_range.cpp plans and runs it, vmd_eval_launch.cpp holds what a batch launches
+// frames [off, off + nb) of a batch: the whole batch, or one of the frame blocks a batch of blocks is made of (blk >= 0)
+struct Sub { size_t off, nb; long blk; };
+
+struct BatchCtx {
+    Batch bt{0, 0, -1, 0};
+    Stage* src = nullptr;
+    size_t f0 = 0, nb = 0;
+    uint32_t pbc = 0;
+    std::vector<Sub> subs;
+    bool two_streams = false;
+    int slot = 0;
+    bool active = false;        // queued, not completed
+    bool poisoned = false;      // queued behind a batch that overflowed: its RDF part saw the flag and did nothing
+    bool snapshot = false;      // h_snap[slot] holds the RDF counts behind this batch's commits (+ w_snap: the weights)
+    std::vector<size_t> toff;   // [index into props] where a temporal property's rows start in h_temporal_slot[slot] (queue_batch)
+    std::vector<std::vector<uint32_t>> shell_pop;    // rdf over shells: [shell][frame of the batch] populations
+};
+
+// one side of a pair pass: a cell-sorted selection or the hit copy of a shell, a list the pair kernel takes as it is
+struct PairSide { const float* sorted; const uint32_t* cell_start; int n, npad; };
+
+// a scratch row of launch_rdf and the accumulator it is added to behind the overflow flag
+struct RdfCommit { uint64_t* dst; const uint64_t* src; uint64_t mult; };
+
+struct RangeRun {
+    vmd_script_eval_t* e = nullptr;
+    vmd_trajectory_i* traj = nullptr;
+    size_t num_atoms = 0;
+    uint32_t frame_beg = 0, frame_end = 0;
+    bool views = false, spec = false;
+    vmd_device_view_t view;
+    bool have_view = false;
+    const vmd_device_view_t* vw = nullptr;
+    // the plan (plan_range)
+    bool raw_ring = false, f32_ring = false, have_map = false, device_decode = false, cold_walk = false;
+    bool decode_blocks = false;         // the pair grid makes room for the device decoder (rdf_blocks_decode) while this range runs
+    size_t raw_ahead = 3, stage_ahead = 1;
+    std::vector<Batch> batches;
+    bool defer = false;
+    size_t rdf_counts = 0;
+    BatchCtx ctx[2];
+    // launch_rdf, from its first launch to its commits
+    bool forked = false;                // pair_stream holds launches the eval's stream has not waited for
+    size_t row = 0;                     // next scratch row of d_pass
+    std::vector<RdfCommit> commits;
+
+    RawSlot* slot_of(size_t bi) const { return raw_ring ? &e->raw_slots[bi % vmd_script_eval_t::kRawSlots] : nullptr; }
+    Stage& stage_of(size_t bi) const { return e->stages[bi % (stage_ahead + 1)]; }
+    uint64_t* acc_of(PropState* p, const Sub& sb) const {
+        return (sb.blk >= 0 && p->ncounts) ? p->d_blocks.p + (size_t)sb.blk * p->ncounts : p->d_counts.p;
+    }
+    // vmd_eval_range.cpp
+    bool prepare_reference_poses();
+    void plan_range(const std::vector<std::pair<size_t, size_t>>& segments);
+    void rdf_weights(BatchCtx& c, PropState* p);
+    bool complete_batch(BatchCtx& c, BatchCtx* later);
+    bool queue_batch(size_t bi);
+    // vmd_eval_launch.cpp
+    int grid_for(BatchCtx& c, size_t lanes, float r, vmd_grid_t* grid, const float** d_gb);
+    bool build_pair(BatchCtx& c, Selection* a, Selection* b, const float* d_gb, const vmd_grid_t& grid);
+    bool pair_fork();
+    bool pair_join();
+    template <class OnRow>
+    bool launch_pair_pass(BatchCtx& c, const PairSide (&side)[2], bool same, const RdfGroup& g, const float* d_gb, const vmd_grid_t& grid,
+            OnRow on_row);
+    bool shell_pops(BatchCtx& c, size_t hi);
+    bool shell_pencil(BatchCtx& c, size_t hi, const float* d_gb, const vmd_grid_t& grid);
+    bool shell_brute(BatchCtx& c, size_t hi);
+    bool shell_rdf_brute(BatchCtx& c, const RdfGroup& g, PropState* p);
+    bool launch_rdf_groups(BatchCtx& c);
+    bool launch_within_counts(BatchCtx& c);
+    bool launch_shell_masks(BatchCtx& c);
+    bool launch_shell_sdfs(BatchCtx& c);
+    bool launch_rdf(BatchCtx& c);
+    bool launch_sdf(BatchCtx& c, PropState* p, const Shell* mask);
+    bool launch_shape(BatchCtx& c, size_t pi);
+    bool launch_rmsd(BatchCtx& c, PropState* p);
+    bool launch_geometry(BatchCtx& c, PropState* p);
+    bool launch_distance(BatchCtx& c, PropState* p);
+    bool launch_property(BatchCtx& c, size_t pi);
+};
 
 bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame_beg, uint32_t frame_end,
         bool views, bool spec);

@@ -1,0 +1,457 @@
+// viamd_amd/csrc/vmd_eval_launch.cpp - what one batch of a range run puts on the device: launch_rdf (the cell builds and everything
+// behind them that a bucket overflow voids and repeats - pair passes, shells, within counts, shell masks and the sdfs under them, the
+// commits) and one launch function per kind of the remaining properties (launch_property).  Who calls them, and when: vmd_eval_range.cpp.
+#include "vmd_eval_internal.h"
+
+// The grid of this batch for radius r, and the boxes it is cut from: fully periodic cells use the frame boxes; open axes (non-periodic
+// systems, slabs) span the batch's bounding box.  `lanes` is the size of the sparsest list a walk over this grid puts in its lanes
+// (the denser of the two sides of every pass); its density against the first frame's cell decides the pencil split, so that equal
+// radii over equal selections meet on equal grids whoever asks.  -> 1 a grid, 0 none (all pairs), -1 an error
+int RangeRun::grid_for(BatchCtx& c, size_t lanes, float r, vmd_grid_t* grid, const float** d_gb) {
+    const bool open_axes = (c.pbc & 8u) == 0 && (c.pbc & VMD_UNITCELL_PBC_ALL) != VMD_UNITCELL_PBC_ALL;
+    if (open_axes && !g_opt.force_brute && !prepare_open_boxes(e, *c.src, c.nb, c.pbc, num_atoms)) return -1;
+    const bool gboxes = open_axes && c.src->gboxes_ready;
+    const std::vector<float>& gb = gboxes ? c.src->h_gboxes : c.src->h_boxes;
+    *d_gb = gboxes ? c.src->d_gboxes.p : c.src->d_boxes.p;
+    bool dense_lanes = !open_axes;
+    if (dense_lanes) {
+        const float* q = gb.data();
+        const double vol = (double)q[0] * q[1] * q[2];
+        dense_lanes = vol > 0.0 && (double)lanes / vol >= 0.08;
+    }
+    return choose_grid(gb, c.pbc, c.nb, r, grid, dense_lanes) ? 1 : 0;
+}
+
+// both selections of a pass sorted on `grid`, once when they are the same one (build_selection keeps what this batch already sorted on
+// the same grid and re-sorts when the grid differs)
+bool RangeRun::build_pair(BatchCtx& c, Selection* a, Selection* b, const float* d_gb, const vmd_grid_t& grid) {
+    return build_selection(e, a, *c.src, d_gb, c.pbc, c.nb, grid) && (b == a || build_selection(e, b, *c.src, d_gb, c.pbc, c.nb, grid));
+}
+
+// pair_stream takes up behind what the eval's stream holds so far ...
+bool RangeRun::pair_fork() {
+    HIP_OK(hipEventRecord(e->pair_fork, e->stream));
+    HIP_OK(hipStreamWaitEvent(e->pair_stream, e->pair_fork, 0));
+    forked = true;
+    return true;
+}
+
+// ... and the eval's stream waits for it before anything overwrites what its launches read, or reads what they wrote
+bool RangeRun::pair_join() {
+    if (!forked) return true;
+    HIP_OK(hipEventRecord(e->pair_join, e->pair_stream));
+    HIP_OK(hipStreamWaitEvent(e->stream, e->pair_join, 0));
+    forked = false;
+    return true;
+}
+
+// One pair pass over the batch: one launch of the pair kernel per sub, each into its own scratch row.  The blocks' launches alternate
+// between the eval's stream and pair_stream (own partial rows) when the batch asks for it; on_row(sub, scratch row, stream) follows
+// every launch on its stream - what else the row needs, and who it is committed to.
+template <class OnRow>
+bool RangeRun::launch_pair_pass(BatchCtx& c, const PairSide (&side)[2], bool same, const RdfGroup& g, const float* d_gb,
+        const vmd_grid_t& grid, OnRow on_row) {
+    if (c.two_streams && !pair_fork()) return false;
+    const PairSide &a = side[0], &b = side[1];
+    size_t si = 0;
+    for (auto& su : c.subs) {
+        uint64_t* dst = e->d_pass.p + (row++) * VMD_RDF_NUM_BINS;
+        const bool second = c.two_streams && (si++ & 1);
+        hipStream_t ks = second ? e->pair_stream : e->stream;
+        if (!second) e->prof.begin("rdf_pencil", ks);
+        KRN_OK(vmd_hip_rdf_pencil(ks, a.sorted + su.off * 3 * (size_t)a.npad, a.cell_start + su.off * (size_t)(grid.ncell + 1), a.n,
+                a.npad, b.sorted + su.off * 3 * (size_t)b.npad, b.cell_start + su.off * (size_t)(grid.ncell + 1), b.n, b.npad,
+                d_gb + 9 * su.off, (int)su.nb, grid, g.rmin, g.rmax, VMD_RDF_NUM_BINS, same ? 1 : 0, g_opt.rdf_variant, c.pbc,
+                second ? e->d_partial2.p : e->d_partial.p, dst, e->d_overflow.p));
+        if (!second) e->prof.end(ks);
+        if (!on_row(su, dst, ks)) return false;
+    }
+    return true;
+}
+
+// ---- shells as rdf arguments.  One walk + one compaction per shell, batch and grid, whichever properties use it; the
+// per-frame populations travel to the host from here, behind the overflow flag like everything else of launch_rdf.
+bool RangeRun::shell_pops(BatchCtx& c, size_t hi) {
+    Shell* h = e->shells[hi].get();
+    c.shell_pop[hi].assign(c.nb, 0);
+    if (h->sel_t >= 0)
+        HIP_OK(hipMemcpyAsync(c.shell_pop[hi].data(), h->count.p, c.nb * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    return true;
+}
+
+// the hit copy of shell hi on `grid`: (sorted, cell_start) of the members, a selection the pair kernel takes as it is
+bool RangeRun::shell_pencil(BatchCtx& c, size_t hi, const float* d_gb, const vmd_grid_t& grid) {
+    Shell* h = e->shells[hi].get();
+    if (h->sel_t < 0) { h->built = 1; return shell_pops(c, hi); }
+    if (h->built == 1 && h->built_grid.nxf == grid.nxf && h->built_grid.ny == grid.ny && h->built_grid.nz == grid.nz) return true;
+    Selection* st = e->sels[h->sel_t].get();
+    Selection* sr = e->sels[h->sel_r].get();
+    if (!build_pair(c, st, sr, d_gb, grid)) return false;
+    const size_t npen = (size_t)grid.ny * grid.nz;
+    const size_t rows = c.nb * 3 * (size_t)st->nsel_pad + 64;           // the parent's rows, slack included
+    if (rows > h->sorted.cap) {
+        if (!h->sorted.ensure(rows)) return false;
+        HIP_OK(hipMemsetAsync(h->sorted.p, 0, rows * sizeof(float), e->stream));     // what lies beyond a population stays finite
+    }
+    if (!h->flags.ensure(c.nb * (size_t)st->nsel_pad) || !h->count.ensure(c.nb) || !h->pen_hits.ensure(c.nb * (npen + 1)) ||
+        !h->pen_base.ensure(c.nb * (npen + 1)) || !h->cell_start.ensure(c.nb * (size_t)(grid.ncell + 1))) return false;
+    e->prof.begin("shell_flags", e->stream);
+    KRN_OK(vmd_hip_within_pencil_flags(e->stream, sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, st->sorted.p,
+            st->cell_start.p, (int)st->idx.size(), st->nsel_pad, d_gb, (int)c.nb, grid, h->rmin, h->rmax,
+            e->spec.within_closed ? 1 : 0, c.pbc, h->count.p, e->d_overflow.p, h->flags.p, h->pen_hits.p));
+    e->prof.end(e->stream);
+    e->prof.begin("shell_compact", e->stream);
+    KRN_OK(vmd_hip_shell_compact(e->stream, h->flags.p, h->pen_hits.p, h->pen_base.p, st->sorted.p, st->cell_start.p, st->nsel_pad,
+            (int)c.nb, grid, h->sorted.p, h->cell_start.p, e->d_overflow.p));
+    e->prof.end(e->stream);
+    h->built = 1; h->built_grid = grid;
+    return shell_pops(c, hi);
+}
+
+// no grid: the members as one byte per list entry, from all pairs of the raw frame (always wrapped positions)
+bool RangeRun::shell_brute(BatchCtx& c, size_t hi) {
+    Shell* h = e->shells[hi].get();
+    if (h->built == 2) return true;
+    if (h->sel_t >= 0) {
+        Selection* st = e->sels[h->sel_t].get();
+        Selection* sr = e->sels[h->sel_r].get();
+        if (!h->flags.ensure(c.nb * st->idx.size()) || !h->count.ensure(c.nb)) return false;
+        e->prof.begin("shell_brute", e->stream);
+        KRN_OK(vmd_hip_within_brute_flags(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), h->rmin, h->rmax,
+                e->spec.within_closed ? 1 : 0, h->count.p, h->flags.p));
+        e->prof.end(e->stream);
+    }
+    h->built = 2;
+    return shell_pops(c, hi);
+}
+
+// a shell property by all pairs: list-order masks on the shell sides.  choose_grid failed for the group, or this is spec_rdf_raw
+bool RangeRun::shell_rdf_brute(BatchCtx& c, const RdfGroup& g, PropState* p) {
+    for (int k = 0; k < 2; ++k) if (p->shell_of[k] >= 0 && !shell_brute(c, (size_t)p->shell_of[k])) return false;
+    for (auto& su : c.subs) {
+        uint64_t* dst = e->d_pass.p + (row++) * VMD_RDF_NUM_BINS;
+        if (p->sel_a < 0 || p->sel_b < 0) continue;                      // T minus R is empty: no member in any frame
+        Selection* sa = e->sels[p->sel_a].get();
+        Selection* sb = e->sels[p->sel_b].get();
+        const uint8_t* ma = p->shell_of[0] >= 0 ? e->shells[p->shell_of[0]]->flags.p + su.off * sa->idx.size() : nullptr;
+        const uint8_t* mb = p->shell_of[1] >= 0 ? e->shells[p->shell_of[1]]->flags.p + su.off * sb->idx.size() : nullptr;
+        e->prof.begin("rdf_brute", e->stream);
+        KRN_OK(vmd_hip_rdf_brute_masked(e->stream, c.src->base + su.off * c.src->frame_stride, c.src->frame_stride,
+                c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, sa->d_idx.p, (int)sa->idx.size(), ma,
+                sb->d_idx.p, (int)sb->idx.size(), mb, g.rmin, g.rmax, VMD_RDF_NUM_BINS, dst));
+        e->prof.end(e->stream);
+        commits.push_back({acc_of(p, su), dst, 1});
+    }
+    return true;
+}
+
+// ---- RDF: one pair pass per (group, pass), then the group's rdfs over shells
+bool RangeRun::launch_rdf_groups(BatchCtx& c) {
+    for (auto& h : e->shells) h->built = 0;
+    c.shell_pop.resize(e->shells.size());
+    for (auto& g : e->rdf_groups) {
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        // the sparsest selection any pass of this group puts in the lanes (the denser of its two); shell properties by the parent
+        // lists: what the cell builds sort
+        size_t lanes = (g.passes.empty() && g.shell_props.empty()) ? 0 : SIZE_MAX;
+        for (auto& ps : g.passes) lanes = std::min(lanes, std::max(e->sels[ps.sel_a]->idx.size(), e->sels[ps.sel_b]->idx.size()));
+        for (int pi : g.shell_props) {
+            const PropState* p = e->props[pi].get();
+            lanes = std::min(lanes, std::max(p->sel_a >= 0 ? e->sels[p->sel_a]->idx.size() : 0,
+                                             p->sel_b >= 0 ? e->sels[p->sel_b]->idx.size() : 0));
+        }
+        // (grid_r: the larger of the pair cutoff and the shell radii of the group's members - walk and pair kernel accept a wider edge)
+        const int have_grid = grid_for(c, lanes, g.grid_r, &grid, &d_gb);
+        if (have_grid < 0) return false;
+        if (e->spec.rdf_raw || !have_grid) {
+            // no grid for this batch (cutoff >= half the cell width, ...): all pairs, per property
+            for (int pi : g.props) {
+                PropState* p = e->props[pi].get();
+                Selection* sa = e->sels[p->sel_a].get();
+                Selection* sb = e->sels[p->sel_b].get();
+                for (auto& su : c.subs) {
+                    uint64_t* dst = e->d_pass.p + (row++) * VMD_RDF_NUM_BINS;
+                    e->prof.begin("rdf_brute", e->stream);
+                    KRN_OK(vmd_hip_rdf_brute(e->stream, c.src->base + su.off * c.src->frame_stride, c.src->frame_stride,
+                            c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, sa->d_idx.p, (int)sa->idx.size(),
+                            sb->d_idx.p, (int)sb->idx.size(), g.rmin, g.rmax, VMD_RDF_NUM_BINS, dst));
+                    e->prof.end(e->stream);
+                    commits.push_back({acc_of(p, su), dst, 1});
+                }
+            }
+            for (int pi : g.shell_props) if (!shell_rdf_brute(c, g, e->props[pi].get())) return false;
+            continue;
+        }
+        if (!e->d_partial.ensure(vmd_hip_rdf_partial_words())) return false;
+        if (c.two_streams && !e->d_partial2.ensure(vmd_hip_rdf_partial_words())) return false;
+        for (auto& ps : g.passes) {
+            Selection* sa = e->sels[ps.sel_a].get();
+            Selection* sb = e->sels[ps.sel_b].get();
+            // passes with the same cutoff share the sorted copies; the second stream still reads the sorted copies of the previous pass
+            if (!pair_join() || !build_pair(c, sa, sb, d_gb, grid)) return false;
+            // the pair set is symmetric in (ref, target): put the denser selection in the lanes - 64 of its atoms span a
+            // shorter stretch of the pencil, so the x window of every segment carries less padding
+            if (sb->idx.size() > sa->idx.size()) std::swap(sa, sb);
+            const PairSide side[2] = {{sa->sorted.p, sa->cell_start.p, (int)sa->idx.size(), sa->nsel_pad},
+                                      {sb->sorted.p, sb->cell_start.p, (int)sb->idx.size(), sb->nsel_pad}};
+            const bool bump = e->spec.rdf_closed && ps.same && g.rmin <= 0.0f && 0.0f <= g.rmax;
+            if (!launch_pair_pass(c, side, ps.same, g, d_gb, grid, [&](const Sub& su, uint64_t* dst, hipStream_t ks) -> bool {
+                if (bump) {
+                    // closed interval: d = 0 is a hit, but a same-set pass walks the half shell (j > i, every hit twice) and never
+                    // meets the pairs (i, i) - one per list entry and frame, all in the bin of d = 0 (SPEC S4 binning of 0)
+                    int bin0 = (int)(((0.0f - g.rmin) * (1.0f / (g.rmax - g.rmin))) * (float)VMD_RDF_NUM_BINS);
+                    bin0 = std::min(std::max(bin0, 0), VMD_RDF_NUM_BINS - 1);
+                    KRN_OK(vmd_hip_bump_u64(ks, dst + bin0, (uint64_t)su.nb * (uint64_t)sa->idx.size()));
+                }
+                for (auto& tg : ps.targets) commits.push_back({acc_of(e->props[tg.first].get(), su), dst, tg.second});
+                return true;
+            })) return false;
+        }
+        // ---- the group's rdfs over shells: the same pair kernel over the hit copies.  Never the half-shell pass: a shell pass counts
+        // ordered pairs, (i, i) included at d = 0 where the sides overlap (dropped by the open interval, a hit under spec_rdf_closed)
+        for (int pi : g.shell_props) {
+            PropState* p = e->props[pi].get();
+            // the second stream may still read a hit copy or sorted rows the builds below overwrite
+            if (!pair_join()) return false;
+            for (int k = 0; k < 2; ++k) if (p->shell_of[k] >= 0 && !shell_pencil(c, (size_t)p->shell_of[k], d_gb, grid)) return false;
+            if (p->sel_a < 0 || p->sel_b < 0) { row += c.subs.size(); continue; }     // T minus R is empty
+            PairSide side[2];
+            for (int k = 0; k < 2; ++k) {
+                Selection* sl = e->sels[k ? p->sel_b : p->sel_a].get();
+                if (p->shell_of[k] < 0 && !build_pair(c, sl, sl, d_gb, grid)) return false;
+                const Shell* h = p->shell_of[k] >= 0 ? e->shells[p->shell_of[k]].get() : nullptr;
+                // sizes feed launch heuristics only: the parents'
+                side[k] = {h ? h->sorted.p : sl->sorted.p, h ? h->cell_start.p : sl->cell_start.p, (int)sl->idx.size(), sl->nsel_pad};
+            }
+            if (!launch_pair_pass(c, side, false, g, d_gb, grid, [&](const Sub& su, uint64_t* dst, hipStream_t) -> bool {
+                commits.push_back({acc_of(p, su), dst, 1});
+                return true;
+            })) return false;
+        }
+    }
+    return pair_join();
+}
+
+// ---- within counts: the same grids and cell-sorted copies (a selection an RDF pass of this batch sorted on the same
+// grid is not sorted again), an any-reduction per target atom instead of a histogram.  Part of launch_rdf because a bucket overflow
+// of ITS cell builds repeats the batch like any other; the rows travel to the host from here for the same reason.  Always wrapped
+// positions (spec_rdf_raw does not apply); no grid -> all pairs from the raw frame.
+bool RangeRun::launch_within_counts(BatchCtx& c) {
+    for (int pi : e->within_props) {
+        PropState* p = e->props[pi].get();
+        const Property& d = p->prop;
+        if (!p->d_out.ensure(c.nb) || !p->d_within_count.ensure(c.nb)) return false;
+        if (p->within_empty) {
+            HIP_OK(hipMemsetAsync(p->d_out.p, 0, c.nb * sizeof(float), e->stream));       // T minus R is empty: +0 in every frame
+        } else {
+            Selection* st = e->sels[p->sel_a].get();
+            Selection* sr = e->sels[p->sel_b].get();
+            vmd_grid_t grid;
+            const float* d_gb = nullptr;
+            const int have_grid = grid_for(c, std::max(st->idx.size(), sr->idx.size()), d.rmax, &grid, &d_gb);
+            if (have_grid < 0) return false;
+            if (have_grid) {
+                if (!build_pair(c, st, sr, d_gb, grid)) return false;
+                e->prof.begin("within_pencil", e->stream);
+                KRN_OK(vmd_hip_within_pencil(e->stream, sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, st->sorted.p,
+                        st->cell_start.p, (int)st->idx.size(), st->nsel_pad, d_gb, (int)c.nb, grid, d.rmin, d.rmax,
+                        e->spec.within_closed ? 1 : 0, c.pbc, p->d_within_count.p, e->d_overflow.p));
+                e->prof.end(e->stream);
+                KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, e->d_overflow.p));
+            } else {
+                e->prof.begin("within_brute", e->stream);
+                KRN_OK(vmd_hip_within_brute(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                        (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), d.rmin, d.rmax,
+                        e->spec.within_closed ? 1 : 0, p->d_within_count.p));
+                e->prof.end(e->stream);
+                KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, nullptr));
+            }
+        }
+        HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * sizeof(float), hipMemcpyDeviceToHost,
+                e->stream));
+    }
+    return true;
+}
+
+// ---- sdfs over a shell target.  First every shell's mask in atom order, then, behind the LAST cell build of the batch,
+// alignment and masked scatter.  RULE for the mask: all pairs from the raw frame when R has fewer than shell_brute_below atoms (480:
+// the walk and the build of R cost the same whatever |R| is, all pairs is linear in it, and DESIGN 1.8 measures where they cross) or
+// when no grid exists for the shell radius; otherwise the walk over the cell-sorted copy of R on the grid a within count of the same
+// radius and lists would get.
+bool RangeRun::launch_shell_masks(BatchCtx& c) {
+    for (auto& h : e->shells) h->abuilt = 0;
+    for (int pi : e->shell_sdf_props) {
+        PropState* p = e->props[pi].get();
+        Shell* h = e->shells[p->shell_of[1]].get();
+        if (h->abuilt || h->sel_t < 0) continue;
+        Selection* st = e->sels[h->sel_t].get();
+        Selection* sr = e->sels[h->sel_r].get();
+        const size_t stride = c.src->row_stride;
+        if (h->amask_stride != stride || c.nb * stride > h->amask.cap) {
+            if (!h->amask.ensure(c.nb * stride)) return false;
+            HIP_OK(hipMemsetAsync(h->amask.p, 0, h->amask.cap, e->stream));        // atoms outside T' read 0 for ever
+            h->amask_stride = stride;
+        }
+        if (!h->acount.ensure(c.nb)) return false;
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        const int below = g_opt.shell_brute_below.load();
+        const int have_grid = (int)sr->idx.size() < below ? 0
+                : grid_for(c, std::max(st->idx.size(), sr->idx.size()), h->rmax, &grid, &d_gb);
+        if (have_grid < 0) return false;
+        if (have_grid) {
+            if (!build_pair(c, sr, sr, d_gb, grid)) return false;
+            e->prof.begin("shell_mask", e->stream);
+            KRN_OK(vmd_hip_within_atoms(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, d_gb, c.pbc, (int)c.nb, st->d_idx.p,
+                    (int)st->idx.size(), sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, grid, h->rmin, h->rmax,
+                    e->spec.within_closed ? 1 : 0, h->acount.p, h->amask.p, stride, e->d_overflow.p));
+            e->prof.end(e->stream);
+            h->abuilt = 1;
+        } else {
+            e->prof.begin("shell_mask_brute", e->stream);
+            KRN_OK(vmd_hip_within_brute_atoms(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                    (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), h->rmin, h->rmax,
+                    e->spec.within_closed ? 1 : 0, h->acount.p, h->amask.p, stride));
+            e->prof.end(e->stream);
+            h->abuilt = 2;
+        }
+    }
+    return true;
+}
+
+// The scatter under a shell mask adds to the volume with atomics, so unlike a static sdf it has to be all or nothing: it sits here,
+// where the overflow flag is final, and tests it like the commits of launch_rdf; a repeated batch runs launch_rdf again and its
+// voxels are added exactly once.
+bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
+    for (int pi : e->shell_sdf_props) {
+        PropState* p = e->props[pi].get();
+        const Shell* h = e->shells[p->shell_of[1]].get();
+        if (h->sel_t < 0) continue;                   // T minus R is empty: no member in any frame, no voxel
+        if (!launch_sdf(c, p, h)) return false;
+    }
+    return true;
+}
+
+// ---- everything of a batch that a cell build takes part in; runs again for the batch when a bucket of one overflowed (complete_batch).
+// Every pass accumulates into its own scratch row and the rows are committed to the properties' accumulators by ONE
+// group of k_axpy_u64 launches at the very end, behind the overflow flag: by then every cell build of the batch has run,
+// so the flag is final and the batch's RDF part is all-or-nothing (a bucket of a LATER build may overflow after earlier
+// passes have long finished; nothing of them may stay behind when the batch is repeated).
+bool RangeRun::launch_rdf(BatchCtx& c) {
+    VMD_STAGE("batch: cell build + pair kernels");
+    vmd_hip_set_rdf_closed(e->spec.rdf_closed ? 1 : 0);
+    vmd_hip_set_rdf_raw(e->spec.rdf_raw ? 1 : 0);
+    size_t scratch_rows = 0;
+    for (auto& g : e->rdf_groups) scratch_rows += std::max(g.passes.size(), g.props.size()) + g.shell_props.size();
+    scratch_rows *= c.subs.size();
+    if (!e->d_pass.ensure(std::max<size_t>(scratch_rows, 1) * VMD_RDF_NUM_BINS)) return false;
+    if (scratch_rows) HIP_OK(hipMemsetAsync(e->d_pass.p, 0, scratch_rows * VMD_RDF_NUM_BINS * sizeof(uint64_t), e->stream));
+    commits.clear();
+    row = 0;
+    forked = false;
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_sdfs(c)) return false;
+    for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
+    HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    return true;
+}
+
+// ---- an sdf's alignment and scatter over the batch.  mask: the shell the targets are taken from (launch_shell_sdfs) -
+// its atom-order mask gates the scatter, which then tests the overflow flag; nullptr: a static sdf, gated by its own tag list
+bool RangeRun::launch_sdf(BatchCtx& c, PropState* p, const Shell* mask) {
+    const Property& d = p->prop;
+    if (!p->d_R32.ensure(c.nb * d.K * 9) || !p->d_c32.ensure(c.nb * d.K * 3) || !p->d_group.ensure(c.nb * 4)) return false;
+    e->prof.begin("sdf_align", e->stream);
+    if (p->have_tree && !p->d_tree_pos.ensure(c.nb * d.K * d.m * 3)) return false;
+    KRN_OK(vmd_hip_sdf_align(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+            (int)c.nb, p->d_structs.p, p->d_mass.p, (int)d.K, (int)d.m, p->d_ref_pose.p, p->d_R32.p, p->d_c32.p, nullptr,
+            p->d_group.p, p->have_tree ? p->d_tree_order.p : nullptr, p->have_tree ? p->d_tree_parent.p : nullptr, p->have_tree
+            ? p->d_tree_pos.p : nullptr));
+    e->prof.end(e->stream);
+    e->prof.begin("sdf_scatter", e->stream);
+    for (auto& su : c.subs) {
+        if (mask) KRN_OK(vmd_hip_sdf_scatter_masked(e->stream, c.src->base + su.off * c.src->frame_stride,
+                c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, p->d_structs.p, (int)d.K,
+                (int)d.m, p->d_R32.p + su.off * d.K * 9, p->d_c32.p + su.off * d.K * 3, p->d_tgt.p, (p->have_owner
+                && !e->spec.sdf_include_self) ? p->d_owner.p : nullptr, (int)d.b.size(), d.rmax, VMD_VOLUME_DIM, acc_of(p, su),
+                p->d_group.p + 4 * su.off, p->tgt_first, p->tgt_stride, (p->unowned || e->spec.sdf_include_self) ? 1 : 0,
+                mask->amask.p + su.off * mask->amask_stride, mask->amask_stride, e->d_overflow.p));
+        else KRN_OK(vmd_hip_sdf_scatter(e->stream, c.src->base + su.off * c.src->frame_stride,
+                c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, p->d_structs.p, (int)d.K,
+                (int)d.m, p->d_R32.p + su.off * d.K * 9, p->d_c32.p + su.off * d.K * 3, p->d_tgt.p, (p->have_owner
+                && !e->spec.sdf_include_self) ? p->d_owner.p : nullptr, (int)d.b.size(), d.rmax, VMD_VOLUME_DIM, acc_of(p, su),
+                p->d_group.p + 4 * su.off, (p->have_tag && p->tag_len == c.src->row_stride && !e->spec.sdf_include_self)
+                ? p->d_tag.p : nullptr, p->tgt_first, p->tgt_stride, (p->unowned || e->spec.sdf_include_self) ? 1 : 0));
+    }
+    e->prof.end(e->stream);
+    return true;
+}
+
+// shape_weights: the statement's three descriptors stand in a row; the first one computes all three [nb][P] blocks,
+// each of them copies its own (queue_batch)
+bool RangeRun::launch_shape(BatchCtx& c, size_t pi) {
+    PropState* p = e->props[pi].get();
+    if (p->prop.shape_comp != 0) return true;
+    if (pi + 2 >= e->props.size() || !e->props[pi + 1]->prop.is_shape() || !e->props[pi + 2]->prop.is_shape())
+        return vmd_fail("shape_weights property '%s' has lost its companions", p->prop.name.c_str());
+    PropState* p1 = e->props[pi + 1].get();
+    PropState* p2 = e->props[pi + 2].get();
+    if (!p1->d_out.ensure(c.nb * p->dim1) || !p2->d_out.ensure(c.nb * p->dim1)) return false;
+    if (!p->d_shape_partial.ensure(vmd_hip_shape_partial_doubles((int)c.nb, (int)p->dist_P, p->shape_max_set))) return false;
+    e->prof.begin("shape", e->stream);
+    KRN_OK(vmd_hip_shape(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+            (int)p->dist_P, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->shape_max_set, p->d_shape_partial.p, p->d_out.p,
+            p1->d_out.p, p2->d_out.p));
+    e->prof.end(e->stream);
+    return true;
+}
+
+// rmsd: the same [nb][P] block, the same copy; the batch knows which of its rows is frame 0
+bool RangeRun::launch_rmsd(BatchCtx& c, PropState* p) {
+    const size_t ws = vmd_hip_rmsd_workspace_bytes((int)c.nb, (int)p->dist_P, p->rmsd_max_set);
+    if (!p->d_rmsd_ws.ensure((ws + 7) / 8)) return false;
+    e->prof.begin("rmsd", e->stream);
+    KRN_OK(vmd_hip_rmsd(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+            (int)p->dist_P, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->rmsd_max_set, p->d_rmsd_pose.p, p->d_rmsd_const.p,
+            c.f0 == 0 ? 0 : -1, p->d_rmsd_ws.p, p->d_out.p));
+    e->prof.end(e->stream);
+    return true;
+}
+
+// angle / dihedral (DESIGN S6b): the same [nb][P] block, the same copy
+bool RangeRun::launch_geometry(BatchCtx& c, PropState* p) {
+    const int32_t* sets[4] = {p->d_a.p, p->d_b.p, p->d_c.p, p->d_d.p};
+    const float* ms[4] = {p->d_ma.p, p->d_mb.p, p->d_mc.p, p->d_md.p};
+    const int32_t* offs[4] = {p->d_aoff.p, p->d_boff.p, p->d_coff.p, p->d_doff.p};
+    e->prof.begin("geometry", e->stream);
+    KRN_OK(vmd_hip_geometry(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+            p->prop.nargs(), (int)p->dist_P, sets, ms, offs, e->spec.angle_radians ? 1 : 0, p->d_out.p));
+    e->prof.end(e->stream);
+    return true;
+}
+
+bool RangeRun::launch_distance(BatchCtx& c, PropState* p) {
+    e->prof.begin("distance", e->stream);
+    KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+            p->prop.dist_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
+            p->d_out.p));
+    e->prof.end(e->stream);
+    return true;
+}
+
+// what property pi adds to the batch's queue outside launch_rdf, by kind.  The rows of a temporal kind are left in d_out.
+bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
+    PropState* p = e->props[pi].get();
+    const Property& d = p->prop;
+    // SPEC S4 normalisation, fp64 on the host (needs only the box).  An rdf over shells needs the populations too: its weights
+    // are formed in complete_batch, when they have arrived
+    if (d.kind == PROP_RDF) { if (!d.is_shell_rdf()) rdf_weights(c, p); return true; }
+    // sdf over a shell, within count: launched by launch_rdf, behind the batch's cell builds
+    if (d.is_shell_sdf() || d.is_within()) return true;
+    if (d.kind == PROP_SDF) { VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr); }
+    if (!p->d_out.ensure(c.nb * p->dim1)) return false;
+    if (d.is_shape()) return launch_shape(c, pi);
+    if (d.is_rmsd()) return launch_rmsd(c, p);
+    return d.nargs() > 2 ? launch_geometry(c, p) : launch_distance(c, p);
+}
