@@ -837,29 +837,32 @@ def oracle_distance_population(O, coords, ocell, mass, a_sets, b_sets, kind):
     return np.concatenate(cols, axis=1)
 
 
-def check_distances(lib, O, coords, box, mass, specs, flags=L.PBC_ALL, device=False, ranges=None):
+def check_distances(lib, O, coords, box, mass, specs, flags=L.PBC_ALL, device=False, ranges=None, ir=None, oracle_mass=None):
     """specs: list of (name, a, b, kind) — or (name, a_sets, b_sets, kind, "pop") for a population of contexts.
-    Temporal rows must equal the oracle bit for bit (fp32)."""
+    Temporal rows must equal the oracle bit for bit (fp32).  ir: an IR that already holds the properties of `specs` (a compiled
+    script) instead of one built from them; oracle_mass: the weights the oracle takes when an option makes the library ignore `mass`."""
     ocell, vcell = cell_pair(O, box, flags)
     F, _, N = coords.shape
-    ir = V.ScriptIR(lib)
-    for sp in specs:
-        if len(sp) == 5:
-            ir.add_distance_population(sp[0], sp[1], sp[2], sp[3])
-        else:
-            ir.add_distance(*sp[:3], sp[3])
+    if ir is None:
+        ir = V.ScriptIR(lib)
+        for sp in specs:
+            if len(sp) == 5:
+                ir.add_distance_population(sp[0], sp[1], sp[2], sp[3])
+            else:
+                ir.add_distance(*sp[:3], sp[3])
     ev = V.ScriptEval(F, ir)
     traj = make_traj(lib, coords, vcell, device)
     sysm = V.MolSystem(N, mass=mass, unitcell=vcell)
     for beg, end in (ranges or [(0, F)]):
         assert ev.frame_range(sysm, traj, beg, end)
+    omass = mass if oracle_mass is None else oracle_mass
     for sp in specs:
         name, a, b, kind = sp[:4]
         pd = ev.property_data(name)
         if len(sp) == 5:
-            ref = oracle_distance_population(O, coords, ocell, mass, a, b, kind)
+            ref = oracle_distance_population(O, coords, ocell, omass, a, b, kind)
         else:
-            ref = oracle_distance(O, coords, ocell, mass, np.asarray(a, np.int32), np.asarray(b, np.int32), kind)
+            ref = oracle_distance(O, coords, ocell, omass, np.asarray(a, np.int32), np.asarray(b, np.int32), kind)
         assert pd.dim[0] == F and pd.dim[1] == ref.shape[1]
         got = pd.values.reshape(F, -1)
         np.testing.assert_array_equal(got, ref, err_msg=f"{name}: temporal values differ from the oracle")

@@ -4206,6 +4206,7 @@ extern "C" int vmd_hip_distance(void* stream, const float* xyz, size_t frame_str
                                 const int32_t* b, const float* mass_b, const int32_t* boff, float* out) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || P <= 0 || per <= 0) return 0;
+    if ((long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;     // B * P is an int below, and on grid.x
     vmd_dist_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, a, mass_a, aoff, b, mass_b, boff, P, per, out};
     switch (kind) {
     case 0: hipLaunchKernelGGL(k_distance_com, dim3((B * P + 63) / 64), dim3(64), 0, s, p); break;
