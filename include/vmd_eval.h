@@ -258,8 +258,23 @@ bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* 
  * vmd_ir_add_sdf, with its fingerprint.  Validation as vmd_ir_add_sdf plus, for the shell, that of vmd_ir_add_within_count. */
 bool vmd_ir_add_sdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
                           const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float cutoff);
+/* `name = count(<T> and <dynamic factors>);` and `name = sdf(<structures>, <T> and <dynamic factors>, cutoff);`: and / or / not
+ * over up to four within() terms.  h_i says whether an atom of `target` is in term i - the membership of vmd_ir_add_within_count(target, terms[i]) -
+ * and the atom is a member iff bit sum(h_i << i) of `truth` is set; atoms outside `target` never are.  `not within(r, R)` is one term with
+ * truth 0b01, `within(a, A) and not within(b, B)` two terms with truth 0b0010.  spec_within_closed acts on every term; spec_within_exclude_ref
+ * acts PER TERM (DECISION D-EXPR-SELF): an atom of terms[i].ref has h_i = 0 but stays in `target`, so it can still be a member, e.g. under
+ * `not`.  The records are those of vmd_ir_add_within_count and vmd_ir_add_sdf_shell (a frame without members: +0, no voxel).  One term with
+ * truth 0b10 IS the one-term property: the call forwards and the fingerprint is that property's.  Validation per term as
+ * vmd_ir_add_within_count; nterms outside 1..4, truth bits at or above 2^(2^nterms) and a NULL expr are errors.  A table that ignores a term
+ * or is constant is accepted.  rdf() over expressions is not offered. */
+#define VMD_SHELL_EXPR_MAX_TERMS 4
+typedef struct vmd_shell_expr_t { const vmd_shell_t* terms; size_t nterms; uint32_t truth; } vmd_shell_expr_t;
+bool vmd_ir_add_within_count_expr(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr);
+bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
+                               const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr, float cutoff);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
- * shape_weights or rmsd property, or the reference set followed by the target set of a within count: returns how many
+ * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
+ * term's reference set in term order, then the target set): returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
@@ -315,13 +330,21 @@ const char* vmd_script_report_fallback_source(const vmd_script_report_t* report)
  * VMD_SCRIPT_FEATURE_SHELL_RDF lets either selection argument of rdf() be such an AND, `<sel> and within(<r> | <a>:<b>, <sel>) [and <sel> ...]`
  * (DESIGN 1.7), under the same rules.
  * VMD_SCRIPT_FEATURE_SHELL_SDF lets the TARGET argument of sdf() be such an AND, under the same rules; within() in the structures
- * argument is refused with a reason of its own, and the distance family keeps answering "unsupported function 'within'". */
+ * argument is refused with a reason of its own, and the distance family keeps answering "unsupported function 'within'".
+ * VMD_SCRIPT_FEATURE_SHELL_EXPR extends the forms the bits above enable: with VMD_SCRIPT_FEATURE_WITHIN the argument of count(), with
+ * VMD_SCRIPT_FEATURE_SHELL_SDF the target of sdf(), may hold several DYNAMIC factors at the top level of its AND - `within(...)`,
+ * `not within(...)`, or a parenthesised expression over within() terms only, combined with and / or / not and nested parentheses.  Static
+ * factors AND into the target list as before; terms that repeat (same reference list, same range) are one term, numbered in order of first
+ * appearance; a statement that reduces to one positive term compiles to the one-term property.  Skipped with a reason: more than four
+ * distinct terms, a static selection inside a parenthesised dynamic factor, within() nested in a within() argument, a dynamic factor
+ * under a top-level `or`.  rdf() arguments, distance*() and the sdf structures keep their messages; without the bit nothing changes. */
 #define VMD_SCRIPT_FEATURE_ANGLES 1u
 #define VMD_SCRIPT_FEATURE_SHAPE 2u
 #define VMD_SCRIPT_FEATURE_RMSD 4u
 #define VMD_SCRIPT_FEATURE_WITHIN 8u
 #define VMD_SCRIPT_FEATURE_SHELL_RDF 16u
 #define VMD_SCRIPT_FEATURE_SHELL_SDF 32u
+#define VMD_SCRIPT_FEATURE_SHELL_EXPR 64u
 bool     vmd_ir_compile_from_source_ex(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology, uint32_t features,
                                        vmd_script_report_t** report);
 void     vmd_script_report_free(vmd_script_report_t* report);
@@ -331,7 +354,8 @@ size_t   vmd_ir_property_count(const vmd_script_ir_t* ir);              /* md_sc
 const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir);    /* md_script_ir_property_names, src/main.cpp:1278 */
 vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name); /* src/main.cpp:1285 */
 /* atom pairs ONE frame of the script asks for (rdf |ref| x |target| of the parent lists, plus |T| + |R| per shell; sdf K x (|target| + m), distance |a| x |b| per context, angle /
- * dihedral / shape_weights / rmsd: the atoms of every context's sets, within count: |target| + |ref|): the size a host
+ * dihedral / shape_weights / rmsd: the atoms of every context's sets, within count: |target| + |ref|, a shell expression: |target| + the
+ * sum of its terms' |ref|, for an sdf on top of the sdf's own): the size a host
  * compares with a threshold before it sends a small script to the GPU (vmd_shim_set_min_work; VIAMD's default dataset, src/main.cpp:522-528) */
 uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir);
 
@@ -420,6 +444,7 @@ bool vmd_eval_sdf_payload(vmd_script_eval_t* eval, const char* name, const vmd_s
  * frame.  `name` is a count(... within ...) property, an rdf over shells or an sdf over a shell; `which` selects the side: 0 = the reference
  * argument (rdf only), 1 = the target argument (rdf, sdf; the counted set of a count).  Bit a of `words` (word a / 64, bit a % 64) is atom a;
  * (num_atoms + 63) / 64 words are needed, and all of them are written.  Returns the number of members - 0 is a legitimate answer - or
+ * (for a count or an sdf over a shell expression, DESIGN 1.9, which = 1 answers the members of the whole expression) or
  * VMD_SHELL_MASK_FAILED ((size_t)-1) with vmd_last_error set: unknown property, a property or side that is not a shell, a frame outside the
  * trajectory, a device error, or `cap` too small (nothing is written then).  The frame is evaluated on demand, the way vmd_eval_sdf_payload
  * evaluates its frame: accumulated results, fingerprints and the frame mask are untouched, and the call may come while pool threads are

@@ -20,6 +20,7 @@
  *   vmd_hip_within_*  <- count(sel and within(r, sel))
  *   vmd_hip_within_*_flags, vmd_hip_shell_compact, vmd_hip_rdf_brute_masked  <- rdf() over within() shells
  *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
+ *   vmd_hip_within_atoms_expr, vmd_hip_within_brute_expr, vmd_hip_shell_expr_finish  <- and / or / not over within() shells
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -264,6 +265,26 @@ int vmd_hip_within_brute_atoms(void* stream, const float* xyz, size_t frame_stri
                                const float* boxes, uint32_t pbc_flags, int B,
                                const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
                                float rmin, float rmax, int closed, uint32_t* count_out, uint8_t* mask_out, size_t mask_stride);
+/* K9: and / or / not over up to four within() shells, DESIGN 1.9.  bits is u8[B][stride] indexed by atom index, clean (0) before the first
+ * term pass of a batch; stride must exceed every index of tgt.  A term pass tests the entries of `tgt` whose byte v has bit v of `live` set
+ * against ONE term's reference set - the membership of vmd_hip_within_brute_atoms, bit for bit - and ORs 1 << term into the byte of a hit;
+ * every other entry does no work and keeps its byte.  live = 0xffff tests every entry.  Nothing happens when *skip_flag != 0.
+ *   vmd_hip_within_atoms_expr   the cell walk of vmd_hip_within_atoms over the cell-sorted copy of the term's reference set
+ *   vmd_hip_within_brute_expr   all pairs from the raw frame (any cell, any cutoff)
+ *   vmd_hip_shell_expr_finish   mask_out[b][tgt[t]] = bit bits[b][tgt[t]] of `truth` (the layout of K8's masks; bytes of other atoms are not
+ *                               written), count_out u32[B] (zeroed by the call) = the members per frame.  term < 4, truth and live < 2^16 */
+int vmd_hip_within_atoms_expr(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                              const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
+                              const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad, vmd_grid_t grid,
+                              float rmin, float rmax, int closed, int term, uint32_t live, uint8_t* bits, size_t stride,
+                              const uint32_t* skip_flag);
+int vmd_hip_within_brute_expr(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                              const float* boxes, uint32_t pbc_flags, int B,
+                              const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                              float rmin, float rmax, int closed, int term, uint32_t live, uint8_t* bits, size_t stride,
+                              const uint32_t* skip_flag);
+int vmd_hip_shell_expr_finish(void* stream, int B, const int32_t* tgt, int ntgt, const uint8_t* bits, uint32_t truth,
+                              uint8_t* mask_out, size_t stride, uint32_t* count_out, const uint32_t* skip_flag);
 int vmd_hip_sdf_scatter_masked(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                const float* boxes, uint32_t pbc_flags, int B,
                                const int32_t* structs, int K, int m, const float* R32, const float* c32,

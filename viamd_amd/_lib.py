@@ -71,6 +71,11 @@ class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
     _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
 
 
+class ShellExprC(C.Structure):           # vmd_shell_expr_t (include/vmd_eval.h)
+    _fields_ = [("terms", C.POINTER(ShellC)), ("nterms", C.c_size_t), ("truth", C.c_uint32)]
+
+
+SHELL_EXPR_MAX_TERMS = 4                       # VMD_SHELL_EXPR_MAX_TERMS
 SHELL_MASK_FAILED = C.c_size_t(-1).value      # VMD_SHELL_MASK_FAILED (include/vmd_eval.h)
 
 
@@ -205,6 +210,9 @@ SIGNATURES = [
     ("vmd_eval_set_settled_callback", C.c_bool, [_vp, SETTLED_FN, C.c_void_p]),
     ("vmd_eval_set_frame_mask", None, [_vp, c_uint8_p, C.c_size_t]),
     ("vmd_eval_sdf_structures", c_int32_p, [_vp, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("vmd_ir_add_within_count_expr", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellExprC)]),
+    ("vmd_ir_add_sdf_shell_expr", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.c_size_t, c_int32_p, C.c_size_t, C.POINTER(ShellExprC),
+                                             C.c_float]),
     ("vmd_eval_shell_mask", C.c_size_t, [_vp, C.c_char_p, C.c_int, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32,
                                          C.POINTER(C.c_uint64), C.c_size_t]),
     ("vmd_eval_sdf_payload", C.c_bool, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, C.POINTER(SdfPayload)]),
@@ -361,6 +369,11 @@ SIGNATURES = [
                                        Grid, C.c_float, C.c_float, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     ("vmd_hip_within_brute_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                              C.c_float, C.c_float, C.c_int, _vp, _vp, C.c_size_t]),
+    ("vmd_hip_within_atoms_expr", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int,
+                                            C.c_int, Grid, C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint32, _vp, C.c_size_t, _vp]),
+    ("vmd_hip_within_brute_expr", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                            C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint32, _vp, C.c_size_t, _vp]),
+    ("vmd_hip_shell_expr_finish", C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_uint32, _vp, C.c_size_t, _vp, _vp]),
     ("vmd_hip_sdf_scatter_masked", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp,
                                              _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
                                              _vp]),

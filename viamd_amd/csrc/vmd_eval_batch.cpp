@@ -136,6 +136,11 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
         if (h->rdf_use) per_frame += 24 * e->sels[h->sel_t]->idx.size();
         if (h->sdf_use) per_frame += num_atoms + 64;
     }
+    // a shell expression: two bytes per atom of the frame - the term outcomes and the mask -, every R_i sorted
+    for (auto& x : e->exprs) {
+        for (auto& tm : x->terms) used[tm.sel_r] = 1;
+        per_frame += 2 * (num_atoms + 64);
+    }
     for (size_t i = 0; i < e->sels.size(); ++i) if (used[i]) per_frame += 40 * e->sels[i]->idx.size();
     for (auto& p : e->props) per_frame += p->prop.kind == PROP_SDF ? 64 * p->prop.K : (p->prop.kind == PROP_DIST ? 4 * p->dim1 : 0);
     // 288 GB of HBM: a 16 GB scratch budget holds the 1 000 frames of the 1M-atom RDF (333k selected atoms) in ONE batch
@@ -144,7 +149,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     // pair passes are long (a 1 024-frame batch of the 1M-atom RDF runs ~90 ms: interrupts are polled between batches); scripts
     // without them stream whole frames at HBM speed and take much larger batches, so that launches, the alignment kernel's
     // latency and the per-batch synchronisation stay small against the stream (grid.y = frames of the batch <= 65535)
-    const size_t cap = (e->rdf_groups.empty() && e->within_props.empty() && e->shell_sdf_props.empty()) ? 16384 : 1024;
+    const size_t cap = (e->rdf_groups.empty() && e->within_props.empty() && e->shell_sdf_props.empty() && e->exprs.empty()) ? 16384 : 1024;
     B = std::max<size_t>(1, std::min<size_t>(B, cap));
     return B;
 }

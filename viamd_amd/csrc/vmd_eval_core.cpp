@@ -215,6 +215,66 @@ void build_within_plan(vmd_script_eval_t* e) {
     }
 }
 
+uint32_t shell_expr_live(uint32_t truth, const std::vector<int>& order, size_t pos) {
+    uint32_t done = 0, later = 0;
+    for (size_t k = 0; k < order.size(); ++k) { if (k < pos) done |= 1u << order[k]; else if (k > pos) later |= 1u << order[k]; }
+    const uint32_t bit = 1u << order[pos];
+    uint32_t live = 0;
+    for (uint32_t v = 0; v < (1u << order.size()); ++v) {
+        if (v & ~done) continue;
+        for (uint32_t x = later;; x = (x - 1) & later) {          // every subset of the terms still to come
+            if (((truth >> (v | x)) & 1u) != ((truth >> (v | x | bit)) & 1u)) { live |= 1u << v; break; }
+            if (!x) break;
+        }
+    }
+    return live;
+}
+
+// shell expressions: T, every R_i and, under D-EXPR-SELF flipped, every T minus R_i become interned selections - shared with
+// everything else of the script, so that a cell-sorted copy of an R_i another pass built on the same grid in a batch is not built again
+void build_expr_plan(vmd_script_eval_t* e) {
+    e->exprs.clear();
+    e->expr_count_props.clear();
+    e->expr_sdf_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        const Property& d = p->prop;
+        if (!d.is_within_expr() && !d.is_expr_sdf()) continue;
+        const std::vector<int32_t>& T = d.is_expr_sdf() ? d.b : d.a;
+        auto x = std::make_unique<ShellExpr>();
+        x->sel_t = intern_selection(e, T);
+        x->truth = d.expr_truth;
+        for (const Property::ExprTerm& t : d.expr_terms) {
+            ShellExpr::Term tm;
+            tm.sel_r = intern_selection(e, t.ref);
+            tm.rmin = t.rmin; tm.rmax = t.rmax;
+            tm.sel_tt = x->sel_t;
+            if (e->spec.within_exclude_ref) {
+                std::vector<int32_t> ref = t.ref, tt = T;
+                std::sort(ref.begin(), ref.end());
+                tt.erase(std::remove_if(tt.begin(), tt.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), tt.end());
+                tm.sel_tt = tt.empty() ? -1 : intern_selection(e, tt);
+            }
+            x->terms.push_back(tm);
+        }
+        for (size_t k = 0; k < x->terms.size(); ++k) x->order.push_back((int)k);
+        std::stable_sort(x->order.begin(), x->order.end(), [&](int a, int b) {
+            return e->sels[x->terms[a].sel_r]->idx.size() < e->sels[x->terms[b].sel_r]->idx.size(); });
+        int found = -1;
+        for (size_t q = 0; q < e->exprs.size() && found < 0; ++q) {
+            const ShellExpr& y = *e->exprs[q];
+            bool same = y.sel_t == x->sel_t && y.truth == x->truth && y.terms.size() == x->terms.size();
+            for (size_t k = 0; same && k < y.terms.size(); ++k)
+                same = y.terms[k].sel_r == x->terms[k].sel_r && memcmp(&y.terms[k].rmin, &x->terms[k].rmin, sizeof(float)) == 0 &&
+                       memcmp(&y.terms[k].rmax, &x->terms[k].rmax, sizeof(float)) == 0;
+            if (same) found = (int)q;
+        }
+        if (found < 0) { e->exprs.push_back(std::move(x)); found = (int)e->exprs.size() - 1; }
+        p->expr_of = found;
+        (d.is_expr_sdf() ? e->expr_sdf_props : e->expr_count_props).push_back((int)i);
+    }
+}
+
 extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_script_ir_t* ir) {
     if (!ir) { vmd_fail("vmd_eval_create: ir is NULL"); return nullptr; }
     if (vmd_device_count() <= 0) { vmd_fail("vmd_eval_create: no usable HIP device (the evaluator has no CPU path)"); return nullptr; }
@@ -283,7 +343,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             }
             if (p.is_rmsd())                                                                      // Angstrom, as distance
                 for (size_t c = 0; c < st->dist_P; ++c) st->rmsd_max_set = std::max(st->rmsd_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
-            if (p.is_within()) st->data.unit_str[1] = "";                                         // a count
+            if (p.is_within() || p.is_within_expr()) st->data.unit_str[1] = "";                   // a count
             if (st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;
@@ -307,6 +367,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     }
     build_rdf_plan(e.get());
     build_within_plan(e.get());
+    build_expr_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
                 return nullptr; }
@@ -798,6 +859,8 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
                 HIP_OK(hipStreamSynchronize(e->stream));
             }
             HIP_OK(hipStreamSynchronize(e->stream));
+        } else if (d.is_within_expr()) {
+            // the lists live in the interned selections
         } else if (d.kind == PROP_DIST) {
             if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream)) return false;
             if (!p->d_b.upload(d.b.data(), d.b.size(), e->stream)) return false;
@@ -903,6 +966,8 @@ extern "C" size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name,
     } else if ((p->prop.is_shell_rdf() || p->prop.is_shell_sdf()) && p->prop.shell[which].on) {
         const Shell& h = *e->shells[p->shell_of[which]];
         sel_t = h.sel_t; sel_r = h.sel_r; rmin = h.rmin; rmax = h.rmax;
+    } else if ((p->prop.is_within_expr() || p->prop.is_expr_sdf()) && which == 1) {
+        // every term by all pairs into the eval's one-frame bits, then the finish - handled below
     } else {
         vmd_fail("the %s side of '%s' is not a within() shell", which ? "target" : "reference", name);
         return failed;
@@ -915,23 +980,43 @@ extern "C" size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name,
     if (cap < nwords || (!words && nwords)) { vmd_fail("vmd_eval_shell_mask: %zu words needed, room for %zu", nwords, words ? cap : (size_t)0); return failed; }
     if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
     std::fill(words, words + nwords, (uint64_t)0);
-    if (sel_t < 0) return 0;                   // T minus R is empty (spec_within_exclude_ref)
+    const ShellExpr* x = p->expr_of >= 0 ? e->exprs[p->expr_of].get() : nullptr;
+    if (!x && sel_t < 0) return 0;             // T minus R is empty (spec_within_exclude_ref)
     auto run = [&](size_t* members) -> bool {
         vmd_device_view_t view;
         memset(&view, 0, sizeof(view));
         const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
         BatchSrc src;
         if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
-        const Selection* st = e->sels[sel_t].get();
-        const Selection* sr = e->sels[sel_r].get();
         const size_t stride = std::max(src.row_stride, num_atoms);
         DevBuf<uint8_t>& d_mask = e->d_one_mask;
         DevBuf<uint32_t>& d_count = e->d_one_count;
         if (!d_mask.ensure(stride) || !d_count.ensure(1)) return false;
         HIP_OK(hipMemsetAsync(d_mask.p, 0, stride, e->stream));
-        KRN_OK(vmd_hip_within_brute_atoms(e->stream, src.base, src.frame_stride, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]),
-                1, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), rmin, rmax, e->spec.within_closed ? 1 : 0, d_count.p,
-                d_mask.p, stride));
+        if (x) {
+            if (!e->d_one_bits.ensure(stride)) return false;
+            HIP_OK(hipMemsetAsync(e->d_one_bits.p, 0, stride, e->stream));
+            const bool skip = g_opt.shell_expr_skip.load() != 0;
+            for (size_t pos = 0; pos < x->order.size(); ++pos) {
+                const ShellExpr::Term& tm = x->terms[x->order[pos]];
+                const uint32_t live = skip ? shell_expr_live(x->truth, x->order, pos) : 0xffffu;
+                if (!live || tm.sel_tt < 0) continue;
+                const Selection* tt = e->sels[tm.sel_tt].get();
+                const Selection* tr = e->sels[tm.sel_r].get();
+                KRN_OK(vmd_hip_within_brute_expr(e->stream, src.base, src.frame_stride, src.row_stride, e->stages[0].d_boxes.p,
+                        batch_pbc(e->stages[0]), 1, tt->d_idx.p, (int)tt->idx.size(), tr->d_idx.p, (int)tr->idx.size(), tm.rmin, tm.rmax,
+                        e->spec.within_closed ? 1 : 0, x->order[pos], live, e->d_one_bits.p, stride, nullptr));
+            }
+            const Selection* xt = e->sels[x->sel_t].get();
+            KRN_OK(vmd_hip_shell_expr_finish(e->stream, 1, xt->d_idx.p, (int)xt->idx.size(), e->d_one_bits.p, x->truth, d_mask.p, stride,
+                    d_count.p, nullptr));
+        } else {
+            const Selection* st = e->sels[sel_t].get();
+            const Selection* sr = e->sels[sel_r].get();
+            KRN_OK(vmd_hip_within_brute_atoms(e->stream, src.base, src.frame_stride, src.row_stride, e->stages[0].d_boxes.p,
+                    batch_pbc(e->stages[0]), 1, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), rmin, rmax,
+                    e->spec.within_closed ? 1 : 0, d_count.p, d_mask.p, stride));
+        }
         std::vector<uint8_t> bytes(num_atoms);
         HIP_OK(hipMemcpyAsync(bytes.data(), d_mask.p, num_atoms, hipMemcpyDeviceToHost, e->stream));
         HIP_OK(hipStreamSynchronize(e->stream));

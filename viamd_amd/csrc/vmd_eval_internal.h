@@ -175,6 +175,9 @@ struct Options {
     // an sdf over a shell: a reference list of fewer atoms than this gets its mask from all pairs even where a grid exists -
     // the walk costs the same whatever |R| is, all pairs is linear in it, and the two cross here (0: the walk whenever a grid exists)
     std::atomic<int> shell_brute_below{480};
+    // a shell expression: 1 = a lane whose outcome the earlier terms decided does no walk; 0 = every lane is tested against every
+    // term (the A/B of the measurement; results are identical)
+    std::atomic<int> shell_expr_skip{1};
 };
 
 extern Options g_opt;
@@ -365,6 +368,8 @@ enum { GEOM_RMSD = 7 };
 // `name = count(T and within(rmin:rmax, R))`: one PROP_DIST descriptor, a = T, b = R, the range in rmin / rmax; one value per
 // frame, the number of atoms of T with an atom of R in range
 enum { GEOM_WITHIN = 8 };
+// `name = count(T and <and / or / not over within() terms>)`: one PROP_DIST descriptor, a = T, the terms in expr_terms
+enum { GEOM_WITHIN_EXPR = 9 };
 
 struct Property {
     std::string name;
@@ -385,6 +390,14 @@ struct Property {
     struct ShellArg { bool on = false; std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; } shell[2];
     bool is_shell_rdf() const { return kind == PROP_RDF && (shell[0].on || shell[1].on); }
     bool is_shell_sdf() const { return kind == PROP_SDF && shell[1].on; }     // sdf over a shell target: side 1 only
+    // and / or / not over within() shells: 1..4 terms and a truth table of 2^K bits, indexed by sum(h_i << i).  Count form:
+    // dist_kind GEOM_WITHIN_EXPR, a = T, b empty; sdf form: b = T.  An expression of one positive term never gets here (it IS the
+    // one-term property, by the entry points)
+    struct ExprTerm { std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; };
+    std::vector<ExprTerm> expr_terms;
+    uint32_t expr_truth = 0;
+    bool is_within_expr() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN_EXPR; }
+    bool is_expr_sdf() const { return kind == PROP_SDF && !expr_terms.empty(); }
 };
 
 struct vmd_script_ir_t {
@@ -472,6 +485,24 @@ struct Shell {
     vmd_grid_t built_grid;
 };
 
+// and / or / not over within() shells, interned per (T, terms, truth): properties that name the same expression share its
+// passes, its mask and its populations.  A term pass runs over tt - T, or T minus R_i under spec_within_exclude_ref (D-EXPR-SELF: such an
+// atom has h_i = 0 and stays in T; -1: nothing left, no pass) - in ascending |R_i|; the bit positions stay those of the expression.
+struct ShellExpr {
+    int sel_t = -1;
+    struct Term { int sel_r = -1, sel_tt = -1; float rmin = 0.0f, rmax = 0.0f; };
+    std::vector<Term> terms;
+    uint32_t truth = 0;
+    std::vector<int> order;
+    DevBuf<uint8_t> bits, mask;             // u8[B][stride] by ATOM: the term outcomes, the members (both zeroed when allocated; bits again per batch)
+    DevBuf<uint32_t> count;                 // [B] the population of every frame of the batch
+    size_t stride = 0;
+};
+
+// the live word of the pass at position `pos` of `order` (vmd_hip.h, K9): bit v is set iff, for a byte v with zeros outside the terms already
+// evaluated, some outcome of the terms still to come makes the table differ between h_i = 0 and h_i = 1
+uint32_t shell_expr_live(uint32_t truth, const std::vector<int>& order, size_t pos);
+
 float* zero_volume_view(size_t nfloats);
 
 struct PropState {
@@ -530,6 +561,7 @@ struct PropState {
     bool within_empty = false;
     // rdf over shells: the interned shell of either side (-1: that side is its static list, sel_a / sel_b)
     int shell_of[2] = {-1, -1};
+    int expr_of = -1;                   // a count or an sdf over a shell expression: the interned ShellExpr
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh
@@ -732,6 +764,9 @@ struct vmd_script_eval_t {
     std::vector<int> shell_sdf_props;                   // indices into props of the sdfs over a shell: masked scatter in launch_rdf
     DevBuf<uint8_t> d_one_mask;                         // vmd_eval_shell_mask: one frame's mask by atom and its population, kept between calls
     DevBuf<uint32_t> d_one_count;
+    DevBuf<uint8_t> d_one_bits;                         // ... and the term outcomes of a shell expression's frame
+    std::vector<std::unique_ptr<ShellExpr>> exprs;      // shell expressions and the counts / sdfs over them, indices into props
+    std::vector<int> expr_count_props, expr_sdf_props;
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;
@@ -825,6 +860,7 @@ int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx);
 
 void build_rdf_plan(vmd_script_eval_t* e);
 void build_within_plan(vmd_script_eval_t* e);
+void build_expr_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
 
@@ -992,7 +1028,9 @@ struct RangeRun {
     bool launch_shell_masks(BatchCtx& c);
     bool launch_shell_sdfs(BatchCtx& c);
     bool launch_rdf(BatchCtx& c);
-    bool launch_sdf(BatchCtx& c, PropState* p, const Shell* mask);
+    bool launch_shell_exprs(BatchCtx& c);
+    bool launch_expr_sdfs(BatchCtx& c);
+    bool launch_sdf(BatchCtx& c, PropState* p, const uint8_t* mask, size_t mask_stride);
     bool launch_shape(BatchCtx& c, size_t pi);
     bool launch_rmsd(BatchCtx& c, PropState* p);
     bool launch_geometry(BatchCtx& c, PropState* p);

@@ -26,10 +26,12 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         else if (p.kind == PROP_SDF) {
             w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
             if (p.shell[1].on) w += (uint64_t)p.b.size() + (uint64_t)p.shell[1].ref.size();     // the parent list plus the shell's query
+            if (p.is_expr_sdf()) { w += (uint64_t)p.b.size(); for (auto& t : p.expr_terms) w += (uint64_t)t.ref.size(); }     // |T| + sum |R_i|
         }
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
         else if (p.is_within()) w += (uint64_t)p.a.size() + (uint64_t)p.b.size();        // |T| + |R|: a neighbour query, not all pairs
+        else if (p.is_within_expr()) { w += (uint64_t)p.a.size(); for (auto& t : p.expr_terms) w += (uint64_t)t.ref.size(); }     // |T| + sum |R_i|
         else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
         else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
                 * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
@@ -317,6 +319,68 @@ extern "C" bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, c
     return true;
 }
 
+// and / or / not over within() shells: the checks both entry points share; every term validated like vmd_ir_add_within_count
+static bool expr_ok(const vmd_shell_expr_t* x) {
+    if (!x) return vmd_fail("shell expression is NULL");
+    if (x->nterms < 1 || x->nterms > VMD_SHELL_EXPR_MAX_TERMS || !x->terms)
+        return vmd_fail("shell expression needs 1 to %d terms, got %zu", VMD_SHELL_EXPR_MAX_TERMS, x->nterms);
+    if (x->truth >> (1u << x->nterms)) return vmd_fail("shell expression truth table has bits above 2^%zu", x->nterms);
+    for (size_t i = 0; i < x->nterms; ++i) {
+        const vmd_shell_t& h = x->terms[i];
+        if (!idx_ok(h.ref, h.nref, "within reference set")) return false;
+        if (h.nref > 0x7fffffff) return vmd_fail("within set too large");
+        if (!std::isfinite(h.rmin) || !std::isfinite(h.rmax) || !(h.rmin >= 0.0f) || !(h.rmax > h.rmin))
+            return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
+    }
+    return true;
+}
+
+static void expr_copy(Property& p, const vmd_shell_expr_t* x) {
+    p.expr_terms.resize(x->nterms);
+    for (size_t i = 0; i < x->nterms; ++i) {
+        p.expr_terms[i].ref.assign(x->terms[i].ref, x->terms[i].ref + x->terms[i].nref);
+        p.expr_terms[i].rmin = x->terms[i].rmin; p.expr_terms[i].rmax = x->terms[i].rmax;
+    }
+    p.expr_truth = x->truth;
+}
+
+// `name = count(T and <expression over within() terms>);`.  One term with truth 0b10 IS the one-term count
+extern "C" bool vmd_ir_add_within_count_expr(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
+                                             const vmd_shell_expr_t* expr) {
+    if (!ir_name_ok(ir, name) || !idx_ok(target, ntarget, "within target set") || !expr_ok(expr)) return false;
+    if (ntarget > 0x7fffffff) return vmd_fail("within set too large");
+    if (expr->nterms == 1 && expr->truth == 2u)
+        return vmd_ir_add_within_count(ir, name, target, ntarget, expr->terms[0].ref, expr->terms[0].nref, expr->terms[0].rmin, expr->terms[0].rmax);
+    Property p;
+    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    p.dist_kind = GEOM_WITHIN_EXPR;
+    p.a.assign(target, target + ntarget);
+    p.aoff = {0, (int32_t)ntarget}; p.boff = {0, 0};
+    expr_copy(p, expr);
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
+// `name = sdf(structures, T and <expression over within() terms>, cutoff);`.  One term with truth 0b10 IS vmd_ir_add_sdf_shell
+extern "C" bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
+                                          const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr, float cutoff) {
+    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget,
+            "sdf target set")) return false;
+    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
+    if (!expr_ok(expr)) return false;
+    if (ntarget > 0x7fffffff) return vmd_fail("within set too large");
+    if (expr->nterms == 1 && expr->truth == 2u) return vmd_ir_add_sdf_shell(ir, name, structures, K, m, target, ntarget, &expr->terms[0], cutoff);
+    Property p;
+    p.name = name; p.kind = PROP_SDF; p.flags = VMD_PROPERTY_FLAG_VOLUME;
+    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
+    p.K = K; p.m = m; p.rmax = cutoff;
+    expr_copy(p, expr);
+    ir->props.push_back(std::move(p));
+    ir->rebuild_names();
+    return true;
+}
+
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
 extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
@@ -327,6 +391,13 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
             if (context > 0) return 0;
             size_t n = 0;
             for (const auto* v : {&p.b, &p.a}) for (int32_t i : *v) { if (out && n < cap) out[n] = i; n += 1; }
+            return n;
+        }
+        if (p.is_within_expr()) {     // every term's reference set in term order, then the target set (one context)
+            if (context > 0) return 0;
+            size_t n = 0;
+            for (auto& t : p.expr_terms) for (int32_t i : t.ref) { if (out && n < cap) out[n] = i; n += 1; }
+            for (int32_t i : p.a) { if (out && n < cap) out[n] = i; n += 1; }
             return n;
         }
         if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape() && !p.is_rmsd())) return 0;
@@ -374,6 +445,16 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
             h = fnv1a(h, &side, sizeof(side));
             h = fnv1a(h, p.shell[k].ref.data(), p.shell[k].ref.size() * sizeof(int32_t));
             h = fnv1a(h, &p.shell[k].rmin, sizeof(float)); h = fnv1a(h, &p.shell[k].rmax, sizeof(float));
+        }
+        if (!p.expr_terms.empty()) {                                    // shell expressions only, as above
+            const int32_t tag = 0x45585052;                             // "EXPR"
+            const uint32_t nt = (uint32_t)p.expr_terms.size();
+            h = fnv1a(h, &tag, sizeof(tag)); h = fnv1a(h, &nt, sizeof(nt)); h = fnv1a(h, &p.expr_truth, sizeof(uint32_t));
+            for (auto& t : p.expr_terms) {
+                const uint32_t nr = (uint32_t)t.ref.size();             // the lists of consecutive terms must not run into each other
+                h = fnv1a(h, &nr, sizeof(nr)); h = fnv1a(h, t.ref.data(), t.ref.size() * sizeof(int32_t));
+                h = fnv1a(h, &t.rmin, sizeof(float)); h = fnv1a(h, &t.rmax, sizeof(float));
+            }
         }
     }
     h = h ? h : 1;

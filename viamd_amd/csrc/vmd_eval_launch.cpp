@@ -329,7 +329,78 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
         PropState* p = e->props[pi].get();
         const Shell* h = e->shells[p->shell_of[1]].get();
         if (h->sel_t < 0) continue;                   // T minus R is empty: no member in any frame, no voxel
-        if (!launch_sdf(c, p, h)) return false;
+        if (!launch_sdf(c, p, h->amask.p, h->amask_stride)) return false;
+    }
+    return true;
+}
+
+// ---- shell expressions: one pass per term over T in atom order, ascending |R_i|, then the finish.  Walk or all pairs per term
+// by launch_shell_masks' RULE; the cell-sorted copies come from build_pair, so one that another pass of the batch built on the same grid is
+// reused.  The bits start clean in every batch and in every repeat of one; the counts travel to the host from here, like
+// launch_within_counts' rows and for the same reason.
+bool RangeRun::launch_shell_exprs(BatchCtx& c) {
+    const bool skip = g_opt.shell_expr_skip.load() != 0;
+    const int below = g_opt.shell_brute_below.load();
+    const int closed = e->spec.within_closed ? 1 : 0;
+    for (auto& xp : e->exprs) {
+        ShellExpr* x = xp.get();
+        Selection* st = e->sels[x->sel_t].get();
+        const size_t stride = c.src->row_stride;
+        if (x->stride != stride || c.nb * stride > x->mask.cap) {
+            if (!x->mask.ensure(c.nb * stride) || !x->bits.ensure(c.nb * stride)) return false;
+            HIP_OK(hipMemsetAsync(x->mask.p, 0, x->mask.cap, e->stream));          // atoms outside T read 0 for ever
+            x->stride = stride;
+        }
+        if (!x->count.ensure(c.nb)) return false;
+        HIP_OK(hipMemsetAsync(x->bits.p, 0, c.nb * stride, e->stream));
+        for (size_t pos = 0; pos < x->order.size(); ++pos) {
+            const int i = x->order[pos];
+            const ShellExpr::Term& tm = x->terms[i];
+            const uint32_t live = skip ? shell_expr_live(x->truth, x->order, pos) : 0xffffu;
+            if (!live || tm.sel_tt < 0) continue;              // the table ignores the term here, or T minus R_i is empty: h_i reads 0
+            Selection* tt = e->sels[tm.sel_tt].get();
+            Selection* sr = e->sels[tm.sel_r].get();
+            vmd_grid_t grid;
+            const float* d_gb = nullptr;
+            const int have_grid = (int)sr->idx.size() < below ? 0
+                    : grid_for(c, std::max(st->idx.size(), sr->idx.size()), tm.rmax, &grid, &d_gb);
+            if (have_grid < 0) return false;
+            if (have_grid) {
+                if (!build_pair(c, sr, sr, d_gb, grid)) return false;
+                e->prof.begin("shell_expr", e->stream);
+                KRN_OK(vmd_hip_within_atoms_expr(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, d_gb, c.pbc, (int)c.nb,
+                        tt->d_idx.p, (int)tt->idx.size(), sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, grid, tm.rmin,
+                        tm.rmax, closed, i, live, x->bits.p, stride, e->d_overflow.p));
+                e->prof.end(e->stream);
+            } else {
+                e->prof.begin("shell_expr_brute", e->stream);
+                KRN_OK(vmd_hip_within_brute_expr(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
+                        (int)c.nb, tt->d_idx.p, (int)tt->idx.size(), sr->d_idx.p, (int)sr->idx.size(), tm.rmin, tm.rmax, closed, i, live,
+                        x->bits.p, stride, e->d_overflow.p));
+                e->prof.end(e->stream);
+            }
+        }
+        e->prof.begin("shell_expr_finish", e->stream);
+        KRN_OK(vmd_hip_shell_expr_finish(e->stream, (int)c.nb, st->d_idx.p, (int)st->idx.size(), x->bits.p, x->truth, x->mask.p, stride,
+                x->count.p, e->d_overflow.p));
+        e->prof.end(e->stream);
+    }
+    for (int pi : e->expr_count_props) {
+        PropState* p = e->props[pi].get();
+        if (!p->d_out.ensure(c.nb)) return false;
+        KRN_OK(vmd_hip_within_to_float(e->stream, e->exprs[p->expr_of]->count.p, (int)c.nb, p->d_out.p, e->d_overflow.p));
+        HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * sizeof(float), hipMemcpyDeviceToHost,
+                e->stream));
+    }
+    return true;
+}
+
+// the scatter of an sdf over a shell expression: all or nothing behind the overflow flag, as launch_shell_sdfs
+bool RangeRun::launch_expr_sdfs(BatchCtx& c) {
+    for (int pi : e->expr_sdf_props) {
+        PropState* p = e->props[pi].get();
+        const ShellExpr* x = e->exprs[p->expr_of].get();
+        if (!launch_sdf(c, p, x->mask.p, x->stride)) return false;
     }
     return true;
 }
@@ -351,15 +422,17 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     commits.clear();
     row = 0;
     forked = false;
-    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_sdfs(c)) return false;
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !launch_shell_sdfs(c) ||
+        !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     return true;
 }
 
 // ---- an sdf's alignment and scatter over the batch.  mask: the shell the targets are taken from (launch_shell_sdfs) -
-// its atom-order mask gates the scatter, which then tests the overflow flag; nullptr: a static sdf, gated by its own tag list
-bool RangeRun::launch_sdf(BatchCtx& c, PropState* p, const Shell* mask) {
+// or the shell expression (launch_expr_sdfs): the atom-order mask gates the scatter, which then tests the overflow flag;
+// nullptr: a static sdf, gated by its own tag list
+bool RangeRun::launch_sdf(BatchCtx& c, PropState* p, const uint8_t* mask, size_t mask_stride) {
     const Property& d = p->prop;
     if (!p->d_R32.ensure(c.nb * d.K * 9) || !p->d_c32.ensure(c.nb * d.K * 3) || !p->d_group.ensure(c.nb * 4)) return false;
     e->prof.begin("sdf_align", e->stream);
@@ -376,7 +449,7 @@ bool RangeRun::launch_sdf(BatchCtx& c, PropState* p, const Shell* mask) {
                 (int)d.m, p->d_R32.p + su.off * d.K * 9, p->d_c32.p + su.off * d.K * 3, p->d_tgt.p, (p->have_owner
                 && !e->spec.sdf_include_self) ? p->d_owner.p : nullptr, (int)d.b.size(), d.rmax, VMD_VOLUME_DIM, acc_of(p, su),
                 p->d_group.p + 4 * su.off, p->tgt_first, p->tgt_stride, (p->unowned || e->spec.sdf_include_self) ? 1 : 0,
-                mask->amask.p + su.off * mask->amask_stride, mask->amask_stride, e->d_overflow.p));
+                mask + su.off * mask_stride, mask_stride, e->d_overflow.p));
         else KRN_OK(vmd_hip_sdf_scatter(e->stream, c.src->base + su.off * c.src->frame_stride,
                 c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p + 9 * su.off, c.pbc, (int)su.nb, p->d_structs.p, (int)d.K,
                 (int)d.m, p->d_R32.p + su.off * d.K * 9, p->d_c32.p + su.off * d.K * 3, p->d_tgt.p, (p->have_owner
@@ -448,8 +521,8 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     // are formed in complete_batch, when they have arrived
     if (d.kind == PROP_RDF) { if (!d.is_shell_rdf()) rdf_weights(c, p); return true; }
     // sdf over a shell, within count: launched by launch_rdf, behind the batch's cell builds
-    if (d.is_shell_sdf() || d.is_within()) return true;
-    if (d.kind == PROP_SDF) { VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr); }
+    if (d.is_shell_sdf() || d.is_within() || d.is_within_expr() || d.is_expr_sdf()) return true;     // (... and shell expressions)
+    if (d.kind == PROP_SDF) { VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0); }
     if (!p->d_out.ensure(c.nb * p->dim1)) return false;
     if (d.is_shape()) return launch_shape(c, pi);
     if (d.is_rmsd()) return launch_rmsd(c, p);

@@ -305,13 +305,13 @@ bool RangeRun::queue_batch(size_t bi) {
     c.two_streams = c.subs.size() > 1 && g_opt.block_two_streams.load() != 0;
 
     e->h_overflow[c.slot] = 0;
-    if ((!e->rdf_groups.empty() || !e->within_props.empty() || !e->shell_sdf_props.empty()) && !launch_rdf(c)) return false;
+    if ((!e->rdf_groups.empty() || !e->within_props.empty() || !e->shell_sdf_props.empty() || !e->exprs.empty()) && !launch_rdf(c)) return false;
 
     for (size_t pi = 0; pi < e->props.size(); ++pi) {
         PropState* p = e->props[pi].get();
         if (!launch_property(c, pi)) return false;
         // (a within count's rows are sent by launch_rdf, behind the overflow flag)
-        if (p->prop.kind == PROP_DIST && !p->prop.is_within())
+        if (p->prop.kind == PROP_DIST && !p->prop.is_within() && !p->prop.is_within_expr())
             HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * p->dim1 * sizeof(float),
                     hipMemcpyDeviceToHost, e->stream));
         p->dirty = p->dirty || !spec;

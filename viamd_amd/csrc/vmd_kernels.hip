@@ -2268,6 +2268,172 @@ __global__ __launch_bounds__(256) void k_within_atoms(vmd_within_atoms_params_t 
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
 }
 
+// ------------------------------------------------------------------------------------------------ K9: and / or / not over shells
+
+// A shell expression is up to four terms and a truth table.  Every term gets one pass over the target list; pass i ORs h_i << i into the
+// atom's byte of bits[b][atom], and k_shell_expr_finish looks the byte up in the table.  live: bit v is set iff h_i can still change the
+// outcome of a lane whose byte reads v when the pass starts (the bits of the terms not yet evaluated read 0, so at most 8 of the 16
+// values occur).  A lane whose bit is clear does no walk and leaves its byte alone.
+struct vmd_within_atoms_expr_params_t {
+    vmd_cells_params_t c;       // T as k_within_atoms reads it
+    const float* sref; const uint32_t* cs_ref; int nref_pad;
+    vmd_within_test_t w; float rpad; int ry, rz;
+    unsigned char* bits; size_t stride;         // u8[B][stride], indexed by ATOM
+    int term; uint32_t live;
+    const uint32_t* skip;
+};
+
+// The walk of k_within_atoms (kept as a copy, statement for statement: that kernel keeps the code the compiler gave it) for ONE term of an
+// expression.  The lane reads its byte first; a wave with no live lane leaves after that one load.
+__global__ __launch_bounds__(256) void k_within_atoms_expr(vmd_within_atoms_expr_params_t p) {
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    size_t at = 0;
+    unsigned cur = 0;
+    bool go = false;
+    if (t < p.c.nsel) {
+        at = (size_t)b * p.stride + (size_t)vmd_sel_atom(p.c, t);
+        cur = p.bits[at];
+        go = ((p.live >> cur) & 1u) != 0;
+    }
+    if (!__ballot(go ? 1 : 0)) return;
+    const int nxf = p.c.grid.nxf, ny = p.c.grid.ny, nz = p.c.grid.nz;
+    const bool tri = (p.c.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.c.pbc & 7u) != 7u;
+    const float* q = p.c.boxes + (size_t)VMD_BOX_STRIDE * b;
+    const float Lx = q[0], Ly = q[1], Lz = q[2];
+    const float inv_cx = (float)nxf * q[3];
+    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
+    const bool open_x = open && !(p.c.pbc & 1u), open_y = open && !(p.c.pbc & 2u), open_z = open && !(p.c.pbc & 4u);
+    const float orgx = open_x ? q[6] : 0.0f;
+    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
+    const uint32_t* csr = p.cs_ref + (size_t)b * (p.c.grid.ncell + 1);
+    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
+    const float* ry_ = rx + p.nref_pad;
+    const float* rz_ = ry_ + p.nref_pad;
+    bool hit = false;
+    if (go) {
+        float xi, yi, zi;
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)nxf);
+        const int pz = pen / ny, py = pen - pz * ny;
+        for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
+            int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
+            if (open_z && (qz < 0 || qz >= nz)) continue;
+            if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
+            for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
+                int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+                if (open_y && (qy < 0 || qy >= ny)) continue;
+                if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
+                const int qp = qz * ny + qy;
+                float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
+                if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
+                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
+                    const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                    const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                    if (rr <= 0.0f) continue;
+                    rpad = sqrtf(rr) * 1.0001f;
+                }
+                if (tri) {
+                    const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
+                    const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
+                    offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                    offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+                }
+                for (int kx = -1; kx <= 1 && !hit; ++kx) {
+                    if (open_x && kx != 0) continue;
+                    float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
+                    if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
+                    const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
+                    const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
+                    if (hi < 0.0f || lo >= Lx) continue;
+                    const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
+                    const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
+                    const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
+                    for (unsigned j = ja; j < jb && !hit; ++j) {
+                        const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
+                        hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
+                    }
+                }
+            }
+        }
+        if (hit) p.bits[at] = (unsigned char)(cur | (1u << p.term));
+    }
+}
+
+struct vmd_within_brute_expr_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* tgt; int ntgt; const int32_t* ref; int nref;
+    vmd_within_test_t w;
+    unsigned char* bits; size_t stride;
+    int term; uint32_t live;
+    const uint32_t* skip;
+};
+
+// The brute twin, for a small R or where no grid exists: the arithmetic of k_within_brute<true, true>, R staged through LDS in tiles of 256.
+// One WAVE per block, so that a wave with no live lane can leave after its one load without leaving a tile half staged.
+__global__ __launch_bounds__(64) void k_within_brute_expr(vmd_within_brute_expr_params_t p) {
+    __shared__ float s_r[3][256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x;
+    const int t = blockIdx.x * 64 + lane;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    size_t at = 0;
+    unsigned cur = 0;
+    bool go = false;
+    int a_t = 0;
+    if (t < p.ntgt) {
+        a_t = p.tgt ? p.tgt[t] : t;
+        at = (size_t)b * p.stride + (size_t)a_t;
+        cur = p.bits[at];
+        go = ((p.live >> cur) & 1u) != 0;
+    }
+    if (!__ballot(go ? 1 : 0)) return;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    if (go) vmd_pair_coords(bx, fx[a_t], fy[a_t], fz[a_t], xi, yi, zi);
+    bool hit = false;
+    for (int j0 = 0; j0 < p.nref; j0 += 256) {
+        __syncthreads();
+        const int nj = p.nref - j0 < 256 ? p.nref - j0 : 256;
+        for (int jj = lane; jj < nj; jj += 64) {
+            const int a = p.ref ? p.ref[j0 + jj] : j0 + jj;
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+        }
+        __syncthreads();
+        if (go && !hit)
+            for (int jj = 0; jj < nj && !hit; ++jj)
+                hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
+    }
+    if (go && hit) p.bits[at] = (unsigned char)(cur | (1u << p.term));
+}
+
+struct vmd_shell_expr_finish_params_t {
+    const int32_t* tgt; int ntgt;
+    const unsigned char* bits; unsigned char* mask; size_t stride;
+    uint32_t truth;
+    unsigned* count; const uint32_t* skip;
+};
+
+// One lane per entry of T: the byte the term passes left is the index into the truth table (a skipped term reads 0 - the outcome did not
+// depend on it).  mask[b][atom] is the layout k_sdf_scatter<.., true> and vmd_eval_shell_mask read; count[b] the population, one atomic per wave.
+__global__ __launch_bounds__(256) void k_shell_expr_finish(vmd_shell_expr_finish_params_t p) {
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    bool in = false;
+    if (t < p.ntgt) {
+        const size_t at = (size_t)b * p.stride + (size_t)(p.tgt ? p.tgt[t] : t);
+        in = ((p.truth >> p.bits[at]) & 1u) != 0;
+        p.mask[at] = in ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(in ? 1 : 0);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
+}
+
 // ------------------------------------------------------------------------------------------------ K7: shells as selections
 
 // Stream compaction of a cell-sorted copy: the entries k_within_pencil<true> flagged, in place order, become a second sorted copy with its
@@ -4053,6 +4219,61 @@ extern "C" int vmd_hip_shell_compact(void* stream, const uint8_t* flags, const u
 extern "C" int vmd_hip_within_to_float(void* stream, const uint32_t* counts, int B, float* out, const uint32_t* skip_flag) {
     if (B <= 0) return 0;
     hipLaunchKernelGGL(k_within_to_float, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, counts, B, out, skip_flag);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K9: one term pass of a shell expression, and the finish
+static bool vmd_expr_term_ok(int B, int term, uint32_t live, const uint8_t* bits, size_t stride, float rmin, float rmax) {
+    return B <= 65535 && term >= 0 && term < 4 && live <= 0xffffu && bits && stride && rmin >= 0.0f && rmax > rmin;
+}
+
+extern "C" int vmd_hip_within_atoms_expr(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                         const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
+                                         const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad, vmd_grid_t grid,
+                                         float rmin, float rmax, int closed, int term, uint32_t live, uint8_t* bits, size_t stride,
+                                         const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0 || ntgt <= 0 || !live) return 0;
+    if (!vmd_expr_term_ok(B, term, live, bits, stride, rmin, rmax) || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 ||
+        grid.ncell != grid.nxf * grid.ny * grid.nz || nref <= 0 || !sorted_ref || !cell_start_ref) return (int)hipErrorInvalidValue;
+    vmd_within_atoms_expr_params_t p{};
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
+    p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
+    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
+    p.w = vmd_make_within_test(rmin, rmax, closed);
+    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_within_pencil
+    p.ry = g_pen_ry; p.rz = g_pen_rz;
+    p.bits = bits; p.stride = stride; p.term = term; p.live = live; p.skip = skip_flag;
+    hipLaunchKernelGGL(k_within_atoms_expr, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_within_brute_expr(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
+                                         const float* boxes, uint32_t pbc_flags, int B,
+                                         const int32_t* tgt, int ntgt, const int32_t* ref, int nref,
+                                         float rmin, float rmax, int closed, int term, uint32_t live, uint8_t* bits, size_t stride,
+                                         const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0 || ntgt <= 0 || nref <= 0 || !live) return 0;
+    if (!vmd_expr_term_ok(B, term, live, bits, stride, rmin, rmax)) return (int)hipErrorInvalidValue;
+    vmd_within_brute_expr_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, tgt, ntgt, ref, nref,
+                                     vmd_make_within_test(rmin, rmax, closed), bits, stride, term, live, skip_flag};
+    hipLaunchKernelGGL(k_within_brute_expr, dim3((ntgt + 63) / 64, B), dim3(VMD_WAVE), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_shell_expr_finish(void* stream, int B, const int32_t* tgt, int ntgt, const uint8_t* bits, uint32_t truth,
+                                         uint8_t* mask_out, size_t stride, uint32_t* count_out, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !count_out || !bits || !mask_out || !stride || truth > 0xffffu) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    if (ntgt <= 0) return 0;
+    vmd_shell_expr_finish_params_t p{tgt, ntgt, bits, mask_out, stride, truth, count_out, skip_flag};
+    hipLaunchKernelGGL(k_shell_expr_finish, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

@@ -503,6 +503,86 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                     for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
                     return out;
                 };
+                // DESIGN 1.9 (VMD_SCRIPT_FEATURE_SHELL_EXPR): the argument of count() and the target of sdf() may hold several dynamic
+                // factors at the top level of their AND - within(...), not within(...), or a parenthesised and / or / not over within()
+                // terms only.  Terms that repeat are one term, numbered in order of first appearance; a table over four variables is
+                // carried through the parse and cut to the terms there are
+                struct ExprTerm { std::vector<int32_t> ref; float rmin, rmax; };
+                struct ExprArg { std::vector<int32_t> list; std::vector<ExprTerm> terms; uint32_t truth = 0; bool dynamic = false; };
+                auto is_within_at = [&](size_t q) {
+                    return toks[q].kind == T_ID && toks[q].text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(";
+                };
+                auto expr_arg = [&]() -> ExprArg {
+                    static const uint32_t VAR[4] = {0xAAAAu, 0xCCCCu, 0xF0F0u, 0xFF00u};
+                    ExprArg out;
+                    // [from, the end of the argument or, with stop_and, the next `and` at depth 0) -> {end, holds within(, holds a top-level or}
+                    auto extent = [&](size_t from, bool stop_and, bool* has_within, bool* top_or) {
+                        int depth = 0;
+                        size_t q = from;
+                        for (; q < toks.size(); ++q) {
+                            const Token& tk = toks[q];
+                            if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
+                            if (tk.kind == T_OP && tk.text == "(") depth += 1;
+                            if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
+                            if (stop_and && depth == 0 && tk.kind == T_ID && tk.text == "and") break;
+                            if (is_within_at(q)) *has_within = true;
+                            if (tk.kind == T_ID && tk.text == "or" && depth == 0) *top_or = true;
+                        }
+                        return q;
+                    };
+                    bool has_within = false, top_or = false;
+                    extent(p.i, false, &has_within, &top_or);
+                    if (!has_within) { out.list = p.sel_or().indices(); return out; }
+                    if (top_or) fail("%s: a dynamic factor under a top-level or with a static selection", name.c_str());
+                    out.dynamic = true;
+                    auto within_term = [&]() -> uint32_t {
+                        ++p.i;
+                        p.take("(");
+                        double rmin = 0.0, rmax = p.number();
+                        if (p.accept(":")) {
+                            rmin = rmax; rmax = p.number();
+                            if (!(rmin < rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
+                        } else if (!(rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
+                        p.take(",");
+                        bool nested = false, unused = false;
+                        extent(p.i, false, &nested, &unused);
+                        if (nested) fail("%s: within() nested in a within() argument", name.c_str());
+                        ExprTerm t{p.sel_or().indices(), (float)rmin, (float)rmax};
+                        p.take(")");
+                        if (t.ref.empty()) fail("%s: empty selection", name.c_str());
+                        for (size_t k = 0; k < out.terms.size(); ++k)
+                            if (out.terms[k].ref == t.ref && out.terms[k].rmin == t.rmin && out.terms[k].rmax == t.rmax) return VAR[k];
+                        if (out.terms.size() == VMD_SHELL_EXPR_MAX_TERMS) fail("%s: more than four distinct within() terms", name.c_str());
+                        out.terms.push_back(std::move(t));
+                        return VAR[out.terms.size() - 1];
+                    };
+                    std::function<uint32_t()> dyn_or;
+                    std::function<uint32_t()> dyn_not = [&]() -> uint32_t {
+                        if (p.accept("not")) return ~dyn_not() & 0xffffu;
+                        if (p.i < toks.size() && is_within_at(p.i)) return within_term();
+                        if (p.is_word("(")) { p.take("("); const uint32_t t = dyn_or(); p.take(")"); return t; }
+                        fail("%s: a static selection inside a parenthesised dynamic factor", name.c_str());
+                    };
+                    auto dyn_and = [&]() -> uint32_t { uint32_t t = dyn_not(); while (p.accept("and")) t &= dyn_not(); return t; };
+                    dyn_or = [&]() -> uint32_t { uint32_t t = dyn_and(); while (p.accept("or")) t |= dyn_and(); return t; };
+                    std::vector<uint8_t> tmask(topo.n, 1);
+                    uint32_t table = 0xffffu;
+                    do {
+                        bool dyn = false, unused = false;
+                        extent(p.i, true, &dyn, &unused);
+                        if (dyn) table &= dyn_not();
+                        else { const Sel f = p.sel_not(); for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a]; }
+                    } while (p.accept("and"));
+                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
+                    out.truth = table & ((1u << (1u << out.terms.size())) - 1u);
+                    return out;
+                };
+                auto expr_view = [](const ExprArg& x, std::vector<vmd_shell_t>* terms) {
+                    terms->clear();
+                    for (auto& t : x.terms) terms->push_back(vmd_shell_t{t.ref.data(), t.ref.size(), t.rmin, t.rmax});
+                    return vmd_shell_expr_t{terms->data(), terms->size(), x.truth};
+                };
+                const bool exprs = (features & VMD_SCRIPT_FEATURE_SHELL_EXPR) != 0;
                 if (v == "rdf" && (features & VMD_SCRIPT_FEATURE_SHELL_RDF)) {
                     const DynArg A = dyn_arg("rdf"); p.take(",");
                     const DynArg B = dyn_arg("rdf"); p.take(",");
@@ -548,7 +628,9 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                     }
                     const Sel ref = p.sel_or(); p.take(",");
                     DynArg T;
-                    if (shells) T = dyn_arg("sdf"); else T.list = p.sel_or().indices();
+                    ExprArg X;
+                    if (shells && exprs) { X = expr_arg(); T.list = X.list; }
+                    else if (shells) T = dyn_arg("sdf"); else T.list = p.sel_or().indices();
                     p.take(",");
                     const double cutoff = p.number();
                     p.take(")");
@@ -561,11 +643,29 @@ void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, R
                         flat.insert(flat.end(), st.begin(), st.end());
                     }
                     const size_t K = structs.size();
-                    if (T.shell && T.list.empty()) fail("%s: empty selection", name.c_str());
-                    commit = [=]() {
+                    if ((T.shell || X.dynamic) && T.list.empty()) fail("%s: empty selection", name.c_str());
+                    if (X.dynamic) commit = [=]() {
+                        std::vector<vmd_shell_t> tv;
+                        const vmd_shell_expr_t xv = expr_view(X, &tv);
+                        if (!vmd_ir_add_sdf_shell_expr(ir, name.c_str(), flat.data(), K, m, X.list.data(), X.list.size(), &xv, (float)cutoff))
+                            throw ScriptError(vmd_last_error());
+                    };
+                    else commit = [=]() {
                         const vmd_shell_t sh{T.ref.data(), T.ref.size(), (float)T.rmin, (float)T.rmax};
                         if (!vmd_ir_add_sdf_shell(ir, name.c_str(), flat.data(), K, m, T.list.data(), T.list.size(), T.shell ? &sh : nullptr, (float)cutoff))
                             throw ScriptError(vmd_last_error());
+                    };
+                } else if (v == "count" && exprs) {
+                    // `name = count(<factor> and <factor> ...);` with any number of dynamic factors
+                    const ExprArg X = expr_arg();
+                    if (!X.dynamic) fail("%s: count of a static selection is a constant (left to the fallback)", name.c_str());
+                    p.take(")");
+                    if (p.is_word("in")) fail("%s: count(...) in <contexts> is outside the subset", name.c_str());
+                    if (X.list.empty()) fail("%s: empty selection", name.c_str());
+                    commit = [=]() {
+                        std::vector<vmd_shell_t> tv;
+                        const vmd_shell_expr_t xv = expr_view(X, &tv);
+                        if (!vmd_ir_add_within_count_expr(ir, name.c_str(), X.list.data(), X.list.size(), &xv)) throw ScriptError(vmd_last_error());
                     };
                 } else if (v == "count") {
                     // `name = count(<factor> and <factor> ...);`: exactly one factor is within(<r> | <a>:<b>, <static selection>),

@@ -126,6 +126,34 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_sdf_shell(self.h, name.encode(), s.ctypes.data_as(L.c_int32_p), s.shape[0], s.shape[1],
                                                   tp, t.size, ptr, float(cutoff)))
 
+    def _shell_expr(self, terms, truth):
+        """[(R, r_min, r_max), ...] and a truth table -> a vmd_shell_expr_t and what keeps its lists alive"""
+        import ctypes as C
+        keep = [_idx(t[0]) for t in terms]
+        arr = (L.ShellC * max(len(terms), 1))(*[L.ShellC(k[1], k[0].size, float(t[1]), float(t[2])) for k, t in zip(keep, terms)])
+        return L.ShellExprC(C.cast(arr, C.POINTER(L.ShellC)), len(terms), int(truth)), (keep, arr)
+
+    def add_within_count_expr(self, name, target, terms, truth):
+        """`name = count(target and <and / or / not over within() terms>);`: terms = up to four (R, r_min, r_max); per frame,
+        h_i says whether an atom of `target` is in term i, and it is counted iff bit sum(h_i << i) of `truth` is set.  One term with
+        truth 0b10 is add_within_count."""
+        import ctypes as C
+        t, tp = _idx(target)
+        x, keep = self._shell_expr(terms, truth)
+        self._check(self.lib.vmd_ir_add_within_count_expr(self.h, name.encode(), tp, t.size, C.byref(x)))
+
+    def add_sdf_shell_expr(self, name, structures, target, cutoff, terms, truth):
+        """`name = sdf(structures, target and <and / or / not over within() terms>, cutoff);`: only the members of the
+        expression (add_within_count_expr) are scattered.  One term with truth 0b10 is add_sdf_shell."""
+        import ctypes as C
+        s = np.ascontiguousarray(structures, dtype=np.int32)
+        if s.ndim != 2:
+            raise ValueError("structures must be a [K, m] index array")
+        t, tp = _idx(target)
+        x, keep = self._shell_expr(terms, truth)
+        self._check(self.lib.vmd_ir_add_sdf_shell_expr(self.h, name.encode(), s.ctypes.data_as(L.c_int32_p), s.shape[0], s.shape[1],
+                                                       tp, t.size, C.byref(x), float(cutoff)))
+
     def add_distance(self, name, a, b, kind=L.DIST_COM):
         """`name = distance|distance_min|distance_max|distance_pair(a, b)` (src/main.cpp:2817-2858)."""
         a_, ap = _idx(a)

@@ -271,10 +271,11 @@ FEATURE_RMSD = 4                                # VMD_SCRIPT_FEATURE_RMSD
 FEATURE_WITHIN = 8                              # VMD_SCRIPT_FEATURE_WITHIN
 FEATURE_SHELL_RDF = 16                          # VMD_SCRIPT_FEATURE_SHELL_RDF
 FEATURE_SHELL_SDF = 32                          # VMD_SCRIPT_FEATURE_SHELL_SDF
+FEATURE_SHELL_EXPR = 64                         # VMD_SCRIPT_FEATURE_SHELL_EXPR
 
 
 def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
-                   shell_sdf=False):
+                   shell_sdf=False, shell_expr=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
 
     partial=True (vmd_ir_compile_from_source_partial): statements outside the subset are reported instead of failing the script;
@@ -300,7 +301,12 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
     static list) or dict(ref=idx, rmin=, rmax=).
 
     shell_sdf=True (VMD_SCRIPT_FEATURE_SHELL_SDF, opt-in): the target argument of sdf() may be such an AND; within() in the
-    structures argument is refused; info[name] = dict(kind="sdf", structures=, target=idx, cutoff=, target_shell=) with the shell as above."""
+    structures argument is refused; info[name] = dict(kind="sdf", structures=, target=idx, cutoff=, target_shell=) with the shell as above.
+
+    shell_expr=True (VMD_SCRIPT_FEATURE_SHELL_EXPR, opt-in): with within=True the argument of count(), with shell_sdf=True the target of
+    sdf(), may hold several dynamic factors at the top level of its AND - within(...), not within(...), or a parenthesised and / or / not
+    over within() terms only.  info[name] gains terms=[dict(ref=idx, rmin=, rmax=)] in order of first appearance and
+    truth= (bit sum(h_i << i) set: a member); a count that does not reduce to one positive term has kind="within_count_expr"."""
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -344,7 +350,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
                 p.take("=")
                 if shape and p.peek() == ("id", "shape_weights"):
                     raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf, shell_sdf)
+                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf, shell_sdf, shell_expr)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
@@ -539,6 +545,125 @@ def _count_statement(p, name, topo, env, ir, info):
     return commit
 
 
+_EXPR_VAR = (0xAAAA, 0xCCCC, 0xF0F0, 0xFF00)
+
+
+def _expr_arg(p, name, topo):
+    """the argument of count() / the target of sdf() under shell_expr=True (the twin of expr_arg in vmd_script.cpp): an AND of static
+    factors and dynamic ones -> (index list, terms, truth), terms None for a static argument"""
+    def is_within_at(q):
+        return p.t[q] == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "(")
+
+    def extent(q, stop_and):
+        """-> (holds within(, holds a top-level or) up to the end of the argument or, with stop_and, the next `and` at depth 0"""
+        depth, has_within, top_or = 0, False, False
+        while q < len(p.t):
+            k, v = p.t[q]
+            if k == "op" and v in (",", ";") and depth == 0:
+                break
+            if k == "op" and v == "(":
+                depth += 1
+            if k == "op" and v == ")":
+                if depth == 0:
+                    break
+                depth -= 1
+            if stop_and and depth == 0 and (k, v) == ("id", "and"):
+                break
+            has_within = has_within or is_within_at(q)
+            top_or = top_or or ((k, v) == ("id", "or") and depth == 0)
+            q += 1
+        return has_within, top_or
+
+    has_within, top_or = extent(p.i, False)
+    if not has_within:
+        return p.sel_or().indices(), None, 0
+    if top_or:
+        raise ScriptError(f"{name}: a dynamic factor under a top-level or with a static selection")
+    terms = []
+
+    def within_term():
+        p.i += 1
+        p.take("(")
+        rmin, rmax = 0.0, p.number()
+        if p.accept(":"):
+            rmin, rmax = rmax, p.number()
+            if not rmin < rmax:
+                raise ScriptError(f"{name}: within range needs 0 <= a < b")
+        elif not rmax > 0.0:
+            raise ScriptError(f"{name}: within needs a radius > 0")
+        p.take(",")
+        if extent(p.i, False)[0]:
+            raise ScriptError(f"{name}: within() nested in a within() argument")
+        ref = p.sel_or().indices()
+        p.take(")")
+        if ref.size == 0:
+            raise ScriptError(f"{name}: empty selection")
+        t = dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
+        for k, u in enumerate(terms):
+            if np.array_equal(u["ref"], ref) and u["rmin"] == t["rmin"] and u["rmax"] == t["rmax"]:
+                return _EXPR_VAR[k]
+        if len(terms) == L.SHELL_EXPR_MAX_TERMS:
+            raise ScriptError(f"{name}: more than four distinct within() terms")
+        terms.append(t)
+        return _EXPR_VAR[len(terms) - 1]
+
+    def dyn_not():
+        if p.accept("not"):
+            return ~dyn_not() & 0xffff
+        if p.i < len(p.t) and is_within_at(p.i):
+            return within_term()
+        if p.peek() == ("op", "("):
+            p.take("(")
+            t = dyn_or()
+            p.take(")")
+            return t
+        raise ScriptError(f"{name}: a static selection inside a parenthesised dynamic factor")
+
+    def dyn_and():
+        t = dyn_not()
+        while p.accept("and"):
+            t &= dyn_not()
+        return t
+
+    def dyn_or():
+        t = dyn_and()
+        while p.accept("or"):
+            t |= dyn_and()
+        return t
+
+    tmask = np.ones(topo.num_atoms, bool)
+    table = 0xffff
+    while True:
+        if extent(p.i, True)[0]:
+            table &= dyn_not()
+        else:
+            tmask = tmask & p.sel_not().mask
+        if not p.accept("and"):
+            break
+    return np.nonzero(tmask)[0].astype(np.int32), terms, table & ((1 << (1 << len(terms))) - 1)
+
+
+def _count_expr_statement(p, name, topo, env, ir, info):
+    """`name = count(<factor> and ...)` with any number of dynamic factors (the twin of the count branch under the bit)"""
+    tgt, terms, truth = _expr_arg(p, name, topo)
+    if terms is None:
+        raise ScriptError(f"{name}: count of a static selection is a constant (left to the fallback)")
+    p.take(")")
+    if p.peek() == ("id", "in"):
+        raise ScriptError(f"{name}: count(...) in <contexts> is outside the subset")
+    if tgt.size == 0:
+        raise ScriptError(f"{name}: empty selection")
+
+    def commit():
+        ir.add_within_count_expr(name, tgt, [(t["ref"], t["rmin"], t["rmax"]) for t in terms], truth)
+        if len(terms) == 1 and truth == 2:
+            info[name] = dict(kind="within_count", target=tgt, ref=terms[0]["ref"], rmin=terms[0]["rmin"], rmax=terms[0]["rmax"],
+                              terms=terms, truth=truth)
+        else:
+            info[name] = dict(kind="within_count_expr", target=tgt, terms=terms, truth=truth)
+    return commit
+
+
 def _dyn_arg(p, name, topo, fn="rdf"):
     """one selection argument of rdf() under shell_rdf=True / the target of sdf() under shell_sdf=True (the twin of dyn_arg in
     vmd_script.cpp) -> (index list, shell or None)"""
@@ -592,7 +717,7 @@ def _dyn_arg(p, name, topo, fn="rdf"):
     return np.nonzero(tmask)[0].astype(np.int32), dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
 
 
-def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False, shell_sdf=False):
+def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False, shell_sdf=False, shell_expr=False):
     """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
     IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
     k, v = p.peek()
@@ -603,6 +728,8 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
     p.take("(")
     if v == "rmsd":
         return _rmsd_statement(p, name, topo, env, ir, info), True
+    if v == "count" and shell_expr:
+        return _count_expr_statement(p, name, topo, env, ir, info), True
     if v == "count":
         return _count_statement(p, name, topo, env, ir, info), True
     if v == "rdf" and shell_rdf:
@@ -660,7 +787,13 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
             if (k_, v_) == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "("):
                 raise ScriptError(f"{name}: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)")
         ref = p.sel_or(); p.take(",")
-        tg, sh = _dyn_arg(p, name, topo, "sdf"); p.take(",")
+        terms, truth = None, 0
+        if shell_expr:
+            tg, terms, truth = _expr_arg(p, name, topo)
+            sh = terms[0] if terms is not None and len(terms) == 1 and truth == 2 else None
+        else:
+            tg, sh = _dyn_arg(p, name, topo, "sdf")
+        p.take(",")
         cutoff = p.number()
         p.take(")")
         structs = ref.structures if ref.structures is not None else [ref.indices()]
@@ -668,10 +801,16 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
         if len(sizes) != 1 or 0 in sizes:
             raise ScriptError(f"{name}: sdf reference structures must be non-empty and of equal size, got sizes {sorted(sizes)}")
         st = np.stack([np.asarray(s, np.int32) for s in structs])
-        if sh is not None and tg.size == 0:
+        if (sh is not None or terms is not None) and tg.size == 0:
             raise ScriptError(f"{name}: empty selection")
 
         def commit():
+            if terms is not None:
+                ir.add_sdf_shell_expr(name, st, tg, cutoff, [(t["ref"], t["rmin"], t["rmax"]) for t in terms], truth)
+                info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff, terms=terms, truth=truth)
+                if sh is not None:
+                    info[name]["target_shell"] = sh
+                return
             if sh is None:
                 ir.add_sdf(name, st, tg, cutoff)
                 info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff)
@@ -757,16 +896,18 @@ def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=Fa
 
 
 def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
-                          shell_sdf=False):
+                          shell_sdf=False, shell_expr=False):
     """The same front-end in C++ (vmd_ir_compile_from_source, viamd_amd/csrc/vmd_script.cpp): what a C / C++ host calls.
     Returns a ScriptIR; raises ScriptError with the library's message.  angles=True: vmd_ir_compile_from_source_ex with
     VMD_SCRIPT_FEATURE_ANGLES; shape=True: with VMD_SCRIPT_FEATURE_SHAPE; rmsd=True: with VMD_SCRIPT_FEATURE_RMSD; within=True: with
-    VMD_SCRIPT_FEATURE_WITHIN; shell_rdf=True: with VMD_SCRIPT_FEATURE_SHELL_RDF; shell_sdf=True: with VMD_SCRIPT_FEATURE_SHELL_SDF."""
+    VMD_SCRIPT_FEATURE_WITHIN; shell_rdf=True: with VMD_SCRIPT_FEATURE_SHELL_RDF; shell_sdf=True: with VMD_SCRIPT_FEATURE_SHELL_SDF;
+    shell_expr=True: with VMD_SCRIPT_FEATURE_SHELL_EXPR."""
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
     features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0) | \
-        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0) | (FEATURE_SHELL_SDF if shell_sdf else 0)
+        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0) | (FEATURE_SHELL_SDF if shell_sdf else 0) | \
+        (FEATURE_SHELL_EXPR if shell_expr else 0)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
