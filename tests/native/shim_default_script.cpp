@@ -1,109 +1,42 @@
-// tests/native/shim_default_script.cpp - VIAMD's OWN default script behind the drop-in (VERDICT r04 missing #1).
+// tests/native/shim_default_script.cpp - VIAMD's OWN default script behind the drop-in, no opt-in: the fallback does real work.
 //
-// The literal string of /root/reference/src/main.cpp:528 mixes three hot-path properties (d1 = distance, r = rdf, v = sdf) with two
+// The literal string of VIAMD's src/main.cpp:528 mixes three hot-path properties (d1 = distance, r = rdf, v = sdf) with two
 // statements mdlib alone evaluates (a1 = angle(...) in resname("ALA"); {lin,plan,iso} = shape_weights(all)).  VIAMD evaluates every
 // property of the IR in ONE md_script_eval_frame_range (:993-997) and asks md_script_eval_property_data for every name of
 // md_script_ir_property_names (:1277-1291); a property that comes back NULL silently disappears from the timeline (:1288-1291).
-// include/vmd_md_script_shim.h therefore decorates mdlib's evaluator instead of replacing it: here mdlib is the CPU mock of
-// tests/native/md_mock_eval.h behind VMD_SHIM_FALLBACK(name) = mockmd_##name, and the program checks, through the md_* names only:
+// include/vmd_md_script_shim.h therefore decorates mdlib's evaluator instead of replacing it.  The host (system, trajectory, topology),
+// the script's literal, the fallback hooks (mdlib is the CPU mock of md_mock_eval.h) and the comparison with a direct evaluation are
+// shim_default_script_host.h's, shared with the seven opt-in programs; the flow below is this program's own - two evals driven by pool
+// threads as VIAMD drives them - and checks, through the md_* names only:
 //   * all of d1, a1, r, v, lin, plan, iso come back through md_script_eval_property_data; s1 (a selection, no property) gets mdlib's NULL
 //   * d1 / r / v are bit-identical to direct vmd_* calls and are NOT the fallback's CPU copies; a1 / lin / plan / iso are the mock's values
 //   * md_script_eval_ir_fingerprint == md_script_ir_fingerprint(ir) (:987), perturbed once the GPU binding of the ir changes
 //   * frame_mask = AND of the two evaluators' masks; interrupt, clear_data and free reach both
 //   * with the reduced script (vmd_script_report_fallback_source) bound as the fallback's IR nothing is evaluated twice
+//   * the work threshold (vmd_shim_set_min_work) decides between the GPU and the fallback alone
 //   * a script without any hot-path statement runs on the fallback alone; mdlib's own vis payloads are forwarded
-// Prints "OK ..." and exits 0.
-#include <algorithm>
-#include <atomic>
+// Prints "OK ..." and exits 0.  Built with -DVMD_SHIM_DEFERRED_SETTLE it waits for the helper thread's settle where VIAMD would poll.
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <thread>
-#include <vector>
 
-#include "md_mock.h"
-#include "md_mock_eval.h"
-#define VMD_SHIM_FALLBACK(name) mockmd_##name
-#define VMD_SHIM_FALLBACK_DECLARED
-#define VMD_SHIM_PREFIX(name) name
-#include "vmd_md_script_shim.h"
-
-static void fail(const char* what) {
-    std::fprintf(stderr, "FAIL: %s (%s)\n", what, vmd_last_error());
-    std::exit(1);
-}
-
-struct MockTraj { size_t F, N; float L; std::vector<float> xyz; };
-static bool mock_get_header(void* inst, md_trajectory_header_t* h) { MockTraj* t = (MockTraj*)inst; h->num_frames = t->F; h->num_atoms = t->N; return true; }
-static bool mock_load_frame(void* inst, int64_t idx, md_trajectory_frame_header_t* h, float* x, float* y, float* z) {
-    MockTraj* t = (MockTraj*)inst;
-    if (idx < 0 || (size_t)idx >= t->F) return false;
-    const float* f = t->xyz.data() + (size_t)idx * 3 * t->N;
-    if (x) memcpy(x, f, t->N * sizeof(float));
-    if (y) memcpy(y, f + t->N, t->N * sizeof(float));
-    if (z) memcpy(z, f + 2 * t->N, t->N * sizeof(float));
-    if (h) { h->num_atoms = t->N; h->index = idx; h->timestamp = (double)idx; h->unitcell = md_unitcell_t{t->L, t->L, t->L, 0, 0, 0, 7u}; }
-    return true;
-}
-
-// the literal of /root/reference/src/main.cpp:528
-static const char* kDefaultScript =
-    "s1 = resname(\"ALA\")[2:8];\nd1 = distance(10,30);\na1 = angle(2,1,3) in resname(\"ALA\");\nr = rdf(element('C'), element('H'), 10.0);\nv = sdf(s1, element('H'), 10.0);\n{lin,plan,iso} = shape_weights(all);";
+#include "shim_default_script_host.h"
 
 int main(int argc, char** argv) {
-    const size_t F = argc > 1 ? (size_t)std::atoi(argv[1]) : 16;
-    const size_t n_res = 20, n_blob = n_res * 10, N = n_blob + 933 * 3;
-    const float L = 40.0f;
-    if (vmd_device_count() <= 0) fail("no HIP device");
-    if (vmd_shim_min_work() != VMD_SHIM_MIN_WORK_DEFAULT) fail("default work threshold");
-    vmd_shim_set_min_work(0);                     // this test system is far below the default threshold: send what is bound to the GPU (both sides: below)
-
-    MockTraj mt{F, N, L, std::vector<float>(F * 3 * N)};
-    {
-        vmd_devtraj_t* dt = vmd_devtraj_create(F, N);
-        if (!dt || !vmd_devtraj_synth(dt, 21, L, 0.05f, 0, 0, F)) fail("synth");
-        vmd_trajectory_i* ti = vmd_devtraj_interface(dt);
-        for (size_t f = 0; f < F; ++f) { float* p = mt.xyz.data() + f * 3 * N; if (!ti->load_frame(ti->inst, (int64_t)f, nullptr, p, p + N, p + 2 * N)) fail("download"); }
-        vmd_devtraj_free(dt);
-    }
-    md_trajectory_i traj_i{&mt, mock_get_header, mock_load_frame};
-    std::vector<float> sx(N), sy(N), sz(N), mass(N, 1.0f);
-    md_system_t sys{};
-    sys.atom.count = N; sys.atom.x = sx.data(); sys.atom.y = sy.data(); sys.atom.z = sz.data(); sys.atom.mass = mass.data();
-    sys.unitcell = md_unitcell_t{L, L, L, 0, 0, 0, 7u};
-    sys.trajectory = &traj_i;
-
-    // the molecule's topology: 20 ALA residues of 10 atoms (N C C O C H H H C H), then waters - what selections resolve against
-    static const char* ala[10] = {"N", "C", "C", "O", "C", "H", "H", "H", "C", "H"};
-    std::vector<const char*> elements(N), resnames(N);
-    std::vector<int32_t> residue_index(N);
-    for (size_t i = 0; i < N; ++i) {
-        if (i < n_blob) { elements[i] = ala[i % 10]; resnames[i] = "ALA"; residue_index[i] = (int32_t)(i / 10); }
-        else { const size_t w = i - n_blob; elements[i] = w % 3 == 0 ? "O" : "H"; resnames[i] = "HOH"; residue_index[i] = (int32_t)(n_res + w / 3); }
-    }
-    vmd_topology_t topo{N, elements.data(), nullptr, resnames.data(), residue_index.data(), nullptr};
-    auto residues_of = [&](const std::string& resname) {
-        std::vector<std::vector<int32_t>> out;
-        for (size_t i = 0; i < N; ++i) {
-            if (resname != resnames[i]) continue;
-            if (out.empty() || residue_index[(size_t)out.back().back()] != residue_index[i]) out.emplace_back();
-            out.back().push_back((int32_t)i);
-        }
-        return out;
-    };
+    ShimHost h(ShimHost::frames_arg(argc, argv, 16));
+    const size_t F = h.F, N = h.N, n_res = h.n_res;
+    md_system_t& sys = h.sys;
+    md_allocator_i& persistent = h.persistent;
 
     // ---- "md_script_ir_compile_from_source" (src/main.cpp:878): mdlib compiles the whole script ...
-    md_script_ir_t* eval_ir = mock_ir_compile(kDefaultScript, residues_of);
+    md_script_ir_t* eval_ir = shim_mock_compile(h, kDefaultScript);
     if (!eval_ir || md_script_ir_property_count(eval_ir) != 7) fail("mock mdlib: the default script has seven properties");
     // ... and the backend takes what it evaluates: d1, r, v.  The rest is reported, not refused (vmd_ir_compile_from_source_partial)
     vmd_script_ir_t* vir = vmd_ir_create();
     vmd_script_report_t* report = nullptr;
-    if (!vmd_ir_compile_from_source_partial(vir, kDefaultScript, &topo, &report)) fail("vmd_ir_compile_from_source_partial");
+    if (!vmd_ir_compile_from_source_partial(vir, kDefaultScript, &h.topo, &report)) fail("vmd_ir_compile_from_source_partial");
     if (vmd_ir_property_count(vir) != 3 || vmd_script_report_skipped_count(report) != 2) fail("d1, r, v compiled; a1 and {lin,plan,iso} reported");
     if (strcmp(vmd_script_report_skipped(report)[0].names, "a1") != 0 || strcmp(vmd_script_report_skipped(report)[1].names, "lin,plan,iso") != 0) fail("skipped names");
     vmd_shim_bind_ir(eval_ir, vir);
-    md_allocator_i persistent{nullptr};
 
     // ---- src/main.cpp:966-972, 1275-1316
     md_script_eval_t* full_eval = md_script_eval_create(F, eval_ir, &persistent);
@@ -176,18 +109,11 @@ int main(int argc, char** argv) {
     settled(filt_eval, end_frame - beg_frame);
 
     // ---- what VIAMD then reads: the hot-path properties = direct vmd_* calls, bit for bit; the others = mdlib's (the mock's) own values
-    auto prop = [&](const md_script_eval_t* e, const char* nm) { return md_script_eval_property_data(e, str_t{nm, strlen(nm)}); };
     {
-        vmd_script_eval_t* e = vmd_eval_create(F, vir);
-        vmd_system_t vsys = vmd_shim::wrap_system(&sys);
-        vmd_trajectory_i vt = vmd_shim::wrap_trajectory(&traj_i);
-        if (!e || !vmd_eval_frame_range(e, vir, &vsys, &vt, 0, (uint32_t)F)) fail("direct evaluation");
-        if (!vmd_eval_wait_settled(e)) fail("direct evaluation: settle");       // (a no-op unless the process runs in deferred-settle mode)
+        vmd_script_eval_t* e = shim_compare_with_direct(h, vir, full_eval, {"d1", "r", "v"});
         for (const char* nm : {"d1", "r", "v"}) {
             const vmd_script_property_data_t* want = vmd_eval_property_data(e, nm);
-            const md_script_property_data_t* got = prop(full_eval, nm);
-            if (!want || got->num_values != want->num_values || memcmp(got->values, want->values, want->num_values * sizeof(float)) != 0) fail("d1 / r / v through the shim differ from direct vmd_* calls");
-            for (size_t i = 0; i < got->num_values; ++i) if (got->values[i] == MOCK_CPU_COPY) fail("the shim handed out the fallback's CPU copy of a bound property");
+            const md_script_property_data_t* got = shim_prop(full_eval, nm);
             if (got->weights && (!want->weights || memcmp(got->weights, want->weights, (size_t)want->dim[2] * sizeof(float)) != 0)) fail("rdf weights");
         }
         vmd_eval_free(e);
@@ -196,20 +122,20 @@ int main(int argc, char** argv) {
     {
         std::vector<float> x(N), y(N), z(N), row(64);
         for (size_t f = 0; f < F; ++f) {
-            mock_load_frame(&mt, (int64_t)f, nullptr, x.data(), y.data(), z.data());
+            mock_load_frame(&h.mt, (int64_t)f, nullptr, x.data(), y.data(), z.data());
             for (const MockProp& p : eval_ir->props) {
                 if (p.kind == MockProp::CPU_COPY) continue;
                 mock_eval_row(p, x.data(), y.data(), z.data(), N, row.data());
                 for (int which = 0; which < 2; ++which) {
                     if (which == 1 && (f < beg_frame || f >= end_frame)) continue;
-                    const md_script_property_data_t* got = prop(evals[which], p.name.c_str());
+                    const md_script_property_data_t* got = shim_prop(evals[which], p.name.c_str());
                     if (got->dim[0] != (int32_t)F || got->dim[1] != (int32_t)p.width()) fail("temporal layout of a fallback property (src/main.cpp:1353-1378)");
                     if (memcmp(got->values + f * p.width(), row.data(), p.width() * sizeof(float)) != 0) fail("a1 / lin / plan / iso are not the fallback evaluator's values");
                 }
                 if (p.kind == MockProp::ANGLE) for (size_t c = 0; c < p.width(); ++c) a1_sum += row[c];
             }
         }
-        if (prop(full_eval, "a1")->dim[1] != (int32_t)n_res) fail("angle(...) in resname(\"ALA\"): one value per residue");
+        if (shim_prop(full_eval, "a1")->dim[1] != (int32_t)n_res) fail("angle(...) in resname(\"ALA\"): one value per residue");
     }
     // both evaluators have every frame of their range: the AND of the masks is the range
     for (int which = 0; which < 2; ++which) {
@@ -240,7 +166,7 @@ int main(int argc, char** argv) {
     {
         const char* reduced_text = vmd_script_report_fallback_source(report);
         if (strlen(reduced_text) != strlen(kDefaultScript)) fail("fallback source keeps the offsets of the editor's text");
-        md_script_ir_t* reduced = mock_ir_compile(reduced_text, residues_of);
+        md_script_ir_t* reduced = shim_mock_compile(h, reduced_text);
         if (!reduced || md_script_ir_property_count(reduced) != 4) fail("the reduced script has a1, lin, plan, iso");
         vmd_shim_bind_fallback_ir(eval_ir, reduced);
         md_script_eval_t* e = md_script_eval_create(F, eval_ir, &persistent);
@@ -295,7 +221,7 @@ int main(int argc, char** argv) {
         const uint64_t work = vmd_ir_work_per_frame(vir) * (uint64_t)F;
         // d1: 1 pair; r: |C| x |H|; v: 7 structures (residues 2..8 of ALA, 10 atoms each) x (|H| + 10)
         size_t nC = 0, nH = 0;
-        for (size_t i = 0; i < N; ++i) { nC += elements[i][0] == 'C'; nH += elements[i][0] == 'H'; }
+        for (size_t i = 0; i < N; ++i) { nC += h.elements[i][0] == 'C'; nH += h.elements[i][0] == 'H'; }
         if (work != (1 + (uint64_t)nC * nH + 7 * ((uint64_t)nH + 10)) * F) fail("vmd_ir_work_per_frame of the default script");
         vmd_shim_set_min_work(work + 1);                                   // just too small
         md_script_eval_t* small = md_script_eval_create(F, eval_ir, &persistent);
@@ -304,10 +230,10 @@ int main(int argc, char** argv) {
         md_script_eval_clear_data(small);
         if (!md_script_eval_frame_range(small, eval_ir, &sys, sys.trajectory, 0, (uint32_t)F)) fail("below the threshold: frame_range");
         for (const char* nm : {"d1", "r", "v"}) {
-            const md_script_property_data_t* rec = prop(small, nm);
+            const md_script_property_data_t* rec = shim_prop(small, nm);
             if (!rec || rec->values[0] != MOCK_CPU_COPY) fail("below the threshold: d1 / r / v are the fallback evaluator's own");
         }
-        if (memcmp(prop(small, "a1")->values, prop(full_eval, "a1")->values, prop(small, "a1")->num_values * sizeof(float)) != 0) fail("below the threshold: a1");
+        if (memcmp(shim_prop(small, "a1")->values, shim_prop(full_eval, "a1")->values, shim_prop(small, "a1")->num_values * sizeof(float)) != 0) fail("below the threshold: a1");
         if (md_bitfield_popcount(md_script_eval_frame_mask(small)) != F) fail("below the threshold: frame mask");
         md_script_eval_free(small);
         vmd_shim_set_min_work(work);                                       // exactly enough
@@ -319,14 +245,14 @@ int main(int argc, char** argv) {
 
     // ---- a script without any hot-path statement: nothing is bound, the fallback evaluates it alone
     {
-        md_script_ir_t* only = mock_ir_compile("a1 = angle(2,1,3) in resname(\"ALA\");", residues_of);
+        md_script_ir_t* only = shim_mock_compile(h, "a1 = angle(2,1,3) in resname(\"ALA\");");
         md_script_eval_t* e = md_script_eval_create(F, only, &persistent);
         if (!e || e->eval) fail("an ir without bound properties runs on the fallback alone");
         if (md_script_eval_ir_fingerprint(e) != md_script_ir_fingerprint(only)) fail("fingerprint (fallback alone)");
         md_script_eval_clear_data(e);
         if (!md_script_eval_frame_range(e, only, &sys, sys.trajectory, 0, (uint32_t)F)) fail("frame_range (fallback alone)");
         const md_script_property_data_t* a = md_script_eval_property_data(e, STR_LIT("a1"));
-        if (!a || memcmp(a->values, prop(full_eval, "a1")->values, a->num_values * sizeof(float)) != 0) fail("a1 (fallback alone)");
+        if (!a || memcmp(a->values, shim_prop(full_eval, "a1")->values, a->num_values * sizeof(float)) != 0) fail("a1 (fallback alone)");
         if (md_bitfield_popcount(md_script_eval_frame_mask(e)) != F) fail("frame mask (fallback alone)");
         md_script_eval_free(e);
         md_script_ir_free(only);

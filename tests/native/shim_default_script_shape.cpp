@@ -1,173 +1,33 @@
 // tests/native/shim_default_script_shape.cpp - VIAMD's default script behind the drop-in with BOTH host opt-ins on.
 //
-// The host compiles with vmd_ir_compile_from_source_ex(..., VMD_SCRIPT_FEATURE_ANGLES | VMD_SCRIPT_FEATURE_SHAPE, &report): every property
-// statement of the script (src/main.cpp:528) is the GPU's - d1, a1, r, v, lin, plan, iso - and the text left for mdlib (here the CPU mock
-// of md_mock_eval.h behind VMD_SHIM_FALLBACK) holds the selection `s1 = ...;` alone.  The program checks, through the md_* names:
-//   * the backend compiles seven properties and reports nothing skipped; the fallback text keeps no property statement
-//   * all seven properties of mdlib's IR come back through md_script_eval_property_data, bit-identical to direct vmd_* calls
-//   * lin / plan / iso are the GPU's: Westin's measures (each in [0, 1], summing to 1), not the mock's sorted coordinate variances
-//   * the fallback does no per-frame work: no call reaches its frame_range hook, it evaluates no frame, and the frame mask is complete
+// The host compiles with VMD_SCRIPT_FEATURE_ANGLES | VMD_SCRIPT_FEATURE_SHAPE: every property statement of the script is the GPU's - d1,
+// a1, r, v, lin, plan, iso - and the text left for mdlib holds the selection `s1 = ...;` alone, so the fallback is idle.  The host, the
+// script and the common sequence (compile and split, drive, compare with a direct evaluation, interrupt, tear down) are
+// shim_default_script_host.h's; this file holds the program's data and what is shape_weights' own:
+//   * lin / plan / iso are the GPU's: Westin's measures (each in [0, 1], summing to 1, no unit), not the mock's sorted coordinate variances
 //   * the MD_SCRIPT_VISUALIZE_ATOMS payload of lin marks the selection (all atoms)
 // Prints "OK frames=<F> properties=7 a1=gpu lin=gpu ..." and exits 0.
-#include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "md_mock.h"
-#include "md_mock_eval.h"
+#include "shim_default_script_host.h"
 
-// the fallback hooks: the mock's, with a counter in front of frame_range
-static std::atomic<long> g_fallback_frame_range_calls{0};
-#define countfb_md_script_eval_create mockmd_md_script_eval_create
-#define countfb_md_script_eval_free mockmd_md_script_eval_free
-#define countfb_md_script_eval_clear_data mockmd_md_script_eval_clear_data
-#define countfb_md_script_eval_interrupt mockmd_md_script_eval_interrupt
-#define countfb_md_script_eval_ir_fingerprint mockmd_md_script_eval_ir_fingerprint
-#define countfb_md_script_eval_property_data mockmd_md_script_eval_property_data
-#define countfb_md_script_eval_frame_mask mockmd_md_script_eval_frame_mask
-#define countfb_md_script_ir_property_vis_payload mockmd_md_script_ir_property_vis_payload
-#define countfb_md_script_vis_eval_payload mockmd_md_script_vis_eval_payload
-static inline bool countfb_md_script_eval_frame_range(vmd_shim_fallback_eval_t* e, const md_script_ir_t* ir, const md_system_t* sys, md_trajectory_i* traj,
-                                                      uint32_t frame_beg, uint32_t frame_end) {
-    g_fallback_frame_range_calls += 1;
-    return mockmd_md_script_eval_frame_range(e, ir, sys, traj, frame_beg, frame_end);
-}
-#define VMD_SHIM_FALLBACK(name) countfb_##name
-#define VMD_SHIM_FALLBACK_DECLARED
-#define VMD_SHIM_PREFIX(name) name
-#include "vmd_md_script_shim.h"
-
-static void fail(const char* what) {
-    std::fprintf(stderr, "FAIL: %s (%s)\n", what, vmd_last_error());
-    std::exit(1);
-}
-
-struct MockTraj { size_t F, N; float L; std::vector<float> xyz; };
-static bool mock_get_header(void* inst, md_trajectory_header_t* h) { MockTraj* t = (MockTraj*)inst; h->num_frames = t->F; h->num_atoms = t->N; return true; }
-static bool mock_load_frame(void* inst, int64_t idx, md_trajectory_frame_header_t* h, float* x, float* y, float* z) {
-    MockTraj* t = (MockTraj*)inst;
-    if (idx < 0 || (size_t)idx >= t->F) return false;
-    const float* f = t->xyz.data() + (size_t)idx * 3 * t->N;
-    if (x) memcpy(x, f, t->N * sizeof(float));
-    if (y) memcpy(y, f + t->N, t->N * sizeof(float));
-    if (z) memcpy(z, f + 2 * t->N, t->N * sizeof(float));
-    if (h) { h->num_atoms = t->N; h->index = idx; h->timestamp = (double)idx; h->unitcell = md_unitcell_t{t->L, t->L, t->L, 0, 0, 0, 7u}; }
-    return true;
-}
-
-// the literal of VIAMD's src/main.cpp:528
-static const char* kDefaultScript =
-    "s1 = resname(\"ALA\")[2:8];\nd1 = distance(10,30);\na1 = angle(2,1,3) in resname(\"ALA\");\nr = rdf(element('C'), element('H'), 10.0);\nv = sdf(s1, element('H'), 10.0);\n{lin,plan,iso} = shape_weights(all);";
+static const ShimProgram kProgram = {"", 7, nullptr, nullptr, {{"r", "rdf"}, {"v", "sdf"}}};     // (no other rdf / sdf line: the bare names are gone too)
+static const ShimExpect kBoth = {VMD_SCRIPT_FEATURE_ANGLES | VMD_SCRIPT_FEATURE_SHAPE, {"d1", "a1", "r", "v", "lin", "plan", "iso"}, {}};
 
 int main(int argc, char** argv) {
-    const size_t F = argc > 1 ? (size_t)std::atoi(argv[1]) : 24;
-    const size_t n_res = 20, n_blob = n_res * 10, N = n_blob + 933 * 3;
-    const float L = 40.0f;
-    if (vmd_device_count() <= 0) fail("no HIP device");
-    vmd_shim_set_min_work(0);                     // this test system is far below the default threshold: send what is bound to the GPU
+    ShimHost h(ShimHost::frames_arg(argc, argv, 24));
+    const size_t F = h.F, N = h.N;
+    ShimRun run = shim_compile_and_split(h, kProgram, kBoth);
+    shim_create_and_drive(h, run, kBoth);
 
-    MockTraj mt{F, N, L, std::vector<float>(F * 3 * N)};
-    {
-        vmd_devtraj_t* dt = vmd_devtraj_create(F, N);
-        if (!dt || !vmd_devtraj_synth(dt, 21, L, 0.05f, 0, 0, F)) fail("synth");
-        vmd_trajectory_i* ti = vmd_devtraj_interface(dt);
-        for (size_t f = 0; f < F; ++f) { float* p = mt.xyz.data() + f * 3 * N; if (!ti->load_frame(ti->inst, (int64_t)f, nullptr, p, p + N, p + 2 * N)) fail("download"); }
-        vmd_devtraj_free(dt);
-    }
-    md_trajectory_i traj_i{&mt, mock_get_header, mock_load_frame};
-    std::vector<float> sx(N), sy(N), sz(N), mass(N, 1.0f);
-    md_system_t sys{};
-    sys.atom.count = N; sys.atom.x = sx.data(); sys.atom.y = sy.data(); sys.atom.z = sz.data(); sys.atom.mass = mass.data();
-    sys.unitcell = md_unitcell_t{L, L, L, 0, 0, 0, 7u};
-    sys.trajectory = &traj_i;
-
-    // the molecule's topology: 20 ALA residues of 10 atoms (N C C O C H H H C H), then waters - what selections resolve against
-    static const char* ala[10] = {"N", "C", "C", "O", "C", "H", "H", "H", "C", "H"};
-    std::vector<const char*> elements(N), resnames(N);
-    std::vector<int32_t> residue_index(N);
-    for (size_t i = 0; i < N; ++i) {
-        if (i < n_blob) { elements[i] = ala[i % 10]; resnames[i] = "ALA"; residue_index[i] = (int32_t)(i / 10); }
-        else { const size_t w = i - n_blob; elements[i] = w % 3 == 0 ? "O" : "H"; resnames[i] = "HOH"; residue_index[i] = (int32_t)(n_res + w / 3); }
-    }
-    vmd_topology_t topo{N, elements.data(), nullptr, resnames.data(), residue_index.data(), nullptr};
-    auto residues_of = [&](const std::string& resname) {
-        std::vector<std::vector<int32_t>> out;
-        for (size_t i = 0; i < N; ++i) {
-            if (resname != resnames[i]) continue;
-            if (out.empty() || residue_index[(size_t)out.back().back()] != residue_index[i]) out.emplace_back();
-            out.back().push_back((int32_t)i);
-        }
-        return out;
-    };
-
-    md_script_ir_t* eval_ir = mock_ir_compile(kDefaultScript, residues_of);
-    if (!eval_ir || md_script_ir_property_count(eval_ir) != 7) fail("mock mdlib: the default script has seven properties");
-    // both opt-ins: the whole script is compiled for the GPU
-    vmd_script_ir_t* vir = vmd_ir_create();
-    vmd_script_report_t* report = nullptr;
-    if (!vmd_ir_compile_from_source_ex(vir, kDefaultScript, &topo, VMD_SCRIPT_FEATURE_ANGLES | VMD_SCRIPT_FEATURE_SHAPE, &report)) fail("vmd_ir_compile_from_source_ex");
-    if (vmd_ir_property_count(vir) != 7 || vmd_script_report_skipped_count(report) != 0) fail("seven properties compiled, nothing skipped");
-    static const char* const want_names[7] = {"d1", "a1", "r", "v", "lin", "plan", "iso"};
-    for (size_t i = 0; i < 7; ++i) if (strcmp(vmd_ir_property_names(vir)[i], want_names[i]) != 0) fail("property order d1, a1, r, v, lin, plan, iso");
-    const std::string reduced_text = vmd_script_report_fallback_source(report);
-    vmd_script_report_free(report);
-    if (reduced_text.size() != strlen(kDefaultScript)) fail("fallback source keeps the offsets of the editor's text");
-    for (const char* gone : {"distance", "angle", "rdf", "sdf", "shape_weights", "lin"})
-        if (reduced_text.find(gone) != std::string::npos) fail("the fallback text still holds a property statement");
-    if (reduced_text.find("s1 = resname(\"ALA\")[2:8];") != 0) fail("the fallback text keeps the selection");
-    // what mdlib compiles from that text: no property at all
-    md_script_ir_t* reduced = mock_ir_compile(reduced_text.c_str(), residues_of);
-    if (!reduced || md_script_ir_property_count(reduced) != 0) fail("the reduced script holds no property");
-    vmd_shim_bind_ir(eval_ir, vir);
-    vmd_shim_bind_fallback_ir(eval_ir, reduced);
-    md_allocator_i persistent{nullptr};
-
-    md_script_eval_t* ev = md_script_eval_create(F, eval_ir, &persistent);
-    if (!ev) fail("md_script_eval_create");
-    if (!ev->fb || ev->fb->ir != reduced) fail("the fallback eval must be created from the reduced ir");
-    if (md_script_eval_ir_fingerprint(ev) != md_script_ir_fingerprint(eval_ir)) fail("fingerprint: still the editor's script (src/main.cpp:987)");
-    md_script_eval_clear_data(ev);
-    for (uint32_t f = 0; f < (uint32_t)F; f += 3)
-        if (!md_script_eval_frame_range(ev, eval_ir, &sys, sys.trajectory, f, std::min<uint32_t>(f + 3, (uint32_t)F))) fail("frame_range");
-    if (!vmd_eval_wait_settled(ev->eval)) fail("settle");
-    // no second evaluator walked the frames
-    if (g_fallback_frame_range_calls.load() != 0) fail("a call reached the fallback's frame_range although its ir holds no property");
-    if (ev->fb->frames_evaluated.load() != 0) fail("the fallback evaluated frames");
-    const md_bitfield_t* fm = md_script_eval_frame_mask(ev);
-    if (!fm) fail("frame mask");
-    for (size_t f = 0; f < F; ++f) if (!md_bitfield_test_bit(fm, f)) fail("the frame mask is the GPU evaluator's alone: every frame done");
-
-    const size_t num_props = md_script_ir_property_count(eval_ir);
-    const str_t* prop_names = md_script_ir_property_names(eval_ir);
-    for (size_t i = 0; i < num_props; ++i)
-        if (!md_script_eval_property_data(ev, prop_names[i])) fail("a property of the default script disappeared behind the drop-in");
-    auto prop = [&](const char* nm) { return md_script_eval_property_data(ev, str_t{nm, strlen(nm)}); };
-
-    // all seven are the GPU's: bit-identical to a direct evaluation of the backend's IR
-    {
-        vmd_script_eval_t* e = vmd_eval_create(F, vir);
-        vmd_system_t vsys = vmd_shim::wrap_system(&sys);
-        vmd_trajectory_i vt = vmd_shim::wrap_trajectory(&traj_i);
-        if (!e || !vmd_eval_frame_range(e, vir, &vsys, &vt, 0, (uint32_t)F) || !vmd_eval_wait_settled(e)) fail("direct evaluation");
-        for (const char* nm : want_names) {
-            const vmd_script_property_data_t* want = vmd_eval_property_data(e, nm);
-            const md_script_property_data_t* got = prop(nm);
-            if (!want || got->num_values != want->num_values || memcmp(got->values, want->values, want->num_values * sizeof(float)) != 0) fail("a property through the shim differs from direct vmd_* calls");
-            for (size_t k = 0; k < got->num_values; ++k) if (got->values[k] == MOCK_CPU_COPY) fail("the shim handed out the fallback's copy of a bound property");
-        }
-        if (strcmp(vmd_eval_property_data(e, "lin")->unit_str[1], "") != 0) fail("lin has no unit");
-        vmd_eval_free(e);
-    }
+    vmd_script_eval_t* e = shim_compare_with_direct(h, run.vir, run.ev, kBoth.gpu_names);
+    if (strcmp(vmd_eval_property_data(e, "lin")->unit_str[1], "") != 0) fail("lin has no unit");
+    vmd_eval_free(e);
     // lin / plan / iso: Westin's measures of the covariance matrix, not the mock's formula
     double worst_sum = 0.0;
     size_t differ = 0;
     {
-        const md_script_property_data_t* w[3] = {prop("lin"), prop("plan"), prop("iso")};
+        const md_script_property_data_t* w[3] = {shim_prop(run.ev, "lin"), shim_prop(run.ev, "plan"), shim_prop(run.ev, "iso")};
         std::vector<float> x(N), y(N), z(N);
         for (int k = 0; k < 3; ++k) if (w[k]->dim[0] != (int32_t)F || w[k]->dim[1] != 1 || w[k]->num_values != F) fail("lin / plan / iso: one value per frame");
         for (size_t f = 0; f < F; ++f) {
@@ -175,7 +35,7 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 3; ++k) { const float v = w[k]->values[f]; if (!(v >= 0.0f && v <= 1.0f)) fail("a weight outside [0, 1]"); sum += (double)v; }
             worst_sum = std::max(worst_sum, std::fabs(sum - 1.0));
             float mock[3];
-            mock_load_frame(&mt, (int64_t)f, nullptr, x.data(), y.data(), z.data());
+            mock_load_frame(&h.mt, (int64_t)f, nullptr, x.data(), y.data(), z.data());
             mock_shape(x.data(), y.data(), z.data(), N, mock);
             for (int k = 0; k < 3; ++k) differ += w[k]->values[f] != mock[k];
         }
@@ -183,29 +43,9 @@ int main(int argc, char** argv) {
         if (differ == 0) fail("lin / plan / iso are the mock's values");
     }
     // the ATOMS payload of lin: the selection
-    {
-        md_allocator_i frame_alloc{nullptr};
-        md_script_vis_ctx_t ctx = {eval_ir, &sys, sys.trajectory};
-        const md_script_vis_payload_o* payload = md_script_ir_property_vis_payload(eval_ir, STR_LIT("lin"));
-        if (!payload) fail("md_script_ir_property_vis_payload(lin)");
-        md_script_vis_t vis = {};
-        md_script_vis_init(&vis, &frame_alloc);
-        if (!md_script_vis_eval_payload(&vis, payload, -1, &ctx, MD_SCRIPT_VISUALIZE_ATOMS)) fail("vis payload of lin");
-        if (md_bitfield_popcount(&vis.atom_mask) != N) fail("lin highlights every atom of `all`");
-        md_script_vis_free(&vis);
-    }
-    // interrupt / clear_data still reach both evaluators
-    md_script_eval_interrupt(ev);
-    if (ev->fb->interrupts.load() != 1) fail("interrupt was not forwarded to the fallback");
-    md_script_eval_clear_data(ev);
-    if (!md_script_eval_frame_range(ev, eval_ir, &sys, sys.trajectory, 0, 2)) fail("frame_range after interrupt + clear_data");
-    if (g_fallback_frame_range_calls.load() != 0) fail("a call reached the fallback's frame_range after clear_data");
-    md_script_eval_free(ev);
-    vmd_shim_bind_fallback_ir(eval_ir, nullptr);
-    vmd_shim_bind_ir(eval_ir, nullptr);
-    vmd_ir_free(vir);
-    md_script_ir_free(reduced);
-    md_script_ir_free(eval_ir);
+    if (shim_count(shim_atoms_payload(h, run.eval_ir, "lin", -1)) != N) fail("lin highlights every atom of `all`");
+    shim_interrupt_and_restart(h, run, kBoth);
+    shim_tear_down(run);
     std::printf("OK frames=%zu properties=7 a1=gpu lin=gpu fallback_frame_range_calls=0 sum_error=%.3g\n", F, worst_sum);
     return 0;
 }

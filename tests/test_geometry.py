@@ -2,11 +2,12 @@
 independent restatement tests/geometry_ref.py, ABI validation, the opt-in script front-end (C++ and Python twin), VIAMD's call pattern
 (pool threads, interrupt / clear_data, multi-rank merges), export, and VIAMD's default script through the shim."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -15,8 +16,6 @@ from viamd_amd import script, synth
 import geometry_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_ANGLES_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_angles.cpp")
-SHIM_ANGLES_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_angles")
 
 VIAMD_DEFAULT_SCRIPT = ("s1 = resname(\"ALA\")[2:8];\nd1 = distance(10,30);\na1 = angle(2,1,3) in resname(\"ALA\");\n"
                         "r = rdf(element('C'), element('H'), 10.0);\nv = sdf(s1, element('H'), 10.0);\n{lin,plan,iso} = shape_weights(all);")
@@ -573,32 +572,12 @@ def test_export_labels_the_unit(emu_lib, oracle, tmp_path):
 
 # ---- VIAMD's default script through the shim, angles opted in ----------------------------------------------------------------------
 
-def build_shim_angles(lib_path=None):
-    """tests/native/shim_default_script_angles.cpp linked against the product library (or `lib_path`, e.g. the emulator build)"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    if lib_path:
-        out = lib_path + ".shim_angles"
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_ANGLES_SRC] + inc + [lib_path, "-Wl,-rpath," + os.path.dirname(lib_path),
-                               "-lpthread", "-o", out])
-        return out
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_ANGLES_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_ANGLES_EXE) and os.path.getmtime(SHIM_ANGLES_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_ANGLES_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_ANGLES_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_ANGLES_EXE])
-    return SHIM_ANGLES_EXE
+def build_shim_angles():
+    """tests/native/shim_default_script_angles.cpp linked against the product library"""
+    return native_host.build_shim("shim_default_script_angles")
 
 
 def test_shim_default_script_with_angles_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_angles_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_ANGLES_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=7 a1=gpu"), out.stdout
+    exe = native_host.build_shim("shim_default_script_angles", conftest.build_emu(), tmp_path / "shim_angles_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=7 a1=gpu")

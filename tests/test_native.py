@@ -5,33 +5,16 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "cabi_demo.cpp")
-EXE = os.path.join(ROOT, "tests", "native", "cabi_demo")
+import native_host
+from native_host import ROOT
 
 
 def build_demo():
-    from viamd_amd import build
-    lib = build.build()
-    if os.path.exists(EXE) and os.path.getmtime(EXE) >= max(os.path.getmtime(SRC), os.path.getmtime(lib)):
-        return EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", SRC, "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "viamd_amd"),
-                           "-lviamd_amd", "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib",
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread", "-o", EXE])
-    return EXE
+    return native_host.build_product("cabi_demo")
 
 
 def build_reduce_demo():
-    from viamd_amd import build
-    lib = build.build()
-    src = os.path.join(ROOT, "tests", "native", "cabi_reduce_demo.cpp")
-    exe = os.path.join(ROOT, "tests", "native", "cabi_reduce_demo")
-    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(src), os.path.getmtime(lib)):
-        return exe
-    subprocess.check_call(["g++", "-std=c++17", "-O2", src, "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "viamd_amd"),
-                           "-lviamd_amd", "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib",
-                           "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread", "-o", exe])
-    return exe
+    return native_host.build_product("cabi_reduce_demo")
 
 
 def test_native_host_builds_against_the_c_abi():
@@ -57,10 +40,7 @@ def test_native_rccl_merge_behind_the_abi(tmp_path, gpu_lib):
 
 @pytest.mark.gpu
 def test_native_host_runs_like_viamd():
-    exe = build_demo()
-    out = subprocess.run([exe, "96"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=96"), out.stdout
+    native_host.run_ok([build_demo(), "96"], "OK frames=96", timeout=300)
 
 
 @pytest.mark.parametrize("fmt", ["dcd", "xtc", "pdb"])
@@ -87,11 +67,7 @@ def test_native_host_from_dcd_and_script_text_on_the_emulator(tmp_path, emu_lib,
         V.write_xtc(dcd, coords, cell, lib=emu_lib)
     text = ("s = residue(2:4); v = sdf(s, element('O') and water, 7.0); g = rdf(element('O') and water, not element('H'), 8.0);"
             "d = distance(residue(1), residue(6)); m = distance_min(1:2, element('O')) in residue(2:5);")
-    src = os.path.join(ROOT, "tests", "native", "cabi_script_demo.cpp")
-    exe = str(tmp_path / "cabi_script_demo")
-    emu = conftest.build_emu()
-    subprocess.check_call(["g++", "-std=c++17", "-O1", src, "-I" + os.path.join(ROOT, "include"), emu, "-Wl,-rpath," + os.path.dirname(emu),
-                           "-lpthread", "-o", exe])
+    exe = native_host.build_against(conftest.build_emu(), "cabi_script_demo", tmp_path / "cabi_script_demo")
     out = subprocess.run([exe, str(dcd), str(n_blob), text], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = dict(l.split(" ", 1) for l in out.stdout.strip().split("\n"))
@@ -112,31 +88,25 @@ def test_native_host_from_dcd_and_script_text_on_the_emulator(tmp_path, emu_lib,
     np.testing.assert_allclose(got8, g8[6:8], rtol=1e-5)
 
 
-SHIM_SRC = os.path.join(ROOT, "tests", "native", "shim_callsites.cpp")
-SHIM_EXE = os.path.join(ROOT, "tests", "native", "shim_callsites")
 # C++20: the reference's export_cube uses designated initialisers (src/main.cpp:5751-5755); -Wno-format: it prints a size_t with %i (:5671)
-SHIM_FLAGS = ["-std=c++20", "-Wall", "-Wno-format", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native"),
-              "-I" + os.path.join(ROOT, "oracle")]
+SHIM_FLAGS = ["-std=c++20", "-Wall", "-Wno-format", "-Wno-unused-function", "-I" + native_host.NATIVE, "-I" + os.path.join(ROOT, "oracle")]
 
 
 def build_shim_callsites():
     """VIAMD's call sequence re-typed against a mock of mdlib's declarations, bound to libviamd_amd.so through
     include/vmd_md_script_shim.h (compiled by __graft_entry__.build() too: a boundary that stops compiling is caught without a GPU)."""
-    from viamd_amd import build
     from oracle import make_ref
-    lib = build.build()
     # the program includes the reference's export_cube VERBATIM (oracle/_ref/viamd_export_slices.inc: generated here from /root/reference,
     # travels to the GPU box in the git-ignored oracle/_ref/)
     if not make_ref.slices_available():
         # neither /root/reference nor oracle/_ref/viamd_export_slices.inc: a prebuilt program, or nothing (callers skip)
-        return SHIM_EXE if os.path.exists(SHIM_EXE) else None
-    deps = [SHIM_SRC, lib, make_ref.INC_EXPORT] + [os.path.join(ROOT, "tests", "native", h) for h in ("md_mock.h", "viamd_host_double.h")] + \
-           [os.path.join(ROOT, "include", "vmd_md_script_shim.h")]
-    if os.path.exists(SHIM_EXE) and os.path.getmtime(SHIM_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_EXE
-    subprocess.check_call(["g++"] + SHIM_FLAGS + ["-O2", SHIM_SRC, "-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd", "-L/opt/rocm/lib",
-                           "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread", "-o", SHIM_EXE])
-    return SHIM_EXE
+        from viamd_amd import build
+        build.build()
+        exe = os.path.join(native_host.NATIVE, "shim_callsites")
+        return exe if os.path.exists(exe) else None
+    deps = [make_ref.INC_EXPORT, os.path.join(native_host.INCLUDE, "vmd_md_script_shim.h")] + \
+           [os.path.join(native_host.NATIVE, h) for h in ("md_mock.h", "viamd_host_double.h")]
+    return native_host.build_product("shim_callsites", SHIM_FLAGS, deps)
 
 
 def test_md_script_shim_call_sites_on_the_emulator(tmp_path, emu_lib):
@@ -148,21 +118,15 @@ def test_md_script_shim_call_sites_on_the_emulator(tmp_path, emu_lib):
     if not make_ref.slices_available():
         pytest.skip("the program includes the reference's export_cube (oracle/_ref/viamd_export_slices.inc): neither /root/reference nor the slices are here")
     assert os.access(build_shim_callsites(), os.X_OK)                  # links against the product library
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_callsites_emu")
-    subprocess.check_call(["g++"] + SHIM_FLAGS + ["-O1", SHIM_SRC, emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "12"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=12"), out.stdout
+    exe = native_host.build_against(conftest.build_emu(), "shim_callsites", tmp_path / "shim_callsites_emu", SHIM_FLAGS)
+    native_host.run_ok([exe, "12"], "OK frames=12")
 
 
 @pytest.mark.gpu
 def test_md_script_shim_call_sites(gpu_lib):
     exe = build_shim_callsites()
     assert exe, "tests/native/shim_callsites (or oracle/_ref/viamd_export_slices.inc to build it from) must travel to the GPU box"
-    out = subprocess.run([exe, "48"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=48"), out.stdout
+    native_host.run_ok([exe, "48"], "OK frames=48", timeout=300)
 
 
 def build_ref_callsites():
@@ -207,23 +171,10 @@ def test_viamds_own_call_sites(gpu_lib, tmp_path):
     assert out.stdout.startswith("OK frames=64 display_properties=21") and "log_errors=0" in out.stdout, out.stdout
 
 
-SHIM_DEFAULT_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script.cpp")
-SHIM_DEFAULT_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script")
-
-
 def build_shim_default_script():
     """VIAMD's default script (src/main.cpp:528) behind the shim with a CPU mock of mdlib's evaluator as the fallback
-    (tests/native/md_mock_eval.h); compiled by __graft_entry__.build() too."""
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_DEFAULT_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_DEFAULT_EXE) and os.path.getmtime(SHIM_DEFAULT_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_DEFAULT_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_DEFAULT_SRC, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native"),
-                           "-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd", "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd",
-                           "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread", "-o", SHIM_DEFAULT_EXE])
-    return SHIM_DEFAULT_EXE
+    (tests/native/md_mock_eval.h, tests/native/shim_default_script_host.h); compiled by __graft_entry__.build() too."""
+    return native_host.build_shim("shim_default_script")
 
 
 def test_md_script_shim_keeps_viamds_default_script_whole_on_the_emulator(tmp_path, emu_lib):
@@ -234,35 +185,20 @@ def test_md_script_shim_keeps_viamds_default_script_whole_on_the_emulator(tmp_pa
     import conftest
     assert os.access(build_shim_default_script(), os.X_OK)             # links against the product library
     emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_default_script_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_DEFAULT_SRC, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native"), emu,
-                           "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "12"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=12 properties=7"), out.stdout
+    exe = native_host.build_shim("shim_default_script", emu, tmp_path / "shim_default_script_emu")
+    native_host.run_ok([exe, "12"], "OK frames=12 properties=7")
     # the same program with the shim's opt-in deferred settle (-DVMD_SHIM_DEFERRED_SETTLE: vmd_set_option("readahead_lone", 1) at create)
-    exe2 = str(tmp_path / "shim_default_script_emu_deferred")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-DVMD_SHIM_DEFERRED_SETTLE", SHIM_DEFAULT_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe2])
-    out = subprocess.run([exe2, "12"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=12 properties=7"), out.stdout
+    exe2 = native_host.build_shim("shim_default_script", emu, tmp_path / "shim_default_script_emu_deferred", ["-DVMD_SHIM_DEFERRED_SETTLE"])
+    native_host.run_ok([exe2, "12"], "OK frames=12 properties=7")
 
 
 @pytest.mark.gpu
 def test_md_script_shim_keeps_viamds_default_script_whole(gpu_lib):
-    out = subprocess.run([build_shim_default_script(), "64"], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=64 properties=7"), out.stdout
+    native_host.run_ok([build_shim_default_script(), "64"], "OK frames=64 properties=7", timeout=300)
 
 
-STRESS_SRC = os.path.join(ROOT, "tests", "native", "stress_eval.cpp")
-
-
-def _build_against(lib_path, src, exe, opt="-O2"):
-    subprocess.check_call(["g++", "-std=c++17", opt, "-Wall", src, "-I" + os.path.join(ROOT, "include"), lib_path, "-Wl,-rpath," + os.path.dirname(lib_path),
-                           "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread", "-o", exe])
-    return exe
+def _build_against(lib_path, name, exe, opt="-O2"):
+    return native_host.build_against(lib_path, name, exe, ["-std=c++17", "-Wall"], opt, rocm=True)
 
 
 def test_evaluator_life_cycle_stress_on_the_emulator(tmp_path, emu_lib):
@@ -270,7 +206,7 @@ def test_evaluator_life_cycle_stress_on_the_emulator(tmp_path, emu_lib):
     -> vis payload -> free, repeated; a crash handler reports vmd_last_stage): a few iterations on the emulator build, so the
     program itself cannot rot; the long runs are `-m gpu` and scripts/gpu_r03h.sh (profiles/r03h_stress.txt)."""
     import conftest
-    exe = _build_against(conftest.build_emu(), STRESS_SRC, str(tmp_path / "stress_emu"), "-O1")
+    exe = _build_against(conftest.build_emu(), "stress_eval", str(tmp_path / "stress_emu"), "-O1")
     out = subprocess.run([exe, "2", "6"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.startswith("OK iterations=2"), out.stdout
@@ -282,13 +218,10 @@ def test_evaluator_life_cycle_stress(gpu_lib, tmp_path):
     """200 life cycles on the MI355X with AMD_LOG_LEVEL=1 (runtime errors reach stderr); a SIGABRT would be reported with the
     evaluator stage it happened in."""
     from viamd_amd import build
-    exe = _build_against(build.build(), STRESS_SRC, str(tmp_path / "stress"))
+    exe = _build_against(build.build(), "stress_eval", str(tmp_path / "stress"))
     out = subprocess.run([exe, "200", "48"], capture_output=True, text=True, timeout=900, env=dict(os.environ, AMD_LOG_LEVEL="1"))
     assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
     assert out.stdout.strip().split("\n")[-1].startswith("OK iterations=200"), out.stdout[-500:]
-
-
-RA_STRESS_SRC = os.path.join(ROOT, "tests", "native", "stress_readahead.cpp")
 
 
 def test_read_ahead_stress_on_the_emulator(tmp_path, emu_lib):
@@ -296,7 +229,7 @@ def test_read_ahead_stress_on_the_emulator(tmp_path, emu_lib):
     region sizes, a large direct call amid the small ones, interrupts + restarts - after every evaluation the eval holds bit for bit what
     one call over the same frames leaves with read-ahead off.  A few iterations here; the long runs are `-m gpu`."""
     import conftest
-    exe = _build_against(conftest.build_emu(), RA_STRESS_SRC, str(tmp_path / "stress_ra_emu"), "-O1")
+    exe = _build_against(conftest.build_emu(), "stress_readahead", str(tmp_path / "stress_ra_emu"), "-O1")
     out = subprocess.run([exe, "8", "40", "900", "7"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.startswith("OK iterations=8 (2 in deferred-settle mode)"), out.stdout       # every fourth iteration: option readahead_lone, helper-thread settle
@@ -309,7 +242,7 @@ def test_read_ahead_stress_on_the_emulator(tmp_path, emu_lib):
 def test_read_ahead_stress(gpu_lib, tmp_path):
     """400 randomised pool evaluations of a 30 000-atom box (240 frames) on the MI355X, three seeds"""
     from viamd_amd import build
-    exe = _build_against(build.build(), RA_STRESS_SRC, str(tmp_path / "stress_ra"))
+    exe = _build_against(build.build(), "stress_readahead", str(tmp_path / "stress_ra"))
     for seed in ("1", "2", "3"):
         out = subprocess.run([exe, "400", "240", "30000", seed], capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
@@ -318,8 +251,6 @@ def test_read_ahead_stress(gpu_lib, tmp_path):
     assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
     assert out.stdout.strip().split("\n")[-1].startswith("OK iterations=150 (37 in deferred-settle mode) frames=240 +sdf"), out.stdout[-500:]
 
-REDUCE_THREADS_SRC = os.path.join(ROOT, "tests", "native", "reduce_threads.cpp")
-
 
 def test_ranks_as_threads_of_one_process_merge_on_the_emulator(tmp_path, emu_lib):
     """tests/native/reduce_threads.cpp: three ranks as THREADS of one process, all on one device, merged with vmd_eval_reduce through a
@@ -327,14 +258,12 @@ def test_ranks_as_threads_of_one_process_merge_on_the_emulator(tmp_path, emu_lib
     mutex this dead-locked (rank A in the collective, rank B waiting for A's buffer: ADVICE r03); the merge now leases its buffer from a
     pool.  Every rank must end with the integers of one eval over all frames."""
     import conftest
-    exe = _build_against(conftest.build_emu(), REDUCE_THREADS_SRC, str(tmp_path / "reduce_threads"), "-O1")
+    exe = _build_against(conftest.build_emu(), "reduce_threads", str(tmp_path / "reduce_threads"), "-O1")
     out = subprocess.run([exe, "3", "12", "600"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.startswith("OK ranks=3"), out.stdout
     out = subprocess.run([exe, "5", "7", "450"], capture_output=True, text=True, timeout=300)        # more ranks than some have frames for
     assert out.returncode == 0, out.stderr[-2000:]
-
-CONCURRENT_SRC = os.path.join(ROOT, "tests", "native", "concurrent_evals.cpp")
 
 
 def test_independent_evaluations_side_by_side_on_the_emulator(tmp_path, emu_lib):
@@ -343,7 +272,7 @@ def test_independent_evaluations_side_by_side_on_the_emulator(tmp_path, emu_lib)
     the evals (per-launch parameters, resource cache, checkpoint cache, staging pools) must not leak from one into another: every result
     equals the lone evaluation's integers.  The same program runs under ThreadSanitizer in scripts/tsan_emu.sh."""
     import conftest
-    exe = _build_against(conftest.build_emu(), CONCURRENT_SRC, str(tmp_path / "concurrent_emu"), "-O1")
+    exe = _build_against(conftest.build_emu(), "concurrent_evals", str(tmp_path / "concurrent_emu"), "-O1")
     out = subprocess.run([exe, "2", "10", "600", str(tmp_path)], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.startswith("OK iterations=2"), out.stdout
@@ -353,7 +282,7 @@ def test_independent_evaluations_side_by_side_on_the_emulator(tmp_path, emu_lib)
 def test_independent_evaluations_side_by_side(gpu_lib, tmp_path):
     """the same on the MI355X: 25 rounds of 16 concurrent evaluations over 48 frames of 6 000 atoms"""
     from viamd_amd import build
-    exe = _build_against(build.build(), CONCURRENT_SRC, str(tmp_path / "concurrent"))
+    exe = _build_against(build.build(), "concurrent_evals", str(tmp_path / "concurrent"))
     out = subprocess.run([exe, "25", "48", "6000", str(tmp_path)], capture_output=True, text=True, timeout=180, env=dict(os.environ, AMD_LOG_LEVEL="1"))
     assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
     assert out.stdout.startswith("OK iterations=25"), out.stdout

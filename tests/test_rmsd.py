@@ -5,11 +5,12 @@ through the shim with the three opt-ins."""
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -21,8 +22,6 @@ import test_shape as TS
 from test_geometry import bits_equal, blob_system, evaluate, rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_RMSD_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_rmsd.cpp")
-SHIM_RMSD_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_rmsd")
 VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
 RM_LINE = '\nrm = rmsd(resname("ALA"));'
 
@@ -678,29 +677,13 @@ def test_export_table(emu_lib, oracle, tmp_path):
 
 def build_shim_rmsd():
     """tests/native/shim_default_script_rmsd.cpp linked against the product library"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_RMSD_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_RMSD_EXE) and os.path.getmtime(SHIM_RMSD_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_RMSD_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_RMSD_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_RMSD_EXE])
-    return SHIM_RMSD_EXE
+    return native_host.build_shim("shim_default_script_rmsd")
 
 
 def test_shim_default_script_with_the_rmsd_line_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_rmsd_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_RMSD_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 rm=gpu fallback_frame_range_calls=0"), out.stdout
+    exe = native_host.build_shim("shim_default_script_rmsd", conftest.build_emu(), tmp_path / "shim_rmsd_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=8 rm=gpu fallback_frame_range_calls=0")
     # without the RMSD bit `rm` is reported and stays with the (mock) fallback, which is driven over the frames again
-    out = subprocess.run([exe, "8", "nobit"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 rm=fallback") and "fallback_frame_range_calls=0" not in out.stdout, out.stdout
+    out = native_host.run_ok([exe, "8", "nobit"], "OK frames=8 properties=8 rm=fallback")
+    assert "fallback_frame_range_calls=0" not in out.stdout, out.stdout

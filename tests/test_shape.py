@@ -4,11 +4,12 @@ computation per statement, ABI validation, the opt-in script front-end (C++ and 
 clear_data, multi-rank merges), export, and VIAMD's default script through the shim with both opt-ins."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -19,8 +20,6 @@ import test_geometry as TG
 from test_geometry import bits_equal, blob_system, evaluate, rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SHAPE_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_shape.cpp")
-SHIM_SHAPE_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_shape")
 NAMES = ("lin", "plan", "iso")
 VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
 
@@ -598,25 +597,10 @@ def test_export_table(emu_lib, oracle, tmp_path):
 
 def build_shim_shape():
     """tests/native/shim_default_script_shape.cpp linked against the product library"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_SHAPE_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_SHAPE_EXE) and os.path.getmtime(SHIM_SHAPE_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_SHAPE_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_SHAPE_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_SHAPE_EXE])
-    return SHIM_SHAPE_EXE
+    return native_host.build_shim("shim_default_script_shape")
 
 
 def test_shim_default_script_with_both_opt_ins_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_shape_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_SHAPE_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=7 a1=gpu lin=gpu"), out.stdout
+    exe = native_host.build_shim("shim_default_script_shape", conftest.build_emu(), tmp_path / "shim_shape_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=7 a1=gpu lin=gpu")

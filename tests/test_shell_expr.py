@@ -6,11 +6,12 @@ bridging count and a second-shell sdf through the shim.  The yardstick is tests/
 voxels are integers: every comparison is `==`."""
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -26,8 +27,6 @@ from test_within import options, launches, evaluate, TILT, blob12k, sets_of, var
 from test_shell_sdf import vol, caps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_shell_expr.cpp")
-SHIM_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_shell_expr")
 KEYS = ("shell_expr", "shell_expr_brute", "shell_expr_finish")
 BITS = dict(within=True, shell_sdf=True, shell_expr=True)
 FOUR = X.table(lambda a, b, c, d: a and b and not c and d, 4)
@@ -722,28 +721,12 @@ def test_the_live_words_of_the_term_passes(emu_lib):
 
 def build_shim_shell_expr():
     """tests/native/shim_default_script_shell_expr.cpp linked against the product library"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_EXE) and os.path.getmtime(SHIM_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_EXE])
-    return SHIM_EXE
+    return native_host.build_shim("shim_default_script_shell_expr")
 
 
 def test_shim_default_script_with_the_expression_lines_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_shell_expr_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=9 expr=gpu fallback_frame_range_calls=0"), out.stdout
-    out = subprocess.run([exe, "8", "nobit"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=9 expr=fallback") and "fallback_frame_range_calls=0" not in out.stdout, out.stdout
+    exe = native_host.build_shim("shim_default_script_shell_expr", conftest.build_emu(), tmp_path / "shim_shell_expr_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=9 expr=gpu fallback_frame_range_calls=0")
+    out = native_host.run_ok([exe, "8", "nobit"], "OK frames=8 properties=9 expr=fallback")
+    assert "fallback_frame_range_calls=0" not in out.stdout, out.stdout

@@ -7,11 +7,12 @@ order)."""
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -24,8 +25,6 @@ import test_within as TW
 from test_within import options, launches, evaluate, TILT, blob12k, sets_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SHELL_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_shell_rdf.cpp")
-SHIM_SHELL_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_shell_rdf")
 VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
 GS_LINE = "\ngs = rdf(element('O') and within(3.5, resname(\"ALA\")), element('O'), 8.0);"
 PENCIL_KEYS = ("shell_flags", "shell_compact", "rdf_pencil")
@@ -721,28 +720,12 @@ def test_ir_validation_errors(host_lib):
 
 def build_shim_shell_rdf():
     """tests/native/shim_default_script_shell_rdf.cpp linked against the product library"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_SHELL_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_SHELL_EXE) and os.path.getmtime(SHIM_SHELL_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_SHELL_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_SHELL_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_SHELL_EXE])
-    return SHIM_SHELL_EXE
+    return native_host.build_shim("shim_default_script_shell_rdf")
 
 
 def test_shim_default_script_with_the_shell_line_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_shell_rdf_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_SHELL_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 gs=gpu fallback_frame_range_calls=0"), out.stdout
-    out = subprocess.run([exe, "8", "nobit"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 gs=fallback") and "fallback_frame_range_calls=0" not in out.stdout, out.stdout
+    exe = native_host.build_shim("shim_default_script_shell_rdf", conftest.build_emu(), tmp_path / "shim_shell_rdf_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=8 gs=gpu fallback_frame_range_calls=0")
+    out = native_host.run_ok([exe, "8", "nobit"], "OK frames=8 properties=8 gs=fallback")
+    assert "fallback_frame_range_calls=0" not in out.stdout, out.stdout

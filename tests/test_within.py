@@ -5,11 +5,12 @@ merges, export, the opt-in front-end (C++ and Python twin), ABI validation and V
 through the shim.  Counts are integers: every comparison is `==`."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import native_host
 
 import viamd_amd as V
 from viamd_amd import _lib as L
@@ -21,8 +22,6 @@ from test_geometry import bits_equal, rows
 from geometry_ref import Box
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_WITHIN_SRC = os.path.join(ROOT, "tests", "native", "shim_default_script_within.cpp")
-SHIM_WITHIN_EXE = os.path.join(ROOT, "tests", "native", "shim_default_script_within")
 VIAMD_DEFAULT_SCRIPT = TG.VIAMD_DEFAULT_SCRIPT
 NW_LINE = "\nnw = count(element('O') and within(3.5, resname(\"ALA\")));"
 TILT = (12.0, -8.0, 10.0)
@@ -707,28 +706,12 @@ def test_ir_validation_errors(host_lib):
 
 def build_shim_within():
     """tests/native/shim_default_script_within.cpp linked against the product library"""
-    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "native")]
-    from viamd_amd import build
-    lib = build.build()
-    deps = [SHIM_WITHIN_SRC, lib, os.path.join(ROOT, "include", "vmd_md_script_shim.h"), os.path.join(ROOT, "tests", "native", "md_mock.h"),
-            os.path.join(ROOT, "tests", "native", "md_mock_eval.h")]
-    if os.path.exists(SHIM_WITHIN_EXE) and os.path.getmtime(SHIM_WITHIN_EXE) >= max(os.path.getmtime(d) for d in deps):
-        return SHIM_WITHIN_EXE
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", SHIM_WITHIN_SRC] + inc + ["-L" + os.path.join(ROOT, "viamd_amd"), "-lviamd_amd",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../viamd_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                           "-lpthread", "-o", SHIM_WITHIN_EXE])
-    return SHIM_WITHIN_EXE
+    return native_host.build_shim("shim_default_script_within")
 
 
 def test_shim_default_script_with_the_within_line_on_the_emulator(emu_lib, tmp_path):
     import conftest
-    emu = conftest.build_emu()
-    exe = str(tmp_path / "shim_within_emu")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", SHIM_WITHIN_SRC, "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "tests", "native"), emu, "-Wl,-rpath," + os.path.dirname(emu), "-lpthread", "-o", exe])
-    out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 nw=gpu fallback_frame_range_calls=0"), out.stdout
-    out = subprocess.run([exe, "8", "nobit"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.startswith("OK frames=8 properties=8 nw=fallback") and "fallback_frame_range_calls=0" not in out.stdout, out.stdout
+    exe = native_host.build_shim("shim_default_script_within", conftest.build_emu(), tmp_path / "shim_within_emu")
+    native_host.run_ok([exe, "8"], "OK frames=8 properties=8 nw=gpu fallback_frame_range_calls=0")
+    out = native_host.run_ok([exe, "8", "nobit"], "OK frames=8 properties=8 nw=fallback")
+    assert "fallback_frame_range_calls=0" not in out.stdout, out.stdout
