@@ -177,6 +177,7 @@ typedef uint32_t vmd_property_flags_t;
 #define VMD_PROPERTY_FLAG_TEMPORAL     1u
 #define VMD_PROPERTY_FLAG_DISTRIBUTION 2u
 #define VMD_PROPERTY_FLAG_VOLUME       4u
+#define VMD_PROPERTY_FLAG_MAP          8u   /* a 2-D class map: dim = {1, 4, 512, 512}, channel fastest */
 
 #define VMD_RDF_NUM_BINS 1024   /* mdlib's distribution bin count */
 #define VMD_VOLUME_DIM   128    /* mdlib's volume resolution, BASELINE config 4 "128^3" */
@@ -272,10 +273,33 @@ typedef struct vmd_shell_expr_t { const vmd_shell_t* terms; size_t nterms; uint3
 bool vmd_ir_add_within_count_expr(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr);
 bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
                                const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr, float cutoff);
+/* `{table, map} = ramachandran(backbone)`: the backbone pass VIAMD runs over every frame of a trajectory with a protein
+ * (src/viamd.cpp:469-549) and the density its Ramachandran window bins from it (src/components/ramachandran/ramachandran.cpp:1277-1357).
+ * A backbone is num_segments segments with atoms N, CA, C in num_ranges ranges (chains); a segment has a predecessor or successor only
+ * inside its range.  phi(s) = dihedral(C[s-1], N[s], CA[s], C[s]), psi(s) = dihedral(N[s], CA[s], C[s], N[s+1]), in radians whatever
+ * spec_angle_radians says, bit for bit dihedral()'s value of the same atoms; the angle that lacks its neighbour is +0 (D-BB-ENDS).
+ * rama_class: one byte per segment, 0..3 = general, glycine, proline, pre-proline (MD_RAMACHANDRAN_TYPE_*), 255 = none (never binned).
+ * names[0]: the angle table, TEMPORAL, dim = {num_frames, 2 * nseg}, values[f * 2 * nseg + 2 * s + {0, 1}] = {phi, psi} - the layout
+ * of md_backbone_angles_t[f * stride + s]; unit {"", "rad"}; no aggregate.  names[1]: the density of all evaluated frames, MAP:
+ * dim = {1, 4, 512, 512}, entry (y * 512 + x) * 4 + c is what VIAMD's density_tex[y * 512 + x].elem[c] holds before its blur, with
+ * x = (uint32_t)((phi / 2pi + 0.5) * 512) & 511 in separately rounded fp32 operations (D-RAMA-BIN) and y likewise from psi; a sample with
+ * phi == 0 && psi == 0 is skipped (the reference's rule); vmd_set_option("spec_rama_skip_ends", 1) also skips every segment that lacks
+ * an angle (read at eval creation).  `counts` are the u64 accumulators (vmd_eval_refresh_counts), `values` the same numbers as floats.
+ * Errors (vmd_last_error): NULL arguments, no segment, negative indices, offsets that do not start at 0, increase and end at
+ * num_segments, a class outside 0..3 / 255, names that are already defined or equal to each other. */
+#define VMD_RAMA_MAP_DIM 512
+#define VMD_RAMA_MAP_CLASSES 4
+typedef struct vmd_backbone_t {
+    size_t num_segments;  const int32_t *n, *ca, *c;          /* 0-based atom indices per segment */
+    size_t num_ranges;    const uint32_t* range_offsets;      /* num_ranges + 1, starts at 0, increases, ends at num_segments */
+    const uint8_t* rama_class;                                /* per segment 0..3 or 255; NULL = all 0 */
+} vmd_backbone_t;
+bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* backbone);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
- * there are and writes the first `cap` of them to `out` (NULL: count only).  0 for other properties.  What the shim highlights for
+ * there are and writes the first `cap` of them to `out` (NULL: count only); the angle table of a ramachandran statement: N, CA, C of segment
+ * `context`, or of all segments.  0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
 /* md_script_ir_compile_from_source stand-in (src/main.cpp:878) for the script subset of the hot path: statements
@@ -298,6 +322,14 @@ typedef struct vmd_topology_t {
     const int32_t* residue_seq_id;
 } vmd_topology_t;
 bool     vmd_ir_compile_from_source(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* topology);
+/* A backbone from a topology, for hosts without mdlib (DECISION D-BB-TOPOLOGY; no coordinates, no bond test).  Segments = residues that own
+ * atoms named "N", "CA" and "C" (names[], first match per residue); a range = a maximal run of such residues with consecutive
+ * residue_index; class: resname GLY -> 1, PRO -> 2, else successor in the same range is PRO -> 3, else 0.  NULL + vmd_last_error on a
+ * malformed topology; the view (num_segments may be 0) lives as long as the object. */
+typedef struct vmd_backbone_owned_t vmd_backbone_owned_t;
+vmd_backbone_owned_t* vmd_topology_backbone(const vmd_topology_t* topology);
+const vmd_backbone_t* vmd_backbone_view(const vmd_backbone_owned_t* backbone);
+void     vmd_backbone_free(vmd_backbone_owned_t* backbone);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
  * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of
@@ -453,6 +485,16 @@ bool vmd_eval_sdf_payload(vmd_script_eval_t* eval, const char* name, const vmd_s
 #define VMD_SHELL_MASK_FAILED ((size_t)-1)
 size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name, int which, const vmd_system_t* sys, vmd_trajectory_i* traj,
                            uint32_t frame, uint64_t* words, size_t cap);
+
+/* VIAMD's filtered Ramachandran map (ramachandran.cpp:669-678): the density of the EVALUATED frames of [frame_beg, frame_end), binned from the
+ * angle table the device holds - one small launch per move of the timeline filter.  `name` is the MAP property of a ramachandran statement;
+ * values: host f32[4 * 512 * 512] in the map's layout (NULL: not wanted); sums: the samples per class (rep->den_sum; NULL: not wanted).
+ * frame_beg >= frame_end answers zeros.  false + vmd_last_error: a range past num_frames, an unknown property, a property that is not a
+ * MAP.  Accumulated results, fingerprints and the frame mask are untouched; the call may come while pool threads are inside
+ * vmd_eval_frame_range (it takes its turn between their batches).  After vmd_eval_finalize / vmd_eval_reduce / vmd_eval_set_frame_mask
+ * the device table is refreshed from the host rows first, so every rank of a merged evaluation answers for the whole trajectory. */
+bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, float* values,
+                           uint64_t sums[4]);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

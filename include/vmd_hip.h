@@ -299,6 +299,20 @@ int vmd_hip_add_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n);
 /* u64 counters -> f32 values (values[i] = fl((float)counts[i] * scale); scale = 1: the raw counts of SPEC S5) + max reduction into
  * max_out[0] (device f32) */
 int vmd_hip_counts_to_float(void* stream, const uint64_t* counts, size_t n, float* values, float* max_out, float scale);
+/* K10: backbone phi / psi and the Ramachandran density.  One thread per (frame, segment): phi = dihedral(C[s-1], N[s], CA[s],
+ * C[s]), psi = dihedral(N[s], CA[s], C[s], N[s+1]) with k_geom<4>'s arithmetic on raw positions, radians; a missing neighbour gives +0.
+ * out f32[B][nseg][2] = {phi, psi}; link u8[nseg]: bit 0 has predecessor (segment s-1), bit 1 has successor (s+1).  B * nseg > 2^31 - 1
+ * is refused. */
+#define VMD_RAMA_DIM 512
+#define VMD_RAMA_CLASSES 4
+int vmd_hip_backbone_angles(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                            uint32_t pbc_flags, int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c,
+                            const uint8_t* link, float* out);
+/* bins rows [0, F) of `angles` (row r at angles + r * 2 * nseg) whose mask byte is non-zero (mask NULL: all); rama_class u8[nseg]: 0..3,
+ * 255 = never binned; skip_ends: a segment that lacks a neighbour is not binned; a sample with phi == 0 && psi == 0 never is.
+ * counts u64[512*512*4] (entry (y * 512 + x) * 4 + class) and sums u64[4] (NULL: not wanted) are ADDED to.  F * nseg > 2^31 - 1 is refused. */
+int vmd_hip_rama_bin(void* stream, const float* angles, int F, const uint8_t* row_mask, int nseg, const uint8_t* rama_class,
+                     const uint8_t* link, int skip_ends, uint64_t* counts, uint64_t* sums);
 /* 1: k_sdf_scatter reads the frame with non-temporal loads; returns the previous value */
 int vmd_hip_set_sdf_nt(int on);
 /* candidate columns (one target atom against the 64 reference atoms of a chunk: 64 candidate lanes) k_rdf_pencil has walked on the

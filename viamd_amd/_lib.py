@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("VIAMD_AMD_LIB") or os.path.join(_HERE, "libviamd_amd.
 
 PBC_ALL = 7
 FLAG_TEMPORAL, FLAG_DISTRIBUTION, FLAG_VOLUME = 1, 2, 4
+FLAG_MAP = 8                     # VMD_PROPERTY_FLAG_MAP: the Ramachandran class map, dim = {1, 4, 512, 512}
+RAMA_MAP_DIM, RAMA_MAP_CLASSES = 512, 4
 DIST_COM, DIST_MIN, DIST_MAX, DIST_PAIR = 0, 1, 2, 3
 RDF_NUM_BINS = 1024
 VOLUME_DIM = 128
@@ -65,6 +67,11 @@ class ScriptSkippedC(C.Structure):
 class TopologyC(C.Structure):
     _fields_ = [("num_atoms", C.c_size_t), ("elements", C.POINTER(C.c_char_p)), ("names", C.POINTER(C.c_char_p)),
                 ("resnames", C.POINTER(C.c_char_p)), ("residue_index", c_int32_p), ("residue_seq_id", c_int32_p)]
+
+
+class BackboneC(C.Structure):            # vmd_backbone_t (include/vmd_eval.h)
+    _fields_ = [("num_segments", C.c_size_t), ("n", C.POINTER(C.c_int32)), ("ca", C.POINTER(C.c_int32)), ("c", C.POINTER(C.c_int32)),
+                ("num_ranges", C.c_size_t), ("range_offsets", C.POINTER(C.c_uint32)), ("rama_class", C.POINTER(C.c_uint8))]
 
 
 class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
@@ -173,6 +180,11 @@ SIGNATURES = [
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
     ("vmd_ir_add_sdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.c_size_t, c_int32_p, C.c_size_t, C.POINTER(ShellC),
                                         C.c_float]),
+    ("vmd_ir_add_ramachandran", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(BackboneC)]),
+    ("vmd_topology_backbone", _vp, [C.POINTER(TopologyC)]),
+    ("vmd_backbone_view", C.POINTER(BackboneC), [_vp]),
+    ("vmd_backbone_free", None, [_vp]),
+    ("vmd_eval_rama_density", C.c_bool, [_vp, C.c_char_p, C.c_uint32, C.c_uint32, c_float_p, c_uint64_p]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -346,6 +358,8 @@ SIGNATURES = [
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("vmd_hip_geometry", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.c_int, _vp]),
+    ("vmd_hip_backbone_angles", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("vmd_hip_rama_bin", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     ("vmd_hip_shape_partial_doubles", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("vmd_hip_shape", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                 _vp, _vp, _vp, _vp]),

@@ -211,6 +211,7 @@ bool reuse_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t beg, siz
                         for (size_t k = 0; k < p->ncounts; ++k) p->weights64[k] += q->block_weights64[blk * p->ncounts + k];
                 } else {
                     memcpy(&p->values[f * p->dim1], block_rows(src, q, blk) + f * p->dim1, (bend - f) * p->dim1 * sizeof(float));
+                    if (p->prop.is_rama()) p->table_stale = true;     // the device table follows before the next filtered map
                 }
                 p->dirty = true;
             }
@@ -249,7 +250,7 @@ bool refresh_views_locked(vmd_script_eval_t* e) {
     for (auto& p : e->props) {
         if (!p->dirty) continue;
         if (p->prop.kind == PROP_RDF) { if (!refresh_distribution(e, p.get())) return false; }
-        else if (p->prop.kind == PROP_SDF) {
+        else if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) {
             // vmd_eval_defer_volume_views: a rank of a multi-GPU evaluation does not materialise ITS partial volume's float view (8.4 MB
             // over PCIe after every range) - the merge re-derives the view of the merged counts (vmd_eval_reduce -> vmd_eval_finalize); the
             // volume stays dirty until then

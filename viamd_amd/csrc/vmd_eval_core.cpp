@@ -301,6 +301,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     e->spec.within_closed = g_opt.spec_within_closed.load() != 0;
     e->spec.within_exclude_ref = g_opt.spec_within_exclude_ref.load() != 0;
     e->spec.shell_norm = g_opt.spec_shell_norm.load() != 0;
+    e->spec.rama_skip_ends = g_opt.spec_rama_skip_ends.load() != 0;
     e->frame_mask.assign(num_frames, 0);
     for (auto& p : ir->props) {
         auto st = std::make_unique<PropState>();
@@ -329,7 +330,29 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             st->data.min_range[0] = -p.rmax; st->data.max_range[0] = p.rmax;
             st->data.unit_str[0] = ""; st->data.unit_str[1] = "";
             break;
+        case PROP_RAMA:
+            // the class map behind the angle table; pinned views like a volume's (4 + 8 MB)
+            st->ncounts = (size_t)VMD_RAMA_DIM * VMD_RAMA_DIM * VMD_RAMA_CLASSES;
+            st->values.assign(st->ncounts, 0.0f, true);
+            st->counts.assign(st->ncounts, 0, true);
+            st->pinned = st->values.pinned && st->counts.pinned;
+            st->data.dim[0] = 1; st->data.dim[1] = VMD_RAMA_CLASSES; st->data.dim[2] = st->data.dim[3] = VMD_RAMA_DIM;
+            st->data.min_range[0] = -(float)M_PI; st->data.max_range[0] = (float)M_PI;
+            st->data.unit_str[0] = "rad"; st->data.unit_str[1] = "";
+            break;
         case PROP_DIST:
+            if (p.is_rama()) {
+                // {phi, psi} per segment, radians whatever spec_angle_radians says; no aggregate (VIAMD's table has none)
+                st->dist_P = p.a.size(); st->dist_per = 2;
+                st->dim1 = 2 * p.a.size();
+                st->values.assign(num_frames * st->dim1, 0.0f);
+                st->data.dim[0] = (int32_t)num_frames; st->data.dim[1] = (int32_t)st->dim1;
+                st->data.unit_str[0] = ""; st->data.unit_str[1] = "rad";
+                if (!st->d_table.ensure(num_frames * st->dim1)) return nullptr;
+                if (hipMemsetAsync(st->d_table.p, 0, num_frames * st->dim1 * sizeof(float), e->stream) != hipSuccess) {
+                    vmd_fail("hipMemset failed"); return nullptr; }
+                break;
+            }
             st->dist_P = p.aoff.size() - 1;
             st->dist_per = p.dist_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1;
             st->dim1 = st->dist_P * st->dist_per;
@@ -477,6 +500,10 @@ extern "C" void vmd_eval_clear_data(vmd_script_eval_t* eval) {
         std::fill(p->agg_var.begin(), p->agg_var.end(), 0.0f);
         std::fill(p->agg_ext.begin(), p->agg_ext.end(), 0.0f);
         if (p->ncounts) (void)hipMemsetAsync(p->d_counts.p, 0, p->ncounts * sizeof(uint64_t), eval->stream);
+        if (p->prop.is_rama()) {
+            (void)hipMemsetAsync(p->d_table.p, 0, p->values.size() * sizeof(float), eval->stream);
+            p->table_stale = false;
+        }
         pub(p->data.max_value, 0.0f); pub(p->data.min_value, 0.0f);
         pub(p->data.max_range[1], 0.0f);
         p->dirty = false;
@@ -558,7 +585,7 @@ bool refresh_volume(vmd_script_eval_t* e, PropState* p) {
     VMD_STAGE("refresh_volume: counts -> float view, D2H");
     if (!p->d_max.ensure(1)) return false;
     float scale = 1.0f;
-    if (e->spec.sdf_density) {
+    if (p->prop.kind == PROP_SDF && e->spec.sdf_density) {
         // DECISION(D-SDF-NORM) flipped: number density per cubic Angstrom, averaged over the frames evaluated so far
         const double edge = 2.0 * (double)p->prop.rmax / (double)VMD_VOLUME_DIM;
         const size_t nf = e->frames_done.load();
@@ -602,7 +629,7 @@ void refresh_temporal_stats(vmd_script_eval_t* e, PropState* p) {
         float rlo = row[0], rhi = row[0];
         double s = 0.0;
         for (size_t i = 0; i < p->dim1; ++i) { rlo = std::min(rlo, row[i]); rhi = std::max(rhi, row[i]); s += row[i]; }
-        if (p->dim1 > 1) {
+        if (p->dim1 > 1 && !p->agg_mean.empty()) {      // (a ramachandran table keeps no aggregate)
             const double mean = s / (double)p->dim1;
             double v = 0.0;
             for (size_t i = 0; i < p->dim1; ++i) { const double d = row[i] - mean; v += d * d; }
@@ -634,8 +661,10 @@ extern "C" bool vmd_eval_finalize(vmd_script_eval_t* eval) {
     for (auto& p : eval->props) {
         bool ok = true;
         if (p->prop.kind == PROP_RDF) ok = refresh_distribution(eval, p.get());
-        else if (p->prop.kind == PROP_SDF) ok = refresh_volume(eval, p.get());
+        else if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) ok = refresh_volume(eval, p.get());
         else refresh_temporal_stats(eval, p.get());
+        // rows of other ranks may have joined the host table (vmd_eval_reduce): the device copy follows before the next filtered map
+        if (p->prop.is_rama()) p->table_stale = true;
         if (!ok) return false;
     }
     return true;
@@ -724,6 +753,7 @@ extern "C" void vmd_eval_set_frame_mask(vmd_script_eval_t* eval, const uint8_t* 
         done += eval->frame_mask[f] ? 1 : 0;
     }
     eval->frames_done = done;
+    for (auto& p : eval->props) if (p->prop.is_rama()) p->table_stale = true;     // frames evaluated elsewhere: their rows are on the host
 }
 
 extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t* out, size_t cap) {
@@ -739,6 +769,11 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
             // a voxel receives at most one count per (frame, structure, target atom)
             if (p->prop.kind == PROP_SDF) {
                 const long double b = (long double)eval->num_frames * (long double)p->prop.K * (long double)p->prop.b.size();
+                v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
+            }
+            // a bin receives at most one count per (frame, segment)
+            if (p->prop.kind == PROP_RAMA) {
+                const long double b = (long double)eval->num_frames * (long double)p->prop.K;
                 v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
             }
             if (!p->weights64.empty()) { v.weights64 = p->weights64.data(); v.num_weights = p->weights64.size(); }
@@ -761,6 +796,61 @@ extern "C" vmd_reduce_stats_t* vmd_eval_internal_reduce_stats(vmd_script_eval_t*
 extern "C" void vmd_eval_reduce_stats(const vmd_script_eval_t* eval, vmd_reduce_stats_t* out) {
     if (!out) return;
     if (eval) *out = eval->reduce_stats; else memset(out, 0, sizeof(*out));
+}
+
+// ---- the filtered Ramachandran map: one zeroing, one k_rama_bin over the device table with the frame mask as the row mask,
+// one copy-out.  Under the eval's mutex like vmd_eval_shell_mask, so it takes its turn between the batches of running calls; it writes only
+// the table property's own scratch.
+extern "C" bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, float* values,
+                                      uint64_t sums[4]) {
+    if (!eval || !name) return vmd_fail("vmd_eval_rama_density: NULL argument");
+    vmd_script_eval_t* e = eval;
+    size_t mi = e->props.size();
+    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) mi = i;
+    if (mi == e->props.size()) return vmd_fail("unknown property '%s'", name);
+    if (e->props[mi]->prop.kind != PROP_RAMA || mi == 0 || !e->props[mi - 1]->prop.is_rama())
+        return vmd_fail("'%s' is not a ramachandran map", name);
+    if (frame_beg < frame_end && frame_end > e->num_frames)
+        return vmd_fail("frames [%u, %u) are outside the %zu frames of the evaluation", frame_beg, frame_end, e->num_frames);
+    const size_t nmap = (size_t)VMD_RAMA_DIM * VMD_RAMA_DIM * VMD_RAMA_CLASSES;
+    uint64_t s4[4] = {0, 0, 0, 0};
+    if (frame_beg >= frame_end) {
+        if (values) std::fill(values, values + nmap, 0.0f);
+        if (sums) memcpy(sums, s4, sizeof(s4));
+        return true;
+    }
+    PropState* t = e->props[mi - 1].get();
+    std::lock_guard<std::mutex> lock(e->mtx);
+    HIP_OK(hipSetDevice(e->device));
+    // (a rank that has evaluated nothing itself still answers after a merge: the binning needs only the per-segment bytes)
+    if (!t->uploaded && (!t->d_rama_class.upload(t->prop.rama_class.data(), t->prop.rama_class.size(), e->stream) ||
+                         !t->d_rama_link.upload(t->prop.rama_link.data(), t->prop.rama_link.size(), e->stream))) return false;
+    const size_t nseg = t->prop.a.size(), F = frame_end - frame_beg;
+    if (!t->d_rama_scratch.ensure(nmap + 4) || !t->d_rama_mask.ensure(e->num_frames) || !t->d_values.ensure(nmap) || !t->d_max.ensure(1))
+        return false;
+    if (t->table_stale) {
+        HIP_OK(hipMemcpyAsync(t->d_table.p, t->values.data(), t->values.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        t->table_stale = false;
+    }
+    std::vector<uint8_t> mask(F);
+    for (size_t f = 0; f < F; ++f) mask[f] = mask_get(e->frame_mask, frame_beg + f);
+    HIP_OK(hipMemcpyAsync(t->d_rama_mask.p, mask.data(), F, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemsetAsync(t->d_rama_scratch.p, 0, (nmap + 4) * sizeof(uint64_t), e->stream));
+    // (rows beyond 2^31 - 1 entries per launch: in pieces)
+    const size_t step = std::max<size_t>(1, (size_t)0x7fffffff / nseg);
+    for (size_t f = 0; f < F; f += step) {
+        const size_t nf = std::min(step, F - f);
+        KRN_OK(vmd_hip_rama_bin(e->stream, t->d_table.p + (frame_beg + f) * 2 * nseg, (int)nf, t->d_rama_mask.p + f, (int)nseg,
+                t->d_rama_class.p, t->d_rama_link.p, e->spec.rama_skip_ends ? 1 : 0, t->d_rama_scratch.p, t->d_rama_scratch.p + nmap));
+    }
+    if (values) {
+        KRN_OK(vmd_hip_counts_to_float(e->stream, t->d_rama_scratch.p, nmap, t->d_values.p, t->d_max.p, 1.0f));
+        HIP_OK(hipMemcpyAsync(values, t->d_values.p, nmap * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_OK(hipMemcpyAsync(s4, t->d_rama_scratch.p + nmap, sizeof(s4), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (sums) memcpy(sums, s4, sizeof(s4));
+    return true;
 }
 
 // ---- the hot call -----------------------------------------------------------------------------------------------
@@ -861,6 +951,11 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
             HIP_OK(hipStreamSynchronize(e->stream));
         } else if (d.is_within_expr()) {
             // the lists live in the interned selections
+        } else if (d.is_rama()) {
+            // N, CA, C per segment and the per-segment bytes (the descriptor's vectors live as long as the eval)
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_b.upload(d.b.data(), d.b.size(), e->stream) ||
+                !p->d_c.upload(d.c.data(), d.c.size(), e->stream) || !p->d_rama_class.upload(d.rama_class.data(), d.rama_class.size(), e->stream)
+                || !p->d_rama_link.upload(d.rama_link.data(), d.rama_link.size(), e->stream)) return false;
         } else if (d.kind == PROP_DIST) {
             if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream)) return false;
             if (!p->d_b.upload(d.b.data(), d.b.size(), e->stream)) return false;

@@ -126,6 +126,7 @@ struct Options {
     std::atomic<int> spec_within_closed{0};        // DECISION(D-WITHIN-INTERVAL) flipped: hit iff r_min <= d <= r_max
     std::atomic<int> spec_shell_norm{0};           // DECISION(D-SHELL-NORM) flipped: S4 weights with the parent lists' sizes
     std::atomic<int> spec_within_exclude_ref{0};   // DECISION(D-WITHIN-SELF) flipped: the evaluator counts over T minus R
+    std::atomic<int> spec_rama_skip_ends{0};       // a segment that lacks phi or psi is not binned (VIAMD bins it at column / row 256)
                                                   // setting for matching an mdlib that does it this way, not a fast path)
     // D-RDF-NORM: 0 = cell volume when fully periodic, else the cutoff sphere; 1 = always the cutoff sphere;
     std::atomic<int> spec_rdf_norm{0};
@@ -356,7 +357,7 @@ struct HostBuf {
 };
 
 // ------------------------------------------------------------------------------------------------ IR
-enum PropKind { PROP_RDF = 0, PROP_SDF = 1, PROP_DIST = 2 };
+enum PropKind { PROP_RDF = 0, PROP_SDF = 1, PROP_DIST = 2, PROP_RAMA = 3 };
 
 // temporal properties of DESIGN S6b: PROP_DIST descriptors with three or four argument sets (dist_kind past vmd_distance_kind_t)
 enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
@@ -370,6 +371,10 @@ enum { GEOM_RMSD = 7 };
 enum { GEOM_WITHIN = 8 };
 // `name = count(T and <and / or / not over within() terms>)`: one PROP_DIST descriptor, a = T, the terms in expr_terms
 enum { GEOM_WITHIN_EXPR = 9 };
+// `{table, map} = ramachandran(backbone)`: two descriptors in a row.  The angle table is a PROP_DIST descriptor - a = N, b = CA,
+// c = C per segment, aoff = the range offsets, rama_class / rama_link one byte per segment - whose rows are {phi, psi} per segment; the
+// map behind it is a PROP_RAMA descriptor (K = the segments, for the merge's count bound) that the table's launch bins into
+enum { GEOM_RAMA = 10 };
 
 struct Property {
     std::string name;
@@ -397,6 +402,8 @@ struct Property {
     std::vector<ExprTerm> expr_terms;
     uint32_t expr_truth = 0;
     bool is_within_expr() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN_EXPR; }
+    std::vector<uint8_t> rama_class, rama_link;     // ramachandran table: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
+    bool is_rama() const { return kind == PROP_DIST && dist_kind == GEOM_RAMA; }
     bool is_expr_sdf() const { return kind == PROP_SDF && !expr_terms.empty(); }
 };
 
@@ -562,6 +569,12 @@ struct PropState {
     // rdf over shells: the interned shell of either side (-1: that side is its static list, sel_a / sel_b)
     int shell_of[2] = {-1, -1};
     int expr_of = -1;                   // a count or an sdf over a shell expression: the interned ShellExpr
+    // ramachandran table: the whole angle table on the device, [num_frames][nseg][2] - batches write their rows, the filtered
+    // map (vmd_eval_rama_density) bins from it -, the per-segment bytes, and the scratch of a filtered map (the map, 4 sums, the frame mask)
+    DevBuf<float> d_table;
+    DevBuf<uint8_t> d_rama_class, d_rama_link, d_rama_mask;
+    DevBuf<uint64_t> d_rama_scratch;
+    bool table_stale = false;           // host rows arrived from elsewhere (a source's blocks, a merge): upload them before the next query
     bool uploaded = false;
     bool pinned = false;
     bool dirty = false;                 // device accumulators changed since the last host refresh
@@ -846,7 +859,7 @@ struct vmd_script_eval_t {
     // fixed at creation
     struct Spec { bool rdf_closed = false, sdf_include_self = false, sdf_density = false, dist_geometric_com = false, rdf_raw = false;
             int rdf_norm = 0; bool angle_radians = false; bool within_closed = false, within_exclude_ref = false;
-            bool shell_norm = false; } spec;
+            bool shell_norm = false; bool rama_skip_ends = false; } spec;
     size_t atoms_checked = (size_t)-1;       // trajectory atom count the properties' indices were validated against (under mtx)
 };
 
@@ -1034,6 +1047,7 @@ struct RangeRun {
     bool launch_shape(BatchCtx& c, size_t pi);
     bool launch_rmsd(BatchCtx& c, PropState* p);
     bool launch_geometry(BatchCtx& c, PropState* p);
+    bool launch_rama(BatchCtx& c, size_t pi);
     bool launch_distance(BatchCtx& c, PropState* p);
     bool launch_property(BatchCtx& c, size_t pi);
 };

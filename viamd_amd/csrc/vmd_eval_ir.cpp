@@ -30,6 +30,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         }
         else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
         else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
+        else if (p.is_rama()) w += 3 * (uint64_t)p.a.size();                             // N, CA, C of every segment
         else if (p.is_within()) w += (uint64_t)p.a.size() + (uint64_t)p.b.size();        // |T| + |R|: a neighbour query, not all pairs
         else if (p.is_within_expr()) { w += (uint64_t)p.a.size(); for (auto& t : p.expr_terms) w += (uint64_t)t.ref.size(); }     // |T| + sum |R_i|
         else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
@@ -381,6 +382,48 @@ extern "C" bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name,
     return true;
 }
 
+// `{table, map} = ramachandran(backbone)`: the angle table and the density map, two descriptors in a row
+extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* bb) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names || !bb) return vmd_fail("ramachandran needs two property names and a backbone");
+    for (int k = 0; k < 2; ++k) if (!ir_name_ok(ir, names[k])) return false;
+    if (!strcmp(names[0], names[1])) return vmd_fail("property '%s' already defined", names[1]);
+    const size_t nseg = bb->num_segments;
+    if (nseg == 0) return vmd_fail("ramachandran backbone has no segment");
+    if (nseg > 0x3fffffff) return vmd_fail("ramachandran backbone too large");
+    if (!bb->n || !bb->ca || !bb->c) return vmd_fail("ramachandran backbone has a NULL atom list");
+    if (!idx_ok(bb->n, nseg, "backbone N list") || !idx_ok(bb->ca, nseg, "backbone CA list") || !idx_ok(bb->c, nseg, "backbone C list"))
+        return false;
+    if (!bb->range_offsets || bb->num_ranges == 0) return vmd_fail("ramachandran backbone has no range offsets");
+    if (bb->range_offsets[0] != 0) return vmd_fail("backbone range offsets must start at 0");
+    for (size_t r = 0; r < bb->num_ranges; ++r)
+        if (bb->range_offsets[r + 1] <= bb->range_offsets[r]) return vmd_fail("backbone range %zu is empty (offsets must increase)", r);
+    if (bb->range_offsets[bb->num_ranges] != nseg)
+        return vmd_fail("backbone range offsets end at %u, not at the %zu segments", bb->range_offsets[bb->num_ranges], nseg);
+    if (bb->rama_class)
+        for (size_t s = 0; s < nseg; ++s)
+            if (bb->rama_class[s] > 3 && bb->rama_class[s] != 255)
+                return vmd_fail("backbone segment %zu has class %u (0..3 or 255)", s, (unsigned)bb->rama_class[s]);
+    Property t;
+    t.name = names[0]; t.kind = PROP_DIST; t.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    t.dist_kind = GEOM_RAMA;
+    t.a.assign(bb->n, bb->n + nseg); t.b.assign(bb->ca, bb->ca + nseg); t.c.assign(bb->c, bb->c + nseg);
+    t.aoff.assign(bb->range_offsets, bb->range_offsets + bb->num_ranges + 1);
+    if (bb->rama_class) t.rama_class.assign(bb->rama_class, bb->rama_class + nseg); else t.rama_class.assign(nseg, 0);
+    t.rama_link.assign(nseg, 3);
+    for (size_t r = 0; r < bb->num_ranges; ++r) {
+        t.rama_link[bb->range_offsets[r]] &= (uint8_t)~1u;
+        t.rama_link[bb->range_offsets[r + 1] - 1] &= (uint8_t)~2u;
+    }
+    Property m;
+    m.name = names[1]; m.kind = PROP_RAMA; m.flags = VMD_PROPERTY_FLAG_MAP;
+    m.K = nseg;
+    ir->props.push_back(std::move(t));
+    ir->props.push_back(std::move(m));
+    ir->rebuild_names();
+    return true;
+}
+
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
 extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap) {
@@ -398,6 +441,14 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
             size_t n = 0;
             for (auto& t : p.expr_terms) for (int32_t i : t.ref) { if (out && n < cap) out[n] = i; n += 1; }
             for (int32_t i : p.a) { if (out && n < cap) out[n] = i; n += 1; }
+            return n;
+        }
+        if (p.is_rama()) {     // N, CA, C of the segment(s)
+            if (context >= (int64_t)p.a.size()) return 0;
+            const size_t s0 = context < 0 ? 0 : (size_t)context, s1 = context < 0 ? p.a.size() : (size_t)context + 1;
+            size_t n = 0;
+            for (size_t sg = s0; sg < s1; ++sg)
+                for (const auto* v : {&p.a, &p.b, &p.c}) { if (out && n < cap) out[n] = (*v)[sg]; n += 1; }
             return n;
         }
         if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape() && !p.is_rmsd())) return 0;
@@ -439,6 +490,7 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
         h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
         if (p.is_shape()) h = fnv1a(h, &p.shape_comp, sizeof(int));     // shape_weights only, as above
+        if (p.is_rama()) h = fnv1a(h, p.rama_class.data(), p.rama_class.size());     // ramachandran only, as above
         for (int k = 0; k < 2; ++k) {                                   // rdf / sdf over shells only, as above
             if (!p.shell[k].on) continue;
             const int32_t side = 0x5348454c + k;                        // "SHEL": which side carries the shell

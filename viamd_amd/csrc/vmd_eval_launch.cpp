@@ -504,6 +504,28 @@ bool RangeRun::launch_geometry(BatchCtx& c, PropState* p) {
     return true;
 }
 
+// ramachandran: phi / psi of the batch into its rows of the device table, then those rows binned into the map behind the
+// table - per sub, so that a frame block's samples land in its own partial.  The rows travel to the host from the table (queue_batch).
+// No cell grid, no overflow flag; a frame evaluated twice is counted twice, as an sdf volume counts it.
+bool RangeRun::launch_rama(BatchCtx& c, size_t pi) {
+    PropState* p = e->props[pi].get();
+    if (pi + 1 >= e->props.size() || e->props[pi + 1]->prop.kind != PROP_RAMA)
+        return vmd_fail("ramachandran table '%s' has lost its map", p->prop.name.c_str());
+    PropState* m = e->props[pi + 1].get();
+    const size_t nseg = p->prop.a.size();
+    float* rows = p->d_table.p + c.f0 * p->dim1;
+    e->prof.begin("backbone_angles", e->stream);
+    KRN_OK(vmd_hip_backbone_angles(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
+            (int)nseg, p->d_a.p, p->d_b.p, p->d_c.p, p->d_rama_link.p, rows));
+    e->prof.end(e->stream);
+    e->prof.begin("rama_bin", e->stream);
+    for (auto& su : c.subs)
+        KRN_OK(vmd_hip_rama_bin(e->stream, rows + su.off * p->dim1, (int)su.nb, nullptr, (int)nseg, p->d_rama_class.p, p->d_rama_link.p,
+                e->spec.rama_skip_ends ? 1 : 0, acc_of(m, su), nullptr));
+    e->prof.end(e->stream);
+    return true;
+}
+
 bool RangeRun::launch_distance(BatchCtx& c, PropState* p) {
     e->prof.begin("distance", e->stream);
     KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
@@ -523,6 +545,9 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     // sdf over a shell, within count: launched by launch_rdf, behind the batch's cell builds
     if (d.is_shell_sdf() || d.is_within() || d.is_within_expr() || d.is_expr_sdf()) return true;     // (... and shell expressions)
     if (d.kind == PROP_SDF) { VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0); }
+    // ramachandran: the table's launch also fills the map that follows it
+    if (d.kind == PROP_RAMA) return true;
+    if (d.is_rama()) return launch_rama(c, pi);
     if (!p->d_out.ensure(c.nb * p->dim1)) return false;
     if (d.is_shape()) return launch_shape(c, pi);
     if (d.is_rmsd()) return launch_rmsd(c, p);

@@ -312,8 +312,8 @@ bool RangeRun::queue_batch(size_t bi) {
         if (!launch_property(c, pi)) return false;
         // (a within count's rows are sent by launch_rdf, behind the overflow flag)
         if (p->prop.kind == PROP_DIST && !p->prop.is_within() && !p->prop.is_within_expr())
-            HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * p->dim1 * sizeof(float),
-                    hipMemcpyDeviceToHost, e->stream));
+            HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->prop.is_rama() ? p->d_table.p + c.f0 * p->dim1
+                    : p->d_out.p, c.nb * p->dim1 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         p->dirty = p->dirty || !spec;
     }
     if (defer) {
@@ -442,7 +442,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
     if (views) {
         for (auto& p : e->props) {
             if (!p->dirty) continue;
-            if (p->prop.kind == PROP_SDF) { if (!refresh_volume(e, p.get())) return false; }
+            if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) { if (!refresh_volume(e, p.get())) return false; }
             else if (p->prop.kind == PROP_DIST) refresh_temporal_stats(e, p.get());
         }
         e->views_at = std::chrono::steady_clock::now();

@@ -99,6 +99,7 @@ extern "C" int vmd_set_option(const char* key, int value) {
     else if (!strcmp(key, "spec_rdf_norm")) o = &g_opt.spec_rdf_norm;
     else if (!strcmp(key, "spec_within_closed")) o = &g_opt.spec_within_closed;
     else if (!strcmp(key, "spec_within_exclude_ref")) o = &g_opt.spec_within_exclude_ref;
+    else if (!strcmp(key, "spec_rama_skip_ends")) o = &g_opt.spec_rama_skip_ends;
     else if (!strcmp(key, "spec_shell_norm")) o = &g_opt.spec_shell_norm;
     else if (!strcmp(key, "rdf_blocks_decode")) o = &g_opt.rdf_blocks_decode;
     else if (!strcmp(key, "rdf_classes")) o = &g_opt.rdf_classes;

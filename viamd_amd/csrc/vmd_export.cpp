@@ -87,6 +87,11 @@ extern "C" bool vmd_export_csv(const char* path, const float* const* columns, co
 //   distribution (:5998-6020)  x = sample_range(hist.x_min, hist.x_max, num_bins) labelled with the x unit string (unit_str[0]); y = the
 //                              display histogram labelled `name`, or "name (<unit_str[0]>)" when unit_str[1] is not empty - the reference
 //                              prints `dp.unit_str`, which decays to unit_str[0] (:6003); kept as it is
+// a MAP property by its public record: dim = {1, 4, 512, 512} (a volume is {1, 128, 128, 128})
+static bool is_class_map(const vmd_script_property_data_t* pd) {
+    return pd->dim[1] == VMD_RAMA_MAP_CLASSES && pd->dim[2] == VMD_RAMA_MAP_DIM && pd->dim[3] == VMD_RAMA_MAP_DIM;
+}
+
 // pinned to the reference's own export_csv / export_xvg / sample_range by tests/native/ref_callsites.cpp
 extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* eval, const char* name, const char* format,
                                           const double* frame_times, const char* time_unit, int num_bins) {
@@ -124,6 +129,8 @@ extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* e
             cols.push_back(std::move(c));
             labels.push_back(D > 1 ? std::string(name) + "[" + std::to_string(i + 1) + "]" : unit_y[0] ? std::string(name) + " (" + unit_y + ")" : std::string(name));
         }
+    } else if (is_class_map(pd)) {
+        return exp_fail(std::string("Export: '") + name + "' is a Ramachandran map; export its angle table instead");
     } else {
         return exp_fail(std::string("Export: '") + name + "' is a volume; use vmd_export_cube");
     }
@@ -178,6 +185,7 @@ extern "C" bool vmd_export_cube(const char* path, vmd_script_eval_t* eval, const
     if (!vmd_eval_wait_settled(eval)) return false;
     const vmd_script_property_data_t* pd = vmd_eval_property_data(eval, name);
     if (!pd) return exp_fail("Export Cube: The property to be exported did not exist");
+    if (is_class_map(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is a Ramachandran map, not a volume");
     vmd_sdf_payload_t vis;
     if (!vmd_eval_sdf_payload(eval, name, sys, traj, frame, &vis)) return exp_fail(std::string("Failed to visualize volume for export. ") + vmd_last_error());
     if (!vmd_eval_finalize(eval)) return false;         // the float view VIAMD reads (prop_data->values) is current

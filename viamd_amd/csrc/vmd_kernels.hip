@@ -3277,6 +3277,113 @@ __global__ __launch_bounds__(64) void k_geom(vmd_geom_params_t p) {
     p.out[t] = p.radians ? (float)rad : (float)(rad * (180.0 / M_PI));
 }
 
+// ------------------------------------------------------------------------------------------------ K10: backbone phi / psi, Ramachandran map
+
+struct vmd_bb_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* n; const int32_t* ca; const int32_t* c; const uint8_t* link; int nseg;
+    float* out;   // [B][nseg][2]
+};
+
+typedef float vmd_f2a __attribute__((vector_size(8)));     // {phi, psi}: one 8-byte access (the table's rows are 8-byte aligned)
+
+// fp32 minimum-image bond vector q - p of two raw positions: k_geom<4>'s d[k]
+__device__ __forceinline__ void vmd_bb_bond(const vmd_box_t& bx, const float p[3], const float q[3], float d[3]) {
+    d[0] = q[0] - p[0]; d[1] = q[1] - p[1]; d[2] = q[2] - p[2];
+    vmd_mi3_rintf(bx, d[0], d[1], d[2]);
+}
+
+// k_geom<4>'s value from its three bond vectors and their two normals n1 = b1 x b2, n2 = b2 x b3, in radians
+__device__ __forceinline__ float vmd_bb_dihedral(const float b1[3], const float b2[3], const double n1[3], const double n2[3]) {
+    const double l2 = sqrt(vmd_dot_d(b2[0], b2[1], b2[2], b2[0], b2[1], b2[2]));
+    const double y = l2 * vmd_dot_d(b1[0], b1[1], b1[2], n2[0], n2[1], n2[2]);
+    return (float)atan2(y + 0.0, vmd_dot_d(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2]) + 0.0);
+}
+
+// one thread per (frame, segment), the segment fastest: five gathers, four bond vectors, three normals (the one of N-CA-C serves both
+// angles), two atan2, one 8-byte store.  A single-atom set of k_geom is the atom's raw position (vmd_set_com: w x / w is exact), so phi and
+// psi are dihedral()'s values bit for bit.  DECISION(D-BB-ENDS): the angle that lacks its neighbour is +0.
+__global__ __launch_bounds__(64) void k_backbone_angles(vmd_bb_params_t p) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.B * p.nseg) return;
+    const int b = t / p.nseg, s = t - b * p.nseg;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const unsigned lk = p.link[s];
+    const bool prev = (lk & 1u) && s > 0, next = (lk & 2u) && s + 1 < p.nseg;
+    const int in = p.n[s], ia = p.ca[s], ic = p.c[s];
+    const float N[3] = {fx[in], fy[in], fz[in]}, A[3] = {fx[ia], fy[ia], fz[ia]}, C[3] = {fx[ic], fy[ic], fz[ic]};
+    float b1[3], b2[3];
+    vmd_bb_bond(bx, N, A, b1);
+    vmd_bb_bond(bx, A, C, b2);
+    double nm[3];
+    vmd_cross_d(b1[0], b1[1], b1[2], b2[0], b2[1], b2[2], nm[0], nm[1], nm[2]);
+    float phi = 0.0f, psi = 0.0f;
+    if (prev) {
+        const int ip = p.c[s - 1];
+        const float Cp[3] = {fx[ip], fy[ip], fz[ip]};
+        float b0[3];
+        double n0[3];
+        vmd_bb_bond(bx, Cp, N, b0);
+        vmd_cross_d(b0[0], b0[1], b0[2], b1[0], b1[1], b1[2], n0[0], n0[1], n0[2]);
+        phi = vmd_bb_dihedral(b0, b1, n0, nm);
+    }
+    if (next) {
+        const int iq = p.n[s + 1];
+        const float Nn[3] = {fx[iq], fy[iq], fz[iq]};
+        float b3[3];
+        double n3[3];
+        vmd_bb_bond(bx, C, Nn, b3);
+        vmd_cross_d(b2[0], b2[1], b2[2], b3[0], b3[1], b3[2], n3[0], n3[1], n3[2]);
+        psi = vmd_bb_dihedral(b1, b2, nm, n3);
+    }
+    vmd_f2a o;
+    o[0] = phi; o[1] = psi;
+    *(vmd_f2a*)(p.out + 2 * (size_t)t) = o;
+}
+
+struct vmd_rama_params_t {
+    const float* angles; int F; int nseg;
+    const uint8_t* row_mask; const uint8_t* rama_class; const uint8_t* link; int skip_ends;
+    unsigned long long* counts; unsigned long long* sums;
+};
+
+// DECISION(D-RAMA-BIN): the reference's fp32 expression, every operation rounded on its own (this file is compiled without contraction);
+// u lies in [0, 1], and u = 1 (phi = fl32(pi)) wraps to column 0
+__device__ __forceinline__ unsigned vmd_rama_coord(float a) {
+    const float scale = (float)(1.0 / (2.0 * M_PI));
+    const float u = (a * scale) + 0.5f;
+    return (unsigned)(u * (float)VMD_RAMA_DIM) & (unsigned)(VMD_RAMA_DIM - 1);
+}
+
+// one thread per table entry: one no-return 64-bit atomic per binned sample, the class sums through a ballot per class (one atomic per
+// wave and class).  No lane leaves before the ballots.
+__global__ __launch_bounds__(256) void k_rama_bin(vmd_rama_params_t p) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = t < (long long)p.F * p.nseg;
+    int cls = -1;
+    unsigned x = 0, y = 0;
+    if (live) {
+        const int r = (int)(t / p.nseg), s = (int)(t - (long long)r * p.nseg);
+        const unsigned c = p.rama_class[s];
+        bool go = c < (unsigned)VMD_RAMA_CLASSES && (!p.row_mask || p.row_mask[r] != 0);
+        if (go && p.skip_ends) go = (p.link[s] & 3u) == 3u;
+        if (go) {
+            const vmd_f2a a = *(const vmd_f2a*)(p.angles + 2 * (size_t)t);
+            if (!(a[0] == 0.0f && a[1] == 0.0f)) { cls = (int)c; x = vmd_rama_coord(a[0]); y = vmd_rama_coord(a[1]); }
+        }
+    }
+    if (cls >= 0) atomicAdd(&p.counts[((size_t)y * VMD_RAMA_DIM + x) * VMD_RAMA_CLASSES + (unsigned)cls], 1ull);
+    if (!p.sums) return;
+    for (int c = 0; c < VMD_RAMA_CLASSES; ++c) {
+        const unsigned long long m = __ballot(cls == c ? 1 : 0);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.sums[c], (unsigned long long)__popcll(m));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ K5c: shape_weights
 
 // The reduction order is a function of the set size alone: a set is cut into chunks of VMD_SHAPE_CHUNK atoms; atom j of a chunk belongs to
@@ -4459,6 +4566,27 @@ extern "C" int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_str
     const dim3 g((unsigned)(((long long)B * P + 63) / 64));
     if (nargs == 3) hipLaunchKernelGGL((k_geom<3>), g, dim3(64), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((k_geom<4>), g, dim3(64), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_backbone_angles(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                       uint32_t pbc_flags, int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c,
+                                       const uint8_t* link, float* out) {
+    if (B <= 0 || nseg <= 0) return 0;
+    if (!xyz || !boxes || !n || !ca || !c || !link || !out || (long long)B * nseg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    vmd_bb_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, n, ca, c, link, nseg, out};
+    hipLaunchKernelGGL(k_backbone_angles, dim3((unsigned)(((long long)B * nseg + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_rama_bin(void* stream, const float* angles, int F, const uint8_t* row_mask, int nseg, const uint8_t* rama_class,
+                                const uint8_t* link, int skip_ends, uint64_t* counts, uint64_t* sums) {
+    if (F <= 0 || nseg <= 0) return 0;
+    if (!angles || !rama_class || !link || !counts || (long long)F * nseg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    vmd_rama_params_t p{angles, F, nseg, row_mask, rama_class, link, skip_ends, (unsigned long long*)counts, (unsigned long long*)sums};
+    hipLaunchKernelGGL(k_rama_bin, dim3((unsigned)(((long long)F * nseg + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

@@ -915,3 +915,53 @@ extern "C" size_t vmd_script_report_skipped_count(const vmd_script_report_t* r) 
 extern "C" const vmd_script_skipped_t* vmd_script_report_skipped(const vmd_script_report_t* r) { return r && !r->r.view.empty() ? r->r.view.data() : nullptr; }
 extern "C" const char* vmd_script_report_fallback_source(const vmd_script_report_t* r) { return r ? r->r.fallback_source.c_str() : ""; }
 extern "C" void vmd_script_report_free(vmd_script_report_t* r) { delete r; }
+
+// ---- a backbone from a topology (DECISION D-BB-TOPOLOGY): for hosts without mdlib's protein_backbone.  Names only - no
+// coordinates, no bond test: a segment is a residue that owns atoms named "N", "CA" and "C" (the first of each), a range a maximal run of
+// such residues with consecutive residue_index.
+struct vmd_backbone_owned_t {
+    std::vector<int32_t> n, ca, c;
+    std::vector<uint32_t> offsets;
+    std::vector<uint8_t> cls;
+    vmd_backbone_t view;
+};
+
+extern "C" vmd_backbone_owned_t* vmd_topology_backbone(const vmd_topology_t* topology) {
+    if (!topology) { vmd_set_last_error("vmd_topology_backbone: topology is NULL"); return nullptr; }
+    try {
+        Topo topo(topology);
+        auto bb = std::make_unique<vmd_backbone_owned_t>();
+        std::vector<size_t> seg_res;
+        for (size_t r = 0; r < topo.nres; ++r) {
+            int32_t at[3] = {-1, -1, -1};
+            static const char* const want[3] = {"N", "CA", "C"};
+            for (int32_t i : topo.res_atoms[r])
+                for (int k = 0; k < 3; ++k) if (at[k] < 0 && topo.names[i] == want[k]) at[k] = i;
+            if (at[0] < 0 || at[1] < 0 || at[2] < 0) continue;
+            if (seg_res.empty() || seg_res.back() + 1 != r) bb->offsets.push_back((uint32_t)seg_res.size());
+            seg_res.push_back(r);
+            bb->n.push_back(at[0]); bb->ca.push_back(at[1]); bb->c.push_back(at[2]);
+        }
+        const size_t nseg = seg_res.size();
+        bb->offsets.push_back((uint32_t)nseg);
+        bb->cls.assign(nseg, 0);
+        for (size_t s = 0; s < nseg; ++s) {
+            const std::string rn = upper(topo.residue_name(seg_res[s]));
+            const bool next_pro = s + 1 < nseg && seg_res[s + 1] == seg_res[s] + 1 && upper(topo.residue_name(seg_res[s + 1])) == "PRO";
+            bb->cls[s] = rn == "GLY" ? 1 : rn == "PRO" ? 2 : next_pro ? 3 : 0;
+        }
+        bb->view.num_segments = nseg;
+        bb->view.n = bb->n.data(); bb->view.ca = bb->ca.data(); bb->view.c = bb->c.data();
+        bb->view.num_ranges = bb->offsets.size() - 1;
+        bb->view.range_offsets = bb->offsets.data();
+        bb->view.rama_class = bb->cls.data();
+        return bb.release();
+    } catch (const std::exception& e) {
+        vmd_set_last_error(e.what());
+        return nullptr;
+    }
+}
+
+extern "C" const vmd_backbone_t* vmd_backbone_view(const vmd_backbone_owned_t* backbone) { return backbone ? &backbone->view : nullptr; }
+
+extern "C" void vmd_backbone_free(vmd_backbone_owned_t* backbone) { delete backbone; }

@@ -233,6 +233,25 @@ class ScriptIR:
         r, rp = _idx(ref)
         self._check(self.lib.vmd_ir_add_within_count(self.h, name.encode(), tp, t.size, rp, r.size, float(rmin), float(rmax)))
 
+    def add_ramachandran(self, names, n, ca, c, range_offsets, rama_class=None):
+        """`{table, map} = ramachandran(backbone)`: names = (angle table, density map); n / ca / c: the backbone atoms per
+        segment; range_offsets: num_ranges + 1 segment offsets of the chains; rama_class: one byte per segment, 0..3 = general, glycine,
+        proline, pre-proline, 255 = never binned (None: all general)."""
+        names = list(names)
+        assert len(names) == 2, "ramachandran defines two properties"
+        n_, np_ = _idx(n)
+        a_, ap = _idx(ca)
+        c_, cp = _idx(c)
+        if not (n_.size == a_.size == c_.size):
+            raise ValueError("n, ca and c must list one atom per segment each")
+        off = np.ascontiguousarray(range_offsets, dtype=np.uint32).reshape(-1)
+        cls = None if rama_class is None else np.ascontiguousarray(rama_class, dtype=np.uint8).reshape(-1)
+        if cls is not None and cls.size != n_.size:
+            raise ValueError("rama_class must hold one byte per segment")
+        bb = L.BackboneC(n_.size, np_, ap, cp, max(off.size, 1) - 1, off.ctypes.data_as(C.POINTER(C.c_uint32)) if off.size else None,
+                         cls.ctypes.data_as(L.c_uint8_p) if cls is not None else None)
+        self._check(self.lib.vmd_ir_add_ramachandran(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(bb)))
+
     @staticmethod
     def _names3(names):
         import ctypes as C
@@ -313,6 +332,23 @@ class PropertyDataView:
             raise VmdError(self._ev.lib.last_error())
         n = self.c.dim[2] if self.c.weights else self.c.dim[1] * self.c.dim[2] * self.c.dim[3]
         return self._arr(self.c.counts, n, np.uint64)
+
+    @property
+    def is_map(self):
+        """a Ramachandran class map (VMD_PROPERTY_FLAG_MAP): dim = (1, 4, 512, 512), channel fastest"""
+        return tuple(self.c.dim) == (1, L.RAMA_MAP_CLASSES, L.RAMA_MAP_DIM, L.RAMA_MAP_DIM)
+
+    @property
+    def map_values(self):
+        """a MAP property's float view as [y, x, class]"""
+        assert self.is_map
+        return self.values.reshape(L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES)
+
+    @property
+    def map_counts(self):
+        """a MAP property's u64 accumulators as [y, x, class]"""
+        assert self.is_map
+        return self.counts.reshape(L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES)
 
     @property
     def weights64(self):
@@ -507,6 +543,16 @@ class ScriptEval:
         arr = (L.AccumView * n)()
         self.lib.vmd_eval_accum_views(self.h, arr, n)
         return list(arr)
+
+    def rama_density(self, name, frame_beg, frame_end):
+        """VIAMD's filtered Ramachandran map: the density of the evaluated frames of [frame_beg, frame_end), binned on the
+        device from the angle table it holds -> (values float32 [512, 512, 4] as [y, x, class], sums uint64 [4])"""
+        values = np.zeros((L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES), np.float32)
+        sums = np.zeros(L.RAMA_MAP_CLASSES, np.uint64)
+        if not self.lib.vmd_eval_rama_density(self.h, name.encode(), int(frame_beg), int(frame_end), values.ctypes.data_as(L.c_float_p),
+                                              sums.ctypes.data_as(L.c_uint64_p)):
+            raise VmdError(self.lib.last_error())
+        return values, sums
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""

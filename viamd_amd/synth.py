@@ -16,8 +16,10 @@ MASS = {"H": 1.008, "He": 4.0026, "Li": 6.94, "Be": 9.0122, "B": 10.81, "C": 12.
         "Pb": 207.2}
 
 
-def water_box_topology(n_atoms, n_blob=0, atoms_per_residue=10):
-    """Elements / residue names / residue indices / masses of the synthetic system: [blob residues][O,H,H waters]."""
+def water_box_topology(n_atoms, n_blob=0, atoms_per_residue=10, backbone_names=False):
+    """Elements / residue names / residue indices / masses of the synthetic system: [blob residues][O,H,H waters].
+    backbone_names=True: the atoms also carry names - N, CA, C, O, ... per blob residue, OW / HW in the waters - so that a backbone
+    can be read off the topology (script.backbone_from_topology); otherwise the names are the elements, as ever."""
     elements = np.empty(n_atoms, dtype="<U2")
     resnames = np.empty(n_atoms, dtype="<U4")
     resid = np.empty(n_atoms, np.int64)
@@ -34,7 +36,13 @@ def water_box_topology(n_atoms, n_blob=0, atoms_per_residue=10):
     mass = np.array([MASS[e] for e in ("C", "N", "O", "H")])
     lut = {"C": 0, "N": 1, "O": 2, "H": 3}
     m = mass[np.vectorize(lut.get)(elements)].astype(np.float32)
-    return Topology(elements, resnames, resid, mass=m)
+    names = None
+    if backbone_names:
+        names = np.empty(n_atoms, dtype="<U4")
+        blob_names = np.array(["N", "CA", "C", "O", "CB", "H", "HA", "HB1", "CG", "HG"])
+        names[:n_blob] = blob_names[b % atoms_per_residue % blob_names.size]
+        names[n_blob:] = np.where(w % 3 == 0, "OW", "HW")
+    return Topology(elements, resnames, resid, names=names, mass=m)
 
 
 def _rot(axis, ang):
