@@ -288,6 +288,73 @@ def test_self_rule_on_the_blob_system(emu_lib, oracle):
         assert not counts_of(emu_lib, [("n", o, o, 0.0, 3.5)], coords, 50.0)["n"].any()
 
 
+def brute_tile_edges(lib, device=False):
+    """the all-pairs loop at the edges of its 256-wide tile of R: one frame, a cubic periodic box of edge 60, range 0:2.0.  T: 130 atoms
+    3.0 apart on a line that winds through the cell in the plane z = 10 (three waves of the 64-wide kernel, more than half a block of the
+    256-wide one).  R: nref atoms parked in the plane z = 40, 30 from every target, but for ONE planted entry 1.0 above one target.
+    vmd_hip_within_brute, _brute_flags, _brute_atoms and _brute_expr (term 2, every lane live, the bytes preset to 1), and
+    vmd_hip_within_brute once more without a reference list (R are the frame's first atoms: NULL names them) -> cases checked"""
+    box, rmin, rmax, nt = 60.0, 0.0, 2.0, 130
+    bx = Box((box,) * 3 + (0.0,) * 3, 7)
+    step_y = 0.18                                      # the line passes itself 20 steps on, 3.6 further up: no two targets closer than 3.0
+    i = np.arange(nt)
+    tgt = np.stack([(1.0 + i * np.sqrt(9.0 - step_y ** 2)) % box, 5.0 + i * step_y, np.full(nt, 10.0)]).astype(np.float32)
+    d = tgt[:, :, None] - tgt[:, None, :]
+    d -= box * np.rint(d / box)
+    assert np.sqrt((d * d).sum(0))[~np.eye(nt, dtype=bool)].min() > 2.999
+    cases, checked = [], 0
+    for nref in (1, 255, 256, 257, 512, 513):
+        cases += [(nref, j) for j in sorted({0, nref - 1} | {j for j in (255, 256) if j < nref})]
+    cases.append((257, None))
+    for nref, planted in cases:
+        N = nt + nref
+        R, T = np.arange(nref, dtype=np.int32), np.arange(nref, N, dtype=np.int32)
+        k = np.arange(nref)
+        xyz = np.concatenate([np.stack([1.0 + 0.25 * (k % 32), 1.0 + 0.25 * (k // 32), np.full(nref, 40.0)]).astype(np.float32), tgt], axis=1)
+        at = None
+        if planted is not None:
+            at = (0, 63, 64, 129)[checked % 4]
+            xyz[:, planted] = tgt[:, at] + np.float32([0.0, 0.0, 1.0])
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        want = np.zeros(nt, bool)
+        if at is not None:
+            want[at] = True
+        # the placement, from the restatement alone: exactly the planted member
+        assert np.array_equal(W.hits(xyz, bx, T, R, rmin, rmax, False, False), want), (nref, planted, at)
+        host = dict(xyz=xyz, b9=box9(box), T=T, R=R, cnt=np.full(4, 77, np.uint32), fl=np.full(nt, 9, np.uint8), mb=np.zeros(N, np.uint8),
+                    bits=np.ones(N, np.uint8))
+        if device:
+            import torch
+            dev = {k: torch.from_numpy(v.view(np.int32) if v.dtype == np.uint32 else v).cuda() for k, v in host.items()}
+            torch.cuda.synchronize()
+            p = {k: v.data_ptr() for k, v in dev.items()}
+        else:
+            p = {k: v.ctypes.data for k, v in host.items()}
+        head = (None, p["xyz"], 3 * N, N, p["b9"], 7, 1, p["T"], nt, p["R"], nref, rmin, rmax, 0)
+        assert lib.vmd_hip_within_brute(*head, p["cnt"]) == 0
+        assert lib.vmd_hip_within_brute_flags(*head, p["cnt"] + 4, p["fl"]) == 0
+        assert lib.vmd_hip_within_brute_atoms(*head, p["cnt"] + 8, p["mb"], N) == 0
+        assert lib.vmd_hip_within_brute_expr(*head, 2, 0xffff, p["bits"], N, None) == 0
+        assert lib.vmd_hip_within_brute(*head[:9], None, *head[10:], p["cnt"] + 12) == 0
+        if device:
+            torch.cuda.synchronize()
+            out = {k: dev[k].cpu().numpy() for k in ("cnt", "fl", "mb", "bits")}
+        else:
+            out = host
+        what = (nref, planted, at)
+        by_atom = np.zeros(N, bool); by_atom[nref:] = want
+        assert [int(v) for v in out["cnt"]] == [int(want.sum())] * 4, (what, out["cnt"])
+        assert np.array_equal(out["fl"], want.astype(np.uint8)), what
+        assert np.array_equal(out["mb"], by_atom.astype(np.uint8)), what
+        assert np.array_equal(out["bits"], np.where(by_atom, 1 | 4, 1).astype(np.uint8)), what
+        checked += 1
+    return checked
+
+
+def test_brute_tile_edges_on_the_emulator(emu_lib):
+    assert brute_tile_edges(emu_lib) == 17
+
+
 # ---- 4. script level ---------------------------------------------------------------------------------------------------------------------
 
 BLOB_SCRIPT = ("a = count(water and element('O') and within(3.5, not water));\n"

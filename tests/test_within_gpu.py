@@ -29,6 +29,10 @@ def test_both_kernels_on_the_blob_system(gpu_lib, oracle):
     TW.kernels_on_the_blob(gpu_lib, oracle, device=True, F=4)
 
 
+def test_brute_tile_edges(gpu_lib):
+    assert TW.brute_tile_edges(gpu_lib, device=True) == 17
+
+
 def test_scripts_every_frame(gpu_lib, oracle):
     coords, topo = TW.blob12k(oracle, 4)
     TW.script_parity(gpu_lib, coords, topo, TW.BLOB_SCRIPT, 50.0, device=True)

@@ -1018,6 +1018,11 @@ struct RangeRun {
     uint64_t* acc_of(PropState* p, const Sub& sb) const {
         return (sb.blk >= 0 && p->ncounts) ? p->d_blocks.p + (size_t)sb.blk * p->ncounts : p->d_counts.p;
     }
+    // a temporal property's rows of this batch, on their way to the host behind what the eval's stream holds (launch_rdf's counts)
+    bool queue_temporal_rows(BatchCtx& c, int pi, const float* d_rows) {
+        HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], d_rows, c.nb * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        return true;
+    }
     // vmd_eval_range.cpp
     bool prepare_reference_poses();
     void plan_range(const std::vector<std::pair<size_t, size_t>>& segments);
@@ -1027,6 +1032,7 @@ struct RangeRun {
     // vmd_eval_launch.cpp
     int grid_for(BatchCtx& c, size_t lanes, float r, vmd_grid_t* grid, const float** d_gb);
     bool build_pair(BatchCtx& c, Selection* a, Selection* b, const float* d_gb, const vmd_grid_t& grid);
+    int within_route(BatchCtx& c, Selection* st, Selection* sr, float r, bool atom_order, vmd_grid_t* grid, const float** d_gb);
     bool pair_fork();
     bool pair_join();
     template <class OnRow>

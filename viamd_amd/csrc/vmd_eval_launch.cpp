@@ -28,6 +28,17 @@ bool RangeRun::build_pair(BatchCtx& c, Selection* a, Selection* b, const float* 
     return build_selection(e, a, *c.src, d_gb, c.pbc, c.nb, grid) && (b == a || build_selection(e, b, *c.src, d_gb, c.pbc, c.nb, grid));
 }
 
+// Walk or all pairs for the shell within(.. r, R) of the targets T?  -> 1 the walk on *grid, the cell-sorted copy of R built (and T's where
+// the pass walks T sorted: a count); 0 all pairs from the raw frame; -1 an error.  atom_order couples two things: the pass keeps T in list
+// order, so R alone is sorted (masks, expression terms), AND the RULE measured for such passes applies - all pairs not only where no grid
+// exists for r but also when R has fewer than shell_brute_below atoms (480: DESIGN 1.8 measures where the two costs cross).
+int RangeRun::within_route(BatchCtx& c, Selection* st, Selection* sr, float r, bool atom_order, vmd_grid_t* grid, const float** d_gb) {
+    if (atom_order && (int)sr->idx.size() < g_opt.shell_brute_below.load()) return 0;
+    const int have_grid = grid_for(c, std::max(st->idx.size(), sr->idx.size()), r, grid, d_gb);
+    if (have_grid > 0 && !build_pair(c, atom_order ? sr : st, sr, *d_gb, *grid)) return -1;
+    return have_grid;
+}
+
 // pair_stream takes up behind what the eval's stream holds so far ...
 bool RangeRun::pair_fork() {
     HIP_OK(hipEventRecord(e->pair_fork, e->stream));
@@ -250,36 +261,30 @@ bool RangeRun::launch_within_counts(BatchCtx& c) {
             Selection* sr = e->sels[p->sel_b].get();
             vmd_grid_t grid;
             const float* d_gb = nullptr;
-            const int have_grid = grid_for(c, std::max(st->idx.size(), sr->idx.size()), d.rmax, &grid, &d_gb);
+            const int have_grid = within_route(c, st, sr, d.rmax, false, &grid, &d_gb);
             if (have_grid < 0) return false;
             if (have_grid) {
-                if (!build_pair(c, st, sr, d_gb, grid)) return false;
                 e->prof.begin("within_pencil", e->stream);
                 KRN_OK(vmd_hip_within_pencil(e->stream, sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, st->sorted.p,
                         st->cell_start.p, (int)st->idx.size(), st->nsel_pad, d_gb, (int)c.nb, grid, d.rmin, d.rmax,
                         e->spec.within_closed ? 1 : 0, c.pbc, p->d_within_count.p, e->d_overflow.p));
                 e->prof.end(e->stream);
-                KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, e->d_overflow.p));
             } else {
                 e->prof.begin("within_brute", e->stream);
                 KRN_OK(vmd_hip_within_brute(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc,
                         (int)c.nb, st->d_idx.p, (int)st->idx.size(), sr->d_idx.p, (int)sr->idx.size(), d.rmin, d.rmax,
                         e->spec.within_closed ? 1 : 0, p->d_within_count.p));
                 e->prof.end(e->stream);
-                KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, nullptr));
             }
+            KRN_OK(vmd_hip_within_to_float(e->stream, p->d_within_count.p, (int)c.nb, p->d_out.p, have_grid ? e->d_overflow.p : nullptr));
         }
-        HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * sizeof(float), hipMemcpyDeviceToHost,
-                e->stream));
+        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
     }
     return true;
 }
 
 // ---- sdfs over a shell target.  First every shell's mask in atom order, then, behind the LAST cell build of the batch,
-// alignment and masked scatter.  RULE for the mask: all pairs from the raw frame when R has fewer than shell_brute_below atoms (480:
-// the walk and the build of R cost the same whatever |R| is, all pairs is linear in it, and DESIGN 1.8 measures where they cross) or
-// when no grid exists for the shell radius; otherwise the walk over the cell-sorted copy of R on the grid a within count of the same
-// radius and lists would get.
+// alignment and masked scatter.  Walk or all pairs by within_route's RULE, on the grid a within count of the same radius and lists gets.
 bool RangeRun::launch_shell_masks(BatchCtx& c) {
     for (auto& h : e->shells) h->abuilt = 0;
     for (int pi : e->shell_sdf_props) {
@@ -297,12 +302,9 @@ bool RangeRun::launch_shell_masks(BatchCtx& c) {
         if (!h->acount.ensure(c.nb)) return false;
         vmd_grid_t grid;
         const float* d_gb = nullptr;
-        const int below = g_opt.shell_brute_below.load();
-        const int have_grid = (int)sr->idx.size() < below ? 0
-                : grid_for(c, std::max(st->idx.size(), sr->idx.size()), h->rmax, &grid, &d_gb);
+        const int have_grid = within_route(c, st, sr, h->rmax, true, &grid, &d_gb);
         if (have_grid < 0) return false;
         if (have_grid) {
-            if (!build_pair(c, sr, sr, d_gb, grid)) return false;
             e->prof.begin("shell_mask", e->stream);
             KRN_OK(vmd_hip_within_atoms(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, d_gb, c.pbc, (int)c.nb, st->d_idx.p,
                     (int)st->idx.size(), sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, grid, h->rmin, h->rmax,
@@ -335,12 +337,11 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
 }
 
 // ---- shell expressions: one pass per term over T in atom order, ascending |R_i|, then the finish.  Walk or all pairs per term
-// by launch_shell_masks' RULE; the cell-sorted copies come from build_pair, so one that another pass of the batch built on the same grid is
+// by within_route's RULE; the cell-sorted copies come from build_pair, so one that another pass of the batch built on the same grid is
 // reused.  The bits start clean in every batch and in every repeat of one; the counts travel to the host from here, like
 // launch_within_counts' rows and for the same reason.
 bool RangeRun::launch_shell_exprs(BatchCtx& c) {
     const bool skip = g_opt.shell_expr_skip.load() != 0;
-    const int below = g_opt.shell_brute_below.load();
     const int closed = e->spec.within_closed ? 1 : 0;
     for (auto& xp : e->exprs) {
         ShellExpr* x = xp.get();
@@ -362,11 +363,9 @@ bool RangeRun::launch_shell_exprs(BatchCtx& c) {
             Selection* sr = e->sels[tm.sel_r].get();
             vmd_grid_t grid;
             const float* d_gb = nullptr;
-            const int have_grid = (int)sr->idx.size() < below ? 0
-                    : grid_for(c, std::max(st->idx.size(), sr->idx.size()), tm.rmax, &grid, &d_gb);
+            const int have_grid = within_route(c, st, sr, tm.rmax, true, &grid, &d_gb);
             if (have_grid < 0) return false;
             if (have_grid) {
-                if (!build_pair(c, sr, sr, d_gb, grid)) return false;
                 e->prof.begin("shell_expr", e->stream);
                 KRN_OK(vmd_hip_within_atoms_expr(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, d_gb, c.pbc, (int)c.nb,
                         tt->d_idx.p, (int)tt->idx.size(), sr->sorted.p, sr->cell_start.p, (int)sr->idx.size(), sr->nsel_pad, grid, tm.rmin,
@@ -389,8 +388,7 @@ bool RangeRun::launch_shell_exprs(BatchCtx& c) {
         PropState* p = e->props[pi].get();
         if (!p->d_out.ensure(c.nb)) return false;
         KRN_OK(vmd_hip_within_to_float(e->stream, e->exprs[p->expr_of]->count.p, (int)c.nb, p->d_out.p, e->d_overflow.p));
-        HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->d_out.p, c.nb * sizeof(float), hipMemcpyDeviceToHost,
-                e->stream));
+        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
     }
     return true;
 }

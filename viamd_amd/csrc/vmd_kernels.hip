@@ -2051,8 +2051,29 @@ struct vmd_within_brute_params_t {
     size_t flag_stride;         // ATOMS instantiation: flags is u8[B][flag_stride] indexed by ATOM, flags[b][tgt[t]]
 };
 
-// all pairs from the raw frame (any cell, any cutoff): one lane per target atom, the reference set staged through LDS in tiles of 256, a
-// lane stops testing at its first hit.  One integer atomic per wave.  The device-side definition the cell walk below is tested against.
+// all pairs from the raw frame (any cell, any cutoff), the device-side definition the cell walk below is tested against: one lane per
+// target atom (xi, yi, zi; `active` false: a lane without one), the reference list staged through the caller's LDS tile 256 entries at a
+// time by the block's NT threads, a lane stops testing at its first hit.  Every thread of the block calls it: two barriers per tile.
+template <int NT>
+__device__ __forceinline__ bool vmd_within_all_pairs(float (&s_r)[3][256], const vmd_box_t& bx, const float* fx, const float* fy,
+        const float* fz, const int32_t* ref, int nref, const vmd_within_test_t& w, bool active, float xi, float yi, float zi) {
+    bool hit = false;
+    for (int j0 = 0; j0 < nref; j0 += 256) {
+        __syncthreads();
+        const int nj = nref - j0 < 256 ? nref - j0 : 256;
+        for (int jj = threadIdx.x; jj < nj; jj += NT) {
+            const int a = ref ? ref[j0 + jj] : j0 + jj;
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+        }
+        __syncthreads();
+        if (active && !hit)
+            for (int jj = 0; jj < nj && !hit; ++jj)
+                hit = vmd_within_hit(w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
+    }
+    return hit;
+}
+
+// One lane per target atom over vmd_within_all_pairs, one integer atomic per wave.
 // FLAGS: also one byte per list entry, in list order - the mask vmd_hip_rdf_brute_masked takes.
 // ATOMS (with FLAGS): the byte goes to the atom's place instead, the mask vmd_hip_sdf_scatter_masked takes where no grid exists.
 template <bool FLAGS, bool ATOMS = false>
@@ -2070,116 +2091,130 @@ __global__ __launch_bounds__(256) void k_within_brute(vmd_within_brute_params_t 
         const int a = p.tgt ? p.tgt[t] : t;
         vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi);
     }
-    bool hit = false;
-    for (int j0 = 0; j0 < p.nref; j0 += 256) {
-        __syncthreads();
-        const int j = j0 + threadIdx.x;
-        if (j < p.nref) {
-            const int a = p.ref ? p.ref[j] : j;
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][threadIdx.x], s_r[1][threadIdx.x], s_r[2][threadIdx.x]);
-        }
-        __syncthreads();
-        const int nj = p.nref - j0 < 256 ? p.nref - j0 : 256;
-        if (valid && !hit)
-            for (int jj = 0; jj < nj && !hit; ++jj)
-                hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
-    }
+    const bool hit = vmd_within_all_pairs<256>(s_r, bx, fx, fy, fz, p.ref, p.nref, p.w, valid, xi, yi, zi);
     if (FLAGS && ATOMS) { if (valid) p.flags[(size_t)b * p.flag_stride + (size_t)(p.tgt ? p.tgt[t] : t)] = hit ? 1 : 0; }
     else if (FLAGS) { if (valid) p.flags[(size_t)b * p.ntgt + t] = hit ? 1 : 0; }
     const unsigned long long m = __ballot(hit ? 1 : 0);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&p.count[b], (unsigned)__popcll(m));
 }
 
+// the cell walk's part of a kernel's parameters, as vmd_within_walk_fill writes it ...
+struct vmd_within_walk_params_t {
+    const float* sref; const uint32_t* cs_ref; int nref_pad;      // the sorted copy of R and its cell_start
+    vmd_within_test_t w; float rpad;                              // rpad: the padded window, > rmax
+    int ry, rz;                                                   // neighbour pencils either way (1; 2 with split pencils)
+};
+
+// ... and what a block derives from it for its frame b, once (vmd_within_walk_setup)
+struct vmd_within_walk_t {
+    int nxf, ny, nz;
+    bool tri, open, open_x, open_y, open_z;
+    float Lx, Ly, Lz, inv_cx, txy, txz, tyz, orgx, pad_open, rpad;
+    int ry, rz;
+    const uint32_t* csr; const float *xr, *yr, *zr;               // frame b's cell_start and coordinate rows of the sorted copy
+    vmd_within_test_t w;
+};
+
+__device__ __forceinline__ vmd_within_walk_t vmd_within_walk_setup(const float* boxes, int b, uint32_t pbc, const vmd_grid_t& grid,
+        const vmd_within_walk_params_t& p) {
+    vmd_within_walk_t k;
+    k.nxf = grid.nxf; k.ny = grid.ny; k.nz = grid.nz;
+    k.tri = (pbc & VMD_PBC_TRICLINIC) != 0; k.open = !k.tri && (pbc & 7u) != 7u;
+    const float* q = boxes + (size_t)VMD_BOX_STRIDE * b;
+    k.Lx = q[0]; k.Ly = q[1]; k.Lz = q[2];
+    k.inv_cx = (float)k.nxf * q[3];
+    k.txy = k.tri ? q[6] : 0.0f; k.txz = k.tri ? q[7] : 0.0f; k.tyz = k.tri ? q[8] : 0.0f;
+    k.open_x = k.open && !(pbc & 1u); k.open_y = k.open && !(pbc & 2u); k.open_z = k.open && !(pbc & 4u);
+    k.orgx = k.open_x ? q[6] : 0.0f;
+    k.pad_open = k.open_x ? 8.0e-7f * (fabsf(k.orgx) + k.Lx) : 0.0f;
+    k.rpad = p.rpad; k.ry = p.ry; k.rz = p.rz;
+    k.csr = p.cs_ref + (size_t)b * (grid.ncell + 1);
+    k.xr = p.sref + (size_t)b * 3 * p.nref_pad;
+    k.yr = k.xr + p.nref_pad;
+    k.zr = k.yr + p.nref_pad;
+    k.w = p.w;
+    return k;
+}
+
+// The cell walk: does the atom at (xi, yi, zi), standing in pencil (py, pz) of the grid, have a member of R in range?  R comes cell-sorted
+// (K1), so the x window [x - r, x + r] of a neighbour pencil is one run of the sorted copy per periodic image; pencils, images, window
+// arithmetic and the pair arithmetic are those of k_rdf_pencil (the neighbour cell's image is the comparison's for every d < r_max), with
+// the window of ONE atom instead of a chunk's.  A lane leaves the walk at its first hit.
+__device__ __forceinline__ bool vmd_within_walk(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi) {
+    bool hit = false;
+    for (int dz = -k.rz; dz <= k.rz && !hit; ++dz) {
+        int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
+        if (k.open_z && (qz < 0 || qz >= k.nz)) continue;
+        if (qz < 0) { qz += k.nz; sz = -k.Lz; nc = -1.0f; } else if (qz >= k.nz) { qz -= k.nz; sz = k.Lz; nc = 1.0f; }
+        for (int dy = -k.ry; dy <= k.ry && !hit; ++dy) {
+            int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+            if (k.open_y && (qy < 0 || qy >= k.ny)) continue;
+            if (qy < 0) { qy += k.ny; sy = -k.Ly; nb = -1.0f; } else if (qy >= k.ny) { qy -= k.ny; sy = k.Ly; nb = 1.0f; }
+            const int qp = qz * k.ny + qy;
+            float offmin = 0.0f, offmax = 0.0f, rpad = k.rpad;
+            if (!k.tri && !k.open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
+                const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (k.Ly / (float)k.ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (k.Lz / (float)k.nz);
+                const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                const float rr = k.rpad * k.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                if (rr <= 0.0f) continue;
+                rpad = sqrtf(rr) * 1.0001f;
+            }
+            if (k.tri) {
+                const float y0 = k.txy * ((float)qy / (float)k.ny), y1 = k.txy * ((float)(qy + 1) / (float)k.ny);
+                const float z0 = k.txz * ((float)qz / (float)k.nz), z1 = k.txz * ((float)(qz + 1) / (float)k.nz);
+                offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+            }
+            for (int kx = -1; kx <= 1 && !hit; ++kx) {
+                if (k.open_x && kx != 0) continue;
+                float sx = (float)kx * k.Lx, sy2 = sy, sz2 = sz;
+                if (k.tri) vmd_lattice_shift(k.Lx, k.Ly, k.Lz, k.txy, k.txz, k.tyz, (float)kx, nb, nc, sx, sy2, sz2);
+                const float lo = (xi - rpad) - sx - offmax - k.orgx - k.pad_open;
+                const float hi = (xi + rpad) - sx - offmin - k.orgx + k.pad_open;
+                if (hi < 0.0f || lo >= k.Lx) continue;
+                const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, k.inv_cx, k.nxf);
+                const int cb = hi >= k.Lx ? k.nxf - 1 : vmd_cell_coord(hi, k.inv_cx, k.nxf);
+                const unsigned ja = k.csr[qp * k.nxf + ca], jb = k.csr[qp * k.nxf + cb + 1];
+                for (unsigned j = ja; j < jb && !hit; ++j) {
+                    const float dx = (xi - k.xr[j]) - sx, dy_ = (yi - k.yr[j]) - sy2, dz_ = (zi - k.zr[j]) - sz2;
+                    hit = vmd_within_hit(k.w, vmd_d2(dx, dy_, dz_));
+                }
+            }
+        }
+    }
+    return hit;
+}
+
 struct vmd_within_pencil_params_t {
-    const float* sref; const uint32_t* cs_ref; int nref_pad;
+    vmd_within_walk_params_t k;
     const float* stgt; const uint32_t* cs_tgt; int ntgt_pad;
-    const float* boxes; int B; vmd_grid_t grid;
-    vmd_within_test_t w; float rpad;
-    uint32_t pbc; int ry, rz;
+    const float* boxes; int B; vmd_grid_t grid; uint32_t pbc;
     unsigned* count; const uint32_t* skip;
     // FLAGS instantiation: u8[B][ntgt_pad], one byte per SORTED position of the target copy; u32[B][npen + 1], the hits of
     // every pencil (entry npen is not written: the scan's total goes there)
     unsigned char* flags; uint32_t* pen_hits;
 };
 
-// the cell walk: one block (one wave) per (frame, pencil), one lane per target atom of the pencil.  Both sets come cell-sorted (K1), so
-// the x window [x - r, x + r] of a neighbour pencil is one run of the sorted reference copy per periodic image; pencils, images, window
-// arithmetic and the pair arithmetic are those of k_rdf_pencil (the neighbour cell's image is the comparison's for every d < r_max), with
-// the window of ONE atom instead of a chunk's.  A lane leaves the walk at its first hit.
+// The walk with T cell-sorted too: one block (one wave) per (frame, pencil), one lane per target atom of the pencil.
 // FLAGS: the same walk also says WHICH sorted entries are in - what k_shell_compact turns into a selection of its own.
 template <bool FLAGS>
 __global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t p) {
     if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch
     const int lane = threadIdx.x;
     const int b = blockIdx.y, pen = blockIdx.x;
-    const int nxf = p.grid.nxf, ny = p.grid.ny, nz = p.grid.nz;
-    const int pz = pen / ny, py = pen - pz * ny;
-    const bool tri = (p.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.pbc & 7u) != 7u;
-    const float* q = p.boxes + (size_t)VMD_BOX_STRIDE * b;
-    const float Lx = q[0], Ly = q[1], Lz = q[2];
-    const float inv_cx = (float)nxf * q[3];
-    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
-    const bool open_x = open && !(p.pbc & 1u), open_y = open && !(p.pbc & 2u), open_z = open && !(p.pbc & 4u);
-    const float orgx = open_x ? q[6] : 0.0f;
-    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
-    const uint32_t* csr = p.cs_ref + (size_t)b * (p.grid.ncell + 1);
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.boxes, b, p.pbc, p.grid, p.k);
+    const int pz = pen / k.ny, py = pen - pz * k.ny;
     const uint32_t* cst = p.cs_tgt + (size_t)b * (p.grid.ncell + 1);
-    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
-    const float* ry_ = rx + p.nref_pad;
-    const float* rz_ = ry_ + p.nref_pad;
     const float* tx = p.stgt + (size_t)b * 3 * p.ntgt_pad;
-    const unsigned pbeg = cst[pen * nxf], pend = cst[(pen + 1) * nxf];
+    const unsigned pbeg = cst[pen * k.nxf], pend = cst[(pen + 1) * k.nxf];
     unsigned total = 0;
     for (unsigned i0 = pbeg; i0 < pend; i0 += VMD_WAVE) {
         const unsigned i = i0 + lane;
-        bool hit = false;
-        if (i < pend) {
-            const float xi = tx[i], yi = tx[p.ntgt_pad + i], zi = tx[2 * (size_t)p.ntgt_pad + i];
-            for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
-                int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
-                if (open_z && (qz < 0 || qz >= nz)) continue;
-                if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
-                for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
-                    int qy = py + dy; float sy = 0.0f, nb = 0.0f;
-                    if (open_y && (qy < 0 || qy >= ny)) continue;
-                    if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
-                    const int qp = qz * ny + qy;
-                    float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
-                    if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
-                        const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
-                        const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
-                        const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
-                        if (rr <= 0.0f) continue;
-                        rpad = sqrtf(rr) * 1.0001f;
-                    }
-                    if (tri) {
-                        const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
-                        const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
-                        offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
-                        offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
-                    }
-                    for (int kx = -1; kx <= 1 && !hit; ++kx) {
-                        if (open_x && kx != 0) continue;
-                        float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
-                        if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
-                        const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
-                        const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
-                        if (hi < 0.0f || lo >= Lx) continue;
-                        const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
-                        const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
-                        const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
-                        for (unsigned j = ja; j < jb && !hit; ++j) {
-                            const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
-                            hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
-                        }
-                    }
-                }
-            }
-        }
+        const bool hit = i < pend && vmd_within_walk(k, py, pz, tx[i], tx[p.ntgt_pad + i], tx[2 * (size_t)p.ntgt_pad + i]);
         if (FLAGS) { if (i < pend) p.flags[(size_t)b * p.ntgt_pad + i] = hit ? 1 : 0; }
         total += (unsigned)__popcll(__ballot(hit ? 1 : 0));
     }
-    if (FLAGS) { if (lane == 0) p.pen_hits[(size_t)b * (ny * nz + 1) + pen] = total; }
+    if (FLAGS) { if (lane == 0) p.pen_hits[(size_t)b * (k.ny * k.nz + 1) + pen] = total; }
     if (lane == 0 && total) atomicAdd(&p.count[b], total);
 }
 
@@ -2187,81 +2222,27 @@ __global__ __launch_bounds__(64) void k_within_pencil(vmd_within_pencil_params_t
 
 struct vmd_within_atoms_params_t {
     vmd_cells_params_t c;       // T as a cell build would read it: raw frame, the GRID's boxes, pbc, index list, grid (pat.m = 0; no outputs)
-    const float* sref; const uint32_t* cs_ref; int nref_pad;
-    vmd_within_test_t w; float rpad; int ry, rz;
+    vmd_within_walk_params_t k;
     unsigned char* mask; size_t mask_stride;     // u8[B][mask_stride], indexed by ATOM: mask[b][T[t]] = hit
     unsigned* count; const uint32_t* skip;
 };
 
-// The walk of k_within_pencil with T NOT sorted: one lane per list entry t, in list order.  The lane wraps its atom and derives its cell with
-// vmd_cell_of - the function every cell build bins with, on the same fp32 values - so an atom on a cell boundary stands in the pencil a build
-// would have put it in and sees the neighbour pencils k_within_pencil would have walked for it; pencils, images, split-pencil windows,
-// triclinic offsets, open axes and the pair arithmetic are that kernel's, statement for statement (kept as a copy: the instantiations of
-// k_within_pencil keep the code the compiler gave them).  Only R is cell-sorted, so nothing needs a rank: the answer goes to mask[b][atom].
-// Lanes of a wave are spatially unrelated: every lane walks its own windows and the loads do not coalesce; with a small R under a large T
-// nearly every lane finds its windows empty and leaves after the cell_start reads.
+// The walk with T NOT sorted: one lane per list entry t, in list order.  The lane wraps its atom and derives its cell with vmd_cell_of - the
+// function every cell build bins with, on the same fp32 values - so an atom on a cell boundary stands in the pencil a build would have put
+// it in and sees the neighbour pencils k_within_pencil would have walked for it.  Only R is cell-sorted, so nothing needs a rank: the
+// answer goes to mask[b][atom].  Lanes of a wave are spatially unrelated: every lane walks its own windows and the loads do not coalesce;
+// with a small R under a large T nearly every lane finds its windows empty and leaves after the cell_start reads.
 __global__ __launch_bounds__(256) void k_within_atoms(vmd_within_atoms_params_t p) {
     if (p.skip && *p.skip) return;       // the cell build of R (or another one of this batch) overflowed a bucket: the host repeats the batch
     const int b = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;
-    const int nxf = p.c.grid.nxf, ny = p.c.grid.ny, nz = p.c.grid.nz;
-    const bool tri = (p.c.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.c.pbc & 7u) != 7u;
-    const float* q = p.c.boxes + (size_t)VMD_BOX_STRIDE * b;
-    const float Lx = q[0], Ly = q[1], Lz = q[2];
-    const float inv_cx = (float)nxf * q[3];
-    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
-    const bool open_x = open && !(p.c.pbc & 1u), open_y = open && !(p.c.pbc & 2u), open_z = open && !(p.c.pbc & 4u);
-    const float orgx = open_x ? q[6] : 0.0f;
-    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
-    const uint32_t* csr = p.cs_ref + (size_t)b * (p.c.grid.ncell + 1);
-    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
-    const float* ry_ = rx + p.nref_pad;
-    const float* rz_ = ry_ + p.nref_pad;
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
     bool hit = false;
     if (t < p.c.nsel) {
         float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)nxf);
-        const int pz = pen / ny, py = pen - pz * ny;
-        for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
-            int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
-            if (open_z && (qz < 0 || qz >= nz)) continue;
-            if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
-            for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
-                int qy = py + dy; float sy = 0.0f, nb = 0.0f;
-                if (open_y && (qy < 0 || qy >= ny)) continue;
-                if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
-                const int qp = qz * ny + qy;
-                float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
-                if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
-                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
-                    const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
-                    const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
-                    if (rr <= 0.0f) continue;
-                    rpad = sqrtf(rr) * 1.0001f;
-                }
-                if (tri) {
-                    const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
-                    const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
-                    offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
-                    offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
-                }
-                for (int kx = -1; kx <= 1 && !hit; ++kx) {
-                    if (open_x && kx != 0) continue;
-                    float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
-                    if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
-                    const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
-                    const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
-                    if (hi < 0.0f || lo >= Lx) continue;
-                    const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
-                    const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
-                    const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
-                    for (unsigned j = ja; j < jb && !hit; ++j) {
-                        const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
-                        hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
-                    }
-                }
-            }
-        }
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
+        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        hit = vmd_within_walk(k, py, pz, xi, yi, zi);
         p.mask[(size_t)b * p.mask_stride + (size_t)vmd_sel_atom(p.c, t)] = hit ? 1 : 0;
     }
     const unsigned long long m = __ballot(hit ? 1 : 0);
@@ -2276,15 +2257,13 @@ __global__ __launch_bounds__(256) void k_within_atoms(vmd_within_atoms_params_t 
 // values occur).  A lane whose bit is clear does no walk and leaves its byte alone.
 struct vmd_within_atoms_expr_params_t {
     vmd_cells_params_t c;       // T as k_within_atoms reads it
-    const float* sref; const uint32_t* cs_ref; int nref_pad;
-    vmd_within_test_t w; float rpad; int ry, rz;
+    vmd_within_walk_params_t k;
     unsigned char* bits; size_t stride;         // u8[B][stride], indexed by ATOM
     int term; uint32_t live;
     const uint32_t* skip;
 };
 
-// The walk of k_within_atoms (kept as a copy, statement for statement: that kernel keeps the code the compiler gave it) for ONE term of an
-// expression.  The lane reads its byte first; a wave with no live lane leaves after that one load.
+// The walk of k_within_atoms for ONE term of an expression.  The lane reads its byte first; a wave with no live lane leaves after that one load.
 __global__ __launch_bounds__(256) void k_within_atoms_expr(vmd_within_atoms_expr_params_t p) {
     if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch
     const int b = blockIdx.y;
@@ -2298,65 +2277,12 @@ __global__ __launch_bounds__(256) void k_within_atoms_expr(vmd_within_atoms_expr
         go = ((p.live >> cur) & 1u) != 0;
     }
     if (!__ballot(go ? 1 : 0)) return;
-    const int nxf = p.c.grid.nxf, ny = p.c.grid.ny, nz = p.c.grid.nz;
-    const bool tri = (p.c.pbc & VMD_PBC_TRICLINIC) != 0, open = !tri && (p.c.pbc & 7u) != 7u;
-    const float* q = p.c.boxes + (size_t)VMD_BOX_STRIDE * b;
-    const float Lx = q[0], Ly = q[1], Lz = q[2];
-    const float inv_cx = (float)nxf * q[3];
-    const float txy = tri ? q[6] : 0.0f, txz = tri ? q[7] : 0.0f, tyz = tri ? q[8] : 0.0f;
-    const bool open_x = open && !(p.c.pbc & 1u), open_y = open && !(p.c.pbc & 2u), open_z = open && !(p.c.pbc & 4u);
-    const float orgx = open_x ? q[6] : 0.0f;
-    const float pad_open = open_x ? 8.0e-7f * (fabsf(orgx) + Lx) : 0.0f;
-    const uint32_t* csr = p.cs_ref + (size_t)b * (p.c.grid.ncell + 1);
-    const float* rx = p.sref + (size_t)b * 3 * p.nref_pad;
-    const float* ry_ = rx + p.nref_pad;
-    const float* rz_ = ry_ + p.nref_pad;
-    bool hit = false;
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
     if (go) {
         float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)nxf);
-        const int pz = pen / ny, py = pen - pz * ny;
-        for (int dz = -p.rz; dz <= p.rz && !hit; ++dz) {
-            int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
-            if (open_z && (qz < 0 || qz >= nz)) continue;
-            if (qz < 0) { qz += nz; sz = -Lz; nc = -1.0f; } else if (qz >= nz) { qz -= nz; sz = Lz; nc = 1.0f; }
-            for (int dy = -p.ry; dy <= p.ry && !hit; ++dy) {
-                int qy = py + dy; float sy = 0.0f, nb = 0.0f;
-                if (open_y && (qy < 0 || qy >= ny)) continue;
-                if (qy < 0) { qy += ny; sy = -Ly; nb = -1.0f; } else if (qy >= ny) { qy -= ny; sy = Ly; nb = 1.0f; }
-                const int qp = qz * ny + qy;
-                float offmin = 0.0f, offmax = 0.0f, rpad = p.rpad;
-                if (!tri && !open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
-                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
-                    const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
-                    const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
-                    if (rr <= 0.0f) continue;
-                    rpad = sqrtf(rr) * 1.0001f;
-                }
-                if (tri) {
-                    const float y0 = txy * ((float)qy / (float)ny), y1 = txy * ((float)(qy + 1) / (float)ny);
-                    const float z0 = txz * ((float)qz / (float)nz), z1 = txz * ((float)(qz + 1) / (float)nz);
-                    offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
-                    offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
-                }
-                for (int kx = -1; kx <= 1 && !hit; ++kx) {
-                    if (open_x && kx != 0) continue;
-                    float sx = (float)kx * Lx, sy2 = sy, sz2 = sz;
-                    if (tri) vmd_lattice_shift(Lx, Ly, Lz, txy, txz, tyz, (float)kx, nb, nc, sx, sy2, sz2);
-                    const float lo = (xi - rpad) - sx - offmax - orgx - pad_open;
-                    const float hi = (xi + rpad) - sx - offmin - orgx + pad_open;
-                    if (hi < 0.0f || lo >= Lx) continue;
-                    const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
-                    const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
-                    const unsigned ja = csr[qp * nxf + ca], jb = csr[qp * nxf + cb + 1];
-                    for (unsigned j = ja; j < jb && !hit; ++j) {
-                        const float dx = (xi - rx[j]) - sx, dy_ = (yi - ry_[j]) - sy2, dz_ = (zi - rz_[j]) - sz2;
-                        hit = vmd_within_hit(p.w, vmd_d2(dx, dy_, dz_));
-                    }
-                }
-            }
-        }
-        if (hit) p.bits[at] = (unsigned char)(cur | (1u << p.term));
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
+        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        if (vmd_within_walk(k, py, pz, xi, yi, zi)) p.bits[at] = (unsigned char)(cur | (1u << p.term));
     }
 }
 
@@ -2370,14 +2296,13 @@ struct vmd_within_brute_expr_params_t {
     const uint32_t* skip;
 };
 
-// The brute twin, for a small R or where no grid exists: the arithmetic of k_within_brute<true, true>, R staged through LDS in tiles of 256.
-// One WAVE per block, so that a wave with no live lane can leave after its one load without leaving a tile half staged.
+// The all-pairs twin, for a small R or where no grid exists.  One WAVE per block, so that a wave with no live lane can leave after its one
+// load - in front of the first barrier - without leaving a tile half staged.
 __global__ __launch_bounds__(64) void k_within_brute_expr(vmd_within_brute_expr_params_t p) {
     __shared__ float s_r[3][256];
     if (p.skip && *p.skip) return;
     const int b = blockIdx.y;
-    const int lane = threadIdx.x;
-    const int t = blockIdx.x * 64 + lane;
+    const int t = blockIdx.x * 64 + threadIdx.x;
     const float* fx = p.xyz + (size_t)b * p.frame_stride;
     const float* fy = fx + p.row_stride;
     const float* fz = fy + p.row_stride;
@@ -2395,20 +2320,7 @@ __global__ __launch_bounds__(64) void k_within_brute_expr(vmd_within_brute_expr_
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
     float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
     if (go) vmd_pair_coords(bx, fx[a_t], fy[a_t], fz[a_t], xi, yi, zi);
-    bool hit = false;
-    for (int j0 = 0; j0 < p.nref; j0 += 256) {
-        __syncthreads();
-        const int nj = p.nref - j0 < 256 ? p.nref - j0 : 256;
-        for (int jj = lane; jj < nj; jj += 64) {
-            const int a = p.ref ? p.ref[j0 + jj] : j0 + jj;
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
-        }
-        __syncthreads();
-        if (go && !hit)
-            for (int jj = 0; jj < nj && !hit; ++jj)
-                hit = vmd_within_hit(p.w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
-    }
-    if (go && hit) p.bits[at] = (unsigned char)(cur | (1u << p.term));
+    if (vmd_within_all_pairs<64>(s_r, bx, fx, fy, fz, p.ref, p.nref, p.w, go, xi, yi, zi)) p.bits[at] = (unsigned char)(cur | (1u << p.term));
 }
 
 struct vmd_shell_expr_finish_params_t {
@@ -4236,6 +4148,18 @@ extern "C" int vmd_hip_within_brute_atoms(void* stream, const float* xyz, size_t
                                    count_out, mask_out, mask_stride);
 }
 
+// The walk's part of a launch: the cell-sorted copy of R, the test, the padded window of vmd_hip_rdf_pencil and this thread's pencil reach.
+// false: the grid or the range is none
+static bool vmd_within_walk_fill(vmd_within_walk_params_t& k, const vmd_grid_t& grid, const float* sorted_ref, const uint32_t* cell_start_ref,
+                                 int nref_pad, float rmin, float rmax, int closed) {
+    if (grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 || !(rmin >= 0.0f) || !(rmax > rmin)) return false;
+    k.sref = sorted_ref; k.cs_ref = cell_start_ref; k.nref_pad = nref_pad;
+    k.w = vmd_make_within_test(rmin, rmax, closed);
+    k.rpad = rmax * 1.0001f + 1.0e-4f;
+    k.ry = g_pen_ry; k.rz = g_pen_rz;
+    return true;
+}
+
 extern "C" int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                     const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
                                     const float* sorted_ref, const uint32_t* cell_start_ref, int nref, int nref_pad, vmd_grid_t grid,
@@ -4243,19 +4167,14 @@ extern "C" int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame
                                     const uint32_t* skip_flag) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (B > 65535 || !count_out || !mask_out || !mask_stride || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 ||
-        grid.ncell != grid.nxf * grid.ny * grid.nz) return (int)hipErrorInvalidValue;
-    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    vmd_within_atoms_params_t p{};
+    if (B > 65535 || !count_out || !mask_out || !mask_stride || grid.ncell != grid.nxf * grid.ny * grid.nz ||
+        !vmd_within_walk_fill(p.k, grid, sorted_ref, cell_start_ref, nref_pad, rmin, rmax, closed)) return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
     if (ntgt <= 0) return 0;
     if (nref <= 0 || !sorted_ref || !cell_start_ref) return (int)hipErrorInvalidValue;
-    vmd_within_atoms_params_t p{};
     p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
     p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
-    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
-    p.w = vmd_make_within_test(rmin, rmax, closed);
-    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_within_pencil
-    p.ry = g_pen_ry; p.rz = g_pen_rz;
     p.mask = mask_out; p.mask_stride = mask_stride; p.count = count_out; p.skip = skip_flag;
     hipLaunchKernelGGL(k_within_atoms, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
@@ -4269,17 +4188,13 @@ static int vmd_within_pencil_launch(void* stream, const float* sorted_ref, const
                                      uint8_t* flags_out, uint32_t* pen_hits_out) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (B > 65535 || !count_out || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0) return (int)hipErrorInvalidValue;
-    if (!(rmin >= 0.0f) || !(rmax > rmin)) return (int)hipErrorInvalidValue;
+    vmd_within_pencil_params_t p;
+    if (B > 65535 || !count_out || !vmd_within_walk_fill(p.k, grid, sorted_ref, cell_start_ref, nref_pad, rmin, rmax, closed))
+        return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
     if ((ntgt <= 0 || nref <= 0) && !flags_out) return 0;
-    vmd_within_pencil_params_t p;
-    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
     p.stgt = sorted_tgt; p.cs_tgt = cell_start_tgt; p.ntgt_pad = ntgt_pad;
-    p.boxes = boxes; p.B = B; p.grid = grid;
-    p.w = vmd_make_within_test(rmin, rmax, closed);
-    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_rdf_pencil
-    p.pbc = pbc_flags; p.ry = g_pen_ry; p.rz = g_pen_rz;
+    p.boxes = boxes; p.B = B; p.grid = grid; p.pbc = pbc_flags;
     p.count = count_out; p.skip = skip_flag;
     p.flags = flags_out; p.pen_hits = pen_hits_out;
     if (flags_out) hipLaunchKernelGGL(k_within_pencil<true>, dim3(grid.ny * grid.nz, B), dim3(VMD_WAVE), 0, s, p);
@@ -4342,15 +4257,12 @@ extern "C" int vmd_hip_within_atoms_expr(void* stream, const float* xyz, size_t 
                                          const uint32_t* skip_flag) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || ntgt <= 0 || !live) return 0;
-    if (!vmd_expr_term_ok(B, term, live, bits, stride, rmin, rmax) || grid.ny <= 0 || grid.nz <= 0 || grid.nxf <= 0 ||
-        grid.ncell != grid.nxf * grid.ny * grid.nz || nref <= 0 || !sorted_ref || !cell_start_ref) return (int)hipErrorInvalidValue;
     vmd_within_atoms_expr_params_t p{};
+    if (!vmd_expr_term_ok(B, term, live, bits, stride, rmin, rmax) || grid.ncell != grid.nxf * grid.ny * grid.nz || nref <= 0 ||
+        !sorted_ref || !cell_start_ref || !vmd_within_walk_fill(p.k, grid, sorted_ref, cell_start_ref, nref_pad, rmin, rmax, closed))
+        return (int)hipErrorInvalidValue;
     p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
     p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
-    p.sref = sorted_ref; p.cs_ref = cell_start_ref; p.nref_pad = nref_pad;
-    p.w = vmd_make_within_test(rmin, rmax, closed);
-    p.rpad = rmax * 1.0001f + 1.0e-4f;          // the padded window of vmd_hip_within_pencil
-    p.ry = g_pen_ry; p.rz = g_pen_rz;
     p.bits = bits; p.stride = stride; p.term = term; p.live = live; p.skip = skip_flag;
     hipLaunchKernelGGL(k_within_atoms_expr, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
