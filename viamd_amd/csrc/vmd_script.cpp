@@ -11,8 +11,12 @@
 // Selections: element('X') | type/name/label('X') | resname("X") | residue(a:b) | resid(a:b) | atom(a:b) | integer [: integer] |
 // all | water | protein | identifiers bound earlier, combined with `and`, `or`, `not`, parentheses; `sel[a:b]` slices an array of
 // structures (1-based, inclusive).  Output: property descriptors appended to a vmd_script_ir_t (vmd_ir_add_*); nothing is
-// evaluated here.  viamd_amd/script.py is the same front-end in Python; tests/test_script.py checks that both produce
-// identical IR fingerprints.
+// evaluated here.  viamd_amd/script.py is the same front-end in Python, cut into the same functions under the same names;
+// tests/test_script.py checks that both produce identical IR fingerprints, tests/test_script_pin.py holds each to its recorded outcomes.
+//
+// A new statement form is one *_statement function here, called from statement(), its twin in script.py, and a generator method plus
+// the form's refusals in tests/script_cases.py.  What the forms share - closing_paren, per_context, one_selection_population,
+// within_head, scan_arg, single_within_and, rdf_range - is written once, above them.
 #include <algorithm>
 #include <cctype>
 #include <cstdarg>
@@ -330,540 +334,495 @@ struct Report {
     std::string fallback_source;
 };
 
+using Commit = std::function<void()>;       // appends the statement's descriptor / binds its identifier; runs once the whole statement has parsed
+using Indices = std::vector<int32_t>;
+
+// What a statement function works on.  p stands behind the `(` of the call when a *_statement function is entered.
+struct Statement {
+    const std::vector<Token>& toks;
+    const Topo& topo;
+    std::map<std::string, Sel>& env;
+    vmd_script_ir_t* ir;
+    uint32_t features;
+    Parser& p;
+    std::string name;               // the left-hand side: one name, or the names of a tuple joined by ','
+    bool is_property = false;
+
+    bool has(uint32_t bit) const { return (features & bit) != 0; }
+    const char* nm() const { return name.c_str(); }
+    bool is(size_t q, TokKind kind, const char* text) const { return q < toks.size() && toks[q].kind == kind && toks[q].text == text; }
+    bool is_within_at(size_t q) const { return is(q, T_ID, "within") && is(q + 1, T_OP, "("); }
+};
+
+void added(bool ok) { if (!ok) throw ScriptError(vmd_last_error()); }       // a descriptor the library refuses
+
+// ---- helpers the statement forms share -------------------------------------------------------------------------------------------------
+
+// the token behind the `)` that closes the call p stands in
+size_t closing_paren(const Statement& s) {
+    size_t j = s.p.i;
+    for (int depth = 1; depth; ++j) {
+        if (j >= s.toks.size()) fail("%s: missing ')'", s.nm());
+        if (s.is(j, T_OP, "(")) depth += 1;
+        if (s.is(j, T_OP, ")")) depth -= 1;
+    }
+    return j;
+}
+
+// `f(<arguments>) [in <contexts>]`, after = closing_paren(): body(parser, where) reads the arguments and the `)` - once with the
+// statement's parser (where = ""), or, under `in`, once per structure of the contexts with a parser bound to it (where = " inside a
+// context").  Returns the number of contexts, 0 without `in`.
+template <class Body> size_t per_context(Statement& s, size_t after, Body body) {
+    if (!s.is(after, T_ID, "in")) { body(s.p, ""); return 0; }
+    const size_t start = s.p.i;
+    Parser q(s.toks, s.topo, s.env);
+    q.i = after + 1;
+    const Sel ctx = q.sel_or();
+    if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", s.nm());
+    for (auto& st : ctx.structs) {
+        Parser r(s.toks, s.topo, s.env, &st);
+        r.i = start;
+        body(r, " inside a context");
+    }
+    s.p.i = q.i;
+    return ctx.structs.size();
+}
+
+// index sets back to back: set k is all[off[k] .. off[k + 1])
+struct Population {
+    Indices all, off{0};
+    void push(const Indices& ix) { all.insert(all.end(), ix.begin(), ix.end()); off.push_back((int32_t)all.size()); }
+};
+
+// `fn(sel) [in <contexts>]` (shape_weights, rmsd): one selection, one set per context
+Population one_selection_population(Statement& s, const char* fn) {
+    Population out;
+    per_context(s, closing_paren(s), [&](Parser& r, const char* where) {
+        const Indices ix = r.sel_or().indices();
+        if (r.is_word(",")) fail("%s: %s takes one selection", s.nm(), fn);
+        r.take(")");
+        if (ix.empty()) fail("%s: empty selection%s", s.nm(), where);
+        out.push(ix);
+    });
+    return out;
+}
+
+// A selection argument that may hold within(): the static list and, when shell is set, the one shell that narrows it per frame.
+struct DynArg { Indices list, ref; bool shell = false; double rmin = 0.0, rmax = 0.0; };
+
+// `within(` r | a:b `,` - p stands on `within`; the reference selection follows
+void within_head(Statement& s, double* rmin, double* rmax) {
+    Parser& p = s.p;
+    ++p.i;
+    p.take("(");
+    *rmin = 0.0;
+    *rmax = p.number();
+    if (p.accept(":")) {
+        *rmin = *rmax; *rmax = p.number();
+        if (!(*rmin < *rmax)) fail("%s: within range needs 0 <= a < b", s.nm());
+    } else if (!(*rmax > 0.0)) fail("%s: within needs a radius > 0", s.nm());
+    p.take(",");
+}
+
+// ... and the reference selection with the `)`
+Indices within_ref(Statement& s) {
+    Indices ref = s.p.sel_or().indices();
+    s.p.take(")");
+    if (ref.empty()) fail("%s: empty selection", s.nm());
+    return ref;
+}
+
+// One pass over an argument from token `from`: where it ends, how many within( it holds, how many of those are factors of its top-level
+// AND, whether it has an `or` at depth 0.  end == npos: the argument ends at the `,` `;` or unmatched `)` (with stop_and also at an
+// `and`) at depth 0; otherwise the scan runs to `end` whatever is on the way (count(): the whole call).
+struct ArgScan { size_t end = 0, n_within = 0, n_top = 0; bool top_or = false; };
+const size_t npos = (size_t)-1;
+
+ArgScan scan_arg(const Statement& s, size_t from, bool stop_and = false, size_t end = npos) {
+    ArgScan out;
+    int depth = 0;
+    size_t q = from;
+    for (; q < std::min(end, s.toks.size()); ++q) {
+        if (end == npos && depth == 0 && (s.is(q, T_OP, ",") || s.is(q, T_OP, ";"))) break;
+        if (s.is(q, T_OP, "(")) depth += 1;
+        if (s.is(q, T_OP, ")")) { if (depth == 0) break; depth -= 1; }
+        if (stop_and && depth == 0 && s.is(q, T_ID, "and")) break;
+        if (s.is_within_at(q)) {
+            out.n_within += 1;
+            if (depth == 0 && (q == from || s.is(q - 1, T_ID, "and"))) out.n_top += 1;
+        }
+        if (depth == 0 && s.is(q, T_ID, "or")) out.top_or = true;
+    }
+    out.end = q;
+    return out;
+}
+
+// `<factor> and ... and within(<r> | <a>:<b>, <static selection>) and ...`: exactly one within() factor, at the top
+// level of the AND; the other factors are static and their AND is the list (all atoms when there is none).  what: who takes it, for
+// the message.
+DynArg single_within_and(Statement& s, const ArgScan& scan, const char* what) {
+    Parser& p = s.p;
+    if (scan.n_within > 1) fail("%s: %s takes exactly one within() factor, found %zu", s.nm(), what, scan.n_within);
+    if (scan.n_top != 1 || scan.top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", s.nm());
+    DynArg out;
+    out.shell = true;
+    std::vector<uint8_t> tmask(s.topo.n, 1);
+    do {
+        if (p.is_word("within") && p.peek().kind == T_ID) {
+            within_head(s, &out.rmin, &out.rmax);
+            out.ref = within_ref(s);
+        } else {
+            const Sel f = p.sel_not();
+            for (size_t a = 0; a < s.topo.n; ++a) tmask[a] &= f.mask[a];
+        }
+    } while (p.accept("and"));
+    for (size_t a = 0; a < s.topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
+    return out;
+}
+
+// a selection argument of rdf() / the target of sdf(): static, or with `dynamic` (the function's feature bit) possibly a single-within AND
+DynArg selection_arg(Statement& s, bool dynamic, const char* what) {
+    const ArgScan scan = dynamic ? scan_arg(s, s.p.i) : ArgScan();
+    if (scan.n_within) return single_within_and(s, scan, what);
+    DynArg out;
+    out.list = s.p.sel_or().indices();
+    return out;
+}
+
+// DESIGN 1.9 (VMD_SCRIPT_FEATURE_SHELL_EXPR): the argument of count() and the target of sdf() may hold several dynamic factors at the
+// top level of their AND - within(...), not within(...), or a parenthesised and / or / not over within() terms only.  Terms that repeat
+// are one term, numbered in order of first appearance; a table over four variables is carried through the parse and cut to the terms
+// there are.
+struct ExprTerm { Indices ref; float rmin, rmax; };
+struct ExprArg { Indices list; std::vector<ExprTerm> terms; uint32_t truth = 0; bool dynamic = false; };
+
+struct ExprParser {
+    Statement& s;
+    Parser& p;
+    ExprArg out;
+    explicit ExprParser(Statement& st) : s(st), p(st.p) {}
+
+    ExprArg parse() {
+        const ArgScan whole = scan_arg(s, p.i);
+        if (!whole.n_within) { out.list = p.sel_or().indices(); return out; }
+        if (whole.top_or) fail("%s: a dynamic factor under a top-level or with a static selection", s.nm());
+        out.dynamic = true;
+        std::vector<uint8_t> tmask(s.topo.n, 1);
+        uint32_t table = 0xffffu;
+        do {
+            if (scan_arg(s, p.i, true).n_within) table &= dyn_not();
+            else { const Sel f = p.sel_not(); for (size_t a = 0; a < s.topo.n; ++a) tmask[a] &= f.mask[a]; }
+        } while (p.accept("and"));
+        for (size_t a = 0; a < s.topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
+        out.truth = table & ((1u << (1u << out.terms.size())) - 1u);
+        return out;
+    }
+    uint32_t within_term() {
+        static const uint32_t VAR[4] = {0xAAAAu, 0xCCCCu, 0xF0F0u, 0xFF00u};
+        double rmin, rmax;
+        within_head(s, &rmin, &rmax);
+        if (scan_arg(s, p.i).n_within) fail("%s: within() nested in a within() argument", s.nm());
+        ExprTerm t{within_ref(s), (float)rmin, (float)rmax};
+        for (size_t k = 0; k < out.terms.size(); ++k)
+            if (out.terms[k].ref == t.ref && out.terms[k].rmin == t.rmin && out.terms[k].rmax == t.rmax) return VAR[k];
+        if (out.terms.size() == VMD_SHELL_EXPR_MAX_TERMS) fail("%s: more than four distinct within() terms", s.nm());
+        out.terms.push_back(std::move(t));
+        return VAR[out.terms.size() - 1];
+    }
+    uint32_t dyn_not() {
+        if (p.accept("not")) return ~dyn_not() & 0xffffu;
+        if (s.is_within_at(p.i)) return within_term();
+        if (p.is_word("(")) { p.take("("); const uint32_t t = dyn_or(); p.take(")"); return t; }
+        fail("%s: a static selection inside a parenthesised dynamic factor", s.nm());
+    }
+    uint32_t dyn_and() { uint32_t t = dyn_not(); while (p.accept("and")) t &= dyn_not(); return t; }
+    uint32_t dyn_or() { uint32_t t = dyn_and(); while (p.accept("or")) t |= dyn_and(); return t; }
+};
+
+vmd_shell_expr_t expr_view(const ExprArg& x, std::vector<vmd_shell_t>* terms) {
+    terms->clear();
+    for (auto& t : x.terms) terms->push_back(vmd_shell_t{t.ref.data(), t.ref.size(), t.rmin, t.rmax});
+    return vmd_shell_expr_t{terms->data(), terms->size(), x.truth};
+}
+
+vmd_shell_t shell_view(const DynArg& a) { return vmd_shell_t{a.ref.data(), a.ref.size(), (float)a.rmin, (float)a.rmax}; }
+
+// rdf's third argument: `{a, b}` | `r` | `a:b`
+void rdf_range(Parser& p, double* rmin, double* rmax) {
+    *rmin = 0.0;
+    if (p.accept("{")) { *rmin = p.number(); p.take(","); *rmax = p.number(); p.take("}"); return; }
+    *rmax = p.number();
+    if (p.accept(":")) { *rmin = *rmax; *rmax = p.number(); }
+}
+
+// ---- one function per statement form: each parses up to (not including) the ';' and returns the statement's commit ------------------------
+
+// `{lin, plan, iso} = shape_weights(sel) [in <contexts>];`, from the function's name on: the one function of the subset
+// that defines a tuple
+Commit shape_statement(Statement& s) {
+    std::vector<std::string> nm(1);
+    for (char ch : s.name) { if (ch == ',') nm.emplace_back(); else nm.back() += ch; }
+    if (nm.size() != 3) fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not %zu", s.nm(), nm.size());
+    ++s.p.i;
+    s.p.take("(");
+    const Population sets = one_selection_population(s, "shape_weights");
+    return [ir = s.ir, nm, sets]() {
+        const char* const cn[3] = {nm[0].c_str(), nm[1].c_str(), nm[2].c_str()};
+        added(vmd_ir_add_shape_weights_population(ir, cn, sets.off.size() - 1, sets.all.data(), sets.off.data()));
+    };
+}
+
+// `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context rules of distance()
+Commit rmsd_statement(Statement& s) {
+    const Population sets = one_selection_population(s, "rmsd");
+    return [ir = s.ir, name = s.name, sets]() { added(vmd_ir_add_rmsd_population(ir, name.c_str(), sets.off.size() - 1, sets.all.data(), sets.off.data())); };
+}
+
+void no_count_contexts(Statement& s) {
+    s.p.take(")");
+    if (s.p.is_word("in")) fail("%s: count(...) in <contexts> is outside the subset", s.nm());
+}
+
+// `name = count(<factor> and <factor> ...);`: exactly one factor is within(<r> | <a>:<b>, <static selection>), the others
+// are static selections whose AND is the target set.  The scan covers the whole call, commas included: a second argument is met by
+// the parse, not by the scan.
+Commit count_statement(Statement& s) {
+    const ArgScan scan = scan_arg(s, s.p.i, false, closing_paren(s) - 1);
+    if (scan.n_within == 0) fail("%s: count of a static selection is a constant (left to the fallback)", s.nm());
+    const DynArg A = single_within_and(s, scan, "count");
+    no_count_contexts(s);
+    if (A.list.empty()) fail("%s: empty selection", s.nm());
+    return [ir = s.ir, name = s.name, A]() {
+        added(vmd_ir_add_within_count(ir, name.c_str(), A.list.data(), A.list.size(), A.ref.data(), A.ref.size(), (float)A.rmin, (float)A.rmax));
+    };
+}
+
+// the same with any number of dynamic factors
+Commit count_expr_statement(Statement& s) {
+    const ExprArg X = ExprParser(s).parse();
+    if (!X.dynamic) fail("%s: count of a static selection is a constant (left to the fallback)", s.nm());
+    no_count_contexts(s);
+    if (X.list.empty()) fail("%s: empty selection", s.nm());
+    return [ir = s.ir, name = s.name, X]() {
+        std::vector<vmd_shell_t> tv;
+        const vmd_shell_expr_t xv = expr_view(X, &tv);
+        added(vmd_ir_add_within_count_expr(ir, name.c_str(), X.list.data(), X.list.size(), &xv));
+    };
+}
+
+// `name = rdf(sel, sel, <range>);` - with VMD_SCRIPT_FEATURE_SHELL_RDF either selection may be a single-within AND
+Commit rdf_statement(Statement& s) {
+    Parser& p = s.p;
+    const bool shells = s.has(VMD_SCRIPT_FEATURE_SHELL_RDF);
+    const DynArg A = selection_arg(s, shells, "an rdf argument"); p.take(",");
+    const DynArg B = selection_arg(s, shells, "an rdf argument"); p.take(",");
+    double rmin, rmax;
+    rdf_range(p, &rmin, &rmax);
+    p.take(")");
+    if (A.list.empty() || B.list.empty()) fail("%s: empty selection", s.nm());
+    if (!shells) return [ir = s.ir, name = s.name, A, B, rmin, rmax]() {
+        added(vmd_ir_add_rdf(ir, name.c_str(), A.list.data(), A.list.size(), B.list.data(), B.list.size(), (float)rmin, (float)rmax));
+    };
+    return [ir = s.ir, name = s.name, A, B, rmin, rmax]() {
+        const vmd_shell_t sa = shell_view(A), sb = shell_view(B);
+        added(vmd_ir_add_rdf_shell(ir, name.c_str(), A.list.data(), A.list.size(), A.shell ? &sa : nullptr, B.list.data(), B.list.size(),
+                                   B.shell ? &sb : nullptr, (float)rmin, (float)rmax));
+    };
+}
+
+// `name = sdf(structures, sel, cutoff);` - with VMD_SCRIPT_FEATURE_SHELL_SDF the target may be a single-within AND, with
+// VMD_SCRIPT_FEATURE_SHELL_EXPR on top of it an expression over within() terms.  The structures stay static: the alignment
+// needs fixed atoms.
+Commit sdf_statement(Statement& s) {
+    Parser& p = s.p;
+    const bool shells = s.has(VMD_SCRIPT_FEATURE_SHELL_SDF);
+    if (shells && scan_arg(s, p.i).n_within)
+        fail("%s: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)", s.nm());
+    const Sel ref = p.sel_or(); p.take(",");
+    DynArg T;
+    ExprArg X;
+    if (shells && s.has(VMD_SCRIPT_FEATURE_SHELL_EXPR)) { X = ExprParser(s).parse(); T.list = X.list; }
+    else T = selection_arg(s, shells, "an sdf argument");
+    p.take(",");
+    const double cutoff = p.number();
+    p.take(")");
+    const std::vector<Indices> structs = ref.has_structs ? ref.structs : std::vector<Indices>{ref.indices()};
+    const size_t K = structs.size(), m = K ? structs[0].size() : 0;
+    Indices flat;
+    for (auto& st : structs) {
+        if (st.size() != m) break;
+        flat.insert(flat.end(), st.begin(), st.end());
+    }
+    if (m == 0 || flat.size() != K * m) fail("%s: sdf reference structures must be non-empty and of equal size", s.nm());
+    if ((T.shell || X.dynamic) && T.list.empty()) fail("%s: empty selection", s.nm());
+    if (X.dynamic) return [ir = s.ir, name = s.name, flat, K, m, X, cutoff]() {
+        std::vector<vmd_shell_t> tv;
+        const vmd_shell_expr_t xv = expr_view(X, &tv);
+        added(vmd_ir_add_sdf_shell_expr(ir, name.c_str(), flat.data(), K, m, X.list.data(), X.list.size(), &xv, (float)cutoff));
+    };
+    return [ir = s.ir, name = s.name, flat, K, m, T, cutoff]() {
+        const vmd_shell_t sh = shell_view(T);
+        added(vmd_ir_add_sdf_shell(ir, name.c_str(), flat.data(), K, m, T.list.data(), T.list.size(), T.shell ? &sh : nullptr, (float)cutoff));
+    };
+}
+
+// `name = distance*(a, b) | angle(a, b, c) | dihedral(a, b, c, d) [in <contexts>];` (DESIGN S6b): fn is the function's name
+Commit geometry_statement(Statement& s, const std::string& fn) {
+    const size_t nargs = fn == "angle" ? 3 : (fn == "dihedral" ? 4 : 2);
+    std::vector<Population> sets(nargs);
+    const size_t P = per_context(s, closing_paren(s), [&](Parser& r, const char* where) {
+        std::vector<Indices> idx;
+        for (size_t k = 0; k < nargs; ++k) { if (k) r.take(","); idx.push_back(r.sel_or().indices()); }
+        r.take(")");
+        if (*where) for (auto& ix : idx) if (ix.empty()) fail("%s: empty selection%s", s.nm(), where);
+        for (size_t k = 0; k < nargs; ++k) sets[k].push(idx[k]);
+    });
+    const vmd_distance_kind_t kind = dist_kind(fn);
+    if (P) return [ir = s.ir, name = s.name, sets, nargs, kind, P]() {          // one value per context
+        const int32_t *a = sets[0].all.data(), *ao = sets[0].off.data(), *b = sets[1].all.data(), *bo = sets[1].off.data();
+        if (nargs == 2) { added(vmd_ir_add_distance_population(ir, name.c_str(), kind, P, a, ao, b, bo)); return; }
+        const int32_t *c = sets[2].all.data(), *co = sets[2].off.data();
+        added(nargs == 3 ? vmd_ir_add_angle_population(ir, name.c_str(), P, a, ao, b, bo, c, co)
+                         : vmd_ir_add_dihedral_population(ir, name.c_str(), P, a, ao, b, bo, c, co, sets[3].all.data(), sets[3].off.data()));
+    };
+    return [ir = s.ir, name = s.name, sets, nargs, kind]() {
+        const Indices &a = sets[0].all, &b = sets[1].all;
+        if (nargs == 2) { added(vmd_ir_add_distance(ir, name.c_str(), kind, a.data(), a.size(), b.data(), b.size())); return; }
+        const Indices& c = sets[2].all;
+        added(nargs == 3 ? vmd_ir_add_angle(ir, name.c_str(), a.data(), a.size(), b.data(), b.size(), c.data(), c.size())
+                         : vmd_ir_add_dihedral(ir, name.c_str(), a.data(), a.size(), b.data(), b.size(), c.data(), c.size(), sets[3].all.data(),
+                                               sets[3].all.size()));
+    };
+}
+
+// One statement from its first token up to (not including) its ';': the left-hand side into s.name, then the form's function.
+// features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
+// `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)`, VMD_SCRIPT_FEATURE_WITHIN
+// `name = count(sel and within(r, sel))`, VMD_SCRIPT_FEATURE_SHELL_RDF the same AND as an argument of rdf(), VMD_SCRIPT_FEATURE_SHELL_SDF
+// as the target argument of sdf(), VMD_SCRIPT_FEATURE_SHELL_EXPR expressions over within() in count() and sdf() (opt-in; 0 = the subset
+// of the header, byte for byte)
+Commit statement(Statement& s) {
+    Parser& p = s.p;
+    if (p.is_word("{")) {
+        // tuple assignment `{a, b, c} = f(...)`: shape_weights, under its bit, or nothing
+        p.take("{");
+        s.name = p.take(nullptr, T_ID);
+        while (p.accept(",")) s.name += "," + p.take(nullptr, T_ID);
+        p.take("}");
+        p.take("=");
+        const Token& f = p.peek();
+        if (s.has(VMD_SCRIPT_FEATURE_RMSD) && f.kind == T_ID && f.text == "rmsd") fail("%s: rmsd defines one property, not a tuple", s.nm());
+        if (!(s.has(VMD_SCRIPT_FEATURE_SHAPE) && f.kind == T_ID && f.text == "shape_weights"))
+            fail("unsupported %s '%s' (outside the rdf / sdf / distance path)", f.kind == T_ID ? "function" : "expression", f.text.c_str());
+        s.is_property = true;
+        return shape_statement(s);
+    }
+    s.name = p.take(nullptr, T_ID);
+    p.take("=");
+    const Token k = p.peek();
+    const std::string& v = k.text;
+    if (s.has(VMD_SCRIPT_FEATURE_SHAPE) && k.kind == T_ID && v == "shape_weights")
+        fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not 1", s.nm());
+    const bool is_func = k.kind == T_ID && (v == "rdf" || v == "sdf" || v == "distance" || v == "distance_min" || v == "distance_max" ||
+                                            v == "distance_pair" || (s.has(VMD_SCRIPT_FEATURE_ANGLES) && (v == "angle" || v == "dihedral")) ||
+                                            (s.has(VMD_SCRIPT_FEATURE_RMSD) && v == "rmsd") || (s.has(VMD_SCRIPT_FEATURE_WITHIN) && v == "count"));
+    if (!is_func) {
+        const Sel sel = p.sel_or();
+        return [&env = s.env, name = s.name, sel]() { env[name] = sel; };
+    }
+    s.is_property = true;
+    ++p.i;
+    p.take("(");
+    if (v == "rdf") return rdf_statement(s);
+    if (v == "sdf") return sdf_statement(s);
+    if (v == "rmsd") return rmsd_statement(s);
+    if (v == "count") return s.has(VMD_SCRIPT_FEATURE_SHELL_EXPR) ? count_expr_statement(s) : count_statement(s);
+    return geometry_statement(s, v);
+}
+
+// a compiled property that a SKIPPED statement uses (`d = distance(1,2); x = d * 2;`) must stay in the fallback's text, or
+// mdlib cannot compile the reduced script.  Blanked statements {left-hand name, token range, byte range} and the token ranges of the
+// skipped ones are recorded; after the pass every blanked statement whose name a kept statement mentions is restored, transitively
+struct Blanked { std::string name; size_t tok_first, tok_end, beg, end; bool kept; };
+using TokRange = std::pair<size_t, size_t>;
+
+void restore_mentioned(std::string& fallback, const char* source, const std::vector<Token>& toks, std::vector<Blanked>& blanked,
+                       const std::vector<TokRange>& skipped_toks) {
+    std::set<std::string> used;
+    // identifiers on the right-hand side of a statement (everything after its first `=`; the whole statement when it has none)
+    auto collect = [&](size_t a, size_t b) {
+        size_t k = a;
+        for (size_t q = a; q < b && q < toks.size(); ++q) if (toks[q].kind == T_OP && toks[q].text == "=") { k = q + 1; break; }
+        for (; k < b && k < toks.size(); ++k) if (toks[k].kind == T_ID) used.insert(toks[k].text);
+    };
+    for (const auto& r : skipped_toks) collect(r.first, r.second);
+    for (bool changed = true; changed;) {
+        changed = false;
+        for (Blanked& b : blanked) {
+            // (a shape_weights statement carries its three names joined by ',')
+            bool mentioned = false;
+            for (size_t n0 = 0; n0 <= b.name.size() && !mentioned;) {
+                const size_t n1 = std::min(b.name.find(',', n0), b.name.size());
+                mentioned = used.count(b.name.substr(n0, n1 - n0)) != 0;
+                n0 = n1 + 1;
+            }
+            if (b.kept || !mentioned) continue;
+            b.kept = changed = true;
+            for (size_t c = b.beg; c < b.end; ++c) fallback[c] = source[c];        // the GPU still evaluates it; mdlib evaluates it too, for its users
+            collect(b.tok_first, b.tok_end);
+        }
+    }
+}
+
 // One statement at a time.  A statement is parsed completely - up to its ';' - before its descriptor is appended, so a statement that
 // fails leaves neither a property nor an identifier behind.  report == nullptr: the first error ends the compilation (the strict
 // mode).  Otherwise the failing statement is recorded {left-hand names, source range, reason} and the next one is compiled: what a host
 // hands to the evaluator it falls back on (include/vmd_md_script_shim.h), e.g. `a1 = angle(2,1,3) in resname("ALA");` and
 // `{lin,plan,iso} = shape_weights(all);` of VIAMD's default script (src/main.cpp:528).  A later statement that uses an identifier of a
 // skipped one is skipped with it ("unknown identifier").
-// features: VMD_SCRIPT_FEATURE_ANGLES also takes angle() / dihedral(), VMD_SCRIPT_FEATURE_SHAPE the tuple statement
-// `{lin, plan, iso} = shape_weights(sel)`, VMD_SCRIPT_FEATURE_RMSD `name = rmsd(sel)`, VMD_SCRIPT_FEATURE_WITHIN
-// `name = count(sel and within(r, sel))`, VMD_SCRIPT_FEATURE_SHELL_RDF the same AND as an argument of rdf(), VMD_SCRIPT_FEATURE_SHELL_SDF as the
-// target argument of sdf() (opt-in; 0 = the subset above, byte for byte)
 void compile(vmd_script_ir_t* ir, const char* source, const vmd_topology_t* t, Report* report, uint32_t features = 0) {
     const Topo topo(t);
     const std::vector<Token> toks = tokenize(source, report != nullptr);
     std::map<std::string, Sel> env;
     Parser p(toks, topo, env);
-    auto check = [](bool ok) { if (!ok) throw ScriptError(vmd_last_error()); };
     std::string fallback(source);
-    // a compiled property that a SKIPPED statement uses (`d = distance(1,2); x = d * 2;`) must stay in the fallback's text, or
-    // mdlib cannot compile the reduced script.  Blanked statements {left-hand name, token range, byte range} and the token ranges of the
-    // skipped ones are recorded; after the pass every blanked statement whose name a kept statement mentions is restored, transitively
-    struct Blanked { std::string name; size_t tok_first, tok_end, beg, end; bool kept; };
     std::vector<Blanked> blanked;
-    std::vector<std::pair<size_t, size_t>> skipped_toks;
+    std::vector<TokRange> skipped_toks;
     while (p.peek().kind != T_END) {
         if (p.accept(";")) continue;
         const size_t first = p.i;
         // the statement's extent: up to the next ';' outside brackets (or the end of the text)
         size_t last = first;
-        {
-            int depth = 0;
-            for (; last < toks.size(); ++last) {
-                const Token& k = toks[last];
-                if (k.kind != T_OP) continue;
-                if (k.text == "(" || k.text == "[" || k.text == "{") depth += 1;
-                else if (k.text == ")" || k.text == "]" || k.text == "}") depth -= 1;
-                else if (k.text == ";" && depth <= 0) break;
-            }
+        for (int depth = 0; last < toks.size(); ++last) {
+            const Token& k = toks[last];
+            if (k.kind != T_OP) continue;
+            if (k.text == "(" || k.text == "[" || k.text == "{") depth += 1;
+            else if (k.text == ")" || k.text == "]" || k.text == "}") depth -= 1;
+            else if (k.text == ";" && depth <= 0) break;
         }
-        std::string names;
-        std::function<void()> commit;
-        bool is_property = false;
-        // the end of every statement: its ';', the descriptor, and in partial mode the statement's text taken out of the fallback's
-        auto finish_statement = [&]() {
+        Statement s{toks, topo, env, ir, features, p, ""};
+        try {
+            const Commit commit = statement(s);
+            // the end of every statement: its ';', the descriptor, and in partial mode the statement's text taken out of the fallback's
             if (p.peek().kind != T_END && !p.is_word(";")) fail("expected ;, found '%s'", p.peek().text.c_str());
             commit();
             if (p.peek().kind != T_END) p.take(";");
-            if (is_property && report) {
+            if (s.is_property && report) {
                 // the fallback evaluates the text WITHOUT this statement: blanked in place, so that every other offset stays what the editor shows
                 const size_t e = last < toks.size() ? toks[last].end : toks[last - 1].end;
                 for (size_t c = toks[first].beg; c < e && c < fallback.size(); ++c) if (fallback[c] != '\n') fallback[c] = ' ';
-                blanked.push_back(Blanked{names, first, last, toks[first].beg, std::min(e, fallback.size()), false});
+                blanked.push_back(Blanked{s.name, first, last, toks[first].beg, std::min(e, fallback.size()), false});
             }
-        };
-        try {
-            if (p.is_word("{")) {
-                // tuple assignment `{a, b, c} = f(...)`: no hot-path function returns a tuple
-                p.take("{");
-                names = p.take(nullptr, T_ID);
-                while (p.accept(",")) names += "," + p.take(nullptr, T_ID);
-                p.take("}");
-                p.take("=");
-                const Token& f = p.peek();
-                if ((features & VMD_SCRIPT_FEATURE_RMSD) && f.kind == T_ID && f.text == "rmsd")
-                    fail("%s: rmsd defines one property, not a tuple", names.c_str());
-                if (!((features & VMD_SCRIPT_FEATURE_SHAPE) && f.kind == T_ID && f.text == "shape_weights"))
-                    fail("unsupported %s '%s' (outside the rdf / sdf / distance path)", f.kind == T_ID ? "function" : "expression", f.text.c_str());
-                // `{lin, plan, iso} = shape_weights(sel) [in <contexts>];`: the one function of the subset that defines a tuple
-                std::vector<std::string> nm(1);
-                for (char ch : names) { if (ch == ',') nm.emplace_back(); else nm.back() += ch; }
-                if (nm.size() != 3) fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not %zu", names.c_str(), nm.size());
-                ++p.i;
-                p.take("(");
-                const size_t start = p.i;
-                size_t j = p.i;
-                int depth = 1;
-                while (depth) {
-                    if (j >= toks.size()) fail("%s: missing ')'", names.c_str());
-                    if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
-                    if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
-                    ++j;
-                }
-                std::vector<int32_t> all, off{0};
-                auto one_set = [&](Parser& r, const char* where) {
-                    const std::vector<int32_t> ix = r.sel_or().indices();
-                    if (r.is_word(",")) fail("%s: shape_weights takes one selection", names.c_str());
-                    r.take(")");
-                    if (ix.empty()) fail("%s: empty selection%s", names.c_str(), where);
-                    all.insert(all.end(), ix.begin(), ix.end());
-                    off.push_back((int32_t)all.size());
-                };
-                if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
-                    Parser q(toks, topo, env);
-                    q.i = j + 1;
-                    const Sel ctx = q.sel_or();
-                    if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", names.c_str());
-                    for (auto& st : ctx.structs) {
-                        Parser r(toks, topo, env, &st);
-                        r.i = start;
-                        one_set(r, " inside a context");
-                    }
-                    p.i = q.i;
-                } else one_set(p, "");
-                is_property = true;
-                commit = [=]() {
-                    const char* const cn[3] = {nm[0].c_str(), nm[1].c_str(), nm[2].c_str()};
-                    if (!vmd_ir_add_shape_weights_population(ir, cn, off.size() - 1, all.data(), off.data())) throw ScriptError(vmd_last_error());
-                };
-                finish_statement();
-                continue;
-            }
-            const std::string name = p.take(nullptr, T_ID);
-            names = name;
-            p.take("=");
-            const Token k = p.peek();
-            if ((features & VMD_SCRIPT_FEATURE_SHAPE) && k.kind == T_ID && k.text == "shape_weights")
-                fail("%s: shape_weights defines three properties, {linear, planar, isotropic}, not 1", name.c_str());
-            const bool is_func = k.kind == T_ID && (k.text == "rdf" || k.text == "sdf" || k.text == "distance" || k.text == "distance_min" ||
-                                                    k.text == "distance_max" || k.text == "distance_pair" ||
-                                                    ((features & VMD_SCRIPT_FEATURE_ANGLES) && (k.text == "angle" || k.text == "dihedral")) ||
-                                                    ((features & VMD_SCRIPT_FEATURE_RMSD) && k.text == "rmsd") ||
-                                                    ((features & VMD_SCRIPT_FEATURE_WITHIN) && k.text == "count"));
-            if (is_func) {
-                is_property = true;
-                const std::string v = k.text;
-                ++p.i;
-                p.take("(");
-                // a selection argument of rdf() (either one) or sdf() (the target) may be
-                // `<factor> and ... and within(<r> | <a>:<b>, <static selection>)` - the rules of the count form below: exactly one within() per
-                // argument, at the top level of the AND, its argument static
-                struct DynArg { std::vector<int32_t> list, ref; bool shell = false; double rmin = 0.0, rmax = 0.0; };
-                auto dyn_arg = [&](const char* fn) -> DynArg {
-                    DynArg out;
-                    const size_t start = p.i;
-                    size_t n_within = 0, n_top = 0;
-                    bool top_or = false;
-                    int depth = 0;
-                    for (size_t q = start; q < toks.size(); ++q) {      // up to the ',' that ends the argument
-                        const Token& tk = toks[q];
-                        if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
-                        if (tk.kind == T_OP && tk.text == "(") depth += 1;
-                        if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
-                        if (tk.kind == T_ID && tk.text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(") {
-                            n_within += 1;
-                            if (depth == 0 && (q == start || (toks[q - 1].kind == T_ID && toks[q - 1].text == "and"))) n_top += 1;
-                        }
-                        if (tk.kind == T_ID && tk.text == "or" && depth == 0) top_or = true;
-                    }
-                    if (n_within == 0) { out.list = p.sel_or().indices(); return out; }
-                    if (n_within > 1) fail("%s: an %s argument takes exactly one within() factor, found %zu", name.c_str(), fn, n_within);
-                    if (n_top != 1 || top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", name.c_str());
-                    std::vector<uint8_t> tmask(topo.n, 1);
-                    out.shell = true;
-                    do {
-                        if (p.peek().kind == T_ID && p.peek().text == "within") {
-                            ++p.i;
-                            p.take("(");
-                            out.rmax = p.number();
-                            if (p.accept(":")) {
-                                out.rmin = out.rmax; out.rmax = p.number();
-                                if (!(out.rmin < out.rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
-                            } else if (!(out.rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
-                            p.take(",");
-                            out.ref = p.sel_or().indices();
-                            p.take(")");
-                            if (out.ref.empty()) fail("%s: empty selection", name.c_str());
-                        } else {
-                            const Sel f = p.sel_not();
-                            for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a];
-                        }
-                    } while (p.accept("and"));
-                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
-                    return out;
-                };
-                // DESIGN 1.9 (VMD_SCRIPT_FEATURE_SHELL_EXPR): the argument of count() and the target of sdf() may hold several dynamic
-                // factors at the top level of their AND - within(...), not within(...), or a parenthesised and / or / not over within()
-                // terms only.  Terms that repeat are one term, numbered in order of first appearance; a table over four variables is
-                // carried through the parse and cut to the terms there are
-                struct ExprTerm { std::vector<int32_t> ref; float rmin, rmax; };
-                struct ExprArg { std::vector<int32_t> list; std::vector<ExprTerm> terms; uint32_t truth = 0; bool dynamic = false; };
-                auto is_within_at = [&](size_t q) {
-                    return toks[q].kind == T_ID && toks[q].text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(";
-                };
-                auto expr_arg = [&]() -> ExprArg {
-                    static const uint32_t VAR[4] = {0xAAAAu, 0xCCCCu, 0xF0F0u, 0xFF00u};
-                    ExprArg out;
-                    // [from, the end of the argument or, with stop_and, the next `and` at depth 0) -> {end, holds within(, holds a top-level or}
-                    auto extent = [&](size_t from, bool stop_and, bool* has_within, bool* top_or) {
-                        int depth = 0;
-                        size_t q = from;
-                        for (; q < toks.size(); ++q) {
-                            const Token& tk = toks[q];
-                            if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
-                            if (tk.kind == T_OP && tk.text == "(") depth += 1;
-                            if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
-                            if (stop_and && depth == 0 && tk.kind == T_ID && tk.text == "and") break;
-                            if (is_within_at(q)) *has_within = true;
-                            if (tk.kind == T_ID && tk.text == "or" && depth == 0) *top_or = true;
-                        }
-                        return q;
-                    };
-                    bool has_within = false, top_or = false;
-                    extent(p.i, false, &has_within, &top_or);
-                    if (!has_within) { out.list = p.sel_or().indices(); return out; }
-                    if (top_or) fail("%s: a dynamic factor under a top-level or with a static selection", name.c_str());
-                    out.dynamic = true;
-                    auto within_term = [&]() -> uint32_t {
-                        ++p.i;
-                        p.take("(");
-                        double rmin = 0.0, rmax = p.number();
-                        if (p.accept(":")) {
-                            rmin = rmax; rmax = p.number();
-                            if (!(rmin < rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
-                        } else if (!(rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
-                        p.take(",");
-                        bool nested = false, unused = false;
-                        extent(p.i, false, &nested, &unused);
-                        if (nested) fail("%s: within() nested in a within() argument", name.c_str());
-                        ExprTerm t{p.sel_or().indices(), (float)rmin, (float)rmax};
-                        p.take(")");
-                        if (t.ref.empty()) fail("%s: empty selection", name.c_str());
-                        for (size_t k = 0; k < out.terms.size(); ++k)
-                            if (out.terms[k].ref == t.ref && out.terms[k].rmin == t.rmin && out.terms[k].rmax == t.rmax) return VAR[k];
-                        if (out.terms.size() == VMD_SHELL_EXPR_MAX_TERMS) fail("%s: more than four distinct within() terms", name.c_str());
-                        out.terms.push_back(std::move(t));
-                        return VAR[out.terms.size() - 1];
-                    };
-                    std::function<uint32_t()> dyn_or;
-                    std::function<uint32_t()> dyn_not = [&]() -> uint32_t {
-                        if (p.accept("not")) return ~dyn_not() & 0xffffu;
-                        if (p.i < toks.size() && is_within_at(p.i)) return within_term();
-                        if (p.is_word("(")) { p.take("("); const uint32_t t = dyn_or(); p.take(")"); return t; }
-                        fail("%s: a static selection inside a parenthesised dynamic factor", name.c_str());
-                    };
-                    auto dyn_and = [&]() -> uint32_t { uint32_t t = dyn_not(); while (p.accept("and")) t &= dyn_not(); return t; };
-                    dyn_or = [&]() -> uint32_t { uint32_t t = dyn_and(); while (p.accept("or")) t |= dyn_and(); return t; };
-                    std::vector<uint8_t> tmask(topo.n, 1);
-                    uint32_t table = 0xffffu;
-                    do {
-                        bool dyn = false, unused = false;
-                        extent(p.i, true, &dyn, &unused);
-                        if (dyn) table &= dyn_not();
-                        else { const Sel f = p.sel_not(); for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a]; }
-                    } while (p.accept("and"));
-                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) out.list.push_back((int32_t)a);
-                    out.truth = table & ((1u << (1u << out.terms.size())) - 1u);
-                    return out;
-                };
-                auto expr_view = [](const ExprArg& x, std::vector<vmd_shell_t>* terms) {
-                    terms->clear();
-                    for (auto& t : x.terms) terms->push_back(vmd_shell_t{t.ref.data(), t.ref.size(), t.rmin, t.rmax});
-                    return vmd_shell_expr_t{terms->data(), terms->size(), x.truth};
-                };
-                const bool exprs = (features & VMD_SCRIPT_FEATURE_SHELL_EXPR) != 0;
-                if (v == "rdf" && (features & VMD_SCRIPT_FEATURE_SHELL_RDF)) {
-                    const DynArg A = dyn_arg("rdf"); p.take(",");
-                    const DynArg B = dyn_arg("rdf"); p.take(",");
-                    double rmin = 0.0, rmax;
-                    if (p.accept("{")) { rmin = p.number(); p.take(","); rmax = p.number(); p.take("}"); }
-                    else {
-                        rmax = p.number();
-                        if (p.accept(":")) { rmin = rmax; rmax = p.number(); }
-                    }
-                    p.take(")");
-                    if (A.list.empty() || B.list.empty()) fail("%s: empty selection", name.c_str());
-                    commit = [=]() {
-                        const vmd_shell_t sa{A.ref.data(), A.ref.size(), (float)A.rmin, (float)A.rmax};
-                        const vmd_shell_t sb{B.ref.data(), B.ref.size(), (float)B.rmin, (float)B.rmax};
-                        if (!vmd_ir_add_rdf_shell(ir, name.c_str(), A.list.data(), A.list.size(), A.shell ? &sa : nullptr, B.list.data(), B.list.size(),
-                                B.shell ? &sb : nullptr, (float)rmin, (float)rmax)) throw ScriptError(vmd_last_error());
-                    };
-                } else if (v == "rdf") {
-                    const Sel ref = p.sel_or(); p.take(",");
-                    const Sel tgt = p.sel_or(); p.take(",");
-                    double rmin = 0.0, rmax;
-                    if (p.accept("{")) { rmin = p.number(); p.take(","); rmax = p.number(); p.take("}"); }
-                    else {
-                        rmax = p.number();
-                        if (p.accept(":")) { rmin = rmax; rmax = p.number(); }
-                    }
-                    p.take(")");
-                    const auto a = ref.indices(), b = tgt.indices();
-                    if (a.empty() || b.empty()) fail("%s: empty selection", name.c_str());
-                    commit = [=]() { if (!vmd_ir_add_rdf(ir, name.c_str(), a.data(), a.size(), b.data(), b.size(), (float)rmin, (float)rmax)) throw ScriptError(vmd_last_error()); };
-                } else if (v == "sdf") {
-                    const bool shells = (features & VMD_SCRIPT_FEATURE_SHELL_SDF) != 0;
-                    if (shells) {       // the structures stay static - the alignment needs fixed atoms
-                        int depth = 0;
-                        for (size_t q = p.i; q < toks.size(); ++q) {
-                            const Token& tk = toks[q];
-                            if (tk.kind == T_OP && (tk.text == "," || tk.text == ";") && depth == 0) break;
-                            if (tk.kind == T_OP && tk.text == "(") depth += 1;
-                            if (tk.kind == T_OP && tk.text == ")") { if (depth == 0) break; depth -= 1; }
-                            if (tk.kind == T_ID && tk.text == "within" && q + 1 < toks.size() && toks[q + 1].kind == T_OP && toks[q + 1].text == "(")
-                                fail("%s: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)", name.c_str());
-                        }
-                    }
-                    const Sel ref = p.sel_or(); p.take(",");
-                    DynArg T;
-                    ExprArg X;
-                    if (shells && exprs) { X = expr_arg(); T.list = X.list; }
-                    else if (shells) T = dyn_arg("sdf"); else T.list = p.sel_or().indices();
-                    p.take(",");
-                    const double cutoff = p.number();
-                    p.take(")");
-                    std::vector<std::vector<int32_t>> structs = ref.has_structs ? ref.structs : std::vector<std::vector<int32_t>>{ref.indices()};
-                    if (structs.empty()) fail("%s: sdf reference structures must be non-empty and of equal size", name.c_str());
-                    const size_t m = structs[0].size();
-                    std::vector<int32_t> flat;
-                    for (auto& st : structs) {
-                        if (st.size() != m || m == 0) fail("%s: sdf reference structures must be non-empty and of equal size", name.c_str());
-                        flat.insert(flat.end(), st.begin(), st.end());
-                    }
-                    const size_t K = structs.size();
-                    if ((T.shell || X.dynamic) && T.list.empty()) fail("%s: empty selection", name.c_str());
-                    if (X.dynamic) commit = [=]() {
-                        std::vector<vmd_shell_t> tv;
-                        const vmd_shell_expr_t xv = expr_view(X, &tv);
-                        if (!vmd_ir_add_sdf_shell_expr(ir, name.c_str(), flat.data(), K, m, X.list.data(), X.list.size(), &xv, (float)cutoff))
-                            throw ScriptError(vmd_last_error());
-                    };
-                    else commit = [=]() {
-                        const vmd_shell_t sh{T.ref.data(), T.ref.size(), (float)T.rmin, (float)T.rmax};
-                        if (!vmd_ir_add_sdf_shell(ir, name.c_str(), flat.data(), K, m, T.list.data(), T.list.size(), T.shell ? &sh : nullptr, (float)cutoff))
-                            throw ScriptError(vmd_last_error());
-                    };
-                } else if (v == "count" && exprs) {
-                    // `name = count(<factor> and <factor> ...);` with any number of dynamic factors
-                    const ExprArg X = expr_arg();
-                    if (!X.dynamic) fail("%s: count of a static selection is a constant (left to the fallback)", name.c_str());
-                    p.take(")");
-                    if (p.is_word("in")) fail("%s: count(...) in <contexts> is outside the subset", name.c_str());
-                    if (X.list.empty()) fail("%s: empty selection", name.c_str());
-                    commit = [=]() {
-                        std::vector<vmd_shell_t> tv;
-                        const vmd_shell_expr_t xv = expr_view(X, &tv);
-                        if (!vmd_ir_add_within_count_expr(ir, name.c_str(), X.list.data(), X.list.size(), &xv)) throw ScriptError(vmd_last_error());
-                    };
-                } else if (v == "count") {
-                    // `name = count(<factor> and <factor> ...);`: exactly one factor is within(<r> | <a>:<b>, <static selection>),
-                    // the others are static selections whose AND is the target set (all atoms when there is none)
-                    const size_t start = p.i;
-                    size_t j = p.i;
-                    int depth = 1;
-                    while (depth) {
-                        if (j >= toks.size()) fail("%s: missing ')'", name.c_str());
-                        if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
-                        if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
-                        ++j;
-                    }
-                    size_t n_within = 0, n_top = 0;
-                    bool top_or = false;
-                    depth = 0;
-                    for (size_t q = start; q + 1 < j; ++q) {
-                        const Token& tk = toks[q];
-                        if (tk.kind == T_OP && tk.text == "(") depth += 1;
-                        if (tk.kind == T_OP && tk.text == ")") depth -= 1;
-                        if (tk.kind == T_ID && tk.text == "within" && toks[q + 1].kind == T_OP && toks[q + 1].text == "(") {
-                            n_within += 1;
-                            if (depth == 0 && (q == start || (toks[q - 1].kind == T_ID && toks[q - 1].text == "and"))) n_top += 1;
-                        }
-                        if (tk.kind == T_ID && tk.text == "or" && depth == 0) top_or = true;
-                    }
-                    if (n_within == 0) fail("%s: count of a static selection is a constant (left to the fallback)", name.c_str());
-                    if (n_within > 1) fail("%s: count takes exactly one within() factor, found %zu", name.c_str(), n_within);
-                    if (n_top != 1 || top_or) fail("%s: within() must be a factor of the top-level AND (not under not / or / parentheses)", name.c_str());
-                    std::vector<uint8_t> tmask(topo.n, 1);
-                    std::vector<int32_t> ref;
-                    double rmin = 0.0, rmax = 0.0;
-                    do {
-                        if (p.peek().kind == T_ID && p.peek().text == "within") {
-                            ++p.i;
-                            p.take("(");
-                            rmax = p.number();
-                            if (p.accept(":")) {
-                                rmin = rmax; rmax = p.number();
-                                if (!(rmin < rmax)) fail("%s: within range needs 0 <= a < b", name.c_str());
-                            } else if (!(rmax > 0.0)) fail("%s: within needs a radius > 0", name.c_str());
-                            p.take(",");
-                            ref = p.sel_or().indices();
-                            p.take(")");
-                            if (ref.empty()) fail("%s: empty selection", name.c_str());
-                        } else {
-                            const Sel f = p.sel_not();
-                            for (size_t a = 0; a < topo.n; ++a) tmask[a] &= f.mask[a];
-                        }
-                    } while (p.accept("and"));
-                    p.take(")");
-                    if (p.is_word("in")) fail("%s: count(...) in <contexts> is outside the subset", name.c_str());
-                    std::vector<int32_t> tgt;
-                    for (size_t a = 0; a < topo.n; ++a) if (tmask[a]) tgt.push_back((int32_t)a);
-                    if (tgt.empty()) fail("%s: empty selection", name.c_str());
-                    commit = [=]() {
-                        if (!vmd_ir_add_within_count(ir, name.c_str(), tgt.data(), tgt.size(), ref.data(), ref.size(), (float)rmin, (float)rmax))
-                            throw ScriptError(vmd_last_error());
-                    };
-                } else if (v == "rmsd") {
-                    // `name = rmsd(sel) [in <contexts>];`: one selection, the selection and context rules of distance()
-                    const size_t start = p.i;
-                    size_t j = p.i;
-                    int depth = 1;
-                    while (depth) {
-                        if (j >= toks.size()) fail("%s: missing ')'", name.c_str());
-                        if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
-                        if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
-                        ++j;
-                    }
-                    std::vector<int32_t> all, off{0};
-                    auto one_set = [&](Parser& r, const char* where) {
-                        const std::vector<int32_t> ix = r.sel_or().indices();
-                        if (r.is_word(",")) fail("%s: rmsd takes one selection", name.c_str());
-                        r.take(")");
-                        if (ix.empty()) fail("%s: empty selection%s", name.c_str(), where);
-                        all.insert(all.end(), ix.begin(), ix.end());
-                        off.push_back((int32_t)all.size());
-                    };
-                    if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
-                        Parser q(toks, topo, env);
-                        q.i = j + 1;
-                        const Sel ctx = q.sel_or();
-                        if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", name.c_str());
-                        for (auto& st : ctx.structs) {
-                            Parser r(toks, topo, env, &st);
-                            r.i = start;
-                            one_set(r, " inside a context");
-                        }
-                        p.i = q.i;
-                    } else one_set(p, "");
-                    commit = [=]() {
-                        if (!vmd_ir_add_rmsd_population(ir, name.c_str(), off.size() - 1, all.data(), off.data())) throw ScriptError(vmd_last_error());
-                    };
-                } else {
-                    // the arguments may be followed by `in <contexts>`: find the closing parenthesis first
-                    const size_t start = p.i;
-                    size_t j = p.i;
-                    int depth = 1;
-                    while (depth) {
-                        if (j >= toks.size()) fail("%s: missing ')'", name.c_str());
-                        if (toks[j].kind == T_OP && toks[j].text == "(") depth += 1;
-                        if (toks[j].kind == T_OP && toks[j].text == ")") depth -= 1;
-                        ++j;
-                    }
-                    // distance*: two argument sets; angle: three; dihedral: four (DESIGN S6b)
-                    const int nargs = v == "angle" ? 3 : (v == "dihedral" ? 4 : 2);
-                    if (j < toks.size() && toks[j].kind == T_ID && toks[j].text == "in") {
-                        Parser q(toks, topo, env);
-                        q.i = j + 1;
-                        const Sel ctx = q.sel_or();
-                        if (!ctx.has_structs || ctx.structs.empty()) fail("%s: `in` needs an array of structures (residue(...), resname(...))", name.c_str());
-                        std::vector<std::vector<int32_t>> all(nargs), off(nargs, std::vector<int32_t>{0});
-                        for (auto& st : ctx.structs) {
-                            Parser r(toks, topo, env, &st);
-                            r.i = start;
-                            std::vector<std::vector<int32_t>> idx;
-                            for (int k = 0; k < nargs; ++k) { if (k) r.take(","); idx.push_back(r.sel_or().indices()); }
-                            r.take(")");
-                            for (auto& ix : idx) if (ix.empty()) fail("%s: empty selection inside a context", name.c_str());
-                            for (int k = 0; k < nargs; ++k) { all[k].insert(all[k].end(), idx[k].begin(), idx[k].end()); off[k].push_back((int32_t)all[k].size()); }
-                        }
-                        p.i = q.i;
-                        const size_t P = ctx.structs.size();
-                        if (nargs == 2) {
-                            const vmd_distance_kind_t kind = dist_kind(v);
-                            const std::vector<int32_t> a_all = all[0], b_all = all[1], a_off = off[0], b_off = off[1];
-                            commit = [=]() {
-                                if (!vmd_ir_add_distance_population(ir, name.c_str(), kind, P, a_all.data(), a_off.data(), b_all.data(), b_off.data())) throw ScriptError(vmd_last_error());
-                            };
-                        } else {
-                            commit = [=]() {
-                                const bool ok = nargs == 3
-                                    ? vmd_ir_add_angle_population(ir, name.c_str(), P, all[0].data(), off[0].data(), all[1].data(), off[1].data(), all[2].data(), off[2].data())
-                                    : vmd_ir_add_dihedral_population(ir, name.c_str(), P, all[0].data(), off[0].data(), all[1].data(), off[1].data(), all[2].data(),
-                                                                     off[2].data(), all[3].data(), off[3].data());
-                                if (!ok) throw ScriptError(vmd_last_error());
-                            };
-                        }
-                    } else {
-                        std::vector<std::vector<int32_t>> idx;
-                        for (int k = 0; k < nargs; ++k) { if (k) p.take(","); idx.push_back(p.sel_or().indices()); }
-                        p.take(")");
-                        if (nargs == 2) {
-                            const auto ai = idx[0], bi = idx[1];
-                            const vmd_distance_kind_t kind = dist_kind(v);
-                            commit = [=]() { if (!vmd_ir_add_distance(ir, name.c_str(), kind, ai.data(), ai.size(), bi.data(), bi.size())) throw ScriptError(vmd_last_error()); };
-                        } else {
-                            commit = [=]() {
-                                const bool ok = nargs == 3
-                                    ? vmd_ir_add_angle(ir, name.c_str(), idx[0].data(), idx[0].size(), idx[1].data(), idx[1].size(), idx[2].data(), idx[2].size())
-                                    : vmd_ir_add_dihedral(ir, name.c_str(), idx[0].data(), idx[0].size(), idx[1].data(), idx[1].size(), idx[2].data(),
-                                                          idx[2].size(), idx[3].data(), idx[3].size());
-                                if (!ok) throw ScriptError(vmd_last_error());
-                            };
-                        }
-                    }
-                }
-            } else {
-                const Sel sel = p.sel_or();
-                commit = [&env, name, sel]() { env[name] = sel; };
-            }
-            finish_statement();
         } catch (const ScriptError& e) {
             if (!report) throw;
-            (void)check;
-            if (names.empty()) names = toks[first].text;
             const size_t send = last > first ? toks[last - 1].end : toks[first].end;
-            report->skipped.push_back({names, toks[first].beg, send, e.what()});
+            report->skipped.push_back({s.name.empty() ? toks[first].text : s.name, toks[first].beg, send, e.what()});
             skipped_toks.emplace_back(first, last);
             p.i = last < toks.size() ? last + 1 : last;
         }
     }
     if (report) {
-        std::set<std::string> used;
-        // identifiers on the right-hand side of a statement (everything after its first `=`; the whole statement when it has none)
-        auto collect = [&](size_t a, size_t b) {
-            size_t k = a;
-            for (size_t q = a; q < b && q < toks.size(); ++q) if (toks[q].kind == T_OP && toks[q].text == "=") { k = q + 1; break; }
-            for (; k < b && k < toks.size(); ++k) if (toks[k].kind == T_ID) used.insert(toks[k].text);
-        };
-        for (const auto& r : skipped_toks) collect(r.first, r.second);
-        for (bool changed = true; changed;) {
-            changed = false;
-            for (Blanked& b : blanked) {
-                // (a shape_weights statement carries its three names joined by ',')
-                bool mentioned = false;
-                for (size_t n0 = 0; n0 <= b.name.size() && !mentioned;) {
-                    const size_t n1 = std::min(b.name.find(',', n0), b.name.size());
-                    mentioned = used.count(b.name.substr(n0, n1 - n0)) != 0;
-                    n0 = n1 + 1;
-                }
-                if (b.kept || !mentioned) continue;
-                b.kept = changed = true;
-                for (size_t c = b.beg; c < b.end; ++c) fallback[c] = source[c];        // the GPU still evaluates it; mdlib evaluates it too, for its users
-                collect(b.tok_first, b.tok_end);
-            }
-        }
+        restore_mentioned(fallback, source, toks, blanked, skipped_toks);
         report->fallback_source = fallback;
     }
 }

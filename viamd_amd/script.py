@@ -12,6 +12,10 @@ generates or ships as defaults (src/main.cpp:528, :2817-2858):
 Selections: element('X') | type/name('X') | resname("X") | residue(a:b) | resid(a:b) | atom(a:b) | integer | all | water |
 protein, combined with `and`, `or`, `not`, parentheses; `sel[a:b]` slices an array of structures (1-based, inclusive).
 The output is a ScriptIR of property descriptors (vmd_ir_add_rdf/_sdf/_distance); nothing is evaluated here.
+
+The twin of viamd_amd/csrc/vmd_script.cpp, cut into the same functions under the same names (with a leading underscore): _statement()
+reads the left-hand side and calls one _*_statement function per statement form.  A new form is one such function here, its twin
+there, and a generator method plus the form's refusals in tests/script_cases.py.
 """
 import re
 
@@ -274,6 +278,12 @@ FEATURE_SHELL_SDF = 32                          # VMD_SCRIPT_FEATURE_SHELL_SDF
 FEATURE_SHELL_EXPR = 64                         # VMD_SCRIPT_FEATURE_SHELL_EXPR
 
 
+def _feature_mask(angles, shape, rmsd, within, shell_rdf, shell_sdf, shell_expr):
+    """the keyword switches of compile_script / compile_script_native as the `features` of vmd_ir_compile_from_source_ex"""
+    switches = (angles, shape, rmsd, within, shell_rdf, shell_sdf, shell_expr)
+    return sum(1 << k for k, on in enumerate(switches) if on)
+
+
 def compile_script(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
                    shell_sdf=False, shell_expr=False):
     """Returns (ScriptIR, info) where info[name] = dict(kind=..., plus the resolved index arrays).
@@ -307,6 +317,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
     sdf(), may hold several dynamic factors at the top level of its AND - within(...), not within(...), or a parenthesised and / or / not
     over within() terms only.  info[name] gains terms=[dict(ref=idx, rmin=, rmax=)] in order of first appearance and
     truth= (bit sum(h_i << i) set: a member); a count that does not reduce to one positive term has kind="within_count_expr"."""
+    features = _feature_mask(angles, shape, rmsd, within, shell_rdf, shell_sdf, shell_expr)
     ir = ScriptIR(lib)
     env, info = {}, {}
     spans = []
@@ -319,7 +330,7 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
         if p.accept(";"):
             continue
         first = p.i
-        last, depth = first, 0
+        last, depth = first, 0          # the statement's extent: up to the next ';' outside brackets (or the end of the text)
         while last < len(toks):
             v = toks[last][1] if toks[last][0] == "op" else None
             if v in ("(", "[", "{"):
@@ -329,570 +340,501 @@ def compile_script(text, topo, lib=None, partial=False, angles=False, shape=Fals
             elif v == ";" and depth <= 0:
                 break
             last += 1
-        names = ""
+        s = _Statement(p, topo, env, ir, info, features)
         try:
-            if p.peek()[1] == "{" and p.peek()[0] == "op":
-                p.take("{")
-                names = p.take(kind="id")
-                while p.accept(","):
-                    names += "," + p.take(kind="id")
-                p.take("}")
-                p.take("=")
-                k, v = p.peek()
-                if rmsd and k == "id" and v == "rmsd":
-                    raise ScriptError(f"{names}: rmsd defines one property, not a tuple")
-                if not (shape and k == "id" and v == "shape_weights"):
-                    raise ScriptError(f"unsupported {'function' if k == 'id' else 'expression'} {v!r} (outside the rdf / sdf / distance path)")
-                commit, is_property = _shape_statement(p, names, topo, env, ir, info), True
-            else:
-                name = p.take(kind="id")
-                names = name
-                p.take("=")
-                if shape and p.peek() == ("id", "shape_weights"):
-                    raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
-                commit, is_property = _statement(p, name, topo, env, ir, info, angles, rmsd, within, shell_rdf, shell_sdf, shell_expr)
+            commit = _statement(s)
             if p.peek()[0] is not None and p.peek()[1] != ";":
                 raise ScriptError(f"expected ;, found {p.peek()[1]!r}")
             commit()
             if p.peek()[0] is not None:
                 p.take(";")
-            if is_property and partial:
+            if s.is_property and partial:
                 e = spans[last][1] if last < len(toks) else spans[last - 1][1]
                 for c in range(spans[first][0], min(e, len(fallback))):
                     if fallback[c] != "\n":
                         fallback[c] = " "
-                blanked.append([names, first, last, spans[first][0], min(e, len(fallback)), False])
+                blanked.append([s.name, first, last, spans[first][0], min(e, len(fallback)), False])
         except (ValueError, VmdError) as e:   # ScriptError, int() / float() on a malformed number, a descriptor the library refuses
             if not partial:
                 raise
             send = spans[last - 1][1] if last > first else spans[first][1]
-            skipped.append(dict(names=names or toks[first][1], beg=spans[first][0], end=send, reason=str(e)))
+            skipped.append(dict(names=s.name or toks[first][1], beg=spans[first][0], end=send, reason=str(e)))
             skipped_toks.append((first, last))
             p.i = last + 1 if last < len(toks) else last
     if partial:
-        # a compiled property that a skipped statement uses stays in the fallback's text (the twin of vmd_script.cpp)
-        used = set()
-
-        def collect(a, b):
-            k = a
-            for q in range(a, min(b, len(toks))):
-                if toks[q][0] == "op" and toks[q][1] == "=":
-                    k = q + 1
-                    break
-            used.update(toks[q][1] for q in range(k, min(b, len(toks))) if toks[q][0] == "id")
-
-        for a, b in skipped_toks:
-            collect(a, b)
-        changed = True
-        while changed:
-            changed = False
-            for item in blanked:
-                if item[5] or not any(n in used for n in item[0].split(",")):      # (shape_weights: three names joined by ',')
-                    continue
-                item[5] = changed = True
-                fallback[item[3]:item[4]] = text[item[3]:item[4]]
-                collect(item[1], item[2])
+        _restore_mentioned(fallback, text, toks, blanked, skipped_toks)
         return ir, info, dict(skipped=skipped, fallback_source="".join(fallback))
     return ir, info
 
 
-def _shape_statement(p, names, topo, env, ir, info):
-    """`{n0, n1, n2} = shape_weights(sel) [in <contexts>]` from the function name on (the twin of the tuple branch of vmd_script.cpp)."""
-    nm = names.split(",")
-    if len(nm) != 3:
-        raise ScriptError(f"{names}: shape_weights defines three properties, {{linear, planar, isotropic}}, not {len(nm)}")
+def _restore_mentioned(fallback, text, toks, blanked, skipped_toks):
+    """a compiled property that a skipped statement uses stays in the fallback's text (the twin of restore_mentioned in vmd_script.cpp;
+    ADVICE r05 #2)"""
+    used = set()
+
+    def collect(a, b):
+        k = a
+        for q in range(a, min(b, len(toks))):
+            if toks[q][0] == "op" and toks[q][1] == "=":
+                k = q + 1
+                break
+        used.update(toks[q][1] for q in range(k, min(b, len(toks))) if toks[q][0] == "id")
+
+    for a, b in skipped_toks:
+        collect(a, b)
+    changed = True
+    while changed:
+        changed = False
+        for item in blanked:
+            if item[5] or not any(n in used for n in item[0].split(",")):      # (shape_weights: three names joined by ',')
+                continue
+            item[5] = changed = True
+            fallback[item[3]:item[4]] = text[item[3]:item[4]]
+            collect(item[1], item[2])
+
+
+class _Statement:
+    """What a statement function works on (the twin of struct Statement in vmd_script.cpp).  p stands behind the `(` of the call when a
+    _*_statement function is entered; name: the left-hand side, one name or the names of a tuple joined by ','."""
+
+    def __init__(self, p, topo, env, ir, info, features):
+        self.p, self.topo, self.env, self.ir, self.info, self.features = p, topo, env, ir, info, features
+        self.t, self.name, self.is_property = p.t, "", False
+
+    def has(self, bit):
+        return bool(self.features & bit)
+
+    def is_within_at(self, q):
+        return q + 1 < len(self.t) and self.t[q] == ("id", "within") and self.t[q + 1] == ("op", "(")
+
+
+# ---- helpers the statement forms share (each the twin of the function of the same name in vmd_script.cpp) -------------------------------------
+
+def _closing_paren(s):
+    """the token behind the `)` that closes the call p stands in"""
+    j, depth = s.p.i, 1
+    while depth:
+        if j >= len(s.t):
+            raise ScriptError(f"{s.name}: missing ')'")
+        depth += {"(": 1, ")": -1}.get(s.t[j][1], 0) if s.t[j][0] == "op" else 0
+        j += 1
+    return j
+
+
+def _per_context(s, after, body):
+    """`f(<arguments>) [in <contexts>]`, after = _closing_paren(): body(parser, where) reads the arguments and the `)` - once with the
+    statement's parser (where = ""), or, under `in`, once per structure of the contexts with a parser bound to it (where = " inside a
+    context").  Returns the number of contexts, 0 without `in`."""
+    if not (after < len(s.t) and s.t[after] == ("id", "in")):
+        body(s.p, "")
+        return 0
+    start = s.p.i
+    q = _Parser(s.t, s.topo, s.env)
+    q.i = after + 1
+    ctx = q.sel_or()
+    if ctx.structures is None or not ctx.structures:
+        raise ScriptError(f"{s.name}: `in` needs an array of structures (residue(...), resname(...))")
+    for st in ctx.structures:
+        r = _Parser(s.t, s.topo, s.env, ctx=np.asarray(st))
+        r.i = start
+        body(r, " inside a context")
+    s.p.i = q.i
+    return len(ctx.structures)
+
+
+def _one_selection_population(s, fn):
+    """`fn(sel) [in <contexts>]` (shape_weights, rmsd): one selection, one index set per context"""
+    sets = []
+
+    def one_set(r, where):
+        ix = r.sel_or().indices()
+        if r.peek() == ("op", ","):
+            raise ScriptError(f"{s.name}: {fn} takes one selection")
+        r.take(")")
+        if ix.size == 0:
+            raise ScriptError(f"{s.name}: empty selection{where}")
+        sets.append(ix)
+
+    _per_context(s, _closing_paren(s), one_set)
+    return sets
+
+
+def _within_head(s):
+    """`within(` r | a:b `,` - p stands on `within`; the reference selection follows.  -> (rmin, rmax)"""
+    p = s.p
     p.i += 1
     p.take("(")
-    start = p.i
-    j, depth = p.i, 1
-    while depth:
-        if j >= len(p.t):
-            raise ScriptError(f"{names}: missing ')'")
-        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
-        j += 1
-    sets = []
-
-    def one_set(r, where):
-        ix = r.sel_or().indices()
-        if r.peek() == ("op", ","):
-            raise ScriptError(f"{names}: shape_weights takes one selection")
-        r.take(")")
-        if ix.size == 0:
-            raise ScriptError(f"{names}: empty selection{where}")
-        sets.append(ix)
-
-    if j < len(p.t) and p.t[j] == ("id", "in"):
-        q = _Parser(p.t, topo, env)
-        q.i = j + 1
-        ctx = q.sel_or()
-        if ctx.structures is None or not ctx.structures:
-            raise ScriptError(f"{names}: `in` needs an array of structures (residue(...), resname(...))")
-        for st in ctx.structures:
-            r = _Parser(p.t, topo, env, ctx=np.asarray(st))
-            r.i = start
-            one_set(r, " inside a context")
-        p.i = q.i
-    else:
-        one_set(p, "")
-
-    def commit():
-        ir.add_shape_weights_population(nm, sets)
-        for k, n in enumerate(nm):
-            info[n] = dict(kind="shape_weights", component=k, sets=sets)
-    return commit
+    rmin, rmax = 0.0, p.number()
+    if p.accept(":"):
+        rmin, rmax = rmax, p.number()
+        if not rmin < rmax:
+            raise ScriptError(f"{s.name}: within range needs 0 <= a < b")
+    elif not rmax > 0.0:
+        raise ScriptError(f"{s.name}: within needs a radius > 0")
+    p.take(",")
+    return float(np.float32(rmin)), float(np.float32(rmax))
 
 
-def _rmsd_statement(p, name, topo, env, ir, info):
-    """`name = rmsd(sel) [in <contexts>]` behind the opening parenthesis (the twin of the rmsd branch of vmd_script.cpp)."""
-    start = p.i
-    j, depth = p.i, 1
-    while depth:
-        if j >= len(p.t):
-            raise ScriptError(f"{name}: missing ')'")
-        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
-        j += 1
-    sets = []
-
-    def one_set(r, where):
-        ix = r.sel_or().indices()
-        if r.peek() == ("op", ","):
-            raise ScriptError(f"{name}: rmsd takes one selection")
-        r.take(")")
-        if ix.size == 0:
-            raise ScriptError(f"{name}: empty selection{where}")
-        sets.append(ix)
-
-    if j < len(p.t) and p.t[j] == ("id", "in"):
-        q = _Parser(p.t, topo, env)
-        q.i = j + 1
-        ctx = q.sel_or()
-        if ctx.structures is None or not ctx.structures:
-            raise ScriptError(f"{name}: `in` needs an array of structures (residue(...), resname(...))")
-        for st in ctx.structures:
-            r = _Parser(p.t, topo, env, ctx=np.asarray(st))
-            r.i = start
-            one_set(r, " inside a context")
-        p.i = q.i
-    else:
-        one_set(p, "")
-
-    def commit():
-        ir.add_rmsd_population(name, sets)
-        info[name] = dict(kind="rmsd", sets=sets)
-    return commit
+def _within_ref(s):
+    """... and the reference selection with the `)`"""
+    ref = s.p.sel_or().indices()
+    s.p.take(")")
+    if ref.size == 0:
+        raise ScriptError(f"{s.name}: empty selection")
+    return ref
 
 
-def _count_statement(p, name, topo, env, ir, info):
-    """`name = count(<factor> and ...)` behind the opening parenthesis (the twin of the count branch of vmd_script.cpp)."""
-    start = p.i
-    j, depth = p.i, 1
-    while depth:
-        if j >= len(p.t):
-            raise ScriptError(f"{name}: missing ')'")
-        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
-        j += 1
+def _scan_arg(s, start, stop_and=False, end=None):
+    """One pass over an argument from token `start` -> (where it ends, how many within( it holds, how many of those are factors of its
+    top-level AND, whether it has an `or` at depth 0).  end=None: the argument ends at the `,` `;` or unmatched `)` (with stop_and also
+    at an `and`) at depth 0; otherwise the scan runs to `end` whatever is on the way (count(): the whole call)."""
     n_within = n_top = depth = 0
     top_or = False
-    for q in range(start, j - 1):
-        k, v = p.t[q]
-        if k == "op":
-            depth += {"(": 1, ")": -1}.get(v, 0)
-        if (k, v) == ("id", "within") and p.t[q + 1] == ("op", "("):
+    q = start
+    while q < (len(s.t) if end is None else end):
+        k, v = s.t[q]
+        if end is None and depth == 0 and k == "op" and v in (",", ";"):
+            break
+        if (k, v) == ("op", "("):
+            depth += 1
+        if (k, v) == ("op", ")"):
+            if depth == 0:
+                break
+            depth -= 1
+        if stop_and and depth == 0 and (k, v) == ("id", "and"):
+            break
+        if s.is_within_at(q):
             n_within += 1
-            if depth == 0 and (q == start or p.t[q - 1] == ("id", "and")):
+            if depth == 0 and (q == start or s.t[q - 1] == ("id", "and")):
                 n_top += 1
         if (k, v) == ("id", "or") and depth == 0:
             top_or = True
-    if n_within == 0:
-        raise ScriptError(f"{name}: count of a static selection is a constant (left to the fallback)")
+        q += 1
+    return q, n_within, n_top, top_or
+
+
+def _single_within_and(s, scan, what):
+    """`<factor> and ... and within(<r> | <a>:<b>, <static selection>) and ...`: exactly one within() factor, at the
+    top level of the AND; the other factors are static and their AND is the list.  what: who takes it, for the message.
+    -> (index list, dict(ref=, rmin=, rmax=))"""
+    p = s.p
+    _, n_within, n_top, top_or = scan
     if n_within > 1:
-        raise ScriptError(f"{name}: count takes exactly one within() factor, found {n_within}")
+        raise ScriptError(f"{s.name}: {what} takes exactly one within() factor, found {n_within}")
     if n_top != 1 or top_or:
-        raise ScriptError(f"{name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
-    tmask = np.ones(topo.num_atoms, bool)
-    ref, rmin, rmax = None, 0.0, 0.0
+        raise ScriptError(f"{s.name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
+    tmask = np.ones(s.topo.num_atoms, bool)
+    shell = None
     while True:
         if p.peek() == ("id", "within"):
-            p.i += 1
-            p.take("(")
-            rmax = p.number()
-            if p.accept(":"):
-                rmin, rmax = rmax, p.number()
-                if not rmin < rmax:
-                    raise ScriptError(f"{name}: within range needs 0 <= a < b")
-            elif not rmax > 0.0:
-                raise ScriptError(f"{name}: within needs a radius > 0")
-            p.take(",")
-            ref = p.sel_or().indices()
-            p.take(")")
-            if ref.size == 0:
-                raise ScriptError(f"{name}: empty selection")
+            rmin, rmax = _within_head(s)
+            shell = dict(ref=_within_ref(s), rmin=rmin, rmax=rmax)
         else:
             tmask = tmask & p.sel_not().mask
         if not p.accept("and"):
             break
-    p.take(")")
-    if p.peek() == ("id", "in"):
-        raise ScriptError(f"{name}: count(...) in <contexts> is outside the subset")
-    tgt = np.nonzero(tmask)[0].astype(np.int32)
-    if tgt.size == 0:
-        raise ScriptError(f"{name}: empty selection")
-    lo, hi = float(np.float32(rmin)), float(np.float32(rmax))
+    return np.nonzero(tmask)[0].astype(np.int32), shell
 
-    def commit():
-        ir.add_within_count(name, tgt, ref, lo, hi)
-        info[name] = dict(kind="within_count", target=tgt, ref=ref, rmin=lo, rmax=hi)
-    return commit
+
+def _selection_arg(s, dynamic, what):
+    """a selection argument of rdf() / the target of sdf(): static, or with `dynamic` (the function's feature bit) possibly a single-within
+    AND -> (index list, shell or None)"""
+    scan = _scan_arg(s, s.p.i) if dynamic else None
+    if scan is not None and scan[1]:
+        return _single_within_and(s, scan, what)
+    return s.p.sel_or().indices(), None
 
 
 _EXPR_VAR = (0xAAAA, 0xCCCC, 0xF0F0, 0xFF00)
 
 
-def _expr_arg(p, name, topo):
-    """the argument of count() / the target of sdf() under shell_expr=True (the twin of expr_arg in vmd_script.cpp): an AND of static
-    factors and dynamic ones -> (index list, terms, truth), terms None for a static argument"""
-    def is_within_at(q):
-        return p.t[q] == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "(")
+class _ExprParser:
+    """the argument of count() / the target of sdf() under shell_expr=True (the twin of ExprParser in vmd_script.cpp): an AND of static
+    factors and dynamic ones - within(...), not within(...), or a parenthesised and / or / not over within() terms only"""
 
-    def extent(q, stop_and):
-        """-> (holds within(, holds a top-level or) up to the end of the argument or, with stop_and, the next `and` at depth 0"""
-        depth, has_within, top_or = 0, False, False
-        while q < len(p.t):
-            k, v = p.t[q]
-            if k == "op" and v in (",", ";") and depth == 0:
+    def __init__(self, s):
+        self.s, self.p, self.terms = s, s.p, []
+
+    def parse(self):
+        """-> (index list, terms, truth), terms None for a static argument"""
+        s, p = self.s, self.p
+        _, has_within, _, top_or = _scan_arg(s, p.i)
+        if not has_within:
+            return p.sel_or().indices(), None, 0
+        if top_or:
+            raise ScriptError(f"{s.name}: a dynamic factor under a top-level or with a static selection")
+        tmask = np.ones(s.topo.num_atoms, bool)
+        table = 0xffff
+        while True:
+            if _scan_arg(s, p.i, stop_and=True)[1]:
+                table &= self.dyn_not()
+            else:
+                tmask = tmask & p.sel_not().mask
+            if not p.accept("and"):
                 break
-            if k == "op" and v == "(":
-                depth += 1
-            if k == "op" and v == ")":
-                if depth == 0:
-                    break
-                depth -= 1
-            if stop_and and depth == 0 and (k, v) == ("id", "and"):
-                break
-            has_within = has_within or is_within_at(q)
-            top_or = top_or or ((k, v) == ("id", "or") and depth == 0)
-            q += 1
-        return has_within, top_or
+        return np.nonzero(tmask)[0].astype(np.int32), self.terms, table & ((1 << (1 << len(self.terms))) - 1)
 
-    has_within, top_or = extent(p.i, False)
-    if not has_within:
-        return p.sel_or().indices(), None, 0
-    if top_or:
-        raise ScriptError(f"{name}: a dynamic factor under a top-level or with a static selection")
-    terms = []
-
-    def within_term():
-        p.i += 1
-        p.take("(")
-        rmin, rmax = 0.0, p.number()
-        if p.accept(":"):
-            rmin, rmax = rmax, p.number()
-            if not rmin < rmax:
-                raise ScriptError(f"{name}: within range needs 0 <= a < b")
-        elif not rmax > 0.0:
-            raise ScriptError(f"{name}: within needs a radius > 0")
-        p.take(",")
-        if extent(p.i, False)[0]:
-            raise ScriptError(f"{name}: within() nested in a within() argument")
-        ref = p.sel_or().indices()
-        p.take(")")
-        if ref.size == 0:
-            raise ScriptError(f"{name}: empty selection")
-        t = dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
+    def within_term(self):
+        s, terms = self.s, self.terms
+        rmin, rmax = _within_head(s)
+        if _scan_arg(s, self.p.i)[1]:
+            raise ScriptError(f"{s.name}: within() nested in a within() argument")
+        t = dict(ref=_within_ref(s), rmin=rmin, rmax=rmax)
         for k, u in enumerate(terms):
-            if np.array_equal(u["ref"], ref) and u["rmin"] == t["rmin"] and u["rmax"] == t["rmax"]:
+            if np.array_equal(u["ref"], t["ref"]) and u["rmin"] == t["rmin"] and u["rmax"] == t["rmax"]:
                 return _EXPR_VAR[k]
         if len(terms) == L.SHELL_EXPR_MAX_TERMS:
-            raise ScriptError(f"{name}: more than four distinct within() terms")
+            raise ScriptError(f"{s.name}: more than four distinct within() terms")
         terms.append(t)
         return _EXPR_VAR[len(terms) - 1]
 
-    def dyn_not():
+    def dyn_not(self):
+        p = self.p
         if p.accept("not"):
-            return ~dyn_not() & 0xffff
-        if p.i < len(p.t) and is_within_at(p.i):
-            return within_term()
+            return ~self.dyn_not() & 0xffff
+        if self.s.is_within_at(p.i):
+            return self.within_term()
         if p.peek() == ("op", "("):
             p.take("(")
-            t = dyn_or()
+            t = self.dyn_or()
             p.take(")")
             return t
-        raise ScriptError(f"{name}: a static selection inside a parenthesised dynamic factor")
+        raise ScriptError(f"{self.s.name}: a static selection inside a parenthesised dynamic factor")
 
-    def dyn_and():
-        t = dyn_not()
-        while p.accept("and"):
-            t &= dyn_not()
+    def dyn_and(self):
+        t = self.dyn_not()
+        while self.p.accept("and"):
+            t &= self.dyn_not()
         return t
 
-    def dyn_or():
-        t = dyn_and()
-        while p.accept("or"):
-            t |= dyn_and()
+    def dyn_or(self):
+        t = self.dyn_and()
+        while self.p.accept("or"):
+            t |= self.dyn_and()
         return t
 
-    tmask = np.ones(topo.num_atoms, bool)
-    table = 0xffff
-    while True:
-        if extent(p.i, True)[0]:
-            table &= dyn_not()
-        else:
-            tmask = tmask & p.sel_not().mask
-        if not p.accept("and"):
-            break
-    return np.nonzero(tmask)[0].astype(np.int32), terms, table & ((1 << (1 << len(terms))) - 1)
+
+def _shell_tuple(sh):
+    return sh and (sh["ref"], sh["rmin"], sh["rmax"])
 
 
-def _count_expr_statement(p, name, topo, env, ir, info):
-    """`name = count(<factor> and ...)` with any number of dynamic factors (the twin of the count branch under the bit)"""
-    tgt, terms, truth = _expr_arg(p, name, topo)
-    if terms is None:
-        raise ScriptError(f"{name}: count of a static selection is a constant (left to the fallback)")
-    p.take(")")
-    if p.peek() == ("id", "in"):
-        raise ScriptError(f"{name}: count(...) in <contexts> is outside the subset")
-    if tgt.size == 0:
-        raise ScriptError(f"{name}: empty selection")
+def _rdf_range(p):
+    """rdf's third argument: `{a, b}` | `r` | `a:b` -> (rmin, rmax)"""
+    if p.accept("{"):
+        rmin = p.number(); p.take(","); rmax = p.number(); p.take("}")
+        return rmin, rmax
+    rmin, rmax = 0.0, p.number()
+    if p.accept(":"):
+        rmin, rmax = rmax, p.number()
+    return rmin, rmax
+
+
+# ---- one function per statement form: each parses up to (not including) the ';' and returns the statement's commit.  Nothing is added
+# to the IR, to info or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind ------------------
+
+def _shape_statement(s):
+    """`{n0, n1, n2} = shape_weights(sel) [in <contexts>]` from the function name on"""
+    nm = s.name.split(",")
+    if len(nm) != 3:
+        raise ScriptError(f"{s.name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not {len(nm)}")
+    s.p.i += 1
+    s.p.take("(")
+    sets = _one_selection_population(s, "shape_weights")
 
     def commit():
-        ir.add_within_count_expr(name, tgt, [(t["ref"], t["rmin"], t["rmax"]) for t in terms], truth)
-        if len(terms) == 1 and truth == 2:
-            info[name] = dict(kind="within_count", target=tgt, ref=terms[0]["ref"], rmin=terms[0]["rmin"], rmax=terms[0]["rmax"],
-                              terms=terms, truth=truth)
-        else:
-            info[name] = dict(kind="within_count_expr", target=tgt, terms=terms, truth=truth)
+        s.ir.add_shape_weights_population(nm, sets)
+        for k, n in enumerate(nm):
+            s.info[n] = dict(kind="shape_weights", component=k, sets=sets)
     return commit
 
 
-def _dyn_arg(p, name, topo, fn="rdf"):
-    """one selection argument of rdf() under shell_rdf=True / the target of sdf() under shell_sdf=True (the twin of dyn_arg in
-    vmd_script.cpp) -> (index list, shell or None)"""
-    start = p.i
-    n_within = n_top = depth = 0
-    top_or = False
-    for q in range(start, len(p.t)):
-        k, v = p.t[q]
-        if k == "op" and v in (",", ";") and depth == 0:
-            break
-        if k == "op" and v == "(":
-            depth += 1
-        if k == "op" and v == ")":
-            if depth == 0:
-                break
-            depth -= 1
-        if (k, v) == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "("):
-            n_within += 1
-            if depth == 0 and (q == start or p.t[q - 1] == ("id", "and")):
-                n_top += 1
-        if (k, v) == ("id", "or") and depth == 0:
-            top_or = True
-    if n_within == 0:
-        return p.sel_or().indices(), None
-    if n_within > 1:
-        raise ScriptError(f"{name}: an {fn} argument takes exactly one within() factor, found {n_within}")
-    if n_top != 1 or top_or:
-        raise ScriptError(f"{name}: within() must be a factor of the top-level AND (not under not / or / parentheses)")
-    tmask = np.ones(topo.num_atoms, bool)
-    ref, rmin, rmax = None, 0.0, 0.0
-    while True:
-        if p.peek() == ("id", "within"):
-            p.i += 1
-            p.take("(")
-            rmax = p.number()
-            if p.accept(":"):
-                rmin, rmax = rmax, p.number()
-                if not rmin < rmax:
-                    raise ScriptError(f"{name}: within range needs 0 <= a < b")
-            elif not rmax > 0.0:
-                raise ScriptError(f"{name}: within needs a radius > 0")
-            p.take(",")
-            ref = p.sel_or().indices()
-            p.take(")")
-            if ref.size == 0:
-                raise ScriptError(f"{name}: empty selection")
+def _rmsd_statement(s):
+    """`name = rmsd(sel) [in <contexts>]`"""
+    sets = _one_selection_population(s, "rmsd")
+
+    def commit():
+        s.ir.add_rmsd_population(s.name, sets)
+        s.info[s.name] = dict(kind="rmsd", sets=sets)
+    return commit
+
+
+def _no_count_contexts(s):
+    s.p.take(")")
+    if s.p.peek() == ("id", "in"):
+        raise ScriptError(f"{s.name}: count(...) in <contexts> is outside the subset")
+
+
+def _count_statement(s):
+    """`name = count(<factor> and ...)` with exactly one within() factor.  The scan covers the whole call, commas included:
+    a second argument is met by the parse, not by the scan."""
+    scan = _scan_arg(s, s.p.i, end=_closing_paren(s) - 1)
+    if scan[1] == 0:
+        raise ScriptError(f"{s.name}: count of a static selection is a constant (left to the fallback)")
+    tgt, sh = _single_within_and(s, scan, "count")
+    _no_count_contexts(s)
+    if tgt.size == 0:
+        raise ScriptError(f"{s.name}: empty selection")
+
+    def commit():
+        s.ir.add_within_count(s.name, tgt, sh["ref"], sh["rmin"], sh["rmax"])
+        s.info[s.name] = dict(kind="within_count", target=tgt, **sh)
+    return commit
+
+
+def _count_expr_statement(s):
+    """the same with any number of dynamic factors"""
+    tgt, terms, truth = _ExprParser(s).parse()
+    if terms is None:
+        raise ScriptError(f"{s.name}: count of a static selection is a constant (left to the fallback)")
+    _no_count_contexts(s)
+    if tgt.size == 0:
+        raise ScriptError(f"{s.name}: empty selection")
+
+    def commit():
+        s.ir.add_within_count_expr(s.name, tgt, [_shell_tuple(t) for t in terms], truth)
+        if len(terms) == 1 and truth == 2:
+            s.info[s.name] = dict(kind="within_count", target=tgt, **terms[0], terms=terms, truth=truth)
         else:
-            tmask = tmask & p.sel_not().mask
-        if not p.accept("and"):
-            break
-    return np.nonzero(tmask)[0].astype(np.int32), dict(ref=ref, rmin=float(np.float32(rmin)), rmax=float(np.float32(rmax)))
+            s.info[s.name] = dict(kind="within_count_expr", target=tgt, terms=terms, truth=truth)
+    return commit
 
 
-def _statement(p, name, topo, env, ir, info, angles=False, rmsd=False, within=False, shell_rdf=False, shell_sdf=False, shell_expr=False):
-    """parses the right-hand side of `name = ...` up to (not including) the ';'.  Returns (commit, is_property): nothing is added to the
-    IR or to the identifiers before commit() runs, so a statement that fails half way leaves nothing behind."""
-    k, v = p.peek()
-    if not (k == "id" and (v in _FUNCS or (angles and v in _GEOM_NARGS) or (rmsd and v == "rmsd") or (within and v == "count"))):
-        sel = p.sel_or()
-        return (lambda: env.__setitem__(name, sel)), False
-    p.i += 1
-    p.take("(")
-    if v == "rmsd":
-        return _rmsd_statement(p, name, topo, env, ir, info), True
-    if v == "count" and shell_expr:
-        return _count_expr_statement(p, name, topo, env, ir, info), True
-    if v == "count":
-        return _count_statement(p, name, topo, env, ir, info), True
-    if v == "rdf" and shell_rdf:
-        a, sha = _dyn_arg(p, name, topo); p.take(",")
-        b, shb = _dyn_arg(p, name, topo); p.take(",")
-        if p.accept("{"):
-            rmin = p.number(); p.take(","); rmax = p.number(); p.take("}")
+def _rdf_statement(s):
+    """`name = rdf(sel, sel, <range>)` - with shell_rdf=True either selection may be a single-within AND"""
+    p, shells = s.p, s.has(FEATURE_SHELL_RDF)
+    a, sha = _selection_arg(s, shells, "an rdf argument"); p.take(",")
+    b, shb = _selection_arg(s, shells, "an rdf argument"); p.take(",")
+    rmin, rmax = _rdf_range(p)
+    p.take(")")
+    if a.size == 0 or b.size == 0:
+        raise ScriptError(f"{s.name}: empty selection")
+
+    def commit():
+        shells = {}
+        if sha is None and shb is None:
+            s.ir.add_rdf(s.name, a, b, (rmin, rmax))
         else:
-            rmin, rmax = 0.0, p.number()
-            if p.accept(":"):
-                rmin, rmax = rmax, p.number()
-        p.take(")")
-        if a.size == 0 or b.size == 0:
-            raise ScriptError(f"{name}: empty selection")
+            s.ir.add_rdf_shell(s.name, a, b, (rmin, rmax), ref_shell=_shell_tuple(sha), target_shell=_shell_tuple(shb))
+            shells = dict(ref_shell=sha, target_shell=shb)
+        s.info[s.name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax, **shells)
+    return commit
 
-        def commit():
-            if sha is None and shb is None:
-                ir.add_rdf(name, a, b, (rmin, rmax))
-                info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax)
-                return
-            ir.add_rdf_shell(name, a, b, (rmin, rmax), ref_shell=sha and (sha["ref"], sha["rmin"], sha["rmax"]),
-                             target_shell=shb and (shb["ref"], shb["rmin"], shb["rmax"]))
-            info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax, ref_shell=sha, target_shell=shb)
-        return commit, True
-    if v == "rdf":
-        ref = p.sel_or(); p.take(",")
-        tgt = p.sel_or(); p.take(",")
-        if p.accept("{"):
-            rmin = p.number(); p.take(","); rmax = p.number(); p.take("}")
+
+def _sdf_statement(s):
+    """`name = sdf(structures, sel, cutoff)` - with shell_sdf=True the target may be a single-within AND, with shell_expr=True
+    on top of it an expression over within() terms.  The structures stay static: the alignment needs fixed atoms."""
+    p, shells = s.p, s.has(FEATURE_SHELL_SDF)
+    if shells and _scan_arg(s, p.i)[1]:
+        raise ScriptError(f"{s.name}: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)")
+    ref = p.sel_or(); p.take(",")
+    terms, truth = None, 0
+    if shells and s.has(FEATURE_SHELL_EXPR):
+        tg, terms, truth = _ExprParser(s).parse()
+        sh = terms[0] if terms is not None and len(terms) == 1 and truth == 2 else None
+    else:
+        tg, sh = _selection_arg(s, shells, "an sdf argument")
+    p.take(",")
+    cutoff = p.number()
+    p.take(")")
+    structs = ref.structures if ref.structures is not None else [ref.indices()]
+    sizes = {len(x) for x in structs}
+    if len(sizes) != 1 or 0 in sizes:
+        raise ScriptError(f"{s.name}: sdf reference structures must be non-empty and of equal size, got sizes {sorted(sizes)}")
+    st = np.stack([np.asarray(x, np.int32) for x in structs])
+    if (sh is not None or terms is not None) and tg.size == 0:
+        raise ScriptError(f"{s.name}: empty selection")
+
+    def commit():
+        dynamic = {}
+        if terms is not None:
+            s.ir.add_sdf_shell_expr(s.name, st, tg, cutoff, [_shell_tuple(t) for t in terms], truth)
+            dynamic = dict(terms=terms, truth=truth)
+        elif sh is None:
+            s.ir.add_sdf(s.name, st, tg, cutoff)
         else:
-            rmin, rmax = 0.0, p.number()
-            if p.accept(":"):
-                rmin, rmax = rmax, p.number()
-        p.take(")")
-        a, b = ref.indices(), tgt.indices()
-        if a.size == 0 or b.size == 0:
-            raise ScriptError(f"{name}: empty selection")
+            s.ir.add_sdf_shell(s.name, st, tg, cutoff, target_shell=_shell_tuple(sh))
+        if sh is not None:
+            dynamic["target_shell"] = sh
+        s.info[s.name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff, **dynamic)
+    return commit
 
-        def commit():
-            ir.add_rdf(name, a, b, (rmin, rmax))
-            info[name] = dict(kind="rdf", ref=a, target=b, rmin=rmin, rmax=rmax)
-        return commit, True
-    if v == "sdf" and shell_sdf:
-        depth = 0
-        for q in range(p.i, len(p.t)):          # DESIGN 1.8: the structures stay static - the alignment needs fixed atoms
-            k_, v_ = p.t[q]
-            if k_ == "op" and v_ in (",", ";") and depth == 0:
-                break
-            if k_ == "op" and v_ == "(":
-                depth += 1
-            if k_ == "op" and v_ == ")":
-                if depth == 0:
-                    break
-                depth -= 1
-            if (k_, v_) == ("id", "within") and q + 1 < len(p.t) and p.t[q + 1] == ("op", "("):
-                raise ScriptError(f"{name}: within() in the structures argument of sdf() is not supported (the alignment needs fixed atoms)")
-        ref = p.sel_or(); p.take(",")
-        terms, truth = None, 0
-        if shell_expr:
-            tg, terms, truth = _expr_arg(p, name, topo)
-            sh = terms[0] if terms is not None and len(terms) == 1 and truth == 2 else None
-        else:
-            tg, sh = _dyn_arg(p, name, topo, "sdf")
-        p.take(",")
-        cutoff = p.number()
-        p.take(")")
-        structs = ref.structures if ref.structures is not None else [ref.indices()]
-        sizes = {len(s) for s in structs}
-        if len(sizes) != 1 or 0 in sizes:
-            raise ScriptError(f"{name}: sdf reference structures must be non-empty and of equal size, got sizes {sorted(sizes)}")
-        st = np.stack([np.asarray(s, np.int32) for s in structs])
-        if (sh is not None or terms is not None) and tg.size == 0:
-            raise ScriptError(f"{name}: empty selection")
 
-        def commit():
-            if terms is not None:
-                ir.add_sdf_shell_expr(name, st, tg, cutoff, [(t["ref"], t["rmin"], t["rmax"]) for t in terms], truth)
-                info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff, terms=terms, truth=truth)
-                if sh is not None:
-                    info[name]["target_shell"] = sh
-                return
-            if sh is None:
-                ir.add_sdf(name, st, tg, cutoff)
-                info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff)
-                return
-            ir.add_sdf_shell(name, st, tg, cutoff, target_shell=(sh["ref"], sh["rmin"], sh["rmax"]))
-            info[name] = dict(kind="sdf", structures=st, target=tg, cutoff=cutoff, target_shell=sh)
-        return commit, True
-    if v == "sdf":
-        ref = p.sel_or(); p.take(",")
-        tgt = p.sel_or(); p.take(",")
-        cutoff = p.number()
-        p.take(")")
-        structs = ref.structures if ref.structures is not None else [ref.indices()]
-        sizes = {len(s) for s in structs}
-        if len(sizes) != 1 or 0 in sizes:
-            raise ScriptError(f"{name}: sdf reference structures must be non-empty and of equal size, got sizes {sorted(sizes)}")
-        st = np.stack([np.asarray(s, np.int32) for s in structs])
+def _geometry_statement(s, fn):
+    """`name = distance*(a, b) | angle(a, b, c) | dihedral(a, b, c, d) [in <contexts>]` (DESIGN S6b): fn is the function's name"""
+    nargs = _GEOM_NARGS.get(fn, 2)
+    sets = [[] for _ in range(nargs)]
 
-        def commit():
-            ir.add_sdf(name, st, tgt.indices(), cutoff)
-            info[name] = dict(kind="sdf", structures=st, target=tgt.indices(), cutoff=cutoff)
-        return commit, True
-    # the arguments may be followed by `in <contexts>`: find the closing parenthesis first
-    start, depth, j = p.i, 1, p.i
-    while depth:
-        if j >= len(p.t):
-            raise ScriptError(f"{name}: missing ')'")
-        depth += {"(": 1, ")": -1}.get(p.t[j][1], 0) if p.t[j][0] == "op" else 0
-        j += 1
-    nargs = _GEOM_NARGS.get(v, 2)       # distance*: two argument sets; angle: three; dihedral: four (DESIGN S6b)
-    if j < len(p.t) and p.t[j] == ("id", "in"):
-        q = _Parser(p.t, topo, env)
-        q.i = j + 1
-        ctx = q.sel_or()
-        if ctx.structures is None or not ctx.structures:
-            raise ScriptError(f"{name}: `in` needs an array of structures (residue(...), resname(...))")
-        sets = [[] for _ in range(nargs)]
-        for st in ctx.structures:
-            r = _Parser(p.t, topo, env, ctx=np.asarray(st))
-            r.i = start
-            idx = []
-            for n in range(nargs):
-                if n:
-                    r.take(",")
-                idx.append(r.sel_or().indices())
-            r.take(")")
-            if any(x.size == 0 for x in idx):
-                raise ScriptError(f"{name}: empty selection inside a context")
-            for n in range(nargs):
-                sets[n].append(idx[n])
-        p.i = q.i
-        if nargs > 2:
-            def commit():
-                (ir.add_angle_population if nargs == 3 else ir.add_dihedral_population)(name, *sets)
-                info[name] = dict(kind=v, sets=sets)
-            return commit, True
-        a_sets, b_sets = sets
-
-        def commit():
-            ir.add_distance_population(name, a_sets, b_sets, _DIST_KIND[v])
-            info[name] = dict(kind=v, a_sets=a_sets, b_sets=b_sets)
-        return commit, True
-    if nargs > 2:
+    def one_context(r, where):
         idx = []
         for n in range(nargs):
             if n:
-                p.take(",")
-            idx.append(p.sel_or().indices())
-        p.take(")")
+                r.take(",")
+            idx.append(r.sel_or().indices())
+        r.take(")")
+        if where and any(x.size == 0 for x in idx):
+            raise ScriptError(f"{s.name}: empty selection{where}")
+        for n in range(nargs):
+            sets[n].append(idx[n])
 
-        def commit():
-            (ir.add_angle if nargs == 3 else ir.add_dihedral)(name, *idx)
-            info[name] = dict(kind=v, sets=idx)
-        return commit, True
-    a = p.sel_or(); p.take(",")
-    b = p.sel_or()
-    p.take(")")
+    populations = _per_context(s, _closing_paren(s), one_context)
+    ir, name = s.ir, s.name
 
     def commit():
-        ir.add_distance(name, a.indices(), b.indices(), _DIST_KIND[v])
-        info[name] = dict(kind=v, a=a.indices(), b=b.indices())
-    return commit, True
+        if populations and nargs > 2:
+            (ir.add_angle_population if nargs == 3 else ir.add_dihedral_population)(name, *sets)
+            s.info[name] = dict(kind=fn, sets=sets)
+        elif populations:
+            ir.add_distance_population(name, sets[0], sets[1], _DIST_KIND[fn])
+            s.info[name] = dict(kind=fn, a_sets=sets[0], b_sets=sets[1])
+        elif nargs > 2:
+            idx = [x[0] for x in sets]
+            (ir.add_angle if nargs == 3 else ir.add_dihedral)(name, *idx)
+            s.info[name] = dict(kind=fn, sets=idx)
+        else:
+            ir.add_distance(name, sets[0][0], sets[1][0], _DIST_KIND[fn])
+            s.info[name] = dict(kind=fn, a=sets[0][0], b=sets[1][0])
+    return commit
+
+
+def _statement(s):
+    """One statement from its first token up to (not including) its ';' (the twin of statement() in vmd_script.cpp): the left-hand side
+    into s.name, then the form's function.  Returns the statement's commit."""
+    p = s.p
+    if p.peek() == ("op", "{"):
+        p.take("{")
+        s.name = p.take(kind="id")
+        while p.accept(","):
+            s.name += "," + p.take(kind="id")
+        p.take("}")
+        p.take("=")
+        k, v = p.peek()
+        if s.has(FEATURE_RMSD) and k == "id" and v == "rmsd":
+            raise ScriptError(f"{s.name}: rmsd defines one property, not a tuple")
+        if not (s.has(FEATURE_SHAPE) and k == "id" and v == "shape_weights"):
+            raise ScriptError(f"unsupported {'function' if k == 'id' else 'expression'} {v!r} (outside the rdf / sdf / distance path)")
+        s.is_property = True
+        return _shape_statement(s)
+    name = s.name = p.take(kind="id")
+    p.take("=")
+    k, v = p.peek()
+    if s.has(FEATURE_SHAPE) and (k, v) == ("id", "shape_weights"):
+        raise ScriptError(f"{name}: shape_weights defines three properties, {{linear, planar, isotropic}}, not 1")
+    if not (k == "id" and (v in _FUNCS or (s.has(FEATURE_ANGLES) and v in _GEOM_NARGS) or (s.has(FEATURE_RMSD) and v == "rmsd") or
+                           (s.has(FEATURE_WITHIN) and v == "count"))):
+        sel = p.sel_or()
+        return lambda: s.env.__setitem__(name, sel)
+    s.is_property = True
+    p.i += 1
+    p.take("(")
+    if v == "rdf":
+        return _rdf_statement(s)
+    if v == "sdf":
+        return _sdf_statement(s)
+    if v == "rmsd":
+        return _rmsd_statement(s)
+    if v == "count":
+        return _count_expr_statement(s) if s.has(FEATURE_SHELL_EXPR) else _count_statement(s)
+    return _geometry_statement(s, v)
 
 
 def compile_script_native(text, topo, lib=None, partial=False, angles=False, shape=False, rmsd=False, within=False, shell_rdf=False,
@@ -905,9 +847,7 @@ def compile_script_native(text, topo, lib=None, partial=False, angles=False, sha
     import ctypes as C
     ir = ScriptIR(lib)
     n = topo.num_atoms
-    features = (FEATURE_ANGLES if angles else 0) | (FEATURE_SHAPE if shape else 0) | (FEATURE_RMSD if rmsd else 0) | \
-        (FEATURE_WITHIN if within else 0) | (FEATURE_SHELL_RDF if shell_rdf else 0) | (FEATURE_SHELL_SDF if shell_sdf else 0) | \
-        (FEATURE_SHELL_EXPR if shell_expr else 0)
+    features = _feature_mask(angles, shape, rmsd, within, shell_rdf, shell_sdf, shell_expr)
 
     def strings(arr):
         return (C.c_char_p * n)(*[str(v).encode() for v in arr])
