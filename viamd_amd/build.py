@@ -26,6 +26,9 @@ OUT = os.path.join(_HERE, "libviamd_amd.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-value", "-Wno-pass-failed",
          "-Wno-inline-asm"]      # vmd_pop_hot0 names m0 (the base of ds_read_addtid_b32) as clobbered: "reserved register", by design
+# the evaluator dispatches on a property's Form through switches without a default (csrc/vmd_eval_internal.h): a form one of them forgets
+# is an error, not a fall-through
+EVAL_FLAGS = ["-Werror=switch"]
 
 
 def hipcc():
@@ -58,7 +61,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_header):
             return obj
-        cmd = [hipcc()] + cflags + ["-I", os.path.join(ROOT, "include"), "-x", "hip", "-c", src, "-o", obj]
+        cmd = [hipcc()] + cflags + (EVAL_FLAGS if os.path.basename(src) in EVAL_SOURCES else []) + \
+              ["-I", os.path.join(ROOT, "include"), "-x", "hip", "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -142,7 +142,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
         per_frame += 2 * (num_atoms + 64);
     }
     for (size_t i = 0; i < e->sels.size(); ++i) if (used[i]) per_frame += 40 * e->sels[i]->idx.size();
-    for (auto& p : e->props) per_frame += p->prop.kind == PROP_SDF ? 64 * p->prop.K : (p->prop.kind == PROP_DIST ? 4 * p->dim1 : 0);
+    for (auto& p : e->props) per_frame += p->prop.form == Form::SDF ? 64 * p->prop.K : (p->prop.temporal() ? 4 * p->dim1 : 0);
     // 288 GB of HBM: a 16 GB scratch budget holds the 1 000 frames of the 1M-atom RDF (333k selected atoms) in ONE batch
     // (every batch boundary costs ~1 ms of host round trips against ~37 ms of kernels per 500 frames)
     size_t B = (size_t)(16ull << 30) / std::max<size_t>(per_frame, 1);
@@ -207,11 +207,11 @@ bool reuse_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t beg, siz
                 const PropState* q = src->props[i].get();
                 if (p->ncounts) {
                     KRN_OK(vmd_hip_add_u64(e->stream, p->d_counts.p, q->d_blocks.p + blk * p->ncounts, p->ncounts));
-                    if (p->prop.kind == PROP_RDF)
+                    if (p->prop.cls() == ResultClass::DISTRIBUTION)
                         for (size_t k = 0; k < p->ncounts; ++k) p->weights64[k] += q->block_weights64[blk * p->ncounts + k];
                 } else {
                     memcpy(&p->values[f * p->dim1], block_rows(src, q, blk) + f * p->dim1, (bend - f) * p->dim1 * sizeof(float));
-                    if (p->prop.is_rama()) p->table_stale = true;     // the device table follows before the next filtered map
+                    if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // the device table follows before the next filtered map
                 }
                 p->dirty = true;
             }
@@ -228,7 +228,7 @@ bool reuse_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t beg, siz
         e->frames_done += reused;
         e->frames_reused += reused;
         { HostTimer host_timer("host_refresh");
-          for (auto& p : e->props) if (p->prop.kind == PROP_RDF) { if (!refresh_distribution(e, p.get())) return false; } }
+          for (auto& p : e->props) if (p->prop.cls() == ResultClass::DISTRIBUTION) { if (!refresh_distribution(e, p.get())) return false; } }
     }
     return true;
 }
@@ -249,15 +249,11 @@ bool refresh_views_locked(vmd_script_eval_t* e) {
     HIP_OK(hipSetDevice(e->device));
     for (auto& p : e->props) {
         if (!p->dirty) continue;
-        if (p->prop.kind == PROP_RDF) { if (!refresh_distribution(e, p.get())) return false; }
-        else if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) {
-            // vmd_eval_defer_volume_views: a rank of a multi-GPU evaluation does not materialise ITS partial volume's float view (8.4 MB
-            // over PCIe after every range) - the merge re-derives the view of the merged counts (vmd_eval_reduce -> vmd_eval_finalize); the
-            // volume stays dirty until then
-            if (e->defer_volume_views.load(std::memory_order_relaxed)) continue;
-            if (!refresh_volume(e, p.get())) return false;
-        }
-        else refresh_temporal_stats(e, p.get());
+        // vmd_eval_defer_volume_views: a rank of a multi-GPU evaluation does not materialise ITS partial volume's float view (8.4 MB
+        // over PCIe after every range) - the merge re-derives the view of the merged counts (vmd_eval_reduce -> vmd_eval_finalize); the
+        // volume stays dirty until then
+        if (p->prop.counts_view() && e->defer_volume_views.load(std::memory_order_relaxed)) continue;
+        if (!refresh_view(e, p.get())) return false;
     }
     e->views_at = std::chrono::steady_clock::now();
     return true;

@@ -67,7 +67,7 @@ bool ra_engage(vmd_script_eval_t* e, vmd_trajectory_i* traj) {
                 ra.disabled = true;
                 return true;
             }
-            if (p->prop.kind == PROP_RDF) p->block_weights64.assign(nblocks * p->ncounts, 0.0);
+            if (p->prop.cls() == ResultClass::DISTRIBUTION) p->block_weights64.assign(nblocks * p->ncounts, 0.0);
         }
         e->block_ready.reset(new std::atomic<uint8_t>[nblocks]);
         for (size_t b = 0; b < nblocks; ++b) e->block_ready[b] = 0;
@@ -115,12 +115,12 @@ bool ra_adopt_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t b0, s
             if (p->ncounts) {
                 HIP_OK(hipMemcpyAsync(p->d_blocks.p + b * p->ncounts, q->d_blocks.p + b * p->ncounts, p->ncounts * sizeof(uint64_t),
                         hipMemcpyDeviceToDevice, e->stream));
-                if (p->prop.kind == PROP_RDF) memcpy(&p->block_weights64[b * p->ncounts], &q->block_weights64[b * p->ncounts], p->ncounts
+                if (p->prop.cls() == ResultClass::DISTRIBUTION) memcpy(&p->block_weights64[b * p->ncounts], &q->block_weights64[b * p->ncounts], p->ncounts
                         * sizeof(double));
             } else {
                 if (p->ahead_values.size() != p->values.size()) p->ahead_values.assign(p->values.size(), 0.0f);
                 memcpy(&p->ahead_values[f0 * p->dim1], block_rows(src, q, b) + f0 * p->dim1, (f1 - f0) * p->dim1 * sizeof(float));
-                if (p->prop.is_rama()) p->table_stale = true;     // adopted rows reach the device table once committed
+                if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // adopted rows reach the device table once committed
             }
         }
         e->block_ready[b] = BLOCK_ROWS_AHEAD;           // (the rows went into the side buffer above)
@@ -140,11 +140,11 @@ bool ra_commit_block(vmd_script_eval_t* e, size_t blk) {
     for (auto& p : e->props) {
         if (p->ncounts) {
             KRN_OK(vmd_hip_add_u64(e->stream, p->d_counts.p, p->d_blocks.p + blk * p->ncounts, p->ncounts));
-            if (p->prop.kind == PROP_RDF) for (size_t k = 0; k < p->ncounts; ++k) p->weights64[k] += p->block_weights64[blk * p->ncounts
+            if (p->prop.cls() == ResultClass::DISTRIBUTION) for (size_t k = 0; k < p->ncounts; ++k) p->weights64[k] += p->block_weights64[blk * p->ncounts
                     + k];
         } else if (p->ahead_values.size() == p->values.size()) {
             memcpy(&p->values[f0 * p->dim1], &p->ahead_values[f0 * p->dim1], (f1 - f0) * p->dim1 * sizeof(float));
-            if (p->prop.is_rama()) p->table_stale = true;     // (rows adopted from a source exist on the host only)
+            if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // (rows adopted from a source exist on the host only)
         }
         p->dirty = true;
     }

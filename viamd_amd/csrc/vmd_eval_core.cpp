@@ -85,7 +85,7 @@ void build_rdf_plan(vmd_script_eval_t* e) {
     e->shells.clear();
     for (size_t i = 0; i < e->props.size(); ++i) {
         const Property& d = e->props[i]->prop;
-        if (d.kind != PROP_RDF) continue;
+        if (d.cls() != ResultClass::DISTRIBUTION) continue;
         RdfGroup* g = nullptr;
         for (auto& q : e->rdf_groups) if (memcmp(&q.rmin, &d.rmin, sizeof(float)) == 0 && memcmp(&q.rmax, &d.rmax, sizeof(float)) == 0) g =
                 &q;
@@ -99,7 +99,7 @@ void build_rdf_plan(vmd_script_eval_t* e) {
     // every property keeps its own sets as selections (index lists only; sorted copies exist for the selections passes use):
     // the all-pairs kernel, which takes over when a batch cannot use the grid, works per property
     for (auto& p : e->props) {
-        if (p->prop.kind != PROP_RDF) continue;
+        if (p->prop.cls() != ResultClass::DISTRIBUTION) continue;
         if (p->prop.is_shell_rdf()) {
             for (int k = 0; k < 2; ++k) {
                 const Property::ShellArg& h = p->prop.shell[k];
@@ -195,19 +195,21 @@ void build_rdf_plan(vmd_script_eval_t* e) {
     }
 }
 
+// T minus R, in T's order (D-WITHIN-SELF / D-EXPR-SELF flipped)
+static std::vector<int32_t> minus(std::vector<int32_t> t, std::vector<int32_t> ref) {
+    std::sort(ref.begin(), ref.end());
+    t.erase(std::remove_if(t.begin(), t.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), t.end());
+    return t;
+}
+
 // within counts: the target and reference sets become interned selections - shared with the RDF properties of the script -
 // so that a cell-sorted copy one of them built on the same grid in a batch is not built again.  D-WITHIN-SELF flipped: T minus R, formed here
 void build_within_plan(vmd_script_eval_t* e) {
     e->within_props.clear();
     for (size_t i = 0; i < e->props.size(); ++i) {
         PropState* p = e->props[i].get();
-        if (!p->prop.is_within()) continue;
-        std::vector<int32_t> tgt = p->prop.a;
-        if (e->spec.within_exclude_ref) {
-            std::vector<int32_t> ref = p->prop.b;
-            std::sort(ref.begin(), ref.end());
-            tgt.erase(std::remove_if(tgt.begin(), tgt.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), tgt.end());
-        }
+        if (p->prop.form != Form::WITHIN) continue;
+        const std::vector<int32_t> tgt = e->spec.within_exclude_ref ? minus(p->prop.a, p->prop.b) : p->prop.a;
         p->within_empty = tgt.empty();
         p->sel_a = p->within_empty ? -1 : intern_selection(e, tgt);
         p->sel_b = intern_selection(e, p->prop.b);
@@ -239,7 +241,7 @@ void build_expr_plan(vmd_script_eval_t* e) {
     for (size_t i = 0; i < e->props.size(); ++i) {
         PropState* p = e->props[i].get();
         const Property& d = p->prop;
-        if (!d.is_within_expr() && !d.is_expr_sdf()) continue;
+        if (d.form != Form::WITHIN_EXPR && !d.is_expr_sdf()) continue;
         const std::vector<int32_t>& T = d.is_expr_sdf() ? d.b : d.a;
         auto x = std::make_unique<ShellExpr>();
         x->sel_t = intern_selection(e, T);
@@ -250,9 +252,7 @@ void build_expr_plan(vmd_script_eval_t* e) {
             tm.rmin = t.rmin; tm.rmax = t.rmax;
             tm.sel_tt = x->sel_t;
             if (e->spec.within_exclude_ref) {
-                std::vector<int32_t> ref = t.ref, tt = T;
-                std::sort(ref.begin(), ref.end());
-                tt.erase(std::remove_if(tt.begin(), tt.end(), [&](int32_t a) { return std::binary_search(ref.begin(), ref.end(), a); }), tt.end());
+                const std::vector<int32_t> tt = minus(T, t.ref);
                 tm.sel_tt = tt.empty() ? -1 : intern_selection(e, tt);
             }
             x->terms.push_back(tm);
@@ -308,8 +308,17 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         st->prop = p;
         memset(&st->data, 0, sizeof(st->data));
         memset(&st->aggregate, 0, sizeof(st->aggregate));
-        switch (p.kind) {
-        case PROP_RDF:
+        const FormFacts& f = p.facts();
+        st->data.unit_str[0] = f.unit[0];
+        st->data.unit_str[1] = e->spec.angle_radians && f.unit_y_radians ? f.unit_y_radians : f.unit[1];     // DESIGN S6b, D-ANGLE-UNIT
+        bool aggregate = true;      // a temporal population has one
+        if (p.temporal()) st->dist_P = p.aoff.size() - 1;     // the contexts (a table: its segments, below)
+        // the 8 + 17 MB host views of a volume (a map: 4 + 8 MB) are pinned: their D2H refresh runs at PCIe speed
+        auto pinned_views = [&](size_t n) { st->ncounts = n; st->values.assign(n, 0.0f, true); st->counts.assign(n, 0, true);
+                                            st->pinned = st->values.pinned && st->counts.pinned; };
+        auto largest_set = [&]() { int n = 0; for (size_t c = 0; c + 1 < p.aoff.size(); ++c) n = std::max(n, (int)(p.aoff[c + 1] - p.aoff[c])); return n; };
+        switch (p.form) {
+        case Form::RDF:
             st->ncounts = VMD_RDF_NUM_BINS;
             st->values.assign(st->ncounts, 0.0f); st->weights.assign(st->ncounts, 0.0f);
             st->counts.assign(st->ncounts, 0); st->weights64.assign(st->ncounts, 0.0);
@@ -317,57 +326,37 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             st->data.weights = st->weights.data();
             st->data.weights64 = st->weights64.data();
             st->data.min_range[0] = p.rmin; st->data.max_range[0] = p.rmax;
-            st->data.unit_str[0] = "\xC3\x85"; st->data.unit_str[1] = "";
             st->same_set = (p.a == p.b);         // selections are interned by build_rdf_plan (own sets, or the classes they split into)
             break;
-        case PROP_SDF:
-            st->ncounts = (size_t)VMD_VOLUME_DIM * VMD_VOLUME_DIM * VMD_VOLUME_DIM;
-            // the 8 + 17 MB host views of a volume are pinned: their D2H refresh runs at PCIe speed
-            st->values.assign(st->ncounts, 0.0f, true);
-            st->counts.assign(st->ncounts, 0, true);
-            st->pinned = st->values.pinned && st->counts.pinned;
+        case Form::SDF:
+            pinned_views((size_t)VMD_VOLUME_DIM * VMD_VOLUME_DIM * VMD_VOLUME_DIM);
             st->data.dim[0] = 1; st->data.dim[1] = st->data.dim[2] = st->data.dim[3] = VMD_VOLUME_DIM;
             st->data.min_range[0] = -p.rmax; st->data.max_range[0] = p.rmax;
-            st->data.unit_str[0] = ""; st->data.unit_str[1] = "";
             break;
-        case PROP_RAMA:
+        case Form::RAMA_MAP:
             // the class map behind the angle table; pinned views like a volume's (4 + 8 MB)
-            st->ncounts = (size_t)VMD_RAMA_DIM * VMD_RAMA_DIM * VMD_RAMA_CLASSES;
-            st->values.assign(st->ncounts, 0.0f, true);
-            st->counts.assign(st->ncounts, 0, true);
-            st->pinned = st->values.pinned && st->counts.pinned;
+            pinned_views((size_t)VMD_RAMA_DIM * VMD_RAMA_DIM * VMD_RAMA_CLASSES);
             st->data.dim[0] = 1; st->data.dim[1] = VMD_RAMA_CLASSES; st->data.dim[2] = st->data.dim[3] = VMD_RAMA_DIM;
             st->data.min_range[0] = -(float)M_PI; st->data.max_range[0] = (float)M_PI;
-            st->data.unit_str[0] = "rad"; st->data.unit_str[1] = "";
             break;
-        case PROP_DIST:
-            if (p.is_rama()) {
-                // {phi, psi} per segment, radians whatever spec_angle_radians says; no aggregate (VIAMD's table has none)
-                st->dist_P = p.a.size(); st->dist_per = 2;
-                st->dim1 = 2 * p.a.size();
-                st->values.assign(num_frames * st->dim1, 0.0f);
-                st->data.dim[0] = (int32_t)num_frames; st->data.dim[1] = (int32_t)st->dim1;
-                st->data.unit_str[0] = ""; st->data.unit_str[1] = "rad";
-                if (!st->d_table.ensure(num_frames * st->dim1)) return nullptr;
-                if (hipMemsetAsync(st->d_table.p, 0, num_frames * st->dim1 * sizeof(float), e->stream) != hipSuccess) {
-                    vmd_fail("hipMemset failed"); return nullptr; }
-                break;
-            }
-            st->dist_P = p.aoff.size() - 1;
-            st->dist_per = p.dist_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1;
+        case Form::RAMA_TABLE:
+            // {phi, psi} per segment; no aggregate (VIAMD's table has none); the whole table lives on the device
+            st->dist_P = p.a.size(); st->dist_per = 2;
+            aggregate = false;
+            if (!st->d_table.ensure(num_frames * 2 * p.a.size())) return nullptr;
+            if (hipMemsetAsync(st->d_table.p, 0, num_frames * 2 * p.a.size() * sizeof(float), e->stream) != hipSuccess) {
+                vmd_fail("hipMemset failed"); return nullptr; }
+            break;
+        case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
+        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: break;
+        case Form::SHAPE: st->shape_max_set = largest_set(); break;
+        case Form::RMSD: st->rmsd_max_set = largest_set(); break;
+        }
+        if (p.temporal()) {     // [num_frames][contexts x values per context]
             st->dim1 = st->dist_P * st->dist_per;
             st->values.assign(num_frames * st->dim1, 0.0f);
             st->data.dim[0] = (int32_t)num_frames; st->data.dim[1] = (int32_t)st->dim1;
-            st->data.unit_str[0] = ""; st->data.unit_str[1] = "\xC3\x85";
-            if (p.nargs() > 2) st->data.unit_str[1] = e->spec.angle_radians ? "rad" : "\xC2\xB0";     // DESIGN S6b, D-ANGLE-UNIT
-            if (p.is_shape()) {                                                                     // a pure number
-                st->data.unit_str[1] = "";
-                for (size_t c = 0; c < st->dist_P; ++c) st->shape_max_set = std::max(st->shape_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
-            }
-            if (p.is_rmsd())                                                                      // Angstrom, as distance
-                for (size_t c = 0; c < st->dist_P; ++c) st->rmsd_max_set = std::max(st->rmsd_max_set, (int)(p.aoff[c + 1] - p.aoff[c]));
-            if (p.is_within() || p.is_within_expr()) st->data.unit_str[1] = "";                   // a count
-            if (st->dim1 > 1) {
+            if (aggregate && st->dim1 > 1) {
                 st->agg_mean.assign(num_frames, 0.0f); st->agg_var.assign(num_frames, 0.0f); st->agg_ext.assign(num_frames * 2, 0.0f);
                 st->aggregate.num_values = num_frames;
                 st->aggregate.population_mean = st->agg_mean.data();
@@ -375,7 +364,6 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
                 st->aggregate.population_ext = (float(*)[2])st->agg_ext.data();
                 st->data.aggregate = &st->aggregate;
             }
-            break;
         }
         st->data.values = st->values.data();
         st->data.num_values = st->values.size();
@@ -482,7 +470,7 @@ extern "C" void vmd_eval_clear_data(vmd_script_eval_t* eval) {
         // (profiles/r06a_c4_1250_timeline.txt) - a fifth of a rank's 1 250-frame share of configs[3].  A reader polling `fingerprint`
         // (src/main.cpp:1508; density_volume.cpp:159-163, 279-283) sees zeros under the new fingerprint at once, never the previous run's
         // voxels; VIAMD dereferences prop_data->values when it uploads.
-        if (p->prop.kind == PROP_SDF) {
+        if (p->prop.cls() == ResultClass::VOLUME) {
             float* zeros = zero_volume_view(p->ncounts);
             if (zeros) pub(p->data.values, zeros);
             else {      // no address space for the shared zeros: zero the view itself, as before round 6 (never a NULL `values`)
@@ -493,21 +481,21 @@ extern "C" void vmd_eval_clear_data(vmd_script_eval_t* eval) {
         else std::fill(p->values.begin(), p->values.end(), 0.0f);
         std::fill(p->weights.begin(), p->weights.end(), 0.0f);
         // the 17 MB u64 mirror of a volume is only ever read after vmd_eval_refresh_counts: mark it stale instead of zeroing it
-        if (p->prop.kind == PROP_SDF) p->counts_stale = true;
+        if (p->prop.cls() == ResultClass::VOLUME) p->counts_stale = true;
         else std::fill(p->counts.begin(), p->counts.end(), (uint64_t)0);
         std::fill(p->weights64.begin(), p->weights64.end(), 0.0);
         std::fill(p->agg_mean.begin(), p->agg_mean.end(), 0.0f);
         std::fill(p->agg_var.begin(), p->agg_var.end(), 0.0f);
         std::fill(p->agg_ext.begin(), p->agg_ext.end(), 0.0f);
         if (p->ncounts) (void)hipMemsetAsync(p->d_counts.p, 0, p->ncounts * sizeof(uint64_t), eval->stream);
-        if (p->prop.is_rama()) {
+        if (p->prop.form == Form::RAMA_TABLE) {
             (void)hipMemsetAsync(p->d_table.p, 0, p->values.size() * sizeof(float), eval->stream);
             p->table_stale = false;
         }
         pub(p->data.max_value, 0.0f); pub(p->data.min_value, 0.0f);
         pub(p->data.max_range[1], 0.0f);
         p->dirty = false;
-        if (p->prop.kind != PROP_SDF) p->counts_stale = false;
+        if (p->prop.cls() != ResultClass::VOLUME) p->counts_stale = false;
         pub_touch(p->data.fingerprint);
     }
     (void)hipStreamSynchronize(eval->stream);
@@ -585,7 +573,7 @@ bool refresh_volume(vmd_script_eval_t* e, PropState* p) {
     VMD_STAGE("refresh_volume: counts -> float view, D2H");
     if (!p->d_max.ensure(1)) return false;
     float scale = 1.0f;
-    if (p->prop.kind == PROP_SDF && e->spec.sdf_density) {
+    if (p->prop.form == Form::SDF && e->spec.sdf_density) {
         // DECISION(D-SDF-NORM) flipped: number density per cubic Angstrom, averaged over the frames evaluated so far
         const double edge = 2.0 * (double)p->prop.rmax / (double)VMD_VOLUME_DIM;
         const size_t nf = e->frames_done.load();
@@ -647,6 +635,16 @@ void refresh_temporal_stats(vmd_script_eval_t* e, PropState* p) {
     p->dirty = false;
 }
 
+// brings the host view of one property up to date, by what a host reads of it
+bool refresh_view(vmd_script_eval_t* e, PropState* p) {
+    switch (p->prop.cls()) {
+    case ResultClass::DISTRIBUTION: return refresh_distribution(e, p);
+    case ResultClass::VOLUME: case ResultClass::MAP: return refresh_volume(e, p);
+    case ResultClass::TEMPORAL: refresh_temporal_stats(e, p); return true;
+    }
+    return true;
+}
+
 extern "C" bool vmd_eval_defer_volume_views(vmd_script_eval_t* eval, bool defer) {
     if (!eval) return vmd_fail("eval is NULL");
     eval->defer_volume_views.store(defer, std::memory_order_relaxed);
@@ -659,12 +657,9 @@ extern "C" bool vmd_eval_finalize(vmd_script_eval_t* eval) {
     std::lock_guard<std::mutex> l(eval->mtx);
     HIP_OK(hipSetDevice(eval->device));
     for (auto& p : eval->props) {
-        bool ok = true;
-        if (p->prop.kind == PROP_RDF) ok = refresh_distribution(eval, p.get());
-        else if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) ok = refresh_volume(eval, p.get());
-        else refresh_temporal_stats(eval, p.get());
+        const bool ok = refresh_view(eval, p.get());
         // rows of other ranks may have joined the host table (vmd_eval_reduce): the device copy follows before the next filtered map
-        if (p->prop.is_rama()) p->table_stale = true;
+        if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;
         if (!ok) return false;
     }
     return true;
@@ -702,7 +697,7 @@ extern "C" bool vmd_eval_set_block_frames(vmd_script_eval_t* eval, size_t block_
     for (auto& p : eval->props) {
         if (!p->ncounts) continue;
         if (!p->d_blocks.ensure(nblocks * p->ncounts)) return false;
-        if (p->prop.kind == PROP_RDF) p->block_weights64.assign(nblocks * p->ncounts, 0.0);
+        if (p->prop.cls() == ResultClass::DISTRIBUTION) p->block_weights64.assign(nblocks * p->ncounts, 0.0);
     }
     eval->block_ready.reset(new std::atomic<uint8_t>[nblocks]);
     for (size_t b = 0; b < nblocks; ++b) eval->block_ready[b] = 0;
@@ -753,7 +748,7 @@ extern "C" void vmd_eval_set_frame_mask(vmd_script_eval_t* eval, const uint8_t* 
         done += eval->frame_mask[f] ? 1 : 0;
     }
     eval->frames_done = done;
-    for (auto& p : eval->props) if (p->prop.is_rama()) p->table_stale = true;     // frames evaluated elsewhere: their rows are on the host
+    for (auto& p : eval->props) if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // frames evaluated elsewhere: their rows are on the host
 }
 
 extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t* out, size_t cap) {
@@ -764,20 +759,16 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
             vmd_accum_view_t v;
             memset(&v, 0, sizeof(v));
             v.name = p->prop.name.c_str();
-            v.flags = p->prop.flags;
+            v.flags = p->prop.flags();
             if (p->ncounts) { v.counts_dev = p->d_counts.p; v.num_counts = p->ncounts; }
-            // a voxel receives at most one count per (frame, structure, target atom)
-            if (p->prop.kind == PROP_SDF) {
-                const long double b = (long double)eval->num_frames * (long double)p->prop.K * (long double)p->prop.b.size();
-                v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
-            }
-            // a bin receives at most one count per (frame, segment)
-            if (p->prop.kind == PROP_RAMA) {
-                const long double b = (long double)eval->num_frames * (long double)p->prop.K;
+            // a voxel receives at most one count per (frame, structure, target atom), a bin of a map one per (frame, segment)
+            if (p->prop.counts_view()) {
+                const long double per_frame = (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
+                const long double b = (long double)eval->num_frames * per_frame;
                 v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
             }
             if (!p->weights64.empty()) { v.weights64 = p->weights64.data(); v.num_weights = p->weights64.size(); }
-            if (p->prop.kind == PROP_DIST) { v.temporal = p->values.data(); v.num_temporal = p->values.size(); }
+            if (p->prop.temporal()) { v.temporal = p->values.data(); v.num_temporal = p->values.size(); }
             out[n] = v;
         }
         n += 1;
@@ -808,7 +799,7 @@ extern "C" bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name,
     size_t mi = e->props.size();
     for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) mi = i;
     if (mi == e->props.size()) return vmd_fail("unknown property '%s'", name);
-    if (e->props[mi]->prop.kind != PROP_RAMA || mi == 0 || !e->props[mi - 1]->prop.is_rama())
+    if (e->props[mi]->prop.form != Form::RAMA_MAP || mi == 0 || e->props[mi - 1]->prop.form != Form::RAMA_TABLE)
         return vmd_fail("'%s' is not a ramachandran map", name);
     if (frame_beg < frame_end && frame_end > e->num_frames)
         return vmd_fail("frames [%u, %u) are outside the %zu frames of the evaluation", frame_beg, frame_end, e->num_frames);
@@ -865,10 +856,13 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
             out.resize(idx.size());
             for (size_t i = 0; i < idx.size(); ++i)
                 out[i] = (sys && sys->mass && (size_t)idx[i] < sys->atom_count) ? sys->mass[idx[i]] : 1.0f;
-            if (d.kind == PROP_DIST && e->spec.dist_geometric_com) std::fill(out.begin(), out.end(), 1.0f);   // D-DIST-COM flipped
+            if (d.temporal() && e->spec.dist_geometric_com) std::fill(out.begin(), out.end(), 1.0f);   // D-DIST-COM flipped
         };
         std::vector<float> tmp;
-        if (d.kind == PROP_SDF) {
+        switch (d.form) {
+        case Form::RDF: case Form::RAMA_MAP: break;      // the sets of an rdf are interned selections; a map has none
+        case Form::WITHIN_EXPR: break;                   // the lists live in the interned selections
+        case Form::SDF: {
             if (!p->d_structs.upload(d.a.data(), d.a.size(), e->stream)) return false;
             if (!p->d_tgt.upload(d.b.data(), d.b.size(), e->stream)) return false;
             masses(d.a, tmp);
@@ -949,35 +943,30 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
                 HIP_OK(hipStreamSynchronize(e->stream));
             }
             HIP_OK(hipStreamSynchronize(e->stream));
-        } else if (d.is_within_expr()) {
-            // the lists live in the interned selections
-        } else if (d.is_rama()) {
+            break;
+        }
+        case Form::RAMA_TABLE:
             // N, CA, C per segment and the per-segment bytes (the descriptor's vectors live as long as the eval)
             if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_b.upload(d.b.data(), d.b.size(), e->stream) ||
                 !p->d_c.upload(d.c.data(), d.c.size(), e->stream) || !p->d_rama_class.upload(d.rama_class.data(), d.rama_class.size(), e->stream)
                 || !p->d_rama_link.upload(d.rama_link.data(), d.rama_link.size(), e->stream)) return false;
-        } else if (d.kind == PROP_DIST) {
-            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream)) return false;
-            if (!p->d_b.upload(d.b.data(), d.b.size(), e->stream)) return false;
-            if (!p->d_aoff.upload(d.aoff.data(), d.aoff.size(), e->stream)) return false;
-            if (!p->d_boff.upload(d.boff.data(), d.boff.size(), e->stream)) return false;
-            masses(d.a, tmp);
-            if (!p->d_ma.upload(tmp.data(), tmp.size(), e->stream)) return false;
-            masses(d.b, tmp);
-            if (!p->d_mb.upload(tmp.data(), tmp.size(), e->stream)) return false;
-            // angle / dihedral: the third and fourth argument sets (DESIGN S6b)
-            if (d.nargs() > 2) {
-                HIP_OK(hipStreamSynchronize(e->stream));       // tmp is refilled below
-                if (!p->d_c.upload(d.c.data(), d.c.size(), e->stream) || !p->d_coff.upload(d.coff.data(), d.coff.size(), e->stream)) return false;
-                masses(d.c, tmp);
-                if (!p->d_mc.upload(tmp.data(), tmp.size(), e->stream)) return false;
+            break;
+        case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::WITHIN: {
+            // the form's argument sets (two for distance, three and four for angle / dihedral, DESIGN S6b), their offsets and masses
+            const std::vector<int32_t>* sets[4] = {&d.a, &d.b, &d.c, &d.d};
+            const std::vector<int32_t>* offs[4] = {&d.aoff, &d.boff, &d.coff, &d.doff};
+            DevBuf<int32_t>* d_set[4] = {&p->d_a, &p->d_b, &p->d_c, &p->d_d};
+            DevBuf<int32_t>* d_off[4] = {&p->d_aoff, &p->d_boff, &p->d_coff, &p->d_doff};
+            DevBuf<float>* d_m[4] = {&p->d_ma, &p->d_mb, &p->d_mc, &p->d_md};
+            for (int k = 0; k < d.nargs(); ++k) {
+                if (k) HIP_OK(hipStreamSynchronize(e->stream));       // tmp is refilled below
+                if (!d_set[k]->upload(sets[k]->data(), sets[k]->size(), e->stream) || !d_off[k]->upload(offs[k]->data(), offs[k]->size(), e->stream))
+                    return false;
+                masses(*sets[k], tmp);
+                if (!d_m[k]->upload(tmp.data(), tmp.size(), e->stream)) return false;
             }
-            if (d.nargs() > 3) {
-                HIP_OK(hipStreamSynchronize(e->stream));
-                if (!p->d_d.upload(d.d.data(), d.d.size(), e->stream) || !p->d_doff.upload(d.doff.data(), d.doff.size(), e->stream)) return false;
-                masses(d.d, tmp);
-                if (!p->d_md.upload(tmp.data(), tmp.size(), e->stream)) return false;
-            }
+            break;
+        }
         }
         HIP_OK(hipStreamSynchronize(e->stream));   // tmp goes out of scope
         p->uploaded = true;
@@ -988,7 +977,7 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
 extern "C" const int32_t* vmd_eval_sdf_structures(const vmd_script_eval_t* eval, const char* name, size_t* num_structures,
         size_t* atoms_per_structure) {
     PropState* p = find_prop(eval, name);
-    if (!p || p->prop.kind != PROP_SDF) { vmd_fail("'%s' is not an sdf property", name ? name : "(null)"); return nullptr; }
+    if (!p || p->prop.form != Form::SDF) { vmd_fail("'%s' is not an sdf property", name ? name : "(null)"); return nullptr; }
     if (num_structures) *num_structures = p->prop.K;
     if (atoms_per_structure) *atoms_per_structure = p->prop.m;
     return p->prop.a.data();
@@ -998,7 +987,7 @@ extern "C" bool vmd_eval_sdf_matrices(vmd_script_eval_t* eval, const char* name,
                                       vmd_trajectory_i* traj, uint32_t frame, float* matrices, size_t* K_out, float* extent_out) {
     if (!eval || !traj) return vmd_fail("vmd_eval_sdf_matrices: NULL argument");
     PropState* p = find_prop(eval, name);
-    if (!p || p->prop.kind != PROP_SDF) return vmd_fail("'%s' is not an sdf property", name ? name : "(null)");
+    if (!p || p->prop.form != Form::SDF) return vmd_fail("'%s' is not an sdf property", name ? name : "(null)");
     std::lock_guard<std::mutex> lock(eval->mtx);
     HIP_OK(hipSetDevice(eval->device));
     vmd_script_eval_t* e = eval;
@@ -1056,12 +1045,12 @@ extern "C" size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name,
     // created, and nothing changes them afterwards - pool threads inside frame_range only read them too)
     int sel_t = -1, sel_r = -1;
     float rmin = 0.0f, rmax = 0.0f;
-    if (p->prop.is_within() && which == 1) {
+    if (p->prop.form == Form::WITHIN && which == 1) {
         sel_t = p->sel_a; sel_r = p->sel_b; rmin = p->prop.rmin; rmax = p->prop.rmax;
     } else if ((p->prop.is_shell_rdf() || p->prop.is_shell_sdf()) && p->prop.shell[which].on) {
         const Shell& h = *e->shells[p->shell_of[which]];
         sel_t = h.sel_t; sel_r = h.sel_r; rmin = h.rmin; rmax = h.rmax;
-    } else if ((p->prop.is_within_expr() || p->prop.is_expr_sdf()) && which == 1) {
+    } else if ((p->prop.form == Form::WITHIN_EXPR || p->prop.is_expr_sdf()) && which == 1) {
         // every term by all pairs into the eval's one-frame bits, then the finish - handled below
     } else {
         vmd_fail("the %s side of '%s' is not a within() shell", which ? "target" : "reference", name);

@@ -12,6 +12,8 @@
 //     vmd_eval_traj.cpp     trajectory kinds, checkpoint / mapping caches    vmd_eval_post.cpp   histogram post-processing
 // - and this header holds every struct they share, in the order the single file declared them, with each function's prototype where
 // its definition used to stand.  Nothing here is part of the ABI.
+// What a property IS is its Form (section IR below).  A NEW FORM gets a value in that enum, its row in kFormFacts and a case in every
+// `switch (....form)` - those have no default and these files are built with -Werror=switch (viamd_amd/build.py): the compiler lists them.
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -357,54 +359,86 @@ struct HostBuf {
 };
 
 // ------------------------------------------------------------------------------------------------ IR
-enum PropKind { PROP_RDF = 0, PROP_SDF = 1, PROP_DIST = 2, PROP_RAMA = 3 };
+// One Form per thing the evaluator does with a descriptor, set once where the descriptor is made (make_property, vmd_eval_ir.cpp); a new
+// one: see the head of this file and DESIGN 1.11.  Shell and expression arguments of rdf / sdf are modifiers on those two forms, not forms.
+enum class Form : int {
+    RDF,             // a = ref, b = target, rmin / rmax; either side may be a shell (shell[])
+    SDF,             // a = structures (K * m), b = target, rmax = cutoff; the target may be a shell (shell[1]) or an expression (1.9)
+    DISTANCE,        // a / b with context offsets aoff / boff; distance_kind says which of the four
+    ANGLE, DIHEDRAL, // DESIGN S6b: three or four argument sets per context (a .. d, aoff .. doff)
+    // `{lin, plan, iso} = shape_weights(sel)`: three descriptors in a row, one per name, that carry the same set (a / aoff) and a
+    // component index; the device work is done once, where the batch meets component 0
+    SHAPE,
+    RMSD,            // `name = rmsd(sel)`: the set (a / aoff); the evaluator keeps the frame-0 pose of the set
+    // `name = count(T and within(rmin:rmax, R))`: a = T, b = R, the range in rmin / rmax; one value per frame, the number of
+    // atoms of T with an atom of R in range
+    WITHIN,
+    // `name = count(T and <and / or / not over within() terms>)`: a = T, b empty, the terms in expr_terms.  An expression of
+    // one positive term never gets here (it IS the one-term property, by the entry points)
+    WITHIN_EXPR,
+    // `{table, map} = ramachandran(backbone)`: two descriptors in a row.  The table - a = N, b = CA, c = C per segment, aoff =
+    // the range offsets, rama_class / rama_link one byte per segment - has rows {phi, psi} per segment; the map behind it (K = the segments,
+    // for the merge's count bound) is what the table's launch bins into
+    RAMA_TABLE, RAMA_MAP,
+};
 
-// temporal properties of DESIGN S6b: PROP_DIST descriptors with three or four argument sets (dist_kind past vmd_distance_kind_t)
-enum { GEOM_ANGLE = 4, GEOM_DIHEDRAL = 5 };
-// `{lin, plan, iso} = shape_weights(sel)`: three PROP_DIST descriptors in a row, one per name, that carry the same set (a / aoff)
-// and a component index; the device work is done once, where the batch meets component 0
-enum { GEOM_SHAPE = 6 };
-// `name = rmsd(sel)`: one PROP_DIST descriptor that carries the set (a / aoff); the evaluator keeps the frame-0 pose of the set
-enum { GEOM_RMSD = 7 };
-// `name = count(T and within(rmin:rmax, R))`: one PROP_DIST descriptor, a = T, b = R, the range in rmin / rmax; one value per
-// frame, the number of atoms of T with an atom of R in range
-enum { GEOM_WITHIN = 8 };
-// `name = count(T and <and / or / not over within() terms>)`: one PROP_DIST descriptor, a = T, the terms in expr_terms
-enum { GEOM_WITHIN_EXPR = 9 };
-// `{table, map} = ramachandran(backbone)`: two descriptors in a row.  The angle table is a PROP_DIST descriptor - a = N, b = CA,
-// c = C per segment, aoff = the range offsets, rama_class / rama_link one byte per segment - whose rows are {phi, psi} per segment; the
-// map behind it is a PROP_RAMA descriptor (K = the segments, for the merge's count bound) that the table's launch bins into
-enum { GEOM_RAMA = 10 };
+// what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
+enum class ResultClass : uint32_t { DISTRIBUTION = 0, VOLUME = 1, TEMPORAL = 2, MAP = 3 };
+constexpr vmd_property_flags_t kClassFlags[] = {VMD_PROPERTY_FLAG_DISTRIBUTION, VMD_PROPERTY_FLAG_VOLUME, VMD_PROPERTY_FLAG_TEMPORAL, VMD_PROPERTY_FLAG_MAP};
+
+struct FormFacts {
+    ResultClass cls;
+    int nargs;                      // argument sets with context offsets (a, b, c, d in this order)
+    const char* word;               // in messages
+    const char* unit[2];            // data.unit_str ...
+    const char* unit_y_radians;     // ... and [1] under spec_angle_radians (D-ANGLE-UNIT), where that differs
+    bool behind_cells;              // launched by launch_rdf behind the batch's cell builds, not by launch_property
+    int geom_code;                  // the second value the fingerprint hashes (an int; DISTANCE: its vmd_distance_kind_t, 0..3, instead)
+};
+constexpr FormFacts kFormFacts[] = {
+    /* RDF         */ {ResultClass::DISTRIBUTION, 2, "rdf",           {"\xC3\x85", ""}, nullptr, true,  0},
+    /* SDF         */ {ResultClass::VOLUME,       2, "sdf",           {"", ""},         nullptr, false, 0},     // (over a shell / an expression: behind the cells)
+    /* DISTANCE    */ {ResultClass::TEMPORAL,     2, "distance",      {"", "\xC3\x85"}, nullptr, false, 0},
+    /* ANGLE       */ {ResultClass::TEMPORAL,     3, "angle",         {"", "\xC2\xB0"}, "rad",   false, 4},
+    /* DIHEDRAL    */ {ResultClass::TEMPORAL,     4, "dihedral",      {"", "\xC2\xB0"}, "rad",   false, 5},
+    /* SHAPE       */ {ResultClass::TEMPORAL,     1, "shape_weights", {"", ""},         nullptr, false, 6},     // a pure number
+    /* RMSD        */ {ResultClass::TEMPORAL,     1, "rmsd",          {"", "\xC3\x85"}, nullptr, false, 7},     // Angstrom, as distance
+    /* WITHIN      */ {ResultClass::TEMPORAL,     2, "within",        {"", ""},         nullptr, true,  8},     // a count
+    /* WITHIN_EXPR */ {ResultClass::TEMPORAL,     1, "within",        {"", ""},         nullptr, true,  9},
+    /* RAMA_TABLE  */ {ResultClass::TEMPORAL,     3, "ramachandran",  {"", "rad"},      nullptr, false, 10},    // radians whatever spec_angle_radians says
+    /* RAMA_MAP    */ {ResultClass::MAP,          0, "ramachandran",  {"rad", ""},      nullptr, false, 0},
+};
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::RAMA_MAP + 1, "one row of kFormFacts per Form");
 
 struct Property {
     std::string name;
-    PropKind kind;
-    vmd_property_flags_t flags;
-    std::vector<int32_t> a, b;      // RDF: ref/target; SDF: structures (K*m)/target; DIST: a/b
-    float rmin = 0.0f, rmax = 0.0f; // RDF range; SDF: rmax = cutoff (half extent)
+    Form form;
+    const FormFacts& facts() const { return kFormFacts[(int)form]; }
+    ResultClass cls() const { return facts().cls; }
+    bool temporal() const { return cls() == ResultClass::TEMPORAL; }          // rows per frame in `values`
+    bool counts_view() const { return cls() == ResultClass::VOLUME || cls() == ResultClass::MAP; }     // a float view made from u64 counts
+    vmd_property_flags_t flags() const { return kClassFlags[(int)cls()]; }
+    std::vector<int32_t> a, b;      // the first two argument sets (see Form)
+    float rmin = 0.0f, rmax = 0.0f; // RDF, WITHIN: the range; SDF: rmax = cutoff (half extent)
     size_t K = 0, m = 0;
-    int dist_kind = 0;              // DIST: vmd_distance_kind_t, or GEOM_ANGLE / GEOM_DIHEDRAL
-    std::vector<int32_t> aoff, boff;   // DIST: context offsets into a / b (population), size P + 1
-    std::vector<int32_t> c, d, coff, doff;   // angle / dihedral: the third and fourth argument sets, offsets as aoff
-    int nargs() const { return dist_kind == GEOM_DIHEDRAL ? 4 : (dist_kind == GEOM_ANGLE ? 3 : 2); }
-    int shape_comp = 0;             // shape_weights: 0 = linear, 1 = planar, 2 = isotropic
-    bool is_shape() const { return kind == PROP_DIST && dist_kind == GEOM_SHAPE; }
-    bool is_rmsd() const { return kind == PROP_DIST && dist_kind == GEOM_RMSD; }
-    bool is_within() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN; }
+    int distance_kind = 0;          // DISTANCE: vmd_distance_kind_t
+    int geom_code() const { return form == Form::DISTANCE ? distance_kind : facts().geom_code; }     // (the fingerprint's)
+    std::vector<int32_t> aoff, boff;   // context offsets into a / b (population), size P + 1
+    std::vector<int32_t> c, d, coff, doff;   // the third and fourth argument sets, offsets as aoff
+    int nargs() const { return facts().nargs; }
+    int shape_comp = 0;             // SHAPE: 0 = linear, 1 = planar, 2 = isotropic
     // rdf over within() shells: side 0 = a (reference), 1 = b (target); on: that argument is the shell (list, ref, rmin, rmax)
     struct ShellArg { bool on = false; std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; } shell[2];
-    bool is_shell_rdf() const { return kind == PROP_RDF && (shell[0].on || shell[1].on); }
-    bool is_shell_sdf() const { return kind == PROP_SDF && shell[1].on; }     // sdf over a shell target: side 1 only
-    // and / or / not over within() shells: 1..4 terms and a truth table of 2^K bits, indexed by sum(h_i << i).  Count form:
-    // dist_kind GEOM_WITHIN_EXPR, a = T, b empty; sdf form: b = T.  An expression of one positive term never gets here (it IS the
-    // one-term property, by the entry points)
-    struct ExprTerm { std::vector<int32_t> ref; float rmin = 0.0f, rmax = 0.0f; };
+    bool is_shell_rdf() const { return form == Form::RDF && (shell[0].on || shell[1].on); }
+    bool is_shell_sdf() const { return form == Form::SDF && shell[1].on; }     // sdf over a shell target: side 1 only
+    // and / or / not over within() shells: 1..4 terms and a truth table of 2^K bits, indexed by sum(h_i << i).  WITHIN_EXPR:
+    // a = T; SDF: b = T
+    typedef ShellArg ExprTerm;
     std::vector<ExprTerm> expr_terms;
     uint32_t expr_truth = 0;
-    bool is_within_expr() const { return kind == PROP_DIST && dist_kind == GEOM_WITHIN_EXPR; }
-    std::vector<uint8_t> rama_class, rama_link;     // ramachandran table: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
-    bool is_rama() const { return kind == PROP_DIST && dist_kind == GEOM_RAMA; }
-    bool is_expr_sdf() const { return kind == PROP_SDF && !expr_terms.empty(); }
+    std::vector<uint8_t> rama_class, rama_link;     // RAMA_TABLE: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
+    bool is_expr_sdf() const { return form == Form::SDF && !expr_terms.empty(); }
+    bool behind_cells() const { return facts().behind_cells || is_shell_sdf() || is_expr_sdf(); }     // launch_rdf launches it, not launch_property
 };
 
 struct vmd_script_ir_t {
@@ -898,6 +932,8 @@ bool refresh_distribution(vmd_script_eval_t* e, PropState* p);
 bool refresh_volume(vmd_script_eval_t* e, PropState* p);
 
 void refresh_temporal_stats(vmd_script_eval_t* e, PropState* p);
+
+bool refresh_view(vmd_script_eval_t* e, PropState* p);
 
 extern "C" bool vmd_eval_wait_settled(vmd_script_eval_t* eval);
 

@@ -11,6 +11,9 @@ uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
 
 extern "C" vmd_script_ir_t* vmd_ir_create(void) { return new vmd_script_ir_t(); }
 
+static uint64_t sum_sizes(std::initializer_list<const std::vector<int32_t>*> sets) { uint64_t n = 0; for (auto* v : sets) n += v->size(); return n; }
+static uint64_t expr_refs(const Property& p) { uint64_t n = 0; for (auto& t : p.expr_terms) n += t.ref.size(); return n; }
+
 // atom pairs one frame of this script asks for (rdf: |ref| x |target|; sdf: K x |target| + K m for the alignment; distance: |a| x |b| of
 // every context; angle / dihedral / shape_weights: the atoms of every context's sets): what a host compares with its threshold before it sends a SMALL script to the GPU at all (include/vmd_md_script_shim.h,
 // vmd_shim_set_min_work; VIAMD's default dataset is ~1e2 atoms, src/main.cpp:522-528)
@@ -18,25 +21,28 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
     if (!ir) return 0;
     uint64_t w = 0;
     for (const Property& p : ir->props) {
-        if (p.kind == PROP_RDF) {
+        switch (p.form) {
+        case Form::RDF:
             w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
             // the parent sizes (a bound that needs no frame) plus one neighbour query per shell, |T| + |R|
             for (int k = 0; k < 2; ++k) if (p.shell[k].on) w += (uint64_t)(k ? p.b : p.a).size() + (uint64_t)p.shell[k].ref.size();
-        }
-        else if (p.kind == PROP_SDF) {
+            break;
+        case Form::SDF:
             w += (uint64_t)p.K * ((uint64_t)p.b.size() + (uint64_t)p.m);
             if (p.shell[1].on) w += (uint64_t)p.b.size() + (uint64_t)p.shell[1].ref.size();     // the parent list plus the shell's query
-            if (p.is_expr_sdf()) { w += (uint64_t)p.b.size(); for (auto& t : p.expr_terms) w += (uint64_t)t.ref.size(); }     // |T| + sum |R_i|
+            if (p.is_expr_sdf()) w += (uint64_t)p.b.size() + expr_refs(p);                      // |T| + sum |R_i|
+            break;
+        case Form::DISTANCE:
+            for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c]) * (uint64_t)(p.boff[c + 1] - p.boff[c]);
+            break;
+        case Form::ANGLE: case Form::DIHEDRAL: w += sum_sizes({&p.a, &p.b, &p.c, &p.d}); break;     // each context: the sum of its set sizes
+        case Form::SHAPE: if (p.shape_comp == 0) w += p.a.size(); break;     // one pass over every context's set per statement
+        case Form::RMSD: w += p.a.size(); break;                             // the atoms of every context's set
+        case Form::WITHIN: w += sum_sizes({&p.a, &p.b}); break;              // |T| + |R|: a neighbour query, not all pairs
+        case Form::WITHIN_EXPR: w += p.a.size() + expr_refs(p); break;       // |T| + sum |R_i|
+        case Form::RAMA_TABLE: w += 3 * (uint64_t)p.a.size(); break;         // N, CA, C of every segment
+        case Form::RAMA_MAP: break;                                          // binned by its table's launch
         }
-        else if (p.is_shape()) { if (p.shape_comp == 0) w += (uint64_t)p.a.size(); }     // one pass over every context's set per statement
-        else if (p.is_rmsd()) w += (uint64_t)p.a.size();                                 // the atoms of every context's set
-        else if (p.is_rama()) w += 3 * (uint64_t)p.a.size();                             // N, CA, C of every segment
-        else if (p.is_within()) w += (uint64_t)p.a.size() + (uint64_t)p.b.size();        // |T| + |R|: a neighbour query, not all pairs
-        else if (p.is_within_expr()) { w += (uint64_t)p.a.size(); for (auto& t : p.expr_terms) w += (uint64_t)t.ref.size(); }     // |T| + sum |R_i|
-        else if (p.nargs() > 2) { for (const auto* v : {&p.a, &p.b, &p.c, &p.d}) w += (uint64_t)v->size(); }     // each context: the sum of its set sizes
-        else if (p.aoff.size() > 1) { for (size_t c = 0; c + 1 < p.aoff.size(); ++c) w += (uint64_t)(p.aoff[c + 1] - p.aoff[c])
-                * (uint64_t)(p.boff[c + 1] - p.boff[c]); }
-        else w += (uint64_t)p.a.size() * (uint64_t)p.b.size();
     }
     return w;
 }
@@ -56,52 +62,109 @@ bool idx_ok(const int32_t* idx, size_t n, const char* what) {
     return true;
 }
 
-extern "C" bool vmd_ir_add_rdf(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref,
-                               const int32_t* target, size_t ntarget, float rmin, float rmax) {
-    if (!ir_name_ok(ir, name) || !idx_ok(ref, nref, "rdf reference set") || !idx_ok(target, ntarget, "rdf target set")) return false;
-    if (!(rmin >= 0.0f) || !(rmax > rmin)) return vmd_fail("rdf range must satisfy 0 <= rmin < rmax");
-    Property p;
-    p.name = name; p.kind = PROP_RDF; p.flags = VMD_PROPERTY_FLAG_DISTRIBUTION;
+static const size_t kMaxSet = 0x7fffffff;     // ---- from here: what the entry points share, each check and each piece of construction once
+
+// the names of a statement that defines several properties: each free, no two alike
+static bool names_ok(vmd_script_ir_t* ir, const char* const* names, int n) {
+    for (int k = 0; k < n; ++k) {
+        if (!ir_name_ok(ir, names[k])) return false;
+        for (int j = 0; j < k; ++j) if (!strcmp(names[j], names[k])) return vmd_fail("property '%s' already defined", names[k]);
+    }
+    return true;
+}
+
+// one argument set of a population: P + 1 offsets that start at 0 and increase, valid indices.  `what` is the form's word; `arg` names the set
+// among several (" a"), or is "" where the form has one
+static bool population_ok(const char* what, const char* arg, size_t P, const int32_t* idx, const int32_t* offs) {
+    if (!offs) return vmd_fail("%s set%s has no context offsets", what, arg);
+    if (offs[0] != 0) return vmd_fail("context offsets must start at 0");
+    for (size_t c = 0; c < P; ++c)
+        if (offs[c + 1] <= offs[c]) return vmd_fail("%s context %zu has an empty set%s (offsets must increase)", what, c, arg);
+    char label[48];
+    snprintf(label, sizeof(label), "%s set%s", what, arg);
+    return idx_ok(idx, (size_t)offs[P], label);
+}
+
+static bool range_ok(Form f, float rmin, float rmax) {
+    if (f == Form::RDF) return (rmin >= 0.0f && rmax > rmin) || vmd_fail("rdf range must satisfy 0 <= rmin < rmax");
+    return (std::isfinite(rmin) && std::isfinite(rmax) && rmin >= 0.0f && rmax > rmin)
+        || vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
+}
+
+static bool set_size_ok(std::initializer_list<size_t> sizes) {
+    for (size_t n : sizes) if (n > kMaxSet) return vmd_fail("within set too large");
+    return true;
+}
+
+// a within() shell (an rdf / sdf argument, a term of an expression): its reference list, its size, its range
+static bool shell_ok(const vmd_shell_t& h) {
+    return idx_ok(h.ref, h.nref, "within reference set") && set_size_ok({h.nref}) && range_ok(Form::WITHIN, h.rmin, h.rmax);
+}
+
+static Property make_property(Form form, const char* name) { Property p; p.name = name; p.form = form; return p; }
+
+// the part of a descriptor every rdf entry point shares, checked and filled; the same for sdf
+static bool rdf_head(Property& p, vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const int32_t* target, size_t ntarget,
+                     float rmin, float rmax) {
+    if (!ir_name_ok(ir, name) || !idx_ok(ref, nref, "rdf reference set") || !idx_ok(target, ntarget, "rdf target set")
+        || !range_ok(Form::RDF, rmin, rmax)) return false;
+    p = make_property(Form::RDF, name);
     p.a.assign(ref, ref + nref); p.b.assign(target, target + ntarget);
     p.rmin = rmin; p.rmax = rmax;
-    ir->props.push_back(std::move(p));
+    return true;
+}
+
+static bool sdf_head(Property& p, vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m, const int32_t* target,
+                     size_t ntarget, float cutoff) {
+    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget, "sdf target set"))
+        return false;
+    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
+    p = make_property(Form::SDF, name);
+    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
+    p.K = K; p.m = m; p.rmax = cutoff;
+    return true;
+}
+
+static void shell_copy(Property::ShellArg& dst, const vmd_shell_t& h) {
+    dst.on = true; dst.ref.assign(h.ref, h.ref + h.nref); dst.rmin = h.rmin; dst.rmax = h.rmax;
+}
+
+static bool commit(vmd_script_ir_t* ir, Property* p, int n = 1) {
+    for (int k = 0; k < n; ++k) ir->props.push_back(std::move(p[k]));
     ir->rebuild_names();
     return true;
+}
+
+extern "C" bool vmd_ir_add_rdf(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref,
+                               const int32_t* target, size_t ntarget, float rmin, float rmax) {
+    Property p;
+    return rdf_head(p, ir, name, ref, nref, target, ntarget, rmin, rmax) && commit(ir, &p);
 }
 
 extern "C" bool vmd_ir_add_sdf(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
                                const int32_t* target, size_t ntarget, float cutoff) {
-    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget,
-            "sdf target set")) return false;
-    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
     Property p;
-    p.name = name; p.kind = PROP_SDF; p.flags = VMD_PROPERTY_FLAG_VOLUME;
-    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
-    p.K = K; p.m = m; p.rmax = cutoff;
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return sdf_head(p, ir, name, structures, K, m, target, ntarget, cutoff) && commit(ir, &p);
 }
+
+static bool distance_kind_ok(vmd_distance_kind_t kind) { return ((int)kind >= 0 && (int)kind <= 3) || vmd_fail("unknown distance kind %d", (int)kind); }
 
 extern "C" bool vmd_ir_add_distance(vmd_script_ir_t* ir, const char* name, vmd_distance_kind_t kind,
                                     const int32_t* a, size_t na, const int32_t* b, size_t nb) {
-    if (!ir_name_ok(ir, name) || !idx_ok(a, na, "distance set a") || !idx_ok(b, nb, "distance set b")) return false;
-    if ((int)kind < 0 || (int)kind > 3) return vmd_fail("unknown distance kind %d", (int)kind);
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    if (!ir_name_ok(ir, name) || !idx_ok(a, na, "distance set a") || !idx_ok(b, nb, "distance set b") || !distance_kind_ok(kind)) return false;
+    Property p = make_property(Form::DISTANCE, name);
     p.a.assign(a, a + na); p.b.assign(b, b + nb);
     p.aoff = {0, (int32_t)na}; p.boff = {0, (int32_t)nb};
-    p.dist_kind = (int)kind;
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    p.distance_kind = (int)kind;
+    return commit(ir, &p);
 }
 
+// (the one population whose two sets are checked context by context, side by side: its messages name no set)
 extern "C" bool vmd_ir_add_distance_population(vmd_script_ir_t* ir, const char* name, vmd_distance_kind_t kind, size_t P,
                                                const int32_t* a, const int32_t* a_offsets, const int32_t* b, const int32_t* b_offsets) {
     if (!ir_name_ok(ir, name)) return false;
     if (P == 0 || !a_offsets || !b_offsets) return vmd_fail("distance population is empty");
-    if ((int)kind < 0 || (int)kind > 3) return vmd_fail("unknown distance kind %d", (int)kind);
+    if (!distance_kind_ok(kind)) return false;
     if (a_offsets[0] != 0 || b_offsets[0] != 0) return vmd_fail("context offsets must start at 0");
     for (size_t c = 0; c < P; ++c) {
         if (a_offsets[c + 1] <= a_offsets[c] || b_offsets[c + 1] <= b_offsets[c]) return vmd_fail("distance context %zu has an empty set",
@@ -111,66 +174,64 @@ extern "C" bool vmd_ir_add_distance_population(vmd_script_ir_t* ir, const char* 
             return vmd_fail("distance_pair needs contexts of equal size");
     }
     if (!idx_ok(a, (size_t)a_offsets[P], "distance set a") || !idx_ok(b, (size_t)b_offsets[P], "distance set b")) return false;
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
+    Property p = make_property(Form::DISTANCE, name);
     p.a.assign(a, a + a_offsets[P]); p.b.assign(b, b + b_offsets[P]);
     p.aoff.assign(a_offsets, a_offsets + P + 1); p.boff.assign(b_offsets, b_offsets + P + 1);
-    p.dist_kind = (int)kind;
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    p.distance_kind = (int)kind;
+    return commit(ir, &p);
 }
 
-// angle / dihedral (DESIGN S6b): n argument sets per context, validated like the distance population
-static bool ir_add_geometry(vmd_script_ir_t* ir, const char* name, int kind, size_t P, const int32_t* const* sets, const int32_t* const* offs) {
-    static const char* const arg[4] = {"a", "b", "c", "d"};
-    const char* what = kind == GEOM_ANGLE ? "angle" : "dihedral";
-    const int n = kind == GEOM_ANGLE ? 3 : 4;
-    if (!ir_name_ok(ir, name)) return false;
-    if (P == 0) return vmd_fail("%s population is empty", what);
-    char label[48];
-    for (int k = 0; k < n; ++k) {
-        if (!offs[k]) return vmd_fail("%s set %s has no context offsets", what, arg[k]);
-        if (offs[k][0] != 0) return vmd_fail("context offsets must start at 0");
-        for (size_t c = 0; c < P; ++c)
-            if (offs[k][c + 1] <= offs[k][c]) return vmd_fail("%s context %zu has an empty set %s (offsets must increase)", what, c, arg[k]);
-        snprintf(label, sizeof(label), "%s set %s", what, arg[k]);
-        if (!idx_ok(sets[k], (size_t)offs[k][P], label)) return false;
+// angle / dihedral (DESIGN S6b), `{n0, n1, n2} = shape_weights(sel)` and `name = rmsd(sel)` `[in <contexts>]`: the
+// form's argument sets per context; shape_weights defines three properties over its one set, a component each
+static bool ir_add_sets(vmd_script_ir_t* ir, Form form, const char* const* names, size_t P, const int32_t* const* sets, const int32_t* const* offs) {
+    static const char* const arg[4] = {" a", " b", " c", " d"};
+    const FormFacts& f = kFormFacts[(int)form];
+    const int nprops = form == Form::SHAPE ? 3 : 1;
+    if (!names_ok(ir, names, nprops)) return false;
+    if (P == 0) return vmd_fail("%s population is empty", f.word);
+    for (int k = 0; k < f.nargs; ++k) if (!population_ok(f.word, f.nargs > 1 ? arg[k] : "", P, sets[k], offs[k])) return false;
+    Property p[3];
+    for (int j = 0; j < nprops; ++j) {
+        p[j] = make_property(form, names[j]);
+        p[j].shape_comp = j;
+        std::vector<int32_t>* dst[4] = {&p[j].a, &p[j].b, &p[j].c, &p[j].d};
+        std::vector<int32_t>* dof[4] = {&p[j].aoff, &p[j].boff, &p[j].coff, &p[j].doff};
+        for (int k = 0; k < f.nargs; ++k) { dst[k]->assign(sets[k], sets[k] + offs[k][P]); dof[k]->assign(offs[k], offs[k] + P + 1); }
     }
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-    p.dist_kind = kind;
-    std::vector<int32_t>* dst[4] = {&p.a, &p.b, &p.c, &p.d};
-    std::vector<int32_t>* dof[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
-    for (int k = 0; k < n; ++k) { dst[k]->assign(sets[k], sets[k] + offs[k][P]); dof[k]->assign(offs[k], offs[k] + P + 1); }
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return commit(ir, p, nprops);
+}
+
+// the single forms: one context whose offsets are {0, n}
+static bool ir_add_sets_single(vmd_script_ir_t* ir, Form form, const char* const* names, const int32_t* const* sets, const size_t* n) {
+    const FormFacts& f = kFormFacts[(int)form];
+    int32_t o[4][2];
+    const int32_t* offs[4];
+    for (int k = 0; k < f.nargs; ++k) {
+        if (n[k] > kMaxSet) return vmd_fail("%s set too large", f.word);
+        o[k][0] = 0; o[k][1] = (int32_t)n[k]; offs[k] = o[k];
+    }
+    return ir_add_sets(ir, form, names, 1, sets, offs);
 }
 
 extern "C" bool vmd_ir_add_angle(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
                                  const int32_t* c, size_t nc) {
-    if (na > 0x7fffffff || nb > 0x7fffffff || nc > 0x7fffffff) return vmd_fail("angle set too large");
-    const int32_t ao[2] = {0, (int32_t)na}, bo[2] = {0, (int32_t)nb}, co[2] = {0, (int32_t)nc};
     const int32_t* sets[3] = {a, b, c};
-    const int32_t* offs[3] = {ao, bo, co};
-    return ir_add_geometry(ir, name, GEOM_ANGLE, 1, sets, offs);
+    const size_t n[3] = {na, nb, nc};
+    return ir_add_sets_single(ir, Form::ANGLE, &name, sets, n);
 }
 
 extern "C" bool vmd_ir_add_dihedral(vmd_script_ir_t* ir, const char* name, const int32_t* a, size_t na, const int32_t* b, size_t nb,
                                     const int32_t* c, size_t nc, const int32_t* d, size_t nd) {
-    if (na > 0x7fffffff || nb > 0x7fffffff || nc > 0x7fffffff || nd > 0x7fffffff) return vmd_fail("dihedral set too large");
-    const int32_t ao[2] = {0, (int32_t)na}, bo[2] = {0, (int32_t)nb}, co[2] = {0, (int32_t)nc}, dof[2] = {0, (int32_t)nd};
     const int32_t* sets[4] = {a, b, c, d};
-    const int32_t* offs[4] = {ao, bo, co, dof};
-    return ir_add_geometry(ir, name, GEOM_DIHEDRAL, 1, sets, offs);
+    const size_t n[4] = {na, nb, nc, nd};
+    return ir_add_sets_single(ir, Form::DIHEDRAL, &name, sets, n);
 }
 
 extern "C" bool vmd_ir_add_angle_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
                                             const int32_t* b, const int32_t* b_offsets, const int32_t* c, const int32_t* c_offsets) {
     const int32_t* sets[3] = {a, b, c};
     const int32_t* offs[3] = {a_offsets, b_offsets, c_offsets};
-    return ir_add_geometry(ir, name, GEOM_ANGLE, P, sets, offs);
+    return ir_add_sets(ir, Form::ANGLE, &name, P, sets, offs);
 }
 
 extern "C" bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* a, const int32_t* a_offsets,
@@ -178,216 +239,114 @@ extern "C" bool vmd_ir_add_dihedral_population(vmd_script_ir_t* ir, const char* 
                                                const int32_t* d, const int32_t* d_offsets) {
     const int32_t* sets[4] = {a, b, c, d};
     const int32_t* offs[4] = {a_offsets, b_offsets, c_offsets, d_offsets};
-    return ir_add_geometry(ir, name, GEOM_DIHEDRAL, P, sets, offs);
+    return ir_add_sets(ir, Form::DIHEDRAL, &name, P, sets, offs);
 }
 
-// `{n0, n1, n2} = shape_weights(sel) [in <contexts>];`: three temporal properties over one population of sets
-static bool ir_add_shape(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx, const int32_t* offs) {
+// (a statement of three names: the descriptor list and the names are looked at before anything else)
+static bool shape_names_ok(vmd_script_ir_t* ir, const char* const names[3]) {
     if (!ir) return vmd_fail("ir is NULL");
-    if (!names) return vmd_fail("shape_weights needs three property names");
-    for (int k = 0; k < 3; ++k) {
-        if (!ir_name_ok(ir, names[k])) return false;
-        for (int j = 0; j < k; ++j)
-            if (!strcmp(names[j], names[k])) return vmd_fail("property '%s' already defined", names[k]);
-    }
-    if (P == 0) return vmd_fail("shape_weights population is empty");
-    if (!offs) return vmd_fail("shape_weights set has no context offsets");
-    if (offs[0] != 0) return vmd_fail("context offsets must start at 0");
-    for (size_t c = 0; c < P; ++c)
-        if (offs[c + 1] <= offs[c]) return vmd_fail("shape_weights context %zu has an empty set (offsets must increase)", c);
-    if (!idx_ok(idx, (size_t)offs[P], "shape_weights set")) return false;
-    for (int k = 0; k < 3; ++k) {
-        Property p;
-        p.name = names[k]; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-        p.dist_kind = GEOM_SHAPE; p.shape_comp = k;
-        p.a.assign(idx, idx + offs[P]); p.aoff.assign(offs, offs + P + 1);
-        ir->props.push_back(std::move(p));
-    }
-    ir->rebuild_names();
-    return true;
+    return names || vmd_fail("shape_weights needs three property names");
 }
 
 extern "C" bool vmd_ir_add_shape_weights(vmd_script_ir_t* ir, const char* const names[3], const int32_t* idx, size_t n) {
-    if (n > 0x7fffffff) return vmd_fail("shape_weights set too large");
-    const int32_t off[2] = {0, (int32_t)n};
-    return ir_add_shape(ir, names, 1, idx, off);
+    if (n > kMaxSet) return vmd_fail("shape_weights set too large");
+    return shape_names_ok(ir, names) && ir_add_sets_single(ir, Form::SHAPE, names, &idx, &n);
 }
 
 extern "C" bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const names[3], size_t P, const int32_t* idx,
                                                     const int32_t* offsets) {
-    return ir_add_shape(ir, names, P, idx, offsets);
-}
-
-// `name = rmsd(sel) [in <contexts>];`: one temporal property over a population of sets, validated like ir_add_geometry
-static bool ir_add_rmsd(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offs) {
-    if (!ir_name_ok(ir, name)) return false;
-    if (P == 0) return vmd_fail("rmsd population is empty");
-    if (!offs) return vmd_fail("rmsd set has no context offsets");
-    if (offs[0] != 0) return vmd_fail("context offsets must start at 0");
-    for (size_t c = 0; c < P; ++c)
-        if (offs[c + 1] <= offs[c]) return vmd_fail("rmsd context %zu has an empty set (offsets must increase)", c);
-    if (!idx_ok(idx, (size_t)offs[P], "rmsd set")) return false;
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-    p.dist_kind = GEOM_RMSD;
-    p.a.assign(idx, idx + offs[P]); p.aoff.assign(offs, offs + P + 1);
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return shape_names_ok(ir, names) && ir_add_sets(ir, Form::SHAPE, names, P, &idx, &offsets);
 }
 
 extern "C" bool vmd_ir_add_rmsd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n) {
-    if (n > 0x7fffffff) return vmd_fail("rmsd set too large");
-    const int32_t off[2] = {0, (int32_t)n};
-    return ir_add_rmsd(ir, name, 1, idx, off);
+    return ir_add_sets_single(ir, Form::RMSD, &name, &idx, &n);
 }
 
 extern "C" bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets) {
-    return ir_add_rmsd(ir, name, P, idx, offsets);
+    return ir_add_sets(ir, Form::RMSD, &name, P, &idx, &offsets);
 }
 
-// `name = rdf(T and within(a:b, R), target, {rmin, rmax});`: vmd_ir_add_rdf with either side a shell; the shells validated like
-// vmd_ir_add_within_count
+// `name = rdf(T and within(a:b, R), target, {rmin, rmax});`: vmd_ir_add_rdf with either side a shell
 extern "C" bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const vmd_shell_t* ref_shell,
                                      const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float rmin, float rmax) {
     if (!ref_shell && !target_shell) return vmd_ir_add_rdf(ir, name, ref, nref, target, ntarget, rmin, rmax);
-    if (!ir_name_ok(ir, name) || !idx_ok(ref, nref, "rdf reference set") || !idx_ok(target, ntarget, "rdf target set")) return false;
-    if (!(rmin >= 0.0f) || !(rmax > rmin)) return vmd_fail("rdf range must satisfy 0 <= rmin < rmax");
-    if (nref > 0x7fffffff || ntarget > 0x7fffffff) return vmd_fail("within set too large");
-    const vmd_shell_t* sh[2] = {ref_shell, target_shell};
-    for (const vmd_shell_t* h : sh) {
-        if (!h) continue;
-        if (!idx_ok(h->ref, h->nref, "within reference set")) return false;
-        if (h->nref > 0x7fffffff) return vmd_fail("within set too large");
-        if (!std::isfinite(h->rmin) || !std::isfinite(h->rmax) || !(h->rmin >= 0.0f) || !(h->rmax > h->rmin))
-            return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
-    }
     Property p;
-    p.name = name; p.kind = PROP_RDF; p.flags = VMD_PROPERTY_FLAG_DISTRIBUTION;
-    p.a.assign(ref, ref + nref); p.b.assign(target, target + ntarget);
-    p.rmin = rmin; p.rmax = rmax;
-    for (int k = 0; k < 2; ++k) {
-        if (!sh[k]) continue;
-        p.shell[k].on = true;
-        p.shell[k].ref.assign(sh[k]->ref, sh[k]->ref + sh[k]->nref);
-        p.shell[k].rmin = sh[k]->rmin; p.shell[k].rmax = sh[k]->rmax;
-    }
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    if (!rdf_head(p, ir, name, ref, nref, target, ntarget, rmin, rmax) || !set_size_ok({nref, ntarget})) return false;
+    const vmd_shell_t* sh[2] = {ref_shell, target_shell};
+    for (const vmd_shell_t* h : sh) if (h && !shell_ok(*h)) return false;
+    for (int k = 0; k < 2; ++k) if (sh[k]) shell_copy(p.shell[k], *sh[k]);
+    return commit(ir, &p);
 }
 
-// `name = sdf(structures, T and within(a:b, R), cutoff);`: vmd_ir_add_sdf with the target a shell, validated like
-// vmd_ir_add_within_count
+// `name = sdf(structures, T and within(a:b, R), cutoff);`: vmd_ir_add_sdf with the target a shell
 extern "C" bool vmd_ir_add_sdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
                                      const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float cutoff) {
     if (!target_shell) return vmd_ir_add_sdf(ir, name, structures, K, m, target, ntarget, cutoff);
-    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget,
-            "sdf target set")) return false;
-    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
-    const vmd_shell_t* h = target_shell;
-    if (!idx_ok(h->ref, h->nref, "within reference set")) return false;
-    if (ntarget > 0x7fffffff || h->nref > 0x7fffffff) return vmd_fail("within set too large");
-    if (!std::isfinite(h->rmin) || !std::isfinite(h->rmax) || !(h->rmin >= 0.0f) || !(h->rmax > h->rmin))
-        return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
     Property p;
-    p.name = name; p.kind = PROP_SDF; p.flags = VMD_PROPERTY_FLAG_VOLUME;
-    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
-    p.K = K; p.m = m; p.rmax = cutoff;
-    p.shell[1].on = true;
-    p.shell[1].ref.assign(h->ref, h->ref + h->nref);
-    p.shell[1].rmin = h->rmin; p.shell[1].rmax = h->rmax;
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    const vmd_shell_t& h = *target_shell;
+    // (the target's size is checked between the shell's list and the shell's size)
+    if (!sdf_head(p, ir, name, structures, K, m, target, ntarget, cutoff) || !idx_ok(h.ref, h.nref, "within reference set")
+        || !set_size_ok({ntarget, h.nref}) || !range_ok(Form::WITHIN, h.rmin, h.rmax)) return false;
+    shell_copy(p.shell[1], h);
+    return commit(ir, &p);
 }
 
-// `name = count(T and within(rmin:rmax, R));`: one temporal property, one value per frame; validated like ir_add_geometry
+// `name = count(T and within(rmin:rmax, R));`: one temporal property, one value per frame
 extern "C" bool vmd_ir_add_within_count(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
                                         const int32_t* ref, size_t nref, float rmin, float rmax) {
     if (!ir_name_ok(ir, name) || !idx_ok(target, ntarget, "within target set") || !idx_ok(ref, nref, "within reference set")) return false;
-    if (ntarget > 0x7fffffff || nref > 0x7fffffff) return vmd_fail("within set too large");
-    if (!std::isfinite(rmin) || !std::isfinite(rmax) || !(rmin >= 0.0f) || !(rmax > rmin))
-        return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-    p.dist_kind = GEOM_WITHIN;
+    if (!set_size_ok({ntarget, nref}) || !range_ok(Form::WITHIN, rmin, rmax)) return false;
+    Property p = make_property(Form::WITHIN, name);
     p.a.assign(target, target + ntarget); p.b.assign(ref, ref + nref);
     p.aoff = {0, (int32_t)ntarget}; p.boff = {0, (int32_t)nref};
     p.rmin = rmin; p.rmax = rmax;
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return commit(ir, &p);
 }
 
-// and / or / not over within() shells: the checks both entry points share; every term validated like vmd_ir_add_within_count
+// and / or / not over within() shells: the checks both entry points share
 static bool expr_ok(const vmd_shell_expr_t* x) {
     if (!x) return vmd_fail("shell expression is NULL");
     if (x->nterms < 1 || x->nterms > VMD_SHELL_EXPR_MAX_TERMS || !x->terms)
         return vmd_fail("shell expression needs 1 to %d terms, got %zu", VMD_SHELL_EXPR_MAX_TERMS, x->nterms);
     if (x->truth >> (1u << x->nterms)) return vmd_fail("shell expression truth table has bits above 2^%zu", x->nterms);
-    for (size_t i = 0; i < x->nterms; ++i) {
-        const vmd_shell_t& h = x->terms[i];
-        if (!idx_ok(h.ref, h.nref, "within reference set")) return false;
-        if (h.nref > 0x7fffffff) return vmd_fail("within set too large");
-        if (!std::isfinite(h.rmin) || !std::isfinite(h.rmax) || !(h.rmin >= 0.0f) || !(h.rmax > h.rmin))
-            return vmd_fail("within range must be finite and satisfy 0 <= rmin < rmax");
-    }
+    for (size_t i = 0; i < x->nterms; ++i) if (!shell_ok(x->terms[i])) return false;
     return true;
 }
 
 static void expr_copy(Property& p, const vmd_shell_expr_t* x) {
     p.expr_terms.resize(x->nterms);
-    for (size_t i = 0; i < x->nterms; ++i) {
-        p.expr_terms[i].ref.assign(x->terms[i].ref, x->terms[i].ref + x->terms[i].nref);
-        p.expr_terms[i].rmin = x->terms[i].rmin; p.expr_terms[i].rmax = x->terms[i].rmax;
-    }
+    for (size_t i = 0; i < x->nterms; ++i) shell_copy(p.expr_terms[i], x->terms[i]);
     p.expr_truth = x->truth;
 }
 
 // `name = count(T and <expression over within() terms>);`.  One term with truth 0b10 IS the one-term count
 extern "C" bool vmd_ir_add_within_count_expr(vmd_script_ir_t* ir, const char* name, const int32_t* target, size_t ntarget,
                                              const vmd_shell_expr_t* expr) {
-    if (!ir_name_ok(ir, name) || !idx_ok(target, ntarget, "within target set") || !expr_ok(expr)) return false;
-    if (ntarget > 0x7fffffff) return vmd_fail("within set too large");
+    if (!ir_name_ok(ir, name) || !idx_ok(target, ntarget, "within target set") || !expr_ok(expr) || !set_size_ok({ntarget})) return false;
     if (expr->nterms == 1 && expr->truth == 2u)
         return vmd_ir_add_within_count(ir, name, target, ntarget, expr->terms[0].ref, expr->terms[0].nref, expr->terms[0].rmin, expr->terms[0].rmax);
-    Property p;
-    p.name = name; p.kind = PROP_DIST; p.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-    p.dist_kind = GEOM_WITHIN_EXPR;
+    Property p = make_property(Form::WITHIN_EXPR, name);
     p.a.assign(target, target + ntarget);
     p.aoff = {0, (int32_t)ntarget}; p.boff = {0, 0};
     expr_copy(p, expr);
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return commit(ir, &p);
 }
 
 // `name = sdf(structures, T and <expression over within() terms>, cutoff);`.  One term with truth 0b10 IS vmd_ir_add_sdf_shell
 extern "C" bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name, const int32_t* structures, size_t K, size_t m,
                                           const int32_t* target, size_t ntarget, const vmd_shell_expr_t* expr, float cutoff) {
-    if (!ir_name_ok(ir, name) || !idx_ok(structures, K * m, "sdf reference structures") || !idx_ok(target, ntarget,
-            "sdf target set")) return false;
-    if (!(cutoff > 0.0f)) return vmd_fail("sdf cutoff must be positive");
-    if (!expr_ok(expr)) return false;
-    if (ntarget > 0x7fffffff) return vmd_fail("within set too large");
-    if (expr->nterms == 1 && expr->truth == 2u) return vmd_ir_add_sdf_shell(ir, name, structures, K, m, target, ntarget, &expr->terms[0], cutoff);
     Property p;
-    p.name = name; p.kind = PROP_SDF; p.flags = VMD_PROPERTY_FLAG_VOLUME;
-    p.a.assign(structures, structures + K * m); p.b.assign(target, target + ntarget);
-    p.K = K; p.m = m; p.rmax = cutoff;
+    if (!sdf_head(p, ir, name, structures, K, m, target, ntarget, cutoff) || !expr_ok(expr) || !set_size_ok({ntarget})) return false;
+    if (expr->nterms == 1 && expr->truth == 2u) return vmd_ir_add_sdf_shell(ir, name, structures, K, m, target, ntarget, &expr->terms[0], cutoff);
     expr_copy(p, expr);
-    ir->props.push_back(std::move(p));
-    ir->rebuild_names();
-    return true;
+    return commit(ir, &p);
 }
 
 // `{table, map} = ramachandran(backbone)`: the angle table and the density map, two descriptors in a row
 extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* bb) {
     if (!ir) return vmd_fail("ir is NULL");
     if (!names || !bb) return vmd_fail("ramachandran needs two property names and a backbone");
-    for (int k = 0; k < 2; ++k) if (!ir_name_ok(ir, names[k])) return false;
-    if (!strcmp(names[0], names[1])) return vmd_fail("property '%s' already defined", names[1]);
+    if (!names_ok(ir, names, 2)) return false;
     const size_t nseg = bb->num_segments;
     if (nseg == 0) return vmd_fail("ramachandran backbone has no segment");
     if (nseg > 0x3fffffff) return vmd_fail("ramachandran backbone too large");
@@ -404,9 +363,7 @@ extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const n
         for (size_t s = 0; s < nseg; ++s)
             if (bb->rama_class[s] > 3 && bb->rama_class[s] != 255)
                 return vmd_fail("backbone segment %zu has class %u (0..3 or 255)", s, (unsigned)bb->rama_class[s]);
-    Property t;
-    t.name = names[0]; t.kind = PROP_DIST; t.flags = VMD_PROPERTY_FLAG_TEMPORAL;
-    t.dist_kind = GEOM_RAMA;
+    Property t = make_property(Form::RAMA_TABLE, names[0]);
     t.a.assign(bb->n, bb->n + nseg); t.b.assign(bb->ca, bb->ca + nseg); t.c.assign(bb->c, bb->c + nseg);
     t.aoff.assign(bb->range_offsets, bb->range_offsets + bb->num_ranges + 1);
     if (bb->rama_class) t.rama_class.assign(bb->rama_class, bb->rama_class + nseg); else t.rama_class.assign(nseg, 0);
@@ -415,14 +372,18 @@ extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const n
         t.rama_link[bb->range_offsets[r]] &= (uint8_t)~1u;
         t.rama_link[bb->range_offsets[r + 1] - 1] &= (uint8_t)~2u;
     }
-    Property m;
-    m.name = names[1]; m.kind = PROP_RAMA; m.flags = VMD_PROPERTY_FLAG_MAP;
-    m.K = nseg;
-    ir->props.push_back(std::move(t));
-    ir->props.push_back(std::move(m));
-    ir->rebuild_names();
-    return true;
+    Property tm[2] = {std::move(t), make_property(Form::RAMA_MAP, names[1])};
+    tm[1].K = nseg;
+    return commit(ir, tm, 2);
 }
+
+// what vmd_ir_geometry_atoms has counted and written so far
+struct AtomSink {
+    int32_t* out; size_t cap, n = 0;
+    void put(int32_t i) { if (out && n < cap) out[n] = i; n += 1; }
+    void put(const std::vector<int32_t>& v) { for (int32_t i : v) put(i); }
+    void put(const std::vector<int32_t>& v, int32_t beg, int32_t end) { for (int32_t i = beg; i < end; ++i) put(v[(size_t)i]); }
+};
 
 // the atoms of an angle / dihedral property: every set of context `context` (all contexts when < 0), in argument order.  Returns the
 // count and writes up to `cap` of them; 0 for other properties (the shim's MD_SCRIPT_VISUALIZE_ATOMS payload)
@@ -430,43 +391,40 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
     if (!ir || !name) return 0;
     for (const Property& p : ir->props) {
         if (p.name != name) continue;
-        if (p.is_within()) {     // the static candidates: the reference set, then the target set (one context)
+        AtomSink s{out, cap};
+        // the contexts asked for, of `count`: [c0, c1), empty when there is no such context
+        auto contexts = [&](size_t count, size_t& c0, size_t& c1) {
+            c0 = context < 0 ? 0 : (size_t)context; c1 = context < 0 ? count : (size_t)context + 1;
+            return context < (int64_t)count;
+        };
+        size_t c0 = 0, c1 = 0;
+        switch (p.form) {
+        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: return 0;
+        case Form::WITHIN:          // the static candidates: the reference set, then the target set (one context)
             if (context > 0) return 0;
-            size_t n = 0;
-            for (const auto* v : {&p.b, &p.a}) for (int32_t i : *v) { if (out && n < cap) out[n] = i; n += 1; }
-            return n;
-        }
-        if (p.is_within_expr()) {     // every term's reference set in term order, then the target set (one context)
+            s.put(p.b); s.put(p.a);
+            return s.n;
+        case Form::WITHIN_EXPR:     // every term's reference set in term order, then the target set (one context)
             if (context > 0) return 0;
-            size_t n = 0;
-            for (auto& t : p.expr_terms) for (int32_t i : t.ref) { if (out && n < cap) out[n] = i; n += 1; }
-            for (int32_t i : p.a) { if (out && n < cap) out[n] = i; n += 1; }
-            return n;
+            for (auto& t : p.expr_terms) s.put(t.ref);
+            s.put(p.a);
+            return s.n;
+        case Form::RAMA_TABLE:      // N, CA, C of the segment(s)
+            if (!contexts(p.a.size(), c0, c1)) return 0;
+            for (size_t sg = c0; sg < c1; ++sg) for (const auto* v : {&p.a, &p.b, &p.c}) s.put((*v)[sg]);
+            return s.n;
+        case Form::SHAPE: case Form::RMSD:      // the set of the context(s)
+            if (!contexts(p.aoff.size() - 1, c0, c1)) return 0;
+            s.put(p.a, p.aoff[c0], p.aoff[c1]);
+            return s.n;
+        case Form::ANGLE: case Form::DIHEDRAL: {
+            if (!contexts(p.aoff.size() - 1, c0, c1)) return 0;
+            const std::vector<int32_t>* sets[4] = {&p.a, &p.b, &p.c, &p.d};
+            const std::vector<int32_t>* offs[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
+            for (size_t c = c0; c < c1; ++c) for (int k = 0; k < p.nargs(); ++k) s.put(*sets[k], (*offs[k])[c], (*offs[k])[c + 1]);
+            return s.n;
         }
-        if (p.is_rama()) {     // N, CA, C of the segment(s)
-            if (context >= (int64_t)p.a.size()) return 0;
-            const size_t s0 = context < 0 ? 0 : (size_t)context, s1 = context < 0 ? p.a.size() : (size_t)context + 1;
-            size_t n = 0;
-            for (size_t sg = s0; sg < s1; ++sg)
-                for (const auto* v : {&p.a, &p.b, &p.c}) { if (out && n < cap) out[n] = (*v)[sg]; n += 1; }
-            return n;
         }
-        if (p.kind != PROP_DIST || (p.nargs() < 3 && !p.is_shape() && !p.is_rmsd())) return 0;
-        const size_t P = p.aoff.size() - 1;
-        if (context >= (int64_t)P) return 0;
-        const size_t c0 = context < 0 ? 0 : (size_t)context, c1 = context < 0 ? P : (size_t)context + 1;
-        if (p.is_shape() || p.is_rmsd()) {     // shape_weights, rmsd: the set of the context(s)
-            size_t n = 0;
-            for (int32_t i = p.aoff[c0]; i < p.aoff[c1]; ++i) { if (out && n < cap) out[n] = p.a[(size_t)i]; n += 1; }
-            return n;
-        }
-        const std::vector<int32_t>* sets[4] = {&p.a, &p.b, &p.c, &p.d};
-        const std::vector<int32_t>* offs[4] = {&p.aoff, &p.boff, &p.coff, &p.doff};
-        size_t n = 0;
-        for (size_t c = c0; c < c1; ++c)
-            for (int k = 0; k < p.nargs(); ++k)
-                for (int32_t i = (*offs[k])[c]; i < (*offs[k])[c + 1]; ++i) { if (out && n < cap) out[n] = (*sets[k])[(size_t)i]; n += 1; }
-        return n;
     }
     return 0;
 }
@@ -479,18 +437,24 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
     if (cached) return cached;
     uint64_t h = 0xCBF29CE484222325ull;
     for (auto& p : ir->props) {
+        const uint32_t kind = (uint32_t)p.cls();      // what used to be the descriptor's kind (4 bytes, 0..3) and dist_kind (an int, 0..10)
+        const int geom = p.geom_code();
         h = fnv1a(h, p.name.data(), p.name.size());
-        h = fnv1a(h, &p.kind, sizeof(p.kind));
+        h = fnv1a(h, &kind, sizeof(kind));
         h = fnv1a(h, p.a.data(), p.a.size() * sizeof(int32_t));
         h = fnv1a(h, p.b.data(), p.b.size() * sizeof(int32_t));
         h = fnv1a(h, &p.rmin, sizeof(float)); h = fnv1a(h, &p.rmax, sizeof(float));
-        h = fnv1a(h, &p.K, sizeof(p.K)); h = fnv1a(h, &p.m, sizeof(p.m)); h = fnv1a(h, &p.dist_kind, sizeof(int));
+        h = fnv1a(h, &p.K, sizeof(p.K)); h = fnv1a(h, &p.m, sizeof(p.m)); h = fnv1a(h, &geom, sizeof(int));
         h = fnv1a(h, p.aoff.data(), p.aoff.size() * sizeof(int32_t)); h = fnv1a(h, p.boff.data(), p.boff.size() * sizeof(int32_t));
         // angle / dihedral only (empty otherwise: hashing no bytes leaves every earlier fingerprint as it was)
         h = fnv1a(h, p.c.data(), p.c.size() * sizeof(int32_t)); h = fnv1a(h, p.d.data(), p.d.size() * sizeof(int32_t));
         h = fnv1a(h, p.coff.data(), p.coff.size() * sizeof(int32_t)); h = fnv1a(h, p.doff.data(), p.doff.size() * sizeof(int32_t));
-        if (p.is_shape()) h = fnv1a(h, &p.shape_comp, sizeof(int));     // shape_weights only, as above
-        if (p.is_rama()) h = fnv1a(h, p.rama_class.data(), p.rama_class.size());     // ramachandran only, as above
+        switch (p.form) {     // what a form hashes of its own
+        case Form::SHAPE: h = fnv1a(h, &p.shape_comp, sizeof(int)); break;
+        case Form::RAMA_TABLE: h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); break;     // 
+        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
+        case Form::WITHIN_EXPR: case Form::RAMA_MAP: break;
+        }
         for (int k = 0; k < 2; ++k) {                                   // rdf / sdf over shells only, as above
             if (!p.shell[k].on) continue;
             const int32_t side = 0x5348454c + k;                        // "SHEL": which side carries the shell
@@ -520,6 +484,6 @@ extern "C" const char* const* vmd_ir_property_names(const vmd_script_ir_t* ir) {
 
 extern "C" vmd_property_flags_t vmd_ir_property_flags(const vmd_script_ir_t* ir, const char* name) {
     if (!ir || !name) return VMD_PROPERTY_FLAG_NONE;
-    for (auto& p : ir->props) if (p.name == name) return p.flags;
+    for (auto& p : ir->props) if (p.name == name) return p.flags();
     return VMD_PROPERTY_FLAG_NONE;
 }

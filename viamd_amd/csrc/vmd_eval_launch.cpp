@@ -464,7 +464,7 @@ bool RangeRun::launch_sdf(BatchCtx& c, PropState* p, const uint8_t* mask, size_t
 bool RangeRun::launch_shape(BatchCtx& c, size_t pi) {
     PropState* p = e->props[pi].get();
     if (p->prop.shape_comp != 0) return true;
-    if (pi + 2 >= e->props.size() || !e->props[pi + 1]->prop.is_shape() || !e->props[pi + 2]->prop.is_shape())
+    if (pi + 2 >= e->props.size() || e->props[pi + 1]->prop.form != Form::SHAPE || e->props[pi + 2]->prop.form != Form::SHAPE)
         return vmd_fail("shape_weights property '%s' has lost its companions", p->prop.name.c_str());
     PropState* p1 = e->props[pi + 1].get();
     PropState* p2 = e->props[pi + 2].get();
@@ -507,7 +507,7 @@ bool RangeRun::launch_geometry(BatchCtx& c, PropState* p) {
 // No cell grid, no overflow flag; a frame evaluated twice is counted twice, as an sdf volume counts it.
 bool RangeRun::launch_rama(BatchCtx& c, size_t pi) {
     PropState* p = e->props[pi].get();
-    if (pi + 1 >= e->props.size() || e->props[pi + 1]->prop.kind != PROP_RAMA)
+    if (pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::RAMA_MAP)
         return vmd_fail("ramachandran table '%s' has lost its map", p->prop.name.c_str());
     PropState* m = e->props[pi + 1].get();
     const size_t nseg = p->prop.a.size();
@@ -527,27 +527,32 @@ bool RangeRun::launch_rama(BatchCtx& c, size_t pi) {
 bool RangeRun::launch_distance(BatchCtx& c, PropState* p) {
     e->prof.begin("distance", e->stream);
     KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
-            p->prop.dist_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
+            p->prop.distance_kind, (int)p->dist_P, (int)p->dist_per, p->d_a.p, p->d_ma.p, p->d_aoff.p, p->d_b.p, p->d_mb.p, p->d_boff.p,
             p->d_out.p));
     e->prof.end(e->stream);
     return true;
 }
 
-// what property pi adds to the batch's queue outside launch_rdf, by kind.  The rows of a temporal kind are left in d_out.
+// what property pi adds to the batch's queue outside launch_rdf, by form.  The rows of a temporal form are left in d_out.
 bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     PropState* p = e->props[pi].get();
     const Property& d = p->prop;
-    // SPEC S4 normalisation, fp64 on the host (needs only the box).  An rdf over shells needs the populations too: its weights
-    // are formed in complete_batch, when they have arrived
-    if (d.kind == PROP_RDF) { if (!d.is_shell_rdf()) rdf_weights(c, p); return true; }
-    // sdf over a shell, within count: launched by launch_rdf, behind the batch's cell builds
-    if (d.is_shell_sdf() || d.is_within() || d.is_within_expr() || d.is_expr_sdf()) return true;     // (... and shell expressions)
-    if (d.kind == PROP_SDF) { VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0); }
-    // ramachandran: the table's launch also fills the map that follows it
-    if (d.kind == PROP_RAMA) return true;
-    if (d.is_rama()) return launch_rama(c, pi);
-    if (!p->d_out.ensure(c.nb * p->dim1)) return false;
-    if (d.is_shape()) return launch_shape(c, pi);
-    if (d.is_rmsd()) return launch_rmsd(c, p);
-    return d.nargs() > 2 ? launch_geometry(c, p) : launch_distance(c, p);
+    if (d.behind_cells()) {     // launched by launch_rdf: rdfs, within counts, everything over a shell or an expression (1.8, 1.9)
+        // SPEC S4 normalisation, fp64 on the host (needs only the box).  An rdf over shells needs the populations too: its weights
+        // are formed in complete_batch, when they have arrived
+        if (d.form == Form::RDF && !d.is_shell_rdf()) rdf_weights(c, p);
+        return true;
+    }
+    if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
+    switch (d.form) {
+    case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: return true;     // (behind the cell builds, above)
+    case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
+    case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
+    case Form::RAMA_TABLE: return launch_rama(c, pi);
+    case Form::SHAPE: return launch_shape(c, pi);
+    case Form::RMSD: return launch_rmsd(c, p);
+    case Form::ANGLE: case Form::DIHEDRAL: return launch_geometry(c, p);
+    case Form::DISTANCE: return launch_distance(c, p);
+    }
+    return vmd_fail("property '%s' has no form", d.name.c_str());
 }

@@ -7,7 +7,7 @@
 bool RangeRun::prepare_reference_poses() {
     // SDF reference pose: structure 0 at trajectory frame 0 (SPEC S5)
     for (auto& p : e->props) {
-        if (p->prop.kind != PROP_SDF || p->ref_pose_ready) continue;
+        if (p->prop.form != Form::SDF || p->ref_pose_ready) continue;
         BatchSrc src;
         if (!fetch_batch(e, traj, view_holds(have_view, view, 0) ? &view : nullptr, num_atoms, 0, 1, &src)) return false;
         KRN_OK(vmd_hip_sdf_ref_pose(e->stream, src.base, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), p->d_structs.p,
@@ -20,7 +20,7 @@ bool RangeRun::prepare_reference_poses() {
     // rmsd reference pose: every context's set at trajectory frame 0.  It belongs to (evaluator, trajectory): rebuilt when
     // this call's trajectory is not the one it was built for
     for (auto& p : e->props) {
-        if (!p->prop.is_rmsd()) continue;
+        if (p->prop.form != Form::RMSD) continue;
         const TrajId now = traj_id(traj);
         if (p->rmsd_pose_ready && p->rmsd_pose_inst == now.inst && p->rmsd_pose_fn == now.fn) continue;
         BatchSrc src;
@@ -131,7 +131,7 @@ void RangeRun::plan_range(const std::vector<std::pair<size_t, size_t>>& segments
     // Evals that keep block partials complete every batch before the next is queued.
     defer = g_opt.defer_sync.load() != 0 && e->block_frames == 0 && batches.size() > 1;
     rdf_counts = 0;
-    for (auto& p : e->props) if (p->prop.kind == PROP_RDF) rdf_counts += p->ncounts;
+    for (auto& p : e->props) if (p->prop.cls() == ResultClass::DISTRIBUTION) rdf_counts += p->ncounts;
 }
 
 // SPEC S4 normalisation of one RDF property over the frames of a batch, fp64 on the host
@@ -239,7 +239,7 @@ bool RangeRun::complete_batch(BatchCtx& c, BatchCtx* later) {
     if (g_prof_on) { std::lock_guard<std::mutex> l(g_prof_mtx); g_prof["batches"].launches += 1; }
     for (size_t pi = 0; pi < e->props.size(); ++pi) {
         PropState* p = e->props[pi].get();
-        if (p->prop.kind != PROP_DIST) continue;
+        if (!p->prop.temporal()) continue;
         // evaluated ahead: the rows wait beside the view until their block is committed (a reader of the values array never sees a
         // frame nobody asked for)
         if (spec && p->ahead_values.size() != p->values.size()) p->ahead_values.assign(p->values.size(), 0.0f);
@@ -255,7 +255,7 @@ bool RangeRun::complete_batch(BatchCtx& c, BatchCtx* later) {
     // is queued behind this batch, from the snapshot taken behind its commits otherwise
     size_t soff = (size_t)c.slot * rdf_counts;
     for (auto& p : e->props) {
-        if (p->prop.kind != PROP_RDF) continue;
+        if (p->prop.cls() != ResultClass::DISTRIBUTION) continue;
         // (an rdf over shells has its weights up to THIS batch in weights64: the batch behind adds its own at its completion)
         if (behind && c.snapshot && !repeated && !(later && later->poisoned)) refresh_distribution_from(p.get(), e->h_snap + soff,
                 p->prop.is_shell_rdf() ? p->weights64.data() : e->w_snap.data() + soff);
@@ -263,6 +263,17 @@ bool RangeRun::complete_batch(BatchCtx& c, BatchCtx* later) {
         soff += p->ncounts;
     }
     return true;
+}
+
+// where launch_property has left the batch's rows of a property on the device (NULL: it has none to send from here)
+static const float* batch_rows(const PropState* p, size_t f0) {
+    switch (p->prop.form) {
+    // accumulators, no rows; a within count's rows are sent by launch_rdf, behind the overflow flag
+    case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::WITHIN: case Form::WITHIN_EXPR: return nullptr;
+    case Form::RAMA_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
+    case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: return p->d_out.p;
+    }
+    return nullptr;
 }
 
 // queues batch bi behind whatever is in flight, completes the batch in front of it (deferred) or itself, and stages later batches
@@ -284,7 +295,7 @@ bool RangeRun::queue_batch(size_t bi) {
     size_t temporal_floats = 0;
     c.toff.assign(e->props.size(), 0);
     for (size_t pi = 0; pi < e->props.size(); ++pi) {
-        if (e->props[pi]->prop.kind != PROP_DIST) continue;
+        if (!e->props[pi]->prop.temporal()) continue;
         c.toff[pi] = temporal_floats;
         temporal_floats += c.nb * e->props[pi]->dim1;
     }
@@ -310,10 +321,9 @@ bool RangeRun::queue_batch(size_t bi) {
     for (size_t pi = 0; pi < e->props.size(); ++pi) {
         PropState* p = e->props[pi].get();
         if (!launch_property(c, pi)) return false;
-        // (a within count's rows are sent by launch_rdf, behind the overflow flag)
-        if (p->prop.kind == PROP_DIST && !p->prop.is_within() && !p->prop.is_within_expr())
-            HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], p->prop.is_rama() ? p->d_table.p + c.f0 * p->dim1
-                    : p->d_out.p, c.nb * p->dim1 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        if (const float* rows = batch_rows(p, c.f0))
+            HIP_OK(hipMemcpyAsync(e->h_temporal_slot[c.slot].data() + c.toff[pi], rows, c.nb * p->dim1 * sizeof(float), hipMemcpyDeviceToHost,
+                    e->stream));
         p->dirty = p->dirty || !spec;
     }
     if (defer) {
@@ -321,7 +331,7 @@ bool RangeRun::queue_batch(size_t bi) {
         // commits (the weights as they stand now), and an event to wait on
         size_t soff = (size_t)c.slot * rdf_counts;
         for (auto& p : e->props) {
-            if (p->prop.kind != PROP_RDF) continue;
+            if (p->prop.cls() != ResultClass::DISTRIBUTION) continue;
             HIP_OK(hipMemcpyAsync(e->h_snap + soff, p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
             memcpy(e->w_snap.data() + soff, p->weights64.data(), p->ncounts * sizeof(double));
             soff += p->ncounts;
@@ -442,8 +452,7 @@ bool process_range_locked(vmd_script_eval_t* eval, const vmd_system_t* sys, vmd_
     if (views) {
         for (auto& p : e->props) {
             if (!p->dirty) continue;
-            if (p->prop.kind == PROP_SDF || p->prop.kind == PROP_RAMA) { if (!refresh_volume(e, p.get())) return false; }
-            else if (p->prop.kind == PROP_DIST) refresh_temporal_stats(e, p.get());
+            if (p->prop.cls() != ResultClass::DISTRIBUTION && !refresh_view(e, p.get())) return false;     // (a distribution: per batch)
         }
         e->views_at = std::chrono::steady_clock::now();
     }
