@@ -2705,6 +2705,119 @@ __device__ __forceinline__ bool vmd_sdf_near(const vmd_scatter_params_t& p, cons
 // instead of two (the kernel is bound by the latency of its loads under load: a wave used to live ~12 us).
 // ILP atoms per thread: all their gathers are in flight at once.
 #define VMD_SDF_CAP 512      // survivors of the group test a block holds in LDS at a time (~1 % of its atoms pass; more take another round)
+
+// The pieces the list kernels share.  The register set of a thread: ILP targets of frame b.
+template <int ILP>
+struct vmd_sdf_tile_t { int b; int idx[ILP], own[ILP]; float x[ILP], y[ILP], z[ILP]; };
+
+// index and owner of the target slots t0 + STEP * u, then the gathers of all of them (nt: as non-temporal loads)
+template <int ILP, bool ARITH, int STEP>
+__device__ __forceinline__ void vmd_sdf_targets(const vmd_scatter_params_t& p, int b, int t0, bool nt, vmd_sdf_tile_t<ILP>& T) {
+    T.b = b;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) {
+        const int t = t0 + STEP * u;
+        T.idx[u] = -1; T.own[u] = p.unowned ? -1 : -2;
+        if (t < p.ntgt) {
+            T.idx[u] = ARITH ? p.tgt_first + t * p.tgt_stride : (p.tgt ? p.tgt[t] : t);
+            if (!p.unowned && p.owner) T.own[u] = (int)p.owner[t];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) {
+        T.x[u] = T.y[u] = T.z[u] = 0.0f;
+        if (T.idx[u] >= 0) {
+            if (nt) {
+                T.x[u] = VMD_LOAD_NT(fx + T.idx[u]); T.y[u] = VMD_LOAD_NT(fx + p.row_stride + T.idx[u]); T.z[u] = VMD_LOAD_NT(fx + 2 * p.row_stride + T.idx[u]);
+            } else {
+                T.x[u] = fx[T.idx[u]]; T.y[u] = fx[p.row_stride + T.idx[u]]; T.z[u] = fx[2 * p.row_stride + T.idx[u]];
+            }
+        }
+    }
+}
+
+// bit u: target u of the tile passed the group test
+template <int ILP>
+__device__ __forceinline__ unsigned vmd_sdf_near_mask(const vmd_scatter_params_t& p, const vmd_box_t& bx, const vmd_sdf_tile_t<ILP>& T) {
+    unsigned pending = 0u;
+#pragma unroll
+    for (int u = 0; u < ILP; ++u) if (T.idx[u] >= 0 && vmd_sdf_near(p, bx, T.b, T.x[u], T.y[u], T.z[u])) pending |= 1u << u;
+    return pending;
+}
+
+// the survivors of one round in LDS: CAP = VMD_SDF_CAP per block, VMD_WAVE per wave
+template <int CAP>
+struct vmd_sdf_stack_t {
+    float x[CAP], y[CAP], z[CAP]; int own[CAP], idx[CAP];
+    __device__ __forceinline__ void put(unsigned slot, float px, float py, float pz, int o, int i) {
+        x[slot] = px; y[slot] = py; z[slot] = pz; own[slot] = o; idx[slot] = i;
+    }
+};
+
+// the (survivor, structure) pairs of a stack that holds min(n, CAP) atoms, dealt evenly to nthreads threads
+template <int CAP>
+__device__ __forceinline__ void vmd_sdf_stack_run(const vmd_scatter_params_t& p, const vmd_box_t& bx, int b, const vmd_sdf_stack_t<CAP>& S,
+                                                  unsigned n, int tid, int nthreads) {
+    const int nwork = (int)(n < (unsigned)CAP ? n : (unsigned)CAP) * p.K;
+    for (int w = tid; w < nwork; w += nthreads) {
+        const int a = w / p.K, k = w - a * p.K;
+        vmd_sdf_atom_k(p, bx, b, k, S.x[a], S.y[a], S.z[a], S.own[a], S.idx[a]);
+    }
+}
+
+// per-BLOCK rounds over the NBIT bits of `pending`: every set bit takes a slot (put(bit, slot) fills it from the thread's registers),
+// the block runs the stack, and whoever found it full comes back for the next round
+template <int NBIT, class PUT>
+__device__ __forceinline__ void vmd_sdf_block_rounds(const vmd_scatter_params_t& p, const vmd_box_t& bx, int b, unsigned pending,
+                                                     const vmd_sdf_stack_t<VMD_SDF_CAP>& S, unsigned& s_n, PUT put) {
+    for (;;) {
+        __syncthreads();
+        if (threadIdx.x == 0) s_n = 0u;
+        __syncthreads();
+#pragma unroll
+        for (int bit = 0; bit < NBIT; ++bit) {
+            if (pending & (1u << bit)) {
+                const unsigned slot = atomicAdd(&s_n, 1u);
+                if (slot < VMD_SDF_CAP) { put(bit, slot); pending &= ~(1u << bit); }
+            }
+        }
+        __syncthreads();
+        const unsigned total = s_n;
+        vmd_sdf_stack_run(p, bx, b, S, total, (int)threadIdx.x, 256);
+        if (total <= VMD_SDF_CAP) break;      // block-uniform: everybody read the same s_n
+    }
+}
+
+// per-WAVE rounds (ballot + prefix, 64 slots): no block barrier
+template <int ILP>
+__device__ __forceinline__ void vmd_sdf_wave_rounds(const vmd_scatter_params_t& p, const vmd_box_t& bx, const vmd_sdf_tile_t<ILP>& T,
+                                                    unsigned pending, int lane, vmd_sdf_stack_t<VMD_WAVE>& S) {
+    for (;;) {
+        unsigned base = 0u;                                   // wave-uniform: survivors placed in this round
+        bool left = false;
+#pragma unroll
+        for (int u = 0; u < ILP; ++u) {
+            const bool hit = (pending >> u) & 1u;
+            const unsigned long long m = VMD_BALLOT(hit);
+            if (m == 0ull) continue;
+            const unsigned pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            const unsigned slot = base + pre;
+            if (hit && slot < (unsigned)VMD_WAVE) {
+                S.put(slot, T.x[u], T.y[u], T.z[u], T.own[u], T.idx[u]);
+                pending &= ~(1u << u);
+            }
+            base += (unsigned)__popcll(m);
+            if (base > (unsigned)VMD_WAVE) left = true;
+        }
+        if (base == 0u) break;
+        __builtin_amdgcn_wave_barrier();
+        vmd_sdf_stack_run(p, bx, T.b, S, base, lane, VMD_WAVE);
+        __builtin_amdgcn_wave_barrier();
+        if (!left) break;                                     // wave-uniform
+    }
+}
+
 // MASKED: the target is a within() shell.  mask is u8[B][mask_stride] indexed by ATOM (k_within_atoms, or k_within_brute<true, true>);
 // a target whose byte of frame b is 0 drops out where the group pre-filter drops atoms - everything behind that (D-SDF-EXCL by atom identity,
 // the S5 arithmetic, the u64 voxel atomics) is the static path.  The mask hangs on a cell build, so this instantiation alone tests the batch's
@@ -2715,66 +2828,19 @@ template <> struct vmd_scatter_arg<true> { typedef vmd_scatter_masked_params_t t
 template <int ILP, bool ARITH, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_sdf_scatter(typename vmd_scatter_arg<MASKED>::type p) {
     if constexpr (MASKED) { if (p.skip && *p.skip) return; }
-    __shared__ float s_x[VMD_SDF_CAP], s_y[VMD_SDF_CAP], s_z[VMD_SDF_CAP];
-    __shared__ int s_own[VMD_SDF_CAP], s_idx[VMD_SDF_CAP];
+    __shared__ vmd_sdf_stack_t<VMD_SDF_CAP> S;
     __shared__ unsigned s_n;
-    const int t0 = blockIdx.x * (256 * ILP) + threadIdx.x;
     const int b = blockIdx.y;
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    int idx[ILP], own[ILP];
-    float x[ILP], y[ILP], z[ILP];
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        const int t = t0 + 256 * u;
-        idx[u] = -1; own[u] = p.unowned ? -1 : -2;
-        if (t < p.ntgt) {
-            idx[u] = ARITH ? p.tgt_first + t * p.tgt_stride : (p.tgt ? p.tgt[t] : t);
-            if (!p.unowned && p.owner) own[u] = (int)p.owner[t];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        x[u] = y[u] = z[u] = 0.0f;
-        if (idx[u] >= 0) {
-            if (p.nt) {
-                x[u] = VMD_LOAD_NT(fx + idx[u]); y[u] = VMD_LOAD_NT(fx + p.row_stride + idx[u]); z[u] = VMD_LOAD_NT(fx + 2 * p.row_stride + idx[u]);
-            } else {
-                x[u] = fx[idx[u]]; y[u] = fx[p.row_stride + idx[u]]; z[u] = fx[2 * p.row_stride + idx[u]];
-            }
-        }
-    }
-    unsigned pending = 0u;
+    vmd_sdf_tile_t<ILP> T;
+    vmd_sdf_targets<ILP, ARITH, 256>(p, b, blockIdx.x * (256 * ILP) + threadIdx.x, p.nt != 0, T);
     if constexpr (MASKED) {
         const unsigned char* mk = p.mask + (size_t)b * p.mask_stride;
 #pragma unroll
-        for (int u = 0; u < ILP; ++u) if (idx[u] >= 0 && mk[idx[u]] == 0) idx[u] = -1;
+        for (int u = 0; u < ILP; ++u) if (T.idx[u] >= 0 && mk[T.idx[u]] == 0) T.idx[u] = -1;
     }
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) if (idx[u] >= 0 && vmd_sdf_near(p, bx, b, x[u], y[u], z[u])) pending |= 1u << u;
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_n = 0u;
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < ILP; ++u) {
-            if (pending & (1u << u)) {
-                const unsigned slot = atomicAdd(&s_n, 1u);
-                if (slot < VMD_SDF_CAP) {
-                    s_x[slot] = x[u]; s_y[slot] = y[u]; s_z[slot] = z[u]; s_own[slot] = own[u]; s_idx[slot] = idx[u];
-                    pending &= ~(1u << u);
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned total = s_n;
-        const int nwork = (int)(total < VMD_SDF_CAP ? total : VMD_SDF_CAP) * p.K;
-        for (int w = threadIdx.x; w < nwork; w += 256) {
-            const int a = w / p.K, k = w - a * p.K;
-            vmd_sdf_atom_k(p, bx, b, k, s_x[a], s_y[a], s_z[a], s_own[a], s_idx[a]);
-        }
-        if (total <= VMD_SDF_CAP) break;      // block-uniform: everybody read the same s_n
-    }
+    vmd_sdf_block_rounds<ILP>(p, bx, b, vmd_sdf_near_mask<ILP>(p, bx, T), S, s_n,
+                              [&](int u, unsigned slot) { S.put(slot, T.x[u], T.y[u], T.z[u], T.own[u], T.idx[u]); });
 }
 
 // Wave-level variant (A/B, `sdf_wave`): the survivors of the group test are compacted per WAVE (ballot + prefix, 64 slots of LDS per
@@ -2782,59 +2848,13 @@ __global__ __launch_bounds__(256) void k_sdf_scatter(typename vmd_scatter_arg<MA
 // (most of them: ~1 % of the atoms pass) retires as soon as its loads are tested.
 template <int ILP, bool ARITH>
 __global__ __launch_bounds__(256) void k_sdf_scatter_wave(vmd_scatter_params_t p) {
-    __shared__ float s_x[4][VMD_WAVE], s_y[4][VMD_WAVE], s_z[4][VMD_WAVE];
-    __shared__ int s_own[4][VMD_WAVE], s_idx[4][VMD_WAVE];
+    __shared__ vmd_sdf_stack_t<VMD_WAVE> S[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int t0 = blockIdx.x * (256 * ILP) + wave * (VMD_WAVE * ILP) + lane;      // a wave owns 64 * ILP consecutive targets
     const int b = blockIdx.y;
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    int idx[ILP], own[ILP];
-    float x[ILP], y[ILP], z[ILP];
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        const int t = t0 + VMD_WAVE * u;
-        idx[u] = -1; own[u] = p.unowned ? -1 : -2;
-        if (t < p.ntgt) {
-            idx[u] = ARITH ? p.tgt_first + t * p.tgt_stride : (p.tgt ? p.tgt[t] : t);
-            if (!p.unowned && p.owner) own[u] = (int)p.owner[t];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        x[u] = y[u] = z[u] = 0.0f;
-        if (idx[u] >= 0) { x[u] = fx[idx[u]]; y[u] = fx[p.row_stride + idx[u]]; z[u] = fx[2 * p.row_stride + idx[u]]; }
-    }
-    unsigned pending = 0u;
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) if (idx[u] >= 0 && vmd_sdf_near(p, bx, b, x[u], y[u], z[u])) pending |= 1u << u;
-    for (;;) {
-        unsigned base = 0u;                                   // wave-uniform: survivors placed in this round
-        bool left = false;
-#pragma unroll
-        for (int u = 0; u < ILP; ++u) {
-            const bool hit = (pending >> u) & 1u;
-            const unsigned long long m = VMD_BALLOT(hit);
-            if (m == 0ull) continue;
-            const unsigned pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            const unsigned slot = base + pre;
-            if (hit && slot < (unsigned)VMD_WAVE) {
-                s_x[wave][slot] = x[u]; s_y[wave][slot] = y[u]; s_z[wave][slot] = z[u]; s_own[wave][slot] = own[u]; s_idx[wave][slot] = idx[u];
-                pending &= ~(1u << u);
-            }
-            base += (unsigned)__popcll(m);
-            if (base > (unsigned)VMD_WAVE) left = true;
-        }
-        if (base == 0u) break;
-        __builtin_amdgcn_wave_barrier();
-        const int nwork = (int)(base < (unsigned)VMD_WAVE ? base : (unsigned)VMD_WAVE) * p.K;
-        for (int w = lane; w < nwork; w += VMD_WAVE) {
-            const int a = w / p.K, k = w - a * p.K;
-            vmd_sdf_atom_k(p, bx, b, k, s_x[wave][a], s_y[wave][a], s_z[wave][a], s_own[wave][a], s_idx[wave][a]);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (!left) break;                                     // wave-uniform
-    }
+    vmd_sdf_tile_t<ILP> T;
+    vmd_sdf_targets<ILP, ARITH, VMD_WAVE>(p, b, blockIdx.x * (256 * ILP) + wave * (VMD_WAVE * ILP) + lane, false, T);      // a wave owns 64 * ILP consecutive targets
+    vmd_sdf_wave_rounds<ILP>(p, bx, T, vmd_sdf_near_mask<ILP>(p, bx, T), lane, S[wave]);
 }
 
 // Streaming variant (`sdf_wave` = 2): the one-shot kernels above retire a block after ~12 KB of gathers and pay the launch of its
@@ -2843,73 +2863,24 @@ __global__ __launch_bounds__(256) void k_sdf_scatter_wave(vmd_scatter_params_t p
 // (consecutive waves on consecutive tiles, so the grid reads one moving window of the trajectory) and issues the gathers of its NEXT
 // tile before it tests the current one - two register sets, the wave always has a tile in flight.  Survivors of the group test
 // are compacted per wave as in k_sdf_scatter_wave (no block barrier).  Same arithmetic, same result.
-template <int ILP>
-struct vmd_sdf_tile_t { int b; int idx[ILP], own[ILP]; float x[ILP], y[ILP], z[ILP]; };
-
 template <int ILP, bool ARITH>
 __device__ __forceinline__ void vmd_sdf_tile_load(const vmd_scatter_params_t& p, long long tile, int tiles_per_frame, int lane, vmd_sdf_tile_t<ILP>& T) {
-    T.b = (int)(tile / tiles_per_frame);
-    const int c = (int)(tile - (long long)T.b * tiles_per_frame);
-    const float* fx = p.xyz + (size_t)T.b * p.frame_stride;
-    const int t0 = c * (VMD_WAVE * ILP) + lane;
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        const int t = t0 + VMD_WAVE * u;
-        T.idx[u] = -1; T.own[u] = p.unowned ? -1 : -2;
-        if (t < p.ntgt) {
-            T.idx[u] = ARITH ? p.tgt_first + t * p.tgt_stride : (p.tgt ? p.tgt[t] : t);
-            if (!p.unowned && p.owner) T.own[u] = (int)p.owner[t];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) {
-        T.x[u] = T.y[u] = T.z[u] = 0.0f;
-        if (T.idx[u] >= 0) { T.x[u] = fx[T.idx[u]]; T.y[u] = fx[p.row_stride + T.idx[u]]; T.z[u] = fx[2 * p.row_stride + T.idx[u]]; }
-    }
+    const int b = (int)(tile / tiles_per_frame);
+    const int c = (int)(tile - (long long)b * tiles_per_frame);
+    vmd_sdf_targets<ILP, ARITH, VMD_WAVE>(p, b, c * (VMD_WAVE * ILP) + lane, false, T);
 }
 
 template <int ILP>
-__device__ __forceinline__ void vmd_sdf_tile_scatter(const vmd_scatter_params_t& p, const vmd_sdf_tile_t<ILP>& T, int lane,
-                                                     float* s_x, float* s_y, float* s_z, int* s_own, int* s_idx) {
-    const int b = T.b;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
-    unsigned pending = 0u;
-#pragma unroll
-    for (int u = 0; u < ILP; ++u) if (T.idx[u] >= 0 && vmd_sdf_near(p, bx, b, T.x[u], T.y[u], T.z[u])) pending |= 1u << u;
+__device__ __forceinline__ void vmd_sdf_tile_scatter(const vmd_scatter_params_t& p, const vmd_sdf_tile_t<ILP>& T, int lane, vmd_sdf_stack_t<VMD_WAVE>& S) {
+    const vmd_box_t bx = vmd_load_box(p.boxes, T.b, p.pbc);
+    const unsigned pending = vmd_sdf_near_mask<ILP>(p, bx, T);
     if (VMD_BALLOT(pending != 0u) == 0ull) return;          // ~99 % of the atoms fail the group test: most tiles end here
-    for (;;) {
-        unsigned base = 0u;                                   // wave-uniform: survivors placed in this round
-        bool left = false;
-#pragma unroll
-        for (int u = 0; u < ILP; ++u) {
-            const bool hit = (pending >> u) & 1u;
-            const unsigned long long m = VMD_BALLOT(hit);
-            if (m == 0ull) continue;
-            const unsigned pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            const unsigned slot = base + pre;
-            if (hit && slot < (unsigned)VMD_WAVE) {
-                s_x[slot] = T.x[u]; s_y[slot] = T.y[u]; s_z[slot] = T.z[u]; s_own[slot] = T.own[u]; s_idx[slot] = T.idx[u];
-                pending &= ~(1u << u);
-            }
-            base += (unsigned)__popcll(m);
-            if (base > (unsigned)VMD_WAVE) left = true;
-        }
-        if (base == 0u) break;
-        __builtin_amdgcn_wave_barrier();
-        const int nwork = (int)(base < (unsigned)VMD_WAVE ? base : (unsigned)VMD_WAVE) * p.K;
-        for (int w = lane; w < nwork; w += VMD_WAVE) {
-            const int a = w / p.K, k = w - a * p.K;
-            vmd_sdf_atom_k(p, bx, b, k, s_x[a], s_y[a], s_z[a], s_own[a], s_idx[a]);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (!left) break;                                     // wave-uniform
-    }
+    vmd_sdf_wave_rounds<ILP>(p, bx, T, pending, lane, S);
 }
 
 template <int ILP, bool ARITH>
 __global__ __launch_bounds__(256) void k_sdf_scatter_stream(vmd_scatter_params_t p, int tiles_per_frame) {
-    __shared__ float s_x[4][VMD_WAVE], s_y[4][VMD_WAVE], s_z[4][VMD_WAVE];
-    __shared__ int s_own[4][VMD_WAVE], s_idx[4][VMD_WAVE];
+    __shared__ vmd_sdf_stack_t<VMD_WAVE> S[4];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const long long W = (long long)gridDim.x * 4;
@@ -2921,12 +2892,12 @@ __global__ __launch_bounds__(256) void k_sdf_scatter_stream(vmd_scatter_params_t
     for (;;) {
         const bool more1 = tile + W < ntiles;                 // wave-uniform
         if (more1) vmd_sdf_tile_load<ILP, ARITH>(p, tile + W, tiles_per_frame, lane, B2);
-        vmd_sdf_tile_scatter<ILP>(p, A, lane, s_x[wave], s_y[wave], s_z[wave], s_own[wave], s_idx[wave]);
+        vmd_sdf_tile_scatter<ILP>(p, A, lane, S[wave]);
         if (!more1) break;
         tile += W;
         const bool more2 = tile + W < ntiles;
         if (more2) vmd_sdf_tile_load<ILP, ARITH>(p, tile + W, tiles_per_frame, lane, A);
-        vmd_sdf_tile_scatter<ILP>(p, B2, lane, s_x[wave], s_y[wave], s_z[wave], s_own[wave], s_idx[wave]);
+        vmd_sdf_tile_scatter<ILP>(p, B2, lane, S[wave]);
         if (!more2) break;
         tile += W;
     }
@@ -2939,8 +2910,7 @@ __global__ __launch_bounds__(256) void k_sdf_scatter_stream(vmd_scatter_params_t
 // test go through the same bounded LDS compaction and K-structure loop as in k_sdf_scatter; same arithmetic, same result.
 template <int GPT>
 __global__ __launch_bounds__(256) void k_sdf_scatter_rows(vmd_scatter_params_t p, int g_first, int ngroups) {
-    __shared__ float s_x[VMD_SDF_CAP], s_y[VMD_SDF_CAP], s_z[VMD_SDF_CAP];
-    __shared__ int s_own[VMD_SDF_CAP], s_idx[VMD_SDF_CAP];
+    __shared__ vmd_sdf_stack_t<VMD_SDF_CAP> S;
     __shared__ unsigned s_n;
     const int b = blockIdx.y;
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
@@ -2974,34 +2944,10 @@ __global__ __launch_bounds__(256) void k_sdf_scatter_rows(vmd_scatter_params_t p
             k0 += s;
         }
     }
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_n = 0u;
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < GPT; ++u) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (pending & (1u << (4 * u + k))) {
-                    const unsigned slot = atomicAdd(&s_n, 1u);
-                    if (slot < VMD_SDF_CAP) {
-                        const int idx = a0[u] + k;
-                        s_x[slot] = x4[u][k]; s_y[slot] = y4[u][k]; s_z[slot] = z4[u][k]; s_idx[slot] = idx;
-                        s_own[slot] = p.unowned ? -1 : (p.owner ? (int)p.owner[(idx - first) / s] : -2);
-                        pending &= ~(1u << (4 * u + k));
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned total = s_n;
-        const int nwork = (int)(total < VMD_SDF_CAP ? total : VMD_SDF_CAP) * p.K;
-        for (int w = threadIdx.x; w < nwork; w += 256) {
-            const int a = w / p.K, k = w - a * p.K;
-            vmd_sdf_atom_k(p, bx, b, k, s_x[a], s_y[a], s_z[a], s_own[a], s_idx[a]);
-        }
-        if (total <= VMD_SDF_CAP) break;
-    }
+    vmd_sdf_block_rounds<4 * GPT>(p, bx, b, pending, S, s_n, [&](int bit, unsigned slot) {
+        const int u = bit >> 2, k = bit & 3, idx = a0[u] + k;
+        S.put(slot, x4[u][k], y4[u][k], z4[u][k], p.unowned ? -1 : (p.owner ? (int)p.owner[(idx - first) / s] : -2), idx);
+    });
 }
 
 // dense targets (a sizeable fraction of all atoms, e.g. every water oxygen): stream the WHOLE frame with 16-byte loads per
@@ -4333,6 +4279,34 @@ static int g_sdf_wave = 0;      // 1: per-wave instead of per-block compaction o
 extern "C" int vmd_hip_set_sdf_wave(int on) { const int old = g_sdf_wave; g_sdf_wave = on < 0 ? 0 : (on > 65535 ? 65535 : on); return old; }
 static int g_sdf_ilp = 4;
 extern "C" int vmd_hip_set_sdf_ilp(int n) { const int old = g_sdf_ilp; if (n == 4 || n == 8 || n == 16) g_sdf_ilp = n; return old; }
+
+#include <type_traits>
+static vmd_scatter_params_t vmd_sdf_params(const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags, int B,
+                                           const int32_t* structs, int K, int m, const float* R32, const float* c32,
+                                           const int32_t* tgt, const int8_t* owner, int ntgt, float extent, int dim, uint64_t* volume,
+                                           const float* group, int tgt_first, int tgt_stride, int unowned) {
+    return vmd_scatter_params_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt, extent, dim,
+                                (unsigned long long*)volume, group, tgt_first, tgt_stride, unowned, g_sdf_nt};
+}
+
+// (sdf_ilp, arith) -> template arguments: f(std::integral_constant<int, ILP>, std::bool_constant<ARITH>).  The block kernel exists for
+// ILP 4 / 8 / 16 (WITH_16), the wave and stream kernels for 8, and anything else means 4
+template <bool WITH_16, class F>
+static void vmd_sdf_with_ilp_arith(bool arith, F f) {
+    auto with_arith = [&](auto ilp) { if (arith) f(ilp, std::true_type{}); else f(ilp, std::false_type{}); };
+    if constexpr (WITH_16) { if (g_sdf_ilp == 16) return with_arith(std::integral_constant<int, 16>{}); }
+    if (g_sdf_ilp == 8) with_arith(std::integral_constant<int, 8>{});
+    else with_arith(std::integral_constant<int, 4>{});
+}
+
+template <bool MASKED>
+static void vmd_sdf_launch_block(hipStream_t s, const typename vmd_scatter_arg<MASKED>::type& p) {
+    vmd_sdf_with_ilp_arith<true>(p.tgt_stride > 0, [&](auto ilp, auto arith) {
+        constexpr int ILP = decltype(ilp)::value;
+        hipLaunchKernelGGL((k_sdf_scatter<ILP, decltype(arith)::value, MASKED>), dim3((p.ntgt + 256 * ILP - 1) / (256 * ILP), p.B), dim3(256), 0, s, p);
+    });
+}
+
 extern "C" int vmd_hip_sdf_scatter(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                    const float* boxes, uint32_t pbc_flags, int B,
                                    const int32_t* structs, int K, int m, const float* R32, const float* c32,
@@ -4340,8 +4314,8 @@ extern "C" int vmd_hip_sdf_scatter(void* stream, const float* xyz, size_t frame_
                                    const float* group, const uint8_t* atom_tag, int tgt_first, int tgt_stride, int unowned) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || K <= 0 || ntgt <= 0) return 0;
-    vmd_scatter_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt, extent, dim,
-                           (unsigned long long*)volume, group, tgt_first, tgt_stride, unowned, g_sdf_nt};
+    const vmd_scatter_params_t p = vmd_sdf_params(xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt,
+                                                  extent, dim, volume, group, tgt_first, tgt_stride, unowned);
     if (atom_tag) {
         const int natoms4 = (int)(row_stride / 4);       // rows are padded to a multiple of 64 floats; the tag array covers the padding
         hipLaunchKernelGGL(k_sdf_scatter_dense, dim3((natoms4 + 255) / 256, B), dim3(256), 0, s, p, atom_tag, natoms4);
@@ -4361,47 +4335,21 @@ extern "C" int vmd_hip_sdf_scatter(void* stream, const float* xyz, size_t frame_
         return 0;
     }
     if (g_sdf_wave >= 2) {
-        const int ilp = g_sdf_ilp == 8 ? 8 : 4;
-        const int tiles_per_frame = (ntgt + VMD_WAVE * ilp - 1) / (VMD_WAVE * ilp);
-        const long long ntiles = (long long)tiles_per_frame * B;
-        long long nblocks = g_sdf_wave >= 16 ? g_sdf_wave : 2048;
-        if (nblocks > (ntiles + 3) / 4) nblocks = (ntiles + 3) / 4;
-        const dim3 g((unsigned)nblocks);
-        if (ilp == 8) {
-            if (arith) hipLaunchKernelGGL((k_sdf_scatter_stream<8, true>), g, dim3(256), 0, s, p, tiles_per_frame);
-            else hipLaunchKernelGGL((k_sdf_scatter_stream<8, false>), g, dim3(256), 0, s, p, tiles_per_frame);
-        } else {
-            if (arith) hipLaunchKernelGGL((k_sdf_scatter_stream<4, true>), g, dim3(256), 0, s, p, tiles_per_frame);
-            else hipLaunchKernelGGL((k_sdf_scatter_stream<4, false>), g, dim3(256), 0, s, p, tiles_per_frame);
-        }
-        VMD_LAUNCH_CHECK();
-        return 0;
-    }
-    if (g_sdf_wave) {
-        if (g_sdf_ilp == 8) {
-            const dim3 g((ntgt + 256 * 8 - 1) / (256 * 8), B);
-            if (arith) hipLaunchKernelGGL((k_sdf_scatter_wave<8, true>), g, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((k_sdf_scatter_wave<8, false>), g, dim3(256), 0, s, p);
-        } else {
-            const dim3 g((ntgt + 256 * 4 - 1) / (256 * 4), B);
-            if (arith) hipLaunchKernelGGL((k_sdf_scatter_wave<4, true>), g, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((k_sdf_scatter_wave<4, false>), g, dim3(256), 0, s, p);
-        }
-        VMD_LAUNCH_CHECK();
-        return 0;
-    }
-    if (g_sdf_ilp == 16) {
-        const dim3 g((ntgt + 256 * 16 - 1) / (256 * 16), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<16, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<16, false>), g, dim3(256), 0, s, p);
-    } else if (g_sdf_ilp == 8) {
-        const dim3 g((ntgt + 256 * 8 - 1) / (256 * 8), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<8, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<8, false>), g, dim3(256), 0, s, p);
+        vmd_sdf_with_ilp_arith<false>(arith, [&](auto ilp, auto ar) {
+            constexpr int ILP = decltype(ilp)::value;
+            const int tiles_per_frame = (ntgt + VMD_WAVE * ILP - 1) / (VMD_WAVE * ILP);
+            const long long ntiles = (long long)tiles_per_frame * B;
+            long long nblocks = g_sdf_wave >= 16 ? g_sdf_wave : 2048;
+            if (nblocks > (ntiles + 3) / 4) nblocks = (ntiles + 3) / 4;
+            hipLaunchKernelGGL((k_sdf_scatter_stream<ILP, decltype(ar)::value>), dim3((unsigned)nblocks), dim3(256), 0, s, p, tiles_per_frame);
+        });
+    } else if (g_sdf_wave) {
+        vmd_sdf_with_ilp_arith<false>(arith, [&](auto ilp, auto ar) {
+            constexpr int ILP = decltype(ilp)::value;
+            hipLaunchKernelGGL((k_sdf_scatter_wave<ILP, decltype(ar)::value>), dim3((ntgt + 256 * ILP - 1) / (256 * ILP), B), dim3(256), 0, s, p);
+        });
     } else {
-        const dim3 g((ntgt + 256 * 4 - 1) / (256 * 4), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<4, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<4, false>), g, dim3(256), 0, s, p);
+        vmd_sdf_launch_block<false>(s, p);
     }
     VMD_LAUNCH_CHECK();
     return 0;
@@ -4419,23 +4367,10 @@ extern "C" int vmd_hip_sdf_scatter_masked(void* stream, const float* xyz, size_t
     if (B <= 0 || K <= 0 || ntgt <= 0) return 0;
     if (B > 65535 || !mask || !mask_stride) return (int)hipErrorInvalidValue;
     vmd_scatter_masked_params_t p;
-    (vmd_scatter_params_t&)p = vmd_scatter_params_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt,
-                                                    extent, dim, (unsigned long long*)volume, group, tgt_first, tgt_stride, unowned, g_sdf_nt};
+    (vmd_scatter_params_t&)p = vmd_sdf_params(xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, K, m, R32, c32, tgt, owner, ntgt,
+                                              extent, dim, volume, group, tgt_first, tgt_stride, unowned);
     p.mask = mask; p.mask_stride = mask_stride; p.skip = skip_flag;
-    const bool arith = tgt_stride > 0;
-    if (g_sdf_ilp == 16) {
-        const dim3 g((ntgt + 256 * 16 - 1) / (256 * 16), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<16, true, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<16, false, true>), g, dim3(256), 0, s, p);
-    } else if (g_sdf_ilp == 8) {
-        const dim3 g((ntgt + 256 * 8 - 1) / (256 * 8), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<8, true, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<8, false, true>), g, dim3(256), 0, s, p);
-    } else {
-        const dim3 g((ntgt + 256 * 4 - 1) / (256 * 4), B);
-        if (arith) hipLaunchKernelGGL((k_sdf_scatter<4, true, true>), g, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_sdf_scatter<4, false, true>), g, dim3(256), 0, s, p);
-    }
+    vmd_sdf_launch_block<true>(s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }
