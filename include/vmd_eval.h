@@ -295,11 +295,36 @@ typedef struct vmd_backbone_t {
     const uint8_t* rama_class;                                /* per segment 0..3 or 255; NULL = all 0 */
 } vmd_backbone_t;
 bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* backbone);
+/* `{classes, populations} = secondary_structure(backbone, o)`: the other half of VIAMD's per-frame backbone pass
+ * (src/viamd.cpp:469-549, md_util_backbone_secondary_structure_infer) - the eight DSSP classes from the backbone's C=O ... H-N bonds.
+ * `backbone` as for vmd_ir_add_ramachandran (rama_class == 2 marks a proline, which donates no H; NULL: no proline); o: one carbonyl-oxygen
+ * atom index per segment, -1 = the segment has none (it never accepts, its successor never donates).  Chains are the ranges; the rules
+ * - amide H at 1.0 A along the previous C=O, the DSSP energy at -0.5 kcal/mol behind a 9 A CA gate, every bond counts, turns, bridges,
+ * ladders without bulges, the assignment order - are DESIGN 1.12's DECISIONs.
+ * names[0]: TEMPORAL, dim = {num_frames, nseg}, values[f * nseg + s] = the code of segment s in frame f (exact as a float); names[1]:
+ * TEMPORAL, dim = {num_frames, 9}, column k = the number of segments of the frame with code k.  Units {"", ""}, no aggregate.  A frame that
+ * was not evaluated reads 0 (VMD_SS_UNKNOWN, which the kernels never write) in both.  The codes correspond to MD_SECONDARY_STRUCTURE_* by
+ * name.  Errors (vmd_last_error): everything vmd_ir_add_ramachandran refuses, o == NULL, an o below -1, more than VMD_SS_MAX_SEGMENTS
+ * segments.  vmd_set_option("ss_scratch_bytes", n) bounds the bit matrices of a batch (frames x nseg^2 / 2 bytes; read at eval creation,
+ * default 256 MiB): a larger batch runs in sub-batches of frames, never below one frame. */
+#define VMD_SS_UNKNOWN 0      /* never written by the kernel: the value of a frame that was not evaluated */
+#define VMD_SS_COIL 1
+#define VMD_SS_TURN 2
+#define VMD_SS_BEND 3
+#define VMD_SS_HELIX_310 4
+#define VMD_SS_HELIX_ALPHA 5
+#define VMD_SS_HELIX_PI 6
+#define VMD_SS_BETA_BRIDGE 7
+#define VMD_SS_BETA_SHEET 8
+#define VMD_SS_NUM_CODES 9
+#define VMD_SS_MAX_SEGMENTS 16384
+bool vmd_ir_add_secondary_structure(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* backbone, const int32_t* o);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
  * there are and writes the first `cap` of them to `out` (NULL: count only); the angle table of a ramachandran statement: N, CA, C of segment
- * `context`, or of all segments.  0 for other properties.  What the shim highlights for
+ * `context`, or of all segments; the class table of a secondary_structure statement: N, CA, C, O of the segment(s), a missing O left out.
+ * 0 for other properties.  What the shim highlights for
  * MD_SCRIPT_VISUALIZE_ATOMS (include/vmd_md_script_shim.h). */
 size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* name, int64_t context, int32_t* out, size_t cap);
 /* md_script_ir_compile_from_source stand-in (src/main.cpp:878) for the script subset of the hot path: statements
@@ -330,6 +355,10 @@ typedef struct vmd_backbone_owned_t vmd_backbone_owned_t;
 vmd_backbone_owned_t* vmd_topology_backbone(const vmd_topology_t* topology);
 const vmd_backbone_t* vmd_backbone_view(const vmd_backbone_owned_t* backbone);
 void     vmd_backbone_free(vmd_backbone_owned_t* backbone);
+/* the carbonyl oxygen of every segment of `backbone` (DECISION D-SS-TOPOLOGY-O): the first atom of the CA's residue named "O", failing that
+ * "OT1", then "O1", then "OC1", else -1.  Writes the first `cap` of them to `out` (NULL: count only) and returns num_segments; 0 +
+ * vmd_last_error on a NULL or malformed argument. */
+size_t   vmd_topology_backbone_oxygens(const vmd_topology_t* topology, const vmd_backbone_t* backbone, int32_t* out, size_t cap);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
  * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of

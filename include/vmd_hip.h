@@ -313,6 +313,24 @@ int vmd_hip_backbone_angles(void* stream, const float* xyz, size_t frame_stride,
  * counts u64[512*512*4] (entry (y * 512 + x) * 4 + class) and sums u64[4] (NULL: not wanted) are ADDED to.  F * nseg > 2^31 - 1 is refused. */
 int vmd_hip_rama_bin(void* stream, const float* angles, int F, const uint8_t* row_mask, int nseg, const uint8_t* rama_class,
                      const uint8_t* link, int skip_ends, uint64_t* counts, uint64_t* sums);
+/* K11: per-frame secondary structure, three launches over one scratch block of vmd_hip_ss_scratch_words(B, nseg) u64 - four
+ * bit matrices [B][nseg][ceil(nseg / 64)]: HB, its transpose, the parallel and the antiparallel bridges.  n / ca / c / o i32[nseg] (o: -1 =
+ * the segment has no carbonyl oxygen), rng i32[nseg] the range of every segment, pro u8[nseg] 1 = proline, nbmask u64[ceil(nseg / 64)] bit
+ * j = segment j has both neighbours in its range.  vmd_hip_ss_hbond fills HB and its transpose, vmd_hip_ss_bridges the bridge rows from
+ * them, vmd_hip_ss_assign the class row cls f32[B][nseg] (codes 1..8) and the populations pop f32[B][9] from all four.  nseg above
+ * VMD_SS_SEG_MAX, B * nseg * ceil(nseg / 64) > 2^31 - 1 and NULL arguments are refused before anything is launched. */
+#define VMD_SS_SEG_MAX 16384
+#define VMD_SS_CODES 9
+size_t vmd_hip_ss_scratch_words(int B, int nseg);
+int vmd_hip_ss_hbond(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                     int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                     const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch);
+int vmd_hip_ss_bridges(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                       int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                       const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch);
+int vmd_hip_ss_assign(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                      int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                      const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch, float* cls, float* pop);
 /* 1: k_sdf_scatter reads the frame with non-temporal loads; returns the previous value */
 int vmd_hip_set_sdf_nt(int on);
 /* candidate columns (one target atom against the 64 reference atoms of a chunk: 64 candidate lanes) k_rdf_pencil has walked on the

@@ -14,6 +14,10 @@ PBC_ALL = 7
 FLAG_TEMPORAL, FLAG_DISTRIBUTION, FLAG_VOLUME = 1, 2, 4
 FLAG_MAP = 8                     # VMD_PROPERTY_FLAG_MAP: the Ramachandran class map, dim = {1, 4, 512, 512}
 RAMA_MAP_DIM, RAMA_MAP_CLASSES = 512, 4
+# VMD_SS_* (include/vmd_eval.h): the secondary-structure codes of DESIGN 1.12, and one letter each for printing (DSSP's, '?' = not evaluated)
+SS_UNKNOWN, SS_COIL, SS_TURN, SS_BEND, SS_HELIX_310, SS_HELIX_ALPHA, SS_HELIX_PI, SS_BETA_BRIDGE, SS_BETA_SHEET = range(9)
+SS_NUM_CODES, SS_MAX_SEGMENTS = 9, 16384
+SS_LETTERS = "?-TSGHIBE"
 DIST_COM, DIST_MIN, DIST_MAX, DIST_PAIR = 0, 1, 2, 3
 RDF_NUM_BINS = 1024
 VOLUME_DIM = 128
@@ -181,6 +185,8 @@ SIGNATURES = [
     ("vmd_ir_add_sdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.c_size_t, c_int32_p, C.c_size_t, C.POINTER(ShellC),
                                         C.c_float]),
     ("vmd_ir_add_ramachandran", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(BackboneC)]),
+    ("vmd_ir_add_secondary_structure", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(BackboneC), c_int32_p]),
+    ("vmd_topology_backbone_oxygens", C.c_size_t, [C.POINTER(TopologyC), C.POINTER(BackboneC), c_int32_p, C.c_size_t]),
     ("vmd_topology_backbone", _vp, [C.POINTER(TopologyC)]),
     ("vmd_backbone_view", C.POINTER(BackboneC), [_vp]),
     ("vmd_backbone_free", None, [_vp]),
@@ -360,6 +366,10 @@ SIGNATURES = [
                                    C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.c_int, _vp]),
     ("vmd_hip_backbone_angles", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("vmd_hip_rama_bin", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
+    ("vmd_hip_ss_scratch_words", C.c_size_t, [C.c_int, C.c_int]),
+    ("vmd_hip_ss_hbond", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int] + [_vp] * 8),
+    ("vmd_hip_ss_bridges", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int] + [_vp] * 8),
+    ("vmd_hip_ss_assign", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int] + [_vp] * 10),
     ("vmd_hip_shape_partial_doubles", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("vmd_hip_shape", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                 _vp, _vp, _vp, _vp]),

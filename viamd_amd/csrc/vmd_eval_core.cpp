@@ -302,6 +302,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     e->spec.within_exclude_ref = g_opt.spec_within_exclude_ref.load() != 0;
     e->spec.shell_norm = g_opt.spec_shell_norm.load() != 0;
     e->spec.rama_skip_ends = g_opt.spec_rama_skip_ends.load() != 0;
+    e->ss_scratch_bytes = (size_t)std::max(0, g_opt.ss_scratch_bytes.load());
     e->frame_mask.assign(num_frames, 0);
     for (auto& p : ir->props) {
         auto st = std::make_unique<PropState>();
@@ -347,6 +348,9 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             if (hipMemsetAsync(st->d_table.p, 0, num_frames * 2 * p.a.size() * sizeof(float), e->stream) != hipSuccess) {
                 vmd_fail("hipMemset failed"); return nullptr; }
             break;
+        // one code per segment, nine counts per frame; no aggregate (a mean of class codes says nothing)
+        case Form::SS_CLASS: st->dist_P = p.a.size(); aggregate = false; break;
+        case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
         case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
         case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: break;
         case Form::SHAPE: st->shape_max_set = largest_set(); break;
@@ -860,7 +864,27 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
         };
         std::vector<float> tmp;
         switch (d.form) {
-        case Form::RDF: case Form::RAMA_MAP: break;      // the sets of an rdf are interned selections; a map has none
+        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: break;      // the sets of an rdf are interned selections; a map and the populations have none
+        case Form::SS_CLASS: {
+            // N, CA, C, O per segment and what the kernels read of the ranges - the range of every segment, the proline bytes,
+            // the bit row "has both neighbours in its range"
+            const size_t nseg = d.a.size();
+            std::vector<int32_t> rng(nseg);
+            std::vector<uint8_t> pro(nseg);
+            std::vector<uint64_t> nb((nseg + 63) / 64, 0);
+            for (size_t r = 0; r + 1 < d.aoff.size(); ++r)
+                for (int32_t s = d.aoff[r]; s < d.aoff[r + 1]; ++s) {
+                    rng[(size_t)s] = (int32_t)r;
+                    if (s > d.aoff[r] && s + 1 < d.aoff[r + 1]) nb[(size_t)s >> 6] |= 1ull << (s & 63);
+                }
+            for (size_t s = 0; s < nseg; ++s) pro[s] = d.rama_class[s] == 2;
+            if (!p->d_a.upload(d.a.data(), nseg, e->stream) || !p->d_b.upload(d.b.data(), nseg, e->stream) ||
+                !p->d_c.upload(d.c.data(), nseg, e->stream) || !p->d_ss_o.upload(d.ss_o.data(), nseg, e->stream) ||
+                !p->d_ss_rng.upload(rng.data(), nseg, e->stream) || !p->d_ss_pro.upload(pro.data(), nseg, e->stream) ||
+                !p->d_ss_nb.upload(nb.data(), nb.size(), e->stream)) return false;
+            HIP_OK(hipStreamSynchronize(e->stream));       // the vectors go out of scope
+            break;
+        }
         case Form::WITHIN_EXPR: break;                   // the lists live in the interned selections
         case Form::SDF: {
             if (!p->d_structs.upload(d.a.data(), d.a.size(), e->stream)) return false;

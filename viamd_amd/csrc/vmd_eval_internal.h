@@ -181,6 +181,9 @@ struct Options {
     // a shell expression: 1 = a lane whose outcome the earlier terms decided does no walk; 0 = every lane is tested against every
     // term (the A/B of the measurement; results are identical)
     std::atomic<int> shell_expr_skip{1};
+    // secondary structure: bytes of bit matrices a batch may hold (frames x nseg^2 / 2); a larger batch runs in sub-batches
+    // of frames, never below one frame.  256 MiB: the 1 000 frames x 500 segments of DESIGN 1.10's system take 128 MB in one go
+    std::atomic<int> ss_scratch_bytes{256 << 20};
 };
 
 extern Options g_opt;
@@ -380,6 +383,11 @@ enum class Form : int {
     // the range offsets, rama_class / rama_link one byte per segment - has rows {phi, psi} per segment; the map behind it (K = the segments,
     // for the merge's count bound) is what the table's launch bins into
     RAMA_TABLE, RAMA_MAP,
+    // `{classes, populations} = secondary_structure(backbone, o)`: two descriptors in a row.  The class table carries the
+    // backbone as the angle table does (a = N, b = CA, c = C, aoff = the range offsets, rama_class) and ss_o, one carbonyl oxygen per segment
+    // or -1; its rows are one code per segment.  The populations behind it (K = the segments) are nine counts per frame, written by the
+    // table's launch
+    SS_CLASS, SS_POP,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -407,8 +415,11 @@ constexpr FormFacts kFormFacts[] = {
     /* WITHIN_EXPR */ {ResultClass::TEMPORAL,     1, "within",        {"", ""},         nullptr, true,  9},
     /* RAMA_TABLE  */ {ResultClass::TEMPORAL,     3, "ramachandran",  {"", "rad"},      nullptr, false, 10},    // radians whatever spec_angle_radians says
     /* RAMA_MAP    */ {ResultClass::MAP,          0, "ramachandran",  {"rad", ""},      nullptr, false, 0},
+    /* SS_CLASS    */ {ResultClass::TEMPORAL,     3, "secondary_structure", {"", ""},   nullptr, false, 11},    // a code, a count
+    /* SS_POP      */ {ResultClass::TEMPORAL,     0, "secondary_structure", {"", ""},   nullptr, false, 12},
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::RAMA_MAP + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::SS_POP + 1, "one row of kFormFacts per Form");
+static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES, "the kernels' limits are the interface's");
 
 struct Property {
     std::string name;
@@ -437,6 +448,7 @@ struct Property {
     std::vector<ExprTerm> expr_terms;
     uint32_t expr_truth = 0;
     std::vector<uint8_t> rama_class, rama_link;     // RAMA_TABLE: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
+    std::vector<int32_t> ss_o;                      // SS_CLASS: the carbonyl oxygen of every segment, -1 = none
     bool is_expr_sdf() const { return form == Form::SDF && !expr_terms.empty(); }
     bool behind_cells() const { return facts().behind_cells || is_shell_sdf() || is_expr_sdf(); }     // launch_rdf launches it, not launch_property
 };
@@ -608,6 +620,11 @@ struct PropState {
     DevBuf<float> d_table;
     DevBuf<uint8_t> d_rama_class, d_rama_link, d_rama_mask;
     DevBuf<uint64_t> d_rama_scratch;
+    // secondary structure, the class table: d_a / d_b / d_c as above, the oxygens, the range of every segment, the proline
+    // bytes and the "has both neighbours" bit row
+    DevBuf<int32_t> d_ss_o, d_ss_rng;
+    DevBuf<uint8_t> d_ss_pro;
+    DevBuf<uint64_t> d_ss_nb;
     bool table_stale = false;           // host rows arrived from elsewhere (a source's blocks, a merge): upload them before the next query
     bool uploaded = false;
     bool pinned = false;
@@ -814,6 +831,10 @@ struct vmd_script_eval_t {
     DevBuf<uint8_t> d_one_bits;                         // ... and the term outcomes of a shell expression's frame
     std::vector<std::unique_ptr<ShellExpr>> exprs;      // shell expressions and the counts / sdfs over them, indices into props
     std::vector<int> expr_count_props, expr_sdf_props;
+    // secondary structure: the four bit matrices of the frames in flight, shared by the statements of the script (they run one
+    // after another on the eval's stream), and the bound on them (option ss_scratch_bytes, read at creation)
+    DevBuf<uint64_t> d_ss_scratch;
+    size_t ss_scratch_bytes = 0;
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;
@@ -1090,6 +1111,7 @@ struct RangeRun {
     bool launch_rmsd(BatchCtx& c, PropState* p);
     bool launch_geometry(BatchCtx& c, PropState* p);
     bool launch_rama(BatchCtx& c, size_t pi);
+    bool launch_ss(BatchCtx& c, size_t pi);
     bool launch_distance(BatchCtx& c, PropState* p);
     bool launch_property(BatchCtx& c, size_t pi);
 };

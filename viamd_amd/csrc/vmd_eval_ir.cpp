@@ -42,6 +42,10 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         case Form::WITHIN_EXPR: w += p.a.size() + expr_refs(p); break;       // |T| + sum |R_i|
         case Form::RAMA_TABLE: w += 3 * (uint64_t)p.a.size(); break;         // N, CA, C of every segment
         case Form::RAMA_MAP: break;                                          // binned by its table's launch
+        // the CA gate of every ordered pair of segments - 64 to a wave, an eighth of them reach an energy on a folded chain -
+        // plus N, CA, C, O of every segment
+        case Form::SS_CLASS: w += (uint64_t)p.a.size() * (uint64_t)p.a.size() / 8 + 4 * (uint64_t)p.a.size(); break;
+        case Form::SS_POP: break;                                            // counted by its table's launch
         }
     }
     return w;
@@ -342,18 +346,18 @@ extern "C" bool vmd_ir_add_sdf_shell_expr(vmd_script_ir_t* ir, const char* name,
     return commit(ir, &p);
 }
 
-// `{table, map} = ramachandran(backbone)` (DESIGN 1.10): the angle table and the density map, two descriptors in a row
-extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* bb) {
+// a backbone statement: the names and the backbone, checked in this order; `word` is the form's
+static bool backbone_ok(vmd_script_ir_t* ir, const char* word, const char* const names[2], const vmd_backbone_t* bb) {
     if (!ir) return vmd_fail("ir is NULL");
-    if (!names || !bb) return vmd_fail("ramachandran needs two property names and a backbone");
+    if (!names || !bb) return vmd_fail("%s needs two property names and a backbone", word);
     if (!names_ok(ir, names, 2)) return false;
     const size_t nseg = bb->num_segments;
-    if (nseg == 0) return vmd_fail("ramachandran backbone has no segment");
-    if (nseg > 0x3fffffff) return vmd_fail("ramachandran backbone too large");
-    if (!bb->n || !bb->ca || !bb->c) return vmd_fail("ramachandran backbone has a NULL atom list");
+    if (nseg == 0) return vmd_fail("%s backbone has no segment", word);
+    if (nseg > 0x3fffffff) return vmd_fail("%s backbone too large", word);
+    if (!bb->n || !bb->ca || !bb->c) return vmd_fail("%s backbone has a NULL atom list", word);
     if (!idx_ok(bb->n, nseg, "backbone N list") || !idx_ok(bb->ca, nseg, "backbone CA list") || !idx_ok(bb->c, nseg, "backbone C list"))
         return false;
-    if (!bb->range_offsets || bb->num_ranges == 0) return vmd_fail("ramachandran backbone has no range offsets");
+    if (!bb->range_offsets || bb->num_ranges == 0) return vmd_fail("%s backbone has no range offsets", word);
     if (bb->range_offsets[0] != 0) return vmd_fail("backbone range offsets must start at 0");
     for (size_t r = 0; r < bb->num_ranges; ++r)
         if (bb->range_offsets[r + 1] <= bb->range_offsets[r]) return vmd_fail("backbone range %zu is empty (offsets must increase)", r);
@@ -363,10 +367,24 @@ extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const n
         for (size_t s = 0; s < nseg; ++s)
             if (bb->rama_class[s] > 3 && bb->rama_class[s] != 255)
                 return vmd_fail("backbone segment %zu has class %u (0..3 or 255)", s, (unsigned)bb->rama_class[s]);
-    Property t = make_property(Form::RAMA_TABLE, names[0]);
+    return true;
+}
+
+// ... and copied into the statement's first descriptor: a = N, b = CA, c = C, aoff = the range offsets, the class bytes
+static Property backbone_property(Form form, const char* name, const vmd_backbone_t* bb) {
+    const size_t nseg = bb->num_segments;
+    Property t = make_property(form, name);
     t.a.assign(bb->n, bb->n + nseg); t.b.assign(bb->ca, bb->ca + nseg); t.c.assign(bb->c, bb->c + nseg);
     t.aoff.assign(bb->range_offsets, bb->range_offsets + bb->num_ranges + 1);
     if (bb->rama_class) t.rama_class.assign(bb->rama_class, bb->rama_class + nseg); else t.rama_class.assign(nseg, 0);
+    return t;
+}
+
+// `{table, map} = ramachandran(backbone)` (DESIGN 1.10): the angle table and the density map, two descriptors in a row
+extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* bb) {
+    if (!backbone_ok(ir, "ramachandran", names, bb)) return false;
+    const size_t nseg = bb->num_segments;
+    Property t = backbone_property(Form::RAMA_TABLE, names[0], bb);
     t.rama_link.assign(nseg, 3);
     for (size_t r = 0; r < bb->num_ranges; ++r) {
         t.rama_link[bb->range_offsets[r]] &= (uint8_t)~1u;
@@ -375,6 +393,21 @@ extern "C" bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const n
     Property tm[2] = {std::move(t), make_property(Form::RAMA_MAP, names[1])};
     tm[1].K = nseg;
     return commit(ir, tm, 2);
+}
+
+// `{classes, populations} = secondary_structure(backbone, o)`: the class table and the populations, two descriptors in a row
+extern "C" bool vmd_ir_add_secondary_structure(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* bb, const int32_t* o) {
+    if (!backbone_ok(ir, "secondary_structure", names, bb)) return false;
+    const size_t nseg = bb->num_segments;
+    if (!o) return vmd_fail("secondary_structure has no carbonyl oxygen list");
+    for (size_t s = 0; s < nseg; ++s)
+        if (o[s] < -1) return vmd_fail("backbone O list holds %d for segment %zu (an atom index, or -1 for none)", o[s], s);
+    if (nseg > VMD_SS_MAX_SEGMENTS) return vmd_fail("secondary_structure backbone has %zu segments (at most %d)", nseg, VMD_SS_MAX_SEGMENTS);
+    Property t = backbone_property(Form::SS_CLASS, names[0], bb);
+    t.ss_o.assign(o, o + nseg);
+    Property tp[2] = {std::move(t), make_property(Form::SS_POP, names[1])};
+    tp[1].K = nseg;
+    return commit(ir, tp, 2);
 }
 
 // what vmd_ir_geometry_atoms has counted and written so far
@@ -399,7 +432,7 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         };
         size_t c0 = 0, c1 = 0;
         switch (p.form) {
-        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: return 0;
+        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: return 0;
         case Form::WITHIN:          // the static candidates: the reference set, then the target set (one context)
             if (context > 0) return 0;
             s.put(p.b); s.put(p.a);
@@ -412,6 +445,13 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         case Form::RAMA_TABLE:      // N, CA, C of the segment(s)
             if (!contexts(p.a.size(), c0, c1)) return 0;
             for (size_t sg = c0; sg < c1; ++sg) for (const auto* v : {&p.a, &p.b, &p.c}) s.put((*v)[sg]);
+            return s.n;
+        case Form::SS_CLASS:        // N, CA, C, O of the segment(s), a missing O left out
+            if (!contexts(p.a.size(), c0, c1)) return 0;
+            for (size_t sg = c0; sg < c1; ++sg) {
+                for (const auto* v : {&p.a, &p.b, &p.c}) s.put((*v)[sg]);
+                if (p.ss_o[sg] >= 0) s.put(p.ss_o[sg]);
+            }
             return s.n;
         case Form::SHAPE: case Form::RMSD:      // the set of the context(s)
             if (!contexts(p.aoff.size() - 1, c0, c1)) return 0;
@@ -453,7 +493,10 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::SHAPE: h = fnv1a(h, &p.shape_comp, sizeof(int)); break;
         case Form::RAMA_TABLE: h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); break;     // 
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
-        case Form::WITHIN_EXPR: case Form::RAMA_MAP: break;
+        case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: break;
+        case Form::SS_CLASS:                                            // 
+            h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); h = fnv1a(h, p.ss_o.data(), p.ss_o.size() * sizeof(int32_t));
+            break;
         }
         for (int k = 0; k < 2; ++k) {                                   // rdf / sdf over shells only, as above
             if (!p.shell[k].on) continue;

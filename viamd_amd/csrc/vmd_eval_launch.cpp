@@ -524,6 +524,42 @@ bool RangeRun::launch_rama(BatchCtx& c, size_t pi) {
     return true;
 }
 
+// secondary structure: the class rows [nb][nseg] and, in the descriptor behind, the populations [nb][9]; each copies its own
+// (queue_batch).  The bit matrices take nseg^2 / 2 bytes per frame: the batch runs in as many sub-batches of frames as the eval's bound
+// (ss_scratch_bytes) and the launch limit of 2^31 - 1 words ask for, one after another over the same scratch, never below one frame.
+bool RangeRun::launch_ss(BatchCtx& c, size_t pi) {
+    PropState* p = e->props[pi].get();
+    if (pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::SS_POP)
+        return vmd_fail("secondary_structure table '%s' has lost its populations", p->prop.name.c_str());
+    PropState* q = e->props[pi + 1].get();
+    if (!q->d_out.ensure(c.nb * q->dim1)) return false;
+    const size_t nseg = p->prop.a.size();
+    const size_t frame_words = vmd_hip_ss_scratch_words(1, (int)nseg);
+    if (frame_words / 4 > 0x7fffffffull) return vmd_fail("secondary_structure: %zu segments exceed the launch limit", nseg);
+    size_t step = std::max<size_t>(1, e->ss_scratch_bytes / (frame_words * sizeof(uint64_t)));
+    step = std::min(std::min(step, c.nb), (size_t)0x7fffffffull / (frame_words / 4));
+    if (!e->d_ss_scratch.ensure(step * frame_words)) return false;
+    const Stage& s = *c.src;
+    for (size_t f = 0; f < c.nb; f += step) {
+        const int nf = (int)std::min(step, c.nb - f);
+        const float* xyz = s.base + f * s.frame_stride;
+        const float* boxes = s.d_boxes.p + 9 * f;
+        e->prof.begin("ss_hbond", e->stream);
+        KRN_OK(vmd_hip_ss_hbond(e->stream, xyz, s.frame_stride, s.row_stride, boxes, c.pbc, nf, (int)nseg, p->d_a.p, p->d_b.p, p->d_c.p,
+                p->d_ss_o.p, p->d_ss_rng.p, p->d_ss_pro.p, p->d_ss_nb.p, e->d_ss_scratch.p));
+        e->prof.end(e->stream);
+        e->prof.begin("ss_bridges", e->stream);
+        KRN_OK(vmd_hip_ss_bridges(e->stream, xyz, s.frame_stride, s.row_stride, boxes, c.pbc, nf, (int)nseg, p->d_a.p, p->d_b.p, p->d_c.p,
+                p->d_ss_o.p, p->d_ss_rng.p, p->d_ss_pro.p, p->d_ss_nb.p, e->d_ss_scratch.p));
+        e->prof.end(e->stream);
+        e->prof.begin("ss_assign", e->stream);
+        KRN_OK(vmd_hip_ss_assign(e->stream, xyz, s.frame_stride, s.row_stride, boxes, c.pbc, nf, (int)nseg, p->d_a.p, p->d_b.p, p->d_c.p,
+                p->d_ss_o.p, p->d_ss_rng.p, p->d_ss_pro.p, p->d_ss_nb.p, e->d_ss_scratch.p, p->d_out.p + f * nseg, q->d_out.p + f * q->dim1));
+        e->prof.end(e->stream);
+    }
+    return true;
+}
+
 bool RangeRun::launch_distance(BatchCtx& c, PropState* p) {
     e->prof.begin("distance", e->stream);
     KRN_OK(vmd_hip_distance(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p, c.pbc, (int)c.nb,
@@ -549,6 +585,8 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);
+    case Form::SS_POP: return true;                                             // filled by the launch of the class table in front of it
+    case Form::SS_CLASS: return launch_ss(c, pi);
     case Form::SHAPE: return launch_shape(c, pi);
     case Form::RMSD: return launch_rmsd(c, p);
     case Form::ANGLE: case Form::DIHEDRAL: return launch_geometry(c, p);

@@ -271,7 +271,8 @@ static const float* batch_rows(const PropState* p, size_t f0) {
     // accumulators, no rows; a within count's rows are sent by launch_rdf, behind the overflow flag
     case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::WITHIN: case Form::WITHIN_EXPR: return nullptr;
     case Form::RAMA_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
-    case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: return p->d_out.p;
+    case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::SS_CLASS: case Form::SS_POP:
+        return p->d_out.p;
     }
     return nullptr;
 }

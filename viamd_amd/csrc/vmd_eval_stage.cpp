@@ -17,6 +17,9 @@ bool check_atoms(vmd_script_eval_t* e, size_t num_atoms) {
             for (int32_t i : *v)
                 if ((size_t)i >= num_atoms)
                     return vmd_fail("property '%s' references atom %d but the trajectory has %zu atoms", p->prop.name.c_str(), i, num_atoms);
+        for (int32_t i : p->prop.ss_o)      // (-1 = the segment has no oxygen)
+            if (i >= 0 && (size_t)i >= num_atoms)
+                return vmd_fail("property '%s' references atom %d but the trajectory has %zu atoms", p->prop.name.c_str(), i, num_atoms);
         for (const Property::ExprTerm& t : p->prop.expr_terms)
             for (int32_t i : t.ref)
                 if ((size_t)i >= num_atoms)

@@ -3242,6 +3242,267 @@ __global__ __launch_bounds__(256) void k_rama_bin(vmd_rama_params_t p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ K11: secondary structure
+
+// Four bit matrices per frame, rows of W = ceil(nseg / 64) 64-bit words: HB[a] bit d and HBT[d] bit a = hb(a, d) (the C=O of a accepts from
+// the N-H of d), BP[i] bit j / BA[i] bit j = parallel / antiparallel bridge (i, j).  Bits at and above nseg are zero in every row.
+struct vmd_ss_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+    const int32_t* n; const int32_t* ca; const int32_t* c; const int32_t* o;
+    const int32_t* rng;                 // [nseg] the range of every segment
+    const uint8_t* pro;                 // [nseg] 1 = proline
+    const unsigned long long* nbmask;   // [W] bit j: j has both neighbours in its range
+    int nseg; int W;
+    unsigned long long* hb; unsigned long long* hbt; unsigned long long* bp; unsigned long long* ba;     // [B][nseg][W] each
+    float* cls;                         // [B][nseg]
+    float* pop;                         // [B][VMD_SS_CODES]
+};
+
+__device__ __forceinline__ int vmd_imin(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int vmd_imax(int a, int b) { return a > b ? a : b; }
+__device__ __forceinline__ double vmd_ss_len(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+
+// D-SS-HBOND for a gated pair: ON / CN are the fp32 minimum-image vectors N[d] - O[a] and N[d] - C[a], u the donor's unit C=O direction
+__device__ __forceinline__ bool vmd_ss_bond(const float on[3], const float cn[3], const double u[3]) {
+    const double rON = vmd_ss_len((double)on[0], (double)on[1], (double)on[2]);
+    const double rCN = vmd_ss_len((double)cn[0], (double)cn[1], (double)cn[2]);
+    const double rOH = vmd_ss_len((double)on[0] + u[0], (double)on[1] + u[1], (double)on[2] + u[2]);
+    const double rCH = vmd_ss_len((double)cn[0] + u[0], (double)cn[1] + u[1], (double)cn[2] + u[2]);
+    if (rON < 0.5 || rCN < 0.5 || rOH < 0.5 || rCH < 0.5) return true;
+    return 27.888 * (((1.0 / rON + 1.0 / rCH) - 1.0 / rOH) - 1.0 / rCN) < -0.5;
+}
+
+// one wave per (frame, word of 64 donors, word of 64 acceptors): the donors live in the lanes (their N, CA and unit C=O vector are made once),
+// the 64 acceptors are staged in LDS and walked one at a time.  Only the CA gate is tested in that walk: a pair that passes is pushed on
+// the wave's LDS stack, and whenever 64 pairs stand there they take a lane each for the energy - the gate passes for a few lanes per
+// acceptor, and fp64 square roots and divisions on four lanes of 64 were four fifths of this kernel.  A bond sets its bit in the two
+// 64 x 64 bit blocks in LDS; at the end every lane stores one word of HB (acceptor wa * 64 + lane, donors w) and one of HBT.
+__global__ __launch_bounds__(64) void k_ss_hbond(vmd_ss_params_t p) {
+    __shared__ float s_pos[64][9];      // CA, C, O of the acceptors
+    __shared__ int s_rng[64];
+    __shared__ int s_acc[64];           // the acceptor has an oxygen
+    __shared__ float s_n[64][3];        // the donors' N ...
+    __shared__ double s_u[64][3];       // ... and unit C=O vector
+    __shared__ unsigned short s_stack[128];      // gated pairs: donor lane << 6 | acceptor
+    __shared__ unsigned s_hb[64][2], s_hbt[64][2];      // [acceptor] bits by donor lane, [donor lane] bits by acceptor, two halves each
+    const int lane = threadIdx.x;
+    const long long blk = blockIdx.x;
+    const int w = (int)(blk % p.W), wa = (int)((blk / p.W) % p.W), b = (int)(blk / ((long long)p.W * p.W));
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const int al = wa * 64 + lane;
+    s_acc[lane] = 0; s_rng[lane] = -1;
+    s_hb[lane][0] = s_hb[lane][1] = s_hbt[lane][0] = s_hbt[lane][1] = 0u;
+    if (al < p.nseg) {
+        const int ia = p.ca[al], ic = p.c[al], io = p.o[al];
+        s_pos[lane][0] = fx[ia]; s_pos[lane][1] = fy[ia]; s_pos[lane][2] = fz[ia];
+        s_pos[lane][3] = fx[ic]; s_pos[lane][4] = fy[ic]; s_pos[lane][5] = fz[ic];
+        if (io >= 0) { s_pos[lane][6] = fx[io]; s_pos[lane][7] = fy[io]; s_pos[lane][8] = fz[io]; s_acc[lane] = 1; }
+        s_rng[lane] = p.rng[al];
+    }
+    const int d = w * 64 + lane;
+    bool donor = false;
+    int rd = -2;
+    float A[3] = {0.0f, 0.0f, 0.0f};
+    if (d < p.nseg) {
+        rd = p.rng[d];
+        const int ia = p.ca[d];
+        A[0] = fx[ia]; A[1] = fy[ia]; A[2] = fz[ia];
+        // D-SS-H: the amide H sits at N[d] + u, u the unit vector of mi(C[d-1] - O[d-1])
+        if (d > 0 && p.rng[d - 1] == rd && !p.pro[d] && p.o[d - 1] >= 0) {
+            const int ic = p.c[d - 1], io = p.o[d - 1], in = p.n[d];
+            float v[3] = {fx[ic] - fx[io], fy[ic] - fy[io], fz[ic] - fz[io]};
+            vmd_mi3_rintf(bx, v[0], v[1], v[2]);
+            const double l = vmd_ss_len((double)v[0], (double)v[1], (double)v[2]);
+            if (l > 0.0) {
+                donor = true;
+                s_u[lane][0] = (double)v[0] / l; s_u[lane][1] = (double)v[1] / l; s_u[lane][2] = (double)v[2] / l;
+                s_n[lane][0] = fx[in]; s_n[lane][1] = fy[in]; s_n[lane][2] = fz[in];
+            }
+        }
+    }
+    __syncthreads();
+    // the energy of stack entry e, by whichever lane holds it
+    auto bond = [&](unsigned e) {
+        const int dl = (int)(e >> 6), j = (int)(e & 63u);
+        float on[3] = {s_n[dl][0] - s_pos[j][6], s_n[dl][1] - s_pos[j][7], s_n[dl][2] - s_pos[j][8]};
+        float cn[3] = {s_n[dl][0] - s_pos[j][3], s_n[dl][1] - s_pos[j][4], s_n[dl][2] - s_pos[j][5]};
+        vmd_mi3_rintf(bx, on[0], on[1], on[2]);
+        vmd_mi3_rintf(bx, cn[0], cn[1], cn[2]);
+        const double u[3] = {s_u[dl][0], s_u[dl][1], s_u[dl][2]};
+        if (vmd_ss_bond(on, cn, u)) {
+            atomicOr(&s_hb[j][dl >> 5], 1u << (dl & 31));
+            atomicOr(&s_hbt[dl][j >> 5], 1u << (j & 31));
+        }
+    };
+    const int na = vmd_imin(64, p.nseg - wa * 64);
+    unsigned top = 0u;                  // entries on the stack (the same in every lane)
+    for (int j = 0; j < na; ++j) {
+        const int a = wa * 64 + j;
+        bool gate = false;
+        if (donor && s_acc[j] && a != d && !(d == a + 1 && s_rng[j] == rd)) {
+            float g[3] = {A[0] - s_pos[j][0], A[1] - s_pos[j][1], A[2] - s_pos[j][2]};
+            vmd_mi3_rintf(bx, g[0], g[1], g[2]);
+            gate = ((double)g[0] * (double)g[0] + (double)g[1] * (double)g[1]) + (double)g[2] * (double)g[2] < 81.0;
+        }
+        const unsigned long long m = __ballot(gate ? 1 : 0);
+        if (gate) s_stack[top + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)((lane << 6) | j);
+        top += (unsigned)__popcll(m);
+        if (top >= 64u) {               // < 64 before the push, < 128 after it: the top 64 entries take a lane each
+            __syncthreads();
+            top -= 64u;
+            bond(s_stack[top + lane]);
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if ((unsigned)lane < top) bond(s_stack[lane]);
+    __syncthreads();
+    if (al < p.nseg) p.hb[((size_t)b * p.nseg + al) * p.W + w] = (unsigned long long)s_hb[lane][0] | ((unsigned long long)s_hb[lane][1] << 32);
+    if (d < p.nseg) p.hbt[((size_t)b * p.nseg + d) * p.W + wa] = (unsigned long long)s_hbt[lane][0] | ((unsigned long long)s_hbt[lane][1] << 32);
+}
+
+// word w of a bit row moved by one bit, with the carry of the neighbouring word: bit j of the result is bit j + 1 (down) / j - 1 (up) of the row
+__device__ __forceinline__ unsigned long long vmd_ss_down(const unsigned long long* row, int w, int W) {
+    return (row[w] >> 1) | (w + 1 < W ? row[w + 1] << 63 : 0ull);
+}
+__device__ __forceinline__ unsigned long long vmd_ss_up(const unsigned long long* row, int w) {
+    return (row[w] << 1) | (w > 0 ? row[w - 1] >> 63 : 0ull);
+}
+
+// one thread per (frame, segment i, word): the four bridge patterns of DESIGN 1.12 (5) as ANDs of rows of HB / HBT and of their one-bit
+// moves, masked with "j has both neighbours" and, inside i's range, |i - j| >= 3.  A row whose i lacks a neighbour is zero.
+__global__ __launch_bounds__(256) void k_ss_bridges(vmd_ss_params_t p) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)p.B * p.nseg * p.W) return;
+    const int w = (int)(t % p.W), i = (int)((t / p.W) % p.nseg);
+    const size_t b = (size_t)(t / ((long long)p.W * p.nseg));
+    unsigned long long par = 0ull, anti = 0ull;
+    if (i >= 1 && i + 1 < p.nseg && p.rng[i - 1] == p.rng[i] && p.rng[i + 1] == p.rng[i]) {
+        const unsigned long long* hb = p.hb + (b * p.nseg + i) * p.W;       // row i; rows i - 1 and i + 1 stand W words before and behind
+        const unsigned long long* hbt = p.hbt + (b * p.nseg + i) * p.W;
+        anti = (hb[w] & hbt[w]) | (vmd_ss_down(hb - p.W, w, p.W) & vmd_ss_up(hbt + p.W, w));
+        par = ((hb - p.W)[w] & (hbt + p.W)[w]) | (vmd_ss_up(hbt, w) & vmd_ss_down(hb, w, p.W));
+        unsigned long long keep = p.nbmask[w];
+        for (int j = vmd_imax(i - 2, 0); j <= vmd_imin(i + 2, p.nseg - 1); ++j)
+            if ((j >> 6) == w && p.rng[j] == p.rng[i]) keep &= ~(1ull << (j & 63));
+        par &= keep; anti &= keep;
+    }
+    p.bp[t] = par;
+    p.ba[t] = anti;
+}
+
+// one block per frame, the seven passes of DESIGN 1.12 (7) with a barrier between them; the codes of a pass stand in one LDS row while the
+// next pass writes the other.  Pass 1 takes a wave per segment (lanes over the words of its rows, one ballot each for "has a bridge" and
+// "is in a ladder"); the later passes take a thread per segment.  The populations: one ballot per code and wave, summed in the wave's
+// registers, one LDS atomic per wave and code at the end.
+__global__ __launch_bounds__(256) void k_ss_assign(vmd_ss_params_t p) {
+    HIP_DYNAMIC_SHARED(uint32_t, s_dyn)             // three rows of nseg bytes (rounded up to 16), at most 3 x VMD_SS_SEG_MAX = 48 KB
+    __shared__ unsigned s_pop[VMD_SS_CODES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t b = blockIdx.x;
+    const int nseg = p.nseg, W = p.W;
+    uint8_t* s_turn = (uint8_t*)s_dyn;              // bit 0 / 1 / 2: turn_3 / turn_4 / turn_5 starts here
+    uint8_t* s_c0 = s_turn + ((nseg + 15) & ~15);
+    uint8_t* s_c1 = s_c0 + ((nseg + 15) & ~15);
+    const unsigned long long* HB = p.hb + b * nseg * W;
+    const unsigned long long* BP = p.bp + b * nseg * W;
+    const unsigned long long* BA = p.ba + b * nseg * W;
+    if (tid < VMD_SS_CODES) s_pop[tid] = 0u;
+    // pass 1: bridge / sheet; the turn bits
+    for (int i = wave; i < nseg; i += 4) {
+        bool bridge = false, ladder = false;
+        for (int w0 = 0; w0 < W; w0 += 64) {
+            const int w = w0 + lane;
+            if (w < W) {
+                const unsigned long long* bp = BP + (size_t)i * W;
+                const unsigned long long* ba = BA + (size_t)i * W;
+                bridge = bridge || (bp[w] | ba[w]) != 0ull;
+                unsigned long long pn = 0ull, an = 0ull;       // partners (j) whose neighbour continues the ladder
+                if (i + 1 < nseg) { pn |= vmd_ss_down(bp + W, w, W); an |= vmd_ss_up(ba + W, w); }
+                if (i > 0) { pn |= vmd_ss_up(bp - W, w); an |= vmd_ss_down(ba - W, w, W); }
+                ladder = ladder || ((bp[w] & pn) | (ba[w] & an)) != 0ull;
+            }
+        }
+        const unsigned long long mb = __ballot(bridge ? 1 : 0), ml = __ballot(ladder ? 1 : 0);
+        if (lane == 0) {
+            s_c0[i] = ml ? 8 : (mb ? 7 : 0);
+            unsigned tb = 0u;
+            for (int n = 3; n <= 5; ++n) {
+                const int j = i + n;
+                if (j < nseg && p.rng[j] == p.rng[i] && ((HB[(size_t)i * W + (j >> 6)] >> (j & 63)) & 1ull)) tb |= 1u << (n - 3);
+            }
+            s_turn[i] = (uint8_t)tb;
+        }
+    }
+    __syncthreads();
+    // pass 2: two consecutive 4-turns write an alpha helix over anything
+    for (int i = tid; i < nseg; i += 256) {
+        bool hx = false;
+        for (int s = vmd_imax(i - 3, 1); s <= i; ++s) hx = hx || ((s_turn[s - 1] & 2u) && (s_turn[s] & 2u));
+        s_c1[i] = hx ? 5 : s_c0[i];
+    }
+    __syncthreads();
+    // pass 3: two consecutive 3-turns, three unassigned segments
+    for (int i = tid; i < nseg; i += 256) {
+        bool hx = false;
+        for (int s = vmd_imax(i - 2, 1); s <= i; ++s)
+            hx = hx || ((s_turn[s - 1] & 1u) && (s_turn[s] & 1u) && s_c1[s] == 0 && s_c1[s + 1] == 0 && s_c1[s + 2] == 0);
+        s_c0[i] = hx ? 4 : s_c1[i];
+    }
+    __syncthreads();
+    // pass 4: two consecutive 5-turns, five unassigned segments
+    for (int i = tid; i < nseg; i += 256) {
+        bool hx = false;
+        for (int s = vmd_imax(i - 4, 1); s <= i; ++s)
+            hx = hx || ((s_turn[s - 1] & 4u) && (s_turn[s] & 4u) && s_c0[s] == 0 && s_c0[s + 1] == 0 && s_c0[s + 2] == 0 && s_c0[s + 3] == 0
+                        && s_c0[s + 4] == 0);
+        s_c1[i] = hx ? 6 : s_c0[i];
+    }
+    __syncthreads();
+    // passes 5 - 7: turn, bend, coil; the class row and the populations
+    const float* fx = p.xyz + b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, (int)b, p.pbc);
+    unsigned cnt[VMD_SS_CODES];
+#pragma unroll
+    for (int k = 0; k < VMD_SS_CODES; ++k) cnt[k] = 0u;
+    for (int i0 = 0; i0 < nseg; i0 += 256) {
+        const int i = i0 + tid;
+        int code = -1;
+        if (i < nseg) {
+            code = s_c1[i];
+            if (code == 0) {
+                bool turn = false;
+                for (int n = 3; n <= 5; ++n)
+                    for (int k = 1; k < n; ++k) turn = turn || (i - k >= 0 && (s_turn[i - k] & (1u << (n - 3))));
+                code = turn ? 2 : 1;
+                if (!turn && i >= 2 && i + 2 < nseg && p.rng[i - 2] == p.rng[i] && p.rng[i + 2] == p.rng[i]) {
+                    const int i0a = p.ca[i - 2], i1a = p.ca[i], i2a = p.ca[i + 2];
+                    float a[3] = {fx[i1a] - fx[i0a], fy[i1a] - fy[i0a], fz[i1a] - fz[i0a]};
+                    float c[3] = {fx[i2a] - fx[i1a], fy[i2a] - fy[i1a], fz[i2a] - fz[i1a]};
+                    vmd_mi3_rintf(bx, a[0], a[1], a[2]);
+                    vmd_mi3_rintf(bx, c[0], c[1], c[2]);
+                    const double aa = vmd_dot_d(a[0], a[1], a[2], a[0], a[1], a[2]), cc = vmd_dot_d(c[0], c[1], c[2], c[0], c[1], c[2]);
+                    const double q = aa * cc;
+                    if (q > 0.0 && vmd_dot_d(a[0], a[1], a[2], c[0], c[1], c[2]) / sqrt(q) < 0.3420201433256687) code = 3;
+                }
+            }
+            p.cls[b * nseg + i] = (float)code;
+        }
+#pragma unroll
+        for (int k = 1; k < VMD_SS_CODES; ++k) cnt[k] += (unsigned)__popcll(__ballot(code == k ? 1 : 0));
+    }
+    if (lane == 0)
+        for (int k = 1; k < VMD_SS_CODES; ++k) if (cnt[k]) atomicAdd(&s_pop[k], cnt[k]);
+    __syncthreads();
+    if (tid < VMD_SS_CODES) p.pop[b * VMD_SS_CODES + tid] = (float)s_pop[tid];
+}
+
 // ------------------------------------------------------------------------------------------------ K5c: shape_weights
 
 // The reduction order is a function of the set size alone: a set is cut into chunks of VMD_SHAPE_CHUNK atoms; atom j of a chunk belongs to
@@ -4434,6 +4695,60 @@ extern "C" int vmd_hip_rama_bin(void* stream, const float* angles, int F, const 
     if (!angles || !rama_class || !link || !counts || (long long)F * nseg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     vmd_rama_params_t p{angles, F, nseg, row_mask, rama_class, link, skip_ends, (unsigned long long*)counts, (unsigned long long*)sums};
     hipLaunchKernelGGL(k_rama_bin, dim3((unsigned)(((long long)F * nseg + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t vmd_hip_ss_scratch_words(int B, int nseg) {
+    if (B <= 0 || nseg <= 0) return 0;
+    return 4 * (size_t)B * (size_t)nseg * (size_t)((nseg + 63) / 64);
+}
+
+// the three launches of a secondary-structure batch share one parameter block; every index a kernel forms is checked here, once
+static int vmd_ss_params(vmd_ss_params_t* p, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                         int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                         const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch) {
+    if (!xyz || !boxes || !n || !ca || !c || !o || !rng || !pro || !nbmask || !scratch || nseg > VMD_SS_SEG_MAX) return (int)hipErrorInvalidValue;
+    const long long W = (nseg + 63) / 64;
+    if ((long long)B * nseg * W > 0x7fffffffLL || (long long)B * W * W > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const size_t rows = (size_t)B * (size_t)nseg * (size_t)W;
+    unsigned long long* s = (unsigned long long*)scratch;
+    *p = vmd_ss_params_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B, n, ca, c, o, rng, pro, (const unsigned long long*)nbmask, nseg, (int)W,
+                         s, s + rows, s + 2 * rows, s + 3 * rows, nullptr, nullptr};
+    return 0;
+}
+
+extern "C" int vmd_hip_ss_hbond(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                                int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                                const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch) {
+    if (B <= 0 || nseg <= 0) return 0;
+    vmd_ss_params_t p;
+    if (int rc = vmd_ss_params(&p, xyz, frame_stride, row_stride, boxes, pbc_flags, B, nseg, n, ca, c, o, rng, pro, nbmask, scratch)) return rc;
+    hipLaunchKernelGGL(k_ss_hbond, dim3((unsigned)((long long)B * p.W * p.W)), dim3(64), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_ss_bridges(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                                  int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                                  const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch) {
+    if (B <= 0 || nseg <= 0) return 0;
+    vmd_ss_params_t p;
+    if (int rc = vmd_ss_params(&p, xyz, frame_stride, row_stride, boxes, pbc_flags, B, nseg, n, ca, c, o, rng, pro, nbmask, scratch)) return rc;
+    hipLaunchKernelGGL(k_ss_bridges, dim3((unsigned)(((long long)B * nseg * p.W + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_ss_assign(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                                 int B, int nseg, const int32_t* n, const int32_t* ca, const int32_t* c, const int32_t* o, const int32_t* rng,
+                                 const uint8_t* pro, const uint64_t* nbmask, uint64_t* scratch, float* cls, float* pop) {
+    if (B <= 0 || nseg <= 0) return 0;
+    vmd_ss_params_t p;
+    if (int rc = vmd_ss_params(&p, xyz, frame_stride, row_stride, boxes, pbc_flags, B, nseg, n, ca, c, o, rng, pro, nbmask, scratch)) return rc;
+    if (!cls || !pop) return (int)hipErrorInvalidValue;
+    p.cls = cls; p.pop = pop;
+    hipLaunchKernelGGL(k_ss_assign, dim3((unsigned)B), dim3(256), 3 * (size_t)((nseg + 15) & ~15), (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

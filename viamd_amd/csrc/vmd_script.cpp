@@ -921,6 +921,28 @@ extern "C" vmd_backbone_owned_t* vmd_topology_backbone(const vmd_topology_t* top
     }
 }
 
+// the carbonyl oxygen of every segment (DECISION D-SS-TOPOLOGY-O): by name, in the residue of the segment's CA
+extern "C" size_t vmd_topology_backbone_oxygens(const vmd_topology_t* topology, const vmd_backbone_t* backbone, int32_t* out, size_t cap) {
+    if (!topology || !backbone) { vmd_set_last_error("vmd_topology_backbone_oxygens: NULL argument"); return 0; }
+    try {
+        Topo topo(topology);
+        static const char* const want[4] = {"O", "OT1", "O1", "OC1"};
+        for (size_t s = 0; s < backbone->num_segments; ++s) {
+            const int32_t ca = backbone->ca ? backbone->ca[s] : -1;
+            if (ca < 0 || (size_t)ca >= topo.n) fail("backbone CA of segment %zu is atom %d (the topology has %zu atoms)", s, ca, topo.n);
+            int32_t o = -1;
+            const size_t r = topology->residue_index ? (size_t)topology->residue_index[ca] : 0;
+            for (int k = 0; k < 4 && o < 0; ++k)
+                for (int32_t i : topo.res_atoms[r]) if (topo.names[i] == want[k]) { o = i; break; }
+            if (out && s < cap) out[s] = o;
+        }
+        return backbone->num_segments;
+    } catch (const std::exception& e) {
+        vmd_set_last_error(e.what());
+        return 0;
+    }
+}
+
 extern "C" const vmd_backbone_t* vmd_backbone_view(const vmd_backbone_owned_t* backbone) { return backbone ? &backbone->view : nullptr; }
 
 extern "C" void vmd_backbone_free(vmd_backbone_owned_t* backbone) { delete backbone; }

@@ -252,6 +252,26 @@ class ScriptIR:
                          cls.ctypes.data_as(L.c_uint8_p) if cls is not None else None)
         self._check(self.lib.vmd_ir_add_ramachandran(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(bb)))
 
+    def add_secondary_structure(self, names, n, ca, c, o, offsets, cls=None):
+        """`{classes, populations} = secondary_structure(backbone, o)`: names = (class table, populations); n / ca / c / o:
+        the backbone atoms per segment, o = -1 where a segment has no carbonyl oxygen; offsets: num_ranges + 1 segment offsets of the
+        chains; cls: the rama_class bytes of add_ramachandran, of which 2 marks a proline (None: no proline)."""
+        names = list(names)
+        assert len(names) == 2, "secondary_structure defines two properties"
+        n_, np_ = _idx(n)
+        a_, ap = _idx(ca)
+        c_, cp = _idx(c)
+        o_, op = (None, None) if o is None else _idx(o)
+        if not (n_.size == a_.size == c_.size) or (o_ is not None and o_.size != n_.size):
+            raise ValueError("n, ca, c and o must list one atom per segment each")
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        cl = None if cls is None else np.ascontiguousarray(cls, dtype=np.uint8).reshape(-1)
+        if cl is not None and cl.size != n_.size:
+            raise ValueError("cls must hold one byte per segment")
+        bb = L.BackboneC(n_.size, np_, ap, cp, max(off.size, 1) - 1, off.ctypes.data_as(C.POINTER(C.c_uint32)) if off.size else None,
+                         cl.ctypes.data_as(L.c_uint8_p) if cl is not None else None)
+        self._check(self.lib.vmd_ir_add_secondary_structure(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(bb), op))
+
     @staticmethod
     def _names3(names):
         import ctypes as C
@@ -349,6 +369,12 @@ class PropertyDataView:
         """a MAP property's u64 accumulators as [y, x, class]"""
         assert self.is_map
         return self.counts.reshape(L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES)
+
+    @property
+    def ss_classes(self):
+        """the class table of a secondary_structure statement as uint8 [frames, nseg]: the VMD_SS_* codes, 0 = a frame that
+        was not evaluated (a copy: the float rows hold the codes exactly)"""
+        return self.values.reshape(self.c.dim[0], self.c.dim[1]).astype(np.uint8)
 
     @property
     def weights64(self):

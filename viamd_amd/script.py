@@ -906,6 +906,44 @@ def backbone_from_topology(topo):
                 range_offsets=np.array(offsets, np.uint32), rama_class=cls)
 
 
+def backbone_oxygens_from_topology(topo, bb):
+    """The carbonyl oxygen of every segment of the backbone `bb` (the dict of backbone_from_topology), for
+    ScriptIR.add_secondary_structure (DECISION D-SS-TOPOLOGY-O; the twin of vmd_topology_backbone_oxygens): the first atom of
+    the CA's residue named "O", failing that "OT1", then "O1", then "OC1", else -1.  Returns int32 [nseg]."""
+    o = np.full(len(bb["ca"]), -1, np.int32)
+    for s, ca in enumerate(bb["ca"]):
+        atoms = topo.residue_atoms(int(topo.residue_index[int(ca)]))
+        for want in ("O", "OT1", "O1", "OC1"):
+            hit = [int(i) for i in atoms if str(topo.names[i]) == want]
+            if hit:
+                o[s] = hit[0]
+                break
+    return o
+
+
+def backbone_oxygens_from_topology_native(topo, bb, lib=None):
+    """The same through the C ABI (vmd_topology_backbone_oxygens).  Raises ScriptError with the library's message."""
+    import ctypes as C
+    lib = lib or L.default_lib()
+    n = topo.num_atoms
+
+    def strings(arr):
+        return (C.c_char_p * max(n, 1))(*[str(v).encode() for v in arr])
+
+    el, nm, rn = strings(topo.elements), strings(topo.names), strings(topo.resnames)
+    ri = np.ascontiguousarray(topo.residue_index, np.int32)
+    tc = L.TopologyC(n, el, nm, rn, ri.ctypes.data_as(L.c_int32_p), None)
+    n_, a_, c_ = (np.ascontiguousarray(bb[k], np.int32) for k in ("n", "ca", "c"))
+    off = np.ascontiguousarray(bb["range_offsets"], np.uint32)
+    bc = L.BackboneC(a_.size, n_.ctypes.data_as(L.c_int32_p), a_.ctypes.data_as(L.c_int32_p), c_.ctypes.data_as(L.c_int32_p),
+                     max(off.size, 1) - 1, off.ctypes.data_as(C.POINTER(C.c_uint32)), None)
+    o = np.full(a_.size, -1, np.int32)
+    got = lib.vmd_topology_backbone_oxygens(C.byref(tc), C.byref(bc), o.ctypes.data_as(L.c_int32_p), o.size)
+    if got != a_.size:
+        raise ScriptError(lib.last_error())
+    return o
+
+
 def backbone_from_topology_native(topo, lib=None):
     """The same through the C ABI (vmd_topology_backbone): what a C / C++ host calls.  Raises ScriptError with the library's message."""
     import ctypes as C
