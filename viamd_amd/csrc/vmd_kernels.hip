@@ -322,6 +322,44 @@ __device__ __forceinline__ void vmd_store_aos(float* aos, size_t slot, float x, 
     const vmd_f4a v = {x, y, z, 0.0f};
     *(vmd_f4a*)(aos + 4 * slot) = v;
 }
+// one atom of the sorted copy at slot `pos` of frame b: ONE record of the staging buffer when the build has one, else the three SoA rows
+__device__ __forceinline__ void vmd_store_sorted(const vmd_cells_params_t& p, int b, uint32_t pos, float x, float y, float z) {
+    if (p.aos) { vmd_store_aos(p.aos, (size_t)b * p.nsel_pad + pos, x, y, z); return; }
+    float* s = p.sorted + (size_t)b * 3 * p.nsel_pad;
+    s[pos] = x; s[p.nsel_pad + pos] = y; s[2 * (size_t)p.nsel_pad + pos] = z;
+}
+
+// Hillis-Steele inclusive scan of one value per thread of an NT-thread block over the CALLER's part[NT] (no helper of the builds owns LDS:
+// k_cells_pen_sort gives all of its to the dynamic part) -> the thread's inclusive value; the total stays readable in part[NT - 1]
+template <int NT>
+__device__ __forceinline__ uint32_t vmd_block_scan(uint32_t* part, int tid, uint32_t v) {
+    part[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < NT; o <<= 1) {
+        const uint32_t u = tid >= o ? part[tid - o] : 0u;
+        __syncthreads();
+        part[tid] += u;
+        __syncthreads();
+    }
+    return part[tid];
+}
+// thread tid of NT owns the contiguous stretch [beg, end) of a table of n entries (empty for the last threads of a short table)
+struct vmd_stretch_t { int beg, end; };
+template <int NT>
+__device__ __forceinline__ vmd_stretch_t vmd_stretch(int n, int tid) {
+    const int per = (n + NT - 1) / NT, beg = tid * per;
+    return {beg, beg + per < n ? beg + per : n};
+}
+// exclusive prefix over a table of n entries, a stretch per thread: count(c) is entry c's population, start(c, first) takes its first slot
+template <int NT, class Count, class Start>
+__device__ __forceinline__ void vmd_stretch_scan(uint32_t* part, int n, int tid, Count count, Start start) {
+    const vmd_stretch_t st = vmd_stretch<NT>(n, tid);
+    uint32_t sum = 0;
+    for (int c = st.beg; c < st.end; ++c) sum += count(c);
+    uint32_t run = vmd_block_scan<NT>(part, tid, sum) - sum;
+    for (int c = st.beg; c < st.end; ++c) { const uint32_t m = count(c); start(c, run); run += m; }
+}
+
 __global__ __launch_bounds__(256) void k_cells_repack(const float* __restrict__ aos, float* __restrict__ sorted, int nsel, int nsel_pad) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
@@ -369,15 +407,7 @@ __global__ __launch_bounds__(1024) void k_cells_scan(const uint32_t* __restrict_
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = c0 + k < ncell ? cnt[c0 + k] : 0u;
         const uint32_t s = v[0] + v[1] + v[2] + v[3];
-        part[tid] = s;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const uint32_t u = tid >= o ? part[tid - o] : 0u;
-            __syncthreads();
-            part[tid] += u;
-            __syncthreads();
-        }
-        uint32_t run = carry + part[tid] - s;   // exclusive
+        uint32_t run = carry + vmd_block_scan<1024>(part, tid, s) - s;   // exclusive
         const uint32_t total = part[1023];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { if (c0 + k < ncell) out[c0 + k] = run; run += v[k]; }
@@ -401,15 +431,8 @@ __global__ __launch_bounds__(256) void k_cells_scatter(vmd_cells_params_t p) {
             pos[u] = p.cell_start[(size_t)b * (p.grid.ncell + 1) + c] + p.rank[(size_t)b * p.nsel + t];
         }
     }
-    float* s = p.sorted + (size_t)b * 3 * p.nsel_pad;
 #pragma unroll
-    for (int u = 0; u < VMD_CELLS_ILP; ++u) {
-        if (pos[u] == 0xffffffffu) continue;
-        if (p.aos) { vmd_store_aos(p.aos, (size_t)b * p.nsel_pad + pos[u], xw[u], yw[u], zw[u]); continue; }
-        s[pos[u]] = xw[u];
-        s[p.nsel_pad + pos[u]] = yw[u];
-        s[2 * (size_t)p.nsel_pad + pos[u]] = zw[u];
-    }
+    for (int u = 0; u < VMD_CELLS_ILP; ++u) if (pos[u] != 0xffffffffu) vmd_store_sorted(p, b, pos[u], xw[u], yw[u], zw[u]);
 }
 
 // Fused build for grids whose cell table fits in LDS: ONE 1024-thread block per frame does count (LDS atomics) ->
@@ -427,33 +450,14 @@ __global__ __launch_bounds__(1024) void k_cells_fused(vmd_cells_params_t p) {
     float xw, yw, zw;
     for (int t = tid; t < p.nsel; t += 1024) atomicAdd(&s_cnt[vmd_cell_of(p, b, t, xw, yw, zw)], 1u);
     __syncthreads();
-    // exclusive scan, same scheme as k_cells_scan
-    const int per = (ncell + 1023) / 1024;
-    const int beg = tid * per;
-    const int end = beg + per < ncell ? beg + per : ncell;
-    uint32_t sum = 0;
-    for (int c = beg; c < end; ++c) sum += s_cnt[c];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = tid >= o ? s_part[tid - o] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
+    // the counters become cursors (a stretch of ceil(ncell / 1024) cells per thread: the table is in LDS, there are no loads to coalesce)
     uint32_t* out = p.cell_start + (size_t)b * (ncell + 1);
-    for (int c = beg; c < end; ++c) { const uint32_t n = s_cnt[c]; s_cnt[c] = run; out[c] = run; run += n; }
+    vmd_stretch_scan<1024>(s_part, ncell, tid, [&](int c) { return s_cnt[c]; }, [&](int c, uint32_t first) { s_cnt[c] = first; out[c] = first; });
     if (tid == 1023) out[ncell] = s_part[1023];
     __syncthreads();
-    float* srt = p.sorted + (size_t)b * 3 * p.nsel_pad;
     for (int t = tid; t < p.nsel; t += 1024) {
         const uint32_t c = vmd_cell_of(p, b, t, xw, yw, zw);
-        const uint32_t pos = atomicAdd(&s_cnt[c], 1u);
-        if (p.aos) { vmd_store_aos(p.aos, (size_t)b * p.nsel_pad + pos, xw, yw, zw); continue; }
-        srt[pos] = xw;
-        srt[p.nsel_pad + pos] = yw;
-        srt[2 * (size_t)p.nsel_pad + pos] = zw;
+        vmd_store_sorted(p, b, atomicAdd(&s_cnt[c], 1u), xw, yw, zw);
     }
 }
 
@@ -467,6 +471,10 @@ struct vmd_cells_split_t {
     uint32_t* table;     // [B][G][ncell]
     int G; int slice;    // atoms per block (multiple of 1024)
 };
+// block g's slice of the selection: [t0, t1)
+__device__ __forceinline__ void vmd_slice(const vmd_cells_split_t& q, int g, int& t0, int& t1) {
+    t0 = g * q.slice; t1 = t0 + q.slice < q.c.nsel ? t0 + q.slice : q.c.nsel;
+}
 
 __global__ __launch_bounds__(1024) void k_cells_split_count(vmd_cells_split_t q) {
     HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
@@ -474,9 +482,9 @@ __global__ __launch_bounds__(1024) void k_cells_split_count(vmd_cells_split_t q)
     const int ncell = q.c.grid.ncell;
     for (int c = tid; c < ncell; c += 1024) s_dyn[c] = 0u;
     __syncthreads();
-    const int t1 = (g + 1) * q.slice < q.c.nsel ? (g + 1) * q.slice : q.c.nsel;
+    int t0, t1; vmd_slice(q, g, t0, t1);
     float xw, yw, zw;
-    for (int t = g * q.slice + tid; t < t1; t += 1024) atomicAdd(&s_dyn[vmd_cell_of(q.c, b, t, xw, yw, zw)], 1u);
+    for (int t = t0 + tid; t < t1; t += 1024) atomicAdd(&s_dyn[vmd_cell_of(q.c, b, t, xw, yw, zw)], 1u);
     __syncthreads();
     uint32_t* out = q.table + ((size_t)b * q.G + g) * ncell;
     for (int c = tid; c < ncell; c += 1024) out[c] = s_dyn[c];
@@ -493,21 +501,14 @@ __global__ __launch_bounds__(1024) void k_cells_split_scan(uint32_t* __restrict_
         const int c = base + tid;
         uint32_t s = 0;
         if (c < ncell) for (int g = 0; g < G; ++g) s += tb[(size_t)g * ncell + c];
-        part[tid] = s;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const uint32_t v = tid >= o ? part[tid - o] : 0u;
-            __syncthreads();
-            part[tid] += v;
-            __syncthreads();
-        }
+        const uint32_t incl = vmd_block_scan<1024>(part, tid, s);
         if (c < ncell) {
-            uint32_t run = carry + part[tid] - s;   // exclusive
+            uint32_t run = carry + incl - s;         // exclusive
             out[c] = run;
             for (int g = 0; g < G; ++g) { const uint32_t n = tb[(size_t)g * ncell + c]; tb[(size_t)g * ncell + c] = run; run += n; }
         }
         carry += part[1023];
-        __syncthreads();
+        __syncthreads();                             // part[] is rewritten by the next row
     }
     if (tid == 0) out[ncell] = carry;
 }
@@ -519,16 +520,11 @@ __global__ __launch_bounds__(1024) void k_cells_split_scatter(vmd_cells_split_t 
     const uint32_t* first = q.table + ((size_t)b * q.G + g) * ncell;
     for (int c = tid; c < ncell; c += 1024) s_dyn[c] = first[c];
     __syncthreads();
-    const int t1 = (g + 1) * q.slice < q.c.nsel ? (g + 1) * q.slice : q.c.nsel;
-    float* srt = q.c.sorted + (size_t)b * 3 * q.c.nsel_pad;
+    int t0, t1; vmd_slice(q, g, t0, t1);
     float xw, yw, zw;
-    for (int t = g * q.slice + tid; t < t1; t += 1024) {
+    for (int t = t0 + tid; t < t1; t += 1024) {
         const uint32_t c = vmd_cell_of(q.c, b, t, xw, yw, zw);
-        const uint32_t pos = atomicAdd(&s_dyn[c], 1u);
-        if (q.c.aos) { vmd_store_aos(q.c.aos, (size_t)b * q.c.nsel_pad + pos, xw, yw, zw); continue; }
-        srt[pos] = xw;
-        srt[q.c.nsel_pad + pos] = yw;
-        srt[2 * (size_t)q.c.nsel_pad + pos] = zw;
+        vmd_store_sorted(q.c, b, atomicAdd(&s_dyn[c], 1u), xw, yw, zw);
     }
 }
 
@@ -557,28 +553,69 @@ struct vmd_bin_params_t {
     int rec3;                        // 1: 12-byte records {x, y, z} (the fine cell follows from x alone: x-periodic, non-triclinic cells)
 };
 #define VMD_BIN_ILP 4          // atoms per thread: 4096-atom slices (8 per thread: measured slower, profiles/r02d_ab.txt)
+// The bucket record, the one place that knows its two formats: rec3 ? 12 bytes {x, y, z} : 16 bytes {x, y, z, fine cell}.  `bk` is the first
+// record of a run (a frame's buckets start at the same float whichever the format: vmd_rec_run), i counts records from there.
+template <class F>
+__device__ __forceinline__ F* vmd_rec_run(F* bucket, int b, int total_cap, int rec3, uint32_t first) {
+    return bucket + 4 * (size_t)b * total_cap + (size_t)(rec3 ? 3 : 4) * first;
+}
+__device__ __forceinline__ void vmd_rec_put(float* bk, int rec3, size_t i, float x, float y, float z, uint32_t cx) {
+    if (rec3) {
+        float* r = bk + 3 * i;
+        r[0] = x; r[1] = y; r[2] = z;
+    } else {
+        const vmd_f4a v = {x, y, z, __int_as_float((int)cx)};
+        *(vmd_f4a*)(bk + 4 * i) = v;
+    }
+}
+// the fine cell alone: reads word 3 (16-byte records) or x (12-byte records: the cell follows from x exactly as vmd_cell_of computed it,
+// inv_cx = (float)nxf * the frame's 1 / Lx), nothing else
+__device__ __forceinline__ uint32_t vmd_rec_get_cell(const float* bk, int rec3, size_t i, float inv_cx, int nxf) {
+    return rec3 ? (uint32_t)vmd_cell_coord(bk[3 * i], inv_cx, nxf) : (uint32_t)__float_as_int(bk[4 * i + 3]);
+}
+__device__ __forceinline__ uint32_t vmd_rec_get(const float* bk, int rec3, size_t i, float inv_cx, int nxf, float& x, float& y, float& z) {
+    if (rec3) {
+        const float* r = bk + 3 * i;
+        x = r[0]; y = r[1]; z = r[2];
+        return (uint32_t)vmd_cell_coord(x, inv_cx, nxf);
+    }
+    const vmd_f4a v = *(const vmd_f4a*)(bk + 4 * i);
+    x = v[0]; y = v[1]; z = v[2];
+    return (uint32_t)__float_as_int(v[3]);
+}
+
+// The head of level 1: the thread's VMD_BIN_ILP atoms of block g's slice, wrapped, with pencil, fine cell and rank among the block's atoms of
+// that pencil (pen = 0xffffffff: no atom).  Zeroes the block's pencil counters s_cnt[npen] first; they are complete when it returns.
+struct vmd_bin_atoms_t {
+    float xw[VMD_BIN_ILP], yw[VMD_BIN_ILP], zw[VMD_BIN_ILP];
+    uint32_t pen[VMD_BIN_ILP], cx[VMD_BIN_ILP], rank[VMD_BIN_ILP];
+};
+__device__ __forceinline__ void vmd_bin_head(const vmd_bin_params_t& q, uint32_t* s_cnt, int g, int b, int tid, vmd_bin_atoms_t& a) {
+    const uint32_t nxf = (uint32_t)q.c.grid.nxf;
+    for (int c = tid; c < q.npen; c += 1024) s_cnt[c] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < VMD_BIN_ILP; ++u) {
+        const int t = (g * VMD_BIN_ILP + u) * 1024 + tid;
+        a.pen[u] = 0xffffffffu;
+        if (t < q.c.nsel) {
+            const uint32_t cell = vmd_cell_of(q.c, b, t, a.xw[u], a.yw[u], a.zw[u]);
+            a.pen[u] = cell / nxf;
+            a.cx[u] = cell - a.pen[u] * nxf;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < VMD_BIN_ILP; ++u) if (a.pen[u] != 0xffffffffu) a.rank[u] = atomicAdd(&s_cnt[a.pen[u]], 1u);
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(1024) void k_cells_bin(vmd_bin_params_t q) {
     HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
     uint32_t* s_cnt = s_dyn;                 // [npen] atoms of this block per pencil, then the block's first slot in the bucket
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int npen = q.npen, nxf = q.c.grid.nxf;
-    for (int c = tid; c < npen; c += 1024) s_cnt[c] = 0u;
-    __syncthreads();
-    float xw[VMD_BIN_ILP], yw[VMD_BIN_ILP], zw[VMD_BIN_ILP];
-    uint32_t pen[VMD_BIN_ILP], cx[VMD_BIN_ILP], rank[VMD_BIN_ILP];
-#pragma unroll
-    for (int u = 0; u < VMD_BIN_ILP; ++u) {
-        const int t = (g * VMD_BIN_ILP + u) * 1024 + tid;
-        pen[u] = 0xffffffffu;
-        if (t < q.c.nsel) {
-            const uint32_t cell = vmd_cell_of(q.c, b, t, xw[u], yw[u], zw[u]);
-            pen[u] = cell / (uint32_t)nxf;
-            cx[u] = cell - pen[u] * (uint32_t)nxf;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < VMD_BIN_ILP; ++u) if (pen[u] != 0xffffffffu) rank[u] = atomicAdd(&s_cnt[pen[u]], 1u);
-    __syncthreads();
+    const int npen = q.npen;
+    vmd_bin_atoms_t a;
+    vmd_bin_head(q, s_cnt, g, b, tid, a);
     uint32_t* gcount = q.pen_count + (size_t)b * npen;
     for (int c = tid; c < npen; c += 1024) {
         const uint32_t n = s_cnt[c];
@@ -586,68 +623,21 @@ __global__ __launch_bounds__(1024) void k_cells_bin(vmd_bin_params_t q) {
     }
     if (!q.bucket) return;                   // counting mode: the host only wants the populations
     __syncthreads();
-    float* bk = q.bucket + (size_t)b * q.total_cap * 4;
+    float* bk = vmd_rec_run(q.bucket, b, q.total_cap, q.rec3, 0u);
 #pragma unroll
     for (int u = 0; u < VMD_BIN_ILP; ++u) {
-        if (pen[u] == 0xffffffffu) continue;
-        const uint32_t off = q.pen_off[pen[u]], cap = q.pen_off[pen[u] + 1] - off;
-        const uint32_t slot = s_cnt[pen[u]] + rank[u];
-        if (slot < cap) {
-            if (q.rec3) {
-                float* r = bk + 3 * (size_t)(off + slot);
-                r[0] = xw[u]; r[1] = yw[u]; r[2] = zw[u];
-            } else {
-                const vmd_f4a v = {xw[u], yw[u], zw[u], __int_as_float((int)cx[u])};
-                *(vmd_f4a*)(bk + 4 * (size_t)(off + slot)) = v;
-            }
-        } else {
-            atomicOr(q.overflow, q.overflow_bit);
-        }
+        if (a.pen[u] == 0xffffffffu) continue;
+        const uint32_t off = q.pen_off[a.pen[u]], cap = q.pen_off[a.pen[u] + 1] - off;
+        const uint32_t slot = s_cnt[a.pen[u]] + a.rank[u];
+        if (slot < cap) vmd_rec_put(bk, q.rec3, (size_t)(off + slot), a.xw[u], a.yw[u], a.zw[u], a.cx[u]);
+        else atomicOr(q.overflow, q.overflow_bit);
     }
 }
 
-// Level 1 with a block-local sort (the default): k_cells_bin stores every record from the lane that wrapped the atom, i.e. a wave's 64
-// records go to ~64 different buckets - one partial-line write transaction each.  Here the block first orders its 4 096 records by
-// pencil in LDS (rank inside the pencil from the LDS counter, the pencil's first slot from a block scan of the counters), then
-// consecutive lanes write consecutive records: a (block, pencil) run of ~14 records leaves as one or two coalesced stores.
-// LDS: 3 tables of npen words + 1 040 scan words + 4 096 records of 4 (12-byte output) or 5 (16-byte output) words.
-__global__ __launch_bounds__(1024) void k_cells_bin_sorted(vmd_bin_params_t q) {
-    HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
-    const int npen = q.npen, nxf = q.c.grid.nxf;
-    const int rw = q.rec3 ? 4 : 5;             // words per LDS record: x, y, z, pencil (, fine cell)
-    uint32_t* s_cnt = s_dyn;                   // [npen] atoms of this block per pencil
-    uint32_t* s_off = s_dyn + npen;            // [npen] first LDS slot of the pencil's run
-    uint32_t* s_gbase = s_dyn + 2 * npen;      // [npen] first slot of the run in the pencil's bucket
-    uint32_t* s_p = s_dyn + 3 * npen;          // [1024 + 16] scan partials
-    uint32_t* s_rec = s_p + 1040;              // [4096][rw]
-    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int c = tid; c < npen; c += 1024) s_cnt[c] = 0u;
-    __syncthreads();
-    float xw[VMD_BIN_ILP], yw[VMD_BIN_ILP], zw[VMD_BIN_ILP];
-    uint32_t pen[VMD_BIN_ILP], cx[VMD_BIN_ILP], rank[VMD_BIN_ILP];
-#pragma unroll
-    for (int u = 0; u < VMD_BIN_ILP; ++u) {
-        const int t = (g * VMD_BIN_ILP + u) * 1024 + tid;
-        pen[u] = 0xffffffffu;
-        if (t < q.c.nsel) {
-            const uint32_t cell = vmd_cell_of(q.c, b, t, xw[u], yw[u], zw[u]);
-            pen[u] = cell / (uint32_t)nxf;
-            cx[u] = cell - pen[u] * (uint32_t)nxf;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < VMD_BIN_ILP; ++u) if (pen[u] != 0xffffffffu) rank[u] = atomicAdd(&s_cnt[pen[u]], 1u);
-    __syncthreads();
-    // reserve the runs in the buckets, and scan the counters: thread t owns the counters [t * per, t * per + per)
-    uint32_t* gcount = q.pen_count + (size_t)b * npen;
-    const int per = (npen + 1023) / 1024;
-    const int cb = tid * per, ce = cb + per < npen ? cb + per : npen;
-    uint32_t sum = 0;
-    for (int c = cb; c < ce; ++c) {
-        const uint32_t n = s_cnt[c];
-        s_gbase[c] = n ? atomicAdd(&gcount[c], n) : 0u;
-        sum += n;
-    }
+// k_cells_bin_sorted's scan of one value per thread of its 1024-thread block, over the caller's s_p[1024 + 16]: two block barriers against the
+// twenty of vmd_block_scan.  A measured choice, as the block scan is k_cells_pen_sort's: the two are not to be merged.  -> inclusive value
+__device__ __forceinline__ uint32_t vmd_wave_scan_1024(uint32_t* s_p, int tid, uint32_t sum, uint32_t& total) {
+    const int lane = tid & 63, wave = tid >> 6;
     volatile uint32_t* vp = s_p;                             // lanes exchange through LDS between wave barriers: no caching in registers
     vp[tid] = sum;
     __builtin_amdgcn_wave_barrier();
@@ -668,37 +658,57 @@ __global__ __launch_bounds__(1024) void k_cells_bin_sorted(vmd_bin_params_t q) {
         }
     }
     __syncthreads();
-    const uint32_t ntot = s_p[1024 + 15];
-    uint32_t run = (s_p[tid] - sum) + (wave ? s_p[1024 + wave - 1] : 0u);
-    for (int c = cb; c < ce; ++c) { s_off[c] = run; run += s_cnt[c]; }
-    if (!q.bucket) return;                   // counting mode: the host only wants the populations
+    total = s_p[1024 + 15];
+    return s_p[tid] + (wave ? s_p[1024 + wave - 1] : 0u);
+}
+
+// Level 1 with a block-local sort (the default): k_cells_bin stores every record from the lane that wrapped the atom, i.e. a wave's 64
+// records go to ~64 different buckets - one partial-line write transaction each.  Here the block first orders its 4 096 records by
+// pencil in LDS (rank inside the pencil from the LDS counter, the pencil's first slot from a block scan of the counters), then
+// consecutive lanes write consecutive records: a (block, pencil) run of ~14 records leaves as one or two coalesced stores.
+// LDS: 3 tables of npen words + 1 040 scan words + 4 096 records of 4 (12-byte output) or 5 (16-byte output) words.
+__global__ __launch_bounds__(1024) void k_cells_bin_sorted(vmd_bin_params_t q) {
+    HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
+    const int npen = q.npen;
+    const int rw = q.rec3 ? 4 : 5;             // words per LDS record: x, y, z, pencil (, fine cell)
+    uint32_t* s_cnt = s_dyn;                   // [npen] atoms of this block per pencil
+    uint32_t* s_off = s_dyn + npen;            // [npen] first LDS slot of the pencil's run
+    uint32_t* s_gbase = s_dyn + 2 * npen;      // [npen] first slot of the run in the pencil's bucket
+    uint32_t* s_p = s_dyn + 3 * npen;          // [1024 + 16] scan partials
+    uint32_t* s_rec = s_p + 1040;              // [4096][rw]
+    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    vmd_bin_atoms_t a;
+    vmd_bin_head(q, s_cnt, g, b, tid, a);
+    // reserve the runs in the buckets, and scan the counters: every thread its stretch of them
+    uint32_t* gcount = q.pen_count + (size_t)b * npen;
+    const vmd_stretch_t st = vmd_stretch<1024>(npen, tid);
+    uint32_t sum = 0;
+    for (int c = st.beg; c < st.end; ++c) {
+        const uint32_t n = s_cnt[c];
+        s_gbase[c] = n ? atomicAdd(&gcount[c], n) : 0u;
+        sum += n;
+    }
+    uint32_t ntot;
+    uint32_t run = vmd_wave_scan_1024(s_p, tid, sum, ntot) - sum;
+    for (int c = st.beg; c < st.end; ++c) { s_off[c] = run; run += s_cnt[c]; }
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < VMD_BIN_ILP; ++u) {
-        if (pen[u] == 0xffffffffu) continue;
-        uint32_t* r = s_rec + (size_t)rw * (s_off[pen[u]] + rank[u]);
-        r[0] = (uint32_t)__float_as_int(xw[u]); r[1] = (uint32_t)__float_as_int(yw[u]); r[2] = (uint32_t)__float_as_int(zw[u]); r[3] = pen[u];
-        if (!q.rec3) r[4] = cx[u];
+        if (a.pen[u] == 0xffffffffu) continue;
+        uint32_t* r = s_rec + (size_t)rw * (s_off[a.pen[u]] + a.rank[u]);
+        r[0] = (uint32_t)__float_as_int(a.xw[u]); r[1] = (uint32_t)__float_as_int(a.yw[u]); r[2] = (uint32_t)__float_as_int(a.zw[u]); r[3] = a.pen[u];
+        if (!q.rec3) r[4] = a.cx[u];
     }
     __syncthreads();
-    float* bk = q.bucket + (size_t)b * q.total_cap * 4;
+    float* bk = vmd_rec_run(q.bucket, b, q.total_cap, q.rec3, 0u);
     bool over = false;
     for (uint32_t t = tid; t < ntot; t += 1024) {
         const uint32_t* r = s_rec + (size_t)rw * t;
         const uint32_t pn = r[3];
         const uint32_t off = q.pen_off[pn], cap = q.pen_off[pn + 1] - off;
         const uint32_t slot = s_gbase[pn] + (t - s_off[pn]);
-        if (slot < cap) {
-            if (q.rec3) {
-                float* d = bk + 3 * (size_t)(off + slot);
-                d[0] = __int_as_float((int)r[0]); d[1] = __int_as_float((int)r[1]); d[2] = __int_as_float((int)r[2]);
-            } else {
-                const vmd_f4a v = {__int_as_float((int)r[0]), __int_as_float((int)r[1]), __int_as_float((int)r[2]), __int_as_float((int)r[4])};
-                *(vmd_f4a*)(bk + 4 * (size_t)(off + slot)) = v;
-            }
-        } else {
-            over = true;
-        }
+        if (slot < cap) vmd_rec_put(bk, q.rec3, (size_t)(off + slot), __int_as_float((int)r[0]), __int_as_float((int)r[1]), __int_as_float((int)r[2]), q.rec3 ? 0u : r[4]);
+        else over = true;
     }
     if (over) atomicOr(q.overflow, q.overflow_bit);
 }
@@ -710,20 +720,9 @@ __global__ __launch_bounds__(256) void k_cells_pen_scan(const uint32_t* __restri
     const int b = blockIdx.x, tid = threadIdx.x;
     const uint32_t* cnt = pen_count + (size_t)b * npen;
     uint32_t* out = pen_start + (size_t)b * (npen + 1);
-    const int per = (npen + 255) / 256;
-    const int beg = tid * per, end = beg + per < npen ? beg + per : npen;
-    uint32_t s = 0;
-    for (int c = beg; c < end; ++c) { const uint32_t cap = pen_off[c + 1] - pen_off[c]; s += cnt[c] < cap ? cnt[c] : cap; }
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t v = tid >= o ? part[tid - o] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - s;
-    for (int c = beg; c < end; ++c) { const uint32_t cap = pen_off[c + 1] - pen_off[c]; out[c] = run; run += cnt[c] < cap ? cnt[c] : cap; }
+    vmd_stretch_scan<256>(part, npen, tid,
+                          [&](int c) { const uint32_t cap = pen_off[c + 1] - pen_off[c]; return cnt[c] < cap ? cnt[c] : cap; },
+                          [&](int c, uint32_t first) { out[c] = first; });
     if (tid == 255) out[npen] = part[255];
 }
 
@@ -744,46 +743,22 @@ __global__ __launch_bounds__(256) void k_cells_pen_sort(vmd_pensort_params_t q) 
     uint32_t n = q.pen_count[(size_t)b * q.npen + pen];
     n = n < cap ? n : cap;
     const uint32_t start = q.pen_start[(size_t)b * (q.npen + 1) + pen];
-    const int rs = q.rec3 ? 3 : 4;                           // floats per record; a frame's buckets start at the same place either way
-    const float* bk = q.bucket + 4 * (size_t)b * q.total_cap + (size_t)rs * off;
+    const float* bk = vmd_rec_run(q.bucket, b, q.total_cap, q.rec3, off);
     const float inv_cx = (float)nxf * q.boxes[(size_t)VMD_BOX_STRIDE * b + 3];
     for (int c = tid; c < nxf; c += 256) s_cnt[c] = 0u;
     __syncthreads();
-    for (uint32_t k = tid; k < n; k += 256) {
-        const uint32_t c = q.rec3 ? (uint32_t)vmd_cell_coord(bk[3 * (size_t)k], inv_cx, nxf) : (uint32_t)__float_as_int(bk[4 * (size_t)k + 3]);
-        atomicAdd(&s_cnt[c], 1u);
-    }
+    for (uint32_t k = tid; k < n; k += 256) atomicAdd(&s_cnt[vmd_rec_get_cell(bk, q.rec3, k, inv_cx, nxf)], 1u);
     __syncthreads();
-    // exclusive scan over the fine cells of the pencil
-    const int per = (nxf + 255) / 256;
-    const int beg = tid * per, end = beg + per < nxf ? beg + per : nxf;
-    uint32_t sum = 0;
-    for (int c = beg; c < end; ++c) sum += s_cnt[c];
+    // exclusive scan over the fine cells of the pencil: the counters become cursors
     // (a per-wave scan through LDS with one block barrier measured 7 % slower for this kernel than the plain block scan: profiles/r02y)
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t v = tid >= o ? s_part[tid - o] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
     uint32_t* cs = q.cell_start + (size_t)b * (q.ncell + 1) + (size_t)pen * nxf;
-    for (int c = beg; c < end; ++c) { const uint32_t m = s_cnt[c]; s_cnt[c] = run; cs[c] = start + run; run += m; }
+    vmd_stretch_scan<256>(s_part, nxf, tid, [&](int c) { return s_cnt[c]; }, [&](int c, uint32_t first) { s_cnt[c] = first; cs[c] = start + first; });
     if (pen == q.npen - 1 && tid == 255) q.cell_start[(size_t)b * (q.ncell + 1) + q.ncell] = start + n;
     __syncthreads();
     float* sx = s_xyz; float* sy = s_xyz + q.cap_max; float* sz = s_xyz + 2 * (size_t)q.cap_max;
     for (uint32_t k = tid; k < n; k += 256) {
-        float x, y, z; uint32_t c;
-        if (q.rec3) {
-            const float* r = bk + 3 * (size_t)k;
-            x = r[0]; y = r[1]; z = r[2];
-            c = (uint32_t)vmd_cell_coord(x, inv_cx, nxf);
-        } else {
-            const vmd_f4a v = *(const vmd_f4a*)(bk + 4 * (size_t)k);
-            x = v[0]; y = v[1]; z = v[2]; c = (uint32_t)__float_as_int(v[3]);
-        }
+        float x, y, z;
+        const uint32_t c = vmd_rec_get(bk, q.rec3, k, inv_cx, nxf, x, y, z);
         const uint32_t pos = atomicAdd(&s_cnt[c], 1u);
         sx[pos] = x; sy[pos] = y; sz[pos] = z;
     }
@@ -4104,8 +4079,9 @@ extern "C" size_t vmd_hip_cells_scratch_words(vmd_grid_t grid, int nsel) {
     return split > (size_t)nsel ? split : (size_t)nsel;
 }
 
+#define VMD_LDS_OPT_IN (160 * 1024 - 64)     // bytes of dynamic LDS the kernels of this file opt in to, and the limit its launch code sizes tables against
 static int vmd_lds_opt_in(const void* kernel) {
-    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+    return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VMD_LDS_OPT_IN);
 }
 
 // per host thread, set by the evaluator before the builds of one selection and cleared after them (like the overflow bit below): the
@@ -4119,6 +4095,15 @@ extern "C" void vmd_hip_set_cells_sel_pattern(int m, int first, int period, cons
     }
     g_cells_sel_pattern = p;
 }
+// what every build kernel is told about the frames, the selection (the thread's pattern included) and the grid; the outputs and the scratch
+// of the single-level builds are the caller's to add
+static vmd_cells_params_t vmd_cells_params(const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                                           const int32_t* sel, int nsel, int nsel_pad, vmd_grid_t grid) {
+    vmd_cells_params_t p = {};
+    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags;
+    p.sel = sel; p.nsel = nsel; p.nsel_pad = nsel_pad; p.grid = grid; p.pat = g_cells_sel_pattern;
+    return p;
+}
 
 extern "C" int vmd_hip_cells_build(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                    const float* boxes, uint32_t pbc_flags, int B, const int32_t* sel, int nsel, int nsel_pad,
@@ -4127,7 +4112,8 @@ extern "C" int vmd_hip_cells_build(void* stream, const float* xyz, size_t frame_
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || nsel <= 0) return 0;
     const dim3 grp((nsel + 255) / 256, B);
-    vmd_cells_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, nsel_pad, grid, cell_count, rank, cell_start, sorted, aos, g_cells_sel_pattern};
+    vmd_cells_params_t p = vmd_cells_params(xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, nsel_pad, grid);
+    p.cell_count = cell_count; p.rank = rank; p.cell_start = cell_start; p.sorted = sorted; p.aos = aos;
     if (vmd_hip_cells_fused_ok(grid, nsel)) {
         const size_t shm = sizeof(uint32_t) * ((size_t)grid.ncell + 1 + 1024);
         int ea = vmd_lds_opt_in((const void*)k_cells_fused);
@@ -4863,6 +4849,23 @@ extern "C" int vmd_hip_cells_pencil_ok(vmd_grid_t grid) {
 }
 extern "C" int vmd_hip_cells_pencil_cap_max(void) { return VMD_PEN_CAP_MAX; }
 
+static int g_cells_bin_lds = 1;   // level 1 orders a block's records by pencil in LDS before writing them (A/B switch)
+extern "C" int vmd_hip_set_cells_bin_lds(int on) { const int old = g_cells_bin_lds; g_cells_bin_lds = on ? 1 : 0; return old; }
+static thread_local uint32_t g_cells_overflow_bit = 1u;    // per host thread, set by the evaluator before each selection's build (vmd_hip_set_cells_overflow_bit)
+extern "C" uint32_t vmd_hip_set_cells_overflow_bit(uint32_t bit) { const uint32_t old = g_cells_overflow_bit; g_cells_overflow_bit = bit ? bit : 1u; return old; }
+static int g_cells_rec3 = 1;      // 12-byte bucket records where the cell kind allows it (A/B switch)
+extern "C" int vmd_hip_set_cells_rec3(int on) { const int old = g_cells_rec3; g_cells_rec3 = on ? 1 : 0; return old; }
+
+// level 1's parameters, for the counting mode (no buckets: pen_off, bucket and overflow NULL) and for the build; the thread's overflow bit
+static vmd_bin_params_t vmd_bin_params(const vmd_cells_params_t& c, const uint32_t* pen_off, uint32_t* pen_count, float* bucket, uint32_t* overflow,
+                                       int total_cap, int rec3) {
+    vmd_bin_params_t q = {};
+    q.c = c; q.pen_off = pen_off; q.pen_count = pen_count; q.bucket = bucket; q.overflow = overflow; q.overflow_bit = g_cells_overflow_bit;
+    q.npen = c.grid.ny * c.grid.nz; q.total_cap = total_cap; q.rec3 = rec3;
+    return q;
+}
+static dim3 vmd_bin_grid(int nsel, int frames) { return dim3((nsel + 1024 * VMD_BIN_ILP - 1) / (1024 * VMD_BIN_ILP), frames); }   // level 1
+
 extern "C" int vmd_hip_cells_pencil_count(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
                                           uint32_t pbc_flags, int S, const int32_t* sel, int nsel, vmd_grid_t grid, uint32_t* counts) {
     hipStream_t s = (hipStream_t)stream;
@@ -4870,19 +4873,13 @@ extern "C" int vmd_hip_cells_pencil_count(void* stream, const float* xyz, size_t
     const int npen = grid.ny * grid.nz;
     hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)S * npen, s);
     if (e != hipSuccess) return (int)e;
-    vmd_bin_params_t q{{xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, 0, grid, nullptr, nullptr, nullptr, nullptr, nullptr, g_cells_sel_pattern},
-                       nullptr, counts, nullptr, nullptr, 1u, npen, 0, 0};
-    hipLaunchKernelGGL(k_cells_bin, dim3((nsel + 1024 * VMD_BIN_ILP - 1) / (1024 * VMD_BIN_ILP), S), dim3(1024), sizeof(uint32_t) * npen, s, q);
+    const vmd_bin_params_t q = vmd_bin_params(vmd_cells_params(xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, 0, grid),
+                                              nullptr, counts, nullptr, nullptr, 0, 0);
+    hipLaunchKernelGGL(k_cells_bin, vmd_bin_grid(nsel, S), dim3(1024), sizeof(uint32_t) * npen, s, q);
     VMD_LAUNCH_CHECK();
     return 0;
 }
 
-static int g_cells_bin_lds = 1;   // level 1 orders a block's records by pencil in LDS before writing them (A/B switch)
-extern "C" int vmd_hip_set_cells_bin_lds(int on) { const int old = g_cells_bin_lds; g_cells_bin_lds = on ? 1 : 0; return old; }
-static thread_local uint32_t g_cells_overflow_bit = 1u;    // per host thread, set by the evaluator before each selection's build (vmd_hip_set_cells_overflow_bit)
-extern "C" uint32_t vmd_hip_set_cells_overflow_bit(uint32_t bit) { const uint32_t old = g_cells_overflow_bit; g_cells_overflow_bit = bit ? bit : 1u; return old; }
-static int g_cells_rec3 = 1;      // 12-byte bucket records where the cell kind allows it (A/B switch)
-extern "C" int vmd_hip_set_cells_rec3(int on) { const int old = g_cells_rec3; g_cells_rec3 = on ? 1 : 0; return old; }
 extern "C" int vmd_hip_cells_build_pencil(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
                                           uint32_t pbc_flags, int B, const int32_t* sel, int nsel, int nsel_pad, vmd_grid_t grid,
                                           const uint32_t* pen_off, int total_cap, int cap_max, uint32_t* pen_count, uint32_t* pen_start,
@@ -4895,22 +4892,22 @@ extern "C" int vmd_hip_cells_build_pencil(void* stream, const float* xyz, size_t
     if (e != hipSuccess) return (int)e;
     // x-periodic, non-triclinic cells: the grid bins the wrapped x itself, so the record need not carry the fine cell
     const int rec3 = (g_cells_rec3 && (pbc_flags & 1u) && !(pbc_flags & VMD_PBC_TRICLINIC)) ? 1 : 0;
-    vmd_bin_params_t q{{xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, nsel_pad, grid, nullptr, nullptr, nullptr, nullptr, nullptr, g_cells_sel_pattern},
-                       pen_off, pen_count, bucket, overflow, g_cells_overflow_bit ? g_cells_overflow_bit : 1u, npen, total_cap, rec3};
+    const vmd_bin_params_t q = vmd_bin_params(vmd_cells_params(xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, nsel_pad, grid),
+                                              pen_off, pen_count, bucket, overflow, total_cap, rec3);
     const size_t shm_sorted = sizeof(uint32_t) * (3 * (size_t)npen + 1040 + (size_t)1024 * VMD_BIN_ILP * (rec3 ? 4 : 5));
-    if (g_cells_bin_lds && shm_sorted <= 160 * 1024 - 64) {
+    if (g_cells_bin_lds && shm_sorted <= VMD_LDS_OPT_IN) {
         int eb = vmd_lds_opt_in((const void*)k_cells_bin_sorted);
         if (eb) return eb;
-        hipLaunchKernelGGL(k_cells_bin_sorted, dim3((nsel + 1024 * VMD_BIN_ILP - 1) / (1024 * VMD_BIN_ILP), B), dim3(1024), shm_sorted, s, q);
+        hipLaunchKernelGGL(k_cells_bin_sorted, vmd_bin_grid(nsel, B), dim3(1024), shm_sorted, s, q);
     } else {
-        hipLaunchKernelGGL(k_cells_bin, dim3((nsel + 1024 * VMD_BIN_ILP - 1) / (1024 * VMD_BIN_ILP), B), dim3(1024), sizeof(uint32_t) * npen, s, q);
+        hipLaunchKernelGGL(k_cells_bin, vmd_bin_grid(nsel, B), dim3(1024), sizeof(uint32_t) * npen, s, q);
     }
     VMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cells_pen_scan, dim3(B), dim3(256), 0, s, (const uint32_t*)pen_count, pen_off, pen_start, npen);
     VMD_LAUNCH_CHECK();
     vmd_pensort_params_t ps{bucket, pen_off, pen_count, pen_start, cell_start, sorted, npen, grid.nxf, grid.ncell, nsel_pad, total_cap, cap_max, boxes, rec3};
     const size_t shm = sizeof(uint32_t) * ((size_t)grid.nxf + 256 + 3 * (size_t)cap_max);
-    if (shm > 160 * 1024 - 64) return (int)hipErrorInvalidValue;
+    if (shm > VMD_LDS_OPT_IN) return (int)hipErrorInvalidValue;
     int ea = vmd_lds_opt_in((const void*)k_cells_pen_sort);
     if (ea) return ea;
     // grid.y = B <= 65535 (frame batches are far smaller); pencils on grid.x
