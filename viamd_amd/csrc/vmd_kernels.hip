@@ -16,6 +16,13 @@
 //   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
 //   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
 //
+// What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
+//   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
+//   vmd_com_t                    the fp64 centre of mass of vmd_set_com, k_sdf_align and k_sdf_ref_pose
+//   vmd_bond / vmd_normal / vmd_dihedral   the bond vectors and the dihedral of k_geom, k_backbone_angles and k_ss_assign's bend
+//   vmd_set_*                    shape_weights' and rmsd's reduction (rules 1 - 5): constants, block decode, context slice,
+//                                wave / block / chunk sums, the fp64 cell (vmd_set_frame) and the atom load (vmd_set_load)
+//
 // Design notes (DESIGN.md has the long form):
 //  * wave64 everywhere; a wave is the unit of work in the pair kernel (private LDS histogram + private LDS
 //    hit queue per wave, no block barrier in the hot loop).
@@ -116,6 +123,24 @@ __device__ __forceinline__ vmd_box_t vmd_load_box(const float* boxes, int b, uin
     bx.Lx = q[0]; bx.Ly = q[1]; bx.Lz = q[2]; bx.iLx = q[3]; bx.iLy = q[4]; bx.iLz = q[5]; bx.xy = q[6]; bx.xz = q[7]; bx.yz = q[8];
     bx.px = pbc & 1u; bx.py = pbc & 2u; bx.pz = pbc & 4u; bx.tri = pbc & VMD_PBC_TRICLINIC;
     return bx;
+}
+// The head of every property kernel's parameter block (K3, K5 - K5d, K10, K11): the batch's coordinates, frame b at xyz + b * frame_stride
+// as three rows row_stride apart, and its cells.  vmd_frame is frame b as a kernel sees it.
+struct vmd_frames_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc; int B;
+};
+static inline vmd_frames_t vmd_frames(const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags, int B) {
+    return vmd_frames_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B};
+}
+struct vmd_frame_t { const float* x; const float* y; const float* z; vmd_box_t bx; };
+__device__ __forceinline__ vmd_frame_t vmd_frame(const vmd_frames_t& f, int b) {
+    vmd_frame_t v;
+    v.x = f.xyz + (size_t)b * f.frame_stride;
+    v.y = v.x + f.row_stride;
+    v.z = v.y + f.row_stride;
+    v.bx = vmd_load_box(f.boxes, b, f.pbc);
+    return v;
 }
 // SPEC S3t: Cartesian -> fractional and back, fp32
 __device__ __forceinline__ void vmd_frac(const vmd_box_t& b, float x, float y, float z, float& sx, float& sy, float& sz) {
@@ -2454,17 +2479,23 @@ __device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
     R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
 }
 
+// a centre of mass in fp64: the weighted sums in the order the atoms are handed over, one division per axis at the end
+struct vmd_com_t {
+    double sw = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    __device__ __forceinline__ void add(double w, double x, double y, double z) { sw = sw + w; sx = sx + w * x; sy = sy + w * y; sz = sz + w * z; }
+    __device__ __forceinline__ void centre(double& c0, double& c1, double& c2) const { c0 = sx / sw; c1 = sy / sw; c2 = sz / sw; }
+};
+
 // walks the unwrap chain of one structure; calls f(a, w, px, py, pz) for every atom in order
 template <typename F>
-__device__ __forceinline__ void vmd_unwrap_chain(const float* fx, const float* fy, const float* fz,
-                                                 const int32_t* idx, const float* mass, int m, const vmd_box_t& bx, F f) {
+__device__ __forceinline__ void vmd_unwrap_chain(const vmd_frame_t& fr, const int32_t* idx, const float* mass, int m, F f) {
     double qx = 0.0, qy = 0.0, qz = 0.0;
     for (int a = 0; a < m; ++a) {
         const int i = idx[a];
-        double x = (double)fx[i], y = (double)fy[i], z = (double)fz[i];
+        double x = (double)fr.x[i], y = (double)fr.y[i], z = (double)fr.z[i];
         if (a > 0) {
             double dx = x - qx, dy = y - qy, dz = z - qz;
-            vmd_mi3_rint(bx, dx, dy, dz);
+            vmd_mi3_rint(fr.bx, dx, dy, dz);
             x = qx + dx; y = qy + dy; z = qz + dz;
         }
         qx = x; qy = y; qz = z;
@@ -2476,16 +2507,16 @@ __device__ __forceinline__ void vmd_unwrap_chain(const float* fx, const float* f
 // its bond tree - atom order[t] hangs on atom parent[order[t]] (local indices; parent < 0 = the root) - as mdlib's
 // md_util_unwrap does (/root/reference/src/viamd.cpp:2257), instead of along the index order.  Positions go to `pos` (m x 3 doubles
 // of scratch per thread: a parent is not the atom visited last); the callers then sum in INDEX order, as the chain walk does.
-__device__ __forceinline__ void vmd_unwrap_tree(const float* fx, const float* fy, const float* fz, const int32_t* idx, int m, const vmd_box_t& bx,
-                                                const int32_t* order, const int32_t* parent, double* pos) {
+__device__ __forceinline__ void vmd_unwrap_tree(const vmd_frame_t& fr, const int32_t* idx, int m, const int32_t* order, const int32_t* parent,
+                                                double* pos) {
     for (int t = 0; t < m; ++t) {
         const int a = order[t], par = parent[a];
         const int i = idx[a];
-        double x = (double)fx[i], y = (double)fy[i], z = (double)fz[i];
+        double x = (double)fr.x[i], y = (double)fr.y[i], z = (double)fr.z[i];
         if (par >= 0) {
             const double qx = pos[3 * par + 0], qy = pos[3 * par + 1], qz = pos[3 * par + 2];
             double dx = x - qx, dy = y - qy, dz = z - qz;
-            vmd_mi3_rint(bx, dx, dy, dz);
+            vmd_mi3_rint(fr.bx, dx, dy, dz);
             x = qx + dx; y = qy + dy; z = qz + dz;
         }
         pos[3 * a + 0] = x; pos[3 * a + 1] = y; pos[3 * a + 2] = z;
@@ -2493,8 +2524,7 @@ __device__ __forceinline__ void vmd_unwrap_tree(const float* fx, const float* fy
 }
 
 struct vmd_align_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     const int32_t* structs; const float* mass; int K; int m;
     const double* ref_pose;
     float* R32; float* c32; double* M64;
@@ -2504,20 +2534,17 @@ struct vmd_align_params_t {
 
 __global__ __launch_bounds__(64) void k_sdf_align(vmd_align_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.K) return;
+    if (t >= p.f.B * p.K) return;
     const int b = t / p.K, k = t - b * p.K;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     const int32_t* idx = p.structs + (size_t)k * p.m;
     const float* mass = p.mass ? p.mass + (size_t)k * p.m : nullptr;
 
-    double sw = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    vmd_com_t cm;
     double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     const double* ref = p.ref_pose;
     double com0, com1, com2;
-    auto add_com = [&](int, double w, double x, double y, double z) { sw = sw + w; sx = sx + w * x; sy = sy + w * y; sz = sz + w * z; };
+    auto add_com = [&](int, double w, double x, double y, double z) { cm.add(w, x, y, z); };
     auto add_cov = [&](int a, double w, double x, double y, double z) {
         const double c0 = x - com0, c1 = y - com1, c2 = z - com2;
         const double r0 = ref[3 * a + 0], r1 = ref[3 * a + 1], r2 = ref[3 * a + 2];
@@ -2528,14 +2555,14 @@ __global__ __launch_bounds__(64) void k_sdf_align(vmd_align_params_t p) {
     };
     if (p.tree_order) {
         double* pos = p.tree_pos + (size_t)t * 3 * p.m;
-        vmd_unwrap_tree(fx, fy, fz, idx, p.m, bx, p.tree_order + (size_t)k * p.m, p.tree_parent + (size_t)k * p.m, pos);
+        vmd_unwrap_tree(fr, idx, p.m, p.tree_order + (size_t)k * p.m, p.tree_parent + (size_t)k * p.m, pos);
         for (int a = 0; a < p.m; ++a) add_com(a, mass ? (double)mass[a] : 1.0, pos[3 * a + 0], pos[3 * a + 1], pos[3 * a + 2]);
-        com0 = sx / sw; com1 = sy / sw; com2 = sz / sw;
+        cm.centre(com0, com1, com2);
         for (int a = 0; a < p.m; ++a) add_cov(a, mass ? (double)mass[a] : 1.0, pos[3 * a + 0], pos[3 * a + 1], pos[3 * a + 2]);
     } else {
-        vmd_unwrap_chain(fx, fy, fz, idx, mass, p.m, bx, add_com);
-        com0 = sx / sw; com1 = sy / sw; com2 = sz / sw;
-        vmd_unwrap_chain(fx, fy, fz, idx, mass, p.m, bx, add_cov);
+        vmd_unwrap_chain(fr, idx, mass, p.m, add_com);
+        cm.centre(com0, com1, com2);
+        vmd_unwrap_chain(fr, idx, mass, p.m, add_cov);
     }
     double R[9];
     vmd_horn_rotation(S, R);
@@ -2556,25 +2583,19 @@ __global__ __launch_bounds__(64) void k_sdf_ref_pose(const float* xyz, size_t ro
                                                      const int32_t* idx, const float* mass, int m, double* ref_pose,
                                                      const int32_t* tree_order, const int32_t* tree_parent) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const float* fx = xyz;
-    const float* fy = fx + row_stride;
-    const float* fz = fy + row_stride;
-    const vmd_box_t bx = vmd_load_box(box, 0, pbc);
-    double sw = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    const vmd_frame_t fr = vmd_frame(vmd_frames_t{xyz, 0, row_stride, box, pbc, 1}, 0);
+    vmd_com_t cm;
     if (tree_order) {
-        vmd_unwrap_tree(fx, fy, fz, idx, m, bx, tree_order, tree_parent, ref_pose);      // the pose array doubles as the walk's scratch
-        for (int a = 0; a < m; ++a) {
-            const double w = mass ? (double)mass[a] : 1.0;
-            sw = sw + w; sx = sx + w * ref_pose[3 * a + 0]; sy = sy + w * ref_pose[3 * a + 1]; sz = sz + w * ref_pose[3 * a + 2];
-        }
+        vmd_unwrap_tree(fr, idx, m, tree_order, tree_parent, ref_pose);      // the pose array doubles as the walk's scratch
+        for (int a = 0; a < m; ++a) cm.add(mass ? (double)mass[a] : 1.0, ref_pose[3 * a + 0], ref_pose[3 * a + 1], ref_pose[3 * a + 2]);
     } else {
-        vmd_unwrap_chain(fx, fy, fz, idx, mass, m, bx,
-                         [&](int a, double w, double x, double y, double z) {
-                             ref_pose[3 * a + 0] = x; ref_pose[3 * a + 1] = y; ref_pose[3 * a + 2] = z;
-                             sw = sw + w; sx = sx + w * x; sy = sy + w * y; sz = sz + w * z;
-                         });
+        vmd_unwrap_chain(fr, idx, mass, m, [&](int a, double w, double x, double y, double z) {
+            ref_pose[3 * a + 0] = x; ref_pose[3 * a + 1] = y; ref_pose[3 * a + 2] = z;
+            cm.add(w, x, y, z);
+        });
     }
-    const double com0 = sx / sw, com1 = sy / sw, com2 = sz / sw;
+    double com0, com1, com2;
+    cm.centre(com0, com1, com2);
     for (int a = 0; a < m; ++a) {
         ref_pose[3 * a + 0] = ref_pose[3 * a + 0] - com0;
         ref_pose[3 * a + 1] = ref_pose[3 * a + 1] - com1;
@@ -2950,59 +2971,51 @@ __global__ __launch_bounds__(256) void k_sdf_scatter_dense(vmd_scatter_params_t 
 // ------------------------------------------------------------------------------------------------ K5: distances
 
 struct vmd_dist_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     // population of P contexts (`... in residue(:)`): context c uses a[aoff[c]..aoff[c+1]) and b[boff[c]..boff[c+1])
     const int32_t* a; const float* mass_a; const int32_t* aoff; const int32_t* b; const float* mass_b; const int32_t* boff; int P;
     int per;      // values per context: 1, or |a_c|*|b_c| for distance_pair (equal for all contexts)
     float* out;   // [B][P*per]
 };
 
-__device__ void vmd_set_com(const float* fx, const float* fy, const float* fz, const int32_t* idx, const float* mass, int n,
-                            const vmd_box_t& bx, float out[3]) {
-    double sw = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+__device__ void vmd_set_com(const vmd_frame_t& fr,const int32_t* idx, const float* mass, int n, float out[3]) {
+    vmd_com_t cm;
     double p0x = 0.0, p0y = 0.0, p0z = 0.0;
     for (int a = 0; a < n; ++a) {
         const int i = idx[a];
-        double x = (double)fx[i], y = (double)fy[i], z = (double)fz[i];
+        double x = (double)fr.x[i], y = (double)fr.y[i], z = (double)fr.z[i];
         if (a == 0) { p0x = x; p0y = y; p0z = z; }
         else {
             double dx = x - p0x, dy = y - p0y, dz = z - p0z;
-            vmd_mi3_rint(bx, dx, dy, dz);
+            vmd_mi3_rint(fr.bx, dx, dy, dz);
             x = p0x + dx; y = p0y + dy; z = p0z + dz;
         }
-        const double w = mass ? (double)mass[a] : 1.0;
-        sw = sw + w; sx = sx + w * x; sy = sy + w * y; sz = sz + w * z;
+        cm.add(mass ? (double)mass[a] : 1.0, x, y, z);
     }
-    out[0] = (float)(sx / sw); out[1] = (float)(sy / sw); out[2] = (float)(sz / sw);
+    double c0, c1, c2;
+    cm.centre(c0, c1, c2);
+    out[0] = (float)c0; out[1] = (float)c1; out[2] = (float)c2;
 }
 
 __global__ __launch_bounds__(64) void k_distance_com(vmd_dist_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.P) return;
+    if (t >= p.f.B * p.P) return;
     const int b = t / p.P, c = t - b * p.P;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     const int a0 = p.aoff[c], na = p.aoff[c + 1] - a0, b0 = p.boff[c], nb = p.boff[c + 1] - b0;
     float ca[3], cb[3];
-    vmd_set_com(fx, fy, fz, p.a + a0, p.mass_a ? p.mass_a + a0 : nullptr, na, bx, ca);
-    vmd_set_com(fx, fy, fz, p.b + b0, p.mass_b ? p.mass_b + b0 : nullptr, nb, bx, cb);
+    vmd_set_com(fr, p.a + a0, p.mass_a ? p.mass_a + a0 : nullptr, na, ca);
+    vmd_set_com(fr, p.b + b0, p.mass_b ? p.mass_b + b0 : nullptr, nb, cb);
     float dx = ca[0] - cb[0], dy = ca[1] - cb[1], dz = ca[2] - cb[2];
-    vmd_mi3_rintf(bx, dx, dy, dz);
+    vmd_mi3_rintf(fr.bx, dx, dy, dz);
     p.out[t] = sqrtf(vmd_d2(dx, dy, dz));
 }
 
-__device__ __forceinline__ float vmd_pair_d2(const vmd_dist_params_t& p, int b, int i, int j) {
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+__device__ __forceinline__ float vmd_pair_d2(const vmd_frame_t& fr, int i, int j) {
     float xi, yi, zi, xj, yj, zj;
-    vmd_pair_coords(bx, fx[i], fy[i], fz[i], xi, yi, zi);
-    vmd_pair_coords(bx, fx[j], fy[j], fz[j], xj, yj, zj);
-    return vmd_pair_d2_general(bx, xi, yi, zi, xj, yj, zj);
+    vmd_pair_coords(fr.bx, fr.x[i], fr.y[i], fr.z[i], xi, yi, zi);
+    vmd_pair_coords(fr.bx, fr.x[j], fr.y[j], fr.z[j], xj, yj, zj);
+    return vmd_pair_d2_general(fr.bx, xi, yi, zi, xj, yj, zj);
 }
 
 // one block per (frame, context); MAXI = false -> min, true -> max
@@ -3012,10 +3025,11 @@ __global__ __launch_bounds__(256) void k_distance_minmax(vmd_dist_params_t p) {
     const int b = blockIdx.x / p.P, c = blockIdx.x - b * p.P;
     const int a0 = p.aoff[c], na = p.aoff[c + 1] - a0, b0 = p.boff[c], nb = p.boff[c + 1] - b0;
     const long long npairs = (long long)na * nb;
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     float best = MAXI ? 0.0f : 3.4028235e38f;
     for (long long k = threadIdx.x; k < npairs; k += 256) {
         const int ia = (int)(k / nb), ib = (int)(k - (long long)ia * nb);
-        const float d2 = vmd_pair_d2(p, b, p.a[a0 + ia], p.b[b0 + ib]);
+        const float d2 = vmd_pair_d2(fr, p.a[a0 + ia], p.b[b0 + ib]);
         best = MAXI ? fmaxf(best, d2) : fminf(best, d2);
     }
     s_red[threadIdx.x] = best;
@@ -3038,14 +3052,13 @@ __global__ __launch_bounds__(256) void k_distance_pair(vmd_dist_params_t p) {
     if (k >= p.per) return;
     const int a0 = p.aoff[c], b0 = p.boff[c], nb = p.boff[c + 1] - b0;
     const int ia = (int)(k / nb), ib = (int)(k - (long long)ia * nb);
-    p.out[((size_t)b * p.P + c) * p.per + k] = sqrtf(vmd_pair_d2(p, b, p.a[a0 + ia], p.b[b0 + ib]));
+    p.out[((size_t)b * p.P + c) * p.per + k] = sqrtf(vmd_pair_d2(vmd_frame(p.f, b), p.a[a0 + ia], p.b[b0 + ib]));
 }
 
 // ------------------------------------------------------------------------------------------------ K5b: angle / dihedral (DESIGN S6b)
 
 struct vmd_geom_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     // argument k of context c: set[k][off[k][c] .. off[k][c+1]), masses parallel to set[k]
     const int32_t* set[4]; const float* mass[4]; const int32_t* off[4]; int P;
     int radians;  // D-ANGLE-UNIT: 0 = degrees
@@ -3063,49 +3076,55 @@ __device__ __forceinline__ double vmd_dot_d(double ax, double ay, double az, dou
     return (ax * bx + ay * by) + az * bz;
 }
 
+// fp32 minimum-image bond vector q - p of two points
+__device__ __forceinline__ void vmd_bond(const vmd_box_t& bx, const float p[3], const float q[3], float d[3]) {
+    d[0] = q[0] - p[0]; d[1] = q[1] - p[1]; d[2] = q[2] - p[2];
+    vmd_mi3_rintf(bx, d[0], d[1], d[2]);
+}
+__device__ __forceinline__ void vmd_normal(const float a[3], const float b[3], double n[3]) {
+    vmd_cross_d(a[0], a[1], a[2], b[0], b[1], b[2], n[0], n[1], n[2]);
+}
+// the dihedral, in radians (IUPAC sign), from its first two bond vectors and the two normals n1 = b1 x b2, n2 = b2 x b3.  `+ 0.0` turns a
+// -0 operand of atan2 into +0: degenerate input gives atan2(+0, +0) = 0 (D-ANGLE-DEGENERATE) and a dihedral never comes out as -180.
+__device__ __forceinline__ double vmd_dihedral(const float b1[3], const float b2[3], const double n1[3], const double n2[3]) {
+    const double l2 = sqrt(vmd_dot_d(b2[0], b2[1], b2[2], b2[0], b2[1], b2[2]));
+    const double y = l2 * vmd_dot_d(b1[0], b1[1], b1[2], n2[0], n2[1], n2[2]);
+    return atan2(y + 0.0, vmd_dot_d(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2]) + 0.0);
+}
+
 // one thread per (frame, context): the NARG argument points are the S6 centres of distance(a, b) (vmd_set_com), joined by fp32
-// minimum-image differences; the value is formed in fp64 (no contraction) and rounded once.  `+ 0.0` turns a -0 operand of atan2
-// into +0: degenerate input gives atan2(+0, +0) = 0 (D-ANGLE-DEGENERATE) and a dihedral never comes out as -180.
+// minimum-image differences (vmd_bond); the value is formed in fp64 (no contraction) and rounded once.
 template <int NARG>
 __global__ __launch_bounds__(64) void k_geom(vmd_geom_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.P) return;
+    if (t >= p.f.B * p.P) return;
     const int b = t / p.P, c = t - b * p.P;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     float q[NARG][3];
 #pragma unroll
     for (int k = 0; k < NARG; ++k) {
         const int k0 = p.off[k][c], n = p.off[k][c + 1] - k0;
-        vmd_set_com(fx, fy, fz, p.set[k] + k0, p.mass[k] + k0, n, bx, q[k]);
+        vmd_set_com(fr, p.set[k] + k0, p.mass[k] + k0, n, q[k]);
     }
     double rad;
     if constexpr (NARG == 3) {
         // angle(a, b, c) at the middle point: u = mi(pa - pb), v = mi(pc - pb)
-        float ux = q[0][0] - q[1][0], uy = q[0][1] - q[1][1], uz = q[0][2] - q[1][2];
-        float vx = q[2][0] - q[1][0], vy = q[2][1] - q[1][1], vz = q[2][2] - q[1][2];
-        vmd_mi3_rintf(bx, ux, uy, uz);
-        vmd_mi3_rintf(bx, vx, vy, vz);
-        double cx, cy, cz;
-        vmd_cross_d(ux, uy, uz, vx, vy, vz, cx, cy, cz);
-        const double s = sqrt(vmd_dot_d(cx, cy, cz, cx, cy, cz));
-        rad = atan2(s + 0.0, vmd_dot_d(ux, uy, uz, vx, vy, vz) + 0.0);
+        float u[3], v[3];
+        double n[3];
+        vmd_bond(fr.bx, q[1], q[0], u);
+        vmd_bond(fr.bx, q[1], q[2], v);
+        vmd_normal(u, v, n);
+        const double s = sqrt(vmd_dot_d(n[0], n[1], n[2], n[0], n[1], n[2]));
+        rad = atan2(s + 0.0, vmd_dot_d(u[0], u[1], u[2], v[0], v[1], v[2]) + 0.0);
     } else {
-        // dihedral(a, b, c, d): b1 = mi(pb - pa), b2 = mi(pc - pb), b3 = mi(pd - pc); IUPAC sign
+        // dihedral(a, b, c, d): b1 = mi(pb - pa), b2 = mi(pc - pb), b3 = mi(pd - pc)
         float d[3][3];
+        double n1[3], n2[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k][0] = q[k + 1][0] - q[k][0]; d[k][1] = q[k + 1][1] - q[k][1]; d[k][2] = q[k + 1][2] - q[k][2];
-            vmd_mi3_rintf(bx, d[k][0], d[k][1], d[k][2]);
-        }
-        double n1x, n1y, n1z, n2x, n2y, n2z;
-        vmd_cross_d(d[0][0], d[0][1], d[0][2], d[1][0], d[1][1], d[1][2], n1x, n1y, n1z);
-        vmd_cross_d(d[1][0], d[1][1], d[1][2], d[2][0], d[2][1], d[2][2], n2x, n2y, n2z);
-        const double l2 = sqrt(vmd_dot_d(d[1][0], d[1][1], d[1][2], d[1][0], d[1][1], d[1][2]));
-        const double y = l2 * vmd_dot_d(d[0][0], d[0][1], d[0][2], n2x, n2y, n2z);
-        rad = atan2(y + 0.0, vmd_dot_d(n1x, n1y, n1z, n2x, n2y, n2z) + 0.0);
+        for (int k = 0; k < 3; ++k) vmd_bond(fr.bx, q[k], q[k + 1], d[k]);
+        vmd_normal(d[0], d[1], n1);
+        vmd_normal(d[1], d[2], n2);
+        rad = vmd_dihedral(d[0], d[1], n1, n2);
     }
     p.out[t] = p.radians ? (float)rad : (float)(rad * (180.0 / M_PI));
 }
@@ -3113,65 +3132,49 @@ __global__ __launch_bounds__(64) void k_geom(vmd_geom_params_t p) {
 // ------------------------------------------------------------------------------------------------ K10: backbone phi / psi, Ramachandran map
 
 struct vmd_bb_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     const int32_t* n; const int32_t* ca; const int32_t* c; const uint8_t* link; int nseg;
     float* out;   // [B][nseg][2]
 };
 
 typedef float vmd_f2a __attribute__((vector_size(8)));     // {phi, psi}: one 8-byte access (the table's rows are 8-byte aligned)
 
-// fp32 minimum-image bond vector q - p of two raw positions: k_geom<4>'s d[k]
-__device__ __forceinline__ void vmd_bb_bond(const vmd_box_t& bx, const float p[3], const float q[3], float d[3]) {
-    d[0] = q[0] - p[0]; d[1] = q[1] - p[1]; d[2] = q[2] - p[2];
-    vmd_mi3_rintf(bx, d[0], d[1], d[2]);
-}
-
-// k_geom<4>'s value from its three bond vectors and their two normals n1 = b1 x b2, n2 = b2 x b3, in radians
-__device__ __forceinline__ float vmd_bb_dihedral(const float b1[3], const float b2[3], const double n1[3], const double n2[3]) {
-    const double l2 = sqrt(vmd_dot_d(b2[0], b2[1], b2[2], b2[0], b2[1], b2[2]));
-    const double y = l2 * vmd_dot_d(b1[0], b1[1], b1[2], n2[0], n2[1], n2[2]);
-    return (float)atan2(y + 0.0, vmd_dot_d(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2]) + 0.0);
-}
-
 // one thread per (frame, segment), the segment fastest: five gathers, four bond vectors, three normals (the one of N-CA-C serves both
-// angles), two atan2, one 8-byte store.  A single-atom set of k_geom is the atom's raw position (vmd_set_com: w x / w is exact), so phi and
-// psi are dihedral()'s values bit for bit.  DECISION(D-BB-ENDS): the angle that lacks its neighbour is +0.
+// angles), two atan2, one 8-byte store.  A single-atom set of k_geom is the atom's raw position (vmd_set_com: w x / w is exact) and both
+// kernels call vmd_bond / vmd_dihedral, so phi and psi are dihedral()'s values bit for bit.  DECISION(D-BB-ENDS): the angle that lacks its
+// neighbour is +0.
 __global__ __launch_bounds__(64) void k_backbone_angles(vmd_bb_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.nseg) return;
+    if (t >= p.f.B * p.nseg) return;
     const int b = t / p.nseg, s = t - b * p.nseg;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     const unsigned lk = p.link[s];
     const bool prev = (lk & 1u) && s > 0, next = (lk & 2u) && s + 1 < p.nseg;
     const int in = p.n[s], ia = p.ca[s], ic = p.c[s];
-    const float N[3] = {fx[in], fy[in], fz[in]}, A[3] = {fx[ia], fy[ia], fz[ia]}, C[3] = {fx[ic], fy[ic], fz[ic]};
+    const float N[3] = {fr.x[in], fr.y[in], fr.z[in]}, A[3] = {fr.x[ia], fr.y[ia], fr.z[ia]}, C[3] = {fr.x[ic], fr.y[ic], fr.z[ic]};
     float b1[3], b2[3];
-    vmd_bb_bond(bx, N, A, b1);
-    vmd_bb_bond(bx, A, C, b2);
+    vmd_bond(fr.bx, N, A, b1);
+    vmd_bond(fr.bx, A, C, b2);
     double nm[3];
-    vmd_cross_d(b1[0], b1[1], b1[2], b2[0], b2[1], b2[2], nm[0], nm[1], nm[2]);
+    vmd_normal(b1, b2, nm);
     float phi = 0.0f, psi = 0.0f;
     if (prev) {
         const int ip = p.c[s - 1];
-        const float Cp[3] = {fx[ip], fy[ip], fz[ip]};
+        const float Cp[3] = {fr.x[ip], fr.y[ip], fr.z[ip]};
         float b0[3];
         double n0[3];
-        vmd_bb_bond(bx, Cp, N, b0);
-        vmd_cross_d(b0[0], b0[1], b0[2], b1[0], b1[1], b1[2], n0[0], n0[1], n0[2]);
-        phi = vmd_bb_dihedral(b0, b1, n0, nm);
+        vmd_bond(fr.bx, Cp, N, b0);
+        vmd_normal(b0, b1, n0);
+        phi = (float)vmd_dihedral(b0, b1, n0, nm);
     }
     if (next) {
         const int iq = p.n[s + 1];
-        const float Nn[3] = {fx[iq], fy[iq], fz[iq]};
+        const float Nn[3] = {fr.x[iq], fr.y[iq], fr.z[iq]};
         float b3[3];
         double n3[3];
-        vmd_bb_bond(bx, C, Nn, b3);
-        vmd_cross_d(b2[0], b2[1], b2[2], b3[0], b3[1], b3[2], n3[0], n3[1], n3[2]);
-        psi = vmd_bb_dihedral(b1, b2, nm, n3);
+        vmd_bond(fr.bx, C, Nn, b3);
+        vmd_normal(b2, b3, n3);
+        psi = (float)vmd_dihedral(b1, b2, nm, n3);
     }
     vmd_f2a o;
     o[0] = phi; o[1] = psi;
@@ -3222,8 +3225,7 @@ __global__ __launch_bounds__(256) void k_rama_bin(vmd_rama_params_t p) {
 // Four bit matrices per frame, rows of W = ceil(nseg / 64) 64-bit words: HB[a] bit d and HBT[d] bit a = hb(a, d) (the C=O of a accepts from
 // the N-H of d), BP[i] bit j / BA[i] bit j = parallel / antiparallel bridge (i, j).  Bits at and above nseg are zero in every row.
 struct vmd_ss_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     const int32_t* n; const int32_t* ca; const int32_t* c; const int32_t* o;
     const int32_t* rng;                 // [nseg] the range of every segment
     const uint8_t* pro;                 // [nseg] 1 = proline
@@ -3264,18 +3266,15 @@ __global__ __launch_bounds__(64) void k_ss_hbond(vmd_ss_params_t p) {
     const int lane = threadIdx.x;
     const long long blk = blockIdx.x;
     const int w = (int)(blk % p.W), wa = (int)((blk / p.W) % p.W), b = (int)(blk / ((long long)p.W * p.W));
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, b);
     const int al = wa * 64 + lane;
     s_acc[lane] = 0; s_rng[lane] = -1;
     s_hb[lane][0] = s_hb[lane][1] = s_hbt[lane][0] = s_hbt[lane][1] = 0u;
     if (al < p.nseg) {
         const int ia = p.ca[al], ic = p.c[al], io = p.o[al];
-        s_pos[lane][0] = fx[ia]; s_pos[lane][1] = fy[ia]; s_pos[lane][2] = fz[ia];
-        s_pos[lane][3] = fx[ic]; s_pos[lane][4] = fy[ic]; s_pos[lane][5] = fz[ic];
-        if (io >= 0) { s_pos[lane][6] = fx[io]; s_pos[lane][7] = fy[io]; s_pos[lane][8] = fz[io]; s_acc[lane] = 1; }
+        s_pos[lane][0] = fr.x[ia]; s_pos[lane][1] = fr.y[ia]; s_pos[lane][2] = fr.z[ia];
+        s_pos[lane][3] = fr.x[ic]; s_pos[lane][4] = fr.y[ic]; s_pos[lane][5] = fr.z[ic];
+        if (io >= 0) { s_pos[lane][6] = fr.x[io]; s_pos[lane][7] = fr.y[io]; s_pos[lane][8] = fr.z[io]; s_acc[lane] = 1; }
         s_rng[lane] = p.rng[al];
     }
     const int d = w * 64 + lane;
@@ -3285,17 +3284,17 @@ __global__ __launch_bounds__(64) void k_ss_hbond(vmd_ss_params_t p) {
     if (d < p.nseg) {
         rd = p.rng[d];
         const int ia = p.ca[d];
-        A[0] = fx[ia]; A[1] = fy[ia]; A[2] = fz[ia];
+        A[0] = fr.x[ia]; A[1] = fr.y[ia]; A[2] = fr.z[ia];
         // D-SS-H: the amide H sits at N[d] + u, u the unit vector of mi(C[d-1] - O[d-1])
         if (d > 0 && p.rng[d - 1] == rd && !p.pro[d] && p.o[d - 1] >= 0) {
             const int ic = p.c[d - 1], io = p.o[d - 1], in = p.n[d];
-            float v[3] = {fx[ic] - fx[io], fy[ic] - fy[io], fz[ic] - fz[io]};
-            vmd_mi3_rintf(bx, v[0], v[1], v[2]);
+            float v[3] = {fr.x[ic] - fr.x[io], fr.y[ic] - fr.y[io], fr.z[ic] - fr.z[io]};
+            vmd_mi3_rintf(fr.bx, v[0], v[1], v[2]);
             const double l = vmd_ss_len((double)v[0], (double)v[1], (double)v[2]);
             if (l > 0.0) {
                 donor = true;
                 s_u[lane][0] = (double)v[0] / l; s_u[lane][1] = (double)v[1] / l; s_u[lane][2] = (double)v[2] / l;
-                s_n[lane][0] = fx[in]; s_n[lane][1] = fy[in]; s_n[lane][2] = fz[in];
+                s_n[lane][0] = fr.x[in]; s_n[lane][1] = fr.y[in]; s_n[lane][2] = fr.z[in];
             }
         }
     }
@@ -3305,8 +3304,8 @@ __global__ __launch_bounds__(64) void k_ss_hbond(vmd_ss_params_t p) {
         const int dl = (int)(e >> 6), j = (int)(e & 63u);
         float on[3] = {s_n[dl][0] - s_pos[j][6], s_n[dl][1] - s_pos[j][7], s_n[dl][2] - s_pos[j][8]};
         float cn[3] = {s_n[dl][0] - s_pos[j][3], s_n[dl][1] - s_pos[j][4], s_n[dl][2] - s_pos[j][5]};
-        vmd_mi3_rintf(bx, on[0], on[1], on[2]);
-        vmd_mi3_rintf(bx, cn[0], cn[1], cn[2]);
+        vmd_mi3_rintf(fr.bx, on[0], on[1], on[2]);
+        vmd_mi3_rintf(fr.bx, cn[0], cn[1], cn[2]);
         const double u[3] = {s_u[dl][0], s_u[dl][1], s_u[dl][2]};
         if (vmd_ss_bond(on, cn, u)) {
             atomicOr(&s_hb[j][dl >> 5], 1u << (dl & 31));
@@ -3320,7 +3319,7 @@ __global__ __launch_bounds__(64) void k_ss_hbond(vmd_ss_params_t p) {
         bool gate = false;
         if (donor && s_acc[j] && a != d && !(d == a + 1 && s_rng[j] == rd)) {
             float g[3] = {A[0] - s_pos[j][0], A[1] - s_pos[j][1], A[2] - s_pos[j][2]};
-            vmd_mi3_rintf(bx, g[0], g[1], g[2]);
+            vmd_mi3_rintf(fr.bx, g[0], g[1], g[2]);
             gate = ((double)g[0] * (double)g[0] + (double)g[1] * (double)g[1]) + (double)g[2] * (double)g[2] < 81.0;
         }
         const unsigned long long m = __ballot(gate ? 1 : 0);
@@ -3352,7 +3351,7 @@ __device__ __forceinline__ unsigned long long vmd_ss_up(const unsigned long long
 // moves, masked with "j has both neighbours" and, inside i's range, |i - j| >= 3.  A row whose i lacks a neighbour is zero.
 __global__ __launch_bounds__(256) void k_ss_bridges(vmd_ss_params_t p) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long long)p.B * p.nseg * p.W) return;
+    if (t >= (long long)p.f.B * p.nseg * p.W) return;
     const int w = (int)(t % p.W), i = (int)((t / p.W) % p.nseg);
     const size_t b = (size_t)(t / ((long long)p.W * p.nseg));
     unsigned long long par = 0ull, anti = 0ull;
@@ -3439,10 +3438,7 @@ __global__ __launch_bounds__(256) void k_ss_assign(vmd_ss_params_t p) {
     }
     __syncthreads();
     // passes 5 - 7: turn, bend, coil; the class row and the populations
-    const float* fx = p.xyz + b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_box_t bx = vmd_load_box(p.boxes, (int)b, p.pbc);
+    const vmd_frame_t fr = vmd_frame(p.f, (int)b);
     unsigned cnt[VMD_SS_CODES];
 #pragma unroll
     for (int k = 0; k < VMD_SS_CODES; ++k) cnt[k] = 0u;
@@ -3458,10 +3454,11 @@ __global__ __launch_bounds__(256) void k_ss_assign(vmd_ss_params_t p) {
                 code = turn ? 2 : 1;
                 if (!turn && i >= 2 && i + 2 < nseg && p.rng[i - 2] == p.rng[i] && p.rng[i + 2] == p.rng[i]) {
                     const int i0a = p.ca[i - 2], i1a = p.ca[i], i2a = p.ca[i + 2];
-                    float a[3] = {fx[i1a] - fx[i0a], fy[i1a] - fy[i0a], fz[i1a] - fz[i0a]};
-                    float c[3] = {fx[i2a] - fx[i1a], fy[i2a] - fy[i1a], fz[i2a] - fz[i1a]};
-                    vmd_mi3_rintf(bx, a[0], a[1], a[2]);
-                    vmd_mi3_rintf(bx, c[0], c[1], c[2]);
+                    const float A0[3] = {fr.x[i0a], fr.y[i0a], fr.z[i0a]}, A1[3] = {fr.x[i1a], fr.y[i1a], fr.z[i1a]};
+                    const float A2[3] = {fr.x[i2a], fr.y[i2a], fr.z[i2a]};
+                    float a[3], c[3];
+                    vmd_bond(fr.bx, A0, A1, a);
+                    vmd_bond(fr.bx, A1, A2, c);
                     const double aa = vmd_dot_d(a[0], a[1], a[2], a[0], a[1], a[2]), cc = vmd_dot_d(c[0], c[1], c[2], c[0], c[1], c[2]);
                     const double q = aa * cc;
                     if (q > 0.0 && vmd_dot_d(a[0], a[1], a[2], c[0], c[1], c[2]) / sqrt(q) < 0.3420201433256687) code = 3;
@@ -3480,21 +3477,39 @@ __global__ __launch_bounds__(256) void k_ss_assign(vmd_ss_params_t p) {
 
 // ------------------------------------------------------------------------------------------------ K5c: shape_weights
 
-// The reduction order is a function of the set size alone: a set is cut into chunks of VMD_SHAPE_CHUNK atoms; atom j of a chunk belongs to
-// thread j % 256, which adds its atoms in increasing j; the 64 lanes of a wave are summed by the xor butterfly 32, 16, 8, 4, 2, 1; the four
-// waves of the block and then the chunks are added in increasing order.
-#define VMD_SHAPE_CHUNK 4096
-#define VMD_SHAPE_BLOCK 256
-#define VMD_SHAPE_WAVE_SET 64      // a population whose largest set has at most this many atoms: one wave per set (k_shape_small)
+// ---- the set reduction of K5c and K5d (rules 1 - 5): its order is a function of the set size alone.  (1) A set is cut into
+// chunks of VMD_SET_CHUNK atoms, atom j of a chunk belongs to thread j % VMD_SET_BLOCK; (2) a thread adds its atoms in increasing j;
+// (3) the 64 lanes of a wave are summed by the xor butterfly 32, 16, 8, 4, 2, 1 (vmd_set_wave_sum); (4) the four waves of the block as
+// ((w0 + w1) + w2) + w3 (vmd_set_block_sum); (5) the chunks in increasing order (vmd_set_chunk_sum).  None of the helpers owns LDS.
+#define VMD_SET_CHUNK 4096
+#define VMD_SET_BLOCK 256
+#define VMD_SET_STEPS (VMD_SET_CHUNK / VMD_SET_BLOCK)       // atoms per thread and chunk
+#define VMD_SET_WAVES (VMD_SET_BLOCK / 64)
+#define VMD_SET_WAVE_SET 64        // a population whose largest set has at most this many atoms: one wave per set (the _small kernels)
+#define VMD_RMSD_GROUP 2           // atoms a thread takes per step of k_rmsd_moments (loads first, one barrier per step); the others take 4
+static_assert(VMD_SET_STEPS == 16, "rule 2 and the pinned restatements of the tests: at most 16 atoms per thread and chunk");
+static_assert(VMD_SET_STEPS % 4 == 0 && VMD_SET_STEPS % VMD_RMSD_GROUP == 0, "a step's atoms divide the chunk's steps");
+static_assert(VMD_SET_WAVES == 4, "rule 4 is written out for four waves");
+static_assert(VMD_SET_WAVE_SET == 64, "a _small kernel holds one atom per lane");
 
-struct vmd_shape_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
-    const int32_t* set; const float* mass; const int32_t* off; int P;   // context c: set[off[c] .. off[c+1]), masses parallel to set
-    int nchunk;        // chunks of the largest set
-    double* partial;   // [B][P][nchunk][10]: W, S1 x y z, S2 xx xy xz yy yz zz
-    float* lin; float* plan; float* iso;   // [B][P] each
-};
+__host__ __device__ inline int vmd_set_chunks(int n) { return (n + VMD_SET_CHUNK - 1) / VMD_SET_CHUNK; }
+
+// context c of a population: its atoms are set[k0 .. k0 + n), masses parallel to them
+struct vmd_set_slice_t { int k0, n; };
+__device__ __forceinline__ vmd_set_slice_t vmd_set_slice(const int32_t* off, int c) {
+    const int k0 = off[c];
+    return vmd_set_slice_t{k0, off[c + 1] - k0};
+}
+// block blockIdx.x of a (frame, context, chunk) grid: bc = b * P + c, a0 = the chunk's first atom.  False: the whole block leaves (a context
+// with fewer chunks than the largest set).
+struct vmd_set_block_t { int chunk, bc, b, c, a0; vmd_set_slice_t s; };
+__device__ __forceinline__ bool vmd_set_block(const int32_t* off, int P, int nchunk, vmd_set_block_t& w) {
+    w.chunk = blockIdx.x % nchunk; w.bc = blockIdx.x / nchunk;
+    w.b = w.bc / P; w.c = w.bc - w.b * P;
+    w.s = vmd_set_slice(off, w.c);
+    w.a0 = w.chunk * VMD_SET_CHUNK;
+    return w.a0 < w.s.n;
+}
 
 // both 32-bit halves of a double through the float shuffle (bit moves)
 __device__ __forceinline__ double vmd_shfl_xor_f64(double v, int o) {
@@ -3505,49 +3520,89 @@ __device__ __forceinline__ double vmd_shfl_xor_f64(double v, int o) {
     __builtin_memcpy(&v, h, 8);
     return v;
 }
+template <int N>
+__device__ __forceinline__ void vmd_set_wave_sum(double s[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] = s[k] + vmd_shfl_xor_f64(s[k], o);
+}
+// the block's N sums from its waves' (every lane of a wave holds the wave's), through the caller's s_wave: out[k] by thread k
+template <class T, int N>
+__device__ __forceinline__ void vmd_set_block_sum(const T s[N], T (*s_wave)[N], T* out) {
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_wave[tid >> 6][k] = s[k];
+    __syncthreads();
+    if (tid < N) out[tid] = ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid];
+}
+// the sums of a set of n atoms from its chunks' partials q[chunk][N]
+template <int N>
+__device__ __forceinline__ void vmd_set_chunk_sum(const double* q, int n, double s[N]) {
+    const int nch = vmd_set_chunks(n);
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = q[k];
+    for (int ch = 1; ch < nch; ++ch)
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] = s[k] + q[ch * N + k];
+}
+// what rules 4 and 5 make of a wave's sum when the set is one wave of one chunk: three empty waves add +0 (a -0 becomes +0)
+__device__ __forceinline__ double vmd_set_small_sum(double v) { return ((v + 0.0) + 0.0) + 0.0; }
 
-// The shape kernels' offset e = mi(x - x_first), vmd_mi3_rint bit for bit.  Orthorhombic axes avoid the division in the common case:
-// d - L rint(d / L) needs only the INTEGER nearest to d / L, and q = d * (1 / L) is within 2^-51 |q| of the quotient, so rint(q) is that
-// integer unless q lies that close to a half-integer; then (and for huge |q|) the quotients themselves are formed - one rare branch per
-// atom, behind the loads.  iL = 1 / L in fp64, once per thread.
-struct vmd_shape_box_t { vmd_box_t bx; double Lx, Ly, Lz, iLx, iLy, iLz; };
-__device__ __forceinline__ vmd_shape_box_t vmd_shape_box(const float* boxes, int b, uint32_t pbc) {
-    vmd_shape_box_t s;
-    s.bx = vmd_load_box(boxes, b, pbc);
-    s.Lx = (double)s.bx.Lx; s.Ly = (double)s.bx.Ly; s.Lz = (double)s.bx.Lz;
+// A frame's cell in fp64 with 1 / L, once per thread.  Orthorhombic axes avoid the division in the common case: d - L rint(d / L) needs only
+// the INTEGER nearest to d / L, and q = d * (1 / L) is within 2^-51 |q| of the quotient, so rint(q) is that integer unless q lies that
+// close to a half-integer (vmd_set_round_sure); then (and for huge |q|) the quotient itself is formed - one rare branch per atom, behind
+// the loads.
+struct vmd_set_frame_t { vmd_frame_t fr; double Lx, Ly, Lz, iLx, iLy, iLz, xy, xz, yz; };
+__device__ __forceinline__ vmd_set_frame_t vmd_set_frame(const vmd_frames_t& f, int b) {
+    vmd_set_frame_t s;
+    s.fr = vmd_frame(f, b);
+    s.Lx = (double)s.fr.bx.Lx; s.Ly = (double)s.fr.bx.Ly; s.Lz = (double)s.fr.bx.Lz;
+    s.xy = (double)s.fr.bx.xy; s.xz = (double)s.fr.bx.xz; s.yz = (double)s.fr.bx.yz;
     s.iLx = 1.0 / s.Lx; s.iLy = 1.0 / s.Ly; s.iLz = 1.0 / s.Lz;
     return s;
 }
-__device__ __forceinline__ bool vmd_shape_round_sure(double q, double r) { return fabs(q - r) < 0.499999 && fabs(q) < 1.0e9; }
-__device__ __forceinline__ void vmd_shape_mi(const vmd_shape_box_t& s, double& dx, double& dy, double& dz) {
-    if (s.bx.tri) { vmd_mi3_rint(s.bx, dx, dy, dz); return; }
-    const double qx = dx * s.iLx, qy = dy * s.iLy, qz = dz * s.iLz;
-    double rx = rint(qx), ry = rint(qy), rz = rint(qz);
-    const bool sure = (!s.bx.px || vmd_shape_round_sure(qx, rx)) && (!s.bx.py || vmd_shape_round_sure(qy, ry)) &&
-                      (!s.bx.pz || vmd_shape_round_sure(qz, rz));
-    if (__builtin_expect(!sure, 0)) { rx = rint(dx / s.Lx); ry = rint(dy / s.Ly); rz = rint(dz / s.Lz); }
-    if (s.bx.px) dx = dx - s.Lx * rx;
-    if (s.bx.py) dy = dy - s.Ly * ry;
-    if (s.bx.pz) dz = dz - s.Lz * rz;
-}
+__device__ __forceinline__ bool vmd_set_round_sure(double q, double r) { return fabs(q - r) < 0.499999 && fabs(q) < 1.0e9; }
 
 // Atom a of the set in two steps, so that a thread has the loads of several atoms in flight before it looks at the first (a branch
 // between two loads makes the compiler wait for each of them).  An atom past the end is read as atom 0 with weight 0: every term is
 // +-0 and leaves the sums as they are.
-struct vmd_shape_atom_t { float x, y, z, w; };
-__device__ __forceinline__ vmd_shape_atom_t vmd_shape_load(const float* fx, const float* fy, const float* fz, const int32_t* set,
-                                                           const float* mass, int a, int n) {
+struct vmd_set_atom_t { float x, y, z, w; };
+__device__ __forceinline__ vmd_set_atom_t vmd_set_load(const vmd_frame_t& fr, const int32_t* set, const float* mass, int a, int n) {
     const bool live = a < n;
     const int aa = live ? a : 0;
     const int i = set[aa];
-    vmd_shape_atom_t q;
-    q.x = fx[i]; q.y = fy[i]; q.z = fz[i];
+    vmd_set_atom_t q;
+    q.x = fr.x[i]; q.y = fr.y[i]; q.z = fr.z[i];
     const float m = mass[aa];
     q.w = live ? m : 0.0f;
     return q;
 }
+
+struct vmd_shape_params_t {
+    vmd_frames_t f;
+    const int32_t* set; const float* mass; const int32_t* off; int P;   // context c: set[off[c] .. off[c+1]), masses parallel to set
+    int nchunk;        // chunks of the largest set
+    double* partial;   // [B][P][nchunk][10]: W, S1 x y z, S2 xx xy xz yy yz zz
+    float* lin; float* plan; float* iso;   // [B][P] each
+};
+
+// The shape kernels' offset e = mi(x - x_first), vmd_mi3_rint bit for bit
+__device__ __forceinline__ void vmd_shape_mi(const vmd_set_frame_t& s, double& dx, double& dy, double& dz) {
+    const vmd_box_t& bx = s.fr.bx;
+    if (bx.tri) { vmd_mi3_rint(bx, dx, dy, dz); return; }
+    const double qx = dx * s.iLx, qy = dy * s.iLy, qz = dz * s.iLz;
+    double rx = rint(qx), ry = rint(qy), rz = rint(qz);
+    const bool sure = (!bx.px || vmd_set_round_sure(qx, rx)) && (!bx.py || vmd_set_round_sure(qy, ry)) && (!bx.pz || vmd_set_round_sure(qz, rz));
+    if (__builtin_expect(!sure, 0)) { rx = rint(dx / s.Lx); ry = rint(dy / s.Ly); rz = rint(dz / s.Lz); }
+    if (bx.px) dx = dx - s.Lx * rx;
+    if (bx.py) dy = dy - s.Ly * ry;
+    if (bx.pz) dz = dz - s.Lz * rz;
+}
+
 // the ten moments of one atom added to s
-__device__ __forceinline__ void vmd_shape_add(const vmd_shape_atom_t& q, const vmd_shape_box_t& bx, double p0x, double p0y, double p0z,
+__device__ __forceinline__ void vmd_shape_add(const vmd_set_atom_t& q, const vmd_set_frame_t& bx, double p0x, double p0y, double p0z,
                                               double s[10]) {
     const double w = (double)q.w;
     double ex = (double)q.x - p0x, ey = (double)q.y - p0y, ez = (double)q.z - p0z;
@@ -3557,13 +3612,6 @@ __device__ __forceinline__ void vmd_shape_add(const vmd_shape_atom_t& q, const v
     s[1] = s[1] + wx; s[2] = s[2] + wy; s[3] = s[3] + wz;
     s[4] = s[4] + wx * ex; s[5] = s[5] + wx * ey; s[6] = s[6] + wx * ez;
     s[7] = s[7] + wy * ey; s[8] = s[8] + wy * ez; s[9] = s[9] + wz * ez;
-}
-
-__device__ __forceinline__ void vmd_shape_wave_sum(double s[10]) {
-#pragma unroll
-    for (int k = 0; k < 10; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] = s[k] + vmd_shfl_xor_f64(s[k], o);
 }
 
 // Westin's measures of M = S2 - S1 S1^T / W: eigenvalues by cyclic Jacobi (pairs (0,1), (0,2), (1,2), at most 16 sweeps, ends when the
@@ -3611,77 +3659,56 @@ __device__ void vmd_shape_values(const double s[10], float& lin, float& plan, fl
 }
 
 // one block per (frame, context, chunk): ten fp64 sums per thread in registers, wave butterfly, the four wave sums through LDS
-__global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_moments(vmd_shape_params_t p) {
-    __shared__ double s_wave[VMD_SHAPE_BLOCK / 64][10];
-    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
-    const int b = bc / p.P, c = bc - b * p.P;
-    const int k0 = p.off[c], n = p.off[c + 1] - k0;
-    const int a0 = chunk * VMD_SHAPE_CHUNK;
-    if (a0 >= n) return;          // the whole block: a context with fewer chunks than the largest set
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_shape_box_t bx = vmd_shape_box(p.boxes, b, p.pbc);
-    const int32_t* set = p.set + k0;
-    const float* mass = p.mass + k0;
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_shape_moments(vmd_shape_params_t p) {
+    __shared__ double s_wave[VMD_SET_WAVES][10];
+    vmd_set_block_t w;
+    if (!vmd_set_block(p.off, p.P, p.nchunk, w)) return;
+    const vmd_set_frame_t sf = vmd_set_frame(p.f, w.b);
+    const int32_t* set = p.set + w.s.k0;
+    const float* mass = p.mass + w.s.k0;
     const int i0 = set[0];
-    const double p0x = (double)fx[i0], p0y = (double)fy[i0], p0z = (double)fz[i0];
+    const double p0x = (double)sf.fr.x[i0], p0y = (double)sf.fr.y[i0], p0z = (double)sf.fr.z[i0];
     double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int tid = threadIdx.x;
     // four atoms per step: their sixteen loads first, then the sums in atom order
 #pragma unroll 1
-    for (int k = 0; k < VMD_SHAPE_CHUNK / VMD_SHAPE_BLOCK; k += 4) {
-        vmd_shape_atom_t q[4];
+    for (int k = 0; k < VMD_SET_STEPS; k += 4) {
+        vmd_set_atom_t q[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = vmd_shape_load(fx, fy, fz, set, mass, a0 + (k + u) * VMD_SHAPE_BLOCK + tid, n);
+        for (int u = 0; u < 4; ++u) q[u] = vmd_set_load(sf.fr, set, mass, w.a0 + (k + u) * VMD_SET_BLOCK + tid, w.s.n);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) vmd_shape_add(q[u], bx, p0x, p0y, p0z, s);
+        for (int u = 0; u < 4; ++u) vmd_shape_add(q[u], sf, p0x, p0y, p0z, s);
     }
-    vmd_shape_wave_sum(s);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 10; ++k) s_wave[tid >> 6][k] = s[k];
-    __syncthreads();
-    if (tid < 10) p.partial[(size_t)blockIdx.x * 10 + tid] = ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid];
+    vmd_set_wave_sum<10>(s);
+    vmd_set_block_sum<double, 10>(s, s_wave, p.partial + (size_t)blockIdx.x * 10);
 }
 
 // one thread per (frame, context): the chunk sums in chunk order, then the three values
 __global__ __launch_bounds__(64) void k_shape_finish(vmd_shape_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.P) return;
-    const int c = t % p.P;
-    const int n = p.off[c + 1] - p.off[c];
-    const int nch = (n + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK;
-    const double* q = p.partial + (size_t)t * p.nchunk * 10;
+    if (t >= p.f.B * p.P) return;
     double s[10];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) s[k] = q[k];
-    for (int ch = 1; ch < nch; ++ch)
-#pragma unroll
-        for (int k = 0; k < 10; ++k) s[k] = s[k] + q[ch * 10 + k];
+    vmd_set_chunk_sum<10>(p.partial + (size_t)t * p.nchunk * 10, vmd_set_slice(p.off, t % p.P).n, s);
     vmd_shape_values(s, p.lin[t], p.plan[t], p.iso[t]);
 }
 
 // populations of small sets (`... in residue(:)`): one wave per (frame, context), lane j holds atom j; the same sums in the same order as
 // k_shape_moments + k_shape_finish give for such a set (one chunk, one atom per thread, three empty waves), without the partials
-__global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_small(vmd_shape_params_t p) {
-    const int t = blockIdx.x * (VMD_SHAPE_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (t >= p.B * p.P) return;   // the whole wave
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_shape_small(vmd_shape_params_t p) {
+    const int t = blockIdx.x * VMD_SET_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= p.f.B * p.P) return;   // the whole wave
     const int b = t / p.P, c = t - b * p.P;
-    const int k0 = p.off[c], n = p.off[c + 1] - k0;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_shape_box_t bx = vmd_shape_box(p.boxes, b, p.pbc);
-    const int32_t* set = p.set + k0;
+    const vmd_set_slice_t sl = vmd_set_slice(p.off, c);
+    const vmd_set_frame_t sf = vmd_set_frame(p.f, b);
+    const int32_t* set = p.set + sl.k0;
     const int i0 = set[0];
-    const double p0x = (double)fx[i0], p0y = (double)fy[i0], p0z = (double)fz[i0];
+    const double p0x = (double)sf.fr.x[i0], p0y = (double)sf.fr.y[i0], p0z = (double)sf.fr.z[i0];
     double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    vmd_shape_add(vmd_shape_load(fx, fy, fz, set, p.mass + k0, lane, n), bx, p0x, p0y, p0z, s);
-    vmd_shape_wave_sum(s);
+    vmd_shape_add(vmd_set_load(sf.fr, set, p.mass + sl.k0, lane, sl.n), sf, p0x, p0y, p0z, s);
+    vmd_set_wave_sum<10>(s);
     if (lane != 0) return;
 #pragma unroll
-    for (int k = 0; k < 10; ++k) s[k] = ((s[k] + 0.0) + 0.0) + 0.0;
+    for (int k = 0; k < 10; ++k) s[k] = vmd_set_small_sum(s[k]);
     vmd_shape_values(s, p.lin[t], p.plan[t], p.iso[t]);
 }
 
@@ -3690,18 +3717,12 @@ __global__ __launch_bounds__(VMD_SHAPE_BLOCK) void k_shape_small(vmd_shape_param
 // `name = rmsd(sel)`: the mass-weighted RMSD of a set after the best rigid fit onto its own pose at trajectory frame 0.  The set is made
 // whole along its index chain with INTEGER link shifts (n_a = -rint(frac(x_a - x_{a-1})), k_a = n_1 + ... + n_a: a prefix sum any order
 // of which gives the same result), the offsets e_a = (x_a - x_0) + cart(k_a) enter thirteen fp64 sums, and Horn's largest eigenvalue
-// gives the value without the rotation.  The reduction order is shape_weights' (DESIGN 1.4): a function of the set size alone.
-#define VMD_RMSD_CHUNK 4096
-#define VMD_RMSD_BLOCK 256
-#define VMD_RMSD_STEPS (VMD_RMSD_CHUNK / VMD_RMSD_BLOCK)
-#define VMD_RMSD_WAVE_SET 64       // a population whose largest set has at most this many atoms: one wave per set (k_rmsd_small)
-#define VMD_RMSD_GROUP 2           // atoms a thread takes per step of k_rmsd_moments (loads first, one barrier per step)
+// gives the value without the rotation.  The reduction is shape_weights' (the vmd_set_* helpers of K5c).
 #define VMD_RMSD_NSUM 14           // S1 x y z, G, C xx xy xz yx yy yz zx zy zz (C_ij = sum (w e_i) u_j), W (the pose pass only)
 #define VMD_RMSD_NCONST 8          // the pose's constants per context: W, U1 x y z, Gu (three unused)
 
 struct vmd_rmsd_params_t {
-    const float* xyz; size_t frame_stride; size_t row_stride;
-    const float* boxes; uint32_t pbc; int B;
+    vmd_frames_t f;
     const int32_t* set; const float* mass; const int32_t* off; int P;   // context c: set[off[c] .. off[c+1]), masses parallel to set
     int nchunk;         // chunks of the largest set
     int32_t* shift;     // [B][P][nchunk][4]: the chunk's total link shift x y z (one unused)
@@ -3712,29 +3733,21 @@ struct vmd_rmsd_params_t {
     float* out;         // [B][P]
 };
 
-struct vmd_rmsd_box_t { bool px, py, pz, tri; double Lx, Ly, Lz, iLx, iLy, iLz, xy, xz, yz; };
-__device__ __forceinline__ vmd_rmsd_box_t vmd_rmsd_box(const float* boxes, int b, uint32_t pbc) {
-    const vmd_box_t bx = vmd_load_box(boxes, b, pbc);
-    vmd_rmsd_box_t s;
-    s.Lx = (double)bx.Lx; s.Ly = (double)bx.Ly; s.Lz = (double)bx.Lz;
-    s.xy = (double)bx.xy; s.xz = (double)bx.xz; s.yz = (double)bx.yz;
-    s.tri = bx.tri;
-    s.px = bx.px && s.Lx > 0.0; s.py = bx.py && s.Ly > 0.0; s.pz = bx.pz && s.Lz > 0.0;
-    s.iLx = 1.0 / s.Lx; s.iLy = 1.0 / s.Ly; s.iLz = 1.0 / s.Lz;
-    return s;
-}
-// -rint(d / L) as an integer.  Only the integer is needed, so the quotient is formed through 1 / L unless that could round to the other
-// side of a half-integer (vmd_shape_round_sure); then the division itself decides.
-__device__ __forceinline__ int vmd_rmsd_axis_shift(double d, double L, double iL) {
+// -rint(d / L) as an integer, 0 on an axis that is open.  Only the integer is needed, so the quotient is formed through 1 / L unless that
+// could round to the other side of a half-integer (vmd_set_round_sure); then the division itself decides.  An axis flagged periodic
+// whose length is not > 0 counts as open HERE and not in vmd_set_frame: the evaluator clears such flags itself (batch_pbc) but the C ABI
+// can be called with them set, the integer of d / 0 is undefined, and shape_weights (vmd_shape_mi) keeps what its division gives.
+__device__ __forceinline__ int vmd_rmsd_axis_shift(bool periodic, double d, double L, double iL) {
+    if (!(periodic && L > 0.0)) return 0;
     const double q = d * iL;
     double r = rint(q);
-    if (__builtin_expect(!vmd_shape_round_sure(q, r), 0)) r = rint(d / L);
+    if (__builtin_expect(!vmd_set_round_sure(q, r), 0)) r = rint(d / L);
     return -(int)r;
 }
 // the lattice vector k in Cartesian components, in this written-out order
-__device__ __forceinline__ void vmd_rmsd_cart(const vmd_rmsd_box_t& b, int kx, int ky, int kz, double& cx, double& cy, double& cz) {
+__device__ __forceinline__ void vmd_rmsd_cart(const vmd_set_frame_t& b, int kx, int ky, int kz, double& cx, double& cy, double& cz) {
     const double fx = (double)kx, fy = (double)ky, fz = (double)kz;
-    if (b.tri) {
+    if (b.fr.bx.tri) {
         cx = (fx * b.Lx + b.xy * fy) + b.xz * fz;
         cy = fy * b.Ly + b.yz * fz;
         cz = fz * b.Lz;
@@ -3743,32 +3756,26 @@ __device__ __forceinline__ void vmd_rmsd_cart(const vmd_rmsd_box_t& b, int kx, i
 
 // Atom a of the set and its predecessor in the chain, loaded together (all loads of a step stand before its first branch, as in
 // k_shape_moments).  An atom past the end is read as atom 0 with weight 0; atom 0 is its own predecessor: both have link shift 0.
-struct vmd_rmsd_atom_t { float x, y, z, qx, qy, qz, w; };
-__device__ __forceinline__ vmd_rmsd_atom_t vmd_rmsd_load(const float* fx, const float* fy, const float* fz, const int32_t* set,
-                                                         const float* mass, int a, int n) {
-    const bool live = a < n;
-    const int aa = live ? a : 0;
-    const int pa = aa > 0 ? aa - 1 : 0;
-    const int i = set[aa], j = set[pa];
+struct vmd_rmsd_atom_t { vmd_set_atom_t at; float qx, qy, qz; };
+__device__ __forceinline__ vmd_rmsd_atom_t vmd_rmsd_load(const vmd_frame_t& fr, const int32_t* set, const float* mass, int a, int n) {
     vmd_rmsd_atom_t q;
-    q.x = fx[i]; q.y = fy[i]; q.z = fz[i];
-    q.qx = fx[j]; q.qy = fy[j]; q.qz = fz[j];
-    const float m = mass[aa];
-    q.w = live ? m : 0.0f;
+    const int j = set[a < n && a > 0 ? a - 1 : 0];      // both index loads in front of the coordinates' (k_rmsd_shift: 64 VGPRs, 73 the other way)
+    q.at = vmd_set_load(fr, set, mass, a, n);
+    q.qx = fr.x[j]; q.qy = fr.y[j]; q.qz = fr.z[j];
     return q;
 }
-__device__ __forceinline__ void vmd_rmsd_link(const vmd_rmsd_atom_t& q, const vmd_rmsd_box_t& b, int& nx, int& ny, int& nz) {
-    const double dx = (double)q.x - (double)q.qx, dy = (double)q.y - (double)q.qy, dz = (double)q.z - (double)q.qz;
-    if (b.tri) {
+__device__ __forceinline__ void vmd_rmsd_link(const vmd_rmsd_atom_t& q, const vmd_set_frame_t& b, int& nx, int& ny, int& nz) {
+    const double dx = (double)q.at.x - (double)q.qx, dy = (double)q.at.y - (double)q.qy, dz = (double)q.at.z - (double)q.qz;
+    if (b.fr.bx.tri) {
         const double sz = dz / b.Lz;
         const double sy = (dy - b.yz * sz) / b.Ly;
         const double sx = ((dx - b.xy * sy) - b.xz * sz) / b.Lx;
         nx = -(int)rint(sx); ny = -(int)rint(sy); nz = -(int)rint(sz);
         return;
     }
-    nx = b.px ? vmd_rmsd_axis_shift(dx, b.Lx, b.iLx) : 0;
-    ny = b.py ? vmd_rmsd_axis_shift(dy, b.Ly, b.iLy) : 0;
-    nz = b.pz ? vmd_rmsd_axis_shift(dz, b.Lz, b.iLz) : 0;
+    nx = vmd_rmsd_axis_shift(b.fr.bx.px, dx, b.Lx, b.iLx);
+    ny = vmd_rmsd_axis_shift(b.fr.bx.py, dy, b.Ly, b.iLy);
+    nz = vmd_rmsd_axis_shift(b.fr.bx.pz, dz, b.Lz, b.iLz);
 }
 
 __device__ __forceinline__ int vmd_shfl_xor_i32(int v, int o) { return __float_as_int(__shfl_xor(__int_as_float(v), o)); }
@@ -3785,7 +3792,7 @@ __device__ __forceinline__ void vmd_wave_scan_i32(int v, int lane, int& incl, in
 
 // the sums of one atom: k = its accumulated shift, u = its pose offset (frame pass) / where its pose offset goes (pose pass, live atoms)
 template <bool POSE>
-__device__ __forceinline__ void vmd_rmsd_add(const vmd_rmsd_atom_t& q, const vmd_rmsd_box_t& b, double x0, double y0, double z0,
+__device__ __forceinline__ void vmd_rmsd_add(const vmd_set_atom_t& q, const vmd_set_frame_t& b, double x0, double y0, double z0,
                                              int kx, int ky, int kz, const double u[3], double* pose_out, double s[VMD_RMSD_NSUM]) {
     const double w = (double)q.w;
     double cx, cy, cz;
@@ -3802,13 +3809,6 @@ __device__ __forceinline__ void vmd_rmsd_add(const vmd_rmsd_atom_t& q, const vmd
         s[7] = s[7] + wy * u[0]; s[8] = s[8] + wy * u[1]; s[9] = s[9] + wy * u[2];
         s[10] = s[10] + wz * u[0]; s[11] = s[11] + wz * u[1]; s[12] = s[12] + wz * u[2];
     }
-}
-
-__device__ __forceinline__ void vmd_rmsd_wave_sum(double s[VMD_RMSD_NSUM]) {
-#pragma unroll
-    for (int k = 0; k < VMD_RMSD_NSUM; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] = s[k] + vmd_shfl_xor_f64(s[k], o);
 }
 
 // the value from the thirteen sums and the pose's constants: Horn's largest eigenvalue, no rotation matrix
@@ -3830,77 +3830,64 @@ __device__ float vmd_rmsd_value(const double s[VMD_RMSD_NSUM], const double* cst
 }
 
 // one block per (frame, context, chunk): the chunk's total link shift, the link to the previous chunk's last atom included
-__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_shift(vmd_rmsd_params_t p) {
-    __shared__ int s_w[VMD_RMSD_BLOCK / 64][3];
-    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
-    const int b = bc / p.P, c = bc - b * p.P;
-    const int k0 = p.off[c], n = p.off[c + 1] - k0;
-    const int a0 = chunk * VMD_RMSD_CHUNK;
-    if (a0 >= n) return;          // the whole block
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
-    const int32_t* set = p.set + k0;
-    const float* mass = p.mass + k0;
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_shift(vmd_rmsd_params_t p) {
+    __shared__ int s_w[VMD_SET_WAVES][3];
+    vmd_set_block_t w;
+    if (!vmd_set_block(p.off, p.P, p.nchunk, w)) return;
+    const vmd_set_frame_t sf = vmd_set_frame(p.f, w.b);
+    const int32_t* set = p.set + w.s.k0;
+    const float* mass = p.mass + w.s.k0;
     const int tid = threadIdx.x;
-    int sx = 0, sy = 0, sz = 0;
+    int s[3] = {0, 0, 0};
 #pragma unroll 1
-    for (int g = 0; g < VMD_RMSD_STEPS; g += 4) {
+    for (int g = 0; g < VMD_SET_STEPS; g += 4) {
         vmd_rmsd_atom_t q[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = vmd_rmsd_load(fx, fy, fz, set, mass, a0 + (g + u) * VMD_RMSD_BLOCK + tid, n);
+        for (int u = 0; u < 4; ++u) q[u] = vmd_rmsd_load(sf.fr, set, mass, w.a0 + (g + u) * VMD_SET_BLOCK + tid, w.s.n);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             int nx, ny, nz;
-            vmd_rmsd_link(q[u], bx, nx, ny, nz);
-            sx += nx; sy += ny; sz += nz;
+            vmd_rmsd_link(q[u], sf, nx, ny, nz);
+            s[0] += nx; s[1] += ny; s[2] += nz;
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sx += vmd_shfl_xor_i32(sx, o); sy += vmd_shfl_xor_i32(sy, o); sz += vmd_shfl_xor_i32(sz, o); }
-    if ((tid & 63) == 0) { s_w[tid >> 6][0] = sx; s_w[tid >> 6][1] = sy; s_w[tid >> 6][2] = sz; }
-    __syncthreads();
-    if (tid < 3) p.shift[(size_t)blockIdx.x * 4 + tid] = ((s_w[0][tid] + s_w[1][tid]) + s_w[2][tid]) + s_w[3][tid];
+    for (int o = 32; o > 0; o >>= 1) { s[0] += vmd_shfl_xor_i32(s[0], o); s[1] += vmd_shfl_xor_i32(s[1], o); s[2] += vmd_shfl_xor_i32(s[2], o); }
+    vmd_set_block_sum<int, 3>(s, s_w, p.shift + (size_t)blockIdx.x * 4);
 }
 
 // one block per (frame, context, chunk): carry-in from the earlier chunks' totals, the in-chunk prefix sum of the link shifts (a wave
 // scan per step, the waves and steps joined through LDS), the sums per thread in registers, wave butterfly, the four waves through LDS.
 // POSE: the same over trajectory frame 0 - stores u_a and sums W instead of C.
 template <bool POSE>
-__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_moments(vmd_rmsd_params_t p) {
-    __shared__ int s_tot[VMD_RMSD_STEPS][VMD_RMSD_BLOCK / 64][3];
-    __shared__ double s_wave[VMD_RMSD_BLOCK / 64][VMD_RMSD_NSUM];
-    const int chunk = blockIdx.x % p.nchunk, bc = blockIdx.x / p.nchunk;
-    const int b = bc / p.P, c = bc - b * p.P;
-    const int k0 = p.off[c], n = p.off[c + 1] - k0;
-    const int a0 = chunk * VMD_RMSD_CHUNK;
-    if (a0 >= n) return;          // the whole block: a context with fewer chunks than the largest set
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
-    const int32_t* set = p.set + k0;
-    const float* mass = p.mass + k0;
-    double* pose = p.pose + (size_t)k0 * 3;
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_moments(vmd_rmsd_params_t p) {
+    __shared__ int s_tot[VMD_SET_STEPS][VMD_SET_WAVES][3];
+    __shared__ double s_wave[VMD_SET_WAVES][VMD_RMSD_NSUM];
+    vmd_set_block_t w;
+    if (!vmd_set_block(p.off, p.P, p.nchunk, w)) return;
+    const int n = w.s.n, a0 = w.a0;
+    const vmd_set_frame_t sf = vmd_set_frame(p.f, w.b);
+    const int32_t* set = p.set + w.s.k0;
+    const float* mass = p.mass + w.s.k0;
+    double* pose = p.pose + (size_t)w.s.k0 * 3;
     const int i0 = set[0];
-    const double x0 = (double)fx[i0], y0 = (double)fy[i0], z0 = (double)fz[i0];
+    const double x0 = (double)sf.fr.x[i0], y0 = (double)sf.fr.y[i0], z0 = (double)sf.fr.z[i0];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the shift of every atom in front of the current step
     int rx = 0, ry = 0, rz = 0;
-    const int32_t* sh = p.shift + (size_t)bc * p.nchunk * 4;
-    for (int ch = 0; ch < chunk; ++ch) { rx += sh[4 * ch + 0]; ry += sh[4 * ch + 1]; rz += sh[4 * ch + 2]; }
+    const int32_t* sh = p.shift + (size_t)w.bc * p.nchunk * 4;
+    for (int ch = 0; ch < w.chunk; ++ch) { rx += sh[4 * ch + 0]; ry += sh[4 * ch + 1]; rz += sh[4 * ch + 2]; }
     double s[VMD_RMSD_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // VMD_RMSD_GROUP atoms per step: their loads first, the link shifts and their wave scans, one barrier, then the sums in atom order
 #pragma unroll 1
-    for (int g = 0; g < VMD_RMSD_STEPS; g += VMD_RMSD_GROUP) {
+    for (int g = 0; g < VMD_SET_STEPS; g += VMD_RMSD_GROUP) {
         vmd_rmsd_atom_t q[VMD_RMSD_GROUP];
         double u[VMD_RMSD_GROUP][3];
         int ix[VMD_RMSD_GROUP], iy[VMD_RMSD_GROUP], iz[VMD_RMSD_GROUP];
 #pragma unroll
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
-            const int a = a0 + (g + k) * VMD_RMSD_BLOCK + tid;
-            q[k] = vmd_rmsd_load(fx, fy, fz, set, mass, a, n);
+            const int a = a0 + (g + k) * VMD_SET_BLOCK + tid;
+            q[k] = vmd_rmsd_load(sf.fr, set, mass, a, n);
             const int aa = a < n ? a : 0;
             if (!POSE) { u[k][0] = pose[3 * aa + 0]; u[k][1] = pose[3 * aa + 1]; u[k][2] = pose[3 * aa + 2]; }
             else { u[k][0] = 0.0; u[k][1] = 0.0; u[k][2] = 0.0; }
@@ -3908,7 +3895,7 @@ __global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_moments(vmd_rmsd_params
 #pragma unroll
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
             int nx, ny, nz, tx, ty, tz;
-            vmd_rmsd_link(q[k], bx, nx, ny, nz);
+            vmd_rmsd_link(q[k], sf, nx, ny, nz);
             // a molecule that is whole in the cell has no shift along most of its chain: a wave without any skips its three scans
             if (__ballot((nx | ny | nz) != 0) == 0ull) { ix[k] = iy[k] = iz[k] = tx = ty = tz = 0; }
             else {
@@ -3923,39 +3910,28 @@ __global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_moments(vmd_rmsd_params
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
             int kx = rx + ix[k], ky = ry + iy[k], kz = rz + iz[k];
 #pragma unroll
-            for (int w = 0; w < VMD_RMSD_BLOCK / 64; ++w) {
-                const int tx = s_tot[g + k][w][0], ty = s_tot[g + k][w][1], tz = s_tot[g + k][w][2];
-                if (w < wave) { kx += tx; ky += ty; kz += tz; }
+            for (int v = 0; v < VMD_SET_WAVES; ++v) {
+                const int tx = s_tot[g + k][v][0], ty = s_tot[g + k][v][1], tz = s_tot[g + k][v][2];
+                if (v < wave) { kx += tx; ky += ty; kz += tz; }
                 rx += tx; ry += ty; rz += tz;
             }
-            const int a = a0 + (g + k) * VMD_RMSD_BLOCK + tid;
-            vmd_rmsd_add<POSE>(q[k], bx, x0, y0, z0, kx, ky, kz, u[k], (POSE && a < n) ? pose + 3 * (size_t)a : nullptr, s);
+            const int a = a0 + (g + k) * VMD_SET_BLOCK + tid;
+            vmd_rmsd_add<POSE>(q[k].at, sf, x0, y0, z0, kx, ky, kz, u[k], (POSE && a < n) ? pose + 3 * (size_t)a : nullptr, s);
         }
     }
-    vmd_rmsd_wave_sum(s);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < VMD_RMSD_NSUM; ++k) s_wave[wave][k] = s[k];
-    __syncthreads();
-    if (tid < VMD_RMSD_NSUM)
-        p.partial[(size_t)blockIdx.x * VMD_RMSD_NSUM + tid] = ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid];
+    vmd_set_wave_sum<VMD_RMSD_NSUM>(s);
+    vmd_set_block_sum<double, VMD_RMSD_NSUM>(s, s_wave, p.partial + (size_t)blockIdx.x * VMD_RMSD_NSUM);
 }
 
 // one thread per (frame, context): the chunk sums in chunk order, then the value (POSE: the constants of the context)
 template <bool POSE>
 __global__ __launch_bounds__(64) void k_rmsd_finish(vmd_rmsd_params_t p) {
     const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= p.B * p.P) return;
+    if (t >= p.f.B * p.P) return;
     const int b = t / p.P, c = t - b * p.P;
-    const int n = p.off[c + 1] - p.off[c];
-    const int nch = (n + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK;
-    const double* q = p.partial + (size_t)t * p.nchunk * VMD_RMSD_NSUM;
+    const int n = vmd_set_slice(p.off, c).n;
     double s[VMD_RMSD_NSUM];
-#pragma unroll
-    for (int k = 0; k < VMD_RMSD_NSUM; ++k) s[k] = q[k];
-    for (int ch = 1; ch < nch; ++ch)
-#pragma unroll
-        for (int k = 0; k < VMD_RMSD_NSUM; ++k) s[k] = s[k] + q[ch * VMD_RMSD_NSUM + k];
+    vmd_set_chunk_sum<VMD_RMSD_NSUM>(p.partial + (size_t)t * p.nchunk * VMD_RMSD_NSUM, n, s);
     double* cst = p.cst + (size_t)c * VMD_RMSD_NCONST;
     if (POSE) { cst[0] = s[13]; cst[1] = s[0]; cst[2] = s[1]; cst[3] = s[2]; cst[4] = s[3]; }
     else p.out[t] = b == p.zero_row ? 0.0f : vmd_rmsd_value(s, cst, n);
@@ -3966,34 +3942,32 @@ __global__ __launch_bounds__(64) void k_rmsd_finish(vmd_rmsd_params_t p) {
 // to the partials (one "chunk" per set) and k_rmsd_finish forms the values, 64 sets per wave: a Jacobi iteration in lane 0 of every
 // wave kept the other 63 lanes waiting (1.97 ms per 200 000 sets against 0.3 ms this way)
 template <bool POSE>
-__global__ __launch_bounds__(VMD_RMSD_BLOCK) void k_rmsd_small(vmd_rmsd_params_t p) {
-    const int t = blockIdx.x * (VMD_RMSD_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (t >= p.B * p.P) return;   // the whole wave
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_small(vmd_rmsd_params_t p) {
+    const int t = blockIdx.x * VMD_SET_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= p.f.B * p.P) return;   // the whole wave
     const int b = t / p.P, c = t - b * p.P;
-    const int k0 = p.off[c], n = p.off[c + 1] - k0;
-    const float* fx = p.xyz + (size_t)b * p.frame_stride;
-    const float* fy = fx + p.row_stride;
-    const float* fz = fy + p.row_stride;
-    const vmd_rmsd_box_t bx = vmd_rmsd_box(p.boxes, b, p.pbc);
-    const int32_t* set = p.set + k0;
-    double* pose = p.pose + (size_t)k0 * 3;
+    const vmd_set_slice_t sl = vmd_set_slice(p.off, c);
+    const int n = sl.n;
+    const vmd_set_frame_t sf = vmd_set_frame(p.f, b);
+    const int32_t* set = p.set + sl.k0;
+    double* pose = p.pose + (size_t)sl.k0 * 3;
     const int i0 = set[0];
-    const double x0 = (double)fx[i0], y0 = (double)fy[i0], z0 = (double)fz[i0];
-    const vmd_rmsd_atom_t q = vmd_rmsd_load(fx, fy, fz, set, p.mass + k0, lane, n);
+    const double x0 = (double)sf.fr.x[i0], y0 = (double)sf.fr.y[i0], z0 = (double)sf.fr.z[i0];
+    const vmd_rmsd_atom_t q = vmd_rmsd_load(sf.fr, set, p.mass + sl.k0, lane, n);
     const int aa = lane < n ? lane : 0;
     double u[3] = {0.0, 0.0, 0.0};
     if (!POSE) { u[0] = pose[3 * aa + 0]; u[1] = pose[3 * aa + 1]; u[2] = pose[3 * aa + 2]; }
     int nx, ny, nz, kx, ky, kz, tx, ty, tz;
-    vmd_rmsd_link(q, bx, nx, ny, nz);
+    vmd_rmsd_link(q, sf, nx, ny, nz);
     vmd_wave_scan_i32(nx, lane, kx, tx);
     vmd_wave_scan_i32(ny, lane, ky, ty);
     vmd_wave_scan_i32(nz, lane, kz, tz);
     double s[VMD_RMSD_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    vmd_rmsd_add<POSE>(q, bx, x0, y0, z0, kx, ky, kz, u, (POSE && lane < n) ? pose + 3 * (size_t)lane : nullptr, s);
-    vmd_rmsd_wave_sum(s);
+    vmd_rmsd_add<POSE>(q.at, sf, x0, y0, z0, kx, ky, kz, u, (POSE && lane < n) ? pose + 3 * (size_t)lane : nullptr, s);
+    vmd_set_wave_sum<VMD_RMSD_NSUM>(s);
     if (lane != 0) return;
 #pragma unroll
-    for (int k = 0; k < VMD_RMSD_NSUM; ++k) p.partial[(size_t)t * VMD_RMSD_NSUM + k] = ((s[k] + 0.0) + 0.0) + 0.0;
+    for (int k = 0; k < VMD_RMSD_NSUM; ++k) p.partial[(size_t)t * VMD_RMSD_NSUM + k] = vmd_set_small_sum(s[k]);
 }
 
 // ------------------------------------------------------------------------------------------------ misc
@@ -4498,7 +4472,7 @@ extern "C" int vmd_hip_sdf_align(void* stream, const float* xyz, size_t frame_st
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || K <= 0 || m <= 0) return 0;
     if ((tree_order != nullptr) != (tree_parent != nullptr) || (tree_order && !tree_pos)) return (int)hipErrorInvalidValue;
-    vmd_align_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, structs, mass, K, m, ref_pose, R32, c32, M64, tree_order, tree_parent, tree_pos};
+    vmd_align_params_t p{vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), structs, mass, K, m, ref_pose, R32, c32, M64, tree_order, tree_parent, tree_pos};
     hipLaunchKernelGGL(k_sdf_align, dim3((B * K + 63) / 64), dim3(64), 0, s, p);
     VMD_LAUNCH_CHECK();
     if (group) {
@@ -4629,7 +4603,7 @@ extern "C" int vmd_hip_distance(void* stream, const float* xyz, size_t frame_str
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || P <= 0 || per <= 0) return 0;
     if ((long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;     // B * P is an int below, and on grid.x
-    vmd_dist_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, a, mass_a, aoff, b, mass_b, boff, P, per, out};
+    vmd_dist_params_t p{vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), a, mass_a, aoff, b, mass_b, boff, P, per, out};
     switch (kind) {
     case 0: hipLaunchKernelGGL(k_distance_com, dim3((B * P + 63) / 64), dim3(64), 0, s, p); break;
     case 1: hipLaunchKernelGGL((k_distance_minmax<false>), dim3(B * P), dim3(256), 0, s, p); break;
@@ -4651,7 +4625,7 @@ extern "C" int vmd_hip_geometry(void* stream, const float* xyz, size_t frame_str
     if (B <= 0 || P <= 0) return 0;
     if ((nargs != 3 && nargs != 4) || !sets || !masses || !offsets || (long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     vmd_geom_params_t p{};
-    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
+    p.f = vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B); p.P = P;
     for (int k = 0; k < nargs; ++k) {
         if (!sets[k] || !masses[k] || !offsets[k]) return (int)hipErrorInvalidValue;
         p.set[k] = sets[k]; p.mass[k] = masses[k]; p.off[k] = offsets[k];
@@ -4669,7 +4643,7 @@ extern "C" int vmd_hip_backbone_angles(void* stream, const float* xyz, size_t fr
                                        const uint8_t* link, float* out) {
     if (B <= 0 || nseg <= 0) return 0;
     if (!xyz || !boxes || !n || !ca || !c || !link || !out || (long long)B * nseg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    vmd_bb_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, B, n, ca, c, link, nseg, out};
+    vmd_bb_params_t p{vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), n, ca, c, link, nseg, out};
     hipLaunchKernelGGL(k_backbone_angles, dim3((unsigned)(((long long)B * nseg + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
@@ -4699,8 +4673,8 @@ static int vmd_ss_params(vmd_ss_params_t* p, const float* xyz, size_t frame_stri
     if ((long long)B * nseg * W > 0x7fffffffLL || (long long)B * W * W > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     const size_t rows = (size_t)B * (size_t)nseg * (size_t)W;
     unsigned long long* s = (unsigned long long*)scratch;
-    *p = vmd_ss_params_t{xyz, frame_stride, row_stride, boxes, pbc_flags, B, n, ca, c, o, rng, pro, (const unsigned long long*)nbmask, nseg, (int)W,
-                         s, s + rows, s + 2 * rows, s + 3 * rows, nullptr, nullptr};
+    *p = vmd_ss_params_t{vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), n, ca, c, o, rng, pro, (const unsigned long long*)nbmask,
+                         nseg, (int)W, s, s + rows, s + 2 * rows, s + 3 * rows, nullptr, nullptr};
     return 0;
 }
 
@@ -4739,9 +4713,12 @@ extern "C" int vmd_hip_ss_assign(void* stream, const float* xyz, size_t frame_st
     return 0;
 }
 
+// the grid of a _small kernel: one wave per (frame, context)
+static dim3 vmd_set_small_grid(long long BP) { return dim3((unsigned)((BP + VMD_SET_WAVES - 1) / VMD_SET_WAVES)); }
+
 extern "C" size_t vmd_hip_shape_partial_doubles(int B, int P, int max_set) {
-    if (B <= 0 || P <= 0 || max_set <= VMD_SHAPE_WAVE_SET) return 0;
-    return (size_t)B * (size_t)P * (size_t)((max_set + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK) * 10;
+    if (B <= 0 || P <= 0 || max_set <= VMD_SET_WAVE_SET) return 0;
+    return (size_t)B * (size_t)P * (size_t)vmd_set_chunks(max_set) * 10;
 }
 
 extern "C" int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
@@ -4751,18 +4728,17 @@ extern "C" int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride
     if (B <= 0 || P <= 0) return 0;
     if (!set || !mass || !offsets || !lin || !plan || !iso || max_set <= 0 || (long long)B * P > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     vmd_shape_params_t p{};
-    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
+    p.f = vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B); p.P = P;
     p.set = set; p.mass = mass; p.off = offsets; p.lin = lin; p.plan = plan; p.iso = iso;
-    if (max_set <= VMD_SHAPE_WAVE_SET) {
-        const int per = VMD_SHAPE_BLOCK / 64;
-        hipLaunchKernelGGL(k_shape_small, dim3((unsigned)(((long long)B * P + per - 1) / per)), dim3(VMD_SHAPE_BLOCK), 0, (hipStream_t)stream, p);
+    if (max_set <= VMD_SET_WAVE_SET) {
+        hipLaunchKernelGGL(k_shape_small, vmd_set_small_grid((long long)B * P), dim3(VMD_SET_BLOCK), 0, (hipStream_t)stream, p);
         VMD_LAUNCH_CHECK();
         return 0;
     }
-    p.nchunk = (max_set + VMD_SHAPE_CHUNK - 1) / VMD_SHAPE_CHUNK;
+    p.nchunk = vmd_set_chunks(max_set);
     p.partial = partial;
     if (!partial || (long long)B * P * p.nchunk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_shape_moments, dim3((unsigned)((long long)B * P * p.nchunk)), dim3(VMD_SHAPE_BLOCK), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_shape_moments, dim3((unsigned)((long long)B * P * p.nchunk)), dim3(VMD_SET_BLOCK), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_shape_finish, dim3((unsigned)(((long long)B * P + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
@@ -4771,38 +4747,36 @@ extern "C" int vmd_hip_shape(void* stream, const float* xyz, size_t frame_stride
 
 extern "C" size_t vmd_hip_rmsd_workspace_bytes(int B, int P, int max_set) {
     if (B <= 0 || P <= 0 || max_set <= 0) return 0;
-    if (max_set <= VMD_RMSD_WAVE_SET) return (size_t)B * (size_t)P * VMD_RMSD_NSUM * sizeof(double);      // one wave per set: the sums only
-    const size_t blocks = (size_t)B * (size_t)P * (size_t)((max_set + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK);
+    if (max_set <= VMD_SET_WAVE_SET) return (size_t)B * (size_t)P * VMD_RMSD_NSUM * sizeof(double);      // one wave per set: the sums only
+    const size_t blocks = (size_t)B * (size_t)P * (size_t)vmd_set_chunks(max_set);
     return blocks * (VMD_RMSD_NSUM * sizeof(double) + 4 * sizeof(int32_t));
 }
 
-// both passes: pose = true runs the kernels' POSE forms over one frame
-static int vmd_rmsd_launch(bool pose_pass, hipStream_t stream, vmd_rmsd_params_t p, int max_set, void* workspace) {
-    const long long BP = (long long)p.B * p.P;
-    p.nchunk = (max_set + VMD_RMSD_CHUNK - 1) / VMD_RMSD_CHUNK;
+// both passes: POSE runs the kernels' POSE forms over one frame (B = 1, frame_stride 0, no zero row, no values)
+template <bool POSE>
+static int vmd_rmsd_launch(void* stream, vmd_frames_t f, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                           const double* pose, const double* consts, int zero_row, void* workspace, float* out) {
+    hipStream_t s = (hipStream_t)stream;
+    const long long BP = (long long)f.B * P;
+    vmd_rmsd_params_t p{};
+    p.f = f; p.P = P; p.set = set; p.mass = mass; p.off = offsets;
+    p.pose = const_cast<double*>(pose); p.cst = const_cast<double*>(consts);      // written by the pose pass only
+    p.zero_row = zero_row; p.out = out;
+    p.nchunk = vmd_set_chunks(max_set);
     if (!workspace || BP * p.nchunk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     p.partial = (double*)workspace;
-    const dim3 rows((unsigned)((BP + 63) / 64));
-    if (max_set <= VMD_RMSD_WAVE_SET) {
-        const int per = VMD_RMSD_BLOCK / 64;
-        const dim3 grid((unsigned)((BP + per - 1) / per));
-        if (pose_pass) hipLaunchKernelGGL(k_rmsd_small<true>, grid, dim3(VMD_RMSD_BLOCK), 0, stream, p);
-        else hipLaunchKernelGGL(k_rmsd_small<false>, grid, dim3(VMD_RMSD_BLOCK), 0, stream, p);
+    if (max_set <= VMD_SET_WAVE_SET) {
+        hipLaunchKernelGGL(k_rmsd_small<POSE>, vmd_set_small_grid(BP), dim3(VMD_SET_BLOCK), 0, s, p);
         VMD_LAUNCH_CHECK();
-        if (pose_pass) hipLaunchKernelGGL(k_rmsd_finish<true>, rows, dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(k_rmsd_finish<false>, rows, dim3(64), 0, stream, p);
+    } else {
+        p.shift = (int32_t*)((char*)workspace + (size_t)(BP * p.nchunk) * VMD_RMSD_NSUM * sizeof(double));
+        const dim3 blocks((unsigned)(BP * p.nchunk));
+        hipLaunchKernelGGL(k_rmsd_shift, blocks, dim3(VMD_SET_BLOCK), 0, s, p);
         VMD_LAUNCH_CHECK();
-        return 0;
+        hipLaunchKernelGGL(k_rmsd_moments<POSE>, blocks, dim3(VMD_SET_BLOCK), 0, s, p);
+        VMD_LAUNCH_CHECK();
     }
-    p.shift = (int32_t*)((char*)workspace + (size_t)(BP * p.nchunk) * VMD_RMSD_NSUM * sizeof(double));
-    const dim3 blocks((unsigned)(BP * p.nchunk));
-    hipLaunchKernelGGL(k_rmsd_shift, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
-    VMD_LAUNCH_CHECK();
-    if (pose_pass) hipLaunchKernelGGL(k_rmsd_moments<true>, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL(k_rmsd_moments<false>, blocks, dim3(VMD_RMSD_BLOCK), 0, stream, p);
-    VMD_LAUNCH_CHECK();
-    if (pose_pass) hipLaunchKernelGGL(k_rmsd_finish<true>, rows, dim3(64), 0, stream, p);
-    else hipLaunchKernelGGL(k_rmsd_finish<false>, rows, dim3(64), 0, stream, p);
+    hipLaunchKernelGGL(k_rmsd_finish<POSE>, dim3((unsigned)((BP + 63) / 64)), dim3(64), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }
@@ -4812,10 +4786,8 @@ extern "C" int vmd_hip_rmsd_pose(void* stream, const float* xyz, size_t row_stri
                                  void* workspace, double* pose, double* consts) {
     if (P <= 0) return 0;
     if (!xyz || !set || !mass || !offsets || !pose || !consts || max_set <= 0) return (int)hipErrorInvalidValue;
-    vmd_rmsd_params_t p{};
-    p.xyz = xyz; p.frame_stride = 0; p.row_stride = row_stride; p.boxes = box; p.pbc = pbc_flags; p.B = 1; p.P = P;
-    p.set = set; p.mass = mass; p.off = offsets; p.pose = pose; p.cst = consts; p.zero_row = -1;
-    return vmd_rmsd_launch(true, (hipStream_t)stream, p, max_set, workspace);
+    return vmd_rmsd_launch<true>(stream, vmd_frames(xyz, 0, row_stride, box, pbc_flags, 1), P, set, mass, offsets, max_set, pose, consts, -1,
+                                 workspace, nullptr);
 }
 
 extern "C" int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
@@ -4825,11 +4797,8 @@ extern "C" int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride,
     if (B <= 0 || P <= 0) return 0;
     if (!xyz || !set || !mass || !offsets || !pose || !consts || !out || max_set <= 0 || (long long)B * P > 0x7fffffffLL)
         return (int)hipErrorInvalidValue;
-    vmd_rmsd_params_t p{};
-    p.xyz = xyz; p.frame_stride = frame_stride; p.row_stride = row_stride; p.boxes = boxes; p.pbc = pbc_flags; p.B = B; p.P = P;
-    p.set = set; p.mass = mass; p.off = offsets; p.pose = const_cast<double*>(pose); p.cst = const_cast<double*>(consts);
-    p.zero_row = zero_row; p.out = out;
-    return vmd_rmsd_launch(false, (hipStream_t)stream, p, max_set, workspace);
+    return vmd_rmsd_launch<false>(stream, vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), P, set, mass, offsets, max_set, pose,
+                                  consts, zero_row, workspace, out);
 }
 
 extern "C" int vmd_hip_bbox(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, int B, int natoms, float* out) {
