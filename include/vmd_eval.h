@@ -237,6 +237,18 @@ bool vmd_ir_add_shape_weights_population(vmd_script_ir_t* ir, const char* const 
  * and a name that is already defined are errors (vmd_last_error). */
 bool vmd_ir_add_rmsd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n);
 bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets);
+/* rmsf (an entry point, no script syntax): the per-atom residual of rmsd's fit - d_a = R (e_a - ebar) - (u_a - ubar), the set
+ * made whole, weighted, fitted to its frame-0 pose and degenerate exactly as by rmsd - accumulated over all evaluated frames.  Arguments
+ * and errors are vmd_ir_add_rmsd[_population]'s.  One MAP property (VMD_PROPERTY_FLAG_MAP) of u64 accumulators, dim = {ntot + 1, 4}, ntot =
+ * the sum of the set sizes: row j < ntot belongs to entry j of idx (the contexts back to back); words 0..2 are the two's-complement i64
+ * sums of llrint(d 2^24) per axis, word 3 the sum of llrint(min(|d|^2, 2^20) 2^24); row ntot word 0 is the number of frames accumulated.
+ * Integer sums: the record is the same bit for bit however calls, batches and ranks arrive.  |d| <= 1024 A over 2^20 frames cannot
+ * overflow; a larger |d|^2 saturates word 3's term, silently.  Trajectory frame 0 counts as a frame and adds nothing; a frame evaluated
+ * twice without vmd_eval_clear_data is counted twice, as by a ramachandran map.  `counts` are the accumulators (vmd_eval_refresh_counts);
+ * `values` holds the same words as floats and is of no use for words 0..2.  An rmsd property defined earlier in the same ir over the same
+ * sets shares its sums with this one. */
+bool vmd_ir_add_rmsf(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n);
+bool vmd_ir_add_rmsf_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets);
 /* `name = count(<T> and within(rmin:rmax, <R>));`: the population of a shell per frame - how many atoms of the target set have
  * SOME atom of the reference set (itself included) at rmin <= d < rmax, d the pair distance rdf() bins (positions wrapped, SPEC S3 image).
  * The scalar form within(r, R) is rmin = 0.  One temporal property, values[frame], dim = {num_frames, 1}, no unit.
@@ -524,6 +536,12 @@ size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name, int which,
  * the device table is refreshed from the host rows first, so every rank of a merged evaluation answers for the whole trajectory. */
 bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, float* values,
                            uint64_t sums[4]);
+
+/* An rmsf property read from its record as it stands - partially evaluated or merged alike.  With F = the frames
+ * accumulated: m = sum_q / (2^24 F) per axis, msf = sum_q2 / (2^24 F) - |m|^2 clamped at 0, rmsf = sqrt(msf): the fluctuation about the
+ * mean aligned position, in Angstrom.  rmsf: double[ntot], mean_dev: double[ntot][3], frames: the count; each may be NULL.  F == 0
+ * answers zeros.  false + vmd_last_error: an unknown property, a property that is not an rmsf. */
+bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double* rmsf, double* mean_dev, uint64_t* frames);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

@@ -17,6 +17,7 @@
  *   vmd_hip_geometry  <- angle / dihedral (DESIGN S6b)
  *   vmd_hip_shape     <- shape_weights
  *   vmd_hip_rmsd      <- rmsd
+ *   vmd_hip_rmsf_*    <- rmsf
  *   vmd_hip_within_*  <- count(sel and within(r, sel))
  *   vmd_hip_within_*_flags, vmd_hip_shell_compact, vmd_hip_rdf_brute_masked  <- rdf() over within() shells
  *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
@@ -196,6 +197,24 @@ int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride, size_t row
                  const float* boxes, uint32_t pbc_flags, int B, int P,
                  const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
                  const double* pose, const double* consts, int zero_row, void* workspace, float* out);
+
+/* K5e: rmsf, DESIGN 1.13: the per-atom residual of K5d's fit, accumulated over frames in fixed point.  Sets, pose, consts, max_set and
+ * workspace as for vmd_hip_rmsd.  vmd_hip_rmsf_fit runs the sums of the batch into `workspace` (have_sums != 0: a vmd_hip_rmsd call over
+ * the same sets and batch has left them there) and writes R, ebar and ubar of every (frame, context) to rot, device memory of
+ * vmd_hip_rmsf_rot_doubles(B, P) doubles.  vmd_hip_rmsf_accumulate adds frames [b0, b0 + nb) of the batch to acc, u64[offsets[P] + 1][4]:
+ * row j = entry j of set, words 0..2 the two's-complement sums of llrint(d 2^24) per axis, word 3 the sum of llrint(min(|d|^2, 2^20) 2^24);
+ * the last row's word 0 gains nb.  zero_row: the row of the batch that is trajectory frame 0 (counted, adds nothing), or -1.  groups: the
+ * frame groups of the launch, <= 0 for vmd_hip_rmsf_groups' own choice (which is also how a given number is clamped); every choice gives
+ * the same record. */
+size_t vmd_hip_rmsf_rot_doubles(int B, int P);
+int vmd_hip_rmsf_groups(int nb, int P, int max_set, int want);
+int vmd_hip_rmsf_fit(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                     int B, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set, const double* pose,
+                     const double* consts, void* workspace, int have_sums, double* rot);
+int vmd_hip_rmsf_accumulate(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                            uint32_t pbc_flags, int B, int P, const int32_t* set, const float* mass, const int32_t* offsets,
+                            int max_set, const double* pose, const double* consts, int zero_row, void* workspace,
+                            const double* rot, int b0, int nb, int groups, uint64_t* acc);
 
 /* K6: count(T and within(rmin:rmax, R)), DESIGN 1.6: count_out u32[B] (zeroed by the call) = the atoms t of the target set for which SOME
  * atom a of the reference set (a == t included) lies at rmin <= d(t, a) < rmax (closed != 0: <= rmax); positions wrapped (SPEC S2 / S3t),

@@ -179,6 +179,9 @@ SIGNATURES = [
     ("vmd_ir_add_shape_weights_population", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.c_size_t, c_int32_p, c_int32_p]),
     ("vmd_ir_add_rmsd", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
     ("vmd_ir_add_rmsd_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
+    ("vmd_ir_add_rmsf", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
+    ("vmd_ir_add_rmsf_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
+    ("vmd_eval_rmsf", C.c_bool, [_vp, C.c_char_p, c_double_p, c_double_p, c_uint64_p]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
@@ -377,6 +380,12 @@ SIGNATURES = [
     ("vmd_hip_rmsd_pose", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("vmd_hip_rmsd", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                _vp, _vp, C.c_int, _vp, _vp]),
+    ("vmd_hip_rmsf_rot_doubles", C.c_size_t, [C.c_int, C.c_int]),
+    ("vmd_hip_rmsf_groups", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("vmd_hip_rmsf_fit", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
+                                   _vp, _vp, _vp, C.c_int, _vp]),
+    ("vmd_hip_rmsf_accumulate", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
+                                          _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

@@ -355,6 +355,20 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: break;
         case Form::SHAPE: st->shape_max_set = largest_set(); break;
         case Form::RMSD: st->rmsd_max_set = largest_set(); break;
+        case Form::RMSF: {
+            // four u64 words per entry of the set and the row of the frame count; the float view is the words as numbers, as a
+            // map's.  An rmsd property in front of it over the same sets lends it pose, sums and chunk shifts
+            st->rmsd_max_set = largest_set();
+            st->dist_P = p.aoff.size() - 1;
+            st->rmsf_groups = std::max(0, g_opt.rmsf_frame_groups.load());
+            pinned_views((p.a.size() + 1) * 4);
+            st->data.dim[0] = (int32_t)(p.a.size() + 1); st->data.dim[1] = 4; st->data.dim[2] = st->data.dim[3] = 0;
+            for (size_t j = 0; j < e->props.size(); ++j) {
+                const Property& o = e->props[j]->prop;
+                if (o.form == Form::RMSD && o.a == p.a && o.aoff == p.aoff) { st->rmsf_of = (int)j; break; }
+            }
+            break;
+        }
         }
         if (p.temporal()) {     // [num_frames][contexts x values per context]
             st->dim1 = st->dist_P * st->dist_per;
@@ -848,6 +862,37 @@ extern "C" bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name,
     return true;
 }
 
+// ---- rmsf read from its record: m = sum_q / (2^24 F) per axis, msf = sum_q2 / (2^24 F) - |m|^2 clamped at 0, rmsf = sqrt(msf).
+// Whatever the record holds - a partial evaluation, a merged one - is what is read; under the eval's mutex, touching nothing it keeps.
+extern "C" bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double* rmsf, double* mean_dev, uint64_t* frames) {
+    if (!eval || !name) return vmd_fail("vmd_eval_rmsf: NULL argument");
+    PropState* p = find_prop(eval, name);
+    if (!p) return vmd_fail("unknown property '%s'", name);
+    if (p->prop.form != Form::RMSF) return vmd_fail("'%s' is not an rmsf property", name);
+    const size_t ntot = p->prop.a.size();
+    std::vector<uint64_t> acc(p->ncounts);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        HIP_OK(hipSetDevice(eval->device));
+        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
+        HIP_OK(hipStreamSynchronize(eval->stream));
+    }
+    const uint64_t F = acc[4 * ntot];
+    if (frames) *frames = F;
+    const double scale = 16777216.0 * (double)F;
+    for (size_t j = 0; j < ntot; ++j) {
+        double m[3] = {0.0, 0.0, 0.0}, r = 0.0;
+        if (F) {
+            for (int k = 0; k < 3; ++k) m[k] = (double)(int64_t)acc[4 * j + k] / scale;
+            const double msf = (double)acc[4 * j + 3] / scale - ((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+            r = std::sqrt(msf < 0.0 ? 0.0 : msf);
+        }
+        if (rmsf) rmsf[j] = r;
+        if (mean_dev) for (int k = 0; k < 3; ++k) mean_dev[3 * j + k] = m[k];
+    }
+    return true;
+}
+
 // ---- the hot call -----------------------------------------------------------------------------------------------
 bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_atoms) {
     for (auto& s : e->sels) {
@@ -860,7 +905,7 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
             out.resize(idx.size());
             for (size_t i = 0; i < idx.size(); ++i)
                 out[i] = (sys && sys->mass && (size_t)idx[i] < sys->atom_count) ? sys->mass[idx[i]] : 1.0f;
-            if (d.temporal() && e->spec.dist_geometric_com) std::fill(out.begin(), out.end(), 1.0f);   // D-DIST-COM flipped
+            if ((d.temporal() || d.form == Form::RMSF) && e->spec.dist_geometric_com) std::fill(out.begin(), out.end(), 1.0f);   // D-DIST-COM flipped
         };
         std::vector<float> tmp;
         switch (d.form) {
@@ -975,7 +1020,7 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
                 !p->d_c.upload(d.c.data(), d.c.size(), e->stream) || !p->d_rama_class.upload(d.rama_class.data(), d.rama_class.size(), e->stream)
                 || !p->d_rama_link.upload(d.rama_link.data(), d.rama_link.size(), e->stream)) return false;
             break;
-        case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::WITHIN: {
+        case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::RMSF: case Form::WITHIN: {
             // the form's argument sets (two for distance, three and four for angle / dihedral, DESIGN S6b), their offsets and masses
             const std::vector<int32_t>* sets[4] = {&d.a, &d.b, &d.c, &d.d};
             const std::vector<int32_t>* offs[4] = {&d.aoff, &d.boff, &d.coff, &d.doff};

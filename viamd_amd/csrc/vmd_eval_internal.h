@@ -184,6 +184,7 @@ struct Options {
     // secondary structure: bytes of bit matrices a batch may hold (frames x nseg^2 / 2); a larger batch runs in sub-batches
     // of frames, never below one frame.  256 MiB: the 1 000 frames x 500 segments of DESIGN 1.10's system take 128 MB in one go
     std::atomic<int> ss_scratch_bytes{256 << 20};
+    std::atomic<int> rmsf_frame_groups{0};      // frame groups of an accumulate launch, 0 = chosen per launch (read at eval creation)
 };
 
 extern Options g_opt;
@@ -388,6 +389,9 @@ enum class Form : int {
     // or -1; its rows are one code per segment.  The populations behind it (K = the segments) are nine counts per frame, written by the
     // table's launch
     SS_CLASS, SS_POP,
+    // rmsf: the set of rmsd (a / aoff).  A MAP-class record of u64 accumulators, [ntot + 1][4]: per entry of a the fixed-point
+    // sums of the fit's residual over the evaluated frames, the frame count in the last row
+    RMSF,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -417,8 +421,9 @@ constexpr FormFacts kFormFacts[] = {
     /* RAMA_MAP    */ {ResultClass::MAP,          0, "ramachandran",  {"rad", ""},      nullptr, false, 0},
     /* SS_CLASS    */ {ResultClass::TEMPORAL,     3, "secondary_structure", {"", ""},   nullptr, false, 11},    // a code, a count
     /* SS_POP      */ {ResultClass::TEMPORAL,     0, "secondary_structure", {"", ""},   nullptr, false, 12},
+    /* RMSF        */ {ResultClass::MAP,          1, "rmsf",          {"", "\xC3\x85"}, nullptr, false, 13},    // Angstrom in 2^-24 quanta
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::SS_POP + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::RMSF + 1, "one row of kFormFacts per Form");
 static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES, "the kernels' limits are the interface's");
 
 struct Property {
@@ -608,6 +613,11 @@ struct PropState {
     const void* rmsd_pose_inst = nullptr;
     const void* rmsd_pose_fn = nullptr;
     bool rmsd_pose_ready = false;
+    // rmsf keeps its pose in the fields above; rmsf_of: the rmsd property in front of it over the same sets whose pose, sums
+    // and chunk shifts it reads instead (-1: its own); the rotations of the batch; the frame groups asked for (option rmsf_frame_groups)
+    int rmsf_of = -1;
+    DevBuf<double> d_rmsf_rot;
+    int rmsf_groups = 0;
     // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
@@ -1109,6 +1119,7 @@ struct RangeRun {
     bool launch_sdf(BatchCtx& c, PropState* p, const uint8_t* mask, size_t mask_stride);
     bool launch_shape(BatchCtx& c, size_t pi);
     bool launch_rmsd(BatchCtx& c, PropState* p);
+    bool launch_rmsf(BatchCtx& c, size_t pi);
     bool launch_geometry(BatchCtx& c, PropState* p);
     bool launch_rama(BatchCtx& c, size_t pi);
     bool launch_ss(BatchCtx& c, size_t pi);

@@ -38,6 +38,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         case Form::ANGLE: case Form::DIHEDRAL: w += sum_sizes({&p.a, &p.b, &p.c, &p.d}); break;     // each context: the sum of its set sizes
         case Form::SHAPE: if (p.shape_comp == 0) w += p.a.size(); break;     // one pass over every context's set per statement
         case Form::RMSD: w += p.a.size(); break;                             // the atoms of every context's set
+        case Form::RMSF: w += 2 * (uint64_t)p.a.size(); break;               // twice, the sums and the second pass
         case Form::WITHIN: w += sum_sizes({&p.a, &p.b}); break;              // |T| + |R|: a neighbour query, not all pairs
         case Form::WITHIN_EXPR: w += p.a.size() + expr_refs(p); break;       // |T| + sum |R_i|
         case Form::RAMA_TABLE: w += 3 * (uint64_t)p.a.size(); break;         // N, CA, C of every segment
@@ -270,6 +271,15 @@ extern "C" bool vmd_ir_add_rmsd_population(vmd_script_ir_t* ir, const char* name
     return ir_add_sets(ir, Form::RMSD, &name, P, &idx, &offsets);
 }
 
+// rmsf: rmsd's sets and rmsd's checks; one MAP-class record of per-atom accumulators
+extern "C" bool vmd_ir_add_rmsf(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n) {
+    return ir_add_sets_single(ir, Form::RMSF, &name, &idx, &n);
+}
+
+extern "C" bool vmd_ir_add_rmsf_population(vmd_script_ir_t* ir, const char* name, size_t P, const int32_t* idx, const int32_t* offsets) {
+    return ir_add_sets(ir, Form::RMSF, &name, P, &idx, &offsets);
+}
+
 // `name = rdf(T and within(a:b, R), target, {rmin, rmax});`: vmd_ir_add_rdf with either side a shell
 extern "C" bool vmd_ir_add_rdf_shell(vmd_script_ir_t* ir, const char* name, const int32_t* ref, size_t nref, const vmd_shell_t* ref_shell,
                                      const int32_t* target, size_t ntarget, const vmd_shell_t* target_shell, float rmin, float rmax) {
@@ -453,7 +463,7 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
                 if (p.ss_o[sg] >= 0) s.put(p.ss_o[sg]);
             }
             return s.n;
-        case Form::SHAPE: case Form::RMSD:      // the set of the context(s)
+        case Form::SHAPE: case Form::RMSD: case Form::RMSF:      // the set of the context(s)
             if (!contexts(p.aoff.size() - 1, c0, c1)) return 0;
             s.put(p.a, p.aoff[c0], p.aoff[c1]);
             return s.n;
@@ -493,7 +503,7 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::SHAPE: h = fnv1a(h, &p.shape_comp, sizeof(int)); break;
         case Form::RAMA_TABLE: h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); break;     // 
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
-        case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: break;
+        case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: break;
         case Form::SS_CLASS:                                            // 
             h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); h = fnv1a(h, p.ss_o.data(), p.ss_o.size() * sizeof(int32_t));
             break;

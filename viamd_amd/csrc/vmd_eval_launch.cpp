@@ -490,6 +490,31 @@ bool RangeRun::launch_rmsd(BatchCtx& c, PropState* p) {
     return true;
 }
 
+// rmsf: the sums of the batch - left in its workspace by the rmsd property in front over the same sets, if there is one -,
+// the rotations, then the second pass per sub, so that a frame block's frames land in its own partial.  No cell grid, no overflow flag:
+// a batch repeated for an overflow does not come here again.  A frame evaluated twice is counted twice, as a map counts it.
+bool RangeRun::launch_rmsf(BatchCtx& c, size_t pi) {
+    PropState* p = e->props[pi].get();
+    PropState* s = p->rmsf_of >= 0 && (size_t)p->rmsf_of < pi ? e->props[(size_t)p->rmsf_of].get() : p;     // whose pose, sums and shifts
+    if (s != p && (!s->rmsd_pose_ready || s->prop.form != Form::RMSD))
+        return vmd_fail("rmsf property '%s' has lost the rmsd property it reads", p->prop.name.c_str());
+    const int B = (int)c.nb, P = (int)p->dist_P;
+    if (s == p && !p->d_rmsd_ws.ensure((vmd_hip_rmsd_workspace_bytes(B, P, p->rmsd_max_set) + 7) / 8)) return false;
+    if (!p->d_rmsf_rot.ensure(vmd_hip_rmsf_rot_doubles(B, P))) return false;
+    const Stage& st = *c.src;
+    e->prof.begin("rmsf_rotation", e->stream);
+    KRN_OK(vmd_hip_rmsf_fit(e->stream, st.base, st.frame_stride, st.row_stride, st.d_boxes.p, c.pbc, B, P, p->d_a.p, p->d_ma.p, p->d_aoff.p,
+            p->rmsd_max_set, s->d_rmsd_pose.p, s->d_rmsd_const.p, s->d_rmsd_ws.p, s != p ? 1 : 0, p->d_rmsf_rot.p));
+    e->prof.end(e->stream);
+    e->prof.begin("rmsf", e->stream);
+    for (auto& su : c.subs)
+        KRN_OK(vmd_hip_rmsf_accumulate(e->stream, st.base, st.frame_stride, st.row_stride, st.d_boxes.p, c.pbc, B, P, p->d_a.p, p->d_ma.p,
+                p->d_aoff.p, p->rmsd_max_set, s->d_rmsd_pose.p, s->d_rmsd_const.p, c.f0 == 0 ? 0 : -1, s->d_rmsd_ws.p, p->d_rmsf_rot.p,
+                (int)su.off, (int)su.nb, p->rmsf_groups, acc_of(p, su)));
+    e->prof.end(e->stream);
+    return true;
+}
+
 // angle / dihedral (DESIGN S6b): the same [nb][P] block, the same copy
 bool RangeRun::launch_geometry(BatchCtx& c, PropState* p) {
     const int32_t* sets[4] = {p->d_a.p, p->d_b.p, p->d_c.p, p->d_d.p};
@@ -589,6 +614,7 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     case Form::SS_CLASS: return launch_ss(c, pi);
     case Form::SHAPE: return launch_shape(c, pi);
     case Form::RMSD: return launch_rmsd(c, p);
+    case Form::RMSF: return launch_rmsf(c, pi);
     case Form::ANGLE: case Form::DIHEDRAL: return launch_geometry(c, p);
     case Form::DISTANCE: return launch_distance(c, p);
     }

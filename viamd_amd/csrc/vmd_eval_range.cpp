@@ -20,7 +20,7 @@ bool RangeRun::prepare_reference_poses() {
     // rmsd reference pose: every context's set at trajectory frame 0.  It belongs to (evaluator, trajectory): rebuilt when
     // this call's trajectory is not the one it was built for
     for (auto& p : e->props) {
-        if (p->prop.form != Form::RMSD) continue;
+        if (p->prop.form != Form::RMSD && !(p->prop.form == Form::RMSF && p->rmsf_of < 0)) continue;     // (rmsf, DESIGN 1.13: the same pose)
         const TrajId now = traj_id(traj);
         if (p->rmsd_pose_ready && p->rmsd_pose_inst == now.inst && p->rmsd_pose_fn == now.fn) continue;
         BatchSrc src;
@@ -269,7 +269,7 @@ bool RangeRun::complete_batch(BatchCtx& c, BatchCtx* later) {
 static const float* batch_rows(const PropState* p, size_t f0) {
     switch (p->prop.form) {
     // accumulators, no rows; a within count's rows are sent by launch_rdf, behind the overflow flag
-    case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::WITHIN: case Form::WITHIN_EXPR: return nullptr;
+    case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::RMSF: case Form::WITHIN: case Form::WITHIN_EXPR: return nullptr;
     case Form::RAMA_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
     case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::SS_CLASS: case Form::SS_POP:
         return p->d_out.p;

@@ -15,6 +15,7 @@
 //   angle() / dihedral()         -> k_geom<3> / k_geom<4>
 //   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
 //   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
+//   rmsf           -> rmsd's sums, k_rmsf_rotation, k_rmsf_accumulate (large sets) / k_rmsf_small
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -2459,13 +2460,15 @@ __device__ __forceinline__ void vmd_horn_matrix(const double S[3][3], double N[4
     for (int i = 0; i < 4; ++i) for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
 }
 
-__device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
+// the rotation of the eigenvector of N for its largest eigenvalue.  Inline form: a kernel that keeps S and R in registers (k_rmsf_rotation)
+// calls this one; the column is picked by selects, not by an index into V
+__device__ __forceinline__ void vmd_horn_rotation_inline(const double S[3][3], double R[9]) {
     double N[4][4], V[4][4];
     vmd_horn_matrix(S, N);
-    vmd_jacobi4(N, V);
-    int best = 0;
-    for (int i = 1; i < 4; ++i) if (N[i][i] > N[best][best]) best = i;
-    double qw = V[0][best], qx = V[1][best], qy = V[2][best], qz = V[3][best];
+    vmd_jacobi4_t<true>(N, V);
+    double lam = N[0][0], qw = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) if (N[i][i] > lam) { lam = N[i][i]; qw = V[0][i]; qx = V[1][i]; qy = V[2][i]; qz = V[3][i]; }
     const double nrm = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
     qw = qw / nrm; qx = qx / nrm; qy = qy / nrm; qz = qz / nrm;
     R[0] = 1.0 - 2.0 * (qy * qy + qz * qz);
@@ -2478,6 +2481,7 @@ __device__ void vmd_horn_rotation(const double S[3][3], double R[9]) {
     R[7] = 2.0 * (qy * qz + qw * qx);
     R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
 }
+__device__ void vmd_horn_rotation(const double S[3][3], double R[9]) { vmd_horn_rotation_inline(S, R); }
 
 // a centre of mass in fp64: the weighted sums in the order the atoms are handed over, one division per axis at the end
 struct vmd_com_t {
@@ -3790,14 +3794,45 @@ __device__ __forceinline__ void vmd_wave_scan_i32(int v, int lane, int& incl, in
     }
 }
 
+// the link shift of one atom scanned over its wave: incl = the shifts of the lanes up to and including this one, tot = the wave's.  A
+// molecule that is whole in the cell has no shift along most of its chain: a wave without any skips its three scans
+__device__ __forceinline__ void vmd_rmsd_wave_shift(const vmd_rmsd_atom_t& q, const vmd_set_frame_t& b, int lane, int incl[3], int tot[3]) {
+    int nx, ny, nz;
+    vmd_rmsd_link(q, b, nx, ny, nz);
+    if (__ballot((nx | ny | nz) != 0) == 0ull) { incl[0] = incl[1] = incl[2] = tot[0] = tot[1] = tot[2] = 0; return; }
+    vmd_wave_scan_i32(nx, lane, incl[0], tot[0]);
+    vmd_wave_scan_i32(ny, lane, incl[1], tot[1]);
+    vmd_wave_scan_i32(nz, lane, incl[2], tot[2]);
+}
+// one step's wave totals joined: k = the shift of this thread's atom (what ran in front of the step, the waves in front of its own, its
+// own scan); run advances by the whole step
+__device__ __forceinline__ void vmd_rmsd_join(const int (*tot)[3], int wave, const int incl[3], int run[3], int k[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) k[i] = run[i] + incl[i];
+#pragma unroll
+    for (int v = 0; v < VMD_SET_WAVES; ++v)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int t = tot[v][i];
+            if (v < wave) k[i] += t;
+            run[i] += t;
+        }
+}
+// e_a = (x_a - x_0) + cart(k_a)
+__device__ __forceinline__ void vmd_rmsd_offset(const vmd_set_atom_t& q, const vmd_set_frame_t& b, double x0, double y0, double z0,
+                                                int kx, int ky, int kz, double& ex, double& ey, double& ez) {
+    double cx, cy, cz;
+    vmd_rmsd_cart(b, kx, ky, kz, cx, cy, cz);
+    ex = ((double)q.x - x0) + cx; ey = ((double)q.y - y0) + cy; ez = ((double)q.z - z0) + cz;
+}
+
 // the sums of one atom: k = its accumulated shift, u = its pose offset (frame pass) / where its pose offset goes (pose pass, live atoms)
 template <bool POSE>
 __device__ __forceinline__ void vmd_rmsd_add(const vmd_set_atom_t& q, const vmd_set_frame_t& b, double x0, double y0, double z0,
                                              int kx, int ky, int kz, const double u[3], double* pose_out, double s[VMD_RMSD_NSUM]) {
     const double w = (double)q.w;
-    double cx, cy, cz;
-    vmd_rmsd_cart(b, kx, ky, kz, cx, cy, cz);
-    const double ex = ((double)q.x - x0) + cx, ey = ((double)q.y - y0) + cy, ez = ((double)q.z - z0) + cz;
+    double ex, ey, ez;
+    vmd_rmsd_offset(q, b, x0, y0, z0, kx, ky, kz, ex, ey, ez);
     const double wx = w * ex, wy = w * ey, wz = w * ez;
     s[0] = s[0] + wx; s[1] = s[1] + wy; s[2] = s[2] + wz;
     s[3] = s[3] + ((wx * ex + wy * ey) + wz * ez);
@@ -3811,6 +3846,11 @@ __device__ __forceinline__ void vmd_rmsd_add(const vmd_set_atom_t& q, const vmd_
     }
 }
 
+// S_ij = C_ij - (S1_i U1_j) / W of the finish, from the sums and the pose's constants
+__device__ __forceinline__ void vmd_rmsd_corr(const double s[VMD_RMSD_NSUM], const double* cst, double S[3][3]) {
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = s[4 + 3 * i + j] - (s[i] * cst[1 + j]) / cst[0];
+}
+
 // the value from the thirteen sums and the pose's constants: Horn's largest eigenvalue, no rotation matrix
 __device__ float vmd_rmsd_value(const double s[VMD_RMSD_NSUM], const double* cst, int n) {
     const double W = cst[0];
@@ -3819,7 +3859,7 @@ __device__ float vmd_rmsd_value(const double s[VMD_RMSD_NSUM], const double* cst
     const double Gp = s[3] - ((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]) / W;
     const double Gq = Gu - ((U1[0] * U1[0] + U1[1] * U1[1]) + U1[2] * U1[2]) / W;
     double S[3][3], N[4][4];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = s[4 + 3 * i + j] - (s[i] * U1[j]) / W;
+    vmd_rmsd_corr(s, cst, S);
     vmd_horn_matrix(S, N);
     vmd_jacobi4_t<false>(N, nullptr);                        // vmd_jacobi4's rotations; the eigenvectors are not needed
     double lam = N[0][0];
@@ -3827,6 +3867,12 @@ __device__ float vmd_rmsd_value(const double s[VMD_RMSD_NSUM], const double* cst
     double msd = ((Gp + Gq) - 2.0 * lam) / W;
     msd = msd < 0.0 ? 0.0 : msd;                            // a rigid copy rounds to -1e-13
     return (float)sqrt(msd);
+}
+
+// the shift that runs into chunk `chunk` of a (frame, context): the totals of the chunks in front of it
+__device__ __forceinline__ void vmd_rmsd_carry_in(const int32_t* sh, int chunk, int run[3]) {
+    run[0] = run[1] = run[2] = 0;
+    for (int ch = 0; ch < chunk; ++ch) { run[0] += sh[4 * ch + 0]; run[1] += sh[4 * ch + 1]; run[2] += sh[4 * ch + 2]; }
 }
 
 // one block per (frame, context, chunk): the chunk's total link shift, the link to the previous chunk's last atom included
@@ -3874,16 +3920,15 @@ __global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_moments(vmd_rmsd_params_
     const double x0 = (double)sf.fr.x[i0], y0 = (double)sf.fr.y[i0], z0 = (double)sf.fr.z[i0];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the shift of every atom in front of the current step
-    int rx = 0, ry = 0, rz = 0;
-    const int32_t* sh = p.shift + (size_t)w.bc * p.nchunk * 4;
-    for (int ch = 0; ch < w.chunk; ++ch) { rx += sh[4 * ch + 0]; ry += sh[4 * ch + 1]; rz += sh[4 * ch + 2]; }
+    int run[3];
+    vmd_rmsd_carry_in(p.shift + (size_t)w.bc * p.nchunk * 4, w.chunk, run);
     double s[VMD_RMSD_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // VMD_RMSD_GROUP atoms per step: their loads first, the link shifts and their wave scans, one barrier, then the sums in atom order
 #pragma unroll 1
     for (int g = 0; g < VMD_SET_STEPS; g += VMD_RMSD_GROUP) {
         vmd_rmsd_atom_t q[VMD_RMSD_GROUP];
         double u[VMD_RMSD_GROUP][3];
-        int ix[VMD_RMSD_GROUP], iy[VMD_RMSD_GROUP], iz[VMD_RMSD_GROUP];
+        int incl[VMD_RMSD_GROUP][3];
 #pragma unroll
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
             const int a = a0 + (g + k) * VMD_SET_BLOCK + tid;
@@ -3894,29 +3939,17 @@ __global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_moments(vmd_rmsd_params_
         }
 #pragma unroll
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
-            int nx, ny, nz, tx, ty, tz;
-            vmd_rmsd_link(q[k], sf, nx, ny, nz);
-            // a molecule that is whole in the cell has no shift along most of its chain: a wave without any skips its three scans
-            if (__ballot((nx | ny | nz) != 0) == 0ull) { ix[k] = iy[k] = iz[k] = tx = ty = tz = 0; }
-            else {
-                vmd_wave_scan_i32(nx, lane, ix[k], tx);
-                vmd_wave_scan_i32(ny, lane, iy[k], ty);
-                vmd_wave_scan_i32(nz, lane, iz[k], tz);
-            }
-            if (lane == 0) { s_tot[g + k][wave][0] = tx; s_tot[g + k][wave][1] = ty; s_tot[g + k][wave][2] = tz; }
+            int tot[3];
+            vmd_rmsd_wave_shift(q[k], sf, lane, incl[k], tot);
+            if (lane == 0) { s_tot[g + k][wave][0] = tot[0]; s_tot[g + k][wave][1] = tot[1]; s_tot[g + k][wave][2] = tot[2]; }
         }
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
-            int kx = rx + ix[k], ky = ry + iy[k], kz = rz + iz[k];
-#pragma unroll
-            for (int v = 0; v < VMD_SET_WAVES; ++v) {
-                const int tx = s_tot[g + k][v][0], ty = s_tot[g + k][v][1], tz = s_tot[g + k][v][2];
-                if (v < wave) { kx += tx; ky += ty; kz += tz; }
-                rx += tx; ry += ty; rz += tz;
-            }
+            int kk[3];
+            vmd_rmsd_join(s_tot[g + k], wave, incl[k], run, kk);
             const int a = a0 + (g + k) * VMD_SET_BLOCK + tid;
-            vmd_rmsd_add<POSE>(q[k].at, sf, x0, y0, z0, kx, ky, kz, u[k], (POSE && a < n) ? pose + 3 * (size_t)a : nullptr, s);
+            vmd_rmsd_add<POSE>(q[k].at, sf, x0, y0, z0, kk[0], kk[1], kk[2], u[k], (POSE && a < n) ? pose + 3 * (size_t)a : nullptr, s);
         }
     }
     vmd_set_wave_sum<VMD_RMSD_NSUM>(s);
@@ -3968,6 +4001,186 @@ __global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsd_small(vmd_rmsd_params_t 
     if (lane != 0) return;
 #pragma unroll
     for (int k = 0; k < VMD_RMSD_NSUM; ++k) p.partial[(size_t)t * VMD_RMSD_NSUM + k] = vmd_set_small_sum(s[k]);
+}
+
+// ------------------------------------------------------------------------------------------------ K5e: rmsf
+
+// The per-atom residual of rmsd's fit, d_a = R (e_a - ebar) - (u_a - ubar), accumulated over frames in fixed point: per atom the i64 sums
+// of q(d_x), q(d_y), q(d_z) and the u64 sum of q2(|d|^2), q(v) = q2(v) = llrint(v 2^24) (D-RMSF-FIXED) - integers, so the record does not
+// depend on the order in which frames, blocks, batches and ranks arrive.  The sums are rmsd's (k_rmsd_shift + k_rmsd_moments, or
+// k_rmsd_small); k_rmsf_rotation forms R and the centroids from them, k_rmsf_accumulate / k_rmsf_small make the second pass over the set.
+#define VMD_RMSF_NROT 15           // per (frame, context): R row-major (9), ebar (3), ubar (3)
+#define VMD_RMSF_FRAMES 64         // most frames of one frame group of k_rmsf_accumulate (its LDS row of running shifts)
+#define VMD_RMSF_ONE 16777216.0    // 2^24: one Angstrom (one square Angstrom) in quanta
+#define VMD_RMSF_D2_MAX 1048576.0  // 2^20 A^2: where q2 saturates
+
+struct vmd_rmsf_params_t {
+    vmd_rmsd_params_t r;    // the frames, the set, the pose and its constants, the sums and chunk shifts of the batch, zero_row
+    double* rot;            // [B][P][VMD_RMSF_NROT]
+    uint64_t* acc;          // [off[P] + 1][4]: the record; row off[P] word 0 counts the frames
+    int b0, nb;             // the frames of the batch this launch accumulates: [b0, b0 + nb)
+    int groups;             // frame groups: group g takes frames b0 + g per .. b0 + (g + 1) per, per = ceil(nb / groups)
+};
+
+// one thread per (frame, context): the chunk sums in chunk order, then the rotation vmd_horn_rotation forms of the S of rmsd's finish and
+// the two centroids.  D-RMSF-DEGENERATE sets get zeros (the second pass leaves them out by the same test).
+__global__ __launch_bounds__(64) void k_rmsf_rotation(vmd_rmsf_params_t q) {
+    const vmd_rmsd_params_t& p = q.r;
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= p.f.B * p.P) return;
+    const int c = t % p.P;
+    const int n = vmd_set_slice(p.off, c).n;
+    const double* cst = p.cst + (size_t)c * VMD_RMSD_NCONST;
+    double* o = q.rot + (size_t)t * VMD_RMSF_NROT;
+    const double W = cst[0];
+    if (n <= 1 || W == 0.0) {
+        for (int k = 0; k < VMD_RMSF_NROT; ++k) o[k] = 0.0;
+        return;
+    }
+    double s[VMD_RMSD_NSUM], S[3][3], R[9];
+    vmd_set_chunk_sum<VMD_RMSD_NSUM>(p.partial + (size_t)t * p.nchunk * VMD_RMSD_NSUM, n, s);
+    vmd_rmsd_corr(s, cst, S);
+    vmd_horn_rotation_inline(S, R);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = R[k];
+    for (int k = 0; k < 3; ++k) { o[9 + k] = s[k] / W; o[12 + k] = cst[1 + k] / W; }
+}
+
+// the four quantised terms of one atom in one frame added to its registers
+__device__ __forceinline__ void vmd_rmsf_add(const double* rot, double ex, double ey, double ez, const double u[3], long long a[4]) {
+    const double px = ex - rot[9], py = ey - rot[10], pz = ez - rot[11];
+    const double dx = ((rot[0] * px + rot[1] * py) + rot[2] * pz) - (u[0] - rot[12]);
+    const double dy = ((rot[3] * px + rot[4] * py) + rot[5] * pz) - (u[1] - rot[13]);
+    const double dz = ((rot[6] * px + rot[7] * py) + rot[8] * pz) - (u[2] - rot[14]);
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    a[0] += llrint(dx * VMD_RMSF_ONE); a[1] += llrint(dy * VMD_RMSF_ONE); a[2] += llrint(dz * VMD_RMSF_ONE);
+    a[3] += llrint((d2 < VMD_RMSF_D2_MAX ? d2 : VMD_RMSF_D2_MAX) * VMD_RMSF_ONE);
+}
+__device__ __forceinline__ void vmd_rmsf_commit(uint64_t* row, const long long a[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (a[j]) atomicAdd((unsigned long long*)row + j, (unsigned long long)a[j]);
+}
+// the frames of group g: [fb, fb + nf)
+__device__ __forceinline__ void vmd_rmsf_group(const vmd_rmsf_params_t& q, int g, int& fb, int& nf) {
+    const int per = (q.nb + q.groups - 1) / q.groups;
+    fb = q.b0 + g * per;
+    nf = q.b0 + q.nb - fb;
+    nf = nf < per ? nf : per;
+    nf = nf < 0 ? 0 : nf;
+}
+
+// One block per (context, chunk, frame group).  A thread owns VMD_RMSD_GROUP atoms at a time: for each step of the chunk it walks the
+// group's frames - per frame k_rmsd_moments' step (loads, vmd_rmsd_wave_shift, the waves joined through LDS, one barrier) gives e_a -,
+// keeps the step's 4 x i64 per atom in registers, and issues their atomics behind the last frame.  What has run in front of the step in
+// each frame stands in an LDS row, double-buffered by step like the wave totals by iteration: one barrier per (step, frame) is enough -
+// both are read only behind the iteration's barrier, and written again no earlier than behind the next one.
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsf_accumulate(vmd_rmsf_params_t q) {
+    __shared__ int s_tot[2][VMD_RMSD_GROUP][VMD_SET_WAVES][3];
+    __shared__ int s_run[2][VMD_RMSF_FRAMES][3];
+    const vmd_rmsd_params_t& p = q.r;
+    const int g = blockIdx.x % q.groups, cc = blockIdx.x / q.groups;
+    const int chunk = cc % p.nchunk, c = cc / p.nchunk;
+    const vmd_set_slice_t sl = vmd_set_slice(p.off, c);
+    const int n = sl.n, a0 = chunk * VMD_SET_CHUNK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int fb, nf;
+    vmd_rmsf_group(q, g, fb, nf);
+    if (cc == 0 && tid == 0 && nf > 0) atomicAdd((unsigned long long*)q.acc + 4 * (size_t)p.off[p.P], (unsigned long long)nf);
+    if (a0 >= n || nf == 0 || n <= 1 || p.cst[(size_t)c * VMD_RMSD_NCONST] == 0.0) return;     // the whole block (D-RMSF-DEGENERATE: d = 0)
+    const int32_t* set = p.set + sl.k0;
+    const float* mass = p.mass + sl.k0;
+    const double* pose = p.pose + (size_t)sl.k0 * 3;
+    const int i0 = set[0];
+    if (tid < nf) {
+        int run[3];
+        vmd_rmsd_carry_in(p.shift + ((size_t)(fb + tid) * p.P + c) * p.nchunk * 4, chunk, run);
+        s_run[0][tid][0] = run[0]; s_run[0][tid][1] = run[1]; s_run[0][tid][2] = run[2];
+    }
+    __syncthreads();
+    int it = 0;
+#pragma unroll 1
+    for (int st = 0; st < VMD_SET_STEPS; st += VMD_RMSD_GROUP) {
+        if (a0 + st * VMD_SET_BLOCK >= n) break;                 // (the whole block: no atom of this step or a later one)
+        const int par = (st / VMD_RMSD_GROUP) & 1;
+        long long acc[VMD_RMSD_GROUP][4];
+        double u[VMD_RMSD_GROUP][3];
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+            const int a = a0 + (st + k) * VMD_SET_BLOCK + tid, aa = a < n ? a : 0;
+            acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+            u[k][0] = pose[3 * aa + 0]; u[k][1] = pose[3 * aa + 1]; u[k][2] = pose[3 * aa + 2];
+        }
+#pragma unroll 1
+        for (int f = 0; f < nf; ++f) {
+            const int b = fb + f;
+            if (b == p.zero_row) continue;                        // trajectory frame 0: d = 0 by construction, nothing to add
+            const vmd_set_frame_t sf = vmd_set_frame(p.f, b);
+            const double x0 = (double)sf.fr.x[i0], y0 = (double)sf.fr.y[i0], z0 = (double)sf.fr.z[i0];
+            const double* rot = q.rot + ((size_t)b * p.P + c) * VMD_RMSF_NROT;
+            vmd_rmsd_atom_t at[VMD_RMSD_GROUP];
+            int incl[VMD_RMSD_GROUP][3];
+#pragma unroll
+            for (int k = 0; k < VMD_RMSD_GROUP; ++k) at[k] = vmd_rmsd_load(sf.fr, set, mass, a0 + (st + k) * VMD_SET_BLOCK + tid, n);
+#pragma unroll
+            for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+                int tot[3];
+                vmd_rmsd_wave_shift(at[k], sf, lane, incl[k], tot);
+                if (lane == 0) { s_tot[it & 1][k][wave][0] = tot[0]; s_tot[it & 1][k][wave][1] = tot[1]; s_tot[it & 1][k][wave][2] = tot[2]; }
+            }
+            __syncthreads();
+            // (read behind the barrier: thread 0 wrote this row at the end of the frame's iteration of the step before)
+            int run[3] = {s_run[par][f][0], s_run[par][f][1], s_run[par][f][2]};
+#pragma unroll
+            for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+                int kk[3];
+                double ex, ey, ez;
+                vmd_rmsd_join(s_tot[it & 1][k], wave, incl[k], run, kk);
+                vmd_rmsd_offset(at[k].at, sf, x0, y0, z0, kk[0], kk[1], kk[2], ex, ey, ez);
+                if (a0 + (st + k) * VMD_SET_BLOCK + tid < n) vmd_rmsf_add(rot, ex, ey, ez, u[k], acc[k]);
+            }
+            if (tid == 0) { s_run[par ^ 1][f][0] = run[0]; s_run[par ^ 1][f][1] = run[1]; s_run[par ^ 1][f][2] = run[2]; }
+            it += 1;
+        }
+#pragma unroll
+        for (int k = 0; k < VMD_RMSD_GROUP; ++k) {
+            const int a = a0 + (st + k) * VMD_SET_BLOCK + tid;
+            if (a < n) vmd_rmsf_commit(q.acc + 4 * ((size_t)sl.k0 + a), acc[k]);
+        }
+    }
+}
+
+// populations of small sets: one wave per (context, frame group), lane j owns atom j over the group's frames - k_rmsd_small's walk per
+// frame, the same e_a, the same registers and atomics as the block form
+__global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsf_small(vmd_rmsf_params_t q) {
+    const vmd_rmsd_params_t& p = q.r;
+    const int t = blockIdx.x * VMD_SET_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = t % q.groups, c = t / q.groups;
+    if (c >= p.P) return;            // the whole wave
+    int fb, nf;
+    vmd_rmsf_group(q, g, fb, nf);
+    if (c == 0 && lane == 0 && nf > 0) atomicAdd((unsigned long long*)q.acc + 4 * (size_t)p.off[p.P], (unsigned long long)nf);
+    const vmd_set_slice_t sl = vmd_set_slice(p.off, c);
+    const int n = sl.n;
+    if (n <= 1 || p.cst[(size_t)c * VMD_RMSD_NCONST] == 0.0) return;     // D-RMSF-DEGENERATE
+    const int32_t* set = p.set + sl.k0;
+    const double* pose = p.pose + (size_t)sl.k0 * 3;
+    const int i0 = set[0], aa = lane < n ? lane : 0;
+    const double u[3] = {pose[3 * aa + 0], pose[3 * aa + 1], pose[3 * aa + 2]};
+    long long acc[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (int f = 0; f < nf; ++f) {
+        const int b = fb + f;
+        if (b == p.zero_row) continue;
+        const vmd_set_frame_t sf = vmd_set_frame(p.f, b);
+        const double x0 = (double)sf.fr.x[i0], y0 = (double)sf.fr.y[i0], z0 = (double)sf.fr.z[i0];
+        const vmd_rmsd_atom_t at = vmd_rmsd_load(sf.fr, set, p.mass + sl.k0, lane, n);
+        int kk[3], tot[3];
+        double ex, ey, ez;
+        vmd_rmsd_wave_shift(at, sf, lane, kk, tot);
+        vmd_rmsd_offset(at.at, sf, x0, y0, z0, kk[0], kk[1], kk[2], ex, ey, ez);
+        if (lane < n) vmd_rmsf_add(q.rot + ((size_t)b * p.P + c) * VMD_RMSF_NROT, ex, ey, ez, u, acc);
+    }
+    if (lane < n) vmd_rmsf_commit(q.acc + 4 * ((size_t)sl.k0 + lane), acc);
 }
 
 // ------------------------------------------------------------------------------------------------ misc
@@ -4752,31 +4965,45 @@ extern "C" size_t vmd_hip_rmsd_workspace_bytes(int B, int P, int max_set) {
     return blocks * (VMD_RMSD_NSUM * sizeof(double) + 4 * sizeof(int32_t));
 }
 
-// both passes: POSE runs the kernels' POSE forms over one frame (B = 1, frame_stride 0, no zero row, no values)
-template <bool POSE>
-static int vmd_rmsd_launch(void* stream, vmd_frames_t f, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+// the parameter block of the rmsd and rmsf launches: the workspace holds the sums and, for the block kernels, the chunk shifts behind them
+static int vmd_rmsd_params(vmd_rmsd_params_t& p, vmd_frames_t f, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
                            const double* pose, const double* consts, int zero_row, void* workspace, float* out) {
-    hipStream_t s = (hipStream_t)stream;
     const long long BP = (long long)f.B * P;
-    vmd_rmsd_params_t p{};
+    p = vmd_rmsd_params_t{};
     p.f = f; p.P = P; p.set = set; p.mass = mass; p.off = offsets;
     p.pose = const_cast<double*>(pose); p.cst = const_cast<double*>(consts);      // written by the pose pass only
     p.zero_row = zero_row; p.out = out;
     p.nchunk = vmd_set_chunks(max_set);
     if (!workspace || BP * p.nchunk > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     p.partial = (double*)workspace;
+    if (max_set > VMD_SET_WAVE_SET) p.shift = (int32_t*)((char*)workspace + (size_t)(BP * p.nchunk) * VMD_RMSD_NSUM * sizeof(double));
+    return 0;
+}
+// the sums of every (frame, context): one wave per set, or the chunk shifts and the block kernel
+template <bool POSE>
+static int vmd_rmsd_sums(hipStream_t s, const vmd_rmsd_params_t& p, int max_set) {
+    const long long BP = (long long)p.f.B * p.P;
     if (max_set <= VMD_SET_WAVE_SET) {
         hipLaunchKernelGGL(k_rmsd_small<POSE>, vmd_set_small_grid(BP), dim3(VMD_SET_BLOCK), 0, s, p);
         VMD_LAUNCH_CHECK();
     } else {
-        p.shift = (int32_t*)((char*)workspace + (size_t)(BP * p.nchunk) * VMD_RMSD_NSUM * sizeof(double));
         const dim3 blocks((unsigned)(BP * p.nchunk));
         hipLaunchKernelGGL(k_rmsd_shift, blocks, dim3(VMD_SET_BLOCK), 0, s, p);
         VMD_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_rmsd_moments<POSE>, blocks, dim3(VMD_SET_BLOCK), 0, s, p);
         VMD_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_rmsd_finish<POSE>, dim3((unsigned)((BP + 63) / 64)), dim3(64), 0, s, p);
+    return 0;
+}
+// both passes: POSE runs the kernels' POSE forms over one frame (B = 1, frame_stride 0, no zero row, no values)
+template <bool POSE>
+static int vmd_rmsd_launch(void* stream, vmd_frames_t f, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set,
+                           const double* pose, const double* consts, int zero_row, void* workspace, float* out) {
+    hipStream_t s = (hipStream_t)stream;
+    vmd_rmsd_params_t p;
+    if (int rc = vmd_rmsd_params(p, f, P, set, mass, offsets, max_set, pose, consts, zero_row, workspace, out)) return rc;
+    if (int rc = vmd_rmsd_sums<POSE>(s, p, max_set)) return rc;
+    hipLaunchKernelGGL(k_rmsd_finish<POSE>, dim3((unsigned)(((long long)f.B * P + 63) / 64)), dim3(64), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }
@@ -4799,6 +5026,73 @@ extern "C" int vmd_hip_rmsd(void* stream, const float* xyz, size_t frame_stride,
         return (int)hipErrorInvalidValue;
     return vmd_rmsd_launch<false>(stream, vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), P, set, mass, offsets, max_set, pose,
                                   consts, zero_row, workspace, out);
+}
+
+// rmsf.  vmd_hip_rmsf_fit: the sums of the batch (have_sums != 0: an rmsd launch over the same sets has left them in
+// `workspace`) and the rotation and centroids of every (frame, context) into rot.  vmd_hip_rmsf_accumulate: frames [b0, b0 + nb) of the
+// batch into the record acc, in `groups` frame groups (<= 0: chosen here so that a small set still fills the card)
+extern "C" size_t vmd_hip_rmsf_rot_doubles(int B, int P) { return B > 0 && P > 0 ? (size_t)B * (size_t)P * VMD_RMSF_NROT : 0; }
+
+static int vmd_rmsf_params(vmd_rmsf_params_t& q, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                           int B, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set, const double* pose,
+                           const double* consts, int zero_row, void* workspace, double* rot) {
+    if (!xyz || !set || !mass || !offsets || !pose || !consts || !rot || max_set <= 0 || (long long)B * P > 0x7fffffffLL)
+        return (int)hipErrorInvalidValue;
+    q = vmd_rmsf_params_t{};
+    q.rot = rot;
+    return vmd_rmsd_params(q.r, vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), P, set, mass, offsets, max_set, pose, consts,
+                           zero_row, workspace, nullptr);
+}
+
+extern "C" int vmd_hip_rmsf_fit(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                                int B, int P, const int32_t* set, const float* mass, const int32_t* offsets, int max_set, const double* pose,
+                                const double* consts, void* workspace, int have_sums, double* rot) {
+    if (B <= 0 || P <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    vmd_rmsf_params_t q;
+    if (int rc = vmd_rmsf_params(q, xyz, frame_stride, row_stride, boxes, pbc_flags, B, P, set, mass, offsets, max_set, pose, consts, -1, workspace,
+                                 rot)) return rc;
+    if (!have_sums) if (int rc = vmd_rmsd_sums<false>(s, q.r, max_set)) return rc;
+    hipLaunchKernelGGL(k_rmsf_rotation, dim3((unsigned)(((long long)B * P + 63) / 64)), dim3(64), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// the frame groups of one accumulate launch.  Block kernel: about four blocks per CU of (context, chunk, group), never more than
+// VMD_RMSF_FRAMES frames to a group; one wave per set: about 4096 waves.  `want` > 0 asks for that many (clamped the same way)
+extern "C" int vmd_hip_rmsf_groups(int nb, int P, int max_set, int want) {
+    if (nb <= 0 || P <= 0 || max_set <= 0) return 0;
+    const bool small = max_set <= VMD_SET_WAVE_SET;
+    const long long units = small ? P : (long long)P * vmd_set_chunks(max_set);
+    long long g = want > 0 ? want : ((small ? 4096 : 1024) + units - 1) / units;
+    const long long lo = small ? 1 : (nb + VMD_RMSF_FRAMES - 1) / VMD_RMSF_FRAMES;
+    g = g < lo ? lo : g;
+    g = g > nb ? nb : g;
+    return (int)g;
+}
+
+extern "C" int vmd_hip_rmsf_accumulate(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                       uint32_t pbc_flags, int B, int P, const int32_t* set, const float* mass, const int32_t* offsets,
+                                       int max_set, const double* pose, const double* consts, int zero_row, void* workspace,
+                                       const double* rot, int b0, int nb, int groups, uint64_t* acc) {
+    if (B <= 0 || P <= 0 || nb <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    vmd_rmsf_params_t q;
+    if (int rc = vmd_rmsf_params(q, xyz, frame_stride, row_stride, boxes, pbc_flags, B, P, set, mass, offsets, max_set, pose, consts, zero_row,
+                                 workspace, const_cast<double*>(rot))) return rc;
+    if (!acc || b0 < 0 || b0 + (long long)nb > B) return (int)hipErrorInvalidValue;
+    q.acc = acc; q.b0 = b0; q.nb = nb;
+    q.groups = vmd_hip_rmsf_groups(nb, P, max_set, groups);
+    if (max_set <= VMD_SET_WAVE_SET) {
+        if ((long long)P * q.groups > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_rmsf_small, vmd_set_small_grid((long long)P * q.groups), dim3(VMD_SET_BLOCK), 0, s, q);
+    } else {
+        const long long blocks = (long long)P * q.r.nchunk * q.groups;
+        if (blocks > 0x7fffffffLL || (nb + q.groups - 1) / q.groups > VMD_RMSF_FRAMES) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_rmsf_accumulate, dim3((unsigned)blocks), dim3(VMD_SET_BLOCK), 0, s, q);
+    }
+    VMD_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int vmd_hip_bbox(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, int B, int natoms, float* out) {

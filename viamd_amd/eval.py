@@ -226,6 +226,17 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_rmsd_population(self.h, name.encode(), len(sets), flat.ctypes.data_as(L.c_int32_p),
                                                         off.ctypes.data_as(L.c_int32_p)))
 
+    def add_rmsf(self, name, idx, offsets=None):
+        """rmsf: the per-atom residual of rmsd's fit accumulated over the evaluated frames, one record of u64 accumulators
+        [ntot + 1, 4].  idx: the set; offsets: P + 1 context offsets into idx for a population (None: one set)."""
+        x, xp = _idx(idx)
+        if offsets is None:
+            self._check(self.lib.vmd_ir_add_rmsf(self.h, name.encode(), xp, x.size))
+            return
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        self._check(self.lib.vmd_ir_add_rmsf_population(self.h, name.encode(), max(off.size, 1) - 1, xp,
+                                                        off.ctypes.data_as(L.c_int32_p) if off.size else None))
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -369,6 +380,15 @@ class PropertyDataView:
         """a MAP property's u64 accumulators as [y, x, class]"""
         assert self.is_map
         return self.counts.reshape(L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES)
+
+    @property
+    def rmsf_accumulators(self):
+        """the record of an rmsf property as uint64 [ntot + 1, 4]: per entry of the set the two's-complement sums of
+        q(d_x), q(d_y), q(d_z) and the sum of q2(|d|^2); the last row's first word is the number of frames accumulated"""
+        assert self.c.dim[1] == 4 and self.c.dim[2] == 0, "not an rmsf record"
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, self.c.dim[0] * 4, np.uint64).reshape(self.c.dim[0], 4)
 
     @property
     def ss_classes(self):
@@ -579,6 +599,16 @@ class ScriptEval:
                                               sums.ctypes.data_as(L.c_uint64_p)):
             raise VmdError(self.lib.last_error())
         return values, sums
+
+    def rmsf(self, name):
+        """an rmsf property read from its record as it stands -> (rmsf float64 [ntot], mean_dev float64 [ntot, 3], frames)"""
+        ntot = self.property_data(name).dim[0] - 1
+        rmsf, mean = np.zeros(max(ntot, 0), np.float64), np.zeros((max(ntot, 0), 3), np.float64)
+        frames = C.c_uint64(0)
+        if not self.lib.vmd_eval_rmsf(self.h, name.encode(), rmsf.ctypes.data_as(L.c_double_p), mean.ctypes.data_as(L.c_double_p),
+                                      C.byref(frames)):
+            raise VmdError(self.lib.last_error())
+        return rmsf, mean, int(frames.value)
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""
