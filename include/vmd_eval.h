@@ -331,6 +331,28 @@ bool vmd_ir_add_ramachandran(vmd_script_ir_t* ir, const char* const names[2], co
 #define VMD_SS_NUM_CODES 9
 #define VMD_SS_MAX_SEGMENTS 16384
 bool vmd_ir_add_secondary_structure(vmd_script_ir_t* ir, const char* const names[2], const vmd_backbone_t* backbone, const int32_t* o);
+/* Hydrogen bonds between a donor set and an acceptor set (an entry point, no script syntax): per frame their number, over the
+ * run how often every donor hydrogen and every acceptor takes part.  sites: npairs donor pairs - pair j is the heavy atom donor[j] with its
+ * explicit hydrogen hydrogen[j]; a donor with two H is two pairs - and nacc acceptors.  A bond is one (pair j, acceptor k) combination with
+ *   1. distance: d(D, A) <= / < r_da exactly as within(r_da, .) tests it - wrapped positions, the SPEC S3 image, r_min = 0,
+ *      spec_within_closed acting on it as on a shell; e = (D - A) - shift is the delta of that test;
+ *   2. identity: A is neither donor[j] nor hydrogen[j], by atom index;
+ *   3. hydrogen: h = the minimum image of (H - D) from the raw frame (the image of distance());
+ *   4. angle: u = -h, v = -e - h; the D-H...A angle is at least angle_min_deg iff u.u > 0, v.v > 0, u.v <= 0 and
+ *      (u.v)^2 >= c2 (u.u v.v), c2 = cos^2(angle_min) formed in double and rounded once to fp32.  fp32, every operation rounded on its own.
+ * Acceptors whose wrapped positions coincide bit for bit in a frame all answer as the lowest such list entry (D-HB-COINCIDENT).
+ * names[0]: TEMPORAL, dim = {num_frames, 1}, no unit: the bonds of the frame (+0 for none; follows the frame mask like a within count).
+ * names[1]: MAP (VMD_PROPERTY_FLAG_MAP) of u64 accumulators, dim = {npairs + nacc + 1, 1}: row j < npairs the bonds pair j donated over
+ * all evaluated frames, row npairs + k the bonds acceptor k accepted, the last row the frames accumulated.  Integer counts: the record is
+ * the same bit for bit however calls, batches, frame groups and ranks arrive, and merges like every MAP; a frame evaluated twice without
+ * vmd_eval_clear_data counts twice.  `counts` are the accumulators (vmd_eval_refresh_counts), `values` the same numbers as floats.
+ * Errors (vmd_last_error): NULL arguments, npairs == 0 or nacc == 0, negative indices, hydrogen[j] == donor[j], r_da not finite or <= 0,
+ * angle_min_deg outside [90, 180], names already defined or equal to each other.  vmd_ir_geometry_atoms: donors, hydrogens, acceptors. */
+typedef struct vmd_hbond_sites_t {
+    size_t npairs;  const int32_t *donor, *hydrogen;
+    size_t nacc;    const int32_t *acceptor;
+} vmd_hbond_sites_t;
+bool vmd_ir_add_hbonds(vmd_script_ir_t* ir, const char* const names[2], const vmd_hbond_sites_t* sites, float r_da, float angle_min_deg);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
@@ -371,6 +393,14 @@ void     vmd_backbone_free(vmd_backbone_owned_t* backbone);
  * "OT1", then "O1", then "OC1", else -1.  Writes the first `cap` of them to `out` (NULL: count only) and returns num_segments; 0 +
  * vmd_last_error on a NULL or malformed argument. */
 size_t   vmd_topology_backbone_oxygens(const vmd_topology_t* topology, const vmd_backbone_t* backbone, int32_t* out, size_t cap);
+/* Hydrogen-bond sites from a topology and its bonds (DECISION D-HB-TOPOLOGY; elements only, no coordinates): a donor pair for every bond
+ * between an atom of element H and an atom of element N or O, the acceptors every atom of element N, O or F; both lists in ascending atom
+ * order (pairs by donor, then hydrogen).  Elements compare without regard to case.  NULL + vmd_last_error on a NULL topology, NULL bonds
+ * with nbonds > 0, or a bond that names an atom outside the topology; the view (either list may be empty) lives as long as the object. */
+typedef struct vmd_hbond_sites_owned_t vmd_hbond_sites_owned_t;
+vmd_hbond_sites_owned_t* vmd_topology_hbond_sites(const vmd_topology_t* topology, const int32_t (*bonds)[2], size_t nbonds);
+const vmd_hbond_sites_t* vmd_hbond_sites_view(const vmd_hbond_sites_owned_t* sites);
+void     vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
  * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of
@@ -542,6 +572,18 @@ bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name, uint32_t f
  * mean aligned position, in Angstrom.  rmsf: double[ntot], mean_dev: double[ntot][3], frames: the count; each may be NULL.  F == 0
  * answers zeros.  false + vmd_last_error: an unknown property, a property that is not an rmsf. */
 bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double* rmsf, double* mean_dev, uint64_t* frames);
+
+/* A hydrogen-bond occupancy (names[1] of vmd_ir_add_hbonds) read from its record as it stands - partially evaluated or
+ * merged alike: donor_occ double[npairs], acc_occ double[nacc] = count / frames, frames: the count; each may be NULL.  F == 0 answers
+ * zeros.  false + vmd_last_error: an unknown property, a property of another form. */
+bool vmd_eval_hbonds(vmd_script_eval_t* eval, const char* name, double* donor_occ, double* acc_occ, uint64_t* frames);
+/* The bonds of ONE frame, on demand (either name of the statement), under vmd_eval_shell_mask's contract: nothing accumulated is touched, it
+ * may be called while pool threads are inside vmd_eval_frame_range.  Returns the number of bonds and writes the first `cap` as
+ * {donor, hydrogen, acceptor} atoms in ascending (pair index, acceptor list position) order (out may be NULL with cap == 0);
+ * VMD_HBOND_PAIRS_FAILED + vmd_last_error on failure. */
+#define VMD_HBOND_PAIRS_FAILED ((size_t)-1)
+size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                            int32_t (*out)[3], size_t cap);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

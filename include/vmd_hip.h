@@ -22,6 +22,7 @@
  *   vmd_hip_within_*_flags, vmd_hip_shell_compact, vmd_hip_rdf_brute_masked  <- rdf() over within() shells
  *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
  *   vmd_hip_within_atoms_expr, vmd_hip_within_brute_expr, vmd_hip_shell_expr_finish  <- and / or / not over within() shells
+ *   vmd_hip_sorted_atoms, vmd_hip_hbond_*  <- hydrogen bonds
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -310,6 +311,38 @@ int vmd_hip_sdf_scatter_masked(void* stream, const float* xyz, size_t frame_stri
                                const int32_t* tgt, const int8_t* owner, int ntgt, float extent, int dim, uint64_t* volume,
                                const float* group, int tgt_first, int tgt_stride, int unowned,
                                const uint8_t* mask, size_t mask_stride, const uint32_t* skip_flag);
+
+/* K12: hydrogen bonds, DESIGN 1.14.  A bond is one (donor pair j, acceptor entry k) combination: D = don[j], H = hyd[j], A = accl[k] at
+ * 0 <= d(D, A) < r_da (closed != 0: <= r_da; the pair distance of K6), A neither D nor H by atom index, and the D-H...A angle at least
+ * angle_min: with h = the minimum image of H - D from the raw frame, e the delta of the distance test, u = -h, v = -e - h:
+ * u.u > 0, v.v > 0, u.v <= 0 and (u.v)^2 >= c2 (u.u v.v), c2 = fl(cos^2(angle_min)); every operation fp32, separately rounded.
+ * Outputs: count_out u32[B] (zeroed by the call), the bonds of every frame; acc u64[npairs + nacc + 1], ADDED to: row j the bonds pair j
+ * donated, row npairs + k the bonds entry k accepted.  Acceptor entries whose wrapped coordinates coincide bit for bit in a frame all
+ * answer as the lowest of them (D-HB-COINCIDENT).  Nothing happens when *skip_flag != 0.  B <= 65535.
+ *   vmd_hip_sorted_atoms  the identity of a cell-sorted copy (K1): ident_out u32[B][nsel_pad], slot -> the lowest list entry t whose wrapped
+ *                         coordinates are the slot's, bit for bit; boxes are the GRID's, as the build took them
+ *   vmd_hip_hbond_atoms   the cell walk of K8 over the cell-sorted copy of the acceptors, one lane per donor pair, every hit visited;
+ *                         grid_boxes: the grid's; frame_boxes: the frames' own (the hydrogen's image)
+ *   vmd_hip_hbond_brute   all pairs from the raw frame (any cell, any cutoff); canon: scratch, u32[B][nacc]
+ *   vmd_hip_hbond_list    ONE frame by all pairs: list u32[list_cap][2] = {j, list position k} of the first list_cap bonds found (in no order;
+ *                         the entry that answers for k is canon[k]), *list_count (device, zeroed by the call) = the bonds; nothing is
+ *                         accumulated
+ *   vmd_hip_hbond_finish  out[b] = (float)counts[b], *frames_row += B */
+int vmd_hip_sorted_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                         int B, const int32_t* sel, int nsel, const float* sorted, const uint32_t* cell_start, int nsel_pad, vmd_grid_t grid,
+                         uint32_t* ident_out, const uint32_t* skip_flag);
+int vmd_hip_hbond_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes,
+                        const float* frame_boxes, uint32_t pbc_flags, int B, const int32_t* don, const int32_t* hyd, int npairs,
+                        const int32_t* accl, int nacc, const float* sorted_acc, const uint32_t* cell_start_acc, int nacc_pad,
+                        const uint32_t* ident, vmd_grid_t grid, float r_da, float c2, int closed, uint32_t* count_out, uint64_t* acc,
+                        const uint32_t* skip_flag);
+int vmd_hip_hbond_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                        int B, const int32_t* don, const int32_t* hyd, int npairs, const int32_t* accl, int nacc, uint32_t* canon,
+                        float r_da, float c2, int closed, uint32_t* count_out, uint64_t* acc, const uint32_t* skip_flag);
+int vmd_hip_hbond_list(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, const int32_t* don,
+                       const int32_t* hyd, int npairs, const int32_t* accl, int nacc, uint32_t* canon, float r_da, float c2, int closed,
+                       uint32_t* list, uint32_t list_cap, uint32_t* list_count);
+int vmd_hip_hbond_finish(void* stream, const uint32_t* counts, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -78,6 +78,11 @@ class BackboneC(C.Structure):            # vmd_backbone_t (include/vmd_eval.h)
                 ("num_ranges", C.c_size_t), ("range_offsets", C.POINTER(C.c_uint32)), ("rama_class", C.POINTER(C.c_uint8))]
 
 
+class HbondSitesC(C.Structure):          # vmd_hbond_sites_t (include/vmd_eval.h)
+    _fields_ = [("npairs", C.c_size_t), ("donor", C.POINTER(C.c_int32)), ("hydrogen", C.POINTER(C.c_int32)),
+                ("nacc", C.c_size_t), ("acceptor", C.POINTER(C.c_int32))]
+
+
 class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
     _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
 
@@ -182,6 +187,12 @@ SIGNATURES = [
     ("vmd_ir_add_rmsf", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
     ("vmd_ir_add_rmsf_population", C.c_bool, [_vp, C.c_char_p, C.c_size_t, c_int32_p, c_int32_p]),
     ("vmd_eval_rmsf", C.c_bool, [_vp, C.c_char_p, c_double_p, c_double_p, c_uint64_p]),
+    ("vmd_ir_add_hbonds", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(HbondSitesC), C.c_float, C.c_float]),
+    ("vmd_eval_hbonds", C.c_bool, [_vp, C.c_char_p, c_double_p, c_double_p, c_uint64_p]),
+    ("vmd_eval_hbond_pairs", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, c_int32_p, C.c_size_t]),
+    ("vmd_topology_hbond_sites", _vp, [C.POINTER(TopologyC), c_int32_p, C.c_size_t]),
+    ("vmd_hbond_sites_view", C.POINTER(HbondSitesC), [_vp]),
+    ("vmd_hbond_sites_free", None, [_vp]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
@@ -386,6 +397,15 @@ SIGNATURES = [
                                    _vp, _vp, _vp, C.c_int, _vp]),
     ("vmd_hip_rmsf_accumulate", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int,
                                           _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    ("vmd_hip_sorted_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, Grid,
+                                       _vp, _vp]),
+    ("vmd_hip_hbond_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int,
+                                      _vp, _vp, C.c_int, _vp, Grid, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_hbond_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
+                                      C.c_float, C.c_float, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_hbond_list", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_float,
+                                     C.c_int, _vp, C.c_uint32, _vp]),
+    ("vmd_hip_hbond_finish", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

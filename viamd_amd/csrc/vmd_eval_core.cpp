@@ -217,6 +217,20 @@ void build_within_plan(vmd_script_eval_t* e) {
     }
 }
 
+// hydrogen bonds: the acceptors become an interned selection - shared with everything else of the script, so that a
+// cell-sorted copy another pass built on the same grid in a batch is not built again; the donors are walked in list order and are never
+// sorted (their selection only says how many lanes the grid is chosen for)
+void build_hbond_plan(vmd_script_eval_t* e) {
+    e->hbond_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        if (p->prop.form != Form::HBOND_COUNT) continue;
+        p->sel_a = intern_selection(e, p->prop.a);
+        p->sel_b = intern_selection(e, p->prop.b);
+        e->hbond_props.push_back((int)i);
+    }
+}
+
 uint32_t shell_expr_live(uint32_t truth, const std::vector<int>& order, size_t pos) {
     uint32_t done = 0, later = 0;
     for (size_t k = 0; k < order.size(); ++k) { if (k < pos) done |= 1u << order[k]; else if (k > pos) later |= 1u << order[k]; }
@@ -352,7 +366,12 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         case Form::SS_CLASS: st->dist_P = p.a.size(); aggregate = false; break;
         case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
         case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
-        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: break;
+        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: break;
+        case Form::HBOND_OCC:
+            // one u64 word per donor pair, per acceptor, and the frame count; the float view is the words as numbers, as a map's
+            pinned_views(p.K + p.m + 1);
+            st->data.dim[0] = (int32_t)(p.K + p.m + 1); st->data.dim[1] = 1; st->data.dim[2] = st->data.dim[3] = 0;
+            break;
         case Form::SHAPE: st->shape_max_set = largest_set(); break;
         case Form::RMSD: st->rmsd_max_set = largest_set(); break;
         case Form::RMSF: {
@@ -396,6 +415,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     }
     build_rdf_plan(e.get());
     build_within_plan(e.get());
+    build_hbond_plan(e.get());
     build_expr_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
@@ -781,7 +801,9 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
             if (p->ncounts) { v.counts_dev = p->d_counts.p; v.num_counts = p->ncounts; }
             // a voxel receives at most one count per (frame, structure, target atom), a bin of a map one per (frame, segment)
             if (p->prop.counts_view()) {
-                const long double per_frame = (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
+                // (a donor row at most one count per acceptor and frame, an acceptor row one per pair)
+                const long double per_frame = p->prop.form == Form::HBOND_OCC ? (long double)std::max(p->prop.K, p->prop.m)
+                        : (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
                 const long double b = (long double)eval->num_frames * per_frame;
                 v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
             }
@@ -893,6 +915,96 @@ extern "C" bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double*
     return true;
 }
 
+// ---- hydrogen-bond occupancies read from their record: count / frames per donor pair and per acceptor.  Whatever the
+// record holds - a partial evaluation, a merged one - is what is read; under the eval's mutex, touching nothing it keeps.
+extern "C" bool vmd_eval_hbonds(vmd_script_eval_t* eval, const char* name, double* donor_occ, double* acc_occ, uint64_t* frames) {
+    if (!eval || !name) return vmd_fail("vmd_eval_hbonds: NULL argument");
+    PropState* p = find_prop(eval, name);
+    if (!p) return vmd_fail("unknown property '%s'", name);
+    if (p->prop.form != Form::HBOND_OCC) return vmd_fail("'%s' is not a hydrogen-bond occupancy", name);
+    const size_t npairs = p->prop.K, nacc = p->prop.m;
+    std::vector<uint64_t> acc(p->ncounts);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        HIP_OK(hipSetDevice(eval->device));
+        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
+        HIP_OK(hipStreamSynchronize(eval->stream));
+    }
+    const uint64_t F = acc[npairs + nacc];
+    if (frames) *frames = F;
+    if (donor_occ) for (size_t j = 0; j < npairs; ++j) donor_occ[j] = F ? (double)acc[j] / (double)F : 0.0;
+    if (acc_occ) for (size_t k = 0; k < nacc; ++k) acc_occ[k] = F ? (double)acc[npairs + k] / (double)F : 0.0;
+    return true;
+}
+
+// The bonds of one frame.  One frame on demand, as vmd_eval_shell_mask: all pairs from the raw frame (for ONE frame the cell
+// build and the identity pass a walk needs cost more than they save) into a capped list behind a counter, sorted on the host.  Nothing the
+// evaluation keeps is touched: canon, counter and list live in one buffer of the eval that only this call uses (kept between calls).
+extern "C" size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                                       int32_t (*out)[3], size_t cap) {
+    const size_t failed = VMD_HBOND_PAIRS_FAILED;
+    if (!eval || !traj || !name || (!out && cap)) { vmd_fail("vmd_eval_hbond_pairs: NULL argument"); return failed; }
+    vmd_script_eval_t* e = eval;
+    size_t pi = e->props.size();
+    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
+    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return failed; }
+    if (e->props[pi]->prop.form == Form::HBOND_OCC && pi > 0) pi -= 1;         // the occupancy names the statement as well as its count
+    PropState* p = e->props[pi].get();
+    if (p->prop.form != Form::HBOND_COUNT) { vmd_fail("'%s' is not a hydrogen-bond property", name); return failed; }
+    if (frame >= e->num_frames) { vmd_fail("vmd_eval_hbond_pairs: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
+    const Property& d = p->prop;
+    const size_t npairs = d.a.size(), nacc = d.b.size();
+    std::vector<uint32_t> list, canon_h(nacc);
+    uint32_t found = 0;
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
+        const size_t num_atoms = traj->num_atoms(traj->inst);
+        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
+        auto run = [&]() -> bool {
+            vmd_device_view_t view;
+            memset(&view, 0, sizeof(view));
+            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
+            BatchSrc src;
+            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+            // two passes at the most: the list is sized for what a caller asks for (and a fair share more), the second pass for what was found
+            size_t room = std::min<size_t>(std::max<size_t>(cap, 4 * npairs), (size_t)0x3fffffff);
+            for (int pass = 0; pass < 2; ++pass) {
+                if (!e->d_one_hbonds.ensure(nacc + 1 + 2 * room)) return false;
+                uint32_t* canon = e->d_one_hbonds.p;
+                uint32_t* counter = canon + nacc;
+                uint32_t* dl = counter + 1;
+                KRN_OK(vmd_hip_hbond_list(e->stream, src.base, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), p->d_a.p,
+                        p->d_c.p, (int)npairs, p->d_b.p, (int)nacc, canon, d.rmax, d.hb_c2, e->spec.within_closed ? 1 : 0, dl, (uint32_t)room,
+                        counter));
+                HIP_OK(hipMemcpyAsync(&found, counter, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+                HIP_OK(hipStreamSynchronize(e->stream));
+                if (found <= room) {
+                    list.resize(2 * (size_t)found);
+                    if (found) HIP_OK(hipMemcpyAsync(list.data(), dl, list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+                    HIP_OK(hipMemcpyAsync(canon_h.data(), canon, nacc * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+                    HIP_OK(hipStreamSynchronize(e->stream));
+                    return true;
+                }
+                if (found > 0x3fffffffu) return vmd_fail("vmd_eval_hbond_pairs: %u bonds in one frame", found);
+                room = found;
+            }
+            return vmd_fail("vmd_eval_hbond_pairs: the frame's bonds changed between two passes");
+        };
+        if (!run()) return failed;
+    }
+    // ascending (pair index, acceptor list position); the appends arrive in no order.  The acceptor named is the entry that answers for
+    // the position (D-HB-COINCIDENT)
+    std::vector<uint64_t> keys(found);
+    for (size_t i = 0; i < found; ++i) keys[i] = ((uint64_t)list[2 * i] << 32) | list[2 * i + 1];
+    std::sort(keys.begin(), keys.end());
+    for (size_t i = 0; i < found && i < cap; ++i) {
+        const size_t j = (size_t)(keys[i] >> 32), k = (size_t)(keys[i] & 0xffffffffu);
+        out[i][0] = d.a[j]; out[i][1] = d.c[j]; out[i][2] = d.b[canon_h[k]];
+    }
+    return found;
+}
+
 // ---- the hot call -----------------------------------------------------------------------------------------------
 bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_atoms) {
     for (auto& s : e->sels) {
@@ -909,7 +1021,12 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
         };
         std::vector<float> tmp;
         switch (d.form) {
-        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: break;      // the sets of an rdf are interned selections; a map and the populations have none
+        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: break;      // the sets of an rdf are interned selections; a map, the populations and an occupancy have none
+        case Form::HBOND_COUNT:
+            // the donors, their hydrogens, the acceptors in list order (the acceptors are an interned selection as well)
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_c.upload(d.c.data(), d.c.size(), e->stream) ||
+                !p->d_b.upload(d.b.data(), d.b.size(), e->stream)) return false;
+            break;
         case Form::SS_CLASS: {
             // N, CA, C, O per segment and what the kernels read of the ranges - the range of every segment, the proline bytes,
             // the bit row "has both neighbours in its range"

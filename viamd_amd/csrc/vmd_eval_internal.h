@@ -392,6 +392,10 @@ enum class Form : int {
     // rmsf: the set of rmsd (a / aoff).  A MAP-class record of u64 accumulators, [ntot + 1][4]: per entry of a the fixed-point
     // sums of the fit's residual over the evaluated frames, the frame count in the last row
     RMSF,
+    // `{count, occupancy} = hbonds(sites, r_da, angle_min)`: two descriptors in a row.  The count - a = donors, c = their
+    // hydrogens (pair j = a[j], c[j]), b = acceptors, rmax = r_da, hb_angle / hb_c2 - has one value per frame; the occupancy behind it
+    // (K = the pairs, m = the acceptors) is a MAP-class record of u64 accumulators, [K + m + 1], that the count's launch adds to
+    HBOND_COUNT, HBOND_OCC,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -422,8 +426,10 @@ constexpr FormFacts kFormFacts[] = {
     /* SS_CLASS    */ {ResultClass::TEMPORAL,     3, "secondary_structure", {"", ""},   nullptr, false, 11},    // a code, a count
     /* SS_POP      */ {ResultClass::TEMPORAL,     0, "secondary_structure", {"", ""},   nullptr, false, 12},
     /* RMSF        */ {ResultClass::MAP,          1, "rmsf",          {"", "\xC3\x85"}, nullptr, false, 13},    // Angstrom in 2^-24 quanta
+    /* HBOND_COUNT */ {ResultClass::TEMPORAL,     0, "hbonds",        {"", ""},         nullptr, true,  14},    // counts
+    /* HBOND_OCC   */ {ResultClass::MAP,          0, "hbonds",        {"", ""},         nullptr, true,  15},
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::RMSF + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::HBOND_OCC + 1, "one row of kFormFacts per Form");
 static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES, "the kernels' limits are the interface's");
 
 struct Property {
@@ -454,6 +460,7 @@ struct Property {
     uint32_t expr_truth = 0;
     std::vector<uint8_t> rama_class, rama_link;     // RAMA_TABLE: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
     std::vector<int32_t> ss_o;                      // SS_CLASS: the carbonyl oxygen of every segment, -1 = none
+    float hb_angle = 0.0f, hb_c2 = 0.0f;            // HBOND_COUNT: angle_min in degrees as given, and fl(cos^2) of it formed in double
     bool is_expr_sdf() const { return form == Form::SDF && !expr_terms.empty(); }
     bool behind_cells() const { return facts().behind_cells || is_shell_sdf() || is_expr_sdf(); }     // launch_rdf launches it, not launch_property
 };
@@ -618,6 +625,9 @@ struct PropState {
     int rmsf_of = -1;
     DevBuf<double> d_rmsf_rot;
     int rmsf_groups = 0;
+    // hydrogen bonds, the count: sel_b is the interned acceptor selection; d_a / d_c / d_b the donor, hydrogen and acceptor
+    // lists; the identity table of the acceptors' cell-sorted copy (or the all-pairs route's canonical entries) and the batch's counts
+    DevBuf<uint32_t> d_hb_ident, d_hb_count;
     // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
@@ -839,12 +849,14 @@ struct vmd_script_eval_t {
     DevBuf<uint8_t> d_one_mask;                         // vmd_eval_shell_mask: one frame's mask by atom and its population, kept between calls
     DevBuf<uint32_t> d_one_count;
     DevBuf<uint8_t> d_one_bits;                         // ... and the term outcomes of a shell expression's frame
+    DevBuf<uint32_t> d_one_hbonds;                      // vmd_eval_hbond_pairs: one frame's canonical entries, its counter, its {pair, entry} list
     std::vector<std::unique_ptr<ShellExpr>> exprs;      // shell expressions and the counts / sdfs over them, indices into props
     std::vector<int> expr_count_props, expr_sdf_props;
     // secondary structure: the four bit matrices of the frames in flight, shared by the statements of the script (they run one
     // after another on the eval's stream), and the bound on them (option ss_scratch_bytes, read at creation)
     DevBuf<uint64_t> d_ss_scratch;
     size_t ss_scratch_bytes = 0;
+    std::vector<int> hbond_props;                       // indices into props of the hydrogen-bond counts: behind the cell builds too
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
     DevBuf<uint64_t> d_pass;
@@ -938,6 +950,8 @@ int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx);
 
 void build_rdf_plan(vmd_script_eval_t* e);
 void build_within_plan(vmd_script_eval_t* e);
+
+void build_hbond_plan(vmd_script_eval_t* e);
 void build_expr_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
@@ -1113,6 +1127,7 @@ struct RangeRun {
     bool launch_within_counts(BatchCtx& c);
     bool launch_shell_masks(BatchCtx& c);
     bool launch_shell_sdfs(BatchCtx& c);
+    bool launch_hbonds(BatchCtx& c);
     bool launch_rdf(BatchCtx& c);
     bool launch_shell_exprs(BatchCtx& c);
     bool launch_expr_sdfs(BatchCtx& c);

@@ -47,6 +47,8 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         // plus N, CA, C, O of every segment
         case Form::SS_CLASS: w += (uint64_t)p.a.size() * (uint64_t)p.a.size() / 8 + 4 * (uint64_t)p.a.size(); break;
         case Form::SS_POP: break;                                            // counted by its table's launch
+        case Form::HBOND_COUNT: w += 2 * (uint64_t)p.a.size() + 2 * (uint64_t)p.b.size(); break;     // a neighbour query per pair (D, H), the acceptors sorted and identified
+        case Form::HBOND_OCC: break;                                         // added to by its count's launch
         }
     }
     return w;
@@ -420,6 +422,33 @@ extern "C" bool vmd_ir_add_secondary_structure(vmd_script_ir_t* ir, const char* 
     return commit(ir, tp, 2);
 }
 
+// `{count, occupancy} = hbonds(sites, r_da, angle_min)`: the per-frame count and the occupancy record, two descriptors in a row
+extern "C" bool vmd_ir_add_hbonds(vmd_script_ir_t* ir, const char* const names[2], const vmd_hbond_sites_t* sites, float r_da, float angle_min_deg) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names || !sites) return vmd_fail("hbonds needs two property names and the sites");
+    if (!names_ok(ir, names, 2)) return false;
+    if (sites->npairs == 0 || !sites->donor || !sites->hydrogen) return vmd_fail("hbonds donor pair list is empty");
+    if (!idx_ok(sites->donor, sites->npairs, "hbonds donor list") || !idx_ok(sites->hydrogen, sites->npairs, "hbonds hydrogen list") ||
+        !idx_ok(sites->acceptor, sites->nacc, "hbonds acceptor list")) return false;
+    if (sites->npairs > kMaxSet || sites->nacc > kMaxSet || sites->npairs + sites->nacc + 1 > kMaxSet) return vmd_fail("hbonds set too large");
+    for (size_t j = 0; j < sites->npairs; ++j)
+        if (sites->hydrogen[j] == sites->donor[j]) return vmd_fail("hbonds pair %zu names atom %d as donor and as its hydrogen", j, sites->donor[j]);
+    if (!std::isfinite(r_da) || !(r_da > 0.0f)) return vmd_fail("hbonds donor-acceptor distance must be finite and positive");
+    if (!(angle_min_deg >= 90.0f && angle_min_deg <= 180.0f)) return vmd_fail("hbonds minimum angle must lie in [90, 180] degrees");
+    Property t = make_property(Form::HBOND_COUNT, names[0]);
+    t.a.assign(sites->donor, sites->donor + sites->npairs); t.c.assign(sites->hydrogen, sites->hydrogen + sites->npairs);
+    t.b.assign(sites->acceptor, sites->acceptor + sites->nacc);
+    t.aoff = {0, (int32_t)sites->npairs}; t.boff = {0, (int32_t)sites->nacc}; t.coff = {0, (int32_t)sites->npairs};
+    t.rmin = 0.0f; t.rmax = r_da;
+    t.hb_angle = angle_min_deg;
+    // c2 = cos^2(angle_min): formed in double, rounded once to fp32 (180 degrees: 1 exactly; 90 degrees: 0 exactly)
+    const double cs = angle_min_deg == 90.0f ? 0.0 : angle_min_deg == 180.0f ? -1.0 : std::cos((double)angle_min_deg * (M_PI / 180.0));
+    t.hb_c2 = (float)(cs * cs);
+    Property tp[2] = {std::move(t), make_property(Form::HBOND_OCC, names[1])};
+    tp[1].K = sites->npairs; tp[1].m = sites->nacc;
+    return commit(ir, tp, 2);
+}
+
 // what vmd_ir_geometry_atoms has counted and written so far
 struct AtomSink {
     int32_t* out; size_t cap, n = 0;
@@ -442,7 +471,11 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         };
         size_t c0 = 0, c1 = 0;
         switch (p.form) {
-        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: return 0;
+        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: return 0;
+        case Form::HBOND_COUNT:     // the donors, then their hydrogens, then the acceptors (one context)
+            if (context > 0) return 0;
+            s.put(p.a); s.put(p.c); s.put(p.b);
+            return s.n;
         case Form::WITHIN:          // the static candidates: the reference set, then the target set (one context)
             if (context > 0) return 0;
             s.put(p.b); s.put(p.a);
@@ -503,7 +536,8 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::SHAPE: h = fnv1a(h, &p.shape_comp, sizeof(int)); break;
         case Form::RAMA_TABLE: h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); break;     // 
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
-        case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: break;
+        case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: case Form::HBOND_OCC: break;
+        case Form::HBOND_COUNT: h = fnv1a(h, &p.hb_angle, sizeof(float)); break;      // (the hydrogens are c, hashed above)
         case Form::SS_CLASS:                                            // 
             h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); h = fnv1a(h, p.ss_o.data(), p.ss_o.size() * sizeof(int32_t));
             break;

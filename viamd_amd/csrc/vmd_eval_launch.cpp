@@ -336,6 +336,73 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
     return true;
 }
 
+// ---- hydrogen bonds.  The occupancy is added to with atomics, so like a masked scatter it has to be all or nothing: the
+// launches stand behind the LAST cell build of the batch, where the overflow flag is final, and test it.  First every statement's cell
+// build (within_route's RULE with the donors in the lanes: the acceptors alone are sorted, on the grid a within count of r_da gets; all
+// pairs below shell_brute_below acceptors or where no grid exists), then, statement by statement, the identity of the sorted copy and
+// the walk - per sub, so that a frame block's bonds land in its own partial.  A copy that a later statement's build has re-sorted on
+// another grid is not built a second time (that would be a cell build behind an accumulation): that statement takes all pairs for this
+// batch, which answers the same bit for bit.
+bool RangeRun::launch_hbonds(BatchCtx& c) {
+    const int closed = e->spec.within_closed ? 1 : 0;
+    std::vector<int> route(e->hbond_props.size(), 0);
+    for (size_t i = 0; i < e->hbond_props.size(); ++i) {
+        PropState* p = e->props[e->hbond_props[i]].get();
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        route[i] = within_route(c, e->sels[p->sel_a].get(), e->sels[p->sel_b].get(), p->prop.rmax, true, &grid, &d_gb);
+        if (route[i] < 0) return false;
+    }
+    for (size_t i = 0; i < e->hbond_props.size(); ++i) {
+        const int pi = e->hbond_props[i];
+        PropState* p = e->props[pi].get();
+        if ((size_t)pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::HBOND_OCC)
+            return vmd_fail("hydrogen-bond count '%s' has lost its occupancy", p->prop.name.c_str());
+        PropState* m = e->props[pi + 1].get();
+        const Property& d = p->prop;
+        Selection* sd = e->sels[p->sel_a].get();
+        Selection* sr = e->sels[p->sel_b].get();
+        const int npairs = (int)d.a.size(), nacc = (int)d.b.size();
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        int have_grid = route[i];
+        if (have_grid) {        // (the grid again: it also sets this thread's pencil reach for the walk)
+            have_grid = grid_for(c, std::max(sd->idx.size(), sr->idx.size()), d.rmax, &grid, &d_gb);
+            if (have_grid < 0) return false;
+            if (have_grid && !(sr->built && sr->built_grid.nxf == grid.nxf && sr->built_grid.ny == grid.ny && sr->built_grid.nz == grid.nz))
+                have_grid = 0;
+        }
+        if (!p->d_out.ensure(c.nb) || !p->d_hb_count.ensure(c.nb) ||
+            !p->d_hb_ident.ensure(c.nb * (size_t)(have_grid ? sr->nsel_pad : nacc))) return false;
+        const Stage& st = *c.src;
+        if (have_grid) {
+            e->prof.begin("sorted_atoms", e->stream);
+            KRN_OK(vmd_hip_sorted_atoms(e->stream, st.base, st.frame_stride, st.row_stride, d_gb, c.pbc, (int)c.nb, sr->d_idx.p, nacc,
+                    sr->sorted.p, sr->cell_start.p, sr->nsel_pad, grid, p->d_hb_ident.p, e->d_overflow.p));
+            e->prof.end(e->stream);
+        }
+        e->prof.begin(have_grid ? "hbond_atoms" : "hbond_brute", e->stream);
+        for (auto& su : c.subs) {
+            const float* xyz = st.base + su.off * st.frame_stride;
+            uint64_t* acc = acc_of(m, su);
+            if (have_grid)
+                KRN_OK(vmd_hip_hbond_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, st.d_boxes.p + 9 * su.off, c.pbc,
+                        (int)su.nb, p->d_a.p, p->d_c.p, npairs, p->d_b.p, nacc, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad,
+                        sr->cell_start.p + su.off * (size_t)(grid.ncell + 1), sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid,
+                        d.rmax, d.hb_c2, closed, p->d_hb_count.p + su.off, acc, e->d_overflow.p));
+            else
+                KRN_OK(vmd_hip_hbond_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
+                        p->d_a.p, p->d_c.p, npairs, p->d_b.p, nacc, p->d_hb_ident.p + su.off * (size_t)nacc, d.rmax, d.hb_c2, closed,
+                        p->d_hb_count.p + su.off, acc, e->d_overflow.p));
+            KRN_OK(vmd_hip_hbond_finish(e->stream, p->d_hb_count.p + su.off, (int)su.nb, p->d_out.p + su.off, acc + npairs + nacc,
+                    e->d_overflow.p));
+        }
+        e->prof.end(e->stream);
+        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
+    }
+    return true;
+}
+
 // ---- shell expressions: one pass per term over T in atom order, ascending |R_i|, then the finish.  Walk or all pairs per term
 // by within_route's RULE; the cell-sorted copies come from build_pair, so one that another pass of the batch built on the same grid is
 // reused.  The bits start clean in every batch and in every repeat of one; the counts travel to the host from here, like
@@ -420,7 +487,7 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     commits.clear();
     row = 0;
     forked = false;
-    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !launch_shell_sdfs(c) ||
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !launch_hbonds(c) || !launch_shell_sdfs(c) ||
         !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -606,7 +673,7 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     }
     if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
     switch (d.form) {
-    case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: return true;     // (behind the cell builds, above)
+    case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: return true;     // (behind the cell builds, above)
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);

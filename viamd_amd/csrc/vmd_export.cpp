@@ -94,6 +94,8 @@ static bool is_class_map(const vmd_script_property_data_t* pd) {
 
 // an rmsf record by its public record: u64 accumulators, dim = {ntot + 1, 4} - rows like a temporal property's, which has none
 static bool is_rmsf_record(const vmd_script_property_data_t* pd) { return pd->counts && !pd->weights && pd->dim[1] == 4 && pd->dim[2] == 0; }
+// ... and a hydrogen-bond occupancy: u64 accumulators, dim = {npairs + nacc + 1, 1}
+static bool is_hbond_record(const vmd_script_property_data_t* pd) { return pd->counts && !pd->weights && pd->dim[1] == 1 && pd->dim[2] == 0; }
 
 // pinned to the reference's own export_csv / export_xvg / sample_range by tests/native/ref_callsites.cpp
 extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* eval, const char* name, const char* format,
@@ -121,6 +123,8 @@ extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* e
         cols.push_back(std::move(g)); labels.push_back(unit_y[0] ? std::string(name) + " (" + unit_x + ")" : std::string(name));
     } else if (is_rmsf_record(pd)) {
         return exp_fail(std::string("Export: '") + name + "' is an rmsf record; read it with vmd_eval_rmsf");
+    } else if (is_hbond_record(pd)) {
+        return exp_fail(std::string("Export: '") + name + "' is a hydrogen-bond occupancy record; read it with vmd_eval_hbonds");
     } else if (pd->dim[3] == 0 || pd->dim[2] == 0) {    // temporal: values[frame * dim[1] + i]
         const size_t F = (size_t)pd->dim[0], D = (size_t)std::max(1, pd->dim[1]);
         rows = F;
@@ -192,6 +196,7 @@ extern "C" bool vmd_export_cube(const char* path, vmd_script_eval_t* eval, const
     if (!pd) return exp_fail("Export Cube: The property to be exported did not exist");
     if (is_class_map(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is a Ramachandran map, not a volume");
     if (is_rmsf_record(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is an rmsf record, not a volume");
+    if (is_hbond_record(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is a hydrogen-bond occupancy record, not a volume");
     vmd_sdf_payload_t vis;
     if (!vmd_eval_sdf_payload(eval, name, sys, traj, frame, &vis)) return exp_fail(std::string("Failed to visualize volume for export. ") + vmd_last_error());
     if (!vmd_eval_finalize(eval)) return false;         // the float view VIAMD reads (prop_data->values) is current

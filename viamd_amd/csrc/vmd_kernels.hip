@@ -16,6 +16,7 @@
 //   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
 //   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
 //   rmsf           -> rmsd's sums, k_rmsf_rotation, k_rmsf_accumulate (large sets) / k_rmsf_small
+//   hydrogen bonds -> k_sorted_atoms + k_hbond_atoms (the cell walk) / k_hbond_canon + k_hbond_brute (all pairs), k_hbond_finish
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -4183,6 +4184,299 @@ __global__ __launch_bounds__(VMD_SET_BLOCK) void k_rmsf_small(vmd_rmsf_params_t 
     if (lane < n) vmd_rmsf_commit(q.acc + 4 * ((size_t)sl.k0 + lane), acc);
 }
 
+// ------------------------------------------------------------------------------------------------ K12: hydrogen bonds
+
+// A bond is one (donor pair j, acceptor k) combination: D = don[j] with its explicit hydrogen H = hyd[j], A the acceptor behind list entry k.
+// Rule 1 (distance) is within()'s: wrapped positions, the SPEC S3 / S3t image, vmd_d2, vmd_within_hit with r_min = 0; e = (D - A) - shift is
+// the delta the test squares.  Rule 2 (identity, by atom index), rules 3 and 4 (the hydrogen's image, the angle) are vmd_hbond_rule below.
+// Every operation is fp32 and separately rounded (no fmaf here: the file is built with -ffp-contract=off).
+__device__ __forceinline__ float vmd_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+// u = -h points from H to D, v = -e - h from H to A: the D-H...A angle is at least angle_min (>= 90 degrees) iff its cosine is at most
+// cos(angle_min) <= 0, i.e. dot <= 0 and dot^2 >= c2 uu vv with c2 = cos^2(angle_min).  No root, no division, no acos.
+__device__ __forceinline__ bool vmd_hbond_angle(float c2, float hx, float hy, float hz, float ex, float ey, float ez) {
+    const float ux = -hx, uy = -hy, uz = -hz;
+    const float vx = -ex - hx, vy = -ey - hy, vz = -ez - hz;
+    const float uu = vmd_dot3(ux, uy, uz, ux, uy, uz), vv = vmd_dot3(vx, vy, vz, vx, vy, vz), dot = vmd_dot3(ux, uy, uz, vx, vy, vz);
+    return uu > 0.0f && vv > 0.0f && dot <= 0.0f && dot * dot >= c2 * (uu * vv);
+}
+
+// one donor pair as its lane holds it: the atoms, and h = the minimum image of (H - D) from the RAW frame (the image function of distance())
+struct vmd_hbond_pair_t { int d, h; float hx, hy, hz; };
+__device__ __forceinline__ vmd_hbond_pair_t vmd_hbond_pair(const vmd_box_t& bx, const float* fx, const float* fy, const float* fz, int d, int h) {
+    vmd_hbond_pair_t q;
+    q.d = d; q.h = h;
+    q.hx = fx[h] - fx[d]; q.hy = fy[h] - fy[d]; q.hz = fz[h] - fz[d];
+    vmd_mi3_rintf(bx, q.hx, q.hy, q.hz);
+    return q;
+}
+// rules 2 - 4 for a distance hit of the pair against acceptor atom `a` at delta e
+__device__ __forceinline__ bool vmd_hbond_rule(const vmd_hbond_pair_t& q, float c2, int a, float ex, float ey, float ez) {
+    return a != q.d && a != q.h && vmd_hbond_angle(c2, q.hx, q.hy, q.hz, ex, ey, ez);
+}
+
+// vmd_pair_d2_general's displacement before it is squared: (i - j) - shift, the shift of the SPEC S3 / S3t image
+__device__ __forceinline__ void vmd_pair_delta_general(const vmd_box_t& b, float xi, float yi, float zi, float xj, float yj, float zj,
+                                                       float& dx, float& dy, float& dz) {
+    if (b.tri) {
+        const float d0x = xi - xj, d0y = yi - yj, d0z = zi - zj;
+        float sx, sy, sz, shx, shy, shz;
+        vmd_frac(b, d0x, d0y, d0z, sx, sy, sz);
+        vmd_lattice_shift(b.Lx, b.Ly, b.Lz, b.xy, b.xz, b.yz, rintf(sx), rintf(sy), rintf(sz), shx, shy, shz);
+        dx = d0x - shx; dy = d0y - shy; dz = d0z - shz;
+        return;
+    }
+    dx = vmd_mi_cmp(xi - xj, b.Lx, 0.5f * b.Lx, b.px);
+    dy = vmd_mi_cmp(yi - yj, b.Ly, 0.5f * b.Ly, b.py);
+    dz = vmd_mi_cmp(zi - zj, b.Lz, 0.5f * b.Lz, b.pz);
+}
+
+__device__ __forceinline__ void vmd_atomic_add_u64(uint64_t* p, uint64_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
+// (the SIMT emulator under tests/emu runs one lane at a time and its header has no atomicMin: there the claim is the plain compare and
+// store its other atomics are)
+__device__ __forceinline__ void vmd_atomic_min_u32(uint32_t* p, uint32_t v) {
+#ifdef __HIPCC__
+    atomicMin(p, v);
+#else
+    if (v < *p) *p = v;
+#endif
+}
+
+// what a lane has found goes out the same way from the walk and from all pairs: the lanes' bond counts summed over the wave into ONE u32
+// atomic on the frame's count, one u64 atomic per lane with bonds into its donor row.  (The acceptor rows take one atomic per bond, where
+// the bond is found.)  Every lane of the wave calls it.
+__device__ __forceinline__ void vmd_hbond_commit(unsigned* frame_count, uint64_t* donor_row, unsigned n) {
+    if (n) vmd_atomic_add_u64(donor_row, n);
+    int tot = (int)n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += vmd_shfl_xor_i32(tot, o);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(frame_count, (unsigned)tot);
+}
+
+// The identity of a cell-sorted copy, recovered without touching the cell build: one lane per list entry t.  vmd_cell_of gives the entry's
+// cell and wrapped coordinates - the values the build binned and stored (k_within_atoms relies on the same fact) -, the lane scans that
+// cell's run of the sorted copy for slots whose three coordinates equal its own bit for bit and claims them with atomicMin (vmd_atomic_min_u32).  ident is
+// u32[B][nsel_pad], preset to 0xffffffff by the launcher.  DECISION(D-HB-COINCIDENT): entries that coincide bit for bit in a frame share
+// their slots, and every one of those slots answers as the LOWEST such entry; a slot left at 0xffffffff after the pass is a bug.
+struct vmd_sorted_atoms_params_t {
+    vmd_cells_params_t c;       // the selection as its cell build read it: raw frame, the GRID's boxes, pbc, index list, grid (no outputs)
+    const uint32_t* cell_start; const float* sorted;
+    uint32_t* ident; const uint32_t* skip;
+};
+__global__ __launch_bounds__(256) void k_sorted_atoms(vmd_sorted_atoms_params_t p) {
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the table it would read is void
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.c.nsel) return;
+    float xw, yw, zw;
+    const uint32_t cell = vmd_cell_of(p.c, b, t, xw, yw, zw);
+    const uint32_t* cs = p.cell_start + (size_t)b * (p.c.grid.ncell + 1);
+    const float* xr = p.sorted + (size_t)b * 3 * p.c.nsel_pad;
+    const float* yr = xr + p.c.nsel_pad;
+    const float* zr = yr + p.c.nsel_pad;
+    uint32_t* id = p.ident + (size_t)b * p.c.nsel_pad;
+    const int bx_ = __float_as_int(xw), by_ = __float_as_int(yw), bz_ = __float_as_int(zw);
+    uint32_t s0 = cs[cell], s1 = cs[cell + 1];
+    if (s1 > (uint32_t)p.c.nsel) s1 = (uint32_t)p.c.nsel;       // (a table is never trusted beyond the copy it indexes)
+    for (uint32_t s = s0; s < s1; ++s)
+        if (__float_as_int(xr[s]) == bx_ && __float_as_int(yr[s]) == by_ && __float_as_int(zr[s]) == bz_) vmd_atomic_min_u32(&id[s], (uint32_t)t);
+}
+
+// vmd_within_walk's sibling that does not leave at the first hit: the same pencils, images, windows and pair arithmetic, and
+// on_hit(slot, ex, ey, ez) for EVERY member of R at 0 <= d <= / < r_max, e = (atom - member) - shift.  A pair is met under one image only:
+// a grid exists only where the minimum image is unique for every hit (choose_grid), so the other images of a slot fail the distance.
+template <class OnHit>
+__device__ __forceinline__ void vmd_within_walk_all(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi, OnHit on_hit) {
+    for (int dz = -k.rz; dz <= k.rz; ++dz) {
+        int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
+        if (k.open_z && (qz < 0 || qz >= k.nz)) continue;
+        if (qz < 0) { qz += k.nz; sz = -k.Lz; nc = -1.0f; } else if (qz >= k.nz) { qz -= k.nz; sz = k.Lz; nc = 1.0f; }
+        for (int dy = -k.ry; dy <= k.ry; ++dy) {
+            int qy = py + dy; float sy = 0.0f, nb = 0.0f;
+            if (k.open_y && (qy < 0 || qy >= k.ny)) continue;
+            if (qy < 0) { qy += k.ny; sy = -k.Ly; nb = -1.0f; } else if (qy >= k.ny) { qy -= k.ny; sy = k.Ly; nb = 1.0f; }
+            const int qp = qz * k.ny + qy;
+            float offmin = 0.0f, offmax = 0.0f, rpad = k.rpad;
+            if (!k.tri && !k.open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
+                const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (k.Ly / (float)k.ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (k.Lz / (float)k.nz);
+                const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
+                const float rr = k.rpad * k.rpad - 0.998f * (gyy * gyy + gzz * gzz);
+                if (rr <= 0.0f) continue;
+                rpad = sqrtf(rr) * 1.0001f;
+            }
+            if (k.tri) {
+                const float y0 = k.txy * ((float)qy / (float)k.ny), y1 = k.txy * ((float)(qy + 1) / (float)k.ny);
+                const float z0 = k.txz * ((float)qz / (float)k.nz), z1 = k.txz * ((float)(qz + 1) / (float)k.nz);
+                offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
+                offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
+            }
+            for (int kx = -1; kx <= 1; ++kx) {
+                if (k.open_x && kx != 0) continue;
+                float sx = (float)kx * k.Lx, sy2 = sy, sz2 = sz;
+                if (k.tri) vmd_lattice_shift(k.Lx, k.Ly, k.Lz, k.txy, k.txz, k.tyz, (float)kx, nb, nc, sx, sy2, sz2);
+                const float lo = (xi - rpad) - sx - offmax - k.orgx - k.pad_open;
+                const float hi = (xi + rpad) - sx - offmin - k.orgx + k.pad_open;
+                if (hi < 0.0f || lo >= k.Lx) continue;
+                const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, k.inv_cx, k.nxf);
+                const int cb = hi >= k.Lx ? k.nxf - 1 : vmd_cell_coord(hi, k.inv_cx, k.nxf);
+                const unsigned ja = k.csr[qp * k.nxf + ca], jb = k.csr[qp * k.nxf + cb + 1];
+                for (unsigned j = ja; j < jb; ++j) {
+                    const float dx = (xi - k.xr[j]) - sx, dy_ = (yi - k.yr[j]) - sy2, dz_ = (zi - k.zr[j]) - sz2;
+                    if (vmd_within_hit(k.w, vmd_d2(dx, dy_, dz_))) on_hit(j, dx, dy_, dz_);
+                }
+            }
+        }
+    }
+}
+
+struct vmd_hbond_atoms_params_t {
+    vmd_cells_params_t c;       // the donors as a cell build would read them: raw frame, the GRID's boxes, pbc, the donor list, grid (no outputs)
+    vmd_within_walk_params_t k; // the cell-sorted copy of the acceptors
+    const float* fboxes;        // the frames' own cells: the hydrogen's image is taken in them (the grid's differ on open axes)
+    const int32_t* hyd; const int32_t* accl; int nacc;
+    const uint32_t* ident;      // k_sorted_atoms' table of the acceptor copy, u32[B][k.nref_pad]
+    float c2;
+    unsigned* count; uint64_t* acc;      // u32[B]; u64[nsel + nacc + 1]: donor rows, acceptor rows (the frames row is k_hbond_finish's)
+    const uint32_t* skip;
+};
+
+// The walk, one lane per donor pair j in list order; D's pencil as k_within_atoms derives a target's.  Every distance hit is put to rules
+// 2 - 4 (rule 4 first, see below).  Lanes of a wave are spatially unrelated, as in k_within_atoms: hits are few (about ten per donor at 3.5 A in
+// water) and are taken where they are found, without compaction.
+__global__ __launch_bounds__(256) void k_hbond_atoms(vmd_hbond_atoms_params_t p) {
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch, nothing may be added
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
+    unsigned n = 0;
+    if (t < p.c.nsel) {
+        float xi, yi, zi;
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
+        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        const float* fx = p.c.xyz + (size_t)b * p.c.frame_stride;
+        const vmd_hbond_pair_t q = vmd_hbond_pair(vmd_load_box(p.fboxes, b, p.c.pbc), fx, fx + p.c.row_stride, fx + 2 * p.c.row_stride,
+                                                  p.c.sel[t], p.hyd[t]);
+        const uint32_t* id = p.ident + (size_t)b * p.k.nref_pad;
+        uint64_t* acc_rows = p.acc + p.c.nsel;
+        const int nacc = p.nacc;
+        const int32_t* accl = p.accl;
+        const float c2 = p.c2;
+        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float ex, float ey, float ez) {
+            // the angle first: it needs no memory and drops all but a few per cent of the distance hits (the donor itself at d = 0 among
+            // them), so the two dependent loads of the identity are paid by what is nearly a bond.  The conjunction is the same.
+            if (!vmd_hbond_angle(c2, q.hx, q.hy, q.hz, ex, ey, ez)) return;
+            const uint32_t a = id[j];
+            if (a >= (uint32_t)nacc) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            const int aa = accl[a];
+            if (aa != q.d && aa != q.h) { vmd_atomic_add_u64(acc_rows + a, 1); n += 1; }
+        });
+    }
+    vmd_hbond_commit(p.count + b, p.acc + (t < p.c.nsel ? t : 0), n);
+}
+
+// D-HB-COINCIDENT for the all-pairs route, which has no sorted copy to ask: canon[b][k] = the lowest list entry whose wrapped coordinates in
+// frame b equal entry k's bit for bit (k itself where nothing coincides) - what k_sorted_atoms' table answers for k's slot.
+struct vmd_hbond_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc;
+    const int32_t* don; const int32_t* hyd; int npairs; const int32_t* accl; int nacc;
+    uint32_t* canon;            // u32[B][nacc]
+    vmd_within_test_t w; float c2;
+    unsigned* count; uint64_t* acc; const uint32_t* skip;
+    uint32_t* list; uint32_t list_cap; unsigned* list_count;      // LIST: u32[list_cap][2] = {pair j, acceptor list position}, the bonds found
+};
+__global__ __launch_bounds__(256) void k_hbond_canon(vmd_hbond_brute_params_t p) {
+    __shared__ int s_r[3][256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    float xi = 0.0f, yi = 0.0f, zi = 0.0f;
+    if (k < p.nacc) { const int a = p.accl[k]; vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi); }
+    const int bxi = __float_as_int(xi), byi = __float_as_int(yi), bzi = __float_as_int(zi);
+    int found = k;
+    const int last = blockIdx.x * 256 + 255 < p.nacc ? blockIdx.x * 256 + 255 : p.nacc - 1;       // the block's highest entry
+    for (int j0 = 0; j0 <= last; j0 += 256) {
+        __syncthreads();
+        const int jj0 = j0 + threadIdx.x;
+        if (jj0 < p.nacc) {
+            const int a = p.accl[jj0];
+            float x, y, z;
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], x, y, z);
+            s_r[0][threadIdx.x] = __float_as_int(x); s_r[1][threadIdx.x] = __float_as_int(y); s_r[2][threadIdx.x] = __float_as_int(z);
+        }
+        __syncthreads();
+        const int nj = p.nacc - j0 < 256 ? p.nacc - j0 : 256;
+        for (int jj = 0; jj < nj && j0 + jj < found; ++jj)
+            if (s_r[0][jj] == bxi && s_r[1][jj] == byi && s_r[2][jj] == bzi) found = j0 + jj;
+    }
+    if (k < p.nacc) p.canon[(size_t)b * p.nacc + k] = (uint32_t)found;
+}
+
+// All pairs from the raw frame: one lane per donor pair, the acceptors staged through an LDS tile like vmd_within_all_pairs, identity = the
+// list position (through canon).  The same rules, the same outputs as the walk.  LIST: the bonds go to a capped buffer through a counter
+// instead (vmd_eval_hbond_pairs), nothing is accumulated.
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_hbond_brute(vmd_hbond_brute_params_t p) {
+    __shared__ float s_r[3][256];
+    __shared__ uint32_t s_k[256];
+    __shared__ int s_a[256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const bool valid = t < p.npairs;
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    vmd_hbond_pair_t q{0, 0, 0.0f, 0.0f, 0.0f};
+    if (valid) {
+        q = vmd_hbond_pair(bx, fx, fy, fz, p.don[t], p.hyd[t]);
+        vmd_pair_coords(bx, fx[q.d], fy[q.d], fz[q.d], xi, yi, zi);
+    }
+    const uint32_t* canon = p.canon + (size_t)b * p.nacc;
+    unsigned n = 0;
+    for (int j0 = 0; j0 < p.nacc; j0 += 256) {
+        __syncthreads();
+        const int nj = p.nacc - j0 < 256 ? p.nacc - j0 : 256;
+        if ((int)threadIdx.x < nj) {
+            const int jj = threadIdx.x;
+            const int a = p.accl[j0 + jj];
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+            s_k[jj] = canon[j0 + jj];
+            s_a[jj] = p.accl[s_k[jj]];
+        }
+        __syncthreads();
+        if (valid)
+            for (int jj = 0; jj < nj; ++jj) {
+                float ex, ey, ez;
+                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
+                if (!vmd_within_hit(p.w, vmd_d2(ex, ey, ez)) || !vmd_hbond_rule(q, p.c2, s_a[jj], ex, ey, ez)) continue;
+                if (LIST) {
+                    const unsigned slot = atomicAdd(p.list_count, 1u);
+                    if (slot < p.list_cap) { p.list[2 * (size_t)slot] = (uint32_t)t; p.list[2 * (size_t)slot + 1] = (uint32_t)(j0 + jj); }
+                } else {
+                    vmd_atomic_add_u64(p.acc + p.npairs + s_k[jj], 1);
+                    n += 1;
+                }
+            }
+    }
+    if (!LIST) vmd_hbond_commit(p.count + b, p.acc + (valid ? t : 0), n);
+}
+
+// the launcher's finishing step, behind the last launch over a frame group: the counts as the temporal rows, the frames row bumped once per
+// frame - under the overflow flag like everything above
+__global__ __launch_bounds__(256) void k_hbond_finish(const unsigned* count, int B, float* out, uint64_t* frames_row, const uint32_t* skip) {
+    if (skip && *skip) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) out[i] = (float)count[i];
+    if (i == 0) *frames_row += (uint64_t)B;
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -4621,6 +4915,94 @@ extern "C" int vmd_hip_shell_compact(void* stream, const uint8_t* flags, const u
 extern "C" int vmd_hip_within_to_float(void* stream, const uint32_t* counts, int B, float* out, const uint32_t* skip_flag) {
     if (B <= 0) return 0;
     hipLaunchKernelGGL(k_within_to_float, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, counts, B, out, skip_flag);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K12: hydrogen bonds
+extern "C" int vmd_hip_sorted_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                    uint32_t pbc_flags, int B, const int32_t* sel, int nsel, const float* sorted, const uint32_t* cell_start,
+                                    int nsel_pad, vmd_grid_t grid, uint32_t* ident_out, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0 || nsel <= 0) return 0;
+    if (B > 65535 || !sel || !sorted || !cell_start || !ident_out || nsel_pad < nsel || grid.nxf <= 0 || grid.ny <= 0 || grid.nz <= 0 ||
+        grid.ncell != grid.nxf * grid.ny * grid.nz) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(ident_out, 0xff, (size_t)B * nsel_pad * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    vmd_sorted_atoms_params_t p{};
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
+    p.c.sel = sel; p.c.nsel = nsel; p.c.nsel_pad = nsel_pad; p.c.grid = grid;
+    p.cell_start = cell_start; p.sorted = sorted; p.ident = ident_out; p.skip = skip_flag;
+    hipLaunchKernelGGL(k_sorted_atoms, dim3((nsel + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+static bool vmd_hbond_args_ok(int B, const int32_t* don, const int32_t* hyd, int npairs, const int32_t* accl, int nacc, float r_da, float c2,
+                              const uint32_t* count_out, const uint64_t* acc) {
+    return B <= 65535 && don && hyd && npairs > 0 && accl && nacc > 0 && r_da > 0.0f && c2 >= 0.0f && c2 <= 1.0f && count_out && acc;
+}
+
+extern "C" int vmd_hip_hbond_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes,
+                                   const float* frame_boxes, uint32_t pbc_flags, int B, const int32_t* don, const int32_t* hyd, int npairs,
+                                   const int32_t* accl, int nacc, const float* sorted_acc, const uint32_t* cell_start_acc, int nacc_pad,
+                                   const uint32_t* ident, vmd_grid_t grid, float r_da, float c2, int closed, uint32_t* count_out,
+                                   uint64_t* acc, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    vmd_hbond_atoms_params_t p{};
+    if (!vmd_hbond_args_ok(B, don, hyd, npairs, accl, nacc, r_da, c2, count_out, acc) || !sorted_acc || !cell_start_acc || !ident ||
+        !grid_boxes || !frame_boxes || nacc_pad < nacc || grid.ncell != grid.nxf * grid.ny * grid.nz ||
+        !vmd_within_walk_fill(p.k, grid, sorted_acc, cell_start_acc, nacc_pad, 0.0f, r_da, closed)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
+    p.c.sel = don; p.c.nsel = npairs; p.c.nsel_pad = npairs; p.c.grid = grid;
+    p.fboxes = frame_boxes; p.hyd = hyd; p.accl = accl; p.nacc = nacc; p.ident = ident; p.c2 = c2;
+    p.count = count_out; p.acc = acc; p.skip = skip_flag;
+    hipLaunchKernelGGL(k_hbond_atoms, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+static int vmd_hbond_brute_launch(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                  uint32_t pbc_flags, int B, const int32_t* don, const int32_t* hyd, int npairs, const int32_t* accl, int nacc,
+                                  uint32_t* canon, float r_da, float c2, int closed, uint32_t* count_out, uint64_t* acc,
+                                  const uint32_t* skip_flag, uint32_t* list, uint32_t list_cap, uint32_t* list_count) {
+    hipStream_t s = (hipStream_t)stream;
+    vmd_hbond_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, don, hyd, npairs, accl, nacc, canon,
+                               vmd_make_within_test(0.0f, r_da, closed), c2, count_out, acc, skip_flag, list, list_cap, list_count};
+    hipLaunchKernelGGL(k_hbond_canon, dim3((nacc + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    if (list) hipLaunchKernelGGL(k_hbond_brute<true>, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_hbond_brute<false>, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_hbond_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                   uint32_t pbc_flags, int B, const int32_t* don, const int32_t* hyd, int npairs, const int32_t* accl, int nacc,
+                                   uint32_t* canon, float r_da, float c2, int closed, uint32_t* count_out, uint64_t* acc,
+                                   const uint32_t* skip_flag) {
+    if (B <= 0) return 0;
+    if (!vmd_hbond_args_ok(B, don, hyd, npairs, accl, nacc, r_da, c2, count_out, acc) || !canon || !boxes) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
+    return vmd_hbond_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, don, hyd, npairs, accl, nacc, canon, r_da, c2,
+                                  closed, count_out, acc, skip_flag, nullptr, 0, nullptr);
+}
+
+extern "C" int vmd_hip_hbond_list(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, const int32_t* don,
+                                  const int32_t* hyd, int npairs, const int32_t* accl, int nacc, uint32_t* canon, float r_da, float c2,
+                                  int closed, uint32_t* list, uint32_t list_cap, uint32_t* list_count) {
+    if (!don || !hyd || npairs <= 0 || !accl || nacc <= 0 || !(r_da > 0.0f) || !canon || !box || !list || !list_count)
+        return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(list_count, 0, sizeof(uint32_t), (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
+    return vmd_hbond_brute_launch(stream, xyz, 0, row_stride, box, pbc_flags, 1, don, hyd, npairs, accl, nacc, canon, r_da, c2, closed, nullptr,
+                                  nullptr, nullptr, list, list_cap, list_count);
+}
+
+extern "C" int vmd_hip_hbond_finish(void* stream, const uint32_t* counts, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag) {
+    if (B <= 0) return 0;
+    if (!counts || !out || !frames_row) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_hbond_finish, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, counts, B, out, frames_row, skip_flag);
     VMD_LAUNCH_CHECK();
     return 0;
 }

@@ -946,3 +946,44 @@ extern "C" size_t vmd_topology_backbone_oxygens(const vmd_topology_t* topology, 
 extern "C" const vmd_backbone_t* vmd_backbone_view(const vmd_backbone_owned_t* backbone) { return backbone ? &backbone->view : nullptr; }
 
 extern "C" void vmd_backbone_free(vmd_backbone_owned_t* backbone) { delete backbone; }
+
+// ---- hydrogen-bond sites from a topology and its bonds (DECISION D-HB-TOPOLOGY): elements only, no coordinates.  A donor pair
+// for every bond between an H and an N or O, the acceptors every N, O or F; both in ascending atom order.
+struct vmd_hbond_sites_owned_t {
+    std::vector<int32_t> donor, hydrogen, acceptor;
+    vmd_hbond_sites_t view;
+};
+
+extern "C" vmd_hbond_sites_owned_t* vmd_topology_hbond_sites(const vmd_topology_t* topology, const int32_t (*bonds)[2], size_t nbonds) {
+    if (!topology) { vmd_set_last_error("vmd_topology_hbond_sites: topology is NULL"); return nullptr; }
+    if (!bonds && nbonds) { vmd_set_last_error("vmd_topology_hbond_sites: bonds is NULL"); return nullptr; }
+    try {
+        const size_t n = topology->num_atoms;
+        std::vector<std::string> el(n);
+        for (size_t i = 0; i < n; ++i) el[i] = upper(topology->elements && topology->elements[i] ? topology->elements[i] : "");
+        auto hs = std::make_unique<vmd_hbond_sites_owned_t>();
+        std::vector<std::pair<int32_t, int32_t>> pairs;
+        for (size_t b = 0; b < nbonds; ++b) {
+            const int32_t i = bonds[b][0], j = bonds[b][1];
+            if (i < 0 || j < 0 || (size_t)i >= n || (size_t)j >= n) fail("bond %zu names atoms %d and %d (the topology has %zu atoms)", b, i, j, n);
+            for (int k = 0; k < 2; ++k) {
+                const int32_t h = k ? j : i, d = k ? i : j;
+                if (el[h] == "H" && (el[d] == "N" || el[d] == "O")) pairs.push_back({d, h});
+            }
+        }
+        std::sort(pairs.begin(), pairs.end());
+        pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());       // a bond listed twice is one pair
+        for (auto& q : pairs) { hs->donor.push_back(q.first); hs->hydrogen.push_back(q.second); }
+        for (size_t i = 0; i < n; ++i) if (el[i] == "N" || el[i] == "O" || el[i] == "F") hs->acceptor.push_back((int32_t)i);
+        hs->view.npairs = hs->donor.size(); hs->view.donor = hs->donor.data(); hs->view.hydrogen = hs->hydrogen.data();
+        hs->view.nacc = hs->acceptor.size(); hs->view.acceptor = hs->acceptor.data();
+        return hs.release();
+    } catch (const std::exception& e) {
+        vmd_set_last_error(e.what());
+        return nullptr;
+    }
+}
+
+extern "C" const vmd_hbond_sites_t* vmd_hbond_sites_view(const vmd_hbond_sites_owned_t* sites) { return sites ? &sites->view : nullptr; }
+
+extern "C" void vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites) { delete sites; }

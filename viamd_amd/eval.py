@@ -237,6 +237,22 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_rmsf_population(self.h, name.encode(), max(off.size, 1) - 1, xp,
                                                         off.ctypes.data_as(L.c_int32_p) if off.size else None))
 
+    def add_hbonds(self, names, donors, hydrogens, acceptors, r_da, angle_min_deg):
+        """Hydrogen bonds: names = (count per frame, occupancy record); pair j is the heavy atom donors[j] with its explicit
+        hydrogen hydrogens[j]; a bond is a (pair, acceptor) combination with d(D, A) within r_da and the D-H...A angle at least
+        angle_min_deg.  The record is u64 [npairs + nacc + 1]: per pair, per acceptor, the frames."""
+        names = list(names)
+        assert len(names) == 2, "hbonds defines two properties"
+        d_, dp = _idx(donors)
+        h_, hp = _idx(hydrogens)
+        a_, ap = _idx(acceptors)
+        if d_.size != h_.size:
+            raise ValueError("donors and hydrogens must list one atom per pair each")
+        sites = L.HbondSitesC(d_.size, dp, hp, a_.size, ap)
+        self._check(self.lib.vmd_ir_add_hbonds(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(sites), float(r_da),
+                                               float(angle_min_deg)))
+        self.hbond_pairs_of = dict(getattr(self, "hbond_pairs_of", {}), **{names[1]: int(d_.size)})
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -389,6 +405,15 @@ class PropertyDataView:
         if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
             raise VmdError(self._ev.lib.last_error())
         return self._arr(self.c.counts, self.c.dim[0] * 4, np.uint64).reshape(self.c.dim[0], 4)
+
+    @property
+    def hbond_accumulators(self):
+        """the record of a hydrogen-bond occupancy as uint64 [npairs + nacc + 1]: the bonds every pair donated, the bonds
+        every acceptor accepted, the frames accumulated"""
+        assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a hydrogen-bond occupancy record"
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
 
     @property
     def ss_classes(self):
@@ -609,6 +634,40 @@ class ScriptEval:
                                       C.byref(frames)):
             raise VmdError(self.lib.last_error())
         return rmsf, mean, int(frames.value)
+
+    def hbonds(self, name, npairs=None):
+        """a hydrogen-bond occupancy read from its record as it stands -> (donor_occ float64 [npairs], acc_occ float64
+        [nacc], frames).  npairs says where the record's donor rows end (None: what ScriptIR.add_hbonds noted for `name`)"""
+        if not self.lib.vmd_eval_hbonds(self.h, name.encode(), None, None, None):      # (the name and the form, before any size is believed)
+            raise VmdError(self.lib.last_error())
+        n = self.property_data(name).dim[0] - 1
+        if npairs is None:
+            npairs = getattr(self.ir, "hbond_pairs_of", {}).get(name)
+            if npairs is None:
+                raise VmdError(f"'{name}' was not defined by add_hbonds of this eval's ir: pass npairs")
+        nacc = n - int(npairs)
+        if nacc < 0:
+            raise ValueError("npairs exceeds the record")
+        don, acc = np.zeros(int(npairs), np.float64), np.zeros(nacc, np.float64)
+        frames = C.c_uint64(0)
+        if not self.lib.vmd_eval_hbonds(self.h, name.encode(), don.ctypes.data_as(L.c_double_p), acc.ctypes.data_as(L.c_double_p),
+                                        C.byref(frames)):
+            raise VmdError(self.lib.last_error())
+        return don, acc, int(frames.value)
+
+    def hbond_pairs(self, name, sys, traj, frame, cap=None):
+        """the bonds of one frame, on demand -> int32 [n, 3] of {donor, hydrogen, acceptor} atoms in ascending (pair index,
+        acceptor list position) order.  cap: room for that many (None: all of them, asked for twice at the most)"""
+        room = 1024 if cap is None else int(cap)
+        while True:
+            out = np.zeros((max(room, 1), 3), np.int32)
+            n = self.lib.vmd_eval_hbond_pairs(self.h, name.encode(), C.byref(sys.c) if sys is not None else None, traj.interface(),
+                                              int(frame), out.ctypes.data_as(L.c_int32_p), room)
+            if n == C.c_size_t(-1).value:
+                raise VmdError(self.lib.last_error())
+            if cap is not None or n <= room:
+                return out[:min(n, room)].copy()
+            room = int(n)
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""

@@ -921,6 +921,44 @@ def backbone_oxygens_from_topology(topo, bb):
     return o
 
 
+def hbond_sites_from_topology(topo, bonds):
+    """Hydrogen-bond sites for ScriptIR.add_hbonds (DECISION D-HB-TOPOLOGY; the twin of vmd_topology_hbond_sites): a donor
+    pair for every bond between an atom of element H and an atom of element N or O, the acceptors every atom of element N, O or F.  Both
+    lists in ascending atom order; elements only, no coordinates.  bonds: [nbonds, 2] atom indices.
+    Returns dict(donor, hydrogen, acceptor) of int32 arrays."""
+    el = [str(e).upper() for e in topo.elements]
+    pairs = set()
+    for i, j in np.asarray(bonds, np.int64).reshape(-1, 2):
+        for h, d in ((int(i), int(j)), (int(j), int(i))):
+            if el[h] == "H" and el[d] in ("N", "O"):
+                pairs.add((d, h))
+    pairs = sorted(pairs)
+    return dict(donor=np.array([p[0] for p in pairs], np.int32), hydrogen=np.array([p[1] for p in pairs], np.int32),
+                acceptor=np.array([i for i, e in enumerate(el) if e in ("N", "O", "F")], np.int32))
+
+
+def hbond_sites_from_topology_native(topo, bonds, lib=None):
+    """The same through the C ABI (vmd_topology_hbond_sites).  Raises ScriptError with the library's message."""
+    import ctypes as C
+    lib = lib or L.default_lib()
+    n = topo.num_atoms
+    el = (C.c_char_p * max(n, 1))(*[str(v).encode() for v in topo.elements])
+    tc = L.TopologyC(n, el, None, None, None, None)
+    b = np.ascontiguousarray(bonds, np.int32).reshape(-1, 2)
+    h = lib.vmd_topology_hbond_sites(C.byref(tc), b.ctypes.data_as(L.c_int32_p) if b.size else None, b.shape[0])
+    if not h:
+        raise ScriptError(lib.last_error())
+    try:
+        v = lib.vmd_hbond_sites_view(h).contents
+
+        def arr(ptr, count):
+            return np.ctypeslib.as_array(ptr, shape=(count,)).astype(np.int32).copy() if count else np.zeros(0, np.int32)
+
+        return dict(donor=arr(v.donor, int(v.npairs)), hydrogen=arr(v.hydrogen, int(v.npairs)), acceptor=arr(v.acceptor, int(v.nacc)))
+    finally:
+        lib.vmd_hbond_sites_free(h)
+
+
 def backbone_oxygens_from_topology_native(topo, bb, lib=None):
     """The same through the C ABI (vmd_topology_backbone_oxygens).  Raises ScriptError with the library's message."""
     import ctypes as C
