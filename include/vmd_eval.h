@@ -353,6 +353,33 @@ typedef struct vmd_hbond_sites_t {
     size_t nacc;    const int32_t *acceptor;
 } vmd_hbond_sites_t;
 bool vmd_ir_add_hbonds(vmd_script_ir_t* ir, const char* const names[2], const vmd_hbond_sites_t* sites, float r_da, float angle_min_deg);
+/* Solvent-accessible surface area by Shrake-Rupley (an entry point, no script syntax): per frame the area of the measured
+ * atoms, over the run the accessible points of every one of them.  sites: nmeas measured entries (atom, radius) whose area is reported and
+ * nenv environment entries (atom, radius) that occlude; the lists are independent, an atom in both is itself by index.  With
+ * R = radius + probe (one fp32 add per entry) and the npoints unit vectors u_k of vmd_sasa_points, fp32, every operation rounded on its own:
+ *   neighbour: environment entry j is a neighbour of measured entry i iff (1) the pair passes the distance test of within(r_cut, .),
+ *      r_cut = 2 max(R) over both lists - wrapped positions, the SPEC S3 image, spec_within_closed; e = (i - j) - shift is its delta, d2 the
+ *      value it compared -, (2) d2 < s s strictly, s = R_i + R_j, (3) j's atom is not i's atom;
+ *   point: point k of entry i is buried by neighbour j iff (u_kx e_x + u_ky e_y) + u_kz e_z < ((R_j R_j - R_i R_i) - d2) / (R_i + R_i);
+ *      n_i = the points buried by no neighbour;
+ *   area: w_i = llround(4 pi R_i^2 / npoints * 2^20) formed in double; the frame's total is the u64 sum of n_i w_i.
+ * Environment entries whose wrapped positions coincide bit for bit in a frame all answer as the lowest such entry, with its atom and radius.
+ * names[0]: TEMPORAL, dim = {num_frames, 1}, unit A^2: (float)(total * 2^-20) (follows the frame mask like a within count).
+ * names[1]: MAP (VMD_PROPERTY_FLAG_MAP) of u64 accumulators, dim = {nmeas + 1, 1}: row i the accessible points of measured entry i summed
+ * over all evaluated frames, the last row the frames accumulated.  Integer counts: the record is the same bit for bit however calls, batches
+ * and ranks arrive, and merges like every MAP; a frame evaluated twice without vmd_eval_clear_data counts twice.
+ * Errors (vmd_last_error): NULL arguments, nmeas == 0 or nenv == 0, negative indices, a radius not finite or <= 0, probe not finite or < 0,
+ * radius + probe > 8, npoints outside [1, 256], names already defined or equal to each other.  vmd_ir_geometry_atoms: measured, environment. */
+typedef struct vmd_sasa_sites_t {
+    size_t nmeas; const int32_t* measured; const float* measured_radius;
+    size_t nenv;  const int32_t* env;      const float* env_radius;
+} vmd_sasa_sites_t;
+#define VMD_SASA_MAX_POINTS 256
+bool vmd_ir_add_sasa(vmd_script_ir_t* ir, const char* const names[2], const vmd_sasa_sites_t* sites, float probe, uint32_t npoints);
+/* The point table the kernels read (D-SASA-POINTS): the golden-section spiral z = 1 - (2k + 1) / P, rho = sqrt(1 - z^2),
+ * phi = k pi (3 - sqrt 5), u = (rho cos phi, rho sin phi, z), formed in double and rounded once to fp32.  Writes the first `cap` points
+ * (out may be NULL with cap == 0) and returns npoints; 0 + vmd_last_error when npoints is outside [1, 256]. */
+size_t vmd_sasa_points(uint32_t npoints, float (*out)[3], size_t cap);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
@@ -401,6 +428,10 @@ typedef struct vmd_hbond_sites_owned_t vmd_hbond_sites_owned_t;
 vmd_hbond_sites_owned_t* vmd_topology_hbond_sites(const vmd_topology_t* topology, const int32_t (*bonds)[2], size_t nbonds);
 const vmd_hbond_sites_t* vmd_hbond_sites_view(const vmd_hbond_sites_owned_t* sites);
 void     vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites);
+/* Van der Waals radii from a topology's elements (DECISION D-SASA-RADII; Bondi, elements without regard to case): H 1.20, C 1.70, N 1.55,
+ * O 1.52, F 1.47, P 1.80, S 1.80, CL 1.75, BR 1.85, I 1.98, anything else 2.00.  Writes the first `cap` of them to `out` (NULL: count
+ * only) and returns num_atoms; 0 + vmd_last_error on a NULL topology. */
+size_t   vmd_topology_vdw_radii(const vmd_topology_t* topology, float* out, size_t cap);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
  * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of
@@ -584,6 +615,17 @@ bool vmd_eval_hbonds(vmd_script_eval_t* eval, const char* name, double* donor_oc
 #define VMD_HBOND_PAIRS_FAILED ((size_t)-1)
 size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
                             int32_t (*out)[3], size_t cap);
+
+/* The mean accessible area per measured entry (names[1] of vmd_ir_add_sasa) read from its record as it stands - partially
+ * evaluated or merged alike: mean_area double[nmeas], row i = count_i / frames * 4 pi R_i^2 / npoints formed in double; frames: the count;
+ * each may be NULL.  F == 0 answers zeros.  false + vmd_last_error: an unknown property, a property of another form. */
+bool vmd_eval_sasa(vmd_script_eval_t* eval, const char* name, double* mean_area, uint64_t* frames);
+/* The accessible points n_i of ONE frame, on demand (either name of the statement), under vmd_eval_hbond_pairs' contract: nothing
+ * accumulated is touched, it may be called while pool threads are inside vmd_eval_frame_range.  All pairs from the raw frame.  Returns
+ * nmeas and writes the first `cap` counts (counts may be NULL with cap == 0); VMD_SASA_ATOMS_FAILED + vmd_last_error on failure. */
+#define VMD_SASA_ATOMS_FAILED ((size_t)-1)
+size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                           uint32_t* counts, size_t cap);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

@@ -23,6 +23,7 @@
  *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
  *   vmd_hip_within_atoms_expr, vmd_hip_within_brute_expr, vmd_hip_shell_expr_finish  <- and / or / not over within() shells
  *   vmd_hip_sorted_atoms, vmd_hip_hbond_*  <- hydrogen bonds
+ *   vmd_hip_sasa_*  <- solvent-accessible surface area
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
 #ifndef VMD_HIP_H
@@ -343,6 +344,34 @@ int vmd_hip_hbond_list(void* stream, const float* xyz, size_t row_stride, const 
                        const int32_t* hyd, int npairs, const int32_t* accl, int nacc, uint32_t* canon, float r_da, float c2, int closed,
                        uint32_t* list, uint32_t list_cap, uint32_t* list_count);
 int vmd_hip_hbond_finish(void* stream, const uint32_t* counts, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag);
+
+/* K13: solvent-accessible surface area by Shrake-Rupley, DESIGN 1.15.  Measured entry i (atom meas[i], R_i = r_meas[i]) carries the npoints
+ * points R_i u_k of `points` f32[npoints][3] (1 <= npoints <= 256); n_i = the points inside no neighbour's sphere.  Environment entry j
+ * (atom envl[j], R_j = r_env[j]; entries whose wrapped coordinates coincide bit for bit answer as the lowest of them, with its atom and its
+ * R) is a neighbour iff 0 <= d < r_cut (closed != 0: <= r_cut; the pair distance of K6, e its delta, d2 the value it compared),
+ * d2 < (R_i + R_j)^2 and its atom is not i's; it buries point k iff (u_kx e_x + u_ky e_y) + u_kz e_z < ((R_j R_j - R_i R_i) - d2) / (R_i + R_i).
+ * fp32, every operation separately rounded.  rmax_env >= every r_env[j]; r_cut >= R_i + R_j for every pair.
+ * Outputs: total_out u64[B] (zeroed by the call) = sum of n_i weight[i]; acc u64[nmeas + 1], ADDED to: row i += n_i.  Nothing happens when
+ * *skip_flag != 0.  B <= 65535.
+ *   vmd_hip_sasa_atoms   the cell walk of K8 over the cell-sorted copy of the environment (ident: vmd_hip_sorted_atoms' table of it), one
+ *                        lane per measured entry
+ *   vmd_hip_sasa_brute   all pairs from the raw frame (any cell, any cutoff); canon: scratch, u32[B][nenv]
+ *   vmd_hip_sasa_list    ONE frame by all pairs: counts_out u32[nmeas] = n_i; nothing is accumulated
+ *   vmd_hip_sasa_finish  out[b] = (float)(totals[b] * 2^-20), *frames_row += B */
+#define VMD_SASA_POINTS_MAX 256
+int vmd_hip_sasa_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes, uint32_t pbc_flags,
+                       int B, const int32_t* meas, int nmeas, const int32_t* envl, int nenv, const float* sorted_env,
+                       const uint32_t* cell_start_env, int nenv_pad, const uint32_t* ident, vmd_grid_t grid, const float* r_meas,
+                       const float* r_env, float rmax_env, const uint32_t* weight, const float* points, int npoints, float r_cut, int closed,
+                       uint64_t* total_out, uint64_t* acc, const uint32_t* skip_flag);
+int vmd_hip_sasa_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags, int B,
+                       const int32_t* meas, int nmeas, const int32_t* envl, int nenv, uint32_t* canon, const float* r_meas, const float* r_env,
+                       float rmax_env, const uint32_t* weight, const float* points, int npoints, float r_cut, int closed, uint64_t* total_out,
+                       uint64_t* acc, const uint32_t* skip_flag);
+int vmd_hip_sasa_list(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, const int32_t* meas, int nmeas,
+                      const int32_t* envl, int nenv, uint32_t* canon, const float* r_meas, const float* r_env, float rmax_env,
+                      const float* points, int npoints, float r_cut, int closed, uint32_t* counts_out);
+int vmd_hip_sasa_finish(void* stream, const uint64_t* totals, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

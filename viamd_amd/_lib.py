@@ -83,6 +83,11 @@ class HbondSitesC(C.Structure):          # vmd_hbond_sites_t (include/vmd_eval.h
                 ("nacc", C.c_size_t), ("acceptor", C.POINTER(C.c_int32))]
 
 
+class SasaSitesC(C.Structure):           # vmd_sasa_sites_t (include/vmd_eval.h)
+    _fields_ = [("nmeas", C.c_size_t), ("measured", C.POINTER(C.c_int32)), ("measured_radius", C.POINTER(C.c_float)),
+                ("nenv", C.c_size_t), ("env", C.POINTER(C.c_int32)), ("env_radius", C.POINTER(C.c_float))]
+
+
 class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
     _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
 
@@ -193,6 +198,12 @@ SIGNATURES = [
     ("vmd_topology_hbond_sites", _vp, [C.POINTER(TopologyC), c_int32_p, C.c_size_t]),
     ("vmd_hbond_sites_view", C.POINTER(HbondSitesC), [_vp]),
     ("vmd_hbond_sites_free", None, [_vp]),
+    ("vmd_ir_add_sasa", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(SasaSitesC), C.c_float, C.c_uint32]),
+    ("vmd_sasa_points", C.c_size_t, [C.c_uint32, c_float_p, C.c_size_t]),
+    ("vmd_eval_sasa", C.c_bool, [_vp, C.c_char_p, c_double_p, c_uint64_p]),
+    ("vmd_eval_sasa_atoms", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, C.POINTER(C.c_uint32),
+                                         C.c_size_t]),
+    ("vmd_topology_vdw_radii", C.c_size_t, [C.POINTER(TopologyC), c_float_p, C.c_size_t]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
@@ -406,6 +417,13 @@ SIGNATURES = [
     ("vmd_hip_hbond_list", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_float,
                                      C.c_int, _vp, C.c_uint32, _vp]),
     ("vmd_hip_hbond_finish", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_sasa_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp,
+                                     C.c_int, _vp, Grid, _vp, _vp, C.c_float, _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_sasa_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
+                                     C.c_float, _vp, _vp, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_sasa_list", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_float, _vp,
+                                    C.c_int, C.c_float, C.c_int, _vp]),
+    ("vmd_hip_sasa_finish", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

@@ -231,6 +231,19 @@ void build_hbond_plan(vmd_script_eval_t* e) {
     }
 }
 
+// accessible area: the environment becomes an interned selection, shared like the acceptors of 1.14; the measured entries are
+// walked in list order and are never sorted (their selection only says how many lanes the grid is chosen for)
+void build_sasa_plan(vmd_script_eval_t* e) {
+    e->sasa_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        if (p->prop.form != Form::SASA_AREA) continue;
+        p->sel_a = intern_selection(e, p->prop.a);
+        p->sel_b = intern_selection(e, p->prop.b);
+        e->sasa_props.push_back((int)i);
+    }
+}
+
 uint32_t shell_expr_live(uint32_t truth, const std::vector<int>& order, size_t pos) {
     uint32_t done = 0, later = 0;
     for (size_t k = 0; k < order.size(); ++k) { if (k < pos) done |= 1u << order[k]; else if (k > pos) later |= 1u << order[k]; }
@@ -366,7 +379,12 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         case Form::SS_CLASS: st->dist_P = p.a.size(); aggregate = false; break;
         case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
         case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
-        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: break;
+        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::SASA_AREA: break;
+        case Form::SASA_OCC:
+            // one u64 word per measured entry and the frame count; the float view is the words as numbers, as a map's
+            pinned_views(p.K + 1);
+            st->data.dim[0] = (int32_t)(p.K + 1); st->data.dim[1] = 1; st->data.dim[2] = st->data.dim[3] = 0;
+            break;
         case Form::HBOND_OCC:
             // one u64 word per donor pair, per acceptor, and the frame count; the float view is the words as numbers, as a map's
             pinned_views(p.K + p.m + 1);
@@ -416,6 +434,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     build_rdf_plan(e.get());
     build_within_plan(e.get());
     build_hbond_plan(e.get());
+    build_sasa_plan(e.get());
     build_expr_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
@@ -802,7 +821,9 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
             // a voxel receives at most one count per (frame, structure, target atom), a bin of a map one per (frame, segment)
             if (p->prop.counts_view()) {
                 // (a donor row at most one count per acceptor and frame, an acceptor row one per pair)
-                const long double per_frame = p->prop.form == Form::HBOND_OCC ? (long double)std::max(p->prop.K, p->prop.m)
+                // (a row at most npoints per frame)
+                const long double per_frame = p->prop.form == Form::SASA_OCC ? (long double)p->prop.m
+                        : p->prop.form == Form::HBOND_OCC ? (long double)std::max(p->prop.K, p->prop.m)
                         : (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
                 const long double b = (long double)eval->num_frames * per_frame;
                 v.count_bound = b < 1.8e19L ? (uint64_t)b : 0;
@@ -1005,6 +1026,80 @@ extern "C" size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name
     return found;
 }
 
+// ---- the mean accessible area per measured entry read from its record: count / frames * 4 pi R^2 / npoints in double.
+// Whatever the record holds - a partial evaluation, a merged one - is what is read; under the eval's mutex, touching nothing it keeps.
+extern "C" bool vmd_eval_sasa(vmd_script_eval_t* eval, const char* name, double* mean_area, uint64_t* frames) {
+    if (!eval || !name) return vmd_fail("vmd_eval_sasa: NULL argument");
+    size_t pi = eval->props.size();
+    for (size_t i = 0; i < eval->props.size(); ++i) if (eval->props[i]->prop.name == name) pi = i;
+    if (pi == eval->props.size()) return vmd_fail("unknown property '%s'", name);
+    PropState* p = eval->props[pi].get();
+    if (p->prop.form != Form::SASA_OCC || pi == 0 || eval->props[pi - 1]->prop.form != Form::SASA_AREA)
+        return vmd_fail("'%s' is not a record of accessible surface points", name);
+    if (!mean_area && !frames) return true;        // (asked for the form alone)
+    const Property& d = eval->props[pi - 1]->prop;
+    const size_t nmeas = p->prop.K;
+    std::vector<uint64_t> acc(p->ncounts);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        HIP_OK(hipSetDevice(eval->device));
+        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
+        HIP_OK(hipStreamSynchronize(eval->stream));
+    }
+    const uint64_t F = acc[nmeas];
+    if (frames) *frames = F;
+    if (mean_area)
+        for (size_t i = 0; i < nmeas; ++i) {
+            const double R = (double)(d.sasa_ra[i] + d.sasa_probe);
+            mean_area[i] = F ? (double)acc[i] / (double)F * (4.0 * M_PI * R * R) / (double)d.sasa_npoints : 0.0;
+        }
+    return true;
+}
+
+// The accessible points of one frame.  One frame on demand, as vmd_eval_hbond_pairs: all pairs from the raw frame.  Nothing the
+// evaluation keeps is touched: canon and counts live in one buffer of the eval that only this call uses (kept between calls).
+extern "C" size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                                      uint32_t* counts, size_t cap) {
+    const size_t failed = VMD_SASA_ATOMS_FAILED;
+    if (!eval || !traj || !name || (!counts && cap)) { vmd_fail("vmd_eval_sasa_atoms: NULL argument"); return failed; }
+    vmd_script_eval_t* e = eval;
+    size_t pi = e->props.size();
+    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
+    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return failed; }
+    if (e->props[pi]->prop.form == Form::SASA_OCC && pi > 0) pi -= 1;          // the record names the statement as well as its area
+    PropState* p = e->props[pi].get();
+    if (p->prop.form != Form::SASA_AREA) { vmd_fail("'%s' is not a sasa property", name); return failed; }
+    if (frame >= e->num_frames) { vmd_fail("vmd_eval_sasa_atoms: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
+    const Property& d = p->prop;
+    const size_t nmeas = d.a.size(), nenv = d.b.size();
+    std::vector<uint32_t> got(nmeas);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
+        const size_t num_atoms = traj->num_atoms(traj->inst);
+        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
+        auto run = [&]() -> bool {
+            vmd_device_view_t view;
+            memset(&view, 0, sizeof(view));
+            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
+            BatchSrc src;
+            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+            if (!e->d_one_sasa.ensure(nenv + nmeas)) return false;
+            uint32_t* canon = e->d_one_sasa.p;
+            uint32_t* dn = canon + nenv;
+            KRN_OK(vmd_hip_sasa_list(e->stream, src.base, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), p->d_a.p, (int)nmeas,
+                    p->d_b.p, (int)nenv, canon, p->d_sasa_ra.p, p->d_sasa_rb.p, p->sasa_rmax_env, p->d_sasa_pts.p, (int)d.sasa_npoints, d.rmax,
+                    e->spec.within_closed ? 1 : 0, dn));
+            HIP_OK(hipMemcpyAsync(got.data(), dn, nmeas * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+            HIP_OK(hipStreamSynchronize(e->stream));
+            return true;
+        };
+        if (!run()) return failed;
+    }
+    for (size_t i = 0; i < nmeas && i < cap; ++i) counts[i] = got[i];
+    return nmeas;
+}
+
 // ---- the hot call -----------------------------------------------------------------------------------------------
 bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_atoms) {
     for (auto& s : e->sels) {
@@ -1021,7 +1116,25 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
         };
         std::vector<float> tmp;
         switch (d.form) {
-        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: break;      // the sets of an rdf are interned selections; a map, the populations and an occupancy have none
+        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC: break;      // the sets of an rdf are interned selections; a map, the populations and an occupancy have none
+        case Form::SASA_AREA: {
+            // both lists in list order, R = radius + probe (one fp32 add per entry), the weights
+            // w_i = llround(4 pi R_i^2 / P * 2^20) formed in double, and the point table vmd_sasa_points hands out
+            std::vector<float> ra(d.a.size()), rb(d.b.size()), pts(3 * (size_t)d.sasa_npoints);
+            std::vector<uint32_t> w(d.a.size());
+            float rmax_env = 0.0f;
+            for (size_t i = 0; i < ra.size(); ++i) {
+                ra[i] = d.sasa_ra[i] + d.sasa_probe;
+                w[i] = (uint32_t)std::llround(4.0 * M_PI * (double)ra[i] * (double)ra[i] / (double)d.sasa_npoints * 1048576.0);
+            }
+            for (size_t j = 0; j < rb.size(); ++j) { rb[j] = d.sasa_rb[j] + d.sasa_probe; rmax_env = std::max(rmax_env, rb[j]); }
+            p->sasa_rmax_env = rmax_env;
+            if (vmd_sasa_points(d.sasa_npoints, (float(*)[3])pts.data(), d.sasa_npoints) != d.sasa_npoints) return false;
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_b.upload(d.b.data(), d.b.size(), e->stream) ||
+                !p->d_sasa_ra.upload(ra.data(), ra.size(), e->stream) || !p->d_sasa_rb.upload(rb.data(), rb.size(), e->stream) ||
+                !p->d_sasa_w.upload(w.data(), w.size(), e->stream) || !p->d_sasa_pts.upload(pts.data(), pts.size(), e->stream)) return false;
+            break;
+        }
         case Form::HBOND_COUNT:
             // the donors, their hydrogens, the acceptors in list order (the acceptors are an interned selection as well)
             if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_c.upload(d.c.data(), d.c.size(), e->stream) ||

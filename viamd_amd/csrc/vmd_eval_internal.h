@@ -396,6 +396,11 @@ enum class Form : int {
     // hydrogens (pair j = a[j], c[j]), b = acceptors, rmax = r_da, hb_angle / hb_c2 - has one value per frame; the occupancy behind it
     // (K = the pairs, m = the acceptors) is a MAP-class record of u64 accumulators, [K + m + 1], that the count's launch adds to
     HBOND_COUNT, HBOND_OCC,
+    // `{area, points} = sasa(sites, probe, npoints)`: two descriptors in a row.  The area - a = the measured atoms, b = the
+    // environment, sasa_ra / sasa_rb their radii as given, sasa_probe, sasa_npoints; rmax = r_cut = 2 max(radius + probe) - has one value
+    // per frame; the record behind it (K = the measured entries, m = npoints) is a MAP-class record of u64 accumulators, [K + 1], that the
+    // area's launch adds to
+    SASA_AREA, SASA_OCC,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -428,9 +433,12 @@ constexpr FormFacts kFormFacts[] = {
     /* RMSF        */ {ResultClass::MAP,          1, "rmsf",          {"", "\xC3\x85"}, nullptr, false, 13},    // Angstrom in 2^-24 quanta
     /* HBOND_COUNT */ {ResultClass::TEMPORAL,     0, "hbonds",        {"", ""},         nullptr, true,  14},    // counts
     /* HBOND_OCC   */ {ResultClass::MAP,          0, "hbonds",        {"", ""},         nullptr, true,  15},
+    /* SASA_AREA   */ {ResultClass::TEMPORAL,     0, "sasa",          {"", "\xC3\x85\xC2\xB2"}, nullptr, true, 16},  // square Angstrom
+    /* SASA_OCC    */ {ResultClass::MAP,          0, "sasa",          {"", ""},         nullptr, true,  17},
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::HBOND_OCC + 1, "one row of kFormFacts per Form");
-static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES, "the kernels' limits are the interface's");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::SASA_OCC + 1, "one row of kFormFacts per Form");
+static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES && VMD_SASA_MAX_POINTS == VMD_SASA_POINTS_MAX,
+              "the kernels' limits are the interface's");
 
 struct Property {
     std::string name;
@@ -461,6 +469,9 @@ struct Property {
     std::vector<uint8_t> rama_class, rama_link;     // RAMA_TABLE: class 0..3 / 255; bit 0 has predecessor, bit 1 has successor
     std::vector<int32_t> ss_o;                      // SS_CLASS: the carbonyl oxygen of every segment, -1 = none
     float hb_angle = 0.0f, hb_c2 = 0.0f;            // HBOND_COUNT: angle_min in degrees as given, and fl(cos^2) of it formed in double
+    std::vector<float> sasa_ra, sasa_rb;            // SASA_AREA: the radii of a and b as given; the probe; the points per sphere
+    float sasa_probe = 0.0f;
+    uint32_t sasa_npoints = 0;
     bool is_expr_sdf() const { return form == Form::SDF && !expr_terms.empty(); }
     bool behind_cells() const { return facts().behind_cells || is_shell_sdf() || is_expr_sdf(); }     // launch_rdf launches it, not launch_property
 };
@@ -628,6 +639,13 @@ struct PropState {
     // hydrogen bonds, the count: sel_b is the interned acceptor selection; d_a / d_c / d_b the donor, hydrogen and acceptor
     // lists; the identity table of the acceptors' cell-sorted copy (or the all-pairs route's canonical entries) and the batch's counts
     DevBuf<uint32_t> d_hb_ident, d_hb_count;
+    // accessible area, the area: sel_a / sel_b the interned measured and environment selections; d_a / d_b their lists,
+    // d_sasa_ra / d_sasa_rb R = radius + probe per entry, d_sasa_w the weights w_i, d_sasa_pts the point table; the identity table goes to
+    // d_hb_ident; the batch's u64 totals
+    DevBuf<float> d_sasa_ra, d_sasa_rb, d_sasa_pts;
+    DevBuf<uint32_t> d_sasa_w;
+    DevBuf<uint64_t> d_sasa_total;
+    float sasa_rmax_env = 0.0f;
     // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
@@ -856,6 +874,8 @@ struct vmd_script_eval_t {
     // after another on the eval's stream), and the bound on them (option ss_scratch_bytes, read at creation)
     DevBuf<uint64_t> d_ss_scratch;
     size_t ss_scratch_bytes = 0;
+    DevBuf<uint32_t> d_one_sasa;                        // vmd_eval_sasa_atoms: one frame's canonical entries and its point counts
+    std::vector<int> sasa_props;                        // indices into props of the accessible areas: behind the cell builds too
     std::vector<int> hbond_props;                       // indices into props of the hydrogen-bond counts: behind the cell builds too
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
@@ -952,6 +972,7 @@ void build_rdf_plan(vmd_script_eval_t* e);
 void build_within_plan(vmd_script_eval_t* e);
 
 void build_hbond_plan(vmd_script_eval_t* e);
+void build_sasa_plan(vmd_script_eval_t* e);
 void build_expr_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
@@ -1093,6 +1114,7 @@ struct RangeRun {
     bool forked = false;                // pair_stream holds launches the eval's stream has not waited for
     size_t row = 0;                     // next scratch row of d_pass
     std::vector<RdfCommit> commits;
+    std::vector<int> sasa_route;        // build_sasa_cells' answer per sasa statement of the batch: 1 the walk, 0 all pairs
 
     RawSlot* slot_of(size_t bi) const { return raw_ring ? &e->raw_slots[bi % vmd_script_eval_t::kRawSlots] : nullptr; }
     Stage& stage_of(size_t bi) const { return e->stages[bi % (stage_ahead + 1)]; }
@@ -1127,7 +1149,11 @@ struct RangeRun {
     bool launch_within_counts(BatchCtx& c);
     bool launch_shell_masks(BatchCtx& c);
     bool launch_shell_sdfs(BatchCtx& c);
+    bool ident_routes(BatchCtx& c, const std::vector<int>& props, std::vector<int>* route);
+    bool ident_table(BatchCtx& c, PropState* p, int route, int* have_grid, vmd_grid_t* grid, const float** d_gb);
     bool launch_hbonds(BatchCtx& c);
+    bool build_sasa_cells(BatchCtx& c);
+    bool launch_sasa(BatchCtx& c);
     bool launch_rdf(BatchCtx& c);
     bool launch_shell_exprs(BatchCtx& c);
     bool launch_expr_sdfs(BatchCtx& c);

@@ -49,6 +49,9 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         case Form::SS_POP: break;                                            // counted by its table's launch
         case Form::HBOND_COUNT: w += 2 * (uint64_t)p.a.size() + 2 * (uint64_t)p.b.size(); break;     // a neighbour query per pair (D, H), the acceptors sorted and identified
         case Form::HBOND_OCC: break;                                         // added to by its count's launch
+        // a neighbour query per measured entry, npoints bits to keep per entry (in units of 32), the environment sorted and identified
+        case Form::SASA_AREA: w += (uint64_t)p.a.size() * (1 + (p.sasa_npoints + 31) / 32) + 2 * (uint64_t)p.b.size(); break;
+        case Form::SASA_OCC: break;                                          // added to by its area's launch
         }
     }
     return w;
@@ -449,6 +452,56 @@ extern "C" bool vmd_ir_add_hbonds(vmd_script_ir_t* ir, const char* const names[2
     return commit(ir, tp, 2);
 }
 
+// D-SASA-POINTS: the golden-section spiral, formed in double, rounded once to fp32.  The evaluator uploads what this function
+// hands out; a restatement takes its points from here, because libm's last bit is nobody's contract.
+extern "C" size_t vmd_sasa_points(uint32_t npoints, float (*out)[3], size_t cap) {
+    if (npoints < 1 || npoints > VMD_SASA_MAX_POINTS) { vmd_fail("sasa points per sphere must lie in [1, %d]", VMD_SASA_MAX_POINTS); return 0; }
+    if (!out && cap) { vmd_fail("vmd_sasa_points: out is NULL"); return 0; }
+    const double golden = M_PI * (3.0 - std::sqrt(5.0));
+    for (uint32_t k = 0; k < npoints && k < cap; ++k) {
+        const double z = 1.0 - (2.0 * (double)k + 1.0) / (double)npoints;
+        const double rho = std::sqrt(1.0 - z * z), phi = (double)k * golden;
+        out[k][0] = (float)(rho * std::cos(phi)); out[k][1] = (float)(rho * std::sin(phi)); out[k][2] = (float)z;
+    }
+    return npoints;
+}
+
+// `{area, points} = sasa(sites, probe, npoints)`: the per-frame area and the record of accessible points, two descriptors in a row
+extern "C" bool vmd_ir_add_sasa(vmd_script_ir_t* ir, const char* const names[2], const vmd_sasa_sites_t* sites, float probe, uint32_t npoints) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names || !sites) return vmd_fail("sasa needs two property names and the sites");
+    if (!names_ok(ir, names, 2)) return false;
+    if (sites->nmeas == 0 || !sites->measured || !sites->measured_radius) return vmd_fail("sasa measured list is empty");
+    if (sites->nenv == 0 || !sites->env || !sites->env_radius) return vmd_fail("sasa environment list is empty");
+    if (!idx_ok(sites->measured, sites->nmeas, "sasa measured list") || !idx_ok(sites->env, sites->nenv, "sasa environment list")) return false;
+    if (sites->nmeas >= kMaxSet || sites->nenv > kMaxSet) return vmd_fail("sasa set too large");
+    if (!std::isfinite(probe) || !(probe >= 0.0f)) return vmd_fail("sasa probe radius must be finite and not negative");
+    if (npoints < 1 || npoints > VMD_SASA_MAX_POINTS) return vmd_fail("sasa points per sphere must lie in [1, %d]", VMD_SASA_MAX_POINTS);
+    float rmax = 0.0f;
+    for (int side = 0; side < 2; ++side) {
+        const float* r = side ? sites->env_radius : sites->measured_radius;
+        const size_t n = side ? sites->nenv : sites->nmeas;
+        for (size_t i = 0; i < n; ++i) {
+            if (!std::isfinite(r[i]) || !(r[i] > 0.0f))
+                return vmd_fail("sasa %s radius %zu must be finite and positive", side ? "environment" : "measured", i);
+            const float R = r[i] + probe;
+            // (keeps the point weight in 32 bits and the cutoff at most 16 A)
+            if (!(R <= 8.0f)) return vmd_fail("sasa %s radius %zu plus the probe exceeds 8", side ? "environment" : "measured", i);
+            rmax = std::max(rmax, R);
+        }
+    }
+    Property t = make_property(Form::SASA_AREA, names[0]);
+    t.a.assign(sites->measured, sites->measured + sites->nmeas); t.b.assign(sites->env, sites->env + sites->nenv);
+    t.aoff = {0, (int32_t)sites->nmeas}; t.boff = {0, (int32_t)sites->nenv};
+    t.sasa_ra.assign(sites->measured_radius, sites->measured_radius + sites->nmeas);
+    t.sasa_rb.assign(sites->env_radius, sites->env_radius + sites->nenv);
+    t.sasa_probe = probe; t.sasa_npoints = npoints;
+    t.rmin = 0.0f; t.rmax = rmax + rmax;            // r_cut = 2 max(R): exact in fp32
+    Property tp[2] = {std::move(t), make_property(Form::SASA_OCC, names[1])};
+    tp[1].K = sites->nmeas; tp[1].m = npoints;
+    return commit(ir, tp, 2);
+}
+
 // what vmd_ir_geometry_atoms has counted and written so far
 struct AtomSink {
     int32_t* out; size_t cap, n = 0;
@@ -471,7 +524,12 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         };
         size_t c0 = 0, c1 = 0;
         switch (p.form) {
-        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: return 0;
+        case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC:
+            return 0;
+        case Form::SASA_AREA:       // the measured atoms, then the environment (one context)
+            if (context > 0) return 0;
+            s.put(p.a); s.put(p.b);
+            return s.n;
         case Form::HBOND_COUNT:     // the donors, then their hydrogens, then the acceptors (one context)
             if (context > 0) return 0;
             s.put(p.a); s.put(p.c); s.put(p.b);
@@ -538,6 +596,11 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
         case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: case Form::HBOND_OCC: break;
         case Form::HBOND_COUNT: h = fnv1a(h, &p.hb_angle, sizeof(float)); break;      // (the hydrogens are c, hashed above)
+        case Form::SASA_OCC: break;
+        case Form::SASA_AREA:                                           // (the lists are a and b, boff says where a's radii end)
+            h = fnv1a(h, &p.sasa_probe, sizeof(float)); h = fnv1a(h, &p.sasa_npoints, sizeof(uint32_t));
+            h = fnv1a(h, p.sasa_ra.data(), p.sasa_ra.size() * sizeof(float)); h = fnv1a(h, p.sasa_rb.data(), p.sasa_rb.size() * sizeof(float));
+            break;
         case Form::SS_CLASS:                                            // 
             h = fnv1a(h, p.rama_class.data(), p.rama_class.size()); h = fnv1a(h, p.ss_o.data(), p.ss_o.size() * sizeof(int32_t));
             break;

@@ -343,16 +343,48 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
 // the walk - per sub, so that a frame block's bonds land in its own partial.  A copy that a later statement's build has re-sorted on
 // another grid is not built a second time (that would be a cell build behind an accumulation): that statement takes all pairs for this
 // batch, which answers the same bit for bit.
-bool RangeRun::launch_hbonds(BatchCtx& c) {
-    const int closed = e->spec.within_closed ? 1 : 0;
-    std::vector<int> route(e->hbond_props.size(), 0);
-    for (size_t i = 0; i < e->hbond_props.size(); ++i) {
-        PropState* p = e->props[e->hbond_props[i]].get();
+// What the two kinds that add to a record with atomics - hydrogen bonds, accessible area (1.15) - share.  ident_routes: every statement's
+// own cell build (sel_a in the lanes, sel_b alone sorted, the radius in rmax) -> per statement 1 the walk, 0 all pairs.
+bool RangeRun::ident_routes(BatchCtx& c, const std::vector<int>& props, std::vector<int>* route) {
+    route->assign(props.size(), 0);
+    for (size_t i = 0; i < props.size(); ++i) {
+        PropState* p = e->props[props[i]].get();
         vmd_grid_t grid;
         const float* d_gb = nullptr;
-        route[i] = within_route(c, e->sels[p->sel_a].get(), e->sels[p->sel_b].get(), p->prop.rmax, true, &grid, &d_gb);
-        if (route[i] < 0) return false;
+        (*route)[i] = within_route(c, e->sels[p->sel_a].get(), e->sels[p->sel_b].get(), p->prop.rmax, true, &grid, &d_gb);
+        if ((*route)[i] < 0) return false;
     }
+    return true;
+}
+
+// ident_table: the statement's route at launch time and its table in d_hb_ident.  A sorted copy that another statement's build has
+// re-sorted on another grid since ident_routes sends the statement to all pairs for this batch.  *have_grid 1: the grid, its boxes, and
+// k_sorted_atoms' table of sel_b's copy, u32[nb][nsel_pad]; 0: room for the all-pairs route's canonical entries, u32[nb][|sel_b|].
+bool RangeRun::ident_table(BatchCtx& c, PropState* p, int route, int* have_grid, vmd_grid_t* grid, const float** d_gb) {
+    Selection* sl = e->sels[p->sel_a].get();
+    Selection* sr = e->sels[p->sel_b].get();
+    *have_grid = route;
+    if (*have_grid) {        // (the grid again: it also sets this thread's pencil reach for the walk)
+        *have_grid = grid_for(c, std::max(sl->idx.size(), sr->idx.size()), p->prop.rmax, grid, d_gb);
+        if (*have_grid < 0) return false;
+        if (*have_grid && !(sr->built && sr->built_grid.nxf == grid->nxf && sr->built_grid.ny == grid->ny && sr->built_grid.nz == grid->nz))
+            *have_grid = 0;
+    }
+    if (!p->d_hb_ident.ensure(c.nb * (*have_grid ? (size_t)sr->nsel_pad : sr->idx.size()))) return false;
+    if (*have_grid) {
+        const Stage& st = *c.src;
+        e->prof.begin("sorted_atoms", e->stream);
+        KRN_OK(vmd_hip_sorted_atoms(e->stream, st.base, st.frame_stride, st.row_stride, *d_gb, c.pbc, (int)c.nb, sr->d_idx.p,
+                (int)sr->idx.size(), sr->sorted.p, sr->cell_start.p, sr->nsel_pad, *grid, p->d_hb_ident.p, e->d_overflow.p));
+        e->prof.end(e->stream);
+    }
+    return true;
+}
+
+bool RangeRun::launch_hbonds(BatchCtx& c) {
+    const int closed = e->spec.within_closed ? 1 : 0;
+    std::vector<int> route;
+    if (!ident_routes(c, e->hbond_props, &route)) return false;
     for (size_t i = 0; i < e->hbond_props.size(); ++i) {
         const int pi = e->hbond_props[i];
         PropState* p = e->props[pi].get();
@@ -360,27 +392,13 @@ bool RangeRun::launch_hbonds(BatchCtx& c) {
             return vmd_fail("hydrogen-bond count '%s' has lost its occupancy", p->prop.name.c_str());
         PropState* m = e->props[pi + 1].get();
         const Property& d = p->prop;
-        Selection* sd = e->sels[p->sel_a].get();
         Selection* sr = e->sels[p->sel_b].get();
         const int npairs = (int)d.a.size(), nacc = (int)d.b.size();
         vmd_grid_t grid;
         const float* d_gb = nullptr;
-        int have_grid = route[i];
-        if (have_grid) {        // (the grid again: it also sets this thread's pencil reach for the walk)
-            have_grid = grid_for(c, std::max(sd->idx.size(), sr->idx.size()), d.rmax, &grid, &d_gb);
-            if (have_grid < 0) return false;
-            if (have_grid && !(sr->built && sr->built_grid.nxf == grid.nxf && sr->built_grid.ny == grid.ny && sr->built_grid.nz == grid.nz))
-                have_grid = 0;
-        }
-        if (!p->d_out.ensure(c.nb) || !p->d_hb_count.ensure(c.nb) ||
-            !p->d_hb_ident.ensure(c.nb * (size_t)(have_grid ? sr->nsel_pad : nacc))) return false;
+        int have_grid = 0;
+        if (!p->d_out.ensure(c.nb) || !p->d_hb_count.ensure(c.nb) || !ident_table(c, p, route[i], &have_grid, &grid, &d_gb)) return false;
         const Stage& st = *c.src;
-        if (have_grid) {
-            e->prof.begin("sorted_atoms", e->stream);
-            KRN_OK(vmd_hip_sorted_atoms(e->stream, st.base, st.frame_stride, st.row_stride, d_gb, c.pbc, (int)c.nb, sr->d_idx.p, nacc,
-                    sr->sorted.p, sr->cell_start.p, sr->nsel_pad, grid, p->d_hb_ident.p, e->d_overflow.p));
-            e->prof.end(e->stream);
-        }
         e->prof.begin(have_grid ? "hbond_atoms" : "hbond_brute", e->stream);
         for (auto& su : c.subs) {
             const float* xyz = st.base + su.off * st.frame_stride;
@@ -396,6 +414,52 @@ bool RangeRun::launch_hbonds(BatchCtx& c) {
                         p->d_hb_count.p + su.off, acc, e->d_overflow.p));
             KRN_OK(vmd_hip_hbond_finish(e->stream, p->d_hb_count.p + su.off, (int)su.nb, p->d_out.p + su.off, acc + npairs + nacc,
                     e->d_overflow.p));
+        }
+        e->prof.end(e->stream);
+        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
+    }
+    return true;
+}
+
+// ---- accessible area.  launch_hbonds' placement and rules, because the record is added to with atomics: behind the LAST cell
+// build of the batch, every statement's own build first (within_route with the measured entries in the lanes: the environment alone is
+// sorted, on the grid a within count of r_cut gets; all pairs below shell_brute_below environment entries or where no grid exists), every
+// kernel under the overflow flag, and a copy that a later statement's build has re-sorted on another grid sends its statement to all pairs
+// for this batch, which answers the same bit for bit.  The builds are a step of their own in front of launch_hbonds, whose occupancies are
+// added to with atomics as well: no cell build of the batch may stand behind either accumulation.
+bool RangeRun::build_sasa_cells(BatchCtx& c) { return ident_routes(c, e->sasa_props, &sasa_route); }
+
+bool RangeRun::launch_sasa(BatchCtx& c) {
+    const int closed = e->spec.within_closed ? 1 : 0;
+    for (size_t i = 0; i < e->sasa_props.size(); ++i) {
+        const int pi = e->sasa_props[i];
+        PropState* p = e->props[pi].get();
+        if ((size_t)pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::SASA_OCC)
+            return vmd_fail("sasa area '%s' has lost its record", p->prop.name.c_str());
+        PropState* m = e->props[pi + 1].get();
+        const Property& d = p->prop;
+        Selection* sr = e->sels[p->sel_b].get();
+        const int nmeas = (int)d.a.size(), nenv = (int)d.b.size(), npoints = (int)d.sasa_npoints;
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        int have_grid = 0;
+        if (!p->d_out.ensure(c.nb) || !p->d_sasa_total.ensure(c.nb) || !ident_table(c, p, sasa_route[i], &have_grid, &grid, &d_gb)) return false;
+        const Stage& st = *c.src;
+        e->prof.begin(have_grid ? "sasa_atoms" : "sasa_brute", e->stream);
+        for (auto& su : c.subs) {
+            const float* xyz = st.base + su.off * st.frame_stride;
+            uint64_t* acc = acc_of(m, su);
+            if (have_grid)
+                KRN_OK(vmd_hip_sasa_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, c.pbc, (int)su.nb, p->d_a.p, nmeas,
+                        p->d_b.p, nenv, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad, sr->cell_start.p + su.off * (size_t)(grid.ncell + 1),
+                        sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid, p->d_sasa_ra.p, p->d_sasa_rb.p, p->sasa_rmax_env,
+                        p->d_sasa_w.p, p->d_sasa_pts.p, npoints, d.rmax, closed, p->d_sasa_total.p + su.off, acc, e->d_overflow.p));
+            else
+                KRN_OK(vmd_hip_sasa_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
+                        p->d_a.p, nmeas, p->d_b.p, nenv, p->d_hb_ident.p + su.off * (size_t)nenv, p->d_sasa_ra.p, p->d_sasa_rb.p,
+                        p->sasa_rmax_env, p->d_sasa_w.p, p->d_sasa_pts.p, npoints, d.rmax, closed, p->d_sasa_total.p + su.off, acc,
+                        e->d_overflow.p));
+            KRN_OK(vmd_hip_sasa_finish(e->stream, p->d_sasa_total.p + su.off, (int)su.nb, p->d_out.p + su.off, acc + nmeas, e->d_overflow.p));
         }
         e->prof.end(e->stream);
         if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
@@ -487,7 +551,7 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     commits.clear();
     row = 0;
     forked = false;
-    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !launch_hbonds(c) || !launch_shell_sdfs(c) ||
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_sasa_cells(c) || !launch_hbonds(c) || !launch_sasa(c) || !launch_shell_sdfs(c) ||
         !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -673,7 +737,8 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     }
     if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
     switch (d.form) {
-    case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: return true;     // (behind the cell builds, above)
+    case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: case Form::SASA_AREA:
+    case Form::SASA_OCC: return true;     // (behind the cell builds, above)
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);

@@ -17,6 +17,7 @@
 //   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
 //   rmsf           -> rmsd's sums, k_rmsf_rotation, k_rmsf_accumulate (large sets) / k_rmsf_small
 //   hydrogen bonds -> k_sorted_atoms + k_hbond_atoms (the cell walk) / k_hbond_canon + k_hbond_brute (all pairs), k_hbond_finish
+//   accessible area -> k_sorted_atoms + k_sasa_atoms (the cell walk) / k_hbond_canon + k_sasa_brute (all pairs), k_sasa_finish
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -4477,6 +4478,222 @@ __global__ __launch_bounds__(256) void k_hbond_finish(const unsigned* count, int
     if (i == 0) *frames_row += (uint64_t)B;
 }
 
+// ------------------------------------------------------------------------------------------------ K13: solvent-accessible surface area
+
+// Shrake-Rupley.  Measured entry i (atom meas[i], R_i = radius + probe) carries P points R_i u_k on its sphere; n_i counts the points
+// that lie inside no neighbour's sphere.  Environment entry j (through its canonical entry: D-SASA-COINCIDENT) is a neighbour iff
+//   1. the pair passes within(r_cut, .)'s distance test, r_cut = 2 max(R) - wrapped positions, the S3 / S3t image, vmd_d2, vmd_within_hit
+//      with r_min = 0; e = (i - j) - shift is the delta that test squares, d2 the value it compared;
+//   2. d2 < s s strictly, s = R_i + R_j;
+//   3. j's atom is not i's atom, by index.
+// Point k is buried by neighbour j iff (u_kx e_x + u_ky e_y) + u_kz e_z < t_ij, t_ij = ((R_j R_j - R_i R_i) - d2) / (R_i + R_i): this is
+// |R_i u_k + e|^2 < R_j^2 rearranged.  fp32, every operation rounded on its own.  The area is integer: w_i = llround(4 pi R_i^2 / P * 2^20)
+// formed on the host, the frame's total the u64 sum of n_i w_i - atomics in any order give the same bits.
+// the point table u32-aligned in LDS, one row of four floats per point: k is uniform over the wave, a read is one broadcast
+__device__ __forceinline__ void vmd_sasa_stage_points(float (&s_u)[VMD_SASA_POINTS_MAX][4], const float* points, int P) {
+    for (int k = threadIdx.x; k < P; k += blockDim.x) {
+        s_u[k][0] = points[3 * k]; s_u[k][1] = points[3 * k + 1]; s_u[k][2] = points[3 * k + 2]; s_u[k][3] = 0.0f;
+    }
+    __syncthreads();
+}
+
+// a lane's P point bits, W words of 32: bit set = not buried so far
+template <int W>
+__device__ __forceinline__ void vmd_sasa_mask_full(uint32_t (&m)[W], int P) {
+#pragma unroll
+    for (int w = 0; w < W; ++w) { const int n = P - 32 * w; m[w] = n >= 32 ? 0xffffffffu : n > 0 ? (1u << n) - 1u : 0u; }
+}
+template <int W>
+__device__ __forceinline__ uint32_t vmd_sasa_mask_any(const uint32_t (&m)[W]) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) v |= m[w];
+    return v;
+}
+template <int W>
+__device__ __forceinline__ unsigned vmd_sasa_mask_count(const uint32_t (&m)[W]) {
+    unsigned n = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) n += (unsigned)__popcll((unsigned long long)m[w]);
+    return n;
+}
+// D-SASA-POINT for one neighbour: the word index is a compile-time constant (the words stay in registers), a word without points left is
+// passed over
+template <int W>
+__device__ __forceinline__ void vmd_sasa_bury(uint32_t (&m)[W], int P, const float (&s_u)[VMD_SASA_POINTS_MAX][4], float ex, float ey,
+                                              float ez, float t) {
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        uint32_t mw = m[w];
+        if (!mw) continue;
+        const int n = P - 32 * w < 32 ? P - 32 * w : 32;
+        for (int kk = 0; kk < n; ++kk) {
+            const float* u = s_u[32 * w + kk];
+            if ((u[0] * ex + u[1] * ey) + u[2] * ez < t) mw &= ~(1u << kk);
+        }
+        m[w] = mw;
+    }
+}
+// rules 2 and 3 and the point tests for one distance hit, the same from the walk and from all pairs.  smax2 = fl(fl(R_i + max R)^2) bounds
+// fl(s s) from above (rounding is monotonic), so the test against it drops a hit before anything is loaded.
+struct vmd_sasa_entry_t { int atom; float R, R2, twoR, smax2; };
+__device__ __forceinline__ vmd_sasa_entry_t vmd_sasa_entry(int atom, float R, float rmax_env) {
+    vmd_sasa_entry_t q;
+    q.atom = atom; q.R = R; q.R2 = R * R; q.twoR = R + R;
+    const float sm = R + rmax_env;
+    q.smax2 = sm * sm;
+    return q;
+}
+template <int W>
+__device__ __forceinline__ void vmd_sasa_neighbour(uint32_t (&m)[W], int P, const float (&s_u)[VMD_SASA_POINTS_MAX][4],
+                                                   const vmd_sasa_entry_t& q, int atom_j, float Rj, float d2, float ex, float ey, float ez) {
+    const float s = q.R + Rj;
+    if (!(d2 < s * s) || atom_j == q.atom) return;
+    const float t = ((Rj * Rj - q.R2) - d2) / q.twoR;
+    vmd_sasa_bury(m, P, s_u, ex, ey, ez, t);
+}
+
+// what a lane has found goes out the same way from the walk and from all pairs: one u64 atomic per lane with points into its row, the lanes'
+// n_i w_i summed over the wave into ONE u64 atomic on the frame's total.  Every lane of the wave calls it.
+__device__ __forceinline__ void vmd_sasa_commit(uint64_t* frame_total, uint64_t* row, unsigned n, uint32_t weight) {
+    if (n) vmd_atomic_add_u64(row, n);
+    uint64_t tot = (uint64_t)n * (uint64_t)weight;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)tot, o), hi = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)(tot >> 32), o);
+        tot += ((uint64_t)hi << 32) | lo;
+    }
+    if ((threadIdx.x & 63) == 0 && tot) vmd_atomic_add_u64(frame_total, tot);
+}
+
+struct vmd_sasa_atoms_params_t {
+    vmd_cells_params_t c;       // the measured entries as a cell build would read them: raw frame, the GRID's boxes, pbc, their list, grid (no outputs)
+    vmd_within_walk_params_t k; // the cell-sorted copy of the environment, the test of within(r_cut, .)
+    const int32_t* envl; int nenv;
+    const uint32_t* ident;      // k_sorted_atoms' table of the environment copy, u32[B][k.nref_pad]
+    const float* r_meas; const float* r_env; float rmax_env;      // R = radius + probe per list entry; the largest of the environment
+    const uint32_t* weight;     // w_i per measured entry
+    const float* points; int npoints;      // f32[npoints][3]
+    uint64_t* total; uint64_t* acc;        // u64[B] (zeroed by the call); u64[nsel + 1]: the rows (the frames row is k_sasa_finish's)
+    const uint32_t* skip;
+};
+
+// The walk, one lane per measured entry in list order; its pencil as k_hbond_atoms derives a donor's.  The lane keeps its point bits in W
+// registers.  Lanes of a wave are spatially unrelated: a neighbour is taken where it is found, without compaction.
+template <int W>
+__global__ __launch_bounds__(256) void k_sasa_atoms(vmd_sasa_atoms_params_t p) {
+    __shared__ float s_u[VMD_SASA_POINTS_MAX][4];
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the host repeats the batch, nothing may be added
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int P = p.npoints;
+    vmd_sasa_stage_points(s_u, p.points, P);
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
+    unsigned n = 0;
+    uint32_t weight = 0;
+    if (t < p.c.nsel) {
+        float xi, yi, zi;
+        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
+        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        const vmd_sasa_entry_t q = vmd_sasa_entry(p.c.sel[t], p.r_meas[t], p.rmax_env);
+        const uint32_t* id = p.ident + (size_t)b * p.k.nref_pad;
+        const int nenv = p.nenv;
+        const int32_t* envl = p.envl;
+        const float* r_env = p.r_env;
+        uint32_t m[W];
+        vmd_sasa_mask_full(m, P);
+        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float ex, float ey, float ez) {
+            // rule 2 against the largest environment radius first: it needs no memory.  A lane whose points are all buried has nothing
+            // left to clear
+            const float d2 = vmd_d2(ex, ey, ez);
+            if (!(d2 < q.smax2) || !vmd_sasa_mask_any(m)) return;
+            const uint32_t a = id[j];
+            if (a >= (uint32_t)nenv) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            vmd_sasa_neighbour(m, P, s_u, q, envl[a], r_env[a], d2, ex, ey, ez);
+        });
+        n = vmd_sasa_mask_count(m);
+        weight = p.weight[t];
+    }
+    vmd_sasa_commit(p.total + b, p.acc + (t < p.c.nsel ? t : 0), n, weight);
+}
+
+struct vmd_sasa_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc;
+    const int32_t* meas; int nmeas; const int32_t* envl; int nenv;
+    const uint32_t* canon;      // k_hbond_canon's table of the environment, u32[B][nenv]
+    const float* r_meas; const float* r_env; float rmax_env;
+    const uint32_t* weight;
+    const float* points; int npoints;
+    vmd_within_test_t w;        // within(r_cut, .)
+    uint64_t* total; uint64_t* acc; const uint32_t* skip;
+    uint32_t* counts;           // LIST: u32[nmeas], n_i of the one frame
+};
+
+// All pairs from the raw frame: one lane per measured entry, the environment staged through an LDS tile of 256 with its canonical entry's
+// atom and R.  The same rules, the same outputs as the walk.  LIST: the point counts of the frame go to counts[nmeas] instead
+// (vmd_eval_sasa_atoms), nothing is accumulated.
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_sasa_brute(vmd_sasa_brute_params_t p) {
+    __shared__ float s_u[VMD_SASA_POINTS_MAX][4];
+    __shared__ float s_r[3][256];
+    __shared__ float s_R[256];
+    __shared__ int s_a[256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int P = p.npoints;
+    vmd_sasa_stage_points(s_u, p.points, P);
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const bool valid = t < p.nmeas;
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    vmd_sasa_entry_t q = vmd_sasa_entry(-1, 1.0f, 1.0f);
+    constexpr int W = VMD_SASA_POINTS_MAX / 32;
+    uint32_t m[W];
+    vmd_sasa_mask_full(m, valid ? P : 0);
+    if (valid) {
+        q = vmd_sasa_entry(p.meas[t], p.r_meas[t], p.rmax_env);
+        vmd_pair_coords(bx, fx[q.atom], fy[q.atom], fz[q.atom], xi, yi, zi);
+    }
+    const uint32_t* canon = p.canon + (size_t)b * p.nenv;
+    for (int j0 = 0; j0 < p.nenv; j0 += 256) {
+        __syncthreads();
+        const int nj = p.nenv - j0 < 256 ? p.nenv - j0 : 256;
+        if ((int)threadIdx.x < nj) {
+            const int jj = threadIdx.x;
+            const int a = p.envl[j0 + jj];
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+            const uint32_t kk = canon[j0 + jj];
+            s_a[jj] = p.envl[kk];
+            s_R[jj] = p.r_env[kk];
+        }
+        __syncthreads();
+        if (valid)
+            for (int jj = 0; jj < nj; ++jj) {
+                float ex, ey, ez;
+                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
+                const float d2 = vmd_d2(ex, ey, ez);
+                if (!vmd_within_hit(p.w, d2) || !(d2 < q.smax2) || !vmd_sasa_mask_any(m)) continue;
+                vmd_sasa_neighbour(m, P, s_u, q, s_a[jj], s_R[jj], d2, ex, ey, ez);
+            }
+    }
+    const unsigned n = vmd_sasa_mask_count(m);
+    if (LIST) { if (valid) p.counts[t] = n; }
+    else vmd_sasa_commit(p.total + b, p.acc + (valid ? t : 0), n, valid ? p.weight[t] : 0u);
+}
+
+// the launcher's finishing step, behind the last launch over a frame group: the totals as the temporal rows, (float)(total 2^-20), the frames
+// row bumped once per frame - under the overflow flag like everything above
+__global__ __launch_bounds__(256) void k_sasa_finish(const uint64_t* total, int B, float* out, uint64_t* frames_row, const uint32_t* skip) {
+    if (skip && *skip) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) out[i] = (float)((double)total[i] * 9.5367431640625e-07);
+    if (i == 0) *frames_row += (uint64_t)B;
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -5003,6 +5220,86 @@ extern "C" int vmd_hip_hbond_finish(void* stream, const uint32_t* counts, int B,
     if (B <= 0) return 0;
     if (!counts || !out || !frames_row) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_hbond_finish, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, counts, B, out, frames_row, skip_flag);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K13: solvent-accessible surface area
+static bool vmd_sasa_args_ok(int B, const int32_t* meas, int nmeas, const int32_t* envl, int nenv, const float* r_meas, const float* r_env,
+                             float rmax_env, const float* points, int npoints, float r_cut) {
+    return B <= 65535 && meas && nmeas > 0 && envl && nenv > 0 && r_meas && r_env && rmax_env > 0.0f && points && npoints >= 1 &&
+           npoints <= VMD_SASA_POINTS_MAX && r_cut > 0.0f;
+}
+
+extern "C" int vmd_hip_sasa_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes,
+                                  uint32_t pbc_flags, int B, const int32_t* meas, int nmeas, const int32_t* envl, int nenv,
+                                  const float* sorted_env, const uint32_t* cell_start_env, int nenv_pad, const uint32_t* ident,
+                                  vmd_grid_t grid, const float* r_meas, const float* r_env, float rmax_env, const uint32_t* weight,
+                                  const float* points, int npoints, float r_cut, int closed, uint64_t* total_out, uint64_t* acc,
+                                  const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    vmd_sasa_atoms_params_t p{};
+    if (!vmd_sasa_args_ok(B, meas, nmeas, envl, nenv, r_meas, r_env, rmax_env, points, npoints, r_cut) || !weight || !total_out || !acc ||
+        !sorted_env || !cell_start_env || !ident || !grid_boxes || nenv_pad < nenv || grid.ncell != grid.nxf * grid.ny * grid.nz ||
+        !vmd_within_walk_fill(p.k, grid, sorted_env, cell_start_env, nenv_pad, 0.0f, r_cut, closed)) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(total_out, 0, (size_t)B * sizeof(uint64_t), s); if (e != hipSuccess) return (int)e; }
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
+    p.c.sel = meas; p.c.nsel = nmeas; p.c.nsel_pad = nmeas; p.c.grid = grid;
+    p.envl = envl; p.nenv = nenv; p.ident = ident; p.r_meas = r_meas; p.r_env = r_env; p.rmax_env = rmax_env; p.weight = weight;
+    p.points = points; p.npoints = npoints; p.total = total_out; p.acc = acc; p.skip = skip_flag;
+    const dim3 g((nmeas + 255) / 256, B);
+    if (npoints <= 128) hipLaunchKernelGGL(k_sasa_atoms<4>, g, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_sasa_atoms<VMD_SASA_POINTS_MAX / 32>, g, dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+static int vmd_sasa_brute_launch(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                 uint32_t pbc_flags, int B, const int32_t* meas, int nmeas, const int32_t* envl, int nenv, uint32_t* canon,
+                                 const float* r_meas, const float* r_env, float rmax_env, const uint32_t* weight, const float* points,
+                                 int npoints, float r_cut, int closed, uint64_t* total_out, uint64_t* acc, const uint32_t* skip_flag,
+                                 uint32_t* counts) {
+    hipStream_t s = (hipStream_t)stream;
+    vmd_hbond_brute_params_t cp{};          // k_hbond_canon reads the frame, the list and the flag of it
+    cp.xyz = xyz; cp.frame_stride = frame_stride; cp.row_stride = row_stride; cp.boxes = boxes; cp.pbc = pbc_flags;
+    cp.accl = envl; cp.nacc = nenv; cp.canon = canon; cp.skip = skip_flag;
+    hipLaunchKernelGGL(k_hbond_canon, dim3((nenv + 255) / 256, B), dim3(256), 0, s, cp);
+    VMD_LAUNCH_CHECK();
+    vmd_sasa_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, meas, nmeas, envl, nenv, canon, r_meas, r_env, rmax_env,
+                              weight, points, npoints, vmd_make_within_test(0.0f, r_cut, closed), total_out, acc, skip_flag, counts};
+    if (counts) hipLaunchKernelGGL(k_sasa_brute<true>, dim3((nmeas + 255) / 256, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_sasa_brute<false>, dim3((nmeas + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_sasa_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                  uint32_t pbc_flags, int B, const int32_t* meas, int nmeas, const int32_t* envl, int nenv, uint32_t* canon,
+                                  const float* r_meas, const float* r_env, float rmax_env, const uint32_t* weight, const float* points,
+                                  int npoints, float r_cut, int closed, uint64_t* total_out, uint64_t* acc, const uint32_t* skip_flag) {
+    if (B <= 0) return 0;
+    if (!vmd_sasa_args_ok(B, meas, nmeas, envl, nenv, r_meas, r_env, rmax_env, points, npoints, r_cut) || !weight || !total_out || !acc ||
+        !canon || !boxes) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(total_out, 0, (size_t)B * sizeof(uint64_t), (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
+    return vmd_sasa_brute_launch(stream, xyz, frame_stride, row_stride, boxes, pbc_flags, B, meas, nmeas, envl, nenv, canon, r_meas, r_env,
+                                 rmax_env, weight, points, npoints, r_cut, closed, total_out, acc, skip_flag, nullptr);
+}
+
+extern "C" int vmd_hip_sasa_list(void* stream, const float* xyz, size_t row_stride, const float* box, uint32_t pbc_flags, const int32_t* meas,
+                                 int nmeas, const int32_t* envl, int nenv, uint32_t* canon, const float* r_meas, const float* r_env,
+                                 float rmax_env, const float* points, int npoints, float r_cut, int closed, uint32_t* counts_out) {
+    // (the LIST instantiation reads no weight and writes no total)
+    if (!vmd_sasa_args_ok(1, meas, nmeas, envl, nenv, r_meas, r_env, rmax_env, points, npoints, r_cut) || !canon || !box ||
+        !counts_out) return (int)hipErrorInvalidValue;
+    return vmd_sasa_brute_launch(stream, xyz, 0, row_stride, box, pbc_flags, 1, meas, nmeas, envl, nenv, canon, r_meas, r_env, rmax_env,
+                                 nullptr, points, npoints, r_cut, closed, nullptr, nullptr, nullptr, counts_out);
+}
+
+extern "C" int vmd_hip_sasa_finish(void* stream, const uint64_t* totals, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag) {
+    if (B <= 0) return 0;
+    if (!totals || !out || !frames_row) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sasa_finish, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, totals, B, out, frames_row, skip_flag);
     VMD_LAUNCH_CHECK();
     return 0;
 }

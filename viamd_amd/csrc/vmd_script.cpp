@@ -987,3 +987,18 @@ extern "C" vmd_hbond_sites_owned_t* vmd_topology_hbond_sites(const vmd_topology_
 extern "C" const vmd_hbond_sites_t* vmd_hbond_sites_view(const vmd_hbond_sites_owned_t* sites) { return sites ? &sites->view : nullptr; }
 
 extern "C" void vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites) { delete sites; }
+
+// ---- van der Waals radii from a topology's elements (DECISION D-SASA-RADII): Bondi's values, 2.00 for anything else
+extern "C" size_t vmd_topology_vdw_radii(const vmd_topology_t* topology, float* out, size_t cap) {
+    if (!topology) { vmd_set_last_error("vmd_topology_vdw_radii: topology is NULL"); return 0; }
+    static const struct { const char* el; float r; } kBondi[] = {{"H", 1.20f}, {"C", 1.70f}, {"N", 1.55f}, {"O", 1.52f}, {"F", 1.47f},
+            {"P", 1.80f}, {"S", 1.80f}, {"CL", 1.75f}, {"BR", 1.85f}, {"I", 1.98f}};
+    const size_t n = topology->num_atoms;
+    for (size_t i = 0; out && i < n && i < cap; ++i) {
+        const std::string el = upper(topology->elements && topology->elements[i] ? topology->elements[i] : "");
+        float r = 2.00f;
+        for (auto& b : kBondi) if (el == b.el) r = b.r;
+        out[i] = r;
+    }
+    return n;
+}

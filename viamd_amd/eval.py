@@ -253,6 +253,34 @@ class ScriptIR:
                                                float(angle_min_deg)))
         self.hbond_pairs_of = dict(getattr(self, "hbond_pairs_of", {}), **{names[1]: int(d_.size)})
 
+    def add_sasa(self, names, atoms, radii, measured=None, probe=1.4, npoints=96):
+        """Solvent-accessible surface area by Shrake-Rupley: names = (area per frame in A^2, record of accessible points).
+        atoms / radii: the environment, every atom that occludes, with its van der Waals radius.  measured: positions INTO `atoms` of the
+        entries whose area is reported (None: all of them) - the measured set is a subset of the environment.  The record is u64
+        [nmeas + 1]: per measured entry the accessible points summed over the evaluated frames, then the frames."""
+        a_, _ = _idx(atoms)
+        r_ = np.ascontiguousarray(radii, np.float32).reshape(-1)
+        if a_.size != r_.size:
+            raise ValueError("atoms and radii must list one value per entry each")
+        sel = np.arange(a_.size) if measured is None else np.asarray(measured, np.int64).reshape(-1)
+        self.add_sasa_lists(names, a_[sel], r_[sel], a_, r_, probe, npoints)
+
+    def add_sasa_lists(self, names, measured, measured_radius, env, env_radius, probe=1.4, npoints=96):
+        """vmd_ir_add_sasa as it is: two independent lists of (atom, radius) - the entries whose area is reported, the entries that
+        occlude.  An atom in both lists is itself, by index."""
+        names = list(names)
+        assert len(names) == 2, "sasa defines two properties"
+        m_, mp = _idx(measured)
+        e_, ep = _idx(env)
+        mr = np.ascontiguousarray(measured_radius, np.float32).reshape(-1)
+        er = np.ascontiguousarray(env_radius, np.float32).reshape(-1)
+        if m_.size != mr.size or e_.size != er.size:
+            raise ValueError("every list entry needs one radius")
+        sites = L.SasaSitesC(m_.size, mp, mr.ctypes.data_as(L.c_float_p) if mr.size else None,
+                             e_.size, ep, er.ctypes.data_as(L.c_float_p) if er.size else None)
+        self._check(self.lib.vmd_ir_add_sasa(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(sites), float(probe),
+                                             int(npoints)))
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -411,6 +439,15 @@ class PropertyDataView:
         """the record of a hydrogen-bond occupancy as uint64 [npairs + nacc + 1]: the bonds every pair donated, the bonds
         every acceptor accepted, the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a hydrogen-bond occupancy record"
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
+
+    @property
+    def sasa_accumulators(self):
+        """the record of a sasa statement as uint64 [nmeas + 1]: the accessible points of every measured entry summed over
+        the evaluated frames, the frames accumulated"""
+        assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a record of accessible surface points"
         if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
             raise VmdError(self._ev.lib.last_error())
         return self._arr(self.c.counts, self.c.dim[0], np.uint64)
@@ -668,6 +705,30 @@ class ScriptEval:
             if cap is not None or n <= room:
                 return out[:min(n, room)].copy()
             room = int(n)
+
+    def sasa(self, name):
+        """the mean accessible area per measured entry read from its record as it stands -> (mean_area float64 [nmeas] in
+        A^2, frames)"""
+        if not self.lib.vmd_eval_sasa(self.h, name.encode(), None, None):      # (the name and the form, before any size is believed)
+            raise VmdError(self.lib.last_error())
+        area = np.zeros(self.property_data(name).dim[0] - 1, np.float64)
+        frames = C.c_uint64(0)
+        if not self.lib.vmd_eval_sasa(self.h, name.encode(), area.ctypes.data_as(L.c_double_p), C.byref(frames)):
+            raise VmdError(self.lib.last_error())
+        return area, int(frames.value)
+
+    def sasa_atoms(self, name, sys, traj, frame):
+        """the accessible points of every measured entry in one frame, on demand -> uint32 [nmeas]"""
+        failed = C.c_size_t(-1).value
+        n = self.lib.vmd_eval_sasa_atoms(self.h, name.encode(), C.byref(sys.c) if sys is not None else None, traj.interface(), int(frame),
+                                         None, 0)
+        if n == failed:
+            raise VmdError(self.lib.last_error())
+        out = np.zeros(max(n, 1), np.uint32)
+        if self.lib.vmd_eval_sasa_atoms(self.h, name.encode(), C.byref(sys.c) if sys is not None else None, traj.interface(), int(frame),
+                                        out.ctypes.data_as(C.POINTER(C.c_uint32)), n) == failed:
+            raise VmdError(self.lib.last_error())
+        return out[:n].copy()
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""

@@ -937,6 +937,38 @@ def hbond_sites_from_topology(topo, bonds):
                 acceptor=np.array([i for i, e in enumerate(el) if e in ("N", "O", "F")], np.int32))
 
 
+VDW_RADII = {"H": 1.20, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.80, "S": 1.80, "CL": 1.75, "BR": 1.85, "I": 1.98}
+
+
+def vdw_radii_from_topology(topo):
+    """Van der Waals radii for ScriptIR.add_sasa (DECISION D-SASA-RADII; the twin of vmd_topology_vdw_radii): Bondi's values by
+    element without regard to case, 2.00 for anything else.  -> float32 [num_atoms]"""
+    return np.array([VDW_RADII.get(str(e).upper(), 2.00) for e in topo.elements], np.float32)
+
+
+def vdw_radii_from_topology_native(topo, lib=None):
+    """The same through the C ABI (vmd_topology_vdw_radii).  Raises ScriptError with the library's message."""
+    import ctypes as C
+    lib = lib or L.default_lib()
+    n = topo.num_atoms
+    el = (C.c_char_p * max(n, 1))(*[str(v).encode() for v in topo.elements])
+    tc = L.TopologyC(n, el, None, None, None, None)
+    out = np.zeros(max(n, 1), np.float32)
+    if lib.vmd_topology_vdw_radii(C.byref(tc), out.ctypes.data_as(L.c_float_p), n) != n:
+        raise ScriptError(lib.last_error())
+    return out[:n].copy()
+
+
+def sasa_points(npoints, lib=None):
+    """The unit vectors the sasa kernels read (vmd_sasa_points, D-SASA-POINTS) -> float32 [npoints, 3]"""
+    lib = lib or L.default_lib()
+    out = np.zeros((max(int(npoints), 1), 3), np.float32)
+    n = lib.vmd_sasa_points(int(npoints), out.ctypes.data_as(L.c_float_p), out.shape[0])
+    if n == 0:
+        raise ScriptError(lib.last_error())
+    return out[:n].copy()
+
+
 def hbond_sites_from_topology_native(topo, bonds, lib=None):
     """The same through the C ABI (vmd_topology_hbond_sites).  Raises ScriptError with the library's message."""
     import ctypes as C
