@@ -53,6 +53,10 @@
 #ifndef VMD_BALLOT
 #define VMD_BALLOT(pred) __builtin_amdgcn_ballot_w64(pred)
 #endif
+// the value lane `lane` (wave-uniform) holds in v, as a wave-uniform value: one v_readlane_b32.  (The SIMT emulator defines its own.)
+#ifndef VMD_READLANE_U32
+#define VMD_READLANE_U32(v, lane) ((uint32_t)__builtin_amdgcn_readlane((int)(v), (int)(lane)))
+#endif
 // floor-to-int and fractional part in one instruction each (v_cvt_flr_i32_f32, v_fract_f32)
 #ifndef VMD_NO_INLINE_ASM
 __device__ __forceinline__ int vmd_floor_to_int(float t) { int b; asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(b) : "v"(t)); return b; }
@@ -248,6 +252,30 @@ __device__ __forceinline__ float vmd_wave_max(float v) {
 __device__ __forceinline__ float vmd_uniform(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
+// The same two reductions for a full wave of 64 active lanes, as one wave-uniform value and without lane addresses: __shfl_xor is
+// ds_bpermute_b32 behind a per-lane byte address (lane ^ o, clamped, times four - three VALU instructions per step that k_rdf_pencil
+// recomputed for every work item, and six VGPRs held across its column loops); ds_swizzle_b32 carries the xor in its immediate (bit-mask
+// mode: and 0x1f, or 0, xor o, inside each half of the wave), and lane 0 - the one vmd_uniform reads - takes the other half's result from
+// lane 32 through one v_readlane.  min / max are exact: the order of the steps does not change the value.
+#ifndef VMD_NO_INLINE_ASM
+#define VMD_SWIZZLE_XOR(v, o) __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), ((o) << 10) | 0x1f))
+__device__ __forceinline__ float vmd_wave64_min(float v) {
+    v = fminf(v, VMD_SWIZZLE_XOR(v, 16)); v = fminf(v, VMD_SWIZZLE_XOR(v, 8)); v = fminf(v, VMD_SWIZZLE_XOR(v, 4));
+    v = fminf(v, VMD_SWIZZLE_XOR(v, 2)); v = fminf(v, VMD_SWIZZLE_XOR(v, 1));
+    return vmd_uniform(fminf(v, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32))));
+}
+__device__ __forceinline__ float vmd_wave64_max(float v) {
+    v = fmaxf(v, VMD_SWIZZLE_XOR(v, 16)); v = fmaxf(v, VMD_SWIZZLE_XOR(v, 8)); v = fmaxf(v, VMD_SWIZZLE_XOR(v, 4));
+    v = fmaxf(v, VMD_SWIZZLE_XOR(v, 2)); v = fmaxf(v, VMD_SWIZZLE_XOR(v, 1));
+    return vmd_uniform(fmaxf(v, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32))));
+}
+// keeps the compiler from evaluating what depends on v before the branch that guards it (an empty volatile asm is not speculated)
+__device__ __forceinline__ float vmd_pin(float v) { asm volatile("" : "+v"(v)); return v; }
+#else
+__device__ __forceinline__ float vmd_wave64_min(float v) { return vmd_uniform(vmd_wave_min(v)); }
+__device__ __forceinline__ float vmd_wave64_max(float v) { return vmd_uniform(vmd_wave_max(v)); }
+__device__ __forceinline__ float vmd_pin(float v) { return v; }
+#endif
 __device__ __forceinline__ unsigned vmd_lane_prefix(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
@@ -1638,6 +1666,13 @@ __device__ __forceinline__ void vmd_segment_pruned(const vmd_pair_params_t& p, W
     }
 }
 
+// sx == 0 && sy == 0 && sz == 0 for the wave-uniform shifts of a segment, decided from their bit patterns: gfx9 has no scalar float
+// compare, the float test is three v_cmp_eq_f32 on 64 lanes for one answer; these are scalar integer instructions.  The shift left drops
+// the sign, so -0.0f is zero as in the float test; a NaN is non-zero in both.
+__device__ __forceinline__ bool vmd_no_shift(float sx, float sy, float sz) {
+    return (((unsigned)__float_as_int(sx) | (unsigned)__float_as_int(sy) | (unsigned)__float_as_int(sz)) << 1) == 0u;
+}
+
 template <int VARIANT, unsigned INC, bool MASKED, class W>
 __device__ __forceinline__ void vmd_segment(const vmd_pair_params_t& p, W& w, vmd_cf32* st,
                                             unsigned ja, unsigned jb, float sx, float sy, float sz,
@@ -1645,7 +1680,7 @@ __device__ __forceinline__ void vmd_segment(const vmd_pair_params_t& p, W& w, vm
     vmd_cf32* tx = st;
     vmd_cf32* ty = st + p.ntgt_pad;
     vmd_cf32* tz = st + 2 * (size_t)p.ntgt_pad;
-    if (sx == 0.0f && sy == 0.0f && sz == 0.0f)
+    if (vmd_no_shift(sx, sy, sz))
         vmd_segment_loop<VARIANT, INC, MASKED, false>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
     else
         vmd_segment_loop<VARIANT, INC, MASKED, true>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
@@ -1655,18 +1690,31 @@ __device__ __forceinline__ void vmd_segment(const vmd_pair_params_t& p, W& w, vm
 // 8 queues by frame index modulo 8.  A wave first drains the queue of its "home" XCD (blockIdx % 8 — the observed block->XCD
 // placement; affinity only, never correctness) so that all pencils of one frame are pulled through ONE XCD's L2, then steals
 // from the other queues.  Splitting pencils (nsub > 1) shrinks the number of frames an XCD has in flight (waves / (npen *
-// nsub)) so the j streams of the running items stay inside its 4 MiB L2.  Returns the global item id
-// ((b * npen + pen) * nsub + sub) or -1 when every queue is empty.  Called by lane 0 only.
-__device__ __forceinline__ int vmd_next_item(unsigned* counters, int& q, int& tries, int B, int nitem_frame) {
+// nsub)) so the j streams of the running items stay inside its 4 MiB L2.  Returns the item's index within its frame
+// ((pen * nsub + sub) * nsplit + part) and the frame in b, or -1 when every queue is empty (the two halves of the global item id, which
+// the kernel used to put together here and divide by nitem_frame again).
+// q and tries are wave-uniform and the queue arithmetic (the bound, the frame of the ticket, the id) runs on the scalar unit; only the
+// returning atomic is a vector instruction, on lane 0 (until the walk cuts it was all lane 0's: ~30 VALU instructions under a narrowed EXEC
+// per item, the division by nitem_frame among them).  vmd_post_item takes a ticket of queue q - it travels while the wave works on the
+// current item -, vmd_next_item turns the ticket into an item, or moves on to the next queue when q has run dry (that wait is exposed: at
+// most eight times in the life of a wave).  Both are called by all lanes of the wave.
+__device__ __forceinline__ unsigned vmd_post_item(unsigned* counters, int q, int tries, int lane) {
+    unsigned ticket = 0u;
+    if (tries < 8 && lane == 0) ticket = atomicAdd(&counters[q * VMD_COUNTER_STRIDE], 1u);
+    return ticket;
+}
+__device__ __forceinline__ int vmd_next_item(unsigned* counters, unsigned ticket, int& q, int& tries, int B, int nitem_frame, int lane, int& b) {
     while (tries < 8) {
+        const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
         const int nframes_q = (B - q + 7) >> 3;                 // frames q, q+8, ... < B
-        const unsigned t = atomicAdd(&counters[q * VMD_COUNTER_STRIDE], 1u);
         if (nframes_q > 0 && t < (unsigned)(nframes_q * nitem_frame)) {
-            const int fq = (int)t / nitem_frame;
-            return (q + 8 * fq) * nitem_frame + ((int)t - fq * nitem_frame);
+            const unsigned fq = t / (unsigned)nitem_frame;
+            b = q + 8 * (int)fq;
+            return (int)(t - fq * (unsigned)nitem_frame);
         }
         q = (q + 1) & 7;
         tries += 1;
+        ticket = vmd_post_item(counters, q, tries, lane);
     }
     return -1;
 }
@@ -1694,8 +1742,9 @@ __device__ __forceinline__ int vmd_next_item(unsigned* counters, int& q, int& tr
 // (half shell, open axis beyond the bounding box, the item's part of an nsplit launch, a shrunk window that vanishes), wraps the pencil and
 // derives sy, sz, the shrunk rpad and the triclinic offset range, then for each x image kx = -1, 0, 1 the window [lo, hi], its fine cells and -
 // with all loads of the chunk in flight together - ja and jb from the cell offsets.  Everything is the expression, in the order, of the scalar
-// walk it replaces.  The entries go to a per-wave LDS table; one ballot per x image says which of them end in a segment (window on the cell,
-// ja < jb), and a scalar loop takes those off the masks, reads ja, jb and the shifts back into wave-uniform registers and runs vmd_segment.
+// walk it replaces.  The entries go to a per-wave LDS table; the walk takes it an x image at a time: the lanes read the image's ja / jb column
+// back, one ballot says which entries end in a segment (ja < jb: a lane without a window holds ja == jb), and a scalar loop takes those off
+// the mask, brings ja, jb and the shifts of an entry into wave-uniform registers with v_readlane and runs vmd_segment.
 // The own pencil is combo (0, 0) = index ry of the half shell.  Segments are walked image by image instead of pencil by pencil: the
 // histograms are integer sums.  The table costs 8 KB of LDS per block (5.5 triclinic); with one histogram per block eight blocks still fit a
 // CU, with wave-private histograms five do instead of seven.
@@ -1759,7 +1808,6 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
     unsigned long long cols_before_flush = 0ull;
     // work items are handed out dynamically (one returning atomic per item, fetched one item ahead)
     int q = blockIdx.x & 7, tries = 0;
-    int item = -1, next_item = -1;
     const int nsub = p.nsub;
     const int nsplit = p.nsplit;
     const int nitem_frame = npen * nsub * nsplit;
@@ -1768,21 +1816,29 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
     const int ncombo = (p.rz - dz0 + 1) * ncy;
     const int cdiv = 65536 / ncy + 1;                       // (c * cdiv) >> 16 == c / ncy for c * ncy < 65536 (the reach is at most 4: 81 combos)
     unsigned* tab = s_tab[wave];
-    if (lane == 0) item = vmd_next_item(p.work_counter, q, tries, p.B, nitem_frame);
-    item = __builtin_amdgcn_readfirstlane(item);
-    for (; item >= 0; item = next_item) {
-        if (lane == 0) next_item = vmd_next_item(p.work_counter, q, tries, p.B, nitem_frame);
-        const int b = item / nitem_frame;
-        const int rem0 = item - b * nitem_frame;
-        const int rem = rem0 / nsplit;
+    // reach 1 in both axes (every unsplit grid): no window ever shrinks, and the pencil widths the shrink needs - two IEEE divisions, which
+    // the compiler otherwise hoists out of the table to the item and runs for every chunk - are not computed at all
+    const bool split = CELL == 0 && (p.ry > 1 || p.rz > 1);
+    unsigned ticket = vmd_post_item(p.work_counter, q, tries, lane);
+    int b = 0;
+    int rem0 = vmd_next_item(p.work_counter, ticket, q, tries, p.B, nitem_frame, lane, b);
+    while (rem0 >= 0) {
+        ticket = vmd_post_item(p.work_counter, q, tries, lane);
+        // (nothing here is negative: unsigned divisions, which cost the scalar unit a third less than signed ones)
+        const int rem = (int)((unsigned)rem0 / (unsigned)nsplit);
         const int part = rem0 - rem * nsplit;               // which of the chunk's neighbour pencils this item walks (fastest: the parts of
-        const int pen = rem / nsub;                         // a chunk go to consecutive waves, which share its i atoms and its neighbourhood)
+        const int pen = (int)((unsigned)rem / (unsigned)nsub);      // a chunk go to consecutive waves, which share its i atoms and its neighbourhood)
         const int sub = rem - pen * nsub;
-        const int pz = pen / ny;
+        const int pz = (int)((unsigned)pen / (unsigned)ny);
         const int py = pen - pz * ny;
         vmd_cf32* boxes = (vmd_cf32*)p.boxes;
-        const float Lx = boxes[VMD_BOX_STRIDE * b + 0], Ly = boxes[VMD_BOX_STRIDE * b + 1], Lz = boxes[VMD_BOX_STRIDE * b + 2];
+        // the box edges are operands of the table's lanes: held in a VGPR each for the item.  As scalars they were parked in VGPR lanes as the
+        // four-dword tuple of their load, and every use in the table round and the image loop read all four lanes back
+        const float Lx = vmd_in_vgpr(boxes[VMD_BOX_STRIDE * b + 0]), Ly = vmd_in_vgpr(boxes[VMD_BOX_STRIDE * b + 1]),
+                    Lz = vmd_in_vgpr(boxes[VMD_BOX_STRIDE * b + 2]);
         const float inv_cx = (float)nxf * boxes[VMD_BOX_STRIDE * b + 3];
+        float wy = 0.0f, wz = 0.0f;                         // the frame's pencil widths, split grids only
+        if (split) { wy = Ly / vmd_pin((float)ny); wz = Lz / vmd_pin((float)nz); }      // (pinned: else both divisions run ahead of the branch, behind two selects)
         const float txy = TRI ? boxes[VMD_BOX_STRIDE * b + 6] : 0.0f, txz = TRI ? boxes[VMD_BOX_STRIDE * b + 7] : 0.0f,
                     tyz = TRI ? boxes[VMD_BOX_STRIDE * b + 8] : 0.0f;
         // open x axis: fine cells count from the bounding-box origin (0 on a periodic axis)
@@ -1804,13 +1860,13 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
             const float xi = valid ? sr[i] : VMD_FAR;
             const float yi = valid ? sr[p.nref_pad + i] : VMD_FAR;
             const float zi = valid ? sr[2 * (size_t)p.nref_pad + i] : VMD_FAR;
-            const float xlo = vmd_uniform(vmd_wave_min(valid ? xi : 3.0e38f));
-            const float xhi = vmd_uniform(vmd_wave_max(valid ? xi : -3.0e38f));
+            const float xlo = vmd_wave64_min(valid ? xi : 3.0e38f);
+            const float xhi = vmd_wave64_max(valid ? xi : -3.0e38f);
             vmd_bbox_t bb = {};
             if (PRUNE) {
                 bb.lox = xlo; bb.hix = xhi;
-                bb.loy = vmd_uniform(vmd_wave_min(valid ? yi : 3.0e38f)); bb.hiy = vmd_uniform(vmd_wave_max(valid ? yi : -3.0e38f));
-                bb.loz = vmd_uniform(vmd_wave_min(valid ? zi : 3.0e38f)); bb.hiz = vmd_uniform(vmd_wave_max(valid ? zi : -3.0e38f));
+                bb.loy = vmd_wave64_min(valid ? yi : 3.0e38f); bb.hiy = vmd_wave64_max(valid ? yi : -3.0e38f);
+                bb.loz = vmd_wave64_min(valid ? zi : 3.0e38f); bb.hiz = vmd_wave64_max(valid ? zi : -3.0e38f);
                 // reach of the box test: the padded cutoff + the rounding of coordinates of this magnitude (images included)
                 const float mag = fmaxf(fmaxf(fmaxf(fabsf(bb.lox), fabsf(bb.hix)), fmaxf(fabsf(bb.loy), fabsf(bb.hiy))), fmaxf(fabsf(bb.loz), fabsf(bb.hiz)))
                                   + Lx + Ly + Lz + fabsf(txy) + fabsf(txz) + fabsf(tyz);
@@ -1837,8 +1893,8 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                 // split pencils: a neighbour two pencils away is at least one pencil width off in that axis, so its x window shrinks
                 // (orthorhombic periodic cells only; the widths of the other cell kinds are not the box edge over the count)
                 float rpad = p.rpad;
-                if (CELL == 0 && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {
-                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (Ly / (float)ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (Lz / (float)nz);
+                if (split && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {          // (split: wave-uniform, a scalar branch around the block)
+                    const float gy = (float)((dy < 0 ? -dy : dy) - 1) * wy, gz = (float)((dz < 0 ? -dz : dz) - 1) * wz;
                     const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
                     const float rr = p.rpad * p.rpad - 0.998f * (gyy * gyy + gzz * gzz);
                     if (rr <= 0.0f) ok = false;
@@ -1852,7 +1908,10 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                     offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
                     offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
                 }
-                int ia[3], ib[3];
+                // (CELL == 0 at reach 1: lo, hi, ca, cb of an image depend on xlo, xhi and kx only, not on the combo lane.  The compiler shares
+                // (xlo - rpad) and (xhi + rpad) across the three unrolled images and folds the TRI / OPEN zeros; what is left per image - one
+                // subtraction, two compares, two vmd_cell_coord - costs a VALU instruction the same for one value as for 64 lanes.)
+                unsigned ia[3], ib[3];                              // (never negative; unsigned: the lanes' load addresses need no sign extension)
                 bool in[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
@@ -1864,8 +1923,8 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                     in[k] = ok && !(open_x && kx != 0) && !(hi < 0.0f || lo >= Lx);
                     const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, inv_cx, nxf);
                     const int cb = hi >= Lx ? nxf - 1 : vmd_cell_coord(hi, inv_cx, nxf);
-                    ia[k] = in[k] ? q * nxf + ca : 0;               // (a lane without a window reads cst[0]: always there)
-                    ib[k] = in[k] ? q * nxf + cb + 1 : 0;
+                    ia[k] = in[k] ? (unsigned)(q * nxf + ca) : 0u;  // (a lane without a window reads cst[0]: always there)
+                    ib[k] = in[k] ? (unsigned)(q * nxf + cb + 1) : 0u;
                     if (TRI && lane < TABW) tab[VMD_TAB_SX(TABW) + k * TABW + lane] = (unsigned)__float_as_int(sx);
                 }
                 // all of the chunk's offsets travel together
@@ -1875,21 +1934,31 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                     tab[VMD_TAB_JB(TABW) + lane] = jb0; tab[VMD_TAB_JB(TABW) + TABW + lane] = jb1; tab[VMD_TAB_JB(TABW) + 2 * TABW + lane] = jb2;
                     tab[VMD_TAB_SY(TABW) + lane] = (unsigned)__float_as_int(sy); tab[VMD_TAB_SZ(TABW) + lane] = (unsigned)__float_as_int(sz);
                 }
-                // the entries that end in a segment (an own pencil's two parts are both empty when ja >= jb)
-                const unsigned long long m0 = VMD_BALLOT(in[0] && ja0 < jb0), m1 = VMD_BALLOT(in[1] && ja1 < jb1), m2 = VMD_BALLOT(in[2] && ja2 < jb2);
                 __builtin_amdgcn_wave_barrier();
+                // The walk takes the table an image at a time: the lanes read the image's ja / jb column back (and once per round the sy / sz
+                // column) and a segment's entry comes out of those registers with v_readlane.  Per SEGMENT it used to be two LDS reads at a
+                // wave-uniform address built in a VGPR and four v_readfirstlane behind their latency; the three ballots of a round were parked
+                // in VGPR lanes and all six halves read back for every image.
+                const unsigned lsy = lane < TABW ? tab[VMD_TAB_SY(TABW) + lane] : 0u, lsz = lane < TABW ? tab[VMD_TAB_SZ(TABW) + lane] : 0u;
 #pragma unroll 1
                 for (int k = 0; k < 3; ++k) {
-                    unsigned long long m = k == 0 ? m0 : (k == 1 ? m1 : m2);
-                    const float sxk = vmd_uniform((float)(k - 1) * Lx);
+                    const unsigned lja = lane < TABW ? tab[VMD_TAB_JA(TABW) + k * TABW + lane] : 0u, ljb = lane < TABW ? tab[VMD_TAB_JB(TABW) + k * TABW + lane] : 0u;
+                    const unsigned lsx = TRI && lane < TABW ? tab[VMD_TAB_SX(TABW) + k * TABW + lane] : 0u;
+                    // the entries that end in a segment (an own pencil's two parts are both empty when ja >= jb).  A lane without a window has
+                    // read cst[0] twice, ja == jb: the compare alone is the ballot
+                    unsigned long long m = VMD_BALLOT(lja < ljb);
+                    const unsigned lxb = (unsigned)__float_as_int(vmd_uniform(Lx));      // (read per image: one v_readfirstlane, no parked SGPR)
+                    // (float)(k - 1) * Lx of a finite Lx, from its bit pattern on the scalar unit: -Lx, a zero with the sign of Lx, Lx
+                    // (on the vector unit it was a subtract, a convert, a multiply and a v_readfirstlane per image)
+                    const float sxk = __int_as_float((int)(k == 0 ? lxb ^ 0x80000000u : (k == 1 ? lxb & 0x80000000u : lxb)));
                     while (m) {
                         const int e = __builtin_ctzll(m);
                         m &= m - 1ull;
-                        unsigned ja = (unsigned)__builtin_amdgcn_readfirstlane(tab[VMD_TAB_JA(TABW) + k * TABW + e]);
-                        const unsigned jb = (unsigned)__builtin_amdgcn_readfirstlane(tab[VMD_TAB_JB(TABW) + k * TABW + e]);
-                        const float sx = TRI ? __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SX(TABW) + k * TABW + e])) : sxk;
-                        const float sy = __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SY(TABW) + e]));
-                        const float sz = __int_as_float(__builtin_amdgcn_readfirstlane(tab[VMD_TAB_SZ(TABW) + e]));
+                        unsigned ja = VMD_READLANE_U32(lja, e);
+                        const unsigned jb = VMD_READLANE_U32(ljb, e);
+                        const float sx = TRI ? __int_as_float((int)VMD_READLANE_U32(lsx, e)) : sxk;
+                        const float sy = __int_as_float((int)VMD_READLANE_U32(lsy, e));
+                        const float sz = __int_as_float((int)VMD_READLANE_U32(lsz, e));
                         if (SAME && c0 + e == p.ry) {               // the own pencil: combo (dz, dy) = (0, 0)
                             // unordered pairs once: j > i.  Inside the chunk the test is per lane, above it all lanes pass.
                             const unsigned cend = cbeg + VMD_WAVE;
@@ -1905,7 +1974,7 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                             w.ncols += jb - ja;
                             if (PRUNE) {
                                 vmd_cf32* tx = st; vmd_cf32* ty = st + p.ntgt_pad; vmd_cf32* tz = st + 2 * (size_t)p.ntgt_pad;
-                                if (sx == 0.0f && sy == 0.0f && sz == 0.0f) vmd_segment_pruned<VARIANT, INC, false>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, bb, lane);
+                                if (vmd_no_shift(sx, sy, sz)) vmd_segment_pruned<VARIANT, INC, false>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, bb, lane);
                                 else vmd_segment_pruned<VARIANT, INC, true>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, bb, lane);
                             } else {
                                 vmd_segment<VARIANT, INC, false>(p, w, st, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
@@ -1932,7 +2001,7 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                 w.ncols = 0;
             }
         }
-        next_item = __builtin_amdgcn_readfirstlane(next_item);
+        rem0 = vmd_next_item(p.work_counter, ticket, q, tries, p.B, nitem_frame, lane, b);
     }
     vmd_drain<VARIANT, INC>(p.bin, w, lane);
     if (p.cols_total && lane == 0) atomicAdd(p.cols_total, cols_before_flush + (unsigned long long)w.ncols);
