@@ -869,6 +869,7 @@ struct vmd_pair_params_t {
     int ry, rz;              // neighbour reach in pencils per axis: 1 (cross-section >= rmax), 2 = split pencils (cross-section >= rmax/2)
     int nsplit;              // > 1 (small launches): a chunk's neighbour pencils are dealt to nsplit work items instead of one - a lone
                              // item is a dependent chain of cold scalar loads (170 us for a one-frame launch, profiles/r03aq)
+    int shift_axes;          // variant 0: an image segment with ONE live shift axis takes the loop that subtracts that shift alone (0: the general loop, A/B)
     int pop;                 // host side only: variant 0 is launched with the folded pop (instantiation POP = 2); 0 unless r_min == 0 and the fast path is usable at all
     unsigned long long* cols_total;   // device counter or NULL: candidate columns of every launch since the host last reset it (one atomic per
                                       // wave at kernel end): bench.py's "candidate lanes per counted hit" is measured, not modelled
@@ -1328,18 +1329,18 @@ __device__ __forceinline__ void vmd_push_hot4(W& w, float d0, float d1, float d2
         : [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3), [r2] "s"(r2)
         : "vcc", "scc", "memory");
 }
-// own pencil: column k counts only j + k > i.  ik = i - k as signed integers (indices stay far below 2^31), so the four
-// conditions are v_cmp_gt_i32 j, ik with ONE uniform j.
+// own pencil: column j counts only j > i.  Lane L holds atom cbeg + L, so column j passes exactly the lanes 0 .. j - cbeg - 1: a wave-uniform
+// mask, made on the scalar unit (until now a v_cmp_gt_i32 per column against i, i - 1, i - 2, i - 3 in four VGPRs).  nm is the COMPLEMENT of
+// the current column's mask, ~0 << (j - cbeg), and moves one lane up behind every column: s_andn2 takes it out of the hits (SCC = any left,
+// as the s_and before it), s_lshl_b64 - which writes SCC too - waits behind the branch.  A width of 64 or more (only columns past the
+// segment: at -VMD_FAR, never a hit) shifts nm out to 0 = all lanes; no width wraps around into an empty or partial mask.
 template <class W>
-__device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, float d2, float d3, float r2,
-                                                     int j, int i0, int i1, int i2, int i3) {
+__device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, float d2, float d3, float r2, unsigned long long& nm) {
     unsigned t, n;
-    unsigned long long m;
     asm volatile(
         VMD_PUSH_NOP
         "v_cmp_gt_f32 vcc, %[r2], %[d0]\n\t"
-        "v_cmp_gt_i32 %[m], %[j], %[i0]\n\t"
-        "s_and_b64 vcc, vcc, %[m]\n\t"
+        "s_andn2_b64 vcc, vcc, %[nm]\n\t"
         "s_cbranch_scc0 .Lvmd_p4m_0_%=\n\t"
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
         "v_mbcnt_hi_u32_b32 %[t], vcc_hi, %[t]\n\t"
@@ -1350,9 +1351,9 @@ __device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, f
         "s_bcnt1_i32_b64 %[n], vcc\n\t"
         "s_lshl2_add_u32 %[q], %[n], %[q]\n"
         ".Lvmd_p4m_0_%=:\n\t"
+        "s_lshl_b64 %[nm], %[nm], 1\n\t"
         "v_cmp_gt_f32 vcc, %[r2], %[d1]\n\t"
-        "v_cmp_gt_i32 %[m], %[j], %[i1]\n\t"
-        "s_and_b64 vcc, vcc, %[m]\n\t"
+        "s_andn2_b64 vcc, vcc, %[nm]\n\t"
         "s_cbranch_scc0 .Lvmd_p4m_1_%=\n\t"
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
         "v_mbcnt_hi_u32_b32 %[t], vcc_hi, %[t]\n\t"
@@ -1363,9 +1364,9 @@ __device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, f
         "s_bcnt1_i32_b64 %[n], vcc\n\t"
         "s_lshl2_add_u32 %[q], %[n], %[q]\n"
         ".Lvmd_p4m_1_%=:\n\t"
+        "s_lshl_b64 %[nm], %[nm], 1\n\t"
         "v_cmp_gt_f32 vcc, %[r2], %[d2]\n\t"
-        "v_cmp_gt_i32 %[m], %[j], %[i2]\n\t"
-        "s_and_b64 vcc, vcc, %[m]\n\t"
+        "s_andn2_b64 vcc, vcc, %[nm]\n\t"
         "s_cbranch_scc0 .Lvmd_p4m_2_%=\n\t"
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
         "v_mbcnt_hi_u32_b32 %[t], vcc_hi, %[t]\n\t"
@@ -1376,9 +1377,9 @@ __device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, f
         "s_bcnt1_i32_b64 %[n], vcc\n\t"
         "s_lshl2_add_u32 %[q], %[n], %[q]\n"
         ".Lvmd_p4m_2_%=:\n\t"
+        "s_lshl_b64 %[nm], %[nm], 1\n\t"
         "v_cmp_gt_f32 vcc, %[r2], %[d3]\n\t"
-        "v_cmp_gt_i32 %[m], %[j], %[i3]\n\t"
-        "s_and_b64 vcc, vcc, %[m]\n\t"
+        "s_andn2_b64 vcc, vcc, %[nm]\n\t"
         "s_cbranch_scc0 .Lvmd_p4m_3_%=\n\t"
         "v_mbcnt_lo_u32_b32 %[t], vcc_lo, 0\n\t"
         "v_mbcnt_hi_u32_b32 %[t], vcc_hi, %[t]\n\t"
@@ -1389,8 +1390,9 @@ __device__ __forceinline__ void vmd_push_hot4_masked(W& w, float d0, float d1, f
         "s_bcnt1_i32_b64 %[n], vcc\n\t"
         "s_lshl2_add_u32 %[q], %[n], %[q]\n"
         ".Lvmd_p4m_3_%=:\n\t"
-        : [q] "+s"(w.qtop), [t] "=&v"(t), [n] "=&s"(n), [m] "=&s"(m)
-        : [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3), [r2] "s"(r2), [j] "s"(j), [i0] "v"(i0), [i1] "v"(i1), [i2] "v"(i2), [i3] "v"(i3)
+        "s_lshl_b64 %[nm], %[nm], 1\n\t"
+        : [q] "+s"(w.qtop), [nm] "+s"(nm), [t] "=&v"(t), [n] "=&s"(n)
+        : [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3), [r2] "s"(r2)
         : "vcc", "scc", "memory");
 }
 // variant 2: one pair-column (two candidate columns), a / b = its two d2 values.  The stack is drained after every pair-column, so it
@@ -1450,33 +1452,37 @@ __device__ __forceinline__ void vmd_push_hot2p_masked(W& w, float a, float b, fl
 #endif
 
 // one uniform j segment [ja, jb) against the wave's 64 i atoms.  MASKED: count only j > i (own pencil, same set).
-// SHIFT: the segment is a periodic image, displaced by (sx,sy,sz) (SPEC S3: dx = fl(fl(xi-xj) - sx)).
-template <int VARIANT, unsigned INC, bool MASKED, bool SHIFT, class W>
+// AXES (bit 0: x, 1: y, 2: z): the segment is a periodic image, displaced by (sx,sy,sz) (SPEC S3: dx = fl(fl(xi-xj) - sx)), and these are the
+// axes whose shift is subtracted.  An axis may be left out when its shift is a zero: fl(d - +-0) is d, but for the sign of a zero d, and d is
+// squared next - d2 has the same bits.  0: no image; 1, 2, 4: the one live axis of nearly every image of an orthorhombic cell; 7: any shift.
+template <int VARIANT, unsigned INC, bool MASKED, int AXES, class W>
 __device__ __forceinline__ void vmd_segment_loop(const vmd_pair_params_t& p, W& w, vmd_cf32* tx, vmd_cf32* ty, vmd_cf32* tz,
                                                  unsigned ja, unsigned jb, float sx, float sy, float sz,
-                                                 float xi, float yi, float zi, unsigned i, int lane) {
+                                                 float xi, float yi, float zi, unsigned i, unsigned cbeg, int lane) {
     const float r2 = p.r2_up;
-    vmd_cf32* px = tx + ja;
-    vmd_cf32* py = ty + ja;
-    vmd_cf32* pz = tz + ja;
     const unsigned n = jb - ja;
     // two j columns per VALU instruction: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 are IEEE per element, so the
     // arithmetic is still SPEC S3 exactly; the j pair sits in an SGPR pair straight from s_load_dwordx4
     const vmd_f2 xi2 = {xi, xi}, yi2 = {yi, yi}, zi2 = {zi, zi};
     const vmd_f2 sx2 = {sx, sx}, sy2 = {sy, sy}, sz2 = {sz, sz};
+    // own pencil, variant 0: the lanes that do NOT pass the next column (vmd_push_hot4_masked).  The masked segment starts at ja >= cbeg and
+    // ends at cbeg + 64 at the latest; the groups take the columns in order, each push moves the mask on by its four
+    unsigned long long nm = MASKED ? ~0ull << ((ja - cbeg) & 63u) : 0ull;
     // four columns (two packed pairs) from one s_load_dwordx4 per coordinate
-    auto group = [&](const vmd_f4& xj, const vmd_f4& yj, const vmd_f4& zj, unsigned k0) {
+    auto group = [&](const vmd_f4& xj, const vmd_f4& yj, const vmd_f4& zj, unsigned j0) {       // j0: the group's first column
         vmd_f2 d2[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const vmd_f2 xj2 = {xj[2 * h], xj[2 * h + 1]}, yj2 = {yj[2 * h], yj[2 * h + 1]}, zj2 = {zj[2 * h], zj[2 * h + 1]};
             vmd_f2 dx = xi2 - xj2, dy = yi2 - yj2, dz = zi2 - zj2;
-            if (SHIFT) { dx = dx - sx2; dy = dy - sy2; dz = dz - sz2; }
+            if (AXES & 1) dx = dx - sx2;
+            if (AXES & 2) dy = dy - sy2;
+            if (AXES & 4) dz = dz - sz2;
             d2[h] = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
         }
 #ifndef VMD_NO_INLINE_ASM
         if (VARIANT == 0) {
-            if (MASKED) vmd_push_hot4_masked(w, d2[0][0], d2[0][1], d2[1][0], d2[1][1], r2, (int)(ja + k0), (int)i, (int)i - 1, (int)i - 2, (int)i - 3);
+            if (MASKED) vmd_push_hot4_masked(w, d2[0][0], d2[0][1], d2[1][0], d2[1][1], r2, nm);
             else vmd_push_hot4(w, d2[0][0], d2[0][1], d2[1][0], d2[1][1], r2);
             vmd_drain_full<VARIANT, INC>(p.bin, w, lane);
             return;
@@ -1484,7 +1490,7 @@ __device__ __forceinline__ void vmd_segment_loop(const vmd_pair_params_t& p, W& 
         if (VARIANT == 2) {
             if (MASKED) {
                 // lanes 0 .. (j - cbeg) of the pair-column starting at j; the chunk starts at the atom of lane 0
-                const int a = (int)(ja + k0) - __builtin_amdgcn_readfirstlane((int)i);
+                const int a = (int)j0 - __builtin_amdgcn_readfirstlane((int)i);
                 const unsigned long long lm0 = a >= 63 ? ~0ull : ((2ull << a) - 1ull);
                 const unsigned long long lm1 = a + 2 >= 63 ? ~0ull : ((2ull << (a + 2)) - 1ull);
                 // the self pair (lane a of the first column, lane a + 2 of the third) never enters the stack
@@ -1506,7 +1512,7 @@ __device__ __forceinline__ void vmd_segment_loop(const vmd_pair_params_t& p, W& 
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 float a = d2[h][0], b = d2[h][1];
-                if (MASKED) { if (!(ja + k0 + 2 * h > i)) a = VMD_JUNK; if (!(ja + k0 + 2 * h + 1 > i)) b = VMD_JUNK; }
+                if (MASKED) { if (!(j0 + 2 * h > i)) a = VMD_JUNK; if (!(j0 + 2 * h + 1 > i)) b = VMD_JUNK; }
                 vmd_push2(w, fminf(a, b) < r2, a, b);
                 vmd_drain_full<VARIANT, INC>(p.bin, w, lane);
             }
@@ -1516,7 +1522,7 @@ __device__ __forceinline__ void vmd_segment_loop(const vmd_pair_params_t& p, W& 
         for (int c = 0; c < 4; ++c) {
             const float v = d2[c >> 1][c & 1];
             bool hit = v < r2;
-            if (MASKED) hit = hit && (ja + k0 + c > i);
+            if (MASKED) hit = hit && (unsigned)lane < j0 + c - cbeg;      // the low j - cbeg lanes, all of them from 64 on: the twin of the scalar mask
             vmd_push<VARIANT, INC>(p.bin, w, hit, v);
         }
         vmd_drain_full<VARIANT, INC>(p.bin, w, lane);
@@ -1527,32 +1533,34 @@ __device__ __forceinline__ void vmd_segment_loop(const vmd_pair_params_t& p, W& 
     // (x = -VMD_FAR: never a hit, for valid and padding lanes alike) - until round 6 a one-column loop with the plain C++ push and a
     // drain of its own: ~1 % of the columns at twice the price (c3: 71.9 -> 71.3 ms per 1 000 frames, profiles/r06r_tail_ab.txt).
     if (n == 0) return;
-    vmd_f4 xa = vmd_uniform_load4(px, 0), ya = vmd_uniform_load4(py, 0), za = vmd_uniform_load4(pz, 0);
+    // the three rows are addressed from their starts, the segment by its byte offset 4 * ja: the row pointers are the same for every segment of
+    // the item and need no copy advanced by ja (three 64-bit additions per segment, into six more scalar registers)
+    unsigned off = 4u * ja;
+    vmd_f4 xa = vmd_uniform_load4(tx, off), ya = vmd_uniform_load4(ty, off), za = vmd_uniform_load4(tz, off);
     // the loop counts BYTES of the j rows and runs against a kept last offset: add + compare + one backward branch per eight columns (counting
     // columns it was add, compare, two branches, a register copy and a shift; every scalar instruction of this loop shows, profiles/r06v_salu_ab.txt)
-    unsigned off = 0;
     if (n >= 8) {
-        const unsigned stop = 4u * n - 32u;
+        const unsigned stop = 4u * jb - 32u;
         do {
-            const vmd_f4 xb = vmd_uniform_load4(px, off + 16u), yb = vmd_uniform_load4(py, off + 16u), zb = vmd_uniform_load4(pz, off + 16u);
+            const vmd_f4 xb = vmd_uniform_load4(tx, off + 16u), yb = vmd_uniform_load4(ty, off + 16u), zb = vmd_uniform_load4(tz, off + 16u);
             group(xa, ya, za, off >> 2);
-            xa = vmd_uniform_load4(px, off + 32u); ya = vmd_uniform_load4(py, off + 32u); za = vmd_uniform_load4(pz, off + 32u);
+            xa = vmd_uniform_load4(tx, off + 32u); ya = vmd_uniform_load4(ty, off + 32u); za = vmd_uniform_load4(tz, off + 32u);
             group(xb, yb, zb, (off >> 2) + 4u);
             off += 32u;
         } while (off <= stop);
     }
-    unsigned k = off >> 2;
-    while (k < n) {                                   // at most twice: xa / ya / za hold columns k .. k + 3
-        const unsigned r = n - k;
+    unsigned j = off >> 2;
+    while (j < jb) {                                  // at most twice: xa / ya / za hold columns j .. j + 3
+        const unsigned r = jb - j;
         vmd_f4 xb = xa, yb = ya, zb = za;
-        if (r > 4) { xb = vmd_uniform_load4(px, 4u * k + 16u); yb = vmd_uniform_load4(py, 4u * k + 16u); zb = vmd_uniform_load4(pz, 4u * k + 16u); }
+        if (r > 4) { xb = vmd_uniform_load4(tx, 4u * j + 16u); yb = vmd_uniform_load4(ty, 4u * j + 16u); zb = vmd_uniform_load4(tz, 4u * j + 16u); }
         if (r < 4) {
             xa[3] = -VMD_FAR;
             if (r < 3) xa[2] = -VMD_FAR;
             if (r < 2) xa[1] = -VMD_FAR;
         }
-        group(xa, ya, za, k);
-        k += 4;
+        group(xa, ya, za, j);
+        j += 4;
         xa = xb; ya = yb; za = zb;
     }
     vmd_drain_full<VARIANT, INC>(p.bin, w, lane);
@@ -1676,14 +1684,31 @@ __device__ __forceinline__ bool vmd_no_shift(float sx, float sy, float sz) {
 template <int VARIANT, unsigned INC, bool MASKED, class W>
 __device__ __forceinline__ void vmd_segment(const vmd_pair_params_t& p, W& w, vmd_cf32* st,
                                             unsigned ja, unsigned jb, float sx, float sy, float sz,
-                                            float xi, float yi, float zi, unsigned i, int lane) {
+                                            float xi, float yi, float zi, unsigned i, unsigned cbeg, int lane) {
     vmd_cf32* tx = st;
     vmd_cf32* ty = st + p.ntgt_pad;
     vmd_cf32* tz = st + 2 * (size_t)p.ntgt_pad;
-    if (vmd_no_shift(sx, sy, sz))
-        vmd_segment_loop<VARIANT, INC, MASKED, false>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
-    else
-        vmd_segment_loop<VARIANT, INC, MASKED, true>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
+    // which shifts are not a zero, from their bit patterns on the scalar unit as in vmd_no_shift (both zeros are zero, a NaN is not).  An image
+    // of an orthorhombic cell has one live axis unless its pencil wraps in y AND z or it is an x image of a wrapped pencil: a y-wrapped
+    // neighbour sy, a z-wrapped one sz, an x image of an unwrapped pencil sx - that loop subtracts one shift per column pair instead of three.
+    // Two or three live axes (and every image of a triclinic cell whose sx moves with sy and sz) take the general loop, as does every image
+    // of the own pencil's masked part, of the other variants, and of all segments with p.shift_axes == 0 (the A/B switch rdf_shift_axes).
+    // (hipcc turns the y and z tests back into v_cmp_eq_f32 against 0; kept from it behind an empty asm they are scalar, eleven scalar
+    // instructions more per segment path set, and the kernel is 0.1 ms slower: profiles/pair_loops_ab.txt, state "s")
+    const unsigned live = (((unsigned)__float_as_int(sx) << 1) != 0u ? 1u : 0u) | (((unsigned)__float_as_int(sy) << 1) != 0u ? 2u : 0u) |
+                          (((unsigned)__float_as_int(sz) << 1) != 0u ? 4u : 0u);
+    if (live == 0u) {
+        vmd_segment_loop<VARIANT, INC, MASKED, 0>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane);
+        return;
+    }
+    if constexpr (VARIANT == 0 && !MASKED) {
+        if (p.shift_axes) {
+            if (live == 1u) { vmd_segment_loop<VARIANT, INC, MASKED, 1>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane); return; }
+            if (live == 2u) { vmd_segment_loop<VARIANT, INC, MASKED, 2>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane); return; }
+            if (live == 4u) { vmd_segment_loop<VARIANT, INC, MASKED, 4>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane); return; }
+        }
+    }
+    vmd_segment_loop<VARIANT, INC, MASKED, 7>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane);
 }
 
 // Work distribution: an item is (frame, pencil, sub): the i-chunks sub, sub + nsub, ... of one pencil.  Items are split into
@@ -1966,7 +1991,7 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                             const unsigned mb = jb < cend ? jb : cend;
                             if (ma < mb) {
                                 w.ncols += mb - ma;
-                                vmd_segment<VARIANT, INC, true>(p, w, st, ma, mb, sx, sy, sz, xi, yi, zi, i, lane);
+                                vmd_segment<VARIANT, INC, true>(p, w, st, ma, mb, sx, sy, sz, xi, yi, zi, i, cbeg, lane);
                             }
                             ja = ja > cend ? ja : cend;
                         }
@@ -1977,7 +2002,7 @@ __global__ __launch_bounds__(256) VMD_PENCIL_OCC(SHIST) void k_rdf_pencil(vmd_pa
                                 if (vmd_no_shift(sx, sy, sz)) vmd_segment_pruned<VARIANT, INC, false>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, bb, lane);
                                 else vmd_segment_pruned<VARIANT, INC, true>(p, w, tx, ty, tz, ja, jb, sx, sy, sz, xi, yi, zi, bb, lane);
                             } else {
-                                vmd_segment<VARIANT, INC, false>(p, w, st, ja, jb, sx, sy, sz, xi, yi, zi, i, lane);
+                                vmd_segment<VARIANT, INC, false>(p, w, st, ja, jb, sx, sy, sz, xi, yi, zi, i, cbeg, lane);
                             }
                         }
                     }
@@ -4926,6 +4951,10 @@ static int g_rdf_nsub_pct = 100;   // automatic nsub = mean chunks per pencil x 
 extern "C" int vmd_hip_set_rdf_nsub_pct(int n) { const int old = g_rdf_nsub_pct; if (n >= 25 && n <= 800) g_rdf_nsub_pct = n; return old; }
 static int g_rdf_shist = 1;       // one LDS histogram per block instead of one per wave: 8 instead of 7 waves per SIMD (default since round 6, see VMD_PENCIL_OCC)
 extern "C" int vmd_hip_set_rdf_shared_hist(int on) { const int old = g_rdf_shist; g_rdf_shist = on ? 1 : 0; return old; }
+// an image segment whose shift has one live axis subtracts that one only (vmd_segment); 0 = every shifted segment takes the general loop.  A/B and
+// cross-check switch: the counts are the same bit for bit (tests/pencil_loop_cases.py), measured in profiles/pair_loops_ab.txt
+static int g_rdf_shift_axes = 1;
+extern "C" int vmd_hip_set_rdf_shift_axes(int on) { const int old = g_rdf_shift_axes; g_rdf_shift_axes = on ? 1 : 0; return old; }
 static thread_local int g_pen_ry = 1, g_pen_rz = 1;   // neighbour reach of the pencil walk; the grid handed to the build and to the walk must be cut to match.  Per host thread like g_rdf_closed: the evaluator sets it (choose_grid) right before that thread's launches, two evals on two threads must not race (TSan: profiles/r04r_tsan.txt)
 extern "C" void vmd_hip_set_pencil_reach(int ry, int rz) { g_pen_ry = ry < 1 ? 1 : (ry > 4 ? 4 : ry); g_pen_rz = rz < 1 ? 1 : (rz > 4 ? 4 : rz); }
 // candidate columns walked by k_rdf_pencil (all launches of this process on the current device) since the last reset
@@ -5001,6 +5030,7 @@ extern "C" int vmd_hip_rdf_pencil(void* stream, const float* sorted_ref, const u
     p.pbc = pbc_flags;
     p.skip = skip_flag;
     p.ry = g_pen_ry; p.rz = g_pen_rz;
+    p.shift_axes = g_rdf_shift_axes;
     p.cols_total = vmd_cols_counter();
     const int cell = (pbc_flags & VMD_PBC_TRICLINIC) ? 1 : ((pbc_flags & 7u) != 7u ? 2 : 0);
     const int which = (variant == 1 ? 6 : variant == 2 ? 12 : variant == 3 ? 18 : 0) + (same_set ? 3 : 0) + cell;
