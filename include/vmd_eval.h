@@ -380,6 +380,31 @@ bool vmd_ir_add_sasa(vmd_script_ir_t* ir, const char* const names[2], const vmd_
  * phi = k pi (3 - sqrt 5), u = (rho cos phi, rho sin phi, z), formed in double and rounded once to fp32.  Writes the first `cap` points
  * (out may be NULL with cap == 0) and returns npoints; 0 + vmd_last_error when npoints is outside [1, 256]. */
 size_t vmd_sasa_points(uint32_t npoints, float (*out)[3], size_t cap);
+/* Residue contact maps and the native-contact fraction Q(t) (an entry point, no script syntax).  sites: nentries list entries,
+ * entry i = an atom and the group (residue) it stands for, 0 <= group < ngroups; nnative group pairs of a reference ("native") set, which
+ * may be empty.  Groups g < h are in contact in a frame iff h - g >= min_sep and some entry of g and some entry of h pass the distance
+ * test of within(r_cut, .): wrapped positions, the SPEC S3 / S3t image, r_min = 0, spec_within_closed acting on it as on a shell (the pair
+ * distance of vmd_ir_add_hbonds, word for word).  Identity is by group: entries whose wrapped positions coincide bit for bit in a frame all
+ * act - on either side of a pair - as the lowest such entry, that is, with its group (D-CT-COINCIDENT).
+ * Pair (g, h), g < h, has the condensed index p = g (2 G - g - 1) / 2 + (h - g - 1), G = ngroups, P = G (G - 1) / 2 (SciPy's pdist order).
+ * names[0]: TEMPORAL, dim = {num_frames, 1}, no unit: the group pairs in contact in the frame (+0 for none; follows the frame mask like a
+ * within count).
+ * names[1]: MAP (VMD_PROPERTY_FLAG_MAP) of u64 accumulators, dim = {P + 1, 1}: row p the evaluated frames in which pair p was in contact
+ * (pairs closer than min_sep stay 0), the last row the frames accumulated.  Integer counts: the record is the same bit for bit however
+ * calls, batches, frame blocks and ranks arrive, and merges like every MAP; a frame evaluated twice without vmd_eval_clear_data counts twice.
+ * names[2]: required iff nnative > 0, NULL otherwise.  TEMPORAL, no unit: Q = (float)n / (float)nnative, n the native pairs in contact in
+ * the frame (one fp32 division).
+ * Errors (vmd_last_error): NULL arguments, nentries == 0, ngroups < 2 or > VMD_CONTACT_MAX_GROUPS, a negative atom, a group outside
+ * [0, ngroups), r_cut not finite or <= 0, min_sep outside [1, ngroups - 1], a native pair with equal groups, out of range, closer than
+ * min_sep or listed twice in either order, names[2] and nnative disagreeing, names already defined or equal to each other.
+ * vmd_ir_geometry_atoms: the entries' atoms. */
+#define VMD_CONTACT_MAX_GROUPS 2048
+typedef struct vmd_contact_sites_t {
+    size_t nentries; const int32_t* atom; const int32_t* group;   /* entry i: an atom and its group, 0 <= group < ngroups */
+    size_t ngroups;
+    size_t nnative;  const int32_t (*native)[2];                   /* group pairs of the reference set; may be 0 / NULL */
+} vmd_contact_sites_t;
+bool vmd_ir_add_contacts(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut, uint32_t min_sep);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
@@ -432,6 +457,14 @@ void     vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites);
  * O 1.52, F 1.47, P 1.80, S 1.80, CL 1.75, BR 1.85, I 1.98, anything else 2.00.  Writes the first `cap` of them to `out` (NULL: count
  * only) and returns num_atoms; 0 + vmd_last_error on a NULL topology. */
 size_t   vmd_topology_vdw_radii(const vmd_topology_t* topology, float* out, size_t cap);
+/* Contact sites from a topology (DECISION D-CT-TOPOLOGY; no coordinates): an entry for every atom - heavy_only: for every atom whose element
+ * is not H, compared without regard to case - in ascending atom order; its group is the atom's residue_index renumbered densely in order
+ * of first appearance among the entries.  No native list.  A NULL residue_index is one group (which vmd_ir_add_contacts refuses, not this
+ * helper).  NULL + vmd_last_error on a NULL topology; the view lives as long as the object. */
+typedef struct vmd_contact_sites_owned_t vmd_contact_sites_owned_t;
+vmd_contact_sites_owned_t* vmd_topology_contact_sites(const vmd_topology_t* topology, bool heavy_only);
+const vmd_contact_sites_t* vmd_contact_sites_view(const vmd_contact_sites_owned_t* sites);
+void     vmd_contact_sites_free(vmd_contact_sites_owned_t* sites);
 /* The same, statement by statement: what the front-end understands is compiled, every other statement is REPORTED instead of failing the
  * script - VIAMD's own default script (src/main.cpp:528) carries `a1 = angle(2,1,3) in resname("ALA");` and
  * `{lin,plan,iso} = shape_weights(all);` next to its distance / rdf / sdf statements (both compile with the opt-in features of
@@ -626,6 +659,19 @@ bool vmd_eval_sasa(vmd_script_eval_t* eval, const char* name, double* mean_area,
 #define VMD_SASA_ATOMS_FAILED ((size_t)-1)
 size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
                            uint32_t* counts, size_t cap);
+
+/* A contact map (any name of a vmd_ir_add_contacts statement) read from its record as it stands - partially evaluated or
+ * merged alike: occupancy double[P] = count / frames in condensed pair order, frames: the count; each may be NULL.  F == 0 answers zeros.
+ * false + vmd_last_error: an unknown property, a property of another form. */
+bool vmd_eval_contacts(vmd_script_eval_t* eval, const char* name, double* occupancy, uint64_t* frames);
+/* The group pairs in contact in ONE frame, on demand (any name of the statement), under vmd_eval_hbond_pairs' contract: nothing
+ * accumulated is touched, it may be called while pool threads are inside vmd_eval_frame_range.  All pairs from the raw frame.  Returns the
+ * number of pairs and writes the first `cap` as {g, h}, g < h, in ascending condensed index (out may be NULL with cap == 0);
+ * VMD_CONTACT_PAIRS_FAILED + vmd_last_error on failure.  A host gets a native list this way: an IR without natives, the reference frame
+ * queried, a second IR with the list. */
+#define VMD_CONTACT_PAIRS_FAILED ((size_t)-1)
+size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                              int32_t (*out)[2], size_t cap);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

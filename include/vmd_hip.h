@@ -23,6 +23,7 @@
  *   vmd_hip_within_atoms, vmd_hip_within_brute_atoms, vmd_hip_sdf_scatter_masked  <- sdf() over a within() shell, shell masks
  *   vmd_hip_within_atoms_expr, vmd_hip_within_brute_expr, vmd_hip_shell_expr_finish  <- and / or / not over within() shells
  *   vmd_hip_sorted_atoms, vmd_hip_hbond_*  <- hydrogen bonds
+ *   vmd_hip_contact_*  <- residue contact maps
  *   vmd_hip_sasa_*  <- solvent-accessible surface area
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
@@ -373,6 +374,30 @@ int vmd_hip_sasa_list(void* stream, const float* xyz, size_t row_stride, const f
                       const int32_t* envl, int nenv, uint32_t* canon, const float* r_meas, const float* r_env, float rmax_env,
                       const float* points, int npoints, float r_cut, int closed, uint32_t* counts_out);
 int vmd_hip_sasa_finish(void* stream, const uint64_t* totals, int B, float* out, uint64_t* frames_row, const uint32_t* skip_flag);
+
+/* K14: residue contact maps, DESIGN 1.16.  The list `ent` (nent atoms) with `grp` (the group of every entry, 0 <= grp < ngroups) is walked
+ * against ITSELF.  Groups g < h with h - g >= min_sep are in contact in frame b when an entry acting for g and an entry acting for h stand at
+ * 0 <= d < r_cut (closed != 0: <= r_cut; the pair distance of K6); an entry acts for the group of the lowest list entry whose wrapped
+ * coordinates coincide with its own bit for bit (D-CT-COINCIDENT).  bits: u32[B][W], W = ceil(P / 32), P = ngroups (ngroups - 1) / 2: bit
+ * p & 31 of word p >> 5 is pair p = g (2 ngroups - g - 1) / 2 + (h - g - 1).  Nothing happens when *skip_flag != 0.  B <= 65535,
+ * 2 <= ngroups <= 2048.
+ *   vmd_hip_contact_atoms   the cell walk of K8 over the cell-sorted copy of the list, one lane per entry, every hit visited; bits are
+ *                           cleared by the call.  ident: vmd_hip_sorted_atoms' table of the copy.  lds_rows != 0: a block ORs its hits
+ *                           into LDS bit rows of the groups its entries act for and flushes the nonzero words (the same bits)
+ *   vmd_hip_contact_brute   all pairs from the raw frame (any cell, any cutoff), the upper triangle of the entry pairs; bits are cleared by
+ *                           the call; canon: scratch, u32[B][nent]
+ *   vmd_hip_contact_finish  bits -> results: acc[p] += the frames of the B with bit p set (acc u64[P + 1], owned by this launch: a plain
+ *                           add), acc[P] += B; out_count[b] = (float)popcount(row b); with nnative > 0 (native: u32[nnative] pair indices)
+ *                           out_q[b] = (float)n_b / (float)nnative.  counts: scratch u32[2 B] */
+int vmd_hip_contact_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes, uint32_t pbc_flags,
+                          int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, uint32_t min_sep, const float* sorted,
+                          const uint32_t* cell_start, int nent_pad, const uint32_t* ident, vmd_grid_t grid, float r_cut, int closed,
+                          int lds_rows, uint32_t* bits, const uint32_t* skip_flag);
+int vmd_hip_contact_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                          int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, uint32_t min_sep, uint32_t* canon,
+                          float r_cut, int closed, uint32_t* bits, const uint32_t* skip_flag);
+int vmd_hip_contact_finish(void* stream, const uint32_t* bits, int B, int ngroups, const uint32_t* native, int nnative, uint32_t* counts,
+                           float* out_count, float* out_q, uint64_t* acc, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -88,6 +88,11 @@ class SasaSitesC(C.Structure):           # vmd_sasa_sites_t (include/vmd_eval.h)
                 ("nenv", C.c_size_t), ("env", C.POINTER(C.c_int32)), ("env_radius", C.POINTER(C.c_float))]
 
 
+class ContactSitesC(C.Structure):        # vmd_contact_sites_t (include/vmd_eval.h)
+    _fields_ = [("nentries", C.c_size_t), ("atom", C.POINTER(C.c_int32)), ("group", C.POINTER(C.c_int32)), ("ngroups", C.c_size_t),
+                ("nnative", C.c_size_t), ("native", C.POINTER(C.c_int32))]
+
+
 class ShellC(C.Structure):               # vmd_shell_t (include/vmd_eval.h)
     _fields_ = [("ref", c_int32_p), ("nref", C.c_size_t), ("rmin", C.c_float), ("rmax", C.c_float)]
 
@@ -204,6 +209,12 @@ SIGNATURES = [
     ("vmd_eval_sasa_atoms", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, C.POINTER(C.c_uint32),
                                          C.c_size_t]),
     ("vmd_topology_vdw_radii", C.c_size_t, [C.POINTER(TopologyC), c_float_p, C.c_size_t]),
+    ("vmd_ir_add_contacts", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(ContactSitesC), C.c_float, C.c_uint32]),
+    ("vmd_eval_contacts", C.c_bool, [_vp, C.c_char_p, c_double_p, c_uint64_p]),
+    ("vmd_eval_contact_pairs", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, c_int32_p, C.c_size_t]),
+    ("vmd_topology_contact_sites", _vp, [C.POINTER(TopologyC), C.c_bool]),
+    ("vmd_contact_sites_view", C.POINTER(ContactSitesC), [_vp]),
+    ("vmd_contact_sites_free", None, [_vp]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
     ("vmd_ir_add_rdf_shell", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, C.POINTER(ShellC), c_int32_p, C.c_size_t,
                                         C.POINTER(ShellC), C.c_float, C.c_float]),
@@ -425,6 +436,11 @@ SIGNATURES = [
     ("vmd_hip_sasa_list", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_float, _vp,
                                     C.c_int, C.c_float, C.c_int, _vp]),
     ("vmd_hip_sasa_finish", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
+    ("vmd_hip_contact_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_uint32,
+                                        _vp, _vp, C.c_int, _vp, Grid, C.c_float, C.c_int, C.c_int, _vp, _vp]),
+    ("vmd_hip_contact_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_uint32,
+                                        _vp, C.c_float, C.c_int, _vp, _vp]),
+    ("vmd_hip_contact_finish", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

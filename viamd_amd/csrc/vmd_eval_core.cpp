@@ -244,6 +244,17 @@ void build_sasa_plan(vmd_script_eval_t* e) {
     }
 }
 
+// contact maps: ONE interned selection, the entry list, on both sides - its cell-sorted copy is what its own entries walk
+void build_contact_plan(vmd_script_eval_t* e) {
+    e->contact_props.clear();
+    for (size_t i = 0; i < e->props.size(); ++i) {
+        PropState* p = e->props[i].get();
+        if (p->prop.form != Form::CONTACT_COUNT) continue;
+        p->sel_a = p->sel_b = intern_selection(e, p->prop.a);
+        e->contact_props.push_back((int)i);
+    }
+}
+
 uint32_t shell_expr_live(uint32_t truth, const std::vector<int>& order, size_t pos) {
     uint32_t done = 0, later = 0;
     for (size_t k = 0; k < order.size(); ++k) { if (k < pos) done |= 1u << order[k]; else if (k > pos) later |= 1u << order[k]; }
@@ -379,7 +390,14 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         case Form::SS_CLASS: st->dist_P = p.a.size(); aggregate = false; break;
         case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
         case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
-        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::SASA_AREA: break;
+        case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::SASA_AREA:
+        case Form::CONTACT_COUNT: break;
+        case Form::CONTACT_NATIVE: st->dist_P = 1; break;       // one fraction per frame (the descriptor carries no set)
+        case Form::CONTACT_OCC:
+            // one u64 word per group pair and the frame count (16 MB at 2048 groups); the float view is the words as numbers
+            pinned_views(p.K + 1);
+            st->data.dim[0] = (int32_t)(p.K + 1); st->data.dim[1] = 1; st->data.dim[2] = st->data.dim[3] = 0;
+            break;
         case Form::SASA_OCC:
             // one u64 word per measured entry and the frame count; the float view is the words as numbers, as a map's
             pinned_views(p.K + 1);
@@ -435,6 +453,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     build_within_plan(e.get());
     build_hbond_plan(e.get());
     build_sasa_plan(e.get());
+    build_contact_plan(e.get());
     build_expr_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
@@ -822,7 +841,9 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
             if (p->prop.counts_view()) {
                 // (a donor row at most one count per acceptor and frame, an acceptor row one per pair)
                 // (a row at most npoints per frame)
-                const long double per_frame = p->prop.form == Form::SASA_OCC ? (long double)p->prop.m
+                // (a pair is in contact in a frame or it is not)
+                const long double per_frame = p->prop.form == Form::CONTACT_OCC ? 1.0L
+                        : p->prop.form == Form::SASA_OCC ? (long double)p->prop.m
                         : p->prop.form == Form::HBOND_OCC ? (long double)std::max(p->prop.K, p->prop.m)
                         : (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
                 const long double b = (long double)eval->num_frames * per_frame;
@@ -1100,6 +1121,88 @@ extern "C" size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name,
     return nmeas;
 }
 
+// ---- contact maps.  Any name of the statement names it: -> the index of its count, or props.size() + vmd_last_error
+static size_t contact_statement(vmd_script_eval_t* e, const char* name) {
+    size_t pi = e->props.size();
+    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
+    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return pi; }
+    const Form f = e->props[pi]->prop.form;
+    if (f == Form::CONTACT_OCC && pi >= 1) pi -= 1;
+    else if (f == Form::CONTACT_NATIVE && pi >= 2) pi -= 2;
+    if (e->props[pi]->prop.form != Form::CONTACT_COUNT || pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::CONTACT_OCC) {
+        vmd_fail("'%s' is not a contacts property", name); return e->props.size(); }
+    return pi;
+}
+
+// count / frames per group pair, read from the record as it stands - a partial evaluation, a merged one; under the eval's mutex, touching
+// nothing it keeps
+extern "C" bool vmd_eval_contacts(vmd_script_eval_t* eval, const char* name, double* occupancy, uint64_t* frames) {
+    if (!eval || !name) return vmd_fail("vmd_eval_contacts: NULL argument");
+    const size_t pi = contact_statement(eval, name);
+    if (pi == eval->props.size()) return false;
+    if (!occupancy && !frames) return true;        // (asked for the form alone)
+    PropState* p = eval->props[pi + 1].get();
+    const size_t P = p->prop.K;
+    std::vector<uint64_t> acc(p->ncounts);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        HIP_OK(hipSetDevice(eval->device));
+        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
+        HIP_OK(hipStreamSynchronize(eval->stream));
+    }
+    const uint64_t F = acc[P];
+    if (frames) *frames = F;
+    if (occupancy) for (size_t k = 0; k < P; ++k) occupancy[k] = F ? (double)acc[k] / (double)F : 0.0;
+    return true;
+}
+
+// The group pairs in contact in one frame.  One frame on demand, as vmd_eval_hbond_pairs: all pairs from the raw frame into one row of
+// bits, read back and listed on the host in ascending pair index.  Nothing the evaluation keeps is touched: canon and the row live in one
+// buffer of the eval that only this call uses (kept between calls).
+extern "C" size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                                         int32_t (*out)[2], size_t cap) {
+    const size_t failed = VMD_CONTACT_PAIRS_FAILED;
+    if (!eval || !traj || !name || (!out && cap)) { vmd_fail("vmd_eval_contact_pairs: NULL argument"); return failed; }
+    vmd_script_eval_t* e = eval;
+    const size_t pi = contact_statement(e, name);
+    if (pi == e->props.size()) return failed;
+    PropState* p = e->props[pi].get();
+    if (frame >= e->num_frames) { vmd_fail("vmd_eval_contact_pairs: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
+    const Property& d = p->prop;
+    const size_t nent = d.a.size(), G = d.K, P = G * (G - 1) / 2, W = (P + 31) / 32;
+    std::vector<uint32_t> row(W);
+    {
+        std::lock_guard<std::mutex> lock(eval->mtx);
+        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
+        const size_t num_atoms = traj->num_atoms(traj->inst);
+        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
+        auto run = [&]() -> bool {
+            vmd_device_view_t view;
+            memset(&view, 0, sizeof(view));
+            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
+            BatchSrc src;
+            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+            if (!e->d_one_contacts.ensure(nent + W)) return false;
+            uint32_t* canon = e->d_one_contacts.p;
+            uint32_t* bits = canon + nent;
+            KRN_OK(vmd_hip_contact_brute(e->stream, src.base, 0, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), 1, p->d_a.p,
+                    p->d_c.p, (int)nent, (int)G, d.ct_min_sep, canon, d.rmax, e->spec.within_closed ? 1 : 0, bits, nullptr));
+            HIP_OK(hipMemcpyAsync(row.data(), bits, W * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+            HIP_OK(hipStreamSynchronize(e->stream));
+            return true;
+        };
+        if (!run()) return failed;
+    }
+    size_t found = 0, pidx = 0;
+    for (size_t g = 0; g + 1 < G; ++g)
+        for (size_t h = g + 1; h < G; ++h, ++pidx)
+            if ((row[pidx >> 5] >> (pidx & 31)) & 1u) {
+                if (found < cap) { out[found][0] = (int32_t)g; out[found][1] = (int32_t)h; }
+                found += 1;
+            }
+    return found;
+}
+
 // ---- the hot call -----------------------------------------------------------------------------------------------
 bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_atoms) {
     for (auto& s : e->sels) {
@@ -1116,7 +1219,21 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
         };
         std::vector<float> tmp;
         switch (d.form) {
-        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC: break;      // the sets of an rdf are interned selections; a map, the populations and an occupancy have none
+        case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC: case Form::CONTACT_OCC:
+        case Form::CONTACT_NATIVE: break;      // the sets of an rdf are interned selections; a map, the populations, an occupancy and a native fraction have none
+        case Form::CONTACT_COUNT: {
+            // the entries' atoms and groups in list order (the atoms are an interned selection as well), the native pairs as
+            // condensed indices
+            const uint32_t G = (uint32_t)d.K;
+            std::vector<uint32_t> nat(d.ct_native.size() / 2);
+            for (size_t k = 0; k < nat.size(); ++k) {
+                const uint32_t g = (uint32_t)d.ct_native[2 * k], h = (uint32_t)d.ct_native[2 * k + 1];
+                nat[k] = g * (2u * G - g - 1u) / 2u + (h - g - 1u);
+            }
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_c.upload(d.ct_group.data(), d.ct_group.size(), e->stream) ||
+                (!nat.empty() && !p->d_ct_native.upload(nat.data(), nat.size(), e->stream))) return false;
+            break;
+        }
         case Form::SASA_AREA: {
             // both lists in list order, R = radius + probe (one fp32 add per entry), the weights
             // w_i = llround(4 pi R_i^2 / P * 2^20) formed in double, and the point table vmd_sasa_points hands out

@@ -181,6 +181,9 @@ struct Options {
     // a shell expression: 1 = a lane whose outcome the earlier terms decided does no walk; 0 = every lane is tested against every
     // term (the A/B of the measurement; results are identical)
     std::atomic<int> shell_expr_skip{1};
+    // contact maps: 1 = the walk ORs a block's hits into LDS bit rows first and flushes the nonzero words; 0 = every hit goes
+    // to the global bit matrix behind a plain load (the A/B of the measurement, DESIGN 1.16: the variant is faster; the bits are identical)
+    std::atomic<int> contact_lds_rows{1};
     // secondary structure: bytes of bit matrices a batch may hold (frames x nseg^2 / 2); a larger batch runs in sub-batches
     // of frames, never below one frame.  256 MiB: the 1 000 frames x 500 segments of DESIGN 1.10's system take 128 MB in one go
     std::atomic<int> ss_scratch_bytes{256 << 20};
@@ -401,6 +404,11 @@ enum class Form : int {
     // per frame; the record behind it (K = the measured entries, m = npoints) is a MAP-class record of u64 accumulators, [K + 1], that the
     // area's launch adds to
     SASA_AREA, SASA_OCC,
+    // `{count, map[, q]} = contacts(sites, r_cut, min_sep)`: two or three descriptors in a row.  The count - a = the entries'
+    // atoms, ct_group = their groups, ct_native = the native group pairs, K = the groups, ct_min_sep, rmax = r_cut - has one value per frame;
+    // the map behind it (K = P, the group pairs) is a MAP-class record of u64 accumulators, [P + 1], that the count's launch adds to; the
+    // native fraction behind that (K = the native pairs), where there are natives, has one value per frame, written by the count's launch
+    CONTACT_COUNT, CONTACT_OCC, CONTACT_NATIVE,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -435,8 +443,11 @@ constexpr FormFacts kFormFacts[] = {
     /* HBOND_OCC   */ {ResultClass::MAP,          0, "hbonds",        {"", ""},         nullptr, true,  15},
     /* SASA_AREA   */ {ResultClass::TEMPORAL,     0, "sasa",          {"", "\xC3\x85\xC2\xB2"}, nullptr, true, 16},  // square Angstrom
     /* SASA_OCC    */ {ResultClass::MAP,          0, "sasa",          {"", ""},         nullptr, true,  17},
+    /* CONTACT_COUNT  */ {ResultClass::TEMPORAL,  0, "contacts",      {"", ""},         nullptr, true,  18},    // counts, a fraction
+    /* CONTACT_OCC    */ {ResultClass::MAP,       0, "contacts",      {"", ""},         nullptr, true,  19},
+    /* CONTACT_NATIVE */ {ResultClass::TEMPORAL,  0, "contacts",      {"", ""},         nullptr, true,  20},
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::SASA_OCC + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::CONTACT_NATIVE + 1, "one row of kFormFacts per Form");
 static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES && VMD_SASA_MAX_POINTS == VMD_SASA_POINTS_MAX,
               "the kernels' limits are the interface's");
 
@@ -472,6 +483,8 @@ struct Property {
     std::vector<float> sasa_ra, sasa_rb;            // SASA_AREA: the radii of a and b as given; the probe; the points per sphere
     float sasa_probe = 0.0f;
     uint32_t sasa_npoints = 0;
+    uint32_t ct_min_sep = 0;                        // CONTACT_COUNT: the least h - g of a pair; the group of every entry of a; the native
+    std::vector<int32_t> ct_group, ct_native;       // pairs, flat {g, h} with g < h (not atoms: they stay out of a .. d)
     bool is_expr_sdf() const { return form == Form::SDF && !expr_terms.empty(); }
     bool behind_cells() const { return facts().behind_cells || is_shell_sdf() || is_expr_sdf(); }     // launch_rdf launches it, not launch_property
 };
@@ -646,6 +659,11 @@ struct PropState {
     DevBuf<uint32_t> d_sasa_w;
     DevBuf<uint64_t> d_sasa_total;
     float sasa_rmax_env = 0.0f;
+    // contact maps, the count: sel_a == sel_b, the interned entry list; d_a the entries' atoms, d_c their groups, d_ct_native
+    // the native pairs' condensed indices; the identity table goes to d_hb_ident; the batch's bit matrix u32[nb][W], its counts u32[2 nb],
+    // and the native fraction's rows (they travel as the rows of the CONTACT_NATIVE property behind the map)
+    DevBuf<uint32_t> d_ct_native, d_ct_bits, d_ct_count;
+    DevBuf<float> d_ct_q;
     // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
@@ -876,6 +894,8 @@ struct vmd_script_eval_t {
     size_t ss_scratch_bytes = 0;
     DevBuf<uint32_t> d_one_sasa;                        // vmd_eval_sasa_atoms: one frame's canonical entries and its point counts
     std::vector<int> sasa_props;                        // indices into props of the accessible areas: behind the cell builds too
+    DevBuf<uint32_t> d_one_contacts;                    // vmd_eval_contact_pairs: one frame's canonical entries and its row of bits
+    std::vector<int> contact_props;                     // indices into props of the contact counts: behind the cell builds too
     std::vector<int> hbond_props;                       // indices into props of the hydrogen-bond counts: behind the cell builds too
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
@@ -973,6 +993,7 @@ void build_within_plan(vmd_script_eval_t* e);
 
 void build_hbond_plan(vmd_script_eval_t* e);
 void build_sasa_plan(vmd_script_eval_t* e);
+void build_contact_plan(vmd_script_eval_t* e);
 void build_expr_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
@@ -1115,6 +1136,7 @@ struct RangeRun {
     size_t row = 0;                     // next scratch row of d_pass
     std::vector<RdfCommit> commits;
     std::vector<int> sasa_route;        // build_sasa_cells' answer per sasa statement of the batch: 1 the walk, 0 all pairs
+    std::vector<int> contact_route;     // build_contact_cells' answer per contacts statement, likewise
 
     RawSlot* slot_of(size_t bi) const { return raw_ring ? &e->raw_slots[bi % vmd_script_eval_t::kRawSlots] : nullptr; }
     Stage& stage_of(size_t bi) const { return e->stages[bi % (stage_ahead + 1)]; }
@@ -1154,6 +1176,8 @@ struct RangeRun {
     bool launch_hbonds(BatchCtx& c);
     bool build_sasa_cells(BatchCtx& c);
     bool launch_sasa(BatchCtx& c);
+    bool build_contact_cells(BatchCtx& c);
+    bool launch_contacts(BatchCtx& c);
     bool launch_rdf(BatchCtx& c);
     bool launch_shell_exprs(BatchCtx& c);
     bool launch_expr_sdfs(BatchCtx& c);

@@ -52,6 +52,8 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         // a neighbour query per measured entry, npoints bits to keep per entry (in units of 32), the environment sorted and identified
         case Form::SASA_AREA: w += (uint64_t)p.a.size() * (1 + (p.sasa_npoints + 31) / 32) + 2 * (uint64_t)p.b.size(); break;
         case Form::SASA_OCC: break;                                          // added to by its area's launch
+        case Form::CONTACT_COUNT: w += 4 * (uint64_t)p.a.size(); break;      // 1.14's rule for a list against itself - a query per entry, the list sorted and identified
+        case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: break;            // written by their count's launch
         }
     }
     return w;
@@ -502,6 +504,51 @@ extern "C" bool vmd_ir_add_sasa(vmd_script_ir_t* ir, const char* const names[2],
     return commit(ir, tp, 2);
 }
 
+// `{count, map[, q]} = contacts(sites, r_cut, min_sep)`: the per-frame count, the record of the map and, with a native list,
+// the native fraction - two or three descriptors in a row
+extern "C" bool vmd_ir_add_contacts(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut,
+                                    uint32_t min_sep) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names || !sites) return vmd_fail("contacts needs its property names and the sites");
+    if (sites->nnative > 0 && !names[2]) return vmd_fail("contacts with a native list needs a third property name");
+    if (sites->nnative == 0 && names[2]) return vmd_fail("contacts without a native list takes two property names (the third must be NULL)");
+    const int nnames = sites->nnative > 0 ? 3 : 2;
+    if (!names_ok(ir, names, nnames)) return false;
+    if (sites->nentries == 0 || !sites->atom || !sites->group) return vmd_fail("contacts entry list is empty");
+    if (!idx_ok(sites->atom, sites->nentries, "contacts entry list")) return false;
+    if (sites->nentries > kMaxSet) return vmd_fail("contacts set too large");
+    if (sites->ngroups < 2 || sites->ngroups > VMD_CONTACT_MAX_GROUPS) return vmd_fail("contacts group count must lie in [2, %d]", VMD_CONTACT_MAX_GROUPS);
+    const int64_t G = (int64_t)sites->ngroups;
+    for (size_t i = 0; i < sites->nentries; ++i)
+        if (sites->group[i] < 0 || sites->group[i] >= G) return vmd_fail("contacts entry %zu names group %d outside [0, %zu)", i, sites->group[i], sites->ngroups);
+    if (!std::isfinite(r_cut) || !(r_cut > 0.0f)) return vmd_fail("contacts cutoff must be finite and positive");
+    if (min_sep < 1 || (int64_t)min_sep > G - 1) return vmd_fail("contacts minimum separation must lie in [1, %zu]", sites->ngroups - 1);
+    if (sites->nnative > 0 && !sites->native) return vmd_fail("contacts native list is NULL");
+    if (sites->nnative > (size_t)(G * (G - 1) / 2)) return vmd_fail("contacts native list names a pair twice");
+    Property t = make_property(Form::CONTACT_COUNT, names[0]);
+    std::vector<uint8_t> seen(sites->nnative ? (size_t)(G * (G - 1) / 2) : 0, 0);
+    for (size_t k = 0; k < sites->nnative; ++k) {
+        int64_t g = sites->native[k][0], h = sites->native[k][1];
+        if (g < 0 || h < 0 || g >= G || h >= G) return vmd_fail("contacts native pair %zu names a group outside [0, %zu)", k, sites->ngroups);
+        if (g == h) return vmd_fail("contacts native pair %zu names group %d twice", k, (int)g);
+        if (g > h) std::swap(g, h);
+        if (h - g < (int64_t)min_sep) return vmd_fail("contacts native pair %zu is closer than the minimum separation", k);
+        const size_t pidx = (size_t)(g * (2 * G - g - 1) / 2 + (h - g - 1));
+        if (seen[pidx]) return vmd_fail("contacts native pair %zu is listed twice", k);
+        seen[pidx] = 1;
+        t.ct_native.push_back((int32_t)g); t.ct_native.push_back((int32_t)h);
+    }
+    t.a.assign(sites->atom, sites->atom + sites->nentries);
+    t.ct_group.assign(sites->group, sites->group + sites->nentries);
+    t.aoff = {0, (int32_t)sites->nentries};
+    t.rmin = 0.0f; t.rmax = r_cut;
+    t.K = sites->ngroups; t.ct_min_sep = min_sep;
+    Property tp[3] = {std::move(t), make_property(Form::CONTACT_OCC, names[1]), make_property(Form::CONTACT_NATIVE, names[2] ? names[2] : "")};
+    tp[1].K = (size_t)(G * (G - 1) / 2);
+    tp[2].K = sites->nnative;
+    return commit(ir, tp, nnames);
+}
+
 // what vmd_ir_geometry_atoms has counted and written so far
 struct AtomSink {
     int32_t* out; size_t cap, n = 0;
@@ -525,7 +572,12 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         size_t c0 = 0, c1 = 0;
         switch (p.form) {
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC:
+        case Form::CONTACT_OCC: case Form::CONTACT_NATIVE:
             return 0;
+        case Form::CONTACT_COUNT:   // the entries' atoms (one context)
+            if (context > 0) return 0;
+            s.put(p.a);
+            return s.n;
         case Form::SASA_AREA:       // the measured atoms, then the environment (one context)
             if (context > 0) return 0;
             s.put(p.a); s.put(p.b);
@@ -596,8 +648,12 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
         case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: case Form::HBOND_OCC: break;
         case Form::HBOND_COUNT: h = fnv1a(h, &p.hb_angle, sizeof(float)); break;      // (the hydrogens are c, hashed above)
-        case Form::SASA_OCC: break;
-        case Form::SASA_AREA:                                           // (the lists are a and b, boff says where a's radii end)
+        case Form::SASA_OCC: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: break;
+        case Form::CONTACT_COUNT:                                       // (the atoms are a, r_cut is rmax, the groups' number K; one group per entry of a, the rest is the native list)
+            h = fnv1a(h, &p.ct_min_sep, sizeof(uint32_t)); h = fnv1a(h, p.ct_group.data(), p.ct_group.size() * sizeof(int32_t));
+            h = fnv1a(h, p.ct_native.data(), p.ct_native.size() * sizeof(int32_t));
+            break;
+        case Form::SASA_AREA:                                          // (the lists are a and b, boff says where a's radii end)
             h = fnv1a(h, &p.sasa_probe, sizeof(float)); h = fnv1a(h, &p.sasa_npoints, sizeof(uint32_t));
             h = fnv1a(h, p.sasa_ra.data(), p.sasa_ra.size() * sizeof(float)); h = fnv1a(h, p.sasa_rb.data(), p.sasa_rb.size() * sizeof(float));
             break;

@@ -467,6 +467,61 @@ bool RangeRun::launch_sasa(BatchCtx& c) {
     return true;
 }
 
+// ---- contact maps.  launch_sasa's placement and rules: the record is added to behind the LAST cell build of the batch, every
+// statement's own build first (ident_routes with the entry list on both sides: it is sorted once, on the grid a within count of r_cut gets;
+// all pairs below shell_brute_below entries or where no grid exists) as a step of its own in front of launch_hbonds, every kernel under the
+// overflow flag, and a copy that another statement's build has re-sorted on another grid sends its statement to all pairs for this batch,
+// which sets the same bits.  Sub by sub the walk or all pairs into the batch's bit matrix (cleared by the launch, so also in a repeated
+// batch), then sub by sub the finish into the sub's partial of the record.
+bool RangeRun::build_contact_cells(BatchCtx& c) { return ident_routes(c, e->contact_props, &contact_route); }
+
+bool RangeRun::launch_contacts(BatchCtx& c) {
+    const int closed = e->spec.within_closed ? 1 : 0;
+    for (size_t i = 0; i < e->contact_props.size(); ++i) {
+        const int pi = e->contact_props[i];
+        PropState* p = e->props[pi].get();
+        const Property& d = p->prop;
+        const int nnative = (int)(d.ct_native.size() / 2);
+        if ((size_t)pi + 1 + (nnative ? 1 : 0) >= e->props.size() || e->props[pi + 1]->prop.form != Form::CONTACT_OCC ||
+            (nnative && e->props[pi + 2]->prop.form != Form::CONTACT_NATIVE))
+            return vmd_fail("contact count '%s' has lost its record", d.name.c_str());
+        PropState* m = e->props[pi + 1].get();
+        Selection* sr = e->sels[p->sel_b].get();
+        const int nent = (int)d.a.size(), G = (int)d.K;
+        const size_t W = ((size_t)G * (size_t)(G - 1) / 2 + 31) / 32;
+        vmd_grid_t grid;
+        const float* d_gb = nullptr;
+        int have_grid = 0;
+        if (!p->d_out.ensure(c.nb) || (nnative && !p->d_ct_q.ensure(c.nb)) || !p->d_ct_count.ensure(2 * c.nb) || !p->d_ct_bits.ensure(c.nb * W) ||
+            !ident_table(c, p, contact_route[i], &have_grid, &grid, &d_gb)) return false;
+        const Stage& st = *c.src;
+        e->prof.begin(have_grid ? "contact_atoms" : "contact_brute", e->stream);
+        for (auto& su : c.subs) {
+            const float* xyz = st.base + su.off * st.frame_stride;
+            uint32_t* bits = p->d_ct_bits.p + su.off * W;
+            if (have_grid)
+                KRN_OK(vmd_hip_contact_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, c.pbc, (int)su.nb, p->d_a.p,
+                        p->d_c.p, nent, G, d.ct_min_sep, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad,
+                        sr->cell_start.p + su.off * (size_t)(grid.ncell + 1), sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid,
+                        d.rmax, closed, g_opt.contact_lds_rows.load(), bits, e->d_overflow.p));
+            else
+                KRN_OK(vmd_hip_contact_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
+                        p->d_a.p, p->d_c.p, nent, G, d.ct_min_sep, p->d_hb_ident.p + su.off * (size_t)nent, d.rmax, closed, bits,
+                        e->d_overflow.p));
+        }
+        e->prof.end(e->stream);
+        e->prof.begin("contact_finish", e->stream);
+        for (auto& su : c.subs)       // (every sub has its own rows of the bit matrix and of the counts)
+            KRN_OK(vmd_hip_contact_finish(e->stream, p->d_ct_bits.p + su.off * W, (int)su.nb, G, p->d_ct_native.p, nnative,
+                    p->d_ct_count.p + 2 * su.off, p->d_out.p + su.off, nnative ? p->d_ct_q.p + su.off : nullptr, acc_of(m, su),
+                    e->d_overflow.p));
+        e->prof.end(e->stream);
+        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
+        if (nnative && !queue_temporal_rows(c, pi + 2, p->d_ct_q.p)) return false;
+    }
+    return true;
+}
+
 // ---- shell expressions: one pass per term over T in atom order, ascending |R_i|, then the finish.  Walk or all pairs per term
 // by within_route's RULE; the cell-sorted copies come from build_pair, so one that another pass of the batch built on the same grid is
 // reused.  The bits start clean in every batch and in every repeat of one; the counts travel to the host from here, like
@@ -551,7 +606,7 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     commits.clear();
     row = 0;
     forked = false;
-    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_sasa_cells(c) || !launch_hbonds(c) || !launch_sasa(c) || !launch_shell_sdfs(c) ||
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_sasa_cells(c) || !build_contact_cells(c) || !launch_hbonds(c) || !launch_sasa(c) || !launch_contacts(c) || !launch_shell_sdfs(c) ||
         !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -738,7 +793,7 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
     switch (d.form) {
     case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: case Form::SASA_AREA:
-    case Form::SASA_OCC: return true;     // (behind the cell builds, above)
+    case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: return true;     // (behind the cell builds, above)
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);

@@ -18,6 +18,8 @@
 //   rmsf           -> rmsd's sums, k_rmsf_rotation, k_rmsf_accumulate (large sets) / k_rmsf_small
 //   hydrogen bonds -> k_sorted_atoms + k_hbond_atoms (the cell walk) / k_hbond_canon + k_hbond_brute (all pairs), k_hbond_finish
 //   accessible area -> k_sorted_atoms + k_sasa_atoms (the cell walk) / k_hbond_canon + k_sasa_brute (all pairs), k_sasa_finish
+//   contact maps   -> k_sorted_atoms + k_contact_atoms (the cell walk) / k_hbond_canon + k_contact_brute (all pairs),
+//                                   k_contact_finish_rows / _frames / _out
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -4788,6 +4790,242 @@ __global__ __launch_bounds__(256) void k_sasa_finish(const uint64_t* total, int 
     if (i == 0) *frames_row += (uint64_t)B;
 }
 
+// ------------------------------------------------------------------------------------------------ K14: residue contact maps
+
+// One list of entries (atom, group) against itself.  Groups g < h with h - g >= min_sep are in contact in a frame when an entry acting for g
+// and an entry acting for h pass within()'s pair distance (rule 1 of K12, word for word).  DECISION(D-CT-COINCIDENT): an entry acts - in the
+// lane and as a hit alike - for the group of the LOWEST list entry whose wrapped coordinates coincide with its own bit for bit, so a pair is
+// the same pair from either side.  Every hit of the walk ends in ONE bit of the frame's row of a bit matrix, u32[B][W]: bit p & 31 of word
+// p >> 5 is the pair with the condensed index p (SciPy's pdist order).  Bits are idempotent: however many atom pairs stand behind a group
+// pair, and from whichever side they are found, the row holds the same word.
+__device__ __forceinline__ uint32_t vmd_contact_pair(uint32_t G, uint32_t g, uint32_t h) { return g * (2u * G - g - 1u) / 2u + (h - g - 1u); }
+// (the SIMT emulator's header has __popcll alone)
+__device__ __forceinline__ unsigned vmd_popc_u32(uint32_t v) { return (unsigned)__popcll((unsigned long long)v); }
+
+// the plain load first: a residue pair in contact has several atom pairs in range, met by both of their lanes, so most hits find their bit
+// set and end here.  A stale zero (another XCD's line in this CU's L1) costs one redundant atomic, never a wrong bit.
+__device__ __forceinline__ void vmd_contact_set(uint32_t* row, uint32_t p) {
+    uint32_t* w = row + (p >> 5);
+    const uint32_t m = 1u << (p & 31u);
+    if (!(*w & m)) atomicOr(w, m);
+}
+// groups a, b of an entry pair in range -> the bit, where they are a pair at all
+__device__ __forceinline__ void vmd_contact_hit(uint32_t* row, uint32_t G, uint32_t min_sep, uint32_t a, uint32_t b) {
+    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+    if (hi - lo >= min_sep) vmd_contact_set(row, vmd_contact_pair(G, lo, hi));
+}
+
+struct vmd_contact_atoms_params_t {
+    vmd_cells_params_t c;       // the entries as their cell build read them: raw frame, the GRID's boxes, pbc, the list, grid (no outputs)
+    vmd_within_walk_params_t k; // the cell-sorted copy of the SAME list, the test of within(r_cut, .)
+    const int32_t* grp; uint32_t ngroups, min_sep;
+    const uint32_t* ident;      // k_sorted_atoms' table of the copy, u32[B][k.nref_pad]
+    uint32_t* bits; uint32_t W; // u32[B][W], cleared by the launcher
+    const uint32_t* skip;
+};
+
+// The walk, one lane per entry in list order; its pencil as k_hbond_atoms derives a donor's.  The lane first finds ITSELF in its cell's run
+// of the sorted copy (the slot whose coordinates are its own, bit for bit - vmd_cell_of gives what the build stored): that slot's identity
+// is the entry the lane acts for.  A hit is kept from the lower group's side only; the other lane finds the same pair from its side.
+// LDS (the measured variant): the block first ORs its hits into LDS - the bit rows of the groups its 256 entries act for are ONE run of
+// pair indices, p0(gmin) .. p0(gmax + 1) - 1 with p0(g) = g (2G - g - 1) / 2, because a hit is kept from the lower group's side - and
+// then flushes the nonzero words with one atomicOr each.  A block whose run does not fit VMD_CONTACT_LDS_WORDS (scattered groups, many
+// groups) takes the direct path, block-uniformly.
+#define VMD_CONTACT_LDS_WORDS 4096
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_contact_atoms(vmd_contact_atoms_params_t p) {
+    __shared__ uint32_t s_bits[LDS ? VMD_CONTACT_LDS_WORDS : 1];
+    __shared__ uint32_t s_rng[2];
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the table and the copy are void
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = t < p.c.nsel;
+    if (!LDS && !valid) return;
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
+    const uint32_t* id = p.ident + (size_t)b * p.k.nref_pad;
+    const uint32_t n = (uint32_t)p.c.nsel;
+    const int32_t* grp = p.grp;
+    const uint32_t G = p.ngroups, min_sep = p.min_sep;
+    float xi = 0.0f, yi = 0.0f, zi = 0.0f;
+    int py = 0, pz = 0;
+    uint32_t gl = 0;
+    if (valid) {
+        const uint32_t cell = vmd_cell_of(p.c, b, t, xi, yi, zi);
+        const int pen = (int)(cell / (uint32_t)k.nxf);
+        pz = pen / k.ny; py = pen - pz * k.ny;
+        uint32_t me = (uint32_t)t;
+        const int bxi = __float_as_int(xi), byi = __float_as_int(yi), bzi = __float_as_int(zi);
+        uint32_t s0 = k.csr[cell], s1 = k.csr[cell + 1];
+        if (s1 > n) s1 = n;              // (a table is never trusted beyond the copy it indexes)
+        for (uint32_t s = s0; s < s1; ++s)
+            if (__float_as_int(k.xr[s]) == bxi && __float_as_int(k.yr[s]) == byi && __float_as_int(k.zr[s]) == bzi) {
+                if (id[s] < n) me = id[s];
+                break;
+            }
+        gl = (uint32_t)grp[me];
+    }
+    uint32_t* row = p.bits + (size_t)b * p.W;
+    uint32_t w0 = 0, nw = 0;             // LDS: the block's run of words of the row, nw = 0 where it takes the direct path
+    if (LDS) {
+        if (threadIdx.x == 0) { s_rng[0] = 0xffffffffu; s_rng[1] = 0u; }
+        __syncthreads();
+        if (valid) { vmd_atomic_min_u32(&s_rng[0], gl); atomicMax(&s_rng[1], gl); }
+        __syncthreads();
+        const uint32_t gmin = s_rng[0], gmax = s_rng[1];
+        const uint32_t pa = gmin * (2u * G - gmin - 1u) / 2u, pb = (gmax + 1u) * (2u * G - gmax - 2u) / 2u;
+        if (pb > pa) {
+            w0 = pa >> 5;
+            nw = ((pb - 1u) >> 5) - w0 + 1u;
+            if (nw > VMD_CONTACT_LDS_WORDS) nw = 0;
+        }
+        for (uint32_t i = threadIdx.x; i < nw; i += 256) s_bits[i] = 0u;
+        __syncthreads();
+    }
+    if (valid)
+        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float, float, float) {
+            const uint32_t a = id[j];
+            if (a >= n) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            const uint32_t go = (uint32_t)grp[a];
+            if (!(go > gl && go - gl >= min_sep)) return;
+            const uint32_t pp = vmd_contact_pair(G, gl, go);
+            if (LDS && nw) vmd_contact_set(s_bits, pp - (w0 << 5));
+            else vmd_contact_set(row, pp);
+        });
+    if (LDS) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < nw; i += 256) {
+            const uint32_t v = s_bits[i];
+            if (v && (row[w0 + i] & v) != v) atomicOr(row + w0 + i, v);
+        }
+    }
+}
+
+struct vmd_contact_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc;
+    const int32_t* ent; const int32_t* grp; int nent; uint32_t ngroups, min_sep;
+    const uint32_t* canon;      // k_hbond_canon's table of the list, u32[B][nent]
+    vmd_within_test_t w;        // within(r_cut, .)
+    uint32_t* bits; uint32_t W; const uint32_t* skip;
+};
+
+// All pairs from the raw frame: one lane per entry, the list staged through an LDS tile of 256 with the group of every entry's canonical
+// entry.  The upper triangle of the entry pairs only: tiles from the block's own onward, in its own tile the entries behind the lane's; the
+// group test (no memory, no arithmetic to speak of) stands in front of the distance.
+__global__ __launch_bounds__(256) void k_contact_brute(vmd_contact_brute_params_t p) {
+    __shared__ float s_r[3][256];
+    __shared__ uint32_t s_g[256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const bool valid = t < p.nent;
+    const uint32_t* canon = p.canon + (size_t)b * p.nent;
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    uint32_t gl = 0;
+    if (valid) {
+        const int a = p.ent[t];
+        vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi);
+        gl = (uint32_t)p.grp[canon[t]];
+    }
+    uint32_t* row = p.bits + (size_t)b * p.W;
+    const uint32_t G = p.ngroups, min_sep = p.min_sep;
+    for (int j0 = blockIdx.x * 256; j0 < p.nent; j0 += 256) {
+        __syncthreads();
+        const int nj = p.nent - j0 < 256 ? p.nent - j0 : 256;
+        if ((int)threadIdx.x < nj) {
+            const int jj = threadIdx.x;
+            const int a = p.ent[j0 + jj];
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+            s_g[jj] = (uint32_t)p.grp[canon[j0 + jj]];
+        }
+        __syncthreads();
+        if (valid)
+            for (int jj = j0 == (int)blockIdx.x * 256 ? (int)threadIdx.x + 1 : 0; jj < nj; ++jj) {
+                const uint32_t go = s_g[jj];
+                if ((go > gl ? go - gl : gl - go) < min_sep) continue;
+                float ex, ey, ez;
+                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
+                if (vmd_within_hit(p.w, vmd_d2(ex, ey, ez))) vmd_contact_hit(row, G, min_sep, gl, go);
+            }
+    }
+}
+
+// The finish, behind the walk or all pairs over a frame group: three launches under the overflow flag.
+struct vmd_contact_finish_params_t {
+    const uint32_t* bits; uint32_t W, P; int B;
+    const uint32_t* native; int nnative;       // the native pairs' condensed indices
+    unsigned* counts;                           // u32[2 B], zeroed by the launcher: the pairs, the native pairs in contact per frame
+    float* out_count; float* out_q; uint64_t* acc; const uint32_t* skip;
+};
+__device__ __forceinline__ void vmd_contact_wave_add(unsigned* dst, unsigned n) {
+    int tot = (int)n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += vmd_shfl_xor_i32(tot, o);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(dst, (unsigned)tot);
+}
+// one lane per WORD of the rows, read once per frame, coalesced: the lane counts its 32 pairs at once in 16 bit planes (a carry-save
+// add of the frame's word into c[0 .. 15]: plane k holds bit k of all 32 counts; B <= 65535 frames fit), then adds every nonzero count
+// to its record row.  The 32 rows belong to this lane of this launch alone - a frame group's partial is added to by the launches of one
+// stream, one after the other - so the add is a plain one, as k_hbond_finish's of the frames row.
+__global__ __launch_bounds__(256) void k_contact_finish_rows(vmd_contact_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= q.W) return;
+    uint32_t c[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) c[k] = 0u;
+    const uint32_t* col = q.bits + w;
+    for (int b = 0; b < q.B; ++b) {
+        uint32_t carry = col[(size_t)b * q.W];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { const uint32_t t = c[k] & carry; c[k] ^= carry; carry = t; }
+    }
+    uint32_t any = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) any |= c[k];
+    for (uint32_t i = 0; i < 32u && any; ++i) {
+        if (!((any >> i) & 1u)) continue;
+        uint32_t sum = 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sum |= ((c[k] >> i) & 1u) << k;
+        const uint32_t p = 32u * w + i;
+        if (p < q.P) q.acc[p] += (uint64_t)sum;
+    }
+}
+// grid.y = the frame.  Blocks x < ceil(W / 256): one lane per word, the popcount of the row (a row's last word holds no bit beyond P: only
+// pair indices are ever set), reduced over the wave into one u32 atomic; the blocks behind them: one lane per native pair, its bit likewise.
+__global__ __launch_bounds__(256) void k_contact_finish_frames(vmd_contact_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const int b = blockIdx.y;
+    const uint32_t* row = q.bits + (size_t)b * q.W;
+    const uint32_t wblocks = (q.W + 255u) / 256u;
+    if (blockIdx.x < wblocks) {
+        const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+        uint32_t v = i < q.W ? row[i] : 0u;
+        if (i + 1 == q.W && (q.P & 31u)) v &= (1u << (q.P & 31u)) - 1u;
+        vmd_contact_wave_add(q.counts + b, vmd_popc_u32(v));
+    } else {
+        const uint32_t i = (blockIdx.x - wblocks) * 256u + threadIdx.x;
+        unsigned n = 0;
+        if (i < (uint32_t)q.nnative) { const uint32_t p = q.native[i]; n = (row[p >> 5] >> (p & 31u)) & 1u; }
+        vmd_contact_wave_add(q.counts + q.B + b, n);
+    }
+}
+// the temporal rows - Q = (float)n / (float)nnative, one fp32 division - and the frames row, bumped once per frame
+__global__ __launch_bounds__(256) void k_contact_finish_out(vmd_contact_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < q.B) {
+        q.out_count[i] = (float)q.counts[i];
+        if (q.out_q) q.out_q[i] = (float)q.counts[q.B + i] / (float)q.nnative;
+    }
+    if (i == 0) q.acc[q.P] += (uint64_t)q.B;
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -5399,6 +5637,73 @@ extern "C" int vmd_hip_sasa_finish(void* stream, const uint64_t* totals, int B, 
     if (B <= 0) return 0;
     if (!totals || !out || !frames_row) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sasa_finish, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, totals, B, out, frames_row, skip_flag);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K14: residue contact maps
+static bool vmd_contact_args_ok(int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, uint32_t min_sep, float r_cut,
+                                const uint32_t* bits) {
+    return B <= 65535 && ent && grp && nent > 0 && ngroups >= 2 && ngroups <= 2048 && min_sep >= 1 && min_sep < (uint32_t)ngroups &&
+           r_cut > 0.0f && bits;
+}
+static uint32_t vmd_contact_pairs(int ngroups) { return (uint32_t)ngroups * (uint32_t)(ngroups - 1) / 2u; }
+
+extern "C" int vmd_hip_contact_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes,
+                                     uint32_t pbc_flags, int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups,
+                                     uint32_t min_sep, const float* sorted, const uint32_t* cell_start, int nent_pad, const uint32_t* ident,
+                                     vmd_grid_t grid, float r_cut, int closed, int lds_rows, uint32_t* bits, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    vmd_contact_atoms_params_t p{};
+    if (!vmd_contact_args_ok(B, ent, grp, nent, ngroups, min_sep, r_cut, bits) || !sorted || !cell_start || !ident || !grid_boxes ||
+        nent_pad < nent || grid.ncell != grid.nxf * grid.ny * grid.nz ||
+        !vmd_within_walk_fill(p.k, grid, sorted, cell_start, nent_pad, 0.0f, r_cut, closed)) return (int)hipErrorInvalidValue;
+    const uint32_t W = (vmd_contact_pairs(ngroups) + 31u) / 32u;
+    { const hipError_t e = hipMemsetAsync(bits, 0, (size_t)B * W * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
+    p.c.sel = ent; p.c.nsel = nent; p.c.nsel_pad = nent; p.c.grid = grid;
+    p.grp = grp; p.ngroups = (uint32_t)ngroups; p.min_sep = min_sep; p.ident = ident; p.bits = bits; p.W = W; p.skip = skip_flag;
+    if (lds_rows) hipLaunchKernelGGL(k_contact_atoms<true>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_contact_atoms<false>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_contact_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                     uint32_t pbc_flags, int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups,
+                                     uint32_t min_sep, uint32_t* canon, float r_cut, int closed, uint32_t* bits, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (!vmd_contact_args_ok(B, ent, grp, nent, ngroups, min_sep, r_cut, bits) || !canon || !boxes) return (int)hipErrorInvalidValue;
+    const uint32_t W = (vmd_contact_pairs(ngroups) + 31u) / 32u;
+    { const hipError_t e = hipMemsetAsync(bits, 0, (size_t)B * W * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    vmd_hbond_brute_params_t cp{};          // k_hbond_canon reads the frame, the list and the flag of it
+    cp.xyz = xyz; cp.frame_stride = frame_stride; cp.row_stride = row_stride; cp.boxes = boxes; cp.pbc = pbc_flags;
+    cp.accl = ent; cp.nacc = nent; cp.canon = canon; cp.skip = skip_flag;
+    hipLaunchKernelGGL(k_hbond_canon, dim3((nent + 255) / 256, B), dim3(256), 0, s, cp);
+    VMD_LAUNCH_CHECK();
+    vmd_contact_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, ent, grp, nent, (uint32_t)ngroups, min_sep, canon,
+                                 vmd_make_within_test(0.0f, r_cut, closed), bits, W, skip_flag};
+    hipLaunchKernelGGL(k_contact_brute, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_contact_finish(void* stream, const uint32_t* bits, int B, int ngroups, const uint32_t* native, int nnative,
+                                      uint32_t* counts, float* out_count, float* out_q, uint64_t* acc, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !bits || ngroups < 2 || ngroups > 2048 || nnative < 0 || (nnative > 0 && (!native || !out_q)) || !counts || !out_count ||
+        !acc) return (int)hipErrorInvalidValue;
+    const uint32_t P = vmd_contact_pairs(ngroups), W = (P + 31u) / 32u;
+    { const hipError_t e = hipMemsetAsync(counts, 0, 2 * (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    vmd_contact_finish_params_t q{bits, W, P, B, native, nnative, counts, out_count, nnative > 0 ? out_q : nullptr, acc, skip_flag};
+    hipLaunchKernelGGL(k_contact_finish_rows, dim3((W + 255u) / 256u), dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_contact_finish_frames, dim3((W + 255u) / 256u + ((uint32_t)nnative + 255u) / 256u, B), dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_contact_finish_out, dim3((B + 255) / 256), dim3(256), 0, s, q);
     VMD_LAUNCH_CHECK();
     return 0;
 }

@@ -988,6 +988,37 @@ extern "C" const vmd_hbond_sites_t* vmd_hbond_sites_view(const vmd_hbond_sites_o
 
 extern "C" void vmd_hbond_sites_free(vmd_hbond_sites_owned_t* sites) { delete sites; }
 
+// ---- contact sites from a topology (DECISION D-CT-TOPOLOGY): every atom, or every atom that is not a hydrogen, in ascending
+// atom order; the group is the residue_index renumbered densely in order of first appearance.  No native list.
+struct vmd_contact_sites_owned_t {
+    std::vector<int32_t> atom, group;
+    vmd_contact_sites_t view;
+};
+
+extern "C" vmd_contact_sites_owned_t* vmd_topology_contact_sites(const vmd_topology_t* topology, bool heavy_only) {
+    if (!topology) { vmd_set_last_error("vmd_topology_contact_sites: topology is NULL"); return nullptr; }
+    try {
+        auto cs = std::make_unique<vmd_contact_sites_owned_t>();
+        std::map<int32_t, int32_t> dense;
+        for (size_t i = 0; i < topology->num_atoms; ++i) {
+            if (heavy_only && upper(topology->elements && topology->elements[i] ? topology->elements[i] : "") == "H") continue;
+            const int32_t r = topology->residue_index ? topology->residue_index[i] : 0;
+            const auto it = dense.emplace(r, (int32_t)dense.size()).first;
+            cs->atom.push_back((int32_t)i); cs->group.push_back(it->second);
+        }
+        cs->view.nentries = cs->atom.size(); cs->view.atom = cs->atom.data(); cs->view.group = cs->group.data();
+        cs->view.ngroups = dense.size(); cs->view.nnative = 0; cs->view.native = nullptr;
+        return cs.release();
+    } catch (const std::exception& e) {
+        vmd_set_last_error(e.what());
+        return nullptr;
+    }
+}
+
+extern "C" const vmd_contact_sites_t* vmd_contact_sites_view(const vmd_contact_sites_owned_t* sites) { return sites ? &sites->view : nullptr; }
+
+extern "C" void vmd_contact_sites_free(vmd_contact_sites_owned_t* sites) { delete sites; }
+
 // ---- van der Waals radii from a topology's elements (DECISION D-SASA-RADII): Bondi's values, 2.00 for anything else
 extern "C" size_t vmd_topology_vdw_radii(const vmd_topology_t* topology, float* out, size_t cap) {
     if (!topology) { vmd_set_last_error("vmd_topology_vdw_radii: topology is NULL"); return 0; }

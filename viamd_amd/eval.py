@@ -5,6 +5,7 @@ frame_range / interrupt / property_data / frame_mask), see /root/reference/src/m
 Everything here is plumbing: the arithmetic runs in the HIP kernels behind libviamd_amd.so.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -281,6 +282,23 @@ class ScriptIR:
         self._check(self.lib.vmd_ir_add_sasa(self.h, (C.c_char_p * 2)(*[x.encode() for x in names]), C.byref(sites), float(probe),
                                              int(npoints)))
 
+    def add_contacts(self, names, atoms, groups, r_cut=4.5, min_sep=3, native=None, ngroups=None):
+        """Residue contact maps and the native-contact fraction: names = (pairs in contact per frame, record of the map[,
+        Q per frame]).  Entry i is atoms[i] standing for group groups[i]; groups g < h are in contact in a frame when h - g >= min_sep and
+        some entry of each is within r_cut of the other.  native: [n, 2] group pairs of the reference set (None / empty: no third name).
+        ngroups: None = max(groups) + 1.  The record is u64 [P + 1], P = G (G - 1) / 2 in SciPy's pdist order, then the frames."""
+        names = list(names)
+        a_, ap = _idx(atoms)
+        g_, gp = _idx(groups)
+        if a_.size != g_.size:
+            raise ValueError("atoms and groups must list one value per entry each")
+        nat = np.zeros((0, 2), np.int32) if native is None else np.ascontiguousarray(native, np.int32).reshape(-1, 2)
+        assert len(names) == (3 if nat.shape[0] else 2), "contacts defines two properties, three with a native list"
+        G = int(ngroups) if ngroups is not None else (int(g_.max()) + 1 if g_.size else 0)
+        sites = L.ContactSitesC(a_.size, ap, gp, G, nat.shape[0], nat.ctypes.data_as(L.c_int32_p) if nat.shape[0] else None)
+        cn = (C.c_char_p * 3)(*([x.encode() for x in names] + [None] * (3 - len(names))))
+        self._check(self.lib.vmd_ir_add_contacts(self.h, cn, C.byref(sites), float(r_cut), int(min_sep)))
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -448,6 +466,15 @@ class PropertyDataView:
         """the record of a sasa statement as uint64 [nmeas + 1]: the accessible points of every measured entry summed over
         the evaluated frames, the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a record of accessible surface points"
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
+
+    @property
+    def contact_accumulators(self):
+        """the record of a contact map as uint64 [P + 1]: per group pair, in condensed order, the evaluated frames in which
+        it was in contact, then the frames accumulated"""
+        assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not the record of a contact map"
         if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
             raise VmdError(self._ev.lib.last_error())
         return self._arr(self.c.counts, self.c.dim[0], np.uint64)
@@ -729,6 +756,47 @@ class ScriptEval:
                                         out.ctypes.data_as(C.POINTER(C.c_uint32)), n) == failed:
             raise VmdError(self.lib.last_error())
         return out[:n].copy()
+
+    def contacts(self, name, square=False):
+        """a contact map read from its record as it stands (any name of the statement) -> (occupancy, frames): occupancy
+        float64 [P] = count / frames in condensed pair order (SciPy's pdist), or with square=True the symmetric [G, G] matrix with a zero
+        diagonal"""
+        if not self.lib.vmd_eval_contacts(self.h, name.encode(), None, None):  # (the name and the form, before any size is believed)
+            raise VmdError(self.lib.last_error())
+        # the statement's record stands behind its count and in front of its native fraction: its rows say P, and P says G.  Of the two
+        # temporal names only the count has atoms (vmd_ir_geometry_atoms: the entries' atoms; the native fraction: none) - what stands
+        # next to the statement in the ir never enters into it
+        names = self.ir.property_names()
+        i = names.index(name)
+        if self.ir.property_flags(name) != L.FLAG_MAP:
+            i = i + 1 if self.ir.geometry_atoms(name).size else i - 1
+        P = self.property_data(names[i]).dim[0] - 1
+        G = (1 + math.isqrt(1 + 8 * P)) // 2
+        assert G * (G - 1) // 2 == P, "not the record of a contact map"
+        occ = np.zeros(P, np.float64)
+        frames = C.c_uint64(0)
+        if not self.lib.vmd_eval_contacts(self.h, name.encode(), occ.ctypes.data_as(L.c_double_p), C.byref(frames)):
+            raise VmdError(self.lib.last_error())
+        if not square:
+            return occ, int(frames.value)
+        full = np.zeros((G, G), np.float64)
+        iu = np.triu_indices(G, 1)
+        full[iu] = occ
+        return full + full.T, int(frames.value)
+
+    def contact_pairs(self, name, sys, traj, frame, cap=None):
+        """the group pairs in contact in one frame, on demand -> int32 [n, 2] of {g, h}, g < h, in ascending condensed
+        index.  cap: room for that many (None: all of them, asked for twice at the most)"""
+        room = 1024 if cap is None else int(cap)
+        while True:
+            out = np.zeros((max(room, 1), 2), np.int32)
+            n = self.lib.vmd_eval_contact_pairs(self.h, name.encode(), C.byref(sys.c) if sys is not None else None, traj.interface(),
+                                                int(frame), out.ctypes.data_as(L.c_int32_p), room)
+            if n == C.c_size_t(-1).value:
+                raise VmdError(self.lib.last_error())
+            if cap is not None or n <= room:
+                return out[:min(n, room)].copy()
+            room = int(n)
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""
