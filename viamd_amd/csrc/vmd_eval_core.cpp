@@ -217,41 +217,24 @@ void build_within_plan(vmd_script_eval_t* e) {
     }
 }
 
-// hydrogen bonds: the acceptors become an interned selection - shared with everything else of the script, so that a
-// cell-sorted copy another pass built on the same grid in a batch is not built again; the donors are walked in list order and are never
-// sorted (their selection only says how many lanes the grid is chosen for)
-void build_hbond_plan(vmd_script_eval_t* e) {
-    e->hbond_props.clear();
-    for (size_t i = 0; i < e->props.size(); ++i) {
-        PropState* p = e->props[i].get();
-        if (p->prop.form != Form::HBOND_COUNT) continue;
-        p->sel_a = intern_selection(e, p->prop.a);
-        p->sel_b = intern_selection(e, p->prop.b);
-        e->hbond_props.push_back((int)i);
-    }
-}
-
-// accessible area: the environment becomes an interned selection, shared like the acceptors of 1.14; the measured entries are
-// walked in list order and are never sorted (their selection only says how many lanes the grid is chosen for)
-void build_sasa_plan(vmd_script_eval_t* e) {
-    e->sasa_props.clear();
-    for (size_t i = 0; i < e->props.size(); ++i) {
-        PropState* p = e->props[i].get();
-        if (p->prop.form != Form::SASA_AREA) continue;
-        p->sel_a = intern_selection(e, p->prop.a);
-        p->sel_b = intern_selection(e, p->prop.b);
-        e->sasa_props.push_back((int)i);
-    }
-}
-
-// contact maps: ONE interned selection, the entry list, on both sides - its cell-sorted copy is what its own entries walk
-void build_contact_plan(vmd_script_eval_t* e) {
-    e->contact_props.clear();
-    for (size_t i = 0; i < e->props.size(); ++i) {
-        PropState* p = e->props[i].get();
-        if (p->prop.form != Form::CONTACT_COUNT) continue;
-        p->sel_a = p->sel_b = intern_selection(e, p->prop.a);
-        e->contact_props.push_back((int)i);
+// The neighbour analyses - hydrogen bonds, accessible area (1.15), contact maps (1.16): the side that is cell-sorted (the
+// acceptors, the environment, the entry list) becomes an interned selection - shared with everything else of the script, so that a
+// cell-sorted copy another pass built on the same grid in a batch is not built again.  The side in the lanes (the donors, the measured
+// entries) is walked in list order and is never sorted: its selection only says how many lanes the grid is chosen for.  Contacts have ONE
+// list, on both sides: its cell-sorted copy is what its own entries walk.
+void build_neighbour_plan(vmd_script_eval_t* e) {
+    const struct { Form count; std::vector<int> vmd_script_eval_t::* props; bool one_list; } kinds[] = {
+        {Form::HBOND_COUNT, &vmd_script_eval_t::hbond_props, false}, {Form::SASA_AREA, &vmd_script_eval_t::sasa_props, false},
+        {Form::CONTACT_COUNT, &vmd_script_eval_t::contact_props, true}};
+    for (auto& k : kinds) {
+        (e->*k.props).clear();
+        for (size_t i = 0; i < e->props.size(); ++i) {
+            PropState* p = e->props[i].get();
+            if (p->prop.form != k.count) continue;
+            p->sel_a = intern_selection(e, p->prop.a);
+            p->sel_b = k.one_list ? p->sel_a : intern_selection(e, p->prop.b);
+            (e->*k.props).push_back((int)i);
+        }
     }
 }
 
@@ -451,9 +434,7 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
     }
     build_rdf_plan(e.get());
     build_within_plan(e.get());
-    build_hbond_plan(e.get());
-    build_sasa_plan(e.get());
-    build_contact_plan(e.get());
+    build_neighbour_plan(e.get());
     build_expr_plan(e.get());
     if (!e->d_overflow.ensure(1) || hipMemsetAsync(e->d_overflow.p, 0, sizeof(uint32_t), e->stream) != hipSuccess ||
         pool_take(kPinned, (void**)&e->h_overflow, 2 * sizeof(uint32_t)) != hipSuccess) { vmd_fail("allocating the overflow flag failed");
@@ -926,6 +907,48 @@ extern "C" bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name,
     return true;
 }
 
+// ---- what the readers of the records and the one-frame calls share
+// A record as it stands - a partial evaluation, a merged one - copied to the host: under the eval's mutex, touching nothing it keeps.
+static bool read_record(vmd_script_eval_t* e, const PropState* p, std::vector<uint64_t>* acc) {
+    acc->resize(p->ncounts);
+    std::lock_guard<std::mutex> lock(e->mtx);
+    HIP_OK(hipSetDevice(e->device));
+    HIP_OK(hipMemcpyAsync(acc->data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return true;
+}
+// rows / frames, 0 where no frame has been counted
+static void rows_over_frames(const uint64_t* rows, size_t n, uint64_t F, double* out) {
+    if (out) for (size_t j = 0; j < n; ++j) out[j] = F ? (double)rows[j] / (double)F : 0.0;
+}
+// Any name of a statement names it: the count (form `count`) or a companion behind it, companions[k] standing k + 1 places behind ->
+// the index of the count, or props.size() + vmd_last_error ("'name' is not <what> property")
+static size_t count_statement(vmd_script_eval_t* e, const char* name, Form count, std::initializer_list<Form> companions, const char* what) {
+    size_t pi = e->props.size();
+    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
+    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return pi; }
+    size_t k = 0;
+    for (Form f : companions) { k += 1; if (e->props[pi]->prop.form == f && pi >= k) { pi -= k; break; } }
+    if (e->props[pi]->prop.form != count) { vmd_fail("'%s' is not %s property", name, what); return e->props.size(); }
+    return pi;
+}
+// One frame on demand: fn(src) with frame `frame` of traj fetched as a batch of one (boxes and pbc: e->stages[0]'s), under the eval's
+// mutex, so that it takes its turn between the batches of running calls.  fn launches on e->stream and waits for what it reads back.
+template <class Fn>
+static bool on_one_frame(vmd_script_eval_t* e, const char* who, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame, Fn fn) {
+    if (frame >= e->num_frames) return vmd_fail("%s: frame %u outside the trajectory (%zu frames)", who, frame, e->num_frames);
+    std::lock_guard<std::mutex> lock(e->mtx);
+    if (hipSetDevice(e->device) != hipSuccess) return vmd_fail("hipSetDevice failed");
+    const size_t num_atoms = traj->num_atoms(traj->inst);
+    if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return false;
+    vmd_device_view_t view;
+    memset(&view, 0, sizeof(view));
+    const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
+    BatchSrc src;
+    if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+    return fn(src);
+}
+
 // ---- rmsf read from its record: m = sum_q / (2^24 F) per axis, msf = sum_q2 / (2^24 F) - |m|^2 clamped at 0, rmsf = sqrt(msf).
 // Whatever the record holds - a partial evaluation, a merged one - is what is read; under the eval's mutex, touching nothing it keeps.
 extern "C" bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double* rmsf, double* mean_dev, uint64_t* frames) {
@@ -934,13 +957,8 @@ extern "C" bool vmd_eval_rmsf(vmd_script_eval_t* eval, const char* name, double*
     if (!p) return vmd_fail("unknown property '%s'", name);
     if (p->prop.form != Form::RMSF) return vmd_fail("'%s' is not an rmsf property", name);
     const size_t ntot = p->prop.a.size();
-    std::vector<uint64_t> acc(p->ncounts);
-    {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        HIP_OK(hipSetDevice(eval->device));
-        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
-        HIP_OK(hipStreamSynchronize(eval->stream));
-    }
+    std::vector<uint64_t> acc;
+    if (!read_record(eval, p, &acc)) return false;
     const uint64_t F = acc[4 * ntot];
     if (frames) *frames = F;
     const double scale = 16777216.0 * (double)F;
@@ -965,17 +983,12 @@ extern "C" bool vmd_eval_hbonds(vmd_script_eval_t* eval, const char* name, doubl
     if (!p) return vmd_fail("unknown property '%s'", name);
     if (p->prop.form != Form::HBOND_OCC) return vmd_fail("'%s' is not a hydrogen-bond occupancy", name);
     const size_t npairs = p->prop.K, nacc = p->prop.m;
-    std::vector<uint64_t> acc(p->ncounts);
-    {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        HIP_OK(hipSetDevice(eval->device));
-        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
-        HIP_OK(hipStreamSynchronize(eval->stream));
-    }
+    std::vector<uint64_t> acc;
+    if (!read_record(eval, p, &acc)) return false;
     const uint64_t F = acc[npairs + nacc];
     if (frames) *frames = F;
-    if (donor_occ) for (size_t j = 0; j < npairs; ++j) donor_occ[j] = F ? (double)acc[j] / (double)F : 0.0;
-    if (acc_occ) for (size_t k = 0; k < nacc; ++k) acc_occ[k] = F ? (double)acc[npairs + k] / (double)F : 0.0;
+    rows_over_frames(acc.data(), npairs, F, donor_occ);
+    rows_over_frames(acc.data() + npairs, nacc, F, acc_occ);
     return true;
 }
 
@@ -987,28 +1000,15 @@ extern "C" size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name
     const size_t failed = VMD_HBOND_PAIRS_FAILED;
     if (!eval || !traj || !name || (!out && cap)) { vmd_fail("vmd_eval_hbond_pairs: NULL argument"); return failed; }
     vmd_script_eval_t* e = eval;
-    size_t pi = e->props.size();
-    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
-    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return failed; }
-    if (e->props[pi]->prop.form == Form::HBOND_OCC && pi > 0) pi -= 1;         // the occupancy names the statement as well as its count
+    const size_t pi = count_statement(e, name, Form::HBOND_COUNT, {Form::HBOND_OCC}, "a hydrogen-bond");
+    if (pi == e->props.size()) return failed;
     PropState* p = e->props[pi].get();
-    if (p->prop.form != Form::HBOND_COUNT) { vmd_fail("'%s' is not a hydrogen-bond property", name); return failed; }
-    if (frame >= e->num_frames) { vmd_fail("vmd_eval_hbond_pairs: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
     const Property& d = p->prop;
     const size_t npairs = d.a.size(), nacc = d.b.size();
     std::vector<uint32_t> list, canon_h(nacc);
     uint32_t found = 0;
     {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
-        const size_t num_atoms = traj->num_atoms(traj->inst);
-        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
-        auto run = [&]() -> bool {
-            vmd_device_view_t view;
-            memset(&view, 0, sizeof(view));
-            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
-            BatchSrc src;
-            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+        auto run = [&](const BatchSrc& src) -> bool {
             // two passes at the most: the list is sized for what a caller asks for (and a fair share more), the second pass for what was found
             size_t room = std::min<size_t>(std::max<size_t>(cap, 4 * npairs), (size_t)0x3fffffff);
             for (int pass = 0; pass < 2; ++pass) {
@@ -1033,7 +1033,7 @@ extern "C" size_t vmd_eval_hbond_pairs(vmd_script_eval_t* eval, const char* name
             }
             return vmd_fail("vmd_eval_hbond_pairs: the frame's bonds changed between two passes");
         };
-        if (!run()) return failed;
+        if (!on_one_frame(e, "vmd_eval_hbond_pairs", sys, traj, frame, run)) return failed;
     }
     // ascending (pair index, acceptor list position); the appends arrive in no order.  The acceptor named is the entry that answers for
     // the position (D-HB-COINCIDENT)
@@ -1060,13 +1060,8 @@ extern "C" bool vmd_eval_sasa(vmd_script_eval_t* eval, const char* name, double*
     if (!mean_area && !frames) return true;        // (asked for the form alone)
     const Property& d = eval->props[pi - 1]->prop;
     const size_t nmeas = p->prop.K;
-    std::vector<uint64_t> acc(p->ncounts);
-    {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        HIP_OK(hipSetDevice(eval->device));
-        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
-        HIP_OK(hipStreamSynchronize(eval->stream));
-    }
+    std::vector<uint64_t> acc;
+    if (!read_record(eval, p, &acc)) return false;
     const uint64_t F = acc[nmeas];
     if (frames) *frames = F;
     if (mean_area)
@@ -1084,27 +1079,14 @@ extern "C" size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name,
     const size_t failed = VMD_SASA_ATOMS_FAILED;
     if (!eval || !traj || !name || (!counts && cap)) { vmd_fail("vmd_eval_sasa_atoms: NULL argument"); return failed; }
     vmd_script_eval_t* e = eval;
-    size_t pi = e->props.size();
-    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
-    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return failed; }
-    if (e->props[pi]->prop.form == Form::SASA_OCC && pi > 0) pi -= 1;          // the record names the statement as well as its area
+    const size_t pi = count_statement(e, name, Form::SASA_AREA, {Form::SASA_OCC}, "a sasa");
+    if (pi == e->props.size()) return failed;
     PropState* p = e->props[pi].get();
-    if (p->prop.form != Form::SASA_AREA) { vmd_fail("'%s' is not a sasa property", name); return failed; }
-    if (frame >= e->num_frames) { vmd_fail("vmd_eval_sasa_atoms: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
     const Property& d = p->prop;
     const size_t nmeas = d.a.size(), nenv = d.b.size();
     std::vector<uint32_t> got(nmeas);
     {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
-        const size_t num_atoms = traj->num_atoms(traj->inst);
-        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
-        auto run = [&]() -> bool {
-            vmd_device_view_t view;
-            memset(&view, 0, sizeof(view));
-            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
-            BatchSrc src;
-            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+        auto run = [&](const BatchSrc& src) -> bool {
             if (!e->d_one_sasa.ensure(nenv + nmeas)) return false;
             uint32_t* canon = e->d_one_sasa.p;
             uint32_t* dn = canon + nenv;
@@ -1115,7 +1097,7 @@ extern "C" size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name,
             HIP_OK(hipStreamSynchronize(e->stream));
             return true;
         };
-        if (!run()) return failed;
+        if (!on_one_frame(e, "vmd_eval_sasa_atoms", sys, traj, frame, run)) return failed;
     }
     for (size_t i = 0; i < nmeas && i < cap; ++i) counts[i] = got[i];
     return nmeas;
@@ -1123,15 +1105,10 @@ extern "C" size_t vmd_eval_sasa_atoms(vmd_script_eval_t* eval, const char* name,
 
 // ---- contact maps.  Any name of the statement names it: -> the index of its count, or props.size() + vmd_last_error
 static size_t contact_statement(vmd_script_eval_t* e, const char* name) {
-    size_t pi = e->props.size();
-    for (size_t i = 0; i < e->props.size(); ++i) if (e->props[i]->prop.name == name) pi = i;
-    if (pi == e->props.size()) { vmd_fail("unknown property '%s'", name); return pi; }
-    const Form f = e->props[pi]->prop.form;
-    if (f == Form::CONTACT_OCC && pi >= 1) pi -= 1;
-    else if (f == Form::CONTACT_NATIVE && pi >= 2) pi -= 2;
-    if (e->props[pi]->prop.form != Form::CONTACT_COUNT || pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::CONTACT_OCC) {
-        vmd_fail("'%s' is not a contacts property", name); return e->props.size(); }
-    return pi;
+    const size_t pi = count_statement(e, name, Form::CONTACT_COUNT, {Form::CONTACT_OCC, Form::CONTACT_NATIVE}, "a contacts");
+    if (pi == e->props.size() || (pi + 1 < e->props.size() && e->props[pi + 1]->prop.form == Form::CONTACT_OCC)) return pi;
+    vmd_fail("'%s' is not a contacts property", name);
+    return e->props.size();
 }
 
 // count / frames per group pair, read from the record as it stands - a partial evaluation, a merged one; under the eval's mutex, touching
@@ -1143,16 +1120,10 @@ extern "C" bool vmd_eval_contacts(vmd_script_eval_t* eval, const char* name, dou
     if (!occupancy && !frames) return true;        // (asked for the form alone)
     PropState* p = eval->props[pi + 1].get();
     const size_t P = p->prop.K;
-    std::vector<uint64_t> acc(p->ncounts);
-    {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        HIP_OK(hipSetDevice(eval->device));
-        HIP_OK(hipMemcpyAsync(acc.data(), p->d_counts.p, p->ncounts * sizeof(uint64_t), hipMemcpyDeviceToHost, eval->stream));
-        HIP_OK(hipStreamSynchronize(eval->stream));
-    }
-    const uint64_t F = acc[P];
-    if (frames) *frames = F;
-    if (occupancy) for (size_t k = 0; k < P; ++k) occupancy[k] = F ? (double)acc[k] / (double)F : 0.0;
+    std::vector<uint64_t> acc;
+    if (!read_record(eval, p, &acc)) return false;
+    if (frames) *frames = acc[P];
+    rows_over_frames(acc.data(), P, acc[P], occupancy);
     return true;
 }
 
@@ -1167,21 +1138,11 @@ extern "C" size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* na
     const size_t pi = contact_statement(e, name);
     if (pi == e->props.size()) return failed;
     PropState* p = e->props[pi].get();
-    if (frame >= e->num_frames) { vmd_fail("vmd_eval_contact_pairs: frame %u outside the trajectory (%zu frames)", frame, e->num_frames); return failed; }
     const Property& d = p->prop;
     const size_t nent = d.a.size(), G = d.K, P = G * (G - 1) / 2, W = (P + 31) / 32;
     std::vector<uint32_t> row(W);
     {
-        std::lock_guard<std::mutex> lock(eval->mtx);
-        if (hipSetDevice(eval->device) != hipSuccess) { vmd_fail("hipSetDevice failed"); return failed; }
-        const size_t num_atoms = traj->num_atoms(traj->inst);
-        if (!check_atoms(e, num_atoms) || !upload_static(e, sys, num_atoms)) return failed;
-        auto run = [&]() -> bool {
-            vmd_device_view_t view;
-            memset(&view, 0, sizeof(view));
-            const bool have_view = traj->device_view && traj->device_view(traj->inst, &view) && view.device == e->device;
-            BatchSrc src;
-            if (!fetch_batch(e, traj, view_holds(have_view, view, frame) ? &view : nullptr, num_atoms, frame, 1, &src)) return false;
+        auto run = [&](const BatchSrc& src) -> bool {
             if (!e->d_one_contacts.ensure(nent + W)) return false;
             uint32_t* canon = e->d_one_contacts.p;
             uint32_t* bits = canon + nent;
@@ -1191,7 +1152,7 @@ extern "C" size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* na
             HIP_OK(hipStreamSynchronize(e->stream));
             return true;
         };
-        if (!run()) return failed;
+        if (!on_one_frame(e, "vmd_eval_contact_pairs", sys, traj, frame, run)) return failed;
     }
     size_t found = 0, pidx = 0;
     for (size_t g = 0; g + 1 < G; ++g)

@@ -991,9 +991,7 @@ int intern_selection(vmd_script_eval_t* e, const std::vector<int32_t>& idx);
 void build_rdf_plan(vmd_script_eval_t* e);
 void build_within_plan(vmd_script_eval_t* e);
 
-void build_hbond_plan(vmd_script_eval_t* e);
-void build_sasa_plan(vmd_script_eval_t* e);
-void build_contact_plan(vmd_script_eval_t* e);
+void build_neighbour_plan(vmd_script_eval_t* e);
 void build_expr_plan(vmd_script_eval_t* e);
 
 void lone_stop(vmd_script_eval_t* e);
@@ -1114,6 +1112,8 @@ struct PairSide { const float* sorted; const uint32_t* cell_start; int n, npad; 
 // a scratch row of launch_rdf and the accumulator it is added to behind the overflow flag
 struct RdfCommit { uint64_t* dst; const uint64_t* src; uint64_t mult; };
 
+struct NeighbourKind;       // vmd_eval_launch.cpp: what hydrogen bonds, accessible area and contact maps each contribute to one route
+
 struct RangeRun {
     vmd_script_eval_t* e = nullptr;
     vmd_trajectory_i* traj = nullptr;
@@ -1135,8 +1135,7 @@ struct RangeRun {
     bool forked = false;                // pair_stream holds launches the eval's stream has not waited for
     size_t row = 0;                     // next scratch row of d_pass
     std::vector<RdfCommit> commits;
-    std::vector<int> sasa_route;        // build_sasa_cells' answer per sasa statement of the batch: 1 the walk, 0 all pairs
-    std::vector<int> contact_route;     // build_contact_cells' answer per contacts statement, likewise
+    std::vector<int> neighbour_route[3];   // build_neighbour_cells' answer per statement of a kind (NeighbourKind::slot): 1 the walk, 0 all pairs
 
     RawSlot* slot_of(size_t bi) const { return raw_ring ? &e->raw_slots[bi % vmd_script_eval_t::kRawSlots] : nullptr; }
     Stage& stage_of(size_t bi) const { return e->stages[bi % (stage_ahead + 1)]; }
@@ -1171,13 +1170,9 @@ struct RangeRun {
     bool launch_within_counts(BatchCtx& c);
     bool launch_shell_masks(BatchCtx& c);
     bool launch_shell_sdfs(BatchCtx& c);
-    bool ident_routes(BatchCtx& c, const std::vector<int>& props, std::vector<int>* route);
     bool ident_table(BatchCtx& c, PropState* p, int route, int* have_grid, vmd_grid_t* grid, const float** d_gb);
-    bool launch_hbonds(BatchCtx& c);
-    bool build_sasa_cells(BatchCtx& c);
-    bool launch_sasa(BatchCtx& c);
-    bool build_contact_cells(BatchCtx& c);
-    bool launch_contacts(BatchCtx& c);
+    bool build_neighbour_cells(BatchCtx& c);
+    bool launch_neighbours(BatchCtx& c, const NeighbourKind& k);
     bool launch_rdf(BatchCtx& c);
     bool launch_shell_exprs(BatchCtx& c);
     bool launch_expr_sdfs(BatchCtx& c);

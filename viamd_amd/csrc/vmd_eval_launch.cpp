@@ -336,30 +336,16 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
     return true;
 }
 
-// ---- hydrogen bonds.  The occupancy is added to with atomics, so like a masked scatter it has to be all or nothing: the
-// launches stand behind the LAST cell build of the batch, where the overflow flag is final, and test it.  First every statement's cell
-// build (within_route's RULE with the donors in the lanes: the acceptors alone are sorted, on the grid a within count of r_da gets; all
-// pairs below shell_brute_below acceptors or where no grid exists), then, statement by statement, the identity of the sorted copy and
-// the walk - per sub, so that a frame block's bonds land in its own partial.  A copy that a later statement's build has re-sorted on
-// another grid is not built a second time (that would be a cell build behind an accumulation): that statement takes all pairs for this
-// batch, which answers the same bit for bit.
-// What the two kinds that add to a record with atomics - hydrogen bonds, accessible area (1.15) - share.  ident_routes: every statement's
-// own cell build (sel_a in the lanes, sel_b alone sorted, the radius in rmax) -> per statement 1 the walk, 0 all pairs.
-bool RangeRun::ident_routes(BatchCtx& c, const std::vector<int>& props, std::vector<int>* route) {
-    route->assign(props.size(), 0);
-    for (size_t i = 0; i < props.size(); ++i) {
-        PropState* p = e->props[props[i]].get();
-        vmd_grid_t grid;
-        const float* d_gb = nullptr;
-        (*route)[i] = within_route(c, e->sels[p->sel_a].get(), e->sels[p->sel_b].get(), p->prop.rmax, true, &grid, &d_gb);
-        if ((*route)[i] < 0) return false;
-    }
-    return true;
-}
-
+// ---- the neighbour analyses: hydrogen bonds, accessible area (1.15), contact maps (1.16).  Each statement adds to a record
+// with atomics (or sets bits of one), so like a masked scatter it has to be all or nothing: its launches stand behind the LAST cell build
+// of the batch, where the overflow flag is final, and test it.  First every statement's cell build (build_neighbour_cells), then, kind by
+// kind and statement by statement, the identity of the sorted copy and the walk - per sub, so that a frame block's part lands in its own
+// partial (launch_neighbours).  What a kind contributes is a NeighbourKind.
+//
 // ident_table: the statement's route at launch time and its table in d_hb_ident.  A sorted copy that another statement's build has
-// re-sorted on another grid since ident_routes sends the statement to all pairs for this batch.  *have_grid 1: the grid, its boxes, and
-// k_sorted_atoms' table of sel_b's copy, u32[nb][nsel_pad]; 0: room for the all-pairs route's canonical entries, u32[nb][|sel_b|].
+// re-sorted on another grid since build_neighbour_cells is not built a second time (that would be a cell build behind an accumulation): the
+// statement takes all pairs for this batch, which answers the same bit for bit.  *have_grid 1: the grid, its boxes, and k_sorted_atoms'
+// table of sel_b's copy, u32[nb][nsel_pad]; 0: room for the all-pairs route's canonical entries, u32[nb][|sel_b|].
 bool RangeRun::ident_table(BatchCtx& c, PropState* p, int route, int* have_grid, vmd_grid_t* grid, const float** d_gb) {
     Selection* sl = e->sels[p->sel_a].get();
     Selection* sr = e->sels[p->sel_b].get();
@@ -381,143 +367,172 @@ bool RangeRun::ident_table(BatchCtx& c, PropState* p, int route, int* have_grid,
     return true;
 }
 
-bool RangeRun::launch_hbonds(BatchCtx& c) {
-    const int closed = e->spec.within_closed ? 1 : 0;
-    std::vector<int> route;
-    if (!ident_routes(c, e->hbond_props, &route)) return false;
-    for (size_t i = 0; i < e->hbond_props.size(); ++i) {
-        const int pi = e->hbond_props[i];
-        PropState* p = e->props[pi].get();
-        if ((size_t)pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::HBOND_OCC)
-            return vmd_fail("hydrogen-bond count '%s' has lost its occupancy", p->prop.name.c_str());
-        PropState* m = e->props[pi + 1].get();
-        const Property& d = p->prop;
-        Selection* sr = e->sels[p->sel_b].get();
-        const int npairs = (int)d.a.size(), nacc = (int)d.b.size();
-        vmd_grid_t grid;
-        const float* d_gb = nullptr;
-        int have_grid = 0;
-        if (!p->d_out.ensure(c.nb) || !p->d_hb_count.ensure(c.nb) || !ident_table(c, p, route[i], &have_grid, &grid, &d_gb)) return false;
-        const Stage& st = *c.src;
-        e->prof.begin(have_grid ? "hbond_atoms" : "hbond_brute", e->stream);
-        for (auto& su : c.subs) {
-            const float* xyz = st.base + su.off * st.frame_stride;
-            uint64_t* acc = acc_of(m, su);
-            if (have_grid)
-                KRN_OK(vmd_hip_hbond_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, st.d_boxes.p + 9 * su.off, c.pbc,
-                        (int)su.nb, p->d_a.p, p->d_c.p, npairs, p->d_b.p, nacc, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad,
-                        sr->cell_start.p + su.off * (size_t)(grid.ncell + 1), sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid,
-                        d.rmax, d.hb_c2, closed, p->d_hb_count.p + su.off, acc, e->d_overflow.p));
-            else
-                KRN_OK(vmd_hip_hbond_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
-                        p->d_a.p, p->d_c.p, npairs, p->d_b.p, nacc, p->d_hb_ident.p + su.off * (size_t)nacc, d.rmax, d.hb_c2, closed,
-                        p->d_hb_count.p + su.off, acc, e->d_overflow.p));
-            KRN_OK(vmd_hip_hbond_finish(e->stream, p->d_hb_count.p + su.off, (int)su.nb, p->d_out.p + su.off, acc + npairs + nacc,
-                    e->d_overflow.p));
+// One sub of one statement as a kind's calls see it, every pointer at the sub's first frame: the frames and their boxes, the statement p
+// with its descriptor d and its record's partial acc; the walk's grid, boxes and copy of sel_b; ident: k_sorted_atoms' table (walk) or the
+// room for the canonical entries (all pairs).
+struct NeighbourSub {
+    hipStream_t s; const uint32_t* overflow;
+    PropState* p; const Property& d; uint64_t* acc;
+    const Stage& st; const Sub& su; uint32_t pbc; int closed;
+    const float *xyz, *fboxes;
+    vmd_grid_t grid; const float *gboxes, *sorted; const uint32_t* cell_start; int npad;
+    uint32_t* ident;
+};
+
+// What differs between the kinds.  record: the companion properties behind the count are still there -> the record (nullptr: vmd_fail said
+// why).  walk / brute / finish: the vmd_hip_* call of one sub.  finish_label: the finishes run in a loop of their own behind the
+// statement's launches, under this profile label (nullptr: behind each sub's launch).  more_rows: temporal rows besides d_out.
+struct NeighbourKind {
+    int slot;                                            // RangeRun::neighbour_route[slot]
+    std::vector<int> vmd_script_eval_t::* props;
+    const char *walk_label, *brute_label, *finish_label;
+    PropState* (*record)(vmd_script_eval_t* e, int pi);
+    bool (*ensure)(PropState* p, size_t nb);
+    int (*walk)(const NeighbourSub& x);
+    int (*brute)(const NeighbourSub& x);
+    int (*finish)(const NeighbourSub& x);
+    bool (*more_rows)(RangeRun& r, BatchCtx& c, int pi, PropState* p);
+};
+
+static PropState* record_behind(vmd_script_eval_t* e, int pi, Form form, const char* lost) {
+    if ((size_t)pi + 1 < e->props.size() && e->props[pi + 1]->prop.form == form) return e->props[pi + 1].get();
+    vmd_fail(lost, e->props[pi]->prop.name.c_str());
+    return nullptr;
+}
+
+static const NeighbourKind kHbonds = {
+    0, &vmd_script_eval_t::hbond_props, "hbond_atoms", "hbond_brute", nullptr,
+    [](vmd_script_eval_t* e, int pi) { return record_behind(e, pi, Form::HBOND_OCC, "hydrogen-bond count '%s' has lost its occupancy"); },
+    [](PropState* p, size_t nb) { return p->d_out.ensure(nb) && p->d_hb_count.ensure(nb); },
+    [](const NeighbourSub& x) {
+        return vmd_hip_hbond_atoms(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.gboxes, x.fboxes, x.pbc, (int)x.su.nb, x.p->d_a.p,
+                x.p->d_c.p, (int)x.d.a.size(), x.p->d_b.p, (int)x.d.b.size(), x.sorted, x.cell_start, x.npad, x.ident, x.grid, x.d.rmax,
+                x.d.hb_c2, x.closed, x.p->d_hb_count.p + x.su.off, x.acc, x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_hbond_brute(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.fboxes, x.pbc, (int)x.su.nb, x.p->d_a.p, x.p->d_c.p,
+                (int)x.d.a.size(), x.p->d_b.p, (int)x.d.b.size(), x.ident, x.d.rmax, x.d.hb_c2, x.closed, x.p->d_hb_count.p + x.su.off,
+                x.acc, x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_hbond_finish(x.s, x.p->d_hb_count.p + x.su.off, (int)x.su.nb, x.p->d_out.p + x.su.off,
+                x.acc + x.d.a.size() + x.d.b.size(), x.overflow);
+    },
+    nullptr};
+
+static const NeighbourKind kSasa = {
+    1, &vmd_script_eval_t::sasa_props, "sasa_atoms", "sasa_brute", nullptr,
+    [](vmd_script_eval_t* e, int pi) { return record_behind(e, pi, Form::SASA_OCC, "sasa area '%s' has lost its record"); },
+    [](PropState* p, size_t nb) { return p->d_out.ensure(nb) && p->d_sasa_total.ensure(nb); },
+    [](const NeighbourSub& x) {
+        return vmd_hip_sasa_atoms(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.gboxes, x.pbc, (int)x.su.nb, x.p->d_a.p,
+                (int)x.d.a.size(), x.p->d_b.p, (int)x.d.b.size(), x.sorted, x.cell_start, x.npad, x.ident, x.grid, x.p->d_sasa_ra.p,
+                x.p->d_sasa_rb.p, x.p->sasa_rmax_env, x.p->d_sasa_w.p, x.p->d_sasa_pts.p, (int)x.d.sasa_npoints, x.d.rmax, x.closed,
+                x.p->d_sasa_total.p + x.su.off, x.acc, x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_sasa_brute(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.fboxes, x.pbc, (int)x.su.nb, x.p->d_a.p,
+                (int)x.d.a.size(), x.p->d_b.p, (int)x.d.b.size(), x.ident, x.p->d_sasa_ra.p, x.p->d_sasa_rb.p, x.p->sasa_rmax_env,
+                x.p->d_sasa_w.p, x.p->d_sasa_pts.p, (int)x.d.sasa_npoints, x.d.rmax, x.closed, x.p->d_sasa_total.p + x.su.off, x.acc,
+                x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_sasa_finish(x.s, x.p->d_sasa_total.p + x.su.off, (int)x.su.nb, x.p->d_out.p + x.su.off, x.acc + x.d.a.size(),
+                x.overflow);
+    },
+    nullptr};
+
+// (contacts: every sub has its own rows of the batch's bit matrix - cleared by the launch, so also in a repeated batch - and of the counts;
+// the native pairs, where the statement has any, stand as a third property behind the record)
+static size_t contact_words(const Property& d) { return ((size_t)d.K * (size_t)(d.K - 1) / 2 + 31) / 32; }
+static int contact_nnative(const Property& d) { return (int)(d.ct_native.size() / 2); }
+static const NeighbourKind kContacts = {
+    2, &vmd_script_eval_t::contact_props, "contact_atoms", "contact_brute", "contact_finish",
+    [](vmd_script_eval_t* e, int pi) {
+        PropState* m = record_behind(e, pi, Form::CONTACT_OCC, "contact count '%s' has lost its record");
+        if (m && contact_nnative(e->props[pi]->prop) &&
+            !((size_t)pi + 2 < e->props.size() && e->props[pi + 2]->prop.form == Form::CONTACT_NATIVE)) {
+            vmd_fail("contact count '%s' has lost its record", e->props[pi]->prop.name.c_str());
+            return (PropState*)nullptr;
         }
-        e->prof.end(e->stream);
-        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
+        return m;
+    },
+    [](PropState* p, size_t nb) {
+        return p->d_out.ensure(nb) && (!contact_nnative(p->prop) || p->d_ct_q.ensure(nb)) && p->d_ct_count.ensure(2 * nb) &&
+               p->d_ct_bits.ensure(nb * contact_words(p->prop));
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_contact_atoms(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.gboxes, x.pbc, (int)x.su.nb, x.p->d_a.p, x.p->d_c.p,
+                (int)x.d.a.size(), (int)x.d.K, x.d.ct_min_sep, x.sorted, x.cell_start, x.npad, x.ident, x.grid, x.d.rmax, x.closed,
+                g_opt.contact_lds_rows.load(), x.p->d_ct_bits.p + x.su.off * contact_words(x.d), x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_contact_brute(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.fboxes, x.pbc, (int)x.su.nb, x.p->d_a.p, x.p->d_c.p,
+                (int)x.d.a.size(), (int)x.d.K, x.d.ct_min_sep, x.ident, x.d.rmax, x.closed,
+                x.p->d_ct_bits.p + x.su.off * contact_words(x.d), x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        const int nnative = contact_nnative(x.d);
+        return vmd_hip_contact_finish(x.s, x.p->d_ct_bits.p + x.su.off * contact_words(x.d), (int)x.su.nb, (int)x.d.K, x.p->d_ct_native.p,
+                nnative, x.p->d_ct_count.p + 2 * x.su.off, x.p->d_out.p + x.su.off, nnative ? x.p->d_ct_q.p + x.su.off : nullptr, x.acc,
+                x.overflow);
+    },
+    [](RangeRun& r, BatchCtx& c, int pi, PropState* p) { return !contact_nnative(p->prop) || r.queue_temporal_rows(c, pi + 2, p->d_ct_q.p); }};
+
+// Every statement's cell build, of all three kinds, as ONE step in front of the first accumulation: no cell build of the batch may stand
+// behind any kind's atomics.  By within_route's RULE: sel_a in the lanes, sel_b alone sorted (contacts: the one list on both sides), on the
+// grid a within count of the radius rmax gets; all pairs below shell_brute_below entries of sel_b or where no grid exists -> per statement
+// 1 the walk, 0 all pairs.  The ORDER of the builds - accessible area, contacts, hydrogen bonds - is part of the behaviour: where two
+// statements sort one selection on different grids the later build wins, and the earlier statement falls back to all pairs (ident_table).
+bool RangeRun::build_neighbour_cells(BatchCtx& c) {
+    for (const NeighbourKind* k : {&kSasa, &kContacts, &kHbonds}) {
+        std::vector<int>& route = neighbour_route[k->slot];
+        route.clear();
+        for (int pi : e->*(k->props)) {
+            PropState* p = e->props[pi].get();
+            vmd_grid_t grid;
+            const float* d_gb = nullptr;
+            route.push_back(within_route(c, e->sels[p->sel_a].get(), e->sels[p->sel_b].get(), p->prop.rmax, true, &grid, &d_gb));
+            if (route.back() < 0) return false;
+        }
     }
     return true;
 }
 
-// ---- accessible area.  launch_hbonds' placement and rules, because the record is added to with atomics: behind the LAST cell
-// build of the batch, every statement's own build first (within_route with the measured entries in the lanes: the environment alone is
-// sorted, on the grid a within count of r_cut gets; all pairs below shell_brute_below environment entries or where no grid exists), every
-// kernel under the overflow flag, and a copy that a later statement's build has re-sorted on another grid sends its statement to all pairs
-// for this batch, which answers the same bit for bit.  The builds are a step of their own in front of launch_hbonds, whose occupancies are
-// added to with atomics as well: no cell build of the batch may stand behind either accumulation.
-bool RangeRun::build_sasa_cells(BatchCtx& c) { return ident_routes(c, e->sasa_props, &sasa_route); }
-
-bool RangeRun::launch_sasa(BatchCtx& c) {
-    const int closed = e->spec.within_closed ? 1 : 0;
-    for (size_t i = 0; i < e->sasa_props.size(); ++i) {
-        const int pi = e->sasa_props[i];
+bool RangeRun::launch_neighbours(BatchCtx& c, const NeighbourKind& k) {
+    const std::vector<int>& props = e->*(k.props);
+    const Stage& st = *c.src;
+    for (size_t i = 0; i < props.size(); ++i) {
+        const int pi = props[i];
         PropState* p = e->props[pi].get();
-        if ((size_t)pi + 1 >= e->props.size() || e->props[pi + 1]->prop.form != Form::SASA_OCC)
-            return vmd_fail("sasa area '%s' has lost its record", p->prop.name.c_str());
-        PropState* m = e->props[pi + 1].get();
-        const Property& d = p->prop;
+        PropState* m = k.record(e, pi);
+        if (!m) return false;
         Selection* sr = e->sels[p->sel_b].get();
-        const int nmeas = (int)d.a.size(), nenv = (int)d.b.size(), npoints = (int)d.sasa_npoints;
-        vmd_grid_t grid;
+        vmd_grid_t grid{};
         const float* d_gb = nullptr;
         int have_grid = 0;
-        if (!p->d_out.ensure(c.nb) || !p->d_sasa_total.ensure(c.nb) || !ident_table(c, p, sasa_route[i], &have_grid, &grid, &d_gb)) return false;
-        const Stage& st = *c.src;
-        e->prof.begin(have_grid ? "sasa_atoms" : "sasa_brute", e->stream);
+        if (!k.ensure(p, c.nb) || !ident_table(c, p, neighbour_route[k.slot][i], &have_grid, &grid, &d_gb)) return false;
+        const size_t ident_row = have_grid ? (size_t)sr->nsel_pad : sr->idx.size();
+        auto sub = [&](const Sub& su) {
+            return NeighbourSub{e->stream, e->d_overflow.p, p, p->prop, acc_of(m, su), st, su, c.pbc, e->spec.within_closed ? 1 : 0,
+                    st.base + su.off * st.frame_stride, st.d_boxes.p + 9 * su.off, grid, have_grid ? d_gb + 9 * su.off : nullptr,
+                    have_grid ? sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad : nullptr,
+                    have_grid ? sr->cell_start.p + su.off * (size_t)(grid.ncell + 1) : nullptr, sr->nsel_pad,
+                    p->d_hb_ident.p + su.off * ident_row};
+        };
+        e->prof.begin(have_grid ? k.walk_label : k.brute_label, e->stream);
         for (auto& su : c.subs) {
-            const float* xyz = st.base + su.off * st.frame_stride;
-            uint64_t* acc = acc_of(m, su);
-            if (have_grid)
-                KRN_OK(vmd_hip_sasa_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, c.pbc, (int)su.nb, p->d_a.p, nmeas,
-                        p->d_b.p, nenv, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad, sr->cell_start.p + su.off * (size_t)(grid.ncell + 1),
-                        sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid, p->d_sasa_ra.p, p->d_sasa_rb.p, p->sasa_rmax_env,
-                        p->d_sasa_w.p, p->d_sasa_pts.p, npoints, d.rmax, closed, p->d_sasa_total.p + su.off, acc, e->d_overflow.p));
-            else
-                KRN_OK(vmd_hip_sasa_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
-                        p->d_a.p, nmeas, p->d_b.p, nenv, p->d_hb_ident.p + su.off * (size_t)nenv, p->d_sasa_ra.p, p->d_sasa_rb.p,
-                        p->sasa_rmax_env, p->d_sasa_w.p, p->d_sasa_pts.p, npoints, d.rmax, closed, p->d_sasa_total.p + su.off, acc,
-                        e->d_overflow.p));
-            KRN_OK(vmd_hip_sasa_finish(e->stream, p->d_sasa_total.p + su.off, (int)su.nb, p->d_out.p + su.off, acc + nmeas, e->d_overflow.p));
+            const NeighbourSub x = sub(su);
+            KRN_OK(have_grid ? k.walk(x) : k.brute(x));
+            if (!k.finish_label) KRN_OK(k.finish(x));
         }
         e->prof.end(e->stream);
-        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
-    }
-    return true;
-}
-
-// ---- contact maps.  launch_sasa's placement and rules: the record is added to behind the LAST cell build of the batch, every
-// statement's own build first (ident_routes with the entry list on both sides: it is sorted once, on the grid a within count of r_cut gets;
-// all pairs below shell_brute_below entries or where no grid exists) as a step of its own in front of launch_hbonds, every kernel under the
-// overflow flag, and a copy that another statement's build has re-sorted on another grid sends its statement to all pairs for this batch,
-// which sets the same bits.  Sub by sub the walk or all pairs into the batch's bit matrix (cleared by the launch, so also in a repeated
-// batch), then sub by sub the finish into the sub's partial of the record.
-bool RangeRun::build_contact_cells(BatchCtx& c) { return ident_routes(c, e->contact_props, &contact_route); }
-
-bool RangeRun::launch_contacts(BatchCtx& c) {
-    const int closed = e->spec.within_closed ? 1 : 0;
-    for (size_t i = 0; i < e->contact_props.size(); ++i) {
-        const int pi = e->contact_props[i];
-        PropState* p = e->props[pi].get();
-        const Property& d = p->prop;
-        const int nnative = (int)(d.ct_native.size() / 2);
-        if ((size_t)pi + 1 + (nnative ? 1 : 0) >= e->props.size() || e->props[pi + 1]->prop.form != Form::CONTACT_OCC ||
-            (nnative && e->props[pi + 2]->prop.form != Form::CONTACT_NATIVE))
-            return vmd_fail("contact count '%s' has lost its record", d.name.c_str());
-        PropState* m = e->props[pi + 1].get();
-        Selection* sr = e->sels[p->sel_b].get();
-        const int nent = (int)d.a.size(), G = (int)d.K;
-        const size_t W = ((size_t)G * (size_t)(G - 1) / 2 + 31) / 32;
-        vmd_grid_t grid;
-        const float* d_gb = nullptr;
-        int have_grid = 0;
-        if (!p->d_out.ensure(c.nb) || (nnative && !p->d_ct_q.ensure(c.nb)) || !p->d_ct_count.ensure(2 * c.nb) || !p->d_ct_bits.ensure(c.nb * W) ||
-            !ident_table(c, p, contact_route[i], &have_grid, &grid, &d_gb)) return false;
-        const Stage& st = *c.src;
-        e->prof.begin(have_grid ? "contact_atoms" : "contact_brute", e->stream);
-        for (auto& su : c.subs) {
-            const float* xyz = st.base + su.off * st.frame_stride;
-            uint32_t* bits = p->d_ct_bits.p + su.off * W;
-            if (have_grid)
-                KRN_OK(vmd_hip_contact_atoms(e->stream, xyz, st.frame_stride, st.row_stride, d_gb + 9 * su.off, c.pbc, (int)su.nb, p->d_a.p,
-                        p->d_c.p, nent, G, d.ct_min_sep, sr->sorted.p + su.off * 3 * (size_t)sr->nsel_pad,
-                        sr->cell_start.p + su.off * (size_t)(grid.ncell + 1), sr->nsel_pad, p->d_hb_ident.p + su.off * (size_t)sr->nsel_pad, grid,
-                        d.rmax, closed, g_opt.contact_lds_rows.load(), bits, e->d_overflow.p));
-            else
-                KRN_OK(vmd_hip_contact_brute(e->stream, xyz, st.frame_stride, st.row_stride, st.d_boxes.p + 9 * su.off, c.pbc, (int)su.nb,
-                        p->d_a.p, p->d_c.p, nent, G, d.ct_min_sep, p->d_hb_ident.p + su.off * (size_t)nent, d.rmax, closed, bits,
-                        e->d_overflow.p));
+        if (k.finish_label) {
+            e->prof.begin(k.finish_label, e->stream);
+            for (auto& su : c.subs) KRN_OK(k.finish(sub(su)));
+            e->prof.end(e->stream);
         }
-        e->prof.end(e->stream);
-        e->prof.begin("contact_finish", e->stream);
-        for (auto& su : c.subs)       // (every sub has its own rows of the bit matrix and of the counts)
-            KRN_OK(vmd_hip_contact_finish(e->stream, p->d_ct_bits.p + su.off * W, (int)su.nb, G, p->d_ct_native.p, nnative,
-                    p->d_ct_count.p + 2 * su.off, p->d_out.p + su.off, nnative ? p->d_ct_q.p + su.off : nullptr, acc_of(m, su),
-                    e->d_overflow.p));
-        e->prof.end(e->stream);
-        if (!queue_temporal_rows(c, pi, p->d_out.p)) return false;
-        if (nnative && !queue_temporal_rows(c, pi + 2, p->d_ct_q.p)) return false;
+        if (!queue_temporal_rows(c, pi, p->d_out.p) || (k.more_rows && !k.more_rows(*this, c, pi, p))) return false;
     }
     return true;
 }
@@ -606,7 +621,8 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     commits.clear();
     row = 0;
     forked = false;
-    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_sasa_cells(c) || !build_contact_cells(c) || !launch_hbonds(c) || !launch_sasa(c) || !launch_contacts(c) || !launch_shell_sdfs(c) ||
+    if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_neighbour_cells(c) ||
+        !launch_neighbours(c, kHbonds) || !launch_neighbours(c, kSasa) || !launch_neighbours(c, kContacts) || !launch_shell_sdfs(c) ||
         !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));

@@ -16,9 +16,9 @@
 //   shape_weights()              -> k_shape_moments + k_shape_finish (large sets) / k_shape_small (populations of small sets)
 //   rmsd()                       -> k_rmsd_shift + k_rmsd_moments + k_rmsd_finish (large sets) / k_rmsd_small; the frame-0 pose by the same kernels
 //   rmsf           -> rmsd's sums, k_rmsf_rotation, k_rmsf_accumulate (large sets) / k_rmsf_small
-//   hydrogen bonds -> k_sorted_atoms + k_hbond_atoms (the cell walk) / k_hbond_canon + k_hbond_brute (all pairs), k_hbond_finish
-//   accessible area -> k_sorted_atoms + k_sasa_atoms (the cell walk) / k_hbond_canon + k_sasa_brute (all pairs), k_sasa_finish
-//   contact maps   -> k_sorted_atoms + k_contact_atoms (the cell walk) / k_hbond_canon + k_contact_brute (all pairs),
+//   hydrogen bonds -> k_sorted_atoms + k_hbond_atoms (the cell walk) / k_canon_entries + k_hbond_brute (all pairs), k_hbond_finish
+//   accessible area -> k_sorted_atoms + k_sasa_atoms (the cell walk) / k_canon_entries + k_sasa_brute (all pairs), k_sasa_finish
+//   contact maps   -> k_sorted_atoms + k_contact_atoms (the cell walk) / k_canon_entries + k_contact_brute (all pairs),
 //                                   k_contact_finish_rows / _frames / _out
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
@@ -199,11 +199,25 @@ __device__ __forceinline__ void vmd_pair_coords(const vmd_box_t& b, float x, flo
     oy = b.py ? vmd_wrap(y, b.Ly, b.iLy) : y;
     oz = b.pz ? vmd_wrap(z, b.Lz, b.iLz) : z;
 }
+// the displacement of a pair of such positions, (i - j) - shift, the shift of the SPEC S3 / S3t image (vmd_pair_d2_tri's operations) ...
+__device__ __forceinline__ void vmd_pair_delta_general(const vmd_box_t& b, float xi, float yi, float zi, float xj, float yj, float zj,
+                                                       float& dx, float& dy, float& dz) {
+    if (b.tri) {
+        const float d0x = xi - xj, d0y = yi - yj, d0z = zi - zj;
+        float sx, sy, sz, shx, shy, shz;
+        vmd_frac(b, d0x, d0y, d0z, sx, sy, sz);
+        vmd_lattice_shift(b.Lx, b.Ly, b.Lz, b.xy, b.xz, b.yz, rintf(sx), rintf(sy), rintf(sz), shx, shy, shz);
+        dx = d0x - shx; dy = d0y - shy; dz = d0z - shz;
+        return;
+    }
+    dx = vmd_mi_cmp(xi - xj, b.Lx, 0.5f * b.Lx, b.px);
+    dy = vmd_mi_cmp(yi - yj, b.Ly, 0.5f * b.Ly, b.py);
+    dz = vmd_mi_cmp(zi - zj, b.Lz, 0.5f * b.Lz, b.pz);
+}
+// ... and its square: the one definition of a pair's squared distance
 __device__ __forceinline__ float vmd_pair_d2_general(const vmd_box_t& b, float xi, float yi, float zi, float xj, float yj, float zj) {
-    if (b.tri) return vmd_pair_d2_tri(b, xi, yi, zi, xj, yj, zj);
-    const float dx = vmd_mi_cmp(xi - xj, b.Lx, 0.5f * b.Lx, b.px);
-    const float dy = vmd_mi_cmp(yi - yj, b.Ly, 0.5f * b.Ly, b.py);
-    const float dz = vmd_mi_cmp(zi - zj, b.Lz, 0.5f * b.Lz, b.pz);
+    float dx, dy, dz;
+    vmd_pair_delta_general(b, xi, yi, zi, xj, yj, zj, dx, dy, dz);
     return vmd_d2(dx, dy, dz);
 }
 // SPEC S5/S6 minimum image of a Cartesian displacement by rounding (fp32 / fp64)
@@ -2150,26 +2164,41 @@ struct vmd_within_brute_params_t {
     size_t flag_stride;         // ATOMS instantiation: flags is u8[B][flag_stride] indexed by ATOM, flags[b][tgt[t]]
 };
 
-// all pairs from the raw frame (any cell, any cutoff), the device-side definition the cell walk below is tested against: one lane per
-// target atom (xi, yi, zi; `active` false: a lane without one), the reference list staged through the caller's LDS tile 256 entries at a
-// time by the block's NT threads, a lane stops testing at its first hit.  Every thread of the block calls it: two barriers per tile.
+// All pairs from the raw frame (any cell, any cutoff), the one tile loop of every all-pairs kernel: one lane per atom at the wrapped position
+// (xi, yi, zi) (`active` false: a lane without one), the list (nullptr: every atom) staged through the caller's LDS tile 256 entries at a
+// time by the block's NT threads, from tile `first` on (block-uniform; 0 but for an upper triangle).  stage(slot, pos) runs for every
+// entry as it is staged, between the same two barriers, and fills the kernel's own LDS columns; visit(slot, pos, ex, ey, ez) runs in the
+// lane for every staged entry, e = (lane - entry) - shift of the S3 / S3t image, and returns true when the lane has seen enough (-> true).
+// Every thread of the block calls it: two barriers per tile.
+template <int NT, class Stage, class Visit>
+__device__ __forceinline__ bool vmd_all_pairs(float (&s_r)[3][256], const vmd_box_t& bx, const float* fx, const float* fy, const float* fz,
+        const int32_t* list, int n, int first, bool active, float xi, float yi, float zi, Stage stage, Visit visit) {
+    bool stop = false;
+    for (int j0 = first; j0 < n; j0 += 256) {
+        __syncthreads();
+        const int nj = n - j0 < 256 ? n - j0 : 256;
+        for (int jj = threadIdx.x; jj < nj; jj += NT) {
+            const int a = list ? list[j0 + jj] : j0 + jj;
+            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
+            stage(jj, j0 + jj);
+        }
+        __syncthreads();
+        if (active && !stop)
+            for (int jj = 0; jj < nj && !stop; ++jj) {
+                float ex, ey, ez;
+                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
+                stop = visit(jj, j0 + jj, ex, ey, ez);
+            }
+    }
+    return stop;
+}
+
+// within() by all pairs, the device-side definition the cell walk below is tested against: a lane stops testing at its first hit
 template <int NT>
 __device__ __forceinline__ bool vmd_within_all_pairs(float (&s_r)[3][256], const vmd_box_t& bx, const float* fx, const float* fy,
         const float* fz, const int32_t* ref, int nref, const vmd_within_test_t& w, bool active, float xi, float yi, float zi) {
-    bool hit = false;
-    for (int j0 = 0; j0 < nref; j0 += 256) {
-        __syncthreads();
-        const int nj = nref - j0 < 256 ? nref - j0 : 256;
-        for (int jj = threadIdx.x; jj < nj; jj += NT) {
-            const int a = ref ? ref[j0 + jj] : j0 + jj;
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
-        }
-        __syncthreads();
-        if (active && !hit)
-            for (int jj = 0; jj < nj && !hit; ++jj)
-                hit = vmd_within_hit(w, vmd_pair_d2_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj]));
-    }
-    return hit;
+    return vmd_all_pairs<NT>(s_r, bx, fx, fy, fz, ref, nref, 0, active, xi, yi, zi, [](int, int) {},
+                             [&](int, int, float ex, float ey, float ez) { return vmd_within_hit(w, vmd_d2(ex, ey, ez)); });
 }
 
 // One lane per target atom over vmd_within_all_pairs, one integer atomic per wave.
@@ -2235,17 +2264,20 @@ __device__ __forceinline__ vmd_within_walk_t vmd_within_walk_setup(const float* 
     return k;
 }
 
-// The cell walk: does the atom at (xi, yi, zi), standing in pencil (py, pz) of the grid, have a member of R in range?  R comes cell-sorted
+// The cell walk: which members of R are in range of the atom at (xi, yi, zi), standing in pencil (py, pz) of the grid?  R comes cell-sorted
 // (K1), so the x window [x - r, x + r] of a neighbour pencil is one run of the sorted copy per periodic image; pencils, images, window
 // arithmetic and the pair arithmetic are those of k_rdf_pencil (the neighbour cell's image is the comparison's for every d < r_max), with
-// the window of ONE atom instead of a chunk's.  A lane leaves the walk at its first hit.
-__device__ __forceinline__ bool vmd_within_walk(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi) {
-    bool hit = false;
-    for (int dz = -k.rz; dz <= k.rz && !hit; ++dz) {
+// the window of ONE atom instead of a chunk's.  visit(slot, ex, ey, ez) for every member that passes vmd_within_hit, e = (atom - member) -
+// shift; it returns true when the lane has seen enough, and the lane leaves the walk (-> true).  A pair is met under one image only: a grid exists
+// only where the minimum image is unique for every hit (choose_grid), so the other images of a slot fail the distance.
+template <class Visit>
+__device__ __forceinline__ bool vmd_within_walk_each(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi, Visit visit) {
+    bool stop = false;
+    for (int dz = -k.rz; dz <= k.rz && !stop; ++dz) {
         int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
         if (k.open_z && (qz < 0 || qz >= k.nz)) continue;
         if (qz < 0) { qz += k.nz; sz = -k.Lz; nc = -1.0f; } else if (qz >= k.nz) { qz -= k.nz; sz = k.Lz; nc = 1.0f; }
-        for (int dy = -k.ry; dy <= k.ry && !hit; ++dy) {
+        for (int dy = -k.ry; dy <= k.ry && !stop; ++dy) {
             int qy = py + dy; float sy = 0.0f, nb = 0.0f;
             if (k.open_y && (qy < 0 || qy >= k.ny)) continue;
             if (qy < 0) { qy += k.ny; sy = -k.Ly; nb = -1.0f; } else if (qy >= k.ny) { qy -= k.ny; sy = k.Ly; nb = 1.0f; }
@@ -2264,7 +2296,7 @@ __device__ __forceinline__ bool vmd_within_walk(const vmd_within_walk_t& k, int 
                 offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
                 offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
             }
-            for (int kx = -1; kx <= 1 && !hit; ++kx) {
+            for (int kx = -1; kx <= 1 && !stop; ++kx) {
                 if (k.open_x && kx != 0) continue;
                 float sx = (float)kx * k.Lx, sy2 = sy, sz2 = sz;
                 if (k.tri) vmd_lattice_shift(k.Lx, k.Ly, k.Lz, k.txy, k.txz, k.tyz, (float)kx, nb, nc, sx, sy2, sz2);
@@ -2274,14 +2306,29 @@ __device__ __forceinline__ bool vmd_within_walk(const vmd_within_walk_t& k, int 
                 const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, k.inv_cx, k.nxf);
                 const int cb = hi >= k.Lx ? k.nxf - 1 : vmd_cell_coord(hi, k.inv_cx, k.nxf);
                 const unsigned ja = k.csr[qp * k.nxf + ca], jb = k.csr[qp * k.nxf + cb + 1];
-                for (unsigned j = ja; j < jb && !hit; ++j) {
+                for (unsigned j = ja; j < jb && !stop; ++j) {
                     const float dx = (xi - k.xr[j]) - sx, dy_ = (yi - k.yr[j]) - sy2, dz_ = (zi - k.zr[j]) - sz2;
-                    hit = vmd_within_hit(k.w, vmd_d2(dx, dy_, dz_));
+                    stop = vmd_within_hit(k.w, vmd_d2(dx, dy_, dz_)) && visit(j, dx, dy_, dz_);
                 }
             }
         }
     }
-    return hit;
+    return stop;
+}
+// within(): a lane leaves the walk at its first hit
+__device__ __forceinline__ bool vmd_within_walk(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi) {
+    return vmd_within_walk_each(k, py, pz, xi, yi, zi, [](unsigned, float, float, float) { return true; });
+}
+
+// what a lane of a walk in LIST order stands on: entry t of the list c wrapped and binned with vmd_cell_of - the function every cell build
+// bins with, on the same fp32 values - so its cell, its pencil (py, pz) and its coordinates are what a build would have stored for it
+struct vmd_walk_lane_t { uint32_t cell; int py, pz; float x, y, z; };
+__device__ __forceinline__ vmd_walk_lane_t vmd_walk_lane(const vmd_cells_params_t& c, const vmd_within_walk_t& k, int b, int t) {
+    vmd_walk_lane_t l;
+    l.cell = vmd_cell_of(c, b, t, l.x, l.y, l.z);
+    const int pen = (int)(l.cell / (uint32_t)k.nxf);
+    l.pz = pen / k.ny; l.py = pen - l.pz * k.ny;
+    return l;
 }
 
 struct vmd_within_pencil_params_t {
@@ -2338,10 +2385,8 @@ __global__ __launch_bounds__(256) void k_within_atoms(vmd_within_atoms_params_t 
     const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
     bool hit = false;
     if (t < p.c.nsel) {
-        float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
-        const int pz = pen / k.ny, py = pen - pz * k.ny;
-        hit = vmd_within_walk(k, py, pz, xi, yi, zi);
+        const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
+        hit = vmd_within_walk(k, l.py, l.pz, l.x, l.y, l.z);
         p.mask[(size_t)b * p.mask_stride + (size_t)vmd_sel_atom(p.c, t)] = hit ? 1 : 0;
     }
     const unsigned long long m = __ballot(hit ? 1 : 0);
@@ -2378,10 +2423,8 @@ __global__ __launch_bounds__(256) void k_within_atoms_expr(vmd_within_atoms_expr
     if (!__ballot(go ? 1 : 0)) return;
     const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
     if (go) {
-        float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
-        const int pz = pen / k.ny, py = pen - pz * k.ny;
-        if (vmd_within_walk(k, py, pz, xi, yi, zi)) p.bits[at] = (unsigned char)(cur | (1u << p.term));
+        const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
+        if (vmd_within_walk(k, l.py, l.pz, l.x, l.y, l.z)) p.bits[at] = (unsigned char)(cur | (1u << p.term));
     }
 }
 
@@ -4312,22 +4355,6 @@ __device__ __forceinline__ bool vmd_hbond_rule(const vmd_hbond_pair_t& q, float 
     return a != q.d && a != q.h && vmd_hbond_angle(c2, q.hx, q.hy, q.hz, ex, ey, ez);
 }
 
-// vmd_pair_d2_general's displacement before it is squared: (i - j) - shift, the shift of the SPEC S3 / S3t image
-__device__ __forceinline__ void vmd_pair_delta_general(const vmd_box_t& b, float xi, float yi, float zi, float xj, float yj, float zj,
-                                                       float& dx, float& dy, float& dz) {
-    if (b.tri) {
-        const float d0x = xi - xj, d0y = yi - yj, d0z = zi - zj;
-        float sx, sy, sz, shx, shy, shz;
-        vmd_frac(b, d0x, d0y, d0z, sx, sy, sz);
-        vmd_lattice_shift(b.Lx, b.Ly, b.Lz, b.xy, b.xz, b.yz, rintf(sx), rintf(sy), rintf(sz), shx, shy, shz);
-        dx = d0x - shx; dy = d0y - shy; dz = d0z - shz;
-        return;
-    }
-    dx = vmd_mi_cmp(xi - xj, b.Lx, 0.5f * b.Lx, b.px);
-    dy = vmd_mi_cmp(yi - yj, b.Ly, 0.5f * b.Ly, b.py);
-    dz = vmd_mi_cmp(zi - zj, b.Lz, 0.5f * b.Lz, b.pz);
-}
-
 __device__ __forceinline__ void vmd_atomic_add_u64(uint64_t* p, uint64_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 // (the SIMT emulator under tests/emu runs one lane at a time and its header has no atomicMin: there the claim is the plain compare and
 // store its other atomics are)
@@ -4339,20 +4366,47 @@ __device__ __forceinline__ void vmd_atomic_min_u32(uint32_t* p, uint32_t v) {
 #endif
 }
 
+// The lanes' values summed over the wave (xor shuffles), ONE atomic of the wave's leader where the sum is not zero.  Every lane of the wave
+// calls them.
+__device__ __forceinline__ void vmd_wave_add_u32(unsigned* dst, unsigned v) {
+    int tot = (int)v;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += vmd_shfl_xor_i32(tot, o);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(dst, (unsigned)tot);
+}
+__device__ __forceinline__ void vmd_wave_add_u64(uint64_t* dst, uint64_t v) {
+    uint64_t tot = v;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)tot, o), hi = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)(tot >> 32), o);
+        tot += ((uint64_t)hi << 32) | lo;
+    }
+    if ((threadIdx.x & 63) == 0 && tot) vmd_atomic_add_u64(dst, tot);
+}
+
 // what a lane has found goes out the same way from the walk and from all pairs: the lanes' bond counts summed over the wave into ONE u32
 // atomic on the frame's count, one u64 atomic per lane with bonds into its donor row.  (The acceptor rows take one atomic per bond, where
 // the bond is found.)  Every lane of the wave calls it.
 __device__ __forceinline__ void vmd_hbond_commit(unsigned* frame_count, uint64_t* donor_row, unsigned n) {
     if (n) vmd_atomic_add_u64(donor_row, n);
-    int tot = (int)n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tot += vmd_shfl_xor_i32(tot, o);
-    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(frame_count, (unsigned)tot);
+    vmd_wave_add_u32(frame_count, n);
 }
 
-// The identity of a cell-sorted copy, recovered without touching the cell build: one lane per list entry t.  vmd_cell_of gives the entry's
-// cell and wrapped coordinates - the values the build binned and stored (k_within_atoms relies on the same fact) -, the lane scans that
-// cell's run of the sorted copy for slots whose three coordinates equal its own bit for bit and claims them with atomicMin (vmd_atomic_min_u32).  ident is
+// An entry's own slots in a cell-sorted copy (cs: its cell_start, xr / yr / zr: its rows, n entries): visit(slot), in ascending order, for
+// every slot in the run of the entry's cell whose three coordinates equal the entry's wrapped ones bit for bit - vmd_cell_of gives the
+// values the build binned and stored -, until it returns true.  (A table is never trusted beyond the copy it indexes.)
+template <class Visit>
+__device__ __forceinline__ void vmd_own_slots(const uint32_t* cs, const float* xr, const float* yr, const float* zr, uint32_t n,
+                                              uint32_t cell, float x, float y, float z, Visit visit) {
+    const int bx_ = __float_as_int(x), by_ = __float_as_int(y), bz_ = __float_as_int(z);
+    uint32_t s0 = cs[cell], s1 = cs[cell + 1];
+    if (s1 > n) s1 = n;
+    for (uint32_t s = s0; s < s1; ++s)
+        if (__float_as_int(xr[s]) == bx_ && __float_as_int(yr[s]) == by_ && __float_as_int(zr[s]) == bz_ && visit(s)) break;
+}
+
+// The identity of a cell-sorted copy, recovered without touching the cell build: one lane per list entry t.  The lane claims every slot of
+// its own (vmd_own_slots) with atomicMin (vmd_atomic_min_u32).  ident is
 // u32[B][nsel_pad], preset to 0xffffffff by the launcher.  DECISION(D-HB-COINCIDENT): entries that coincide bit for bit in a frame share
 // their slots, and every one of those slots answers as the LOWEST such entry; a slot left at 0xffffffff after the pass is a bug.
 struct vmd_sorted_atoms_params_t {
@@ -4372,58 +4426,7 @@ __global__ __launch_bounds__(256) void k_sorted_atoms(vmd_sorted_atoms_params_t 
     const float* yr = xr + p.c.nsel_pad;
     const float* zr = yr + p.c.nsel_pad;
     uint32_t* id = p.ident + (size_t)b * p.c.nsel_pad;
-    const int bx_ = __float_as_int(xw), by_ = __float_as_int(yw), bz_ = __float_as_int(zw);
-    uint32_t s0 = cs[cell], s1 = cs[cell + 1];
-    if (s1 > (uint32_t)p.c.nsel) s1 = (uint32_t)p.c.nsel;       // (a table is never trusted beyond the copy it indexes)
-    for (uint32_t s = s0; s < s1; ++s)
-        if (__float_as_int(xr[s]) == bx_ && __float_as_int(yr[s]) == by_ && __float_as_int(zr[s]) == bz_) vmd_atomic_min_u32(&id[s], (uint32_t)t);
-}
-
-// vmd_within_walk's sibling that does not leave at the first hit: the same pencils, images, windows and pair arithmetic, and
-// on_hit(slot, ex, ey, ez) for EVERY member of R at 0 <= d <= / < r_max, e = (atom - member) - shift.  A pair is met under one image only:
-// a grid exists only where the minimum image is unique for every hit (choose_grid), so the other images of a slot fail the distance.
-template <class OnHit>
-__device__ __forceinline__ void vmd_within_walk_all(const vmd_within_walk_t& k, int py, int pz, float xi, float yi, float zi, OnHit on_hit) {
-    for (int dz = -k.rz; dz <= k.rz; ++dz) {
-        int qz = pz + dz; float sz = 0.0f, nc = 0.0f;
-        if (k.open_z && (qz < 0 || qz >= k.nz)) continue;
-        if (qz < 0) { qz += k.nz; sz = -k.Lz; nc = -1.0f; } else if (qz >= k.nz) { qz -= k.nz; sz = k.Lz; nc = 1.0f; }
-        for (int dy = -k.ry; dy <= k.ry; ++dy) {
-            int qy = py + dy; float sy = 0.0f, nb = 0.0f;
-            if (k.open_y && (qy < 0 || qy >= k.ny)) continue;
-            if (qy < 0) { qy += k.ny; sy = -k.Ly; nb = -1.0f; } else if (qy >= k.ny) { qy -= k.ny; sy = k.Ly; nb = 1.0f; }
-            const int qp = qz * k.ny + qy;
-            float offmin = 0.0f, offmax = 0.0f, rpad = k.rpad;
-            if (!k.tri && !k.open && (dy > 1 || dy < -1 || dz > 1 || dz < -1)) {      // split pencils: the outer ones see a shorter window
-                const float gy = (float)((dy < 0 ? -dy : dy) - 1) * (k.Ly / (float)k.ny), gz = (float)((dz < 0 ? -dz : dz) - 1) * (k.Lz / (float)k.nz);
-                const float gyy = gy > 0.0f ? gy : 0.0f, gzz = gz > 0.0f ? gz : 0.0f;
-                const float rr = k.rpad * k.rpad - 0.998f * (gyy * gyy + gzz * gzz);
-                if (rr <= 0.0f) continue;
-                rpad = sqrtf(rr) * 1.0001f;
-            }
-            if (k.tri) {
-                const float y0 = k.txy * ((float)qy / (float)k.ny), y1 = k.txy * ((float)(qy + 1) / (float)k.ny);
-                const float z0 = k.txz * ((float)qz / (float)k.nz), z1 = k.txz * ((float)(qz + 1) / (float)k.nz);
-                offmin = fminf(y0, y1) + fminf(z0, z1) - 1.0e-3f;
-                offmax = fmaxf(y0, y1) + fmaxf(z0, z1) + 1.0e-3f;
-            }
-            for (int kx = -1; kx <= 1; ++kx) {
-                if (k.open_x && kx != 0) continue;
-                float sx = (float)kx * k.Lx, sy2 = sy, sz2 = sz;
-                if (k.tri) vmd_lattice_shift(k.Lx, k.Ly, k.Lz, k.txy, k.txz, k.tyz, (float)kx, nb, nc, sx, sy2, sz2);
-                const float lo = (xi - rpad) - sx - offmax - k.orgx - k.pad_open;
-                const float hi = (xi + rpad) - sx - offmin - k.orgx + k.pad_open;
-                if (hi < 0.0f || lo >= k.Lx) continue;
-                const int ca = lo <= 0.0f ? 0 : vmd_cell_coord(lo, k.inv_cx, k.nxf);
-                const int cb = hi >= k.Lx ? k.nxf - 1 : vmd_cell_coord(hi, k.inv_cx, k.nxf);
-                const unsigned ja = k.csr[qp * k.nxf + ca], jb = k.csr[qp * k.nxf + cb + 1];
-                for (unsigned j = ja; j < jb; ++j) {
-                    const float dx = (xi - k.xr[j]) - sx, dy_ = (yi - k.yr[j]) - sy2, dz_ = (zi - k.zr[j]) - sz2;
-                    if (vmd_within_hit(k.w, vmd_d2(dx, dy_, dz_))) on_hit(j, dx, dy_, dz_);
-                }
-            }
-        }
-    }
+    vmd_own_slots(cs, xr, yr, zr, (uint32_t)p.c.nsel, cell, xw, yw, zw, [&](uint32_t s) { vmd_atomic_min_u32(&id[s], (uint32_t)t); return false; });
 }
 
 struct vmd_hbond_atoms_params_t {
@@ -4437,7 +4440,7 @@ struct vmd_hbond_atoms_params_t {
     const uint32_t* skip;
 };
 
-// The walk, one lane per donor pair j in list order; D's pencil as k_within_atoms derives a target's.  Every distance hit is put to rules
+// The walk, one lane per donor pair j in list order, D standing where vmd_walk_lane puts it.  Every distance hit is put to rules
 // 2 - 4 (rule 4 first, see below).  Lanes of a wave are spatially unrelated, as in k_within_atoms: hits are few (about ten per donor at 3.5 A in
 // water) and are taken where they are found, without compaction.
 __global__ __launch_bounds__(256) void k_hbond_atoms(vmd_hbond_atoms_params_t p) {
@@ -4447,9 +4450,7 @@ __global__ __launch_bounds__(256) void k_hbond_atoms(vmd_hbond_atoms_params_t p)
     const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
     unsigned n = 0;
     if (t < p.c.nsel) {
-        float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
-        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
         const float* fx = p.c.xyz + (size_t)b * p.c.frame_stride;
         const vmd_hbond_pair_t q = vmd_hbond_pair(vmd_load_box(p.fboxes, b, p.c.pbc), fx, fx + p.c.row_stride, fx + 2 * p.c.row_stride,
                                                   p.c.sel[t], p.hyd[t]);
@@ -4458,32 +4459,33 @@ __global__ __launch_bounds__(256) void k_hbond_atoms(vmd_hbond_atoms_params_t p)
         const int nacc = p.nacc;
         const int32_t* accl = p.accl;
         const float c2 = p.c2;
-        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float ex, float ey, float ez) {
+        vmd_within_walk_each(k, l.py, l.pz, l.x, l.y, l.z, [&](unsigned j, float ex, float ey, float ez) {
             // the angle first: it needs no memory and drops all but a few per cent of the distance hits (the donor itself at d = 0 among
             // them), so the two dependent loads of the identity are paid by what is nearly a bond.  The conjunction is the same.
-            if (!vmd_hbond_angle(c2, q.hx, q.hy, q.hz, ex, ey, ez)) return;
+            if (!vmd_hbond_angle(c2, q.hx, q.hy, q.hz, ex, ey, ez)) return false;
             const uint32_t a = id[j];
-            if (a >= (uint32_t)nacc) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            if (a >= (uint32_t)nacc) return false;    // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
             const int aa = accl[a];
             if (aa != q.d && aa != q.h) { vmd_atomic_add_u64(acc_rows + a, 1); n += 1; }
+            return false;
         });
     }
     vmd_hbond_commit(p.count + b, p.acc + (t < p.c.nsel ? t : 0), n);
 }
 
-// D-HB-COINCIDENT for the all-pairs route, which has no sorted copy to ask: canon[b][k] = the lowest list entry whose wrapped coordinates in
-// frame b equal entry k's bit for bit (k itself where nothing coincides) - what k_sorted_atoms' table answers for k's slot.
-struct vmd_hbond_brute_params_t {
+// The coincidence table of every all-pairs route, which has no sorted copy to ask (D-HB-COINCIDENT, D-SASA-COINCIDENT, D-CT-COINCIDENT):
+// canon[b][k] = the lowest entry of the list whose wrapped coordinates in frame b equal entry k's bit for bit (k itself where nothing
+// coincides) - what k_sorted_atoms' table answers for k's slot.  One lane per entry over vmd_all_pairs, up to the block's highest entry;
+// the lane compares the staged bit patterns and leaves at its first match or at itself.
+struct vmd_canon_params_t {
     const float* xyz; size_t frame_stride; size_t row_stride;
     const float* boxes; uint32_t pbc;
-    const int32_t* don; const int32_t* hyd; int npairs; const int32_t* accl; int nacc;
-    uint32_t* canon;            // u32[B][nacc]
-    vmd_within_test_t w; float c2;
-    unsigned* count; uint64_t* acc; const uint32_t* skip;
-    uint32_t* list; uint32_t list_cap; unsigned* list_count;      // LIST: u32[list_cap][2] = {pair j, acceptor list position}, the bonds found
+    const int32_t* list; int n;
+    uint32_t* canon;            // u32[B][n]
+    const uint32_t* skip;
 };
-__global__ __launch_bounds__(256) void k_hbond_canon(vmd_hbond_brute_params_t p) {
-    __shared__ int s_r[3][256];
+__global__ __launch_bounds__(256) void k_canon_entries(vmd_canon_params_t p) {
+    __shared__ float s_r[3][256];
     if (p.skip && *p.skip) return;
     const int b = blockIdx.y;
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -4491,31 +4493,35 @@ __global__ __launch_bounds__(256) void k_hbond_canon(vmd_hbond_brute_params_t p)
     const float* fy = fx + p.row_stride;
     const float* fz = fy + p.row_stride;
     const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const bool valid = k < p.n;
     float xi = 0.0f, yi = 0.0f, zi = 0.0f;
-    if (k < p.nacc) { const int a = p.accl[k]; vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi); }
+    if (valid) { const int a = p.list[k]; vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi); }
     const int bxi = __float_as_int(xi), byi = __float_as_int(yi), bzi = __float_as_int(zi);
     int found = k;
-    const int last = blockIdx.x * 256 + 255 < p.nacc ? blockIdx.x * 256 + 255 : p.nacc - 1;       // the block's highest entry
-    for (int j0 = 0; j0 <= last; j0 += 256) {
-        __syncthreads();
-        const int jj0 = j0 + threadIdx.x;
-        if (jj0 < p.nacc) {
-            const int a = p.accl[jj0];
-            float x, y, z;
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], x, y, z);
-            s_r[0][threadIdx.x] = __float_as_int(x); s_r[1][threadIdx.x] = __float_as_int(y); s_r[2][threadIdx.x] = __float_as_int(z);
-        }
-        __syncthreads();
-        const int nj = p.nacc - j0 < 256 ? p.nacc - j0 : 256;
-        for (int jj = 0; jj < nj && j0 + jj < found; ++jj)
-            if (s_r[0][jj] == bxi && s_r[1][jj] == byi && s_r[2][jj] == bzi) found = j0 + jj;
-    }
-    if (k < p.nacc) p.canon[(size_t)b * p.nacc + k] = (uint32_t)found;
+    const int last = blockIdx.x * 256 + 255 < p.n ? blockIdx.x * 256 + 255 : p.n - 1;       // the block's highest entry
+    vmd_all_pairs<256>(s_r, bx, fx, fy, fz, p.list, last + 1, 0, valid, xi, yi, zi, [](int, int) {},
+        [&](int jj, int pos, float, float, float) {
+            if (pos >= k) return true;
+            if (__float_as_int(s_r[0][jj]) != bxi || __float_as_int(s_r[1][jj]) != byi || __float_as_int(s_r[2][jj]) != bzi) return false;
+            found = pos;
+            return true;
+        });
+    if (valid) p.canon[(size_t)b * p.n + k] = (uint32_t)found;
 }
 
-// All pairs from the raw frame: one lane per donor pair, the acceptors staged through an LDS tile like vmd_within_all_pairs, identity = the
-// list position (through canon).  The same rules, the same outputs as the walk.  LIST: the bonds go to a capped buffer through a counter
-// instead (vmd_eval_hbond_pairs), nothing is accumulated.
+struct vmd_hbond_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc;
+    const int32_t* don; const int32_t* hyd; int npairs; const int32_t* accl; int nacc;
+    const uint32_t* canon;      // k_canon_entries' table of the acceptors, u32[B][nacc]
+    vmd_within_test_t w; float c2;
+    unsigned* count; uint64_t* acc; const uint32_t* skip;
+    uint32_t* list; uint32_t list_cap; unsigned* list_count;      // LIST: u32[list_cap][2] = {pair j, acceptor list position}, the bonds found
+};
+
+// All pairs from the raw frame: one lane per donor pair over vmd_all_pairs, the acceptors staged with their canonical entry and its atom,
+// identity = the list position (through canon).  The same rules, the same outputs as the walk.  LIST: the bonds go to a capped buffer
+// through a counter instead (vmd_eval_hbond_pairs), nothing is accumulated.
 template <bool LIST>
 __global__ __launch_bounds__(256) void k_hbond_brute(vmd_hbond_brute_params_t p) {
     __shared__ float s_r[3][256];
@@ -4537,31 +4543,19 @@ __global__ __launch_bounds__(256) void k_hbond_brute(vmd_hbond_brute_params_t p)
     }
     const uint32_t* canon = p.canon + (size_t)b * p.nacc;
     unsigned n = 0;
-    for (int j0 = 0; j0 < p.nacc; j0 += 256) {
-        __syncthreads();
-        const int nj = p.nacc - j0 < 256 ? p.nacc - j0 : 256;
-        if ((int)threadIdx.x < nj) {
-            const int jj = threadIdx.x;
-            const int a = p.accl[j0 + jj];
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
-            s_k[jj] = canon[j0 + jj];
-            s_a[jj] = p.accl[s_k[jj]];
-        }
-        __syncthreads();
-        if (valid)
-            for (int jj = 0; jj < nj; ++jj) {
-                float ex, ey, ez;
-                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
-                if (!vmd_within_hit(p.w, vmd_d2(ex, ey, ez)) || !vmd_hbond_rule(q, p.c2, s_a[jj], ex, ey, ez)) continue;
-                if (LIST) {
-                    const unsigned slot = atomicAdd(p.list_count, 1u);
-                    if (slot < p.list_cap) { p.list[2 * (size_t)slot] = (uint32_t)t; p.list[2 * (size_t)slot + 1] = (uint32_t)(j0 + jj); }
-                } else {
-                    vmd_atomic_add_u64(p.acc + p.npairs + s_k[jj], 1);
-                    n += 1;
-                }
+    vmd_all_pairs<256>(s_r, bx, fx, fy, fz, p.accl, p.nacc, 0, valid, xi, yi, zi,
+        [&](int jj, int pos) { s_k[jj] = canon[pos]; s_a[jj] = p.accl[s_k[jj]]; },
+        [&](int jj, int pos, float ex, float ey, float ez) {
+            if (!vmd_within_hit(p.w, vmd_d2(ex, ey, ez)) || !vmd_hbond_rule(q, p.c2, s_a[jj], ex, ey, ez)) return false;
+            if (LIST) {
+                const unsigned slot = atomicAdd(p.list_count, 1u);
+                if (slot < p.list_cap) { p.list[2 * (size_t)slot] = (uint32_t)t; p.list[2 * (size_t)slot + 1] = (uint32_t)pos; }
+            } else {
+                vmd_atomic_add_u64(p.acc + p.npairs + s_k[jj], 1);
+                n += 1;
             }
-    }
+            return false;
+        });
     if (!LIST) vmd_hbond_commit(p.count + b, p.acc + (valid ? t : 0), n);
 }
 
@@ -4653,13 +4647,7 @@ __device__ __forceinline__ void vmd_sasa_neighbour(uint32_t (&m)[W], int P, cons
 // n_i w_i summed over the wave into ONE u64 atomic on the frame's total.  Every lane of the wave calls it.
 __device__ __forceinline__ void vmd_sasa_commit(uint64_t* frame_total, uint64_t* row, unsigned n, uint32_t weight) {
     if (n) vmd_atomic_add_u64(row, n);
-    uint64_t tot = (uint64_t)n * (uint64_t)weight;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)tot, o), hi = (uint32_t)vmd_shfl_xor_i32((int)(uint32_t)(tot >> 32), o);
-        tot += ((uint64_t)hi << 32) | lo;
-    }
-    if ((threadIdx.x & 63) == 0 && tot) vmd_atomic_add_u64(frame_total, tot);
+    vmd_wave_add_u64(frame_total, (uint64_t)n * (uint64_t)weight);
 }
 
 struct vmd_sasa_atoms_params_t {
@@ -4674,7 +4662,7 @@ struct vmd_sasa_atoms_params_t {
     const uint32_t* skip;
 };
 
-// The walk, one lane per measured entry in list order; its pencil as k_hbond_atoms derives a donor's.  The lane keeps its point bits in W
+// The walk, one lane per measured entry in list order, standing where vmd_walk_lane puts it.  The lane keeps its point bits in W
 // registers.  Lanes of a wave are spatially unrelated: a neighbour is taken where it is found, without compaction.
 template <int W>
 __global__ __launch_bounds__(256) void k_sasa_atoms(vmd_sasa_atoms_params_t p) {
@@ -4688,9 +4676,7 @@ __global__ __launch_bounds__(256) void k_sasa_atoms(vmd_sasa_atoms_params_t p) {
     unsigned n = 0;
     uint32_t weight = 0;
     if (t < p.c.nsel) {
-        float xi, yi, zi;
-        const int pen = (int)(vmd_cell_of(p.c, b, t, xi, yi, zi) / (uint32_t)k.nxf);
-        const int pz = pen / k.ny, py = pen - pz * k.ny;
+        const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
         const vmd_sasa_entry_t q = vmd_sasa_entry(p.c.sel[t], p.r_meas[t], p.rmax_env);
         const uint32_t* id = p.ident + (size_t)b * p.k.nref_pad;
         const int nenv = p.nenv;
@@ -4698,14 +4684,15 @@ __global__ __launch_bounds__(256) void k_sasa_atoms(vmd_sasa_atoms_params_t p) {
         const float* r_env = p.r_env;
         uint32_t m[W];
         vmd_sasa_mask_full(m, P);
-        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float ex, float ey, float ez) {
+        vmd_within_walk_each(k, l.py, l.pz, l.x, l.y, l.z, [&](unsigned j, float ex, float ey, float ez) {
             // rule 2 against the largest environment radius first: it needs no memory.  A lane whose points are all buried has nothing
-            // left to clear
+            // left to clear (and walks on all the same)
             const float d2 = vmd_d2(ex, ey, ez);
-            if (!(d2 < q.smax2) || !vmd_sasa_mask_any(m)) return;
+            if (!(d2 < q.smax2) || !vmd_sasa_mask_any(m)) return false;
             const uint32_t a = id[j];
-            if (a >= (uint32_t)nenv) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            if (a >= (uint32_t)nenv) return false;    // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
             vmd_sasa_neighbour(m, P, s_u, q, envl[a], r_env[a], d2, ex, ey, ez);
+            return false;
         });
         n = vmd_sasa_mask_count(m);
         weight = p.weight[t];
@@ -4717,7 +4704,7 @@ struct vmd_sasa_brute_params_t {
     const float* xyz; size_t frame_stride; size_t row_stride;
     const float* boxes; uint32_t pbc;
     const int32_t* meas; int nmeas; const int32_t* envl; int nenv;
-    const uint32_t* canon;      // k_hbond_canon's table of the environment, u32[B][nenv]
+    const uint32_t* canon;      // k_canon_entries' table of the environment, u32[B][nenv]
     const float* r_meas; const float* r_env; float rmax_env;
     const uint32_t* weight;
     const float* points; int npoints;
@@ -4726,7 +4713,7 @@ struct vmd_sasa_brute_params_t {
     uint32_t* counts;           // LIST: u32[nmeas], n_i of the one frame
 };
 
-// All pairs from the raw frame: one lane per measured entry, the environment staged through an LDS tile of 256 with its canonical entry's
+// All pairs from the raw frame: one lane per measured entry over vmd_all_pairs, the environment staged with its canonical entry's
 // atom and R.  The same rules, the same outputs as the walk.  LIST: the point counts of the frame go to counts[nmeas] instead
 // (vmd_eval_sasa_atoms), nothing is accumulated.
 template <bool LIST>
@@ -4755,27 +4742,14 @@ __global__ __launch_bounds__(256) void k_sasa_brute(vmd_sasa_brute_params_t p) {
         vmd_pair_coords(bx, fx[q.atom], fy[q.atom], fz[q.atom], xi, yi, zi);
     }
     const uint32_t* canon = p.canon + (size_t)b * p.nenv;
-    for (int j0 = 0; j0 < p.nenv; j0 += 256) {
-        __syncthreads();
-        const int nj = p.nenv - j0 < 256 ? p.nenv - j0 : 256;
-        if ((int)threadIdx.x < nj) {
-            const int jj = threadIdx.x;
-            const int a = p.envl[j0 + jj];
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
-            const uint32_t kk = canon[j0 + jj];
-            s_a[jj] = p.envl[kk];
-            s_R[jj] = p.r_env[kk];
-        }
-        __syncthreads();
-        if (valid)
-            for (int jj = 0; jj < nj; ++jj) {
-                float ex, ey, ez;
-                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
-                const float d2 = vmd_d2(ex, ey, ez);
-                if (!vmd_within_hit(p.w, d2) || !(d2 < q.smax2) || !vmd_sasa_mask_any(m)) continue;
+    vmd_all_pairs<256>(s_r, bx, fx, fy, fz, p.envl, p.nenv, 0, valid, xi, yi, zi,
+        [&](int jj, int pos) { const uint32_t kk = canon[pos]; s_a[jj] = p.envl[kk]; s_R[jj] = p.r_env[kk]; },
+        [&](int jj, int, float ex, float ey, float ez) {
+            const float d2 = vmd_d2(ex, ey, ez);
+            if (vmd_within_hit(p.w, d2) && d2 < q.smax2 && vmd_sasa_mask_any(m))
                 vmd_sasa_neighbour(m, P, s_u, q, s_a[jj], s_R[jj], d2, ex, ey, ez);
-            }
-    }
+            return false;
+        });
     const unsigned n = vmd_sasa_mask_count(m);
     if (LIST) { if (valid) p.counts[t] = n; }
     else vmd_sasa_commit(p.total + b, p.acc + (valid ? t : 0), n, valid ? p.weight[t] : 0u);
@@ -4824,9 +4798,8 @@ struct vmd_contact_atoms_params_t {
     const uint32_t* skip;
 };
 
-// The walk, one lane per entry in list order; its pencil as k_hbond_atoms derives a donor's.  The lane first finds ITSELF in its cell's run
-// of the sorted copy (the slot whose coordinates are its own, bit for bit - vmd_cell_of gives what the build stored): that slot's identity
-// is the entry the lane acts for.  A hit is kept from the lower group's side only; the other lane finds the same pair from its side.
+// The walk, one lane per entry in list order, standing where vmd_walk_lane puts it.  The lane first finds ITSELF in its cell's run of the
+// sorted copy (the first of vmd_own_slots): that slot's identity is the entry the lane acts for.  A hit is kept from the lower group's side only; the other lane finds the same pair from its side.
 // LDS (the measured variant): the block first ORs its hits into LDS - the bit rows of the groups its 256 entries act for are ONE run of
 // pair indices, p0(gmin) .. p0(gmax + 1) - 1 with p0(g) = g (2G - g - 1) / 2, because a hit is kept from the lower group's side - and
 // then flushes the nonzero words with one atomicOr each.  A block whose run does not fit VMD_CONTACT_LDS_WORDS (scattered groups, many
@@ -4850,18 +4823,10 @@ __global__ __launch_bounds__(256) void k_contact_atoms(vmd_contact_atoms_params_
     int py = 0, pz = 0;
     uint32_t gl = 0;
     if (valid) {
-        const uint32_t cell = vmd_cell_of(p.c, b, t, xi, yi, zi);
-        const int pen = (int)(cell / (uint32_t)k.nxf);
-        pz = pen / k.ny; py = pen - pz * k.ny;
+        const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
+        xi = l.x; yi = l.y; zi = l.z; py = l.py; pz = l.pz;
         uint32_t me = (uint32_t)t;
-        const int bxi = __float_as_int(xi), byi = __float_as_int(yi), bzi = __float_as_int(zi);
-        uint32_t s0 = k.csr[cell], s1 = k.csr[cell + 1];
-        if (s1 > n) s1 = n;              // (a table is never trusted beyond the copy it indexes)
-        for (uint32_t s = s0; s < s1; ++s)
-            if (__float_as_int(k.xr[s]) == bxi && __float_as_int(k.yr[s]) == byi && __float_as_int(k.zr[s]) == bzi) {
-                if (id[s] < n) me = id[s];
-                break;
-            }
+        vmd_own_slots(k.csr, k.xr, k.yr, k.zr, n, l.cell, xi, yi, zi, [&](uint32_t s) { if (id[s] < n) me = id[s]; return true; });
         gl = (uint32_t)grp[me];
     }
     uint32_t* row = p.bits + (size_t)b * p.W;
@@ -4882,14 +4847,15 @@ __global__ __launch_bounds__(256) void k_contact_atoms(vmd_contact_atoms_params_
         __syncthreads();
     }
     if (valid)
-        vmd_within_walk_all(k, py, pz, xi, yi, zi, [&](unsigned j, float, float, float) {
+        vmd_within_walk_each(k, py, pz, xi, yi, zi, [&](unsigned j, float, float, float) {
             const uint32_t a = id[j];
-            if (a >= n) return;          // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+            if (a >= n) return false;    // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
             const uint32_t go = (uint32_t)grp[a];
-            if (!(go > gl && go - gl >= min_sep)) return;
+            if (!(go > gl && go - gl >= min_sep)) return false;
             const uint32_t pp = vmd_contact_pair(G, gl, go);
             if (LDS && nw) vmd_contact_set(s_bits, pp - (w0 << 5));
             else vmd_contact_set(row, pp);
+            return false;
         });
     if (LDS) {
         __syncthreads();
@@ -4904,14 +4870,14 @@ struct vmd_contact_brute_params_t {
     const float* xyz; size_t frame_stride; size_t row_stride;
     const float* boxes; uint32_t pbc;
     const int32_t* ent; const int32_t* grp; int nent; uint32_t ngroups, min_sep;
-    const uint32_t* canon;      // k_hbond_canon's table of the list, u32[B][nent]
+    const uint32_t* canon;      // k_canon_entries' table of the list, u32[B][nent]
     vmd_within_test_t w;        // within(r_cut, .)
     uint32_t* bits; uint32_t W; const uint32_t* skip;
 };
 
-// All pairs from the raw frame: one lane per entry, the list staged through an LDS tile of 256 with the group of every entry's canonical
-// entry.  The upper triangle of the entry pairs only: tiles from the block's own onward, in its own tile the entries behind the lane's; the
-// group test (no memory, no arithmetic to speak of) stands in front of the distance.
+// All pairs from the raw frame: one lane per entry over vmd_all_pairs, the list staged with the group of every entry's canonical entry.
+// The upper triangle of the entry pairs only: tiles from the block's own onward, in its own tile the entries behind the lane's; the
+// group test (no memory, no arithmetic to speak of) stands in front of the distance test.
 __global__ __launch_bounds__(256) void k_contact_brute(vmd_contact_brute_params_t p) {
     __shared__ float s_r[3][256];
     __shared__ uint32_t s_g[256];
@@ -4933,25 +4899,14 @@ __global__ __launch_bounds__(256) void k_contact_brute(vmd_contact_brute_params_
     }
     uint32_t* row = p.bits + (size_t)b * p.W;
     const uint32_t G = p.ngroups, min_sep = p.min_sep;
-    for (int j0 = blockIdx.x * 256; j0 < p.nent; j0 += 256) {
-        __syncthreads();
-        const int nj = p.nent - j0 < 256 ? p.nent - j0 : 256;
-        if ((int)threadIdx.x < nj) {
-            const int jj = threadIdx.x;
-            const int a = p.ent[j0 + jj];
-            vmd_pair_coords(bx, fx[a], fy[a], fz[a], s_r[0][jj], s_r[1][jj], s_r[2][jj]);
-            s_g[jj] = (uint32_t)p.grp[canon[j0 + jj]];
-        }
-        __syncthreads();
-        if (valid)
-            for (int jj = j0 == (int)blockIdx.x * 256 ? (int)threadIdx.x + 1 : 0; jj < nj; ++jj) {
-                const uint32_t go = s_g[jj];
-                if ((go > gl ? go - gl : gl - go) < min_sep) continue;
-                float ex, ey, ez;
-                vmd_pair_delta_general(bx, xi, yi, zi, s_r[0][jj], s_r[1][jj], s_r[2][jj], ex, ey, ez);
-                if (vmd_within_hit(p.w, vmd_d2(ex, ey, ez))) vmd_contact_hit(row, G, min_sep, gl, go);
-            }
-    }
+    vmd_all_pairs<256>(s_r, bx, fx, fy, fz, p.ent, p.nent, blockIdx.x * 256, valid, xi, yi, zi,
+        [&](int jj, int pos) { s_g[jj] = (uint32_t)p.grp[canon[pos]]; },
+        [&](int jj, int pos, float ex, float ey, float ez) {
+            if (pos <= t) return false;
+            const uint32_t go = s_g[jj];
+            if ((go > gl ? go - gl : gl - go) >= min_sep && vmd_within_hit(p.w, vmd_d2(ex, ey, ez))) vmd_contact_hit(row, G, min_sep, gl, go);
+            return false;
+        });
 }
 
 // The finish, behind the walk or all pairs over a frame group: three launches under the overflow flag.
@@ -4961,12 +4916,6 @@ struct vmd_contact_finish_params_t {
     unsigned* counts;                           // u32[2 B], zeroed by the launcher: the pairs, the native pairs in contact per frame
     float* out_count; float* out_q; uint64_t* acc; const uint32_t* skip;
 };
-__device__ __forceinline__ void vmd_contact_wave_add(unsigned* dst, unsigned n) {
-    int tot = (int)n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tot += vmd_shfl_xor_i32(tot, o);
-    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(dst, (unsigned)tot);
-}
 // one lane per WORD of the rows, read once per frame, coalesced: the lane counts its 32 pairs at once in 16 bit planes (a carry-save
 // add of the frame's word into c[0 .. 15]: plane k holds bit k of all 32 counts; B <= 65535 frames fit), then adds every nonzero count
 // to its record row.  The 32 rows belong to this lane of this launch alone - a frame group's partial is added to by the launches of one
@@ -5007,12 +4956,12 @@ __global__ __launch_bounds__(256) void k_contact_finish_frames(vmd_contact_finis
         const uint32_t i = blockIdx.x * 256u + threadIdx.x;
         uint32_t v = i < q.W ? row[i] : 0u;
         if (i + 1 == q.W && (q.P & 31u)) v &= (1u << (q.P & 31u)) - 1u;
-        vmd_contact_wave_add(q.counts + b, vmd_popc_u32(v));
+        vmd_wave_add_u32(q.counts + b, vmd_popc_u32(v));
     } else {
         const uint32_t i = (blockIdx.x - wblocks) * 256u + threadIdx.x;
         unsigned n = 0;
         if (i < (uint32_t)q.nnative) { const uint32_t p = q.native[i]; n = (row[p >> 5] >> (p & 31u)) & 1u; }
-        vmd_contact_wave_add(q.counts + q.B + b, n);
+        vmd_wave_add_u32(q.counts + q.B + b, n);
     }
 }
 // the temporal rows - Q = (float)n / (float)nnative, one fp32 division - and the frames row, bumped once per frame
@@ -5387,6 +5336,21 @@ static bool vmd_within_walk_fill(vmd_within_walk_params_t& k, const vmd_grid_t& 
     k.ry = g_pen_ry; k.rz = g_pen_rz;
     return true;
 }
+// ... of a kernel that also asks the copy's identity (k_sorted_atoms' table): every argument of the walk side checked, then the fill
+static bool vmd_ident_walk_fill(vmd_within_walk_params_t& k, const vmd_grid_t& grid, const float* sorted, const uint32_t* cell_start,
+                                const uint32_t* ident, int n, int n_pad, float r, int closed) {
+    return sorted && cell_start && ident && n_pad >= n && grid.ncell == grid.nxf * grid.ny * grid.nz &&
+           vmd_within_walk_fill(k, grid, sorted, cell_start, n_pad, 0.0f, r, closed);
+}
+// The lane side of a walk in list order: the list as a cell build on `grid` would read it - raw frame, the GRID's boxes, pbc, index list
+// (pat.m = 0; no outputs).
+static vmd_cells_params_t vmd_walk_lanes(const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes, uint32_t pbc_flags,
+                                         const int32_t* list, int n, const vmd_grid_t& grid) {
+    vmd_cells_params_t c{};
+    c.xyz = xyz; c.frame_stride = frame_stride; c.row_stride = row_stride; c.boxes = grid_boxes; c.pbc = pbc_flags;
+    c.sel = list; c.nsel = n; c.nsel_pad = n; c.grid = grid;
+    return c;
+}
 
 extern "C" int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride,
                                     const float* boxes, uint32_t pbc_flags, int B, const int32_t* tgt, int ntgt,
@@ -5401,8 +5365,7 @@ extern "C" int vmd_hip_within_atoms(void* stream, const float* xyz, size_t frame
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
     if (ntgt <= 0) return 0;
     if (nref <= 0 || !sorted_ref || !cell_start_ref) return (int)hipErrorInvalidValue;
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
-    p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, boxes, pbc_flags, tgt, ntgt, grid);
     p.mask = mask_out; p.mask_stride = mask_stride; p.count = count_out; p.skip = skip_flag;
     hipLaunchKernelGGL(k_within_atoms, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
@@ -5483,8 +5446,8 @@ extern "C" int vmd_hip_sorted_atoms(void* stream, const float* xyz, size_t frame
         grid.ncell != grid.nxf * grid.ny * grid.nz) return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(ident_out, 0xff, (size_t)B * nsel_pad * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
     vmd_sorted_atoms_params_t p{};
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
-    p.c.sel = sel; p.c.nsel = nsel; p.c.nsel_pad = nsel_pad; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, boxes, pbc_flags, sel, nsel, grid);
+    p.c.nsel_pad = nsel_pad;             // (the copy's rows and the table's are the build's)
     p.cell_start = cell_start; p.sorted = sorted; p.ident = ident_out; p.skip = skip_flag;
     hipLaunchKernelGGL(k_sorted_atoms, dim3((nsel + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
@@ -5504,15 +5467,22 @@ extern "C" int vmd_hip_hbond_atoms(void* stream, const float* xyz, size_t frame_
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     vmd_hbond_atoms_params_t p{};
-    if (!vmd_hbond_args_ok(B, don, hyd, npairs, accl, nacc, r_da, c2, count_out, acc) || !sorted_acc || !cell_start_acc || !ident ||
-        !grid_boxes || !frame_boxes || nacc_pad < nacc || grid.ncell != grid.nxf * grid.ny * grid.nz ||
-        !vmd_within_walk_fill(p.k, grid, sorted_acc, cell_start_acc, nacc_pad, 0.0f, r_da, closed)) return (int)hipErrorInvalidValue;
+    if (!vmd_hbond_args_ok(B, don, hyd, npairs, accl, nacc, r_da, c2, count_out, acc) || !grid_boxes || !frame_boxes ||
+        !vmd_ident_walk_fill(p.k, grid, sorted_acc, cell_start_acc, ident, nacc, nacc_pad, r_da, closed)) return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(count_out, 0, (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
-    p.c.sel = don; p.c.nsel = npairs; p.c.nsel_pad = npairs; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, grid_boxes, pbc_flags, don, npairs, grid);
     p.fboxes = frame_boxes; p.hyd = hyd; p.accl = accl; p.nacc = nacc; p.ident = ident; p.c2 = c2;
     p.count = count_out; p.acc = acc; p.skip = skip_flag;
     hipLaunchKernelGGL(k_hbond_atoms, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// the coincidence table in front of an all-pairs launch over `list`
+static int vmd_canon_launch(hipStream_t s, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                            int B, const int32_t* list, int n, uint32_t* canon, const uint32_t* skip_flag) {
+    vmd_canon_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, list, n, canon, skip_flag};
+    hipLaunchKernelGGL(k_canon_entries, dim3((n + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }
@@ -5522,10 +5492,9 @@ static int vmd_hbond_brute_launch(void* stream, const float* xyz, size_t frame_s
                                   uint32_t* canon, float r_da, float c2, int closed, uint32_t* count_out, uint64_t* acc,
                                   const uint32_t* skip_flag, uint32_t* list, uint32_t list_cap, uint32_t* list_count) {
     hipStream_t s = (hipStream_t)stream;
+    if (const int rc = vmd_canon_launch(s, xyz, frame_stride, row_stride, boxes, pbc_flags, B, accl, nacc, canon, skip_flag)) return rc;
     vmd_hbond_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, don, hyd, npairs, accl, nacc, canon,
                                vmd_make_within_test(0.0f, r_da, closed), c2, count_out, acc, skip_flag, list, list_cap, list_count};
-    hipLaunchKernelGGL(k_hbond_canon, dim3((nacc + 255) / 256, B), dim3(256), 0, s, p);
-    VMD_LAUNCH_CHECK();
     if (list) hipLaunchKernelGGL(k_hbond_brute<true>, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_hbond_brute<false>, dim3((npairs + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();
@@ -5578,11 +5547,10 @@ extern "C" int vmd_hip_sasa_atoms(void* stream, const float* xyz, size_t frame_s
     if (B <= 0) return 0;
     vmd_sasa_atoms_params_t p{};
     if (!vmd_sasa_args_ok(B, meas, nmeas, envl, nenv, r_meas, r_env, rmax_env, points, npoints, r_cut) || !weight || !total_out || !acc ||
-        !sorted_env || !cell_start_env || !ident || !grid_boxes || nenv_pad < nenv || grid.ncell != grid.nxf * grid.ny * grid.nz ||
-        !vmd_within_walk_fill(p.k, grid, sorted_env, cell_start_env, nenv_pad, 0.0f, r_cut, closed)) return (int)hipErrorInvalidValue;
+        !grid_boxes || !vmd_ident_walk_fill(p.k, grid, sorted_env, cell_start_env, ident, nenv, nenv_pad, r_cut, closed))
+        return (int)hipErrorInvalidValue;
     { const hipError_t e = hipMemsetAsync(total_out, 0, (size_t)B * sizeof(uint64_t), s); if (e != hipSuccess) return (int)e; }
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
-    p.c.sel = meas; p.c.nsel = nmeas; p.c.nsel_pad = nmeas; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, grid_boxes, pbc_flags, meas, nmeas, grid);
     p.envl = envl; p.nenv = nenv; p.ident = ident; p.r_meas = r_meas; p.r_env = r_env; p.rmax_env = rmax_env; p.weight = weight;
     p.points = points; p.npoints = npoints; p.total = total_out; p.acc = acc; p.skip = skip_flag;
     const dim3 g((nmeas + 255) / 256, B);
@@ -5598,11 +5566,7 @@ static int vmd_sasa_brute_launch(void* stream, const float* xyz, size_t frame_st
                                  int npoints, float r_cut, int closed, uint64_t* total_out, uint64_t* acc, const uint32_t* skip_flag,
                                  uint32_t* counts) {
     hipStream_t s = (hipStream_t)stream;
-    vmd_hbond_brute_params_t cp{};          // k_hbond_canon reads the frame, the list and the flag of it
-    cp.xyz = xyz; cp.frame_stride = frame_stride; cp.row_stride = row_stride; cp.boxes = boxes; cp.pbc = pbc_flags;
-    cp.accl = envl; cp.nacc = nenv; cp.canon = canon; cp.skip = skip_flag;
-    hipLaunchKernelGGL(k_hbond_canon, dim3((nenv + 255) / 256, B), dim3(256), 0, s, cp);
-    VMD_LAUNCH_CHECK();
+    if (const int rc = vmd_canon_launch(s, xyz, frame_stride, row_stride, boxes, pbc_flags, B, envl, nenv, canon, skip_flag)) return rc;
     vmd_sasa_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, meas, nmeas, envl, nenv, canon, r_meas, r_env, rmax_env,
                               weight, points, npoints, vmd_make_within_test(0.0f, r_cut, closed), total_out, acc, skip_flag, counts};
     if (counts) hipLaunchKernelGGL(k_sasa_brute<true>, dim3((nmeas + 255) / 256, B), dim3(256), 0, s, p);
@@ -5656,13 +5620,11 @@ extern "C" int vmd_hip_contact_atoms(void* stream, const float* xyz, size_t fram
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     vmd_contact_atoms_params_t p{};
-    if (!vmd_contact_args_ok(B, ent, grp, nent, ngroups, min_sep, r_cut, bits) || !sorted || !cell_start || !ident || !grid_boxes ||
-        nent_pad < nent || grid.ncell != grid.nxf * grid.ny * grid.nz ||
-        !vmd_within_walk_fill(p.k, grid, sorted, cell_start, nent_pad, 0.0f, r_cut, closed)) return (int)hipErrorInvalidValue;
+    if (!vmd_contact_args_ok(B, ent, grp, nent, ngroups, min_sep, r_cut, bits) || !grid_boxes ||
+        !vmd_ident_walk_fill(p.k, grid, sorted, cell_start, ident, nent, nent_pad, r_cut, closed)) return (int)hipErrorInvalidValue;
     const uint32_t W = (vmd_contact_pairs(ngroups) + 31u) / 32u;
     { const hipError_t e = hipMemsetAsync(bits, 0, (size_t)B * W * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = grid_boxes; p.c.pbc = pbc_flags;
-    p.c.sel = ent; p.c.nsel = nent; p.c.nsel_pad = nent; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, grid_boxes, pbc_flags, ent, nent, grid);
     p.grp = grp; p.ngroups = (uint32_t)ngroups; p.min_sep = min_sep; p.ident = ident; p.bits = bits; p.W = W; p.skip = skip_flag;
     if (lds_rows) hipLaunchKernelGGL(k_contact_atoms<true>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_contact_atoms<false>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
@@ -5678,11 +5640,7 @@ extern "C" int vmd_hip_contact_brute(void* stream, const float* xyz, size_t fram
     if (!vmd_contact_args_ok(B, ent, grp, nent, ngroups, min_sep, r_cut, bits) || !canon || !boxes) return (int)hipErrorInvalidValue;
     const uint32_t W = (vmd_contact_pairs(ngroups) + 31u) / 32u;
     { const hipError_t e = hipMemsetAsync(bits, 0, (size_t)B * W * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
-    vmd_hbond_brute_params_t cp{};          // k_hbond_canon reads the frame, the list and the flag of it
-    cp.xyz = xyz; cp.frame_stride = frame_stride; cp.row_stride = row_stride; cp.boxes = boxes; cp.pbc = pbc_flags;
-    cp.accl = ent; cp.nacc = nent; cp.canon = canon; cp.skip = skip_flag;
-    hipLaunchKernelGGL(k_hbond_canon, dim3((nent + 255) / 256, B), dim3(256), 0, s, cp);
-    VMD_LAUNCH_CHECK();
+    if (const int rc = vmd_canon_launch(s, xyz, frame_stride, row_stride, boxes, pbc_flags, B, ent, nent, canon, skip_flag)) return rc;
     vmd_contact_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, ent, grp, nent, (uint32_t)ngroups, min_sep, canon,
                                  vmd_make_within_test(0.0f, r_cut, closed), bits, W, skip_flag};
     hipLaunchKernelGGL(k_contact_brute, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
@@ -5724,8 +5682,7 @@ extern "C" int vmd_hip_within_atoms_expr(void* stream, const float* xyz, size_t 
     if (!vmd_expr_term_ok(B, term, live, bits, stride, rmin, rmax) || grid.ncell != grid.nxf * grid.ny * grid.nz || nref <= 0 ||
         !sorted_ref || !cell_start_ref || !vmd_within_walk_fill(p.k, grid, sorted_ref, cell_start_ref, nref_pad, rmin, rmax, closed))
         return (int)hipErrorInvalidValue;
-    p.c.xyz = xyz; p.c.frame_stride = frame_stride; p.c.row_stride = row_stride; p.c.boxes = boxes; p.c.pbc = pbc_flags;
-    p.c.sel = tgt; p.c.nsel = ntgt; p.c.nsel_pad = ntgt; p.c.grid = grid;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, boxes, pbc_flags, tgt, ntgt, grid);
     p.bits = bits; p.stride = stride; p.term = term; p.live = live; p.skip = skip_flag;
     hipLaunchKernelGGL(k_within_atoms_expr, dim3((ntgt + 255) / 256, B), dim3(256), 0, s, p);
     VMD_LAUNCH_CHECK();

@@ -443,41 +443,39 @@ class PropertyDataView:
         assert self.is_map
         return self.counts.reshape(L.RAMA_MAP_DIM, L.RAMA_MAP_DIM, L.RAMA_MAP_CLASSES)
 
+    def _record(self, n):
+        """the n uint64 words of a record, brought up to date from the device first"""
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, n, np.uint64)
+
     @property
     def rmsf_accumulators(self):
         """the record of an rmsf property as uint64 [ntot + 1, 4]: per entry of the set the two's-complement sums of
         q(d_x), q(d_y), q(d_z) and the sum of q2(|d|^2); the last row's first word is the number of frames accumulated"""
         assert self.c.dim[1] == 4 and self.c.dim[2] == 0, "not an rmsf record"
-        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
-            raise VmdError(self._ev.lib.last_error())
-        return self._arr(self.c.counts, self.c.dim[0] * 4, np.uint64).reshape(self.c.dim[0], 4)
+        return self._record(self.c.dim[0] * 4).reshape(self.c.dim[0], 4)
 
     @property
     def hbond_accumulators(self):
         """the record of a hydrogen-bond occupancy as uint64 [npairs + nacc + 1]: the bonds every pair donated, the bonds
         every acceptor accepted, the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a hydrogen-bond occupancy record"
-        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
-            raise VmdError(self._ev.lib.last_error())
-        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
+        return self._record(self.c.dim[0])
 
     @property
     def sasa_accumulators(self):
         """the record of a sasa statement as uint64 [nmeas + 1]: the accessible points of every measured entry summed over
         the evaluated frames, the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not a record of accessible surface points"
-        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
-            raise VmdError(self._ev.lib.last_error())
-        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
+        return self._record(self.c.dim[0])
 
     @property
     def contact_accumulators(self):
         """the record of a contact map as uint64 [P + 1]: per group pair, in condensed order, the evaluated frames in which
         it was in contact, then the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not the record of a contact map"
-        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
-            raise VmdError(self._ev.lib.last_error())
-        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
+        return self._record(self.c.dim[0])
 
     @property
     def ss_classes(self):
