@@ -405,6 +405,24 @@ typedef struct vmd_contact_sites_t {
     size_t nnative;  const int32_t (*native)[2];                   /* group pairs of the reference set; may be 0 / NULL */
 } vmd_contact_sites_t;
 bool vmd_ir_add_contacts(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut, uint32_t min_sep);
+/* Connected clusters of groups per frame: sizes and labels (an entry point, no script syntax).  sites: the struct of
+ * vmd_ir_add_contacts - nentries list entries, entry i = an atom and the group it stands for, 0 <= group < ngroups - with nnative == 0.
+ * Groups g != h are BONDED in a frame iff some entry of g and some entry of h pass the distance test of vmd_ir_add_contacts, word for word:
+ * wrapped positions, the SPEC S3 / S3t image, r_min = 0, spec_within_closed acting on it as on a shell.  There is no min_sep.  The clusters
+ * of a frame are the connected components of that graph over all ngroups groups; a group bonded to none is a cluster of size 1.  The size
+ * of a cluster is its number of groups, its label its lowest group index.  Coincident entries need no rule (D-CL-GEOMETRIC): they stand at
+ * distance 0, so their groups are bonded, and the components are the purely geometric ones.
+ * names[0]: TEMPORAL, dim = {num_frames, 1}, no unit: the clusters in the frame (follows the frame mask like a within count).
+ * names[1]: MAP (VMD_PROPERTY_FLAG_MAP) of u64 accumulators, dim = {ngroups + 1, 1}: row s - 1 the clusters of s groups summed over the
+ * evaluated frames, the last row the frames accumulated; sum over s of s * row[s - 1] = ngroups * frames.  Integer counts: the record is
+ * the same bit for bit however calls, batches, frame blocks and ranks arrive, and merges like every MAP (at most ngroups per frame on a
+ * row); a frame evaluated twice without vmd_eval_clear_data counts twice.
+ * names[2]: TEMPORAL, no unit: the size of the largest cluster in the frame.
+ * Errors (vmd_last_error): NULL arguments, nentries == 0, ngroups outside [1, VMD_CLUSTER_MAX_GROUPS], a negative atom, a group outside
+ * [0, ngroups), a group without an entry (a cluster of nothing has no size), nnative != 0, r_cut not finite or <= 0, names already
+ * defined or equal to each other.  vmd_ir_geometry_atoms: the entries' atoms. */
+#define VMD_CLUSTER_MAX_GROUPS (1u << 24)      /* every count a float carries stays exact */
+bool vmd_ir_add_clusters(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
@@ -672,6 +690,18 @@ bool vmd_eval_contacts(vmd_script_eval_t* eval, const char* name, double* occupa
 #define VMD_CONTACT_PAIRS_FAILED ((size_t)-1)
 size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
                               int32_t (*out)[2], size_t cap);
+
+/* The cluster sizes of a vmd_ir_add_clusters statement (any of its names) read from the record as it stands - partially
+ * evaluated or merged alike: mean_count double[G], entry s - 1 = the clusters of s groups per frame, row / frames; frames: the count; each
+ * may be NULL.  F == 0 answers zeros.  false + vmd_last_error: an unknown property, a property of another form. */
+bool vmd_eval_cluster_sizes(vmd_script_eval_t* eval, const char* name, double* mean_count, uint64_t* frames);
+/* The labels of ONE frame, on demand (any name of the statement), under vmd_eval_hbond_pairs' contract: nothing accumulated is touched, it
+ * may be called while pool threads are inside vmd_eval_frame_range.  All pairs from the raw frame.  labels: uint32[G], labels[g] = the
+ * lowest group of g's cluster (labels[g] <= g) - what a host colours atoms by.  Returns the number of clusters;
+ * VMD_CLUSTER_LABELS_FAILED + vmd_last_error on failure. */
+#define VMD_CLUSTER_LABELS_FAILED ((size_t)-1)
+size_t vmd_eval_cluster_labels(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                               uint32_t* labels);
 
 /* ---- export, viamd_amd/csrc/vmd_export.cpp: the files VIAMD writes from evaluated properties ---------------------
  * export_xvg / export_csv (src/main.cpp:5640-5716): columns[j][i], one label per column */

@@ -24,6 +24,7 @@
  *   vmd_hip_within_atoms_expr, vmd_hip_within_brute_expr, vmd_hip_shell_expr_finish  <- and / or / not over within() shells
  *   vmd_hip_sorted_atoms, vmd_hip_hbond_*  <- hydrogen bonds
  *   vmd_hip_contact_*  <- residue contact maps
+ *   vmd_hip_cluster_*  <- connected clusters of groups
  *   vmd_hip_sasa_*  <- solvent-accessible surface area
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
@@ -398,6 +399,31 @@ int vmd_hip_contact_brute(void* stream, const float* xyz, size_t frame_stride, s
                           float r_cut, int closed, uint32_t* bits, const uint32_t* skip_flag);
 int vmd_hip_contact_finish(void* stream, const uint32_t* bits, int B, int ngroups, const uint32_t* native, int nnative, uint32_t* counts,
                            float* out_count, float* out_q, uint64_t* acc, const uint32_t* skip_flag);
+
+/* K15: connected clusters of groups, DESIGN 1.17.  The list `ent` (nent atoms) with `grp` (the group of every entry, 0 <= grp < ngroups,
+ * every group named) is walked against ITSELF.  Groups g != h are bonded in frame b when an entry of g and an entry of h stand at
+ * 0 <= d < r_cut (closed != 0: <= r_cut; the pair distance of K6); the clusters are the connected components over all ngroups groups
+ * (D-CL-GEOMETRIC: the lane's group from the list, a hit's through the identity table; the components are the same).  parent: u32[B][ngroups],
+ * a lock-free union-find preset by the call to parent[g] = g; a root is hooked under a lower root only, so a component's final root is its
+ * lowest group.  Nothing happens when *skip_flag != 0.  B <= 65535, 1 <= ngroups <= 2^24.
+ *   vmd_hip_cluster_atoms   the cell walk of K8 over the cell-sorted copy of the list, one lane per entry, every hit of another group a
+ *                           union.  ident: vmd_hip_sorted_atoms' table of the copy.  skip_same != 0: a lane skips the hits that repeat the
+ *                           group it joined last (the same components)
+ *   vmd_hip_cluster_brute   all pairs from the raw frame (any cell, any cutoff), the upper triangle of the entry pairs
+ *   vmd_hip_cluster_finish  parent -> results: root[b][g] = the label of group g (its cluster's lowest group), size[b][r] = the groups
+ *                           under root r (root, size: u32[B][ngroups]); acc[s - 1] += the clusters of s groups over the B frames,
+ *                           acc[ngroups] += B (acc u64[ngroups + 1]); out_count[b] = (float)clusters, out_largest[b] = (float)largest size.
+ *                           acc, out_count, out_largest may each be NULL.  counts: scratch u32[2 B].  wave_singles != 0: the clusters of
+ *                           one group go to acc[0] as one add per wave (the same record) */
+int vmd_hip_cluster_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes, uint32_t pbc_flags,
+                          int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, const float* sorted,
+                          const uint32_t* cell_start, int nent_pad, const uint32_t* ident, vmd_grid_t grid, float r_cut, int closed,
+                          int skip_same, uint32_t* parent, const uint32_t* skip_flag);
+int vmd_hip_cluster_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags,
+                          int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, float r_cut, int closed, uint32_t* parent,
+                          const uint32_t* skip_flag);
+int vmd_hip_cluster_finish(void* stream, const uint32_t* parent, uint32_t* root, uint32_t* size, int B, int ngroups, uint32_t* counts,
+                           float* out_count, float* out_largest, uint64_t* acc, int wave_singles, const uint32_t* skip_flag);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

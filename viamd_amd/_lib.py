@@ -213,6 +213,9 @@ SIGNATURES = [
     ("vmd_eval_contacts", C.c_bool, [_vp, C.c_char_p, c_double_p, c_uint64_p]),
     ("vmd_eval_contact_pairs", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, c_int32_p, C.c_size_t]),
     ("vmd_topology_contact_sites", _vp, [C.POINTER(TopologyC), C.c_bool]),
+    ("vmd_ir_add_clusters", C.c_bool, [_vp, C.POINTER(C.c_char_p), C.POINTER(ContactSitesC), C.c_float]),
+    ("vmd_eval_cluster_sizes", C.c_bool, [_vp, C.c_char_p, c_double_p, c_uint64_p]),
+    ("vmd_eval_cluster_labels", C.c_size_t, [_vp, C.c_char_p, C.POINTER(System), C.POINTER(TrajectoryI), C.c_uint32, C.POINTER(C.c_uint32)]),
     ("vmd_contact_sites_view", C.POINTER(ContactSitesC), [_vp]),
     ("vmd_contact_sites_free", None, [_vp]),
     ("vmd_ir_add_within_count", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t, c_int32_p, C.c_size_t, C.c_float, C.c_float]),
@@ -441,6 +444,11 @@ SIGNATURES = [
     ("vmd_hip_contact_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_uint32,
                                         _vp, C.c_float, C.c_int, _vp, _vp]),
     ("vmd_hip_contact_finish", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("vmd_hip_cluster_atoms", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp,
+                                        C.c_int, _vp, Grid, C.c_float, C.c_int, C.c_int, _vp, _vp]),
+    ("vmd_hip_cluster_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
+                                        C.c_int, _vp, _vp]),
+    ("vmd_hip_cluster_finish", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

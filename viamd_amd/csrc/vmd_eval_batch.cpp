@@ -136,6 +136,11 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
         used[e->props[pi]->sel_b] = 1;
         per_frame += 4 * (e->sels[e->props[pi]->sel_b]->idx.size() + 64) + (G * (G - 1) / 2 + 31) / 32 * 4 + 8;
     }
+    // clusters: the entry list sorted and identified, and the frame's rows of the union-find - parent, root, size - and counts
+    for (int pi : e->cluster_props) {
+        used[e->props[pi]->sel_b] = 1;
+        per_frame += 4 * (e->sels[e->props[pi]->sel_b]->idx.size() + 64) + 12 * e->props[pi]->prop.K + 8;
+    }
     for (auto& g : e->rdf_groups)
         for (int pi : g.shell_props) for (int sl : {e->props[pi]->sel_a, e->props[pi]->sel_b}) if (sl >= 0) used[sl] = 1;
     // a shell keeps a hit copy the size of its parent's sorted rows, one byte per entry and its tables
@@ -160,7 +165,7 @@ size_t auto_batch(const vmd_script_eval_t* e, size_t num_atoms, bool staged) {
     // without them stream whole frames at HBM speed and take much larger batches, so that launches, the alignment kernel's
     // latency and the per-batch synchronisation stay small against the stream (grid.y = frames of the batch <= 65535)
     const size_t cap = (e->rdf_groups.empty() && e->within_props.empty() && e->shell_sdf_props.empty() && e->exprs.empty() &&
-                        e->hbond_props.empty() && e->sasa_props.empty() && e->contact_props.empty()) ? 16384 : 1024;
+                        e->hbond_props.empty() && e->sasa_props.empty() && e->contact_props.empty() && e->cluster_props.empty()) ? 16384 : 1024;
     B = std::max<size_t>(1, std::min<size_t>(B, cap));
     return B;
 }

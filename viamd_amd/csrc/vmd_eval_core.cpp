@@ -217,15 +217,15 @@ void build_within_plan(vmd_script_eval_t* e) {
     }
 }
 
-// The neighbour analyses - hydrogen bonds, accessible area (1.15), contact maps (1.16): the side that is cell-sorted (the
+// The neighbour analyses - hydrogen bonds, accessible area (1.15), contact maps (1.16), clusters (1.17): the side that is cell-sorted (the
 // acceptors, the environment, the entry list) becomes an interned selection - shared with everything else of the script, so that a
 // cell-sorted copy another pass built on the same grid in a batch is not built again.  The side in the lanes (the donors, the measured
-// entries) is walked in list order and is never sorted: its selection only says how many lanes the grid is chosen for.  Contacts have ONE
+// entries) is walked in list order and is never sorted: its selection only says how many lanes the grid is chosen for.  Contacts and clusters have ONE
 // list, on both sides: its cell-sorted copy is what its own entries walk.
 void build_neighbour_plan(vmd_script_eval_t* e) {
     const struct { Form count; std::vector<int> vmd_script_eval_t::* props; bool one_list; } kinds[] = {
         {Form::HBOND_COUNT, &vmd_script_eval_t::hbond_props, false}, {Form::SASA_AREA, &vmd_script_eval_t::sasa_props, false},
-        {Form::CONTACT_COUNT, &vmd_script_eval_t::contact_props, true}};
+        {Form::CONTACT_COUNT, &vmd_script_eval_t::contact_props, true}, {Form::CLUSTER_COUNT, &vmd_script_eval_t::cluster_props, true}};
     for (auto& k : kinds) {
         (e->*k.props).clear();
         for (size_t i = 0; i < e->props.size(); ++i) {
@@ -374,8 +374,14 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
         case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
         case Form::DISTANCE: st->dist_per = p.distance_kind == VMD_DISTANCE_PAIR ? (size_t)p.aoff[1] * (size_t)p.boff[1] : 1; break;
         case Form::ANGLE: case Form::DIHEDRAL: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::SASA_AREA:
-        case Form::CONTACT_COUNT: break;
+        case Form::CONTACT_COUNT: case Form::CLUSTER_COUNT: break;
         case Form::CONTACT_NATIVE: st->dist_P = 1; break;       // one fraction per frame (the descriptor carries no set)
+        case Form::CLUSTER_LARGEST: st->dist_P = 1; break;      // one size per frame (likewise)
+        case Form::CLUSTER_SIZES:
+            // one u64 word per cluster size 1 .. G and the frame count; the float view is the words as numbers
+            pinned_views(p.K + 1);
+            st->data.dim[0] = (int32_t)(p.K + 1); st->data.dim[1] = 1; st->data.dim[2] = st->data.dim[3] = 0;
+            break;
         case Form::CONTACT_OCC:
             // one u64 word per group pair and the frame count (16 MB at 2048 groups); the float view is the words as numbers
             pinned_views(p.K + 1);
@@ -823,7 +829,9 @@ extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t
                 // (a donor row at most one count per acceptor and frame, an acceptor row one per pair)
                 // (a row at most npoints per frame)
                 // (a pair is in contact in a frame or it is not)
+                // (a frame has at most G clusters, of whatever size)
                 const long double per_frame = p->prop.form == Form::CONTACT_OCC ? 1.0L
+                        : p->prop.form == Form::CLUSTER_SIZES ? (long double)p->prop.K
                         : p->prop.form == Form::SASA_OCC ? (long double)p->prop.m
                         : p->prop.form == Form::HBOND_OCC ? (long double)std::max(p->prop.K, p->prop.m)
                         : (long double)p->prop.K * (p->prop.form == Form::SDF ? (long double)p->prop.b.size() : 1.0L);
@@ -1164,6 +1172,62 @@ extern "C" size_t vmd_eval_contact_pairs(vmd_script_eval_t* eval, const char* na
     return found;
 }
 
+// ---- clusters.  Any name of the statement names it: -> the index of its count, or props.size() + vmd_last_error
+static size_t cluster_statement(vmd_script_eval_t* e, const char* name) {
+    const size_t pi = count_statement(e, name, Form::CLUSTER_COUNT, {Form::CLUSTER_SIZES, Form::CLUSTER_LARGEST}, "a clusters");
+    if (pi == e->props.size() || (pi + 1 < e->props.size() && e->props[pi + 1]->prop.form == Form::CLUSTER_SIZES)) return pi;
+    vmd_fail("'%s' is not a clusters property", name);
+    return e->props.size();
+}
+
+// the clusters of s groups per frame, row / frames, read from the record as it stands - a partial evaluation, a merged one; under the
+// eval's mutex, touching nothing it keeps
+extern "C" bool vmd_eval_cluster_sizes(vmd_script_eval_t* eval, const char* name, double* mean_count, uint64_t* frames) {
+    if (!eval || !name) return vmd_fail("vmd_eval_cluster_sizes: NULL argument");
+    const size_t pi = cluster_statement(eval, name);
+    if (pi == eval->props.size()) return false;
+    if (!mean_count && !frames) return true;       // (asked for the form alone)
+    PropState* p = eval->props[pi + 1].get();
+    const size_t G = p->prop.K;
+    std::vector<uint64_t> acc;
+    if (!read_record(eval, p, &acc)) return false;
+    if (frames) *frames = acc[G];
+    rows_over_frames(acc.data(), G, acc[G], mean_count);
+    return true;
+}
+
+// The labels of one frame.  One frame on demand, as vmd_eval_hbond_pairs: all pairs from the raw frame into a union-find of its own, the
+// roots read back.  Nothing the evaluation keeps is touched: parent, root, size and the two counts live in one buffer of the eval that
+// only this call uses (kept between calls).
+extern "C" size_t vmd_eval_cluster_labels(vmd_script_eval_t* eval, const char* name, const vmd_system_t* sys, vmd_trajectory_i* traj, uint32_t frame,
+                                          uint32_t* labels) {
+    const size_t failed = VMD_CLUSTER_LABELS_FAILED;
+    if (!eval || !traj || !name || !labels) { vmd_fail("vmd_eval_cluster_labels: NULL argument"); return failed; }
+    vmd_script_eval_t* e = eval;
+    const size_t pi = cluster_statement(e, name);
+    if (pi == e->props.size()) return failed;
+    PropState* p = e->props[pi].get();
+    const Property& d = p->prop;
+    const size_t nent = d.a.size(), G = d.K;
+    uint32_t counts[2] = {0, 0};
+    auto run = [&](const BatchSrc& src) -> bool {
+        if (!e->d_one_clusters.ensure(3 * G + 2)) return false;
+        uint32_t* parent = e->d_one_clusters.p;
+        uint32_t* root = parent + G;
+        uint32_t* size = root + G;
+        uint32_t* dc = size + G;
+        KRN_OK(vmd_hip_cluster_brute(e->stream, src.base, 0, src.row_stride, e->stages[0].d_boxes.p, batch_pbc(e->stages[0]), 1, p->d_a.p,
+                p->d_c.p, (int)nent, (int)G, d.rmax, e->spec.within_closed ? 1 : 0, parent, nullptr));
+        KRN_OK(vmd_hip_cluster_finish(e->stream, parent, root, size, 1, (int)G, dc, nullptr, nullptr, nullptr, 0, nullptr));
+        HIP_OK(hipMemcpyAsync(labels, root, G * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipMemcpyAsync(counts, dc, sizeof(counts), hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        return true;
+    };
+    if (!on_one_frame(e, "vmd_eval_cluster_labels", sys, traj, frame, run)) return failed;
+    return counts[0];
+}
+
 // ---- the hot call -----------------------------------------------------------------------------------------------
 bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_atoms) {
     for (auto& s : e->sels) {
@@ -1181,7 +1245,12 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
         std::vector<float> tmp;
         switch (d.form) {
         case Form::RDF: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC: case Form::CONTACT_OCC:
-        case Form::CONTACT_NATIVE: break;      // the sets of an rdf are interned selections; a map, the populations, an occupancy and a native fraction have none
+        case Form::CONTACT_NATIVE: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST:
+            break;      // the sets of an rdf are interned selections; a map, the populations, an occupancy, a native fraction and the companions of a cluster count have none
+        case Form::CLUSTER_COUNT:
+            // the entries' atoms and groups in list order (the atoms are an interned selection as well)
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream) || !p->d_c.upload(d.ct_group.data(), d.ct_group.size(), e->stream)) return false;
+            break;
         case Form::CONTACT_COUNT: {
             // the entries' atoms and groups in list order (the atoms are an interned selection as well), the native pairs as
             // condensed indices

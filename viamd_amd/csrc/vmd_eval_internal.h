@@ -184,6 +184,13 @@ struct Options {
     // contact maps: 1 = the walk ORs a block's hits into LDS bit rows first and flushes the nonzero words; 0 = every hit goes
     // to the global bit matrix behind a plain load (the A/B of the measurement, DESIGN 1.16: the variant is faster; the bits are identical)
     std::atomic<int> contact_lds_rows{1};
+    // clusters: 1 = a lane of the walk keeps the last group it joined and the root that union left, and skips the hits that
+    // repeat the group; 0 = every hit of another group goes through the union from the lane's own group (the A/B of the measurement,
+    // the variant is slower where it matters, so it is off; the components are identical)
+    std::atomic<int> cluster_skip_same{0};
+    // 1 = the finish sums the clusters of one group over the wave into one add to row 0 of the record; 0 = one add per cluster (the A/B of
+    // the measurement, DESIGN 1.17: the refinement is faster and is kept; the record is identical)
+    std::atomic<int> cluster_wave_singles{1};
     // secondary structure: bytes of bit matrices a batch may hold (frames x nseg^2 / 2); a larger batch runs in sub-batches
     // of frames, never below one frame.  256 MiB: the 1 000 frames x 500 segments of DESIGN 1.10's system take 128 MB in one go
     std::atomic<int> ss_scratch_bytes{256 << 20};
@@ -409,6 +416,11 @@ enum class Form : int {
     // the map behind it (K = P, the group pairs) is a MAP-class record of u64 accumulators, [P + 1], that the count's launch adds to; the
     // native fraction behind that (K = the native pairs), where there are natives, has one value per frame, written by the count's launch
     CONTACT_COUNT, CONTACT_OCC, CONTACT_NATIVE,
+    // `{count, sizes, largest} = clusters(sites, r_cut)`: three descriptors in a row.  The count - a = the entries' atoms,
+    // ct_group = their groups, K = the groups, rmax = r_cut - has one value per frame, the connected components of the frame's bond graph;
+    // the sizes behind it (K = the groups) are a MAP-class record of u64 accumulators, [K + 1], that the count's launch adds to; the largest
+    // behind that has one value per frame, written by the count's launch
+    CLUSTER_COUNT, CLUSTER_SIZES, CLUSTER_LARGEST,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -446,8 +458,11 @@ constexpr FormFacts kFormFacts[] = {
     /* CONTACT_COUNT  */ {ResultClass::TEMPORAL,  0, "contacts",      {"", ""},         nullptr, true,  18},    // counts, a fraction
     /* CONTACT_OCC    */ {ResultClass::MAP,       0, "contacts",      {"", ""},         nullptr, true,  19},
     /* CONTACT_NATIVE */ {ResultClass::TEMPORAL,  0, "contacts",      {"", ""},         nullptr, true,  20},
+    /* CLUSTER_COUNT   */ {ResultClass::TEMPORAL, 0, "clusters",      {"", ""},         nullptr, true,  21},    // counts
+    /* CLUSTER_SIZES   */ {ResultClass::MAP,      0, "clusters",      {"", ""},         nullptr, true,  22},
+    /* CLUSTER_LARGEST */ {ResultClass::TEMPORAL, 0, "clusters",      {"", ""},         nullptr, true,  23},
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::CONTACT_NATIVE + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::CLUSTER_LARGEST + 1, "one row of kFormFacts per Form");
 static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES && VMD_SASA_MAX_POINTS == VMD_SASA_POINTS_MAX,
               "the kernels' limits are the interface's");
 
@@ -664,6 +679,11 @@ struct PropState {
     // and the native fraction's rows (they travel as the rows of the CONTACT_NATIVE property behind the map)
     DevBuf<uint32_t> d_ct_native, d_ct_bits, d_ct_count;
     DevBuf<float> d_ct_q;
+    // clusters, the count: sel_a == sel_b, the interned entry list; d_a the entries' atoms, d_c their groups; the identity
+    // table goes to d_hb_ident; the batch's union-find u32[nb][G] each - parent, root (the labels), size -, its counts u32[2 nb] (clusters,
+    // largest), and the largest's rows (they travel as the rows of the CLUSTER_LARGEST property behind the record)
+    DevBuf<uint32_t> d_cl_parent, d_cl_root, d_cl_size, d_cl_count;
+    DevBuf<float> d_cl_largest;
     // within: sel_a / sel_b are the interned target (T, or T minus R under spec_within_exclude_ref) and reference selections;
     // the per-frame hit counts of the batch; within_empty: T minus R is empty, the property is 0 in every frame
     DevBuf<uint32_t> d_within_count;
@@ -896,6 +916,8 @@ struct vmd_script_eval_t {
     std::vector<int> sasa_props;                        // indices into props of the accessible areas: behind the cell builds too
     DevBuf<uint32_t> d_one_contacts;                    // vmd_eval_contact_pairs: one frame's canonical entries and its row of bits
     std::vector<int> contact_props;                     // indices into props of the contact counts: behind the cell builds too
+    DevBuf<uint32_t> d_one_clusters;                    // vmd_eval_cluster_labels: one frame's parent, root and size rows and its two counts
+    std::vector<int> cluster_props;                     // indices into props of the cluster counts: behind the cell builds too
     std::vector<int> hbond_props;                       // indices into props of the hydrogen-bond counts: behind the cell builds too
     std::vector<int> within_props;                      // indices into props of the within counts: they share the cell builds
     // [passes of the batch][bins]: scratch histogram of every pair pass, committed at the batch's end
@@ -1112,7 +1134,7 @@ struct PairSide { const float* sorted; const uint32_t* cell_start; int n, npad; 
 // a scratch row of launch_rdf and the accumulator it is added to behind the overflow flag
 struct RdfCommit { uint64_t* dst; const uint64_t* src; uint64_t mult; };
 
-struct NeighbourKind;       // vmd_eval_launch.cpp: what hydrogen bonds, accessible area and contact maps each contribute to one route
+struct NeighbourKind;       // vmd_eval_launch.cpp: what hydrogen bonds, accessible area, contact maps and clusters each contribute to one route
 
 struct RangeRun {
     vmd_script_eval_t* e = nullptr;
@@ -1135,7 +1157,7 @@ struct RangeRun {
     bool forked = false;                // pair_stream holds launches the eval's stream has not waited for
     size_t row = 0;                     // next scratch row of d_pass
     std::vector<RdfCommit> commits;
-    std::vector<int> neighbour_route[3];   // build_neighbour_cells' answer per statement of a kind (NeighbourKind::slot): 1 the walk, 0 all pairs
+    std::vector<int> neighbour_route[4];   // build_neighbour_cells' answer per statement of a kind (NeighbourKind::slot): 1 the walk, 0 all pairs
 
     RawSlot* slot_of(size_t bi) const { return raw_ring ? &e->raw_slots[bi % vmd_script_eval_t::kRawSlots] : nullptr; }
     Stage& stage_of(size_t bi) const { return e->stages[bi % (stage_ahead + 1)]; }

@@ -54,6 +54,8 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         case Form::SASA_OCC: break;                                          // added to by its area's launch
         case Form::CONTACT_COUNT: w += 4 * (uint64_t)p.a.size(); break;      // 1.14's rule for a list against itself - a query per entry, the list sorted and identified
         case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: break;            // written by their count's launch
+        case Form::CLUSTER_COUNT: w += 4 * (uint64_t)p.a.size(); break;      // 1.16's rule
+        case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: break;         // written by their count's launch
         }
     }
     return w;
@@ -549,6 +551,38 @@ extern "C" bool vmd_ir_add_contacts(vmd_script_ir_t* ir, const char* const names
     return commit(ir, tp, nnames);
 }
 
+// `{count, sizes, largest} = clusters(sites, r_cut)`: the clusters per frame, the record of their sizes and the largest
+// cluster per frame - three descriptors in a row
+extern "C" bool vmd_ir_add_clusters(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!names || !sites) return vmd_fail("clusters needs its property names and the sites");
+    if (!names[0] || !names[1] || !names[2]) return vmd_fail("clusters needs three property names");
+    if (!names_ok(ir, names, 3)) return false;
+    if (sites->nentries == 0 || !sites->atom || !sites->group) return vmd_fail("clusters entry list is empty");
+    if (!idx_ok(sites->atom, sites->nentries, "clusters entry list")) return false;
+    if (sites->nentries > kMaxSet) return vmd_fail("clusters set too large");
+    if (sites->ngroups < 1 || sites->ngroups > VMD_CLUSTER_MAX_GROUPS) return vmd_fail("clusters group count must lie in [1, %u]", VMD_CLUSTER_MAX_GROUPS);
+    if (sites->nnative != 0) return vmd_fail("clusters takes no native list (nnative must be 0)");
+    const int64_t G = (int64_t)sites->ngroups;
+    std::vector<uint8_t> named((size_t)G, 0);
+    for (size_t i = 0; i < sites->nentries; ++i) {
+        if (sites->group[i] < 0 || sites->group[i] >= G) return vmd_fail("clusters entry %zu names group %d outside [0, %zu)", i, sites->group[i], sites->ngroups);
+        named[(size_t)sites->group[i]] = 1;
+    }
+    for (size_t g = 0; g < (size_t)G; ++g)
+        if (!named[g]) return vmd_fail("clusters group %zu has no entry (a cluster of nothing has no size)", g);
+    if (!std::isfinite(r_cut) || !(r_cut > 0.0f)) return vmd_fail("clusters cutoff must be finite and positive");
+    Property t = make_property(Form::CLUSTER_COUNT, names[0]);
+    t.a.assign(sites->atom, sites->atom + sites->nentries);
+    t.ct_group.assign(sites->group, sites->group + sites->nentries);
+    t.aoff = {0, (int32_t)sites->nentries};
+    t.rmin = 0.0f; t.rmax = r_cut;
+    t.K = sites->ngroups;
+    Property tp[3] = {std::move(t), make_property(Form::CLUSTER_SIZES, names[1]), make_property(Form::CLUSTER_LARGEST, names[2])};
+    tp[1].K = sites->ngroups;
+    return commit(ir, tp, 3);
+}
+
 // what vmd_ir_geometry_atoms has counted and written so far
 struct AtomSink {
     int32_t* out; size_t cap, n = 0;
@@ -572,9 +606,9 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         size_t c0 = 0, c1 = 0;
         switch (p.form) {
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC:
-        case Form::CONTACT_OCC: case Form::CONTACT_NATIVE:
+        case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST:
             return 0;
-        case Form::CONTACT_COUNT:   // the entries' atoms (one context)
+        case Form::CONTACT_COUNT: case Form::CLUSTER_COUNT:   // the entries' atoms (one context)
             if (context > 0) return 0;
             s.put(p.a);
             return s.n;
@@ -648,7 +682,10 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::RMSD: case Form::WITHIN:
         case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: case Form::HBOND_OCC: break;
         case Form::HBOND_COUNT: h = fnv1a(h, &p.hb_angle, sizeof(float)); break;      // (the hydrogens are c, hashed above)
-        case Form::SASA_OCC: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: break;
+        case Form::SASA_OCC: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: break;
+        case Form::CLUSTER_COUNT:                                       // (the atoms are a, r_cut is rmax, the groups' number K; one group per entry of a)
+            h = fnv1a(h, p.ct_group.data(), p.ct_group.size() * sizeof(int32_t));
+            break;
         case Form::CONTACT_COUNT:                                       // (the atoms are a, r_cut is rmax, the groups' number K; one group per entry of a, the rest is the native list)
             h = fnv1a(h, &p.ct_min_sep, sizeof(uint32_t)); h = fnv1a(h, p.ct_group.data(), p.ct_group.size() * sizeof(int32_t));
             h = fnv1a(h, p.ct_native.data(), p.ct_native.size() * sizeof(int32_t));

@@ -336,7 +336,7 @@ bool RangeRun::launch_shell_sdfs(BatchCtx& c) {
     return true;
 }
 
-// ---- the neighbour analyses: hydrogen bonds, accessible area (1.15), contact maps (1.16).  Each statement adds to a record
+// ---- the neighbour analyses: hydrogen bonds, accessible area (1.15), contact maps (1.16), clusters (1.17).  Each statement adds to a record
 // with atomics (or sets bits of one), so like a masked scatter it has to be all or nothing: its launches stand behind the LAST cell build
 // of the batch, where the overflow flag is final, and test it.  First every statement's cell build (build_neighbour_cells), then, kind by
 // kind and statement by statement, the identity of the sorted copy and the walk - per sub, so that a frame block's part lands in its own
@@ -479,13 +479,46 @@ static const NeighbourKind kContacts = {
     },
     [](RangeRun& r, BatchCtx& c, int pi, PropState* p) { return !contact_nnative(p->prop) || r.queue_temporal_rows(c, pi + 2, p->d_ct_q.p); }};
 
-// Every statement's cell build, of all three kinds, as ONE step in front of the first accumulation: no cell build of the batch may stand
+// (clusters, DESIGN 1.17: every sub has its own rows of the batch's union-find - parent preset by the walk's and all pairs' launch, size
+// and the counts zeroed by the finish's, so also in a repeated batch; the largest cluster stands as a third property behind the record)
+static const NeighbourKind kClusters = {
+    3, &vmd_script_eval_t::cluster_props, "cluster_atoms", "cluster_brute", "cluster_finish",
+    [](vmd_script_eval_t* e, int pi) {
+        PropState* m = record_behind(e, pi, Form::CLUSTER_SIZES, "cluster count '%s' has lost its record");
+        if (m && !((size_t)pi + 2 < e->props.size() && e->props[pi + 2]->prop.form == Form::CLUSTER_LARGEST)) {
+            vmd_fail("cluster count '%s' has lost its largest cluster", e->props[pi]->prop.name.c_str());
+            return (PropState*)nullptr;
+        }
+        return m;
+    },
+    [](PropState* p, size_t nb) {
+        const size_t G = p->prop.K;
+        return p->d_out.ensure(nb) && p->d_cl_largest.ensure(nb) && p->d_cl_count.ensure(2 * nb) && p->d_cl_parent.ensure(nb * G) &&
+               p->d_cl_root.ensure(nb * G) && p->d_cl_size.ensure(nb * G);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_cluster_atoms(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.gboxes, x.pbc, (int)x.su.nb, x.p->d_a.p, x.p->d_c.p,
+                (int)x.d.a.size(), (int)x.d.K, x.sorted, x.cell_start, x.npad, x.ident, x.grid, x.d.rmax, x.closed,
+                g_opt.cluster_skip_same.load(), x.p->d_cl_parent.p + x.su.off * x.d.K, x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_cluster_brute(x.s, x.xyz, x.st.frame_stride, x.st.row_stride, x.fboxes, x.pbc, (int)x.su.nb, x.p->d_a.p, x.p->d_c.p,
+                (int)x.d.a.size(), (int)x.d.K, x.d.rmax, x.closed, x.p->d_cl_parent.p + x.su.off * x.d.K, x.overflow);
+    },
+    [](const NeighbourSub& x) {
+        return vmd_hip_cluster_finish(x.s, x.p->d_cl_parent.p + x.su.off * x.d.K, x.p->d_cl_root.p + x.su.off * x.d.K,
+                x.p->d_cl_size.p + x.su.off * x.d.K, (int)x.su.nb, (int)x.d.K, x.p->d_cl_count.p + 2 * x.su.off, x.p->d_out.p + x.su.off,
+                x.p->d_cl_largest.p + x.su.off, x.acc, g_opt.cluster_wave_singles.load(), x.overflow);
+    },
+    [](RangeRun& r, BatchCtx& c, int pi, PropState* p) { return r.queue_temporal_rows(c, pi + 2, p->d_cl_largest.p); }};
+
+// Every statement's cell build, of all four kinds, as ONE step in front of the first accumulation: no cell build of the batch may stand
 // behind any kind's atomics.  By within_route's RULE: sel_a in the lanes, sel_b alone sorted (contacts: the one list on both sides), on the
 // grid a within count of the radius rmax gets; all pairs below shell_brute_below entries of sel_b or where no grid exists -> per statement
-// 1 the walk, 0 all pairs.  The ORDER of the builds - accessible area, contacts, hydrogen bonds - is part of the behaviour: where two
+// 1 the walk, 0 all pairs.  The ORDER of the builds - accessible area, contacts, clusters, hydrogen bonds - is part of the behaviour: where two
 // statements sort one selection on different grids the later build wins, and the earlier statement falls back to all pairs (ident_table).
 bool RangeRun::build_neighbour_cells(BatchCtx& c) {
-    for (const NeighbourKind* k : {&kSasa, &kContacts, &kHbonds}) {
+    for (const NeighbourKind* k : {&kSasa, &kContacts, &kClusters, &kHbonds}) {
         std::vector<int>& route = neighbour_route[k->slot];
         route.clear();
         for (int pi : e->*(k->props)) {
@@ -622,7 +655,8 @@ bool RangeRun::launch_rdf(BatchCtx& c) {
     row = 0;
     forked = false;
     if (!launch_rdf_groups(c) || !launch_within_counts(c) || !launch_shell_masks(c) || !launch_shell_exprs(c) || !build_neighbour_cells(c) ||
-        !launch_neighbours(c, kHbonds) || !launch_neighbours(c, kSasa) || !launch_neighbours(c, kContacts) || !launch_shell_sdfs(c) ||
+        !launch_neighbours(c, kHbonds) || !launch_neighbours(c, kSasa) || !launch_neighbours(c, kContacts) || !launch_neighbours(c, kClusters) ||
+        !launch_shell_sdfs(c) ||
         !launch_expr_sdfs(c)) return false;
     for (auto& cm : commits) KRN_OK(vmd_hip_axpy_u64(e->stream, cm.dst, cm.src, VMD_RDF_NUM_BINS, cm.mult, e->d_overflow.p));
     HIP_OK(hipMemcpyAsync(&e->h_overflow[c.slot], e->d_overflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -809,7 +843,7 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
     if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
     switch (d.form) {
     case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: case Form::SASA_AREA:
-    case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: return true;     // (behind the cell builds, above)
+    case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_COUNT: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: return true;     // (behind the cell builds, above)
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);

@@ -271,7 +271,7 @@ static const float* batch_rows(const PropState* p, size_t f0) {
     // accumulators, no rows; a within count's rows are sent by launch_rdf, behind the overflow flag
     case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::RMSF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT:
     case Form::HBOND_OCC: case Form::SASA_AREA: case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC:
-    case Form::CONTACT_NATIVE: return nullptr;
+    case Form::CONTACT_NATIVE: case Form::CLUSTER_COUNT: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: return nullptr;
     case Form::RAMA_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
     case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::SS_CLASS: case Form::SS_POP:
         return p->d_out.p;
@@ -320,7 +320,7 @@ bool RangeRun::queue_batch(size_t bi) {
 
     e->h_overflow[c.slot] = 0;
     if ((!e->rdf_groups.empty() || !e->within_props.empty() || !e->shell_sdf_props.empty() || !e->exprs.empty() || !e->hbond_props.empty() ||
-         !e->sasa_props.empty() || !e->contact_props.empty()) &&
+         !e->sasa_props.empty() || !e->contact_props.empty() || !e->cluster_props.empty()) &&
         !launch_rdf(c)) return false;
 
     for (size_t pi = 0; pi < e->props.size(); ++pi) {

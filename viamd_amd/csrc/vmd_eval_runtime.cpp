@@ -121,6 +121,8 @@ extern "C" int vmd_set_option(const char* key, int value) {
     else if (!strcmp(key, "shell_brute_below")) o = &g_opt.shell_brute_below;
     else if (!strcmp(key, "shell_expr_skip")) o = &g_opt.shell_expr_skip;
     else if (!strcmp(key, "contact_lds_rows")) o = &g_opt.contact_lds_rows;
+    else if (!strcmp(key, "cluster_skip_same")) o = &g_opt.cluster_skip_same;
+    else if (!strcmp(key, "cluster_wave_singles")) o = &g_opt.cluster_wave_singles;
     else if (!strcmp(key, "ss_scratch_bytes")) o = &g_opt.ss_scratch_bytes;
     else if (!strcmp(key, "rmsf_frame_groups")) o = &g_opt.rmsf_frame_groups;
     else if (!strcmp(key, "sdf_ilp")) return vmd_hip_set_sdf_ilp(value);

@@ -104,6 +104,10 @@ static bool is_sasa_record(vmd_script_eval_t* eval, const char* name, const vmd_
 static bool is_contact_record(vmd_script_eval_t* eval, const char* name, const vmd_script_property_data_t* pd) {
     return is_hbond_record(pd) && vmd_eval_contacts(eval, name, nullptr, nullptr);
 }
+// ... and the record of a cluster statement, the same shape, dim = {G + 1, 1}, likewise
+static bool is_cluster_record(vmd_script_eval_t* eval, const char* name, const vmd_script_property_data_t* pd) {
+    return is_hbond_record(pd) && vmd_eval_cluster_sizes(eval, name, nullptr, nullptr);
+}
 
 // pinned to the reference's own export_csv / export_xvg / sample_range by tests/native/ref_callsites.cpp
 extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* eval, const char* name, const char* format,
@@ -135,6 +139,8 @@ extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* e
         return exp_fail(std::string("Export: '") + name + "' is a record of accessible surface points; read it with vmd_eval_sasa");
     } else if (is_contact_record(eval, name, pd)) {
         return exp_fail(std::string("Export: '") + name + "' is the record of a contact map; read it with vmd_eval_contacts");
+    } else if (is_cluster_record(eval, name, pd)) {
+        return exp_fail(std::string("Export: '") + name + "' is the record of cluster sizes; read it with vmd_eval_cluster_sizes");
     } else if (is_hbond_record(pd)) {
         return exp_fail(std::string("Export: '") + name + "' is a hydrogen-bond occupancy record; read it with vmd_eval_hbonds");
     } else if (pd->dim[3] == 0 || pd->dim[2] == 0) {    // temporal: values[frame * dim[1] + i]
@@ -210,6 +216,7 @@ extern "C" bool vmd_export_cube(const char* path, vmd_script_eval_t* eval, const
     if (is_rmsf_record(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is an rmsf record, not a volume");
     if (is_sasa_record(eval, name, pd)) return exp_fail(std::string("Export Cube: '") + name + "' is a record of accessible surface points, not a volume");
     if (is_contact_record(eval, name, pd)) return exp_fail(std::string("Export Cube: '") + name + "' is the record of a contact map, not a volume");
+    if (is_cluster_record(eval, name, pd)) return exp_fail(std::string("Export Cube: '") + name + "' is the record of cluster sizes, not a volume");
     if (is_hbond_record(pd)) return exp_fail(std::string("Export Cube: '") + name + "' is a hydrogen-bond occupancy record, not a volume");
     vmd_sdf_payload_t vis;
     if (!vmd_eval_sdf_payload(eval, name, sys, traj, frame, &vis)) return exp_fail(std::string("Failed to visualize volume for export. ") + vmd_last_error());

@@ -20,6 +20,8 @@
 //   accessible area -> k_sorted_atoms + k_sasa_atoms (the cell walk) / k_canon_entries + k_sasa_brute (all pairs), k_sasa_finish
 //   contact maps   -> k_sorted_atoms + k_contact_atoms (the cell walk) / k_canon_entries + k_contact_brute (all pairs),
 //                                   k_contact_finish_rows / _frames / _out
+//   clusters       -> k_cluster_init, k_sorted_atoms + k_cluster_atoms (the cell walk) / k_cluster_brute (all pairs),
+//                                   k_cluster_finish_roots / _count / _out
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -4975,6 +4977,192 @@ __global__ __launch_bounds__(256) void k_contact_finish_out(vmd_contact_finish_p
     if (i == 0) q.acc[q.P] += (uint64_t)q.B;
 }
 
+// ------------------------------------------------------------------------------------------------ K15: clusters of groups
+
+// One list of entries (atom, group) against itself, as K14's.  Groups g != h are BONDED in a frame when an entry of g and an entry of h pass
+// within()'s pair distance (rule 1 of K12, word for word; no min_sep); the clusters of the frame are the connected components of that graph
+// over all G groups.  DECISION(D-CL-GEOMETRIC): the lane of an entry takes its group from the LIST, a hit takes its group through the
+// identity table (the lowest entry coinciding with the slot).  Coincident entries stand at distance 0 of each other, so their groups are
+// bonded, and whichever of them a third entry is said to have met, the closure is the same: the components are the geometric ones and no
+// coincidence rule enters into them (no vmd_own_slots search in the walk, no k_canon_entries pass in front of all pairs).
+//
+// The components are made by a concurrent union-find over the hits, on the frame's row of `parent`, u32[B][G], preset to parent[g] = g.
+// A root is hooked under a LOWER root only, with one compare-and-swap; so a non-root's parent is always lower than itself, a word only
+// ever decreases, and the final root of a component is its lowest group whatever the order of the hits - its label.  No lane ever waits
+// for another: a failed compare-and-swap proves that another lane's hook of the same root succeeded, a root is hooked once, at most G - 1
+// hooks succeed per frame, and a find walks strictly downwards; so every loop is bounded and there is no spin, no lock and no flag.
+// Inside the launch EVERY read and write of a parent word is an agent-scope atomic - relaxed loads, atomicCAS for the hook, atomicMin for
+// path halving: a plain load may be served from a CU's L1 that no other CU's store refreshes, and a retry loop fed by it need not end.
+// (The SIMT emulator runs one lane at a time and its header has none of the three: there they are the plain forms, as vmd_atomic_min_u32's.)
+__device__ __forceinline__ uint32_t vmd_atomic_load_u32(uint32_t* p) {
+#ifdef __HIPCC__
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ uint32_t vmd_atomic_cas_u32(uint32_t* p, uint32_t expected, uint32_t v) {
+#ifdef __HIPCC__
+    return atomicCAS(p, expected, v);
+#else
+    const uint32_t old = *p;
+    if (old == expected) *p = v;
+    return old;
+#endif
+}
+// the root of g's tree as some moment of the launch saw it; path halving on the way (parent[g] <- an ancestor, which is lower: atomicMin)
+__device__ __forceinline__ uint32_t vmd_cluster_find(uint32_t* parent, uint32_t g) {
+    for (;;) {
+        const uint32_t p = vmd_atomic_load_u32(parent + g);
+        if (p == g) return g;
+        const uint32_t gp = vmd_atomic_load_u32(parent + p);
+        if (gp != p) vmd_atomic_min_u32(parent + g, gp);
+        g = gp;                          // (gp <= p < g: strictly downwards)
+    }
+}
+// a and b into one tree -> its root as this lane left it (the lower of the two roots)
+__device__ __forceinline__ uint32_t vmd_cluster_union(uint32_t* parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = vmd_cluster_find(parent, a);
+        b = vmd_cluster_find(parent, b);
+        if (a == b) return a;
+        const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+        const uint32_t old = vmd_atomic_cas_u32(parent + hi, hi, lo);
+        if (old == hi) return lo;
+        a = old; b = lo;                 // another lane hooked hi first: again from what it hooked it under
+    }
+}
+
+struct vmd_cluster_atoms_params_t {
+    vmd_cells_params_t c;       // the entries as their cell build read them: raw frame, the GRID's boxes, pbc, the list, grid (no outputs)
+    vmd_within_walk_params_t k; // the cell-sorted copy of the SAME list, the test of within(r_cut, .)
+    const int32_t* grp; uint32_t ngroups;
+    const uint32_t* ident;      // k_sorted_atoms' table of the copy, u32[B][k.nref_pad]
+    uint32_t* parent;           // u32[B][ngroups], preset by k_cluster_init
+    const uint32_t* skip;
+};
+
+// parent[b][g] = g in front of every walk and every all pairs, a repeated batch included
+__global__ __launch_bounds__(256) void k_cluster_init(uint32_t* parent, uint32_t G, const uint32_t* skip) {
+    if (skip && *skip) return;
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g < G) parent[(size_t)blockIdx.y * G + g] = g;
+}
+
+// The walk, one lane per entry in list order, standing where vmd_walk_lane puts it, its group from the list.  Every hit of another group
+// is a union.  SKIP (option cluster_skip_same, measured and off by default): the lane keeps the last group it joined and the
+// root that union left - a member of its own tree, so the next union may start from it - and skips the hits that repeat that group.
+template <bool SKIP>
+__global__ __launch_bounds__(256) void k_cluster_atoms(vmd_cluster_atoms_params_t p) {
+    if (p.skip && *p.skip) return;       // a cell build of this batch overflowed a bucket: the table and the copy are void
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.c.nsel) return;
+    const vmd_within_walk_t k = vmd_within_walk_setup(p.c.boxes, b, p.c.pbc, p.c.grid, p.k);
+    const uint32_t* id = p.ident + (size_t)b * p.k.nref_pad;
+    const uint32_t n = (uint32_t)p.c.nsel;
+    const int32_t* grp = p.grp;
+    uint32_t* parent = p.parent + (size_t)b * p.ngroups;
+    const vmd_walk_lane_t l = vmd_walk_lane(p.c, k, b, t);
+    const uint32_t gl = (uint32_t)grp[t];
+    uint32_t mine = gl, last = gl;
+    vmd_within_walk_each(k, l.py, l.pz, l.x, l.y, l.z, [&](unsigned j, float, float, float) {
+        const uint32_t a = id[j];
+        if (a >= n) return false;        // (an unclaimed slot would be a bug of k_sorted_atoms; it is never an index)
+        const uint32_t go = (uint32_t)grp[a];
+        if (go == gl || (SKIP && go == last)) return false;
+        const uint32_t r = vmd_cluster_union(parent, mine, go);
+        if (SKIP) { mine = r; last = go; }
+        return false;
+    });
+}
+
+struct vmd_cluster_brute_params_t {
+    const float* xyz; size_t frame_stride; size_t row_stride;
+    const float* boxes; uint32_t pbc;
+    const int32_t* ent; const int32_t* grp; int nent; uint32_t ngroups;
+    vmd_within_test_t w;        // within(r_cut, .)
+    uint32_t* parent; const uint32_t* skip;
+};
+
+// All pairs from the raw frame: one lane per entry over vmd_all_pairs, the list staged with every entry's group from the list.  The upper
+// triangle of the entry pairs only, as k_contact_brute's; the group test stands in front of the distance test.  The same union.
+__global__ __launch_bounds__(256) void k_cluster_brute(vmd_cluster_brute_params_t p) {
+    __shared__ float s_r[3][256];
+    __shared__ uint32_t s_g[256];
+    if (p.skip && *p.skip) return;
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const float* fx = p.xyz + (size_t)b * p.frame_stride;
+    const float* fy = fx + p.row_stride;
+    const float* fz = fy + p.row_stride;
+    const vmd_box_t bx = vmd_load_box(p.boxes, b, p.pbc);
+    const bool valid = t < p.nent;
+    float xi = VMD_FAR, yi = VMD_FAR, zi = VMD_FAR;
+    uint32_t gl = 0;
+    if (valid) {
+        const int a = p.ent[t];
+        vmd_pair_coords(bx, fx[a], fy[a], fz[a], xi, yi, zi);
+        gl = (uint32_t)p.grp[t];
+    }
+    uint32_t* parent = p.parent + (size_t)b * p.ngroups;
+    vmd_all_pairs<256>(s_r, bx, fx, fy, fz, p.ent, p.nent, blockIdx.x * 256, valid, xi, yi, zi,
+        [&](int jj, int pos) { s_g[jj] = (uint32_t)p.grp[pos]; },
+        [&](int jj, int pos, float ex, float ey, float ez) {
+            if (pos <= t) return false;
+            const uint32_t go = s_g[jj];
+            if (go != gl && vmd_within_hit(p.w, vmd_d2(ex, ey, ez))) vmd_cluster_union(parent, gl, go);
+            return false;
+        });
+}
+
+// The finish, behind the walk or all pairs over a frame group: three launches under the overflow flag.  They stand behind a kernel
+// boundary, so the parent words are read with plain loads here.
+struct vmd_cluster_finish_params_t {
+    const uint32_t* parent; uint32_t* root; uint32_t* size; uint32_t G; int B;
+    unsigned* counts;                           // u32[2 B], zeroed by the launcher: the clusters, the largest cluster per frame
+    float* out_count; float* out_largest; uint64_t* acc; const uint32_t* skip;      // (the three may be NULL: the labels of one frame)
+};
+// one lane per (frame, group): the group's root - its label, what vmd_eval_cluster_labels copies back - and one count into the root's size
+__global__ __launch_bounds__(256) void k_cluster_finish_roots(vmd_cluster_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= q.G) return;
+    const size_t row = (size_t)blockIdx.y * q.G;
+    const uint32_t* parent = q.parent + row;
+    uint32_t r = g;
+    for (uint32_t p = parent[r]; p < r; p = parent[r]) r = p;          // (p < r or p == r: a walk strictly downwards, whatever the words hold)
+    q.root[row + g] = r;
+    atomicAdd(q.size + row + r, 1u);
+}
+// one lane per (frame, group), acting where the group is a root: the clusters of the frame summed over the wave, the largest by atomicMax,
+// one u64 add into row size - 1 of the record's partial.  SINGLES (option cluster_wave_singles, measured and kept): the clusters of ONE group - in a dilute system
+// nearly every lane - are summed over the wave into one add to row 0.
+template <bool SINGLES>
+__global__ __launch_bounds__(256) void k_cluster_finish_count(vmd_cluster_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const int b = blockIdx.y;
+    const size_t row = (size_t)b * q.G;
+    const bool is_root = g < q.G && q.root[row + g] == g;
+    const uint32_t s = is_root ? q.size[row + g] : 0u;
+    vmd_wave_add_u32(q.counts + b, is_root ? 1u : 0u);
+    if (is_root) atomicMax(q.counts + q.B + b, s);
+    if (!q.acc) return;
+    if (SINGLES) vmd_wave_add_u64(q.acc, s == 1u ? 1u : 0u);
+    if (s > (SINGLES ? 1u : 0u)) vmd_atomic_add_u64(q.acc + (s - 1u), 1u);
+}
+// the temporal rows and the frames row, bumped once per frame
+__global__ __launch_bounds__(256) void k_cluster_finish_out(vmd_cluster_finish_params_t q) {
+    if (q.skip && *q.skip) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < q.B) {
+        if (q.out_count) q.out_count[i] = (float)q.counts[i];
+        if (q.out_largest) q.out_largest[i] = (float)q.counts[q.B + i];
+    }
+    if (i == 0 && q.acc) q.acc[q.G] += (uint64_t)q.B;
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -5662,6 +5850,69 @@ extern "C" int vmd_hip_contact_finish(void* stream, const uint32_t* bits, int B,
     hipLaunchKernelGGL(k_contact_finish_frames, dim3((W + 255u) / 256u + ((uint32_t)nnative + 255u) / 256u, B), dim3(256), 0, s, q);
     VMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_contact_finish_out, dim3((B + 255) / 256), dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K15: clusters of groups
+static bool vmd_cluster_args_ok(int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, float r_cut, const uint32_t* parent) {
+    return B <= 65535 && ent && grp && nent > 0 && ngroups >= 1 && ngroups <= (1 << 24) && r_cut > 0.0f && parent;
+}
+// parent[b][g] = g, in front of every launch that unites
+static int vmd_cluster_init(hipStream_t s, int B, int ngroups, uint32_t* parent, const uint32_t* skip_flag) {
+    hipLaunchKernelGGL(k_cluster_init, dim3((ngroups + 255) / 256, B), dim3(256), 0, s, parent, (uint32_t)ngroups, skip_flag);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_cluster_atoms(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* grid_boxes,
+                                     uint32_t pbc_flags, int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups,
+                                     const float* sorted, const uint32_t* cell_start, int nent_pad, const uint32_t* ident, vmd_grid_t grid,
+                                     float r_cut, int closed, int skip_same, uint32_t* parent, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    vmd_cluster_atoms_params_t p{};
+    if (!vmd_cluster_args_ok(B, ent, grp, nent, ngroups, r_cut, parent) || !grid_boxes ||
+        !vmd_ident_walk_fill(p.k, grid, sorted, cell_start, ident, nent, nent_pad, r_cut, closed)) return (int)hipErrorInvalidValue;
+    if (const int rc = vmd_cluster_init(s, B, ngroups, parent, skip_flag)) return rc;
+    p.c = vmd_walk_lanes(xyz, frame_stride, row_stride, grid_boxes, pbc_flags, ent, nent, grid);
+    p.grp = grp; p.ngroups = (uint32_t)ngroups; p.ident = ident; p.parent = parent; p.skip = skip_flag;
+    if (skip_same) hipLaunchKernelGGL(k_cluster_atoms<true>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_cluster_atoms<false>, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_cluster_brute(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                     uint32_t pbc_flags, int B, const int32_t* ent, const int32_t* grp, int nent, int ngroups, float r_cut,
+                                     int closed, uint32_t* parent, const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (!vmd_cluster_args_ok(B, ent, grp, nent, ngroups, r_cut, parent) || !boxes) return (int)hipErrorInvalidValue;
+    if (const int rc = vmd_cluster_init(s, B, ngroups, parent, skip_flag)) return rc;
+    vmd_cluster_brute_params_t p{xyz, frame_stride, row_stride, boxes, pbc_flags, ent, grp, nent, (uint32_t)ngroups,
+                                 vmd_make_within_test(0.0f, r_cut, closed), parent, skip_flag};
+    hipLaunchKernelGGL(k_cluster_brute, dim3((nent + 255) / 256, B), dim3(256), 0, s, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_cluster_finish(void* stream, const uint32_t* parent, uint32_t* root, uint32_t* size, int B, int ngroups,
+                                      uint32_t* counts, float* out_count, float* out_largest, uint64_t* acc, int wave_singles,
+                                      const uint32_t* skip_flag) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (B > 65535 || !parent || !root || !size || ngroups < 1 || ngroups > (1 << 24) || !counts) return (int)hipErrorInvalidValue;
+    { const hipError_t e = hipMemsetAsync(size, 0, (size_t)B * (size_t)ngroups * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    { const hipError_t e = hipMemsetAsync(counts, 0, 2 * (size_t)B * sizeof(uint32_t), s); if (e != hipSuccess) return (int)e; }
+    vmd_cluster_finish_params_t q{parent, root, size, (uint32_t)ngroups, B, counts, out_count, out_largest, acc, skip_flag};
+    const dim3 grid((ngroups + 255) / 256, B);
+    hipLaunchKernelGGL(k_cluster_finish_roots, grid, dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    if (wave_singles) hipLaunchKernelGGL(k_cluster_finish_count<true>, grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL(k_cluster_finish_count<false>, grid, dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_cluster_finish_out, dim3((B + 255) / 256), dim3(256), 0, s, q);
     VMD_LAUNCH_CHECK();
     return 0;
 }

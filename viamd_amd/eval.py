@@ -299,6 +299,21 @@ class ScriptIR:
         cn = (C.c_char_p * 3)(*([x.encode() for x in names] + [None] * (3 - len(names))))
         self._check(self.lib.vmd_ir_add_contacts(self.h, cn, C.byref(sites), float(r_cut), int(min_sep)))
 
+    def add_clusters(self, names, atoms, groups, r_cut=3.5, ngroups=None):
+        """Connected clusters of groups per frame: names = (clusters per frame, record of the cluster sizes, largest cluster
+        per frame).  Entry i is atoms[i] standing for group groups[i]; groups are bonded in a frame when some entry of each is within r_cut
+        of the other, and the clusters are the connected components over all groups.  ngroups: None = max(groups) + 1; every group needs an
+        entry.  The record is u64 [G + 1]: row s - 1 the clusters of s groups summed over the evaluated frames, then the frames."""
+        names = list(names)
+        assert len(names) == 3, "clusters defines three properties"
+        a_, ap = _idx(atoms)
+        g_, gp = _idx(groups)
+        if a_.size != g_.size:
+            raise ValueError("atoms and groups must list one value per entry each")
+        G = int(ngroups) if ngroups is not None else (int(g_.max()) + 1 if g_.size else 0)
+        sites = L.ContactSitesC(a_.size, ap, gp, G, 0, None)
+        self._check(self.lib.vmd_ir_add_clusters(self.h, (C.c_char_p * 3)(*[x.encode() for x in names]), C.byref(sites), float(r_cut)))
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -476,6 +491,15 @@ class PropertyDataView:
         it was in contact, then the frames accumulated"""
         assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not the record of a contact map"
         return self._record(self.c.dim[0])
+
+    @property
+    def cluster_accumulators(self):
+        """the record of a cluster statement as uint64 [G + 1]: row s - 1 the clusters of s groups summed over the evaluated
+        frames, then the frames accumulated"""
+        assert self.c.dim[1] == 1 and self.c.dim[2] == 0 and self.c.counts, "not the record of cluster sizes"
+        if self._ev is not None and not self._ev.lib.vmd_eval_refresh_counts(self._ev.h, self._name.encode()):
+            raise VmdError(self._ev.lib.last_error())
+        return self._arr(self.c.counts, self.c.dim[0], np.uint64)
 
     @property
     def ss_classes(self):
@@ -795,6 +819,39 @@ class ScriptEval:
             if cap is not None or n <= room:
                 return out[:min(n, room)].copy()
             room = int(n)
+
+    def _cluster_groups(self, name):
+        """G of the cluster statement that `name` names (any of its three names), from the name's own form: the record is the MAP of the
+        three; of the two temporal names only the count has atoms (vmd_ir_geometry_atoms), so the record stands one place behind the count
+        and one in front of the largest - what stands next to the statement in the ir never enters into it"""
+        if not self.lib.vmd_eval_cluster_sizes(self.h, name.encode(), None, None):     # (the name and the form, before any size is believed)
+            raise VmdError(self.lib.last_error())
+        names = self.ir.property_names()
+        i = names.index(name)
+        if self.ir.property_flags(name) != L.FLAG_MAP:
+            i = i + 1 if self.ir.geometry_atoms(name).size else i - 1
+        return self.property_data(names[i]).dim[0] - 1
+
+    def cluster_sizes(self, name):
+        """the cluster sizes read from their record as it stands (any name of the statement) -> (mean_count, frames):
+        mean_count float64 [G], entry s - 1 = the clusters of s groups per frame"""
+        G = self._cluster_groups(name)
+        mean = np.zeros(G, np.float64)
+        frames = C.c_uint64(0)
+        if not self.lib.vmd_eval_cluster_sizes(self.h, name.encode(), mean.ctypes.data_as(L.c_double_p), C.byref(frames)):
+            raise VmdError(self.lib.last_error())
+        return mean, int(frames.value)
+
+    def cluster_labels(self, name, sys, traj, frame):
+        """the cluster labels of one frame, on demand (DESIGN 1.17) -> (labels uint32 [G], labels[g] = the lowest group of g's cluster;
+        the number of clusters)"""
+        G = self._cluster_groups(name)
+        labels = np.zeros(G, np.uint32)
+        n = self.lib.vmd_eval_cluster_labels(self.h, name.encode(), C.byref(sys.c) if sys is not None else None, traj.interface(),
+                                             int(frame), labels.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if n == C.c_size_t(-1).value:
+            raise VmdError(self.lib.last_error())
+        return labels, int(n)
 
     def sdf_matrices(self, name, sys, traj, frame):
         """vis.sdf.matrices / vis.sdf.extent of md_script_vis_eval_payload (density_volume.cpp:183-204)."""

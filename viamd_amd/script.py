@@ -963,6 +963,7 @@ def contact_sites_from_topology(topo, heavy_only=True):
     """Contact sites for ScriptIR.add_contacts (DECISION D-CT-TOPOLOGY; the twin of vmd_topology_contact_sites): an entry
     for every atom - heavy_only: for every atom whose element is not H, whatever its case - in ascending atom order; its group is the
     atom's residue_index renumbered densely in order of first appearance.  A topology without residue_index is one group.
+    The same sites serve ScriptIR.add_clusters: every group has an entry, and a water residue is a molecule.
     Returns dict(atoms, groups int32 arrays, ngroups)."""
     el = [str(e).upper() for e in topo.elements]
     ri = getattr(topo, "residue_index", None)
