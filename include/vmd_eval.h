@@ -423,6 +423,17 @@ bool vmd_ir_add_contacts(vmd_script_ir_t* ir, const char* const names[3], const 
  * defined or equal to each other.  vmd_ir_geometry_atoms: the entries' atoms. */
 #define VMD_CLUSTER_MAX_GROUPS (1u << 24)      /* every count a float carries stays exact */
 bool vmd_ir_add_clusters(vmd_script_ir_t* ir, const char* const names[3], const vmd_contact_sites_t* sites, float r_cut);
+/* Mean-squared displacement over lag times (an entry point, no script syntax): the first property that relates a frame to
+ * another frame.  The statement defines ONE property, the position table of the n listed atoms: TEMPORAL, dim = {num_frames, 3 n + 9}, row f
+ * = x[n], y[n], z[n] of the atoms as frame f holds them (bit for bit; nothing is computed), then the nine floats of the frame's cell as the
+ * kernels read it - the edges L, their reciprocals fl(1 / L), the tilts xy, xz, yz - with L = 1 / L = 0 on an axis that is not periodic
+ * (its flag is clear, or this frame's edge is not positive).
+ * 12 n + 36 bytes per frame, on the host and on the device, for the whole trajectory (vmd_eval_create fails cleanly when they cannot be
+ * had).  A frame's row is written whenever the frame is evaluated, the same by whatever call, batch, frame block or rank; the table is
+ * kept, flagged and merged as the angle table of vmd_ir_add_ramachandran is, and vmd_eval_clear_data zeroes it.  No aggregate.
+ * Errors (vmd_last_error): NULL arguments, n == 0, a negative atom, more than VMD_MSD_MAX_ATOMS atoms, a name already defined.
+ * vmd_ir_geometry_atoms: the atoms.  vmd_ir_work_per_frame adds n. */
+bool vmd_ir_add_msd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n);
 /* the atoms of an angle / dihedral property, every set of one context (context < 0: of all contexts) in argument order, or the set of a
  * shape_weights or rmsd property, or the reference set followed by the target set of a within count (a count over a shell expression: every
  * term's reference set in term order, then the target set): returns how many
@@ -648,6 +659,25 @@ size_t vmd_eval_shell_mask(vmd_script_eval_t* eval, const char* name, int which,
  * the device table is refreshed from the host rows first, so every rank of a merged evaluation answers for the whole trajectory. */
 bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, float* values,
                            uint64_t sums[4]);
+
+/* MSD over lag times from the position table of a vmd_ir_add_msd statement.  sums: host u64[max_lag + 1][4]; column k < 3 of
+ * row tau = the sum over the origins t = frame_beg, frame_beg + origin_stride, .. with t + tau < frame_end, and over the n atoms, of the
+ * squared displacement along axis k between frames t and t + tau, in 2^-20 A^2 quanta; column 3 = the number of terms, origins x n.  A host
+ * reads MSD(tau) = (c0 + c1 + c2) / (2^20 c3), or the lateral / normal part from the columns it wants.
+ * D-MSD-UNWRAP: per atom and periodic axis an image count n_k(t), 0 at frame_beg; from t to t + 1 the SPEC S3 comparison under the cell of
+ * frame t + 1 decides - x(t+1) - x(t) > L/2: n goes down by one, < -L/2: up by one, otherwise (a jump of exactly half a cell included)
+ * it stays - so that x + n L is the unwrapped coordinate.  An open axis has no count.  The displacement is formed in fp32, each operation
+ * rounded on its own: d = (x(t+tau) - x(t)) + (float)(n(t+tau) - n(t)) * L_k(t+tau), q = (u64)((d * d) * 2^20) truncating.  Every term is
+ * an integer before it is summed: the sums do not depend on the launch.  They overflow when quanta x terms reach 2^64 (|d| <= 1024 A:
+ * 2^40 quanta, 2^24 terms per lag).  frames_used (NULL: not wanted): frame_end - frame_beg.
+ * Under the eval's mutex, as vmd_eval_rama_density: accumulated results, fingerprints and the frame mask are untouched, and after a merge
+ * the device table is refreshed from the host rows first.  false + vmd_last_error: NULL arguments, an unknown name or a name of another
+ * form, an empty or reversed window, frame_end beyond the trajectory, origin_stride == 0, max_lag >= frame_end - frame_beg, a frame of the
+ * window that has not been evaluated (the message names the first), a window above 65535 * 32 frames, a triclinic cell in the window. */
+bool vmd_eval_msd(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, uint32_t max_lag, uint32_t origin_stride,
+                  uint64_t (*sums)[4], uint32_t* frames_used);
+/* the atoms of an msd position table; 0 (no error) for every other name */
+size_t vmd_eval_msd_atoms(const vmd_script_eval_t* eval, const char* name);
 
 /* An rmsf property read from its record as it stands - partially evaluated or merged alike.  With F = the frames
  * accumulated: m = sum_q / (2^24 F) per axis, msf = sum_q2 / (2^24 F) - |m|^2 clamped at 0, rmsf = sqrt(msf): the fluctuation about the

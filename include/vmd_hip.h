@@ -25,6 +25,7 @@
  *   vmd_hip_sorted_atoms, vmd_hip_hbond_*  <- hydrogen bonds
  *   vmd_hip_contact_*  <- residue contact maps
  *   vmd_hip_cluster_*  <- connected clusters of groups
+ *   vmd_hip_msd_*  <- mean-squared displacement over lag times (the reference has no such code)
  *   vmd_hip_sasa_*  <- solvent-accessible surface area
  *   vmd_hip_xtc_decode <- md_xtc frame decompression (f1; /root/reference/src/loader.cpp:147-148)
  */
@@ -424,6 +425,25 @@ int vmd_hip_cluster_brute(void* stream, const float* xyz, size_t frame_stride, s
                           const uint32_t* skip_flag);
 int vmd_hip_cluster_finish(void* stream, const uint32_t* parent, uint32_t* root, uint32_t* size, int B, int ngroups, uint32_t* counts,
                            float* out_count, float* out_largest, uint64_t* acc, int wave_singles, const uint32_t* skip_flag);
+
+/* K16: mean-squared displacement over lag times.  The position table has rows of 3 n + 9 floats: x[n], y[n], z[n] of the n
+ * listed atoms as the frame holds them, then the frame's cell {L, 1/L, tilts} with L = 1/L = 0 on an axis that is not periodic
+ * (its flag is clear in pbc_flags, or the frame's own edge is not positive).
+ *   vmd_hip_msd_gather  rows f32[B][3 n + 9] of a batch; B <= 65535
+ *   vmd_hip_msd_unwrap  counts i32[F][3][n], one word per axis: the image counts of the F consecutive rows at `rows`, 0 in the first, by the
+ *                       SPEC S3 comparison under the later frame's cell (D-MSD-UNWRAP); an axis with L = 0 keeps its count
+ *   vmd_hip_msd_lags    sums u64[max_lag + 1][4] are ADDED to: per lag tau the squared displacements along x, y, z in 2^-20 A^2 quanta,
+ *                       q = (u64)((d * d) * 2^20) with d = (x(t + tau) - x(t)) + (float)(n(t + tau) - n(t)) * L(t + tau) in fp32, summed over
+ *                       the origins t = 0, origin_stride, .. with t + tau < F and over the atoms, and the number of terms (origins x n).
+ *                       0 <= max_lag < F, origin_stride >= 1, F <= 65535 * 32.  Integer sums: the same whatever the launch shape
+ *   vmd_hip_msd_tile    the atoms, origin frames and lags a block of vmd_hip_msd_lags takes (the size edges of a test) */
+#define VMD_MSD_MAX_ATOMS 0x0fffffff
+#define VMD_MSD_CELL_FLOATS 9
+int vmd_hip_msd_gather(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes, uint32_t pbc_flags, int B,
+                       const int32_t* idx, int n, float* rows);
+int vmd_hip_msd_unwrap(void* stream, const float* rows, int F, int n, int32_t* counts);
+int vmd_hip_msd_lags(void* stream, const float* rows, const int32_t* counts, int F, int n, int max_lag, int origin_stride, uint64_t* sums);
+int vmd_hip_msd_tile(int* atoms, int* origins, int* lags);
 
 /* dst[i] += mult * src[i] (u64): one pair pass feeding several histograms; does nothing when *skip_flag != 0 */
 int vmd_hip_axpy_u64(void* stream, uint64_t* dst, const uint64_t* src, size_t n, uint64_t mult, const uint32_t* skip_flag);

@@ -230,6 +230,10 @@ SIGNATURES = [
     ("vmd_backbone_view", C.POINTER(BackboneC), [_vp]),
     ("vmd_backbone_free", None, [_vp]),
     ("vmd_eval_rama_density", C.c_bool, [_vp, C.c_char_p, C.c_uint32, C.c_uint32, c_float_p, c_uint64_p]),
+    ("vmd_ir_add_msd", C.c_bool, [_vp, C.c_char_p, c_int32_p, C.c_size_t]),
+    ("vmd_eval_msd", C.c_bool, [_vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, c_uint64_p, C.POINTER(C.c_uint32)]),
+    ("vmd_eval_msd_atoms", C.c_size_t, [_vp, C.c_char_p]),
+    ("vmd_hip_msd_tile", C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("vmd_ir_geometry_atoms", C.c_size_t, [_vp, C.c_char_p, C.c_int64, c_int32_p, C.c_size_t]),
     ("vmd_ir_compile_from_source", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC)]),
     ("vmd_ir_compile_from_source_ex", C.c_bool, [_vp, C.c_char_p, C.POINTER(TopologyC), C.c_uint32, C.POINTER(_vp)]),
@@ -449,6 +453,9 @@ SIGNATURES = [
     ("vmd_hip_cluster_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
                                         C.c_int, _vp, _vp]),
     ("vmd_hip_cluster_finish", C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    ("vmd_hip_msd_gather", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp]),
+    ("vmd_hip_msd_unwrap", C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    ("vmd_hip_msd_lags", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     ("vmd_hip_within_brute", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_uint32, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                        C.c_float, C.c_float, C.c_int, _vp]),
     ("vmd_hip_within_pencil", C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, Grid,

@@ -227,7 +227,7 @@ bool reuse_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t beg, siz
                         for (size_t k = 0; k < p->ncounts; ++k) p->weights64[k] += q->block_weights64[blk * p->ncounts + k];
                 } else {
                     memcpy(&p->values[f * p->dim1], block_rows(src, q, blk) + f * p->dim1, (bend - f) * p->dim1 * sizeof(float));
-                    if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // the device table follows before the next filtered map
+                    if (p->prop.device_table()) p->table_stale = true;     // the device table follows before the next filtered map
                 }
                 p->dirty = true;
             }

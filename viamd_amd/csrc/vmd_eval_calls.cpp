@@ -120,7 +120,7 @@ bool ra_adopt_blocks(vmd_script_eval_t* e, const TrajId& traj_inst, size_t b0, s
             } else {
                 if (p->ahead_values.size() != p->values.size()) p->ahead_values.assign(p->values.size(), 0.0f);
                 memcpy(&p->ahead_values[f0 * p->dim1], block_rows(src, q, b) + f0 * p->dim1, (f1 - f0) * p->dim1 * sizeof(float));
-                if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // adopted rows reach the device table once committed
+                if (p->prop.device_table()) p->table_stale = true;     // adopted rows reach the device table once committed
             }
         }
         e->block_ready[b] = BLOCK_ROWS_AHEAD;           // (the rows went into the side buffer above)
@@ -144,7 +144,7 @@ bool ra_commit_block(vmd_script_eval_t* e, size_t blk) {
                     + k];
         } else if (p->ahead_values.size() == p->values.size()) {
             memcpy(&p->values[f0 * p->dim1], &p->ahead_values[f0 * p->dim1], (f1 - f0) * p->dim1 * sizeof(float));
-            if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // (rows adopted from a source exist on the host only)
+            if (p->prop.device_table()) p->table_stale = true;     // (rows adopted from a source exist on the host only)
         }
         p->dirty = true;
     }

@@ -369,6 +369,15 @@ extern "C" vmd_script_eval_t* vmd_eval_create(size_t num_frames, const vmd_scrip
             if (hipMemsetAsync(st->d_table.p, 0, num_frames * 2 * p.a.size() * sizeof(float), e->stream) != hipSuccess) {
                 vmd_fail("hipMemset failed"); return nullptr; }
             break;
+        case Form::MSD_TABLE:
+            // x, y, z of every atom and the cell, 12 n + 36 bytes per frame; no aggregate (a mean of coordinates over atoms is
+            // not what the table is for); the whole table lives on the device, as the angle table does
+            st->dist_P = 3 * p.a.size() + VMD_MSD_CELL_FLOATS; st->dist_per = 1;
+            aggregate = false;
+            if (!st->d_table.ensure(num_frames * st->dist_P)) return nullptr;
+            if (hipMemsetAsync(st->d_table.p, 0, num_frames * st->dist_P * sizeof(float), e->stream) != hipSuccess) {
+                vmd_fail("hipMemset failed"); return nullptr; }
+            break;
         // one code per segment, nine counts per frame; no aggregate (a mean of class codes says nothing)
         case Form::SS_CLASS: st->dist_P = p.a.size(); aggregate = false; break;
         case Form::SS_POP: st->dist_P = VMD_SS_NUM_CODES; aggregate = false; break;
@@ -551,7 +560,7 @@ extern "C" void vmd_eval_clear_data(vmd_script_eval_t* eval) {
         std::fill(p->agg_var.begin(), p->agg_var.end(), 0.0f);
         std::fill(p->agg_ext.begin(), p->agg_ext.end(), 0.0f);
         if (p->ncounts) (void)hipMemsetAsync(p->d_counts.p, 0, p->ncounts * sizeof(uint64_t), eval->stream);
-        if (p->prop.form == Form::RAMA_TABLE) {
+        if (p->prop.device_table()) {
             (void)hipMemsetAsync(p->d_table.p, 0, p->values.size() * sizeof(float), eval->stream);
             p->table_stale = false;
         }
@@ -722,7 +731,7 @@ extern "C" bool vmd_eval_finalize(vmd_script_eval_t* eval) {
     for (auto& p : eval->props) {
         const bool ok = refresh_view(eval, p.get());
         // rows of other ranks may have joined the host table (vmd_eval_reduce): the device copy follows before the next filtered map
-        if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;
+        if (p->prop.device_table()) p->table_stale = true;
         if (!ok) return false;
     }
     return true;
@@ -811,7 +820,7 @@ extern "C" void vmd_eval_set_frame_mask(vmd_script_eval_t* eval, const uint8_t* 
         done += eval->frame_mask[f] ? 1 : 0;
     }
     eval->frames_done = done;
-    for (auto& p : eval->props) if (p->prop.form == Form::RAMA_TABLE) p->table_stale = true;     // frames evaluated elsewhere: their rows are on the host
+    for (auto& p : eval->props) if (p->prop.device_table()) p->table_stale = true;     // frames evaluated elsewhere: their rows are on the host
 }
 
 extern "C" size_t vmd_eval_accum_views(vmd_script_eval_t* eval, vmd_accum_view_t* out, size_t cap) {
@@ -913,6 +922,61 @@ extern "C" bool vmd_eval_rama_density(vmd_script_eval_t* eval, const char* name,
     HIP_OK(hipStreamSynchronize(e->stream));
     if (sums) memcpy(sums, s4, sizeof(s4));
     return true;
+}
+
+// ---- mean-squared displacement over lag times: the time unwrap of the window (k_msd_unwrap), then the sums over origins and
+// atoms per lag (k_msd_lags), from the position table the device holds.  Under the eval's mutex like the filtered map above; it writes only
+// the table property's own scratch.  The profile (vmd_profile_ms) splits it into "msd_unwrap" and "msd_lags".
+extern "C" bool vmd_eval_msd(vmd_script_eval_t* eval, const char* name, uint32_t frame_beg, uint32_t frame_end, uint32_t max_lag,
+                             uint32_t origin_stride, uint64_t (*sums)[4], uint32_t* frames_used) {
+    if (!eval || !name || !sums) return vmd_fail("vmd_eval_msd: NULL argument");
+    vmd_script_eval_t* e = eval;
+    PropState* t = nullptr;
+    for (auto& p : e->props) if (p->prop.name == name) t = p.get();
+    if (!t) return vmd_fail("unknown property '%s'", name);
+    if (t->prop.form != Form::MSD_TABLE) return vmd_fail("'%s' is not an msd position table", name);
+    if (frame_beg >= frame_end) return vmd_fail("vmd_eval_msd: the window [%u, %u) is empty or reversed", frame_beg, frame_end);
+    if (frame_end > e->num_frames)
+        return vmd_fail("frames [%u, %u) are outside the %zu frames of the evaluation", frame_beg, frame_end, e->num_frames);
+    if (origin_stride == 0) return vmd_fail("vmd_eval_msd: the origin stride must be at least 1");
+    const size_t F = frame_end - frame_beg, n = t->prop.a.size(), w = t->dim1;
+    if (max_lag >= F) return vmd_fail("vmd_eval_msd: max_lag %u needs more than the %zu frames of the window", max_lag, F);
+    if (F > (size_t)65535 * 32) return vmd_fail("vmd_eval_msd: a window of %zu frames exceeds the launch limit (%d)", F, 65535 * 32);
+    std::lock_guard<std::mutex> lock(e->mtx);
+    HIP_OK(hipSetDevice(e->device));
+    // the unwrap needs consecutive frames: a gap is a refusal, not a guess
+    for (size_t f = frame_beg; f < frame_end; ++f)
+        if (!mask_get(e->frame_mask, f)) return vmd_fail("vmd_eval_msd: frame %zu of the window has not been evaluated", f);
+    for (size_t f = frame_beg; f < frame_end; ++f) {
+        const float* cell = t->values.data() + f * w + 3 * n;
+        if (cell[6] != 0.0f || cell[7] != 0.0f || cell[8] != 0.0f)
+            return vmd_fail("vmd_eval_msd: frame %zu has a triclinic cell (the time unwrap is defined for orthorhombic cells)", f);
+    }
+    if (!t->d_msd_counts.ensure(F * 3 * n) || !t->d_msd_sums.ensure(((size_t)max_lag + 1) * 4)) return false;
+    if (t->table_stale) {
+        HIP_OK(hipMemcpyAsync(t->d_table.p, t->values.data(), t->values.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        t->table_stale = false;
+    }
+    const float* rows = t->d_table.p + (size_t)frame_beg * w;
+    const size_t nsums = ((size_t)max_lag + 1) * 4;
+    HIP_OK(hipMemsetAsync(t->d_msd_sums.p, 0, nsums * sizeof(uint64_t), e->stream));
+    e->prof.begin("msd_unwrap", e->stream);
+    KRN_OK(vmd_hip_msd_unwrap(e->stream, rows, (int)F, (int)n, t->d_msd_counts.p));
+    e->prof.end(e->stream);
+    e->prof.begin("msd_lags", e->stream);
+    KRN_OK(vmd_hip_msd_lags(e->stream, rows, t->d_msd_counts.p, (int)F, (int)n, (int)max_lag, (int)std::min<uint32_t>(origin_stride, 0x7fffffffu),
+            t->d_msd_sums.p));
+    e->prof.end(e->stream);
+    HIP_OK(hipMemcpyAsync(sums, t->d_msd_sums.p, nsums * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    e->prof.resolve();
+    if (frames_used) *frames_used = (uint32_t)F;
+    return true;
+}
+
+extern "C" size_t vmd_eval_msd_atoms(const vmd_script_eval_t* eval, const char* name) {
+    PropState* p = find_prop(eval, name);
+    return p && p->prop.form == Form::MSD_TABLE ? p->prop.a.size() : 0;
 }
 
 // ---- what the readers of the records and the one-frame calls share
@@ -1308,6 +1372,9 @@ bool upload_static(vmd_script_eval_t* e, const vmd_system_t* sys, size_t traj_at
             break;
         }
         case Form::WITHIN_EXPR: break;                   // the lists live in the interned selections
+        case Form::MSD_TABLE:                            // the atoms in list order
+            if (!p->d_a.upload(d.a.data(), d.a.size(), e->stream)) return false;
+            break;
         case Form::SDF: {
             if (!p->d_structs.upload(d.a.data(), d.a.size(), e->stream)) return false;
             if (!p->d_tgt.upload(d.b.data(), d.b.size(), e->stream)) return false;

@@ -421,6 +421,9 @@ enum class Form : int {
     // the sizes behind it (K = the groups) are a MAP-class record of u64 accumulators, [K + 1], that the count's launch adds to; the largest
     // behind that has one value per frame, written by the count's launch
     CLUSTER_COUNT, CLUSTER_SIZES, CLUSTER_LARGEST,
+    // `name = msd positions(atoms)`: one descriptor, a = the atoms (aoff = {0, n}).  Its rows are the position table -
+    // x[n], y[n], z[n] as the frame holds them, then the frame's cell - kept on the device like the angle table; vmd_eval_msd correlates it
+    MSD_TABLE,
 };
 
 // what a host reads of a property; the values are what vmd_ir_fingerprint hashes first (4 bytes): they never change
@@ -461,8 +464,9 @@ constexpr FormFacts kFormFacts[] = {
     /* CLUSTER_COUNT   */ {ResultClass::TEMPORAL, 0, "clusters",      {"", ""},         nullptr, true,  21},    // counts
     /* CLUSTER_SIZES   */ {ResultClass::MAP,      0, "clusters",      {"", ""},         nullptr, true,  22},
     /* CLUSTER_LARGEST */ {ResultClass::TEMPORAL, 0, "clusters",      {"", ""},         nullptr, true,  23},
+    /* MSD_TABLE   */ {ResultClass::TEMPORAL,     0, "msd",           {"", "\xC3\x85"}, nullptr, false, 24},    // Angstrom, as the frame holds them
 };
-static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::CLUSTER_LARGEST + 1, "one row of kFormFacts per Form");
+static_assert(sizeof(kFormFacts) / sizeof(kFormFacts[0]) == (size_t)Form::MSD_TABLE + 1, "one row of kFormFacts per Form");
 static_assert(VMD_SS_MAX_SEGMENTS == VMD_SS_SEG_MAX && VMD_SS_NUM_CODES == VMD_SS_CODES && VMD_SASA_MAX_POINTS == VMD_SASA_POINTS_MAX,
               "the kernels' limits are the interface's");
 
@@ -472,6 +476,7 @@ struct Property {
     const FormFacts& facts() const { return kFormFacts[(int)form]; }
     ResultClass cls() const { return facts().cls; }
     bool temporal() const { return cls() == ResultClass::TEMPORAL; }          // rows per frame in `values`
+    bool device_table() const { return form == Form::RAMA_TABLE || form == Form::MSD_TABLE; }     // ... and in d_table, whole
     bool counts_view() const { return cls() == ResultClass::VOLUME || cls() == ResultClass::MAP; }     // a float view made from u64 counts
     vmd_property_flags_t flags() const { return kClassFlags[(int)cls()]; }
     std::vector<int32_t> a, b;      // the first two argument sets (see Form)
@@ -696,6 +701,10 @@ struct PropState {
     DevBuf<float> d_table;
     DevBuf<uint8_t> d_rama_class, d_rama_link, d_rama_mask;
     DevBuf<uint64_t> d_rama_scratch;
+    // position table: d_table as above, [num_frames][3 n + 9]; d_a the atoms; the scratch of a query - the window's image
+    // counts i32[F][3][n] and its sums u64[max_lag + 1][4]
+    DevBuf<int32_t> d_msd_counts;
+    DevBuf<uint64_t> d_msd_sums;
     // secondary structure, the class table: d_a / d_b / d_c as above, the oxygens, the range of every segment, the proline
     // bytes and the "has both neighbours" bit row
     DevBuf<int32_t> d_ss_o, d_ss_rng;
@@ -1204,6 +1213,7 @@ struct RangeRun {
     bool launch_rmsf(BatchCtx& c, size_t pi);
     bool launch_geometry(BatchCtx& c, PropState* p);
     bool launch_rama(BatchCtx& c, size_t pi);
+    bool launch_msd(BatchCtx& c, PropState* p);
     bool launch_ss(BatchCtx& c, size_t pi);
     bool launch_distance(BatchCtx& c, PropState* p);
     bool launch_property(BatchCtx& c, size_t pi);

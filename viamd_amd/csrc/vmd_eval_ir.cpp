@@ -56,6 +56,7 @@ extern "C" uint64_t vmd_ir_work_per_frame(const vmd_script_ir_t* ir) {
         case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: break;            // written by their count's launch
         case Form::CLUSTER_COUNT: w += 4 * (uint64_t)p.a.size(); break;      // 1.16's rule
         case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: break;         // written by their count's launch
+        case Form::MSD_TABLE: w += p.a.size(); break;                        // one gather per atom
         }
     }
     return w;
@@ -583,6 +584,19 @@ extern "C" bool vmd_ir_add_clusters(vmd_script_ir_t* ir, const char* const names
     return commit(ir, tp, 3);
 }
 
+// `name = the position table of atoms`: one descriptor; vmd_eval_msd correlates its rows over lag times
+extern "C" bool vmd_ir_add_msd(vmd_script_ir_t* ir, const char* name, const int32_t* idx, size_t n) {
+    if (!ir) return vmd_fail("ir is NULL");
+    if (!name) return vmd_fail("msd needs a property name");
+    if (!idx || n == 0) return vmd_fail("msd atom list is empty");
+    if (!ir_name_ok(ir, name) || !idx_ok(idx, n, "msd atom list")) return false;
+    if (n > VMD_MSD_MAX_ATOMS) return vmd_fail("msd set too large");
+    Property t = make_property(Form::MSD_TABLE, name);
+    t.a.assign(idx, idx + n);
+    t.aoff = {0, (int32_t)n};
+    return commit(ir, &t);
+}
+
 // what vmd_ir_geometry_atoms has counted and written so far
 struct AtomSink {
     int32_t* out; size_t cap, n = 0;
@@ -608,7 +622,7 @@ extern "C" size_t vmd_ir_geometry_atoms(const vmd_script_ir_t* ir, const char* n
         case Form::RDF: case Form::SDF: case Form::DISTANCE: case Form::RAMA_MAP: case Form::SS_POP: case Form::HBOND_OCC: case Form::SASA_OCC:
         case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST:
             return 0;
-        case Form::CONTACT_COUNT: case Form::CLUSTER_COUNT:   // the entries' atoms (one context)
+        case Form::CONTACT_COUNT: case Form::CLUSTER_COUNT: case Form::MSD_TABLE:   // the entries' atoms; 1.18: the atoms (one context)
             if (context > 0) return 0;
             s.put(p.a);
             return s.n;
@@ -683,6 +697,7 @@ extern "C" uint64_t vmd_ir_fingerprint(const vmd_script_ir_t* ir) {
         case Form::WITHIN_EXPR: case Form::RAMA_MAP: case Form::SS_POP: case Form::RMSF: case Form::HBOND_OCC: break;
         case Form::HBOND_COUNT: h = fnv1a(h, &p.hb_angle, sizeof(float)); break;      // (the hydrogens are c, hashed above)
         case Form::SASA_OCC: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: break;
+        case Form::MSD_TABLE: break;                                    // (the atoms are a, hashed above, the code 24)
         case Form::CLUSTER_COUNT:                                       // (the atoms are a, r_cut is rmax, the groups' number K; one group per entry of a)
             h = fnv1a(h, p.ct_group.data(), p.ct_group.size() * sizeof(int32_t));
             break;

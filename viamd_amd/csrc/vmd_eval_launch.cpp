@@ -785,6 +785,19 @@ bool RangeRun::launch_rama(BatchCtx& c, size_t pi) {
     return true;
 }
 
+// position table: the batch's rows of the device table, written in place; they travel to the host from the table
+// (queue_batch).  No cell grid, no overflow flag, nothing accumulated: a frame evaluated twice gets the same row twice.
+bool RangeRun::launch_msd(BatchCtx& c, PropState* p) {
+    e->prof.begin("msd_gather", e->stream);
+    // (the cells' own flags, which no frame of a trajectory may change - not c.pbc, which drops an axis for the whole batch when the edge of
+    // its FIRST frame is not positive: the gather looks at every frame's own edge, so a row is the same whatever batch writes it)
+    KRN_OK(vmd_hip_msd_gather(e->stream, c.src->base, c.src->frame_stride, c.src->row_stride, c.src->d_boxes.p,
+            c.src->cells[0].flags & VMD_UNITCELL_PBC_ALL, (int)c.nb, p->d_a.p,
+            (int)p->prop.a.size(), p->d_table.p + c.f0 * p->dim1));
+    e->prof.end(e->stream);
+    return true;
+}
+
 // secondary structure: the class rows [nb][nseg] and, in the descriptor behind, the populations [nb][9]; each copies its own
 // (queue_batch).  The bit matrices take nseg^2 / 2 bytes per frame: the batch runs in as many sub-batches of frames as the eval's bound
 // (ss_scratch_bytes) and the launch limit of 2^31 - 1 words ask for, one after another over the same scratch, never below one frame.
@@ -840,13 +853,14 @@ bool RangeRun::launch_property(BatchCtx& c, size_t pi) {
         if (d.form == Form::RDF && !d.is_shell_rdf()) rdf_weights(c, p);
         return true;
     }
-    if (d.temporal() && d.form != Form::RAMA_TABLE && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
+    if (d.temporal() && !d.device_table() && !p->d_out.ensure(c.nb * p->dim1)) return false;     // (the table's rows have their place)
     switch (d.form) {
     case Form::RDF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT: case Form::HBOND_OCC: case Form::SASA_AREA:
     case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC: case Form::CONTACT_NATIVE: case Form::CLUSTER_COUNT: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: return true;     // (behind the cell builds, above)
     case Form::SDF: VMD_STAGE("batch: sdf align + scatter"); return launch_sdf(c, p, nullptr, 0);
     case Form::RAMA_MAP: return true;                                           // filled by the launch of the table in front of it
     case Form::RAMA_TABLE: return launch_rama(c, pi);
+    case Form::MSD_TABLE: return launch_msd(c, p);
     case Form::SS_POP: return true;                                             // filled by the launch of the class table in front of it
     case Form::SS_CLASS: return launch_ss(c, pi);
     case Form::SHAPE: return launch_shape(c, pi);

@@ -272,7 +272,7 @@ static const float* batch_rows(const PropState* p, size_t f0) {
     case Form::RDF: case Form::SDF: case Form::RAMA_MAP: case Form::RMSF: case Form::WITHIN: case Form::WITHIN_EXPR: case Form::HBOND_COUNT:
     case Form::HBOND_OCC: case Form::SASA_AREA: case Form::SASA_OCC: case Form::CONTACT_COUNT: case Form::CONTACT_OCC:
     case Form::CONTACT_NATIVE: case Form::CLUSTER_COUNT: case Form::CLUSTER_SIZES: case Form::CLUSTER_LARGEST: return nullptr;
-    case Form::RAMA_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
+    case Form::RAMA_TABLE: case Form::MSD_TABLE: return p->d_table.p + f0 * p->dim1;                            // the batch's rows of the whole table
     case Form::DISTANCE: case Form::ANGLE: case Form::DIHEDRAL: case Form::SHAPE: case Form::RMSD: case Form::SS_CLASS: case Form::SS_POP:
         return p->d_out.p;
     }

@@ -143,6 +143,8 @@ extern "C" bool vmd_export_property_table(const char* path, vmd_script_eval_t* e
         return exp_fail(std::string("Export: '") + name + "' is the record of cluster sizes; read it with vmd_eval_cluster_sizes");
     } else if (is_hbond_record(pd)) {
         return exp_fail(std::string("Export: '") + name + "' is a hydrogen-bond occupancy record; read it with vmd_eval_hbonds");
+    } else if (vmd_eval_msd_atoms(eval, name) != 0) {    // (a table of raw positions, 3 n + 9 columns per frame)
+        return exp_fail(std::string("Export: '") + name + "' is an msd position table; read it with vmd_eval_msd");
     } else if (pd->dim[3] == 0 || pd->dim[2] == 0) {    // temporal: values[frame * dim[1] + i]
         const size_t F = (size_t)pd->dim[0], D = (size_t)std::max(1, pd->dim[1]);
         rows = F;

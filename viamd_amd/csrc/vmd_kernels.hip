@@ -22,6 +22,7 @@
 //                                   k_contact_finish_rows / _frames / _out
 //   clusters       -> k_cluster_init, k_sorted_atoms + k_cluster_atoms (the cell walk) / k_cluster_brute (all pairs),
 //                                   k_cluster_finish_roots / _count / _out
+//   msd over lag times -> k_msd_gather (the position table's rows of a batch), k_msd_unwrap + k_msd_lags (a query)
 //
 // What the property kernels (K3 alignment, K5 - K5d, K10 backbone, K11 secondary structure) share, each written once:
 //   vmd_frames_t / vmd_frames()  the head of their parameter blocks, filled by one host function; vmd_frame(): frame b's rows and cell
@@ -5163,6 +5164,144 @@ __global__ __launch_bounds__(256) void k_cluster_finish_out(vmd_cluster_finish_p
     if (i == 0 && q.acc) q.acc[q.G] += (uint64_t)q.B;
 }
 
+// ------------------------------------------------------------------------------------------------ K16: mean-squared displacement
+
+// The position table: row f = x[n], y[n], z[n] of the listed atoms as the frame holds them, then the frame's cell as every kernel reads it
+// ({L, 1/L, tilts}, VMD_BOX_STRIDE floats) with L = 1/L = 0 on an axis that is not periodic (its flag is clear, or THIS frame's edge is
+// not positive - whatever frame leads the batch), so that the table says by itself which axes
+// the unwrap follows.  One lane per (frame, entry of a row), the entry fastest: the reads of the cell and the writes are coalesced, the
+// gathers follow the list.  Nothing is computed.
+struct vmd_msd_gather_params_t {
+    vmd_frames_t f;
+    const int32_t* idx; int n;
+    float* rows;   // [B][3 n + 9]
+};
+__global__ __launch_bounds__(256) void k_msd_gather(vmd_msd_gather_params_t p) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int w = 3 * p.n + VMD_BOX_STRIDE;
+    if (j >= w) return;
+    float v;
+    if (j < 3 * p.n) {
+        const int k = j / p.n, i = j - k * p.n;
+        v = p.f.xyz[(size_t)b * p.f.frame_stride + (size_t)k * p.f.row_stride + (size_t)p.idx[i]];
+    } else {
+        const int c = j - 3 * p.n;
+        v = p.f.boxes[(size_t)VMD_BOX_STRIDE * b + c];
+        if (c < 6 && !(((p.f.pbc >> (c % 3)) & 1u) && p.f.boxes[(size_t)VMD_BOX_STRIDE * b + c % 3] > 0.0f)) v = 0.0f;     // the frame's own edge, not the batch's
+    }
+    p.rows[(size_t)b * w + j] = v;
+}
+
+// DECISION(D-MSD-UNWRAP): the image counts of the window, exact, in integers.  One lane per atom walks frames 0 .. F - 1 of the window in
+// order; per axis the count stands at 0 in frame 0 and, from t to t + 1, the SPEC S3 rule (vmd_mi_cmp's comparisons) under the cell of frame
+// t + 1 decides: a difference above half a cell took one cell too many, the count goes down by one; below minus half a cell, up by one; a
+// difference of exactly half a cell is no crossing (S3's tie).  x + count * L is then the unwrapped coordinate.  An axis with L = 0 in frame
+// t + 1 keeps its count.  counts: i32[F][3][n], one word per axis (the range of a count is that of an int).
+struct vmd_msd_unwrap_params_t {
+    const float* rows; int F; int n;
+    int* counts;
+};
+__global__ __launch_bounds__(256) void k_msd_unwrap(vmd_msd_unwrap_params_t p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n) return;
+    const size_t w = 3 * (size_t)p.n + VMD_BOX_STRIDE, cw = 3 * (size_t)p.n;
+    int c[3] = {0, 0, 0};
+    float prev[3];
+    for (int k = 0; k < 3; ++k) { prev[k] = p.rows[(size_t)k * p.n + i]; p.counts[(size_t)k * p.n + i] = 0; }
+    for (int t = 1; t < p.F; ++t) {
+        const float* row = p.rows + (size_t)t * w;
+        for (int k = 0; k < 3; ++k) {
+            const float x = row[(size_t)k * p.n + i], L = row[3 * (size_t)p.n + k];
+            if (L > 0.0f) {
+                const float d = x - prev[k], hL = 0.5f * L;
+                c[k] += d > hL ? -1 : (d < -hL ? 1 : 0);
+            }
+            prev[k] = x;
+            p.counts[(size_t)t * cw + (size_t)k * p.n + i] = c[k];
+        }
+    }
+}
+
+// The sums over origins and atoms, one lane per LAG.  A block takes a tile of VMD_MSD_A atoms, a span of VMD_MSD_SO origin frames and a chunk
+// of VMD_MSD_LC lags (its threads), and stages what they touch into LDS laid out [atom][axis][frame]: the origins' frames [s0, s0 + SO) and
+// the targets' frames [s0 + l0, s0 + l0 + SO + LC - 1) - positions, image counts and, once per frame, the cell's edges.  Lane `tid` holds lag
+// l0 + tid: for origin s0 + i its target sits at entry i + tid of the target rows, so the 64 lanes of a wave read 64 consecutive words (no
+// bank conflict) and the origin's own values are one word for all of them (a broadcast).  The displacement is formed as DESIGN 1.18 states it,
+// every operation rounded on its own (this file is compiled without contraction), and every term is an integer before it is summed: the
+// sums do not depend on the order of lanes, blocks or atomics.  A block walks the atom tiles blockIdx.x, blockIdx.x + gridDim.x, ... with its
+// four u64 sums in registers and ends with four 64-bit atomics per lag.  A lane whose lag lies beyond max_lag, an origin off the stride or
+// beyond the window and a target beyond the window do nothing.
+#define VMD_MSD_A 8
+#define VMD_MSD_SO 32
+#define VMD_MSD_LC 256
+#define VMD_MSD_FT (VMD_MSD_SO + VMD_MSD_LC - 1)
+struct vmd_msd_lags_params_t {
+    const float* rows; const int* counts;      // the window's rows of the table, its image counts
+    int F; int n; int max_lag; int stride;
+    unsigned long long* sums;                   // [max_lag + 1][4]
+};
+__global__ __launch_bounds__(VMD_MSD_LC) void k_msd_lags(vmd_msd_lags_params_t p) {
+    __shared__ float s_ox[VMD_MSD_A][3][VMD_MSD_SO];
+    __shared__ int s_on[VMD_MSD_A][3][VMD_MSD_SO];
+    __shared__ float s_tx[VMD_MSD_A][3][VMD_MSD_FT];
+    __shared__ int s_tn[VMD_MSD_A][3][VMD_MSD_FT];
+    __shared__ float s_L[3][VMD_MSD_FT];
+    const int tid = threadIdx.x;
+    const int s0 = (int)blockIdx.y * VMD_MSD_SO, l0 = (int)blockIdx.z * VMD_MSD_LC;
+    const int t0 = s0 + l0;                                     // the first target frame
+    if (t0 >= p.F) return;                                      // (the whole block: no origin of the span has a target in the window)
+    const int lag = l0 + tid;
+    const size_t w = 3 * (size_t)p.n + VMD_BOX_STRIDE, cw = 3 * (size_t)p.n;
+    const int no = p.F - s0 < VMD_MSD_SO ? p.F - s0 : VMD_MSD_SO, nt = p.F - t0 < VMD_MSD_FT ? p.F - t0 : VMD_MSD_FT;
+    for (int j = tid; j < 3 * VMD_MSD_FT; j += VMD_MSD_LC) {
+        const int k = j / VMD_MSD_FT, f = j - k * VMD_MSD_FT;
+        s_L[k][f] = f < nt ? p.rows[(size_t)(t0 + f) * w + 3 * (size_t)p.n + k] : 0.0f;
+    }
+    // the origins of the span this lane has a term for: on the stride, and with the target inside the window
+    const int ntiles = (p.n + VMD_MSD_A - 1) / VMD_MSD_A;
+    unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int a0 = tile * VMD_MSD_A, na = p.n - a0 < VMD_MSD_A ? p.n - a0 : VMD_MSD_A;
+        __syncthreads();                                        // the previous tile has been read (and s_L written)
+        for (int j = tid; j < VMD_MSD_A * 3 * VMD_MSD_SO; j += VMD_MSD_LC) {
+            const int a = j % VMD_MSD_A, r = j / VMD_MSD_A, k = r % 3, f = r / 3;
+            const bool in = a < na && f < no;
+            s_ox[a][k][f] = in ? p.rows[(size_t)(s0 + f) * w + (size_t)k * p.n + (size_t)(a0 + a)] : 0.0f;
+            s_on[a][k][f] = in ? p.counts[(size_t)(s0 + f) * cw + (size_t)k * p.n + (size_t)(a0 + a)] : 0;
+        }
+        for (int j = tid; j < VMD_MSD_A * 3 * VMD_MSD_FT; j += VMD_MSD_LC) {
+            const int a = j % VMD_MSD_A, r = j / VMD_MSD_A, k = r % 3, f = r / 3;
+            const bool in = a < na && f < nt;
+            s_tx[a][k][f] = in ? p.rows[(size_t)(t0 + f) * w + (size_t)k * p.n + (size_t)(a0 + a)] : 0.0f;
+            s_tn[a][k][f] = in ? p.counts[(size_t)(t0 + f) * cw + (size_t)k * p.n + (size_t)(a0 + a)] : 0;
+        }
+        __syncthreads();
+        if (lag > p.max_lag) continue;                          // (it still meets the barriers above)
+        for (int i = 0; i < no; ++i) {
+            const int t = s0 + i;
+            if (t % p.stride != 0 || t + lag >= p.F) continue;
+            const int f = i + tid;                              // < FT, and < nt: t0 + f = t + lag < F
+            const float Lx = s_L[0][f], Ly = s_L[1][f], Lz = s_L[2][f];
+            auto term = [&](int a) {
+                const float dx = (s_tx[a][0][f] - s_ox[a][0][i]) + (float)(s_tn[a][0][f] - s_on[a][0][i]) * Lx;
+                const float dy = (s_tx[a][1][f] - s_ox[a][1][i]) + (float)(s_tn[a][1][f] - s_on[a][1][i]) * Ly;
+                const float dz = (s_tx[a][2][f] - s_ox[a][2][i]) + (float)(s_tn[a][2][f] - s_on[a][2][i]) * Lz;
+                acc[0] += (unsigned long long)((dx * dx) * 1048576.0f);
+                acc[1] += (unsigned long long)((dy * dy) * 1048576.0f);
+                acc[2] += (unsigned long long)((dz * dz) * 1048576.0f);
+            };
+            if (na == VMD_MSD_A) {                              // a whole tile: unrolled, its reads in flight together
+#pragma unroll
+                for (int a = 0; a < VMD_MSD_A; ++a) term(a);
+            } else for (int a = 0; a < na; ++a) term(a);
+            acc[3] += (unsigned long long)na;
+        }
+    }
+    if (lag > p.max_lag || !acc[3]) return;
+    for (int k = 0; k < 4; ++k) atomicAdd(&p.sums[4 * (size_t)lag + k], acc[k]);
+}
+
 // ------------------------------------------------------------------------------------------------ misc
 
 __global__ __launch_bounds__(256) void k_counts_to_float(const uint64_t* __restrict__ counts, size_t n, float* __restrict__ values,
@@ -5913,6 +6052,48 @@ extern "C" int vmd_hip_cluster_finish(void* stream, const uint32_t* parent, uint
     else hipLaunchKernelGGL(k_cluster_finish_count<false>, grid, dim3(256), 0, s, q);
     VMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cluster_finish_out, dim3((B + 255) / 256), dim3(256), 0, s, q);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- K16: the position table's rows of a batch, and the two launches of a query
+extern "C" int vmd_hip_msd_gather(void* stream, const float* xyz, size_t frame_stride, size_t row_stride, const float* boxes,
+                                  uint32_t pbc_flags, int B, const int32_t* idx, int n, float* rows) {
+    if (B <= 0) return 0;
+    if (B > 65535 || !xyz || !boxes || !idx || !rows || n < 1 || n > VMD_MSD_MAX_ATOMS) return (int)hipErrorInvalidValue;
+    vmd_msd_gather_params_t p{vmd_frames(xyz, frame_stride, row_stride, boxes, pbc_flags, B), idx, n, rows};
+    hipLaunchKernelGGL(k_msd_gather, dim3((unsigned)((3 * n + VMD_BOX_STRIDE + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_msd_unwrap(void* stream, const float* rows, int F, int n, int32_t* counts) {
+    if (F <= 0) return 0;
+    if (!rows || !counts || n < 1 || n > VMD_MSD_MAX_ATOMS) return (int)hipErrorInvalidValue;
+    vmd_msd_unwrap_params_t p{rows, F, n, counts};
+    hipLaunchKernelGGL(k_msd_unwrap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    VMD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vmd_hip_msd_tile(int* atoms, int* origins, int* lags) {
+    if (atoms) *atoms = VMD_MSD_A;
+    if (origins) *origins = VMD_MSD_SO;
+    if (lags) *lags = VMD_MSD_LC;
+    return 0;
+}
+
+extern "C" int vmd_hip_msd_lags(void* stream, const float* rows, const int32_t* counts, int F, int n, int max_lag, int origin_stride,
+                                uint64_t* sums) {
+    if (F <= 0) return 0;
+    const long long spans = ((long long)F + VMD_MSD_SO - 1) / VMD_MSD_SO, chunks = (long long)max_lag / VMD_MSD_LC + 1;
+    if (!rows || !counts || !sums || n < 1 || n > VMD_MSD_MAX_ATOMS || max_lag < 0 || max_lag >= F || origin_stride < 1 || spans > 65535 ||
+        chunks > 65535) return (int)hipErrorInvalidValue;
+    // enough blocks to fill the device several times over, few enough that the atomics of a lag row stay a small part of its terms
+    const long long tiles = ((long long)n + VMD_MSD_A - 1) / VMD_MSD_A;
+    const long long gx = std::min(tiles, std::max(1LL, 8192LL / (spans * chunks)));
+    vmd_msd_lags_params_t p{rows, counts, F, n, max_lag, origin_stride, (unsigned long long*)sums};
+    hipLaunchKernelGGL(k_msd_lags, dim3((unsigned)gx, (unsigned)spans, (unsigned)chunks), dim3(VMD_MSD_LC), 0, (hipStream_t)stream, p);
     VMD_LAUNCH_CHECK();
     return 0;
 }

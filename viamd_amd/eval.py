@@ -314,6 +314,12 @@ class ScriptIR:
         sites = L.ContactSitesC(a_.size, ap, gp, G, 0, None)
         self._check(self.lib.vmd_ir_add_clusters(self.h, (C.c_char_p * 3)(*[x.encode() for x in names]), C.byref(sites), float(r_cut)))
 
+    def add_msd(self, name, atoms):
+        """The position table of `atoms`: one TEMPORAL property of 3 n + 9 floats per frame - x, y, z of the atoms as the
+        frame holds them, then the frame's cell -, kept on the device for the whole trajectory; ScriptEval.msd correlates it."""
+        a_, ap = _idx(atoms)
+        self._check(self.lib.vmd_ir_add_msd(self.h, name.encode(), ap, a_.size))
+
     def add_within_count(self, name, target, ref, rmin, rmax):
         """`name = count(target and within(rmin:rmax, ref));`: per frame, how many atoms of `target` have some atom of `ref`
         (itself included) at rmin <= d < rmax."""
@@ -502,6 +508,11 @@ class PropertyDataView:
         return self._arr(self.c.counts, self.c.dim[0], np.uint64)
 
     @property
+    def msd_table(self):
+        """the position table of an msd statement as float32 [frames, 3 n + 9]: x[n], y[n], z[n], then the cell's nine"""
+        return self.values.reshape(self.c.dim[0], self.c.dim[1])
+
+    @property
     def ss_classes(self):
         """the class table of a secondary_structure statement as uint8 [frames, nseg]: the VMD_SS_* codes, 0 = a frame that
         was not evaluated (a copy: the float rows hold the codes exactly)"""
@@ -545,6 +556,27 @@ class PropertyDataView:
         return {"mean": own(np.ctypeslib.as_array(a.population_mean, shape=(n,))),
                 "var": own(np.ctypeslib.as_array(a.population_var, shape=(n,))),
                 "ext": own(np.ctypeslib.as_array(a.population_ext, shape=(n * 2,))).reshape(n, 2)}
+
+
+class MsdResult(tuple):
+    """(msd, per_axis, terms) of ScriptEval.msd, with the raw sums (.sums) and the window's frames (.frames_used)"""
+    sums = None
+    frames_used = 0
+
+
+def diffusion_coefficient(msd, dt_ps, lo=0.2, hi=0.8, dims=3):
+    """The diffusion coefficient read off an MSD curve: the least-squares slope of msd over the lags tau with
+    lo * T <= tau <= hi * T, T = len(msd) - 1 the largest lag, divided by 2 dims (Einstein) -> in msd's unit per ps (A^2 / ps; x 1e-4
+    for cm^2 / s).  dt_ps: the time between two frames.  Plain NumPy; needs at least two lags in the range."""
+    y = np.asarray(msd, np.float64).reshape(-1)
+    T = y.size - 1
+    k = np.arange(y.size)
+    sel = (k >= lo * T) & (k <= hi * T)
+    if sel.sum() < 2:
+        raise ValueError("diffusion_coefficient: fewer than two lags in the fit range")
+    t = k[sel] * float(dt_ps)
+    tc, yc = t - t.mean(), y[sel] - y[sel].mean()
+    return float((tc * yc).sum() / (tc * tc).sum()) / (2.0 * dims)
 
 
 class ScriptEval:
@@ -710,6 +742,27 @@ class ScriptEval:
                                               sums.ctypes.data_as(L.c_uint64_p)):
             raise VmdError(self.lib.last_error())
         return values, sums
+
+    def msd(self, name, beg=0, end=None, max_lag=None, stride=1):
+        """Mean-squared displacement over lag times of the position table `name` over the evaluated frames [beg, end), origins
+        every `stride` frames, lags 0 .. max_lag (None: the whole window) -> MsdResult (msd float64 [max_lag + 1], per_axis float64
+        [max_lag + 1, 3], terms float64 [max_lag + 1]) in square Angstrom; its .sums holds the raw uint64 [max_lag + 1, 4] (2^-20 A^2 quanta
+        along x, y, z and the number of terms), its .frames_used the frames of the window."""
+        end = self.num_frames() if end is None else int(end)
+        max_lag = max(end - int(beg) - 1, 0) if max_lag is None else int(max_lag)
+        for v in (beg, end, max_lag, stride):
+            if not 0 <= int(v) <= 0xffffffff:
+                raise ValueError("msd arguments must be frame numbers")
+        sums = np.zeros((max_lag + 1, 4), np.uint64)
+        used = C.c_uint32(0)
+        if not self.lib.vmd_eval_msd(self.h, name.encode(), int(beg), end, max_lag, int(stride), sums.ctypes.data_as(L.c_uint64_p),
+                                     C.byref(used)):
+            raise VmdError(self.lib.last_error())
+        terms = sums[:, 3].astype(np.float64)
+        per_axis = np.divide(sums[:, :3].astype(np.float64), 1048576.0 * terms[:, None], out=np.zeros((max_lag + 1, 3)), where=terms[:, None] > 0)
+        out = MsdResult((per_axis.sum(axis=1), per_axis, terms))
+        out.sums, out.frames_used = sums, int(used.value)
+        return out
 
     def rmsf(self, name):
         """an rmsf property read from its record as it stands -> (rmsf float64 [ntot], mean_dev float64 [ntot, 3], frames)"""
