@@ -350,124 +350,16 @@ def test_decoder_checkpoints_survive_in_a_sidecar_file_on_the_gpu(tmp_path, gpu_
 
 
 def _device_decode(lib, blob, natoms, chunk=0, gpu=False):
-    """Run vmd_hip_xtc_decode (emulator build: "device" memory is host memory) on every frame of an XTC byte string."""
-    import ctypes as C
-    from viamd_amd import _lib as L
-    # chunk -3 / -4: k_xtc_wave (-1) / with checkpoints (-2) on the streams WHERE THE FILE HAS THEM (what the evaluator DMAs out of the
-    # mapped file): 4-byte aligned starts of both phases modulo 8, the next frame's header as the readable bytes behind a stream
-    # chunk -5 / -6: like -2 / -4 with GROUP RECORDS next to the checkpoints - the second pass places every group from them (k_xtc_records)
-    with_rec = chunk in (-5, -6)
-    if with_rec:
-        chunk += 3
-    file_layout = chunk in (-3, -4)
-    if file_layout:
-        chunk += 2
-    off, infos, streams, starts = 0, [], [], []
-    while off < len(blob):
-        n = struct.unpack_from(">i", blob, off + 4)[0]
-        precision, = struct.unpack_from(">f", blob, off + 56)
-        mm = struct.unpack_from(">7i", blob, off + 60)
-        nbytes, = struct.unpack_from(">i", blob, off + 88)
-        streams.append(blob[off + 92: off + 92 + nbytes])
-        starts.append(off + 92)
-        infos.append((precision, mm[0:3], mm[3:6], mm[6], nbytes))
-        off += 92 + ((nbytes + 3) & ~3)
-        assert n == natoms
-    B = len(infos)
-    raw = bytearray()
-    arr = (L.XtcFrame * B)()
-    for b, (precision, mi, ma, sidx, nbytes) in enumerate(infos):
-        arr[b].precision = precision
-        arr[b].minint[:] = mi
-        arr[b].maxint[:] = ma
-        arr[b].smallidx = sidx
-        arr[b].offset = 8 + starts[b] if file_layout else len(raw)
-        arr[b].nbytes = nbytes
-        if not file_layout:
-            raw += streams[b] + b"\0" * ((-len(streams[b])) % 64 + 64)
-    if file_layout:
-        raw = bytearray(b"\xa5" * 8 + blob + b"\xa5" * 64)
-        assert len({int(a.offset) % 8 for a in arr}) == 2 or B < 4, "fixture without both phases"
-    npad = (natoms + 63) & ~63
-    if gpu:                    # the product library on a real GPU: torch owns the device memory (hipMalloc: 256-byte aligned)
-        import torch
-        d_raw = torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
-        d_info = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
-        d_out = torch.full((B, 3, npad), float("nan"), dtype=torch.float32, device="cuda")
-        d_status = torch.full((B,), 99, dtype=torch.int32, device="cuda")
-        raw_p, info_p, out_p, status_p = d_raw.data_ptr(), d_info.data_ptr(), d_out.data_ptr(), d_status.data_ptr()
-        if chunk > 0:
-            d_scratch = torch.zeros(lib.vmd_hip_xtc_scratch_bytes(B, natoms, chunk) // 8 + 1, dtype=torch.int64, device="cuda")
-            scratch_p = d_scratch.data_ptr()
-        torch.cuda.synchronize()
-    else:
-        # 64-byte alignment of the stream starts: copy into an aligned numpy buffer
-        store = np.zeros(len(raw) + 64, np.uint8)
-        base = (-store.ctypes.data) % 64
-        store[base:base + len(raw)] = np.frombuffer(raw, np.uint8)
-        out = np.full((B, 3, npad), np.nan, np.float32)
-        status = np.full(B, 99, np.uint32)
-        raw_p, info_p, out_p, status_p = store.ctypes.data + base, C.addressof(arr), out.ctypes.data, status.ctypes.data
-        if chunk > 0:
-            scratch = np.zeros(lib.vmd_hip_xtc_scratch_bytes(B, natoms, chunk) // 8 + 1, np.uint64)
-            scratch_p = scratch.ctypes.data
-    if chunk == -2:            # k_xtc_wave twice: the first pass leaves checkpoints, the second decodes the frames in sections from them
-        CK = 64                # VMD_XTC_CK_MAX (include/vmd_hip.h)
-        if gpu:
-            d_ck = torch.zeros(B * CK * 4, dtype=torch.int32, device="cuda")
-            d_nck = torch.zeros(B, dtype=torch.int32, device="cuda")
-            ck_p, nck_p = d_ck.data_ptr(), d_nck.data_ptr()
-        else:
-            ck = np.zeros(B * CK * 4, np.uint32)
-            nck = np.zeros(B, np.uint32)
-            ck_p, nck_p = ck.ctypes.data, nck.ctypes.data
-        stride = npad
-        if with_rec:
-            if gpu:
-                d_rec = torch.zeros(B * stride, dtype=torch.int16, device="cuda")
-                d_nrec = torch.zeros(B, dtype=torch.int32, device="cuda")
-                rec_p, nrec_p = d_rec.data_ptr(), d_nrec.data_ptr()
-            else:
-                rec = np.zeros(B * stride, np.uint16)
-                nrec = np.zeros(B, np.uint32)
-                rec_p, nrec_p = rec.ctypes.data, nrec.ctypes.data
-            two_pass = lambda use: lib.vmd_hip_xtc_decode_wave_rec(None, raw_p, info_p, B, natoms, out_p, 3 * npad, npad, status_p, use, ck_p, nck_p, rec_p, nrec_p, stride)
-        else:
-            two_pass = lambda use: lib.vmd_hip_xtc_decode_wave_ck(None, raw_p, info_p, B, natoms, out_p, 3 * npad, npad, status_p, use, ck_p, nck_p)
-        rc = two_pass(0)
-        assert rc == 0
-        if gpu:
-            torch.cuda.synchronize()
-            first, st1 = d_out.cpu().numpy().copy(), d_status.cpu().numpy().copy()
-            d_out.fill_(float("nan"))
-            counts = d_nck.cpu().numpy()
-        else:
-            first, st1 = out.copy(), status.copy()
-            out[:] = np.nan
-            counts = nck
-        if (st1 == 0).all():
-            assert (counts >= 1).all() and (counts <= CK).all(), counts
-            if with_rec:
-                ng = d_nrec.cpu().numpy() if gpu else nrec
-                assert (ng >= 1).all() and (ng <= natoms).all(), ng                  # every frame got its records: one per group
-            rc = two_pass(1)
-            if gpu:
-                torch.cuda.synchronize()
-                second = d_out.cpu().numpy()
-            else:
-                second = out
-            np.testing.assert_array_equal(second[:, :, :natoms], first[:, :, :natoms])      # sections == one walk, bit for bit
-    elif chunk == -1:          # one wave per frame (k_xtc_wave)
-        rc = lib.vmd_hip_xtc_decode_wave(None, raw_p, info_p, B, natoms, out_p, 3 * npad, npad, status_p)
-    elif chunk:                # two passes: index (one thread per frame) + chunks (one thread per chunk)
-        rc = lib.vmd_hip_xtc_decode_chunked(None, raw_p, info_p, B, natoms, out_p, 3 * npad, npad, status_p, chunk, scratch_p)
-    else:
-        rc = lib.vmd_hip_xtc_decode(None, raw_p, info_p, B, natoms, out_p, 3 * npad, npad, status_p)
-    if gpu:
-        torch.cuda.synchronize()
-        out, status = d_out.cpu().numpy(), d_status.cpu().numpy().astype(np.uint32)
-    assert rc == 0, f"launch of the device decoder (chunk {chunk}) returned {rc}"
-    return out[:, :, :natoms], status
+    """Run vmd_hip_xtc_decode (emulator build: "device" memory is host memory) on every frame of an XTC byte string.
+    chunk 0: k_xtc_decode; > 0: k_xtc_index + k_xtc_chunks; -1: k_xtc_wave; -2: k_xtc_wave twice, checkpoints out, then sections from them;
+    -3 / -4: -1 / -2 on the streams WHERE THE FILE HAS THEM (what the evaluator DMAs out of the mapped file): 4-byte aligned starts of both
+    phases modulo 8, the next frame's header as the readable bytes behind a stream; -5 / -6: like -2 / -4 with GROUP RECORDS next to the
+    checkpoints - the second pass places every group from them (k_xtc_records).
+    The launches run inside the guards of tests/xtc_device_cases.py: a larger frame_stride and a frame's worth of room behind the output, the
+    status words and every table, prefilled, and checked after every launch - the damaged streams below included."""
+    import xtc_device_cases
+    r = xtc_device_cases.guarded_decode(lib, blob, natoms, chunk, gpu)
+    return r.out, r.status.astype(np.uint32)
 
 
 def _device_decoder_against_host_reader(tmp_path, lib, chunk, gpu, trials=25):
@@ -608,7 +500,8 @@ def test_xtc_batches_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracle):
     p = tmp_path / "m.xtc"
     V.write_xtc(p, coords, cell, lib=emu_lib)
     o = cases.oxygen(N)
-    ir = V.ScriptIR(emu_lib); ir.add_rdf("g", o, o, 8.0)
+    import xtc_device_cases as X
+    ir = V.ScriptIR(emu_lib); ir.add_rdf("g", o, o, 8.0); X.add_every_atom(ir, N)
     sysm = V.MolSystem(N, unitcell=cell)
     old_b = emu_lib.vmd_set_option(b"batch_frames", 4)
     old_d = emu_lib.vmd_set_option(b"xtc_device_decode", 0)
@@ -616,6 +509,7 @@ def test_xtc_batches_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracle):
         ev = V.ScriptEval(F, ir)
         assert ev.frame_range(sysm, V.XdrTrajectory(p, lib=emu_lib), 0, F)
         want = ev.property_data("g").counts.copy()
+        rows_host = X.every_atom_rows(ev, N)            # distance_pair(anchors, every atom) of the host-decoded frames: every route below must match
         assert want.sum() > 0 and ev.frames_mapped() == 0
         emu_lib.vmd_set_option(b"xtc_device_decode", 3)
         xt = V.XdrTrajectory(p, lib=emu_lib)
@@ -623,6 +517,7 @@ def test_xtc_batches_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracle):
             ev = V.ScriptEval(F, ir)
             assert ev.frame_range(sysm, xt, 0, 3) and ev.frame_range(sysm, xt, 3, F)
             np.testing.assert_array_equal(ev.property_data("g").counts, want)
+            np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows_host, err_msg=f"mapped, pass {rep}")
             assert ev.frames_device_decoded() == F and ev.frames_mapped() == F
             assert ev.frames_section_decoded() == (F if rep else 0)
         old_m = emu_lib.vmd_set_option(b"xtc_mapped", 0)
@@ -630,6 +525,7 @@ def test_xtc_batches_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracle):
             ev = V.ScriptEval(F, ir)
             assert ev.frame_range(sysm, xt, 0, F)
             np.testing.assert_array_equal(ev.property_data("g").counts, want)
+            np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows_host, err_msg="copy")
             assert ev.frames_device_decoded() == F and ev.frames_mapped() == 0
         finally:
             emu_lib.vmd_set_option(b"xtc_mapped", old_m)
@@ -672,7 +568,8 @@ def test_plain_float_files_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracl
     coords = cases.water_box(oracle, 41, N, box, F)
     cell = V.make_unitcell(box)
     o = cases.oxygen(N)
-    ir = V.ScriptIR(emu_lib); ir.add_rdf("g", o, o, 8.0)
+    import xtc_device_cases as X
+    ir = V.ScriptIR(emu_lib); ir.add_rdf("g", o, o, 8.0); X.add_every_atom(ir, N)
     sysm = V.MolSystem(N, unitcell=cell)
     files = {}
     q = tmp_path / "f.trr"; V.write_trr(q, coords, cell, lib=emu_lib); files["trr"] = lambda: V.XdrTrajectory(q, lib=emu_lib)
@@ -688,6 +585,7 @@ def test_plain_float_files_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracl
                 ev = V.ScriptEval(F, ir)
                 assert ev.frame_range(sysm, opener(), 0, F)
                 want = ev.property_data("g").counts.copy()
+                rows_host = X.every_atom_rows(ev, N)
                 assert want.sum() > 0 and ev.frames_mapped() == 0 and ev.frames_device_decoded() == 0
             finally:
                 emu_lib.vmd_set_option(b"raw_f32_device", old)
@@ -695,6 +593,7 @@ def test_plain_float_files_leave_the_mapped_file_by_dma(tmp_path, emu_lib, oracl
             ev = V.ScriptEval(F, ir)
             assert ev.frame_range(sysm, t, 0, 2) and ev.frame_range(sysm, t, 2, F)
             np.testing.assert_array_equal(ev.property_data("g").counts, want, err_msg=tag)
+            np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows_host, err_msg=f"{tag}: every atom, k_raw_f32 against the host reader")
             assert ev.frames_mapped() == F and ev.frames_device_decoded() == F, tag
             os.environ["VIAMD_EMU_NO_HOST_REGISTER"] = "1"        # the mapping cannot be pinned: load_frame on host threads
             try:

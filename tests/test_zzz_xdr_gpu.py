@@ -6,13 +6,14 @@ import pytest
 
 import cases
 import viamd_amd as V
+import xtc_device_cases as X
 
 
 def _xdr_through_the_evaluator(lib, oracle, tmp_path, box, F, N, device_check):
     coords = cases.water_box(oracle, 31, N, box, F)
     cell = V.make_unitcell(box)
     o = cases.oxygen(N)
-    ir = V.ScriptIR(lib); ir.add_rdf("g", o, o, 9.0)
+    ir = V.ScriptIR(lib); ir.add_rdf("g", o, o, 9.0); X.add_every_atom(ir, N)
     sysm = V.MolSystem(N, unitcell=cell)
     res = {}
     for fmt, write in (("xtc", V.write_xtc), ("trr", V.write_trr)):
@@ -21,6 +22,16 @@ def _xdr_through_the_evaluator(lib, oracle, tmp_path, box, F, N, device_check):
         t = V.XdrTrajectory(p, lib=lib)
         decoded = np.stack([t.load_frame(f)[0] for f in range(F)])
         assert abs(decoded - coords).max() < (0.0051 if fmt == "xtc" else 1e-4)
+        # every frame decoded by the host readers: the rows of distance_pair(anchors, every atom) every device route must reproduce bit for bit
+        old_h = [(k, lib.vmd_set_option(k, v)) for k, v in ((b"xtc_device_decode", 0), (b"raw_f32_device", 0), (b"batch_frames", max(4, F // 3)))]
+        try:
+            ev_h = V.ScriptEval(F, ir)
+            assert ev_h.frame_range(sysm, V.XdrTrajectory(p, lib=lib), 0, F)
+        finally:
+            for k, v in old_h:
+                lib.vmd_set_option(k, v)
+        assert ev_h.frames_device_decoded() == 0
+        rows_host = X.every_atom_rows(ev_h, N)
         old = lib.vmd_set_option(b"batch_frames", max(4, F // 3))          # several staged batches, decoded on several threads
         try:
             ev = V.ScriptEval(F, ir)
@@ -28,6 +39,7 @@ def _xdr_through_the_evaluator(lib, oracle, tmp_path, box, F, N, device_check):
         finally:
             lib.vmd_set_option(b"batch_frames", old)
         got = ev.property_data("g").counts.copy()
+        np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows_host, err_msg=f"{fmt}, the default route")
         counts, _ = cases.oracle_rdf(oracle, decoded, oracle.make_cell(box), o, o, 0.0, 9.0)
         np.testing.assert_array_equal(got, counts, err_msg=fmt)            # bit-exact on the coordinates the file holds
         res[fmt] = got
@@ -47,6 +59,7 @@ def _xdr_through_the_evaluator(lib, oracle, tmp_path, box, F, N, device_check):
                     lib.vmd_set_option(b"xtc_device_decode", old_d)
                 assert ev.frames_device_decoded() == F
                 np.testing.assert_array_equal(ev.property_data("g").counts, counts, err_msg=f"xtc, device decode variant {mode}")
+                np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows_host, err_msg=f"xtc, device decode variant {mode}: every atom")
     assert res["xtc"].sum() > 0 and abs(int(res["xtc"].sum()) - int(res["trr"].sum())) < 0.01 * res["trr"].sum()
 
 
@@ -69,9 +82,9 @@ def test_xtc_batches_leave_the_mapped_file_by_dma_on_the_gpu(gpu_lib, oracle, tm
     p = tmp_path / "m.xtc"
     V.write_xtc(p, coords, cell, lib=gpu_lib)
     o = cases.oxygen(N)
-    ir = V.ScriptIR(gpu_lib); ir.add_rdf("g", o, o, 9.0)
+    ir = V.ScriptIR(gpu_lib); ir.add_rdf("g", o, o, 9.0); X.add_every_atom(ir, N)
     sysm = V.MolSystem(N, unitcell=cell)
-    res = {}
+    res, rows = {}, {}
     old_b = gpu_lib.vmd_set_option(b"batch_frames", 16)
     try:
         for name, decode, mapped in (("host", 0, 0), ("copy", 3, 0), ("mapped", 3, 1)):
@@ -87,6 +100,8 @@ def test_xtc_batches_leave_the_mapped_file_by_dma_on_the_gpu(gpu_lib, oracle, tm
                     if decode:
                         assert ev.frames_section_decoded() == (F if rep else 0)
                     np.testing.assert_array_equal(got, res.setdefault(name, got))
+                    # every atom of every frame, the hydrogens and the last one included: host decode first, every device route against it
+                    np.testing.assert_array_equal(X.every_atom_rows(ev, N), rows.setdefault("host", X.every_atom_rows(ev, N)), err_msg=f"{name}, pass {rep}")
             finally:
                 gpu_lib.vmd_set_option(b"xtc_mapped", old_m)
                 gpu_lib.vmd_set_option(b"xtc_device_decode", old_d)
@@ -105,7 +120,7 @@ def test_plain_float_files_leave_the_mapped_file_by_dma_on_the_gpu(gpu_lib, orac
     coords = cases.water_box(oracle, 29, N, box, F)
     cell = V.make_unitcell(box)
     o = cases.oxygen(N)
-    ir = V.ScriptIR(gpu_lib); ir.add_rdf("g", o, o, 9.0)
+    ir = V.ScriptIR(gpu_lib); ir.add_rdf("g", o, o, 9.0); X.add_every_atom(ir, N)
     sysm = V.MolSystem(N, unitcell=cell)
     q = tmp_path / "f.trr"; V.write_trr(q, coords, cell, lib=gpu_lib)
     d1 = tmp_path / "le.dcd"; V.write_dcd(d1, coords, cell)
@@ -114,7 +129,7 @@ def test_plain_float_files_leave_the_mapped_file_by_dma_on_the_gpu(gpu_lib, orac
     old_b = gpu_lib.vmd_set_option(b"batch_frames", 8)
     try:
         for tag, opener in openers.items():
-            res = []
+            res, rows = [], []
             for dev in (0, 1):
                 old = gpu_lib.vmd_set_option(b"raw_f32_device", dev)
                 try:
@@ -122,10 +137,12 @@ def test_plain_float_files_leave_the_mapped_file_by_dma_on_the_gpu(gpu_lib, orac
                     ev = V.ScriptEval(F, ir)
                     assert ev.frame_range(sysm, t, 0, 5) and ev.frame_range(sysm, t, 5, F)
                     res.append(ev.property_data("g").counts.copy())
+                    rows.append(X.every_atom_rows(ev, N))
                     assert ev.frames_mapped() == (F if dev else 0) and ev.frames_device_decoded() == (F if dev else 0), tag
                 finally:
                     gpu_lib.vmd_set_option(b"raw_f32_device", old)
             np.testing.assert_array_equal(res[0], res[1], err_msg=tag)
+            np.testing.assert_array_equal(rows[1], rows[0], err_msg=f"{tag}: every atom, k_raw_f32 against the host reader")
             assert res[0].sum() > 0
     finally:
         gpu_lib.vmd_set_option(b"batch_frames", old_b)

@@ -110,6 +110,10 @@ class XtcFrame(C.Structure):             # vmd_xtc_frame_t (include/vmd_hip.h)
                 ("offset", C.c_uint64), ("nbytes", C.c_uint64)]
 
 
+class F32Frame(C.Structure):             # vmd_f32_frame_t (include/vmd_hip.h)
+    _fields_ = [("offset", C.c_uint64 * 3), ("stride", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float), ("reserved", C.c_uint32)]
+
+
 class TrajectoryI(C.Structure):
     _fields_ = [("inst", C.c_void_p), ("num_frames", NUM_FRAMES_FN), ("num_atoms", NUM_ATOMS_FN),
                 ("load_frame", LOAD_FRAME_FN), ("device_view", DEVICE_VIEW_FN), ("host_view", HOST_VIEW_FN),
